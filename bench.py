@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- input GB/s scanned by the PFAC hot path on N MI355X (BASELINE.json's metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--bytes-per-gpu B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--bytes-per-gpu B] [--dump-outputs DIR]
 
 N > 1 works from a bare command line (the parent spawns one fresh process per GPU before anything touches a GPU) and
 under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` (RANK/LOCAL_RANK/WORLD_SIZE are
@@ -25,6 +25,10 @@ state a long job runs in, not the tail of the ramp.
 Parity, outside the timed region, for EVERY workload timed and on every rank: the GPU's (match count, record checksum) of
 the whole resident shard == one serial Aho-Corasick pass over the bytes copied back from HBM (tests/orc.py: ac_whole_shard),
 plus the records of the first 1 MiB one by one, in order, against the oracle's PFAC walk.
+
+--dump-outputs DIR writes, after the timed steps, what the last of them computed: its match count, the checksum of all its
+records and a seeded sample of the records, as float64 .npy files (dump_outputs, at most 24 MiB).  The inputs are the same
+from run to run, so the files of two builds can be compared one for one.
 
 One JSON line is printed by rank 0 (contract in the task statement) with extra objects:
   roofline         algorithmic bytes (1 B per input byte) / kernel time measured with HIP events on the stream the kernel
@@ -61,6 +65,9 @@ KERNEL_SRC = os.path.join(REPO, "phfpfac_amd", "csrc", "pfac_hip.hip")
 PROFILE = os.path.join(REPO, "profiles", "r3_pmc_per_launch.json")
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 GIB = 1 << 30
+DUMP_RECORDS = 1 << 20         # --dump-outputs: records sampled from the last timed step, over all ranks (24 MiB as float64)
+DUMP_WINDOW = 1 << 14          # ... in windows of this many consecutive records
+DUMP_SEED = 0x44554D50
 
 WORKLOADS = {
     # name: (pattern fixture, input kind, description)
@@ -263,6 +270,36 @@ def committed_traffic():
         return None, "no committed PMC profile"
 
 
+def dump_outputs(out_dir, g, table, slot, n, base, rank, world):
+    """--dump-outputs: what the last timed step computed, as a caller of the scan receives it, as float64 .npy files in
+    `out_dir` (suffix _rank<r> when N > 1): match_count, records_checksum (the order-independent checksum of ALL its
+    records with global positions, low and high 32 bits) and a fixed sample of the records in output order -- windows of
+    DUMP_WINDOW consecutive records, the first and the last always included, the others drawn with DUMP_SEED -- as
+    record_index, record_pos (global start position) and record_pattern_id."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = "" if world == 1 else "_rank%d" % rank
+    chk = g.checksum(n, base=base, slot=slot)
+    idx, pos, pid = [], [], []
+    if n:
+        n_blocks = -(-n // DUMP_WINDOW)
+        want = max(DUMP_RECORDS // world // DUMP_WINDOW, 2)
+        rest = np.arange(1, n_blocks - 1)
+        pick = np.random.default_rng(DUMP_SEED).choice(rest, size=min(want - 2, rest.size), replace=False)
+        for b in np.unique(np.concatenate([[0, n_blocks - 1], pick])):
+            first = int(b) * DUMP_WINDOW
+            rec = g.records_to_host(min(DUMP_WINDOW, n - first), slot=slot, first=first)
+            idx.append(np.arange(first, first + rec.size))
+            pos.append(rec["pos"].astype(np.int64) + base)
+            pid.append(table.idmap[rec["state"]])
+    cat = lambda parts: np.concatenate(parts or [np.empty(0)]).astype(np.float64)      # noqa: E731
+    arrays = {"match_count": np.array([n], dtype=np.float64),
+              "records_checksum": np.array([chk & 0xFFFFFFFF, chk >> 32], dtype=np.float64),
+              "record_index": cat(idx), "record_pos": cat(pos), "record_pattern_id": cat(pid)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + sfx + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -276,7 +313,11 @@ def main():
     ap.add_argument("--sustain-seconds", type=float, default=2.5, help="length of the sustained back-to-back run reported beside the K-step value (0: skip)")
     ap.add_argument("--no-end-to-end", action="store_true", help="skip the PCIe-inclusive config-3 run (4 GiB pinned host -> 4 slots)")
     ap.add_argument("--cpu-threads", type=int, default=-1, help="threads of the all-cores CPU baseline (default: usable cores, at most 32; 0: skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64, see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world == 1 and args.gpus > 1:
@@ -461,6 +502,8 @@ def main():
             cnt_all = int(tot.item())
         else:
             cnt_all = cnt
+        if headline and args.dump_outputs:
+            dump_outputs(args.dump_outputs, g, table, (steps - 1) & 1, cnt, lo, rank, world)
         res = {"name": name, "desc": desc, "ppath": ppath, "kind": kind, "dt": dt, "kernel_ms": float(np.mean(kern_ms)),
                "kernel_ms_min": float(np.min(kern_ms)), "matches": cnt_all, "matches_rank": cnt, "table": table,
                "n_owned": n_owned, "n_avail": n_avail, "settle": settle, "cold_ms": cold_ms, "parity_s": t_par}

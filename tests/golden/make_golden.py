@@ -8,6 +8,7 @@ Outputs: * tests/golden/data/            copies of the small DATA files (pattern
                                          `bytefile_1000000byte` gzip-compressed
          * tests/golden/out/*.txt        small GPU_match_result.txt files, verbatim
          * tests/golden/fingerprints.json  (lines, bytes, md5) of every golden output + table statistics
+         * tests/golden/ref_tables.json  the reference's own tables as digests (ref_tables below)
 
 Every output is produced by oracle/_ref/libpfacref.so = the reference's REAL host sources
 (create_table_reorder.c, phf.c) compiled where they lie, driving the oracle's restatement of the
@@ -40,6 +41,33 @@ CASES = [  # (name, pattern, input, streams, width, keep_verbatim)
     ("b10000_x_b1000000_s1_w256", "bytefile/10000byte", "bytefile/1000000byte", 1, 256, True),
     ("b100000_x_b1000000_s1_w256", "bytefile/100000byte", "bytefile/1000000byte", 1, 256, False),
 ]
+HOST_CODE_CASES = [("experimentpattern", 1, 256), ("xaa", 2, 1024), ("bytefile/10000byte", 1, 4096)]   # (pattern, streams, width)
+
+
+def ref_tables(lib, tmp):
+    """tests/golden/ref_tables.json: what the reference's table code builds, as orc.model_digests -- create_table_reorder
+    + FFDM for HOST_CODE_CASES (tests/test_oracle.py), and its escape-aware reader read_pattern_ext on orc.ESCAPED and
+    on every pattern file of its fuzz (orc.escape_fuzz_images, keyed by the file's sha256)."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    from orc import ESCAPED, bind_model, escape_fuzz_images, model_digests
+    ref = bind_model(C.CDLL(lib))
+    ref.ref_build.restype = C.c_void_p; ref.ref_build.argtypes = [C.c_char_p, C.c_int]
+    ref.ref_ffdm.argtypes = [C.c_void_p, C.c_int]
+    ref.ref_build_single_ext.restype = C.c_void_p; ref.ref_build_single_ext.argtypes = [C.c_char_p]
+    out = {"host_code": {}, "escape_fuzz": []}
+    for pat, streams, width in HOST_CODE_CASES:
+        m = ref.ref_build(os.path.join(REF, pat).encode(), streams)
+        ref.ref_ffdm(m, width)
+        out["host_code"]["%s|%d|%d" % (pat, streams, width)] = model_digests(ref, m, width)
+    pf = os.path.join(tmp, "escaped.pat")
+
+    def ext(img):
+        open(pf, "wb").write(img)
+        m = ref.ref_build_single_ext(pf.encode())
+        return {"image": hashlib.sha256(img).hexdigest(), "n_pat": ref.orc_num_patterns(m), "chunks": model_digests(ref, m)}
+    out["escape_fixed"] = ext(ESCAPED)
+    out["escape_fuzz"] = [ext(img) for img in escape_fuzz_images()]
+    json.dump(out, open(os.path.join(HERE, "ref_tables.json"), "w"), indent=1, sort_keys=True)
 
 
 def main():
@@ -84,6 +112,7 @@ def main():
             shutil.copyfile(opath, os.path.join(out, name + ".txt"))
         print(name, n, fp["cases"][name]["md5"], flush=True)
     json.dump(fp, open(os.path.join(HERE, "fingerprints.json"), "w"), indent=1, sort_keys=True)
+    ref_tables(lib, tmp)
     shutil.rmtree(tmp)
 
 

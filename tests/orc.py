@@ -1,5 +1,6 @@
 """ctypes view of oracle/liboracle.so -- the CHECKER used by the tests (never by the product)."""
 import ctypes as C
+import hashlib
 import os
 
 import numpy as np
@@ -8,26 +9,92 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _L = None
 
 
+def bind_model(L):
+    """Signatures of the orc_* functions that read a built model: liboracle.so and oracle/_ref/libpfacref.so (the
+    reference's host code, tests/golden/make_golden.py) both export them."""
+    vp, i = C.c_void_p, C.c_int
+    for f in ("orc_num_chunks", "orc_num_patterns", "orc_max_len"):
+        getattr(L, f).argtypes = [vp]
+    for f in ("orc_state_num", "orc_final_num", "orc_chunk_max_len"):
+        getattr(L, f).argtypes = [vp, i]
+    L.orc_trie_row.restype = C.POINTER(C.c_int); L.orc_trie_row.argtypes = [vp, i, i]
+    L.orc_idmap.restype = C.POINTER(C.c_int); L.orc_idmap.argtypes = [vp, i]
+    L.orc_phf_stat.argtypes = [vp, i, i]
+    for f in ("orc_phf_r", "orc_phf_HT", "orc_phf_val"):
+        getattr(L, f).restype = C.POINTER(C.c_int); getattr(L, f).argtypes = [vp, i]
+    return L
+
+
+def array_digest(a):
+    """sha256 of an int32 array's little-endian bytes: how tests/golden/ref_tables.json pins the reference's arrays."""
+    return hashlib.sha256(np.ascontiguousarray(a, dtype="<i4").tobytes()).hexdigest()
+
+
+def model_digests(L, m, width=None):
+    """Per pattern chunk of model `m` (read through `L`, see bind_model): state and final counts and the digests of
+    the dense trie and the id map; with the `width` FFDM ran at also the hash table size and the digests of HT / val
+    and of r over the S*256/width+1 rows of the kernel's r table (master_kernel.cu:212) -- rows past the model's own r
+    array are -1, as FFDM leaves every row it does not shift (phf.c:67)."""
+    out = []
+    for c in range(L.orc_num_chunks(m)):
+        S, nf = L.orc_state_num(m, c), L.orc_final_num(m, c)
+        trie = np.stack([np.ctypeslib.as_array(L.orc_trie_row(m, c, s), (256,)) for s in range(S)])
+        d = {"state_num": S, "final_num": nf, "trie": array_digest(trie),
+             "idmap": array_digest(np.ctypeslib.as_array(L.orc_idmap(m, c), (nf,)) if nf else np.empty(0))}
+        if width:
+            mr, hs = L.orc_phf_stat(m, c, 3), L.orc_phf_stat(m, c, 4)
+            r = np.full(S * 256 // width + 1, -1, dtype=np.int32)
+            assert mr <= r.size, (c, mr, r.size)
+            r[:mr] = np.ctypeslib.as_array(L.orc_phf_r(m, c), (mr,))
+            d.update({"ht_size": hs, "r": array_digest(r)})
+            for f in ("HT", "val"):
+                d[f] = array_digest(np.ctypeslib.as_array(getattr(L, "orc_phf_" + f)(m, c), (hs,)) if hs else np.empty(0))
+        out.append(d)
+    return out
+
+
+# a pattern file for the escape-aware readers (tests/test_table.py)
+ESCAPED = (b"tab\\there\n"            # \t
+           b"nl\\nin\\\\side\n"   # \n and \\ inside one pattern
+           b"hex\\x41\\xfe\\x7\n"  # \x41 \xfe \x7
+           b"oct\\101\\7\\377\\0end\n"   # \101 \7 \377 \0
+           b"odd\\8\\q\\'\\\"\n"        # \8 (no octal digit -> byte 0, then '8'), \q (literal backslash), \' \"
+           b"plain\n")
+
+
+def escape_fuzz_images(trials=60, seed=20261004):
+    """The pattern files of tests/test_table.py's escape-reader fuzz: backslashes, digits beyond 7, 'x', signs, "0x"
+    prefixes and white space after "\\x" -- the inputs on which a hand-written parser and libc's scanf disagree."""
+    rng = np.random.default_rng(seed)
+    alphabet = [b"\\", b"\\", b"\\", b"x", b"x", b"0", b"1", b"7", b"8", b"9", b"a", b"f", b"g", b"A", b"F", b"q", b"n", b"t",
+                b" ", b"\t", b"\r", b"+", b"-", b"X", b"'", b"\"", b"3", b"5", b"z", b"\xfe", b"\x00"]
+    images = []
+    for trial in range(trials):
+        lines = []
+        for _ in range(int(rng.integers(1, 12))):
+            k = int(rng.integers(1, 14))
+            line = b"".join(alphabet[int(i)] for i in rng.integers(0, len(alphabet), k))
+            lines.append(line + b"\n")
+        if trial % 5 == 0:
+            lines.insert(0, b"\\x\n41\\x \t7q\\0x41\\x0x41\\+7\\x-f\\x+\n")     # white space / sign / prefix after an escape
+        img = b"".join(lines)
+        if img.endswith(b"\\\n") or img.endswith(b"\\x\n"):            # an escape that swallows the final newline: the
+            img += b"end\n"                                           # reference then reads past EOF and exits
+        images.append(img)
+    return images
+
+
 def lib():
     global _L
     if _L is None:
-        L = C.CDLL(os.path.join(REPO, "oracle", "liboracle.so"))
+        L = bind_model(C.CDLL(os.path.join(REPO, "oracle", "liboracle.so")))
         vp, i = C.c_void_p, C.c_int
         L.orc_build.restype = vp; L.orc_build.argtypes = [C.c_char_p, i, i]
         L.orc_build_ext.restype = vp; L.orc_build_ext.argtypes = [C.c_char_p, i, i]
         L.orc_error.restype = C.c_char_p; L.orc_error.argtypes = [vp]
         L.orc_free.argtypes = [vp]; L.orc_free.restype = None
         L.orc_ffdm.argtypes = [vp, i, i]
-        for f in ("orc_num_chunks", "orc_num_patterns", "orc_max_len"):
-            getattr(L, f).argtypes = [vp]
-        for f in ("orc_state_num", "orc_final_num", "orc_chunk_max_len"):
-            getattr(L, f).argtypes = [vp, i]
-        L.orc_trie_row.restype = C.POINTER(C.c_int); L.orc_trie_row.argtypes = [vp, i, i]
-        L.orc_idmap.restype = C.POINTER(C.c_int); L.orc_idmap.argtypes = [vp, i]
-        L.orc_phf_stat.argtypes = [vp, i, i]
         L.orc_phf_lookup.argtypes = [vp, i, i, i]
-        for f in ("orc_phf_r", "orc_phf_HT", "orc_phf_val"):
-            getattr(L, f).restype = C.POINTER(C.c_int); getattr(L, f).argtypes = [vp, i]
         L.orc_matches_new.restype = vp
         L.orc_matches_free.argtypes = [vp]; L.orc_matches_free.restype = None
         L.orc_matches_count.restype = C.c_int64; L.orc_matches_count.argtypes = [vp]

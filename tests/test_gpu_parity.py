@@ -130,6 +130,36 @@ def test_bench_rank_code_at_the_c4_shard_size(tmp_path):
     assert "gather_ms" in line["config"] and line["value"] > 1000
 
 
+def test_bench_dump_outputs_are_the_last_steps_records(resolve, tmp_path):
+    """`bench.py --dump-outputs DIR`: float64 .npy files of at most 64 MB holding the last timed step's match count, the
+    checksum of all its records and a sample of them -- every sampled record equal to the oracle's at the same index."""
+    import subprocess
+    import sys
+    repo = os.path.dirname(HERE)
+    n = 64 << 20
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--bytes-per-gpu", str(n), "--no-cpu-baseline", "--no-extra", "--no-end-to-end", "--sustain-seconds", "0",
+                        "--dump-outputs", str(out)], cwd=tmp_path, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0
+    files = sorted(os.listdir(out))
+    assert files == ["match_count.npy", "record_index.npy", "record_pattern_id.npy", "record_pos.npy", "records_checksum.npy"]
+    assert sum(os.path.getsize(out / f) for f in files) <= 64 << 20
+    d = {f[:-4]: np.load(out / f) for f in files}
+    assert all(a.dtype == np.float64 for a in d.values())
+    assert d["match_count"][0] == line["config"]["matches_per_step"]
+    pos, ids = oracle_pairs(resolve("experimentpattern"), tiled_bytes(n, open(resolve("paragraph402"), "rb").read()))
+    assert pos.size == line["config"]["matches_per_step"]
+    chk = match_checksum(pos, ids)
+    np.testing.assert_array_equal(d["records_checksum"], [chk & 0xFFFFFFFF, chk >> 32])
+    idx = d["record_index"].astype(np.int64)
+    assert idx.size > 0 and idx[0] == 0 and idx[-1] == pos.size - 1 and (np.diff(idx) > 0).all()
+    np.testing.assert_array_equal(d["record_pos"], pos[idx])
+    np.testing.assert_array_equal(d["record_pattern_id"], ids[idx])
+
+
 @pytest.mark.parametrize("width,env", [(256, {}), (1024, {}), (64, {}), (256, {"PFAC_NO_D1PACK": "1"}),
                                        (4096, {"PFAC_NO_NW4": "1"}), (256, {"PFAC_NO_FUSE": "1"}), (256, {"PFAC_NO_D1": "1"}),
                                        (256, {"PFAC_NO_DENSE2": "1"}), (2048, {"PFAC_NO_DENSE2": "1"}),

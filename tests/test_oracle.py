@@ -3,7 +3,7 @@
   made by tests/golden/make_golden.py through oracle/_ref),
 * against the table statistics and the duplicate rule that the reference's recorded run logs / outputs hold,
 * against an independent algorithm (serial Aho-Corasick with failure links) as a set of (start, id) pairs,
-* and, when oracle/_ref/libpfacref.so is present, array-for-array against the reference-built tables.
+* and array-for-array against the reference-built tables (tests/golden/ref_tables.json, made through oracle/_ref).
 """
 import ctypes as C
 import hashlib
@@ -13,11 +13,11 @@ import os
 import numpy as np
 import pytest
 
-from orc import Oracle, lib, match_checksum
+from orc import Oracle, lib, match_checksum, model_digests
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 FP = json.load(open(os.path.join(HERE, "golden", "fingerprints.json")))
-REF_LIB = os.path.join(os.path.dirname(HERE), "oracle", "_ref", "libpfacref.so")
+REF_TABLES = json.load(open(os.path.join(HERE, "golden", "ref_tables.json")))
 
 
 def test_1m_fixture_regenerates(resolve):
@@ -124,44 +124,16 @@ def test_pfac_equals_serial_aho_corasick_as_a_set(name, resolve):
     o.close()
 
 
-@pytest.mark.skipif(not os.path.exists(REF_LIB), reason="oracle/_ref not built (needs /root/reference)")
 @pytest.mark.parametrize("name,streams,width", [("experimentpattern", 1, 256), ("xaa", 2, 1024), ("bytefile/10000byte", 1, 4096)])
 def test_oracle_equals_reference_host_code(name, streams, width, resolve):
     """Array-for-array: tries, id maps, r / HT / val of the reference's REAL create_table_reorder.c + phf.c
-    (compiled where they lie, oracle/ref_harness.cc) == the oracle's restatement."""
-    ref = C.CDLL(REF_LIB)
-    L = lib()
-    for lb in (ref,):
-        lb.ref_build.restype = C.c_void_p; lb.ref_build.argtypes = [C.c_char_p, C.c_int]
-        lb.ref_ffdm.argtypes = [C.c_void_p, C.c_int]
-        for f in ("orc_num_chunks",):
-            getattr(lb, f).argtypes = [C.c_void_p]
-        for f in ("orc_state_num", "orc_final_num", "orc_chunk_max_len"):
-            getattr(lb, f).argtypes = [C.c_void_p, C.c_int]
-        lb.orc_trie_row.restype = C.POINTER(C.c_int); lb.orc_trie_row.argtypes = [C.c_void_p, C.c_int, C.c_int]
-        lb.orc_idmap.restype = C.POINTER(C.c_int); lb.orc_idmap.argtypes = [C.c_void_p, C.c_int]
-        lb.orc_phf_stat.argtypes = [C.c_void_p, C.c_int, C.c_int]
-        for f in ("orc_phf_r", "orc_phf_HT", "orc_phf_val"):
-            getattr(lb, f).restype = C.POINTER(C.c_int); getattr(lb, f).argtypes = [C.c_void_p, C.c_int]
+    (compiled where they lie, oracle/ref_harness.cc; pinned as sha256 digests per chunk in tests/golden/ref_tables.json
+    by tests/golden/make_golden.py) == the oracle's restatement."""
     o = Oracle(resolve(name), streams, 4)
     o.ffdm(width, exact=True)
-    b = ref.ref_build(os.fsencode(resolve(name)), streams)
-    ref.ref_ffdm(b, width)
-    assert ref.orc_num_chunks(b) == o.P
-    for c in range(o.P):
-        S = L.orc_state_num(o.m, c)
-        assert S == ref.orc_state_num(b, c) and L.orc_final_num(o.m, c) == ref.orc_final_num(b, c)
-        for s in range(S):
-            assert (np.ctypeslib.as_array(L.orc_trie_row(o.m, c, s), (256,)) ==
-                    np.ctypeslib.as_array(ref.orc_trie_row(b, c, s), (256,))).all()
-        nf = L.orc_final_num(o.m, c)
-        if nf:
-            assert (o.idmap(c) == np.ctypeslib.as_array(ref.orc_idmap(b, c), (nf,))).all()
-        hs = L.orc_phf_stat(o.m, c, 4)
-        assert hs == ref.orc_phf_stat(b, c, 4)
-        mr = L.orc_phf_stat(o.m, c, 3)
-        for f in ("orc_phf_HT", "orc_phf_val"):
-            if hs:
-                assert (np.ctypeslib.as_array(getattr(L, f)(o.m, c), (hs,)) == np.ctypeslib.as_array(getattr(ref, f)(b, c), (hs,))).all()
-        assert (np.ctypeslib.as_array(L.orc_phf_r(o.m, c), (mr,)) == np.ctypeslib.as_array(ref.orc_phf_r(b, c), (mr,))).all()
+    got = model_digests(lib(), o.m, width)
     o.close()
+    want = REF_TABLES["host_code"]["%s|%d|%d" % (name, streams, width)]
+    assert len(got) == len(want) == o.P
+    for c, (g, w) in enumerate(zip(got, want)):
+        assert g == w, (c, {k: (g[k], w[k]) for k in w if g[k] != w[k]})

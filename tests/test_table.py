@@ -1,10 +1,16 @@
 """Host-side C table builder (phfpfac_amd/csrc/pfac_table.c through the C-ABI): lookup(state, byte) must equal
 the oracle's dense trie in EVERY cell, for every PHF width; plus the reader's error behaviour and the blob image."""
+import hashlib
+import json
+import os
+
 import numpy as np
 import pytest
 
-from orc import Oracle
+from orc import ESCAPED, Oracle, array_digest, escape_fuzz_images
 from phfpfac_amd import PfacError, PfacTable
+
+REF_TABLES = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_tables.json")))
 
 
 def lookup_all(t):
@@ -146,19 +152,10 @@ def test_parallel_emitter_is_byte_identical(tmp_path):
     assert a.read_bytes() == b.read_bytes()
 
 
-ESCAPED = (b"tab\\there\n"            # \t
-           b"nl\\nin\\\\side\n"   # \n and \\ inside one pattern
-           b"hex\\x41\\xfe\\x7\n"  # \x41 \xfe \x7
-           b"oct\\101\\7\\377\\0end\n"   # \101 \7 \377 \0
-           b"odd\\8\\q\\'\\\"\n"        # \8 (no octal digit -> byte 0, then '8'), \q (literal backslash), \' \"
-           b"plain\n")
-
-
 def test_escape_aware_reader(tmp_path):
     """pfac_table_build_file_escaped == the reference's read_pattern_ext/fgetc_ext (dead code there, restated in the
-    oracle and -- when oracle/_ref is built -- called for real): same tries, same ids, newline bytes inside patterns."""
-    import ctypes as C
-    import os
+    oracle and, through oracle/_ref, called for real: tests/golden/ref_tables.json): same tries, same ids, newline bytes
+    inside patterns."""
     pf = tmp_path / "esc"
     pf.write_bytes(ESCAPED)
     t = PfacTable.from_file(str(pf), 256, escapes=True)
@@ -180,61 +177,30 @@ def test_escape_aware_reader(tmp_path):
         assert t.idmap[s] == pid
     # the plain reader sees the same file as 6 different (longer) patterns
     assert PfacTable.from_file(str(pf), 256).max_pat_len > t.max_pat_len
-    ref_lib = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "libpfacref.so")
-    if os.path.exists(ref_lib):
-        ref = C.CDLL(ref_lib)
-        ref.ref_build_single_ext.restype = C.c_void_p; ref.ref_build_single_ext.argtypes = [C.c_char_p]
-        ref.orc_state_num.argtypes = [C.c_void_p, C.c_int]
-        ref.orc_trie_row.restype = C.POINTER(C.c_int); ref.orc_trie_row.argtypes = [C.c_void_p, C.c_int, C.c_int]
-        ref.orc_idmap.restype = C.POINTER(C.c_int); ref.orc_idmap.argtypes = [C.c_void_p, C.c_int]
-        b = ref.ref_build_single_ext(os.fsencode(str(pf)))
-        assert ref.orc_state_num(b, 0) == dense.shape[0]
-        for st in range(dense.shape[0]):
-            assert (np.ctypeslib.as_array(ref.orc_trie_row(b, 0, st), (256,)) == dense[st]).all()
-        assert (np.ctypeslib.as_array(ref.orc_idmap(b, 0), (6,)) == o.idmap()).all()
+    want = REF_TABLES["escape_fixed"]
+    assert want["image"] == hashlib.sha256(ESCAPED).hexdigest() and want["n_pat"] == 6
+    (w,) = want["chunks"]
+    assert w["state_num"] == dense.shape[0] and w["trie"] == array_digest(dense) and w["idmap"] == array_digest(o.idmap())
     o.close()
 
 
 def test_escape_reader_fuzz_against_the_reference_reader(tmp_path):
     """Differential fuzz of the in-memory escape parser (pfac_table.c: getc_escaped / scan_escape_number) against the
     reference's own read_pattern_ext + fgetc_ext, which scan \\ooo and \\xNN with fscanf on the stream (compiled from
-    the reference sources into oracle/_ref): pattern files full of backslashes, digits beyond 7, 'x', signs, "0x"
-    prefixes and white space after "\\x" -- the inputs on which a hand-written parser and libc's scanf disagree."""
-    import ctypes as C
-    import os
-    ref_lib = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "libpfacref.so")
-    if not os.path.exists(ref_lib):
-        pytest.skip("oracle/_ref not built (needs /root/reference)")
-    ref = C.CDLL(ref_lib)
-    ref.ref_build_single_ext.restype = C.c_void_p; ref.ref_build_single_ext.argtypes = [C.c_char_p]
-    ref.orc_state_num.argtypes = [C.c_void_p, C.c_int]
-    ref.orc_num_patterns.argtypes = [C.c_void_p]
-    ref.orc_trie_row.restype = C.POINTER(C.c_int); ref.orc_trie_row.argtypes = [C.c_void_p, C.c_int, C.c_int]
-    ref.orc_idmap.restype = C.POINTER(C.c_int); ref.orc_idmap.argtypes = [C.c_void_p, C.c_int]
-    rng = np.random.default_rng(20261004)
-    alphabet = [b"\\", b"\\", b"\\", b"x", b"x", b"0", b"1", b"7", b"8", b"9", b"a", b"f", b"g", b"A", b"F", b"q", b"n", b"t",
-                b" ", b"\t", b"\r", b"+", b"-", b"X", b"'", b"\"", b"3", b"5", b"z", b"\xfe", b"\x00"]
-    for trial in range(60):
-        lines = []
-        for _ in range(int(rng.integers(1, 12))):
-            k = int(rng.integers(1, 14))
-            line = b"".join(alphabet[int(i)] for i in rng.integers(0, len(alphabet), k))
-            lines.append(line + b"\n")
-        if trial % 5 == 0:
-            lines.insert(0, b"\\x\n41\\x \t7q\\0x41\\x0x41\\+7\\x-f\\x+\n")     # white space / sign / prefix after an escape
-        img = b"".join(lines)
-        if img.endswith(b"\\\n") or img.endswith(b"\\x\n"):            # an escape that swallows the final newline: the
-            img += b"end\n"                                           # reference then reads past EOF and exits
+    the reference sources into oracle/_ref; its tables pinned as digests in tests/golden/ref_tables.json): pattern files
+    full of backslashes, digits beyond 7, 'x', signs, "0x" prefixes and white space after "\\x" (orc.escape_fuzz_images)
+    -- the inputs on which a hand-written parser and libc's scanf disagree."""
+    images = escape_fuzz_images()
+    assert len(images) == len(REF_TABLES["escape_fuzz"])
+    for trial, (img, want) in enumerate(zip(images, REF_TABLES["escape_fuzz"])):
+        assert want["image"] == hashlib.sha256(img).hexdigest(), trial      # the very pattern file the digests were made from
         pf = tmp_path / f"fz{trial}"
         pf.write_bytes(img)
-        b = ref.ref_build_single_ext(os.fsencode(str(pf)))
-        n_pat = ref.orc_num_patterns(b)
-        S = ref.orc_state_num(b, 0)
+        (w,) = want["chunks"]
         t = PfacTable.from_file(str(pf), 256, escapes=True)
-        assert t.n_patterns == n_pat and t.state_num == S, (trial, img)
-        dense = np.stack([np.ctypeslib.as_array(ref.orc_trie_row(b, 0, st), (256,)) for st in range(S)])
-        assert (lookup_all(t) == dense).all(), (trial, img)
-        assert (np.ctypeslib.as_array(ref.orc_idmap(b, 0), (n_pat,)) == t.idmap).all(), (trial, img)
+        assert t.n_patterns == want["n_pat"] and t.state_num == w["state_num"], (trial, img)
+        assert array_digest(lookup_all(t)) == w["trie"], (trial, img)
+        assert array_digest(t.idmap) == w["idmap"], (trial, img)
 
 
 def test_emit_from_record_heap_and_tile_index(tmp_path):

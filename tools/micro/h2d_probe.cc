@@ -1,4 +1,5 @@
 // GPU box diagnostic (not part of the product): what the host link gives this process.
+//   build: hipcc -O2 -o tools/micro/h2d_probe tools/micro/h2d_probe.cc -lpthread
 //   h2d_probe <file>     pinned H2D rate (one / two streams), the same with 12 threads pread()ing next to it, NUMA facts,
 //                        and whether a page-cache mapping of <file> can be registered for DMA in place (zero-copy ingest)
 #include <hip/hip_runtime.h>

@@ -1,4 +1,5 @@
 // GPU box diagnostic: cost of making page-cache pages DMA-able (populate / register), per 32 MiB piece.
+//   build: hipcc -O2 -o tools/micro/reg_probe tools/micro/reg_probe.cc -lpthread
 #include <hip/hip_runtime.h>
 #include <fcntl.h>
 #include <pthread.h>
