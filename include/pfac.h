@@ -119,6 +119,10 @@ void pfac_outputs_free(pfac_outputs *o);
 
 /* The device lookup evaluated on the host (property tests; never used on the scan path). */
 int32_t pfac_table_lookup(const pfac_table *t, int32_t state, int32_t ch);
+/* len[s] for s in [0, num_final): bytes of the pattern(s) ending in final state s (= its depth in the trie / DFA);
+ * -1 for a final state no input reaches (a duplicate line's own state).  n must be >= num_final.  Computed from the
+ * table alone (any source: files, _part, charclass, from_blob, from_reference_arrays) in O(n_keys + state_num). */
+int pfac_table_final_lengths(const pfac_table *t, int32_t *len, size_t n);
 
 /* Flat int32 image of a table: what gets uploaded, and what RCCL broadcasts
  * between ranks.  Layout: 16-word header {magic, version, width, width_bit,
@@ -298,6 +302,44 @@ int pfac_records_packed_device(pfac_ctx *ctx, int slot, const void *d_records, v
  * the text is not practical.  n = the scan's match count (0: checksum of nothing). */
 int pfac_records_checksum(pfac_ctx *ctx, int slot, const void *d_records, uint64_t n, uint64_t base,
                           uint64_t *checksum);
+
+/* Batches of documents.  One scan covers one contiguous byte range; a batch of independent documents is scanned as
+ * their concatenation and then cut into documents on the device.  Records are keyed by their START offset and a walk
+ * is failureless, so the matches of document [a, b) are exactly the records of the concatenated scan with
+ * a <= pos < b and pos + len(pattern) <= b: the cut drops the records that run across a document end, rebases the
+ * others to their document and builds a per-document index.  The scan itself is unchanged.
+ *
+ * Final-state lengths for the uploaded table (host array, n == num_final, values -1 or 1..1024; see
+ * pfac_table_final_lengths); kept on the device (16-bit) until the next pfac_table_upload / pfac_table_upload_device,
+ * which clears them. */
+int pfac_table_set_final_lengths(pfac_ctx *ctx, const int32_t *len, size_t n);
+/* Document boundaries for a slot: n_docs + 1 offsets, copied into a slot-owned device buffer on the slot's stream
+ * (the host array may be reused when the call returns). */
+int pfac_slot_doc_offsets(pfac_ctx *ctx, int slot, const uint64_t *host_offsets, uint64_t n_docs);
+/* The slot's last finished scan, cut into documents [off[d], off[d+1]):
+ *   d_records      the scan's record heap, NULL = the slot's
+ *   d_doc_offsets  device uint64[n_docs + 1], NULL = the slot's (pfac_slot_doc_offsets, same n_docs).  Required:
+ *                  off[0] == 0, non-decreasing, off[n_docs] == the scan's n_owned; empty documents allowed;
+ *                  n_docs < 2^32.
+ *   keeps a record (pos, state) of document d iff pos + len[state] <= off[d+1]; writes it as {pos - off[d], state}
+ *   to d_out[k] in scan order (= (document, offset, pattern length) order), and d_doc_first[d] = index of document d's
+ *   first kept record, d_doc_first[n_docs] = *n_kept.
+ *   d_out / d_doc_first NULL = slot-owned buffers grown to fit (fetched with pfac_segment_d2h); else device pointers,
+ *   8-B aligned, d_out holding out_cap records and d_doc_first n_docs + 1 entries.
+ * Returns once *n_kept is known; the writes are asynchronous on the slot's stream (pfac_slot_sync completes them).
+ * PFAC_E_OVERFLOW (with *n_kept exact, nothing written) when out_cap is too small for a caller's d_out;
+ * PFAC_E_ARG for offsets that break the rules above (checked on the device, nothing written);
+ * PFAC_E_STATE without a finished scan, for a scan made with an earlier table, or without lengths for the current
+ * table; PFAC_E_OVERFLOW if the scan overflowed.
+ * Three kernels: kept records per tile and per group of 64 tiles (the offsets are checked in the same pass), the
+ * prefix over the groups, and the write; they read the record heap, the tile index, the offsets and the lengths,
+ * never the input bytes. */
+int pfac_records_segment(pfac_ctx *ctx, int slot, const void *d_records, const uint64_t *d_doc_offsets, uint64_t n_docs,
+                         pfac_record *d_out, uint64_t out_cap, uint64_t *d_doc_first, uint64_t *n_kept);
+/* D2H of the slot-owned result of the last pfac_records_segment (host_records: *n_kept records, may be NULL when
+ * d_out was the caller's; host_doc_first: n_docs + 1 entries, may be NULL when d_doc_first was the caller's).
+ * Asynchronous on the slot's stream; pfac_slot_sync completes it. */
+int pfac_segment_d2h(pfac_ctx *ctx, int slot, pfac_record *host_records, uint64_t *host_doc_first);
 
 /* Synthetic input generators, written straight into device memory (the
  * reference built big inputs by tiling a small text, creatbiginput.sh:2-5).

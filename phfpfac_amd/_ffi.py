@@ -74,7 +74,7 @@ HOST_SYMBOLS = (
     "pfac_table_build_mem_part", "pfac_merge_partitions", "pfac_table_free", "pfac_table_lookup",
     "pfac_table_blob_words", "pfac_table_to_blob", "pfac_table_from_blob", "pfac_table_from_reference_arrays",
     "pfac_emit_records", "pfac_emit_records_mt", "pfac_emit_packed", "pfac_table_build_file_charclass",
-    "pfac_table_build_mem_charclass", "pfac_outputs_free", "pfac_emit_records_multi",
+    "pfac_table_build_mem_charclass", "pfac_outputs_free", "pfac_emit_records_multi", "pfac_table_final_lengths",
 )
 HIP_SYMBOLS = (
     "pfac_device_count", "pfac_ctx_create", "pfac_ctx_destroy", "pfac_last_error", "pfac_table_upload",
@@ -84,6 +84,7 @@ HIP_SYMBOLS = (
     "pfac_fill_tiled", "pfac_fill_random", "pfac_scan_info", "pfac_scan_staging", "pfac_trace_table_compat", "pfac_scan_format",
     "pfac_records_expand", "pfac_records_d2h_packed", "pfac_scan_capacity_hint", "pfac_records_packed_device",
     "pfac_emit_text_device", "pfac_text_d2h", "pfac_slot_text", "pfac_slot_h2d_wait", "pfac_slot_h2d_done", "pfac_host_register", "pfac_host_unregister",
+    "pfac_table_set_final_lengths", "pfac_slot_doc_offsets", "pfac_records_segment", "pfac_segment_d2h",
 )
 
 _host = None
@@ -130,6 +131,7 @@ def host_lib() -> C.CDLL:
         L.pfac_outputs_free.restype = None
         L.pfac_emit_records_multi.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, OP]
         L.pfac_emit_records_multi.restype = C.c_int64
+        L.pfac_table_final_lengths.argtypes = [TP, C.c_void_p, C.c_size_t]
         _host = L
     return _host
 
@@ -196,5 +198,9 @@ def hip_lib() -> C.CDLL:
         L.pfac_scan_info.argtypes = [vp, C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i)]
         L.pfac_scan_staging.argtypes = [vp, C.POINTER(i), C.POINTER(C.c_uint32)]
         L.pfac_trace_table_compat.argtypes = [C.POINTER(CThreadData), i]
+        L.pfac_table_set_final_lengths.argtypes = [vp, vp, C.c_size_t]
+        L.pfac_slot_doc_offsets.argtypes = [vp, i, vp, u64]
+        L.pfac_records_segment.argtypes = [vp, i, vp, vp, u64, vp, u64, vp, C.POINTER(u64)]
+        L.pfac_segment_d2h.argtypes = [vp, i, vp, vp]
         _hip = L
     return _hip

@@ -50,6 +50,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <mutex>
 #include <type_traits>
 #include <string>
@@ -2062,6 +2063,198 @@ __global__ void pfac_expand_kernel(const void *rec, const unsigned long long *ti
 }
 
 // ---------------------------------------------------------------------------
+// Documents (pfac_records_segment): the records of a scan over a concatenation of documents, cut at the document ends.
+// A record (pos, state) belongs to document d = the last one with off[d] <= pos, and is kept iff
+// pos + len[state] <= off[d + 1].  Same three-kernel shape as the expand path: kept records per tile and per group of
+// 64 tiles (the offsets are checked in the same pass), pfac_scan_groups_kernel over the group sums, then the write.
+// A tile's documents are found by binary search in the offsets: [ds, de) start in it (the last tile also takes the
+// documents that start at n_owned), and ds - 1 runs into it; a record searches only that small range.
+
+// first d in [0, n) with off[d] >= x (n if none)
+__device__ __forceinline__ unsigned long long doc_lower_bound(const unsigned long long *off, unsigned long long n, unsigned long long x) {
+    unsigned long long lo = 0, hi = n;
+    while (lo < hi) {
+        const unsigned long long mid = (lo + hi) >> 1;
+        if (off[mid] < x) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+// the last d in [lo, hi] with off[d] <= pos (lo when none: off[lo] <= pos holds for valid offsets)
+__device__ __forceinline__ unsigned long long doc_of(const unsigned long long *off, unsigned long long lo, unsigned long long hi, unsigned long long pos) {
+    while (lo < hi) {
+        const unsigned long long mid = (lo + hi + 1) >> 1;
+        if (off[mid] <= pos) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+// documents [*ds, *de) start in tile t; a record of the tile lies in one of [*dlo, *dhi] (clamped to [0, n_docs - 1],
+// so that off[d + 1] stays in bounds while the offsets are still unchecked)
+__device__ __forceinline__ void tile_docs(const unsigned long long *off, unsigned long long n_docs, unsigned long long t,
+                                          unsigned long long n_tiles, unsigned long long &ds, unsigned long long &de,
+                                          unsigned long long &dlo, unsigned long long &dhi) {
+    ds = doc_lower_bound(off, n_docs + 1, t * WTILE);
+    de = t + 1 == n_tiles ? n_docs + 1 : doc_lower_bound(off, n_docs + 1, (t + 1) * WTILE);
+    const unsigned long long top = n_docs - 1;
+    dlo = ds ? ds - 1 : 0;
+    dhi = de ? de - 1 : 0;
+    if (dlo > top) dlo = top;
+    if (dhi > top) dhi = top;
+    if (dhi < dlo) dhi = dlo;
+}
+
+// The documents a record of one tile can lie in, [dlo, dhi]: when off[dlo .. dhi + 1] fit one per lane (a tile holds
+// fewer than 63 document starts -- every document of 64 bytes or more), lane k holds off[dlo + k] and a record finds its
+// document by a binary search over the lanes (shuffles, no memory); else by a binary search in the offsets themselves.
+struct DocWin {
+    unsigned long long dlo, dhi, woff;
+    unsigned n, top;                                           // candidates (dhi - dlo + 1), highest power of two below n
+    bool win;
+};
+__device__ __forceinline__ DocWin doc_window(const unsigned long long *off, unsigned long long dlo, unsigned long long dhi, int lane) {
+    DocWin w;
+    w.dlo = dlo;
+    w.dhi = dhi;
+    w.win = dhi - dlo + 2 <= (unsigned long long)WAVE;
+    w.n = w.win ? (unsigned)(dhi - dlo + 1) : 0u;
+    w.top = w.n > 1 ? 1u << (31 - __clz(w.n - 1)) : 0u;
+    w.woff = w.win && (unsigned)lane <= w.n ? off[dlo + lane] : ~0ull;
+    return w;
+}
+// record at pos -> its document d, off[d], off[d + 1] (every lane takes part: the shuffles)
+__device__ __forceinline__ void doc_lookup(const DocWin &w, const unsigned long long *off, bool have, unsigned pos,
+                                           unsigned long long &d, unsigned long long &base, unsigned long long &end) {
+    if (w.win) {
+        unsigned k = 0;
+        for (unsigned step = w.top; step; step >>= 1) {
+            const unsigned cand = k + step;
+            const unsigned long long v = __shfl(w.woff, cand < w.n ? cand : 0u, WAVE);
+            if (cand < w.n && v <= pos) k = cand;
+        }
+        d = w.dlo + k;
+        base = __shfl(w.woff, k, WAVE);
+        end = __shfl(w.woff, k + 1, WAVE);
+    } else {
+        d = have ? doc_of(off, w.dlo, w.dhi, pos) : w.dlo;
+        base = have ? off[d] : 0ull;
+        end = have ? off[d + 1] : 0ull;
+    }
+}
+// pattern length of final state st: from a register of lane st when the table has at most 64 final states
+__device__ __forceinline__ int final_len(const short *flen, int freg, bool fsmall, bool have, unsigned st) {
+    if (fsmall) return __shfl(freg, (int)st, WAVE);
+    return have ? (int)flen[st] : 0;
+}
+
+template <int BYTES>
+__global__ void pfac_seg_count_kernel(const void *rec, const unsigned long long *tix, unsigned long long n_tiles, unsigned long long cap,
+                                      const unsigned long long *off, unsigned long long n_docs, unsigned long long n_owned,
+                                      const short *flen, unsigned num_final, unsigned *tcnt, unsigned long long *gsum,
+                                      unsigned n_groups, unsigned long long *bad) {
+    // the offsets' rules, one thread per document: a flag, and the host writes nothing behind it
+    const unsigned long long gtid = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const unsigned long long gstride = (unsigned long long)gridDim.x * blockDim.x;
+    for (unsigned long long d = gtid; d < n_docs; d += gstride)
+        if (off[d] > off[d + 1]) *bad = 1ull;
+    if (gtid == 0 && (off[0] != 0ull || off[n_docs] != n_owned)) *bad = 1ull;
+    const int lane = threadIdx.x & (WAVE - 1);
+    const unsigned g = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (g >= n_groups) return;
+    const bool fsmall = num_final <= (unsigned)WAVE;
+    const int freg = fsmall && (unsigned)lane < num_final ? (int)flen[lane] : 0;
+    const unsigned long long t = (unsigned long long)g * XGROUP + lane;
+    const unsigned long long e = t < n_tiles ? tix[t] : 0ull;
+    const unsigned c = (unsigned)(e >> TIX_CNT_SHIFT);
+    const unsigned long long lo = e & TIX_BASE_MASK;
+    unsigned long long ds = 0, de = 0, dlo = 0, dhi = 0;
+    if (c) tile_docs(off, n_docs, t, n_tiles, ds, de, dlo, dhi);
+    unsigned mine = 0;                                          // kept records of tile t
+    for (int j = 0; j < XGROUP; j++) {
+        const unsigned tc = __shfl(c, j, WAVE);
+        if (tc == 0) continue;
+        const unsigned long long tlo = __shfl(lo, j, WAVE);
+        const DocWin w = doc_window(off, __shfl(dlo, j, WAVE), __shfl(dhi, j, WAVE), lane);
+        unsigned kept = 0;
+        for (unsigned c0 = 0; c0 < tc; c0 += WAVE) {
+            const unsigned i = c0 + (unsigned)lane;
+            const bool have = i < tc && tlo + i < cap;
+            unsigned pos = 0, st = 0;
+            if (have) heap_record<BYTES>(rec, tlo + i, (unsigned long long)g * XGROUP + j, pos, st);
+            const int len = final_len(flen, freg, fsmall, have, st);
+            unsigned long long d, base, end;
+            doc_lookup(w, off, have, pos, d, base, end);
+            const bool keep = have && len > 0 && (unsigned long long)pos + (unsigned)len <= end;
+            kept += (unsigned)__popcll(__ballot(keep));
+        }
+        if (lane == j) mine = kept;
+    }
+    if (t < n_tiles) tcnt[t] = mine;
+    const unsigned long long sum = wave_sum64(mine);
+    if (lane == 0) gsum[g] = sum;
+}
+
+// kept records -> out[k] = {pos - off[d], state} at their sorted index k; doc_first[d] for every document that starts
+// in the tile: the index of the first kept record of a document >= d (a document without kept records gets the index
+// of the next one's, the documents behind the last kept record the index past the tile's)
+template <int BYTES>
+__global__ void pfac_seg_write_kernel(const void *rec, const unsigned long long *tix, unsigned long long n_tiles, unsigned long long cap,
+                                      const unsigned long long *off, unsigned long long n_docs, const short *flen, unsigned num_final,
+                                      const unsigned *tcnt, const unsigned long long *gpre, unsigned n_groups,
+                                      pfac_record *out, unsigned long long *doc_first) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    const unsigned g = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (g >= n_groups) return;
+    const bool fsmall = num_final <= (unsigned)WAVE;
+    const int freg = fsmall && (unsigned)lane < num_final ? (int)flen[lane] : 0;
+    const unsigned long long t = (unsigned long long)g * XGROUP + lane;
+    const unsigned long long e = t < n_tiles ? tix[t] : 0ull;
+    const unsigned c = (unsigned)(e >> TIX_CNT_SHIFT);
+    const unsigned long long lo = e & TIX_BASE_MASK;
+    const unsigned kc = t < n_tiles ? tcnt[t] : 0u;
+    const unsigned long long off0 = gpre[g] + (wave_incl_scan(kc) - kc);   // sorted index of the tile's first kept record
+    unsigned long long ds = 0, de = 0, dlo = 0, dhi = 0;
+    if (t < n_tiles) tile_docs(off, n_docs, t, n_tiles, ds, de, dlo, dhi);
+    for (int j = 0; j < XGROUP; j++) {
+        if ((unsigned long long)g * XGROUP + j >= n_tiles) break;
+        const unsigned tc = __shfl(c, j, WAVE);
+        const unsigned long long tlo = __shfl(lo, j, WAVE);
+        const unsigned long long tde = __shfl(de, j, WAVE);
+        unsigned long long k = __shfl(off0, j, WAVE);           // next output index (wave-uniform)
+        unsigned long long nxt = __shfl(ds, j, WAVE);           // first document of the tile whose doc_first is not written yet
+        const unsigned kt = __shfl(kc, j, WAVE);
+        if (kt) {                                               // (a tile without kept records only places its documents)
+            const DocWin w = doc_window(off, __shfl(dlo, j, WAVE), __shfl(dhi, j, WAVE), lane);
+            for (unsigned c0 = 0; c0 < tc; c0 += WAVE) {
+                const unsigned i = c0 + (unsigned)lane;
+                const bool have = i < tc && tlo + i < cap;
+                unsigned pos = 0, st = 0;
+                if (have) heap_record<BYTES>(rec, tlo + i, (unsigned long long)g * XGROUP + j, pos, st);
+                const int len = final_len(flen, freg, fsmall, have, st);
+                unsigned long long d, base, end;
+                doc_lookup(w, off, have, pos, d, base, end);
+                const bool keep = have && len > 0 && (unsigned long long)pos + (unsigned)len <= end;
+                const unsigned long long b = __ballot(keep);
+                if (b == 0) continue;
+                const unsigned long long below = b & ((1ull << lane) - 1ull);    // kept lanes in front of this one
+                const unsigned long long dprev = __shfl(d, below ? 63 - __clzll(below) : lane, WAVE);
+                if (keep) {
+                    const unsigned long long kk = k + (unsigned)__popcll(below);
+                    pfac_record o;
+                    o.pos = pos - (unsigned)base;
+                    o.state = st;
+                    out[kk] = o;
+                    for (unsigned long long dd = below ? dprev + 1 : nxt; dd <= d; dd++) doc_first[dd] = kk;
+                }
+                nxt = __shfl(d, 63 - __clzll(b), WAVE) + 1;
+                k += (unsigned)__popcll(b);
+            }
+        }
+        for (unsigned long long dd = nxt + lane; dd < tde; dd += WAVE) doc_first[dd] = k;
+    }
+}
+
+// ---------------------------------------------------------------------------
 // GPU-side text emitter (replaces the fprintf loop of main.cc:335-350 on the device): the compact records of a scan ->
 // the lines  "At position %4d, match pattern %d\n"  in output order, in one device buffer.  Three kernels: bytes per
 // group of 64 tiles (line length depends on the digit counts), exclusive scan of the group sums (pfac_scan_groups_kernel),
@@ -2257,7 +2450,21 @@ struct Slot {
     bool h2d_issued = false;
     uint64_t last_cap = 0, last_tiles = 0, last_total = 0, last_used = 0;
     bool scanned = false, pending = false, last_dense = false;
+    uint64_t last_owned = 0;              // n_owned of the slot's last scan (what pfac_records_segment cuts)
+    uint64_t last_table = 0;              // ... and the table it ran with (pfac_ctx::table_gen)
     unsigned long long *d_dbg = nullptr;  // PFAC_TRACE_BUILD + PFAC_TRACE
+    // pfac_slot_doc_offsets / pfac_records_segment
+    unsigned long long *d_doc_off = nullptr;   // the slot's document offsets (doc_n + 1 of them)
+    uint64_t doc_off_cap = 0, doc_n = 0;
+    bool doc_set = false;
+    unsigned *d_seg_tcnt = nullptr;       // kept records per tile of the last segment pass
+    uint64_t seg_tcnt_cap = 0;
+    pfac_record *d_seg_out = nullptr;     // slot-owned outputs of the last segment pass (d_out / d_doc_first NULL)
+    uint64_t seg_out_cap = 0;
+    unsigned long long *d_seg_first = nullptr;
+    uint64_t seg_first_cap = 0;
+    uint64_t seg_kept = 0, seg_docs = 0;
+    bool seg_done = false, seg_own_out = false, seg_own_first = false;
 };
 
 }  // namespace
@@ -2307,6 +2514,8 @@ struct pfac_ctx {
     int d1_n2 = 0;                        // > 0: dense rows are packed (fused tables), r[] of the depth-2 states follows them
     int grid_blocks = 0;
     int rec_bytes = 4;                    // record form: 2 (<= 16 final states), 4 (<= 2^20), 8 bytes (pfac_record)
+    short *d_flen = nullptr;              // pattern length of every final state (pfac_table_set_final_lengths), cleared by an upload
+    uint64_t table_gen = 0;               // tables installed so far: a scan's final states index the lengths of ITS table only
     // level-2 filter (ScanArgs::l2f_mode)
     unsigned char *d_bm2 = nullptr;       // 2-byte-prefix bitmap, 256 rows of 32 bytes
     int l2f_mode = 0, n_child = 0, bm2_rows = 0, sh_bm2 = 0, sec_filter = 0, sh_t0 = 0;
@@ -2683,6 +2892,7 @@ int install_table(pfac_ctx *ctx, const int *d_blob, const int32_t *hdr, size_t n
     const size_t off_id = off_T + (size_t)ht_size * 8;
     const size_t total = align_up(off_id + (size_t)num_final * 4, 16) + 16;
     if (ctx->d_tab) { HIP_TRY(ctx, hipFree(ctx->d_tab)); ctx->d_tab = nullptr; }
+    if (ctx->d_flen) { HIP_TRY(ctx, hipFree(ctx->d_flen)); ctx->d_flen = nullptr; }   // the lengths belong to the old table
     HIP_TRY(ctx, hipMalloc((void **)&ctx->d_tab, total));
     ctx->tab_bytes = total;
     unsigned char *base = reinterpret_cast<unsigned char *>(ctx->d_tab);
@@ -2702,6 +2912,7 @@ int install_table(pfac_ctx *ctx, const int *d_blob, const int32_t *hdr, size_t n
         ctx->have_table = false;
         return fail(ctx, PFAC_E_ARG, "table image: a displacement or a state points outside the tables");
     }
+    ctx->table_gen++;
     ctx->width_bit = wbit; ctx->num_final = num_final; ctx->max_pat_len = max_pat_len;
     ctx->max_row = max_row; ctx->ht_size = ht_size; ctx->state_num = state_num;
     ctx->have_table = true;
@@ -2768,6 +2979,10 @@ void pfac_ctx_destroy(pfac_ctx *ctx) {
         if (s.d_text) (void)hipFree(s.d_text);
         if (s.d_wide) (void)hipFree(s.d_wide);
         if (s.d_dbg) (void)hipFree(s.d_dbg);
+        if (s.d_doc_off) (void)hipFree(s.d_doc_off);
+        if (s.d_seg_tcnt) (void)hipFree(s.d_seg_tcnt);
+        if (s.d_seg_out) (void)hipFree(s.d_seg_out);
+        if (s.d_seg_first) (void)hipFree(s.d_seg_first);
         if (s.d_sum) (void)hipFree(s.d_sum);
         if (s.h_ctl) (void)hipHostFree(s.h_ctl);
         if (s.ev0) (void)hipEventDestroy(s.ev0);
@@ -2780,6 +2995,7 @@ void pfac_ctx_destroy(pfac_ctx *ctx) {
     if (ctx->d_d1) (void)hipFree(ctx->d_d1);
     if (ctx->d_T4_alloc) (void)hipFree(ctx->d_T4_alloc);
     if (ctx->d_bm2) (void)hipFree(ctx->d_bm2);
+    if (ctx->d_flen) (void)hipFree(ctx->d_flen);
     delete ctx;
 }
 
@@ -2923,6 +3139,8 @@ int pfac_scan_async(pfac_ctx *ctx, int slot, const void *d_input, uint64_t n_own
     const int lds_bytes = dense ? ctx->lds_bytes_d : L.lds_bytes;
     s.last_dense = dense;
     s.last_tiles = n_tiles;
+    s.last_owned = n_owned;
+    s.last_table = ctx->table_gen;
     s.last_rec_bytes = ctx->rec_bytes;
     s.last_records = d_records;
     // The control header (ticket counters, flags, heap cursor) must start at zero.  The slot has two: every scan
@@ -3273,6 +3491,145 @@ int pfac_records_checksum(pfac_ctx *ctx, int slot, const void *d_records, uint64
     HIP_TRY(ctx, hipMemcpyAsync(s.h_ctl + 8, s.d_sum, 8, hipMemcpyDeviceToHost, s.stream));
     HIP_TRY(ctx, hipStreamSynchronize(s.stream));
     *checksum = ((uint64_t)s.h_ctl[9] << 32) | s.h_ctl[8];
+    return PFAC_OK;
+}
+
+int pfac_table_set_final_lengths(pfac_ctx *ctx, const int32_t *len, size_t n) {
+    if (!ctx) return fail(nullptr, PFAC_E_ARG, "null context");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (!ctx->have_table) return fail(ctx, PFAC_E_STATE, "pfac_table_set_final_lengths before a table upload");
+    if (n != (size_t)ctx->num_final || (!len && n)) return fail(ctx, PFAC_E_ARG, "pfac_table_set_final_lengths: need num_final lengths");
+    std::vector<short> h(n ? n : 1, (short)-1);
+    for (size_t i = 0; i < n; i++) {
+        if (len[i] != -1 && (len[i] < 1 || len[i] > 1024))
+            return fail(ctx, PFAC_E_ARG, "pfac_table_set_final_lengths: a length outside -1, 1..1024 (final state " + std::to_string(i) + ")");
+        h[i] = (short)len[i];
+    }
+    USE_DEVICE(ctx);
+    if (!ctx->d_flen) HIP_TRY(ctx, hipMalloc((void **)&ctx->d_flen, h.size() * sizeof(short)));
+    HIP_TRY(ctx, hipMemcpy(ctx->d_flen, h.data(), h.size() * sizeof(short), hipMemcpyHostToDevice));
+    return PFAC_OK;
+}
+
+int pfac_slot_doc_offsets(pfac_ctx *ctx, int slot, const uint64_t *host_offsets, uint64_t n_docs) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    if (!host_offsets || n_docs >= (1ull << 32)) return fail(ctx, PFAC_E_ARG, "pfac_slot_doc_offsets: need n_docs + 1 offsets, n_docs < 2^32");
+    Slot &s = ctx->slots[slot];
+    USE_DEVICE(ctx);
+    s.doc_set = false;
+    if (n_docs + 1 > s.doc_off_cap) {
+        if (s.d_doc_off) { HIP_TRY(ctx, hipStreamSynchronize(s.stream)); HIP_TRY(ctx, hipFree(s.d_doc_off)); s.d_doc_off = nullptr; s.doc_off_cap = 0; }
+        const uint64_t cap = n_docs + 1 < 4096 ? 4096 : n_docs + 1 + n_docs / 4;
+        HIP_TRY(ctx, hipMalloc((void **)&s.d_doc_off, cap * 8));
+        s.doc_off_cap = cap;
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(s.d_doc_off, host_offsets, (n_docs + 1) * 8, hipMemcpyHostToDevice, s.stream));
+    HIP_TRY(ctx, hipStreamSynchronize(s.stream));        // (the caller's array may go once this returns)
+    s.doc_n = n_docs;
+    s.doc_set = true;
+    return PFAC_OK;
+}
+
+int pfac_records_segment(pfac_ctx *ctx, int slot, const void *d_records, const uint64_t *d_doc_offsets, uint64_t n_docs,
+                         pfac_record *d_out, uint64_t out_cap, uint64_t *d_doc_first, uint64_t *n_kept) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    if (!n_kept) return fail(ctx, PFAC_E_ARG, "null argument");
+    *n_kept = 0;
+    Slot &s = ctx->slots[slot];
+    s.seg_done = false;
+    if (!s.scanned || s.pending) return fail(ctx, PFAC_E_STATE, "pfac_records_segment needs a finished scan");
+    if (!ctx->have_table || !ctx->d_flen) return fail(ctx, PFAC_E_STATE, "pfac_records_segment: no final-state lengths for the uploaded table (pfac_table_set_final_lengths)");
+    if (s.last_table != ctx->table_gen) return fail(ctx, PFAC_E_STATE, "pfac_records_segment: the slot's last scan ran with an earlier table");
+    if (s.last_used > s.last_cap) return fail(ctx, PFAC_E_OVERFLOW, "the slot's last scan overflowed its record heap: scan again with a larger one");
+    const void *src = d_records ? d_records : s.d_records;
+    const unsigned long long *off = reinterpret_cast<const unsigned long long *>(d_doc_offsets);
+    if (!off) {
+        if (!s.doc_set) return fail(ctx, PFAC_E_STATE, "pfac_records_segment: no document offsets for the slot (pfac_slot_doc_offsets)");
+        if (n_docs != s.doc_n) return fail(ctx, PFAC_E_ARG, "pfac_records_segment: n_docs differs from the slot's document offsets");
+        off = s.d_doc_off;
+    }
+    if (n_docs >= (1ull << 32)) return fail(ctx, PFAC_E_ARG, "pfac_records_segment: n_docs must be below 2^32");
+    if (n_docs == 0 && s.last_owned != 0) return fail(ctx, PFAC_E_ARG, "pfac_records_segment: no documents, but the scan owns bytes");
+    if (((uintptr_t)off & 7) || ((uintptr_t)d_out & 7) || ((uintptr_t)d_doc_first & 7))
+        return fail(ctx, PFAC_E_ARG, "pfac_records_segment: device buffers must be 8-byte aligned");
+    if (!src && s.last_tiles) return fail(ctx, PFAC_E_ARG, "null record buffer");
+    USE_DEVICE(ctx);
+    const uint64_t n_tiles = s.last_tiles;
+    const unsigned n_groups = (unsigned)((n_tiles + XGROUP - 1) / XGROUP);
+    rc = ensure_gsum(ctx, s, n_groups + 1);                 // group prefixes, the total, the offsets' error flag
+    if (rc) return rc;
+    if (n_tiles > s.seg_tcnt_cap) {
+        if (s.d_seg_tcnt) { HIP_TRY(ctx, hipStreamSynchronize(s.stream)); HIP_TRY(ctx, hipFree(s.d_seg_tcnt)); s.d_seg_tcnt = nullptr; s.seg_tcnt_cap = 0; }
+        const uint64_t cap = n_tiles < 4096 ? 4096 : n_tiles + n_tiles / 4;
+        HIP_TRY(ctx, hipMalloc((void **)&s.d_seg_tcnt, cap * 4));
+        s.seg_tcnt_cap = cap;
+    }
+    HIP_TRY(ctx, hipMemsetAsync(s.d_gsum + n_groups, 0, 16, s.stream));
+    // count (and check the offsets): four groups per 256-thread block, at least one thread per document up to a cap
+    const uint64_t gblocks = (n_groups + 3) / 4, vblocks = (n_docs + 255) / 256;
+    const unsigned cblocks = (unsigned)std::max<uint64_t>(1, std::max<uint64_t>(gblocks, std::min<uint64_t>(vblocks, 4096)));
+    const int rb = s.last_rec_bytes;
+    auto ck = rb == 2 ? pfac_seg_count_kernel<2> : (rb == 4 ? pfac_seg_count_kernel<4> : pfac_seg_count_kernel<8>);
+    hipLaunchKernelGGL(ck, dim3(cblocks), dim3(256), 0, s.stream, src, s.d_tile_index, (unsigned long long)n_tiles,
+                       (unsigned long long)s.last_cap, off, (unsigned long long)n_docs, (unsigned long long)s.last_owned,
+                       ctx->d_flen, (unsigned)ctx->num_final, s.d_seg_tcnt, s.d_gsum, n_groups, s.d_gsum + n_groups + 1);
+    if (n_groups) hipLaunchKernelGGL(pfac_scan_groups_kernel, dim3(1), dim3(1024), 0, s.stream, s.d_gsum, n_groups);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(s.h_ctl + 10, s.d_gsum + n_groups, 16, hipMemcpyDeviceToHost, s.stream));
+    HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+    const uint64_t total = ((uint64_t)s.h_ctl[11] << 32) | s.h_ctl[10];
+    if (s.h_ctl[12] | s.h_ctl[13])
+        return fail(ctx, PFAC_E_ARG, "pfac_records_segment: document offsets must start at 0, not decrease, and end at the scan's n_owned (" +
+                                         std::to_string(s.last_owned) + ")");
+    *n_kept = total;
+    const bool own_out = d_out == nullptr, own_first = d_doc_first == nullptr;
+    if (!own_out && total > out_cap)
+        return fail(ctx, PFAC_E_OVERFLOW, "pfac_records_segment: " + std::to_string(total) + " records kept, out_cap is " + std::to_string(out_cap));
+    if (own_out && total > s.seg_out_cap) {
+        if (s.d_seg_out) { HIP_TRY(ctx, hipFree(s.d_seg_out)); s.d_seg_out = nullptr; s.seg_out_cap = 0; }
+        const uint64_t cap = total + total / 8 + 4096;
+        HIP_TRY(ctx, hipMalloc((void **)&s.d_seg_out, cap * sizeof(pfac_record)));
+        s.seg_out_cap = cap;
+    }
+    if (own_first && n_docs + 1 > s.seg_first_cap) {
+        if (s.d_seg_first) { HIP_TRY(ctx, hipFree(s.d_seg_first)); s.d_seg_first = nullptr; s.seg_first_cap = 0; }
+        const uint64_t cap = n_docs + 1 < 4096 ? 4096 : n_docs + 1 + n_docs / 4;
+        HIP_TRY(ctx, hipMalloc((void **)&s.d_seg_first, cap * 8));
+        s.seg_first_cap = cap;
+    }
+    pfac_record *out = own_out ? s.d_seg_out : d_out;
+    unsigned long long *first = own_first ? s.d_seg_first : reinterpret_cast<unsigned long long *>(d_doc_first);
+    if (n_groups) {
+        auto wk = rb == 2 ? pfac_seg_write_kernel<2> : (rb == 4 ? pfac_seg_write_kernel<4> : pfac_seg_write_kernel<8>);
+        hipLaunchKernelGGL(wk, dim3((unsigned)gblocks), dim3(256), 0, s.stream, src, s.d_tile_index, (unsigned long long)n_tiles,
+                           (unsigned long long)s.last_cap, off, (unsigned long long)n_docs, ctx->d_flen, (unsigned)ctx->num_final, s.d_seg_tcnt, s.d_gsum,
+                           n_groups, out, first);
+        HIP_TRY(ctx, hipGetLastError());
+    } else {
+        HIP_TRY(ctx, hipMemsetAsync(first, 0, (n_docs + 1) * 8, s.stream));   // nothing scanned: every document is empty
+    }
+    s.seg_kept = total;
+    s.seg_docs = n_docs;
+    s.seg_own_out = own_out;
+    s.seg_own_first = own_first;
+    s.seg_done = true;
+    return PFAC_OK;
+}
+
+int pfac_segment_d2h(pfac_ctx *ctx, int slot, pfac_record *host_records, uint64_t *host_doc_first) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    Slot &s = ctx->slots[slot];
+    if (!s.seg_done) return fail(ctx, PFAC_E_STATE, "pfac_segment_d2h without a finished pfac_records_segment");
+    if ((host_records && !s.seg_own_out) || (host_doc_first && !s.seg_own_first))
+        return fail(ctx, PFAC_E_STATE, "pfac_segment_d2h: the last pfac_records_segment wrote into the caller's buffers");
+    USE_DEVICE(ctx);
+    if (host_records && s.seg_kept)
+        HIP_TRY(ctx, hipMemcpyAsync(host_records, s.d_seg_out, s.seg_kept * sizeof(pfac_record), hipMemcpyDeviceToHost, s.stream));
+    if (host_doc_first)
+        HIP_TRY(ctx, hipMemcpyAsync(host_doc_first, s.d_seg_first, (s.seg_docs + 1) * 8, hipMemcpyDeviceToHost, s.stream));
     return PFAC_OK;
 }
 

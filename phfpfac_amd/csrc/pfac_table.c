@@ -529,6 +529,69 @@ int32_t pfac_table_lookup(const pfac_table *t, int32_t state, int32_t ch) {
     return t->HT[idx] == row ? t->val[idx] : -1;
 }
 
+/* Depth of every final state, from the table alone: the occupied slots of the perfect hash are the edges (slot idx
+ * with HT[idx] = row holds key row*width + idx - r[row], i.e. state key>>8, byte key&255, child val[idx]); s0 adds the
+ * root's.  A BFS from the root over that edge list (CSR by state) gives each state its depth: O(n_keys + state_num).
+ * In a trie the depth of a final state is its pattern's length; a charclass DFA is acyclic and every path into a state
+ * has the same length, so the same holds there.  Finals no input reaches (the states of duplicate lines) get -1. */
+int pfac_table_final_lengths(const pfac_table *t, int32_t *len, size_t n) {
+    if (!t || (!len && t->num_final > 0) || n < (size_t)t->num_final || t->state_num < t->num_final + 2) return PFAC_E_ARG;
+    const int32_t S = t->state_num, root = t->num_final + 1;
+    int32_t *start = (int32_t *)calloc((size_t)S + 1, sizeof(int32_t));
+    int32_t *depth = (int32_t *)malloc((size_t)S * sizeof(int32_t));
+    int32_t *queue = (int32_t *)malloc((size_t)S * sizeof(int32_t));
+    int32_t *adj = NULL;
+    int rc = PFAC_E_NOMEM;
+    if (!start || !depth || !queue) goto out;
+    /* pass 0 counts the out-edges of every state, pass 1 places the children */
+    int32_t *fill = NULL;
+    for (int pass = 0; pass < 2; pass++) {
+        for (int ch = 0; ch < 256; ch++) {
+            const int32_t c = t->s0[ch];
+            if (c < 0 || c >= S) continue;
+            if (pass == 0) start[root + 1]++;
+            else adj[fill[root]++] = c;
+        }
+        for (int32_t idx = 0; idx < t->ht_size; idx++) {
+            const int32_t row = t->HT[idx];
+            if (row < 0 || row >= t->max_row) continue;
+            const int64_t col = (int64_t)idx - t->r[row];
+            if (col < 0 || col >= t->width) continue;
+            const int64_t key = (int64_t)row * t->width + col;
+            const int64_t s = key >> 8;
+            const int32_t c = t->val[idx];
+            if (s < 0 || s >= S || s == root || c < 0 || c >= S) continue;   /* (the root's edges come from s0) */
+            if (pass == 0) start[s + 1]++;
+            else adj[fill[s]++] = c;
+        }
+        if (pass == 0) {
+            for (int32_t s = 0; s < S; s++) start[s + 1] += start[s];
+            adj = (int32_t *)malloc(((size_t)start[S] + 1) * sizeof(int32_t));
+            fill = depth;                          /* (depth is free until the BFS) */
+            if (!adj) goto out;
+            memcpy(fill, start, (size_t)S * sizeof(int32_t));
+        }
+    }
+    for (int32_t s = 0; s < S; s++) depth[s] = -1;
+    int32_t head = 0, tail = 0;
+    depth[root] = 0;
+    queue[tail++] = root;
+    while (head < tail) {
+        const int32_t s = queue[head++];
+        for (int32_t e = start[s]; e < start[s + 1]; e++) {
+            const int32_t c = adj[e];
+            if (depth[c] >= 0) continue;
+            depth[c] = depth[s] + 1;
+            queue[tail++] = c;
+        }
+    }
+    for (int32_t s = 0; s < t->num_final; s++) len[s] = depth[s];
+    rc = PFAC_OK;
+out:
+    free(start); free(depth); free(queue); free(adj);
+    return rc;
+}
+
 /* ---- flat image ---- */
 size_t pfac_table_blob_words(const pfac_table *t) {
     return (size_t)PFAC_BLOB_HEADER_WORDS + 256 + (size_t)t->max_row + 2 * (size_t)t->ht_size + (size_t)t->num_final;

@@ -47,6 +47,7 @@ class GpuMatcher:
         self.table: Optional[PfacTable] = None
         self._keep = {}
         self._last_n = {}
+        self._flen_set = False          # final-state lengths on the device for the uploaded table (scan_documents)
         rc = self._L.pfac_ctx_create(int(device), int(n_streams), C.byref(self._ctx))
         if rc:
             self._ctx = C.c_void_p()
@@ -84,10 +85,12 @@ class GpuMatcher:
         else:
             blob = np.ascontiguousarray(table, dtype=np.int32)
             self.table = PfacTable.from_blob(blob)
+        self._flen_set = False
         self._check(self._L.pfac_table_upload(self._ctx, blob.ctypes.data, blob.size))
 
     def load_table_device(self, d_blob, n_words: int, stream: int = 0, host_table: Optional[PfacTable] = None) -> None:
         """Install a table image that already sits in this GPU's memory (e.g. after an RCCL broadcast)."""
+        self._flen_set = False
         self._check(self._L.pfac_table_upload_device(self._ctx, _ptr(d_blob), int(n_words), stream))
         if host_table is not None:
             self.table = host_table
@@ -267,6 +270,85 @@ class GpuMatcher:
             cnt = self.scan_resident(n, n, slot=slot)
             lists.append(self.records_to_host(cnt, slot))
         return merge_partitions(lists, [t.idmap for t in tables])
+
+    # -- batches of documents ---------------------------------------------
+    def set_final_lengths(self, lengths) -> None:
+        """Pattern length of every final state of the uploaded table (``PfacTable.final_lengths()``); kept on the
+        device until the next table upload."""
+        lens = np.ascontiguousarray(lengths, dtype=np.int32)
+        self._check(self._L.pfac_table_set_final_lengths(self._ctx, lens.ctypes.data, lens.size))
+        self._flen_set = True
+
+    def set_doc_offsets(self, offsets, slot: int = 0) -> None:
+        """Document boundaries of the slot (n_docs + 1 offsets: 0, ends of documents ..., n_owned)."""
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if off.size < 1:
+            raise ValueError("need n_docs + 1 >= 1 offsets")
+        self._check(self._L.pfac_slot_doc_offsets(self._ctx, slot, off.ctypes.data, off.size - 1))
+
+    def segment_records(self, n_docs: int, d_doc_offsets=None, d_out=None, out_cap: int = 0, d_doc_first=None,
+                        slot: int = 0, d_records=None) -> int:
+        """Cut the slot's last finished scan into documents [off[d], off[d+1]) on the GPU: drop the records that run
+        past their document's end, rebase the others to it, index them per document.  ``d_doc_offsets`` None = the
+        slot's (``set_doc_offsets``); ``d_out`` / ``d_doc_first`` None = slot-owned buffers (``segment_to_host``).
+        Returns the number of records kept.  A too small ``out_cap`` raises PfacError(PFAC_E_OVERFLOW) whose
+        ``n_kept`` attribute holds the exact count."""
+        n = C.c_uint64(0)
+        rc = self._L.pfac_records_segment(self._ctx, slot, _ptr(d_records), _ptr(d_doc_offsets), int(n_docs), _ptr(d_out),
+                                          int(out_cap), _ptr(d_doc_first), C.byref(n))
+        if rc:
+            e = PfacError(rc, (self._L.pfac_last_error(self._ctx) or b"").decode())
+            e.n_kept = n.value
+            raise e
+        return n.value
+
+    def segment_to_host(self, n_kept: int, n_docs: int, slot: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+        """(doc_first uint64[n_docs + 1], records) of the slot's last ``segment_records`` into slot-owned buffers."""
+        rec = np.empty(int(n_kept), dtype=RECORD_DTYPE)
+        first = np.empty(int(n_docs) + 1, dtype=np.uint64)
+        self._check(self._L.pfac_segment_d2h(self._ctx, slot, rec.ctypes.data if n_kept else None, first.ctypes.data))
+        self.sync(slot)
+        return first, rec
+
+    def _ensure_final_lengths(self) -> None:
+        if self._flen_set:
+            return
+        if self.table is None:
+            raise PfacError(-7, "no host table to take the final-state lengths from (load_table first)")
+        lens = getattr(self.table, "_final_lengths", None)
+        if lens is None:
+            lens = self.table.final_lengths()
+            self.table._final_lengths = lens          # once per table
+        self.set_final_lengths(lens)
+
+    def scan_documents(self, docs, slot: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+        """Match a batch of independent documents in one scan.  ``docs`` is a sequence of bytes-like objects, or a
+        ``(buffer, offsets)`` pair whose offsets (an integer array or list, n_docs + 1 of them, from 0 to len(buffer))
+        cut ``buffer`` into documents.  Returns (doc_first uint64[n_docs + 1], records): the records of document d are
+        ``records[doc_first[d]:doc_first[d + 1]]``, positions relative to the document, in (offset, pattern length)
+        order -- what scanning each document on its own yields."""
+        if (isinstance(docs, tuple) and len(docs) == 2 and isinstance(docs[1], (np.ndarray, list, range))
+                and np.asarray(docs[1]).dtype != np.uint8):
+            buf, offsets = docs
+            buf = np.frombuffer(buf, dtype=np.uint8) if not isinstance(buf, np.ndarray) else buf.view(np.uint8).ravel()
+            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        else:
+            parts = [np.frombuffer(d, dtype=np.uint8) if not isinstance(d, np.ndarray) else d.view(np.uint8).ravel()
+                     for d in docs]
+            offsets = np.zeros(len(parts) + 1, dtype=np.uint64)
+            if parts:
+                np.cumsum([p.size for p in parts], out=offsets[1:])
+            buf = np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint8)
+        n = int(buf.size)
+        n_docs = int(offsets.size) - 1
+        self._ensure_final_lengths()
+        self.reserve(slot, max(n, 1), max(n // 8, 4096))
+        if n:
+            self.h2d(buf, slot)
+        self.scan_resident(n, n, slot=slot)
+        self.set_doc_offsets(offsets, slot)
+        kept = self.segment_records(n_docs, slot=slot)
+        return self.segment_to_host(kept, n_docs, slot)
 
     # -- synthetic inputs (device resident) --------------------------------
     def fill_tiled(self, d_dst, n: int, pattern: bytes, phase: int = 0, slot: int = 0) -> None:

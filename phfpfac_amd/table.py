@@ -125,6 +125,15 @@ class PfacTable:
         """The device lookup (master_kernel.cu:52-63) evaluated on the host."""
         return int(host_lib().pfac_table_lookup(self._ptr, int(state), int(ch)))
 
+    def final_lengths(self) -> np.ndarray:
+        """int32[num_final]: bytes of the pattern(s) ending in each final state (its depth in the trie / DFA), -1 for
+        a final state no input reaches (the state of a duplicate line).  Computed from the table alone."""
+        out = np.empty(max(self.num_final, 1), dtype=np.int32)
+        rc = host_lib().pfac_table_final_lengths(self._ptr, out.ctypes.data, out.size)
+        if rc:
+            raise PfacError(rc, "pfac_table_final_lengths")
+        return out[: self.num_final]
+
     def blob(self) -> np.ndarray:
         """Flat int32 image (what gets uploaded / broadcast between ranks)."""
         L = host_lib()
