@@ -341,6 +341,32 @@ int pfac_records_segment(pfac_ctx *ctx, int slot, const void *d_records, const u
  * Asynchronous on the slot's stream; pfac_slot_sync completes it. */
 int pfac_segment_d2h(pfac_ctx *ctx, int slot, pfac_record *host_records, uint64_t *host_doc_first);
 
+/* Leftmost-longest, non-overlapping selection over the slot's last finished scan.  From a cursor c = entry
+ * (0 <= entry <= max_pat_len of the uploaded table): take the smallest position p >= c that has a record, select its
+ * record of the greatest pattern length (the last one at p), set c = p + len, repeat while records remain at or after c.
+ *   d_records   the scan's record heap, NULL = the slot's
+ *   d_out       NULL = a slot-owned buffer grown to fit (fetched with pfac_leftmost_longest_d2h); else a device pointer,
+ *               8-B aligned, holding out_cap records.  The selection is written as {pos, state} in ascending pos,
+ *               positions relative to the scan's start (as pfac_records_d2h).
+ *   *exit_offset = max(c_final, n_owned) - n_owned, c_final the cursor after the last pick (entry if none): in
+ *               [0, max_pat_len].  Passed as the next scan's entry, scans chained over consecutive owned ranges (with
+ *               the usual max_pat_len - 1 halo) select exactly what one scan of the whole range selects.
+ * Needs the final-state lengths of the current table (pfac_table_set_final_lengths).
+ * Returns once *n_selected and *exit_offset are known; the writes are asynchronous on the slot's stream.
+ * PFAC_E_OVERFLOW (with *n_selected exact, nothing written) when out_cap is too small for a caller's d_out;
+ * PFAC_E_ARG for entry > max_pat_len or misaligned buffers; PFAC_E_STATE without a finished scan, for a scan made with
+ * an earlier table, without lengths for the current table, or when the scan overflowed its heap.
+ * Kernels: every tile of 4 KiB is a function from its entry offset to its exit offset (the cursor that reaches a tile
+ * lies within max_pat_len of its start); one pass builds them per group of 64 tiles, two small ones compose the groups
+ * and evaluate them from entry, a second pass marks every tile's picks, then the group prefix and the write.  They read
+ * the record heap, the tile index and the lengths, never the input.  The slot-owned output is separate from
+ * pfac_records_segment's. */
+int pfac_records_leftmost_longest(pfac_ctx *ctx, int slot, const void *d_records, uint32_t entry, pfac_record *d_out,
+                                  uint64_t out_cap, uint64_t *n_selected, uint32_t *exit_offset);
+/* D2H of the slot-owned result of the last pfac_records_leftmost_longest (*n_selected records).  Asynchronous on the
+ * slot's stream; pfac_slot_sync completes it. */
+int pfac_leftmost_longest_d2h(pfac_ctx *ctx, int slot, pfac_record *host);
+
 /* Synthetic input generators, written straight into device memory (the
  * reference built big inputs by tiling a small text, creatbiginput.sh:2-5).
  *   tiled : byte i = pattern[(phase + i) % period]

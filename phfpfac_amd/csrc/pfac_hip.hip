@@ -2255,6 +2255,282 @@ __global__ void pfac_seg_write_kernel(const void *rec, const unsigned long long 
 }
 
 // ---------------------------------------------------------------------------
+// Leftmost-longest non-overlapping selection (pfac_records_leftmost_longest).  The greedy -- from cursor c take the
+// first position p >= c that has a record, its longest record, c = p + len -- is sequential, but with
+// M = max_pat_len the cursor that reaches tile t lies in [4096t, 4096t + M]: every earlier pick started before the
+// tile and is at most M long.  So tile t is a function F_t: [0, M] -> [0, M] from its entry offset to the exit offset
+// into tile t + 1 (0 when the cursor ends before that tile starts; the last tile's exit is relative to n_owned), and
+// composition is associative:
+//   pfac_ll_tiles_kernel<., false>  one workgroup per group of 64 tiles, one tile per wave at a time in LDS;
+//                                   G_g = F_{64g+63} o ... o F_{64g} as uint16[M + 1]
+//   pfac_ll_compose_kernel          the G_g of 64 groups -> one function (two levels, no long dependent chain)
+//   pfac_ll_walk_kernel             evaluates them from `entry`: every block's, then every group's entry offset
+//   pfac_ll_tiles_kernel<., true>   the tile functions again; each tile's entry from its group's; the chain from that
+//                                   entry marked in a per-tile bitmap of positions; selected records per tile, group
+//   pfac_scan_groups_kernel, then pfac_ll_write_kernel: a selected record's index is its tile's prefix + ballot rank.
+// Inside a tile: candidates k = the last record at each position (the longest), in position order; next[k] = the first
+// candidate at or after pos[k] + len[k] (K: none, the chain leaves the tile).  Fewer than len[k] candidates lie in
+// between, so a binary search over [k + 1, k + len] finds it.  The end of k's chain, exitE[k], comes from chunks of 64
+// candidates in DESCENDING order: pointer jumping inside the chunk with lane shuffles (6 rounds), then the exitE of the
+// first node past the chunk, already final, from LDS.  O(K log M) per tile whatever the input; chains that never meet
+// (`aa` on a run of `a`) cost nothing extra.
+
+constexpr int LL_WAVES = 4;                                     // waves per workgroup of the tiles kernel: one tile each
+constexpr int LL_WAVE_LDS = WTILE * 2 * 3;                      // cpos, nxt, ends (u16 per candidate); the bitmap reuses ends
+constexpr int LL_CHUNK_BYTES = 32768;                           // functions staged in LDS at a time by compose / walk
+
+__host__ __device__ constexpr unsigned ll_fun_stride(unsigned m1) { return (m1 + 7u) & ~7u; }   // u16 per function (16-B rows)
+static size_t ll_tiles_lds(unsigned m1) {
+    return (size_t)LL_WAVES * LL_WAVE_LDS + (size_t)(LL_WAVES + 1) * ll_fun_stride(m1) * 2 + (2 * LL_WAVES + 2) * 8;
+}
+
+// first k in [lo, hi) with cpos[k] >= x (hi if none)
+__device__ __forceinline__ unsigned ll_lower_bound(const unsigned short *cpos, unsigned lo, unsigned hi, unsigned x) {
+    while (lo < hi) {
+        const unsigned mid = (lo + hi) >> 1;
+        if (cpos[mid] < x) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+template <int BYTES, bool MARK>
+__global__ void __launch_bounds__(LL_WAVES * WAVE)
+pfac_ll_tiles_kernel(const void *rec, const unsigned long long *tix, unsigned long long n_tiles, unsigned long long cap,
+                     unsigned long long n_owned, const short *flen, unsigned num_final, unsigned M,
+                     unsigned short *gfun, const unsigned short *gentry, unsigned long long *bits, unsigned *tcnt,
+                     unsigned long long *gsum) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x >> 6;
+    const unsigned g = blockIdx.x, M1 = M + 1, FS = ll_fun_stride(M1);
+    unsigned short *cpos = reinterpret_cast<unsigned short *>(smem + w * LL_WAVE_LDS);   // tile offset of candidate k
+    unsigned short *nxt = cpos + WTILE;                                                  // next[k]
+    unsigned short *ends = nxt + WTILE;                                                  // pos + len, then exitE[k]
+    unsigned *bm = reinterpret_cast<unsigned *>(ends);                                   // MARK: selected positions
+    unsigned short *fslot = reinterpret_cast<unsigned short *>(smem + LL_WAVES * LL_WAVE_LDS);   // F of each wave's tile
+    unsigned short *G = fslot + LL_WAVES * FS;                                           // !MARK: the running group function
+    unsigned long long *tail = reinterpret_cast<unsigned long long *>(G + FS);           // MARK: tile entries, cursor, sums
+    const bool fsmall = num_final <= (unsigned)WAVE;
+    const int freg = fsmall && (unsigned)lane < num_final ? (int)flen[lane] : 0;
+    if (!MARK)
+        for (unsigned e = threadIdx.x; e < M1; e += blockDim.x) G[e] = (unsigned short)e;
+    if (MARK && threadIdx.x == 0) tail[LL_WAVES] = gentry[g];
+    unsigned long long wsel = 0;                                // selected records of this wave's tiles
+    __syncthreads();
+    for (unsigned b = 0; b < (unsigned)XGROUP; b += LL_WAVES) {
+        const unsigned long long t = (unsigned long long)g * XGROUP + b + w;
+        const bool live = t < n_tiles;                          // (wave-uniform)
+        unsigned K = 0, tend = 0;                               // candidates; the tile's end (a dead tile: identity)
+        if (live) {
+            const unsigned long long e = tix[t];
+            const unsigned c = (unsigned)(e >> TIX_CNT_SHIFT);
+            const unsigned long long lo = e & TIX_BASE_MASK;
+            const unsigned tb = (unsigned)(t * WTILE);
+            tend = t + 1 == n_tiles ? (unsigned)(n_owned - t * WTILE) : (unsigned)WTILE;
+            for (unsigned c0 = 0; c0 < c; c0 += WAVE) {
+                const unsigned i = c0 + (unsigned)lane;
+                const bool have = i < c && lo + i < cap;
+                unsigned pos = 0, st = 0, pn = 0, sn = 0;
+                if (have) heap_record<BYTES>(rec, lo + i, t, pos, st);
+                pn = __shfl(pos, (lane + 1) & (WAVE - 1), WAVE);
+                if (lane == WAVE - 1 && i + 1 < c && lo + i + 1 < cap) heap_record<BYTES>(rec, lo + i + 1, t, pn, sn);
+                const int len = final_len(flen, freg, fsmall, have, st);
+                const bool cand = have && (i + 1 >= c || pn != pos) && len > 0;   // the last (longest) record at pos
+                const unsigned long long bal = __ballot(cand);
+                const unsigned k = K + (unsigned)__popcll(bal & ((1ull << lane) - 1ull));
+                if (cand && k < (unsigned)WTILE) {             // (positions are distinct: at most 4096 candidates)
+                    cpos[k] = (unsigned short)(pos - tb);
+                    ends[k] = (unsigned short)(pos - tb + (unsigned)len);
+                }
+                K = min(K + (unsigned)__popcll(bal), (unsigned)WTILE);
+            }
+            wave_lds_sync();
+            for (int ch = (int)((K + WAVE - 1) / WAVE) - 1; ch >= 0; ch--) {
+                const unsigned base = (unsigned)ch * WAVE, k = base + (unsigned)lane;
+                const bool v = k < K;
+                unsigned nx = K, E = 0;
+                if (v) {
+                    E = ends[k];
+                    nx = ll_lower_bound(cpos, k + 1, min(k + (E - cpos[k]), K), E);
+                }
+                // (J, X, E): the chain goes on at in-chunk node J, or (J = 64) it left the chunk at candidate X (K: the
+                // tile), E the end of its last pick inside the chunk
+                unsigned J = v && nx < K && nx - base < (unsigned)WAVE ? nx - base : (unsigned)WAVE, X = nx;
+#pragma unroll
+                for (int r = 0; r < 6; r++) {
+                    const int src = J < (unsigned)WAVE ? (int)J : lane;
+                    const unsigned J2 = __shfl(J, src, WAVE), X2 = __shfl(X, src, WAVE), E2 = __shfl(E, src, WAVE);
+                    if (J < (unsigned)WAVE) { J = J2; X = X2; E = E2; }
+                }
+                if (v) {
+                    const unsigned ex = X < K ? ends[X] : E;    // X lies in a later chunk: its exitE is final
+                    ends[k] = (unsigned short)ex;
+                    nxt[k] = (unsigned short)nx;
+                }
+                wave_lds_sync();
+            }
+        }
+        // F(e): the end of the chain of the first candidate at offset e or later (candidates at offsets <= M are among
+        // the first M + 1), relative to the tile's end
+        unsigned short *F = fslot + w * FS;
+        for (unsigned e = (unsigned)lane; e < M1; e += WAVE) {
+            const unsigned k = ll_lower_bound(cpos, 0, min(K, M1), e);
+            const unsigned c = k < K ? (unsigned)ends[k] : e;
+            F[e] = (unsigned short)min(c > tend ? c - tend : 0u, M);     // (<= M for lengths that fit the table)
+        }
+        __syncthreads();
+        if (!MARK) {
+            for (unsigned e = threadIdx.x; e < M1; e += blockDim.x) {
+                unsigned v = G[e];
+#pragma unroll
+                for (int ww = 0; ww < LL_WAVES; ww++) v = fslot[ww * FS + v];
+                G[e] = (unsigned short)v;
+            }
+        } else {
+            if (threadIdx.x == 0) {
+                unsigned v = (unsigned)tail[LL_WAVES];
+                for (int ww = 0; ww < LL_WAVES; ww++) { tail[ww] = v; v = fslot[ww * FS + v]; }
+                tail[LL_WAVES] = v;
+            }
+            __syncthreads();
+            if (live) {
+                for (unsigned i = (unsigned)lane; i < (unsigned)WTILE / 32; i += WAVE) bm[i] = 0u;   // (ends is dead now)
+                wave_lds_sync();
+                unsigned T = ll_lower_bound(cpos, 0, min(K, M1), (unsigned)tail[w]);
+                unsigned sel = 0;
+                while (T < K) {                                 // the chunk holding T: mark its part of the chain
+                    const unsigned base = T & ~(unsigned)(WAVE - 1), k = base + (unsigned)lane;
+                    const bool v = k < K;
+                    const unsigned nx = v ? (unsigned)nxt[k] : K;
+                    unsigned Jl[6];                             // in-chunk node 2^l steps on (64: left the chunk)
+                    Jl[0] = v && nx < K && nx - base < (unsigned)WAVE ? nx - base : (unsigned)WAVE;
+#pragma unroll
+                    for (int l = 1; l < 6; l++) {
+                        const unsigned p = Jl[l - 1];
+                        const unsigned q = __shfl(p, p < (unsigned)WAVE ? (int)p : lane, WAVE);
+                        Jl[l] = p < (unsigned)WAVE ? q : (unsigned)WAVE;
+                    }
+                    // the chain's furthest node <= lane (nodes increase along it): lane is on it iff that is lane;
+                    // and its last node in the chunk
+                    unsigned x = T - base, L = T - base;
+#pragma unroll
+                    for (int l = 5; l >= 0; l--) {
+                        const unsigned y = __shfl(Jl[l], (int)x, WAVE), z = __shfl(Jl[l], (int)L, WAVE);
+                        if (y <= (unsigned)lane) x = y;
+                        if (z < (unsigned)WAVE) L = z;
+                    }
+                    const bool on = v && x == (unsigned)lane;
+                    if (on) {
+                        const unsigned p = cpos[k];
+                        atomicOr(&bm[p >> 5], 1u << (p & 31u));
+                    }
+                    sel += (unsigned)__popcll(__ballot(on));
+                    T = __shfl(nx, (int)L, WAVE);
+                }
+                wave_lds_sync();
+                bits[t * (WTILE / 64) + lane] = (unsigned long long)bm[2 * lane] | ((unsigned long long)bm[2 * lane + 1] << 32);
+                if (lane == 0) tcnt[t] = sel;
+                wsel += sel;
+            }
+        }
+        __syncthreads();
+    }
+    if (!MARK) {
+        for (unsigned e = threadIdx.x; e < FS; e += blockDim.x) gfun[(unsigned long long)g * FS + e] = e < M1 ? G[e] : 0;
+    } else {
+        if (lane == 0) tail[LL_WAVES + 1 + w] = wsel;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            unsigned long long s = 0;
+            for (int ww = 0; ww < LL_WAVES; ww++) s += tail[LL_WAVES + 1 + ww];
+            gsum[g] = s;
+        }
+    }
+}
+
+// out[b] = fun[f1 - 1] o ... o fun[f0] for [f0, f1) = block b's `per` functions (blockDim >= M + 1: one entry each)
+__global__ void pfac_ll_compose_kernel(const unsigned short *fun, unsigned M1, unsigned n, unsigned per, unsigned short *out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned short *buf = reinterpret_cast<unsigned short *>(smem);
+    const unsigned FS = ll_fun_stride(M1), nfc = (unsigned)(LL_CHUNK_BYTES / 2) / FS;
+    const unsigned f0 = blockIdx.x * per, f1 = min(f0 + per, n);
+    unsigned v = threadIdx.x;
+    for (unsigned a = f0; a < f1; a += nfc) {
+        const unsigned m = min(nfc, f1 - a);
+        __syncthreads();
+        for (unsigned i = threadIdx.x; i < m * FS / 8; i += blockDim.x)
+            reinterpret_cast<uint4 *>(buf)[i] = reinterpret_cast<const uint4 *>(fun + (unsigned long long)a * FS)[i];
+        __syncthreads();
+        if (threadIdx.x < M1)
+            for (unsigned j = 0; j < m; j++) v = buf[j * FS + v];
+    }
+    if (threadIdx.x < FS) out[(unsigned long long)blockIdx.x * FS + threadIdx.x] = threadIdx.x < M1 ? (unsigned short)v : 0;
+}
+
+// block b: x = start[b] (start NULL: entry); for i in its [f0, f1): at[i] = x, x = fun[i](x).  The block that holds the
+// last function stores the final x in *last (when last is not NULL).  The walk itself runs over LDS.
+__global__ void pfac_ll_walk_kernel(const unsigned short *fun, unsigned M1, unsigned n, unsigned per, const unsigned short *start,
+                                    unsigned entry, unsigned short *at, unsigned long long *last) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned short *buf = reinterpret_cast<unsigned short *>(smem);
+    const unsigned FS = ll_fun_stride(M1), nfc = (unsigned)(LL_CHUNK_BYTES / 2) / FS;
+    const unsigned f0 = blockIdx.x * per, f1 = min(f0 + per, n);
+    unsigned x = start ? start[blockIdx.x] : entry;
+    for (unsigned a = f0; a < f1; a += nfc) {
+        const unsigned m = min(nfc, f1 - a);
+        __syncthreads();
+        for (unsigned i = threadIdx.x; i < m * FS / 8; i += blockDim.x)
+            reinterpret_cast<uint4 *>(buf)[i] = reinterpret_cast<const uint4 *>(fun + (unsigned long long)a * FS)[i];
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (unsigned j = 0; j < m; j++) { at[a + j] = (unsigned short)x; x = buf[j * FS + x]; }
+    }
+    if (threadIdx.x == 0 && last && f1 == n) *last = x;
+}
+
+// selected records -> out[k] = {pos, state} at their sorted index k (one wave per group of 64 tiles)
+template <int BYTES>
+__global__ void pfac_ll_write_kernel(const void *rec, const unsigned long long *tix, unsigned long long n_tiles, unsigned long long cap,
+                                     const unsigned long long *bits, const unsigned *tcnt, const unsigned long long *gpre,
+                                     unsigned n_groups, pfac_record *out) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    const unsigned g = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (g >= n_groups) return;
+    const unsigned long long t = (unsigned long long)g * XGROUP + lane;
+    const unsigned long long e = t < n_tiles ? tix[t] : 0ull;
+    const unsigned c = (unsigned)(e >> TIX_CNT_SHIFT);
+    const unsigned long long lo = e & TIX_BASE_MASK;
+    const unsigned kc = t < n_tiles ? tcnt[t] : 0u;
+    const unsigned long long off0 = gpre[g] + (wave_incl_scan(kc) - kc);   // sorted index of the tile's first pick
+    for (int j = 0; j < XGROUP; j++) {
+        if (__shfl(kc, j, WAVE) == 0) continue;
+        const unsigned long long tj = (unsigned long long)g * XGROUP + j;
+        const unsigned tc = __shfl(c, j, WAVE);
+        const unsigned long long tlo = __shfl(lo, j, WAVE);
+        const unsigned long long *tb = bits + tj * (WTILE / 64);
+        unsigned long long k = __shfl(off0, j, WAVE);
+        for (unsigned c0 = 0; c0 < tc; c0 += WAVE) {
+            const unsigned i = c0 + (unsigned)lane;
+            const bool have = i < tc && tlo + i < cap;
+            unsigned pos = 0, st = 0, pn = 0, sn = 0;
+            if (have) heap_record<BYTES>(rec, tlo + i, tj, pos, st);
+            pn = __shfl(pos, (lane + 1) & (WAVE - 1), WAVE);
+            if (lane == WAVE - 1 && i + 1 < tc && tlo + i + 1 < cap) heap_record<BYTES>(rec, tlo + i + 1, tj, pn, sn);
+            const unsigned p = pos - (unsigned)(tj * WTILE);
+            const bool sel = have && (i + 1 >= tc || pn != pos) && ((tb[p >> 6] >> (p & 63u)) & 1ull);
+            const unsigned long long bal = __ballot(sel);
+            if (sel) {
+                pfac_record o;
+                o.pos = pos;
+                o.state = st;
+                out[k + (unsigned)__popcll(bal & ((1ull << lane) - 1ull))] = o;
+            }
+            k += (unsigned)__popcll(bal);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // GPU-side text emitter (replaces the fprintf loop of main.cc:335-350 on the device): the compact records of a scan ->
 // the lines  "At position %4d, match pattern %d\n"  in output order, in one device buffer.  Three kernels: bytes per
 // group of 64 tiles (line length depends on the digit counts), exclusive scan of the group sums (pfac_scan_groups_kernel),
@@ -2465,6 +2741,12 @@ struct Slot {
     uint64_t seg_first_cap = 0;
     uint64_t seg_kept = 0, seg_docs = 0;
     bool seg_done = false, seg_own_out = false, seg_own_first = false;
+    // pfac_records_leftmost_longest
+    unsigned char *d_ll_tmp = nullptr;    // group functions, group entries, picks per tile, per-tile selection bitmaps
+    uint64_t ll_tmp_cap = 0;
+    pfac_record *d_ll_out = nullptr;      // slot-owned selection (d_out NULL)
+    uint64_t ll_out_cap = 0, ll_n = 0;
+    bool ll_done = false, ll_own_out = false;
 };
 
 }  // namespace
@@ -2983,6 +3265,8 @@ void pfac_ctx_destroy(pfac_ctx *ctx) {
         if (s.d_seg_tcnt) (void)hipFree(s.d_seg_tcnt);
         if (s.d_seg_out) (void)hipFree(s.d_seg_out);
         if (s.d_seg_first) (void)hipFree(s.d_seg_first);
+        if (s.d_ll_tmp) (void)hipFree(s.d_ll_tmp);
+        if (s.d_ll_out) (void)hipFree(s.d_ll_out);
         if (s.d_sum) (void)hipFree(s.d_sum);
         if (s.h_ctl) (void)hipHostFree(s.h_ctl);
         if (s.ev0) (void)hipEventDestroy(s.ev0);
@@ -3630,6 +3914,109 @@ int pfac_segment_d2h(pfac_ctx *ctx, int slot, pfac_record *host_records, uint64_
         HIP_TRY(ctx, hipMemcpyAsync(host_records, s.d_seg_out, s.seg_kept * sizeof(pfac_record), hipMemcpyDeviceToHost, s.stream));
     if (host_doc_first)
         HIP_TRY(ctx, hipMemcpyAsync(host_doc_first, s.d_seg_first, (s.seg_docs + 1) * 8, hipMemcpyDeviceToHost, s.stream));
+    return PFAC_OK;
+}
+
+int pfac_records_leftmost_longest(pfac_ctx *ctx, int slot, const void *d_records, uint32_t entry, pfac_record *d_out,
+                                  uint64_t out_cap, uint64_t *n_selected, uint32_t *exit_offset) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    if (!n_selected || !exit_offset) return fail(ctx, PFAC_E_ARG, "null argument");
+    *n_selected = 0;
+    *exit_offset = entry;
+    Slot &s = ctx->slots[slot];
+    s.ll_done = false;
+    if (!s.scanned || s.pending) return fail(ctx, PFAC_E_STATE, "pfac_records_leftmost_longest needs a finished scan");
+    if (!ctx->have_table || !ctx->d_flen) return fail(ctx, PFAC_E_STATE, "pfac_records_leftmost_longest: no final-state lengths for the uploaded table (pfac_table_set_final_lengths)");
+    if (s.last_table != ctx->table_gen) return fail(ctx, PFAC_E_STATE, "pfac_records_leftmost_longest: the slot's last scan ran with an earlier table");
+    if (s.last_used > s.last_cap) return fail(ctx, PFAC_E_STATE, "pfac_records_leftmost_longest: the slot's last scan overflowed its record heap");
+    const unsigned M = (unsigned)ctx->max_pat_len;
+    if (entry > M) return fail(ctx, PFAC_E_ARG, "pfac_records_leftmost_longest: entry " + std::to_string(entry) + " exceeds max_pat_len " + std::to_string(M));
+    const int rb = s.last_rec_bytes;
+    const void *src = d_records ? d_records : s.d_records;
+    if (((uintptr_t)d_out & 7) || ((uintptr_t)src & (uintptr_t)(rb - 1)))
+        return fail(ctx, PFAC_E_ARG, "pfac_records_leftmost_longest: misaligned buffer (d_out 8 B, records their width)");
+    if (!src && s.last_tiles) return fail(ctx, PFAC_E_ARG, "null record buffer");
+    USE_DEVICE(ctx);
+    const uint64_t n_tiles = s.last_tiles;
+    const bool own_out = d_out == nullptr;
+    if (n_tiles == 0) {                                     // nothing scanned: nothing picked, the cursor stays
+        s.ll_n = 0;
+        s.ll_own_out = own_out;
+        s.ll_done = true;
+        return PFAC_OK;
+    }
+    const unsigned n_groups = (unsigned)((n_tiles + XGROUP - 1) / XGROUP), nb = (n_groups + XGROUP - 1) / XGROUP;
+    const unsigned M1 = M + 1, FS = ll_fun_stride(M1);
+    // scratch: G_g, the composed functions of 64 groups, their entries, the groups' entries, picks per tile, bitmaps
+    const size_t o_gfun = 0, o_hfun = align_up(o_gfun + (size_t)n_groups * FS * 2, 256);
+    const size_t o_hat = align_up(o_hfun + (size_t)nb * FS * 2, 256), o_gat = align_up(o_hat + (size_t)nb * 2, 256);
+    const size_t o_tcnt = align_up(o_gat + (size_t)n_groups * 2, 256), o_bits = align_up(o_tcnt + n_tiles * 4, 256);
+    const size_t need = o_bits + n_tiles * (WTILE / 8);
+    if (need > s.ll_tmp_cap) {
+        if (s.d_ll_tmp) { HIP_TRY(ctx, hipStreamSynchronize(s.stream)); HIP_TRY(ctx, hipFree(s.d_ll_tmp)); s.d_ll_tmp = nullptr; s.ll_tmp_cap = 0; }
+        const uint64_t cap = need + need / 4;
+        HIP_TRY(ctx, hipMalloc((void **)&s.d_ll_tmp, cap));
+        s.ll_tmp_cap = cap;
+    }
+    unsigned short *gfun = reinterpret_cast<unsigned short *>(s.d_ll_tmp + o_gfun), *hfun = reinterpret_cast<unsigned short *>(s.d_ll_tmp + o_hfun);
+    unsigned short *hat = reinterpret_cast<unsigned short *>(s.d_ll_tmp + o_hat), *gat = reinterpret_cast<unsigned short *>(s.d_ll_tmp + o_gat);
+    unsigned *tcnt = reinterpret_cast<unsigned *>(s.d_ll_tmp + o_tcnt);
+    unsigned long long *bits = reinterpret_cast<unsigned long long *>(s.d_ll_tmp + o_bits);
+    rc = ensure_gsum(ctx, s, n_groups + 1);                 // group prefixes, the total, the exit offset
+    if (rc) return rc;
+    auto fk = rb == 2 ? pfac_ll_tiles_kernel<2, false> : (rb == 4 ? pfac_ll_tiles_kernel<4, false> : pfac_ll_tiles_kernel<8, false>);
+    auto mk = rb == 2 ? pfac_ll_tiles_kernel<2, true> : (rb == 4 ? pfac_ll_tiles_kernel<4, true> : pfac_ll_tiles_kernel<8, true>);
+    const size_t lds = ll_tiles_lds(M1);
+    HIP_TRY(ctx, hipFuncSetAttribute((const void *)fk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIP_TRY(ctx, hipFuncSetAttribute((const void *)mk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const unsigned long long nt = n_tiles, cap = s.last_cap, own = s.last_owned;
+    hipLaunchKernelGGL(fk, dim3(n_groups), dim3(LL_WAVES * WAVE), lds, s.stream, src, s.d_tile_index, nt, cap, own, ctx->d_flen,
+                       (unsigned)ctx->num_final, M, gfun, (const unsigned short *)nullptr, bits, tcnt, s.d_gsum);
+    hipLaunchKernelGGL(pfac_ll_compose_kernel, dim3(nb), dim3(1024), LL_CHUNK_BYTES, s.stream, gfun, M1, n_groups, (unsigned)XGROUP, hfun);
+    hipLaunchKernelGGL(pfac_ll_walk_kernel, dim3(1), dim3(256), LL_CHUNK_BYTES, s.stream, hfun, M1, nb, nb, (const unsigned short *)nullptr,
+                       (unsigned)entry, hat, s.d_gsum + n_groups + 1);
+    hipLaunchKernelGGL(pfac_ll_walk_kernel, dim3(nb), dim3(256), LL_CHUNK_BYTES, s.stream, gfun, M1, n_groups, (unsigned)XGROUP,
+                       (const unsigned short *)hat, 0u, gat, (unsigned long long *)nullptr);
+    hipLaunchKernelGGL(mk, dim3(n_groups), dim3(LL_WAVES * WAVE), lds, s.stream, src, s.d_tile_index, nt, cap, own, ctx->d_flen,
+                       (unsigned)ctx->num_final, M, (unsigned short *)nullptr, (const unsigned short *)gat, bits, tcnt, s.d_gsum);
+    hipLaunchKernelGGL(pfac_scan_groups_kernel, dim3(1), dim3(1024), 0, s.stream, s.d_gsum, n_groups);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(s.h_ctl + 10, s.d_gsum + n_groups, 16, hipMemcpyDeviceToHost, s.stream));
+    HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+    const uint64_t total = ((uint64_t)s.h_ctl[11] << 32) | s.h_ctl[10];
+    *n_selected = total;
+    *exit_offset = s.h_ctl[12];
+    if (!own_out && total > out_cap)
+        return fail(ctx, PFAC_E_OVERFLOW, "pfac_records_leftmost_longest: " + std::to_string(total) + " records selected, out_cap is " + std::to_string(out_cap));
+    if (own_out && total > s.ll_out_cap) {
+        if (s.d_ll_out) { HIP_TRY(ctx, hipFree(s.d_ll_out)); s.d_ll_out = nullptr; s.ll_out_cap = 0; }
+        const uint64_t ocap = total + total / 8 + 4096;
+        HIP_TRY(ctx, hipMalloc((void **)&s.d_ll_out, ocap * sizeof(pfac_record)));
+        s.ll_out_cap = ocap;
+    }
+    pfac_record *out = own_out ? s.d_ll_out : d_out;
+    if (total) {
+        auto wk = rb == 2 ? pfac_ll_write_kernel<2> : (rb == 4 ? pfac_ll_write_kernel<4> : pfac_ll_write_kernel<8>);
+        hipLaunchKernelGGL(wk, dim3((n_groups + 3) / 4), dim3(256), 0, s.stream, src, s.d_tile_index, nt, cap, bits, tcnt, s.d_gsum,
+                           n_groups, out);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    s.ll_n = total;
+    s.ll_own_out = own_out;
+    s.ll_done = true;
+    return PFAC_OK;
+}
+
+int pfac_leftmost_longest_d2h(pfac_ctx *ctx, int slot, pfac_record *host) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    Slot &s = ctx->slots[slot];
+    if (!s.ll_done) return fail(ctx, PFAC_E_STATE, "pfac_leftmost_longest_d2h without a finished pfac_records_leftmost_longest");
+    if (!s.ll_own_out) return fail(ctx, PFAC_E_STATE, "pfac_leftmost_longest_d2h: the last selection wrote into the caller's buffer");
+    if (!host && s.ll_n) return fail(ctx, PFAC_E_ARG, "null host buffer");
+    USE_DEVICE(ctx);
+    if (s.ll_n) HIP_TRY(ctx, hipMemcpyAsync(host, s.d_ll_out, s.ll_n * sizeof(pfac_record), hipMemcpyDeviceToHost, s.stream));
     return PFAC_OK;
 }
 

@@ -350,6 +350,47 @@ class GpuMatcher:
         kept = self.segment_records(n_docs, slot=slot)
         return self.segment_to_host(kept, n_docs, slot)
 
+    # -- leftmost-longest non-overlapping matches ---------------------------
+    def select_leftmost_longest(self, entry: int = 0, d_out=None, out_cap: int = 0, slot: int = 0,
+                                d_records=None) -> Tuple[int, int]:
+        """Leftmost-longest, non-overlapping selection over the slot's last finished scan, on the GPU: from cursor
+        ``entry`` take the first position with a record, its longest record, move the cursor past it, repeat.
+        Returns (n_selected, exit): ``exit`` is how far the last pick runs past n_owned, the ``entry`` of the scan
+        of the next owned range.  ``d_out`` None = a slot-owned buffer (``selection_to_host``).  A too small
+        ``out_cap`` raises PfacError(PFAC_E_OVERFLOW) whose ``n_selected`` attribute holds the exact count."""
+        n = C.c_uint64(0)
+        ex = C.c_uint32(0)
+        rc = self._L.pfac_records_leftmost_longest(self._ctx, slot, _ptr(d_records), int(entry), _ptr(d_out), int(out_cap),
+                                                   C.byref(n), C.byref(ex))
+        if rc:
+            e = PfacError(rc, (self._L.pfac_last_error(self._ctx) or b"").decode())
+            e.n_selected = n.value
+            raise e
+        return n.value, ex.value
+
+    def selection_to_host(self, n_selected: int, slot: int = 0) -> np.ndarray:
+        """The records of the slot's last ``select_leftmost_longest`` into its slot-owned buffer, ascending pos."""
+        rec = np.empty(int(n_selected), dtype=RECORD_DTYPE)
+        self._check(self._L.pfac_leftmost_longest_d2h(self._ctx, slot, rec.ctypes.data if n_selected else None))
+        self.sync(slot)
+        return rec
+
+    def scan_leftmost_longest(self, data, n_owned: Optional[int] = None, entry: int = 0,
+                              slot: int = 0) -> Tuple[np.ndarray, int]:
+        """H2D + scan + selection of one host buffer (``n_owned`` < len(data) leaves the rest as halo).  Returns
+        (records, exit): the leftmost-longest non-overlapping matches that start in the owned range, and the entry
+        offset for the scan of the range that follows."""
+        buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data.view(np.uint8).ravel()
+        n_avail = int(buf.size)
+        n_owned = n_avail if n_owned is None else int(n_owned)
+        self._ensure_final_lengths()
+        self.reserve(slot, max(n_avail, 1), max(n_avail // 8, 4096))
+        if n_avail:
+            self.h2d(buf, slot)
+        self.scan_resident(n_owned, n_avail, slot=slot)
+        n, ex = self.select_leftmost_longest(entry, slot=slot)
+        return self.selection_to_host(n, slot), ex
+
     # -- synthetic inputs (device resident) --------------------------------
     def fill_tiled(self, d_dst, n: int, pattern: bytes, phase: int = 0, slot: int = 0) -> None:
         pat = np.frombuffer(pattern, dtype=np.uint8)
