@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- input GB/s scanned by the PFAC hot path on N MI355X (BASELINE.json's metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--bytes-per-gpu B] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--bytes-per-gpu B] [--dump-outputs DIR] [--full]
 
 N > 1 works from a bare command line (the parent spawns one fresh process per GPU before anything touches a GPU) and
 under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` (RANK/LOCAL_RANK/WORLD_SIZE are
@@ -22,9 +22,16 @@ clocks ramp, with intermediate plateaus); its length and the cold figure are rep
 after it: on some boxes the governor needs longer than the settling launches, and the K timed steps should see the clock
 state a long job runs in, not the tail of the ramp.
 
-Parity, outside the timed region, for EVERY workload timed and on every rank: the GPU's (match count, record checksum) of
-the whole resident shard == one serial Aho-Corasick pass over the bytes copied back from HBM (tests/orc.py: ac_whole_shard),
-plus the records of the first 1 MiB one by one, in order, against the oracle's PFAC walk.
+A plain run does only what the headline figure needs: set up (table, resident input, record buffers, and the settling
+launches and sustained run that bring the card to the clock state the steps are timed in), the W warm-up and K timed
+steps, --dump-outputs if given, and the JSON line with `value`, `ms_per_step`, `roofline` (from the timed steps' own HIP
+events) and `sustained`.  --full adds everything else, each part outside the timed region: the parity check, the consumer
+costs (`config.*_ms`), `other_workloads`, `end_to_end` and the CPU baselines; --no-extra, --no-end-to-end,
+--no-cpu-baseline and --cpu-threads trim a --full run.
+
+Parity (--full), outside the timed region, for EVERY workload timed and on every rank: the GPU's (match count, record
+checksum) of the whole resident shard == one serial Aho-Corasick pass over the bytes copied back from HBM (tests/orc.py:
+ac_whole_shard), plus the records of the first 1 MiB one by one, in order, against the oracle's PFAC walk.
 
 --dump-outputs DIR writes, after the timed steps, what the last of them computed: its match count, the checksum of all its
 records and a seeded sample of the records, as float64 .npy files (dump_outputs, at most 24 MiB).  The inputs are the same
@@ -38,15 +45,15 @@ One JSON line is printed by rank 0 (contract in the task statement) with extra o
   sustained        the same scan back to back for --sustain-seconds (default 2.5 s, ~11 000 launches): mean / p5 / p50 / p95 of
                    the per-launch kernel rate and the wall-clock rate -- what a long job sees, next to the K-step `value`
                    (run before the W + K steps, see above)
-  end_to_end       BASELINE configs[2], PCIe inclusive: 4 GiB in pinned host memory -> four slots on four streams
+  end_to_end       (--full) BASELINE configs[2], PCIe inclusive: 4 GiB in pinned host memory -> four slots on four streams
                    (hipMemcpyAsync H2D || scan) -> counts (N = 1 only; never reported as `value`)
-  config.*_ms      what an ordered / host / text consumer pays on top of the scan, each outside the timed region: expand_ms
+  config.*_ms      (--full) what an ordered / host / text consumer pays on top of the scan, each outside the timed region: expand_ms
                    (heap -> sorted 8-byte records on the device), readback_ms (compact form D2H), emit_text_ms (GPU-side text
                    emitter), gather_ms (N > 1: compact records to rank 0 over RCCL)
-  cpu_baseline     serial Aho-Corasick (oracle/ac_serial.c, the CHECKER, kind "port") on ONE host core, bounded sample;
+  cpu_baseline     (--full) serial Aho-Corasick (oracle/ac_serial.c, the CHECKER, kind "port") on ONE host core, bounded sample;
                    cpu_baseline_pfac (the oracle's PFAC-on-CPU walk, one core) and cpu_baseline_threads (serial AC on
                    all the cores this process may use) next to it (N = 1 only)
-  other_workloads  short passes of the other BASELINE configurations' pattern sets / inputs (N = 1 only)
+  other_workloads  (--full) short passes of the other BASELINE configurations' pattern sets / inputs (N = 1 only)
 """
 import argparse
 import hashlib
@@ -307,12 +314,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default=HEADLINE, choices=sorted(WORKLOADS))
     ap.add_argument("--bytes-per-gpu", type=int, default=0, help="default: 1 GiB at --gpus 1, 4 GiB per GPU otherwise")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--extra", action="store_true", help="(default at --gpus 1) also time the other workloads (short)")
-    ap.add_argument("--no-extra", action="store_true", help="time the named workload only")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: parity, consumer costs, other workloads, end to end, CPU baselines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--extra", action="store_true", help="(default of --full at --gpus 1) also time the other workloads (short)")
+    ap.add_argument("--no-extra", action="store_true", help="--full without the other workloads")
     ap.add_argument("--sustain-seconds", type=float, default=2.5, help="length of the sustained back-to-back run reported beside the K-step value (0: skip)")
-    ap.add_argument("--no-end-to-end", action="store_true", help="skip the PCIe-inclusive config-3 run (4 GiB pinned host -> 4 slots)")
-    ap.add_argument("--cpu-threads", type=int, default=-1, help="threads of the all-cores CPU baseline (default: usable cores, at most 32; 0: skip)")
+    ap.add_argument("--no-end-to-end", action="store_true", help="--full without the PCIe-inclusive config-3 run (4 GiB pinned host -> 4 slots)")
+    ap.add_argument("--cpu-threads", type=int, default=-1, help="threads of the --full all-cores CPU baseline (default: usable cores, at most 32; 0: skip)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step computed to DIR/<name>.npy (float64, see dump_outputs)")
     args = ap.parse_args()
@@ -387,33 +396,35 @@ def main():
         _, _, used = g.scan_format(0)
         g.reserve(1, 0, max(cap, used + used // 8))
         assert g.scan_resident(n_owned, n_avail, d_input=buf, slot=1) == n
-        # Parity (outside the timed region), on the FULL-SIZE launch itself: the GPU's (match count, order-independent
-        # record checksum) of the WHOLE shard against one serial Aho-Corasick pass (oracle/ac_serial.c, the CHECKER) over
-        # the very bytes the kernel read, copied back from HBM -- every record of the shard enters the comparison.  The
-        # checksum cannot see order, so the records of the first 1 MiB are also compared one by one, in order, with the
-        # oracle's PFAC walk (in (position, length) order they are a prefix of the record sequence).
-        from orc import Oracle, ac_whole_shard
-        chk = g.checksum(n, base=lo, slot=1)
-        host = buf[:n_avail].cpu().numpy()
-        t_par = time.perf_counter()
-        cnt_o, chk_o = ac_whole_shard(ppath, host, n_owned=n_owned, base=lo)
-        t_par = time.perf_counter() - t_par
-        if (n, chk) != (cnt_o, chk_o):
-            raise SystemExit(f"rank {rank}: PARITY FAILURE on workload {name}: GPU (count, checksum) = ({n}, {chk:#x}), "
-                             f"serial Aho-Corasick over the same {n_avail} bytes = ({cnt_o}, {chk_o:#x})")
-        m = min(1 << 20, n_owned)
-        o = Oracle(ppath, 1, 1)
-        opos, oids = o.scan_spec(host[: min(n_avail, m + table.halo)], None)
-        keep = opos < m
-        opos, oids = opos[keep], oids[keep]
-        o.close()
-        del host
-        k = int(opos.size)
-        rec = g.records_to_host(min(n, k + 1), slot=1)
-        ok = n >= k and np.array_equal(rec["pos"][:k].astype(np.int64), opos) and \
-            np.array_equal(table.idmap[rec["state"][:k]], oids) and (n == k or int(rec["pos"][k]) >= m)
-        if not ok:
-            raise SystemExit(f"rank {rank}: PARITY FAILURE on workload {name}: first {k} records differ from the oracle")
+        t_par = None
+        if args.full:
+            # Parity (outside the timed region), on the FULL-SIZE launch itself: the GPU's (match count, order-independent
+            # record checksum) of the WHOLE shard against one serial Aho-Corasick pass (oracle/ac_serial.c, the CHECKER) over
+            # the very bytes the kernel read, copied back from HBM -- every record of the shard enters the comparison.  The
+            # checksum cannot see order, so the records of the first 1 MiB are also compared one by one, in order, with the
+            # oracle's PFAC walk (in (position, length) order they are a prefix of the record sequence).
+            from orc import Oracle, ac_whole_shard
+            chk = g.checksum(n, base=lo, slot=1)
+            host = buf[:n_avail].cpu().numpy()
+            t_par = time.perf_counter()
+            cnt_o, chk_o = ac_whole_shard(ppath, host, n_owned=n_owned, base=lo)
+            t_par = time.perf_counter() - t_par
+            if (n, chk) != (cnt_o, chk_o):
+                raise SystemExit(f"rank {rank}: PARITY FAILURE on workload {name}: GPU (count, checksum) = ({n}, {chk:#x}), "
+                                 f"serial Aho-Corasick over the same {n_avail} bytes = ({cnt_o}, {chk_o:#x})")
+            m = min(1 << 20, n_owned)
+            o = Oracle(ppath, 1, 1)
+            opos, oids = o.scan_spec(host[: min(n_avail, m + table.halo)], None)
+            keep = opos < m
+            opos, oids = opos[keep], oids[keep]
+            o.close()
+            del host
+            k = int(opos.size)
+            rec = g.records_to_host(min(n, k + 1), slot=1)
+            ok = n >= k and np.array_equal(rec["pos"][:k].astype(np.int64), opos) and \
+                np.array_equal(table.idmap[rec["state"][:k]], oids) and (n == k or int(rec["pos"][k]) >= m)
+            if not ok:
+                raise SystemExit(f"rank {rank}: PARITY FAILURE on workload {name}: first {k} records differ from the oracle")
 
         pending = []
         inflight = []                          # slots with an enqueued, not yet finished scan (depth <= 2)
@@ -521,18 +532,17 @@ def main():
                                  "the card's power/clock state over seconds is part of this figure"}
             res["sustained"] = sustained
         if headline:
+            rec_b, n_tiles, used = g.scan_format(1)
+            res.update(rec_bytes=rec_b, heap_used=used, n_tiles=n_tiles)
+        if headline and args.full:
             # What a consumer of ONE ordered record stream pays on top of the scan, reported next to the timed value:
             # heap -> sorted 8-byte records on the device (expand), and (N > 1) their ordered gather on rank 0.
-            rec_b, n_tiles, used = g.scan_format(1)
-            res["rec_bytes"] = rec_b
             wide = torch.empty(max(cnt, 1), dtype=torch.int64, device=dev)
             torch.cuda.synchronize()
             t1 = time.perf_counter()
             g.expand_records(cnt, wide, slot=1)
             g.sync(1)
             res["expand_ms"] = (time.perf_counter() - t1) * 1e3
-            res["heap_used"] = used
-            res["n_tiles"] = n_tiles
             del wide
             # D2H of the compact form itself (heap words + tile index into pinned host memory): what the CLI's emitter
             # and any host consumer reads back -- the counterpart of the reference's dense D2H (master_kernel.cu:428)
@@ -592,16 +602,9 @@ def main():
                    "matches_per_step": res["matches"], "record_bytes": rec_bytes,
                    "record_layout": "heap of compact records (pos:12 | final state, as wide as the automaton needs) + ordered tile index (8 B per 4 KiB tile)",
                    "parity": "whole shard: count + checksum == serial AC (every rank, over the bytes copied back from HBM); "
-                             "records of the first 1 MiB == CPU oracle in order, bit-exact",
+                             "records of the first 1 MiB == CPU oracle in order, bit-exact" if args.full else "not checked (see --full)",
                    "settle_launches": res["settle"], "cold_first20_gbs": round(res["n_owned"] / (res["cold_ms"] * 1e-3) / 1e9, 1),
                    "value_note": "steady state: K steps after the clock-settling launches and the sustained run; `sustained` is the same scan run back to back for seconds, every launch timed",
-                   "expand_ms": round(res["expand_ms"], 3),
-                   "expand_note": "heap -> one sorted pfac_record array on the device, outside the timed region (what an ordered consumer pays)",
-                   "readback_ms": round(res["readback_ms"], 3), "readback_bytes": res["readback_bytes"],
-                   **({"emit_text_ms": round(res["emit_text_ms"], 3), "emit_text_bytes": res["emit_text_bytes"],
-                       "emit_text_note": "GPU-side text emitter (pfac_emit_text_device): these records formatted into the lines of GPU_match_result.txt in device memory, outside the timed region"}
-                      if "emit_text_ms" in res else {}),
-                   "readback_note": "D2H of the compact form (record heap + tile index) into pinned host memory, outside the timed region (the reference's dense D2H, master_kernel.cu:428, made compact)",
                    "multi_gpu_note": "N > 1 numbers exist only where the driver ran them (SCALE_rNN.json): the builder's box has one GPU"},
         "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_note": traffic_note,
@@ -613,11 +616,21 @@ def main():
     }
     if "sustained" in res:
         out["sustained"] = res["sustained"]
+    if "expand_ms" in res:
+        out["config"].update({
+            "expand_ms": round(res["expand_ms"], 3),
+            "expand_note": "heap -> one sorted pfac_record array on the device, outside the timed region (what an ordered consumer pays)",
+            "readback_ms": round(res["readback_ms"], 3), "readback_bytes": res["readback_bytes"],
+            "readback_note": "D2H of the compact form (record heap + tile index) into pinned host memory, outside the timed region (the reference's dense D2H, master_kernel.cu:428, made compact)"})
+    if "emit_text_ms" in res:
+        out["config"].update({
+            "emit_text_ms": round(res["emit_text_ms"], 3), "emit_text_bytes": res["emit_text_bytes"],
+            "emit_text_note": "GPU-side text emitter (pfac_emit_text_device): these records formatted into the lines of GPU_match_result.txt in device memory, outside the timed region"})
     if "gather_ms" in res:
         out["config"]["gather_ms"] = round(res["gather_ms"], 3)
         out["config"]["gather_note"] = (f"ordered gather of {res.get('gather_records')} records to rank 0 in the COMPACT form the scan "
                                         f"wrote ({res.get('gather_bytes')} bytes: heap words + tile index, send/recv over RCCL), outside the timed region")
-    if world == 1 and not args.no_extra:
+    if args.full and world == 1 and not args.no_extra:
         out["other_workloads"] = {}
         for name in sorted(WORKLOADS):
             if name == args.workload:
@@ -629,9 +642,9 @@ def main():
                 "kernel_gbs": round(r["n_owned"] / (r["kernel_ms"] * 1e-3) / 1e9, 2),
                 "frac_of_hbm_peak": round(r["n_owned"] / (r["kernel_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
                 "steps": k, "matches_per_step": r["matches"], "kernel_variant": r["info"]["variant"]}
-    if world == 1 and not args.no_end_to_end and args.workload == HEADLINE:
+    if args.full and world == 1 and not args.no_end_to_end and args.workload == HEADLINE:
         out["end_to_end"] = config3_end_to_end(res["ppath"], para, local_rank)
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(res["ppath"], res["kind"], para)
         out["cpu_baseline_pfac"] = cpu_baseline_pfac(res["ppath"], res["kind"], para)
         nthr = min(usable_cores(), 32) if args.cpu_threads < 0 else args.cpu_threads

@@ -114,13 +114,14 @@ def test_gphf_several_workers_share_the_emitter(workers, streams, emit, resolve,
 def test_bench_rank_code_at_the_c4_shard_size(tmp_path):
     """Exactly what the driver's scaling run executes per rank: `bench.py --gpus 1` with the RCCL path forced
     (table broadcast, count all-gather, compact record gather) at the C4 / C5 shard size of 4 GiB per GPU.  Its own
-    whole-shard parity check (count + checksum == serial Aho-Corasick over the 4 GiB copied back) must pass."""
+    whole-shard parity check (count + checksum == serial Aho-Corasick over the 4 GiB copied back) must pass; the
+    check and the record gather run under --full."""
     import subprocess
     import sys
     repo = os.path.dirname(HERE)
     env = dict(os.environ, PFAC_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29547")
     r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-                        "--bytes-per-gpu", str(1 << 32), "--no-cpu-baseline", "--no-extra", "--no-end-to-end", "--sustain-seconds", "0.5"], env=env, cwd=tmp_path,
+                        "--bytes-per-gpu", str(1 << 32), "--full", "--no-cpu-baseline", "--no-extra", "--no-end-to-end", "--sustain-seconds", "0.5"], env=env, cwd=tmp_path,
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
