@@ -367,6 +367,37 @@ int pfac_records_leftmost_longest(pfac_ctx *ctx, int slot, const void *d_records
  * slot's stream; pfac_slot_sync completes it. */
 int pfac_leftmost_longest_d2h(pfac_ctx *ctx, int slot, pfac_record *host);
 
+/* Find-and-replace over the leftmost-longest selection.  Every final state s gets a replacement: bytes[offsets[s] ..
+ * offsets[s+1]) (offsets holds n_states + 1 ascending entries, the last <= n_bytes < 2^32; n_states must equal num_final
+ * of the uploaded table, else PFAC_E_ARG).  One replacement is at most PFAC_MAX_REPLACEMENT bytes (else PFAC_E_ARG).
+ * The replacement of a pattern id goes to its state through idmap: for duplicate lines the state of the line that wins,
+ * for character-class tables the state's first (lowest) id; unreachable states may be empty.  Kept on the device until
+ * the next table upload clears them, like the final lengths. */
+#define PFAC_MAX_REPLACEMENT 65536u
+int pfac_table_set_replacements(pfac_ctx *ctx, const uint32_t *offsets, uint64_t n_states, const void *bytes, uint64_t n_bytes);
+/* Rewrites the slot's last scan with its last leftmost-longest selection (picks (p_k, s_k), made from `entry`, ending in
+ * `exit`; L_k = the final length of s_k, R_k = its replacement):
+ *   input[entry : p_0] + R_0 + input[p_0 + L_0 : p_1] + R_1 + ... + R_{n-1} + input[p_{n-1} + L_{n-1} : n_owned]
+ * (a slice with end <= start is empty; no picks: input[entry : n_owned]).  *out_bytes = n_owned + exit - entry +
+ * sum_k (R_k - L_k).  Chained ranges (entry = the previous range's exit) concatenate to the output of one scan of all.
+ *   d_input  NULL = the slot's input buffer; else the buffer the scan read (16-B aligned)
+ *   d_sel    NULL = the slot-owned selection; else the caller's d_out of pfac_records_leftmost_longest
+ *   d_out    NULL = a slot-owned buffer grown to fit (fetched with pfac_replace_d2h); else a device pointer, 16-B aligned,
+ *            of out_cap bytes.  No byte at or past *out_bytes is written.
+ * Returns once *out_bytes is known; the writes are asynchronous on the slot's stream.  PFAC_E_OVERFLOW (with *out_bytes
+ * exact, nothing written) when out_cap is too small for a caller's d_out.  PFAC_E_STATE without a selection since the
+ * slot's last scan, for a selection made with an earlier table, or without replacements or final lengths for the current
+ * table.  PFAC_E_ARG for misaligned buffers or a d_sel that is not the selection of this scan.
+ * Kernels: a count pass sums R_k - L_k per 1024 picks (and per block of 64), the group prefix, then an output-driven
+ * write: each wave finds the block of its first output byte by a 64-ary search over the block offsets, rebuilds the
+ * block's segment offsets with a wave prefix and assembles 16 output bytes per lane in registers (one dwordx4 store;
+ * only the last partial 16 B of the output is stored in pieces).  Input reads stay inside [0, n_avail) of the scan. */
+int pfac_replace_leftmost_longest(pfac_ctx *ctx, int slot, const void *d_input, const pfac_record *d_sel, void *d_out,
+                                  uint64_t out_cap, uint64_t *out_bytes);
+/* D2H of bytes [first, first + n) of the slot-owned output of the last pfac_replace_leftmost_longest.  Asynchronous on
+ * the slot's stream; pfac_slot_sync completes it. */
+int pfac_replace_d2h(pfac_ctx *ctx, int slot, void *host, uint64_t first, uint64_t n);
+
 /* Synthetic input generators, written straight into device memory (the
  * reference built big inputs by tiling a small text, creatbiginput.sh:2-5).
  *   tiled : byte i = pattern[(phase + i) % period]

@@ -86,6 +86,7 @@ HIP_SYMBOLS = (
     "pfac_emit_text_device", "pfac_text_d2h", "pfac_slot_text", "pfac_slot_h2d_wait", "pfac_slot_h2d_done", "pfac_host_register", "pfac_host_unregister",
     "pfac_table_set_final_lengths", "pfac_slot_doc_offsets", "pfac_records_segment", "pfac_segment_d2h",
     "pfac_records_leftmost_longest", "pfac_leftmost_longest_d2h",
+    "pfac_table_set_replacements", "pfac_replace_leftmost_longest", "pfac_replace_d2h",
 )
 
 _host = None
@@ -205,5 +206,8 @@ def hip_lib() -> C.CDLL:
         L.pfac_segment_d2h.argtypes = [vp, i, vp, vp]
         L.pfac_records_leftmost_longest.argtypes = [vp, i, vp, C.c_uint32, vp, u64, C.POINTER(u64), C.POINTER(C.c_uint32)]
         L.pfac_leftmost_longest_d2h.argtypes = [vp, i, vp]
+        L.pfac_table_set_replacements.argtypes = [vp, vp, u64, vp, u64]
+        L.pfac_replace_leftmost_longest.argtypes = [vp, i, vp, vp, vp, u64, C.POINTER(u64)]
+        L.pfac_replace_d2h.argtypes = [vp, i, vp, u64, u64]
         _hip = L
     return _hip

@@ -2531,6 +2531,272 @@ __global__ void pfac_ll_write_kernel(const void *rec, const unsigned long long *
 }
 
 // ---------------------------------------------------------------------------
+// Find-and-replace over the leftmost-longest selection (pfac_replace_leftmost_longest).  Picks (p_k, s_k) of the slot's
+// last selection, L_k = flen[s_k], R_k = the replacement of s_k; c_{-1} = entry, c_k = p_k + L_k.  Segment k < n is the
+// input gap [c_{k-1}, p_k) followed by R_k; segment n is the gap [c_{n-1}, n_owned) (empty when c_{n-1} >= n_owned).
+// Segment k starts at output offset O_k = c_{k-1} - entry + D_k, D_k = sum_{j<k} (R_j - L_j).
+//   pfac_rp_count_kernel     one workgroup per 1024 picks: per block of 64 picks X[b] = O_{64b} minus the group's
+//                            prefix; the group's delta sum; checks the selection against the table and the scan
+//   pfac_scan_groups_kernel  the group prefixes and the total delta, which give out_bytes on the host
+//   pfac_rp_write_kernel     output-driven: each wave owns `wins` windows of 1 KiB, one 16-B chunk per lane.  The block
+//                            that holds a byte is found by a 64-ary search over O_{64b} (ballot over 64 probes per
+//                            round); a block's 64 segment offsets are rebuilt with a wave prefix into LDS; each lane
+//                            merges the pieces of its chunk in registers and stores it with one dwordx4.
+// Blocks whose segments are all empty (deletions with no gap between them) are never loaded: after a block the next
+// one is found by galloping from it, so a window costs its bytes times a log factor, whatever collapses into it.
+
+constexpr int RP_BLOCK = 64;                        // picks per block (one wave)
+constexpr int RP_GROUP = 16;                        // blocks per workgroup of the count kernel (1024 picks)
+constexpr int RP_WIN = 16 * WAVE;                   // output bytes per window (16 per lane)
+constexpr int RP_WAVES = 4;                         // waves per workgroup of the write kernel
+
+__device__ __forceinline__ unsigned long long wave_incl_scan64(unsigned long long x) {
+    const int lane = threadIdx.x & (WAVE - 1);
+#pragma unroll
+    for (int d = 1; d < WAVE; d <<= 1) {
+        const unsigned long long t = __shfl_up(x, (unsigned)d, WAVE);
+        if (lane >= d) x += t;
+    }
+    return x;
+}
+
+__global__ void __launch_bounds__(RP_GROUP / 4 * WAVE)
+pfac_rp_count_kernel(const pfac_record *sel, unsigned long long n, unsigned long long entry, unsigned long long n_owned,
+                     const short *flen, const unsigned *roff, unsigned num_final, unsigned long long *X,
+                     unsigned long long *gsum, unsigned long long *res) {
+    __shared__ unsigned long long bsum[RP_GROUP];
+    __shared__ unsigned long long cst[RP_GROUP];
+    const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x >> 6;
+    const unsigned long long nb = (n + RP_BLOCK - 1) / RP_BLOCK;
+    bool bad = false;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const unsigned lb = (unsigned)w * 4 + (unsigned)i;
+        const unsigned long long b = (unsigned long long)blockIdx.x * RP_GROUP + lb;
+        const unsigned long long k = b * RP_BLOCK + (unsigned)lane;
+        const bool v = k < n;
+        unsigned long long p = 0, end = 0, d = 0;
+        if (v) {
+            const pfac_record r = sel[k];
+            p = r.pos;
+            if (r.state < num_final) {
+                const int L = flen[r.state];
+                const unsigned R = roff[r.state + 1] - roff[r.state];
+                end = p + (unsigned long long)(L > 0 ? L : 0);
+                d = (unsigned long long)((long long)R - (long long)L);   // (two's complement: sums wrap correctly)
+                bad |= L < 1;
+            } else {
+                bad = true;
+            }
+            bad |= p >= n_owned;
+        }
+        unsigned long long prev = __shfl_up(end, 1u, WAVE);
+        if (lane == 0) {
+            prev = entry;
+            if (v && k > 0) {
+                const pfac_record r = sel[k - 1];
+                if (r.state < num_final) {
+                    const int L = flen[r.state];
+                    prev = (unsigned long long)r.pos + (unsigned long long)(L > 0 ? L : 0);
+                }
+            }
+        }
+        if (v) {
+            bad |= p < prev;
+            if (k + 1 == n) res[1] = end;                  // c_{n-1}
+        }
+        const unsigned long long s = wave_sum64(d);
+        if (lane == 0) { bsum[lb] = s; cst[lb] = prev; }
+    }
+    if (__ballot(bad) && lane == 0) atomicOr(&res[0], 1ull);
+    __syncthreads();
+    if (threadIdx.x < RP_GROUP) {
+        const unsigned long long b = (unsigned long long)blockIdx.x * RP_GROUP + threadIdx.x;
+        unsigned long long pre = 0;
+        for (unsigned j = 0; j < threadIdx.x; j++) pre += bsum[j];
+        if (b < nb) X[b] = cst[threadIdx.x] - entry + pre;
+        if (threadIdx.x == RP_GROUP - 1) gsum[blockIdx.x] = pre + bsum[RP_GROUP - 1];
+    }
+}
+
+// O_{64b}: the output offset of block b's first segment (b < nb)
+__device__ __forceinline__ unsigned long long rp_block_out(const unsigned long long *X, const unsigned long long *gpre,
+                                                           unsigned long long b) {
+    return b == 0 ? 0ull : X[b] + gpre[b / RP_GROUP];
+}
+
+// the last block b in [lo, nb) with O_{64b} <= x, given O_{64 lo} <= x (wave-uniform): gallop, then narrow, 64 probes a round
+__device__ unsigned long long rp_find(const unsigned long long *X, const unsigned long long *gpre, unsigned long long nb,
+                                      unsigned long long lo, unsigned long long x) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    unsigned long long stride = 1;
+    for (;;) {
+        const unsigned long long idx = lo + (unsigned long long)(lane + 1) * stride;
+        const bool t = idx < nb && rp_block_out(X, gpre, idx) <= x;
+        const unsigned c = (unsigned)__popcll(__ballot(t));
+        if (c < (unsigned)WAVE) { lo += c * stride; break; }
+        lo += (unsigned long long)WAVE * stride;
+        stride *= WAVE;
+    }
+    while (stride > 1) {                                    // the answer lies in [lo, lo + stride)
+        stride /= WAVE;
+        const unsigned long long idx = lo + (unsigned long long)(lane + 1) * stride;
+        const bool t = idx < nb && rp_block_out(X, gpre, idx) <= x;
+        lo += (unsigned)__popcll(__ballot(t)) * stride;
+    }
+    return lo;
+}
+
+// 16 bytes at buf[a, a + 16), aligned a; bytes outside [0, size) read as 0 (only the chunks at the ends take the slow path)
+__device__ __forceinline__ uint4 rp_half(const unsigned char *buf, long long a, unsigned long long size) {
+    if (a >= 0 && (unsigned long long)a + 16 <= size) return *reinterpret_cast<const uint4 *>(buf + a);
+    unsigned v[4] = {0u, 0u, 0u, 0u};
+    if (a + 16 > 0 && a < (long long)size) {
+#pragma unroll
+        for (int i = 0; i < 16; i++) {
+            const long long j = a + i;
+            if (j >= 0 && (unsigned long long)j < size) v[i >> 2] |= (unsigned)buf[j] << (8 * (i & 3));
+        }
+    }
+    return make_uint4(v[0], v[1], v[2], v[3]);
+}
+
+// acc bytes [j0, j1) := buf[a + j0, a + j1) (a may lie before the buffer: only bytes inside it are needed)
+__device__ __forceinline__ void rp_merge(uint4 &acc, const unsigned char *buf, long long a, unsigned long long size,
+                                         unsigned j0, unsigned j1) {
+    const unsigned sh = (unsigned)(a & 15);
+    const long long a0 = a - (long long)sh;
+    const uint4 h0 = rp_half(buf, a0, size);
+    const uint4 h1 = sh ? rp_half(buf, a0 + 16, size) : make_uint4(0u, 0u, 0u, 0u);
+    const unsigned q = sh >> 2, r = sh & 3;
+    const unsigned e0 = q == 0 ? h0.x : q == 1 ? h0.y : q == 2 ? h0.z : h0.w;
+    const unsigned e1 = q == 0 ? h0.y : q == 1 ? h0.z : q == 2 ? h0.w : h1.x;
+    const unsigned e2 = q == 0 ? h0.z : q == 1 ? h0.w : q == 2 ? h1.x : h1.y;
+    const unsigned e3 = q == 0 ? h0.w : q == 1 ? h1.x : q == 2 ? h1.y : h1.z;
+    const unsigned e4 = q == 0 ? h1.x : q == 1 ? h1.y : q == 2 ? h1.z : h1.w;
+    const unsigned v0 = __builtin_amdgcn_alignbyte(e1, e0, r), v1 = __builtin_amdgcn_alignbyte(e2, e1, r);
+    const unsigned v2 = __builtin_amdgcn_alignbyte(e3, e2, r), v3 = __builtin_amdgcn_alignbyte(e4, e3, r);
+    auto low = [](int m) -> unsigned { return m <= 0 ? 0u : m >= 4 ? 0xffffffffu : (1u << (8 * m)) - 1u; };
+    const unsigned m0 = low((int)j1) & ~low((int)j0), m1 = low((int)j1 - 4) & ~low((int)j0 - 4);
+    const unsigned m2 = low((int)j1 - 8) & ~low((int)j0 - 8), m3 = low((int)j1 - 12) & ~low((int)j0 - 12);
+    acc.x = (acc.x & ~m0) | (v0 & m0);
+    acc.y = (acc.y & ~m1) | (v1 & m1);
+    acc.z = (acc.z & ~m2) | (v2 & m2);
+    acc.w = (acc.w & ~m3) | (v3 & m3);
+}
+
+__global__ void __launch_bounds__(RP_WAVES * WAVE)
+pfac_rp_write_kernel(const unsigned char *in, unsigned long long n_avail, const pfac_record *sel, unsigned long long n,
+                     unsigned long long entry, const short *flen, const unsigned *roff, const unsigned char *rep,
+                     unsigned long long rep_size, const unsigned long long *X, const unsigned long long *gpre,
+                     unsigned long long out_bytes, unsigned wins, unsigned char *out) {
+    __shared__ unsigned long long s_o[RP_WAVES][RP_BLOCK + 1];      // segment k's output offset (k = cnt: the tail entry)
+    __shared__ unsigned long long s_src[RP_WAVES][RP_BLOCK + 1];    // c_{k-1}: where its gap starts in the input
+    __shared__ unsigned long long s_glen[RP_WAVES][RP_BLOCK + 1];   // its gap's length
+    __shared__ unsigned s_roff[RP_WAVES][RP_BLOCK];                 // its replacement's offset in rep
+    const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x >> 6;
+    const unsigned long long A = ((unsigned long long)blockIdx.x * RP_WAVES + (unsigned)w) * wins * RP_WIN;
+    if (A >= out_bytes) return;
+    const unsigned long long nb = n ? (n + RP_BLOCK - 1) / RP_BLOCK : 1;
+    unsigned long long *so = s_o[w], *ssrc = s_src[w], *sgl = s_glen[w];
+    unsigned *sro = s_roff[w];
+    unsigned long long b = rp_find(X, gpre, nb, 0, A);
+    unsigned long long Ob = 0, hi = 0;
+    unsigned cnt = 0;
+    auto load_block = [&]() {
+        const unsigned long long k = b * RP_BLOCK + (unsigned)lane;
+        const bool v = k < n;
+        unsigned long long p = 0, end = 0;
+        unsigned ro = 0, R = 0;
+        if (v) {
+            const pfac_record r = sel[k];
+            p = r.pos;
+            end = p + (unsigned long long)flen[r.state];
+            ro = roff[r.state];
+            R = roff[r.state + 1] - ro;
+        }
+        unsigned long long prev = __shfl_up(end, 1u, WAVE);
+        if (lane == 0) {
+            prev = entry;
+            if (b > 0) {
+                const pfac_record r = sel[k - 1];
+                prev = (unsigned long long)r.pos + (unsigned long long)flen[r.state];
+            }
+        }
+        const unsigned long long G = v ? p - prev : 0ull;
+        const unsigned long long seg = v ? G + R : 0ull;
+        const unsigned long long incl = wave_incl_scan64(seg);
+        Ob = rp_block_out(X, gpre, b);
+        cnt = (unsigned)min((unsigned long long)RP_BLOCK, n - min(n, b * RP_BLOCK));
+        if (v) {
+            so[lane] = Ob + incl - seg;
+            ssrc[lane] = prev;
+            sgl[lane] = G;
+            sro[lane] = ro;
+        }
+        const unsigned long long oT = Ob + (cnt ? __shfl(incl, (int)cnt - 1, WAVE) : 0ull);
+        const unsigned long long cT = cnt ? __shfl(end, (int)cnt - 1, WAVE) : __shfl(prev, 0, WAVE);
+        const bool last = b + 1 == nb;
+        if (lane == 0) {
+            so[cnt] = oT;
+            ssrc[cnt] = cT;
+            sgl[cnt] = last ? out_bytes - oT : 0ull;
+        }
+        hi = last ? out_bytes : oT;
+        wave_lds_sync();
+    };
+    load_block();
+    for (unsigned wi = 0; wi < wins; wi++) {
+        const unsigned long long W = A + (unsigned long long)wi * RP_WIN;
+        if (W >= out_bytes) break;
+        const unsigned long long o = W + 16ull * (unsigned)lane;
+        uint4 acc = make_uint4(0u, 0u, 0u, 0u);
+        for (;;) {
+            const unsigned long long e = min(o + 16, hi);
+            unsigned long long pos = max(o, Ob);
+            while (pos < e) {
+                unsigned l = 0, h = cnt + 1;                    // the last segment k with so[k] <= pos
+                while (h - l > 1) {
+                    const unsigned m = (l + h) >> 1;
+                    if (so[m] <= pos) l = m;
+                    else h = m;
+                }
+                const unsigned long long gs = so[l], ge = gs + sgl[l];
+                unsigned long long pe;
+                if (pos < ge) {                                 // the input gap
+                    pe = min(ge, e);
+                    rp_merge(acc, in, (long long)(ssrc[l] + o - gs), n_avail, (unsigned)(pos - o), (unsigned)(pe - o));
+                } else {                                        // the replacement (l < cnt here)
+                    pe = min(so[l + 1], e);
+                    rp_merge(acc, rep, (long long)sro[l] + (long long)(o - ge), rep_size, (unsigned)(pos - o), (unsigned)(pe - o));
+                }
+                pos = pe;
+            }
+            if (hi >= W + RP_WIN || hi >= out_bytes) break;
+            b = rp_find(X, gpre, nb, b + 1, hi);
+            wave_lds_sync();                                    // (every lane is done with the old block)
+            load_block();
+        }
+        if (o + 16 <= out_bytes) {
+            *reinterpret_cast<uint4 *>(out + o) = acc;
+        } else if (o < out_bytes) {                             // the last partial 16 B of the whole output
+            const unsigned m = (unsigned)(out_bytes - o);
+            const unsigned v[4] = {acc.x, acc.y, acc.z, acc.w};
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                if ((unsigned)(4 * i + 4) <= m) {
+                    *reinterpret_cast<unsigned *>(out + o + 4 * i) = v[i];
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; j++)
+                        if ((unsigned)(4 * i + j) < m) out[o + 4 * i + j] = (unsigned char)(v[i] >> (8 * j));
+                }
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // GPU-side text emitter (replaces the fprintf loop of main.cc:335-350 on the device): the compact records of a scan ->
 // the lines  "At position %4d, match pattern %d\n"  in output order, in one device buffer.  Three kernels: bytes per
 // group of 64 tiles (line length depends on the digit counts), exclusive scan of the group sums (pfac_scan_groups_kernel),
@@ -2747,6 +3013,16 @@ struct Slot {
     pfac_record *d_ll_out = nullptr;      // slot-owned selection (d_out NULL)
     uint64_t ll_out_cap = 0, ll_n = 0;
     bool ll_done = false, ll_own_out = false;
+    uint64_t ll_seq = 0;                  // the scan it selected from (scan_seq), ...
+    uint32_t ll_entry = 0, ll_exit = 0;   // ... and its entry and exit offsets
+    // pfac_replace_leftmost_longest
+    uint64_t last_avail = 0;              // n_avail of the slot's last scan (the input bytes it may read)
+    uint64_t scan_seq = 0;                // scans issued on this slot
+    unsigned char *d_rp_tmp = nullptr;    // X per block of 64 picks
+    uint64_t rp_tmp_cap = 0;
+    unsigned char *d_rp_out = nullptr;    // slot-owned output (d_out NULL)
+    uint64_t rp_out_cap = 0, rp_bytes = 0;
+    bool rp_done = false, rp_own_out = false;
 };
 
 }  // namespace
@@ -2797,6 +3073,9 @@ struct pfac_ctx {
     int grid_blocks = 0;
     int rec_bytes = 4;                    // record form: 2 (<= 16 final states), 4 (<= 2^20), 8 bytes (pfac_record)
     short *d_flen = nullptr;              // pattern length of every final state (pfac_table_set_final_lengths), cleared by an upload
+    unsigned *d_rep_off = nullptr;        // replacement of every final state (pfac_table_set_replacements): offsets[num_final + 1]
+    unsigned char *d_rep = nullptr;       // ... and the bytes, zero-padded to rep_size (a multiple of 16); cleared by an upload
+    uint64_t rep_size = 0;
     uint64_t table_gen = 0;               // tables installed so far: a scan's final states index the lengths of ITS table only
     // level-2 filter (ScanArgs::l2f_mode)
     unsigned char *d_bm2 = nullptr;       // 2-byte-prefix bitmap, 256 rows of 32 bytes
@@ -3175,6 +3454,8 @@ int install_table(pfac_ctx *ctx, const int *d_blob, const int32_t *hdr, size_t n
     const size_t total = align_up(off_id + (size_t)num_final * 4, 16) + 16;
     if (ctx->d_tab) { HIP_TRY(ctx, hipFree(ctx->d_tab)); ctx->d_tab = nullptr; }
     if (ctx->d_flen) { HIP_TRY(ctx, hipFree(ctx->d_flen)); ctx->d_flen = nullptr; }   // the lengths belong to the old table
+    if (ctx->d_rep_off) { HIP_TRY(ctx, hipFree(ctx->d_rep_off)); ctx->d_rep_off = nullptr; }   // ... and so do the replacements
+    if (ctx->d_rep) { HIP_TRY(ctx, hipFree(ctx->d_rep)); ctx->d_rep = nullptr; ctx->rep_size = 0; }
     HIP_TRY(ctx, hipMalloc((void **)&ctx->d_tab, total));
     ctx->tab_bytes = total;
     unsigned char *base = reinterpret_cast<unsigned char *>(ctx->d_tab);
@@ -3267,6 +3548,8 @@ void pfac_ctx_destroy(pfac_ctx *ctx) {
         if (s.d_seg_first) (void)hipFree(s.d_seg_first);
         if (s.d_ll_tmp) (void)hipFree(s.d_ll_tmp);
         if (s.d_ll_out) (void)hipFree(s.d_ll_out);
+        if (s.d_rp_tmp) (void)hipFree(s.d_rp_tmp);
+        if (s.d_rp_out) (void)hipFree(s.d_rp_out);
         if (s.d_sum) (void)hipFree(s.d_sum);
         if (s.h_ctl) (void)hipHostFree(s.h_ctl);
         if (s.ev0) (void)hipEventDestroy(s.ev0);
@@ -3280,6 +3563,8 @@ void pfac_ctx_destroy(pfac_ctx *ctx) {
     if (ctx->d_T4_alloc) (void)hipFree(ctx->d_T4_alloc);
     if (ctx->d_bm2) (void)hipFree(ctx->d_bm2);
     if (ctx->d_flen) (void)hipFree(ctx->d_flen);
+    if (ctx->d_rep_off) (void)hipFree(ctx->d_rep_off);
+    if (ctx->d_rep) (void)hipFree(ctx->d_rep);
     delete ctx;
 }
 
@@ -3424,6 +3709,8 @@ int pfac_scan_async(pfac_ctx *ctx, int slot, const void *d_input, uint64_t n_own
     s.last_dense = dense;
     s.last_tiles = n_tiles;
     s.last_owned = n_owned;
+    s.last_avail = n_avail;
+    s.scan_seq++;
     s.last_table = ctx->table_gen;
     s.last_rec_bytes = ctx->rec_bytes;
     s.last_records = d_records;
@@ -3940,8 +4227,11 @@ int pfac_records_leftmost_longest(pfac_ctx *ctx, int slot, const void *d_records
     USE_DEVICE(ctx);
     const uint64_t n_tiles = s.last_tiles;
     const bool own_out = d_out == nullptr;
+    s.ll_seq = s.scan_seq;
+    s.ll_entry = entry;
     if (n_tiles == 0) {                                     // nothing scanned: nothing picked, the cursor stays
         s.ll_n = 0;
+        s.ll_exit = entry;
         s.ll_own_out = own_out;
         s.ll_done = true;
         return PFAC_OK;
@@ -4003,6 +4293,7 @@ int pfac_records_leftmost_longest(pfac_ctx *ctx, int slot, const void *d_records
         HIP_TRY(ctx, hipGetLastError());
     }
     s.ll_n = total;
+    s.ll_exit = *exit_offset;
     s.ll_own_out = own_out;
     s.ll_done = true;
     return PFAC_OK;
@@ -4017,6 +4308,134 @@ int pfac_leftmost_longest_d2h(pfac_ctx *ctx, int slot, pfac_record *host) {
     if (!host && s.ll_n) return fail(ctx, PFAC_E_ARG, "null host buffer");
     USE_DEVICE(ctx);
     if (s.ll_n) HIP_TRY(ctx, hipMemcpyAsync(host, s.d_ll_out, s.ll_n * sizeof(pfac_record), hipMemcpyDeviceToHost, s.stream));
+    return PFAC_OK;
+}
+
+int pfac_table_set_replacements(pfac_ctx *ctx, const uint32_t *offsets, uint64_t n_states, const void *bytes, uint64_t n_bytes) {
+    if (!ctx) return fail(nullptr, PFAC_E_ARG, "null context");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (!ctx->have_table) return fail(ctx, PFAC_E_STATE, "pfac_table_set_replacements before a table upload");
+    if (n_states != (uint64_t)ctx->num_final || !offsets || (!bytes && n_bytes))
+        return fail(ctx, PFAC_E_ARG, "pfac_table_set_replacements: need num_final + 1 offsets (num_final " + std::to_string(ctx->num_final) + ")");
+    if (n_bytes >= (1ull << 32)) return fail(ctx, PFAC_E_ARG, "pfac_table_set_replacements: n_bytes must be below 2^32");
+    for (uint64_t i = 0; i < n_states; i++) {
+        if (offsets[i + 1] < offsets[i] || offsets[i + 1] > n_bytes)
+            return fail(ctx, PFAC_E_ARG, "pfac_table_set_replacements: offsets must ascend within n_bytes (final state " + std::to_string(i) + ")");
+        if (offsets[i + 1] - offsets[i] > PFAC_MAX_REPLACEMENT)
+            return fail(ctx, PFAC_E_ARG, "pfac_table_set_replacements: the replacement of final state " + std::to_string(i) + " exceeds " +
+                                             std::to_string(PFAC_MAX_REPLACEMENT) + " bytes");
+    }
+    USE_DEVICE(ctx);
+    if (ctx->d_rep_off) { HIP_TRY(ctx, hipFree(ctx->d_rep_off)); ctx->d_rep_off = nullptr; }
+    if (ctx->d_rep) { HIP_TRY(ctx, hipFree(ctx->d_rep)); ctx->d_rep = nullptr; ctx->rep_size = 0; }
+    const uint64_t size = align_up(n_bytes, 16) + 16;
+    HIP_TRY(ctx, hipMalloc((void **)&ctx->d_rep_off, (n_states + 1) * 4));
+    HIP_TRY(ctx, hipMalloc((void **)&ctx->d_rep, size));
+    HIP_TRY(ctx, hipMemset(ctx->d_rep, 0, size));
+    HIP_TRY(ctx, hipMemcpy(ctx->d_rep_off, offsets, (n_states + 1) * 4, hipMemcpyHostToDevice));
+    if (n_bytes) HIP_TRY(ctx, hipMemcpy(ctx->d_rep, bytes, n_bytes, hipMemcpyHostToDevice));
+    ctx->rep_size = size;
+    return PFAC_OK;
+}
+
+int pfac_replace_leftmost_longest(pfac_ctx *ctx, int slot, const void *d_input, const pfac_record *d_sel, void *d_out,
+                                  uint64_t out_cap, uint64_t *out_bytes) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    if (!out_bytes) return fail(ctx, PFAC_E_ARG, "null argument");
+    *out_bytes = 0;
+    Slot &s = ctx->slots[slot];
+    s.rp_done = false;
+    if (!s.ll_done || s.ll_seq != s.scan_seq)
+        return fail(ctx, PFAC_E_STATE, "pfac_replace_leftmost_longest needs a pfac_records_leftmost_longest since the slot's last scan");
+    if (!ctx->have_table || s.last_table != ctx->table_gen)
+        return fail(ctx, PFAC_E_STATE, "pfac_replace_leftmost_longest: the selection was made with an earlier table");
+    if (!ctx->d_rep) return fail(ctx, PFAC_E_STATE, "pfac_replace_leftmost_longest: no replacements for the uploaded table (pfac_table_set_replacements)");
+    if (!ctx->d_flen) return fail(ctx, PFAC_E_STATE, "pfac_replace_leftmost_longest: no final-state lengths for the uploaded table");
+    if (!d_sel && !s.ll_own_out)
+        return fail(ctx, PFAC_E_STATE, "pfac_replace_leftmost_longest: the selection went to the caller's buffer; pass it as d_sel");
+    const pfac_record *sel = d_sel ? d_sel : s.d_ll_out;
+    const unsigned char *in = d_input ? static_cast<const unsigned char *>(d_input) : s.d_input;
+    const uint64_t n = s.ll_n, n_owned = s.last_owned, n_avail = s.last_avail, entry = s.ll_entry, ex = s.ll_exit;
+    if (((uintptr_t)d_out & 15) || ((uintptr_t)in & 15) || ((uintptr_t)d_sel & 7))
+        return fail(ctx, PFAC_E_ARG, "pfac_replace_leftmost_longest: misaligned buffer (d_input and d_out 16 B, d_sel 8 B)");
+    if (n_owned > entry && !in) return fail(ctx, PFAC_E_ARG, "pfac_replace_leftmost_longest: no input buffer");
+    if (!d_input && n_avail > s.input_cap) return fail(ctx, PFAC_E_ARG, "pfac_replace_leftmost_longest: the scan read more than the slot's input buffer holds");
+    USE_DEVICE(ctx);
+    int64_t delta = 0;
+    const uint64_t nb = n ? (n + RP_BLOCK - 1) / RP_BLOCK : 1;
+    const uint64_t n_groups = (nb + RP_GROUP - 1) / RP_GROUP;
+    if (n_groups >= (1ull << 32)) return fail(ctx, PFAC_E_ARG, "pfac_replace_leftmost_longest: too many picks");
+    unsigned long long *X = nullptr;
+    if (n) {
+        const size_t need = nb * 8;
+        if (need > s.rp_tmp_cap) {
+            if (s.d_rp_tmp) { HIP_TRY(ctx, hipStreamSynchronize(s.stream)); HIP_TRY(ctx, hipFree(s.d_rp_tmp)); s.d_rp_tmp = nullptr; s.rp_tmp_cap = 0; }
+            const uint64_t cap = need + need / 4 + 4096;
+            HIP_TRY(ctx, hipMalloc((void **)&s.d_rp_tmp, cap));
+            s.rp_tmp_cap = cap;
+        }
+        X = reinterpret_cast<unsigned long long *>(s.d_rp_tmp);
+        rc = ensure_gsum(ctx, s, (unsigned)n_groups + 2);       // group prefixes, the total delta, error flag, c_{n-1}
+        if (rc) return rc;
+        unsigned long long *res = s.d_gsum + n_groups + 1;
+        HIP_TRY(ctx, hipMemsetAsync(res, 0, 16, s.stream));
+        hipLaunchKernelGGL(pfac_rp_count_kernel, dim3((unsigned)n_groups), dim3(RP_GROUP / 4 * WAVE), 0, s.stream, sel,
+                           (unsigned long long)n, (unsigned long long)entry, (unsigned long long)n_owned, ctx->d_flen,
+                           ctx->d_rep_off, (unsigned)ctx->num_final, X, s.d_gsum, res);
+        hipLaunchKernelGGL(pfac_scan_groups_kernel, dim3(1), dim3(1024), 0, s.stream, s.d_gsum, (unsigned)n_groups);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(s.h_ctl + 10, s.d_gsum + n_groups, 24, hipMemcpyDeviceToHost, s.stream));
+        HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+        delta = (int64_t)(((uint64_t)s.h_ctl[11] << 32) | s.h_ctl[10]);
+        const uint64_t err = ((uint64_t)s.h_ctl[13] << 32) | s.h_ctl[12];
+        const uint64_t c_last = ((uint64_t)s.h_ctl[15] << 32) | s.h_ctl[14];
+        if (err || (c_last > n_owned ? c_last - n_owned : 0) != ex)
+            return fail(ctx, PFAC_E_ARG, "pfac_replace_leftmost_longest: the selection is not one of this scan and table");
+    }
+    const int64_t total = (int64_t)(n_owned + ex) - (int64_t)entry + delta;
+    if (total < 0) return fail(ctx, PFAC_E_INTERNAL, "pfac_replace_leftmost_longest: negative output length");
+    const uint64_t ob = (uint64_t)total;
+    *out_bytes = ob;
+    const bool own_out = d_out == nullptr;
+    if (!own_out && ob > out_cap)
+        return fail(ctx, PFAC_E_OVERFLOW, "pfac_replace_leftmost_longest: " + std::to_string(ob) + " output bytes, out_cap is " + std::to_string(out_cap));
+    if (own_out && ob > s.rp_out_cap) {
+        if (s.d_rp_out) { HIP_TRY(ctx, hipStreamSynchronize(s.stream)); HIP_TRY(ctx, hipFree(s.d_rp_out)); s.d_rp_out = nullptr; s.rp_out_cap = 0; }
+        const uint64_t cap = align_up(ob + ob / 8, 4096);
+        HIP_TRY(ctx, hipMalloc((void **)&s.d_rp_out, cap));
+        s.rp_out_cap = cap;
+    }
+    unsigned char *out = own_out ? s.d_rp_out : static_cast<unsigned char *>(d_out);
+    if (ob) {
+        // one window of 1 KiB per wave while the output is small (every window's search runs in parallel), four above
+        uint64_t wins = ob >= (64ull << 20) ? 4 : 1;
+        const uint64_t max_blocks = 1ull << 20;
+        const uint64_t per_block = (uint64_t)RP_WAVES * RP_WIN;
+        if ((ob + per_block * wins - 1) / (per_block * wins) > max_blocks) wins = (ob + per_block * max_blocks - 1) / (per_block * max_blocks);
+        const uint64_t blocks = (ob + per_block * wins - 1) / (per_block * wins);
+        hipLaunchKernelGGL(pfac_rp_write_kernel, dim3((unsigned)blocks), dim3(RP_WAVES * WAVE), 0, s.stream, in,
+                           (unsigned long long)n_avail, sel, (unsigned long long)n, (unsigned long long)entry, ctx->d_flen,
+                           ctx->d_rep_off, ctx->d_rep, (unsigned long long)ctx->rep_size, X, s.d_gsum,
+                           (unsigned long long)ob, (unsigned)wins, out);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    s.rp_bytes = ob;
+    s.rp_own_out = own_out;
+    s.rp_done = true;
+    return PFAC_OK;
+}
+
+int pfac_replace_d2h(pfac_ctx *ctx, int slot, void *host, uint64_t first, uint64_t n) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    Slot &s = ctx->slots[slot];
+    if (!s.rp_done) return fail(ctx, PFAC_E_STATE, "pfac_replace_d2h without a finished pfac_replace_leftmost_longest");
+    if (!s.rp_own_out) return fail(ctx, PFAC_E_STATE, "pfac_replace_d2h: the last replacement wrote into the caller's buffer");
+    if (first > s.rp_bytes || n > s.rp_bytes - first) return fail(ctx, PFAC_E_ARG, "pfac_replace_d2h: [first, first + n) exceeds the output");
+    if (!host && n) return fail(ctx, PFAC_E_ARG, "null host buffer");
+    USE_DEVICE(ctx);
+    if (n) HIP_TRY(ctx, hipMemcpyAsync(host, s.d_rp_out + first, n, hipMemcpyDeviceToHost, s.stream));
     return PFAC_OK;
 }
 

@@ -14,7 +14,7 @@ from typing import Optional, Tuple
 import numpy as np
 
 from ._ffi import PFAC_E_OVERFLOW, CRecord, PfacError, hip_lib
-from .table import RECORD_DTYPE, PfacTable
+from .table import RECORD_DTYPE, PfacTable, redaction_table, replacement_table
 
 
 def device_count() -> int:
@@ -390,6 +390,63 @@ class GpuMatcher:
         self.scan_resident(n_owned, n_avail, slot=slot)
         n, ex = self.select_leftmost_longest(entry, slot=slot)
         return self.selection_to_host(n, slot), ex
+
+    # -- find-and-replace over the leftmost-longest selection ---------------
+    def _set_replacement_table(self, offsets, data: bytes) -> None:
+        off = np.ascontiguousarray(offsets, dtype=np.uint32)
+        buf = np.frombuffer(data, dtype=np.uint8) if data else np.zeros(1, dtype=np.uint8)
+        self._check(self._L.pfac_table_set_replacements(self._ctx, off.ctypes.data, off.size - 1, buf.ctypes.data,
+                                                        len(data)))
+
+    def set_replacements(self, replacements) -> None:
+        """The replacement of every pattern of the uploaded table (``replacement_table``: a dict {id: bytes} or one
+        entry per line), kept on the device until the next table upload."""
+        if self.table is None:
+            raise PfacError(-7, "no host table to map pattern ids to states (load_table first)")
+        self._set_replacement_table(*replacement_table(self.table, replacements))
+
+    def set_redaction(self, fill: bytes = b"*") -> None:
+        """Replacements that mask every match: ``fill`` repeated to the pattern's length."""
+        if self.table is None:
+            raise PfacError(-7, "no host table to take the final-state lengths from (load_table first)")
+        self._set_replacement_table(*redaction_table(self.table, fill))
+
+    def replace_selection(self, d_input=None, d_out=None, out_cap: int = 0, slot: int = 0, d_sel=None) -> int:
+        """Rewrites the slot's last scan on the GPU: every pick of its last ``select_leftmost_longest`` replaced by its
+        state's replacement, the bytes between copied, from the selection's entry to n_owned.  Returns the output's
+        length.  ``d_out`` None = a slot-owned buffer (``replacement_to_host``); ``d_sel`` None = the slot-owned
+        selection.  A too small ``out_cap`` raises PfacError(PFAC_E_OVERFLOW) whose ``out_bytes`` attribute holds the
+        exact length."""
+        n = C.c_uint64(0)
+        rc = self._L.pfac_replace_leftmost_longest(self._ctx, slot, _ptr(d_input), _ptr(d_sel), _ptr(d_out), int(out_cap),
+                                                   C.byref(n))
+        if rc:
+            e = PfacError(rc, (self._L.pfac_last_error(self._ctx) or b"").decode())
+            e.out_bytes = n.value
+            raise e
+        return n.value
+
+    def replacement_to_host(self, n: int, slot: int = 0, first: int = 0) -> np.ndarray:
+        """Bytes [first, first + n) of the slot's last ``replace_selection`` into its slot-owned buffer."""
+        out = np.empty(int(n), dtype=np.uint8)
+        self._check(self._L.pfac_replace_d2h(self._ctx, slot, out.ctypes.data if n else None, int(first), int(n)))
+        self.sync(slot)
+        return out
+
+    def replace(self, data, n_owned: Optional[int] = None, entry: int = 0, slot: int = 0) -> Tuple[np.ndarray, int]:
+        """H2D + scan + selection + replacement of one host buffer (``n_owned`` < len(data) leaves the rest as halo).
+        Returns (output bytes, exit): ``exit`` is the ``entry`` of the range that follows."""
+        buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data.view(np.uint8).ravel()
+        n_avail = int(buf.size)
+        n_owned = n_avail if n_owned is None else int(n_owned)
+        self._ensure_final_lengths()
+        self.reserve(slot, max(n_avail, 1), max(n_avail // 8, 4096))
+        if n_avail:
+            self.h2d(buf, slot)
+        self.scan_resident(n_owned, n_avail, slot=slot)
+        _, ex = self.select_leftmost_longest(entry, slot=slot)
+        n = self.replace_selection(slot=slot)
+        return self.replacement_to_host(n, slot), ex
 
     # -- synthetic inputs (device resident) --------------------------------
     def fill_tiled(self, d_dst, n: int, pattern: bytes, phase: int = 0, slot: int = 0) -> None:

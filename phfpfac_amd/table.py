@@ -162,6 +162,60 @@ class PfacTable:
             self._ptr = None
 
 
+MAX_REPLACEMENT = 65536              # bytes of one replacement (PFAC_MAX_REPLACEMENT)
+
+
+def _state_lengths(table: "PfacTable") -> np.ndarray:
+    lens = getattr(table, "_final_lengths", None)
+    if lens is None:
+        lens = table.final_lengths()
+        table._final_lengths = lens          # once per table
+    return lens
+
+
+def replacement_table(table: "PfacTable", replacements) -> tuple:
+    """-> (offsets uint32[num_final + 1], bytes): the replacement of every final state, for
+    ``pfac_table_set_replacements``.  ``replacements`` is a dict {pattern id: bytes} or a sequence with one entry per
+    line of the pattern file, in file order (``replacements[id - 1]``; None = none given).  A state gets the
+    replacement of ``idmap[s]``: the winning line of duplicates, the first (lowest) id of a character-class state.
+    Unreachable states get an empty one.  Every reachable state must be covered: ValueError names the smallest id
+    that is missing."""
+    lens = _state_lengths(table)
+    ids = np.asarray(table.idmap, dtype=np.int64)
+    if isinstance(replacements, dict):
+        get = replacements.get
+    else:
+        seq = list(replacements)
+        get = lambda i: seq[i - 1] if 1 <= i <= len(seq) else None   # noqa: E731
+    offsets = np.zeros(int(table.num_final) + 1, dtype=np.uint32)
+    parts, missing, at = [], [], 0
+    for s in range(int(table.num_final)):
+        if lens[s] >= 1:
+            r = get(int(ids[s]))
+            if r is None:
+                missing.append(int(ids[s]))
+            else:
+                r = bytes(r)
+                if len(r) > MAX_REPLACEMENT:
+                    raise ValueError(f"the replacement of pattern id {int(ids[s])} is longer than {MAX_REPLACEMENT} bytes")
+                parts.append(r)
+                at += len(r)
+        offsets[s + 1] = at
+    if missing:
+        raise ValueError(f"no replacement for pattern id {min(missing)}")
+    return offsets, b"".join(parts)
+
+
+def redaction_table(table: "PfacTable", fill: bytes = b"*") -> tuple:
+    """``replacement_table`` of a redaction: every reachable state gets ``fill`` repeated to its pattern length."""
+    lens = _state_lengths(table)
+    fill = bytes(fill)
+    reps = [fill * int(n) if n >= 1 else b"" for n in lens]
+    offsets = np.zeros(int(table.num_final) + 1, dtype=np.uint32)
+    offsets[1:] = np.cumsum([len(r) for r in reps], dtype=np.uint64)
+    return offsets, b"".join(reps)
+
+
 def merge_partitions(record_lists, idmaps=None) -> np.ndarray:
     """The reference's host merge (main.cc:304-324) on compact records: ``record_lists[k]`` are the position-sorted
     records of pattern partition k; returns one array ordered by (position, partition) whose ``state`` field holds
