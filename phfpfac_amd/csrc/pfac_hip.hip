@@ -75,6 +75,7 @@ constexpr int QCAP = SUB / 2 + 4 * WAVE;   // survivor FIFO: < one round (at mos
 #define PFAC_CAPW 256
 #endif
 constexpr int CAPW = PFAC_CAPW;            // records staged in LDS per tile per buffer (more -> synchronous re-walk)
+static_assert(CAPW % 8 == 0, "staging buffers start on 16-byte boundaries (copy_out reads them 16 bytes per lane)");
 constexpr int PACK_STATE_BITS = 20;        // staged record = pos:12 | state:20 (larger automata re-walk)
 constexpr int MAX_WAVES_PER_BLOCK = 16;     // 15 compute waves + the coordinator
 constexpr int LDS_TOTAL = 160 * 1024;
@@ -598,9 +599,19 @@ __device__ __forceinline__ void put_record(const ScanArgs &a, unsigned long long
     }
 }
 
+// One record into a tile's LDS staging buffer, in the packed format.  S16 (the kernels with their tables in LDS, where
+// the small automata with 16-bit records run): 16-bit records are staged as 16-bit words, so that copy_out moves them
+// to global memory as they lie.  Else, and for the wider packed form, as 32-bit words (the L2-table kernels are paced
+// by their instruction stream and registers: they keep the one form).
+template <bool S16>
+__device__ __forceinline__ void stage_put(const ScanArgs &a, unsigned *stage, unsigned i, unsigned v) {
+    if (S16 && a.rec_bytes == 2) reinterpret_cast<unsigned short *>(stage)[i] = (unsigned short)v;
+    else stage[i] = v;
+}
+
 // Same walk for the rare offsets where more patterns start than the fast walk keeps final states in registers:
 // every final state goes to the LDS staging buffer (packed) or straight to global memory.
-template <bool W8, bool DIRECT>
+template <bool W8, bool DIRECT, bool S16>
 __device__ __forceinline__ void walk_store(const ScanArgs &a, const unsigned char *tile, const int *s0, const int *R, const int2 *T,
                                            unsigned pos, unsigned lim, unsigned *stage, unsigned long long ri, unsigned gpos) {
     unsigned n = 0;
@@ -609,7 +620,7 @@ __device__ __forceinline__ void walk_store(const ScanArgs &a, const unsigned cha
     while (s >= 0) {
         if (s < a.num_final) {
             if (DIRECT) put_record(a, ri + n, pos, gpos, (unsigned)s);
-            else if (ri + n < a.stage_cap) stage[ri + n] = pos | ((unsigned)s << 12);
+            else if (ri + n < a.stage_cap) stage_put<S16>(a, stage, (unsigned)ri + n, pos | ((unsigned)s << 12));
             n++;
         }
         if (p >= lim) break;
@@ -631,7 +642,7 @@ struct Dense1 {
 // are appended, in queue (= position) order, at index `wrun` of the staging buffer (DIRECT == false) or of the global
 // record array.  Entries without QDEEP are shallow-final survivors: one record, the depth-1 state of their byte; a
 // round made of those alone needs neither a walk nor a prefix sum.  Returns the number of records.
-template <bool W8, bool DIRECT, int NWALK, bool FUSED, int ROOT>
+template <bool W8, bool DIRECT, int NWALK, bool FUSED, int ROOT, bool S16>
 __device__ __forceinline__ unsigned roundN(const ScanArgs &a, const unsigned char *tile, const int *s0, const Dense1 &d1,
                                            const int *R, const int2 *T, const unsigned short *q, unsigned q0,
                                            unsigned nact, int lane, unsigned *stage, unsigned lim,
@@ -659,7 +670,7 @@ __device__ __forceinline__ unsigned roundN(const ScanArgs &a, const unsigned cha
             const unsigned st = ROOT == 1 ? (unsigned)a.root_state : (unsigned)s0[tile[pos[w]]];
             const unsigned long long ri = wrun + WAVE * w + lane;
             if (DIRECT) put_record(a, ri, pos[w], (unsigned)tile_base + pos[w], st);
-            else if (ri < a.stage_cap) stage[ri] = pos[w] | (st << 12);
+            else if (ri < a.stage_cap) stage_put<S16>(a, stage, (unsigned)ri, pos[w] | (st << 12));
         }
         return nact;
     }
@@ -707,14 +718,14 @@ __device__ __forceinline__ unsigned roundN(const ScanArgs &a, const unsigned cha
 #pragma unroll
             for (int k = 1; k < MREG; k++)
                 if (regs && n[w] > (unsigned)k) put_record(a, ri + k, pos[w], gpos, m[w][k]);
-            if (!regs) walk_store<W8, true>(a, tile, s0, R, T, pos[w], lim, nullptr, ri, gpos);
+            if (!regs) walk_store<W8, true, S16>(a, tile, s0, R, T, pos[w], lim, nullptr, ri, gpos);
         } else {
             const unsigned ri = (unsigned)wrun + ex[w];        // tile-local record index: 32 bits are plenty
-            if (regs && n[w] > 0 && ri < a.stage_cap) stage[ri] = pos[w] | (m[w][0] << 12);
+            if (regs && n[w] > 0 && ri < a.stage_cap) stage_put<S16>(a, stage, ri, pos[w] | (m[w][0] << 12));
 #pragma unroll
             for (int k = 1; k < MREG; k++)
-                if (regs && n[w] > (unsigned)k && ri + k < a.stage_cap) stage[ri + k] = pos[w] | (m[w][k] << 12);
-            if (!regs) walk_store<W8, false>(a, tile, s0, R, T, pos[w], lim, stage, ri, 0);
+                if (regs && n[w] > (unsigned)k && ri + k < a.stage_cap) stage_put<S16>(a, stage, ri + k, pos[w] | (m[w][k] << 12));
+            if (!regs) walk_store<W8, false, S16>(a, tile, s0, R, T, pos[w], lim, stage, ri, 0);
         }
     }
     return total;
@@ -733,6 +744,7 @@ __device__ __forceinline__ unsigned long long tile_pass(const ScanArgs &a, const
                                                         unsigned lim, unsigned long long tile_base,
                                                         unsigned long long wrun) {
     unsigned head = 0, tail = 0;               // pending survivors: q[head, tail), always fewer than one round between appends
+    constexpr bool S16 = NWALK == 1;           // the kernels with their tables in LDS: 16-bit staging (stage_put)
     // per-lane survivor counts of the 2 half-tiles, prefix-summed in one packed DPP scan (16-bit fields: a
     // half-tile holds at most 2048 survivors)
     static_assert(MSUBS == 2, "the packed scan assumes 2 half-tiles");
@@ -757,6 +769,17 @@ __device__ __forceinline__ unsigned long long tile_pass(const ScanArgs &a, const
             if (!DIRECT && totals[0] + totals[1] <= a.stage_cap) {
                 // everything fits (else the tile is walked again, DIRECT): no bound checks, two records per trip
                 const unsigned w0 = lpos | (st << 12);
+                if (S16 && a.rec_bytes == 2) {
+                    unsigned short *s16 = reinterpret_cast<unsigned short *>(stage);
+                    for (unsigned m = keep[j]; m;) {
+                        s16[o] = (unsigned short)(w0 + (unsigned)__ffs(m) - 1u);
+                        m &= m - 1;
+                        if (m) s16[o + 1] = (unsigned short)(w0 + (unsigned)__ffs(m) - 1u);
+                        m &= m - 1;
+                        o += 2;
+                    }
+                    continue;
+                }
                 for (unsigned m = keep[j]; m;) {
                     stage[o] = w0 + (unsigned)__ffs(m) - 1u;
                     m &= m - 1;
@@ -769,7 +792,7 @@ __device__ __forceinline__ unsigned long long tile_pass(const ScanArgs &a, const
             for (unsigned m = keep[j]; m; m &= m - 1) {
                 const unsigned pos = lpos + (__ffs(m) - 1);
                 if (DIRECT) put_record(a, wrun + o, pos, (unsigned)tile_base + pos, st);
-                else if (o < a.stage_cap) stage[o] = pos | (st << 12);
+                else if (o < a.stage_cap) stage_put<S16>(a, stage, o, pos | (st << 12));
                 o++;
             }
         }
@@ -823,7 +846,7 @@ __device__ __forceinline__ unsigned long long tile_pass(const ScanArgs &a, const
             tail += gcnt;
             wave_lds_sync();
             for (; head + RW <= tail; head += RW)
-                TP_ROUND((wrun += roundN<W8, DIRECT, NWALK, FUSED, ROOT>(a, tile, s0, d1, R, T, q, head, RW, lane, stage, lim, tile_base, wrun)));
+                TP_ROUND((wrun += roundN<W8, DIRECT, NWALK, FUSED, ROOT, S16>(a, tile, s0, d1, R, T, q, head, RW, lane, stage, lim, tile_base, wrun)));
         }
     }
     // (the last, partial round runs where its entries lie: nothing is appended behind them any more; with two walks per
@@ -831,9 +854,9 @@ __device__ __forceinline__ unsigned long long tile_pass(const ScanArgs &a, const
     // sparse L2-table kernels are paced by their instruction stream, and their typical tile ends on such a round)
     if (tail > head) {
         if (NWALK == 2 && !DIRECT && tail - head <= (unsigned)WAVE)
-            TP_ROUND((wrun += roundN<W8, DIRECT, 1, FUSED, ROOT>(a, tile, s0, d1, R, T, q, head, tail - head, lane, stage, lim, tile_base, wrun)));
+            TP_ROUND((wrun += roundN<W8, DIRECT, 1, FUSED, ROOT, S16>(a, tile, s0, d1, R, T, q, head, tail - head, lane, stage, lim, tile_base, wrun)));
         else
-            TP_ROUND((wrun += roundN<W8, DIRECT, NWALK, FUSED, ROOT>(a, tile, s0, d1, R, T, q, head, tail - head, lane, stage, lim, tile_base, wrun)));
+            TP_ROUND((wrun += roundN<W8, DIRECT, NWALK, FUSED, ROOT, S16>(a, tile, s0, d1, R, T, q, head, tail - head, lane, stage, lim, tile_base, wrun)));
     }
 #ifdef PFAC_TRACE_BUILD
     if (!DIRECT && a.dbg && blockIdx.x < 8 && lane == 0 && (threadIdx.x >> 6) == 0) {
@@ -855,8 +878,25 @@ __device__ __forceinline__ void copy_out(const ScanArgs &a, const unsigned *stag
 #ifdef PFAC_ABL_NOEMIT                         // ablation builds only: records never leave LDS
     return;
 #endif
+    if (a.rec_bytes == 2 && !SPARSE) {
+        // automata with at most 16 final states, tables in LDS: 16-bit staged words, and every run starts on a 16-byte
+        // boundary of the record array (the heap hands out multiples of 8 records), so it leaves as whole 16-byte
+        // blocks, one ds_read_b128 and one store per lane; the last block carries whatever the staging buffer holds past
+        // cnt into the run's own padding (stage_cap is a multiple of 8)
+        const unsigned short *s16 = reinterpret_cast<const unsigned short *>(stage);
+        unsigned short *out = static_cast<unsigned short *>(a.out);
+        if (((unsigned)base & 7u) != 0u || base + ((cnt + 7u) & ~7u) > a.out_cap) {
+            for (unsigned i = (unsigned)lane; i < cnt; i += WAVE)       // the record array ends inside this run: checked
+                if (base + i < a.out_cap) out[base + i] = s16[i];
+            return;
+        }
+        for (unsigned i = 8u * (unsigned)lane; i < cnt; i += 8u * WAVE)
+            __builtin_nontemporal_store(*reinterpret_cast<const u32x4 *>(s16 + i), reinterpret_cast<u32x4 *>(out + base + i));
+        return;
+    }
     if (a.rec_bytes == 2) {
-        // automata with at most 16 final states: the record is the low half of the staged word; eight per 16-byte store
+        // the same records staged as 32-bit words (the L2-table kernels): the record is the low half of the staged word;
+        // eight per 16-byte store, the ragged head and tail one lane each (none when the run is aligned)
         unsigned short *out = static_cast<unsigned short *>(a.out);
         if (base + cnt > a.out_cap) {
             for (unsigned i = (unsigned)lane; i < cnt; i += WAVE)
@@ -872,7 +912,6 @@ __device__ __forceinline__ void copy_out(const ScanArgs &a, const unsigned *stag
                              (stage[i + 4] & 0xFFFFu) | (stage[i + 5] << 16), (stage[i + 6] & 0xFFFFu) | (stage[i + 7] << 16)};
             __builtin_nontemporal_store(v, reinterpret_cast<u32x4 *>(out + base + i));
         }
-        // the last 1..7 records: one lane each (not a loop in the one lane that stopped there: seven dependent LDS trips)
         const unsigned tail = head + ((cnt - head) & ~7u);
         if (tail + (unsigned)lane < cnt) out[base + tail + lane] = (unsigned short)stage[tail + lane];
         return;
@@ -1421,6 +1460,7 @@ __device__ __forceinline__ void scan_body(const ScanArgs &a, unsigned char *smem
         };
         unsigned long long ch_base = 0, spare = order_chunk(), local_total = 0;
         unsigned ch_size = 0, ch_used = 0;
+        const unsigned rec_pad = a.rec_bytes == 2 ? 7u : 0u;           // a run's allocation: its count rounded up to rec_pad + 1
         for (unsigned r = 0;; r++) {
             const unsigned g_cur = g[0];
             const unsigned long long first = (unsigned long long)g_cur * (unsigned)nc;
@@ -1441,11 +1481,12 @@ __device__ __forceinline__ void scan_body(const ScanArgs &a, unsigned char *smem
             const unsigned c_raw = (unsigned)lane < n_valid ? hdr[H_CNT + (r & 7) * 16 + lane] : 0u;
             const unsigned c_all = c_raw & 0x7FFFFFFFu;
             const bool self_placed = (c_raw >> 31) != 0u;
-            const unsigned c = self_placed ? 0u : c_all;
+            // 16-bit records: each run takes its count rounded up to 8 records, so that every run starts on a 16-byte
+            // boundary (chunks and exact allocations are multiples of 8 records too) and leaves as whole 16-byte stores
+            const unsigned c = self_placed ? 0u : (c_all + rec_pad) & ~rec_pad;
             const unsigned incl = wave_incl_scan(c);        // 15 tile counts of < 2^22 each
             const unsigned tot = bcast_last(incl);
             const unsigned excl = incl - c;
-            const unsigned tot_all = __any(self_placed) ? bcast_last(wave_incl_scan(c_all)) : tot;
             // ---- place the tiles (lane c: the tile of compute wave c)
             unsigned long long wb;
             if (tot == 0) {
@@ -1472,7 +1513,6 @@ __device__ __forceinline__ void scan_body(const ScanArgs &a, unsigned char *smem
                 ch_used = tot - off;
                 spare = order_chunk();
             }
-            local_total += tot_all;
             const bool mute = (a.fault & 1u) && blockIdx.x == 1 && r == 1;   // test knob: the bases of this round never come
             if (lane < nc) {
                 hdr[H_WBASE + (r & 7) * 32 + lane * 2] = (unsigned)wb;
@@ -1480,7 +1520,9 @@ __device__ __forceinline__ void scan_body(const ScanArgs &a, unsigned char *smem
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             if (lane == 0 && !mute) lds_store(&hdr[H_READY + (r & 7)], r + 1);
-            if ((unsigned)lane < n_valid && !self_placed) a.tile_index[first + (unsigned)lane] = wb | ((unsigned long long)c << TIX_CNT_SHIFT);
+            if ((unsigned)lane < n_valid && !self_placed) a.tile_index[first + (unsigned)lane] = wb | ((unsigned long long)c_all << TIX_CNT_SHIFT);
+            // the matches (exact counts, self-placed tiles included): behind the bases, off the compute waves' path
+            local_total += (rec_pad || __any(self_placed)) ? bcast_last(wave_incl_scan(c_all)) : tot;
 #ifdef PFAC_TRACE_BUILD
             if (trace) { tr[2] = __builtin_amdgcn_s_memrealtime(); tr[3] = g_cur; }
 #endif
@@ -1760,10 +1802,12 @@ __device__ __forceinline__ void scan_body(const ScanArgs &a, unsigned char *smem
         if (now && cnt != 0) {
             // A tile that leaves at once waits for nobody: it takes exactly its records from the heap cursor itself (one
             // device atomic per tile -- these are the dense tiles, tens of microseconds each) and writes its own index
-            // word; the coordinator only adds its count to the total.
+            // word; the coordinator only adds its count to the total.  (16-bit records: a multiple of 8 records, like
+            // every allocation of the heap -- the runs placed after it stay on 16-byte boundaries.)
+            const unsigned long long take = a.rec_bytes == 2 ? (cnt + 7ull) & ~7ull : cnt;
             unsigned long long v = 0;
             if (lane == 0)
-                v = __hip_atomic_fetch_add(reinterpret_cast<unsigned long long *>(a.ctl + CTL_CURSOR), (unsigned long long)cnt,
+                v = __hip_atomic_fetch_add(reinterpret_cast<unsigned long long *>(a.ctl + CTL_CURSOR), take,
                                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const unsigned long long base = ((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned)(v >> 32)) << 32) |
                                             __builtin_amdgcn_readfirstlane((unsigned)v);
@@ -3784,7 +3828,7 @@ int pfac_scan_async(pfac_ctx *ctx, int slot, const void *d_input, uint64_t n_own
         // heap chunk: 1/32 of an even share of the record array per workgroup -- the current and the spare chunk of
         // every workgroup can stay unfilled at the end, i.e. at most 1/16 of the capacity; record arrays too small for
         // chunks of 1024 records get exact allocations (one atomic per batch)
-        uint64_t chunk = (capacity / (32 * grid)) & ~3ull;
+        uint64_t chunk = (capacity / (32 * grid)) & ~7ull;        // (a multiple of 8 records: see the placement)
         if (chunk > (1u << 22)) chunk = 1u << 22;
         a.chunk = (chunk >= 1024 && !dense) ? (unsigned)chunk : 0u;      // (dense mode: every tile takes its own space)
         void *kargs[] = {&a};
