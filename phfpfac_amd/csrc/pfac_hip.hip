@@ -1878,7 +1878,12 @@ __global__ __launch_bounds__(WAVE * MAX_WAVES_PER_BLOCK) void pfac_scan_kernel(S
 #ifdef PFAC_TRACE_BUILD
             if (a.dbg && blockIdx.x < 8) a.dbg[((size_t)blockIdx.x * 64 + 2) * 32 + 15] = __builtin_amdgcn_s_memrealtime();
 #endif
-            const unsigned done = __hip_atomic_fetch_add(&a.ctl[CTL_DONE], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+            // Relaxed: the last workgroup reads nothing but words that every workgroup changed with device-scope atomics, and
+            // each wave waited for its own (vmcnt above) before it was counted out, so they are performed when CTL_DONE
+            // reaches the grid.  Records, tile index and the next control header are read only after the kernel (its end
+            // releases them).  An acq_rel here wrote the XCD's L2 back at every workgroup's exit (buffer_wbl2): with the
+            // records of the last rounds dirty in it, several microseconds on the path of the last workgroups to leave.
+            const unsigned done = __hip_atomic_fetch_add(&a.ctl[CTL_DONE], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (done + 1 == gridDim.x) {
                 const unsigned long long tot = __hip_atomic_load(reinterpret_cast<unsigned long long *>(a.ctl + CTL_TOTAL), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 const unsigned long long cur = __hip_atomic_load(reinterpret_cast<unsigned long long *>(a.ctl + CTL_CURSOR), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
