@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+from docref import oracle_per_doc, random_offsets
 from orc import Oracle, ac_whole_shard
 from phfpfac_amd import GpuMatcher, PfacError, PfacTable
 from phfpfac_amd import _ffi
@@ -21,25 +22,6 @@ def para_bytes(resolve, n):
     return tiled_bytes(n, open(resolve("paragraph402"), "rb").read())
 
 
-def oracle_per_doc(o, buf, off):
-    """(doc_first, pos, ids) of scanning every document [off[d], off[d+1]) of buf on its own."""
-    first = np.zeros(off.size, dtype=np.uint64)
-    pos, ids = [], []
-    k = 0
-    for d in range(off.size - 1):
-        a, b = int(off[d]), int(off[d + 1])
-        first[d] = k
-        if b > a:
-            p, i = o.scan_spec(np.ascontiguousarray(buf[a:b]))
-            pos.append(p)
-            ids.append(i)
-            k += p.size
-    first[-1] = k
-    pos = np.concatenate(pos) if pos else np.empty(0, np.int64)
-    ids = np.concatenate(ids) if ids else np.empty(0, np.int32)
-    return first, pos, ids
-
-
 def assert_docs(table, got, want):
     first, rec = got
     wfirst, wpos, wids = want
@@ -47,15 +29,6 @@ def assert_docs(table, got, want):
     np.testing.assert_array_equal(first, wfirst)
     np.testing.assert_array_equal(rec["pos"].astype(np.int64), wpos)
     np.testing.assert_array_equal(table.idmap[rec["state"]], wids)
-
-
-def random_offsets(rng, n, n_docs, empties=0):
-    cuts = np.sort(rng.integers(0, n + 1, n_docs - 1))
-    off = np.concatenate([[0], cuts, [n]]).astype(np.uint64)
-    if empties:
-        at = rng.integers(0, off.size, empties)
-        off = np.sort(np.concatenate([off, off[at]]))
-    return off
 
 
 def check(pattern_path, buf, off, n_streams=1, table=None):
