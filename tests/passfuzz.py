@@ -74,11 +74,19 @@ class Case:
         self.n_owned = n if rng.random() < 0.7 else int(rng.integers(0, n + 1))
         self.M = max(len(p) for p in lines)
         self.entry = int(rng.integers(0, self.M + 1))
-        # replacements: 0 to 64 bytes, now and then 1 000 to 5 000
-        self.reps = {}
-        for i in range(1, len(lines) + 1):
+        self.reps = self.replacements(rng)
+        self.plan_passes(rng)
+
+    def replacements(self, rng):
+        """{pattern id: bytes}: 0 to 64 bytes, now and then 1 000 to 5 000."""
+        reps = {}
+        for i in range(1, len(self.lines) + 1):
             L = int(rng.integers(1000, 5001)) if rng.random() < 0.01 else int(rng.integers(0, 65))
-            self.reps[i] = rng.integers(0, 256, L).astype(np.uint8).tobytes()
+            reps[i] = rng.integers(0, 256, L).astype(np.uint8).tobytes()
+        return reps
+
+    def plan_passes(self, rng):
+        """Document offsets and the cuts of a chained selection over the owned range."""
         # documents: random cuts with empty documents, cuts at 4096k - 1, 4096k, 4096k + 1, runs of documents under
         # 64 bytes in some tiles
         no = self.n_owned
@@ -116,15 +124,17 @@ class Case:
 class Expect:
     """What the CPU says for a case (never reads the device)."""
 
-    def __init__(self, case, path):
+    def __init__(self, case, path, matcher=None):
+        """`matcher`: an object with ``Oracle.scan_spec``'s interface (tests/bigref.py); None = the CPU oracle."""
         c = case
         self.entry, self.n_owned = c.entry, c.n_owned
-        o = Oracle(path, 1, 1)
+        o = Oracle(path, 1, 1) if matcher is None else matcher
         pos, ids = o.scan_spec(c.data, None)
         own = pos < c.n_owned                       # (the rest of the buffer is halo: read, not scanned from)
         self.pos, self.ids = pos[own], ids[own]
         self.docs = oracle_per_doc(o, c.data, c.off)
-        o.close()
+        if matcher is None:
+            o.close()
         self.ll = line_lengths(path)
         self.lens = self.ll[self.ids]
         if self.pos.size <= GREEDY_MAX:
@@ -144,23 +154,23 @@ class Expect:
         return check_greedy(self.pos, self.lens, (spos, slen), self.entry, self.n_owned)
 
 
-def run_case(g_factory, case, tmp_dir):
+def run_case(g_factory, case, tmp_dir, matcher=None):
     """Runs one case through scan (twice), selection, replace, documents and a chained selection, each compared bit
-    for bit with the CPU.  `g_factory()` -> a GpuMatcher.  Returns the number of records compared; raises
-    AssertionError naming the case."""
+    for bit with the CPU (`matcher`: see Expect).  `g_factory()` -> a GpuMatcher.  Returns the number of records
+    compared; raises AssertionError naming the case."""
     c = case
     path = c.write_patterns(os.path.join(tmp_dir, f"fuzz_{c.seed}.pat"))
     where = c.describe()
     try:
-        return _run(g_factory, c, path)
+        return _run(g_factory, c, path, matcher)
     except AssertionError as e:
         raise AssertionError(f"{where}: {e}") from e
 
 
-def _run(g_factory, c, path):
+def _run(g_factory, c, path, matcher=None):
     table = PfacTable.from_file(path, c.width)
     assert table.max_pat_len == c.M
-    want = Expect(c, path)
+    want = Expect(c, path, matcher)
     compared = 0
     with g_factory() as g:
         g.load_table(table)
