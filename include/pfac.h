@@ -367,6 +367,36 @@ int pfac_records_leftmost_longest(pfac_ctx *ctx, int slot, const void *d_records
  * slot's stream; pfac_slot_sync completes it. */
 int pfac_leftmost_longest_d2h(pfac_ctx *ctx, int slot, pfac_record *host);
 
+/* Leftmost-longest selection per document: the slot's last finished scan cut into documents [off[d], off[d+1]) (the
+ * rules of pfac_records_segment), and every document given its own leftmost-longest selection from cursor 0 over the
+ * records that end inside it (pos + len <= off[d+1]): what pfac_records_leftmost_longest of each document scanned on
+ * its own selects.  The kernels run the selection above over the whole scan from entry 0 with one change: at a
+ * position p of document d the candidate is the longest record at p that ends at or before off[d+1].  No candidate
+ * crosses a document end, so the cursor never passes a document start and the selection restarts at every document.
+ *   d_records      the scan's record heap, NULL = the slot's
+ *   d_doc_offsets  device uint64[n_docs + 1], NULL = the slot's (pfac_slot_doc_offsets, same n_docs); the rules of
+ *                  pfac_records_segment (off[0] == 0, non-decreasing, off[n_docs] == n_owned, n_docs < 2^32)
+ *   d_out          the selection as {pos, state} in ascending pos, pos RELATIVE TO THE SCAN (not the document); NULL =
+ *                  the slot-owned selection buffer of pfac_records_leftmost_longest; else 8-B aligned, out_cap records
+ *   d_doc_first    d_doc_first[d] = index of document d's first pick, d_doc_first[n_docs] = *n_selected; NULL = a
+ *                  slot-owned buffer (fetched with pfac_leftmost_longest_documents_d2h); else 8-B aligned, n_docs + 1
+ * The call is the slot's last selection, with entry 0 and exit 0: pfac_replace_leftmost_longest consumes it unchanged
+ * (and returns the documents' outputs concatenated), pfac_replace_documents adds the per-document output offsets.
+ * Returns once *n_selected is known; the writes are asynchronous on the slot's stream.  PFAC_E_OVERFLOW (with
+ * *n_selected exact, nothing written) when out_cap is too small for a caller's d_out; PFAC_E_ARG for offsets that break
+ * the rules (checked on the device in the first pass, nothing written) or misaligned buffers; PFAC_E_STATE as
+ * pfac_records_leftmost_longest, or without offsets for the slot.
+ * Kernels: those of pfac_records_leftmost_longest, the two tile passes in a document form (each tile finds a record's
+ * document in a window of the offsets: lane shuffles when fewer than 63 documents start in it, else a binary search in
+ * memory), and a document write that also fills d_doc_first from the tiles' pick bitmaps. */
+int pfac_records_leftmost_longest_documents(pfac_ctx *ctx, int slot, const void *d_records, const uint64_t *d_doc_offsets,
+                                            uint64_t n_docs, pfac_record *d_out, uint64_t out_cap, uint64_t *d_doc_first,
+                                            uint64_t *n_selected);
+/* D2H of the slot-owned result of the last pfac_records_leftmost_longest_documents (host_records: *n_selected records,
+ * may be NULL when d_out was the caller's; host_doc_first: n_docs + 1 entries, may be NULL when d_doc_first was the
+ * caller's).  Asynchronous on the slot's stream; pfac_slot_sync completes it. */
+int pfac_leftmost_longest_documents_d2h(pfac_ctx *ctx, int slot, pfac_record *host_records, uint64_t *host_doc_first);
+
 /* Find-and-replace over the leftmost-longest selection.  Every final state s gets a replacement: bytes[offsets[s] ..
  * offsets[s+1]) (offsets holds n_states + 1 ascending entries, the last <= n_bytes < 2^32; n_states must equal num_final
  * of the uploaded table, else PFAC_E_ARG).  One replacement is at most PFAC_MAX_REPLACEMENT bytes (else PFAC_E_ARG).
@@ -397,6 +427,25 @@ int pfac_replace_leftmost_longest(pfac_ctx *ctx, int slot, const void *d_input, 
 /* D2H of bytes [first, first + n) of the slot-owned output of the last pfac_replace_leftmost_longest.  Asynchronous on
  * the slot's stream; pfac_slot_sync completes it. */
 int pfac_replace_d2h(pfac_ctx *ctx, int slot, void *host, uint64_t first, uint64_t n);
+
+/* Find-and-replace per document: pfac_replace_leftmost_longest over the slot's last selection, which must be a
+ * pfac_records_leftmost_longest_documents since the slot's last scan (else PFAC_E_STATE).  The output is every
+ * document's own output concatenated, with the same contract, arguments and errors as pfac_replace_leftmost_longest;
+ * alongside it the output offsets out_off[n_docs + 1]: out[out_off[d] : out_off[d+1]] is document d's output,
+ *   out_off[d] = off[d] + sum_{k < doc_first[d]} (R_k - L_k),   out_off[n_docs] = *out_bytes.
+ *   d_doc_offsets  the offsets the selection cut with: NULL = the slot's (PFAC_E_STATE if the selection was given the
+ *                  caller's, or if pfac_slot_doc_offsets replaced the slot's since); else the caller's device buffer
+ *   d_doc_first    the selection's doc_first: NULL = its slot-owned one (PFAC_E_STATE if it went to the caller's
+ *                  buffer); else that buffer
+ *   d_out_offsets  NULL = a slot-owned buffer (fetched with pfac_replace_documents_d2h); else 8-B aligned, n_docs + 1
+ * Extra kernels behind the write, O(n_picks + n_docs): one wave per block of 64 picks writes D_k = sum_{j<k} (R_j - L_j)
+ * for every pick (8 B of scratch per pick), then one thread per document writes out_off[d] = off[d] + D_{doc_first[d]}.
+ * The bytes are fetched with pfac_replace_d2h. */
+int pfac_replace_documents(pfac_ctx *ctx, int slot, const void *d_input, const pfac_record *d_sel, const uint64_t *d_doc_offsets,
+                           const uint64_t *d_doc_first, void *d_out, uint64_t out_cap, uint64_t *d_out_offsets, uint64_t *out_bytes);
+/* D2H of the slot-owned output offsets of the last pfac_replace_documents (n_docs + 1 entries).  Asynchronous on the
+ * slot's stream; pfac_slot_sync completes it. */
+int pfac_replace_documents_d2h(pfac_ctx *ctx, int slot, uint64_t *host_out_offsets);
 
 /* Synthetic input generators, written straight into device memory (the
  * reference built big inputs by tiling a small text, creatbiginput.sh:2-5).

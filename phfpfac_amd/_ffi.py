@@ -87,6 +87,8 @@ HIP_SYMBOLS = (
     "pfac_table_set_final_lengths", "pfac_slot_doc_offsets", "pfac_records_segment", "pfac_segment_d2h",
     "pfac_records_leftmost_longest", "pfac_leftmost_longest_d2h",
     "pfac_table_set_replacements", "pfac_replace_leftmost_longest", "pfac_replace_d2h",
+    "pfac_records_leftmost_longest_documents", "pfac_leftmost_longest_documents_d2h", "pfac_replace_documents",
+    "pfac_replace_documents_d2h",
 )
 
 _host = None
@@ -209,5 +211,9 @@ def hip_lib() -> C.CDLL:
         L.pfac_table_set_replacements.argtypes = [vp, vp, u64, vp, u64]
         L.pfac_replace_leftmost_longest.argtypes = [vp, i, vp, vp, vp, u64, C.POINTER(u64)]
         L.pfac_replace_d2h.argtypes = [vp, i, vp, u64, u64]
+        L.pfac_records_leftmost_longest_documents.argtypes = [vp, i, vp, vp, u64, vp, u64, vp, C.POINTER(u64)]
+        L.pfac_leftmost_longest_documents_d2h.argtypes = [vp, i, vp, vp]
+        L.pfac_replace_documents.argtypes = [vp, i, vp, vp, vp, vp, vp, u64, vp, C.POINTER(u64)]
+        L.pfac_replace_documents_d2h.argtypes = [vp, i, vp]
         _hip = L
     return _hip

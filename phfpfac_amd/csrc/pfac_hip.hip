@@ -2343,12 +2343,43 @@ __device__ __forceinline__ unsigned ll_lower_bound(const unsigned short *cpos, u
     return lo;
 }
 
-template <int BYTES, bool MARK>
+// The candidate rule of the per-document selection (pfac_records_leftmost_longest_documents), shared by both tile
+// passes and the write: at a position p of document d the candidate is the longest record at p that ends at or before
+// off[d + 1].  Records at one position come in ascending length, so the ones that fit are a prefix of them: record i is
+// the candidate iff it fits and the record behind it (at another position, or too long) does not.  Record i of the tile
+// (heap index lo + i of c) -> pos, st, len, its document d; every lane takes part (the shuffles of final_len and
+// doc_lookup), and lane 63 re-reads the record behind its chunk for the length and fit of that one.
+template <int BYTES>
+__device__ __forceinline__ bool ll_doc_candidate(const void *rec, unsigned long long lo, unsigned c, unsigned i,
+                                                 unsigned long long cap, unsigned long long t, const short *flen, int freg,
+                                                 bool fsmall, const DocWin &w, const unsigned long long *off, int lane,
+                                                 unsigned &pos, unsigned &st, int &len, unsigned long long &d) {
+    const bool have = i < c && lo + i < cap, hn = i + 1 < c && lo + i + 1 < cap;
+    pos = 0;
+    st = 0;
+    if (have) heap_record<BYTES>(rec, lo + i, t, pos, st);
+    unsigned pn = __shfl(pos, (lane + 1) & (WAVE - 1), WAVE), sn = __shfl(st, (lane + 1) & (WAVE - 1), WAVE);
+    if (lane == WAVE - 1 && hn) heap_record<BYTES>(rec, lo + i + 1, t, pn, sn);
+    len = final_len(flen, freg, fsmall, have, st);
+    const int ln = final_len(flen, freg, fsmall, hn, sn);
+    unsigned long long base, end;
+    doc_lookup(w, off, have, pos, d, base, end);
+    const bool fit = have && len > 0 && (unsigned long long)pos + (unsigned)len <= end;
+    const bool next_fits = hn && pn == pos && ln > 0 && (unsigned long long)pn + (unsigned)ln <= end;   // (same document)
+    return fit && !next_fits;
+}
+
+// DOCS: the per-document selection.  The candidate of a position is ll_doc_candidate's; a record's document comes from
+// the tile's document window (lane j of every wave holds [dlo, dhi] of tile 64g + j).  The function pass also checks
+// the offsets (as pfac_seg_count_kernel does) into *bad.  No candidate crosses a document end, so the chain restarts
+// at every document by itself.
+template <int BYTES, bool MARK, bool DOCS = false>
 __global__ void __launch_bounds__(LL_WAVES * WAVE)
 pfac_ll_tiles_kernel(const void *rec, const unsigned long long *tix, unsigned long long n_tiles, unsigned long long cap,
                      unsigned long long n_owned, const short *flen, unsigned num_final, unsigned M,
                      unsigned short *gfun, const unsigned short *gentry, unsigned long long *bits, unsigned *tcnt,
-                     unsigned long long *gsum) {
+                     unsigned long long *gsum, const unsigned long long *off, unsigned long long n_docs,
+                     unsigned long long *bad) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x >> 6;
     const unsigned g = blockIdx.x, M1 = M + 1, FS = ll_fun_stride(M1);
@@ -2365,6 +2396,19 @@ pfac_ll_tiles_kernel(const void *rec, const unsigned long long *tix, unsigned lo
         for (unsigned e = threadIdx.x; e < M1; e += blockDim.x) G[e] = (unsigned short)e;
     if (MARK && threadIdx.x == 0) tail[LL_WAVES] = gentry[g];
     unsigned long long wsel = 0;                                // selected records of this wave's tiles
+    unsigned long long tdlo = 0, tdhi = 0;                      // DOCS: documents of tile 64g + lane
+    if constexpr (DOCS) {
+        if constexpr (!MARK) {                                  // the offsets' rules, one thread per document
+            const unsigned long long gtid = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+            const unsigned long long gstride = (unsigned long long)gridDim.x * blockDim.x;
+            for (unsigned long long d = gtid; d < n_docs; d += gstride)
+                if (off[d] > off[d + 1]) *bad = 1ull;
+            if (gtid == 0 && (off[0] != 0ull || off[n_docs] != n_owned)) *bad = 1ull;
+        }
+        const unsigned long long tl = (unsigned long long)g * XGROUP + (unsigned)lane;
+        unsigned long long ds, de;
+        if (tl < n_tiles) tile_docs(off, n_docs, tl, n_tiles, ds, de, tdlo, tdhi);
+    }
     __syncthreads();
     for (unsigned b = 0; b < (unsigned)XGROUP; b += LL_WAVES) {
         const unsigned long long t = (unsigned long long)g * XGROUP + b + w;
@@ -2376,15 +2420,26 @@ pfac_ll_tiles_kernel(const void *rec, const unsigned long long *tix, unsigned lo
             const unsigned long long lo = e & TIX_BASE_MASK;
             const unsigned tb = (unsigned)(t * WTILE);
             tend = t + 1 == n_tiles ? (unsigned)(n_owned - t * WTILE) : (unsigned)WTILE;
+            DocWin dw{};
+            if constexpr (DOCS)
+                if (c) dw = doc_window(off, __shfl(tdlo, (int)(b + w), WAVE), __shfl(tdhi, (int)(b + w), WAVE), lane);
             for (unsigned c0 = 0; c0 < c; c0 += WAVE) {
                 const unsigned i = c0 + (unsigned)lane;
-                const bool have = i < c && lo + i < cap;
-                unsigned pos = 0, st = 0, pn = 0, sn = 0;
-                if (have) heap_record<BYTES>(rec, lo + i, t, pos, st);
-                pn = __shfl(pos, (lane + 1) & (WAVE - 1), WAVE);
-                if (lane == WAVE - 1 && i + 1 < c && lo + i + 1 < cap) heap_record<BYTES>(rec, lo + i + 1, t, pn, sn);
-                const int len = final_len(flen, freg, fsmall, have, st);
-                const bool cand = have && (i + 1 >= c || pn != pos) && len > 0;   // the last (longest) record at pos
+                unsigned pos = 0, st = 0;
+                int len;
+                bool cand;
+                if constexpr (DOCS) {
+                    unsigned long long d;
+                    cand = ll_doc_candidate<BYTES>(rec, lo, c, i, cap, t, flen, freg, fsmall, dw, off, lane, pos, st, len, d);
+                } else {
+                    const bool have = i < c && lo + i < cap;
+                    unsigned pn = 0, sn = 0;
+                    if (have) heap_record<BYTES>(rec, lo + i, t, pos, st);
+                    pn = __shfl(pos, (lane + 1) & (WAVE - 1), WAVE);
+                    if (lane == WAVE - 1 && i + 1 < c && lo + i + 1 < cap) heap_record<BYTES>(rec, lo + i + 1, t, pn, sn);
+                    len = final_len(flen, freg, fsmall, have, st);
+                    cand = have && (i + 1 >= c || pn != pos) && len > 0;   // the last (longest) record at pos
+                }
                 const unsigned long long bal = __ballot(cand);
                 const unsigned k = K + (unsigned)__popcll(bal & ((1ull << lane) - 1ull));
                 if (cand && k < (unsigned)WTILE) {             // (positions are distinct: at most 4096 candidates)
@@ -2575,6 +2630,78 @@ __global__ void pfac_ll_write_kernel(const void *rec, const unsigned long long *
                 out[k + (unsigned)__popcll(bal & ((1ull << lane) - 1ull))] = o;
             }
             k += (unsigned)__popcll(bal);
+        }
+    }
+}
+
+// The per-document selection's write (one wave per group of 64 tiles): a record is written when it is the candidate
+// under ll_doc_candidate's rule and its position bit is set, at its tile's prefix plus a ballot rank, as {pos, state}
+// with pos relative to the scan.  doc_first[d] for every document d that starts in the tile = the tile's prefix plus
+// the picks of the tile in front of off[d] (a pick of document d' < d lies before off[d], one of d' >= d at or after
+// it): a popcount over the tile's bitmap, every lane one document, so no lane walks a run of documents.
+template <int BYTES>
+__global__ void pfac_ll_doc_write_kernel(const void *rec, const unsigned long long *tix, unsigned long long n_tiles,
+                                         unsigned long long cap, const unsigned long long *off, unsigned long long n_docs,
+                                         const short *flen, unsigned num_final, const unsigned long long *bits,
+                                         const unsigned *tcnt, const unsigned long long *gpre, unsigned n_groups,
+                                         pfac_record *out, unsigned long long *doc_first) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    const unsigned g = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (g >= n_groups) return;
+    const bool fsmall = num_final <= (unsigned)WAVE;
+    const int freg = fsmall && (unsigned)lane < num_final ? (int)flen[lane] : 0;
+    const unsigned long long t = (unsigned long long)g * XGROUP + lane;
+    const unsigned long long e = t < n_tiles ? tix[t] : 0ull;
+    const unsigned c = (unsigned)(e >> TIX_CNT_SHIFT);
+    const unsigned long long lo = e & TIX_BASE_MASK;
+    const unsigned kc = t < n_tiles ? tcnt[t] : 0u;
+    const unsigned long long off0 = gpre[g] + (wave_incl_scan(kc) - kc);   // sorted index of the tile's first pick
+    unsigned long long ds = 0, de = 0, dlo = 0, dhi = 0;
+    if (t < n_tiles) tile_docs(off, n_docs, t, n_tiles, ds, de, dlo, dhi);
+    for (int j = 0; j < XGROUP; j++) {
+        const unsigned long long tj = (unsigned long long)g * XGROUP + j;
+        if (tj >= n_tiles) break;
+        const unsigned kt = __shfl(kc, j, WAVE);
+        const unsigned long long k0 = __shfl(off0, j, WAVE);
+        const unsigned long long *tb = bits + tj * (WTILE / 64);
+        if (kt) {
+            const unsigned tc = __shfl(c, j, WAVE);
+            const unsigned long long tlo = __shfl(lo, j, WAVE);
+            const DocWin w = doc_window(off, __shfl(dlo, j, WAVE), __shfl(dhi, j, WAVE), lane);
+            unsigned long long k = k0;
+            for (unsigned c0 = 0; c0 < tc; c0 += WAVE) {
+                unsigned pos, st;
+                int len;
+                unsigned long long d;
+                const bool cand = ll_doc_candidate<BYTES>(rec, tlo, tc, c0 + (unsigned)lane, cap, tj, flen, freg, fsmall, w,
+                                                          off, lane, pos, st, len, d);
+                const unsigned p = pos - (unsigned)(tj * WTILE);
+                const bool sel = cand && ((tb[p >> 6] >> (p & 63u)) & 1ull);
+                const unsigned long long bal = __ballot(sel);
+                if (sel) {
+                    pfac_record o;
+                    o.pos = pos;
+                    o.state = st;
+                    out[k + (unsigned)__popcll(bal & ((1ull << lane) - 1ull))] = o;
+                }
+                k += (unsigned)__popcll(bal);
+            }
+        }
+        const unsigned long long tds = __shfl(ds, j, WAVE), tde = __shfl(de, j, WAVE);
+        if (tds < tde) {
+            const unsigned long long bw = kt ? tb[lane] : 0ull;       // picks at tile offsets 64 lane .. 64 lane + 63
+            const unsigned pc = (unsigned)__popcll(bw), below = wave_incl_scan(pc) - pc;
+            for (unsigned long long d0 = tds; d0 < tde; d0 += WAVE) {
+                const unsigned long long dd = d0 + (unsigned)lane;
+                const bool v = dd < tde;
+                const unsigned long long x = v ? off[dd] - tj * WTILE : 0ull;   // in [0, 4096] (checked offsets)
+                const unsigned o = (unsigned)min(x, (unsigned long long)WTILE);
+                const int wi = (int)min(o >> 6, 63u);
+                const unsigned long long m = o >= (unsigned)WTILE ? ~0ull : (1ull << (o & 63u)) - 1ull;
+                const unsigned long long wbits = __shfl(bw, wi, WAVE);
+                const unsigned cnt = __shfl(below, wi, WAVE) + (unsigned)__popcll(wbits & m);
+                if (v) doc_first[dd] = k0 + cnt;
+            }
         }
     }
 }
@@ -2845,6 +2972,42 @@ pfac_rp_write_kernel(const unsigned char *in, unsigned long long n_avail, const 
     }
 }
 
+// Per-document output offsets (pfac_replace_documents), for a selection made from entry 0: out_off[d] = off[d] +
+// D_{doc_first[d]}, D_k = sum_{j<k} (R_j - L_j).  Two kernels, O(n_picks + n_docs), no walk over a range:
+//   pfac_rp_doc_delta_kernel    one wave per block of 64 picks: D_k for every pick, D[n] = the total.  The block's base
+//                               comes from the count kernel: O_{64b} = c_{64b-1} + D_{64b} (entry 0).
+//   pfac_rp_doc_offsets_kernel  one thread per document.
+__global__ void __launch_bounds__(4 * WAVE)
+pfac_rp_doc_delta_kernel(const pfac_record *sel, unsigned long long n, const short *flen, const unsigned *roff,
+                         const unsigned long long *X, const unsigned long long *gpre, unsigned long long *D) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    const unsigned long long b = (unsigned long long)blockIdx.x * 4 + (threadIdx.x >> 6), k = b * RP_BLOCK + (unsigned)lane;
+    if (b * RP_BLOCK >= n) return;
+    unsigned long long dk = 0;
+    if (k < n) {
+        const pfac_record r = sel[k];
+        dk = (unsigned long long)((long long)(roff[r.state + 1] - roff[r.state]) - (long long)flen[r.state]);
+    }
+    unsigned long long base = 0;                                // D_{64b}
+    if (b > 0) {
+        const pfac_record r = sel[b * RP_BLOCK - 1];
+        base = X[b] + gpre[b / RP_GROUP] - ((unsigned long long)r.pos + (unsigned long long)flen[r.state]);
+    }
+    const unsigned long long incl = base + wave_incl_scan64(dk);
+    if (k < n) D[k] = incl - dk;
+    if (k + 1 == n) D[n] = incl;
+}
+
+__global__ void pfac_rp_doc_offsets_kernel(const unsigned long long *off, const unsigned long long *doc_first,
+                                           unsigned long long n_docs, const unsigned long long *D, unsigned long long n,
+                                           unsigned long long *out_off) {
+    const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
+    for (unsigned long long d = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; d <= n_docs; d += stride) {
+        const unsigned long long f = doc_first[d];
+        out_off[d] = off[d] + (n ? D[f < n ? f : n] : 0ull);
+    }
+}
+
 // ---------------------------------------------------------------------------
 // GPU-side text emitter (replaces the fprintf loop of main.cc:335-350 on the device): the compact records of a scan ->
 // the lines  "At position %4d, match pattern %d\n"  in output order, in one device buffer.  Three kernels: bytes per
@@ -3072,6 +3235,18 @@ struct Slot {
     unsigned char *d_rp_out = nullptr;    // slot-owned output (d_out NULL)
     uint64_t rp_out_cap = 0, rp_bytes = 0;
     bool rp_done = false, rp_own_out = false;
+    // pfac_records_leftmost_longest_documents / pfac_replace_documents
+    uint64_t doc_gen = 0;                 // pfac_slot_doc_offsets calls: a selection remembers the offsets it cut with
+    bool ll_docs = false;                 // the slot's last selection was per document, ...
+    uint64_t lld_docs = 0, lld_gen = 0;   // ... over this many documents, with the slot's offsets of this generation
+    bool lld_own_off = false, lld_own_first = false;   // (or the caller's offsets / doc_first)
+    unsigned long long *d_lld_first = nullptr;   // slot-owned doc_first (d_doc_first NULL)
+    uint64_t lld_first_cap = 0;
+    unsigned long long *d_rpd_tmp = nullptr;     // D_k per pick (and the total behind them)
+    uint64_t rpd_tmp_cap = 0;
+    unsigned long long *d_rpd_off = nullptr;     // slot-owned output offsets (d_out_offsets NULL)
+    uint64_t rpd_off_cap = 0, rpd_docs = 0;
+    bool rpd_done = false, rpd_own_off = false;
 };
 
 }  // namespace
@@ -3599,6 +3774,9 @@ void pfac_ctx_destroy(pfac_ctx *ctx) {
         if (s.d_ll_out) (void)hipFree(s.d_ll_out);
         if (s.d_rp_tmp) (void)hipFree(s.d_rp_tmp);
         if (s.d_rp_out) (void)hipFree(s.d_rp_out);
+        if (s.d_lld_first) (void)hipFree(s.d_lld_first);
+        if (s.d_rpd_tmp) (void)hipFree(s.d_rpd_tmp);
+        if (s.d_rpd_off) (void)hipFree(s.d_rpd_off);
         if (s.d_sum) (void)hipFree(s.d_sum);
         if (s.h_ctl) (void)hipHostFree(s.h_ctl);
         if (s.ev0) (void)hipEventDestroy(s.ev0);
@@ -4148,6 +4326,7 @@ int pfac_slot_doc_offsets(pfac_ctx *ctx, int slot, const uint64_t *host_offsets,
     HIP_TRY(ctx, hipStreamSynchronize(s.stream));        // (the caller's array may go once this returns)
     s.doc_n = n_docs;
     s.doc_set = true;
+    s.doc_gen++;
     return PFAC_OK;
 }
 
@@ -4253,37 +4432,97 @@ int pfac_segment_d2h(pfac_ctx *ctx, int slot, pfac_record *host_records, uint64_
     return PFAC_OK;
 }
 
-int pfac_records_leftmost_longest(pfac_ctx *ctx, int slot, const void *d_records, uint32_t entry, pfac_record *d_out,
-                                  uint64_t out_cap, uint64_t *n_selected, uint32_t *exit_offset) {
-    int rc = check_slot(ctx, slot);
-    if (rc) return rc;
-    if (!n_selected || !exit_offset) return fail(ctx, PFAC_E_ARG, "null argument");
-    *n_selected = 0;
-    *exit_offset = entry;
-    Slot &s = ctx->slots[slot];
+// The documents of a per-document selection, as the caller passed them (NULL: the slot's offsets / a slot-owned
+// doc_first); ll_select without them makes the plain selection.
+struct LlDocs {
+    const uint64_t *off;
+    uint64_t n_docs;
+    uint64_t *first;
+};
+
+// The slot-owned doc_first of a per-document selection, grown to n_docs + 1 entries.
+static int lld_first_buffer(pfac_ctx *ctx, Slot &s, uint64_t n_docs) {
+    if (n_docs + 1 <= s.lld_first_cap) return PFAC_OK;
+    if (s.d_lld_first) { HIP_TRY(ctx, hipStreamSynchronize(s.stream)); HIP_TRY(ctx, hipFree(s.d_lld_first)); s.d_lld_first = nullptr; s.lld_first_cap = 0; }
+    const uint64_t cap = n_docs + 1 < 4096 ? 4096 : n_docs + 1 + n_docs / 4;
+    HIP_TRY(ctx, hipMalloc((void **)&s.d_lld_first, cap * 8));
+    s.lld_first_cap = cap;
+    return PFAC_OK;
+}
+
+// pfac_records_leftmost_longest, and with `docs` pfac_records_leftmost_longest_documents (entry 0): the same kernels,
+// the tile passes in their document form, and the document write.
+static int ll_select(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *d_records, uint32_t entry, pfac_record *d_out,
+                     uint64_t out_cap, uint64_t *n_selected, uint32_t *exit_offset, const LlDocs *docs) {
     s.ll_done = false;
-    if (!s.scanned || s.pending) return fail(ctx, PFAC_E_STATE, "pfac_records_leftmost_longest needs a finished scan");
-    if (!ctx->have_table || !ctx->d_flen) return fail(ctx, PFAC_E_STATE, "pfac_records_leftmost_longest: no final-state lengths for the uploaded table (pfac_table_set_final_lengths)");
-    if (s.last_table != ctx->table_gen) return fail(ctx, PFAC_E_STATE, "pfac_records_leftmost_longest: the slot's last scan ran with an earlier table");
-    if (s.last_used > s.last_cap) return fail(ctx, PFAC_E_STATE, "pfac_records_leftmost_longest: the slot's last scan overflowed its record heap");
+    if (!s.scanned || s.pending) return fail(ctx, PFAC_E_STATE, fn + " needs a finished scan");
+    if (!ctx->have_table || !ctx->d_flen) return fail(ctx, PFAC_E_STATE, fn + ": no final-state lengths for the uploaded table (pfac_table_set_final_lengths)");
+    if (s.last_table != ctx->table_gen) return fail(ctx, PFAC_E_STATE, fn + ": the slot's last scan ran with an earlier table");
+    if (s.last_used > s.last_cap) return fail(ctx, PFAC_E_STATE, fn + ": the slot's last scan overflowed its record heap");
     const unsigned M = (unsigned)ctx->max_pat_len;
-    if (entry > M) return fail(ctx, PFAC_E_ARG, "pfac_records_leftmost_longest: entry " + std::to_string(entry) + " exceeds max_pat_len " + std::to_string(M));
+    if (entry > M) return fail(ctx, PFAC_E_ARG, fn + ": entry " + std::to_string(entry) + " exceeds max_pat_len " + std::to_string(M));
     const int rb = s.last_rec_bytes;
     const void *src = d_records ? d_records : s.d_records;
     if (((uintptr_t)d_out & 7) || ((uintptr_t)src & (uintptr_t)(rb - 1)))
-        return fail(ctx, PFAC_E_ARG, "pfac_records_leftmost_longest: misaligned buffer (d_out 8 B, records their width)");
+        return fail(ctx, PFAC_E_ARG, fn + ": misaligned buffer (d_out 8 B, records their width)");
     if (!src && s.last_tiles) return fail(ctx, PFAC_E_ARG, "null record buffer");
+    const unsigned long long *off = nullptr;
+    const uint64_t n_docs = docs ? docs->n_docs : 0;
+    if (docs) {                                             // (the rules of pfac_records_segment)
+        off = reinterpret_cast<const unsigned long long *>(docs->off);
+        if (!off) {
+            if (!s.doc_set) return fail(ctx, PFAC_E_STATE, fn + ": no document offsets for the slot (pfac_slot_doc_offsets)");
+            if (n_docs != s.doc_n) return fail(ctx, PFAC_E_ARG, fn + ": n_docs differs from the slot's document offsets");
+            off = s.d_doc_off;
+        }
+        if (n_docs >= (1ull << 32)) return fail(ctx, PFAC_E_ARG, fn + ": n_docs must be below 2^32");
+        if (n_docs == 0 && s.last_owned != 0) return fail(ctx, PFAC_E_ARG, fn + ": no documents, but the scan owns bytes");
+        if (((uintptr_t)off & 7) || ((uintptr_t)docs->first & 7))
+            return fail(ctx, PFAC_E_ARG, fn + ": device buffers must be 8-byte aligned");
+    }
     USE_DEVICE(ctx);
     const uint64_t n_tiles = s.last_tiles;
-    const bool own_out = d_out == nullptr;
-    s.ll_seq = s.scan_seq;
-    s.ll_entry = entry;
-    if (n_tiles == 0) {                                     // nothing scanned: nothing picked, the cursor stays
-        s.ll_n = 0;
-        s.ll_exit = entry;
+    const bool own_out = d_out == nullptr, own_first = docs && !docs->first;
+    unsigned long long *first = docs ? reinterpret_cast<unsigned long long *>(docs->first) : nullptr;
+    auto done = [&](uint64_t total, uint32_t ex) {
+        s.ll_seq = s.scan_seq;
+        s.ll_entry = entry;
+        s.ll_n = total;
+        s.ll_exit = ex;
         s.ll_own_out = own_out;
+        s.ll_docs = docs != nullptr;
+        if (docs) {
+            s.lld_docs = n_docs;
+            s.lld_gen = s.doc_gen;
+            s.lld_own_off = docs->off == nullptr;
+            s.lld_own_first = own_first;
+        }
         s.ll_done = true;
         return PFAC_OK;
+    };
+    int rc;
+    if (n_tiles == 0) {                                     // nothing scanned: nothing picked, the cursor stays
+        if (!docs) return done(0, entry);
+        // every document is empty: check the offsets (pfac_seg_count_kernel without tiles), then doc_first = 0
+        rc = ensure_gsum(ctx, s, 1);
+        if (rc) return rc;
+        HIP_TRY(ctx, hipMemsetAsync(s.d_gsum, 0, 8, s.stream));
+        const unsigned vblocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_docs + 255) / 256, 4096));
+        hipLaunchKernelGGL(pfac_seg_count_kernel<4>, dim3(vblocks), dim3(256), 0, s.stream, (const void *)nullptr,
+                           (const unsigned long long *)nullptr, 0ull, 0ull, off, (unsigned long long)n_docs, 0ull,
+                           ctx->d_flen, (unsigned)ctx->num_final, (unsigned *)nullptr, (unsigned long long *)nullptr, 0u, s.d_gsum);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(s.h_ctl + 12, s.d_gsum, 8, hipMemcpyDeviceToHost, s.stream));
+        HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+        if (s.h_ctl[12] | s.h_ctl[13])
+            return fail(ctx, PFAC_E_ARG, fn + ": document offsets must start at 0, not decrease, and end at the scan's n_owned (0)");
+        if (own_first) {
+            rc = lld_first_buffer(ctx, s, n_docs);
+            if (rc) return rc;
+            first = s.d_lld_first;
+        }
+        HIP_TRY(ctx, hipMemsetAsync(first, 0, (n_docs + 1) * 8, s.stream));
+        return done(0, entry);
     }
     const unsigned n_groups = (unsigned)((n_tiles + XGROUP - 1) / XGROUP), nb = (n_groups + XGROUP - 1) / XGROUP;
     const unsigned M1 = M + 1, FS = ll_fun_stride(M1);
@@ -4302,32 +4541,45 @@ int pfac_records_leftmost_longest(pfac_ctx *ctx, int slot, const void *d_records
     unsigned short *hat = reinterpret_cast<unsigned short *>(s.d_ll_tmp + o_hat), *gat = reinterpret_cast<unsigned short *>(s.d_ll_tmp + o_gat);
     unsigned *tcnt = reinterpret_cast<unsigned *>(s.d_ll_tmp + o_tcnt);
     unsigned long long *bits = reinterpret_cast<unsigned long long *>(s.d_ll_tmp + o_bits);
-    rc = ensure_gsum(ctx, s, n_groups + 1);                 // group prefixes, the total, the exit offset
+    rc = ensure_gsum(ctx, s, n_groups + 2);                 // group prefixes, the total, the exit offset, the offsets' error word
     if (rc) return rc;
+    unsigned long long *bad = docs ? s.d_gsum + n_groups + 2 : nullptr;
+    if (docs) HIP_TRY(ctx, hipMemsetAsync(bad, 0, 8, s.stream));
     auto fk = rb == 2 ? pfac_ll_tiles_kernel<2, false> : (rb == 4 ? pfac_ll_tiles_kernel<4, false> : pfac_ll_tiles_kernel<8, false>);
     auto mk = rb == 2 ? pfac_ll_tiles_kernel<2, true> : (rb == 4 ? pfac_ll_tiles_kernel<4, true> : pfac_ll_tiles_kernel<8, true>);
+    if (docs) {
+        fk = rb == 2 ? pfac_ll_tiles_kernel<2, false, true> : (rb == 4 ? pfac_ll_tiles_kernel<4, false, true> : pfac_ll_tiles_kernel<8, false, true>);
+        mk = rb == 2 ? pfac_ll_tiles_kernel<2, true, true> : (rb == 4 ? pfac_ll_tiles_kernel<4, true, true> : pfac_ll_tiles_kernel<8, true, true>);
+    }
     const size_t lds = ll_tiles_lds(M1);
     HIP_TRY(ctx, hipFuncSetAttribute((const void *)fk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     HIP_TRY(ctx, hipFuncSetAttribute((const void *)mk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const unsigned long long nt = n_tiles, cap = s.last_cap, own = s.last_owned;
+    const unsigned long long nt = n_tiles, cap = s.last_cap, own = s.last_owned, nd = n_docs;
     hipLaunchKernelGGL(fk, dim3(n_groups), dim3(LL_WAVES * WAVE), lds, s.stream, src, s.d_tile_index, nt, cap, own, ctx->d_flen,
-                       (unsigned)ctx->num_final, M, gfun, (const unsigned short *)nullptr, bits, tcnt, s.d_gsum);
+                       (unsigned)ctx->num_final, M, gfun, (const unsigned short *)nullptr, bits, tcnt, s.d_gsum, off, nd, bad);
     hipLaunchKernelGGL(pfac_ll_compose_kernel, dim3(nb), dim3(1024), LL_CHUNK_BYTES, s.stream, gfun, M1, n_groups, (unsigned)XGROUP, hfun);
     hipLaunchKernelGGL(pfac_ll_walk_kernel, dim3(1), dim3(256), LL_CHUNK_BYTES, s.stream, hfun, M1, nb, nb, (const unsigned short *)nullptr,
                        (unsigned)entry, hat, s.d_gsum + n_groups + 1);
     hipLaunchKernelGGL(pfac_ll_walk_kernel, dim3(nb), dim3(256), LL_CHUNK_BYTES, s.stream, gfun, M1, n_groups, (unsigned)XGROUP,
                        (const unsigned short *)hat, 0u, gat, (unsigned long long *)nullptr);
     hipLaunchKernelGGL(mk, dim3(n_groups), dim3(LL_WAVES * WAVE), lds, s.stream, src, s.d_tile_index, nt, cap, own, ctx->d_flen,
-                       (unsigned)ctx->num_final, M, (unsigned short *)nullptr, (const unsigned short *)gat, bits, tcnt, s.d_gsum);
+                       (unsigned)ctx->num_final, M, (unsigned short *)nullptr, (const unsigned short *)gat, bits, tcnt, s.d_gsum,
+                       off, nd, (unsigned long long *)nullptr);
     hipLaunchKernelGGL(pfac_scan_groups_kernel, dim3(1), dim3(1024), 0, s.stream, s.d_gsum, n_groups);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(s.h_ctl + 10, s.d_gsum + n_groups, 16, hipMemcpyDeviceToHost, s.stream));
+    HIP_TRY(ctx, hipMemcpyAsync(s.h_ctl + 10, s.d_gsum + n_groups, docs ? 24 : 16, hipMemcpyDeviceToHost, s.stream));
     HIP_TRY(ctx, hipStreamSynchronize(s.stream));
     const uint64_t total = ((uint64_t)s.h_ctl[11] << 32) | s.h_ctl[10];
+    if (docs) {
+        if (s.h_ctl[14] | s.h_ctl[15])
+            return fail(ctx, PFAC_E_ARG, fn + ": document offsets must start at 0, not decrease, and end at the scan's n_owned (" +
+                                             std::to_string(s.last_owned) + ")");
+        if (s.h_ctl[12]) return fail(ctx, PFAC_E_INTERNAL, fn + ": a pick ran past the last document");
+    }
     *n_selected = total;
     *exit_offset = s.h_ctl[12];
     if (!own_out && total > out_cap)
-        return fail(ctx, PFAC_E_OVERFLOW, "pfac_records_leftmost_longest: " + std::to_string(total) + " records selected, out_cap is " + std::to_string(out_cap));
+        return fail(ctx, PFAC_E_OVERFLOW, fn + ": " + std::to_string(total) + " records selected, out_cap is " + std::to_string(out_cap));
     if (own_out && total > s.ll_out_cap) {
         if (s.d_ll_out) { HIP_TRY(ctx, hipFree(s.d_ll_out)); s.d_ll_out = nullptr; s.ll_out_cap = 0; }
         const uint64_t ocap = total + total / 8 + 4096;
@@ -4335,17 +4587,47 @@ int pfac_records_leftmost_longest(pfac_ctx *ctx, int slot, const void *d_records
         s.ll_out_cap = ocap;
     }
     pfac_record *out = own_out ? s.d_ll_out : d_out;
-    if (total) {
+    if (docs) {
+        if (own_first) {
+            rc = lld_first_buffer(ctx, s, n_docs);
+            if (rc) return rc;
+            first = s.d_lld_first;
+        }
+        auto wk = rb == 2 ? pfac_ll_doc_write_kernel<2> : (rb == 4 ? pfac_ll_doc_write_kernel<4> : pfac_ll_doc_write_kernel<8>);
+        hipLaunchKernelGGL(wk, dim3((n_groups + 3) / 4), dim3(256), 0, s.stream, src, s.d_tile_index, nt, cap, off, nd, ctx->d_flen,
+                           (unsigned)ctx->num_final, bits, tcnt, s.d_gsum, n_groups, out, first);
+        HIP_TRY(ctx, hipGetLastError());
+    } else if (total) {
         auto wk = rb == 2 ? pfac_ll_write_kernel<2> : (rb == 4 ? pfac_ll_write_kernel<4> : pfac_ll_write_kernel<8>);
         hipLaunchKernelGGL(wk, dim3((n_groups + 3) / 4), dim3(256), 0, s.stream, src, s.d_tile_index, nt, cap, bits, tcnt, s.d_gsum,
                            n_groups, out);
         HIP_TRY(ctx, hipGetLastError());
     }
-    s.ll_n = total;
-    s.ll_exit = *exit_offset;
-    s.ll_own_out = own_out;
-    s.ll_done = true;
-    return PFAC_OK;
+    return done(total, *exit_offset);
+}
+
+int pfac_records_leftmost_longest(pfac_ctx *ctx, int slot, const void *d_records, uint32_t entry, pfac_record *d_out,
+                                  uint64_t out_cap, uint64_t *n_selected, uint32_t *exit_offset) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    if (!n_selected || !exit_offset) return fail(ctx, PFAC_E_ARG, "null argument");
+    *n_selected = 0;
+    *exit_offset = entry;
+    return ll_select(ctx, ctx->slots[slot], "pfac_records_leftmost_longest", d_records, entry, d_out, out_cap, n_selected,
+                     exit_offset, nullptr);
+}
+
+int pfac_records_leftmost_longest_documents(pfac_ctx *ctx, int slot, const void *d_records, const uint64_t *d_doc_offsets,
+                                            uint64_t n_docs, pfac_record *d_out, uint64_t out_cap, uint64_t *d_doc_first,
+                                            uint64_t *n_selected) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    if (!n_selected) return fail(ctx, PFAC_E_ARG, "null argument");
+    *n_selected = 0;
+    uint32_t ex = 0;
+    const LlDocs docs{d_doc_offsets, n_docs, d_doc_first};
+    return ll_select(ctx, ctx->slots[slot], "pfac_records_leftmost_longest_documents", d_records, 0, d_out, out_cap, n_selected,
+                     &ex, &docs);
 }
 
 int pfac_leftmost_longest_d2h(pfac_ctx *ctx, int slot, pfac_record *host) {
@@ -4357,6 +4639,22 @@ int pfac_leftmost_longest_d2h(pfac_ctx *ctx, int slot, pfac_record *host) {
     if (!host && s.ll_n) return fail(ctx, PFAC_E_ARG, "null host buffer");
     USE_DEVICE(ctx);
     if (s.ll_n) HIP_TRY(ctx, hipMemcpyAsync(host, s.d_ll_out, s.ll_n * sizeof(pfac_record), hipMemcpyDeviceToHost, s.stream));
+    return PFAC_OK;
+}
+
+int pfac_leftmost_longest_documents_d2h(pfac_ctx *ctx, int slot, pfac_record *host_records, uint64_t *host_doc_first) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    Slot &s = ctx->slots[slot];
+    if (!s.ll_done || !s.ll_docs)
+        return fail(ctx, PFAC_E_STATE, "pfac_leftmost_longest_documents_d2h without a finished pfac_records_leftmost_longest_documents");
+    if ((host_records && !s.ll_own_out) || (host_doc_first && !s.lld_own_first))
+        return fail(ctx, PFAC_E_STATE, "pfac_leftmost_longest_documents_d2h: the last selection wrote into the caller's buffers");
+    USE_DEVICE(ctx);
+    if (host_records && s.ll_n)
+        HIP_TRY(ctx, hipMemcpyAsync(host_records, s.d_ll_out, s.ll_n * sizeof(pfac_record), hipMemcpyDeviceToHost, s.stream));
+    if (host_doc_first)
+        HIP_TRY(ctx, hipMemcpyAsync(host_doc_first, s.d_lld_first, (s.lld_docs + 1) * 8, hipMemcpyDeviceToHost, s.stream));
     return PFAC_OK;
 }
 
@@ -4387,35 +4685,58 @@ int pfac_table_set_replacements(pfac_ctx *ctx, const uint32_t *offsets, uint64_t
     return PFAC_OK;
 }
 
-int pfac_replace_leftmost_longest(pfac_ctx *ctx, int slot, const void *d_input, const pfac_record *d_sel, void *d_out,
-                                  uint64_t out_cap, uint64_t *out_bytes) {
-    int rc = check_slot(ctx, slot);
-    if (rc) return rc;
-    if (!out_bytes) return fail(ctx, PFAC_E_ARG, "null argument");
-    *out_bytes = 0;
-    Slot &s = ctx->slots[slot];
+// The documents of pfac_replace_documents as the caller passed them (NULL: the slot's offsets / doc_first of the
+// selection, the slot-owned output offsets); rp_run without them is pfac_replace_leftmost_longest.
+struct RpDocs {
+    const uint64_t *off, *first;
+    uint64_t *out_off;
+};
+
+static int rp_run(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *d_input, const pfac_record *d_sel, void *d_out,
+                  uint64_t out_cap, uint64_t *out_bytes, const RpDocs *docs) {
     s.rp_done = false;
-    if (!s.ll_done || s.ll_seq != s.scan_seq)
-        return fail(ctx, PFAC_E_STATE, "pfac_replace_leftmost_longest needs a pfac_records_leftmost_longest since the slot's last scan");
+    s.rpd_done = false;
+    if (!s.ll_done || s.ll_seq != s.scan_seq || (docs && !s.ll_docs))
+        return fail(ctx, PFAC_E_STATE, fn + (docs ? " needs a pfac_records_leftmost_longest_documents since the slot's last scan"
+                                                  : " needs a pfac_records_leftmost_longest since the slot's last scan"));
     if (!ctx->have_table || s.last_table != ctx->table_gen)
-        return fail(ctx, PFAC_E_STATE, "pfac_replace_leftmost_longest: the selection was made with an earlier table");
-    if (!ctx->d_rep) return fail(ctx, PFAC_E_STATE, "pfac_replace_leftmost_longest: no replacements for the uploaded table (pfac_table_set_replacements)");
-    if (!ctx->d_flen) return fail(ctx, PFAC_E_STATE, "pfac_replace_leftmost_longest: no final-state lengths for the uploaded table");
+        return fail(ctx, PFAC_E_STATE, fn + ": the selection was made with an earlier table");
+    if (!ctx->d_rep) return fail(ctx, PFAC_E_STATE, fn + ": no replacements for the uploaded table (pfac_table_set_replacements)");
+    if (!ctx->d_flen) return fail(ctx, PFAC_E_STATE, fn + ": no final-state lengths for the uploaded table");
     if (!d_sel && !s.ll_own_out)
-        return fail(ctx, PFAC_E_STATE, "pfac_replace_leftmost_longest: the selection went to the caller's buffer; pass it as d_sel");
+        return fail(ctx, PFAC_E_STATE, fn + ": the selection went to the caller's buffer; pass it as d_sel");
     const pfac_record *sel = d_sel ? d_sel : s.d_ll_out;
     const unsigned char *in = d_input ? static_cast<const unsigned char *>(d_input) : s.d_input;
     const uint64_t n = s.ll_n, n_owned = s.last_owned, n_avail = s.last_avail, entry = s.ll_entry, ex = s.ll_exit;
     if (((uintptr_t)d_out & 15) || ((uintptr_t)in & 15) || ((uintptr_t)d_sel & 7))
-        return fail(ctx, PFAC_E_ARG, "pfac_replace_leftmost_longest: misaligned buffer (d_input and d_out 16 B, d_sel 8 B)");
-    if (n_owned > entry && !in) return fail(ctx, PFAC_E_ARG, "pfac_replace_leftmost_longest: no input buffer");
-    if (!d_input && n_avail > s.input_cap) return fail(ctx, PFAC_E_ARG, "pfac_replace_leftmost_longest: the scan read more than the slot's input buffer holds");
+        return fail(ctx, PFAC_E_ARG, fn + ": misaligned buffer (d_input and d_out 16 B, d_sel 8 B)");
+    if (n_owned > entry && !in) return fail(ctx, PFAC_E_ARG, fn + ": no input buffer");
+    if (!d_input && n_avail > s.input_cap) return fail(ctx, PFAC_E_ARG, fn + ": the scan read more than the slot's input buffer holds");
+    const unsigned long long *doff = nullptr, *dfirst = nullptr;
+    unsigned long long *dout_off = nullptr;
+    if (docs) {
+        doff = reinterpret_cast<const unsigned long long *>(docs->off);
+        dfirst = reinterpret_cast<const unsigned long long *>(docs->first);
+        dout_off = reinterpret_cast<unsigned long long *>(docs->out_off);
+        if (!doff) {
+            if (!s.lld_own_off) return fail(ctx, PFAC_E_STATE, fn + ": the selection cut the caller's document offsets; pass them as d_doc_offsets");
+            if (s.lld_gen != s.doc_gen || !s.doc_set) return fail(ctx, PFAC_E_STATE, fn + ": the slot's document offsets changed since the selection");
+            doff = s.d_doc_off;
+        }
+        if (!dfirst) {
+            if (!s.lld_own_first) return fail(ctx, PFAC_E_STATE, fn + ": the selection's doc_first went to the caller's buffer; pass it as d_doc_first");
+            dfirst = s.d_lld_first;
+        }
+        if (((uintptr_t)doff & 7) || ((uintptr_t)dfirst & 7) || ((uintptr_t)dout_off & 7))
+            return fail(ctx, PFAC_E_ARG, fn + ": device buffers must be 8-byte aligned");
+    }
     USE_DEVICE(ctx);
     int64_t delta = 0;
     const uint64_t nb = n ? (n + RP_BLOCK - 1) / RP_BLOCK : 1;
     const uint64_t n_groups = (nb + RP_GROUP - 1) / RP_GROUP;
-    if (n_groups >= (1ull << 32)) return fail(ctx, PFAC_E_ARG, "pfac_replace_leftmost_longest: too many picks");
+    if (n_groups >= (1ull << 32)) return fail(ctx, PFAC_E_ARG, fn + ": too many picks");
     unsigned long long *X = nullptr;
+    int rc;
     if (n) {
         const size_t need = nb * 8;
         if (need > s.rp_tmp_cap) {
@@ -4440,15 +4761,30 @@ int pfac_replace_leftmost_longest(pfac_ctx *ctx, int slot, const void *d_input, 
         const uint64_t err = ((uint64_t)s.h_ctl[13] << 32) | s.h_ctl[12];
         const uint64_t c_last = ((uint64_t)s.h_ctl[15] << 32) | s.h_ctl[14];
         if (err || (c_last > n_owned ? c_last - n_owned : 0) != ex)
-            return fail(ctx, PFAC_E_ARG, "pfac_replace_leftmost_longest: the selection is not one of this scan and table");
+            return fail(ctx, PFAC_E_ARG, fn + ": the selection is not one of this scan and table");
     }
     const int64_t total = (int64_t)(n_owned + ex) - (int64_t)entry + delta;
-    if (total < 0) return fail(ctx, PFAC_E_INTERNAL, "pfac_replace_leftmost_longest: negative output length");
+    if (total < 0) return fail(ctx, PFAC_E_INTERNAL, fn + ": negative output length");
     const uint64_t ob = (uint64_t)total;
     *out_bytes = ob;
     const bool own_out = d_out == nullptr;
     if (!own_out && ob > out_cap)
-        return fail(ctx, PFAC_E_OVERFLOW, "pfac_replace_leftmost_longest: " + std::to_string(ob) + " output bytes, out_cap is " + std::to_string(out_cap));
+        return fail(ctx, PFAC_E_OVERFLOW, fn + ": " + std::to_string(ob) + " output bytes, out_cap is " + std::to_string(out_cap));
+    const uint64_t n_docs = s.lld_docs;
+    if (docs) {                                             // (everything allocated before the first write)
+        if (!dout_off && n_docs + 1 > s.rpd_off_cap) {
+            if (s.d_rpd_off) { HIP_TRY(ctx, hipStreamSynchronize(s.stream)); HIP_TRY(ctx, hipFree(s.d_rpd_off)); s.d_rpd_off = nullptr; s.rpd_off_cap = 0; }
+            const uint64_t cap = n_docs + 1 < 4096 ? 4096 : n_docs + 1 + n_docs / 4;
+            HIP_TRY(ctx, hipMalloc((void **)&s.d_rpd_off, cap * 8));
+            s.rpd_off_cap = cap;
+        }
+        if (n && n + 1 > s.rpd_tmp_cap) {
+            if (s.d_rpd_tmp) { HIP_TRY(ctx, hipStreamSynchronize(s.stream)); HIP_TRY(ctx, hipFree(s.d_rpd_tmp)); s.d_rpd_tmp = nullptr; s.rpd_tmp_cap = 0; }
+            const uint64_t cap = n + 1 + n / 8 + 4096;
+            HIP_TRY(ctx, hipMalloc((void **)&s.d_rpd_tmp, cap * 8));
+            s.rpd_tmp_cap = cap;
+        }
+    }
     if (own_out && ob > s.rp_out_cap) {
         if (s.d_rp_out) { HIP_TRY(ctx, hipStreamSynchronize(s.stream)); HIP_TRY(ctx, hipFree(s.d_rp_out)); s.d_rp_out = nullptr; s.rp_out_cap = 0; }
         const uint64_t cap = align_up(ob + ob / 8, 4096);
@@ -4469,9 +4805,53 @@ int pfac_replace_leftmost_longest(pfac_ctx *ctx, int slot, const void *d_input, 
                            (unsigned long long)ob, (unsigned)wins, out);
         HIP_TRY(ctx, hipGetLastError());
     }
+    if (docs) {
+        unsigned long long *oo = dout_off ? dout_off : s.d_rpd_off;
+        if (n)
+            hipLaunchKernelGGL(pfac_rp_doc_delta_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(4 * WAVE), 0, s.stream, sel,
+                               (unsigned long long)n, ctx->d_flen, ctx->d_rep_off, X, s.d_gsum, s.d_rpd_tmp);
+        const unsigned oblocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_docs + 1 + 255) / 256, 65536));
+        hipLaunchKernelGGL(pfac_rp_doc_offsets_kernel, dim3(oblocks), dim3(256), 0, s.stream, doff, dfirst,
+                           (unsigned long long)n_docs, (const unsigned long long *)s.d_rpd_tmp, (unsigned long long)n, oo);
+        HIP_TRY(ctx, hipGetLastError());
+        s.rpd_docs = n_docs;
+        s.rpd_own_off = dout_off == nullptr;
+        s.rpd_done = true;
+    }
     s.rp_bytes = ob;
     s.rp_own_out = own_out;
     s.rp_done = true;
+    return PFAC_OK;
+}
+
+int pfac_replace_leftmost_longest(pfac_ctx *ctx, int slot, const void *d_input, const pfac_record *d_sel, void *d_out,
+                                  uint64_t out_cap, uint64_t *out_bytes) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    if (!out_bytes) return fail(ctx, PFAC_E_ARG, "null argument");
+    *out_bytes = 0;
+    return rp_run(ctx, ctx->slots[slot], "pfac_replace_leftmost_longest", d_input, d_sel, d_out, out_cap, out_bytes, nullptr);
+}
+
+int pfac_replace_documents(pfac_ctx *ctx, int slot, const void *d_input, const pfac_record *d_sel, const uint64_t *d_doc_offsets,
+                           const uint64_t *d_doc_first, void *d_out, uint64_t out_cap, uint64_t *d_out_offsets, uint64_t *out_bytes) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    if (!out_bytes) return fail(ctx, PFAC_E_ARG, "null argument");
+    *out_bytes = 0;
+    const RpDocs docs{d_doc_offsets, d_doc_first, d_out_offsets};
+    return rp_run(ctx, ctx->slots[slot], "pfac_replace_documents", d_input, d_sel, d_out, out_cap, out_bytes, &docs);
+}
+
+int pfac_replace_documents_d2h(pfac_ctx *ctx, int slot, uint64_t *host_out_offsets) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    Slot &s = ctx->slots[slot];
+    if (!s.rpd_done) return fail(ctx, PFAC_E_STATE, "pfac_replace_documents_d2h without a finished pfac_replace_documents");
+    if (!s.rpd_own_off) return fail(ctx, PFAC_E_STATE, "pfac_replace_documents_d2h: the last replacement wrote its offsets into the caller's buffer");
+    if (!host_out_offsets) return fail(ctx, PFAC_E_ARG, "null host buffer");
+    USE_DEVICE(ctx);
+    HIP_TRY(ctx, hipMemcpyAsync(host_out_offsets, s.d_rpd_off, (s.rpd_docs + 1) * 8, hipMemcpyDeviceToHost, s.stream));
     return PFAC_OK;
 }
 

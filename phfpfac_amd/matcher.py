@@ -321,32 +321,26 @@ class GpuMatcher:
             self.table._final_lengths = lens          # once per table
         self.set_final_lengths(lens)
 
-    def scan_documents(self, docs, slot: int = 0) -> Tuple[np.ndarray, np.ndarray]:
-        """Match a batch of independent documents in one scan.  ``docs`` is a sequence of bytes-like objects, or a
-        ``(buffer, offsets)`` pair whose offsets (an integer array or list, n_docs + 1 of them, from 0 to len(buffer))
-        cut ``buffer`` into documents.  Returns (doc_first uint64[n_docs + 1], records): the records of document d are
-        ``records[doc_first[d]:doc_first[d + 1]]``, positions relative to the document, in (offset, pattern length)
-        order -- what scanning each document on its own yields."""
-        if (isinstance(docs, tuple) and len(docs) == 2 and isinstance(docs[1], (np.ndarray, list, range))
-                and np.asarray(docs[1]).dtype != np.uint8):
-            buf, offsets = docs
-            buf = np.frombuffer(buf, dtype=np.uint8) if not isinstance(buf, np.ndarray) else buf.view(np.uint8).ravel()
-            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        else:
-            parts = [np.frombuffer(d, dtype=np.uint8) if not isinstance(d, np.ndarray) else d.view(np.uint8).ravel()
-                     for d in docs]
-            offsets = np.zeros(len(parts) + 1, dtype=np.uint64)
-            if parts:
-                np.cumsum([p.size for p in parts], out=offsets[1:])
-            buf = np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint8)
+    def _scan_docs(self, docs, slot: int) -> Tuple[np.ndarray, int]:
+        """Upload and scan a batch of documents (``docs`` as ``scan_documents`` takes it) and set its offsets on the
+        slot.  Returns (offsets uint64[n_docs + 1], n_docs)."""
+        buf, offsets = _docs_buffer(docs)
         n = int(buf.size)
-        n_docs = int(offsets.size) - 1
         self._ensure_final_lengths()
         self.reserve(slot, max(n, 1), max(n // 8, 4096))
         if n:
             self.h2d(buf, slot)
         self.scan_resident(n, n, slot=slot)
         self.set_doc_offsets(offsets, slot)
+        return offsets, int(offsets.size) - 1
+
+    def scan_documents(self, docs, slot: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+        """Match a batch of independent documents in one scan.  ``docs`` is a sequence of bytes-like objects, or a
+        ``(buffer, offsets)`` pair whose offsets (an integer array or list, n_docs + 1 of them, from 0 to len(buffer))
+        cut ``buffer`` into documents.  Returns (doc_first uint64[n_docs + 1], records): the records of document d are
+        ``records[doc_first[d]:doc_first[d + 1]]``, positions relative to the document, in (offset, pattern length)
+        order -- what scanning each document on its own yields."""
+        _, n_docs = self._scan_docs(docs, slot)
         kept = self.segment_records(n_docs, slot=slot)
         return self.segment_to_host(kept, n_docs, slot)
 
@@ -390,6 +384,47 @@ class GpuMatcher:
         self.scan_resident(n_owned, n_avail, slot=slot)
         n, ex = self.select_leftmost_longest(entry, slot=slot)
         return self.selection_to_host(n, slot), ex
+
+    def select_leftmost_longest_documents(self, n_docs: int, d_doc_offsets=None, d_out=None, out_cap: int = 0,
+                                          d_doc_first=None, slot: int = 0, d_records=None) -> int:
+        """Leftmost-longest selection of every document [off[d], off[d+1]) of the slot's last finished scan on its own,
+        on the GPU (one call for the batch).  ``d_doc_offsets`` None = the slot's (``set_doc_offsets``); ``d_out`` /
+        ``d_doc_first`` None = slot-owned buffers (``doc_selection_to_host``).  Positions stay relative to the scan.
+        The call is the slot's last selection (entry 0, exit 0): ``replace_selection`` and
+        ``replace_selection_documents`` consume it.  Returns the number of picks.  A too small ``out_cap`` raises
+        PfacError(PFAC_E_OVERFLOW) whose ``n_selected`` attribute holds the exact count."""
+        n = C.c_uint64(0)
+        rc = self._L.pfac_records_leftmost_longest_documents(self._ctx, slot, _ptr(d_records), _ptr(d_doc_offsets),
+                                                             int(n_docs), _ptr(d_out), int(out_cap), _ptr(d_doc_first),
+                                                             C.byref(n))
+        if rc:
+            e = PfacError(rc, (self._L.pfac_last_error(self._ctx) or b"").decode())
+            e.n_selected = n.value
+            raise e
+        return n.value
+
+    def doc_selection_to_host(self, n_selected: int, n_docs: int, slot: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+        """(doc_first uint64[n_docs + 1], records) of the slot's last ``select_leftmost_longest_documents`` into
+        slot-owned buffers; positions relative to the scan."""
+        rec = np.empty(int(n_selected), dtype=RECORD_DTYPE)
+        first = np.empty(int(n_docs) + 1, dtype=np.uint64)
+        self._check(self._L.pfac_leftmost_longest_documents_d2h(self._ctx, slot, rec.ctypes.data if n_selected else None,
+                                                                first.ctypes.data))
+        self.sync(slot)
+        return first, rec
+
+    def select_documents(self, docs, slot: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+        """Leftmost-longest selection of a batch of independent documents (``docs`` as ``scan_documents`` takes it) in
+        one scan.  Returns (doc_first uint64[n_docs + 1], records): the picks of document d are
+        ``records[doc_first[d]:doc_first[d + 1]]``, positions relative to the document -- what
+        ``scan_leftmost_longest`` of each document on its own returns."""
+        offsets, n_docs = self._scan_docs(docs, slot)
+        n = self.select_leftmost_longest_documents(n_docs, slot=slot)
+        first, rec = self.doc_selection_to_host(n, n_docs, slot)
+        if n:
+            doc = np.repeat(np.arange(n_docs, dtype=np.int64), np.diff(first.astype(np.int64)))
+            rec["pos"] -= offsets[doc].astype(np.uint32)
+        return first, rec
 
     # -- find-and-replace over the leftmost-longest selection ---------------
     def _set_replacement_table(self, offsets, data: bytes) -> None:
@@ -448,6 +483,39 @@ class GpuMatcher:
         n = self.replace_selection(slot=slot)
         return self.replacement_to_host(n, slot), ex
 
+    def replace_selection_documents(self, d_input=None, d_out=None, out_cap: int = 0, d_out_offsets=None, slot: int = 0,
+                                    d_sel=None, d_doc_offsets=None, d_doc_first=None) -> int:
+        """``replace_selection`` over the slot's last ``select_leftmost_longest_documents``: every document's output,
+        concatenated, and the output offsets of the documents (``d_out_offsets`` None = a slot-owned buffer,
+        ``replacement_doc_offsets_to_host``).  ``d_doc_offsets`` / ``d_doc_first``: the buffers the selection was
+        given (None = the slot's).  Returns the output's length; a too small ``out_cap`` raises
+        PfacError(PFAC_E_OVERFLOW) whose ``out_bytes`` attribute holds the exact length."""
+        n = C.c_uint64(0)
+        rc = self._L.pfac_replace_documents(self._ctx, slot, _ptr(d_input), _ptr(d_sel), _ptr(d_doc_offsets),
+                                            _ptr(d_doc_first), _ptr(d_out), int(out_cap), _ptr(d_out_offsets), C.byref(n))
+        if rc:
+            e = PfacError(rc, (self._L.pfac_last_error(self._ctx) or b"").decode())
+            e.out_bytes = n.value
+            raise e
+        return n.value
+
+    def replacement_doc_offsets_to_host(self, n_docs: int, slot: int = 0) -> np.ndarray:
+        """The output offsets (uint64[n_docs + 1]) of the slot's last ``replace_selection_documents``."""
+        out = np.empty(int(n_docs) + 1, dtype=np.uint64)
+        self._check(self._L.pfac_replace_documents_d2h(self._ctx, slot, out.ctypes.data))
+        self.sync(slot)
+        return out
+
+    def replace_documents(self, docs, slot: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+        """Find-and-replace in a batch of independent documents (``docs`` as ``scan_documents`` takes it) in one scan,
+        every document on its own.  Returns (out_offsets uint64[n_docs + 1], out uint8[out_bytes]): document d's
+        output is ``out[out_offsets[d]:out_offsets[d + 1]]`` -- what ``replace`` of each document alone returns."""
+        _, n_docs = self._scan_docs(docs, slot)
+        self.select_leftmost_longest_documents(n_docs, slot=slot)
+        n = self.replace_selection_documents(slot=slot)
+        out_off = self.replacement_doc_offsets_to_host(n_docs, slot)
+        return out_off, self.replacement_to_host(n, slot)
+
     # -- synthetic inputs (device resident) --------------------------------
     def fill_tiled(self, d_dst, n: int, pattern: bytes, phase: int = 0, slot: int = 0) -> None:
         pat = np.frombuffer(pattern, dtype=np.uint8)
@@ -455,6 +523,25 @@ class GpuMatcher:
 
     def fill_random(self, d_dst, n: int, seed: int, slot: int = 0) -> None:
         self._check(self._L.pfac_fill_random(self._ctx, slot, _ptr(d_dst), int(n), int(seed) & (2**64 - 1)))
+
+
+def _docs_buffer(docs) -> Tuple[np.ndarray, np.ndarray]:
+    """A batch of documents -> (buffer uint8, offsets uint64[n_docs + 1]).  ``docs`` is a sequence of bytes-like
+    objects, or a ``(buffer, offsets)`` pair whose offsets (an integer array or list, n_docs + 1 of them, from 0 to
+    len(buffer)) cut ``buffer`` into documents."""
+    if (isinstance(docs, tuple) and len(docs) == 2 and isinstance(docs[1], (np.ndarray, list, range))
+            and np.asarray(docs[1]).dtype != np.uint8):
+        buf, offsets = docs
+        buf = np.frombuffer(buf, dtype=np.uint8) if not isinstance(buf, np.ndarray) else buf.view(np.uint8).ravel()
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    else:
+        parts = [np.frombuffer(d, dtype=np.uint8) if not isinstance(d, np.ndarray) else d.view(np.uint8).ravel()
+                 for d in docs]
+        offsets = np.zeros(len(parts) + 1, dtype=np.uint64)
+        if parts:
+            np.cumsum([p.size for p in parts], out=offsets[1:])
+        buf = np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint8)
+    return buf, offsets
 
 
 def trace_table_compat(input_bytes: np.ndarray, table: PfacTable, device: int = 0) -> np.ndarray:
