@@ -206,6 +206,12 @@ const char *pfac_last_error(const pfac_ctx *ctx);                    /* ctx may 
  * host memory; the _device variant takes an image already in this GPU's
  * memory (e.g. the receive buffer of an RCCL broadcast) and uses `stream_handle`
  * (a hipStream_t, may be NULL) for ordering. */
+/* An upload waits for the scans still pending on the context's slots (they read the old tables); such a scan is
+ * finished with pfac_scan_finish as usual.  The records of a scan made with an EARLIER table stay valid as records:
+ * pfac_records_d2h, pfac_records_expand and the packed fetches deliver them, their `state` indexing the idmap of the
+ * table they were scanned with.  Everything that needs that table on the device is gone with it: the text emitter and
+ * the checksum (idmap), the segment pass, both selections and both replaces (final lengths, replacements) return
+ * PFAC_E_STATE for such a scan. */
 int pfac_table_upload(pfac_ctx *ctx, const int32_t *blob, size_t n_words);
 int pfac_table_upload_device(pfac_ctx *ctx, const void *d_blob, size_t n_words, void *stream_handle);
 
@@ -220,12 +226,21 @@ int pfac_host_unregister(void *p);
 
 /* Per-slot device buffers owned by the context.  Input capacity is rounded up
  * so the kernel's tile loads stay in bounds (master_kernel.cu:217 pads by
- * one tile + 512 B for the same reason). */
+ * one tile + 512 B for the same reason), by less than two tiles.  Buffers only grow.  A request no larger than an
+ * earlier one changes nothing.  A request that outgrows a buffer the slot already has REPLACES it, and the contents are
+ * not kept: the call first waits for everything the slot still does with the old buffer (a pending scan, H2D copies),
+ * and the slot then has NO FINISHED SCAN -- pfac_scan_finish, the record fetches, the text emitter, the checksum and
+ * every pass return PFAC_E_STATE until the next pfac_scan_async, whichever buffers the lost scan used.  (Copying a
+ * heap of up to gigabytes that its only callers -- the overflow retry, the next chunk -- are about to overwrite would
+ * be wasted work; a caller that wants the old records fetches them first.)  Results of earlier passes in their own
+ * slot-owned buffers (selection, segment, replace output, text) stay fetchable. */
 int pfac_slot_reserve(pfac_ctx *ctx, int slot, uint64_t input_bytes, uint64_t record_capacity);
 void *pfac_slot_input(pfac_ctx *ctx, int slot);          /* device pointer, 256-B aligned */
 void *pfac_slot_records(pfac_ctx *ctx, int slot);        /* device pointer (record_capacity x 8 bytes, either record form) */
 void *pfac_slot_stream(pfac_ctx *ctx, int slot);         /* the slot's hipStream_t */
-/* Use an EXTERNAL stream (e.g. torch's current stream) for a slot; NULL restores the slot's own. */
+/* Use an EXTERNAL stream (e.g. torch's current stream) for a slot; NULL restores the slot's own.  A change of stream
+ * waits for everything the slot has queued on the old one (a scan, the asynchronous writes of a pass): what follows on
+ * the new stream may read it. */
 int pfac_slot_set_stream(pfac_ctx *ctx, int slot, void *stream_handle);
 
 /* Async H2D of input bytes into the slot's input buffer at dst_offset
@@ -263,7 +278,9 @@ int pfac_scan_capacity_hint(pfac_ctx *ctx, int slot, uint64_t *capacity);
  * analogue of "2. MASTER: The elapsed time is %f ms", master_kernel.cu:400-421). */
 int pfac_scan_elapsed_ms(pfac_ctx *ctx, int slot, float *ms);
 /* D2H of records [first, first+n) of the sorted sequence as pfac_record (the compact replacement of the dense
- * cudaMemcpy D2H, master_kernel.cu:428).  Asynchronous; pfac_slot_sync() completes it. */
+ * cudaMemcpy D2H, master_kernel.cu:428).  Asynchronous; pfac_slot_sync() completes it.  n == 0 does nothing.
+ * PFAC_E_STATE without a scan or before its pfac_scan_finish, PFAC_E_OVERFLOW if the scan overflowed its heap,
+ * PFAC_E_ARG when first + n exceeds the match count (same for pfac_records_expand). */
 int pfac_records_d2h(pfac_ctx *ctx, int slot, const void *d_records, pfac_record *host, uint64_t first, uint64_t n);
 int pfac_slot_sync(pfac_ctx *ctx, int slot);
 /* Record form of the slot's last finished scan: *record_bytes = 2 or 4 (compact words) or 8 (pfac_record in the
@@ -285,7 +302,9 @@ int pfac_records_d2h_packed(pfac_ctx *ctx, int slot, const void *d_records, void
  * depends on the digit counts: one kernel sizes the lines per 64 tiles, a prefix sum places them, a third formats -- the
  * host only copies finished text (pfac_text_d2h, asynchronous on the slot's stream; pfac_slot_sync completes it) and
  * write()s it.  base + 2^32 must stay below 10^18.  Byte-identical to pfac_emit_records / pfac_emit_packed.
- * (Character-class tables, whose final states may stand for several patterns, print on the host: pfac_emit_records_multi.) */
+ * (Character-class tables, whose final states may stand for several patterns, print on the host: pfac_emit_records_multi;
+ * the device prints idmap[state], the first id, once.)  PFAC_E_STATE without a finished scan or for a scan made with an
+ * earlier table, PFAC_E_OVERFLOW if the scan overflowed its heap. */
 int pfac_emit_text_device(pfac_ctx *ctx, int slot, const void *d_records, uint64_t base, uint64_t *n_bytes);
 int pfac_text_d2h(pfac_ctx *ctx, int slot, void *host, uint64_t first, uint64_t n_bytes);
 void *pfac_slot_text(pfac_ctx *ctx, int slot);            /* device pointer of that text (valid until the slot's next pfac_emit_text_device) */
@@ -299,7 +318,8 @@ int pfac_records_packed_device(pfac_ctx *ctx, int slot, const void *d_records, v
 
 /* Order-independent 64-bit checksum of ALL records of the slot's last scan (sum over records of
  * mix(base+pos, idmap[state])), computed on the GPU; used for full-size parity checks where materialising
- * the text is not practical.  n = the scan's match count (0: checksum of nothing). */
+ * the text is not practical.  n = the scan's match count (0: checksum of nothing).  For n > 0: PFAC_E_STATE without a
+ * finished scan or for a scan made with an earlier table, PFAC_E_OVERFLOW if the scan overflowed its heap. */
 int pfac_records_checksum(pfac_ctx *ctx, int slot, const void *d_records, uint64_t n, uint64_t base,
                           uint64_t *checksum);
 
@@ -338,7 +358,13 @@ int pfac_records_segment(pfac_ctx *ctx, int slot, const void *d_records, const u
                          pfac_record *d_out, uint64_t out_cap, uint64_t *d_doc_first, uint64_t *n_kept);
 /* D2H of the slot-owned result of the last pfac_records_segment (host_records: *n_kept records, may be NULL when
  * d_out was the caller's; host_doc_first: n_docs + 1 entries, may be NULL when d_doc_first was the caller's).
- * Asynchronous on the slot's stream; pfac_slot_sync completes it. */
+ * Asynchronous on the slot's stream; pfac_slot_sync completes it.
+ * Lifetime of a pass's slot-owned result (the same for the selections, the replaces and their fetches below): it stays
+ * fetchable, unchanged, until the slot's next call of the SAME pass -- through later scans, table uploads, other passes,
+ * pfac_slot_reserve, pfac_slot_doc_offsets and pfac_table_set_replacements (a replace output holds the bytes of the
+ * replacements set when it ran).  The next call of the same pass discards it even when that call fails; the fetch then
+ * returns PFAC_E_STATE, as it does when the pass wrote into the caller's buffers.  The two selections share one
+ * slot-owned buffer and count as one pass here; so do the two replaces. */
 int pfac_segment_d2h(pfac_ctx *ctx, int slot, pfac_record *host_records, uint64_t *host_doc_first);
 
 /* Leftmost-longest, non-overlapping selection over the slot's last finished scan.  From a cursor c = entry
@@ -417,7 +443,8 @@ int pfac_table_set_replacements(pfac_ctx *ctx, const uint32_t *offsets, uint64_t
  * Returns once *out_bytes is known; the writes are asynchronous on the slot's stream.  PFAC_E_OVERFLOW (with *out_bytes
  * exact, nothing written) when out_cap is too small for a caller's d_out.  PFAC_E_STATE without a selection since the
  * slot's last scan, for a selection made with an earlier table, or without replacements or final lengths for the current
- * table.  PFAC_E_ARG for misaligned buffers or a d_sel that is not the selection of this scan.
+ * table, or after a pfac_slot_reserve that replaced a buffer of the slot (no scan to rewrite).  PFAC_E_ARG for misaligned
+ * buffers or a d_sel that is not the selection of this scan.
  * Kernels: a count pass sums R_k - L_k per 1024 picks (and per block of 64), the group prefix, then an output-driven
  * write: each wave finds the block of its first output byte by a 64-ary search over the block offsets, rebuilds the
  * block's segment offsets with a wave prefix and assembles 16 output bytes per lane in registers (one dwordx4 store;

@@ -3676,6 +3676,8 @@ int install_table(pfac_ctx *ctx, const int *d_blob, const int32_t *hdr, size_t n
     const size_t off_T = align_up(off_r + (size_t)max_row * 4, 16);
     const size_t off_id = off_T + (size_t)ht_size * 8;
     const size_t total = align_up(off_id + (size_t)num_final * 4, 16) + 16;
+    for (auto &sl : ctx->slots)                             // a scan still in flight reads the tables freed below
+        if (sl.pending) HIP_TRY(ctx, hipEventSynchronize(sl.ev1));
     if (ctx->d_tab) { HIP_TRY(ctx, hipFree(ctx->d_tab)); ctx->d_tab = nullptr; }
     if (ctx->d_flen) { HIP_TRY(ctx, hipFree(ctx->d_flen)); ctx->d_flen = nullptr; }   // the lengths belong to the old table
     if (ctx->d_rep_off) { HIP_TRY(ctx, hipFree(ctx->d_rep_off)); ctx->d_rep_off = nullptr; }   // ... and so do the replacements
@@ -3845,6 +3847,15 @@ int pfac_slot_reserve(pfac_ctx *ctx, int slot, uint64_t input_bytes, uint64_t re
     if (rc) return rc;
     USE_DEVICE(ctx);
     Slot &s = ctx->slots[slot];
+    // Replacing a buffer the slot already has: whatever the slot's stream and the copy stream still do with the old one
+    // finishes first (a pending scan writes the heap and reads the input), and the new, uninitialised buffer holds no
+    // scan -- the slot is back to "no finished scan", so nothing reads it as if it held the last one.
+    if ((input_bytes > s.input_cap && s.d_input) || (record_capacity > s.record_cap && s.d_records)) {
+        HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+        if (s.pending) HIP_TRY(ctx, hipEventSynchronize(s.ev1));       // (the stream may have been swapped under the scan)
+        if (s.h2d_issued) HIP_TRY(ctx, hipEventSynchronize(s.ev_h2d));
+        s.scanned = s.pending = false;
+    }
     if (input_bytes > s.input_cap) {
         if (s.d_input) { HIP_TRY(ctx, hipFree(s.d_input)); s.d_input = nullptr; s.input_cap = 0; }
         const uint64_t cap = align_up(input_bytes, WTILE) + HALO_MAX + 256;
@@ -3868,7 +3879,9 @@ int pfac_slot_set_stream(pfac_ctx *ctx, int slot, void *stream_handle) {
     if (rc) return rc;
     Slot &s = ctx->slots[slot];
     hipStream_t ns = stream_handle ? reinterpret_cast<hipStream_t>(stream_handle) : s.own_stream;
-    if (ns != s.stream && s.pending) HIP_TRY(ctx, hipStreamSynchronize(s.stream));   // a scan in flight zeroes the next scan's control words
+    // what the slot still has queued on the old stream finishes first: a scan in flight zeroes the next scan's control
+    // words, and the writes of a pass (a selection, say) are asynchronous -- the next pass, on the new stream, reads them
+    if (ns != s.stream) { USE_DEVICE(ctx); HIP_TRY(ctx, hipStreamSynchronize(s.stream)); }
     s.stream = ns;
     return PFAC_OK;
 }
@@ -4157,9 +4170,9 @@ int pfac_records_d2h(pfac_ctx *ctx, int slot, const void *d_records, pfac_record
     if (rc) return rc;
     Slot &s = ctx->slots[slot];
     const void *src = d_records ? d_records : s.d_records;
-    if (!src || (!host && n)) return fail(ctx, PFAC_E_ARG, "pfac_records_d2h: null buffer");
     if (n == 0) return PFAC_OK;
     if (!s.scanned) return fail(ctx, PFAC_E_STATE, "pfac_records_d2h without a scan");
+    if (!src || !host) return fail(ctx, PFAC_E_ARG, "pfac_records_d2h: null buffer");
     USE_DEVICE(ctx);
     if (n > s.wide_cap) {
         if (s.d_wide) { HIP_TRY(ctx, hipStreamSynchronize(s.stream)); HIP_TRY(ctx, hipFree(s.d_wide)); s.d_wide = nullptr; s.wide_cap = 0; }
@@ -4213,6 +4226,7 @@ int pfac_emit_text_device(pfac_ctx *ctx, int slot, const void *d_records, uint64
     Slot &s = ctx->slots[slot];
     const void *src = d_records ? d_records : s.d_records;
     if (!s.scanned || s.pending) return fail(ctx, PFAC_E_STATE, "pfac_emit_text_device needs a finished scan");
+    if (s.last_table != ctx->table_gen) return fail(ctx, PFAC_E_STATE, "pfac_emit_text_device: the slot's last scan ran with an earlier table (its states index that table's idmap)");
     if (s.last_used > s.last_cap) return fail(ctx, PFAC_E_OVERFLOW, "the slot's last scan overflowed its record heap: scan again with a larger one");
     if (base + (1ull << 32) >= 1000000000000000000ull) return fail(ctx, PFAC_E_ARG, "pfac_emit_text_device: positions must stay below 10^18");
     s.text_bytes = 0;
@@ -4276,8 +4290,10 @@ int pfac_records_checksum(pfac_ctx *ctx, int slot, const void *d_records, uint64
     if (!ctx->have_table) return fail(ctx, PFAC_E_STATE, "no table uploaded");
     Slot &s = ctx->slots[slot];
     const void *src = d_records ? d_records : s.d_records;
+    if (n && (!s.scanned || s.pending)) return fail(ctx, PFAC_E_STATE, "pfac_records_checksum needs a finished scan");
+    if (n && s.last_table != ctx->table_gen) return fail(ctx, PFAC_E_STATE, "pfac_records_checksum: the slot's last scan ran with an earlier table (its states index that table's idmap)");
+    if (n && s.last_used > s.last_cap) return fail(ctx, PFAC_E_OVERFLOW, "the slot's last scan overflowed its record heap: scan again with a larger one");
     if (!src && n) return fail(ctx, PFAC_E_ARG, "null record buffer");
-    if (n && !s.scanned) return fail(ctx, PFAC_E_STATE, "pfac_records_checksum without a scan");
     USE_DEVICE(ctx);
     HIP_TRY(ctx, hipMemsetAsync(s.d_sum, 0, 16, s.stream));
     if (n && s.last_tiles) {
@@ -4696,7 +4712,7 @@ static int rp_run(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *d_i
                   uint64_t out_cap, uint64_t *out_bytes, const RpDocs *docs) {
     s.rp_done = false;
     s.rpd_done = false;
-    if (!s.ll_done || s.ll_seq != s.scan_seq || (docs && !s.ll_docs))
+    if (!s.scanned || !s.ll_done || s.ll_seq != s.scan_seq || (docs && !s.ll_docs))
         return fail(ctx, PFAC_E_STATE, fn + (docs ? " needs a pfac_records_leftmost_longest_documents since the slot's last scan"
                                                   : " needs a pfac_records_leftmost_longest since the slot's last scan"));
     if (!ctx->have_table || s.last_table != ctx->table_gen)

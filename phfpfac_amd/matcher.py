@@ -46,6 +46,7 @@ class GpuMatcher:
         self.n_streams = n_streams
         self.table: Optional[PfacTable] = None
         self._keep = {}
+        self._keep_mark = {}            # per slot: how many of its kept h2d sources were queued before its last scan_async
         self._last_n = {}
         self._flen_set = False          # final-state lengths on the device for the uploaded table (scan_documents)
         rc = self._L.pfac_ctx_create(int(device), int(n_streams), C.byref(self._ctx))
@@ -124,9 +125,17 @@ class GpuMatcher:
         self._keep.setdefault(slot, []).append(host)   # the copy is asynchronous: released by sync()/scan_finish()
         self._check(self._L.pfac_slot_h2d(self._ctx, slot, host.ctypes.data, host.size, int(dst_offset)))
 
+    def h2d_done(self, slot: int = 0) -> bool:
+        """Whether the slot's last ``h2d`` has left its host array (``pfac_slot_h2d_done``; never blocks)."""
+        rc = self._L.pfac_slot_h2d_done(self._ctx, slot)
+        if rc < 0:
+            self._check(rc)
+        return rc == 1
+
     def sync(self, slot: int = 0) -> None:
         self._check(self._L.pfac_slot_sync(self._ctx, slot))
         self._keep.pop(slot, None)
+        self._keep_mark.pop(slot, None)
 
     # -- the scan ---------------------------------------------------------
     def scan_async(self, n_owned: int, n_avail: Optional[int] = None, d_input=None, d_records=None,
@@ -135,13 +144,19 @@ class GpuMatcher:
         n_avail = n_owned if n_avail is None else n_avail
         self._check(self._L.pfac_scan_async(self._ctx, slot, _ptr(d_input), int(n_owned), int(n_avail),
                                             _ptr(d_records), int(capacity)))
+        self._keep_mark[slot] = len(self._keep.get(slot, ()))
 
     def scan_finish(self, slot: int = 0, allow_overflow: bool = False) -> Tuple[int, bool]:
         n = C.c_uint64(0)
         rc = self._check(self._L.pfac_scan_finish(self._ctx, slot, C.byref(n)), allow_overflow=allow_overflow)
-        # the scan's end event is ordered after the slot's H2D copies on its stream: their host arrays can go
-        # (a streaming caller that never calls sync() would otherwise keep every chunk it ever uploaded alive)
-        self._keep.pop(slot, None)
+        # the scan's end event is ordered after the H2D copies queued BEFORE its scan_async: their host arrays can go
+        # (a streaming caller that never calls sync() would otherwise keep every chunk it ever uploaded alive).  A copy
+        # queued after scan_async -- the next chunk -- may not have started: its array stays until a later
+        # scan_finish / sync.
+        kept = self._keep.get(slot)
+        if kept:
+            del kept[:self._keep_mark.get(slot, 0)]
+        self._keep_mark[slot] = 0
         self._last_n[slot] = n.value
         return n.value, rc == PFAC_E_OVERFLOW
 

@@ -1,0 +1,1128 @@
+"""Model-based session tests: ONE context driven through a random sequence of calls, the way a long-running service
+drives it -- many tables, many sizes, two slots, passes in any order, results fetched late.
+
+Three parts, none of which needs a GPU to import:
+
+  Pool / Expectations  a small pool of tables and inputs, and what the CPU says about them (the CPU oracle, llref, replref,
+                       docref, docreplref, orc.match_checksum -- as passfuzz.Expect, never the device, never
+                       PfacTable.final_lengths), cached by (table, input, n_owned, ...).
+  Model                what include/pfac.h PROMISES for every call given the calls before it: a value or a
+                       PfacError.status.  It mirrors the header, not pfac_hip.hip; its state holds only keys into the cache.
+  plan / run / shrink  plan(seed) draws about 60 operations, asking the model which are legal and picking an illegal one
+                       about one time in eight; run(g, plan, model) performs them on a GpuMatcher (or anything shaped like
+                       one) and compares bit for bit; shrink(seed, k) is the plan cut before operation k.
+
+The device under test hands out final STATES; they are mapped to pattern ids with the idmap of the table the scan ran
+with (a stand-in that already works in ids says so with ``states_are_ids``)."""
+import copy
+import importlib.util
+import os
+import tempfile
+
+import numpy as np
+
+from docref import oracle_per_doc, random_offsets
+from docreplref import per_doc
+from llref import greedy
+from orc import Oracle, match_checksum
+from passfuzz import GROUP, KNOB_NAMES, KNOBS, record_width
+from phfpfac_amd import PfacError, PfacTable
+from replref import rep_table, splice
+
+OK, E_ARG, E_STATE, E_OVERFLOW = 0, -1, -7, -8
+STATUS_NAMES = {OK: "OK", E_ARG: "PFAC_E_ARG", E_STATE: "PFAC_E_STATE", E_OVERFLOW: "PFAC_E_OVERFLOW", None: "UNDEFINED"}
+TILE = 4096
+N_SLOTS = 2
+SEEDS = list(range(24))                 # the suite's plans
+PLAN_OPS = 60
+IN_STEP, REC_STEP = 8 << 20, 4 << 20    # reserve_grow number k asks for k * IN_STEP bytes / k * REC_STEP records: above
+                                        # anything a plan's scans reserve (inputs <= 2 000 003 bytes, heaps below 4 Mi records)
+REC = np.dtype([("pos", np.uint32), ("state", np.uint32)])
+
+_REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_spec = importlib.util.spec_from_file_location("charclass_oracle", os.path.join(_REPO, "oracle", "charclass_oracle.py"))
+cco = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(cco)
+
+CCLASS = (b"[a-c]x\n" b"ax\n" b"[^a-z0-9 ]\n" b"q[0-9][0-9]\n" b"[a-c]\n" b"\\x41[\\x42-\\x44]\\n\n" b"[-a]z\n" b"ax[xy]\n"
+          b"[a-c]x\n")
+CCLASS_ALPHABET = b"abcxyzq0123456789 AB\nCD-Z!"
+
+
+def _k(**knobs):
+    return KNOBS.index(knobs)
+
+
+# name -> how the table is made, which entries of passfuzz.KNOBS it may be installed under, and its inputs (name, bytes,
+# style).  Together: 2-, 4- and 8-byte records, tables in LDS and through L2, dense mode's second form, a character-class
+# table, duplicate lines; every size of passfuzz.Case; one dense and one matchless input of >= 64 tiles for a table with
+# no knob pinned, so the staging mode can flip.
+TABLES = {
+    "abc2": dict(lines=[b"a", b"ab", b"abc"], knobs=[_k()],
+                 inputs=[("dense", 300_007, "abc:0.3"), ("none", 300_007, "abc:0"), ("thin", GROUP + 1, "abc:0.02"), ("s17", 17, "abc:0.3")]),
+    "mid4": dict(gen=(101, 26, 150, 8, 0), knobs=[_k(), _k(PFAC_LAG="1"), _k(PFAC_LAG="2"), _k(PFAC_L2F="0"), _k(PFAC_L2F="2"),
+                                                   _k(PFAC_L2F="3"), _k(PFAC_NWB="4"), _k(PFAC_TICKET_WAYS="1"), _k(PFAC_TICKET_WAYS="2")],
+                 inputs=[("big", 2_000_003, "plant"), ("t4097", 4097, "plant"), ("g1", GROUP + 1, "plant")]),
+    "wide8": dict(gen=(102, 8, 40, 6, 0), knobs=[_k(PFAC_WIDE="1")],
+                  inputs=[("t4095", 4095, "plant"), ("gm1", GROUP - 1, "plant"), ("one", 1, "plant")]),
+    "l2": dict(gen=(103, 4, 40, 14, 0), knobs=[_k(PFAC_FORCE_L2="1"), _k(PFAC_FORCE_L2="1", PFAC_NO_FUSE="1"),
+                                                _k(PFAC_FORCE_L2="1", PFAC_NO_D1="1"), _k(PFAC_L2F="3", PFAC_FORCE_L2="1"),
+                                                _k(PFAC_NO_SECF="1", PFAC_FORCE_L2="1")],
+               inputs=[("m300", 300_007, "plant"), ("t4097", 4097, "plant"), ("s17", 17, "plant")]),
+    "dense2": dict(gen=(104, 3, 20, 3, 0), knobs=[_k(PFAC_FORCE_L2="1", PFAC_DENSE="1"), _k(PFAC_FORCE_L2="1", PFAC_DENSE="1", PFAC_D2_LOGCAP="64"),
+                                                   _k(PFAC_FORCE_L2="1", PFAC_DENSE="1", PFAC_NWB="5"),
+                                                   _k(PFAC_FORCE_L2="1", PFAC_NO_NW4="1", PFAC_DENSE="1"),
+                                                   _k(PFAC_FORCE_L2="1", PFAC_DENSE="1", PFAC_NO_DENSE2="1")],
+                   inputs=[("g1", GROUP + 1, "plant"), ("t4095", 4095, "plant"), ("empty", 0, "plant")]),
+    "cclass": dict(cclass=CCLASS, knobs=[_k(), _k(PFAC_REC_BYTES="4")],
+                   inputs=[("gm1", GROUP - 1, "cc"), ("t4097", 4097, "cc"), ("one", 1, "cc")]),
+    "dups": dict(gen=(105, 3, 9, 4, 3), knobs=[_k(), _k(PFAC_DENSE="1")],
+                 inputs=[("m300", 300_007, "plant"), ("t4095", 4095, "plant"), ("empty", 0, "plant")]),
+}
+REP_KEYS = ("r0", "r1", "redact")
+DOC_KEYS = ("d0", "d1", "bad_end", "bad_order")
+TEXT_BASES = (0, 999_999_990)
+
+
+def _gen_lines(seed, alpha, npat, maxlen, dups):
+    rng = np.random.default_rng([seed, 0x53455353])
+    symbols = rng.permutation(np.array([b for b in range(256) if b != 10], dtype=np.uint8))[:alpha]
+    pats = set()
+    for _ in range(npat * 4):
+        if len(pats) >= npat:
+            break
+        pats.add(bytes(symbols[rng.integers(0, alpha, int(rng.integers(1, maxlen + 1)))]))
+    lines = sorted(pats, key=lambda x: rng.random())
+    for _ in range(dups):                                      # duplicate lines: unreachable final states
+        lines.insert(int(rng.integers(0, len(lines) + 1)), lines[int(rng.integers(0, len(lines)))])
+    return lines, symbols
+
+
+class _ClassMatcher:
+    """Oracle.scan_spec's interface over the brute-force character-class matcher: one record per (position, length),
+    carrying the lowest pattern id that ends there -- idmap[state] of the one DFA state reached."""
+
+    def __init__(self, image):
+        self.image = image
+        self.lens = np.array([0] + [len(p) for p in cco.parse(image)], dtype=np.int64)
+
+    def scan_spec(self, data, n=None):
+        pos, ids = cco.match(self.image, np.asarray(data, dtype=np.uint8))
+        if pos.size == 0:
+            return pos, ids
+        ln = self.lens[ids]
+        first = np.append(True, (pos[1:] != pos[:-1]) | (ln[1:] != ln[:-1]))     # (sorted by position, length, id)
+        return pos[first], ids[first]
+
+
+class Expectations:
+    """What the CPU says, computed once per key."""
+
+    def __init__(self):
+        self.dir = tempfile.mkdtemp(prefix="pfac_session_")
+        self._c = {}
+
+    def _memo(self, key, fn):
+        if key not in self._c:
+            self._c[key] = fn()
+        return self._c[key]
+
+    # -- tables -------------------------------------------------------------
+    def _table(self, t):
+        d = TABLES[t]
+        if "cclass" in d:
+            m = _ClassMatcher(d["cclass"])
+            return dict(table=PfacTable.from_charclass(d["cclass"], 256), matcher=m, ll=m.lens, symbols=None, lines=None)
+        lines, symbols = (d["lines"], np.frombuffer(b"abc", dtype=np.uint8)) if "lines" in d else _gen_lines(*d["gen"])
+        path = os.path.join(self.dir, t + ".pat")
+        with open(path, "wb") as f:
+            f.write(b"".join(p + b"\n" for p in lines))
+        ll = np.array([0] + [len(p) for p in lines], dtype=np.int64)      # the file's own lines
+        return dict(table=PfacTable.from_file(path, 256), matcher=Oracle(path, 1, 1), ll=ll, symbols=symbols, lines=lines)
+
+    def tinfo(self, t):
+        return self._memo(("table", t), lambda: self._table(t))
+
+    def table(self, t):
+        return self.tinfo(t)["table"]
+
+    def M(self, t):
+        return int(self.table(t).max_pat_len)
+
+    def width(self, t, knob):
+        return record_width(int(self.table(t).num_final), KNOBS[knob])
+
+    # -- inputs -------------------------------------------------------------
+    def _input(self, t, i):
+        name, n, style = TABLES[t]["inputs"][i]
+        rng = np.random.default_rng([sorted(TABLES).index(t), i, 0x494E])
+        if style.startswith("abc:"):
+            d = float(style[4:])
+            u = rng.random(n)
+            return np.where(u < d, ord("a"), np.where(u < d + 0.3, ord("b"), ord("c"))).astype(np.uint8)
+        if style == "cc":
+            alphabet = np.frombuffer(CCLASS_ALPHABET, dtype=np.uint8)
+            return alphabet[rng.integers(0, alphabet.size, n)]
+        info = self.tinfo(t)
+        sym = info["symbols"]
+        data = sym[rng.integers(0, sym.size, n)]
+        plist = sorted(set(info["lines"]))
+        for at in rng.integers(0, max(n - 1, 1), n // 50):
+            pt = np.frombuffer(plist[int(rng.integers(0, len(plist)))], dtype=np.uint8)
+            m = min(len(pt), n - int(at))
+            data[int(at):int(at) + m] = pt[:m]
+        return data
+
+    def input(self, t, i):
+        return self._memo(("input", t, i), lambda: self._input(t, i))
+
+    def input_size(self, t, i):
+        return TABLES[t]["inputs"][i][1]
+
+    # -- the scan -----------------------------------------------------------
+    def scan(self, t, i, no):
+        """(pos, ids, lens) of the records that start in [0, no); walks may read the whole input (the halo)."""
+        def make():
+            info = self.tinfo(t)
+            pos, ids = self._memo(("whole", t, i), lambda: info["matcher"].scan_spec(self.input(t, i), None))
+            own = pos < no
+            pos, ids = pos[own].astype(np.int64), ids[own].astype(np.int64)
+            return pos, ids, info["ll"][ids]
+        return self._memo(("scan", t, i, no), make)
+
+    def count(self, t, i, no):
+        return int(self.scan(t, i, no)[0].size)
+
+    def text(self, t, i, no, base):
+        def make():
+            pos, ids, _ = self.scan(t, i, no)
+            return "".join("At position %4d, match pattern %d\n" % (p + base, k) for p, k in zip(pos.tolist(), ids.tolist())).encode()
+        return self._memo(("text", t, i, no, base), make)
+
+    def checksum(self, t, i, no, base):
+        pos, ids, _ = self.scan(t, i, no)
+        return match_checksum(pos + base, ids)
+
+    # -- selection and replace ------------------------------------------------
+    def sel(self, t, i, no, entry):
+        """(pos, ids, exit) of the leftmost-longest selection from `entry`."""
+        def make():
+            pos, ids, lens = self.scan(t, i, no)
+            idx, ex = greedy(pos, lens, entry, no)
+            return pos[idx], ids[idx], int(ex)
+        return self._memo(("sel", t, i, no, entry), make)
+
+    def reps(self, t, rkey):
+        def make():
+            ll = self.tinfo(t)["ll"]
+            if rkey == "redact":
+                return {k: b"#" * int(ll[k]) for k in range(1, ll.size)}
+            rng = np.random.default_rng([sorted(TABLES).index(t), REP_KEYS.index(rkey), 0x5245])
+            return {k: rng.integers(0, 256, int(rng.integers(1000, 3000)) if rng.random() < 0.02 else int(rng.integers(0, 33))).astype(np.uint8).tobytes()
+                    for k in range(1, ll.size)}
+        return self._memo(("reps", t, rkey), make)
+
+    def replace(self, t, i, no, entry, rkey):
+        def make():
+            spos, sids, _ = self.sel(t, i, no, entry)
+            return splice(self.input(t, i), entry, no, spos, self.tinfo(t)["ll"][sids], sids, rep_table(self.reps(t, rkey)))
+        return self._memo(("replace", t, i, no, entry, rkey), make)
+
+    # -- documents ----------------------------------------------------------
+    def offsets(self, t, i, no, dkey):
+        def make():
+            rng = np.random.default_rng([sorted(TABLES).index(t), i, no, DOC_KEYS.index(dkey), 0x444F])
+            off = random_offsets(rng, no, int(rng.integers(1, 60)), empties=int(rng.integers(0, 4)))
+            cuts = [c for k in rng.integers(1, max(no // TILE, 1) + 1, 2) for c in (int(k) * TILE - 1, int(k) * TILE, int(k) * TILE + 1) if c <= no]
+            off = np.sort(np.concatenate([off, np.array(cuts, dtype=np.uint64)]))
+            if dkey == "d1":                                   # empty documents at the very end
+                off = np.concatenate([off, np.array([no, no], dtype=np.uint64)])
+            if dkey == "bad_end":
+                off = off.copy()
+                off[-1] = no + 1
+            if dkey == "bad_order":
+                tail = [no + 2, no] if no < 2 else [no - 1, no - 2, no]
+                off = np.concatenate([off[:1] if no < 2 else off[:-1], np.array(tail, dtype=np.uint64)])
+            return off.astype(np.uint64)
+        return self._memo(("off", t, i, no, dkey), make)
+
+    def seg(self, t, i, no, dkey):
+        """(doc_first, pos relative to the document, ids) of every document scanned on its own."""
+        def make():
+            first, pos, ids = oracle_per_doc(self.tinfo(t)["matcher"], self.input(t, i)[:no], self.offsets(t, i, no, dkey))
+            return first, pos.astype(np.int64), ids.astype(np.int64)
+        return self._memo(("seg", t, i, no, dkey), make)
+
+    def docsel(self, t, i, no, dkey, rkey=None):
+        """(doc_first, pos relative to the SCAN, ids, out_off, out) of every document's own selection (and output)."""
+        def make():
+            off = self.offsets(t, i, no, dkey)
+            tab = None if rkey is None else rep_table(self.reps(t, rkey))
+            first, pos, ids, out_off, out = per_doc(self.tinfo(t)["matcher"], self.input(t, i)[:no], off, self.tinfo(t)["ll"], tab)
+            doc = np.repeat(np.arange(off.size - 1, dtype=np.int64), np.diff(first.astype(np.int64)))
+            return first, pos.astype(np.int64) + off[doc].astype(np.int64), ids.astype(np.int64), out_off, out
+        return self._memo(("docsel", t, i, no, dkey, rkey), make)
+
+
+_EXP = None
+
+
+def expectations():
+    global _EXP
+    if _EXP is None:
+        _EXP = Expectations()
+    return _EXP
+
+
+def offsets_ok(off, n_owned):
+    off = off.astype(np.int64)
+    return bool(off[0] == 0 and off[-1] == n_owned and (np.diff(off) >= 0).all())
+
+
+# ---------------------------------------------------------------------------
+# the model
+
+class Exp:
+    """What the contract says about one operation: a status and, for OK, the value (computed on demand); `count` is the
+    exact figure an overflow error must carry; `tab` the table whose idmap the device's states belong to."""
+    __slots__ = ("status", "fn", "count", "tab")
+
+    def __init__(self, status=OK, fn=None, count=None, tab=None):
+        self.status, self.fn, self.count, self.tab = status, fn, count, tab
+
+    def value(self):
+        return self.fn() if self.fn else None
+
+
+class _Slot:
+    def __init__(self):
+        self.scan = None          # the slot's last scan: dict(tab, knob, gen, inp, no, over, pending, ext, seq)
+        self.seq = 0              # scans issued
+        self.has_in = self.has_rec = False      # the slot owns an input buffer / a record heap
+        self.grow = 0             # reserve_grow calls so far
+        self.doc = None           # (tab, inp, no, dkey) of the slot's document offsets, and how often they were set
+        self.doc_gen = 0
+        self.sel = self.seg = self.rp = self.rpd = None     # what each slot-owned output holds
+        self.text = None
+        self.shared = False
+
+
+PASSES = ("segment", "select", "select_docs", "replace", "replace_docs")
+FETCH_OF = {"segment": "seg_fetch", "select": "sel_fetch", "select_docs": "docsel_fetch", "replace": "rp_fetch", "replace_docs": "rpd_fetch"}
+
+
+class Model:
+    def __init__(self, exps=None):
+        self.x = exps or expectations()
+        self.tab = None
+        self.knob = 0
+        self.gen = 0
+        self.flen = False
+        self.reps = None
+        self.slots = [_Slot() for _ in range(N_SLOTS)]
+
+    def predict(self, op):
+        return copy.deepcopy(self).apply(op)
+
+    def apply(self, op):
+        return getattr(self, "_" + op["op"])(op, self.slots[op.get("slot", 0)])
+
+    def __deepcopy__(self, memo):
+        m = Model.__new__(Model)
+        m.__dict__.update(self.__dict__)                        # (the cache is shared, not copied)
+        m.slots = []
+        for s in self.slots:
+            c = _Slot()
+            c.__dict__.update(s.__dict__)
+            for name in ("scan", "sel", "seg", "rp", "rpd"):
+                v = getattr(s, name)
+                setattr(c, name, dict(v) if v is not None else None)
+            m.slots.append(c)
+        return m
+
+    # -- tables -------------------------------------------------------------
+    def _load_table(self, op, s):
+        self.tab, self.knob = op["tab"], op["knob"]
+        self.gen += 1
+        self.flen, self.reps = False, None                      # lengths and replacements go with the old table
+        return Exp()
+
+    def _set_flen(self, op, s):
+        if self.tab is None:
+            return Exp(E_STATE)
+        self.flen = True
+        return Exp()
+
+    def _set_reps(self, op, s):
+        if self.tab is None:
+            return Exp(E_STATE)
+        self.reps = op["rkey"]
+        return Exp()
+
+    # -- scans --------------------------------------------------------------
+    def _new_scan(self, s, op, pending, ext, over=False):
+        s.seq += 1
+        s.scan = dict(tab=self.tab, knob=self.knob, gen=self.gen, inp=op["inp"], no=op["no"], over=over, pending=pending, ext=ext, seq=s.seq)
+
+    def _rec_fn(self, sc, first=0, n=None):
+        def fn():
+            pos, ids, _ = self.x.scan(sc["tab"], sc["inp"], sc["no"])
+            return (pos[first:], ids[first:]) if n is None else (pos[first:first + n], ids[first:first + n])
+        return fn
+
+    def _scan_bytes(self, op, s):
+        s.has_in = s.has_rec = True                             # (scan_bytes reserves both before it scans)
+        if self.tab is None:
+            return Exp(E_STATE)
+        self._new_scan(s, op, False, False)
+        return Exp(OK, self._rec_fn(s.scan), tab=self.tab)
+
+    def _scan_start(self, op, s):
+        s.has_in = s.has_rec = True
+        if self.tab is None:
+            return Exp(E_STATE)
+        self._new_scan(s, op, True, False)
+        return Exp()
+
+    def _scan_finish(self, op, s):
+        if s.scan is None:
+            return Exp(E_STATE)
+        s.scan["pending"] = False
+        sc = s.scan
+        return Exp(OK, lambda: (self.x.count(sc["tab"], sc["inp"], sc["no"]), sc["over"]))
+
+    def _scan_ext(self, op, s):
+        if self.tab is None:
+            return Exp(E_STATE)
+        n = self.x.count(self.tab, op["inp"], op["no"])
+        fit = n + n // 4 + 65536                                # the slack the header asks for, and more
+        assert op["cap"] >= fit or op["cap"] < n, "a capacity the contract does not decide"
+        self._new_scan(s, op, False, True, over=op["cap"] < n)
+        sc = s.scan
+        return Exp(OK, lambda: (n, sc["over"]))
+
+    def _records(self, op, s):
+        if op["n"] == 0:
+            return Exp(OK, lambda: (np.empty(0, np.int64), np.empty(0, np.int64)), tab=self.tab)
+        if s.scan is None or s.scan["pending"]:
+            return Exp(E_STATE)
+        sc = s.scan
+        if op["first"] + op["n"] > self.x.count(sc["tab"], sc["inp"], sc["no"]):
+            return Exp(E_ARG)
+        if sc["over"]:
+            return Exp(E_OVERFLOW)
+        return Exp(OK, self._rec_fn(sc, op["first"], op["n"]), tab=sc["tab"])
+
+    def _packed(self, op, s):
+        if s.scan is None:
+            return Exp(E_STATE)
+        sc = s.scan
+        if sc["pending"] or sc["over"]:
+            return Exp(None)                                    # (the compact form of an unfinished or overflowed scan: no promise)
+        if self.x.width(sc["tab"], sc["knob"]) == 8:
+            return Exp(E_STATE)
+        return Exp(OK, self._rec_fn(sc), tab=sc["tab"])
+
+    def _checksum(self, op, s):
+        if self.tab is None:
+            return Exp(E_STATE)
+        sc = s.scan
+        if sc is not None and self.x.count(sc["tab"], sc["inp"], sc["no"]) == 0:
+            return Exp(OK, lambda: 0)                           # (n = 0: the checksum of nothing, whatever the slot holds)
+        if sc is None or sc["pending"] or sc["gen"] != self.gen:
+            return Exp(E_STATE)
+        if sc["over"]:
+            return Exp(E_OVERFLOW)
+        return Exp(OK, lambda: self.x.checksum(sc["tab"], sc["inp"], sc["no"], op["base"]))
+
+    def _text(self, op, s):
+        s.text = None
+        if self.tab is None:
+            return Exp(E_STATE)
+        sc = s.scan
+        if sc is None or sc["pending"] or sc["gen"] != self.gen:
+            return Exp(E_STATE)
+        if sc["over"]:
+            return Exp(E_OVERFLOW)
+        s.text = (sc["tab"], sc["inp"], sc["no"], op["base"])
+        key = s.text
+        return Exp(OK, lambda: self.x.text(*key))
+
+    def _text_fetch(self, op, s):
+        if s.text is None:
+            return Exp(None)
+        key = s.text
+        if op["first"] + op["n"] > len(self.x.text(*key)):
+            return Exp(E_ARG)
+        return Exp(OK, lambda: self.x.text(*key)[op["first"]:op["first"] + op["n"]])
+
+    # -- documents ----------------------------------------------------------
+    def _set_doc(self, op, s):
+        s.doc = (op["tab"], op["inp"], op["no"], op["dkey"])
+        s.doc_gen += 1
+        return Exp()
+
+    def _pass_state(self, s, overflow_status):
+        """The checks every pass makes on the slot's last scan, in the header's order."""
+        if s.scan is None or s.scan["pending"]:
+            return E_STATE
+        if not self.flen or s.scan["gen"] != self.gen:
+            return E_STATE
+        return overflow_status if s.scan["over"] else OK
+
+    def _doc_state(self, s):
+        if s.doc is None:
+            return E_STATE
+        return OK if offsets_ok(self.x.offsets(*s.doc), s.scan["no"]) else E_ARG
+
+    def _doc_value_key(self, s):
+        """Offsets that fit the scan: the plan makes them for (table, input, n_owned), and only those are keyed."""
+        sc = s.scan
+        if s.doc[:3] != (sc["tab"], sc["inp"], sc["no"]):
+            return None
+        return (sc["tab"], sc["inp"], sc["no"], s.doc[3])
+
+    def _segment(self, op, s):
+        s.seg = None
+        st = self._pass_state(s, E_OVERFLOW) or self._doc_state(s)
+        if st:
+            return Exp(st)
+        key = self._doc_value_key(s)
+        if key is None:
+            return Exp(None)
+        n = int(self.x.seg(*key)[0][-1])
+        if not op["own"] and op["small"]:
+            return Exp(E_OVERFLOW if n > 0 else None, count=n)
+        s.seg = dict(key=key, own=op["own"], tab=s.scan["tab"])
+        if op["own"]:
+            return Exp(OK, lambda: n)
+        return Exp(OK, lambda: (n,) + self.x.seg(*key), tab=s.scan["tab"])
+
+    def _seg_fetch(self, op, s):
+        if s.seg is None or not s.seg["own"]:
+            return Exp(E_STATE)
+        key = s.seg["key"]
+        return Exp(OK, lambda: self.x.seg(*key), tab=s.seg["tab"])
+
+    # -- selection ----------------------------------------------------------
+    def _select(self, op, s):
+        s.sel = None
+        st = self._pass_state(s, E_STATE)
+        if st:
+            return Exp(st)
+        sc = s.scan
+        if op["entry"] > self.x.M(sc["tab"]):
+            return Exp(E_ARG)
+        key = (sc["tab"], sc["inp"], sc["no"], op["entry"])
+        n = int(self.x.sel(*key)[0].size)
+        if not op["own"] and op["small"]:
+            return Exp(E_OVERFLOW if n > 0 else None, count=n)
+        s.sel = dict(kind="whole", key=key, own=op["own"], tab=sc["tab"], seq=sc["seq"], entry=op["entry"])
+        if op["own"]:
+            return Exp(OK, lambda: (n, self.x.sel(*key)[2]))
+        return Exp(OK, lambda: (n, self.x.sel(*key)[2]) + self.x.sel(*key)[:2], tab=sc["tab"])
+
+    def _select_docs(self, op, s):
+        s.sel = None
+        st = self._pass_state(s, E_STATE) or self._doc_state(s)
+        if st:
+            return Exp(st)
+        key = self._doc_value_key(s)
+        if key is None:
+            return Exp(None)
+        n = int(self.x.docsel(*key)[0][-1])
+        if not op["own"] and op["small"]:
+            return Exp(E_OVERFLOW if n > 0 else None, count=n)
+        s.sel = dict(kind="docs", key=key, own=op["own"], tab=s.scan["tab"], seq=s.scan["seq"], entry=0, doc_gen=s.doc_gen)
+        if op["own"]:
+            return Exp(OK, lambda: n)
+        return Exp(OK, lambda: (n,) + self.x.docsel(*key)[:3], tab=s.scan["tab"])
+
+    def _sel_fetch(self, op, s):
+        if s.sel is None or not s.sel["own"]:
+            return Exp(E_STATE)
+        sel = s.sel
+        if sel["kind"] == "whole":
+            return Exp(OK, lambda: self.x.sel(*sel["key"])[:2], tab=sel["tab"])
+        return Exp(OK, lambda: self.x.docsel(*sel["key"])[1:3], tab=sel["tab"])
+
+    def _docsel_fetch(self, op, s):
+        if s.sel is None or s.sel["kind"] != "docs" or not s.sel["own"]:
+            return Exp(E_STATE)
+        sel = s.sel
+        return Exp(OK, lambda: self.x.docsel(*sel["key"])[:3], tab=sel["tab"])
+
+    # -- replace ------------------------------------------------------------
+    def _rp_state(self, s, docs):
+        if s.scan is None or s.sel is None or s.sel["seq"] != s.scan["seq"] or (docs and s.sel["kind"] != "docs"):
+            return E_STATE
+        if s.scan["gen"] != self.gen or self.reps is None or not self.flen:
+            return E_STATE
+        if docs and s.sel["doc_gen"] != s.doc_gen:
+            return E_STATE
+        return OK
+
+    def _rp_out(self, sel, rkey):
+        if sel["kind"] == "whole":
+            t, i, no, entry = sel["key"]
+            return lambda: self.x.replace(t, i, no, entry, rkey)
+        return lambda: self.x.docsel(*sel["key"], rkey)[4]
+
+    def _replace(self, op, s, docs=False):
+        s.rp = s.rpd = None
+        st = self._rp_state(s, docs)
+        if st:
+            return Exp(st)
+        sel, rkey = s.sel, self.reps
+        out = self._rp_out(sel, rkey)
+        n = int(out().size)
+        if not op["own"] and op["small"]:
+            return Exp(E_OVERFLOW if n > 0 else None, count=n)
+        s.rp = dict(out=out, own=op["own"])
+        if docs:
+            off = lambda: self.x.docsel(*sel["key"], rkey)[3]                # noqa: E731
+            s.rpd = dict(off=off, own=op["own"])
+            return Exp(OK, (lambda: n) if op["own"] else (lambda: (n, out(), off())))
+        return Exp(OK, (lambda: n) if op["own"] else (lambda: (n, out())))
+
+    def _replace_docs(self, op, s):
+        return self._replace(op, s, docs=True)
+
+    def _rp_fetch(self, op, s):
+        if s.rp is None or not s.rp["own"]:
+            return Exp(E_STATE)
+        out = s.rp["out"]
+        if op["first"] + op["n"] > out().size:
+            return Exp(E_ARG)
+        return Exp(OK, lambda: out()[op["first"]:op["first"] + op["n"]])
+
+    def _rpd_fetch(self, op, s):
+        if s.rpd is None or not s.rpd["own"]:
+            return Exp(E_STATE)
+        return Exp(OK, s.rpd["off"])
+
+    # -- plumbing -----------------------------------------------------------
+    def _set_stream(self, op, s):
+        s.shared = op["share"]
+        return Exp()
+
+    def _sync(self, op, s):
+        return Exp()
+
+    def _reserve_grow(self, op, s):
+        """A reserve above everything the slot holds: a buffer it already has is replaced, and the slot then has no
+        finished scan."""
+        s.grow = op["k"]
+        grow_in, grow_rec = op["which"] in ("input", "both"), op["which"] in ("records", "both")
+        if (grow_in and s.has_in) or (grow_rec and s.has_rec):
+            s.scan = None
+        s.has_in, s.has_rec = s.has_in or grow_in, s.has_rec or grow_rec
+        return Exp()
+
+
+# ---------------------------------------------------------------------------
+# plans
+
+def fmt(op):
+    return op["op"] + "(" + ", ".join(f"{k}={v}" for k, v in op.items() if k != "op") + ")"
+
+
+def _window(rng, total):
+    """A [first, first + n) window of `total` items: all, a slice, or (now and then) one past the end."""
+    r = rng.random()
+    if r < 0.35 or total == 0:
+        return (0, total) if r < 0.3 or total == 0 and r < 0.9 else (0, total + 1)
+    if r < 0.9:
+        first = int(rng.integers(0, total))
+        return first, int(rng.integers(0, total - first + 1))
+    return int(rng.integers(0, total + 1)), total + 1
+
+
+KINDS = {"load_table": 4, "set_flen": 1, "set_reps": 2, "scan_bytes": 9, "scan_start": 5, "scan_finish": 2, "scan_ext": 6, "records": 7,
+         "packed": 4, "checksum": 4, "text": 5, "text_fetch": 3, "set_doc": 4, "segment": 4, "select": 4, "select_docs": 4, "replace": 4,
+         "replace_docs": 4, "seg_fetch": 3, "sel_fetch": 3, "docsel_fetch": 3, "rp_fetch": 3, "rpd_fetch": 3, "set_stream": 2, "sync": 1,
+         "reserve_grow": 3}
+
+
+def _propose(rng, m):
+    """One candidate operation, drawn with an eye on the model's state (so most candidates have real data behind them)
+    but never filtered by it: the caller asks the model what the candidate is worth."""
+    x = m.x
+    slot = int(rng.integers(0, N_SLOTS))
+    s = m.slots[slot]
+    sc = s.scan
+    w = np.array(list(KINDS.values()), dtype=float)
+    kind = str(rng.choice(list(KINDS), p=w / w.sum()))
+    op = dict(op=kind, slot=slot)
+    if kind == "load_table":
+        op.pop("slot")
+        op["tab"] = str(rng.choice(sorted(TABLES)))
+        op["knob"] = int(rng.choice(TABLES[op["tab"]]["knobs"]))
+    elif kind == "set_flen":
+        op.pop("slot")
+    elif kind == "set_reps":
+        op.pop("slot")
+        op["rkey"] = str(rng.choice(REP_KEYS))
+    elif kind in ("scan_bytes", "scan_start", "scan_ext"):
+        tab = m.tab or "abc2"
+        op["inp"] = int(rng.integers(0, len(TABLES[tab]["inputs"])))
+        n = x.input_size(tab, op["inp"])
+        op["no"] = n if rng.random() < 0.6 else (n * 5) // 8
+        if kind != "scan_bytes":
+            cnt = x.count(tab, op["inp"], op["no"])
+            op["cap"] = cnt // 2 if (kind == "scan_ext" and cnt >= 64 and rng.random() < 0.3) else cnt + cnt // 4 + 65536
+    elif kind == "records":
+        total = x.count(sc["tab"], sc["inp"], sc["no"]) if sc else 5
+        op["first"], op["n"] = _window(rng, total)
+    elif kind in ("checksum", "text"):
+        op["base"] = int(rng.choice(TEXT_BASES))
+    elif kind == "text_fetch":
+        total = len(x.text(*s.text)) if s.text else 0
+        op["first"], op["n"] = _window(rng, total)
+    elif kind == "set_doc":
+        if sc is None:
+            return None
+        op.update(tab=sc["tab"], inp=sc["inp"], no=sc["no"], dkey=str(rng.choice(DOC_KEYS, p=[.4, .4, .1, .1])))
+    elif kind in PASSES:
+        op["own"] = bool(rng.random() < 0.6)
+        op["small"] = bool(not op["own"] and rng.random() < 0.25)
+        if kind == "select":
+            M = x.M(sc["tab"]) if sc else 1
+            op["entry"] = int(rng.choice([0, 0, 1, M, M + 1], p=[.3, .2, .2, .2, .1]))
+    elif kind == "rp_fetch":
+        total = int(s.rp["out"]().size) if s.rp else 3
+        op["first"], op["n"] = _window(rng, total)
+    elif kind == "set_stream":
+        op["slot"] = 1
+        op["share"] = not m.slots[1].shared
+    elif kind == "reserve_grow":
+        op["which"] = str(rng.choice(["input", "records", "both"]))
+        op["k"] = s.grow + 1
+    return op
+
+
+def _pass_op(kind, slot, own=True):
+    op = dict(op=kind, slot=slot, own=own, small=False)
+    if kind == "select":
+        op["entry"] = 0
+    return op
+
+
+PRODUCER_OF = {v: k for k, v in FETCH_OF.items()}
+
+
+def _prepare(rng, kind, slot):
+    """What a session does before pass `kind` on `slot` so that the pass has something to work on: steps that look at
+    the model when their turn comes and return an operation, or None when nothing is missing."""
+    def table(m):
+        if m.tab is None:
+            tab = str(rng.choice(sorted(TABLES)))
+            return dict(op="load_table", tab=tab, knob=int(rng.choice(TABLES[tab]["knobs"])))
+
+    def scan(m):
+        sc = m.slots[slot].scan
+        if sc is not None and sc["pending"]:
+            return dict(op="scan_finish", slot=slot)
+        if sc is None or sc["over"] or sc["gen"] != m.gen:
+            inp = int(rng.integers(0, len(TABLES[m.tab]["inputs"])))
+            n = m.x.input_size(m.tab, inp)
+            return dict(op="scan_bytes", slot=slot, inp=inp, no=n if rng.random() < 0.6 else (n * 5) // 8)
+
+    def doc(m):
+        s = m.slots[slot]
+        sc = s.scan
+        if sc is not None and (s.doc is None or s.doc[:3] != (sc["tab"], sc["inp"], sc["no"]) or s.doc[3].startswith("bad")):
+            return dict(op="set_doc", slot=slot, tab=sc["tab"], inp=sc["inp"], no=sc["no"], dkey=str(rng.choice(DOC_KEYS[:2])))
+
+    def sel(m):
+        s = m.slots[slot]
+        want = "docs" if kind == "replace_docs" else None
+        if s.scan is None or s.sel is None or s.sel["seq"] != s.scan["seq"] or (want and (s.sel["kind"] != want or s.sel["doc_gen"] != s.doc_gen)):
+            return _pass_op("select_docs" if want or rng.random() < 0.3 else "select", slot, own=bool(rng.random() < 0.7))
+
+    steps = [table, lambda m: None if m.flen else dict(op="set_flen")]
+    if kind in ("replace", "replace_docs"):
+        steps.append(lambda m: None if m.reps else dict(op="set_reps", rkey=str(rng.choice(REP_KEYS))))
+    steps.append(scan)
+    if kind in ("segment", "select_docs", "replace_docs", "replace"):
+        steps.append(doc)
+    if kind in ("replace", "replace_docs"):
+        steps.append(sel)
+    return steps
+
+
+def plan(seed, n_ops=PLAN_OPS):
+    """The plan of `seed`: a list of operations (dicts).  Deterministic; the model decides what each one is worth."""
+    rng = np.random.default_rng([seed, 0x53455353494F4E])
+    m = Model()
+    ops, agenda = [], []
+    while len(ops) < n_ops:
+        want_err = rng.random() < 1 / 8
+        chosen = None
+        while agenda and chosen is None and not want_err:      # what the session set out to do comes first
+            cand = agenda.pop(0)
+            cand = cand(m) if callable(cand) else cand
+            if cand is not None and m.predict(cand).status is not None:
+                chosen = cand
+        for _ in range(60):
+            if chosen is not None:
+                break
+            cand = _propose(rng, m)
+            if cand is None:
+                continue
+            st = m.predict(cand).status
+            if st is None:
+                continue
+            if (st != OK) == want_err:
+                chosen = cand
+            elif st != OK and not agenda and (cand["op"] in PASSES or cand["op"] in PRODUCER_OF):
+                # a pass (or the fetch of one) with nothing to work on: do what is missing first, then the pass
+                if cand["op"] in PASSES:
+                    agenda = _prepare(rng, cand["op"], cand["slot"]) + [cand]
+                else:
+                    prod = PRODUCER_OF[cand["op"]]
+                    agenda = _prepare(rng, prod, cand["slot"]) + [_pass_op(prod, cand["slot"]), cand]
+        if chosen is None:
+            continue
+        st = m.apply(chosen).status
+        ops.append(chosen)
+        # a pass that left a slot-owned result: now and then another pass first, then the late fetch of this one's output
+        if st == OK and chosen["op"] in PASSES and chosen.get("own") and rng.random() < 0.4:
+            other = str(rng.choice([p for p in PASSES if p != chosen["op"]]))
+            slot = chosen["slot"]
+            agenda += _prepare(rng, other, slot) + [_pass_op(other, slot), dict(op=FETCH_OF[chosen["op"]], slot=slot,
+                                                                                **({"first": 0, "n": 1} if chosen["op"] == "replace" else {}))]
+        # histories the header has a sentence for: a replace of a selection made before a table upload; records of a
+        # scan that overflowed its heap; ...
+        if st == OK and chosen["op"] in ("select", "select_docs") and rng.random() < 0.15:
+            tab = str(rng.choice(sorted(TABLES)))
+            agenda = [dict(op="load_table", tab=tab, knob=int(rng.choice(TABLES[tab]["knobs"]))), dict(op="set_flen"),
+                      dict(op="set_reps", rkey=str(rng.choice(REP_KEYS))), _pass_op("replace", chosen["slot"])] + agenda
+        if st == OK and chosen["op"] == "select_docs" and rng.random() < 0.15:     # ... a per-document replace after new offsets
+            sc = m.slots[chosen["slot"]].scan
+            agenda = [dict(op="set_doc", slot=chosen["slot"], tab=sc["tab"], inp=sc["inp"], no=sc["no"], dkey=str(rng.choice(DOC_KEYS[:2]))),
+                      _pass_op("replace_docs", chosen["slot"])] + agenda
+        if st == OK and chosen["op"] == "scan_ext" and m.slots[chosen["slot"]].scan["over"] and rng.random() < 0.7:
+            agenda = [dict(op="records", slot=chosen["slot"], first=0, n=int(rng.integers(1, 33)))] + agenda
+        if st == OK and chosen["op"] == "load_table" and rng.random() < 0.75:   # after an upload most sessions set lengths and replacements again
+            agenda = [dict(op="set_flen"), dict(op="set_reps", rkey=str(rng.choice(REP_KEYS)))] + agenda
+        if st == OK and chosen["op"] == "scan_start" and rng.random() < 0.7:    # the other slot works while this scan is pending
+            agenda = [dict(op="scan_bytes", slot=1 - chosen["slot"], inp=chosen["inp"], no=chosen["no"]),
+                      dict(op="scan_finish", slot=chosen["slot"])] + agenda
+    return ops
+
+
+def shrink(seed, k, n_ops=PLAN_OPS):
+    """The plan of `seed` with operation k onwards removed: cut a failing history down by hand."""
+    return plan(seed, n_ops)[:k]
+
+
+# ---------------------------------------------------------------------------
+# the executor
+
+class _SlotBufs:
+    def __init__(self):
+        self.inp = self.rec = self.sel = self.first = None      # caller-owned device buffers the slot's state refers to
+
+
+def _alloc(g, n_bytes):
+    if hasattr(g, "alloc"):
+        return g.alloc(n_bytes)
+    import torch
+    return torch.empty(max(int(n_bytes), 16), dtype=torch.uint8, device=f"cuda:{g.device}")
+
+
+def _upload(g, arr):
+    if hasattr(g, "upload"):
+        return g.upload(arr)
+    import torch
+    buf = _alloc(g, arr.nbytes + 4096)
+    if arr.nbytes:
+        buf[:arr.nbytes].copy_(torch.from_numpy(np.ascontiguousarray(arr).view(np.uint8).copy()))
+    torch.cuda.synchronize(g.device)
+    return buf
+
+
+def _download(g, buf, dtype, count):
+    if hasattr(g, "download"):
+        return g.download(buf, dtype, count)
+    return buf.cpu().numpy()[:count * np.dtype(dtype).itemsize].view(dtype).copy()
+
+
+def _same(got, want, what="value"):
+    if isinstance(want, tuple):
+        assert isinstance(got, tuple) and len(got) == len(want), f"{what}: got {got!r:.80}, want {len(want)} parts"
+        for k, (a, b) in enumerate(zip(got, want)):
+            _same(a, b, f"{what}[{k}]")
+    elif isinstance(want, np.ndarray):
+        got = np.asarray(got)
+        assert got.size == want.size, f"{what}: {got.size} entries, want {want.size}"
+        if got.size:
+            ne = np.flatnonzero(got.astype(np.uint64) != want.astype(np.uint64))
+            assert ne.size == 0, f"{what}: first difference at index {int(ne[0])}: {got[ne[0]]} != {want[ne[0]]} ({ne.size} differ)"
+    elif isinstance(want, (bytes, bytearray)):
+        got = bytes(got)
+        assert len(got) == len(want), f"{what}: {len(got)} bytes, want {len(want)}"
+        if got != want:
+            ne = np.flatnonzero(np.frombuffer(got, np.uint8) != np.frombuffer(want, np.uint8))
+            raise AssertionError(f"{what}: first difference at byte {int(ne[0])} ({ne.size} differ)")
+    else:
+        assert got == want and (got is None) == (want is None), f"{what}: {got}, want {want}"
+
+
+class Executor:
+    def __init__(self, g, model):
+        self.g, self.m = g, model
+        self.x = model.x
+        self.bufs = [_SlotBufs() for _ in range(N_SLOTS)]
+        self.stats = dict(ops=0, errors=0, compared=0, widths=set(), staging=set(), variants=set(), statuses=set())
+        self.ids_direct = getattr(g, "states_are_ids", False)
+
+    def ids(self, tab, states):
+        st = np.asarray(states).astype(np.int64)
+        return st if self.ids_direct or tab is None else np.asarray(self.x.table(tab).idmap, dtype=np.int64)[st]
+
+    def recs(self, tab, rec):
+        self.stats["compared"] += int(rec.size)
+        return rec["pos"].astype(np.int64), self.ids(tab, rec["state"])
+
+    def note_scan(self, slot):
+        self.stats["widths"].add(int(self.g.scan_format(slot)[0]))
+        info = self.g.info()
+        self.stats["staging"].add((info["staging_buffers"], info["staging_records"]))
+        self.stats["variants"].add(info["variant"])
+
+    def step(self, op):
+        """Perform one operation and compare with the model.  Returns the model's status."""
+        s = self.m.slots[op.get("slot", 0)]
+        before = dict(scan=dict(s.scan) if s.scan else None, sel=dict(s.sel) if s.sel else None)
+        exp = self.m.apply(op)
+        assert exp.status is not None, "the contract does not decide this operation: a plan must not contain it"
+        self.stats["ops"] += 1
+        self.stats["statuses"].add(exp.status)
+        try:
+            got = getattr(self, "do_" + op["op"])(op, exp, before)
+        except PfacError as e:
+            assert e.status == exp.status, f"raised {e} (status {e.status}), want {STATUS_NAMES[exp.status]}"
+            if exp.count is not None:
+                n = [getattr(e, a) for a in ("n_kept", "n_selected", "out_bytes") if hasattr(e, a)]
+                assert n == [exp.count], f"the overflow error carries {n}, want [{exp.count}]"
+            self.stats["errors"] += 1
+            return exp.status
+        assert exp.status == OK, f"returned normally, want {STATUS_NAMES[exp.status]}"
+        _same(got, exp.value())
+        return OK
+
+    # -- tables -------------------------------------------------------------
+    def do_load_table(self, op, exp, before):
+        saved = {k: os.environ.get(k) for k in KNOB_NAMES}
+        for k in KNOB_NAMES:
+            os.environ.pop(k, None)
+        os.environ.update(KNOBS[op["knob"]])                    # knobs are read when a table is installed
+        try:
+            self.g.load_table(self.x.table(op["tab"]))
+        finally:
+            for k, v in saved.items():
+                os.environ.pop(k, None)
+                if v is not None:
+                    os.environ[k] = v
+
+    def do_set_flen(self, op, exp, before):
+        t = self.m.tab
+        self.g.set_final_lengths(self.x.table(t).final_lengths() if t else np.ones(1, np.int32))
+
+    def do_set_reps(self, op, exp, before):
+        if op["rkey"] == "redact":
+            self.g.set_redaction(b"#")
+        else:
+            self.g.set_replacements(self.x.reps(self.m.tab, op["rkey"]) if self.m.tab else {})
+
+    # -- scans --------------------------------------------------------------
+    def _data(self, op):
+        return self.x.input(self.m.tab or "abc2", op["inp"])
+
+    def _own_scan(self, slot):
+        self.bufs[slot].inp = self.bufs[slot].rec = None
+
+    def do_scan_bytes(self, op, exp, before):
+        self._own_scan(op["slot"])
+        rec = self.g.scan_bytes(self._data(op), op["no"], slot=op["slot"])
+        self.note_scan(op["slot"])
+        return self.recs(exp.tab, rec)
+
+    def do_scan_start(self, op, exp, before):
+        g, data, slot = self.g, self._data(op), op["slot"]
+        self._own_scan(slot)
+        g.reserve(slot, max(data.size, 1), max(op["cap"], 1))
+        if data.size:
+            g.h2d(data, slot)
+        g.scan_async(op["no"], data.size, slot=slot)
+
+    def do_scan_finish(self, op, exp, before):
+        n, over = self.g.scan_finish(op["slot"], allow_overflow=True)
+        self.note_scan(op["slot"])
+        return int(n), bool(over)
+
+    def do_scan_ext(self, op, exp, before):
+        g, data, slot = self.g, self._data(op), op["slot"]
+        d_in, d_rec = _upload(g, data), _alloc(g, max(op["cap"], 1) * 8 + 64)
+        g.scan_async(op["no"], data.size, d_input=d_in, d_records=d_rec, capacity=op["cap"], slot=slot)
+        self.bufs[slot].inp, self.bufs[slot].rec = d_in, d_rec
+        n, over = g.scan_finish(slot, allow_overflow=True)
+        self.note_scan(slot)
+        return int(n), bool(over)
+
+    def do_records(self, op, exp, before):
+        rec = self.g.records_to_host(op["n"], op["slot"], d_records=self.bufs[op["slot"]].rec, first=op["first"])
+        return self.recs(exp.tab, rec)
+
+    def do_packed(self, op, exp, before):
+        from phfpfac_amd.dist import packed_to_records
+        words, tix = self.g.packed_to_host(op["slot"], d_records=self.bufs[op["slot"]].rec)
+        return self.recs(exp.tab, packed_to_records(words, tix, self.g.scan_format(op["slot"])[0]))
+
+    def do_checksum(self, op, exp, before):
+        sc = before["scan"]
+        n = self.x.count(sc["tab"], sc["inp"], sc["no"]) if sc else 1
+        return int(self.g.checksum(n, op["base"], op["slot"], d_records=self.bufs[op["slot"]].rec))
+
+    def do_text(self, op, exp, before):
+        n = self.g.emit_text_device(op["base"], op["slot"], d_records=self.bufs[op["slot"]].rec)
+        self.stats["compared"] += int(n)
+        return self.g.text_to_host(n, op["slot"])
+
+    def do_text_fetch(self, op, exp, before):
+        return self.g.text_to_host(op["n"], op["slot"], first=op["first"])
+
+    # -- documents ----------------------------------------------------------
+    def do_set_doc(self, op, exp, before):
+        self.g.set_doc_offsets(self.x.offsets(op["tab"], op["inp"], op["no"], op["dkey"]), op["slot"])
+
+    def _n_docs(self, slot):
+        doc = self.m.slots[slot].doc
+        return int(self.x.offsets(*doc).size - 1) if doc else 1
+
+    def _cap(self, op, exp):
+        if exp.status == OK:
+            return exp.value()[0]
+        return exp.count // 2 if exp.count is not None else 0   # (an overflow the model expects, else the call fails before it looks)
+
+    def do_segment(self, op, exp, before):
+        g, slot = self.g, op["slot"]
+        nd = self._n_docs(slot)
+        if op["own"]:
+            return int(g.segment_records(nd, slot=slot, d_records=self.bufs[slot].rec))
+        cap = self._cap(op, exp)
+        d_out, d_first = _alloc(g, cap * 8 + 16), _alloc(g, (nd + 1) * 8)
+        n = int(g.segment_records(nd, d_out=d_out, out_cap=cap, d_doc_first=d_first, slot=slot, d_records=self.bufs[slot].rec))
+        g.sync(slot)
+        return (n, _download(g, d_first, np.uint64, nd + 1)) + self.recs(exp.tab, _download(g, d_out, REC, n))
+
+    def do_seg_fetch(self, op, exp, before):
+        seg = self.m.slots[op["slot"]].seg
+        n, nd = (int(self.x.seg(*seg["key"])[0][-1]), int(self.x.offsets(*seg["key"]).size - 1)) if seg else (0, 1)
+        first, rec = self.g.segment_to_host(n, nd, op["slot"])
+        return (first,) + self.recs(exp.tab, rec)
+
+    # -- selection ----------------------------------------------------------
+    def do_select(self, op, exp, before):
+        g, slot = self.g, op["slot"]
+        self.bufs[slot].sel = self.bufs[slot].first = None
+        if op["own"]:
+            n, ex = g.select_leftmost_longest(op["entry"], slot=slot, d_records=self.bufs[slot].rec)
+            return int(n), int(ex)
+        cap = self._cap(op, exp)
+        d_out = _alloc(g, cap * 8 + 16)
+        n, ex = g.select_leftmost_longest(op["entry"], d_out=d_out, out_cap=cap, slot=slot, d_records=self.bufs[slot].rec)
+        g.sync(slot)
+        self.bufs[slot].sel = d_out
+        return (int(n), int(ex)) + self.recs(exp.tab, _download(g, d_out, REC, int(n)))
+
+    def do_select_docs(self, op, exp, before):
+        g, slot = self.g, op["slot"]
+        nd = self._n_docs(slot)
+        self.bufs[slot].sel = self.bufs[slot].first = None
+        if op["own"]:
+            return int(g.select_leftmost_longest_documents(nd, slot=slot, d_records=self.bufs[slot].rec))
+        cap = self._cap(op, exp)
+        d_out, d_first = _alloc(g, cap * 8 + 16), _alloc(g, (nd + 1) * 8)
+        n = int(g.select_leftmost_longest_documents(nd, d_out=d_out, out_cap=cap, d_doc_first=d_first, slot=slot, d_records=self.bufs[slot].rec))
+        g.sync(slot)
+        self.bufs[slot].sel, self.bufs[slot].first = d_out, d_first
+        return (n, _download(g, d_first, np.uint64, nd + 1)) + self.recs(exp.tab, _download(g, d_out, REC, n))
+
+    def _sel_n(self, slot):
+        sel = self.m.slots[slot].sel
+        if sel is None:
+            return 0, 1
+        if sel["kind"] == "whole":
+            return int(self.x.sel(*sel["key"])[0].size), 1
+        return int(self.x.docsel(*sel["key"])[0][-1]), int(self.x.offsets(*sel["key"]).size - 1)
+
+    def do_sel_fetch(self, op, exp, before):
+        return self.recs(exp.tab, self.g.selection_to_host(self._sel_n(op["slot"])[0], op["slot"]))
+
+    def do_docsel_fetch(self, op, exp, before):
+        n, nd = self._sel_n(op["slot"])
+        first, rec = self.g.doc_selection_to_host(n, nd, op["slot"])
+        return (first,) + self.recs(exp.tab, rec)
+
+    # -- replace ------------------------------------------------------------
+    def do_replace(self, op, exp, before, docs=False):
+        g, slot = self.g, op["slot"]
+        b, sel = self.bufs[slot], before["sel"]
+        kw = dict(d_input=b.inp, slot=slot, d_sel=b.sel)
+        if docs:
+            kw["d_doc_first"] = b.first
+        call = g.replace_selection_documents if docs else g.replace_selection
+        if op["own"]:
+            return int(call(**kw))
+        cap = self._cap(op, exp)
+        d_out = _alloc(g, cap + 64)
+        nd = int(self.x.offsets(*sel["key"]).size - 1) if docs and sel is not None and sel["kind"] == "docs" else 1
+        if docs:
+            kw["d_out_offsets"] = _alloc(g, (nd + 1) * 8)
+        n = int(call(d_out=d_out, out_cap=cap, **kw))
+        g.sync(slot)
+        self.stats["compared"] += n
+        out = (n, _download(g, d_out, np.uint8, n))
+        return out + (_download(g, kw["d_out_offsets"], np.uint64, nd + 1),) if docs else out
+
+    def do_replace_docs(self, op, exp, before):
+        return self.do_replace(op, exp, before, docs=True)
+
+    def do_rp_fetch(self, op, exp, before):
+        self.stats["compared"] += op["n"]
+        return self.g.replacement_to_host(op["n"], op["slot"], first=op["first"])
+
+    def do_rpd_fetch(self, op, exp, before):
+        rpd = self.m.slots[op["slot"]].rpd
+        return self.g.replacement_doc_offsets_to_host(int(rpd["off"]().size - 1) if rpd else 1, op["slot"])
+
+    # -- plumbing -----------------------------------------------------------
+    def do_set_stream(self, op, exp, before):
+        self.g.set_stream(1, self.g.stream_handle(0) if op["share"] else 0)
+
+    def do_sync(self, op, exp, before):
+        self.g.sync(op["slot"])
+
+    def do_reserve_grow(self, op, exp, before):
+        self.g.reserve(op["slot"], op["k"] * IN_STEP if op["which"] in ("input", "both") else 0,
+                       op["k"] * REC_STEP if op["which"] in ("records", "both") else 0)
+        if self.m.slots[op["slot"]].scan is None:
+            self._own_scan(op["slot"])
+
+
+def run(g, ops, model=None, seed=None):
+    """Performs `ops` on `g` (one context, never re-created), comparing every result with `model` bit for bit.  Returns
+    the executor's statistics; raises AssertionError naming the seed, the operation and the ten before it."""
+    ex = Executor(g, model or Model())
+    for k, op in enumerate(ops):
+        try:
+            ex.step(op)
+        except AssertionError as e:
+            hist = "\n".join(f"    {j:3d}  {fmt(ops[j])}" for j in range(max(0, k - 10), k + 1))
+            e2 = AssertionError(f"session seed {seed}, operation {k} {fmt(op)}: {e}\n  the operations up to it (cut the plan with shrink({seed}, k)):\n{hist}")
+            e2.op_index = k
+            raise e2 from e
+    return ex.stats

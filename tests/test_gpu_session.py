@@ -1,0 +1,266 @@
+"""Sessions: ONE GpuMatcher context driven through long sequences of calls (tests/session.py) -- many tables under different
+kernel knobs, many sizes, two slots, passes in any order, results fetched late, documented errors in between -- every
+result compared bit for bit with what include/pfac.h promises for that history.  The random plans are the suite's seeds;
+the named sessions are histories random plans reach rarely.  Run with -m gpu on an MI355X.  Expectations come from the
+CPU oracle, llref, replref, docref, docreplref and the pattern files, never from the device.  No session aims at the
+scan's wait protocol: they provoke the errors the header documents, nothing else."""
+import gc
+import weakref
+
+import numpy as np
+import pytest
+
+import session as S
+from phfpfac_amd import GpuMatcher
+from phfpfac_amd.matcher import splitmix64_bytes
+
+pytestmark = pytest.mark.gpu
+
+X = S.expectations()
+
+
+def k(tab, **knobs):
+    i = S.KNOBS.index(knobs)
+    assert i in S.TABLES[tab]["knobs"]
+    return i
+
+
+def load(tab, rkey="r0", **knobs):
+    return [dict(op="load_table", tab=tab, knob=k(tab, **knobs)), dict(op="set_flen"), dict(op="set_reps", rkey=rkey)]
+
+
+def scan(tab, inp, slot=0, no=None):
+    return dict(op="scan_bytes", slot=slot, inp=inp, no=X.input_size(tab, inp) if no is None else no)
+
+
+def records(tab, inp, slot=0, no=None, first=0, n=None):
+    total = X.count(tab, inp, X.input_size(tab, inp) if no is None else no)
+    return dict(op="records", slot=slot, first=first, n=total - first if n is None else n)
+
+
+def doc(tab, inp, dkey, slot=0, no=None):
+    return dict(op="set_doc", slot=slot, tab=tab, inp=inp, no=X.input_size(tab, inp) if no is None else no, dkey=dkey)
+
+
+def pss(kind, slot=0, own=True, entry=0):
+    op = dict(op=kind, slot=slot, own=own, small=False)
+    if kind == "select":
+        op["entry"] = entry
+    return op
+
+
+def fetch(kind, slot=0, **kw):
+    return dict(op=kind, slot=slot, **kw)
+
+
+def run(ops, want=None):
+    """The operations on one fresh context; `want`: the statuses the model must give, as a check of the session itself."""
+    m = S.Model()
+    if want is not None:
+        probe = S.Model()
+        got = [probe.apply(op).status for op in ops]
+        assert got == want, [(S.fmt(op), S.STATUS_NAMES[g]) for op, g in zip(ops, got)]
+    with GpuMatcher(0, S.N_SLOTS) as g:
+        return S.run(g, ops, m, seed="named")
+
+
+@pytest.mark.parametrize("seed", S.SEEDS)
+def test_session(seed):
+    """One random plan on one context."""
+    ops = S.plan(seed)
+    with GpuMatcher(0, S.N_SLOTS) as g:
+        st = S.run(g, ops, S.Model(), seed=seed)
+    print(f"session {seed}: {st['ops']} operations ({st['errors']} documented errors), {st['compared']} records and bytes compared, "
+          f"record widths {sorted(st['widths'])}, staging {sorted(st['staging'])}, {sorted(st['variants'])}")
+
+
+def test_large_dense_then_tiny_sparse_then_every_pass():
+    """Every scratch and output buffer is sized by the large scan and then used by a tiny one: what a pass does not
+    clear of d_gsum, the tile counts, the bitmaps or the outputs still holds the large call's data."""
+    t = "abc2"
+    ops = load(t) + [scan(t, 0), records(t, 0), doc(t, 0, "d0"), pss("segment"), pss("select"), pss("replace"), pss("select_docs"),
+                     pss("replace_docs"), fetch("text", base=0), fetch("checksum", base=0)]
+    for inp in (3, 2):                                           # 17 bytes, then 64 tiles + 1 byte at 2 % density
+        total = len(X.text(t, inp, X.input_size(t, inp), 999_999_990))
+        ops += [scan(t, inp), records(t, inp), fetch("packed"), fetch("checksum", base=999_999_990), fetch("text", base=999_999_990),
+                fetch("text_fetch", first=total // 2, n=total - total // 2),
+                doc(t, inp, "d1"), pss("segment"), fetch("seg_fetch"), pss("select", entry=1), fetch("sel_fetch"), pss("replace"),
+                fetch("rp_fetch", first=0, n=int(X.replace(t, inp, X.input_size(t, inp), 1, "r0").size)),
+                pss("select_docs"), fetch("docsel_fetch"), fetch("seg_fetch"), pss("replace_docs"), fetch("rpd_fetch"),
+                pss("segment", own=False), pss("select_docs", own=False), pss("replace_docs", own=False), pss("select", own=False),
+                pss("replace", own=False)]
+    st = run(ops, want=[S.OK] * len(ops))
+    assert st["compared"] > 300_000
+
+
+def test_staging_layout_flips_both_ways_with_exact_records():
+    """Dense and matchless inputs of 74 tiles in turn, no knob pinned: the staging layout of the NEXT scan follows the
+    density of the last one, for the whole context -- so slot 1's scan runs in the mode slot 0's scan chose."""
+    t = "abc2"
+    seen = []
+    with GpuMatcher(0, S.N_SLOTS) as g:
+        ex = S.Executor(g, S.Model())
+        for op in load(t):
+            ex.step(op)
+        seen.append(g.info()["staging_buffers"])
+        for rnd, inp in enumerate((0, 1, 0, 0, 1, 1, 0, 1)):
+            ex.step(scan(t, inp, slot=rnd % 2))
+            seen.append(g.info()["staging_buffers"])
+            ex.step(records(t, inp, slot=rnd % 2))
+            ex.step(fetch("checksum", slot=rnd % 2, base=0))
+    to_dense = sum(a != 1 and b == 1 for a, b in zip(seen, seen[1:]))
+    from_dense = sum(a == 1 and b != 1 for a, b in zip(seen, seen[1:]))
+    assert to_dense >= 1 and from_dense >= 1, seen
+
+
+def test_record_width_2_then_8_then_4_on_one_heap():
+    """The record width follows the table while the slot's heap and tile index are reused; the records of a scan made
+    with an earlier table stay fetchable in THEIR width after the upload, while what needs that table's idmap, lengths
+    or replacements is refused (and a refused selection leaves no selection to fetch)."""
+    ops = load("abc2") + [scan("abc2", 0), records("abc2", 0), pss("select")]
+    ops += load("wide8", PFAC_WIDE="1") + [records("abc2", 0, first=5, n=1000), fetch("packed"), fetch("checksum", base=0), fetch("text", base=0),
+                                            pss("select"), pss("replace"), fetch("sel_fetch"),
+                                            scan("wide8", 1), records("wide8", 1), fetch("packed"), fetch("checksum", base=0), pss("select")]
+    ops += load("mid4") + [records("wide8", 1), pss("segment"), scan("mid4", 2), records("mid4", 2), fetch("packed"), pss("select"),
+                           fetch("sel_fetch"), pss("replace"), fetch("rp_fetch", first=0, n=64)]
+    E = S.E_STATE
+    st = run(ops, want=[0] * 3 + [0, 0, 0] + [0] * 3 + [0, 0, E, E, E, E, E, 0, 0, E, 0, 0] + [0] * 3 + [0, E, 0, 0, 0, 0, 0, 0, 0])
+    assert st["widths"] == {2, 4, 8}
+
+
+def test_bad_document_offsets_then_good_ones():
+    """PFAC_E_ARG for offsets that break the rules, and the very next call with good ones is exact (the error word of
+    the check is the pass's to clear); new offsets for the slot, even equal ones, end the right of the per-document replace
+    to the selection cut with the old ones; an empty scan's per-document selection zeroes every doc_first."""
+    t = "l2"
+    A = S.E_ARG
+    ops = load(t, PFAC_FORCE_L2="1") + [scan(t, 0), doc(t, 0, "bad_end"), pss("segment"), doc(t, 0, "d0"), pss("segment"), fetch("seg_fetch"),
+                                        doc(t, 0, "bad_order"), pss("select_docs"), fetch("docsel_fetch"), doc(t, 0, "d1"), pss("select_docs"),
+                                        fetch("docsel_fetch"), doc(t, 0, "d1"), pss("replace_docs"), fetch("docsel_fetch"),
+                                        doc(t, 0, "bad_order"), pss("segment"), doc(t, 0, "d1"), pss("segment", own=False),
+                                        doc(t, 0, "bad_end"), pss("select_docs", own=False), doc(t, 0, "d0"), pss("select_docs", own=False)]
+    run(ops, want=[0] * 3 + [0, 0, A, 0, 0, 0, 0, A, S.E_STATE, 0, 0, 0, 0, S.E_STATE, 0, 0, A, 0, 0, 0, A, 0, 0])
+    t = "dups"
+    ops = load(t) + [scan(t, 0), doc(t, 0, "d1"), pss("select_docs"), fetch("docsel_fetch"), pss("segment"),
+                     scan(t, 2), doc(t, 2, "d1"), pss("select_docs"), fetch("docsel_fetch"), pss("segment"), fetch("seg_fetch"),
+                     pss("replace_docs"), fetch("rpd_fetch"), doc(t, 2, "bad_end"), pss("select_docs"), doc(t, 2, "d0"), pss("select_docs", own=False)]
+    run(ops, want=[0] * 3 + [0] * 13 + [0, A, 0, 0])
+
+
+def test_replace_output_outlives_new_replacements():
+    """replace_selection into the slot-owned buffer, then another table of replacements, then the fetch: the bytes are
+    those of the replacements set when the replace ran."""
+    t = "mid4"
+    n = int(X.replace(t, 2, X.input_size(t, 2), 0, "r0").size)
+    ops = load(t, rkey="r0") + [scan(t, 2), pss("select"), pss("replace"), dict(op="set_reps", rkey="r1"), fetch("rp_fetch", first=0, n=n),
+                                dict(op="set_reps", rkey="redact"), fetch("rp_fetch", first=n // 3, n=n - n // 3), pss("replace"),
+                                fetch("rp_fetch", first=0, n=int(X.replace(t, 2, X.input_size(t, 2), 0, "redact").size))]
+    run(ops, want=[S.OK] * len(ops))
+
+
+@pytest.mark.parametrize("share", [True, False], ids=["shared-stream", "own-streams"])
+def test_two_slots_select_and_replace_interleaved(share):
+    t = "l2"
+    ops = [dict(op="set_stream", slot=1, share=share)] if share else []
+    ops += load(t, PFAC_FORCE_L2="1") + [scan(t, 0, slot=0), scan(t, 0, slot=1, no=(300_007 * 5) // 8), pss("select", slot=0, entry=0),
+                                         pss("select", slot=1, entry=X.M(t)), pss("replace", slot=0), fetch("sel_fetch", slot=1),
+                                         pss("replace", slot=1), fetch("sel_fetch", slot=0),
+                                         fetch("rp_fetch", slot=0, first=0, n=int(X.replace(t, 0, 300_007, 0, "r0").size)),
+                                         fetch("rp_fetch", slot=1, first=0, n=int(X.replace(t, 0, (300_007 * 5) // 8, X.M(t), "r0").size))]
+    if share:
+        ops += [dict(op="set_stream", slot=1, share=False), pss("select", slot=1, entry=1), fetch("sel_fetch", slot=1)]
+    run(ops, want=[S.OK] * len(ops))
+
+
+def test_reserve_that_replaces_a_buffer_leaves_no_finished_scan():
+    """pfac_slot_reserve growing the record heap or the input after a finished scan, and while one is pending: it waits
+    for the scan, and nothing reads the new, uninitialised buffer as if it held the last scan -- PFAC_E_STATE from
+    everything that needs one, exact results from the next scan.  Outputs of earlier passes stay fetchable."""
+    t = "mid4"
+    E = S.E_STATE
+    cnt = X.count(t, 2, X.input_size(t, 2))
+    grow = lambda which, n: dict(op="reserve_grow", slot=0, which=which, k=n)      # noqa: E731
+    ops = load(t) + [scan(t, 2), pss("select"), grow("records", 1), records(t, 2), fetch("checksum", base=0), fetch("text", base=0),
+                     fetch("packed"), pss("segment"), pss("select"), pss("replace"), dict(op="scan_finish", slot=0),
+                     scan(t, 2), records(t, 2), pss("select"), grow("input", 2), pss("replace"), fetch("sel_fetch"), records(t, 2, n=3),
+                     scan(t, 1), records(t, 1),
+                     dict(op="scan_start", slot=0, inp=2, no=X.input_size(t, 2), cap=cnt + cnt // 4 + 65536), grow("both", 3),
+                     dict(op="scan_finish", slot=0), records(t, 2, n=1), fetch("checksum", base=0),
+                     dict(op="scan_start", slot=0, inp=2, no=X.input_size(t, 2), cap=cnt + cnt // 4 + 65536), dict(op="scan_finish", slot=0),
+                     records(t, 2), grow("both", 4), records(t, 2, n=2)]
+    run(ops, want=[0] * 3 + [0, 0, 0] + [E] * 8 + [0, 0, 0, 0, E, 0, E, 0, 0, 0, 0, E, E, E, 0, 0, 0, 0, E])
+
+
+def test_scan_finish_keeps_the_copy_queued_after_scan_async():
+    """scan_async, h2d of the next chunk, scan_finish: the next chunk's host array is still referenced, or its copy has
+    left it -- and the scan after it sees the right bytes."""
+    t = "abc2"
+    first, nxt = X.input(t, 1), X.input(t, 0).copy()
+    with GpuMatcher(0, 1) as g:
+        g.load_table(X.table(t))
+        g.reserve(0, nxt.size, 1 << 20)
+        g.h2d(first.copy(), 0)
+        g.scan_async(first.size, slot=0)
+        ref = weakref.ref(nxt)
+        g.h2d(nxt, 0)
+        del nxt
+        n0, over = g.scan_finish(0)
+        gc.collect()
+        alive = ref() is not None
+        done = g.h2d_done(0)
+        assert alive or done, "scan_finish released a host array whose copy had not finished"
+        assert (n0, over) == (X.count(t, 1, first.size), False)
+        g.scan_async(first.size, slot=0)
+        n1, over = g.scan_finish(0)
+        rec = g.records_to_host(n1)
+        pos, ids, _ = X.scan(t, 0, first.size)
+    assert ref() is None, "sync released the array"
+    assert n1 == pos.size and not over
+    np.testing.assert_array_equal(rec["pos"].astype(np.int64), pos)
+    np.testing.assert_array_equal(X.table(t).idmap[rec["state"]], ids)
+
+
+def test_fill_then_partial_h2d_into_the_same_buffer():
+    """fill_random of a 1 GiB slot input, then 4 KiB of known bytes into its last tile: the fills return once the slot's
+    stream is idle, so the copy -- which is ordered after the slot's last SCAN only -- cannot be overtaken by the fill.
+    The tile is read back through a scan with no match and a replace without picks, which copies its input."""
+    t, n = "abc2", 1 << 30
+    rng = np.random.default_rng(5)
+    known = rng.integers(0, 256, 4096).astype(np.uint8)
+    known[known == ord("a")] = 0
+    with GpuMatcher(0, 1) as g:
+        g.load_table(X.table(t))
+        g.set_final_lengths(X.table(t).final_lengths())
+        g.set_replacements(X.reps(t, "r0"))
+        g.reserve(0, n, 4096)
+        g.fill_random(g.input_ptr(0), n, 0x1234)
+        g.h2d(known, 0, dst_offset=n - 4096)
+        g.sync(0)
+        off = n - 4096
+        g.scan_async(4096, 4096, d_input=g.input_ptr(0) + off, slot=0)
+        assert g.scan_finish(0) == (0, False)
+        assert g.select_leftmost_longest(0) == (0, 0)
+        assert g.replace_selection(d_input=g.input_ptr(0) + off) == 4096
+        np.testing.assert_array_equal(g.replacement_to_host(4096), known)
+        g.scan_async(4096, 4096, d_input=g.input_ptr(0) + off - 4096, slot=0)      # the tile before it still holds the fill
+        n_before = g.scan_finish(0)[0]
+        g.select_leftmost_longest(0)
+        m = g.replace_selection(d_input=g.input_ptr(0) + off - 4096)
+        want = splitmix64_bytes(n, 0x1234)[off - 4096:off]
+        assert n_before == int((want == ord("a")).sum())
+        if n_before == 0:
+            np.testing.assert_array_equal(g.replacement_to_host(m), want)
+
+
+def test_stream_change_between_a_selection_and_its_replace():
+    """A selection's writes are asynchronous on the slot's stream; set_stream then moves the slot to another stream, where
+    the replace reads them.  The change of stream waits for the old one (found by `tools/fuzz.py session`: without the
+    wait the replace now and then saw a half-written selection and refused it with PFAC_E_ARG)."""
+    t = "mid4"
+    n = X.input_size(t, 0)
+    ops = load(t) + [scan(t, 0, slot=1)]
+    for rnd in range(6):
+        entry = rnd % 3
+        ops += [pss("select", slot=1, entry=entry), dict(op="set_stream", slot=1, share=rnd % 2 == 0), pss("replace", slot=1),
+                fetch("rp_fetch", slot=1, first=0, n=int(X.replace(t, 0, n, entry, "r0").size))]
+    run(ops, want=[S.OK] * len(ops))

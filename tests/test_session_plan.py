@@ -1,0 +1,533 @@
+"""CPU side of the session tests (tests/session.py): the suite's plans are deterministic, well formed and together reach
+every operation, table, record width, status, slot and stream arrangement, and every (producer pass, other pass, late
+fetch) order; the executor and the model run every plan against CpuDevice, a stand-in for GpuMatcher that implements the
+contract of include/pfac.h in the most obvious way; and each of CpuDevice's switchable defects makes a plan fail at or
+after the first operation the defect touches -- the harness has teeth without a kernel being mutated."""
+import os
+
+import numpy as np
+import pytest
+
+import session as S
+from llref import greedy
+from orc import match_checksum
+from passfuzz import KNOBS, record_width
+from phfpfac_amd import GpuMatcher, PfacError
+from phfpfac_amd.table import RECORD_DTYPE
+from replref import rep_table, splice
+
+
+def _err(status, msg, **attrs):
+    e = PfacError(status, msg)
+    for k, v in attrs.items():
+        setattr(e, k, v)
+    return e
+
+
+class CpuBuf:
+    def __init__(self, n_bytes, src=None):
+        self.a = np.zeros(max(int(n_bytes), 16), dtype=np.uint8)
+        self.src = src
+
+    def put(self, arr):
+        raw = np.ascontiguousarray(arr).view(np.uint8).ravel()
+        self.a[:raw.size] = raw
+
+
+class _CpuSlot:
+    def __init__(self):
+        self.in_cap = self.rec_cap = 0
+        self.data = None
+        self.scan = None
+        self.seq = 0
+        self.doc = None
+        self.doc_gen = 0
+        self.sel = self.seg = self.rp = self.rpd = None
+        self.text = b""
+        self.prev_first = 0
+
+
+DEFECTS = ("stale_selection_survives_upload", "late_segment_returns_selection", "smaller_scan_returns_tail",
+           "overflowed_scan_hands_out_records", "stale_doc_first_of_empty_trailing_document", "slot1_exit_is_slot0s")
+
+
+class CpuDevice:
+    """GpuMatcher's surface on the CPU: every result recomputed from the oracle's records, outputs kept in dicts.  Works
+    in pattern ids (``states_are_ids``).  `defects`: names from DEFECTS to switch on."""
+    states_are_ids = True
+    device = 0
+
+    def __init__(self, defects=()):
+        self.x = S.expectations()
+        self.defects = set(defects)
+        self.tab = None
+        self.gen = 0
+        self.width = 4
+        self.flen = False
+        self.reps = None
+        self.slots = [_CpuSlot() for _ in range(S.N_SLOTS)]
+        self.hit = False
+
+    def _defect(self, name):
+        if name in self.defects:
+            self.hit = True
+            return True
+        return False
+
+    # -- buffers ------------------------------------------------------------
+    def alloc(self, n_bytes):
+        return CpuBuf(n_bytes)
+
+    def upload(self, arr):
+        return CpuBuf(16, src=arr)
+
+    def download(self, buf, dtype, count):
+        return buf.a[:count * np.dtype(dtype).itemsize].view(dtype).copy()
+
+    def close(self):
+        pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        pass
+
+    # -- tables -------------------------------------------------------------
+    def load_table(self, table):
+        self.tab = next(t for t in S.TABLES if self.x.table(t) is table)
+        knobs = {k: os.environ[k] for d in KNOBS for k in d if k in os.environ}
+        self.width = record_width(int(table.num_final), knobs)
+        self.gen += 1
+        self.flen, self.reps = False, None
+
+    def info(self):
+        return {"variant": "cpu", "staging_buffers": 0, "staging_records": 0}
+
+    def set_final_lengths(self, lengths):
+        if self.tab is None:
+            raise _err(S.E_STATE, "no table")
+        self.flen = True
+
+    def set_replacements(self, reps):
+        if self.tab is None:
+            raise _err(S.E_STATE, "no table")
+        self.reps = dict(reps)
+
+    def set_redaction(self, fill=b"*"):
+        if self.tab is None:
+            raise _err(S.E_STATE, "no table")
+        ll = self.x.tinfo(self.tab)["ll"]
+        self.reps = {k: fill * int(ll[k]) for k in range(1, ll.size)}
+
+    # -- plumbing -----------------------------------------------------------
+    def reserve(self, slot=0, input_bytes=0, record_capacity=0):
+        s = self.slots[slot]
+        if (input_bytes > s.in_cap and s.in_cap) or (record_capacity > s.rec_cap and s.rec_cap):
+            s.scan = None                                       # a buffer is replaced: no finished scan
+        if input_bytes > s.in_cap:
+            s.in_cap = (input_bytes + 4095) // 4096 * 4096 + 1280
+        s.rec_cap = max(s.rec_cap, record_capacity)
+
+    def h2d(self, host, slot=0, dst_offset=0):
+        self.slots[slot].data = host
+
+    def sync(self, slot=0):
+        pass
+
+    def stream_handle(self, slot=0):
+        return 1 + slot
+
+    def set_stream(self, slot, handle):
+        pass
+
+    # -- scans --------------------------------------------------------------
+    def scan_async(self, n_owned, n_avail=None, d_input=None, d_records=None, capacity=0, slot=0):
+        if self.tab is None:
+            raise _err(S.E_STATE, "scan before a table upload")
+        s = self.slots[slot]
+        data = d_input.src if d_input is not None else s.data
+        n_avail = n_owned if n_avail is None else n_avail
+        if n_avail == 0:
+            inp = next(i for i, d in enumerate(S.TABLES[self.tab]["inputs"]) if d[1] == 0)
+        else:
+            inp = next(i for i in range(len(S.TABLES[self.tab]["inputs"])) if self.x.input(self.tab, i) is data)
+        pos, ids, lens = self.x.scan(self.tab, inp, n_owned)
+        cap = capacity if d_records is not None else s.rec_cap
+        prev = s.scan
+        s.seq += 1
+        s.scan = dict(tab=self.tab, width=self.width, gen=self.gen, data=self.x.input(self.tab, inp), no=n_owned, pos=pos, ids=ids, lens=lens,
+                      over=pos.size > cap, pending=True, seq=s.seq, prev=(prev["pos"], prev["ids"]) if prev else None)
+
+    def scan_finish(self, slot=0, allow_overflow=False):
+        s = self.slots[slot]
+        if s.scan is None:
+            raise _err(S.E_STATE, "no scan")
+        s.scan["pending"] = False
+        if s.scan["over"] and not allow_overflow:
+            raise _err(S.E_OVERFLOW, "overflow")
+        return int(s.scan["pos"].size), s.scan["over"]
+
+    def capacity_hint(self, slot=0):
+        n = int(self.slots[slot].scan["pos"].size)
+        return n + n // 4 + 65536
+
+    scan_resident = GpuMatcher.scan_resident
+    scan_bytes = GpuMatcher.scan_bytes
+
+    def scan_format(self, slot=0):
+        sc = self.slots[slot].scan
+        if sc is None:
+            raise _err(S.E_STATE, "no scan yet")
+        return sc["width"], (sc["no"] + 4095) // 4096, int(sc["pos"].size)
+
+    def _finished(self, slot, overflow_status):
+        sc = self.slots[slot].scan
+        if sc is None or sc["pending"]:
+            raise _err(S.E_STATE, "needs a finished scan")
+        if sc["over"] and overflow_status:
+            raise _err(overflow_status, "the scan overflowed")
+        return sc
+
+    @staticmethod
+    def _rec(pos, ids):
+        out = np.empty(pos.size, dtype=RECORD_DTYPE)
+        out["pos"], out["state"] = pos, ids
+        return out
+
+    def records_to_host(self, n, slot=0, d_records=None, first=0):
+        if n == 0:
+            return np.empty(0, dtype=RECORD_DTYPE)
+        sc = self._finished(slot, 0)
+        if first + n > sc["pos"].size:
+            raise _err(S.E_ARG, "beyond the match count")
+        if sc["over"] and not self._defect("overflowed_scan_hands_out_records"):
+            raise _err(S.E_OVERFLOW, "the scan overflowed")
+        pos, ids = sc["pos"], sc["ids"]
+        if sc["prev"] is not None and sc["prev"][0].size > pos.size and self._defect("smaller_scan_returns_tail"):
+            pos, ids = sc["prev"][0][-pos.size:], sc["prev"][1][-pos.size:]
+        return self._rec(pos[first:first + n], ids[first:first + n])
+
+    def packed_to_host(self, slot=0, d_records=None):
+        rb, nt, used = self.scan_format(slot)
+        if rb == 8:
+            raise _err(S.E_STATE, "not compact")
+        sc = self.slots[slot].scan
+        pos, ids = sc["pos"], sc["ids"]
+        words = ((pos & 4095) | (ids << 12)).astype(np.uint16 if rb == 2 else np.uint32)
+        cnt = np.bincount(pos >> 12, minlength=nt).astype(np.uint64)
+        start = (np.cumsum(cnt) - cnt).astype(np.uint64)
+        return words, start | (cnt << np.uint64(40))
+
+    def checksum(self, n, base=0, slot=0, d_records=None):
+        if self.tab is None:
+            raise _err(S.E_STATE, "no table")
+        if n == 0:
+            return 0
+        sc = self._finished(slot, 0)
+        if sc["gen"] != self.gen:
+            raise _err(S.E_STATE, "earlier table")
+        if sc["over"]:
+            raise _err(S.E_OVERFLOW, "overflow")
+        return match_checksum(sc["pos"] + base, sc["ids"])
+
+    def emit_text_device(self, base=0, slot=0, d_records=None):
+        if self.tab is None:
+            raise _err(S.E_STATE, "no table")
+        sc = self._finished(slot, 0)
+        if sc["gen"] != self.gen:
+            raise _err(S.E_STATE, "earlier table")
+        if sc["over"]:
+            raise _err(S.E_OVERFLOW, "overflow")
+        self.slots[slot].text = "".join("At position %4d, match pattern %d\n" % (p + base, k)
+                                        for p, k in zip(sc["pos"].tolist(), sc["ids"].tolist())).encode()
+        return len(self.slots[slot].text)
+
+    def text_to_host(self, n_bytes, slot=0, first=0):
+        if first + n_bytes > len(self.slots[slot].text):
+            raise _err(S.E_ARG, "beyond the text")
+        return self.slots[slot].text[first:first + n_bytes]
+
+    # -- documents ----------------------------------------------------------
+    def set_doc_offsets(self, offsets, slot=0):
+        s = self.slots[slot]
+        s.doc = np.array(offsets, dtype=np.uint64)
+        s.doc_gen += 1
+
+    def _pass_scan(self, slot, overflow_status):
+        sc = self.slots[slot].scan
+        if sc is None or sc["pending"] or not self.flen or sc["gen"] != self.gen:
+            raise _err(S.E_STATE, "needs a finished scan of the current table and its lengths")
+        if sc["over"]:
+            raise _err(overflow_status, "the scan overflowed")
+        return sc
+
+    def _docs(self, slot, sc):
+        s = self.slots[slot]
+        if s.doc is None:
+            raise _err(S.E_STATE, "no document offsets")
+        if not S.offsets_ok(s.doc, sc["no"]):
+            raise _err(S.E_ARG, "bad offsets")
+        off = s.doc.astype(np.int64)
+        doc = np.searchsorted(off, sc["pos"], side="right") - 1
+        keep = sc["pos"] + sc["lens"] <= off[doc + 1]
+        return off, doc[keep], sc["pos"][keep], sc["ids"][keep], sc["lens"][keep]
+
+    def _first(self, s, first):
+        if first.size >= 3 and first.size and self.slots[s].doc[-1] == self.slots[s].doc[-2] and self._defect("stale_doc_first_of_empty_trailing_document"):
+            first = first.copy()
+            first[-2] = self.slots[s].prev_first
+        self.slots[s].prev_first = int(first[-1]) + 1
+        return first
+
+    def _deliver(self, what, n, rec, first, d_out, out_cap, d_first, attr):
+        if d_out is not None and n > out_cap:
+            raise _err(S.E_OVERFLOW, "out_cap too small", **{attr: n})
+        if d_out is not None:
+            d_out.put(rec)
+            if d_first is not None:
+                d_first.put(first)
+        return dict(rec=rec, first=first, own=d_out is None)
+
+    def segment_records(self, n_docs, d_doc_offsets=None, d_out=None, out_cap=0, d_doc_first=None, slot=0, d_records=None):
+        s = self.slots[slot]
+        s.seg = None
+        sc = self._pass_scan(slot, S.E_OVERFLOW)
+        off, doc, pos, ids, _ = self._docs(slot, sc)
+        first = self._first(slot, np.searchsorted(doc, np.arange(off.size), side="left").astype(np.uint64))
+        s.seg = self._deliver("seg", pos.size, self._rec(pos - off[doc], ids), first, d_out, out_cap, d_doc_first, "n_kept")
+        s.seg["after_sel"] = False
+        return int(pos.size)
+
+    def segment_to_host(self, n_kept, n_docs, slot=0):
+        s = self.slots[slot]
+        if s.seg is None or not s.seg["own"]:
+            raise _err(S.E_STATE, "no slot-owned segment result")
+        if s.seg["after_sel"] and s.sel is not None and self._defect("late_segment_returns_selection"):
+            return s.seg["first"], s.sel["rec"]
+        return s.seg["first"], s.seg["rec"]
+
+    # -- selection ----------------------------------------------------------
+    def select_leftmost_longest(self, entry=0, d_out=None, out_cap=0, slot=0, d_records=None):
+        s = self.slots[slot]
+        s.sel = None
+        sc = self._pass_scan(slot, S.E_STATE)
+        if entry > self.x.M(sc["tab"]):
+            raise _err(S.E_ARG, "entry > max_pat_len")
+        idx, ex = greedy(sc["pos"], sc["lens"], entry, sc["no"])
+        s.sel = self._deliver("sel", idx.size, self._rec(sc["pos"][idx], sc["ids"][idx]), None, d_out, out_cap, None, "n_selected")
+        s.sel.update(kind="whole", seq=sc["seq"], gen=sc["gen"], entry=entry, exit=int(ex), lens=sc["lens"][idx])
+        if s.seg is not None:
+            s.seg["after_sel"] = True
+        if slot == 1 and self.slots[0].sel is not None and self._defect("slot1_exit_is_slot0s"):
+            return int(idx.size), self.slots[0].sel["exit"]
+        return int(idx.size), int(ex)
+
+    def select_leftmost_longest_documents(self, n_docs, d_doc_offsets=None, d_out=None, out_cap=0, d_doc_first=None, slot=0, d_records=None):
+        s = self.slots[slot]
+        s.sel = None
+        sc = self._pass_scan(slot, S.E_STATE)
+        off, doc, pos, ids, lens = self._docs(slot, sc)
+        picks = []
+        bounds = np.searchsorted(doc, np.arange(off.size), side="left")
+        for d in range(off.size - 1):
+            a, b = int(bounds[d]), int(bounds[d + 1])
+            if b > a:
+                idx, _ = greedy(pos[a:b], lens[a:b], int(off[d]), int(off[d + 1]))
+                picks.append(idx + a)
+        idx = np.concatenate(picks) if picks else np.empty(0, np.int64)
+        first = self._first(slot, np.searchsorted(doc[idx], np.arange(off.size), side="left").astype(np.uint64))
+        s.sel = self._deliver("sel", idx.size, self._rec(pos[idx], ids[idx]), first, d_out, out_cap, d_doc_first, "n_selected")
+        s.sel.update(kind="docs", seq=sc["seq"], gen=sc["gen"], entry=0, exit=0, lens=lens[idx], doc_gen=s.doc_gen, off=off)
+        if s.seg is not None:
+            s.seg["after_sel"] = True
+        return int(idx.size)
+
+    def selection_to_host(self, n_selected, slot=0):
+        s = self.slots[slot]
+        if s.sel is None or not s.sel["own"]:
+            raise _err(S.E_STATE, "no slot-owned selection")
+        return s.sel["rec"]
+
+    def doc_selection_to_host(self, n_selected, n_docs, slot=0):
+        s = self.slots[slot]
+        if s.sel is None or s.sel["kind"] != "docs" or not s.sel["own"]:
+            raise _err(S.E_STATE, "no slot-owned per-document selection")
+        return s.sel["first"], s.sel["rec"]
+
+    # -- replace ------------------------------------------------------------
+    def _replace(self, slot, docs, d_out, out_cap, d_out_offsets):
+        s = self.slots[slot]
+        s.rp = s.rpd = None
+        sc, sel = s.scan, s.sel
+        if sc is None or sel is None or sel["seq"] != sc["seq"] or (docs and sel["kind"] != "docs"):
+            raise _err(S.E_STATE, "no selection since the slot's last scan")
+        stale = sc["gen"] != self.gen
+        if stale and not self._defect("stale_selection_survives_upload"):
+            raise _err(S.E_STATE, "earlier table")
+        if self.reps is None or not self.flen:
+            raise _err(S.E_STATE, "no replacements or lengths")
+        if docs and sel["doc_gen"] != s.doc_gen:
+            raise _err(S.E_STATE, "the offsets changed since the selection")
+        table = rep_table(self.reps if not stale else {k: b"?" for k in range(1, 4096)})
+        pos, ids, lens = sel["rec"]["pos"].astype(np.int64), sel["rec"]["state"].astype(np.int64), sel["lens"]
+        if sel["kind"] == "whole":
+            out = splice(sc["data"], sel["entry"], sc["no"], pos, lens, ids, table)
+            out_off = None
+        else:
+            off, first = sel["off"], sel["first"].astype(np.int64)
+            parts = [splice(sc["data"][int(off[d]):int(off[d + 1])], 0, int(off[d + 1] - off[d]), pos[first[d]:first[d + 1]] - off[d],
+                            lens[first[d]:first[d + 1]], ids[first[d]:first[d + 1]], table) for d in range(off.size - 1)]
+            out = np.concatenate(parts) if parts else np.empty(0, np.uint8)
+            out_off = np.concatenate([[0], np.cumsum([p.size for p in parts])]).astype(np.uint64)
+        if d_out is not None and out.size > out_cap:
+            raise _err(S.E_OVERFLOW, "out_cap too small", out_bytes=int(out.size))
+        if d_out is not None:
+            d_out.put(out)
+        s.rp = dict(out=out, own=d_out is None)
+        if docs:
+            if d_out_offsets is not None:
+                d_out_offsets.put(out_off)
+            s.rpd = dict(off=out_off, own=d_out_offsets is None)
+        return int(out.size)
+
+    def replace_selection(self, d_input=None, d_out=None, out_cap=0, slot=0, d_sel=None):
+        return self._replace(slot, False, d_out, out_cap, None)
+
+    def replace_selection_documents(self, d_input=None, d_out=None, out_cap=0, d_out_offsets=None, slot=0, d_sel=None, d_doc_offsets=None,
+                                    d_doc_first=None):
+        return self._replace(slot, True, d_out, out_cap, d_out_offsets)
+
+    def replacement_to_host(self, n, slot=0, first=0):
+        s = self.slots[slot]
+        if s.rp is None or not s.rp["own"]:
+            raise _err(S.E_STATE, "no slot-owned replace output")
+        if first + n > s.rp["out"].size:
+            raise _err(S.E_ARG, "beyond the output")
+        return s.rp["out"][first:first + n]
+
+    def replacement_doc_offsets_to_host(self, n_docs, slot=0):
+        s = self.slots[slot]
+        if s.rpd is None or not s.rpd["own"]:
+            raise _err(S.E_STATE, "no slot-owned output offsets")
+        return s.rpd["off"]
+
+
+# ---------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def plans():
+    return {seed: S.plan(seed) for seed in S.SEEDS}
+
+
+def test_plans_are_deterministic_and_well_formed(plans):
+    for seed in S.SEEDS[:4]:
+        assert S.plan(seed) == plans[seed]
+        assert S.shrink(seed, 17) == plans[seed][:17]
+    assert plans[0] != plans[1]
+    for seed, ops in plans.items():
+        assert len(ops) == S.PLAN_OPS
+        m = S.Model()
+        for k, op in enumerate(ops):
+            assert hasattr(S.Executor, "do_" + op["op"]), f"seed {seed} op {k}: the executor cannot perform {S.fmt(op)}"
+            st = m.apply(op).status
+            assert st in (S.OK, S.E_ARG, S.E_STATE, S.E_OVERFLOW), f"seed {seed} op {k}: the contract does not decide {S.fmt(op)}"
+
+
+def test_suite_plans_reach_everything(plans):
+    x = S.expectations()
+    kinds, tables, widths, statuses, slots, streams, pairs, errs, inputs = set(), set(), set(), set(), set(), set(), set(), 0, set()
+    pending_other = False
+    total = 0
+    for seed, ops in plans.items():
+        m = S.Model()
+        made = {}                                               # (slot, pass) -> (index of its last OK slot-owned run, passes since)
+        for k, op in enumerate(ops):
+            st = m.apply(op).status
+            total += 1
+            errs += st != S.OK
+            kinds.add(op["op"])
+            statuses.add(st)
+            slots.add(op.get("slot"))
+            for s in m.slots:
+                streams.add(s.shared)
+                if s.scan is not None and op["op"].startswith("scan") and st == S.OK:
+                    tables.add(s.scan["tab"])
+                    widths.add(x.width(s.scan["tab"], s.scan["knob"]))
+                    inputs.add((s.scan["tab"], s.scan["inp"]))
+            if op["op"] == "scan_bytes" and st == S.OK and (m.slots[1 - op["slot"]].scan or {}).get("pending"):
+                pending_other = True
+            if op["op"] in S.PASSES:
+                for key in made:
+                    if key[0] == op["slot"] and key[1] != op["op"]:
+                        made[key].add(op["op"])
+                if st == S.OK and op["own"]:
+                    made[(op["slot"], op["op"])] = set()
+                else:
+                    made.pop((op["slot"], op["op"]), None)
+            if op["op"] in S.PRODUCER_OF and st == S.OK:
+                prod = S.PRODUCER_OF[op["op"]]
+                for other in made.get((op["slot"], prod), ()):
+                    pairs.add((prod, other))
+    assert kinds == set(S.KINDS), set(S.KINDS) - kinds
+    assert tables == set(S.TABLES) and widths == {2, 4, 8}
+    assert inputs == {(t, i) for t in S.TABLES for i in range(len(S.TABLES[t]["inputs"]))}, "an input of the pool is never scanned"
+    assert statuses == {S.OK, S.E_ARG, S.E_STATE, S.E_OVERFLOW}
+    assert slots >= {0, 1} and streams == {True, False} and pending_other
+    assert 0.08 < errs / total < 0.2, f"{errs} of {total} operations are illegal: about one in eight was the plan"
+    # the two selections share a buffer, and so do the two replaces: the later one discards the earlier one's result
+    shared = {("select", "select_docs"), ("select_docs", "select"), ("replace", "replace_docs"), ("replace_docs", "replace")}
+    want = {(a, b) for a in S.PASSES for b in S.PASSES if a != b} - shared
+    assert pairs >= want, sorted(want - pairs)
+    sizes = {d[1] for t in S.TABLES.values() for d in t["inputs"]}
+    assert sizes >= {0, 1, 17, 4095, 4097, S.GROUP - 1, S.GROUP + 1, 300_007, 2_000_003}
+
+
+@pytest.mark.parametrize("seed", S.SEEDS)
+def test_plan_passes_on_the_cpu_device(seed, plans):
+    stats = S.run(CpuDevice(), plans[seed], S.Model(), seed=seed)
+    assert stats["ops"] == S.PLAN_OPS and stats["errors"] > 0
+
+
+def first_touch(seed, ops, defect):
+    """(index of the first operation the defect changes, index of the operation the executor fails at or None)."""
+    dev = CpuDevice([defect])
+    ex = S.Executor(dev, S.Model())
+    touched = None
+    for k, op in enumerate(ops):
+        try:
+            ex.step(op)
+        except AssertionError:
+            return (k if touched is None and dev.hit else touched), k
+        if dev.hit and touched is None:
+            touched = k
+    return touched, None
+
+
+@pytest.mark.parametrize("defect", DEFECTS)
+def test_every_defect_is_caught(defect, plans):
+    caught = []
+    for seed, ops in plans.items():
+        touched, failed = first_touch(seed, ops, defect)
+        assert failed is None or (touched is not None and failed >= touched), f"seed {seed}: failed at {failed} before the defect acted ({touched})"
+        if failed is not None:
+            with pytest.raises(AssertionError) as e:
+                S.run(CpuDevice([defect]), ops, S.Model(), seed=seed)
+            assert f"session seed {seed}, operation {failed} " in str(e.value) and e.value.op_index == failed
+            caught.append((seed, touched, failed))
+            if len(caught) == 2:                                # (two plans are proof enough; every plan costs a second)
+                break
+    assert caught, f"no suite plan notices {defect}"
+    print(f"{defect}: caught by plans (seed, first touched, failed at) {caught}")
+
+
+def test_shrink_keeps_a_failure(plans):
+    """A failing history cut just past the failing operation still fails there; cut before it, it passes."""
+    defect = "overflowed_scan_hands_out_records"
+    for seed, ops in plans.items():
+        touched, failed = first_touch(seed, ops, defect)
+        if failed is not None:
+            with pytest.raises(AssertionError):
+                S.run(CpuDevice([defect]), S.shrink(seed, failed + 1), S.Model(), seed=seed)
+            S.run(CpuDevice([defect]), S.shrink(seed, failed), S.Model(), seed=seed)
+            return
+    raise AssertionError("no plan to shrink")

@@ -1,7 +1,9 @@
 """GPU differential fuzz: random pattern sets x random inputs, random kernel knobs; every record of the scan, the
 documents pass, the leftmost-longest selection and the find-and-replace output compared with the CPU references.
 The cases and checks are tests/passfuzz.py's (the suite runs a fixed list of its seeds).
-usage: fuzz.py [seconds] [seed]"""
+usage: fuzz.py [seconds] [seed]
+       fuzz.py session [seconds] [seed]     random SESSIONS instead: one context per plan driven through about 60 calls
+                                            in random order (tests/session.py: the model, plans and executor of the suite)"""
 import os, sys, tempfile, time
 os.environ.setdefault("PFAC_ENABLE_KNOBS", "1")     # tuning / test knobs of libpfac_hip.so are opt-in
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -11,6 +13,26 @@ from phfpfac_amd import GpuMatcher, PfacTable
 from orc import Oracle
 from passfuzz import KNOB_NAMES, KNOBS, Case, knob_label, run_case
 
+if len(sys.argv) > 1 and sys.argv[1] == "session":
+    import session as S
+    seconds = float(sys.argv[2]) if len(sys.argv) > 2 else 60.0
+    seed = int(sys.argv[3]) if len(sys.argv) > 3 else 1
+    t0 = t_last = time.time(); plans = 0; tot = {"ops": 0, "errors": 0, "compared": 0}; widths = set(); staging = set()
+    while time.time() - t0 < seconds:
+        plan_seed = (seed << 20) + len(S.SEEDS) + plans        # (beyond the suite's seeds)
+        with GpuMatcher(0, S.N_SLOTS) as g:
+            try:
+                st = S.run(g, S.plan(plan_seed), S.Model(), seed=plan_seed)
+            except AssertionError as e:
+                raise SystemExit(f"MISMATCH in plan {plans}: {e}")
+        for k in tot: tot[k] += st[k]
+        widths |= st["widths"]; staging |= st["staging"]; plans += 1
+        if time.time() - t_last > 30:
+            t_last = time.time(); print(f"  ... {plans} plans, {tot['ops']} operations, {tot['compared']} records and bytes compared, {t_last - t0:.0f} s", flush=True)
+    print(f"session fuzz ok: {plans} plans in {time.time() - t0:.0f} s (seed {seed}), {tot['ops']} operations of which {tot['errors']} "
+          f"documented errors, {tot['compared']} records and bytes compared")
+    print(f"record widths {sorted(widths)}, staging layouts (buffers, records) {sorted(staging)}")
+    raise SystemExit(0)
 seconds = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 rng = np.random.default_rng(seed)
