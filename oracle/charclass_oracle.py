@@ -133,12 +133,13 @@ def parse(image: bytes):
     return pats
 
 
-def match(image: bytes, data: np.ndarray):
-    """-> (pos int64[], id int32[]) ordered by (position, pattern length, pattern id)."""
+def match(image: bytes, data: np.ndarray, parsed=None):
+    """-> (pos int64[], id int32[]) ordered by (position, pattern length, pattern id).  `parsed`: parse(image), for a
+    caller that matches one image against many inputs."""
     data = np.ascontiguousarray(data, dtype=np.uint8)
     n = data.size
     pos_l, id_l, len_l = [], [], []
-    for pid, elems in enumerate(parse(image), start=1):
+    for pid, elems in enumerate(parse(image) if parsed is None else parsed, start=1):
         L = len(elems)
         if L > n:
             continue

@@ -124,8 +124,9 @@ class Case:
 class Expect:
     """What the CPU says for a case (never reads the device)."""
 
-    def __init__(self, case, path, matcher=None):
-        """`matcher`: an object with ``Oracle.scan_spec``'s interface (tests/bigref.py); None = the CPU oracle."""
+    def __init__(self, case, path, matcher=None, lengths=None):
+        """`matcher`: an object with ``Oracle.scan_spec``'s interface (tests/bigref.py); None = the CPU oracle.
+        `lengths`: int64[n_lines + 1], [id] = bytes of pattern id; None = the lines of the plain pattern file `path`."""
         c = case
         self.entry, self.n_owned = c.entry, c.n_owned
         o = Oracle(path, 1, 1) if matcher is None else matcher
@@ -135,7 +136,7 @@ class Expect:
         self.docs = oracle_per_doc(o, c.data, c.off)
         if matcher is None:
             o.close()
-        self.ll = line_lengths(path)
+        self.ll = line_lengths(path) if lengths is None else np.asarray(lengths, dtype=np.int64)
         self.lens = self.ll[self.ids]
         if self.pos.size <= GREEDY_MAX:
             sel, self.exit = greedy(self.pos, self.lens, c.entry, c.n_owned)
@@ -167,10 +168,12 @@ def run_case(g_factory, case, tmp_dir, matcher=None):
         raise AssertionError(f"{where}: {e}") from e
 
 
-def _run(g_factory, c, path, matcher=None):
-    table = PfacTable.from_file(path, c.width)
+def _run(g_factory, c, path, matcher=None, table_factory=None, lengths=None):
+    """`table_factory(path, width)` -> the PfacTable of the case (None = a plain pattern file) and `lengths` (see
+    Expect) let the cases of tests/classfuzz.py, whose files are no plain lines, through the same checks."""
+    table = PfacTable.from_file(path, c.width) if table_factory is None else table_factory(path, c.width)
     assert table.max_pat_len == c.M
-    want = Expect(c, path, matcher)
+    want = Expect(c, path, matcher, lengths)
     compared = 0
     with g_factory() as g:
         g.load_table(table)
@@ -196,7 +199,7 @@ def _run(g_factory, c, path, matcher=None):
         rwant = splice(c.data, c.entry, c.n_owned, spos, want.ll[sids], sids, want.table)
         assert out.size == rwant.size, f"replace: {out.size} bytes, want {rwant.size}"
         assert np.array_equal(out, rwant), f"replace: first difference at byte {int(np.argmax(out != rwant))}"
-        if len(c.lines) <= 20 and c.n <= 300_007:
+        if table_factory is None and len(c.lines) <= 20 and c.n <= 300_007:      # (plain literal lines only)
             r2, ex2 = re_replace(c.lines, c.reps, c.data, c.entry, c.n_owned)
             assert np.array_equal(out, r2) and ex2 == ex, "replace: differs from the regular-expression reference"
         # documents of the same scan

@@ -14,13 +14,14 @@ Three parts, none of which needs a GPU to import:
 
 The device under test hands out final STATES; they are mapped to pattern ids with the idmap of the table the scan ran
 with (a stand-in that already works in ids says so with ``states_are_ids``)."""
+import atexit
 import copy
-import importlib.util
 import os
 import tempfile
 
 import numpy as np
 
+from classfuzz import ClassMatcher as _ClassMatcher
 from docref import oracle_per_doc, random_offsets
 from docreplref import per_doc
 from llref import greedy
@@ -39,14 +40,11 @@ IN_STEP, REC_STEP = 8 << 20, 4 << 20    # reserve_grow number k asks for k * IN_
                                         # anything a plan's scans reserve (inputs <= 2 000 003 bytes, heaps below 4 Mi records)
 REC = np.dtype([("pos", np.uint32), ("state", np.uint32)])
 
-_REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_spec = importlib.util.spec_from_file_location("charclass_oracle", os.path.join(_REPO, "oracle", "charclass_oracle.py"))
-cco = importlib.util.module_from_spec(_spec)
-_spec.loader.exec_module(cco)
-
 CCLASS = (b"[a-c]x\n" b"ax\n" b"[^a-z0-9 ]\n" b"q[0-9][0-9]\n" b"[a-c]\n" b"\\x41[\\x42-\\x44]\\n\n" b"[-a]z\n" b"ax[xy]\n"
           b"[a-c]x\n")
 CCLASS_ALPHABET = b"abcxyzq0123456789 AB\nCD-Z!"
+CCNEG = b"[^a]\n" b"ab[^c]\n" b"[^b]\n" b"[a-c][\\x00-\\xff]y\n" b"a\\n[^\\n]\n"      # one-byte negated classes: a record or two per byte
+ESCNL = b"\\n\n" b"a\\nb\n" b"\\nx\n" b"x\\n\n" b"\\x00\\n\\x00\n" b"\\x61\\x0ab\n" b"q\\012\n" b"\\n\\n\n"   # newline as first, middle, last byte; a duplicate
 
 
 def _k(**knobs):
@@ -56,7 +54,8 @@ def _k(**knobs):
 # name -> how the table is made, which entries of passfuzz.KNOBS it may be installed under, and its inputs (name, bytes,
 # style).  Together: 2-, 4- and 8-byte records, tables in LDS and through L2, dense mode's second form, a character-class
 # table, duplicate lines; every size of passfuzz.Case; one dense and one matchless input of >= 64 tiles for a table with
-# no knob pinned, so the staging mode can flip.
+# no knob pinned, so the staging mode can flip; a class table whose one-byte negated classes give a record or two per byte
+# and an escaped table with newline edges, both in LDS, through L2 and in dense mode.
 TABLES = {
     "abc2": dict(lines=[b"a", b"ab", b"abc"], knobs=[_k()],
                  inputs=[("dense", 300_007, "abc:0.3"), ("none", 300_007, "abc:0"), ("thin", GROUP + 1, "abc:0.02"), ("s17", 17, "abc:0.3")]),
@@ -76,6 +75,10 @@ TABLES = {
                    inputs=[("g1", GROUP + 1, "plant"), ("t4095", 4095, "plant"), ("empty", 0, "plant")]),
     "cclass": dict(cclass=CCLASS, knobs=[_k(), _k(PFAC_REC_BYTES="4")],
                    inputs=[("gm1", GROUP - 1, "cc"), ("t4097", 4097, "cc"), ("one", 1, "cc")]),
+    "negcc": dict(cclass=CCNEG, knobs=[_k(), _k(PFAC_FORCE_L2="1"), _k(PFAC_FORCE_L2="1", PFAC_DENSE="1"), _k(PFAC_DENSE="1")],
+                  inputs=[("t4095", 4095, "cc"), ("m70", 70_001, "cc")]),
+    "nlesc": dict(escaped=ESCNL, knobs=[_k(), _k(PFAC_FORCE_L2="1"), _k(PFAC_FORCE_L2="1", PFAC_DENSE="1"), _k(PFAC_DENSE="1")],
+                  inputs=[("g1", GROUP + 1, "cc0"), ("s17", 17, "cc0")]),
     "dups": dict(gen=(105, 3, 9, 4, 3), knobs=[_k(), _k(PFAC_DENSE="1")],
                  inputs=[("m300", 300_007, "plant"), ("t4095", 4095, "plant"), ("empty", 0, "plant")]),
 }
@@ -98,23 +101,6 @@ def _gen_lines(seed, alpha, npat, maxlen, dups):
     return lines, symbols
 
 
-class _ClassMatcher:
-    """Oracle.scan_spec's interface over the brute-force character-class matcher: one record per (position, length),
-    carrying the lowest pattern id that ends there -- idmap[state] of the one DFA state reached."""
-
-    def __init__(self, image):
-        self.image = image
-        self.lens = np.array([0] + [len(p) for p in cco.parse(image)], dtype=np.int64)
-
-    def scan_spec(self, data, n=None):
-        pos, ids = cco.match(self.image, np.asarray(data, dtype=np.uint8))
-        if pos.size == 0:
-            return pos, ids
-        ln = self.lens[ids]
-        first = np.append(True, (pos[1:] != pos[:-1]) | (ln[1:] != ln[:-1]))     # (sorted by position, length, id)
-        return pos[first], ids[first]
-
-
 class Expectations:
     """What the CPU says, computed once per key."""
 
@@ -133,6 +119,12 @@ class Expectations:
         if "cclass" in d:
             m = _ClassMatcher(d["cclass"])
             return dict(table=PfacTable.from_charclass(d["cclass"], 256), matcher=m, ll=m.lens, symbols=None, lines=None)
+        if "escaped" in d:                                      # (lengths from the parsed lines; the matcher is the CPU oracle's escape-aware reader)
+            path = os.path.join(self.dir, t + ".pat")
+            with open(path, "wb") as f:
+                f.write(d["escaped"])
+            return dict(table=PfacTable.from_file(path, 256, escapes=True), matcher=Oracle(path, 1, 1, escapes=True),
+                        ll=_ClassMatcher(d["escaped"], "last").lens, symbols=None, lines=None)
         lines, symbols = (d["lines"], np.frombuffer(b"abc", dtype=np.uint8)) if "lines" in d else _gen_lines(*d["gen"])
         path = os.path.join(self.dir, t + ".pat")
         with open(path, "wb") as f:
@@ -142,6 +134,13 @@ class Expectations:
 
     def tinfo(self, t):
         return self._memo(("table", t), lambda: self._table(t))
+
+    def close(self):
+        """Frees the CPU oracles of the tables made so far (they serve every later expectation, so not before)."""
+        for key in [k for k in self._c if k[0] == "table"]:
+            m = self._c.pop(key)["matcher"]
+            if hasattr(m, "close"):
+                m.close()
 
     def table(self, t):
         return self.tinfo(t)["table"]
@@ -160,8 +159,8 @@ class Expectations:
             d = float(style[4:])
             u = rng.random(n)
             return np.where(u < d, ord("a"), np.where(u < d + 0.3, ord("b"), ord("c"))).astype(np.uint8)
-        if style == "cc":
-            alphabet = np.frombuffer(CCLASS_ALPHABET, dtype=np.uint8)
+        if style in ("cc", "cc0"):                              # (cc0: with byte 0, which the escaped table's lines hold)
+            alphabet = np.frombuffer(CCLASS_ALPHABET + (b"\x00\x00\x00" if style == "cc0" else b""), dtype=np.uint8)
             return alphabet[rng.integers(0, alphabet.size, n)]
         info = self.tinfo(t)
         sym = info["symbols"]
@@ -271,6 +270,7 @@ def expectations():
     global _EXP
     if _EXP is None:
         _EXP = Expectations()
+        atexit.register(_EXP.close)
     return _EXP
 
 

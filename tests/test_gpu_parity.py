@@ -975,9 +975,11 @@ def test_malformed_table_image_is_refused_at_upload(resolve):
 @pytest.mark.parametrize("n_first,n_second", [(120, 40), (30, 256), (100, 256), (255, 3), (256, 5)])
 def test_dense_depth1_rows_by_column(n_first, n_second, force_l2, tmp_path, monkeypatch):
     """The dense rows of the depth-1 states sit in LDS with only the columns of bytes that are some pattern's second
-    byte (+ a "no edge" column): many first bytes x few second bytes (120 x 40), every byte a second byte (no spare
-    column: 30 x 256), too much for LDS (100 x 256: the walk hashes its second byte), 255 depth-1 states, and one too
-    many for a row index (256) -- tables in LDS and through L2, records == oracle."""
+    byte (+ a "no edge" column): many first bytes x few second bytes (120 x 40), every byte a literal file can have as a
+    second byte (30 x 255: a row stride of 256 WITH the spare column), too much for LDS (100 x 255: the walk hashes its
+    second byte), 254 and 255 depth-1 states (the most a literal file can have: dense rows are still allowed) -- tables
+    in LDS and through L2, records == oracle.  A literal file cannot hold byte 10, so 256 columns without a spare and a
+    root fan-out of 256 are test_dense_depth1_rows_by_column_escaped's."""
     if force_l2:
         monkeypatch.setenv("PFAC_FORCE_L2", "1")
     rng = np.random.default_rng(n_first * 1000 + n_second)
@@ -1002,6 +1004,52 @@ def test_dense_depth1_rows_by_column(n_first, n_second, force_l2, tmp_path, monk
         data[at:at + len(pt)] = np.frombuffer(pt, dtype=np.uint8)
     rec = gpu_records(table, data)
     pos, ids = oracle_pairs(str(pf), data)
+    assert pos.size > 3000
+    assert_same(table, rec, pos, ids)
+
+
+@pytest.mark.parametrize("force_l2", [False, True])
+@pytest.mark.parametrize("n_first,n_second,rows", [(30, 256, "30 x 256"), (100, 256, "0 x 0"), (256, 5, "0 x 0")])
+def test_dense_depth1_rows_by_column_escaped(n_first, n_second, rows, force_l2, tmp_path, monkeypatch, capfd):
+    """The same through an escaped file, where byte 10 is a pattern byte like any other: every byte a second byte (256
+    columns, NO spare column: 30 x 256), too much for LDS (100 x 256), and one root edge too many for a row index (fan
+    256: no dense rows).  The shape is asserted on the host and in the device's configuration line before the scan;
+    records == the oracle's escape-aware reader."""
+    from classfuzz import shape
+    if force_l2:
+        monkeypatch.setenv("PFAC_FORCE_L2", "1")
+    monkeypatch.setenv("PFAC_VERBOSE", "1")
+    rng = np.random.default_rng(n_first * 1000 + n_second + 7)
+    firsts = rng.permutation(256)[:n_first].astype(np.uint8)
+    if n_first < 256 and 10 not in firsts:
+        firsts[0] = 10
+    seconds = rng.permutation(256)[:n_second].astype(np.uint8)
+    pats = set()
+    for f in firsts:
+        for sb in rng.choice(seconds, size=min(6, len(seconds)), replace=False):
+            tail = bytes(int(x) for x in rng.choice(seconds, size=int(rng.integers(0, 4))))
+            pats.add(bytes([int(f), int(sb)]) + tail)
+    for sb in seconds:
+        pats.add(bytes([int(firsts[int(rng.integers(0, len(firsts)))]), int(sb)]))
+    plist = sorted(pats)
+    pf = tmp_path / "p"
+    pf.write_bytes(b"".join(b"".join(b"\\x%02x" % b for b in p) + b"\n" for p in plist))
+    table = PfacTable.from_file(str(pf), 256, escapes=True)
+    fan, _, cols, _ = shape(table)
+    assert (fan, cols) == (n_first, n_second)
+    alphabet = np.union1d(firsts, seconds)
+    data = alphabet[rng.integers(0, alphabet.size, 150_001)].astype(np.uint8)
+    for at in rng.integers(0, data.size - 8, 4000):
+        pt = plist[int(rng.integers(0, len(plist)))]
+        data[at:at + len(pt)] = np.frombuffer(pt, dtype=np.uint8)
+    with GpuMatcher(0, 1) as g:
+        capfd.readouterr()
+        g.load_table(table)
+        assert f"dense rows {rows}," in capfd.readouterr().err
+        rec = g.scan_bytes(data)
+    o = Oracle(str(pf), 1, 1, escapes=True)
+    pos, ids = o.scan_spec(data)
+    o.close()
     assert pos.size > 3000
     assert_same(table, rec, pos, ids)
 

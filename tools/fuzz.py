@@ -3,7 +3,9 @@ documents pass, the leftmost-longest selection and the find-and-replace output c
 The cases and checks are tests/passfuzz.py's (the suite runs a fixed list of its seeds).
 usage: fuzz.py [seconds] [seed]
        fuzz.py session [seconds] [seed]     random SESSIONS instead: one context per plan driven through about 60 calls
-                                            in random order (tests/session.py: the model, plans and executor of the suite)"""
+                                            in random order (tests/session.py: the model, plans and executor of the suite)
+       fuzz.py class [seconds] [seed]       character-class and escaped-file cases instead (tests/classfuzz.py), against the
+                                            brute-force matcher oracle/charclass_oracle.py and the escape-aware CPU oracle"""
 import os, sys, tempfile, time
 os.environ.setdefault("PFAC_ENABLE_KNOBS", "1")     # tuning / test knobs of libpfac_hip.so are opt-in
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -32,6 +34,32 @@ if len(sys.argv) > 1 and sys.argv[1] == "session":
     print(f"session fuzz ok: {plans} plans in {time.time() - t0:.0f} s (seed {seed}), {tot['ops']} operations of which {tot['errors']} "
           f"documented errors, {tot['compared']} records and bytes compared")
     print(f"record widths {sorted(widths)}, staging layouts (buffers, records) {sorted(staging)}")
+    raise SystemExit(0)
+if len(sys.argv) > 1 and sys.argv[1] == "class":
+    import classfuzz as F
+    seconds = float(sys.argv[2]) if len(sys.argv) > 2 else 60.0
+    seed = int(sys.argv[3]) if len(sys.argv) > 3 else 1
+    rng = np.random.default_rng(seed)
+    tmp = tempfile.mkdtemp()
+    t0 = t_last = time.time(); cases = 0; recs = 0; per_knob = {}; kinds = {}
+    while time.time() - t0 < seconds:
+        case_seed = (seed << 32) + len(F.SEEDS) + cases        # (beyond the suite's seeds)
+        knobs = KNOBS[int(rng.integers(0, len(KNOBS)))]
+        c = F.ClassCase(case_seed, knobs)
+        for k in KNOB_NAMES: os.environ.pop(k, None)
+        os.environ.update(knobs)
+        try:
+            recs += F.run_class_case(lambda: GpuMatcher(0, 1), c, tmp)
+        except AssertionError as e:
+            raise SystemExit(f"MISMATCH case {cases} (ClassCase({case_seed}, {knobs})): {e}")
+        per_knob[knob_label(knobs)] = per_knob.get(knob_label(knobs), 0) + 1
+        kinds[c.kind] = kinds.get(c.kind, 0) + 1
+        cases += 1
+        if time.time() - t_last > 30:
+            t_last = time.time(); print(f"  ... {cases} cases, {recs} records compared, {t_last - t0:.0f} s", flush=True)
+    print(f"class fuzz ok: {cases} cases in {time.time() - t0:.0f} s (seed {seed}; {', '.join(f'{v} {k}' for k, v in sorted(kinds.items()))}), "
+          f"{recs} records compared (scan x2, documents, selection, replace, outputs lists, GPU text)")
+    print("cases per knob set: " + ", ".join(f"{k} {v}" for k, v in sorted(per_knob.items())))
     raise SystemExit(0)
 seconds = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
