@@ -3172,33 +3172,83 @@ __global__ void pfac_fill_tiled_kernel(unsigned char *dst, unsigned long long n,
 
 thread_local std::string g_err;
 
+int fail(pfac_ctx *ctx, int code, const std::string &msg);
+
+#define HIP_TRY(ctx, expr)                                                                     \
+    do {                                                                                       \
+        hipError_t e_ = (expr);                                                                \
+        if (e_ != hipSuccess)                                                                  \
+            return fail(ctx, PFAC_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
+    } while (0)
+
+// A device allocation that a context or a slot owns: pointer and capacity (in elements of T) live and die together.
+// It only grows, and the caller names the new capacity -- the growth policies differ per buffer on purpose.  The
+// lifetime rule of the runtime is kept HERE: nothing queued on the owner's stream may still use the buffer when it
+// is freed, so a slot's buffer is grown with the slot's stream, which is synchronised first (the context's table
+// buffers and a call's temporaries pass none: install_table waits for the scans in flight itself).  Freed with its
+// owner: pfac_ctx_destroy synchronises the streams, then deletes the context under its device guard.
+template <typename T>
+struct DevBuf {
+    T *p = nullptr;
+    uint64_t cap = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
+    ~DevBuf() { reset(); }
+    void reset() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+    int ensure(pfac_ctx *ctx, hipStream_t stream, uint64_t need, uint64_t new_cap) {
+        if (need <= cap) return PFAC_OK;
+        if (p) {
+            if (stream) HIP_TRY(ctx, hipStreamSynchronize(stream));
+            HIP_TRY(ctx, hipFree(p));
+            p = nullptr;
+            cap = 0;
+        }
+        HIP_TRY(ctx, hipMalloc((void **)&p, new_cap * sizeof(T)));
+        cap = new_cap;
+        return PFAC_OK;
+    }
+};
+
+// capacity of a per-tile array asked for n entries: a quarter more, 4096 at least
+uint64_t quarter_more(uint64_t n) { return n < 4096 ? 4096 : n + n / 4; }
+
+// 64-bit words in Slot::h_ctl (as indices of its 32-bit words)
+enum : int {
+    H_MATCHES = 0,                        // written by the scan kernel: matches, ...
+    H_USED = 4,                           // ... heap records used
+    H_CHECKSUM = 8,                       // pfac_records_checksum
+    H_PASS = 10,                          // what a pass copies back from behind its group prefixes: the total, ...
+    H_PASS1 = 12,                         // ... the word behind it (segment: bad offsets; selection: exit offset; replace: error), ...
+    H_PASS2 = 14,                         // ... and the one behind that (document selection: bad offsets; replace: c_{n-1})
+};
+
 struct Slot {
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
-    unsigned char *d_input = nullptr;
-    uint64_t input_cap = 0;
-    void *d_records = nullptr;            // record_cap x 8 bytes: holds either record format
-    uint64_t record_cap = 0;
-    unsigned long long *d_tile_index = nullptr;   // per tile of the last scan: first record | count << 40
-    unsigned *d_d2log = nullptr;                  // dense mode, second form: the record logs of the grid's compute waves
-    size_t d2log_words = 0;
-    uint64_t tile_cap = 0;
-    unsigned long long *d_gsum = nullptr; // scratch of the expand / text paths: record (byte) prefix per group of 64 tiles (+ the total)
-    uint64_t gsum_cap = 0;
-    unsigned char *d_text = nullptr;      // pfac_emit_text_device: the formatted lines of the slot's last scan
-    uint64_t text_cap = 0, text_bytes = 0;
-    pfac_record *d_wide = nullptr;        // scratch of pfac_records_d2h: packed records expanded on the device
-    uint64_t wide_cap = 0;
+    DevBuf<unsigned char> input;
+    DevBuf<pfac_record> records;          // cap x 8 bytes: holds either record format
+    DevBuf<unsigned long long> tile_index;        // per tile of the last scan: first record | count << 40
+    DevBuf<unsigned> d2log;               // dense mode, second form: the record logs of the grid's compute waves
+    DevBuf<unsigned long long> gsum;      // scratch of the expand / text paths: record (byte) prefix per group of 64 tiles (+ the total)
+    DevBuf<unsigned char> text;           // pfac_emit_text_device: the formatted lines of the slot's last scan
+    uint64_t text_bytes = 0;
+    DevBuf<pfac_record> wide;             // scratch of pfac_records_d2h: packed records expanded on the device
     int last_rec_bytes = 4;               // record form of the slot's last scan (2, 4 or 8 bytes)
     const void *last_records = nullptr;   // ... and where it wrote
-    unsigned *d_ctl = nullptr;            // TWO control headers (ticket counters, flags, heap cursor), used alternately:
+    DevBuf<unsigned> ctl;                 // TWO control headers (ticket counters, flags, heap cursor), used alternately:
     unsigned *d_ctlbuf[2] = {nullptr, nullptr};   // a scan zeroes the other one for the scan after it
     bool clean[2] = {false, false};       // header known to be zero
     int flip = 0;                         // header of the next scan
     unsigned *h_ctl = nullptr;            // pinned, device-visible: [0..1] matches, [2] err, [3] dense tiles, [4..5] heap
-                                          // records used (written by the kernel), [8..9] checksum
+                                          // records used (written by the kernel), [8..9] checksum, [10..15] a pass's
+                                          // results (the H_ constants above name the 64-bit ones)
     unsigned *d_res = nullptr;            // device-side address of h_ctl
-    unsigned long long *d_sum = nullptr;
+    DevBuf<unsigned long long> sum;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipEvent_t ev_h2d = nullptr;          // behind the slot's last pfac_slot_h2d: the host buffer may be reused once it has fired
     bool h2d_issued = false;
@@ -3206,46 +3256,39 @@ struct Slot {
     bool scanned = false, pending = false, last_dense = false;
     uint64_t last_owned = 0;              // n_owned of the slot's last scan (what pfac_records_segment cuts)
     uint64_t last_table = 0;              // ... and the table it ran with (pfac_ctx::table_gen)
-    unsigned long long *d_dbg = nullptr;  // PFAC_TRACE_BUILD + PFAC_TRACE
+    DevBuf<unsigned long long> dbg;       // PFAC_TRACE_BUILD + PFAC_TRACE
     // pfac_slot_doc_offsets / pfac_records_segment
-    unsigned long long *d_doc_off = nullptr;   // the slot's document offsets (doc_n + 1 of them)
-    uint64_t doc_off_cap = 0, doc_n = 0;
+    DevBuf<unsigned long long> doc_off;   // the slot's document offsets (doc_n + 1 of them)
+    uint64_t doc_n = 0;
     bool doc_set = false;
-    unsigned *d_seg_tcnt = nullptr;       // kept records per tile of the last segment pass
-    uint64_t seg_tcnt_cap = 0;
-    pfac_record *d_seg_out = nullptr;     // slot-owned outputs of the last segment pass (d_out / d_doc_first NULL)
-    uint64_t seg_out_cap = 0;
-    unsigned long long *d_seg_first = nullptr;
-    uint64_t seg_first_cap = 0;
+    DevBuf<unsigned> seg_tcnt;            // kept records per tile of the last segment pass
+    DevBuf<pfac_record> seg_out;          // slot-owned outputs of the last segment pass (d_out / d_doc_first NULL)
+    DevBuf<unsigned long long> seg_first;
     uint64_t seg_kept = 0, seg_docs = 0;
     bool seg_done = false, seg_own_out = false, seg_own_first = false;
     // pfac_records_leftmost_longest
-    unsigned char *d_ll_tmp = nullptr;    // group functions, group entries, picks per tile, per-tile selection bitmaps
-    uint64_t ll_tmp_cap = 0;
-    pfac_record *d_ll_out = nullptr;      // slot-owned selection (d_out NULL)
-    uint64_t ll_out_cap = 0, ll_n = 0;
+    DevBuf<unsigned char> ll_tmp;         // group functions, group entries, picks per tile, per-tile selection bitmaps
+    DevBuf<pfac_record> ll_out;           // slot-owned selection (d_out NULL)
+    uint64_t ll_n = 0;
     bool ll_done = false, ll_own_out = false;
     uint64_t ll_seq = 0;                  // the scan it selected from (scan_seq), ...
     uint32_t ll_entry = 0, ll_exit = 0;   // ... and its entry and exit offsets
     // pfac_replace_leftmost_longest
     uint64_t last_avail = 0;              // n_avail of the slot's last scan (the input bytes it may read)
     uint64_t scan_seq = 0;                // scans issued on this slot
-    unsigned char *d_rp_tmp = nullptr;    // X per block of 64 picks
-    uint64_t rp_tmp_cap = 0;
-    unsigned char *d_rp_out = nullptr;    // slot-owned output (d_out NULL)
-    uint64_t rp_out_cap = 0, rp_bytes = 0;
+    DevBuf<unsigned char> rp_tmp;         // X per block of 64 picks
+    DevBuf<unsigned char> rp_out;         // slot-owned output (d_out NULL)
+    uint64_t rp_bytes = 0;
     bool rp_done = false, rp_own_out = false;
     // pfac_records_leftmost_longest_documents / pfac_replace_documents
     uint64_t doc_gen = 0;                 // pfac_slot_doc_offsets calls: a selection remembers the offsets it cut with
     bool ll_docs = false;                 // the slot's last selection was per document, ...
     uint64_t lld_docs = 0, lld_gen = 0;   // ... over this many documents, with the slot's offsets of this generation
     bool lld_own_off = false, lld_own_first = false;   // (or the caller's offsets / doc_first)
-    unsigned long long *d_lld_first = nullptr;   // slot-owned doc_first (d_doc_first NULL)
-    uint64_t lld_first_cap = 0;
-    unsigned long long *d_rpd_tmp = nullptr;     // D_k per pick (and the total behind them)
-    uint64_t rpd_tmp_cap = 0;
-    unsigned long long *d_rpd_off = nullptr;     // slot-owned output offsets (d_out_offsets NULL)
-    uint64_t rpd_off_cap = 0, rpd_docs = 0;
+    DevBuf<unsigned long long> lld_first; // slot-owned doc_first (d_doc_first NULL)
+    DevBuf<unsigned long long> rpd_tmp;   // D_k per pick (and the total behind them)
+    DevBuf<unsigned long long> rpd_off;   // slot-owned output offsets (d_out_offsets NULL)
+    uint64_t rpd_docs = 0;
     bool rpd_done = false, rpd_own_off = false;
 };
 
@@ -3265,12 +3308,11 @@ struct pfac_ctx {
                                           // kernels on the slots' own streams leave gaps (45 GB/s measured); the slot's stream
                                           // waits for its copy through an event
     // table
-    int *d_tab = nullptr;
-    size_t tab_bytes = 0;
+    DevBuf<unsigned char> tab;            // the repacked tables: the four views below
     int *d_s0 = nullptr, *d_r = nullptr, *d_idmap = nullptr;
     int2 *d_T = nullptr;
     int4 *d_T4 = nullptr;                 // fused slots (variant 1, width >= 256), else null: slot 0 of ...
-    int4 *d_T4_alloc = nullptr;           // ... this allocation, which starts at slot min(0, min r) = -rn_bias
+    DevBuf<int4> T4_alloc;                // ... this allocation, which starts at slot min(0, min r) = -rn_bias
     int rn_bias = 0;
     int width_bit = 0, num_final = 0, max_pat_len = 0, max_row = 0, ht_size = 0, state_num = 0;
     bool have_table = false;
@@ -3284,25 +3326,24 @@ struct pfac_ctx {
     StageLayout lay[2];                   // sparse staging: [0] two buffers (emission lags one round), [1] three (two rounds)
     bool lag2_ok = false, lag2 = false, lag_forced = false;   // three-buffer layout usable / in use / pinned (PFAC_LAG)
     const StageLayout &sparse() const { return lay[lag2 ? 1 : 0]; }
-    // the dense-mode twin of {pw_bytes, waves_per_block, lds_bytes, stage_cap}: one big staging buffer per wave
-    int pw_bytes_d = 0, waves_per_block_d = 0, lds_bytes_d = 0;
-    unsigned stage_cap_d = 0;
+    StageLayout lay_d;                    // dense staging: one big buffer per wave (stage_cap 0: dense mode unavailable)
     bool dense = false;                   // current staging mode (adapts to the match density seen by the last scan)
+    bool run_dense() const { return dense && lay_d.stage_cap; }       // ... of the next launch
+    const StageLayout &layout(bool dense_mode) const { return dense_mode ? lay_d : sparse(); }
     bool dense2 = false;                  // dense mode runs in its second form (dense2_tile): fused tables, packed dense rows, 4-byte records
     unsigned d2log_cap = 0;               // ... words of record log per compute wave (test knob PFAC_D2_LOGCAP: a smaller one)
     int dense_forced = -1;                // PFAC_DENSE=0/1 pins the mode
-    int *d_d1 = nullptr;                  // dense depth-1 rows + (after them) the 256-byte row index
+    DevBuf<int> d1;                       // dense depth-1 rows + (after them) the 256-byte row index
     int d1_rows = 0, d1_stride = 0, d1_ncols = 0, d1_lds_bytes = 0;
     int d1_n2 = 0;                        // > 0: dense rows are packed (fused tables), r[] of the depth-2 states follows them
     int grid_blocks = 0;
     int rec_bytes = 4;                    // record form: 2 (<= 16 final states), 4 (<= 2^20), 8 bytes (pfac_record)
-    short *d_flen = nullptr;              // pattern length of every final state (pfac_table_set_final_lengths), cleared by an upload
-    unsigned *d_rep_off = nullptr;        // replacement of every final state (pfac_table_set_replacements): offsets[num_final + 1]
-    unsigned char *d_rep = nullptr;       // ... and the bytes, zero-padded to rep_size (a multiple of 16); cleared by an upload
-    uint64_t rep_size = 0;
+    DevBuf<short> flen;                   // pattern length of every final state (pfac_table_set_final_lengths), cleared by an upload
+    DevBuf<unsigned> rep_off;             // replacement of every final state (pfac_table_set_replacements): offsets[num_final + 1]
+    DevBuf<unsigned char> rep;            // ... and the bytes, zero-padded to its capacity (a multiple of 16); cleared by an upload
     uint64_t table_gen = 0;               // tables installed so far: a scan's final states index the lengths of ITS table only
     // level-2 filter (ScanArgs::l2f_mode)
-    unsigned char *d_bm2 = nullptr;       // 2-byte-prefix bitmap, 256 rows of 32 bytes
+    DevBuf<unsigned char> bm2;            // 2-byte-prefix bitmap, 256 rows of 32 bytes
     int l2f_mode = 0, n_child = 0, bm2_rows = 0, sh_bm2 = 0, sec_filter = 0, sh_t0 = 0;
     unsigned child0 = 0, child1 = 0;
     // tuning / test knobs, read from the environment ONCE, when a table is installed
@@ -3319,13 +3360,6 @@ int fail(pfac_ctx *ctx, int code, const std::string &msg) {
     if (ctx) ctx->err = msg;
     return code;
 }
-
-#define HIP_TRY(ctx, expr)                                                                     \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess)                                                                  \
-            return fail(ctx, PFAC_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
-    } while (0)
 
 // Every entry point works on its context's device and leaves the calling thread's current device as it found it
 // (a caller that drives several GPUs from one thread -- torch does -- must not have it changed under its feet).
@@ -3358,26 +3392,74 @@ size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 constexpr size_t CTL_REGION = (CTL_WORDS * 4 + 255) / 256 * 256;
 
 int ensure_ctl(pfac_ctx *ctx, Slot &s) {
-    if (s.d_ctl) return PFAC_OK;
-    HIP_TRY(ctx, hipMalloc((void **)&s.d_ctl, 2 * CTL_REGION));
-    s.d_ctlbuf[0] = s.d_ctl;
-    s.d_ctlbuf[1] = reinterpret_cast<unsigned *>(reinterpret_cast<unsigned char *>(s.d_ctl) + CTL_REGION);
+    if (s.ctl.p) return PFAC_OK;
+    int rc = s.ctl.ensure(ctx, s.stream, 1, 2 * CTL_REGION / 4);
+    if (rc) return rc;
+    s.d_ctlbuf[0] = s.ctl.p;
+    s.d_ctlbuf[1] = s.ctl.p + CTL_REGION / 4;
     s.clean[0] = s.clean[1] = false;
     s.flip = 0;
     return PFAC_OK;
 }
 
-int ensure_tiles(pfac_ctx *ctx, Slot &s, uint64_t n_entries) {
-    if (s.d_tile_index && s.tile_cap >= n_entries) return PFAC_OK;
-    if (s.d_tile_index) {
-        HIP_TRY(ctx, hipStreamSynchronize(s.stream));
-        HIP_TRY(ctx, hipFree(s.d_tile_index));
-        s.d_tile_index = nullptr;
-    }
-    const uint64_t cap = n_entries < 4096 ? 4096 : n_entries + n_entries / 4;
-    HIP_TRY(ctx, hipMalloc((void **)&s.d_tile_index, cap * 8));
-    s.tile_cap = cap;
+// n_groups prefixes + the grand total behind them (callers that keep more words behind the total ask for more groups)
+int ensure_gsum(pfac_ctx *ctx, Slot &s, unsigned n_groups) {
+    return s.gsum.ensure(ctx, s.stream, (uint64_t)n_groups + 1, quarter_more(n_groups) + 1);
+}
+
+// a slot-owned array of n_docs + 1 entries (offsets, doc_first)
+int ensure_docs(pfac_ctx *ctx, Slot &s, DevBuf<unsigned long long> &b, uint64_t n_docs) {
+    return b.ensure(ctx, s.stream, n_docs + 1, n_docs + 1 < 4096 ? 4096 : n_docs + 1 + n_docs / 4);
+}
+
+// f(std::integral_constant<int, BYTES>()) for a record width of 2, 4 or 8 bytes: how a pass picks the kernel of the
+// last scan's record form, as in  by_width(rb, [](auto w) { return pfac_expand_kernel<w()>; })
+template <typename F>
+auto by_width(int rec_bytes, F f) {
+    return rec_bytes == 2 ? f(std::integral_constant<int, 2>()) : (rec_bytes == 4 ? f(std::integral_constant<int, 4>()) : f(std::integral_constant<int, 8>()));
+}
+
+uint64_t host_u64(const Slot &s, int word) { return ((uint64_t)s.h_ctl[word + 1] << 32) | s.h_ctl[word]; }
+
+// What a pass needs of the slot's last scan, tested in this order (the first failure is the one reported).
+enum : unsigned {
+    SCAN_FINISHED = 1,                    // there is one, and pfac_scan_finish has returned
+    SCAN_LENGTHS = 2,                     // the uploaded table has its final-state lengths
+    SCAN_TABLE = 4,                       // it ran with the table that is installed now, ...
+    SCAN_IDMAP = 8,                       // ... (the same, for a pass that maps its states through that table's idmap)
+    SCAN_FITS = 16,                       // its records fitted the heap
+};
+int last_scan_usable(pfac_ctx *ctx, const Slot &s, const std::string &fn, unsigned what) {
+    if ((what & SCAN_FINISHED) && (!s.scanned || s.pending)) return fail(ctx, PFAC_E_STATE, fn + " needs a finished scan");
+    if ((what & SCAN_LENGTHS) && (!ctx->have_table || !ctx->flen.p))
+        return fail(ctx, PFAC_E_STATE, fn + ": no final-state lengths for the uploaded table (pfac_table_set_final_lengths)");
+    if ((what & (SCAN_TABLE | SCAN_IDMAP)) && s.last_table != ctx->table_gen)
+        return fail(ctx, PFAC_E_STATE, fn + ": the slot's last scan ran with an earlier table" +
+                                           ((what & SCAN_IDMAP) ? " (its states index that table's idmap)" : ""));
+    if ((what & SCAN_FITS) && s.last_used > s.last_cap)
+        return fail(ctx, PFAC_E_OVERFLOW, "the slot's last scan overflowed its record heap: scan again with a larger one");
     return PFAC_OK;
+}
+
+// The documents argument of a pass: NULL means the slot's offsets (pfac_slot_doc_offsets), and then n_docs must be
+// theirs; `others` are the bits of the pass's other document-sized device pointers, which share the alignment rule.
+int resolve_docs(pfac_ctx *ctx, const Slot &s, const std::string &fn, const uint64_t *d_doc_offsets, uint64_t n_docs,
+                 uintptr_t others, const unsigned long long **off) {
+    *off = reinterpret_cast<const unsigned long long *>(d_doc_offsets);
+    if (!*off) {
+        if (!s.doc_set) return fail(ctx, PFAC_E_STATE, fn + ": no document offsets for the slot (pfac_slot_doc_offsets)");
+        if (n_docs != s.doc_n) return fail(ctx, PFAC_E_ARG, fn + ": n_docs differs from the slot's document offsets");
+        *off = s.doc_off.p;
+    }
+    if (n_docs >= (1ull << 32)) return fail(ctx, PFAC_E_ARG, fn + ": n_docs must be below 2^32");
+    if (n_docs == 0 && s.last_owned != 0) return fail(ctx, PFAC_E_ARG, fn + ": no documents, but the scan owns bytes");
+    if (((uintptr_t)*off | others) & 7) return fail(ctx, PFAC_E_ARG, fn + ": device buffers must be 8-byte aligned");
+    return PFAC_OK;
+}
+
+int bad_doc_offsets(pfac_ctx *ctx, const Slot &s, const std::string &fn) {     // (the device found them so)
+    return fail(ctx, PFAC_E_ARG, fn + ": document offsets must start at 0, not decrease, and end at the scan's n_owned (" +
+                                     std::to_string(s.last_owned) + ")");
 }
 
 // Tuning and test knobs (PFAC_FORCE_L2, PFAC_NWB, PFAC_FAULT, ...) are honoured ONLY in a process that opts in with
@@ -3393,9 +3475,34 @@ int env_int(const char *name, int dflt) {
 }
 
 static int max_lds(const pfac_ctx *ctx) {
-    int v = ctx->lds_bytes_d;
+    int v = ctx->lay_d.lds_bytes;
     for (const StageLayout &L : ctx->lay) v = L.lds_bytes > v ? L.lds_bytes : v;
     return v;
+}
+
+// one workgroup per CU: ask for more than half of the LDS so two never share a CU while another idles
+int lds_of_one_block_per_cu(int lds_bytes) { return lds_bytes < LDS_TOTAL / 2 + 256 ? LDS_TOTAL / 2 + 256 : lds_bytes; }
+
+// The scan kernel of a table placement (0: tables via L2, 1: tables in LDS, 2: fused L2 tables, 3: fused L2 tables
+// with four walks per lane -- dense mode, two staging buffers only), hash width, root test and NB staging buffers.
+template <int NB, bool TLDS, bool FUSED, int NW>
+const void *scan_kernel_of(bool w8, int root) {
+    const void *const k[2][2] = {
+        {(const void *)pfac_scan_kernel<TLDS, false, 0, FUSED, NW, NB>, (const void *)pfac_scan_kernel<TLDS, false, 1, FUSED, NW, NB>},
+        {(const void *)pfac_scan_kernel<TLDS, true, 0, FUSED, NW, NB>, (const void *)pfac_scan_kernel<TLDS, true, 1, FUSED, NW, NB>}};
+    return k[w8 ? 1 : 0][root];
+}
+template <int NB>
+const void *scan_kernel(int placement, bool w8, int root) {
+    // (three walks per lane for the sparse fused kernels -- one round per tile of the 75 840-pattern set on random bytes
+    // instead of 1.45 -- measured 3 % slower than two: 112 VGPRs and the longer round cost more than the second round)
+    constexpr int FNW = PFAC_SPARSE_FUSED_NW;   // walks per lane of the sparse-mode kernels on fused L2 tables
+    switch (placement) {
+    case 0: return scan_kernel_of<NB, false, false, 2>(w8, root);
+    case 1: return scan_kernel_of<NB, true, false, 1>(w8, root);
+    case 2: return scan_kernel_of<NB, false, true, FNW>(w8, root);
+    default: return scan_kernel_of<2, false, true, 4>(w8, root);
+    }
 }
 
 // layout of pfac_ctx::d_d1: rows (d1_rows x 256 int32) | 256-byte row index | the depth-1 states | (packed rows) {r[], child
@@ -3424,23 +3531,24 @@ int configure_kernel(pfac_ctx *ctx, const int32_t *s0_host) {
     // tables via L2 and PHF width >= 256: fused slots, one gather per step
     const bool fused = ctx->variant == 1 && ctx->width_bit >= 8 && !knob("PFAC_NO_FUSE");
     ctx->d1_n2 = 0;
-    if (ctx->d_d1) { HIP_TRY(ctx, hipFree(ctx->d_d1)); ctx->d_d1 = nullptr; }
+    ctx->d1.reset();
     if (ctx->d1_rows) {
         const size_t off_r2 = d1_off_r2(ctx->d1_rows);
         const size_t off_col = d1_off_col(ctx->d1_rows);
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_d1, off_col + 512));
-        unsigned char *b = reinterpret_cast<unsigned char *>(ctx->d_d1);
+        int rc = ctx->d1.ensure(ctx, nullptr, (off_col + 512) / 4, (off_col + 512) / 4);
+        if (rc) return rc;
+        unsigned char *b = reinterpret_cast<unsigned char *>(ctx->d1.p);
         int *d_state = reinterpret_cast<int *>(b + (size_t)ctx->d1_rows * 1024 + 256);
         HIP_TRY(ctx, hipMemcpy(b + (size_t)ctx->d1_rows * 1024, d1idx, 256, hipMemcpyHostToDevice));
         HIP_TRY(ctx, hipMemcpy(d_state, d1state, (size_t)ctx->d1_rows * 4, hipMemcpyHostToDevice));
         hipLaunchKernelGGL(pfac_build_d1_kernel, dim3(ctx->d1_rows), dim3(256), 0, 0, d_state, ctx->d_r, ctx->d_T,
-                           ctx->width_bit, ctx->ht_size, ctx->d_d1);
+                           ctx->width_bit, ctx->ht_size, ctx->d1.p);
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipDeviceSynchronize());
         // which bytes are the second byte of some pattern: the LDS rows keep those columns only (host copy of the
         // rows: at most 255 KiB); too many rows x columns for LDS: no dense level
         std::vector<int> rows((size_t)ctx->d1_rows * 256);
-        HIP_TRY(ctx, hipMemcpy(rows.data(), ctx->d_d1, rows.size() * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(rows.data(), ctx->d1.p, rows.size() * 4, hipMemcpyDeviceToHost));
         unsigned char colmap[256], colbyte[256];
         int ncols = 0;
         for (int c = 0; c < 256; c++) {
@@ -3452,8 +3560,7 @@ int configure_kernel(pfac_ctx *ctx, const int32_t *s0_host) {
         for (int c = 0; c < 256; c++) colmap[c] = (unsigned char)(ncols & 255);
         for (int k = 0; k < ncols; k++) colmap[colbyte[k]] = (unsigned char)k;
         if ((size_t)ctx->d1_rows * stride * 4 > (size_t)D1_LDS_MAX) {
-            HIP_TRY(ctx, hipFree(ctx->d_d1));
-            ctx->d_d1 = nullptr;
+            ctx->d1.reset();
             ctx->d1_rows = 0;
         } else {
             ctx->d1_stride = stride;
@@ -3470,7 +3577,7 @@ int configure_kernel(pfac_ctx *ctx, const int32_t *s0_host) {
                 int2 *r2 = reinterpret_cast<int2 *>(b + off_r2);
                 int *counter = reinterpret_cast<int *>(r2 + D1_N2_MAX);
                 HIP_TRY(ctx, hipMemset(counter, 0, 4));
-                hipLaunchKernelGGL(pfac_pack_d1_kernel, dim3((unsigned)ctx->d1_rows), dim3(256), 0, 0, ctx->d_d1,
+                hipLaunchKernelGGL(pfac_pack_d1_kernel, dim3((unsigned)ctx->d1_rows), dim3(256), 0, 0, ctx->d1.p,
                                    ctx->d1_rows * 256, ctx->d_r, ctx->d_T, ctx->width_bit, ctx->ht_size, ctx->max_row, r2, counter);
                 HIP_TRY(ctx, hipGetLastError());
                 HIP_TRY(ctx, hipDeviceSynchronize());
@@ -3484,9 +3591,10 @@ int configure_kernel(pfac_ctx *ctx, const int32_t *s0_host) {
     if (ctx->d1_n2 > 0) { ctx->sh_t0 = ctx->shared_bytes; ctx->shared_bytes += 1024; }   // dense mode, second form: its root table
     // ---- level-2 filter: the 2-byte-prefix bitmap is built on the device from the uploaded tables; a single-edge
     // root with at most two grandchildren gets the bit-parallel form (their bytes), everything else the lookup form
-    if (!ctx->d_bm2) HIP_TRY(ctx, hipMalloc((void **)&ctx->d_bm2, 256 * 32 + 256));   // bitmap + the second-byte flags
+    int rc = ctx->bm2.ensure(ctx, nullptr, 256 * 32 + 256, 256 * 32 + 256);   // bitmap + the second-byte flags
+    if (rc) return rc;
     hipLaunchKernelGGL(pfac_build_bm2_kernel, dim3(256), dim3(256), 0, 0, ctx->d_s0, ctx->d_r, ctx->d_T, ctx->width_bit,
-                       ctx->ht_size, reinterpret_cast<unsigned long long *>(ctx->d_bm2));
+                       ctx->ht_size, reinterpret_cast<unsigned long long *>(ctx->bm2.p));
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipDeviceSynchronize());
     ctx->l2f_mode = 2;
@@ -3494,13 +3602,13 @@ int configure_kernel(pfac_ctx *ctx, const int32_t *s0_host) {
     ctx->n_child = 0;
     ctx->child0 = ctx->child1 = 0;
     std::vector<unsigned char> bm2_host(256 * 32 + 256);
-    HIP_TRY(ctx, hipMemcpy(bm2_host.data(), ctx->d_bm2, 256 * 32, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(bm2_host.data(), ctx->bm2.p, 256 * 32, hipMemcpyDeviceToHost));
     for (int c = 0; c < 256; c++) {                         // column OR: can byte c be a pattern's second byte?
         unsigned char any = 0;
         for (int b0 = 0; b0 < 256; b0++) any |= (unsigned char)(bm2_host[(size_t)b0 * 32 + (c >> 3)] >> (c & 7) & 1);
         bm2_host[256 * 32 + c] = any;
     }
-    HIP_TRY(ctx, hipMemcpy(ctx->d_bm2 + 256 * 32, bm2_host.data() + 256 * 32, 256, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(ctx->bm2.p + 256 * 32, bm2_host.data() + 256 * 32, 256, hipMemcpyHostToDevice));
     bool any_fin1 = false;                                  // a 1-byte pattern: its survivors are kept whatever follows
     for (int i = 0; i < 256; i++) any_fin1 = any_fin1 || (s0_host[i] >= 0 && s0_host[i] < ctx->num_final);
     ctx->sec_filter = (fan != 1 && !any_fin1 && !knob("PFAC_NO_SECF")) ? 1 : 0;
@@ -3562,9 +3670,7 @@ int configure_kernel(pfac_ctx *ctx, const int32_t *s0_host) {
         if (cap > 1024u) cap = 1024u;
         L.pw_bytes += (int)(cap - base_cap) * nb * 4;
         L.stage_cap = cap;
-        L.lds_bytes = ctx->shared_bytes + (nwb - 1) * L.pw_bytes;
-        // one workgroup per CU: ask for more than half of the LDS so two never share a CU while another idles
-        if (L.lds_bytes < LDS_TOTAL / 2 + 256) L.lds_bytes = LDS_TOTAL / 2 + 256;
+        L.lds_bytes = lds_of_one_block_per_cu(ctx->shared_bytes + (nwb - 1) * L.pw_bytes);
     }
     const int lag_knob = env_int("PFAC_LAG", 0);          // 1 / 2: pin the emission lag (tests, A/B runs)
     ctx->lag2_ok = ctx->lay[1].stage_cap >= (unsigned)CAPW3_MIN && lag_knob != 1;
@@ -3589,17 +3695,19 @@ int configure_kernel(pfac_ctx *ctx, const int32_t *s0_host) {
     ctx->d2log_cap = D2_LOG_CAP;
     const int d2cap_knob = env_int("PFAC_D2_LOGCAP", 0);     // test knob: tiles with more records than this take the fallback pass
     if (d2cap_knob >= 16 && (unsigned)d2cap_knob < D2_LOG_CAP) ctx->d2log_cap = (unsigned)d2cap_knob;
-    ctx->pw_bytes_d = (int)align_up((size_t)(ctx->dense2 ? PW_FIXED_DENSE2 : PW_FIXED_DENSE) + ctx->halo, 16);
-    int nwd = (LDS_TOTAL - ctx->shared_bytes) / ctx->pw_bytes_d + 1;
+    StageLayout &D = ctx->lay_d;
+    D.nbuf = 1;
+    D.pw_bytes = (int)align_up((size_t)(ctx->dense2 ? PW_FIXED_DENSE2 : PW_FIXED_DENSE) + ctx->halo, 16);
+    int nwd = (LDS_TOTAL - ctx->shared_bytes) / D.pw_bytes + 1;
     if (nwd > MAX_WAVES_PER_BLOCK) nwd = MAX_WAVES_PER_BLOCK;
-    ctx->waves_per_block_d = nwd;
-    ctx->lds_bytes_d = ctx->shared_bytes + (nwd - 1) * ctx->pw_bytes_d;
-    if (ctx->lds_bytes_d < LDS_TOTAL / 2 + 256) ctx->lds_bytes_d = LDS_TOTAL / 2 + 256;
-    ctx->stage_cap_d = (nwd >= 4 && ctx->lay[0].stage_cap) ? (unsigned)CAPW_DENSE : 0u;   // 0: dense mode unavailable
+    D.waves_per_block = nwd;
+    D.lds_bytes = lds_of_one_block_per_cu(ctx->shared_bytes + (nwd - 1) * D.pw_bytes);
+    D.stage_cap = (nwd >= 4 && ctx->lay[0].stage_cap) ? (unsigned)CAPW_DENSE : 0u;   // 0: dense mode unavailable
     ctx->dense_forced = knob("PFAC_DENSE") ? atoi(knob("PFAC_DENSE")) : -1;
-    ctx->dense = ctx->dense_forced == 1 && ctx->stage_cap_d;
+    ctx->dense = ctx->dense_forced == 1 && D.stage_cap;
     const bool w8 = ctx->width_bit == 8;
-    if (ctx->d_T4_alloc) { HIP_TRY(ctx, hipFree(ctx->d_T4_alloc)); ctx->d_T4_alloc = ctx->d_T4 = nullptr; }
+    ctx->T4_alloc.reset();
+    ctx->d_T4 = nullptr;
     ctx->rn_bias = 0;
     if (fused) {
         std::vector<int> r_host((size_t)ctx->max_row);
@@ -3610,46 +3718,26 @@ int configure_kernel(pfac_ctx *ctx, const int32_t *s0_host) {
             hi = (long long)v + (1 << ctx->width_bit) > hi ? (long long)v + (1 << ctx->width_bit) : hi;
         }
         if (hi - lo >= (1ll << 28)) return fail(ctx, PFAC_E_ARG, "table image: more than 2^28 hash slots");
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_T4_alloc, (size_t)(hi - lo) * sizeof(int4)));
-        ctx->d_T4 = ctx->d_T4_alloc - lo;
+        rc = ctx->T4_alloc.ensure(ctx, nullptr, (uint64_t)(hi - lo), (uint64_t)(hi - lo));
+        if (rc) return rc;
+        ctx->d_T4 = ctx->T4_alloc.p - lo;
         ctx->rn_bias = (int)-lo;
         hipLaunchKernelGGL(pfac_fuse_kernel, dim3(256), dim3(256), 0, 0, ctx->d_T, ctx->d_r, ctx->width_bit, ctx->ht_size,
                            ctx->max_row, ctx->d_T4, (int)lo, (int)hi);
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipDeviceSynchronize());
     }
-    constexpr int FNW = PFAC_SPARSE_FUSED_NW;   // walks per lane of the sparse-mode kernels on fused L2 tables
-    const void *k[4][2][2] = {
-        {{(const void *)pfac_scan_kernel<false, false, 0, false, 2>, (const void *)pfac_scan_kernel<false, false, 1, false, 2>},
-         {(const void *)pfac_scan_kernel<false, true, 0, false, 2>, (const void *)pfac_scan_kernel<false, true, 1, false, 2>}},
-        {{(const void *)pfac_scan_kernel<true, false, 0, false, 1>, (const void *)pfac_scan_kernel<true, false, 1, false, 1>},
-         {(const void *)pfac_scan_kernel<true, true, 0, false, 1>, (const void *)pfac_scan_kernel<true, true, 1, false, 1>}},
-        {{(const void *)pfac_scan_kernel<false, false, 0, true, FNW>, (const void *)pfac_scan_kernel<false, false, 1, true, FNW>},
-         {(const void *)pfac_scan_kernel<false, true, 0, true, FNW>, (const void *)pfac_scan_kernel<false, true, 1, true, FNW>}},
-        {{(const void *)pfac_scan_kernel<false, false, 0, true, 4>, (const void *)pfac_scan_kernel<false, false, 1, true, 4>},
-         {(const void *)pfac_scan_kernel<false, true, 0, true, 4>, (const void *)pfac_scan_kernel<false, true, 1, true, 4>}}};
-    // (three walks per lane for the sparse fused kernels -- one round per tile of the 75 840-pattern set on random bytes
-    // instead of 1.45 -- measured 3 % slower than two: 112 VGPRs and the longer round cost more than the second round)
-    ctx->kernel = k[ctx->variant == 0 ? 1 : (fused ? 2 : 0)][w8 ? 1 : 0][ctx->root_mode];
-    // dense mode on fused L2 tables: four walks per lane (needs <= MAX_WAVES_NW4 waves per workgroup)
+    const int placement = ctx->variant == 0 ? 1 : (fused ? 2 : 0);
+    ctx->kernel = scan_kernel<2>(placement, w8, ctx->root_mode);
     ctx->kernel_d = ctx->kernel;
-    {
-        const void *k3[3][2][2] = {
-            {{(const void *)pfac_scan_kernel<false, false, 0, false, 2, 3>, (const void *)pfac_scan_kernel<false, false, 1, false, 2, 3>},
-             {(const void *)pfac_scan_kernel<false, true, 0, false, 2, 3>, (const void *)pfac_scan_kernel<false, true, 1, false, 2, 3>}},
-            {{(const void *)pfac_scan_kernel<true, false, 0, false, 1, 3>, (const void *)pfac_scan_kernel<true, false, 1, false, 1, 3>},
-             {(const void *)pfac_scan_kernel<true, true, 0, false, 1, 3>, (const void *)pfac_scan_kernel<true, true, 1, false, 1, 3>}},
-            {{(const void *)pfac_scan_kernel<false, false, 0, true, FNW, 3>, (const void *)pfac_scan_kernel<false, false, 1, true, FNW, 3>},
-             {(const void *)pfac_scan_kernel<false, true, 0, true, FNW, 3>, (const void *)pfac_scan_kernel<false, true, 1, true, FNW, 3>}}};
-        ctx->kernel3 = k3[ctx->variant == 0 ? 1 : (fused ? 2 : 0)][w8 ? 1 : 0][ctx->root_mode];
-        HIP_TRY(ctx, hipFuncSetAttribute(ctx->kernel3, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds(ctx)));
-    }
+    ctx->kernel3 = scan_kernel<3>(placement, w8, ctx->root_mode);
+    HIP_TRY(ctx, hipFuncSetAttribute(ctx->kernel3, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds(ctx)));
+    // dense mode on fused L2 tables: four walks per lane (needs <= MAX_WAVES_NW4 waves per workgroup)
     if (fused && !knob("PFAC_NO_NW4")) {
-        ctx->kernel_d = k[3][w8 ? 1 : 0][ctx->root_mode];
-        if (!ctx->dense2 && ctx->waves_per_block_d > MAX_WAVES_NW4) {
-            ctx->waves_per_block_d = MAX_WAVES_NW4;
-            ctx->lds_bytes_d = ctx->shared_bytes + (MAX_WAVES_NW4 - 1) * ctx->pw_bytes_d;
-            if (ctx->lds_bytes_d < LDS_TOTAL / 2 + 256) ctx->lds_bytes_d = LDS_TOTAL / 2 + 256;
+        ctx->kernel_d = scan_kernel<2>(3, w8, ctx->root_mode);
+        if (!ctx->dense2 && D.waves_per_block > MAX_WAVES_NW4) {
+            D.waves_per_block = MAX_WAVES_NW4;
+            D.lds_bytes = lds_of_one_block_per_cu(ctx->shared_bytes + (MAX_WAVES_NW4 - 1) * D.pw_bytes);
         }
         HIP_TRY(ctx, hipFuncSetAttribute(ctx->kernel_d, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds(ctx)));
     }
@@ -3657,7 +3745,7 @@ int configure_kernel(pfac_ctx *ctx, const int32_t *s0_host) {
     if (knob("PFAC_VERBOSE"))
         fprintf(stderr, "pfac: variant %d fused %d shared LDS %d B; sparse: %d waves x %d B; dense%s: %d waves x %d B; dense rows %d x %d, %d depth-2 states, level-2 filter mode %d\n",
                 ctx->variant, (int)fused, ctx->shared_bytes, ctx->lay[0].waves_per_block, ctx->lay[0].pw_bytes, ctx->dense2 ? " (second form)" : "",
-                ctx->waves_per_block_d, ctx->pw_bytes_d, ctx->d1_rows, ctx->d1_stride, ctx->d1_n2, ctx->l2f_mode);
+                D.waves_per_block, D.pw_bytes, ctx->d1_rows, ctx->d1_stride, ctx->d1_n2, ctx->l2f_mode);
     return PFAC_OK;
 }
 
@@ -3678,13 +3766,13 @@ int install_table(pfac_ctx *ctx, const int *d_blob, const int32_t *hdr, size_t n
     const size_t total = align_up(off_id + (size_t)num_final * 4, 16) + 16;
     for (auto &sl : ctx->slots)                             // a scan still in flight reads the tables freed below
         if (sl.pending) HIP_TRY(ctx, hipEventSynchronize(sl.ev1));
-    if (ctx->d_tab) { HIP_TRY(ctx, hipFree(ctx->d_tab)); ctx->d_tab = nullptr; }
-    if (ctx->d_flen) { HIP_TRY(ctx, hipFree(ctx->d_flen)); ctx->d_flen = nullptr; }   // the lengths belong to the old table
-    if (ctx->d_rep_off) { HIP_TRY(ctx, hipFree(ctx->d_rep_off)); ctx->d_rep_off = nullptr; }   // ... and so do the replacements
-    if (ctx->d_rep) { HIP_TRY(ctx, hipFree(ctx->d_rep)); ctx->d_rep = nullptr; ctx->rep_size = 0; }
-    HIP_TRY(ctx, hipMalloc((void **)&ctx->d_tab, total));
-    ctx->tab_bytes = total;
-    unsigned char *base = reinterpret_cast<unsigned char *>(ctx->d_tab);
+    ctx->tab.reset();
+    ctx->flen.reset();                                      // the lengths belong to the old table
+    ctx->rep_off.reset();                                   // ... and so do the replacements
+    ctx->rep.reset();
+    int rc = ctx->tab.ensure(ctx, nullptr, total, total);
+    if (rc) return rc;
+    unsigned char *base = ctx->tab.p;
     ctx->d_s0 = reinterpret_cast<int *>(base);
     ctx->d_r = reinterpret_cast<int *>(base + off_r);
     ctx->d_T = reinterpret_cast<int2 *>(base + off_T);
@@ -3745,7 +3833,8 @@ int pfac_ctx_create(int device, int n_streams, pfac_ctx **out) {
         HIP_TRY(ctx, hipHostMalloc((void **)&s.h_ctl, 64, hipHostMallocMapped));
         memset(s.h_ctl, 0, 64);
         HIP_TRY(ctx, hipHostGetDevicePointer((void **)&s.d_res, s.h_ctl, 0));
-        HIP_TRY(ctx, hipMalloc((void **)&s.d_sum, 16));
+        int rc = s.sum.ensure(ctx, nullptr, 2, 2);
+        if (rc) return rc;
         HIP_TRY(ctx, hipEventCreate(&s.ev0));
         HIP_TRY(ctx, hipEventCreate(&s.ev1));
         HIP_TRY(ctx, hipEventCreateWithFlags(&s.ev_h2d, hipEventDisableTiming));
@@ -3759,27 +3848,6 @@ void pfac_ctx_destroy(pfac_ctx *ctx) {
     DeviceGuard device_guard_(ctx->device);
     for (auto &s : ctx->slots) {
         if (s.own_stream) (void)hipStreamSynchronize(s.own_stream);
-        if (s.d_input) (void)hipFree(s.d_input);
-        if (s.d_records) (void)hipFree(s.d_records);
-        if (s.d_ctl) (void)hipFree(s.d_ctl);
-        if (s.d_tile_index) (void)hipFree(s.d_tile_index);
-        if (s.d_d2log) (void)hipFree(s.d_d2log);
-        if (s.d_gsum) (void)hipFree(s.d_gsum);
-        if (s.d_text) (void)hipFree(s.d_text);
-        if (s.d_wide) (void)hipFree(s.d_wide);
-        if (s.d_dbg) (void)hipFree(s.d_dbg);
-        if (s.d_doc_off) (void)hipFree(s.d_doc_off);
-        if (s.d_seg_tcnt) (void)hipFree(s.d_seg_tcnt);
-        if (s.d_seg_out) (void)hipFree(s.d_seg_out);
-        if (s.d_seg_first) (void)hipFree(s.d_seg_first);
-        if (s.d_ll_tmp) (void)hipFree(s.d_ll_tmp);
-        if (s.d_ll_out) (void)hipFree(s.d_ll_out);
-        if (s.d_rp_tmp) (void)hipFree(s.d_rp_tmp);
-        if (s.d_rp_out) (void)hipFree(s.d_rp_out);
-        if (s.d_lld_first) (void)hipFree(s.d_lld_first);
-        if (s.d_rpd_tmp) (void)hipFree(s.d_rpd_tmp);
-        if (s.d_rpd_off) (void)hipFree(s.d_rpd_off);
-        if (s.d_sum) (void)hipFree(s.d_sum);
         if (s.h_ctl) (void)hipHostFree(s.h_ctl);
         if (s.ev0) (void)hipEventDestroy(s.ev0);
         if (s.ev1) (void)hipEventDestroy(s.ev1);
@@ -3787,13 +3855,7 @@ void pfac_ctx_destroy(pfac_ctx *ctx) {
         if (s.own_stream) (void)hipStreamDestroy(s.own_stream);
     }
     if (ctx->copy_stream) { (void)hipStreamSynchronize(ctx->copy_stream); (void)hipStreamDestroy(ctx->copy_stream); }
-    if (ctx->d_tab) (void)hipFree(ctx->d_tab);
-    if (ctx->d_d1) (void)hipFree(ctx->d_d1);
-    if (ctx->d_T4_alloc) (void)hipFree(ctx->d_T4_alloc);
-    if (ctx->d_bm2) (void)hipFree(ctx->d_bm2);
-    if (ctx->d_flen) (void)hipFree(ctx->d_flen);
-    if (ctx->d_rep_off) (void)hipFree(ctx->d_rep_off);
-    if (ctx->d_rep) (void)hipFree(ctx->d_rep);
+    // every device buffer of the slots and the context goes with its DevBuf: the streams are idle, the device guard holds
     delete ctx;
 }
 
@@ -3801,13 +3863,12 @@ int pfac_table_upload(pfac_ctx *ctx, const int32_t *blob, size_t n_words) {
     if (!ctx || !blob || n_words < PFAC_BLOB_HEADER_WORDS) return fail(ctx, PFAC_E_ARG, "bad argument to pfac_table_upload");
     std::lock_guard<std::mutex> lk(ctx->mu);
     USE_DEVICE(ctx);
-    int *d_blob = nullptr;
-    HIP_TRY(ctx, hipMalloc((void **)&d_blob, n_words * 4));
-    hipError_t e = hipMemcpy(d_blob, blob, n_words * 4, hipMemcpyHostToDevice);   // master_kernel.cu:365-383
-    int rc = e == hipSuccess ? install_table(ctx, d_blob, blob, n_words, ctx->slots[0].stream)
-                             : fail(ctx, PFAC_E_HIP, std::string("hipMemcpy(table): ") + hipGetErrorString(e));
-    (void)hipFree(d_blob);
-    return rc;
+    DevBuf<int> d_blob;
+    int rc = d_blob.ensure(ctx, nullptr, n_words, n_words);
+    if (rc) return rc;
+    hipError_t e = hipMemcpy(d_blob.p, blob, n_words * 4, hipMemcpyHostToDevice);   // master_kernel.cu:365-383
+    return e == hipSuccess ? install_table(ctx, d_blob.p, blob, n_words, ctx->slots[0].stream)
+                           : fail(ctx, PFAC_E_HIP, std::string("hipMemcpy(table): ") + hipGetErrorString(e));
 }
 
 int pfac_table_upload_device(pfac_ctx *ctx, const void *d_blob, size_t n_words, void *stream_handle) {
@@ -3850,28 +3911,19 @@ int pfac_slot_reserve(pfac_ctx *ctx, int slot, uint64_t input_bytes, uint64_t re
     // Replacing a buffer the slot already has: whatever the slot's stream and the copy stream still do with the old one
     // finishes first (a pending scan writes the heap and reads the input), and the new, uninitialised buffer holds no
     // scan -- the slot is back to "no finished scan", so nothing reads it as if it held the last one.
-    if ((input_bytes > s.input_cap && s.d_input) || (record_capacity > s.record_cap && s.d_records)) {
+    if ((input_bytes > s.input.cap && s.input.p) || (record_capacity > s.records.cap && s.records.p)) {
         HIP_TRY(ctx, hipStreamSynchronize(s.stream));
         if (s.pending) HIP_TRY(ctx, hipEventSynchronize(s.ev1));       // (the stream may have been swapped under the scan)
         if (s.h2d_issued) HIP_TRY(ctx, hipEventSynchronize(s.ev_h2d));
         s.scanned = s.pending = false;
     }
-    if (input_bytes > s.input_cap) {
-        if (s.d_input) { HIP_TRY(ctx, hipFree(s.d_input)); s.d_input = nullptr; s.input_cap = 0; }
-        const uint64_t cap = align_up(input_bytes, WTILE) + HALO_MAX + 256;
-        HIP_TRY(ctx, hipMalloc((void **)&s.d_input, cap));
-        s.input_cap = cap;
-    }
-    if (record_capacity > s.record_cap) {
-        if (s.d_records) { HIP_TRY(ctx, hipFree(s.d_records)); s.d_records = nullptr; s.record_cap = 0; }
-        HIP_TRY(ctx, hipMalloc((void **)&s.d_records, record_capacity * sizeof(pfac_record)));
-        s.record_cap = record_capacity;
-    }
-    return PFAC_OK;
+    rc = s.input.ensure(ctx, s.stream, input_bytes, align_up(input_bytes, WTILE) + HALO_MAX + 256);
+    if (rc) return rc;
+    return s.records.ensure(ctx, s.stream, record_capacity, record_capacity);
 }
 
-void *pfac_slot_input(pfac_ctx *ctx, int slot) { return check_slot(ctx, slot) ? nullptr : ctx->slots[slot].d_input; }
-void *pfac_slot_records(pfac_ctx *ctx, int slot) { return check_slot(ctx, slot) ? nullptr : ctx->slots[slot].d_records; }
+void *pfac_slot_input(pfac_ctx *ctx, int slot) { return check_slot(ctx, slot) ? nullptr : ctx->slots[slot].input.p; }
+void *pfac_slot_records(pfac_ctx *ctx, int slot) { return check_slot(ctx, slot) ? nullptr : ctx->slots[slot].records.p; }
 void *pfac_slot_stream(pfac_ctx *ctx, int slot) { return check_slot(ctx, slot) ? nullptr : (void *)ctx->slots[slot].stream; }
 
 int pfac_slot_set_stream(pfac_ctx *ctx, int slot, void *stream_handle) {
@@ -3890,12 +3942,12 @@ int pfac_slot_h2d(pfac_ctx *ctx, int slot, const void *host, uint64_t n_bytes, u
     int rc = check_slot(ctx, slot);
     if (rc) return rc;
     Slot &s = ctx->slots[slot];
-    if (!host || dst_offset + n_bytes > s.input_cap) return fail(ctx, PFAC_E_ARG, "pfac_slot_h2d: range exceeds the reserved input buffer");
+    if (!host || dst_offset + n_bytes > s.input.cap) return fail(ctx, PFAC_E_ARG, "pfac_slot_h2d: range exceeds the reserved input buffer");
     USE_DEVICE(ctx);
     // on the context's copy stream, behind whatever the slot's stream still does with the buffer (its last scan reads it);
     // the slot's stream then waits for the copy: same ordering as a copy on the slot's stream, without the gaps
     if (s.scanned) HIP_TRY(ctx, hipStreamWaitEvent(ctx->copy_stream, s.ev1, 0));
-    HIP_TRY(ctx, hipMemcpyAsync(s.d_input + dst_offset, host, n_bytes, hipMemcpyHostToDevice, ctx->copy_stream));
+    HIP_TRY(ctx, hipMemcpyAsync(s.input.p + dst_offset, host, n_bytes, hipMemcpyHostToDevice, ctx->copy_stream));
     HIP_TRY(ctx, hipEventRecord(s.ev_h2d, ctx->copy_stream));
     HIP_TRY(ctx, hipStreamWaitEvent(s.stream, s.ev_h2d, 0));
     s.h2d_issued = true;
@@ -3926,12 +3978,12 @@ int pfac_scan_async(pfac_ctx *ctx, int slot, const void *d_input, uint64_t n_own
     if (rc) return rc;
     if (!ctx->have_table) return fail(ctx, PFAC_E_STATE, "pfac_scan_async before a table upload");
     Slot &s = ctx->slots[slot];
-    const unsigned char *in = d_input ? static_cast<const unsigned char *>(d_input) : s.d_input;
-    if (!d_records) { d_records = s.d_records; capacity = s.record_cap; }
+    const unsigned char *in = d_input ? static_cast<const unsigned char *>(d_input) : s.input.p;
+    if (!d_records) { d_records = s.records.p; capacity = s.records.cap; }
     if (!in) return fail(ctx, PFAC_E_ARG, "pfac_scan_async: no input buffer");
     if (((uintptr_t)in & 15) != 0) return fail(ctx, PFAC_E_ARG, "pfac_scan_async: input pointer must be 16-byte aligned");
     if (n_owned > n_avail || n_owned > (1ull << 32)) return fail(ctx, PFAC_E_ARG, "pfac_scan_async: need n_owned <= n_avail and n_owned <= 2^32");
-    if (!d_input && n_avail > s.input_cap) return fail(ctx, PFAC_E_ARG, "pfac_scan_async: n_avail exceeds the reserved input buffer");
+    if (!d_input && n_avail > s.input.cap) return fail(ctx, PFAC_E_ARG, "pfac_scan_async: n_avail exceeds the reserved input buffer");
     if (((uintptr_t)d_records & 15) != 0) return fail(ctx, PFAC_E_ARG, "pfac_scan_async: record buffer must be 16-byte aligned");
     if (!d_records && capacity) return fail(ctx, PFAC_E_ARG, "pfac_scan_async: no record buffer");
     USE_DEVICE(ctx);
@@ -3942,10 +3994,9 @@ int pfac_scan_async(pfac_ctx *ctx, int slot, const void *d_input, uint64_t n_own
     s.pending = true;
     for (int i = 0; i < 7; i++) s.h_ctl[i] = 0;        // result words (the kernel writes them through the host mapping)
     // staging mode of this launch (see pfac_scan_finish for the adaptation)
-    const bool dense = ctx->dense && ctx->stage_cap_d;
-    const StageLayout &L = ctx->sparse();
-    const int wpb = dense ? ctx->waves_per_block_d : L.waves_per_block;
-    const int lds_bytes = dense ? ctx->lds_bytes_d : L.lds_bytes;
+    const bool dense = ctx->run_dense();
+    const StageLayout &L = ctx->layout(dense);
+    const int wpb = L.waves_per_block;
     s.last_dense = dense;
     s.last_tiles = n_tiles;
     s.last_owned = n_owned;
@@ -3958,7 +4009,7 @@ int pfac_scan_async(pfac_ctx *ctx, int slot, const void *d_input, uint64_t n_own
     // zeroes, in its own prologue, the other one for the scan after it, so back-to-back scans need no memset.
     rc = ensure_ctl(ctx, s);
     if (rc) return rc;
-    rc = ensure_tiles(ctx, s, n_tiles + 1);
+    rc = s.tile_index.ensure(ctx, s.stream, n_tiles + 1, quarter_more(n_tiles + 1));
     if (rc) return rc;
     const uint64_t n_batches = (n_tiles + wpb - 2) / (wpb - 1);
     unsigned *const cur = s.d_ctlbuf[s.flip], *const nxt = s.d_ctlbuf[1 - s.flip];
@@ -3968,39 +4019,36 @@ int pfac_scan_async(pfac_ctx *ctx, int slot, const void *d_input, uint64_t n_own
         ScanArgs a;
         a.in = in; a.n_owned = n_owned; a.n_avail = n_avail;
         a.out = d_records; a.out_cap = capacity;
-        a.tile_index = s.d_tile_index;
+        a.tile_index = s.tile_index.p;
         a.rec_bytes = (unsigned)ctx->rec_bytes;
         a.l2f_mode = ctx->l2f_mode; a.child0 = ctx->child0; a.child1 = ctx->child1; a.n_child = ctx->n_child;
-        a.bm2 = ctx->d_bm2; a.bm2_rows = ctx->bm2_rows; a.sh_bm2 = ctx->sh_bm2; a.sh_t0 = ctx->sh_t0;
-        a.sec2 = ctx->d_bm2 + 256 * 32; a.sec_filter = ctx->sec_filter;
+        a.bm2 = ctx->bm2.p; a.bm2_rows = ctx->bm2_rows; a.sh_bm2 = ctx->sh_bm2; a.sh_t0 = ctx->sh_t0;
+        a.sec2 = ctx->bm2.p + 256 * 32; a.sec_filter = ctx->sec_filter;
         a.spin_max = ctx->spin_max; a.fault = ctx->fault;
-        a.s0 = ctx->d_s0; a.r = ctx->d_r; a.T = ctx->d_T; a.T4 = ctx->d_T4_alloc; a.rn_bias = ctx->rn_bias;
+        a.s0 = ctx->d_s0; a.r = ctx->d_r; a.T = ctx->d_T; a.T4 = ctx->T4_alloc.p; a.rn_bias = ctx->rn_bias;
         a.r_words = ctx->max_row; a.t_entries = ctx->ht_size;
         a.ht_size = ctx->ht_size; a.wbit = ctx->width_bit; a.num_final = ctx->num_final;
         a.halo = ctx->halo;
-        a.shared_bytes = ctx->shared_bytes; a.pw_bytes = dense ? ctx->pw_bytes_d : L.pw_bytes;
-        a.d1 = ctx->d_d1; a.d1_rows = ctx->d1_rows; a.d1_stride = ctx->d1_stride; a.d1_ncols = ctx->d1_ncols; a.d1_lds_bytes = ctx->d1_lds_bytes;
-        a.d1_colmap = ctx->d_d1 ? reinterpret_cast<const unsigned char *>(ctx->d_d1) + d1_off_col(ctx->d1_rows) : nullptr;
+        a.shared_bytes = ctx->shared_bytes; a.pw_bytes = L.pw_bytes;
+        a.d1 = ctx->d1.p; a.d1_rows = ctx->d1_rows; a.d1_stride = ctx->d1_stride; a.d1_ncols = ctx->d1_ncols; a.d1_lds_bytes = ctx->d1_lds_bytes;
+        a.d1_colmap = ctx->d1.p ? reinterpret_cast<const unsigned char *>(ctx->d1.p) + d1_off_col(ctx->d1_rows) : nullptr;
         a.d1_colbyte = a.d1_colmap ? a.d1_colmap + 256 : nullptr;
         a.d1_n2 = ctx->d1_n2;
-        a.d1r2 = ctx->d1_n2 ? reinterpret_cast<const int2 *>(reinterpret_cast<const unsigned char *>(ctx->d_d1) + d1_off_r2(ctx->d1_rows))
+        a.d1r2 = ctx->d1_n2 ? reinterpret_cast<const int2 *>(reinterpret_cast<const unsigned char *>(ctx->d1.p) + d1_off_r2(ctx->d1_rows))
                             : nullptr;
-        a.d1idx = ctx->d_d1 ? reinterpret_cast<const unsigned char *>(ctx->d_d1) + (size_t)ctx->d1_rows * 1024 : nullptr;
+        a.d1idx = ctx->d1.p ? reinterpret_cast<const unsigned char *>(ctx->d1.p) + (size_t)ctx->d1_rows * 1024 : nullptr;
         a.root_byte = ctx->root_byte;
         a.root_state = ctx->root_state;
-        a.stage_cap = dense ? ctx->stage_cap_d : L.stage_cap;
-        a.nbuf = dense ? 1u : (unsigned)L.nbuf;
+        a.stage_cap = L.stage_cap;
+        a.nbuf = (unsigned)L.nbuf;
         a.dense2 = dense && ctx->dense2 ? 1 : 0;
         a.d2log = nullptr; a.d2log_cap = ctx->d2log_cap;
         if (a.dense2) {
             a.stage_cap = 0;                   // (its LDS carve has no staging buffer: a tile it gives up on is counted, then written directly)
             const size_t words = (size_t)ctx->grid_blocks * (size_t)(wpb - 1) * ctx->d2log_cap;
-            if (s.d2log_words < words) {
-                if (s.d_d2log) { HIP_TRY(ctx, hipStreamSynchronize(s.stream)); HIP_TRY(ctx, hipFree(s.d_d2log)); s.d_d2log = nullptr; s.d2log_words = 0; }
-                HIP_TRY(ctx, hipMalloc((void **)&s.d_d2log, words * 4));
-                s.d2log_words = words;
-            }
-            a.d2log = s.d_d2log;
+            rc = s.d2log.ensure(ctx, s.stream, words, words);
+            if (rc) return rc;
+            a.d2log = s.d2log.p;
         }
         a.sparse_cap = ctx->lay[0].stage_cap;
         a.small_cap = ctx->lag2_ok ? ctx->lay[1].stage_cap : ctx->lay[0].stage_cap;
@@ -4012,9 +4060,10 @@ int pfac_scan_async(pfac_ctx *ctx, int slot, const void *d_input, uint64_t n_own
         a.dbg = nullptr;
 #ifdef PFAC_TRACE_BUILD
         if (!ctx->trace_file.empty()) {
-            if (!s.d_dbg) HIP_TRY(ctx, hipMalloc((void **)&s.d_dbg, 8 * 64 * 32 * 8));
-            HIP_TRY(ctx, hipMemsetAsync(s.d_dbg, 0, 8 * 64 * 32 * 8, s.stream));
-            a.dbg = s.d_dbg;
+            rc = s.dbg.ensure(ctx, s.stream, 8 * 64 * 32, 8 * 64 * 32);
+            if (rc) return rc;
+            HIP_TRY(ctx, hipMemsetAsync(s.dbg.p, 0, 8 * 64 * 32 * 8, s.stream));
+            a.dbg = s.dbg.p;
         }
 #endif
         const uint64_t want = n_batches;
@@ -4031,7 +4080,7 @@ int pfac_scan_async(pfac_ctx *ctx, int slot, const void *d_input, uint64_t n_own
         // the slot's two events ride on the dispatch itself (start / stop of THIS kernel): no barrier packets of their own
         // in front of and behind every scan
         HIP_TRY(ctx, hipExtLaunchKernel(dense ? ctx->kernel_d : (ctx->lag2 ? ctx->kernel3 : ctx->kernel), dim3((unsigned)grid),
-                                        dim3(WAVE * wpb), kargs, (size_t)lds_bytes, s.stream, s.ev0, s.ev1, 0));
+                                        dim3(WAVE * wpb), kargs, (size_t)L.lds_bytes, s.stream, s.ev0, s.ev1, 0));
         s.clean[s.flip] = false;               // used by this scan
         s.clean[1 - s.flip] = true;            // zeroed by this scan
         s.flip = 1 - s.flip;
@@ -4050,14 +4099,14 @@ int pfac_scan_finish(pfac_ctx *ctx, int slot, uint64_t *n_matches) {
     // its scan -- enqueued after this one -- should keep the GPU busy while the host reads this result
     HIP_TRY(ctx, hipEventSynchronize(s.ev1));
     s.pending = false;
-    const uint64_t total = ((uint64_t)s.h_ctl[1] << 32) | s.h_ctl[0];
+    const uint64_t total = host_u64(s, H_MATCHES);
     s.last_total = total;
-    s.last_used = ((uint64_t)s.h_ctl[5] << 32) | s.h_ctl[4];
+    s.last_used = host_u64(s, H_USED);
     if (n_matches) *n_matches = total;
 #ifdef PFAC_TRACE_BUILD
-    if (s.d_dbg && !ctx->trace_file.empty()) {
+    if (s.dbg.p && !ctx->trace_file.empty()) {
         std::vector<unsigned long long> h(8 * 64 * 32);
-        if (hipMemcpy(h.data(), s.d_dbg, h.size() * 8, hipMemcpyDeviceToHost) == hipSuccess) {
+        if (hipMemcpy(h.data(), s.dbg.p, h.size() * 8, hipMemcpyDeviceToHost) == hipSuccess) {
             if (FILE *f = fopen(ctx->trace_file.c_str(), "wb")) { fwrite(h.data(), 8, h.size(), f); fclose(f); }
         }
     }
@@ -4072,7 +4121,7 @@ int pfac_scan_finish(pfac_ctx *ctx, int slot, uint64_t *n_matches) {
     // when fewer than 1/16 do.  PFAC_DENSE=0/1 pins the mode.  Likewise between the three- and the two-buffer layout,
     // on the tiles above the (smaller) three-buffer capacity: 1/16 of the tiles walked twice cost what the earlier
     // emission gains.  PFAC_LAG=1/2 pins that.
-    if (ctx->dense_forced < 0 && ctx->stage_cap_d && s.last_tiles >= 64) {
+    if (ctx->dense_forced < 0 && ctx->lay_d.stage_cap && s.last_tiles >= 64) {
         const uint64_t ovf = s.h_ctl[3];
         if (!ctx->dense && ovf * 4 > s.last_tiles) ctx->dense = true;
         else if (ctx->dense && ovf * 16 < s.last_tiles) ctx->dense = false;
@@ -4101,32 +4150,24 @@ int pfac_scan_elapsed_ms(pfac_ctx *ctx, int slot, float *ms) {
 
 // Records [first, first+n) of the slot's last scan, in (position, pattern length) order -> pfac_record at d_out
 // (device), on the slot's stream: prefix over the tile index, then a copy out of the heap.
-static int ensure_gsum(pfac_ctx *ctx, Slot &s, unsigned n_groups) {       // n_groups prefixes + the grand total behind them
-    if ((uint64_t)n_groups + 1 <= s.gsum_cap) return PFAC_OK;
-    if (s.d_gsum) { HIP_TRY(ctx, hipStreamSynchronize(s.stream)); HIP_TRY(ctx, hipFree(s.d_gsum)); s.d_gsum = nullptr; }
-    const uint64_t cap = n_groups < 4096 ? 4097 : (uint64_t)n_groups + n_groups / 4 + 1;
-    HIP_TRY(ctx, hipMalloc((void **)&s.d_gsum, cap * 8));
-    s.gsum_cap = cap;
-    return PFAC_OK;
-}
-
 static int expand_records(pfac_ctx *ctx, Slot &s, const void *src, uint64_t first, uint64_t n, pfac_record *d_out) {
     // records that do not exist, or that the last scan could not write, are never delivered as if they did: the copy
     // kernel skips them and the caller would read whatever its buffer held before
     if (s.pending) return fail(ctx, PFAC_E_STATE, "records requested before pfac_scan_finish");
     if (first + n > s.last_total) return fail(ctx, PFAC_E_ARG, "records [first, first + n) exceed the scan's match count");
-    if (s.last_used > s.last_cap) return fail(ctx, PFAC_E_OVERFLOW, "the slot's last scan overflowed its record heap: scan again with a larger one");
+    int rc = last_scan_usable(ctx, s, "", SCAN_FITS);
+    if (rc) return rc;
     if (n == 0 || s.last_tiles == 0) return PFAC_OK;
     const unsigned n_groups = (unsigned)((s.last_tiles + XGROUP - 1) / XGROUP);
-    int rc = ensure_gsum(ctx, s, n_groups);
+    rc = ensure_gsum(ctx, s, n_groups);
     if (rc) return rc;
     const unsigned gblocks = (n_groups + 3) / 4;           // four waves (groups) per 256-thread block
-    hipLaunchKernelGGL(pfac_tix_group_sum_kernel, dim3(gblocks), dim3(256), 0, s.stream, s.d_tile_index,
-                       (unsigned long long)s.last_tiles, s.d_gsum, n_groups);
-    hipLaunchKernelGGL(pfac_scan_groups_kernel, dim3(1), dim3(1024), 0, s.stream, s.d_gsum, n_groups);
-    auto ek = s.last_rec_bytes == 2 ? pfac_expand_kernel<2> : (s.last_rec_bytes == 4 ? pfac_expand_kernel<4> : pfac_expand_kernel<8>);
-    hipLaunchKernelGGL(ek, dim3(gblocks), dim3(256), 0, s.stream, src, s.d_tile_index, (unsigned long long)s.last_tiles,
-                       s.d_gsum, n_groups, (unsigned long long)s.last_cap, (unsigned long long)first, (unsigned long long)n, d_out);
+    hipLaunchKernelGGL(pfac_tix_group_sum_kernel, dim3(gblocks), dim3(256), 0, s.stream, s.tile_index.p,
+                       (unsigned long long)s.last_tiles, s.gsum.p, n_groups);
+    hipLaunchKernelGGL(pfac_scan_groups_kernel, dim3(1), dim3(1024), 0, s.stream, s.gsum.p, n_groups);
+    auto ek = by_width(s.last_rec_bytes, [](auto w) { return pfac_expand_kernel<w()>; });
+    hipLaunchKernelGGL(ek, dim3(gblocks), dim3(256), 0, s.stream, src, s.tile_index.p, (unsigned long long)s.last_tiles,
+                       s.gsum.p, n_groups, (unsigned long long)s.last_cap, (unsigned long long)first, (unsigned long long)n, d_out);
     HIP_TRY(ctx, hipGetLastError());
     return PFAC_OK;
 }
@@ -4158,7 +4199,7 @@ int pfac_records_expand(pfac_ctx *ctx, int slot, const void *d_records, uint64_t
     int rc = check_slot(ctx, slot);
     if (rc) return rc;
     Slot &s = ctx->slots[slot];
-    const void *src = d_records ? d_records : s.d_records;
+    const void *src = d_records ? d_records : s.records.p;
     if (!s.scanned) return fail(ctx, PFAC_E_STATE, "pfac_records_expand without a scan");
     if (!src || (!d_out && n) || ((uintptr_t)d_out & 7)) return fail(ctx, PFAC_E_ARG, "pfac_records_expand: bad buffer");
     USE_DEVICE(ctx);
@@ -4169,19 +4210,16 @@ int pfac_records_d2h(pfac_ctx *ctx, int slot, const void *d_records, pfac_record
     int rc = check_slot(ctx, slot);
     if (rc) return rc;
     Slot &s = ctx->slots[slot];
-    const void *src = d_records ? d_records : s.d_records;
+    const void *src = d_records ? d_records : s.records.p;
     if (n == 0) return PFAC_OK;
     if (!s.scanned) return fail(ctx, PFAC_E_STATE, "pfac_records_d2h without a scan");
     if (!src || !host) return fail(ctx, PFAC_E_ARG, "pfac_records_d2h: null buffer");
     USE_DEVICE(ctx);
-    if (n > s.wide_cap) {
-        if (s.d_wide) { HIP_TRY(ctx, hipStreamSynchronize(s.stream)); HIP_TRY(ctx, hipFree(s.d_wide)); s.d_wide = nullptr; s.wide_cap = 0; }
-        HIP_TRY(ctx, hipMalloc((void **)&s.d_wide, n * sizeof(pfac_record)));
-        s.wide_cap = n;
-    }
-    rc = expand_records(ctx, s, src, first, n, s.d_wide);
+    rc = s.wide.ensure(ctx, s.stream, n, n);
     if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(host, s.d_wide, n * sizeof(pfac_record), hipMemcpyDeviceToHost, s.stream));
+    rc = expand_records(ctx, s, src, first, n, s.wide.p);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(host, s.wide.p, n * sizeof(pfac_record), hipMemcpyDeviceToHost, s.stream));
     return PFAC_OK;
 }
 
@@ -4190,13 +4228,13 @@ int pfac_records_d2h_packed(pfac_ctx *ctx, int slot, const void *d_records, void
     int rc = check_slot(ctx, slot);
     if (rc) return rc;
     Slot &s = ctx->slots[slot];
-    const void *src = d_records ? d_records : s.d_records;
+    const void *src = d_records ? d_records : s.records.p;
     if (!s.scanned || s.last_rec_bytes == 8) return fail(ctx, PFAC_E_STATE, "pfac_records_d2h_packed: the slot's last scan did not produce compact records");
     if (!src || (!host_words && n_words) || !host_tile_index) return fail(ctx, PFAC_E_ARG, "pfac_records_d2h_packed: null buffer");
     if (n_words > s.last_cap) return fail(ctx, PFAC_E_ARG, "pfac_records_d2h_packed: more words than the record array holds");
     USE_DEVICE(ctx);
     if (n_words) HIP_TRY(ctx, hipMemcpyAsync(host_words, src, n_words * (uint64_t)s.last_rec_bytes, hipMemcpyDeviceToHost, s.stream));
-    if (s.last_tiles) HIP_TRY(ctx, hipMemcpyAsync(host_tile_index, s.d_tile_index, s.last_tiles * 8, hipMemcpyDeviceToHost, s.stream));
+    if (s.last_tiles) HIP_TRY(ctx, hipMemcpyAsync(host_tile_index, s.tile_index.p, s.last_tiles * 8, hipMemcpyDeviceToHost, s.stream));
     return PFAC_OK;
 }
 
@@ -4205,15 +4243,16 @@ int pfac_records_packed_device(pfac_ctx *ctx, int slot, const void *d_records, v
     int rc = check_slot(ctx, slot);
     if (rc) return rc;
     Slot &s = ctx->slots[slot];
-    const void *src = d_records ? d_records : s.d_records;
+    const void *src = d_records ? d_records : s.records.p;
     if (!s.scanned || s.pending || s.last_rec_bytes == 8) return fail(ctx, PFAC_E_STATE, "pfac_records_packed_device: the slot's last finished scan did not produce compact records");
-    if (s.last_used > s.last_cap) return fail(ctx, PFAC_E_OVERFLOW, "the slot's last scan overflowed its record heap: scan again with a larger one");
+    rc = last_scan_usable(ctx, s, "", SCAN_FITS);
+    if (rc) return rc;
     if (!d_tile_index_out || (d_words_out && !src)) return fail(ctx, PFAC_E_ARG, "pfac_records_packed_device: null buffer");
     if (n_words > s.last_cap) return fail(ctx, PFAC_E_ARG, "pfac_records_packed_device: more words than the record array holds");
     USE_DEVICE(ctx);
     if (d_words_out && n_words && d_words_out != src)
         HIP_TRY(ctx, hipMemcpyAsync(d_words_out, src, n_words * (uint64_t)s.last_rec_bytes, hipMemcpyDeviceToDevice, s.stream));
-    if (s.last_tiles) HIP_TRY(ctx, hipMemcpyAsync(d_tile_index_out, s.d_tile_index, s.last_tiles * 8, hipMemcpyDeviceToDevice, s.stream));
+    if (s.last_tiles) HIP_TRY(ctx, hipMemcpyAsync(d_tile_index_out, s.tile_index.p, s.last_tiles * 8, hipMemcpyDeviceToDevice, s.stream));
     return PFAC_OK;
 }
 
@@ -4224,10 +4263,9 @@ int pfac_emit_text_device(pfac_ctx *ctx, int slot, const void *d_records, uint64
     *n_bytes = 0;
     if (!ctx->have_table) return fail(ctx, PFAC_E_STATE, "no table uploaded");
     Slot &s = ctx->slots[slot];
-    const void *src = d_records ? d_records : s.d_records;
-    if (!s.scanned || s.pending) return fail(ctx, PFAC_E_STATE, "pfac_emit_text_device needs a finished scan");
-    if (s.last_table != ctx->table_gen) return fail(ctx, PFAC_E_STATE, "pfac_emit_text_device: the slot's last scan ran with an earlier table (its states index that table's idmap)");
-    if (s.last_used > s.last_cap) return fail(ctx, PFAC_E_OVERFLOW, "the slot's last scan overflowed its record heap: scan again with a larger one");
+    const void *src = d_records ? d_records : s.records.p;
+    rc = last_scan_usable(ctx, s, "pfac_emit_text_device", SCAN_FINISHED | SCAN_IDMAP | SCAN_FITS);
+    if (rc) return rc;
     if (base + (1ull << 32) >= 1000000000000000000ull) return fail(ctx, PFAC_E_ARG, "pfac_emit_text_device: positions must stay below 10^18");
     s.text_bytes = 0;
     if (s.last_total == 0 || s.last_tiles == 0) return PFAC_OK;
@@ -4237,23 +4275,19 @@ int pfac_emit_text_device(pfac_ctx *ctx, int slot, const void *d_records, uint64
     rc = ensure_gsum(ctx, s, n_groups);
     if (rc) return rc;
     const unsigned gblocks = (n_groups + 3) / 4;           // four waves (groups of 64 tiles) per 256-thread block
-    auto sk = s.last_rec_bytes == 2 ? pfac_text_size_kernel<2> : (s.last_rec_bytes == 4 ? pfac_text_size_kernel<4> : pfac_text_size_kernel<8>);
-    hipLaunchKernelGGL(sk, dim3(gblocks), dim3(256), 0, s.stream, src, s.d_tile_index, (unsigned long long)s.last_tiles,
-                       (unsigned long long)s.last_cap, (unsigned long long)base, ctx->d_idmap, s.d_gsum, n_groups);
-    hipLaunchKernelGGL(pfac_scan_groups_kernel, dim3(1), dim3(1024), 0, s.stream, s.d_gsum, n_groups);
+    auto sk = by_width(s.last_rec_bytes, [](auto w) { return pfac_text_size_kernel<w()>; });
+    hipLaunchKernelGGL(sk, dim3(gblocks), dim3(256), 0, s.stream, src, s.tile_index.p, (unsigned long long)s.last_tiles,
+                       (unsigned long long)s.last_cap, (unsigned long long)base, ctx->d_idmap, s.gsum.p, n_groups);
+    hipLaunchKernelGGL(pfac_scan_groups_kernel, dim3(1), dim3(1024), 0, s.stream, s.gsum.p, n_groups);
     HIP_TRY(ctx, hipGetLastError());
     unsigned long long total = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&total, s.d_gsum + n_groups, 8, hipMemcpyDeviceToHost, s.stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&total, s.gsum.p + n_groups, 8, hipMemcpyDeviceToHost, s.stream));
     HIP_TRY(ctx, hipStreamSynchronize(s.stream));
-    if (total + 32 > s.text_cap) {
-        if (s.d_text) { HIP_TRY(ctx, hipFree(s.d_text)); s.d_text = nullptr; s.text_cap = 0; }
-        const uint64_t cap = total + total / 8 + 4096;
-        HIP_TRY(ctx, hipMalloc((void **)&s.d_text, cap));
-        s.text_cap = cap;
-    }
-    auto fk = s.last_rec_bytes == 2 ? pfac_text_format_kernel<2> : (s.last_rec_bytes == 4 ? pfac_text_format_kernel<4> : pfac_text_format_kernel<8>);
-    hipLaunchKernelGGL(fk, dim3(gblocks), dim3(256), 0, s.stream, src, s.d_tile_index, (unsigned long long)s.last_tiles,
-                       (unsigned long long)s.last_cap, (unsigned long long)base, ctx->d_idmap, s.d_gsum, n_groups, s.d_text);
+    rc = s.text.ensure(ctx, s.stream, total + 32, total + total / 8 + 4096);
+    if (rc) return rc;
+    auto fk = by_width(s.last_rec_bytes, [](auto w) { return pfac_text_format_kernel<w()>; });
+    hipLaunchKernelGGL(fk, dim3(gblocks), dim3(256), 0, s.stream, src, s.tile_index.p, (unsigned long long)s.last_tiles,
+                       (unsigned long long)s.last_cap, (unsigned long long)base, ctx->d_idmap, s.gsum.p, n_groups, s.text.p);
     HIP_TRY(ctx, hipGetLastError());
     s.text_bytes = total;
     *n_bytes = total;
@@ -4268,11 +4302,11 @@ int pfac_text_d2h(pfac_ctx *ctx, int slot, void *host, uint64_t first, uint64_t 
     if (n == 0) return PFAC_OK;
     if (!host) return fail(ctx, PFAC_E_ARG, "null buffer");
     USE_DEVICE(ctx);
-    HIP_TRY(ctx, hipMemcpyAsync(host, s.d_text + first, n, hipMemcpyDeviceToHost, s.stream));
+    HIP_TRY(ctx, hipMemcpyAsync(host, s.text.p + first, n, hipMemcpyDeviceToHost, s.stream));
     return PFAC_OK;
 }
 
-void *pfac_slot_text(pfac_ctx *ctx, int slot) { return check_slot(ctx, slot) ? nullptr : ctx->slots[slot].d_text; }
+void *pfac_slot_text(pfac_ctx *ctx, int slot) { return check_slot(ctx, slot) ? nullptr : ctx->slots[slot].text.p; }
 
 int pfac_slot_sync(pfac_ctx *ctx, int slot) {
     int rc = check_slot(ctx, slot);
@@ -4289,22 +4323,21 @@ int pfac_records_checksum(pfac_ctx *ctx, int slot, const void *d_records, uint64
     if (!checksum) return fail(ctx, PFAC_E_ARG, "null argument");
     if (!ctx->have_table) return fail(ctx, PFAC_E_STATE, "no table uploaded");
     Slot &s = ctx->slots[slot];
-    const void *src = d_records ? d_records : s.d_records;
-    if (n && (!s.scanned || s.pending)) return fail(ctx, PFAC_E_STATE, "pfac_records_checksum needs a finished scan");
-    if (n && s.last_table != ctx->table_gen) return fail(ctx, PFAC_E_STATE, "pfac_records_checksum: the slot's last scan ran with an earlier table (its states index that table's idmap)");
-    if (n && s.last_used > s.last_cap) return fail(ctx, PFAC_E_OVERFLOW, "the slot's last scan overflowed its record heap: scan again with a larger one");
+    const void *src = d_records ? d_records : s.records.p;
+    rc = n ? last_scan_usable(ctx, s, "pfac_records_checksum", SCAN_FINISHED | SCAN_IDMAP | SCAN_FITS) : PFAC_OK;
+    if (rc) return rc;
     if (!src && n) return fail(ctx, PFAC_E_ARG, "null record buffer");
     USE_DEVICE(ctx);
-    HIP_TRY(ctx, hipMemsetAsync(s.d_sum, 0, 16, s.stream));
+    HIP_TRY(ctx, hipMemsetAsync(s.sum.p, 0, 16, s.stream));
     if (n && s.last_tiles) {
-        auto ck = s.last_rec_bytes == 2 ? pfac_checksum_kernel<2> : (s.last_rec_bytes == 4 ? pfac_checksum_kernel<4> : pfac_checksum_kernel<8>);
-        hipLaunchKernelGGL(ck, dim3(1024), dim3(256), 0, s.stream, src, s.d_tile_index, (unsigned long long)s.last_tiles,
-                           (unsigned long long)s.last_cap, (unsigned long long)base, ctx->d_idmap, s.d_sum);
+        auto ck = by_width(s.last_rec_bytes, [](auto w) { return pfac_checksum_kernel<w()>; });
+        hipLaunchKernelGGL(ck, dim3(1024), dim3(256), 0, s.stream, src, s.tile_index.p, (unsigned long long)s.last_tiles,
+                           (unsigned long long)s.last_cap, (unsigned long long)base, ctx->d_idmap, s.sum.p);
         HIP_TRY(ctx, hipGetLastError());
     }
-    HIP_TRY(ctx, hipMemcpyAsync(s.h_ctl + 8, s.d_sum, 8, hipMemcpyDeviceToHost, s.stream));
+    HIP_TRY(ctx, hipMemcpyAsync(s.h_ctl + H_CHECKSUM, s.sum.p, 8, hipMemcpyDeviceToHost, s.stream));
     HIP_TRY(ctx, hipStreamSynchronize(s.stream));
-    *checksum = ((uint64_t)s.h_ctl[9] << 32) | s.h_ctl[8];
+    *checksum = host_u64(s, H_CHECKSUM);
     return PFAC_OK;
 }
 
@@ -4320,8 +4353,9 @@ int pfac_table_set_final_lengths(pfac_ctx *ctx, const int32_t *len, size_t n) {
         h[i] = (short)len[i];
     }
     USE_DEVICE(ctx);
-    if (!ctx->d_flen) HIP_TRY(ctx, hipMalloc((void **)&ctx->d_flen, h.size() * sizeof(short)));
-    HIP_TRY(ctx, hipMemcpy(ctx->d_flen, h.data(), h.size() * sizeof(short), hipMemcpyHostToDevice));
+    int rc = ctx->flen.ensure(ctx, nullptr, h.size(), h.size());
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpy(ctx->flen.p, h.data(), h.size() * sizeof(short), hipMemcpyHostToDevice));
     return PFAC_OK;
 }
 
@@ -4332,13 +4366,9 @@ int pfac_slot_doc_offsets(pfac_ctx *ctx, int slot, const uint64_t *host_offsets,
     Slot &s = ctx->slots[slot];
     USE_DEVICE(ctx);
     s.doc_set = false;
-    if (n_docs + 1 > s.doc_off_cap) {
-        if (s.d_doc_off) { HIP_TRY(ctx, hipStreamSynchronize(s.stream)); HIP_TRY(ctx, hipFree(s.d_doc_off)); s.d_doc_off = nullptr; s.doc_off_cap = 0; }
-        const uint64_t cap = n_docs + 1 < 4096 ? 4096 : n_docs + 1 + n_docs / 4;
-        HIP_TRY(ctx, hipMalloc((void **)&s.d_doc_off, cap * 8));
-        s.doc_off_cap = cap;
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(s.d_doc_off, host_offsets, (n_docs + 1) * 8, hipMemcpyHostToDevice, s.stream));
+    rc = ensure_docs(ctx, s, s.doc_off, n_docs);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(s.doc_off.p, host_offsets, (n_docs + 1) * 8, hipMemcpyHostToDevice, s.stream));
     HIP_TRY(ctx, hipStreamSynchronize(s.stream));        // (the caller's array may go once this returns)
     s.doc_n = n_docs;
     s.doc_set = true;
@@ -4354,72 +4384,50 @@ int pfac_records_segment(pfac_ctx *ctx, int slot, const void *d_records, const u
     *n_kept = 0;
     Slot &s = ctx->slots[slot];
     s.seg_done = false;
-    if (!s.scanned || s.pending) return fail(ctx, PFAC_E_STATE, "pfac_records_segment needs a finished scan");
-    if (!ctx->have_table || !ctx->d_flen) return fail(ctx, PFAC_E_STATE, "pfac_records_segment: no final-state lengths for the uploaded table (pfac_table_set_final_lengths)");
-    if (s.last_table != ctx->table_gen) return fail(ctx, PFAC_E_STATE, "pfac_records_segment: the slot's last scan ran with an earlier table");
-    if (s.last_used > s.last_cap) return fail(ctx, PFAC_E_OVERFLOW, "the slot's last scan overflowed its record heap: scan again with a larger one");
-    const void *src = d_records ? d_records : s.d_records;
-    const unsigned long long *off = reinterpret_cast<const unsigned long long *>(d_doc_offsets);
-    if (!off) {
-        if (!s.doc_set) return fail(ctx, PFAC_E_STATE, "pfac_records_segment: no document offsets for the slot (pfac_slot_doc_offsets)");
-        if (n_docs != s.doc_n) return fail(ctx, PFAC_E_ARG, "pfac_records_segment: n_docs differs from the slot's document offsets");
-        off = s.d_doc_off;
-    }
-    if (n_docs >= (1ull << 32)) return fail(ctx, PFAC_E_ARG, "pfac_records_segment: n_docs must be below 2^32");
-    if (n_docs == 0 && s.last_owned != 0) return fail(ctx, PFAC_E_ARG, "pfac_records_segment: no documents, but the scan owns bytes");
-    if (((uintptr_t)off & 7) || ((uintptr_t)d_out & 7) || ((uintptr_t)d_doc_first & 7))
-        return fail(ctx, PFAC_E_ARG, "pfac_records_segment: device buffers must be 8-byte aligned");
+    const std::string fn = "pfac_records_segment";
+    rc = last_scan_usable(ctx, s, fn, SCAN_FINISHED | SCAN_LENGTHS | SCAN_TABLE | SCAN_FITS);
+    if (rc) return rc;
+    const void *src = d_records ? d_records : s.records.p;
+    const unsigned long long *off;
+    rc = resolve_docs(ctx, s, fn, d_doc_offsets, n_docs, (uintptr_t)d_out | (uintptr_t)d_doc_first, &off);
+    if (rc) return rc;
     if (!src && s.last_tiles) return fail(ctx, PFAC_E_ARG, "null record buffer");
     USE_DEVICE(ctx);
     const uint64_t n_tiles = s.last_tiles;
     const unsigned n_groups = (unsigned)((n_tiles + XGROUP - 1) / XGROUP);
     rc = ensure_gsum(ctx, s, n_groups + 1);                 // group prefixes, the total, the offsets' error flag
     if (rc) return rc;
-    if (n_tiles > s.seg_tcnt_cap) {
-        if (s.d_seg_tcnt) { HIP_TRY(ctx, hipStreamSynchronize(s.stream)); HIP_TRY(ctx, hipFree(s.d_seg_tcnt)); s.d_seg_tcnt = nullptr; s.seg_tcnt_cap = 0; }
-        const uint64_t cap = n_tiles < 4096 ? 4096 : n_tiles + n_tiles / 4;
-        HIP_TRY(ctx, hipMalloc((void **)&s.d_seg_tcnt, cap * 4));
-        s.seg_tcnt_cap = cap;
-    }
-    HIP_TRY(ctx, hipMemsetAsync(s.d_gsum + n_groups, 0, 16, s.stream));
+    rc = s.seg_tcnt.ensure(ctx, s.stream, n_tiles, quarter_more(n_tiles));
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemsetAsync(s.gsum.p + n_groups, 0, 16, s.stream));
     // count (and check the offsets): four groups per 256-thread block, at least one thread per document up to a cap
     const uint64_t gblocks = (n_groups + 3) / 4, vblocks = (n_docs + 255) / 256;
     const unsigned cblocks = (unsigned)std::max<uint64_t>(1, std::max<uint64_t>(gblocks, std::min<uint64_t>(vblocks, 4096)));
     const int rb = s.last_rec_bytes;
-    auto ck = rb == 2 ? pfac_seg_count_kernel<2> : (rb == 4 ? pfac_seg_count_kernel<4> : pfac_seg_count_kernel<8>);
-    hipLaunchKernelGGL(ck, dim3(cblocks), dim3(256), 0, s.stream, src, s.d_tile_index, (unsigned long long)n_tiles,
+    auto ck = by_width(rb, [](auto w) { return pfac_seg_count_kernel<w()>; });
+    hipLaunchKernelGGL(ck, dim3(cblocks), dim3(256), 0, s.stream, src, s.tile_index.p, (unsigned long long)n_tiles,
                        (unsigned long long)s.last_cap, off, (unsigned long long)n_docs, (unsigned long long)s.last_owned,
-                       ctx->d_flen, (unsigned)ctx->num_final, s.d_seg_tcnt, s.d_gsum, n_groups, s.d_gsum + n_groups + 1);
-    if (n_groups) hipLaunchKernelGGL(pfac_scan_groups_kernel, dim3(1), dim3(1024), 0, s.stream, s.d_gsum, n_groups);
+                       ctx->flen.p, (unsigned)ctx->num_final, s.seg_tcnt.p, s.gsum.p, n_groups, s.gsum.p + n_groups + 1);
+    if (n_groups) hipLaunchKernelGGL(pfac_scan_groups_kernel, dim3(1), dim3(1024), 0, s.stream, s.gsum.p, n_groups);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(s.h_ctl + 10, s.d_gsum + n_groups, 16, hipMemcpyDeviceToHost, s.stream));
+    HIP_TRY(ctx, hipMemcpyAsync(s.h_ctl + H_PASS, s.gsum.p + n_groups, 16, hipMemcpyDeviceToHost, s.stream));
     HIP_TRY(ctx, hipStreamSynchronize(s.stream));
-    const uint64_t total = ((uint64_t)s.h_ctl[11] << 32) | s.h_ctl[10];
-    if (s.h_ctl[12] | s.h_ctl[13])
-        return fail(ctx, PFAC_E_ARG, "pfac_records_segment: document offsets must start at 0, not decrease, and end at the scan's n_owned (" +
-                                         std::to_string(s.last_owned) + ")");
+    const uint64_t total = host_u64(s, H_PASS);
+    if (host_u64(s, H_PASS1)) return bad_doc_offsets(ctx, s, fn);
     *n_kept = total;
     const bool own_out = d_out == nullptr, own_first = d_doc_first == nullptr;
     if (!own_out && total > out_cap)
-        return fail(ctx, PFAC_E_OVERFLOW, "pfac_records_segment: " + std::to_string(total) + " records kept, out_cap is " + std::to_string(out_cap));
-    if (own_out && total > s.seg_out_cap) {
-        if (s.d_seg_out) { HIP_TRY(ctx, hipFree(s.d_seg_out)); s.d_seg_out = nullptr; s.seg_out_cap = 0; }
-        const uint64_t cap = total + total / 8 + 4096;
-        HIP_TRY(ctx, hipMalloc((void **)&s.d_seg_out, cap * sizeof(pfac_record)));
-        s.seg_out_cap = cap;
-    }
-    if (own_first && n_docs + 1 > s.seg_first_cap) {
-        if (s.d_seg_first) { HIP_TRY(ctx, hipFree(s.d_seg_first)); s.d_seg_first = nullptr; s.seg_first_cap = 0; }
-        const uint64_t cap = n_docs + 1 < 4096 ? 4096 : n_docs + 1 + n_docs / 4;
-        HIP_TRY(ctx, hipMalloc((void **)&s.d_seg_first, cap * 8));
-        s.seg_first_cap = cap;
-    }
-    pfac_record *out = own_out ? s.d_seg_out : d_out;
-    unsigned long long *first = own_first ? s.d_seg_first : reinterpret_cast<unsigned long long *>(d_doc_first);
+        return fail(ctx, PFAC_E_OVERFLOW, fn + ": " + std::to_string(total) + " records kept, out_cap is " + std::to_string(out_cap));
+    rc = own_out ? s.seg_out.ensure(ctx, s.stream, total, total + total / 8 + 4096) : PFAC_OK;
+    if (rc) return rc;
+    rc = own_first ? ensure_docs(ctx, s, s.seg_first, n_docs) : PFAC_OK;
+    if (rc) return rc;
+    pfac_record *out = own_out ? s.seg_out.p : d_out;
+    unsigned long long *first = own_first ? s.seg_first.p : reinterpret_cast<unsigned long long *>(d_doc_first);
     if (n_groups) {
-        auto wk = rb == 2 ? pfac_seg_write_kernel<2> : (rb == 4 ? pfac_seg_write_kernel<4> : pfac_seg_write_kernel<8>);
-        hipLaunchKernelGGL(wk, dim3((unsigned)gblocks), dim3(256), 0, s.stream, src, s.d_tile_index, (unsigned long long)n_tiles,
-                           (unsigned long long)s.last_cap, off, (unsigned long long)n_docs, ctx->d_flen, (unsigned)ctx->num_final, s.d_seg_tcnt, s.d_gsum,
+        auto wk = by_width(rb, [](auto w) { return pfac_seg_write_kernel<w()>; });
+        hipLaunchKernelGGL(wk, dim3((unsigned)gblocks), dim3(256), 0, s.stream, src, s.tile_index.p, (unsigned long long)n_tiles,
+                           (unsigned long long)s.last_cap, off, (unsigned long long)n_docs, ctx->flen.p, (unsigned)ctx->num_final, s.seg_tcnt.p, s.gsum.p,
                            n_groups, out, first);
         HIP_TRY(ctx, hipGetLastError());
     } else {
@@ -4442,9 +4450,9 @@ int pfac_segment_d2h(pfac_ctx *ctx, int slot, pfac_record *host_records, uint64_
         return fail(ctx, PFAC_E_STATE, "pfac_segment_d2h: the last pfac_records_segment wrote into the caller's buffers");
     USE_DEVICE(ctx);
     if (host_records && s.seg_kept)
-        HIP_TRY(ctx, hipMemcpyAsync(host_records, s.d_seg_out, s.seg_kept * sizeof(pfac_record), hipMemcpyDeviceToHost, s.stream));
+        HIP_TRY(ctx, hipMemcpyAsync(host_records, s.seg_out.p, s.seg_kept * sizeof(pfac_record), hipMemcpyDeviceToHost, s.stream));
     if (host_doc_first)
-        HIP_TRY(ctx, hipMemcpyAsync(host_doc_first, s.d_seg_first, (s.seg_docs + 1) * 8, hipMemcpyDeviceToHost, s.stream));
+        HIP_TRY(ctx, hipMemcpyAsync(host_doc_first, s.seg_first.p, (s.seg_docs + 1) * 8, hipMemcpyDeviceToHost, s.stream));
     return PFAC_OK;
 }
 
@@ -4456,46 +4464,26 @@ struct LlDocs {
     uint64_t *first;
 };
 
-// The slot-owned doc_first of a per-document selection, grown to n_docs + 1 entries.
-static int lld_first_buffer(pfac_ctx *ctx, Slot &s, uint64_t n_docs) {
-    if (n_docs + 1 <= s.lld_first_cap) return PFAC_OK;
-    if (s.d_lld_first) { HIP_TRY(ctx, hipStreamSynchronize(s.stream)); HIP_TRY(ctx, hipFree(s.d_lld_first)); s.d_lld_first = nullptr; s.lld_first_cap = 0; }
-    const uint64_t cap = n_docs + 1 < 4096 ? 4096 : n_docs + 1 + n_docs / 4;
-    HIP_TRY(ctx, hipMalloc((void **)&s.d_lld_first, cap * 8));
-    s.lld_first_cap = cap;
-    return PFAC_OK;
-}
-
 // pfac_records_leftmost_longest, and with `docs` pfac_records_leftmost_longest_documents (entry 0): the same kernels,
 // the tile passes in their document form, and the document write.
 static int ll_select(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *d_records, uint32_t entry, pfac_record *d_out,
                      uint64_t out_cap, uint64_t *n_selected, uint32_t *exit_offset, const LlDocs *docs) {
     s.ll_done = false;
-    if (!s.scanned || s.pending) return fail(ctx, PFAC_E_STATE, fn + " needs a finished scan");
-    if (!ctx->have_table || !ctx->d_flen) return fail(ctx, PFAC_E_STATE, fn + ": no final-state lengths for the uploaded table (pfac_table_set_final_lengths)");
-    if (s.last_table != ctx->table_gen) return fail(ctx, PFAC_E_STATE, fn + ": the slot's last scan ran with an earlier table");
+    int rc = last_scan_usable(ctx, s, fn, SCAN_FINISHED | SCAN_LENGTHS | SCAN_TABLE);
+    if (rc) return rc;
+    // (PFAC_E_STATE, as pfac.h documents for the selections; the other passes report PFAC_E_OVERFLOW)
     if (s.last_used > s.last_cap) return fail(ctx, PFAC_E_STATE, fn + ": the slot's last scan overflowed its record heap");
     const unsigned M = (unsigned)ctx->max_pat_len;
     if (entry > M) return fail(ctx, PFAC_E_ARG, fn + ": entry " + std::to_string(entry) + " exceeds max_pat_len " + std::to_string(M));
     const int rb = s.last_rec_bytes;
-    const void *src = d_records ? d_records : s.d_records;
+    const void *src = d_records ? d_records : s.records.p;
     if (((uintptr_t)d_out & 7) || ((uintptr_t)src & (uintptr_t)(rb - 1)))
         return fail(ctx, PFAC_E_ARG, fn + ": misaligned buffer (d_out 8 B, records their width)");
     if (!src && s.last_tiles) return fail(ctx, PFAC_E_ARG, "null record buffer");
     const unsigned long long *off = nullptr;
     const uint64_t n_docs = docs ? docs->n_docs : 0;
-    if (docs) {                                             // (the rules of pfac_records_segment)
-        off = reinterpret_cast<const unsigned long long *>(docs->off);
-        if (!off) {
-            if (!s.doc_set) return fail(ctx, PFAC_E_STATE, fn + ": no document offsets for the slot (pfac_slot_doc_offsets)");
-            if (n_docs != s.doc_n) return fail(ctx, PFAC_E_ARG, fn + ": n_docs differs from the slot's document offsets");
-            off = s.d_doc_off;
-        }
-        if (n_docs >= (1ull << 32)) return fail(ctx, PFAC_E_ARG, fn + ": n_docs must be below 2^32");
-        if (n_docs == 0 && s.last_owned != 0) return fail(ctx, PFAC_E_ARG, fn + ": no documents, but the scan owns bytes");
-        if (((uintptr_t)off & 7) || ((uintptr_t)docs->first & 7))
-            return fail(ctx, PFAC_E_ARG, fn + ": device buffers must be 8-byte aligned");
-    }
+    rc = docs ? resolve_docs(ctx, s, fn, docs->off, n_docs, (uintptr_t)docs->first, &off) : PFAC_OK;
+    if (rc) return rc;
     USE_DEVICE(ctx);
     const uint64_t n_tiles = s.last_tiles;
     const bool own_out = d_out == nullptr, own_first = docs && !docs->first;
@@ -4516,26 +4504,24 @@ static int ll_select(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *
         s.ll_done = true;
         return PFAC_OK;
     };
-    int rc;
     if (n_tiles == 0) {                                     // nothing scanned: nothing picked, the cursor stays
         if (!docs) return done(0, entry);
         // every document is empty: check the offsets (pfac_seg_count_kernel without tiles), then doc_first = 0
         rc = ensure_gsum(ctx, s, 1);
         if (rc) return rc;
-        HIP_TRY(ctx, hipMemsetAsync(s.d_gsum, 0, 8, s.stream));
+        HIP_TRY(ctx, hipMemsetAsync(s.gsum.p, 0, 8, s.stream));
         const unsigned vblocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_docs + 255) / 256, 4096));
         hipLaunchKernelGGL(pfac_seg_count_kernel<4>, dim3(vblocks), dim3(256), 0, s.stream, (const void *)nullptr,
                            (const unsigned long long *)nullptr, 0ull, 0ull, off, (unsigned long long)n_docs, 0ull,
-                           ctx->d_flen, (unsigned)ctx->num_final, (unsigned *)nullptr, (unsigned long long *)nullptr, 0u, s.d_gsum);
+                           ctx->flen.p, (unsigned)ctx->num_final, (unsigned *)nullptr, (unsigned long long *)nullptr, 0u, s.gsum.p);
         HIP_TRY(ctx, hipGetLastError());
-        HIP_TRY(ctx, hipMemcpyAsync(s.h_ctl + 12, s.d_gsum, 8, hipMemcpyDeviceToHost, s.stream));
+        HIP_TRY(ctx, hipMemcpyAsync(s.h_ctl + H_PASS1, s.gsum.p, 8, hipMemcpyDeviceToHost, s.stream));
         HIP_TRY(ctx, hipStreamSynchronize(s.stream));
-        if (s.h_ctl[12] | s.h_ctl[13])
-            return fail(ctx, PFAC_E_ARG, fn + ": document offsets must start at 0, not decrease, and end at the scan's n_owned (0)");
+        if (host_u64(s, H_PASS1)) return bad_doc_offsets(ctx, s, fn);      // (no tiles: n_owned is 0)
         if (own_first) {
-            rc = lld_first_buffer(ctx, s, n_docs);
+            rc = ensure_docs(ctx, s, s.lld_first, n_docs);
             if (rc) return rc;
-            first = s.d_lld_first;
+            first = s.lld_first.p;
         }
         HIP_TRY(ctx, hipMemsetAsync(first, 0, (n_docs + 1) * 8, s.stream));
         return done(0, entry);
@@ -4547,75 +4533,62 @@ static int ll_select(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *
     const size_t o_hat = align_up(o_hfun + (size_t)nb * FS * 2, 256), o_gat = align_up(o_hat + (size_t)nb * 2, 256);
     const size_t o_tcnt = align_up(o_gat + (size_t)n_groups * 2, 256), o_bits = align_up(o_tcnt + n_tiles * 4, 256);
     const size_t need = o_bits + n_tiles * (WTILE / 8);
-    if (need > s.ll_tmp_cap) {
-        if (s.d_ll_tmp) { HIP_TRY(ctx, hipStreamSynchronize(s.stream)); HIP_TRY(ctx, hipFree(s.d_ll_tmp)); s.d_ll_tmp = nullptr; s.ll_tmp_cap = 0; }
-        const uint64_t cap = need + need / 4;
-        HIP_TRY(ctx, hipMalloc((void **)&s.d_ll_tmp, cap));
-        s.ll_tmp_cap = cap;
-    }
-    unsigned short *gfun = reinterpret_cast<unsigned short *>(s.d_ll_tmp + o_gfun), *hfun = reinterpret_cast<unsigned short *>(s.d_ll_tmp + o_hfun);
-    unsigned short *hat = reinterpret_cast<unsigned short *>(s.d_ll_tmp + o_hat), *gat = reinterpret_cast<unsigned short *>(s.d_ll_tmp + o_gat);
-    unsigned *tcnt = reinterpret_cast<unsigned *>(s.d_ll_tmp + o_tcnt);
-    unsigned long long *bits = reinterpret_cast<unsigned long long *>(s.d_ll_tmp + o_bits);
+    rc = s.ll_tmp.ensure(ctx, s.stream, need, need + need / 4);
+    if (rc) return rc;
+    unsigned short *gfun = reinterpret_cast<unsigned short *>(s.ll_tmp.p + o_gfun), *hfun = reinterpret_cast<unsigned short *>(s.ll_tmp.p + o_hfun);
+    unsigned short *hat = reinterpret_cast<unsigned short *>(s.ll_tmp.p + o_hat), *gat = reinterpret_cast<unsigned short *>(s.ll_tmp.p + o_gat);
+    unsigned *tcnt = reinterpret_cast<unsigned *>(s.ll_tmp.p + o_tcnt);
+    unsigned long long *bits = reinterpret_cast<unsigned long long *>(s.ll_tmp.p + o_bits);
     rc = ensure_gsum(ctx, s, n_groups + 2);                 // group prefixes, the total, the exit offset, the offsets' error word
     if (rc) return rc;
-    unsigned long long *bad = docs ? s.d_gsum + n_groups + 2 : nullptr;
+    unsigned long long *bad = docs ? s.gsum.p + n_groups + 2 : nullptr;
     if (docs) HIP_TRY(ctx, hipMemsetAsync(bad, 0, 8, s.stream));
-    auto fk = rb == 2 ? pfac_ll_tiles_kernel<2, false> : (rb == 4 ? pfac_ll_tiles_kernel<4, false> : pfac_ll_tiles_kernel<8, false>);
-    auto mk = rb == 2 ? pfac_ll_tiles_kernel<2, true> : (rb == 4 ? pfac_ll_tiles_kernel<4, true> : pfac_ll_tiles_kernel<8, true>);
-    if (docs) {
-        fk = rb == 2 ? pfac_ll_tiles_kernel<2, false, true> : (rb == 4 ? pfac_ll_tiles_kernel<4, false, true> : pfac_ll_tiles_kernel<8, false, true>);
-        mk = rb == 2 ? pfac_ll_tiles_kernel<2, true, true> : (rb == 4 ? pfac_ll_tiles_kernel<4, true, true> : pfac_ll_tiles_kernel<8, true, true>);
-    }
+    const bool dk = docs != nullptr;
+    auto fk = by_width(rb, [dk](auto w) { return dk ? pfac_ll_tiles_kernel<w(), false, true> : pfac_ll_tiles_kernel<w(), false, false>; });
+    auto mk = by_width(rb, [dk](auto w) { return dk ? pfac_ll_tiles_kernel<w(), true, true> : pfac_ll_tiles_kernel<w(), true, false>; });
     const size_t lds = ll_tiles_lds(M1);
     HIP_TRY(ctx, hipFuncSetAttribute((const void *)fk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     HIP_TRY(ctx, hipFuncSetAttribute((const void *)mk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const unsigned long long nt = n_tiles, cap = s.last_cap, own = s.last_owned, nd = n_docs;
-    hipLaunchKernelGGL(fk, dim3(n_groups), dim3(LL_WAVES * WAVE), lds, s.stream, src, s.d_tile_index, nt, cap, own, ctx->d_flen,
-                       (unsigned)ctx->num_final, M, gfun, (const unsigned short *)nullptr, bits, tcnt, s.d_gsum, off, nd, bad);
+    hipLaunchKernelGGL(fk, dim3(n_groups), dim3(LL_WAVES * WAVE), lds, s.stream, src, s.tile_index.p, nt, cap, own, ctx->flen.p,
+                       (unsigned)ctx->num_final, M, gfun, (const unsigned short *)nullptr, bits, tcnt, s.gsum.p, off, nd, bad);
     hipLaunchKernelGGL(pfac_ll_compose_kernel, dim3(nb), dim3(1024), LL_CHUNK_BYTES, s.stream, gfun, M1, n_groups, (unsigned)XGROUP, hfun);
     hipLaunchKernelGGL(pfac_ll_walk_kernel, dim3(1), dim3(256), LL_CHUNK_BYTES, s.stream, hfun, M1, nb, nb, (const unsigned short *)nullptr,
-                       (unsigned)entry, hat, s.d_gsum + n_groups + 1);
+                       (unsigned)entry, hat, s.gsum.p + n_groups + 1);
     hipLaunchKernelGGL(pfac_ll_walk_kernel, dim3(nb), dim3(256), LL_CHUNK_BYTES, s.stream, gfun, M1, n_groups, (unsigned)XGROUP,
                        (const unsigned short *)hat, 0u, gat, (unsigned long long *)nullptr);
-    hipLaunchKernelGGL(mk, dim3(n_groups), dim3(LL_WAVES * WAVE), lds, s.stream, src, s.d_tile_index, nt, cap, own, ctx->d_flen,
-                       (unsigned)ctx->num_final, M, (unsigned short *)nullptr, (const unsigned short *)gat, bits, tcnt, s.d_gsum,
+    hipLaunchKernelGGL(mk, dim3(n_groups), dim3(LL_WAVES * WAVE), lds, s.stream, src, s.tile_index.p, nt, cap, own, ctx->flen.p,
+                       (unsigned)ctx->num_final, M, (unsigned short *)nullptr, (const unsigned short *)gat, bits, tcnt, s.gsum.p,
                        off, nd, (unsigned long long *)nullptr);
-    hipLaunchKernelGGL(pfac_scan_groups_kernel, dim3(1), dim3(1024), 0, s.stream, s.d_gsum, n_groups);
+    hipLaunchKernelGGL(pfac_scan_groups_kernel, dim3(1), dim3(1024), 0, s.stream, s.gsum.p, n_groups);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(s.h_ctl + 10, s.d_gsum + n_groups, docs ? 24 : 16, hipMemcpyDeviceToHost, s.stream));
+    HIP_TRY(ctx, hipMemcpyAsync(s.h_ctl + H_PASS, s.gsum.p + n_groups, docs ? 24 : 16, hipMemcpyDeviceToHost, s.stream));
     HIP_TRY(ctx, hipStreamSynchronize(s.stream));
-    const uint64_t total = ((uint64_t)s.h_ctl[11] << 32) | s.h_ctl[10];
+    const uint64_t total = host_u64(s, H_PASS);
     if (docs) {
-        if (s.h_ctl[14] | s.h_ctl[15])
-            return fail(ctx, PFAC_E_ARG, fn + ": document offsets must start at 0, not decrease, and end at the scan's n_owned (" +
-                                             std::to_string(s.last_owned) + ")");
-        if (s.h_ctl[12]) return fail(ctx, PFAC_E_INTERNAL, fn + ": a pick ran past the last document");
+        if (host_u64(s, H_PASS2)) return bad_doc_offsets(ctx, s, fn);
+        if (s.h_ctl[H_PASS1]) return fail(ctx, PFAC_E_INTERNAL, fn + ": a pick ran past the last document");
     }
     *n_selected = total;
-    *exit_offset = s.h_ctl[12];
+    *exit_offset = s.h_ctl[H_PASS1];
     if (!own_out && total > out_cap)
         return fail(ctx, PFAC_E_OVERFLOW, fn + ": " + std::to_string(total) + " records selected, out_cap is " + std::to_string(out_cap));
-    if (own_out && total > s.ll_out_cap) {
-        if (s.d_ll_out) { HIP_TRY(ctx, hipFree(s.d_ll_out)); s.d_ll_out = nullptr; s.ll_out_cap = 0; }
-        const uint64_t ocap = total + total / 8 + 4096;
-        HIP_TRY(ctx, hipMalloc((void **)&s.d_ll_out, ocap * sizeof(pfac_record)));
-        s.ll_out_cap = ocap;
-    }
-    pfac_record *out = own_out ? s.d_ll_out : d_out;
+    rc = own_out ? s.ll_out.ensure(ctx, s.stream, total, total + total / 8 + 4096) : PFAC_OK;
+    if (rc) return rc;
+    pfac_record *out = own_out ? s.ll_out.p : d_out;
     if (docs) {
         if (own_first) {
-            rc = lld_first_buffer(ctx, s, n_docs);
+            rc = ensure_docs(ctx, s, s.lld_first, n_docs);
             if (rc) return rc;
-            first = s.d_lld_first;
+            first = s.lld_first.p;
         }
-        auto wk = rb == 2 ? pfac_ll_doc_write_kernel<2> : (rb == 4 ? pfac_ll_doc_write_kernel<4> : pfac_ll_doc_write_kernel<8>);
-        hipLaunchKernelGGL(wk, dim3((n_groups + 3) / 4), dim3(256), 0, s.stream, src, s.d_tile_index, nt, cap, off, nd, ctx->d_flen,
-                           (unsigned)ctx->num_final, bits, tcnt, s.d_gsum, n_groups, out, first);
+        auto wk = by_width(rb, [](auto w) { return pfac_ll_doc_write_kernel<w()>; });
+        hipLaunchKernelGGL(wk, dim3((n_groups + 3) / 4), dim3(256), 0, s.stream, src, s.tile_index.p, nt, cap, off, nd, ctx->flen.p,
+                           (unsigned)ctx->num_final, bits, tcnt, s.gsum.p, n_groups, out, first);
         HIP_TRY(ctx, hipGetLastError());
     } else if (total) {
-        auto wk = rb == 2 ? pfac_ll_write_kernel<2> : (rb == 4 ? pfac_ll_write_kernel<4> : pfac_ll_write_kernel<8>);
-        hipLaunchKernelGGL(wk, dim3((n_groups + 3) / 4), dim3(256), 0, s.stream, src, s.d_tile_index, nt, cap, bits, tcnt, s.d_gsum,
+        auto wk = by_width(rb, [](auto w) { return pfac_ll_write_kernel<w()>; });
+        hipLaunchKernelGGL(wk, dim3((n_groups + 3) / 4), dim3(256), 0, s.stream, src, s.tile_index.p, nt, cap, bits, tcnt, s.gsum.p,
                            n_groups, out);
         HIP_TRY(ctx, hipGetLastError());
     }
@@ -4654,7 +4627,7 @@ int pfac_leftmost_longest_d2h(pfac_ctx *ctx, int slot, pfac_record *host) {
     if (!s.ll_own_out) return fail(ctx, PFAC_E_STATE, "pfac_leftmost_longest_d2h: the last selection wrote into the caller's buffer");
     if (!host && s.ll_n) return fail(ctx, PFAC_E_ARG, "null host buffer");
     USE_DEVICE(ctx);
-    if (s.ll_n) HIP_TRY(ctx, hipMemcpyAsync(host, s.d_ll_out, s.ll_n * sizeof(pfac_record), hipMemcpyDeviceToHost, s.stream));
+    if (s.ll_n) HIP_TRY(ctx, hipMemcpyAsync(host, s.ll_out.p, s.ll_n * sizeof(pfac_record), hipMemcpyDeviceToHost, s.stream));
     return PFAC_OK;
 }
 
@@ -4668,9 +4641,9 @@ int pfac_leftmost_longest_documents_d2h(pfac_ctx *ctx, int slot, pfac_record *ho
         return fail(ctx, PFAC_E_STATE, "pfac_leftmost_longest_documents_d2h: the last selection wrote into the caller's buffers");
     USE_DEVICE(ctx);
     if (host_records && s.ll_n)
-        HIP_TRY(ctx, hipMemcpyAsync(host_records, s.d_ll_out, s.ll_n * sizeof(pfac_record), hipMemcpyDeviceToHost, s.stream));
+        HIP_TRY(ctx, hipMemcpyAsync(host_records, s.ll_out.p, s.ll_n * sizeof(pfac_record), hipMemcpyDeviceToHost, s.stream));
     if (host_doc_first)
-        HIP_TRY(ctx, hipMemcpyAsync(host_doc_first, s.d_lld_first, (s.lld_docs + 1) * 8, hipMemcpyDeviceToHost, s.stream));
+        HIP_TRY(ctx, hipMemcpyAsync(host_doc_first, s.lld_first.p, (s.lld_docs + 1) * 8, hipMemcpyDeviceToHost, s.stream));
     return PFAC_OK;
 }
 
@@ -4689,15 +4662,15 @@ int pfac_table_set_replacements(pfac_ctx *ctx, const uint32_t *offsets, uint64_t
                                              std::to_string(PFAC_MAX_REPLACEMENT) + " bytes");
     }
     USE_DEVICE(ctx);
-    if (ctx->d_rep_off) { HIP_TRY(ctx, hipFree(ctx->d_rep_off)); ctx->d_rep_off = nullptr; }
-    if (ctx->d_rep) { HIP_TRY(ctx, hipFree(ctx->d_rep)); ctx->d_rep = nullptr; ctx->rep_size = 0; }
+    ctx->rep_off.reset();
+    ctx->rep.reset();
     const uint64_t size = align_up(n_bytes, 16) + 16;
-    HIP_TRY(ctx, hipMalloc((void **)&ctx->d_rep_off, (n_states + 1) * 4));
-    HIP_TRY(ctx, hipMalloc((void **)&ctx->d_rep, size));
-    HIP_TRY(ctx, hipMemset(ctx->d_rep, 0, size));
-    HIP_TRY(ctx, hipMemcpy(ctx->d_rep_off, offsets, (n_states + 1) * 4, hipMemcpyHostToDevice));
-    if (n_bytes) HIP_TRY(ctx, hipMemcpy(ctx->d_rep, bytes, n_bytes, hipMemcpyHostToDevice));
-    ctx->rep_size = size;
+    int rc = ctx->rep_off.ensure(ctx, nullptr, n_states + 1, n_states + 1);
+    if (!rc) rc = ctx->rep.ensure(ctx, nullptr, size, size);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemset(ctx->rep.p, 0, size));
+    HIP_TRY(ctx, hipMemcpy(ctx->rep_off.p, offsets, (n_states + 1) * 4, hipMemcpyHostToDevice));
+    if (n_bytes) HIP_TRY(ctx, hipMemcpy(ctx->rep.p, bytes, n_bytes, hipMemcpyHostToDevice));
     return PFAC_OK;
 }
 
@@ -4717,17 +4690,17 @@ static int rp_run(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *d_i
                                                   : " needs a pfac_records_leftmost_longest since the slot's last scan"));
     if (!ctx->have_table || s.last_table != ctx->table_gen)
         return fail(ctx, PFAC_E_STATE, fn + ": the selection was made with an earlier table");
-    if (!ctx->d_rep) return fail(ctx, PFAC_E_STATE, fn + ": no replacements for the uploaded table (pfac_table_set_replacements)");
-    if (!ctx->d_flen) return fail(ctx, PFAC_E_STATE, fn + ": no final-state lengths for the uploaded table");
+    if (!ctx->rep.p) return fail(ctx, PFAC_E_STATE, fn + ": no replacements for the uploaded table (pfac_table_set_replacements)");
+    if (!ctx->flen.p) return fail(ctx, PFAC_E_STATE, fn + ": no final-state lengths for the uploaded table");
     if (!d_sel && !s.ll_own_out)
         return fail(ctx, PFAC_E_STATE, fn + ": the selection went to the caller's buffer; pass it as d_sel");
-    const pfac_record *sel = d_sel ? d_sel : s.d_ll_out;
-    const unsigned char *in = d_input ? static_cast<const unsigned char *>(d_input) : s.d_input;
+    const pfac_record *sel = d_sel ? d_sel : s.ll_out.p;
+    const unsigned char *in = d_input ? static_cast<const unsigned char *>(d_input) : s.input.p;
     const uint64_t n = s.ll_n, n_owned = s.last_owned, n_avail = s.last_avail, entry = s.ll_entry, ex = s.ll_exit;
     if (((uintptr_t)d_out & 15) || ((uintptr_t)in & 15) || ((uintptr_t)d_sel & 7))
         return fail(ctx, PFAC_E_ARG, fn + ": misaligned buffer (d_input and d_out 16 B, d_sel 8 B)");
     if (n_owned > entry && !in) return fail(ctx, PFAC_E_ARG, fn + ": no input buffer");
-    if (!d_input && n_avail > s.input_cap) return fail(ctx, PFAC_E_ARG, fn + ": the scan read more than the slot's input buffer holds");
+    if (!d_input && n_avail > s.input.cap) return fail(ctx, PFAC_E_ARG, fn + ": the scan read more than the slot's input buffer holds");
     const unsigned long long *doff = nullptr, *dfirst = nullptr;
     unsigned long long *dout_off = nullptr;
     if (docs) {
@@ -4737,11 +4710,11 @@ static int rp_run(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *d_i
         if (!doff) {
             if (!s.lld_own_off) return fail(ctx, PFAC_E_STATE, fn + ": the selection cut the caller's document offsets; pass them as d_doc_offsets");
             if (s.lld_gen != s.doc_gen || !s.doc_set) return fail(ctx, PFAC_E_STATE, fn + ": the slot's document offsets changed since the selection");
-            doff = s.d_doc_off;
+            doff = s.doc_off.p;
         }
         if (!dfirst) {
             if (!s.lld_own_first) return fail(ctx, PFAC_E_STATE, fn + ": the selection's doc_first went to the caller's buffer; pass it as d_doc_first");
-            dfirst = s.d_lld_first;
+            dfirst = s.lld_first.p;
         }
         if (((uintptr_t)doff & 7) || ((uintptr_t)dfirst & 7) || ((uintptr_t)dout_off & 7))
             return fail(ctx, PFAC_E_ARG, fn + ": device buffers must be 8-byte aligned");
@@ -4755,27 +4728,22 @@ static int rp_run(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *d_i
     int rc;
     if (n) {
         const size_t need = nb * 8;
-        if (need > s.rp_tmp_cap) {
-            if (s.d_rp_tmp) { HIP_TRY(ctx, hipStreamSynchronize(s.stream)); HIP_TRY(ctx, hipFree(s.d_rp_tmp)); s.d_rp_tmp = nullptr; s.rp_tmp_cap = 0; }
-            const uint64_t cap = need + need / 4 + 4096;
-            HIP_TRY(ctx, hipMalloc((void **)&s.d_rp_tmp, cap));
-            s.rp_tmp_cap = cap;
-        }
-        X = reinterpret_cast<unsigned long long *>(s.d_rp_tmp);
+        rc = s.rp_tmp.ensure(ctx, s.stream, need, need + need / 4 + 4096);
+        if (rc) return rc;
+        X = reinterpret_cast<unsigned long long *>(s.rp_tmp.p);
         rc = ensure_gsum(ctx, s, (unsigned)n_groups + 2);       // group prefixes, the total delta, error flag, c_{n-1}
         if (rc) return rc;
-        unsigned long long *res = s.d_gsum + n_groups + 1;
+        unsigned long long *res = s.gsum.p + n_groups + 1;
         HIP_TRY(ctx, hipMemsetAsync(res, 0, 16, s.stream));
         hipLaunchKernelGGL(pfac_rp_count_kernel, dim3((unsigned)n_groups), dim3(RP_GROUP / 4 * WAVE), 0, s.stream, sel,
-                           (unsigned long long)n, (unsigned long long)entry, (unsigned long long)n_owned, ctx->d_flen,
-                           ctx->d_rep_off, (unsigned)ctx->num_final, X, s.d_gsum, res);
-        hipLaunchKernelGGL(pfac_scan_groups_kernel, dim3(1), dim3(1024), 0, s.stream, s.d_gsum, (unsigned)n_groups);
+                           (unsigned long long)n, (unsigned long long)entry, (unsigned long long)n_owned, ctx->flen.p,
+                           ctx->rep_off.p, (unsigned)ctx->num_final, X, s.gsum.p, res);
+        hipLaunchKernelGGL(pfac_scan_groups_kernel, dim3(1), dim3(1024), 0, s.stream, s.gsum.p, (unsigned)n_groups);
         HIP_TRY(ctx, hipGetLastError());
-        HIP_TRY(ctx, hipMemcpyAsync(s.h_ctl + 10, s.d_gsum + n_groups, 24, hipMemcpyDeviceToHost, s.stream));
+        HIP_TRY(ctx, hipMemcpyAsync(s.h_ctl + H_PASS, s.gsum.p + n_groups, 24, hipMemcpyDeviceToHost, s.stream));
         HIP_TRY(ctx, hipStreamSynchronize(s.stream));
-        delta = (int64_t)(((uint64_t)s.h_ctl[11] << 32) | s.h_ctl[10]);
-        const uint64_t err = ((uint64_t)s.h_ctl[13] << 32) | s.h_ctl[12];
-        const uint64_t c_last = ((uint64_t)s.h_ctl[15] << 32) | s.h_ctl[14];
+        delta = (int64_t)host_u64(s, H_PASS);
+        const uint64_t err = host_u64(s, H_PASS1), c_last = host_u64(s, H_PASS2);
         if (err || (c_last > n_owned ? c_last - n_owned : 0) != ex)
             return fail(ctx, PFAC_E_ARG, fn + ": the selection is not one of this scan and table");
     }
@@ -4788,26 +4756,13 @@ static int rp_run(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *d_i
         return fail(ctx, PFAC_E_OVERFLOW, fn + ": " + std::to_string(ob) + " output bytes, out_cap is " + std::to_string(out_cap));
     const uint64_t n_docs = s.lld_docs;
     if (docs) {                                             // (everything allocated before the first write)
-        if (!dout_off && n_docs + 1 > s.rpd_off_cap) {
-            if (s.d_rpd_off) { HIP_TRY(ctx, hipStreamSynchronize(s.stream)); HIP_TRY(ctx, hipFree(s.d_rpd_off)); s.d_rpd_off = nullptr; s.rpd_off_cap = 0; }
-            const uint64_t cap = n_docs + 1 < 4096 ? 4096 : n_docs + 1 + n_docs / 4;
-            HIP_TRY(ctx, hipMalloc((void **)&s.d_rpd_off, cap * 8));
-            s.rpd_off_cap = cap;
-        }
-        if (n && n + 1 > s.rpd_tmp_cap) {
-            if (s.d_rpd_tmp) { HIP_TRY(ctx, hipStreamSynchronize(s.stream)); HIP_TRY(ctx, hipFree(s.d_rpd_tmp)); s.d_rpd_tmp = nullptr; s.rpd_tmp_cap = 0; }
-            const uint64_t cap = n + 1 + n / 8 + 4096;
-            HIP_TRY(ctx, hipMalloc((void **)&s.d_rpd_tmp, cap * 8));
-            s.rpd_tmp_cap = cap;
-        }
+        rc = dout_off ? PFAC_OK : ensure_docs(ctx, s, s.rpd_off, n_docs);
+        if (!rc && n) rc = s.rpd_tmp.ensure(ctx, s.stream, n + 1, n + 1 + n / 8 + 4096);
+        if (rc) return rc;
     }
-    if (own_out && ob > s.rp_out_cap) {
-        if (s.d_rp_out) { HIP_TRY(ctx, hipStreamSynchronize(s.stream)); HIP_TRY(ctx, hipFree(s.d_rp_out)); s.d_rp_out = nullptr; s.rp_out_cap = 0; }
-        const uint64_t cap = align_up(ob + ob / 8, 4096);
-        HIP_TRY(ctx, hipMalloc((void **)&s.d_rp_out, cap));
-        s.rp_out_cap = cap;
-    }
-    unsigned char *out = own_out ? s.d_rp_out : static_cast<unsigned char *>(d_out);
+    rc = own_out ? s.rp_out.ensure(ctx, s.stream, ob, align_up(ob + ob / 8, 4096)) : PFAC_OK;
+    if (rc) return rc;
+    unsigned char *out = own_out ? s.rp_out.p : static_cast<unsigned char *>(d_out);
     if (ob) {
         // one window of 1 KiB per wave while the output is small (every window's search runs in parallel), four above
         uint64_t wins = ob >= (64ull << 20) ? 4 : 1;
@@ -4816,19 +4771,19 @@ static int rp_run(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *d_i
         if ((ob + per_block * wins - 1) / (per_block * wins) > max_blocks) wins = (ob + per_block * max_blocks - 1) / (per_block * max_blocks);
         const uint64_t blocks = (ob + per_block * wins - 1) / (per_block * wins);
         hipLaunchKernelGGL(pfac_rp_write_kernel, dim3((unsigned)blocks), dim3(RP_WAVES * WAVE), 0, s.stream, in,
-                           (unsigned long long)n_avail, sel, (unsigned long long)n, (unsigned long long)entry, ctx->d_flen,
-                           ctx->d_rep_off, ctx->d_rep, (unsigned long long)ctx->rep_size, X, s.d_gsum,
+                           (unsigned long long)n_avail, sel, (unsigned long long)n, (unsigned long long)entry, ctx->flen.p,
+                           ctx->rep_off.p, ctx->rep.p, (unsigned long long)ctx->rep.cap, X, s.gsum.p,
                            (unsigned long long)ob, (unsigned)wins, out);
         HIP_TRY(ctx, hipGetLastError());
     }
     if (docs) {
-        unsigned long long *oo = dout_off ? dout_off : s.d_rpd_off;
+        unsigned long long *oo = dout_off ? dout_off : s.rpd_off.p;
         if (n)
             hipLaunchKernelGGL(pfac_rp_doc_delta_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(4 * WAVE), 0, s.stream, sel,
-                               (unsigned long long)n, ctx->d_flen, ctx->d_rep_off, X, s.d_gsum, s.d_rpd_tmp);
+                               (unsigned long long)n, ctx->flen.p, ctx->rep_off.p, X, s.gsum.p, s.rpd_tmp.p);
         const unsigned oblocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_docs + 1 + 255) / 256, 65536));
         hipLaunchKernelGGL(pfac_rp_doc_offsets_kernel, dim3(oblocks), dim3(256), 0, s.stream, doff, dfirst,
-                           (unsigned long long)n_docs, (const unsigned long long *)s.d_rpd_tmp, (unsigned long long)n, oo);
+                           (unsigned long long)n_docs, (const unsigned long long *)s.rpd_tmp.p, (unsigned long long)n, oo);
         HIP_TRY(ctx, hipGetLastError());
         s.rpd_docs = n_docs;
         s.rpd_own_off = dout_off == nullptr;
@@ -4867,7 +4822,7 @@ int pfac_replace_documents_d2h(pfac_ctx *ctx, int slot, uint64_t *host_out_offse
     if (!s.rpd_own_off) return fail(ctx, PFAC_E_STATE, "pfac_replace_documents_d2h: the last replacement wrote its offsets into the caller's buffer");
     if (!host_out_offsets) return fail(ctx, PFAC_E_ARG, "null host buffer");
     USE_DEVICE(ctx);
-    HIP_TRY(ctx, hipMemcpyAsync(host_out_offsets, s.d_rpd_off, (s.rpd_docs + 1) * 8, hipMemcpyDeviceToHost, s.stream));
+    HIP_TRY(ctx, hipMemcpyAsync(host_out_offsets, s.rpd_off.p, (s.rpd_docs + 1) * 8, hipMemcpyDeviceToHost, s.stream));
     return PFAC_OK;
 }
 
@@ -4880,7 +4835,7 @@ int pfac_replace_d2h(pfac_ctx *ctx, int slot, void *host, uint64_t first, uint64
     if (first > s.rp_bytes || n > s.rp_bytes - first) return fail(ctx, PFAC_E_ARG, "pfac_replace_d2h: [first, first + n) exceeds the output");
     if (!host && n) return fail(ctx, PFAC_E_ARG, "null host buffer");
     USE_DEVICE(ctx);
-    if (n) HIP_TRY(ctx, hipMemcpyAsync(host, s.d_rp_out + first, n, hipMemcpyDeviceToHost, s.stream));
+    if (n) HIP_TRY(ctx, hipMemcpyAsync(host, s.rp_out.p + first, n, hipMemcpyDeviceToHost, s.stream));
     return PFAC_OK;
 }
 
@@ -4890,16 +4845,16 @@ int pfac_fill_tiled(pfac_ctx *ctx, int slot, void *d_dst, uint64_t n, const void
     if (!d_dst || !host_pattern || period == 0 || ((uintptr_t)d_dst & 15)) return fail(ctx, PFAC_E_ARG, "bad argument to pfac_fill_tiled");
     Slot &s = ctx->slots[slot];
     USE_DEVICE(ctx);
-    unsigned char *d_pat = nullptr;
-    HIP_TRY(ctx, hipMalloc((void **)&d_pat, period));
-    hipError_t e = hipMemcpy(d_pat, host_pattern, period, hipMemcpyHostToDevice);
+    DevBuf<unsigned char> d_pat;
+    rc = d_pat.ensure(ctx, nullptr, period, period);
+    if (rc) return rc;
+    hipError_t e = hipMemcpy(d_pat.p, host_pattern, period, hipMemcpyHostToDevice);
     if (e == hipSuccess && n) {
         hipLaunchKernelGGL(pfac_fill_tiled_kernel, dim3(2048), dim3(256), 0, s.stream, static_cast<unsigned char *>(d_dst),
-                           (unsigned long long)n, d_pat, period, (unsigned long long)phase);
+                           (unsigned long long)n, d_pat.p, period, (unsigned long long)phase);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(s.stream);
-    (void)hipFree(d_pat);
     if (e != hipSuccess) return fail(ctx, PFAC_E_HIP, std::string("pfac_fill_tiled: ") + hipGetErrorString(e));
     return PFAC_OK;
 }
@@ -4925,17 +4880,18 @@ int pfac_scan_info(pfac_ctx *ctx, int *variant, int *tile_bytes, int *grid_block
     if (variant) *variant = ctx->variant;
     if (tile_bytes) *tile_bytes = WTILE;
     if (grid_blocks) *grid_blocks = ctx->grid_blocks;
-    if (lds_bytes) *lds_bytes = (ctx->dense && ctx->stage_cap_d) ? ctx->lds_bytes_d : ctx->sparse().lds_bytes;
+    if (lds_bytes) *lds_bytes = ctx->layout(ctx->run_dense()).lds_bytes;
     return PFAC_OK;
 }
 
 int pfac_scan_staging(pfac_ctx *ctx, int *buffers, uint32_t *records_per_buffer) {
     if (!ctx) return fail(nullptr, PFAC_E_ARG, "null context");
     if (!ctx->have_table) return fail(ctx, PFAC_E_STATE, "no table uploaded");
-    const bool dense = ctx->dense && ctx->stage_cap_d;
-    if (buffers) *buffers = dense ? 1 : ctx->sparse().nbuf;
+    const bool dense = ctx->run_dense();
+    const StageLayout &L = ctx->layout(dense);
+    if (buffers) *buffers = L.nbuf;
     // (dense mode's second form has no staging buffer: what bounds a tile there is the wave's record log)
-    if (records_per_buffer) *records_per_buffer = dense ? (ctx->dense2 ? ctx->d2log_cap : ctx->stage_cap_d) : ctx->sparse().stage_cap;
+    if (records_per_buffer) *records_per_buffer = dense && ctx->dense2 ? ctx->d2log_cap : L.stage_cap;
     return PFAC_OK;
 }
 
