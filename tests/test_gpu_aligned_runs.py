@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+from heapguard import GuardedBuffer
 from orc import Oracle, match_checksum
 from phfpfac_amd import GpuMatcher, PfacTable
 from phfpfac_amd.dist import packed_to_records
@@ -96,7 +97,8 @@ def test_golden_through_aligned_runs(resolve):
 
 def test_capacity_limit(resolve):
     """Near the capacity limit: a record array of capacity_hint() records fits the scan (same matches), one with fewer
-    records than matches reports overflow and still the exact count."""
+    records than matches reports overflow and still the exact count.  The record array is exactly `cap` 16-bit records
+    inside guard bytes (tests/heapguard.py), so a store past the capacity shows."""
     import torch
     c = FP["cases"]["exp_x_1M_s1_w256"]
     table = PfacTable.from_file(resolve(c["pattern"]), c["width"])
@@ -107,13 +109,14 @@ def test_capacity_limit(resolve):
         hint = g.capacity_hint(0)
         d_in = torch.from_numpy(np.concatenate([data, np.zeros(64, np.uint8)])).to("cuda:0")
         for cap, over_expected in ((hint, False), (want.size - 1, True), (want.size // 2, True)):
-            d_rec = torch.zeros(cap // 4 + 8, dtype=torch.int64, device="cuda:0")     # cap 16-bit records (and more)
-            g.scan_async(data.size, data.size, d_input=d_in, d_records=d_rec, capacity=cap)
+            d_rec = GuardedBuffer(cap * 2)                                             # cap 16-bit records, no more
+            g.scan_async(data.size, data.size, d_input=d_in, d_records=d_rec.ptr, capacity=cap)
             n, over = g.scan_finish(0, allow_overflow=True)
             assert n == want.size and over == over_expected, (cap, n, over)
             if not over:
                 rb, _, used = g.scan_format(0)
                 assert rb == 2 and used <= cap
-                got = g.records_to_host(n, d_records=d_rec)
+                got = g.records_to_host(n, d_records=d_rec.ptr)
                 np.testing.assert_array_equal(got["pos"], want["pos"])
                 np.testing.assert_array_equal(got["state"], want["state"])
+            d_rec.check(what=f"the record array of capacity {cap}")

@@ -5,7 +5,11 @@ usage: fuzz.py [seconds] [seed]
        fuzz.py session [seconds] [seed]     random SESSIONS instead: one context per plan driven through about 60 calls
                                             in random order (tests/session.py: the model, plans and executor of the suite)
        fuzz.py class [seconds] [seed]       character-class and escaped-file cases instead (tests/classfuzz.py), against the
-                                            brute-force matcher oracle/charclass_oracle.py and the escape-aware CPU oracle"""
+                                            brute-force matcher oracle/charclass_oracle.py and the escape-aware CPU oracle
+       fuzz.py guard [seconds] [seed]       the capacity contract instead (tests/heapguard.py): the scan of random cases into
+                                            guarded record heaps of random capacities -- count, overflow flag, hint, records,
+                                            heap layout, guards.  Every case runs in a child process of its own under a time
+                                            limit; the first failure (or a child that dies or runs over) stops the tool"""
 import os, sys, tempfile, time
 os.environ.setdefault("PFAC_ENABLE_KNOBS", "1")     # tuning / test knobs of libpfac_hip.so are opt-in
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -59,6 +63,59 @@ if len(sys.argv) > 1 and sys.argv[1] == "class":
             t_last = time.time(); print(f"  ... {cases} cases, {recs} records compared, {t_last - t0:.0f} s", flush=True)
     print(f"class fuzz ok: {cases} cases in {time.time() - t0:.0f} s (seed {seed}; {', '.join(f'{v} {k}' for k, v in sorted(kinds.items()))}), "
           f"{recs} records compared (scan x2, documents, selection, replace, outputs lists, GPU text)")
+    print("cases per knob set: " + ", ".join(f"{k} {v}" for k, v in sorted(per_knob.items())))
+    raise SystemExit(0)
+if len(sys.argv) > 1 and sys.argv[1] == "guard-case":         # one case on the GPU (the child of `guard` below)
+    import torch
+    import heapguard as H
+    from passfuzz import record_width
+    case_seed = int(sys.argv[2])
+    rng = np.random.default_rng([case_seed, 0x4755415244])
+    knobs = KNOBS[int(rng.integers(0, len(KNOBS)))]
+    c = Case(case_seed, knobs)
+    for k in KNOB_NAMES: os.environ.pop(k, None)
+    os.environ.update(knobs)
+    pf = c.write_patterns(os.path.join(tempfile.mkdtemp(), "guard.pat"))
+    o = Oracle(pf, 1, 1); want = H.oracle_want(o, c.data, c.n_owned, c.n); o.close()
+    table = PfacTable.from_file(pf, c.width)
+    rb = record_width(table.num_final, knobs)
+    P = want.padded(rb)
+    d_in = torch.from_numpy(np.concatenate([c.data, np.zeros(2 * H.TILE, np.uint8)])).to("cuda:0")
+    scans = 0
+    with GpuMatcher(0, 1) as g:
+        g.load_table(table)
+        hints = []
+        first = H.verdict(g, table, want, d_in, c.n_owned, c.n, 0, rb, H.FILLS[0], hints, c.describe())
+        ladder = H.capacity_ladder(want.n, P, first["hint"])
+        caps = [int(x) for x in rng.choice(ladder, min(len(ladder), 12), replace=False)] + \
+               [int(x) for x in rng.integers(0, 4 * first["hint"] + 1, 6)] + [int(x) for x in rng.integers(max(P - 64, 0), P + 65, 6)]
+        for k, cap in enumerate(caps):
+            H.verdict(g, table, want, d_in, c.n_owned, c.n, cap, rb, H.FILLS[k % 2], hints, c.describe())
+            scans += 1
+    print(f"{scans} {want.n} {knob_label(knobs)}")
+    raise SystemExit(0)
+if len(sys.argv) > 1 and sys.argv[1] == "guard":
+    import subprocess
+    seconds = float(sys.argv[2]) if len(sys.argv) > 2 else 60.0
+    seed = int(sys.argv[3]) if len(sys.argv) > 3 else 1
+    STEP_LIMIT = 300                                           # seconds one case may take (oracle + some twenty scans)
+    t0 = t_last = time.time(); cases = 0; scans = 0; recs = 0; per_knob = {}
+    while time.time() - t0 < seconds:
+        case_seed = (seed << 32) + cases
+        try:                                                   # (this process never opens the GPU: every step is a fresh child)
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "guard-case", str(case_seed)], capture_output=True,
+                               text=True, timeout=STEP_LIMIT)
+        except subprocess.TimeoutExpired:
+            raise SystemExit(f"TIME LIMIT: case {cases} (fuzz.py guard-case {case_seed}) ran over {STEP_LIMIT} s; stopping")
+        if r.returncode:
+            raise SystemExit(f"FAILED case {cases} (fuzz.py guard-case {case_seed}), exit status {r.returncode}; stopping\n"
+                             + r.stdout[-2000:] + r.stderr[-4000:])
+        k, n, label = r.stdout.strip().split("\n")[-1].split(" ", 2)
+        scans += int(k); recs += int(n) ; per_knob[label] = per_knob.get(label, 0) + 1; cases += 1
+        if time.time() - t_last > 30:
+            t_last = time.time(); print(f"  ... {cases} cases, {scans} guarded scans, {t_last - t0:.0f} s", flush=True)
+    print(f"guard fuzz ok: {cases} cases in {time.time() - t0:.0f} s (seed {seed}), {scans} scans into guarded heaps, "
+          f"{recs} matches per ladder in all")
     print("cases per knob set: " + ", ".join(f"{k} {v}" for k, v in sorted(per_knob.items())))
     raise SystemExit(0)
 seconds = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
