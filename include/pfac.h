@@ -367,6 +367,47 @@ int pfac_records_segment(pfac_ctx *ctx, int slot, const void *d_records, const u
  * slot-owned buffer and count as one pass here; so do the two replaces. */
 int pfac_segment_d2h(pfac_ctx *ctx, int slot, pfac_record *host_records, uint64_t *host_doc_first);
 
+/* Whole-word filter: drops, IN PLACE, the records of the slot's last finished scan that split a word, so that every
+ * consumer of the scan (the fetches, the text emitter, the checksum, the segment pass, both selections and both
+ * replaces) sees whole-word matches only -- a selection then chooses among whole-word candidates, which no filter
+ * behind it could repair.  The scan kernel is not involved.
+ *   W(b)   = bit b of word_set: a 256-bit set, byte b at bit (b & 63) of word_set[b >> 6].  NULL = [0-9A-Za-z_]
+ *            (a UTF-8 user also sets 0x80..0xFF).
+ *   in[i]  = the scanned buffer for 0 <= i < n_avail; in[-1] = prev_byte and in[n_avail] = next_byte, each -1 (no byte:
+ *            the text starts / ends there) or 0..255 -- what makes chained ranges exact.
+ *   cut(i) = in[i-1] and in[i] both exist and are word bytes; with documents, and i is none of the document offsets.
+ *   A record (pos, state), L = the final length of state, is KEPT iff
+ *            !((edges & PFAC_WORD_LEFT) && cut(pos)) && !((edges & PFAC_WORD_RIGHT) && cut(pos + L)).
+ * So a pattern that begins (ends) with a non-word byte is unconstrained on that side, and for patterns of word bytes
+ * only LEFT | RIGHT is (?<!\w)pat(?!\w).  pos + L <= n_avail holds for every record: input reads stay in [0, n_avail).
+ * Effect: every tile's kept words are compacted to the front of the tile's own run of the heap, order preserved;
+ * tile_index[t] keeps its FIRST and gets the new COUNT; *n_kept becomes the scan's match count for everything that
+ * follows -- a repeated pfac_scan_finish, the first + n bounds of pfac_records_expand / pfac_records_d2h, the n of the
+ * checksum, the text emitter, every pass.  used, record_bytes and n_tiles of pfac_scan_format do not change, and no byte
+ * outside the words the scan itself wrote is written.  Filtering again with the same arguments changes nothing; other
+ * arguments compose (the intersection).  A selection made before the filter is stale: pfac_replace_* return
+ * PFAC_E_STATE for it, as after a new scan.  Slot-owned results of earlier passes stay fetchable (the lifetime rule
+ * of pfac_segment_d2h).
+ *   d_input        NULL = the slot's input buffer; else the buffer the scan read (16-B aligned)
+ *   d_records      NULL = the slot's heap; else the heap the scan wrote (any other pointer: PFAC_E_ARG)
+ *   n_docs         0 = no documents.  Else the rules of pfac_records_segment hold for d_doc_offsets (NULL = the slot's,
+ *                  pfac_slot_doc_offsets with the same n_docs, else PFAC_E_STATE); they are checked on the device in
+ *                  front of the filter, whose kernel reads the check's flag and leaves at once: a violation returns
+ *                  PFAC_E_ARG with heap, index and count untouched, at no extra host round trip.  A record that runs
+ *                  across a document end is judged like any other (the document passes drop it later, as ever).
+ * Returns once *n_kept is known.  PFAC_E_ARG: edges outside 1..3, prev_byte / next_byte outside -1..255, a d_records
+ * that is not this scan's heap, a misaligned d_input.  PFAC_E_STATE: no finished scan (also after a pfac_slot_reserve
+ * that dropped it), a scan made with an earlier table, no final lengths for the current table.  PFAC_E_OVERFLOW: the
+ * scan overflowed its heap.
+ * Kernel: one wave per tile at a time, 64 tiles per wave; per chunk of 64 records the record, its length, up to four
+ * byte gathers (pos - 1, pos, pos + L - 1, pos + L), a ballot, and the kept words stored at FIRST + kept + rank -- at or
+ * below the chunk's own slots, after all of the chunk's loads, so no later chunk is overwritten before it is read. */
+#define PFAC_WORD_LEFT  1u   /* the match must not begin inside a word */
+#define PFAC_WORD_RIGHT 2u   /* the match must not end inside a word   */
+int pfac_records_filter_words(pfac_ctx *ctx, int slot, const void *d_input, void *d_records, const uint64_t word_set[4],
+                              uint32_t edges, int prev_byte, int next_byte, const uint64_t *d_doc_offsets, uint64_t n_docs,
+                              uint64_t *n_kept);
+
 /* Leftmost-longest, non-overlapping selection over the slot's last finished scan.  From a cursor c = entry
  * (0 <= entry <= max_pat_len of the uploaded table): take the smallest position p >= c that has a record, select its
  * record of the greatest pattern length (the last one at p), set c = p + len, repeat while records remain at or after c.

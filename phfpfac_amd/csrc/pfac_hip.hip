@@ -2304,6 +2304,108 @@ __global__ void pfac_seg_write_kernel(const void *rec, const unsigned long long 
 }
 
 // ---------------------------------------------------------------------------
+// Whole-word filter (pfac_records_filter_words): drops, IN PLACE, the records that split a word.  With W the 256-bit
+// set of word bytes, cut(i) = W(in[i-1]) && W(in[i]) (in[-1] = prev, in[n_avail] = next, -1 = no byte; never at a
+// document offset); a record (pos, state) of length L goes when its tested edge(s) cut: cut(pos), cut(pos + L).
+// One wave per tile at a time, a group of 64 tiles per wave as in the expand and segment kernels.  Per chunk of 64
+// records: the record, its length, up to four byte gathers, a ballot, and the kept words stored to
+// FIRST + kept so far + rank.  Why in place is safe: the stores of chunk k depend on the ballot over ALL lanes' loads
+// of chunk k, so those loads have completed; they land in [FIRST, FIRST + 64 (k + 1)), and chunk k + 1 loads from
+// FIRST + 64 (k + 1) on -- a later chunk is never clobbered, whichever way the two are scheduled.  Stores are as wide
+// as a record (a 2-byte store for 16-bit words: the neighbouring tile's run may share the dword, and another wave
+// owns it).  The tile index keeps FIRST and gets the new COUNT; the kept total goes through one atomicAdd per wave.
+template <int BYTES>
+__device__ __forceinline__ void heap_put(void *rec, unsigned long long i, unsigned pos, unsigned state) {
+    if (BYTES == 2) {
+        static_cast<unsigned short *>(rec)[i] = (unsigned short)((pos & 0xFFFu) | state << 12);
+    } else if (BYTES == 4) {
+        static_cast<unsigned *>(rec)[i] = (pos & 0xFFFu) | state << 12;
+    } else {
+        pfac_record r;
+        r.pos = pos;
+        r.state = state;
+        static_cast<pfac_record *>(rec)[i] = r;
+    }
+}
+struct WordSet {
+    unsigned long long w[4];
+};
+// W(b) for b in -1..255 (-1: no byte there)
+__device__ __forceinline__ bool word_byte(const WordSet &ws, int b) {
+    if (b < 0) return false;
+    const unsigned long long lo = (b & 64) ? ws.w[1] : ws.w[0], hi = (b & 64) ? ws.w[3] : ws.w[2];
+    return (((b & 128) ? hi : lo) >> (b & 63)) & 1ull;
+}
+template <int BYTES, bool DOCS>
+__global__ void pfac_filter_words_kernel(void *rec, unsigned long long *tix, unsigned long long n_tiles, unsigned long long cap,
+                                         const unsigned char *in, unsigned long long n_avail, const short *flen,
+                                         unsigned num_final, WordSet ws, unsigned edges, int prev_byte, int next_byte,
+                                         const unsigned long long *off, unsigned long long n_docs,
+                                         const unsigned long long *bad, unsigned long long *total) {
+    if (DOCS && *bad) return;                                   // offsets that break the rules: nothing is touched
+    const int lane = threadIdx.x & (WAVE - 1);
+    const unsigned g = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const unsigned n_groups = (unsigned)((n_tiles + XGROUP - 1) / XGROUP);
+    if (g >= n_groups) return;
+    const bool fsmall = num_final <= (unsigned)WAVE;
+    const int freg = fsmall && (unsigned)lane < num_final ? (int)flen[lane] : 0;
+    const unsigned long long t = (unsigned long long)g * XGROUP + lane;
+    const unsigned long long e = t < n_tiles ? tix[t] : 0ull;
+    const unsigned c = (unsigned)(e >> TIX_CNT_SHIFT);
+    const unsigned long long lo = e & TIX_BASE_MASK;
+    unsigned long long ds = 0, de = 0, dlo = 0, dhi = 0;
+    if (DOCS && c) tile_docs(off, n_docs, t, n_tiles, ds, de, dlo, dhi);
+    unsigned mine = c;                                          // records tile t keeps
+    for (int j = 0; j < XGROUP; j++) {
+        const unsigned tc = __shfl(c, j, WAVE);
+        if (tc == 0) continue;
+        const unsigned long long tlo = __shfl(lo, j, WAVE);
+        DocWin w;
+        if (DOCS) w = doc_window(off, __shfl(dlo, j, WAVE), __shfl(dhi, j, WAVE), lane);
+        unsigned kept = 0;
+        for (unsigned c0 = 0; c0 < tc; c0 += WAVE) {
+            const unsigned i = c0 + (unsigned)lane;
+            const bool have = i < tc && tlo + i < cap;
+            unsigned pos = 0, st = 0;
+            if (have) heap_record<BYTES>(rec, tlo + i, (unsigned long long)g * XGROUP + j, pos, st);
+            const int len = final_len(flen, freg, fsmall, have, st);
+            const unsigned long long end = (unsigned long long)pos + (unsigned)(len > 0 ? len : 0);
+            const bool ok = have && len > 0;                    // (a state without a length never occurs in a record)
+            bool lcut = false, rcut = false;
+            if (ok && (edges & PFAC_WORD_LEFT)) {
+                const int a = pos ? (int)in[pos - 1] : prev_byte;
+                lcut = word_byte(ws, a) && pos < n_avail && word_byte(ws, (int)in[pos]);
+            }
+            if (ok && (edges & PFAC_WORD_RIGHT) && end <= n_avail) {
+                const int b = end < n_avail ? (int)in[end] : next_byte;
+                rcut = word_byte(ws, b) && word_byte(ws, (int)in[end - 1]);
+            }
+            if (DOCS) {                                         // no cut at a document offset
+                unsigned long long d, dbase, dend;
+                doc_lookup(w, off, have, pos, d, dbase, dend);
+                if (dbase == pos) lcut = false;
+                if (rcut) {
+                    if (end == dend) rcut = false;
+                    else if (end > dend) {                      // runs across its document's end: any later offset?
+                        const unsigned long long k = doc_lower_bound(off, n_docs + 1, end);
+                        if (k <= n_docs && off[k] == end) rcut = false;
+                    }
+                }
+            }
+            const bool keep = have && !lcut && !rcut;
+            const unsigned long long b = __ballot(keep);
+            const unsigned to = kept + (unsigned)__popcll(b & ((1ull << lane) - 1ull));
+            if (keep && to != i) heap_put<BYTES>(rec, tlo + to, pos, st);
+            kept += (unsigned)__popcll(b);
+        }
+        if (lane == j) mine = kept;
+    }
+    if (t < n_tiles && mine != c) tix[t] = lo | (unsigned long long)mine << TIX_CNT_SHIFT;
+    const unsigned long long sum = wave_sum64(mine);
+    if (lane == 0 && sum) atomicAdd(total, sum);
+}
+
+// ---------------------------------------------------------------------------
 // Leftmost-longest non-overlapping selection (pfac_records_leftmost_longest).  The greedy -- from cursor c take the
 // first position p >= c that has a record, its longest record, c = p + len -- is sequential, but with
 // M = max_pat_len the cursor that reaches tile t lies in [4096t, 4096t + M]: every earlier pick started before the
@@ -3275,7 +3377,7 @@ struct Slot {
     uint32_t ll_entry = 0, ll_exit = 0;   // ... and its entry and exit offsets
     // pfac_replace_leftmost_longest
     uint64_t last_avail = 0;              // n_avail of the slot's last scan (the input bytes it may read)
-    uint64_t scan_seq = 0;                // scans issued on this slot
+    uint64_t scan_seq = 0;                // record sets of this slot: scans issued + whole-word filters run over them
     DevBuf<unsigned char> rp_tmp;         // X per block of 64 picks
     DevBuf<unsigned char> rp_out;         // slot-owned output (d_out NULL)
     uint64_t rp_bytes = 0;
@@ -4453,6 +4555,71 @@ int pfac_segment_d2h(pfac_ctx *ctx, int slot, pfac_record *host_records, uint64_
         HIP_TRY(ctx, hipMemcpyAsync(host_records, s.seg_out.p, s.seg_kept * sizeof(pfac_record), hipMemcpyDeviceToHost, s.stream));
     if (host_doc_first)
         HIP_TRY(ctx, hipMemcpyAsync(host_doc_first, s.seg_first.p, (s.seg_docs + 1) * 8, hipMemcpyDeviceToHost, s.stream));
+    return PFAC_OK;
+}
+
+int pfac_records_filter_words(pfac_ctx *ctx, int slot, const void *d_input, void *d_records, const uint64_t word_set[4],
+                              uint32_t edges, int prev_byte, int next_byte, const uint64_t *d_doc_offsets, uint64_t n_docs,
+                              uint64_t *n_kept) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    if (!n_kept) return fail(ctx, PFAC_E_ARG, "null argument");
+    *n_kept = 0;
+    Slot &s = ctx->slots[slot];
+    const std::string fn = "pfac_records_filter_words";
+    rc = last_scan_usable(ctx, s, fn, SCAN_FINISHED | SCAN_LENGTHS | SCAN_TABLE | SCAN_FITS);
+    if (rc) return rc;
+    if (edges < 1 || edges > (PFAC_WORD_LEFT | PFAC_WORD_RIGHT)) return fail(ctx, PFAC_E_ARG, fn + ": edges must be PFAC_WORD_LEFT, PFAC_WORD_RIGHT or both");
+    if (prev_byte < -1 || prev_byte > 255 || next_byte < -1 || next_byte > 255)
+        return fail(ctx, PFAC_E_ARG, fn + ": prev_byte and next_byte must be -1 (no byte) or 0..255");
+    void *heap = d_records ? d_records : (void *)s.records.p;
+    if (heap != s.last_records) return fail(ctx, PFAC_E_ARG, fn + ": d_records is not the record heap of the slot's last scan");
+    const unsigned char *in = d_input ? static_cast<const unsigned char *>(d_input) : s.input.p;
+    if ((uintptr_t)in & 15) return fail(ctx, PFAC_E_ARG, fn + ": d_input must be 16-byte aligned");
+    if (!d_input && s.last_avail > s.input.cap) return fail(ctx, PFAC_E_ARG, fn + ": the scan read more than the slot's input buffer holds");
+    if (!in && s.last_total) return fail(ctx, PFAC_E_ARG, fn + ": no input buffer");
+    const unsigned long long *off = nullptr;
+    if (n_docs && !d_doc_offsets && (!s.doc_set || n_docs != s.doc_n))
+        return fail(ctx, PFAC_E_STATE, fn + ": the slot has no document offsets for this n_docs (pfac_slot_doc_offsets)");
+    rc = n_docs ? resolve_docs(ctx, s, fn, d_doc_offsets, n_docs, 0, &off) : PFAC_OK;
+    if (rc) return rc;
+    WordSet ws;
+    for (int k = 0; k < 4; k++)                              // NULL: [0-9A-Za-z_]
+        ws.w[k] = word_set ? word_set[k] : (k == 0 ? 0x03FF000000000000ull : (k == 1 ? 0x07FFFFFE87FFFFFEull : 0ull));
+    USE_DEVICE(ctx);
+    const uint64_t n_tiles = s.last_tiles;
+    const unsigned n_groups = (unsigned)((n_tiles + XGROUP - 1) / XGROUP);
+    rc = ensure_gsum(ctx, s, 1);                            // the kept total and the offsets' error flag
+    if (rc) return rc;
+    unsigned long long *res = s.gsum.p;
+    HIP_TRY(ctx, hipMemsetAsync(res, 0, 16, s.stream));
+    if (n_docs) {                                           // the offsets' rules (pfac_seg_count_kernel without tiles), in front of the filter
+        const unsigned vblocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_docs + 255) / 256, 4096));
+        hipLaunchKernelGGL(pfac_seg_count_kernel<4>, dim3(vblocks), dim3(256), 0, s.stream, (const void *)nullptr,
+                           (const unsigned long long *)nullptr, 0ull, 0ull, off, (unsigned long long)n_docs,
+                           (unsigned long long)s.last_owned, ctx->flen.p, (unsigned)ctx->num_final, (unsigned *)nullptr,
+                           (unsigned long long *)nullptr, 0u, res + 1);
+    }
+    if (n_groups) {
+        const bool dk = n_docs != 0;
+        auto fk = by_width(s.last_rec_bytes, [dk](auto w) { return dk ? pfac_filter_words_kernel<w(), true> : pfac_filter_words_kernel<w(), false>; });
+        hipLaunchKernelGGL(fk, dim3((n_groups + 3) / 4), dim3(256), 0, s.stream, heap, s.tile_index.p, (unsigned long long)n_tiles,
+                           (unsigned long long)s.last_cap, in, (unsigned long long)s.last_avail, ctx->flen.p, (unsigned)ctx->num_final,
+                           ws, (unsigned)edges, prev_byte, next_byte, off, (unsigned long long)n_docs,
+                           (const unsigned long long *)(res + 1), res);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(s.h_ctl + H_PASS, res, 16, hipMemcpyDeviceToHost, s.stream));
+    HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+    if (host_u64(s, H_PASS1)) return bad_doc_offsets(ctx, s, fn);
+    // the kept records ARE the scan's records from here on: its match count (a repeated pfac_scan_finish reads it from
+    // the result words), and a new record set for whatever selected from the old one
+    const uint64_t total = host_u64(s, H_PASS);
+    s.last_total = total;
+    s.h_ctl[H_MATCHES] = (unsigned)total;
+    s.h_ctl[H_MATCHES + 1] = (unsigned)(total >> 32);
+    s.scan_seq++;
+    *n_kept = total;
     return PFAC_OK;
 }
 

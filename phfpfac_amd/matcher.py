@@ -13,7 +13,7 @@ from typing import Optional, Tuple
 
 import numpy as np
 
-from ._ffi import PFAC_E_OVERFLOW, CRecord, PfacError, hip_lib
+from ._ffi import PFAC_E_OVERFLOW, PFAC_WORD_LEFT, PFAC_WORD_RIGHT, CRecord, PfacError, hip_lib
 from .table import RECORD_DTYPE, PfacTable, redaction_table, replacement_table
 
 
@@ -23,6 +23,23 @@ def device_count() -> int:
     if rc:
         raise PfacError(rc, (hip_lib().pfac_last_error(None) or b"").decode())
     return n.value
+
+
+def word_set(chars: bytes) -> np.ndarray:
+    """The 256-bit set of ``pfac_records_filter_words`` (uint64[4]: byte b at bit b & 63 of word b >> 6) that holds the
+    bytes of ``chars``."""
+    w = [0, 0, 0, 0]
+    for b in bytes(chars):
+        w[b >> 6] |= 1 << (b & 63)
+    return np.array(w, dtype=np.uint64)
+
+
+_EDGES = {"both": PFAC_WORD_LEFT | PFAC_WORD_RIGHT, "left": PFAC_WORD_LEFT, "right": PFAC_WORD_RIGHT}
+
+
+def _word_bytes(whole_words):
+    """The ``word_bytes`` of ``filter_whole_words`` for a ``whole_words`` keyword: True = the default set."""
+    return None if whole_words is True else whole_words
 
 
 def _ptr(x) -> int:
@@ -257,16 +274,52 @@ class GpuMatcher:
             raise PfacError(PFAC_E_OVERFLOW, "record heap still too small after four attempts")
         return n
 
-    def scan_bytes(self, data, n_owned: Optional[int] = None, slot: int = 0) -> np.ndarray:
-        """H2D + scan + D2H of one host buffer.  ``n_owned`` < len(data) leaves the rest as read-only halo."""
+    def scan_bytes(self, data, n_owned: Optional[int] = None, slot: int = 0, whole_words=False, prev_byte: int = -1,
+                   next_byte: int = -1) -> np.ndarray:
+        """H2D + scan + D2H of one host buffer.  ``n_owned`` < len(data) leaves the rest as read-only halo.
+        ``whole_words`` (True, or the word bytes) keeps the whole-word matches only (``filter_whole_words``);
+        ``prev_byte`` / ``next_byte`` are then the bytes around ``data`` when it is one range of a longer text."""
         buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data
         n_avail = int(buf.size)
         n_owned = n_avail if n_owned is None else int(n_owned)
+        if whole_words is not False:
+            self._ensure_final_lengths()
         self.reserve(slot, max(n_avail, 1), max(n_avail // 8, 4096))
         if n_avail:
             self.h2d(buf, slot)
         n = self.scan_resident(n_owned, n_avail, slot=slot)
+        if whole_words is not False:
+            n = self.filter_whole_words(slot, _word_bytes(whole_words), prev_byte=prev_byte, next_byte=next_byte)
         return self.records_to_host(n, slot)
+
+    # -- whole-word matches -------------------------------------------------
+    def filter_whole_words(self, slot: int = 0, word_bytes=None, edges: str = "both", prev_byte: int = -1,
+                           next_byte: int = -1, n_docs: int = 0, d_doc_offsets=None, d_input=None, d_records=None) -> int:
+        """Drops, in place on the GPU, the records of the slot's last finished scan that split a word
+        (``pfac_records_filter_words``): everything that reads the scan afterwards -- the fetches, the text, the
+        checksum, the document cut, the selections, the replaces -- sees whole-word matches only.  ``word_bytes``: the
+        bytes that make up words (None = ``[0-9A-Za-z_]``; or a ``word_set`` array); ``edges``: "both", or only the
+        "left" / "right" end of a match; ``prev_byte`` / ``next_byte``: the byte in front of / behind the scanned
+        buffer (-1: the text starts / ends there); ``n_docs`` > 0: document offsets are boundaries too
+        (``d_doc_offsets`` None = the slot's).  Returns the number of records kept, which ``last_count`` reports
+        from then on."""
+        if edges not in _EDGES:
+            raise ValueError(f"edges must be one of {sorted(_EDGES)}")
+        if word_bytes is None:
+            ws = None
+        elif isinstance(word_bytes, np.ndarray) and word_bytes.dtype == np.uint64:
+            ws = np.ascontiguousarray(word_bytes)
+            if ws.size != 4:
+                raise ValueError("a word set holds four 64-bit words")
+        else:
+            ws = word_set(word_bytes)
+        n = C.c_uint64(0)
+        self._check(self._L.pfac_records_filter_words(self._ctx, slot, _ptr(d_input), _ptr(d_records),
+                                                      ws.ctypes.data if ws is not None else None, _EDGES[edges],
+                                                      int(prev_byte), int(next_byte), _ptr(d_doc_offsets), int(n_docs),
+                                                      C.byref(n)))
+        self._last_n[slot] = n.value
+        return n.value
 
     def scan_partitioned(self, tables, data, slot: int = 0) -> np.ndarray:
         """Pattern-partition mode on ONE GPU: the input is copied once, every partition's table (``tables[k]`` =
@@ -336,9 +389,10 @@ class GpuMatcher:
             self.table._final_lengths = lens          # once per table
         self.set_final_lengths(lens)
 
-    def _scan_docs(self, docs, slot: int) -> Tuple[np.ndarray, int]:
+    def _scan_docs(self, docs, slot: int, whole_words=False) -> Tuple[np.ndarray, int]:
         """Upload and scan a batch of documents (``docs`` as ``scan_documents`` takes it) and set its offsets on the
-        slot.  Returns (offsets uint64[n_docs + 1], n_docs)."""
+        slot; with ``whole_words`` the whole-word filter follows, document ends being boundaries.  Returns (offsets
+        uint64[n_docs + 1], n_docs)."""
         buf, offsets = _docs_buffer(docs)
         n = int(buf.size)
         self._ensure_final_lengths()
@@ -347,15 +401,17 @@ class GpuMatcher:
             self.h2d(buf, slot)
         self.scan_resident(n, n, slot=slot)
         self.set_doc_offsets(offsets, slot)
+        if whole_words is not False and offsets.size > 1:
+            self.filter_whole_words(slot, _word_bytes(whole_words), n_docs=int(offsets.size) - 1)
         return offsets, int(offsets.size) - 1
 
-    def scan_documents(self, docs, slot: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+    def scan_documents(self, docs, slot: int = 0, whole_words=False) -> Tuple[np.ndarray, np.ndarray]:
         """Match a batch of independent documents in one scan.  ``docs`` is a sequence of bytes-like objects, or a
         ``(buffer, offsets)`` pair whose offsets (an integer array or list, n_docs + 1 of them, from 0 to len(buffer))
         cut ``buffer`` into documents.  Returns (doc_first uint64[n_docs + 1], records): the records of document d are
         ``records[doc_first[d]:doc_first[d + 1]]``, positions relative to the document, in (offset, pattern length)
-        order -- what scanning each document on its own yields."""
-        _, n_docs = self._scan_docs(docs, slot)
+        order -- what scanning each document on its own yields (and, with ``whole_words``, filtering it on its own)."""
+        _, n_docs = self._scan_docs(docs, slot, whole_words)
         kept = self.segment_records(n_docs, slot=slot)
         return self.segment_to_host(kept, n_docs, slot)
 
@@ -384,11 +440,13 @@ class GpuMatcher:
         self.sync(slot)
         return rec
 
-    def scan_leftmost_longest(self, data, n_owned: Optional[int] = None, entry: int = 0,
-                              slot: int = 0) -> Tuple[np.ndarray, int]:
+    def scan_leftmost_longest(self, data, n_owned: Optional[int] = None, entry: int = 0, slot: int = 0, whole_words=False,
+                              prev_byte: int = -1, next_byte: int = -1) -> Tuple[np.ndarray, int]:
         """H2D + scan + selection of one host buffer (``n_owned`` < len(data) leaves the rest as halo).  Returns
         (records, exit): the leftmost-longest non-overlapping matches that start in the owned range, and the entry
-        offset for the scan of the range that follows."""
+        offset for the scan of the range that follows.  ``whole_words`` (True, or the word bytes): the selection
+        chooses among whole-word matches only; ``prev_byte`` / ``next_byte`` are the bytes around ``data`` when it is
+        one range of a longer text."""
         buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data.view(np.uint8).ravel()
         n_avail = int(buf.size)
         n_owned = n_avail if n_owned is None else int(n_owned)
@@ -397,6 +455,8 @@ class GpuMatcher:
         if n_avail:
             self.h2d(buf, slot)
         self.scan_resident(n_owned, n_avail, slot=slot)
+        if whole_words is not False:
+            self.filter_whole_words(slot, _word_bytes(whole_words), prev_byte=prev_byte, next_byte=next_byte)
         n, ex = self.select_leftmost_longest(entry, slot=slot)
         return self.selection_to_host(n, slot), ex
 
@@ -428,12 +488,12 @@ class GpuMatcher:
         self.sync(slot)
         return first, rec
 
-    def select_documents(self, docs, slot: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+    def select_documents(self, docs, slot: int = 0, whole_words=False) -> Tuple[np.ndarray, np.ndarray]:
         """Leftmost-longest selection of a batch of independent documents (``docs`` as ``scan_documents`` takes it) in
         one scan.  Returns (doc_first uint64[n_docs + 1], records): the picks of document d are
         ``records[doc_first[d]:doc_first[d + 1]]``, positions relative to the document -- what
         ``scan_leftmost_longest`` of each document on its own returns."""
-        offsets, n_docs = self._scan_docs(docs, slot)
+        offsets, n_docs = self._scan_docs(docs, slot, whole_words)
         n = self.select_leftmost_longest_documents(n_docs, slot=slot)
         first, rec = self.doc_selection_to_host(n, n_docs, slot)
         if n:
@@ -483,9 +543,12 @@ class GpuMatcher:
         self.sync(slot)
         return out
 
-    def replace(self, data, n_owned: Optional[int] = None, entry: int = 0, slot: int = 0) -> Tuple[np.ndarray, int]:
+    def replace(self, data, n_owned: Optional[int] = None, entry: int = 0, slot: int = 0, whole_words=False,
+                prev_byte: int = -1, next_byte: int = -1) -> Tuple[np.ndarray, int]:
         """H2D + scan + selection + replacement of one host buffer (``n_owned`` < len(data) leaves the rest as halo).
-        Returns (output bytes, exit): ``exit`` is the ``entry`` of the range that follows."""
+        Returns (output bytes, exit): ``exit`` is the ``entry`` of the range that follows.  ``whole_words`` (True, or
+        the word bytes): only whole-word matches are replaced; ``prev_byte`` / ``next_byte`` as in
+        ``scan_leftmost_longest``."""
         buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data.view(np.uint8).ravel()
         n_avail = int(buf.size)
         n_owned = n_avail if n_owned is None else int(n_owned)
@@ -494,6 +557,8 @@ class GpuMatcher:
         if n_avail:
             self.h2d(buf, slot)
         self.scan_resident(n_owned, n_avail, slot=slot)
+        if whole_words is not False:
+            self.filter_whole_words(slot, _word_bytes(whole_words), prev_byte=prev_byte, next_byte=next_byte)
         _, ex = self.select_leftmost_longest(entry, slot=slot)
         n = self.replace_selection(slot=slot)
         return self.replacement_to_host(n, slot), ex
@@ -521,11 +586,11 @@ class GpuMatcher:
         self.sync(slot)
         return out
 
-    def replace_documents(self, docs, slot: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+    def replace_documents(self, docs, slot: int = 0, whole_words=False) -> Tuple[np.ndarray, np.ndarray]:
         """Find-and-replace in a batch of independent documents (``docs`` as ``scan_documents`` takes it) in one scan,
         every document on its own.  Returns (out_offsets uint64[n_docs + 1], out uint8[out_bytes]): document d's
         output is ``out[out_offsets[d]:out_offsets[d + 1]]`` -- what ``replace`` of each document alone returns."""
-        _, n_docs = self._scan_docs(docs, slot)
+        _, n_docs = self._scan_docs(docs, slot, whole_words)
         self.select_leftmost_longest_documents(n_docs, slot=slot)
         n = self.replace_selection_documents(slot=slot)
         out_off = self.replacement_doc_offsets_to_host(n_docs, slot)

@@ -9,7 +9,12 @@ usage: fuzz.py [seconds] [seed]
        fuzz.py guard [seconds] [seed]       the capacity contract instead (tests/heapguard.py): the scan of random cases into
                                             guarded record heaps of random capacities -- count, overflow flag, hint, records,
                                             heap layout, guards.  Every case runs in a child process of its own under a time
-                                            limit; the first failure (or a child that dies or runs over) stops the tool"""
+                                            limit; the first failure (or a child that dies or runs over) stops the tool
+       fuzz.py words [seconds] [seed]       the whole-word filter instead (tests/wordfuzz.py): random word / phrase sets,
+                                            edges, word sets, neighbour bytes and document cuts -- the filtered records,
+                                            the selection and the replacement or the document cut behind the filter,
+                                            against tests/wordref.py over the CPU oracle's records.  One child process
+                                            per case under a time limit, as `guard`"""
 import os, sys, tempfile, time
 os.environ.setdefault("PFAC_ENABLE_KNOBS", "1")     # tuning / test knobs of libpfac_hip.so are opt-in
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -116,6 +121,43 @@ if len(sys.argv) > 1 and sys.argv[1] == "guard":
             t_last = time.time(); print(f"  ... {cases} cases, {scans} guarded scans, {t_last - t0:.0f} s", flush=True)
     print(f"guard fuzz ok: {cases} cases in {time.time() - t0:.0f} s (seed {seed}), {scans} scans into guarded heaps, "
           f"{recs} matches per ladder in all")
+    print("cases per knob set: " + ", ".join(f"{k} {v}" for k, v in sorted(per_knob.items())))
+    raise SystemExit(0)
+if len(sys.argv) > 1 and sys.argv[1] == "words-case":         # one case on the GPU (the child of `words` below)
+    import wordfuzz as W
+    case_seed = int(sys.argv[2])
+    c = W.WordCase(case_seed, W.KNOBS[int(np.random.default_rng([case_seed, 0x4B4E4F42]).integers(0, len(W.KNOBS)))])
+    for k in set(KNOB_NAMES) | set(W.KNOB_NAMES): os.environ.pop(k, None)
+    os.environ.update(c.knobs)
+    try:
+        n = W.run_word_case(lambda: GpuMatcher(0, 1), c, tempfile.mkdtemp())
+    except AssertionError as e:
+        raise SystemExit(f"MISMATCH: {e}")
+    print(f"{n} {knob_label(c.knobs)}")
+    raise SystemExit(0)
+if len(sys.argv) > 1 and sys.argv[1] == "words":
+    import subprocess
+    import wordfuzz as W
+    seconds = float(sys.argv[2]) if len(sys.argv) > 2 else 60.0
+    seed = int(sys.argv[3]) if len(sys.argv) > 3 else 1
+    STEP_LIMIT = 120                                           # seconds one case may take
+    t0 = t_last = time.time(); cases = 0; recs = 0; per_knob = {}
+    while time.time() - t0 < seconds:
+        case_seed = (seed << 32) + len(W.SEEDS) + cases        # (beyond the suite's seeds)
+        try:                                                   # (this process never opens the GPU: every case is a fresh child)
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "words-case", str(case_seed)], capture_output=True,
+                               text=True, timeout=STEP_LIMIT)
+        except subprocess.TimeoutExpired:
+            raise SystemExit(f"TIME LIMIT: case {cases} (fuzz.py words-case {case_seed}) ran over {STEP_LIMIT} s; stopping")
+        if r.returncode:
+            raise SystemExit(f"FAILED case {cases} (fuzz.py words-case {case_seed}), exit status {r.returncode}; stopping\n"
+                             + r.stdout[-2000:] + r.stderr[-4000:])
+        n, label = r.stdout.strip().split("\n")[-1].split(" ", 1)
+        recs += int(n); per_knob[label] = per_knob.get(label, 0) + 1; cases += 1
+        if time.time() - t_last > 30:
+            t_last = time.time(); print(f"  ... {cases} cases, {recs} records compared, {t_last - t0:.0f} s", flush=True)
+    print(f"words fuzz ok: {cases} cases in {time.time() - t0:.0f} s (seed {seed}), {recs} records compared (scan, filter, "
+          f"selection + replace or documents)")
     print("cases per knob set: " + ", ".join(f"{k} {v}" for k, v in sorted(per_knob.items())))
     raise SystemExit(0)
 seconds = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
