@@ -387,7 +387,8 @@ int pfac_segment_d2h(pfac_ctx *ctx, int slot, pfac_record *host_records, uint64_
  * outside the words the scan itself wrote is written.  Filtering again with the same arguments changes nothing; other
  * arguments compose (the intersection).  A selection made before the filter is stale: pfac_replace_* return
  * PFAC_E_STATE for it, as after a new scan.  Slot-owned results of earlier passes stay fetchable (the lifetime rule
- * of pfac_segment_d2h).
+ * of pfac_segment_d2h), and so does the text of an earlier pfac_emit_text_device, as it was emitted.  The filter belongs
+ * to the scan it ran on: the slot's next scan reports its own full count, and the other slots are not touched.
  *   d_input        NULL = the slot's input buffer; else the buffer the scan read (16-B aligned)
  *   d_records      NULL = the slot's heap; else the heap the scan wrote (any other pointer: PFAC_E_ARG)
  *   n_docs         0 = no documents.  Else the rules of pfac_records_segment hold for d_doc_offsets (NULL = the slot's,
@@ -398,7 +399,10 @@ int pfac_segment_d2h(pfac_ctx *ctx, int slot, pfac_record *host_records, uint64_
  * Returns once *n_kept is known.  PFAC_E_ARG: edges outside 1..3, prev_byte / next_byte outside -1..255, a d_records
  * that is not this scan's heap, a misaligned d_input.  PFAC_E_STATE: no finished scan (also after a pfac_slot_reserve
  * that dropped it), a scan made with an earlier table, no final lengths for the current table.  PFAC_E_OVERFLOW: the
- * scan overflowed its heap.
+ * scan overflowed its heap.  A call that breaks several rules: the scan's state is judged before the arguments
+ * (PFAC_E_STATE, then PFAC_E_OVERFLOW, then the rest); among the arguments no order is promised, except that offsets
+ * whose n_docs is not the slot's are not looked at (PFAC_E_STATE).  Every error leaves heap, index, count, and what a
+ * selection made before may still be used for, as they were.
  * Kernel: one wave per tile at a time, 64 tiles per wave; per chunk of 64 records the record, its length, up to four
  * byte gathers (pos - 1, pos, pos + L - 1, pos + L), a ballot, and the kept words stored at FIRST + kept + rank -- at or
  * below the chunk's own slots, after all of the chunk's loads, so no later chunk is overwritten before it is read. */

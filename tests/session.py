@@ -3,14 +3,17 @@ drives it -- many tables, many sizes, two slots, passes in any order, results fe
 
 Three parts, none of which needs a GPU to import:
 
-  Pool / Expectations  a small pool of tables and inputs, and what the CPU says about them (the CPU oracle, llref, replref,
-                       docref, docreplref, orc.match_checksum -- as passfuzz.Expect, never the device, never
-                       PfacTable.final_lengths), cached by (table, input, n_owned, ...).
+  Pool / Expectations  a small pool of tables, inputs and whole-word filters, and what the CPU says about them (the CPU
+                       oracle, its records passed through wordref for a filtered scan, then llref, replref, docref,
+                       docreplref, orc.match_checksum -- as passfuzz.Expect, never the device, never
+                       PfacTable.final_lengths), cached by (table, input, n_owned, ..., filter state).
   Model                what include/pfac.h PROMISES for every call given the calls before it: a value or a
                        PfacError.status.  It mirrors the header, not pfac_hip.hip; its state holds only keys into the cache.
   plan / run / shrink  plan(seed) draws about 60 operations, asking the model which are legal and picking an illegal one
                        about one time in eight; run(g, plan, model) performs them on a GpuMatcher (or anything shaped like
                        one) and compares bit for bit; shrink(seed, k) is the plan cut before operation k.
+                       plan(seed, words=True) is a second family with the whole-word filter among the operations; the
+                       first is pinned to what it was before.
 
 The device under test hands out final STATES; they are mapped to pattern ids with the idmap of the table the scan ran
 with (a stand-in that already works in ids says so with ``states_are_ids``)."""
@@ -21,6 +24,7 @@ import tempfile
 
 import numpy as np
 
+import wordref
 from classfuzz import ClassMatcher as _ClassMatcher
 from docref import oracle_per_doc, random_offsets
 from docreplref import per_doc
@@ -35,6 +39,7 @@ STATUS_NAMES = {OK: "OK", E_ARG: "PFAC_E_ARG", E_STATE: "PFAC_E_STATE", E_OVERFL
 TILE = 4096
 N_SLOTS = 2
 SEEDS = list(range(24))                 # the suite's plans
+WORD_SEEDS = list(range(24))            # ... and the seeds of its plans with the whole-word filter: plan(seed, words=True)
 PLAN_OPS = 60
 IN_STEP, REC_STEP = 8 << 20, 4 << 20    # reserve_grow number k asks for k * IN_STEP bytes / k * REC_STEP records: above
                                         # anything a plan's scans reserve (inputs <= 2 000 003 bytes, heaps below 4 Mi records)
@@ -86,6 +91,29 @@ REP_KEYS = ("r0", "r1", "redact")
 DOC_KEYS = ("d0", "d1", "bad_end", "bad_order")
 TEXT_BASES = (0, 999_999_990)
 
+# The whole-word filters a session may apply: a small fixed pool, so that the expectations of a filtered scan are shared
+# between plans.  ws: "def" = NULL ([0-9A-Za-z_]), "hi" = that and 0x80..0xFF, "tab" = a part of the table's own alphabet
+# (WORD_TAB; the gen tables draw their symbols from all 256 bytes, where the default set says next to nothing).
+# prev / next: -1 = no byte, "w" = a word byte of the set, "n" = a byte outside it.  doc: "none" = n_docs 0, "slot" = the
+# slot's document offsets (whatever set_doc left there: d0, d1, bad_end, bad_order, or none) and their n_docs, "wrong_n" =
+# the slot's offsets with an n_docs that is not theirs.
+FILTERS = (
+    dict(edges="both", ws="def", prev=-1, next=-1, doc="none"),
+    dict(edges="both", ws="tab", prev=-1, next=-1, doc="none"),
+    dict(edges="left", ws="tab", prev="w", next="n", doc="none"),
+    dict(edges="right", ws="tab", prev="n", next="w", doc="none"),
+    dict(edges="both", ws="hi", prev="w", next="w", doc="none"),
+    dict(edges="left", ws="tab", prev=-1, next="w", doc="slot"),
+    dict(edges="right", ws="tab", prev="w", next=-1, doc="slot"),
+    dict(edges="both", ws="tab", prev="n", next="n", doc="slot"),
+    dict(edges="both", ws="hi", prev="w", next="n", doc="slot"),
+    dict(edges="left", ws="def", prev="n", next="w", doc="slot"),
+    dict(edges="both", ws="tab", prev=-1, next=-1, doc="wrong_n"),
+)
+EDGE_BITS = {"left": wordref.LEFT, "right": wordref.RIGHT, "both": wordref.BOTH}
+MAX_FILTERS = 3                         # distinct filters on one scan: more would only thin out the cache
+WORD_TAB = {"cclass": b"abcxyz", "negcc": b"abcy", "nlesc": b"abxq\n"}     # (the other tables: the first half of their symbols)
+
 
 def _gen_lines(seed, alpha, npat, maxlen, dups):
     rng = np.random.default_rng([seed, 0x53455353])
@@ -95,7 +123,7 @@ def _gen_lines(seed, alpha, npat, maxlen, dups):
         if len(pats) >= npat:
             break
         pats.add(bytes(symbols[rng.integers(0, alpha, int(rng.integers(1, maxlen + 1)))]))
-    lines = sorted(pats, key=lambda x: rng.random())
+    lines = sorted(sorted(pats), key=lambda x: rng.random())     # (sorted first: a set of bytes iterates in another order in every process)
     for _ in range(dups):                                      # duplicate lines: unreachable final states
         lines.insert(int(rng.integers(0, len(lines) + 1)), lines[int(rng.integers(0, len(lines)))])
     return lines, symbols
@@ -178,38 +206,84 @@ class Expectations:
     def input_size(self, t, i):
         return TABLES[t]["inputs"][i][1]
 
+    # -- whole-word filters ---------------------------------------------------
+    def word_bytes(self, t, ws):
+        """The bytes of word set `ws` for table `t` (None: the call's NULL, the default set)."""
+        if ws == "def":
+            return None
+        if ws == "hi":
+            return wordref.DEFAULT_WORD + bytes(range(0x80, 0x100))
+        sym = self.tinfo(t)["symbols"]
+        return WORD_TAB[t] if sym is None else bytes(sym[:(sym.size + 1) // 2])
+
+    def neighbour(self, t, ws, which):
+        """The prev_byte / next_byte of a descriptor: -1, or the smallest byte inside ("w") / outside ("n") the set."""
+        if which == -1:
+            return -1
+        inside = set(self.word_bytes(t, ws) or wordref.DEFAULT_WORD)
+        return min(b for b in range(256) if (b in inside) == (which == "w"))
+
+    def applied(self, t, f, dkey):
+        """Descriptor FILTERS[f] as applied to a scan of table `t`: (edge bits, ws, prev_byte, next_byte, dkey or "").
+        A scan's filter state is the sorted tuple of the distinct ones applied to it."""
+        d = FILTERS[f]
+        return (EDGE_BITS[d["edges"]], d["ws"], self.neighbour(t, d["ws"], d["prev"]), self.neighbour(t, d["ws"], d["next"]), dkey or "")
+
+    def _keep(self, t, i, no, one):
+        """The keep mask of ONE applied filter over the unfiltered records of the scan (composition is intersection)."""
+        def make():
+            edges, ws, prev, nxt, dkey = one
+            chars = self.word_bytes(t, ws)
+            bits = None
+            if chars is not None:
+                bits = np.zeros(4, dtype=np.uint64)
+                for b in chars:
+                    bits[b >> 6] |= np.uint64(1 << (b & 63))
+            pos, _, lens = self.scan(t, i, no)
+            off = self.offsets(t, i, no, dkey) if dkey else None
+            return wordref.filter_words(self.input(t, i), pos, lens, bits, edges, prev, nxt, off)   # (n_avail: the whole input)
+        return self._memo(("keep", t, i, no, one), make)
+
     # -- the scan -----------------------------------------------------------
-    def scan(self, t, i, no):
-        """(pos, ids, lens) of the records that start in [0, no); walks may read the whole input (the halo)."""
+    def scan(self, t, i, no, f=()):
+        """(pos, ids, lens) of the records that start in [0, no); walks may read the whole input (the halo).  `f`: the
+        scan's filter state (`applied`), whose filters the records have passed."""
         def make():
             info = self.tinfo(t)
             pos, ids = self._memo(("whole", t, i), lambda: info["matcher"].scan_spec(self.input(t, i), None))
             own = pos < no
             pos, ids = pos[own].astype(np.int64), ids[own].astype(np.int64)
             return pos, ids, info["ll"][ids]
-        return self._memo(("scan", t, i, no), make)
 
-    def count(self, t, i, no):
-        return int(self.scan(t, i, no)[0].size)
+        def filtered():
+            pos, ids, lens = self.scan(t, i, no)
+            keep = np.ones(pos.size, dtype=bool)
+            for one in f:
+                keep &= self._keep(t, i, no, one)
+            return pos[keep], ids[keep], lens[keep]
+        return self._memo(("scan", t, i, no, f), filtered) if f else self._memo(("scan", t, i, no), make)
 
-    def text(self, t, i, no, base):
+    def count(self, t, i, no, f=()):
+        return int(self.scan(t, i, no, f)[0].size)
+
+    def text(self, t, i, no, base, f=()):
         def make():
-            pos, ids, _ = self.scan(t, i, no)
+            pos, ids, _ = self.scan(t, i, no, f)
             return "".join("At position %4d, match pattern %d\n" % (p + base, k) for p, k in zip(pos.tolist(), ids.tolist())).encode()
-        return self._memo(("text", t, i, no, base), make)
+        return self._memo(("text", t, i, no, base, f), make)
 
-    def checksum(self, t, i, no, base):
-        pos, ids, _ = self.scan(t, i, no)
+    def checksum(self, t, i, no, base, f=()):
+        pos, ids, _ = self.scan(t, i, no, f)
         return match_checksum(pos + base, ids)
 
     # -- selection and replace ------------------------------------------------
-    def sel(self, t, i, no, entry):
+    def sel(self, t, i, no, entry, f=()):
         """(pos, ids, exit) of the leftmost-longest selection from `entry`."""
         def make():
-            pos, ids, lens = self.scan(t, i, no)
+            pos, ids, lens = self.scan(t, i, no, f)
             idx, ex = greedy(pos, lens, entry, no)
             return pos[idx], ids[idx], int(ex)
-        return self._memo(("sel", t, i, no, entry), make)
+        return self._memo(("sel", t, i, no, entry, f), make)
 
     def reps(self, t, rkey):
         def make():
@@ -221,11 +295,11 @@ class Expectations:
                     for k in range(1, ll.size)}
         return self._memo(("reps", t, rkey), make)
 
-    def replace(self, t, i, no, entry, rkey):
+    def replace(self, t, i, no, entry, rkey, f=()):
         def make():
-            spos, sids, _ = self.sel(t, i, no, entry)
+            spos, sids, _ = self.sel(t, i, no, entry, f)
             return splice(self.input(t, i), entry, no, spos, self.tinfo(t)["ll"][sids], sids, rep_table(self.reps(t, rkey)))
-        return self._memo(("replace", t, i, no, entry, rkey), make)
+        return self._memo(("replace", t, i, no, entry, rkey, f), make)
 
     # -- documents ----------------------------------------------------------
     def offsets(self, t, i, no, dkey):
@@ -245,22 +319,45 @@ class Expectations:
             return off.astype(np.uint64)
         return self._memo(("off", t, i, no, dkey), make)
 
-    def seg(self, t, i, no, dkey):
+    def _doc_matcher(self, t, i, no, dkey, f):
+        """What docref / docreplref scan every document with: the CPU oracle, or for a filtered scan the scan's kept
+        records cut at the documents (the filter judged them in the whole buffer, which no scan of a document repeats)."""
+        return _DocCut(self.scan(t, i, no, f), self.offsets(t, i, no, dkey)) if f else self.tinfo(t)["matcher"]
+
+    def seg(self, t, i, no, dkey, f=()):
         """(doc_first, pos relative to the document, ids) of every document scanned on its own."""
         def make():
-            first, pos, ids = oracle_per_doc(self.tinfo(t)["matcher"], self.input(t, i)[:no], self.offsets(t, i, no, dkey))
+            first, pos, ids = oracle_per_doc(self._doc_matcher(t, i, no, dkey, f), self.input(t, i)[:no], self.offsets(t, i, no, dkey))
             return first, pos.astype(np.int64), ids.astype(np.int64)
-        return self._memo(("seg", t, i, no, dkey), make)
+        return self._memo(("seg", t, i, no, dkey, f), make)
 
-    def docsel(self, t, i, no, dkey, rkey=None):
+    def docsel(self, t, i, no, dkey, f=(), rkey=None):
         """(doc_first, pos relative to the SCAN, ids, out_off, out) of every document's own selection (and output)."""
         def make():
             off = self.offsets(t, i, no, dkey)
             tab = None if rkey is None else rep_table(self.reps(t, rkey))
-            first, pos, ids, out_off, out = per_doc(self.tinfo(t)["matcher"], self.input(t, i)[:no], off, self.tinfo(t)["ll"], tab)
+            first, pos, ids, out_off, out = per_doc(self._doc_matcher(t, i, no, dkey, f), self.input(t, i)[:no], off, self.tinfo(t)["ll"], tab)
             doc = np.repeat(np.arange(off.size - 1, dtype=np.int64), np.diff(first.astype(np.int64)))
             return first, pos.astype(np.int64) + off[doc].astype(np.int64), ids.astype(np.int64), out_off, out
-        return self._memo(("docsel", t, i, no, dkey, rkey), make)
+        return self._memo(("docsel", t, i, no, dkey, f, rkey), make)
+
+
+class _DocCut:
+    """Stands where the CPU oracle stands in docref.oracle_per_doc for a FILTERED scan: asked for the non-empty documents
+    in turn, it answers with the scan's kept records that lie inside each one, positions relative to the document."""
+
+    def __init__(self, rows, off):
+        self.rows = rows
+        off = off.astype(np.int64)
+        self.ranges = iter([(int(a), int(b)) for a, b in zip(off[:-1], off[1:]) if b > a])
+
+    def scan_spec(self, buf, *_):
+        a, b = next(self.ranges)
+        assert buf.size == b - a
+        pos, ids, lens = self.rows
+        lo, hi = np.searchsorted(pos, [a, b], side="left")
+        inside = pos[lo:hi] + lens[lo:hi] <= b
+        return pos[lo:hi][inside] - a, ids[lo:hi][inside]
 
 
 _EXP = None
@@ -296,7 +393,7 @@ class Exp:
 
 class _Slot:
     def __init__(self):
-        self.scan = None          # the slot's last scan: dict(tab, knob, gen, inp, no, over, pending, ext, seq)
+        self.scan = None          # the slot's last scan: dict(tab, knob, gen, inp, no, over, pending, ext, seq, filt)
         self.seq = 0              # scans issued
         self.has_in = self.has_rec = False      # the slot owns an input buffer / a record heap
         self.grow = 0             # reserve_grow calls so far
@@ -362,11 +459,22 @@ class Model:
     # -- scans --------------------------------------------------------------
     def _new_scan(self, s, op, pending, ext, over=False):
         s.seq += 1
-        s.scan = dict(tab=self.tab, knob=self.knob, gen=self.gen, inp=op["inp"], no=op["no"], over=over, pending=pending, ext=ext, seq=s.seq)
+        s.scan = dict(tab=self.tab, knob=self.knob, gen=self.gen, inp=op["inp"], no=op["no"], over=over, pending=pending, ext=ext, seq=s.seq,
+                      filt=())                                  # (filt: the filters applied to it, Expectations.applied, sorted)
+
+    @staticmethod
+    def _sk(sc):
+        """The scan as the expectations key it: table, input, n_owned and filter state."""
+        return sc["tab"], sc["inp"], sc["no"], sc["filt"]
+
+    def _count(self, sc):
+        return self.x.count(*self._sk(sc))
 
     def _rec_fn(self, sc, first=0, n=None):
+        key = self._sk(sc)
+
         def fn():
-            pos, ids, _ = self.x.scan(sc["tab"], sc["inp"], sc["no"])
+            pos, ids, _ = self.x.scan(*key)
             return (pos[first:], ids[first:]) if n is None else (pos[first:first + n], ids[first:first + n])
         return fn
 
@@ -389,7 +497,8 @@ class Model:
             return Exp(E_STATE)
         s.scan["pending"] = False
         sc = s.scan
-        return Exp(OK, lambda: (self.x.count(sc["tab"], sc["inp"], sc["no"]), sc["over"]))
+        n = self._count(sc)
+        return Exp(OK, lambda: (n, sc["over"]))
 
     def _scan_ext(self, op, s):
         if self.tab is None:
@@ -407,7 +516,7 @@ class Model:
         if s.scan is None or s.scan["pending"]:
             return Exp(E_STATE)
         sc = s.scan
-        if op["first"] + op["n"] > self.x.count(sc["tab"], sc["inp"], sc["no"]):
+        if op["first"] + op["n"] > self._count(sc):
             return Exp(E_ARG)
         if sc["over"]:
             return Exp(E_OVERFLOW)
@@ -427,13 +536,14 @@ class Model:
         if self.tab is None:
             return Exp(E_STATE)
         sc = s.scan
-        if sc is not None and self.x.count(sc["tab"], sc["inp"], sc["no"]) == 0:
+        if sc is not None and self._count(sc) == 0:
             return Exp(OK, lambda: 0)                           # (n = 0: the checksum of nothing, whatever the slot holds)
         if sc is None or sc["pending"] or sc["gen"] != self.gen:
             return Exp(E_STATE)
         if sc["over"]:
             return Exp(E_OVERFLOW)
-        return Exp(OK, lambda: self.x.checksum(sc["tab"], sc["inp"], sc["no"], op["base"]))
+        key = self._sk(sc)
+        return Exp(OK, lambda: self.x.checksum(*key[:3], op["base"], key[3]))
 
     def _text(self, op, s):
         s.text = None
@@ -444,7 +554,7 @@ class Model:
             return Exp(E_STATE)
         if sc["over"]:
             return Exp(E_OVERFLOW)
-        s.text = (sc["tab"], sc["inp"], sc["no"], op["base"])
+        s.text = (sc["tab"], sc["inp"], sc["no"], op["base"], sc["filt"])      # (the filter state at emission: a later filter leaves the text alone)
         key = s.text
         return Exp(OK, lambda: self.x.text(*key))
 
@@ -480,7 +590,41 @@ class Model:
         sc = s.scan
         if s.doc[:3] != (sc["tab"], sc["inp"], sc["no"]):
             return None
-        return (sc["tab"], sc["inp"], sc["no"], s.doc[3])
+        return (sc["tab"], sc["inp"], sc["no"], s.doc[3], sc["filt"])
+
+    # -- the whole-word filter ------------------------------------------------
+    def _filter(self, op, s):
+        """pfac_records_filter_words with descriptor FILTERS[op["f"]]; op["heap"]: "own" = the heap the scan wrote (NULL
+        for a slot-owned one), "none" / "slot" = NULL / the slot's own heap, which for a scan into a caller's heap is
+        not the scan's.  The scan's state is judged before the arguments; among the arguments the header promises no
+        order, so a heap that is not the scan's (PFAC_E_ARG) together with an n_docs that is not the slot's
+        (PFAC_E_STATE) is undecided.  On any error the scan stays as it was."""
+        d = FILTERS[op["f"]]
+        sc = s.scan
+        st = self._pass_state(s, E_OVERFLOW)
+        bad_heap = sc is not None and sc["ext"] and op["heap"] != "own"
+        if st:
+            return Exp(st)
+        arg = {E_ARG} if bad_heap else set()
+        dkey = ""
+        if d["doc"] != "none":
+            if s.doc is None or d["doc"] == "wrong_n":
+                arg.add(E_STATE)                                # (offsets that are not this n_docs' are not looked at)
+            elif not offsets_ok(self.x.offsets(*s.doc), sc["no"]):
+                arg.add(E_ARG)
+            elif s.doc[:3] != (sc["tab"], sc["inp"], sc["no"]):
+                return Exp(None)                                # (another scan's offsets that happen to fit: not keyed)
+            else:
+                dkey = s.doc[3]
+        if arg:
+            return Exp(arg.pop() if len(arg) == 1 else None)
+        filt = tuple(sorted(set(sc["filt"]) | {self.x.applied(sc["tab"], op["f"], dkey)}))
+        if len(filt) > MAX_FILTERS:
+            return Exp(None)                                    # (legal, but a plan stops at MAX_FILTERS)
+        s.seq += 1                                              # a new record set: a selection made before is stale for both
+        sc["seq"], sc["filt"] = s.seq, filt                     # replaces, as after a new scan; it stays fetchable
+        n = self._count(sc)
+        return Exp(OK, lambda: n)
 
     def _segment(self, op, s):
         s.seg = None
@@ -513,7 +657,7 @@ class Model:
         sc = s.scan
         if op["entry"] > self.x.M(sc["tab"]):
             return Exp(E_ARG)
-        key = (sc["tab"], sc["inp"], sc["no"], op["entry"])
+        key = (sc["tab"], sc["inp"], sc["no"], op["entry"], sc["filt"])
         n = int(self.x.sel(*key)[0].size)
         if not op["own"] and op["small"]:
             return Exp(E_OVERFLOW if n > 0 else None, count=n)
@@ -564,8 +708,8 @@ class Model:
 
     def _rp_out(self, sel, rkey):
         if sel["kind"] == "whole":
-            t, i, no, entry = sel["key"]
-            return lambda: self.x.replace(t, i, no, entry, rkey)
+            t, i, no, entry, f = sel["key"]
+            return lambda: self.x.replace(t, i, no, entry, rkey, f)
         return lambda: self.x.docsel(*sel["key"], rkey)[4]
 
     def _replace(self, op, s, docs=False):
@@ -642,17 +786,19 @@ KINDS = {"load_table": 4, "set_flen": 1, "set_reps": 2, "scan_bytes": 9, "scan_s
          "packed": 4, "checksum": 4, "text": 5, "text_fetch": 3, "set_doc": 4, "segment": 4, "select": 4, "select_docs": 4, "replace": 4,
          "replace_docs": 4, "seg_fetch": 3, "sel_fetch": 3, "docsel_fetch": 3, "rp_fetch": 3, "rpd_fetch": 3, "set_stream": 2, "sync": 1,
          "reserve_grow": 3}
+WORD_KINDS = dict(KINDS, filter=9)      # the kinds of a plan with the whole-word filter (plan(seed, words=True))
+READERS = ("records", "packed", "checksum", "text", "scan_finish")          # what reads a finished scan, besides the passes
 
 
-def _propose(rng, m):
+def _propose(rng, m, kinds=KINDS):
     """One candidate operation, drawn with an eye on the model's state (so most candidates have real data behind them)
     but never filtered by it: the caller asks the model what the candidate is worth."""
     x = m.x
     slot = int(rng.integers(0, N_SLOTS))
     s = m.slots[slot]
     sc = s.scan
-    w = np.array(list(KINDS.values()), dtype=float)
-    kind = str(rng.choice(list(KINDS), p=w / w.sum()))
+    w = np.array(list(kinds.values()), dtype=float)
+    kind = str(rng.choice(list(kinds), p=w / w.sum()))
     op = dict(op=kind, slot=slot)
     if kind == "load_table":
         op.pop("slot")
@@ -672,7 +818,7 @@ def _propose(rng, m):
             cnt = x.count(tab, op["inp"], op["no"])
             op["cap"] = cnt // 2 if (kind == "scan_ext" and cnt >= 64 and rng.random() < 0.3) else cnt + cnt // 4 + 65536
     elif kind == "records":
-        total = x.count(sc["tab"], sc["inp"], sc["no"]) if sc else 5
+        total = m._count(sc) if sc else 5
         op["first"], op["n"] = _window(rng, total)
     elif kind in ("checksum", "text"):
         op["base"] = int(rng.choice(TEXT_BASES))
@@ -682,7 +828,7 @@ def _propose(rng, m):
     elif kind == "set_doc":
         if sc is None:
             return None
-        op.update(tab=sc["tab"], inp=sc["inp"], no=sc["no"], dkey=str(rng.choice(DOC_KEYS, p=[.4, .4, .1, .1])))
+        op.update(tab=sc["tab"], inp=sc["inp"], no=sc["no"], dkey=str(rng.choice(DOC_KEYS, p=[.4, .4, .1, .1] if kinds is KINDS else [.3, .3, .2, .2])))
     elif kind in PASSES:
         op["own"] = bool(rng.random() < 0.6)
         op["small"] = bool(not op["own"] and rng.random() < 0.25)
@@ -692,6 +838,9 @@ def _propose(rng, m):
     elif kind == "rp_fetch":
         total = int(s.rp["out"]().size) if s.rp else 3
         op["first"], op["n"] = _window(rng, total)
+    elif kind == "filter":
+        op["f"] = int(rng.integers(0, len(FILTERS)))
+        op["heap"] = str(rng.choice(["none", "slot"])) if sc and sc["ext"] and rng.random() < 0.3 else "own"
     elif kind == "set_stream":
         op["slot"] = 1
         op["share"] = not m.slots[1].shared
@@ -711,9 +860,10 @@ def _pass_op(kind, slot, own=True):
 PRODUCER_OF = {v: k for k, v in FETCH_OF.items()}
 
 
-def _prepare(rng, kind, slot):
-    """What a session does before pass `kind` on `slot` so that the pass has something to work on: steps that look at
-    the model when their turn comes and return an operation, or None when nothing is missing."""
+def _prepare(rng, kind, slot, docs=False):
+    """What a session does before pass `kind` on `slot` (or before a filter, with `docs` when it reads the slot's
+    offsets) so that it has something to work on: steps that look at the model when their turn comes and return an
+    operation, or None when nothing is missing."""
     def table(m):
         if m.tab is None:
             tab = str(rng.choice(sorted(TABLES)))
@@ -744,20 +894,48 @@ def _prepare(rng, kind, slot):
     if kind in ("replace", "replace_docs"):
         steps.append(lambda m: None if m.reps else dict(op="set_reps", rkey=str(rng.choice(REP_KEYS))))
     steps.append(scan)
-    if kind in ("segment", "select_docs", "replace_docs", "replace"):
+    if kind in ("segment", "select_docs", "replace_docs", "replace") or docs:
         steps.append(doc)
     if kind in ("replace", "replace_docs"):
         steps.append(sel)
     return steps
 
 
-def plan(seed, n_ops=PLAN_OPS):
-    """The plan of `seed`: a list of operations (dicts).  Deterministic; the model decides what each one is worth."""
-    rng = np.random.default_rng([seed, 0x53455353494F4E])
+def _after_filter(rng, slot):
+    """What a session does with a filtered scan: a reader of the scan, or a pass and the fetch of its result."""
+    what = str(rng.choice(READERS + PASSES))
+    if what in PASSES:
+        fetch = dict(op=FETCH_OF[what], slot=slot, **({"first": 0, "n": 1} if what == "replace" else {}))
+        return _prepare(rng, what, slot) + [_pass_op(what, slot), fetch]
+    if what == "records":
+        return [lambda m: dict(op="records", slot=slot, first=0, n=m._count(m.slots[slot].scan)) if m.slots[slot].scan else None]
+    if what in ("checksum", "text"):
+        return [dict(op=what, slot=slot, base=int(rng.choice(TEXT_BASES)))]
+    return [dict(op=what, slot=slot)]
+
+
+def _filter_step(rng, slot):
+    """A filter the session means to succeed: a descriptor drawn now; when its turn comes and the slot's offsets do
+    not allow it, one without documents instead."""
+    first, second = int(rng.integers(0, len(FILTERS))), int(rng.integers(0, 5))
+    assert all(FILTERS[k]["doc"] == ("none" if k < 5 else "slot") for k in range(10))
+
+    def step(m):
+        op = dict(op="filter", slot=slot, f=first, heap="own")
+        return op if m.predict(op).status == OK else dict(op, f=second)
+    return step
+
+
+def plan(seed, n_ops=PLAN_OPS, words=False):
+    """The plan of `seed`: a list of operations (dicts).  Deterministic; the model decides what each one is worth.
+    `words`: the second family of plans, in which the whole-word filter is one of the operations (the first family is
+    what it was before the filter existed, seed for seed)."""
+    rng = np.random.default_rng([seed, 0x53455353494F4E] + ([0x574F5244] if words else []))
+    kinds = WORD_KINDS if words else KINDS
     m = Model()
     ops, agenda = [], []
     while len(ops) < n_ops:
-        want_err = rng.random() < 1 / 8
+        want_err = rng.random() < (1 / 16 if words else 1 / 8)   # (words: the filter between a selection and its replace adds errors of its own)
         chosen = None
         while agenda and chosen is None and not want_err:      # what the session set out to do comes first
             cand = agenda.pop(0)
@@ -767,7 +945,7 @@ def plan(seed, n_ops=PLAN_OPS):
         for _ in range(60):
             if chosen is not None:
                 break
-            cand = _propose(rng, m)
+            cand = _propose(rng, m, kinds)
             if cand is None:
                 continue
             st = m.predict(cand).status
@@ -782,10 +960,36 @@ def plan(seed, n_ops=PLAN_OPS):
                 else:
                     prod = PRODUCER_OF[cand["op"]]
                     agenda = _prepare(rng, prod, cand["slot"]) + [_pass_op(prod, cand["slot"]), cand]
+            elif st != OK and not agenda and cand["op"] == "filter" and cand["heap"] == "own":
+                agenda = _prepare(rng, "filter", cand["slot"], docs=FILTERS[cand["f"]]["doc"] == "slot") + [cand]
         if chosen is None:
             continue
         st = m.apply(chosen).status
         ops.append(chosen)
+        if words:
+            slot = chosen.get("slot", 0)
+            f = _filter_step(rng, slot)
+            # a filtered scan is there to be read: most filters are followed by a reader or a pass ...
+            if st == OK and chosen["op"] == "filter" and rng.random() < 0.75:
+                agenda = _after_filter(rng, slot) + agenda
+            # ... results made before a filter are fetched after it ...
+            elif st == OK and chosen["op"] in PASSES and chosen.get("own") and rng.random() < 0.35:
+                agenda += [f, dict(op=FETCH_OF[chosen["op"]], slot=slot, **({"first": 0, "n": 1} if chosen["op"] == "replace" else {}))]
+            elif st == OK and chosen["op"] == "text" and rng.random() < 0.5:
+                agenda += [f, lambda m, slot=slot: dict(op="text_fetch", slot=slot, first=0, n=len(m.x.text(*m.slots[slot].text))) if m.slots[slot].text else None]
+            # ... an overflowed scan is PFAC_E_OVERFLOW ...
+            elif st == OK and chosen["op"] == "scan_ext" and m.slots[slot].scan["over"]:
+                agenda = [lambda m: None if m.flen else dict(op="set_flen"), dict(op="filter", slot=slot, f=int(rng.integers(0, 5)), heap="own")] + agenda
+            # ... bad offsets, then good ones ...
+            elif st == OK and chosen["op"] == "set_doc" and chosen["dkey"].startswith("bad") and rng.random() < 0.8:
+                good = dict(chosen, dkey=str(rng.choice(DOC_KEYS[:2])))
+                agenda = _prepare(rng, "filter", slot) + [dict(op="filter", slot=slot, f=int(rng.integers(5, 10)), heap="own"), good,
+                                                           dict(op="filter", slot=slot, f=int(rng.integers(5, 10)), heap="own")] + agenda
+            # ... and a fresh scan (mostly one with something to drop) is filtered before anything else looks at it, a
+            # caller's heap with the wrong pointer first
+            elif st == OK and chosen["op"] in ("scan_bytes", "scan_ext", "scan_finish") and not m.slots[slot].scan["over"] and rng.random() < (0.6 if m._count(m.slots[slot].scan) >= 16 else 0.15):
+                wrong = [dict(op="filter", slot=slot, f=int(rng.integers(0, 5)), heap=str(rng.choice(["none", "slot"])))] if chosen["op"] == "scan_ext" and rng.random() < 0.5 else []
+                agenda = _prepare(rng, "filter", slot, docs=rng.random() < 0.5) + wrong + [f] + agenda
         # a pass that left a slot-owned result: now and then another pass first, then the late fetch of this one's output
         if st == OK and chosen["op"] in PASSES and chosen.get("own") and rng.random() < 0.4:
             other = str(rng.choice([p for p in PASSES if p != chosen["op"]]))
@@ -812,9 +1016,9 @@ def plan(seed, n_ops=PLAN_OPS):
     return ops
 
 
-def shrink(seed, k, n_ops=PLAN_OPS):
+def shrink(seed, k, n_ops=PLAN_OPS, words=False):
     """The plan of `seed` with operation k onwards removed: cut a failing history down by hand."""
-    return plan(seed, n_ops)[:k]
+    return plan(seed, n_ops, words)[:k]
 
 
 # ---------------------------------------------------------------------------
@@ -875,7 +1079,7 @@ class Executor:
         self.g, self.m = g, model
         self.x = model.x
         self.bufs = [_SlotBufs() for _ in range(N_SLOTS)]
-        self.stats = dict(ops=0, errors=0, compared=0, widths=set(), staging=set(), variants=set(), statuses=set())
+        self.stats = dict(ops=0, errors=0, compared=0, filters=0, widths=set(), staging=set(), variants=set(), statuses=set())
         self.ids_direct = getattr(g, "states_are_ids", False)
 
     def ids(self, tab, states):
@@ -983,7 +1187,7 @@ class Executor:
 
     def do_checksum(self, op, exp, before):
         sc = before["scan"]
-        n = self.x.count(sc["tab"], sc["inp"], sc["no"]) if sc else 1
+        n = self.x.count(sc["tab"], sc["inp"], sc["no"], sc["filt"]) if sc else 1
         return int(self.g.checksum(n, op["base"], op["slot"], d_records=self.bufs[op["slot"]].rec))
 
     def do_text(self, op, exp, before):
@@ -1007,6 +1211,20 @@ class Executor:
             return exp.value()[0]
         return exp.count // 2 if exp.count is not None else 0   # (an overflow the model expects, else the call fails before it looks)
 
+    def do_filter(self, op, exp, before):
+        g, slot = self.g, op["slot"]
+        d, b, sc = FILTERS[op["f"]], self.bufs[slot], before["scan"]
+        tab = sc["tab"] if sc else (self.m.tab or "abc2")
+        heap = {"own": b.rec, "none": None, "slot": g.records_ptr(slot) or None}[op["heap"]]
+        nd = 0 if d["doc"] == "none" else self._n_docs(slot) + (d["doc"] == "wrong_n")
+        fmt = g.scan_format(slot) if exp.status == OK else None
+        n = int(g.filter_whole_words(slot, self.x.word_bytes(tab, d["ws"]), d["edges"], self.x.neighbour(tab, d["ws"], d["prev"]),
+                                     self.x.neighbour(tab, d["ws"], d["next"]), n_docs=nd, d_input=b.inp, d_records=heap))
+        assert fmt is None or g.scan_format(slot) == fmt, f"scan_format changed from {fmt} to {g.scan_format(slot)}"
+        assert g.last_count(slot) == n, f"last_count {g.last_count(slot)} after a filter that kept {n}"
+        self.stats["filters"] += 1
+        return n
+
     def do_segment(self, op, exp, before):
         g, slot = self.g, op["slot"]
         nd = self._n_docs(slot)
@@ -1020,7 +1238,7 @@ class Executor:
 
     def do_seg_fetch(self, op, exp, before):
         seg = self.m.slots[op["slot"]].seg
-        n, nd = (int(self.x.seg(*seg["key"])[0][-1]), int(self.x.offsets(*seg["key"]).size - 1)) if seg else (0, 1)
+        n, nd = (int(self.x.seg(*seg["key"])[0][-1]), int(self.x.offsets(*seg["key"][:4]).size - 1)) if seg else (0, 1)
         first, rec = self.g.segment_to_host(n, nd, op["slot"])
         return (first,) + self.recs(exp.tab, rec)
 
@@ -1057,7 +1275,7 @@ class Executor:
             return 0, 1
         if sel["kind"] == "whole":
             return int(self.x.sel(*sel["key"])[0].size), 1
-        return int(self.x.docsel(*sel["key"])[0][-1]), int(self.x.offsets(*sel["key"]).size - 1)
+        return int(self.x.docsel(*sel["key"])[0][-1]), int(self.x.offsets(*sel["key"][:4]).size - 1)
 
     def do_sel_fetch(self, op, exp, before):
         return self.recs(exp.tab, self.g.selection_to_host(self._sel_n(op["slot"])[0], op["slot"]))
@@ -1079,7 +1297,7 @@ class Executor:
             return int(call(**kw))
         cap = self._cap(op, exp)
         d_out = _alloc(g, cap + 64)
-        nd = int(self.x.offsets(*sel["key"]).size - 1) if docs and sel is not None and sel["kind"] == "docs" else 1
+        nd = int(self.x.offsets(*sel["key"][:4]).size - 1) if docs and sel is not None and sel["kind"] == "docs" else 1
         if docs:
             kw["d_out_offsets"] = _alloc(g, (nd + 1) * 8)
         n = int(call(d_out=d_out, out_cap=cap, **kw))

@@ -1,7 +1,8 @@
 """Sessions: ONE GpuMatcher context driven through long sequences of calls (tests/session.py) -- many tables under different
 kernel knobs, many sizes, two slots, passes in any order, results fetched late, documented errors in between -- every
 result compared bit for bit with what include/pfac.h promises for that history.  The random plans are the suite's seeds;
-the named sessions are histories random plans reach rarely.  Run with -m gpu on an MI355X.  Expectations come from the
+the named sessions are histories random plans reach rarely; half of the plans and the sessions at the end of this file
+have the whole-word filter among their calls.  Run with -m gpu on an MI355X.  Expectations come from the
 CPU oracle, llref, replref, docref, docreplref and the pattern files, never from the device.  No session aims at the
 scan's wait protocol: they provoke the errors the header documents, nothing else."""
 import gc
@@ -33,8 +34,17 @@ def scan(tab, inp, slot=0, no=None):
     return dict(op="scan_bytes", slot=slot, inp=inp, no=X.input_size(tab, inp) if no is None else no)
 
 
-def records(tab, inp, slot=0, no=None, first=0, n=None):
-    total = X.count(tab, inp, X.input_size(tab, inp) if no is None else no)
+def fkey(tab, *applied):
+    """The filter state of a scan of `tab` after the (descriptor, dkey) pairs `applied`."""
+    return tuple(sorted({X.applied(tab, f, dkey) for f, dkey in applied}))
+
+
+def flt(f, slot=0, heap="own"):
+    return dict(op="filter", slot=slot, f=f, heap=heap)
+
+
+def records(tab, inp, slot=0, no=None, first=0, n=None, f=()):
+    total = X.count(tab, inp, X.input_size(tab, inp) if no is None else no, f)
     return dict(op="records", slot=slot, first=first, n=total - first if n is None else n)
 
 
@@ -64,13 +74,14 @@ def run(ops, want=None):
         return S.run(g, ops, m, seed="named")
 
 
-@pytest.mark.parametrize("seed", S.SEEDS)
-def test_session(seed):
-    """One random plan on one context."""
-    ops = S.plan(seed)
+@pytest.mark.parametrize("seed,words", [(s, False) for s in S.SEEDS] + [(s, True) for s in S.WORD_SEEDS],
+                         ids=[str(s) for s in S.SEEDS] + [f"words-{s}" for s in S.WORD_SEEDS])
+def test_session(seed, words):
+    """One random plan on one context; `words`: a plan of the family that filters whole words."""
+    ops = S.plan(seed, words=words)
     with GpuMatcher(0, S.N_SLOTS) as g:
-        st = S.run(g, ops, S.Model(), seed=seed)
-    print(f"session {seed}: {st['ops']} operations ({st['errors']} documented errors), {st['compared']} records and bytes compared, "
+        st = S.run(g, ops, S.Model(), seed=f"{seed} (words)" if words else seed)
+    print(f"session {seed}{' (words)' if words else ''}: {st['ops']} operations ({st['errors']} documented errors), {st['compared']} records and bytes compared, "
           f"record widths {sorted(st['widths'])}, staging {sorted(st['staging'])}, {sorted(st['variants'])}")
 
 
@@ -263,4 +274,166 @@ def test_stream_change_between_a_selection_and_its_replace():
         entry = rnd % 3
         ops += [pss("select", slot=1, entry=entry), dict(op="set_stream", slot=1, share=rnd % 2 == 0), pss("replace", slot=1),
                 fetch("rp_fetch", slot=1, first=0, n=int(X.replace(t, 0, n, entry, "r0").size))]
+    run(ops, want=[S.OK] * len(ops))
+
+
+# ---------------------------------------------------------------------------
+# the whole-word filter as one call among many on a long-lived context
+
+def rp_n(t, inp, entry=0, rkey="r0", f=(), no=None):
+    return int(X.replace(t, inp, X.input_size(t, inp) if no is None else no, entry, rkey, f).size)
+
+
+def test_filter_in_buffers_sized_by_a_large_scan():
+    """A dense 300 007-byte scan filtered to nothing (every byte is a word byte and so is prev_byte: every tile's count
+    goes to 0), then 17 bytes and 64 tiles + 1 byte through filters and every pass and reader: scratch, index and
+    outputs are the large call's."""
+    t = "abc2"
+    wipe = fkey(t, (4, ""))
+    assert X.count(t, 0, 300_007, wipe) == 0 < X.count(t, 0, 300_007, fkey(t, (2, "")))
+    ops = load(t) + [scan(t, 0), doc(t, 0, "d0"), pss("segment"), pss("select"), pss("replace"), fetch("text", base=0), flt(2), records(t, 0, f=fkey(t, (2, ""))),
+                     flt(4), records(t, 0, f=wipe), fetch("checksum", base=0), fetch("text", base=0), pss("select_docs"), pss("replace_docs"),
+                     fetch("rpd_fetch"), dict(op="scan_finish", slot=0)]
+    for inp in (3, 2):
+        no = X.input_size(t, inp)
+        f1, f2 = fkey(t, (1, "")), fkey(t, (1, ""), (6, "d1"))
+        total = len(X.text(t, inp, no, 999_999_990, f1))
+        ops += [scan(t, inp), flt(1), records(t, inp, f=f1), fetch("packed"), fetch("checksum", base=999_999_990), fetch("text", base=999_999_990),
+                fetch("text_fetch", first=total // 2, n=total - total // 2), dict(op="scan_finish", slot=0),
+                doc(t, inp, "d1"), flt(6), records(t, inp, f=f2), pss("segment"), fetch("seg_fetch"), pss("select", entry=1), fetch("sel_fetch"),
+                pss("replace"), fetch("rp_fetch", first=0, n=rp_n(t, inp, 1, f=f2)), pss("select_docs"), fetch("docsel_fetch"), fetch("seg_fetch"),
+                pss("replace_docs"), fetch("rpd_fetch"), pss("segment", own=False), pss("select_docs", own=False), pss("replace_docs", own=False),
+                pss("select", own=False), pss("replace", own=False)]
+    st = run(ops, want=[S.OK] * len(ops))
+    assert st["compared"] > 100_000
+
+
+def test_scan_after_a_filter_reports_its_full_count_again():
+    """Filter, every reader of the scan, then the same input scanned again on the same slot: the unfiltered count and
+    records come back, from scan_bytes and from scan_start / scan_finish (whose count the filter had overwritten)."""
+    for t, inp, knobs in (("abc2", 2, {}), ("mid4", 2, dict(PFAC_LAG="2"))):
+        no = X.input_size(t, inp)
+        f1 = fkey(t, (1, ""))
+        cnt = X.count(t, inp, no)
+        assert 0 < X.count(t, inp, no, f1) < cnt
+        start = dict(op="scan_start", slot=0, inp=inp, no=no, cap=cnt + cnt // 4 + 65536)
+        ops = load(t, **knobs) + [scan(t, inp), flt(1), dict(op="scan_finish", slot=0), records(t, inp, f=f1), records(t, inp, f=f1, n=X.count(t, inp, no, f1) + 1),
+                                  fetch("packed"), fetch("checksum", base=0), fetch("text", base=0), pss("select"), pss("replace"),
+                                  scan(t, inp), dict(op="scan_finish", slot=0), records(t, inp), fetch("checksum", base=0), flt(1), flt(3),
+                                  start, dict(op="scan_finish", slot=0), records(t, inp), fetch("packed"), flt(2), dict(op="scan_finish", slot=0),
+                                  records(t, inp, f=fkey(t, (2, ""))), start, flt(1), dict(op="scan_finish", slot=0), dict(op="scan_finish", slot=0)]
+        run(ops, want=[0] * 3 + [0, 0, 0, 0, S.E_ARG] + [0] * 18 + [0, S.E_STATE, 0, 0])
+
+
+def test_results_made_before_a_filter_outlive_it():
+    """Segment, per-document selection, replace_docs and text, then a filter: every output is fetched unchanged, both
+    replaces refuse the selection made before, and a new selection is exact.  The same for select / replace."""
+    t, inp = "l2", 0
+    no = X.input_size(t, inp)
+    f3 = fkey(t, (3, ""))
+    txt = len(X.text(t, inp, no, 0))
+    E = S.E_STATE
+    ops = load(t, PFAC_FORCE_L2="1") + [scan(t, inp), doc(t, inp, "d0"), pss("segment"), pss("select_docs"), pss("replace_docs"), fetch("text", base=0),
+                                        flt(3), fetch("seg_fetch"), fetch("docsel_fetch"), fetch("sel_fetch"), fetch("rpd_fetch"),
+                                        fetch("rp_fetch", first=0, n=int(X.docsel(t, inp, no, "d0", (), "r0")[4].size)), fetch("text_fetch", first=0, n=txt),
+                                        pss("replace_docs"), pss("replace"), fetch("sel_fetch"), pss("select_docs"), fetch("docsel_fetch"), pss("replace_docs"),
+                                        fetch("rp_fetch", first=0, n=int(X.docsel(t, inp, no, "d0", f3, "r0")[4].size)),
+                                        pss("select", entry=2), pss("replace"), flt(1), fetch("sel_fetch"), fetch("rp_fetch", first=0, n=rp_n(t, inp, 2, f=f3)),
+                                        pss("replace"), pss("replace_docs"), fetch("rp_fetch", first=0, n=1), pss("select", entry=2), fetch("sel_fetch"), pss("replace"),
+                                        fetch("rp_fetch", first=0, n=rp_n(t, inp, 2, f=fkey(t, (3, ""), (1, ""))))]
+    run(ops, want=[0] * 3 + [0] * 13 + [E, E, 0, 0, 0, 0, 0] + [0, 0, 0, 0, 0, E, E, E, 0, 0, 0, 0])
+
+
+def test_filter_of_a_scan_into_the_callers_heap():
+    """A caller's heap and a caller's input: NULL (the slot's heap) and the slot's own heap are not the scan's --
+    PFAC_E_ARG, records still unfiltered; the right pointers filter exactly; an overflowed scan is PFAC_E_OVERFLOW."""
+    t, inp = "mid4", 2
+    no = X.input_size(t, inp)
+    cnt = X.count(t, inp, no)
+    f1 = fkey(t, (1, ""))
+    ext = lambda cap: dict(op="scan_ext", slot=0, inp=inp, no=no, cap=cap)      # noqa: E731
+    A = S.E_ARG
+    ops = load(t) + [scan(t, 1), ext(cnt + cnt // 4 + 65536), flt(1, heap="none"), records(t, inp), flt(1, heap="slot"), records(t, inp), fetch("checksum", base=0),
+                     flt(1), records(t, inp, f=f1), fetch("packed"), fetch("text", base=0), pss("select"), pss("replace", own=False), flt(3, heap="none"),
+                     records(t, inp, f=f1), flt(3), records(t, inp, f=fkey(t, (1, ""), (3, ""))),
+                     ext(cnt // 2), flt(1), flt(1, heap="none"), records(t, inp, n=1), scan(t, inp), flt(1), records(t, inp, f=f1)]
+    run(ops, want=[0] * 3 + [0, 0, A, 0, A, 0, 0, 0, 0, 0, 0, 0, 0, A, 0, 0, 0, 0, S.E_OVERFLOW, S.E_OVERFLOW, S.E_OVERFLOW, 0, 0, 0])
+
+
+def test_filter_across_table_changes():
+    """Width 2, then 8, then 4 on one heap: the filtered records of the earlier scan stay fetchable in their width after
+    an upload, while the filter is refused until the next scan AND the new table's lengths."""
+    E = S.E_STATE
+    a, w, m4 = fkey("abc2", (1, "")), fkey("wide8", (1, "")), fkey("mid4", (2, ""))
+    up = lambda tab, **knobs: dict(op="load_table", tab=tab, knob=k(tab, **knobs))      # noqa: E731
+    ops = load("abc2") + [scan("abc2", 0), flt(1), records("abc2", 0, f=a), up("wide8", PFAC_WIDE="1"), records("abc2", 0, f=a, first=5, n=1000), fetch("packed"),
+                          flt(1), dict(op="set_flen"), flt(1), records("abc2", 0, f=a, n=7), scan("wide8", 1), flt(1), records("wide8", 1, f=w),
+                          fetch("checksum", base=0), up("mid4"), records("wide8", 1, f=w), flt(2), scan("mid4", 2), flt(2), dict(op="set_flen"), flt(2),
+                          records("mid4", 2, f=m4), fetch("packed"), dict(op="set_reps", rkey="r1"), pss("select"), pss("replace")]
+    st = run(ops, want=[0] * 3 + [0, 0, 0, 0, 0, 0, E, 0, E, 0, 0, 0, 0, 0, 0, 0, E, 0, E, 0, 0, 0, 0, 0, 0, 0])
+    assert st["widths"] == {2, 4, 8}
+
+
+def test_filter_after_a_reserve_and_on_a_pending_scan():
+    t = "mid4"
+    E = S.E_STATE
+    cnt = X.count(t, 2, X.input_size(t, 2))
+    f1 = fkey(t, (1, ""))
+    grow = lambda which, n: dict(op="reserve_grow", slot=0, which=which, k=n)      # noqa: E731
+    start = dict(op="scan_start", slot=0, inp=2, no=X.input_size(t, 2), cap=cnt + cnt // 4 + 65536)
+    ops = load(t) + [scan(t, 2), flt(1), grow("records", 1), flt(1), records(t, 2, f=f1, n=1), scan(t, 2), records(t, 2), flt(1), records(t, 2, f=f1),
+                     grow("input", 2), flt(3), scan(t, 1), flt(3), records(t, 1, f=fkey(t, (3, ""))),
+                     start, flt(1), dict(op="scan_finish", slot=0), records(t, 2), flt(1), records(t, 2, f=f1), start, grow("both", 3), flt(1),
+                     dict(op="scan_finish", slot=0), scan(t, 2), flt(1), records(t, 2, f=f1)]
+    run(ops, want=[0] * 3 + [0, 0, 0, E, E, 0, 0, 0, 0, 0, E, 0, 0, 0, 0, E, 0, 0, 0, 0, 0, 0, E, E, 0, 0, 0])
+
+
+def test_filter_with_bad_offsets_then_good_ones_and_composition():
+    """Bad offsets leave the scan alone and the next filter exact; left-with-documents and right-without compose; new
+    offsets between a filter and the per-document passes; an n_docs that is not the slot's."""
+    t, inp = "l2", 1
+    A, E = S.E_ARG, S.E_STATE
+    f5, both = fkey(t, (5, "d0")), fkey(t, (5, "d0"), (3, ""))
+    ops = load(t, PFAC_FORCE_L2="1") + [scan(t, inp), flt(5), flt(10), doc(t, inp, "bad_end"), flt(5), records(t, inp), doc(t, inp, "bad_order"), flt(7),
+                                        records(t, inp), fetch("checksum", base=0), doc(t, inp, "d0"), flt(10), flt(5), records(t, inp, f=f5), flt(3),
+                                        records(t, inp, f=both), flt(5), records(t, inp, f=both), doc(t, inp, "d1"), pss("select_docs"),
+                                        fetch("docsel_fetch"), doc(t, inp, "d0"), pss("replace_docs"), pss("select_docs"), pss("replace_docs"), fetch("rpd_fetch"),
+                                        doc(t, inp, "bad_end"), flt(6), pss("segment"), doc(t, inp, "d1"), flt(6), pss("segment"), fetch("seg_fetch"),
+                                        records(t, inp, f=fkey(t, (5, "d0"), (3, ""), (6, "d1")))]
+    run(ops, want=[0] * 3 + [0, E, E, 0, A, 0, 0, A, 0, 0, 0, E, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, E, 0, 0, 0, 0, A, A, 0, 0, 0, 0, 0])
+
+
+@pytest.mark.parametrize("share", [True, False], ids=["shared-stream", "own-streams"])
+def test_two_slots_filtered_differently(share):
+    """Two slots with scans of the same input under different filters, interleaved; and a change of stream between a
+    filter and the selection that reads what it wrote."""
+    t = "l2"
+    n1 = (300_007 * 5) // 8
+    fa, fb, fb2 = fkey(t, (1, "")), fkey(t, (2, "")), fkey(t, (2, ""), (3, ""))
+    ops = [dict(op="set_stream", slot=1, share=share)] if share else []
+    ops += load(t, PFAC_FORCE_L2="1") + [scan(t, 0, slot=0), scan(t, 0, slot=1, no=n1), flt(1, slot=0), flt(2, slot=1), records(t, 0, slot=0, f=fa),
+                                         records(t, 0, slot=1, no=n1, f=fb), pss("select", slot=0), flt(3, slot=1),
+                                         dict(op="set_stream", slot=1, share=not share), pss("select", slot=1, entry=X.M(t)), fetch("sel_fetch", slot=1),
+                                         pss("replace", slot=0), pss("replace", slot=1), fetch("sel_fetch", slot=0),
+                                         fetch("rp_fetch", slot=0, first=0, n=rp_n(t, 0, 0, f=fa)),
+                                         fetch("rp_fetch", slot=1, first=0, n=rp_n(t, 0, X.M(t), f=fb2, no=n1)),
+                                         dict(op="scan_finish", slot=0), dict(op="scan_finish", slot=1), fetch("checksum", slot=0, base=0),
+                                         fetch("checksum", slot=1, base=999_999_990)]
+    run(ops, want=[S.OK] * len(ops))
+
+
+@pytest.mark.parametrize("t,inp,knobs,a,b", [("cclass", 0, {}, 1, 9), ("negcc", 0, dict(PFAC_FORCE_L2="1", PFAC_DENSE="1"), 1, 9),
+                                             ("nlesc", 0, dict(PFAC_DENSE="1"), 1, 9), ("dups", 1, {}, 2, 6)], ids=["cclass", "negcc", "nlesc", "dups"])
+def test_class_and_escaped_tables_through_the_filter(t, inp, knobs, a, b):
+    """Multi-id final states, a record or two per byte, newline and NUL patterns, final states of length -1: filter,
+    records, text, select, replace -- then a second filter with documents and the per-document passes."""
+    no = X.input_size(t, inp)
+    f1, f2 = fkey(t, (a, "")), fkey(t, (a, ""), (b, "d0"))
+    assert 0 < X.count(t, inp, no, f2) < X.count(t, inp, no, f1) < X.count(t, inp, no)
+    ops = load(t, **knobs) + [scan(t, inp), flt(a), records(t, inp, f=f1), fetch("text", base=999_999_990), fetch("checksum", base=0), pss("select"),
+                              fetch("sel_fetch"), pss("replace"), fetch("rp_fetch", first=0, n=rp_n(t, inp, f=f1)), doc(t, inp, "d0"), flt(b),
+                              records(t, inp, f=f2), pss("segment"), fetch("seg_fetch"), pss("select_docs"), fetch("docsel_fetch"), pss("replace_docs"),
+                              fetch("rpd_fetch")]
+    if S.expectations().width(t, k(t, **knobs)) != 8:
+        ops.append(fetch("packed"))
     run(ops, want=[S.OK] * len(ops))

@@ -2,7 +2,12 @@
 every operation, table, record width, status, slot and stream arrangement, and every (producer pass, other pass, late
 fetch) order; the executor and the model run every plan against CpuDevice, a stand-in for GpuMatcher that implements the
 contract of include/pfac.h in the most obvious way; and each of CpuDevice's switchable defects makes a plan fail at or
-after the first operation the defect touches -- the harness has teeth without a kernel being mutated."""
+after the first operation the defect touches -- the harness has teeth without a kernel being mutated.  The plans come in
+two families: those of S.SEEDS, pinned by a digest to what they were before the whole-word filter existed, and those of
+S.WORD_SEEDS, in which the filter is an operation like any other."""
+import collections
+import hashlib
+import json
 import os
 
 import numpy as np
@@ -44,11 +49,18 @@ class _CpuSlot:
         self.doc_gen = 0
         self.sel = self.seg = self.rp = self.rpd = None
         self.text = b""
+        self.text_base = 0
         self.prev_first = 0
+        self.heap = CpuBuf(16)     # stands for the slot's own record heap where a pointer is compared
+        self.last_n = 0
 
 
 DEFECTS = ("stale_selection_survives_upload", "late_segment_returns_selection", "smaller_scan_returns_tail",
            "overflowed_scan_hands_out_records", "stale_doc_first_of_empty_trailing_document", "slot1_exit_is_slot0s")
+# ... and those of the whole-word filter, which only the plans of S.WORD_SEEDS can meet
+WORD_DEFECTS = ("count_stays_the_unfiltered_one", "selection_survives_filter", "refused_filter_filters_anyway",
+                "second_filter_replaces_first", "filter_ignores_neighbour_bytes", "filter_ignores_document_offsets",
+                "slot1_filter_changes_slot0", "text_follows_a_later_filter")
 
 
 class CpuDevice:
@@ -138,6 +150,9 @@ class CpuDevice:
     def stream_handle(self, slot=0):
         return 1 + slot
 
+    def records_ptr(self, slot=0):
+        return self.slots[slot].heap if self.slots[slot].rec_cap else 0
+
     def set_stream(self, slot, handle):
         pass
 
@@ -157,7 +172,8 @@ class CpuDevice:
         prev = s.scan
         s.seq += 1
         s.scan = dict(tab=self.tab, width=self.width, gen=self.gen, data=self.x.input(self.tab, inp), no=n_owned, pos=pos, ids=ids, lens=lens,
-                      over=pos.size > cap, pending=True, seq=s.seq, prev=(prev["pos"], prev["ids"]) if prev else None)
+                      over=pos.size > cap, pending=True, seq=s.seq, prev=(prev["pos"], prev["ids"]) if prev else None,
+                      heap=d_records if d_records is not None else s.heap, full=(pos, ids, lens))
 
     def scan_finish(self, slot=0, allow_overflow=False):
         s = self.slots[slot]
@@ -166,7 +182,14 @@ class CpuDevice:
         s.scan["pending"] = False
         if s.scan["over"] and not allow_overflow:
             raise _err(S.E_OVERFLOW, "overflow")
-        return int(s.scan["pos"].size), s.scan["over"]
+        n = int(s.scan["pos"].size)
+        if n != s.scan["full"][0].size and self._defect("count_stays_the_unfiltered_one"):
+            n = int(s.scan["full"][0].size)
+        s.last_n = n
+        return n, s.scan["over"]
+
+    def last_count(self, slot=0):
+        return self.slots[slot].last_n
 
     def capacity_hint(self, slot=0):
         n = int(self.slots[slot].scan["pos"].size)
@@ -179,7 +202,7 @@ class CpuDevice:
         sc = self.slots[slot].scan
         if sc is None:
             raise _err(S.E_STATE, "no scan yet")
-        return sc["width"], (sc["no"] + 4095) // 4096, int(sc["pos"].size)
+        return sc["width"], (sc["no"] + 4095) // 4096, int(sc["full"][0].size)      # (used: what the scan wrote, filtered or not)
 
     def _finished(self, slot, overflow_status):
         sc = self.slots[slot].scan
@@ -199,7 +222,10 @@ class CpuDevice:
         if n == 0:
             return np.empty(0, dtype=RECORD_DTYPE)
         sc = self._finished(slot, 0)
-        if first + n > sc["pos"].size:
+        bound = sc["pos"].size
+        if bound != sc["full"][0].size and first + n > bound and self._defect("count_stays_the_unfiltered_one"):
+            bound = sc["full"][0].size
+        if first + n > bound:
             raise _err(S.E_ARG, "beyond the match count")
         if sc["over"] and not self._defect("overflowed_scan_hands_out_records"):
             raise _err(S.E_OVERFLOW, "the scan overflowed")
@@ -214,10 +240,12 @@ class CpuDevice:
             raise _err(S.E_STATE, "not compact")
         sc = self.slots[slot].scan
         pos, ids = sc["pos"], sc["ids"]
-        words = ((pos & 4095) | (ids << 12)).astype(np.uint16 if rb == 2 else np.uint32)
-        cnt = np.bincount(pos >> 12, minlength=nt).astype(np.uint64)
-        start = (np.cumsum(cnt) - cnt).astype(np.uint64)
-        return words, start | (cnt << np.uint64(40))
+        full = np.bincount(sc["full"][0] >> 12, minlength=nt)
+        start = np.cumsum(full) - full                          # every tile's run begins where the scan put it
+        cnt = np.bincount(pos >> 12, minlength=nt)
+        words = np.zeros(used, dtype=np.uint16 if rb == 2 else np.uint32)
+        words[start[pos >> 12] + np.arange(pos.size) - (np.cumsum(cnt) - cnt)[pos >> 12]] = (pos & 4095) | (ids << 12)
+        return words, start.astype(np.uint64) | (cnt.astype(np.uint64) << np.uint64(40))
 
     def checksum(self, n, base=0, slot=0, d_records=None):
         if self.tab is None:
@@ -239,9 +267,13 @@ class CpuDevice:
             raise _err(S.E_STATE, "earlier table")
         if sc["over"]:
             raise _err(S.E_OVERFLOW, "overflow")
-        self.slots[slot].text = "".join("At position %4d, match pattern %d\n" % (p + base, k)
-                                        for p, k in zip(sc["pos"].tolist(), sc["ids"].tolist())).encode()
+        self.slots[slot].text = self._text(sc, base)
+        self.slots[slot].text_base = base
         return len(self.slots[slot].text)
+
+    @staticmethod
+    def _text(sc, base):
+        return "".join("At position %4d, match pattern %d\n" % (p + base, k) for p, k in zip(sc["pos"].tolist(), sc["ids"].tolist())).encode()
 
     def text_to_host(self, n_bytes, slot=0, first=0):
         if first + n_bytes > len(self.slots[slot].text):
@@ -272,6 +304,63 @@ class CpuDevice:
         doc = np.searchsorted(off, sc["pos"], side="right") - 1
         keep = sc["pos"] + sc["lens"] <= off[doc + 1]
         return off, doc[keep], sc["pos"][keep], sc["ids"][keep], sc["lens"][keep]
+
+    # -- the whole-word filter ------------------------------------------------
+    def filter_whole_words(self, slot=0, word_bytes=None, edges="both", prev_byte=-1, next_byte=-1, n_docs=0, d_doc_offsets=None,
+                           d_input=None, d_records=None):
+        s = self.slots[slot]
+        sc = self._pass_scan(slot, S.E_OVERFLOW)
+        if (d_records if d_records is not None else s.heap) is not sc["heap"]:
+            raise _err(S.E_ARG, "not the heap of the slot's last scan")
+        off = None
+        if n_docs:
+            if s.doc is None or n_docs != s.doc.size - 1:
+                raise _err(S.E_STATE, "no document offsets with this n_docs")
+            if not S.offsets_ok(s.doc, sc["no"]):
+                if sc["pos"].size and self._defect("refused_filter_filters_anyway"):
+                    self._apply_filter(s, sc, word_bytes, edges, -1, -1, None)
+                raise _err(S.E_ARG, "bad offsets")
+            off = s.doc.astype(np.int64)
+            if self._cuts(sc, word_bytes, prev_byte, next_byte, None)[off].any() and self._defect("filter_ignores_document_offsets"):
+                off = None
+        if (prev_byte, next_byte) != (-1, -1) and self._defect("filter_ignores_neighbour_bytes"):
+            prev_byte = next_byte = -1
+        n = self._apply_filter(s, sc, word_bytes, edges, prev_byte, next_byte, off)
+        if not (s.sel is not None and s.sel["seq"] == sc["seq"] and self._defect("selection_survives_filter")):
+            s.seq += 1                                          # a new record set: what selected from the old one is stale
+            sc["seq"] = s.seq
+        other = self.slots[0].scan
+        if slot == 1 and other is not None and other["pos"].size and self._defect("slot1_filter_changes_slot0"):
+            half = other["pos"].size // 2
+            other["pos"], other["ids"], other["lens"] = other["pos"][:half], other["ids"][:half], other["lens"][:half]
+        if s.text and "text_follows_a_later_filter" in self.defects and self._text(sc, s.text_base) != s.text and self._defect("text_follows_a_later_filter"):
+            s.text = self._text(sc, s.text_base)
+        s.last_n = n
+        return n
+
+    @staticmethod
+    def _cuts(sc, word_bytes, prev_byte, next_byte, off):
+        """bool[n_avail + 1]: a word runs on across i (W of the byte before i and of the byte at i), no document starts there."""
+        isw = np.zeros(256, dtype=bool)
+        isw[list(b"0123456789ABCDEFGHIJKLMNOPQRSTUVWXYZ_abcdefghijklmnopqrstuvwxyz" if word_bytes is None else word_bytes)] = True
+        w = isw[sc["data"]]
+        cut = np.concatenate(([prev_byte >= 0 and isw[prev_byte]], w)) & np.concatenate((w, [next_byte >= 0 and isw[next_byte]]))
+        if off is not None:
+            cut[off] = False
+        return cut
+
+    def _apply_filter(self, s, sc, word_bytes, edges, prev_byte, next_byte, off):
+        cut = self._cuts(sc, word_bytes, prev_byte, next_byte, off)
+        pos, ids, lens = sc["pos"], sc["ids"], sc["lens"]
+        if pos.size != sc["full"][0].size and self._defect("second_filter_replaces_first"):
+            pos, ids, lens = sc["full"]
+        keep = np.ones(pos.size, dtype=bool)
+        if edges in ("left", "both"):
+            keep &= ~cut[pos]
+        if edges in ("right", "both"):
+            keep &= ~cut[pos + lens]
+        sc["pos"], sc["ids"], sc["lens"] = pos[keep], ids[keep], lens[keep]
+        return int(keep.sum())
 
     def _first(self, s, first):
         if first.size >= 3 and first.size and self.slots[s].doc[-1] == self.slots[s].doc[-2] and self._defect("stale_doc_first_of_empty_trailing_document"):
@@ -419,12 +508,31 @@ def plans():
     return {seed: S.plan(seed) for seed in S.SEEDS}
 
 
-def test_plans_are_deterministic_and_well_formed(plans):
+@pytest.fixture(scope="module")
+def word_plans():
+    return {seed: S.plan(seed, words=True) for seed in S.WORD_SEEDS}
+
+
+# SHA-256 of json.dumps([plan(seed) for seed in SEEDS], sort_keys=True) at the commit before the filter joined the
+# harness (with the pool's pattern lines in a fixed order, see _gen_lines): the first family has not moved.
+OLD_PLANS_SHA256 = "e756864a7526abf17871316573c9079f43bc1106d0403266a50f5130050b937a"
+
+
+def test_the_plans_without_the_filter_are_what_they_were(plans):
+    assert [seed for seed in plans] == S.SEEDS and len(S.SEEDS) == 24
+    assert hashlib.sha256(json.dumps([plans[seed] for seed in S.SEEDS], sort_keys=True).encode()).hexdigest() == OLD_PLANS_SHA256
+    assert not any(op["op"] == "filter" for ops in plans.values() for op in ops)
+
+
+def test_plans_are_deterministic_and_well_formed(plans, word_plans):
     for seed in S.SEEDS[:4]:
         assert S.plan(seed) == plans[seed]
         assert S.shrink(seed, 17) == plans[seed][:17]
-    assert plans[0] != plans[1]
-    for seed, ops in plans.items():
+    for seed in S.WORD_SEEDS[:4]:
+        assert S.plan(seed, words=True) == word_plans[seed] != plans[seed]
+        assert S.shrink(seed, 17, words=True) == word_plans[seed][:17]
+    assert plans[0] != plans[1] and word_plans[0] != word_plans[1]
+    for seed, ops in list(plans.items()) + list(word_plans.items()):
         assert len(ops) == S.PLAN_OPS
         m = S.Model()
         for k, op in enumerate(ops):
@@ -482,10 +590,117 @@ def test_suite_plans_reach_everything(plans):
     assert sizes >= {0, 1, 17, 4095, 4097, S.GROUP - 1, S.GROUP + 1, 300_007, 2_000_003}
 
 
+def _walk(plans):
+    """(seed, k, op, status, model after the operation, the slot's scan before it) over the plans."""
+    for seed, ops in plans.items():
+        m = S.Model()
+        for k, op in enumerate(ops):
+            sc = m.slots[op.get("slot", 0)].scan
+            before = dict(sc) if sc else None
+            yield seed, k, op, m.apply(op).status, m, before
+
+
+def test_word_plans_reach_everything(word_plans):
+    """The filter-bearing family: every table filtered under every record width it can have, a caller's heap, both slots,
+    both stream arrangements, every document key, every status from a filter; after an OK filter every pass and every
+    reader; every slot-owned result kind (and the text) made before an OK filter and fetched after it."""
+    x = S.expectations()
+    kinds, filtered, ext, slots, streams, dkeys, statuses, after, late, used = set(), set(), set(), set(), set(), set(), set(), set(), set(), set()
+    errs = total = 0
+    fresh = {}                                                  # slot -> operations since its last OK filter, None before one
+    made = {}                                                   # (slot, fetch kind) -> an OK filter has run since the result was made
+    seed_now = None
+    for seed, k, op, st, m, before in _walk(word_plans):
+        if seed != seed_now:
+            seed_now, fresh, made = seed, {}, {}
+        total += 1
+        errs += st != S.OK
+        kinds.add(op["op"])
+        slot = op.get("slot", 0)
+        if op["op"] == "filter":
+            statuses.add(st)
+            if st == S.OK:
+                sc = m.slots[slot].scan
+                filtered.add((sc["tab"], x.width(sc["tab"], sc["knob"])))
+                ext.add(sc["ext"])
+                slots.add(slot)
+                streams.add(m.slots[1].shared)
+                dkeys |= {one[4] for one in sc["filt"]}
+                used.add(op["f"])
+                fresh[slot] = 0
+                for key in made:
+                    if key[0] == slot:
+                        made[key] = True
+        elif st == S.OK and fresh.get(slot) is not None and ("slot" in op or op["op"] in S.READERS):
+            if op["op"] in S.PASSES + S.READERS and fresh[slot] <= 3 and m.slots[slot].scan and m.slots[slot].scan["filt"]:
+                after.add(op["op"])
+            fresh[slot] += 1
+        if st == S.OK and op["op"] in S.PASSES and op["own"]:
+            made[(slot, S.FETCH_OF[op["op"]])] = False
+            if op["op"] == "select_docs":
+                made[(slot, "sel_fetch")] = False
+            if op["op"] == "replace_docs":
+                made[(slot, "rp_fetch")] = False
+        if st == S.OK and op["op"] == "text":
+            made[(slot, "text_fetch")] = False
+        if st == S.OK and made.get((slot, op["op"])):
+            late.add(op["op"])
+    assert kinds == set(S.WORD_KINDS), set(S.WORD_KINDS) - kinds
+    want = {(t, x.width(t, knob)) for t in S.TABLES for knob in S.TABLES[t]["knobs"]}
+    assert {w for _, w in want} == {2, 4, 8} and filtered == want, sorted(want - filtered)
+    assert ext == {True, False} and slots == {0, 1} and streams == {True, False}
+    assert dkeys >= {"", "d0", "d1"}, dkeys
+    assert statuses == {S.OK, S.E_ARG, S.E_STATE, S.E_OVERFLOW}, statuses
+    assert used == {f for f, d in enumerate(S.FILTERS) if d["doc"] != "wrong_n"}, "a descriptor of the pool is never applied"
+    assert after >= set(S.PASSES + S.READERS), sorted(set(S.PASSES + S.READERS) - after)
+    assert late >= set(S.FETCH_OF.values()) | {"text_fetch"}, sorted((set(S.FETCH_OF.values()) | {"text_fetch"}) - late)
+    assert 0.08 < errs / total < 0.2, f"{errs} of {total} operations are illegal: about one in eight was the plan"
+    # the bad offsets reach the filter too: each refused with PFAC_E_ARG at least once
+    refused = {m.slots[op["slot"]].doc[3] for _, _, op, st, m, _ in _walk(word_plans)
+               if op["op"] == "filter" and st == S.E_ARG and S.FILTERS[op["f"]]["doc"] == "slot" and m.slots[op["slot"]].doc}
+    assert refused >= {"bad_end", "bad_order"}, refused
+
+
+def test_word_plans_filter_something_but_not_everything(word_plans):
+    """By the reference alone: at least half of the suite's OK filter operations keep a count strictly between 0 and the
+    scan's unfiltered count, and for every table at least one does -- the filter is neither the identity nor a wipe."""
+    x = S.expectations()
+    ok, mid = collections.Counter(), collections.Counter()
+    for seed, k, op, st, m, before in _walk(word_plans):
+        if op["op"] == "filter" and st == S.OK:
+            sc = m.slots[op["slot"]].scan
+            ok[sc["tab"]] += 1
+            mid[sc["tab"]] += 0 < m._count(sc) < x.count(sc["tab"], sc["inp"], sc["no"])
+    print({t: (mid[t], ok[t]) for t in sorted(ok)})
+    assert 2 * sum(mid.values()) >= sum(ok.values()) > 100, (sum(mid.values()), sum(ok.values()))
+    assert all(mid[t] >= 1 for t in S.TABLES), {t: mid[t] for t in S.TABLES}
+
+
+def test_filters_compose_by_intersection_in_the_reference():
+    """The model's filter state: sorted distinct descriptors, the same records in whatever order they were applied."""
+    x = S.expectations()
+    t, i, no = "abc2", 2, S.GROUP + 1
+    a, b = x.applied(t, 2, ""), x.applied(t, 3, "")
+    full, fa, fb, fab = x.scan(t, i, no), x.scan(t, i, no, (a,)), x.scan(t, i, no, (b,)), x.scan(t, i, no, tuple(sorted((a, b))))
+    assert 0 < fab[0].size < min(fa[0].size, fb[0].size) < full[0].size
+    assert set(zip(fab[0].tolist(), fab[1].tolist())) == set(zip(fa[0].tolist(), fa[1].tolist())) & set(zip(fb[0].tolist(), fb[1].tolist()))
+    m = S.Model()
+    for op in [dict(op="load_table", tab=t, knob=S.TABLES[t]["knobs"][0]), dict(op="set_flen"), dict(op="scan_bytes", slot=0, inp=i, no=no),
+               dict(op="filter", slot=0, f=3, heap="own"), dict(op="filter", slot=0, f=2, heap="own"), dict(op="filter", slot=0, f=3, heap="own")]:
+        assert m.apply(op).status == S.OK
+    assert m.slots[0].scan["filt"] == tuple(sorted((a, b)))
+
+
 @pytest.mark.parametrize("seed", S.SEEDS)
 def test_plan_passes_on_the_cpu_device(seed, plans):
     stats = S.run(CpuDevice(), plans[seed], S.Model(), seed=seed)
     assert stats["ops"] == S.PLAN_OPS and stats["errors"] > 0
+
+
+@pytest.mark.parametrize("seed", S.WORD_SEEDS)
+def test_word_plan_passes_on_the_cpu_device(seed, word_plans):
+    stats = S.run(CpuDevice(), word_plans[seed], S.Model(), seed=f"{seed} (words)")
+    assert stats["ops"] == S.PLAN_OPS and stats["errors"] > 0 and stats["filters"] > 0
 
 
 def first_touch(seed, ops, defect):
@@ -503,10 +718,11 @@ def first_touch(seed, ops, defect):
     return touched, None
 
 
-@pytest.mark.parametrize("defect", DEFECTS)
-def test_every_defect_is_caught(defect, plans):
+@pytest.mark.parametrize("defect", DEFECTS + WORD_DEFECTS)
+def test_every_defect_is_caught(defect, plans, word_plans):
     caught = []
-    for seed, ops in plans.items():
+    family = {f"{seed} (words)": ops for seed, ops in word_plans.items()} if defect in WORD_DEFECTS else plans
+    for seed, ops in family.items():
         touched, failed = first_touch(seed, ops, defect)
         assert failed is None or (touched is not None and failed >= touched), f"seed {seed}: failed at {failed} before the defect acted ({touched})"
         if failed is not None:
