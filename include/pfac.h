@@ -323,6 +323,55 @@ int pfac_records_packed_device(pfac_ctx *ctx, int slot, const void *d_records, v
 int pfac_records_checksum(pfac_ctx *ctx, int slot, const void *d_records, uint64_t n, uint64_t base,
                           uint64_t *checksum);
 
+/* How often did each pattern match?  The histogram of the FINAL STATES of the slot's last finished scan, computed on the
+ * GPU from the record heap and the tile index (the bytes the checksum reads; no input byte is read):
+ *   counts[s] (+)= number of records whose final state is s,  0 <= s < n_states.
+ * The heap is read through the tile index, so after pfac_records_filter_words the kept records are what is counted.
+ * *n_counted = the scan's current match count = the sum of the counts added.  The host turns states into pattern ids
+ * (idmap[s]; for character-class tables every id of outputs->ids[first[s] .. first[s+1])).
+ *   d_records  NULL = the slot's heap; else the heap the scan wrote (any other pointer: PFAC_E_ARG)
+ *   d_counts   NULL = a slot-owned buffer (fetched with pfac_state_counts_d2h); else a device pointer, 8-B aligned, of
+ *              n_states entries: exactly n_states x 8 bytes are written and none beyond
+ *   n_states   must equal num_final of the uploaded table (else PFAC_E_ARG); the kernel never writes a counter at or
+ *              past n_states whatever the records hold
+ *   flags      0: the counts are zeroed first.  PFAC_COUNT_ACCUMULATE: the call adds -- on a caller's buffer onto
+ *              whatever is there; on the slot-owned buffer onto the counts the slot holds (from zero if it holds none),
+ *              PFAC_E_STATE if those belong to an earlier table.  Chained ranges (owned ranges with the usual
+ *              max_pat_len - 1 halo) and chunked streams are thereby exact on the device: the counts accumulated over the
+ *              ranges are the counts of one scan of the whole.
+ * Both calls are read-only on the heap, the tile index, the match count, the selection and every other pass's slot-owned
+ * result.  The two share the slot-owned counts and are one pass; the counts stay fetchable, unchanged, through scans,
+ * table uploads, pfac_slot_reserve and every other pass (the lifetime rule of pfac_segment_d2h) until the slot's next
+ * count into the slot-owned buffer SUCCEEDS (which accumulation needs): a call that fails, or counts into a caller's
+ * buffer, leaves them as they were.
+ * Returns once *n_counted is known, like the checksum; the counts are then complete on the slot's stream.
+ * PFAC_E_STATE: no finished scan (also after a pfac_slot_reserve that dropped it), a scan made with an earlier table.
+ * PFAC_E_OVERFLOW: the scan overflowed its heap.  PFAC_E_ARG: flags outside 0..1, a wrong n_states, a misaligned d_counts,
+ * a d_records that is not this scan's heap.  The scan's state is judged before the arguments (PFAC_E_STATE, then
+ * PFAC_E_OVERFLOW, then the rest), as in pfac_records_filter_words.  Every error leaves the counts, slot-owned or caller's,
+ * as they were.
+ * Kernel: one wave per tile at a time, as the checksum; a workgroup keeps 32-bit partial counts in LDS -- a table indexed
+ * by state up to 8192 final states (32 KiB), above that a direct-mapped cache of 16384 {state, count} slots (128 KiB, one
+ * workgroup per CU) that a state claims on first sight (a state that finds its slot taken adds to memory at once) -- and
+ * adds the non-zero ones to the 64-bit counters once, with agent-scope atomics.  Where one state fills a good part of a
+ * chunk of 64 records (a wave probes for that every 16th chunk) the chunk is pre-aggregated by ballot, so that the one hot
+ * state of a small pattern set costs one LDS add per chunk instead of 64 serialised ones. */
+#define PFAC_COUNT_ACCUMULATE 1u   /* add onto the counts already there instead of zeroing them first */
+int pfac_records_count_states(pfac_ctx *ctx, int slot, const void *d_records, uint64_t *d_counts, uint64_t n_states,
+                              uint32_t flags, uint64_t *n_counted);
+/* The same over the slot's last leftmost-longest selection (whole-stream or per-document): counts[s] (+)= picks whose state
+ * is s; *n_counted = the number of picks.  d_sel: NULL = the slot-owned selection, else the caller's d_out of that
+ * selection -- the rule and the answers of pfac_replace_leftmost_longest's d_sel: PFAC_E_STATE without a selection since
+ * the slot's last scan (a new scan or a whole-word filter makes it stale), for a selection made with an earlier table, or
+ * for NULL when the selection went to the caller's buffer; PFAC_E_ARG for a misaligned d_sel or one that is not a selection
+ * of this table (a state at or past n_states, positions that do not ascend: checked on the device before any counter
+ * changes).  d_counts, n_states, flags and the errors' effect as above. */
+int pfac_selection_count_states(pfac_ctx *ctx, int slot, const pfac_record *d_sel, uint64_t *d_counts, uint64_t n_states,
+                                uint32_t flags, uint64_t *n_counted);
+/* D2H of the slot-owned counts (n_states entries of the call that wrote them).  Asynchronous on the slot's stream;
+ * pfac_slot_sync completes it.  PFAC_E_STATE when the slot holds no counts. */
+int pfac_state_counts_d2h(pfac_ctx *ctx, int slot, uint64_t *host_counts);
+
 /* Batches of documents.  One scan covers one contiguous byte range; a batch of independent documents is scanned as
  * their concatenation and then cut into documents on the device.  Records are keyed by their START offset and a walk
  * is failureless, so the matches of document [a, b) are exactly the records of the concatenated scan with

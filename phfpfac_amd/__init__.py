@@ -5,8 +5,8 @@ the scan runs in a hand-written gfx950 HIP kernel (``csrc/pfac_hip.hip``) behind
 ``include/pfac.h``.  This package is the thin Python mirror of that ABI plus the
 ``torch.distributed`` plumbing that shards the input byte stream across GPUs.
 """
-from ._ffi import PfacError  # noqa: F401
+from ._ffi import PFAC_COUNT_ACCUMULATE, PfacError  # noqa: F401
 from .table import RECORD_DTYPE, PfacTable, emit_packed, emit_records, emit_records_multi, merge_partitions, replacement_table  # noqa: F401
 from .matcher import GpuMatcher, device_count, word_set  # noqa: F401
 
-__all__ = ["PfacError", "PfacTable", "GpuMatcher", "RECORD_DTYPE", "emit_records", "emit_packed", "emit_records_multi", "merge_partitions", "replacement_table", "device_count", "word_set"]
+__all__ = ["PfacError", "PfacTable", "GpuMatcher", "RECORD_DTYPE", "emit_records", "emit_packed", "emit_records_multi", "merge_partitions", "replacement_table", "device_count", "word_set", "PFAC_COUNT_ACCUMULATE"]

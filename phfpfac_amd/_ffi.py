@@ -30,6 +30,7 @@ PFAC_E_INTERNAL = -9
 
 PFAC_WORD_LEFT = 1      # pfac_records_filter_words: the match must not begin inside a word
 PFAC_WORD_RIGHT = 2     # ... must not end inside one
+PFAC_COUNT_ACCUMULATE = 1   # pfac_records_count_states / pfac_selection_count_states: add onto the counts already there
 
 _STATUS_NAMES = {
     0: "PFAC_OK", -1: "PFAC_E_ARG", -2: "PFAC_E_IO", -3: "PFAC_E_PATTERN", -4: "PFAC_E_NOMEM",
@@ -92,6 +93,7 @@ HIP_SYMBOLS = (
     "pfac_table_set_replacements", "pfac_replace_leftmost_longest", "pfac_replace_d2h",
     "pfac_records_leftmost_longest_documents", "pfac_leftmost_longest_documents_d2h", "pfac_replace_documents",
     "pfac_replace_documents_d2h", "pfac_records_filter_words",
+    "pfac_records_count_states", "pfac_selection_count_states", "pfac_state_counts_d2h",
 )
 
 _host = None
@@ -219,5 +221,8 @@ def hip_lib() -> C.CDLL:
         L.pfac_replace_documents.argtypes = [vp, i, vp, vp, vp, vp, vp, u64, vp, C.POINTER(u64)]
         L.pfac_replace_documents_d2h.argtypes = [vp, i, vp]
         L.pfac_records_filter_words.argtypes = [vp, i, vp, vp, vp, C.c_uint32, i, i, vp, u64, C.POINTER(u64)]
+        L.pfac_records_count_states.argtypes = [vp, i, vp, vp, u64, C.c_uint32, C.POINTER(u64)]
+        L.pfac_selection_count_states.argtypes = [vp, i, vp, vp, u64, C.c_uint32, C.POINTER(u64)]
+        L.pfac_state_counts_d2h.argtypes = [vp, i, vp]
         _hip = L
     return _hip

@@ -2053,6 +2053,143 @@ __global__ void pfac_checksum_kernel(const void *rec, const unsigned long long *
     if (lane == 0) atomicAdd(out, sum);
 }
 
+// Histogram of the final states (pfac_records_count_states / pfac_selection_count_states): the checksum's walk over
+// the heap (one wave per tile at a time), or over a flat pfac_record array in chunks of 64, reduced ON CHIP first.
+// A workgroup keeps 32-bit partial counts in LDS and adds the non-zero ones to the 64-bit counters in memory once, at
+// its end.  Two LDS tables:
+//   DIRECT  n_states <= bins: lds[s] is the partial of state s.
+//   cache   2 words per slot {tag, count}, slot = count_slot_of(state): the first state that reaches an empty slot
+//           claims it (tag = state + 1, by compare-and-swap) and counts there from then on; a state whose slot belongs
+//           to another one adds to memory at once.  Hot states are seen early, so the hot traffic stays in LDS.
+// Why a 32-bit partial cannot wrap: a final state occurs at most once per start position (and a selection picks at
+// most one record per position), so a partial is bounded by the positions its workgroup sees.  A scan owns at most
+// 2^32 positions in 2^20 tiles, dealt round-robin to the grid's waves, and the host never launches fewer than two
+// workgroups: one sees at most 2^19 tiles (2^25 chunks of a selection) = 2^31 positions.
+// 64 lanes adding to ONE LDS address serialise, and with one hot pattern that is every chunk.  So a chunk can be
+// pre-aggregated in the wave: the first lane that holds a record names its state, a ballot finds the lanes that share
+// it, that one lane adds their number, the lanes left over add their own 1.  Such a round costs about as much as 25
+// serialised lanes, so it pays only where one state fills a good part of a chunk -- and loses
+// 15 % on a dictionary.  The wave therefore PROBES: every COUNT_PROBE-th chunk it runs the round and keeps it on for
+// the chunks that follow iff the leader's state held at least PFAC_COUNT_PEEL_MIN of the 64 lanes.
+#ifndef PFAC_COUNT_PEEL
+#define PFAC_COUNT_PEEL 1              // rounds of wave pre-aggregation per chunk (0: never; more than one lost everywhere)
+#endif
+#ifndef PFAC_COUNT_PEEL_MIN
+#define PFAC_COUNT_PEEL_MIN 24         // lanes of the leader's state in a probed chunk that keep the round on (0: always on)
+#endif
+#ifndef PFAC_COUNT_PROBE
+#define PFAC_COUNT_PROBE 16
+#endif
+constexpr unsigned COUNT_PROBE = PFAC_COUNT_PROBE;
+constexpr int COUNT_THREADS = 256;             // a workgroup over a direct table: four waves ...
+constexpr int COUNT_THREADS_MAX = 1024;        // ... over the cache: sixteen, ONE workgroup per CU
+constexpr unsigned COUNT_DIRECT_MAX = 8192;    // states of a direct table, 4 B each: at most 32 KiB of LDS
+constexpr unsigned COUNT_CACHE_SLOTS = 16384;  // slots of the cache, 8 B each: 128 KiB of the CU's 160
+constexpr unsigned COUNT_BINS_MAX = COUNT_CACHE_SLOTS;     // (PFAC_COUNT_BINS: fewer of either)
+
+__device__ __forceinline__ unsigned count_slot_of(unsigned state, unsigned bins) { return __umulhi(state * 0x9E3779B1u, bins); }
+
+template <bool DIRECT>
+__device__ __forceinline__ void count_add(unsigned *lds, unsigned bins, unsigned long long *counts, unsigned st, unsigned n) {
+    if (DIRECT) {
+        __hip_atomic_fetch_add(lds + st, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        return;
+    }
+    unsigned *e = lds + 2 * count_slot_of(st, bins);
+    const unsigned want = st + 1;
+    unsigned tag = __hip_atomic_load(e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if (tag == 0) {
+        const unsigned old = atomicCAS(e, 0u, want);
+        tag = old ? old : want;
+    }
+    if (tag == want) __hip_atomic_fetch_add(e + 1, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    else __hip_atomic_fetch_add(counts + st, (unsigned long long)n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// one chunk: `have` lanes hold a state below n_states (called by the whole wave; `phase` counts the wave's chunks,
+// `peel` is what its last probe decided)
+template <bool DIRECT>
+__device__ __forceinline__ void count_chunk(unsigned *lds, unsigned bins, unsigned long long *counts, bool have, unsigned st, int lane,
+                                            unsigned &phase, bool &peel) {
+    bool todo = have;
+    const bool probe = (phase++ % COUNT_PROBE) == 0;
+    if (PFAC_COUNT_PEEL > 0 && (peel || probe)) {
+#pragma unroll
+        for (int r = 0; r < PFAC_COUNT_PEEL; r++) {
+            const unsigned long long act = __ballot(todo);
+            if (!act) break;
+            const int leader = __ffsll((long long)act) - 1;
+            const unsigned s0 = (unsigned)__builtin_amdgcn_readlane((int)st, leader);
+            const bool mine = todo && st == s0;
+            const unsigned n = (unsigned)__popcll(__ballot(mine));
+            if (r == 0 && probe) peel = n >= (unsigned)PFAC_COUNT_PEEL_MIN;
+            if (lane == leader) count_add<DIRECT>(lds, bins, counts, s0, n);
+            todo = todo && !mine;
+        }
+    }
+    if (todo) count_add<DIRECT>(lds, bins, counts, st, 1u);
+}
+
+// BYTES 0: the flat array `rec` of `cap` pfac_records (a selection) in n_items chunks of 64; else the heap behind the
+// n_items tiles of tix.  No counter at or past n_states is ever written; res[0] += records counted.
+template <int BYTES, bool DIRECT>
+__global__ void __launch_bounds__(COUNT_THREADS_MAX)
+pfac_count_kernel(const void *rec, const unsigned long long *tix, unsigned long long n_items, unsigned long long cap, unsigned n_states,
+                  unsigned bins, unsigned long long *counts, unsigned long long *res) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned *lds = reinterpret_cast<unsigned *>(smem);
+    const unsigned words = DIRECT ? n_states : 2 * bins;
+    for (unsigned i = threadIdx.x; i < words; i += blockDim.x) lds[i] = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & (WAVE - 1);
+    const unsigned long long wstride = (unsigned long long)gridDim.x * (blockDim.x >> 6);
+    unsigned long long counted = 0;
+    unsigned phase = 0;
+    bool peel = false;
+    for (unsigned long long t = (unsigned long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); t < n_items; t += wstride) {
+        if (BYTES == 0) {
+            const unsigned long long i = t * WAVE + lane, n = cap;      // (cap: the records of the array)
+            unsigned st = 0;
+            bool have = i < n;
+            if (have) st = static_cast<const pfac_record *>(rec)[i].state;
+            have = have && st < n_states;
+            counted += have;
+            count_chunk<DIRECT>(lds, bins, counts, have, st, lane, phase, peel);
+        } else {
+            const unsigned long long e = tix[t], lo = e & TIX_BASE_MASK;
+            const unsigned cnt = (unsigned)(e >> TIX_CNT_SHIFT);
+            for (unsigned i0 = 0; i0 < cnt; i0 += WAVE) {
+                const unsigned i = i0 + (unsigned)lane;
+                unsigned pos, st = 0;
+                bool have = i < cnt && lo + i < cap;
+                if (have) heap_record<(BYTES ? BYTES : 4)>(rec, lo + i, t, pos, st);
+                have = have && st < n_states;
+                counted += have;
+                count_chunk<DIRECT>(lds, bins, counts, have, st, lane, phase, peel);
+            }
+        }
+    }
+    __syncthreads();
+    for (unsigned i = threadIdx.x; i < (DIRECT ? n_states : bins); i += blockDim.x) {
+        const unsigned c = DIRECT ? lds[i] : lds[2 * i + 1];
+        const unsigned st = DIRECT ? i : lds[2 * i] - 1u;
+        if (c) __hip_atomic_fetch_add(counts + st, (unsigned long long)c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    counted = wave_sum64(counted);
+    if (lane == 0 && counted) __hip_atomic_fetch_add(res, counted, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// A caller's selection (d_sel) before it is counted: states below n_states, positions ascending.  bad[0] = 1 if not.
+__global__ void pfac_sel_check_kernel(const pfac_record *sel, unsigned long long n, unsigned n_states, unsigned long long *bad) {
+    const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
+    bool wrong = false;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const pfac_record r = sel[i];
+        wrong = wrong || r.state >= n_states || (i + 1 < n && sel[i + 1].pos <= r.pos);
+    }
+    if (wrong) bad[0] = 1ull;
+}
+
 // Heap -> one sorted pfac_record array, three small kernels: records per group of 64 tiles, exclusive scan of the
 // group sums (one block), copy.  Only consumers that want the flat sorted array pay for this.
 constexpr int XGROUP = 64;
@@ -3392,6 +3529,10 @@ struct Slot {
     DevBuf<unsigned long long> rpd_off;   // slot-owned output offsets (d_out_offsets NULL)
     uint64_t rpd_docs = 0;
     bool rpd_done = false, rpd_own_off = false;
+    // pfac_records_count_states / pfac_selection_count_states
+    DevBuf<unsigned long long> cnt;       // slot-owned state counts (d_counts NULL): cnt_states of them, ...
+    uint64_t cnt_states = 0, cnt_table = 0;       // ... counted with this table (pfac_ctx::table_gen)
+    bool cnt_done = false;
 };
 
 }  // namespace
@@ -3450,6 +3591,7 @@ struct pfac_ctx {
     unsigned child0 = 0, child1 = 0;
     // tuning / test knobs, read from the environment ONCE, when a table is installed
     unsigned spin_max = SPIN_MAX, fault = 0, ticket_ways_knob = 0;
+    unsigned count_bins = 0, count_grid = 0, count_threads = 0;   // PFAC_COUNT_BINS / _GRID / _THREADS (0: the defaults)
     std::string trace_file;
     std::string err;
     std::mutex mu;
@@ -3748,6 +3890,12 @@ int configure_kernel(pfac_ctx *ctx, const int32_t *s0_host) {
     ctx->fault = (unsigned)env_int("PFAC_FAULT", 0);
     ctx->ticket_ways_knob = (unsigned)env_int("PFAC_TICKET_WAYS", 0);
     ctx->trace_file = knob("PFAC_TRACE") ? knob("PFAC_TRACE") : "";
+    // the state histogram: a smaller LDS table (the cache regime and its collisions at small automata), a fixed grid
+    const int cbins = env_int("PFAC_COUNT_BINS", 0), cgrid = env_int("PFAC_COUNT_GRID", 0);
+    ctx->count_bins = cbins >= 1 && (unsigned)cbins <= COUNT_BINS_MAX ? (unsigned)cbins : 0u;
+    ctx->count_grid = cgrid >= 1 ? (unsigned)std::min(cgrid, 65536) : 0u;
+    const int cthreads = env_int("PFAC_COUNT_THREADS", 0);
+    ctx->count_threads = cthreads == 256 || cthreads == 512 || cthreads == 1024 ? (unsigned)cthreads : 0u;
     // The two-buffer layout fixes the number of waves; LDS that no further wave fits into goes to the staging buffers
     // (up to 1024 records per 4 KiB tile before it has to be walked a second time).  The three-buffer layout (emission
     // at the top of the round, see NBUF_MAX) is used when it keeps that many waves with room for >= CAPW3_MIN records.
@@ -4440,6 +4588,140 @@ int pfac_records_checksum(pfac_ctx *ctx, int slot, const void *d_records, uint64
     HIP_TRY(ctx, hipMemcpyAsync(s.h_ctl + H_CHECKSUM, s.sum.p, 8, hipMemcpyDeviceToHost, s.stream));
     HIP_TRY(ctx, hipStreamSynchronize(s.stream));
     *checksum = host_u64(s, H_CHECKSUM);
+    return PFAC_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+using CountKernel = void (*)(const void *, const unsigned long long *, unsigned long long, unsigned long long, unsigned, unsigned,
+                             unsigned long long *, unsigned long long *);
+
+// pfac_records_count_states (the heap `heap` through the tile index) and, with is_sel, pfac_selection_count_states
+// (the n_sel records of `sel`; check_sel: it is the caller's), behind their checks of the scan's and the selection's
+// state: the arguments, then the histogram.  Nothing is written before every check has passed.
+int count_run(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *heap, bool is_sel, const pfac_record *sel, uint64_t n_sel,
+              bool check_sel, uint64_t *d_counts, uint64_t n_states, uint32_t flags, uint64_t *n_counted) {
+    if (flags > PFAC_COUNT_ACCUMULATE) return fail(ctx, PFAC_E_ARG, fn + ": flags must be 0 or PFAC_COUNT_ACCUMULATE");
+    if (n_states != (uint64_t)ctx->num_final)
+        return fail(ctx, PFAC_E_ARG, fn + ": n_states must be num_final of the uploaded table (" + std::to_string(ctx->num_final) + ")");
+    if ((uintptr_t)d_counts & 7) return fail(ctx, PFAC_E_ARG, fn + ": d_counts must be 8-byte aligned");
+    const bool own = d_counts == nullptr, acc = (flags & PFAC_COUNT_ACCUMULATE) != 0;
+    if (own && acc && s.cnt_done && s.cnt_table != ctx->table_gen)
+        return fail(ctx, PFAC_E_STATE, fn + ": the slot's counts belong to an earlier table; they cannot be added to");
+    const uint64_t expect = is_sel ? n_sel : s.last_total;
+    const uint64_t n_items = is_sel ? (n_sel + WAVE - 1) / WAVE : s.last_tiles;
+    if (!(is_sel ? (const void *)sel : heap) && n_items) return fail(ctx, PFAC_E_ARG, "null record buffer");
+    USE_DEVICE(ctx);
+    int rc = ensure_gsum(ctx, s, 1);                        // the records counted, the selection check's flag
+    if (rc) return rc;
+    unsigned long long *res = s.gsum.p;
+    const unsigned ns = (unsigned)n_states;
+    if (check_sel && n_sel) {                               // a caller's selection: judged before a counter changes
+        HIP_TRY(ctx, hipMemsetAsync(res, 0, 16, s.stream));
+        const unsigned blocks = (unsigned)std::min<uint64_t>((n_sel + 255) / 256, 1024);
+        hipLaunchKernelGGL(pfac_sel_check_kernel, dim3(blocks), dim3(256), 0, s.stream, sel, (unsigned long long)n_sel, ns, res + 1);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(s.h_ctl + H_PASS1, res + 1, 8, hipMemcpyDeviceToHost, s.stream));
+        HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+        if (host_u64(s, H_PASS1)) return fail(ctx, PFAC_E_ARG, fn + ": d_sel is not the selection of this scan and table");
+    }
+    unsigned long long *dst = reinterpret_cast<unsigned long long *>(d_counts);
+    const bool zero = !acc || (own && !s.cnt_done);
+    if (own) {                                              // (it grows only where the counts start from zero)
+        rc = s.cnt.ensure(ctx, s.stream, std::max<uint64_t>(n_states, 1), std::max<uint64_t>(n_states, 1));
+        if (rc) { s.cnt_done = false; return rc; }
+        dst = s.cnt.p;
+    }
+    HIP_TRY(ctx, hipMemsetAsync(res, 0, 8, s.stream));
+    if (zero && n_states) HIP_TRY(ctx, hipMemsetAsync(dst, 0, n_states * 8, s.stream));
+    if (n_items && n_states) {
+        // a direct table while the states fit it, else the cache
+        const bool direct = ns <= (ctx->count_bins ? std::min(ctx->count_bins, COUNT_DIRECT_MAX) : COUNT_DIRECT_MAX);
+        const unsigned bins = ctx->count_bins ? ctx->count_bins : COUNT_CACHE_SLOTS;
+        const size_t lds = direct ? (size_t)ns * 4 : (size_t)bins * 8;
+        // The grid.  Direct table: workgroups of four waves, as many per CU as their LDS lets be resident, eight at
+        // most (the loads of 32 waves hide the heap's latency).  Cache: ONE workgroup of sixteen waves per CU with
+        // most of its LDS -- every workgroup flushes the slots it claimed and misses what it could not claim, so
+        // more, smaller workgroups over the same records mean more atomics in memory (both measured: DESIGN.md,
+        // section 12).  Never fewer than two workgroups (the bound of a workgroup's 32-bit partials, see the
+        // kernel), never more than there is work for.
+        const unsigned per_cu = direct ? (unsigned)std::min<size_t>(8, LDS_TOTAL / std::max<size_t>(lds, 1)) : 1u;
+        const unsigned threads = ctx->count_threads ? ctx->count_threads : (unsigned)(direct ? COUNT_THREADS : COUNT_THREADS_MAX);
+        const uint64_t wanted = (n_items + threads / WAVE - 1) / (threads / WAVE);
+        unsigned grid = (unsigned)std::min<uint64_t>(wanted, (uint64_t)per_cu * (unsigned)std::max(ctx->n_cu, 1));
+        if (ctx->count_grid) grid = ctx->count_grid;
+        if (grid < 2) grid = 2;
+        CountKernel k = direct ? pfac_count_kernel<0, true> : pfac_count_kernel<0, false>;
+        if (!is_sel) k = by_width(s.last_rec_bytes, [direct](auto w) -> CountKernel { return direct ? pfac_count_kernel<w(), true> : pfac_count_kernel<w(), false>; });
+        if (lds > 64 * 1024) HIP_TRY(ctx, hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(k, dim3(grid), dim3(threads), lds, s.stream, is_sel ? (const void *)sel : heap,
+                           is_sel ? (const unsigned long long *)nullptr : s.tile_index.p, (unsigned long long)n_items,
+                           (unsigned long long)(is_sel ? n_sel : s.last_cap), ns, bins, dst, res);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(s.h_ctl + H_PASS, res, 8, hipMemcpyDeviceToHost, s.stream));
+    HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+    const uint64_t total = host_u64(s, H_PASS);
+    if (own) {
+        s.cnt_states = n_states;
+        s.cnt_table = ctx->table_gen;
+        s.cnt_done = true;
+    }
+    *n_counted = total;
+    if (total != expect)
+        return fail(ctx, PFAC_E_INTERNAL, fn + ": counted " + std::to_string(total) + " records of " + std::to_string(expect) +
+                                              " (a final state at or past n_states)");
+    return PFAC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pfac_records_count_states(pfac_ctx *ctx, int slot, const void *d_records, uint64_t *d_counts, uint64_t n_states,
+                              uint32_t flags, uint64_t *n_counted) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    if (!n_counted) return fail(ctx, PFAC_E_ARG, "null argument");
+    *n_counted = 0;
+    Slot &s = ctx->slots[slot];
+    const std::string fn = "pfac_records_count_states";
+    rc = last_scan_usable(ctx, s, fn, SCAN_FINISHED | SCAN_TABLE | SCAN_FITS);
+    if (rc) return rc;
+    const void *heap = d_records ? d_records : (const void *)s.records.p;
+    if (s.last_tiles && heap != s.last_records) return fail(ctx, PFAC_E_ARG, fn + ": d_records is not the record heap of the slot's last scan");
+    return count_run(ctx, s, fn, heap, false, nullptr, 0, false, d_counts, n_states, flags, n_counted);
+}
+
+int pfac_selection_count_states(pfac_ctx *ctx, int slot, const pfac_record *d_sel, uint64_t *d_counts, uint64_t n_states,
+                                uint32_t flags, uint64_t *n_counted) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    if (!n_counted) return fail(ctx, PFAC_E_ARG, "null argument");
+    *n_counted = 0;
+    Slot &s = ctx->slots[slot];
+    const std::string fn = "pfac_selection_count_states";
+    // the rules of pfac_replace_leftmost_longest's d_sel
+    if (!s.scanned || s.pending || !s.ll_done || s.ll_seq != s.scan_seq)
+        return fail(ctx, PFAC_E_STATE, fn + " needs a leftmost-longest selection since the slot's last scan");
+    if (!ctx->have_table || s.last_table != ctx->table_gen)
+        return fail(ctx, PFAC_E_STATE, fn + ": the selection was made with an earlier table");
+    if (!d_sel && !s.ll_own_out)
+        return fail(ctx, PFAC_E_STATE, fn + ": the selection went to the caller's buffer; pass it as d_sel");
+    if ((uintptr_t)d_sel & 7) return fail(ctx, PFAC_E_ARG, fn + ": d_sel must be 8-byte aligned");
+    return count_run(ctx, s, fn, nullptr, true, d_sel ? d_sel : s.ll_out.p, s.ll_n, d_sel != nullptr, d_counts, n_states, flags, n_counted);
+}
+
+int pfac_state_counts_d2h(pfac_ctx *ctx, int slot, uint64_t *host_counts) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    Slot &s = ctx->slots[slot];
+    if (!s.cnt_done) return fail(ctx, PFAC_E_STATE, "pfac_state_counts_d2h without slot-owned counts (pfac_records_count_states with d_counts NULL)");
+    if (!host_counts && s.cnt_states) return fail(ctx, PFAC_E_ARG, "null host buffer");
+    USE_DEVICE(ctx);
+    if (s.cnt_states) HIP_TRY(ctx, hipMemcpyAsync(host_counts, s.cnt.p, s.cnt_states * 8, hipMemcpyDeviceToHost, s.stream));
     return PFAC_OK;
 }
 

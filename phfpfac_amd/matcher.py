@@ -13,7 +13,7 @@ from typing import Optional, Tuple
 
 import numpy as np
 
-from ._ffi import PFAC_E_OVERFLOW, PFAC_WORD_LEFT, PFAC_WORD_RIGHT, CRecord, PfacError, hip_lib
+from ._ffi import PFAC_COUNT_ACCUMULATE, PFAC_E_OVERFLOW, PFAC_WORD_LEFT, PFAC_WORD_RIGHT, CRecord, PfacError, hip_lib
 from .table import RECORD_DTYPE, PfacTable, redaction_table, replacement_table
 
 
@@ -66,6 +66,7 @@ class GpuMatcher:
         self._keep_mark = {}            # per slot: how many of its kept h2d sources were queued before its last scan_async
         self._last_n = {}
         self._flen_set = False          # final-state lengths on the device for the uploaded table (scan_documents)
+        self._cnt_n = {}                # per slot: entries of its slot-owned state counts (count_states)
         rc = self._L.pfac_ctx_create(int(device), int(n_streams), C.byref(self._ctx))
         if rc:
             self._ctx = C.c_void_p()
@@ -320,6 +321,67 @@ class GpuMatcher:
                                                       C.byref(n)))
         self._last_n[slot] = n.value
         return n.value
+
+    # -- counts per pattern --------------------------------------------------
+    def _n_states(self) -> int:
+        if self.table is None:
+            raise PfacError(-7, "no host table to take num_final from (load_table first)")
+        return int(self.table.num_final)
+
+    def count_states(self, slot: int = 0, d_records=None, d_counts=None, accumulate: bool = False) -> int:
+        """Histogram of the final states of the slot's last finished scan, on the GPU (``pfac_records_count_states``):
+        ``counts[s]`` = records whose state is s, after ``filter_whole_words`` the kept ones.  ``d_counts`` None = a
+        slot-owned buffer (``state_counts_to_host``), else a device buffer of ``num_final`` uint64.  ``accumulate`` adds
+        onto the counts already there -- how chained ranges and chunked streams sum up on the device.  Returns the
+        number of records counted (= ``last_count``).  ``PfacTable.counts_by_pattern`` maps states to pattern ids."""
+        n = C.c_uint64(0)
+        ns = self._n_states()
+        self._check(self._L.pfac_records_count_states(self._ctx, slot, _ptr(d_records), _ptr(d_counts), ns,
+                                                      PFAC_COUNT_ACCUMULATE if accumulate else 0, C.byref(n)))
+        if d_counts is None:
+            self._cnt_n[slot] = ns
+        return n.value
+
+    def count_selection_states(self, slot: int = 0, d_sel=None, d_counts=None, accumulate: bool = False) -> int:
+        """``count_states`` over the slot's last leftmost-longest selection (``select_leftmost_longest`` or
+        ``select_leftmost_longest_documents``): how many of each pattern a replace rewrites.  ``d_sel`` None = the
+        slot-owned selection, else the ``d_out`` the selection was given.  Returns the number of picks."""
+        n = C.c_uint64(0)
+        ns = self._n_states()
+        self._check(self._L.pfac_selection_count_states(self._ctx, slot, _ptr(d_sel), _ptr(d_counts), ns,
+                                                        PFAC_COUNT_ACCUMULATE if accumulate else 0, C.byref(n)))
+        if d_counts is None:
+            self._cnt_n[slot] = ns
+        return n.value
+
+    def state_counts_to_host(self, slot: int = 0) -> np.ndarray:
+        """The slot-owned counts of ``count_states`` / ``count_selection_states``: uint64[num_final] of the table they
+        were counted with."""
+        out = np.empty(self._cnt_n.get(slot, 0), dtype=np.uint64)   # (no counts yet: the call says PFAC_E_STATE)
+        self._check(self._L.pfac_state_counts_d2h(self._ctx, slot, out.ctypes.data if out.size else None))
+        self.sync(slot)
+        return out
+
+    def count_patterns(self, data, n_owned: Optional[int] = None, slot: int = 0, whole_words=False, prev_byte: int = -1,
+                       next_byte: int = -1, accumulate: bool = False) -> np.ndarray:
+        """H2D + scan + count of one host buffer: how often every pattern matches, as uint64 counts indexed by the
+        1-based pattern id (``PfacTable.counts_by_pattern``); only the counts cross the link.  ``n_owned``,
+        ``whole_words``, ``prev_byte`` / ``next_byte`` as in ``scan_bytes``.  ``accumulate``: add onto the slot's counts
+        of the calls before -- over consecutive owned ranges (each with the halo behind it) the last call returns the
+        counts of the whole text."""
+        buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data.view(np.uint8).ravel()
+        n_avail = int(buf.size)
+        n_owned = n_avail if n_owned is None else int(n_owned)
+        if whole_words is not False:
+            self._ensure_final_lengths()
+        self.reserve(slot, max(n_avail, 1), max(n_avail // 8, 4096))
+        if n_avail:
+            self.h2d(buf, slot)
+        self.scan_resident(n_owned, n_avail, slot=slot)
+        if whole_words is not False:
+            self.filter_whole_words(slot, _word_bytes(whole_words), prev_byte=prev_byte, next_byte=next_byte)
+        self.count_states(slot, accumulate=accumulate)
+        return self.table.counts_by_pattern(self.state_counts_to_host(slot))
 
     def scan_partitioned(self, tables, data, slot: int = 0) -> np.ndarray:
         """Pattern-partition mode on ONE GPU: the input is copied once, every partition's table (``tables[k]`` =

@@ -152,6 +152,24 @@ class PfacTable:
     def pattern_ids(self, records: np.ndarray) -> np.ndarray:
         return self.idmap[records["state"]]
 
+    def counts_by_pattern(self, state_counts) -> np.ndarray:
+        """Counts per final state (``GpuMatcher.state_counts_to_host``) -> uint64 counts indexed by the 1-based pattern
+        id (entry 0 is unused), long enough for every id the table can report.  A literal table puts ``counts[s]`` at
+        ``idmap[s]``: of duplicate lines the one that wins has the matches, the others 0.  A character-class table adds
+        ``counts[s]`` to every pattern that ends in state s (``out_ids[out_first[s]:out_first[s + 1]]``)."""
+        counts = np.asarray(state_counts, dtype=np.uint64).ravel()
+        if counts.size != self.num_final:
+            raise ValueError(f"need one count per final state ({self.num_final}), got {counts.size}")
+        first = getattr(self, "out_first", None)
+        if first is None:
+            ids = np.asarray(self.idmap, dtype=np.int64)
+        else:
+            ids = np.asarray(self.out_ids, dtype=np.int64)
+            counts = np.repeat(counts, np.diff(np.asarray(first, dtype=np.int64)))
+        out = np.zeros(max(int(self.n_patterns), int(ids.max()) if ids.size else 0) + 1, dtype=np.uint64)
+        np.add.at(out, ids, counts)
+        return out
+
     def __del__(self):
         ptr = getattr(self, "_ptr", None)
         if ptr is not None:
