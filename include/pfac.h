@@ -365,7 +365,12 @@ int pfac_records_count_states(pfac_ctx *ctx, int slot, const void *d_records, ui
  * the slot's last scan (a new scan or a whole-word filter makes it stale), for a selection made with an earlier table, or
  * for NULL when the selection went to the caller's buffer; PFAC_E_ARG for a misaligned d_sel or one that is not a selection
  * of this table (a state at or past n_states, positions that do not ascend: checked on the device before any counter
- * changes).  d_counts, n_states, flags and the errors' effect as above. */
+ * changes).  d_counts, n_states, flags and the errors' effect as above; the selection's state is judged before the arguments
+ * (PFAC_E_STATE, then the rest), and among the arguments, and between them and the accumulate onto counts of an earlier
+ * table, no order is promised -- in either call.  A selection call that failed, PFAC_E_OVERFLOW for a too-small caller's
+ * d_out included, leaves no selection (passing the d_out of the one before does not bring it back).  New document offsets
+ * for the slot do not make a per-document selection stale here: the picks are counted as they were written, only the
+ * per-document replace cuts them again. */
 int pfac_selection_count_states(pfac_ctx *ctx, int slot, const pfac_record *d_sel, uint64_t *d_counts, uint64_t n_states,
                                 uint32_t flags, uint64_t *n_counted);
 /* D2H of the slot-owned counts (n_states entries of the call that wrote them).  Asynchronous on the slot's stream;

@@ -12,8 +12,11 @@ Three parts, none of which needs a GPU to import:
   plan / run / shrink  plan(seed) draws about 60 operations, asking the model which are legal and picking an illegal one
                        about one time in eight; run(g, plan, model) performs them on a GpuMatcher (or anything shaped like
                        one) and compares bit for bit; shrink(seed, k) is the plan cut before operation k.
-                       plan(seed, words=True) is a second family with the whole-word filter among the operations; the
-                       first is pinned to what it was before.
+                       plan(seed, words=True) is a second family with the whole-word filter among the operations,
+                       plan(seed, counts=True) a third with the per-pattern counts as well (pfac_records_count_states,
+                       pfac_selection_count_states, pfac_state_counts_d2h: slot-owned counts that belong to a table
+                       generation, are shared by two producers, can be added to and outlive everything else); the first
+                       two are pinned to what they were before.
 
 The device under test hands out final STATES; they are mapped to pattern ids with the idmap of the table the scan ran
 with (a stand-in that already works in ids says so with ``states_are_ids``)."""
@@ -24,6 +27,7 @@ import tempfile
 
 import numpy as np
 
+import countref
 import wordref
 from classfuzz import ClassMatcher as _ClassMatcher
 from docref import oracle_per_doc, random_offsets
@@ -40,6 +44,7 @@ TILE = 4096
 N_SLOTS = 2
 SEEDS = list(range(24))                 # the suite's plans
 WORD_SEEDS = list(range(24))            # ... and the seeds of its plans with the whole-word filter: plan(seed, words=True)
+COUNT_SEEDS = list(range(24))           # ... and of its plans with the per-pattern counts as well: plan(seed, counts=True)
 PLAN_OPS = 60
 IN_STEP, REC_STEP = 8 << 20, 4 << 20    # reserve_grow number k asks for k * IN_STEP bytes / k * REC_STEP records: above
                                         # anything a plan's scans reserve (inputs <= 2 000 003 bytes, heaps below 4 Mi records)
@@ -111,6 +116,14 @@ FILTERS = (
     dict(edges="both", ws="tab", prev=-1, next=-1, doc="wrong_n"),
 )
 EDGE_BITS = {"left": wordref.LEFT, "right": wordref.RIGHT, "both": wordref.BOTH}
+# The count knobs a table may be installed under in the count family (read at the upload, like passfuzz.KNOBS, which the
+# pinned plans index and which therefore stays as it is): with 3 to 150 final states the pool's automata then run the
+# cache regime with collisions (num_final above the bins) and the grid-stride loop.
+CKNOBS = ({}, {"PFAC_COUNT_BINS": "1"}, {"PFAC_COUNT_BINS": "16"}, {"PFAC_COUNT_GRID": "2"}, {"PFAC_COUNT_BINS": "16", "PFAC_COUNT_THREADS": "256"})
+CKNOB_NAMES = ("PFAC_COUNT_BINS", "PFAC_COUNT_GRID", "PFAC_COUNT_THREADS")
+COUNT_DIRECT_MAX = 8192                 # final states a workgroup's LDS table holds (include/pfac.h); fewer under PFAC_COUNT_BINS
+CNT_FILL = 0x11                         # a fresh caller's count buffer: every entry CNT_ENTRY, so that an accumulate that
+CNT_ENTRY = CNT_FILL * 0x0101010101010101   # zeroes, or a plain count that does not, shows at the first use
 MAX_FILTERS = 3                         # distinct filters on one scan: more would only thin out the cache
 WORD_TAB = {"cclass": b"abcxyz", "negcc": b"abcy", "nlesc": b"abxq\n"}     # (the other tables: the first half of their symbols)
 
@@ -342,6 +355,44 @@ class Expectations:
         return self._memo(("docsel", t, i, no, dkey, f, rkey), make)
 
 
+    # -- counts per pattern ---------------------------------------------------
+    # A contribution to a count buffer ("part"): ("scan", t, i, no, f), ("sel", t, i, no, entry, f) or
+    # ("docsel", t, i, no, dkey, f) -- the keys of scan / sel / docsel above.
+    def n_ids(self, t):
+        return int(self.tinfo(t)["ll"].size)
+
+    def injective(self, t):
+        """Whether no two final states of table `t` report the same pattern id (then counts compare per state too)."""
+        idmap = np.asarray(self.table(t).idmap)
+        return int(np.unique(idmap).size) == int(self.table(t).num_final)
+
+    def part_ids(self, part):
+        return {"scan": lambda: self.scan(*part[1:])[1], "sel": lambda: self.sel(*part[1:])[1], "docsel": lambda: self.docsel(*part[1:])[2]}[part[0]]()
+
+    def part_counts(self, part):
+        """uint64[n_ids]: the histogram by pattern id of one contribution (numpy.bincount over the CPU's records)."""
+        return self._memo(("cnt",) + part, lambda: np.bincount(self.part_ids(part), minlength=self.n_ids(part[1])).astype(np.uint64))
+
+    def part_states(self, part):
+        """uint64[num_final]: the same by final state, for a table whose idmap is injective (countref.state_counts)."""
+        assert self.injective(part[1])
+        return self._memo(("cnts",) + part, lambda: countref.state_counts(self.table(part[1]), self.part_ids(part)))
+
+    def state_counts(self, t, i, no, f=()):
+        """Counts by pattern id of Expectations.scan(t, i, no, f)."""
+        return self.part_counts(("scan", t, i, no, f))
+
+    def sel_counts(self, t, i, no, entry=0, f=(), dkey=None):
+        """Counts by pattern id of the picks of sel(t, i, no, entry, f), or with `dkey` of docsel(t, i, no, dkey, f)."""
+        return self.part_counts(("sel", t, i, no, entry, f) if dkey is None else ("docsel", t, i, no, dkey, f))
+
+    def sum_counts(self, t, parts, by_state=False):
+        out = np.zeros(int(self.table(t).num_final) if by_state else self.n_ids(t), dtype=np.uint64)
+        for part in parts:
+            out = out + (self.part_states(part) if by_state else self.part_counts(part))
+        return out
+
+
 class _DocCut:
     """Stands where the CPU oracle stands in docref.oracle_per_doc for a FILTERED scan: asked for the non-empty documents
     in turn, it answers with the scan's kept records that lie inside each one, positions relative to the document."""
@@ -402,6 +453,8 @@ class _Slot:
         self.sel = self.seg = self.rp = self.rpd = None     # what each slot-owned output holds
         self.text = None
         self.shared = False
+        self.cnt = None           # the slot-owned counts: dict(tab, gen, parts) -- their value is the sum of the parts' histograms
+        self.cbuf = None          # the caller's count buffer of this slot: dict(tab, serial, base, parts); base: CNT_ENTRY is still in every entry
 
 
 PASSES = ("segment", "select", "select_docs", "replace", "replace_docs")
@@ -416,13 +469,16 @@ class Model:
         self.gen = 0
         self.flen = False
         self.reps = None
+        self.cknob = 0            # the entry of CKNOBS the table was installed under
+        self.serial = 0           # caller's count buffers handed out
         self.slots = [_Slot() for _ in range(N_SLOTS)]
 
     def predict(self, op):
         return copy.deepcopy(self).apply(op)
 
     def apply(self, op):
-        return getattr(self, "_" + op["op"])(op, self.slots[op.get("slot", 0)])
+        fn = getattr(self, "_op_" + op["op"], None) or getattr(self, "_" + op["op"])
+        return fn(op, self.slots[op.get("slot", 0)])
 
     def __deepcopy__(self, memo):
         m = Model.__new__(Model)
@@ -434,12 +490,15 @@ class Model:
             for name in ("scan", "sel", "seg", "rp", "rpd"):
                 v = getattr(s, name)
                 setattr(c, name, dict(v) if v is not None else None)
+            for name in ("cnt", "cbuf"):
+                v = getattr(s, name)
+                setattr(c, name, dict(v, parts=list(v["parts"])) if v is not None else None)
             m.slots.append(c)
         return m
 
     # -- tables -------------------------------------------------------------
     def _load_table(self, op, s):
-        self.tab, self.knob = op["tab"], op["knob"]
+        self.tab, self.knob, self.cknob = op["tab"], op["knob"], op.get("cknob", 0)
         self.gen += 1
         self.flen, self.reps = False, None                      # lengths and replacements go with the old table
         return Exp()
@@ -697,10 +756,10 @@ class Model:
         return Exp(OK, lambda: self.x.docsel(*sel["key"])[:3], tab=sel["tab"])
 
     # -- replace ------------------------------------------------------------
-    def _rp_state(self, s, docs):
+    def _rp_state(self, s, docs, reps=True):
         if s.scan is None or s.sel is None or s.sel["seq"] != s.scan["seq"] or (docs and s.sel["kind"] != "docs"):
             return E_STATE
-        if s.scan["gen"] != self.gen or self.reps is None or not self.flen:
+        if s.scan["gen"] != self.gen or (reps and self.reps is None) or not self.flen:
             return E_STATE
         if docs and s.sel["doc_gen"] != s.doc_gen:
             return E_STATE
@@ -745,6 +804,95 @@ class Model:
             return Exp(E_STATE)
         return Exp(OK, s.rpd["off"])
 
+    # -- counts per pattern ---------------------------------------------------
+    def _cbuf_for(self, op, s):
+        """The caller's count buffer of the slot: exactly num_final x 8 bytes of the CURRENT table, so a fresh one
+        (every entry CNT_ENTRY) whenever the table is not the one it was sized for -- before the call, refused or not."""
+        if op["dst"] != "own" and (s.cbuf is None or s.cbuf["tab"] != self.tab):
+            self.serial += 1
+            s.cbuf = dict(tab=self.tab, serial=self.serial, base=True, parts=[])
+
+    def _count_done(self, op, s, part, n):
+        """The effects of a count that succeeded, and its value: n_counted, and for a caller's buffer its content."""
+        if op["dst"] == "own":
+            if op["acc"] and s.cnt is not None:
+                s.cnt["parts"].append(part)
+            else:
+                s.cnt = dict(tab=part[1], gen=self.gen, parts=[part])
+            return Exp(OK, lambda: n)
+        if op["acc"]:
+            s.cbuf["parts"].append(part)
+        else:
+            s.cbuf.update(base=False, parts=[part])
+        tab, parts = part[1], list(s.cbuf["parts"])
+        return Exp(OK, lambda: (n, self.x.sum_counts(tab, parts)), tab=tab)
+
+    def _count_faults(self, op, s, faults):
+        """The argument faults both count calls share, and what several faults are worth: the header promises no order
+        among two argument faults, nor between one and the accumulate onto counts of an earlier table."""
+        if op["dst"] == "misaligned":
+            faults.append(E_ARG)
+        if op["dst"] == "own" and op["acc"] and s.cnt is not None and s.cnt["gen"] != self.gen:
+            faults.append(E_STATE)
+        if len(faults) > 1:
+            return Exp(None)
+        return Exp(faults[0]) if faults else None
+
+    def _op_count(self, op, s):
+        """pfac_records_count_states.  dst: "own" = d_counts NULL, "caller" = the slot's caller's buffer ("misaligned":
+        four bytes into it); acc: PFAC_COUNT_ACCUMULATE; heap as in _filter; ns: n_states = num_final ("ok"), one less,
+        one more, or 0.  The scan's state is judged first: PFAC_E_STATE, PFAC_E_OVERFLOW, then the arguments."""
+        self._cbuf_for(op, s)
+        sc = s.scan
+        if sc is None or sc["pending"] or sc["gen"] != self.gen:
+            return Exp(E_STATE)
+        if sc["over"]:
+            return Exp(E_OVERFLOW)
+        faults = []
+        if sc["ext"] and op["heap"] != "own":
+            if sc["no"] == 0:
+                return Exp(None)                                # (a scan of nothing wrote no heap: no pointer is "another")
+            faults.append(E_ARG)
+        if op["ns"] != "ok":
+            faults.append(E_ARG)
+        bad = self._count_faults(op, s, faults)
+        if bad is not None:
+            return bad
+        return self._count_done(op, s, ("scan",) + self._sk(sc), self._count(sc))
+
+    def _op_count_sel(self, op, s):
+        """pfac_selection_count_states.  sel: "own" = d_sel NULL, "caller" = the d_out the selection was given, "junk" =
+        a buffer that holds no selection of this table, "misaligned".  The selection's state by the rules of the
+        replace's d_sel (without the replacements), judged before the arguments; new document offsets do not make a
+        per-document selection stale for a count."""
+        self._cbuf_for(op, s)
+        if self._rp_state(s, False, reps=False):
+            return Exp(E_STATE)
+        sel = s.sel
+        if op["sel"] == "own" and not sel["own"]:
+            return Exp(E_STATE)
+        if op["sel"] == "caller" and sel["own"]:
+            return Exp(None)                                    # (there is no caller's d_out to pass)
+        part = (("sel",) if sel["kind"] == "whole" else ("docsel",)) + sel["key"]
+        n = int(self.x.part_ids(part).size)
+        faults = []
+        if op["sel"] == "junk":
+            if n == 0:
+                return Exp(None)                                # (no picks: every buffer holds this selection)
+            faults.append(E_ARG)
+        if op["sel"] == "misaligned":
+            faults.append(E_ARG)
+        bad = self._count_faults(op, s, faults)
+        if bad is not None:
+            return bad
+        return self._count_done(op, s, part, n)
+
+    def _cnt_fetch(self, op, s):
+        if s.cnt is None:
+            return Exp(E_STATE)
+        tab, parts = s.cnt["tab"], list(s.cnt["parts"])
+        return Exp(OK, lambda: self.x.sum_counts(tab, parts), tab=tab)
+
     # -- plumbing -----------------------------------------------------------
     def _set_stream(self, op, s):
         s.shared = op["share"]
@@ -787,6 +935,7 @@ KINDS = {"load_table": 4, "set_flen": 1, "set_reps": 2, "scan_bytes": 9, "scan_s
          "replace_docs": 4, "seg_fetch": 3, "sel_fetch": 3, "docsel_fetch": 3, "rp_fetch": 3, "rpd_fetch": 3, "set_stream": 2, "sync": 1,
          "reserve_grow": 3}
 WORD_KINDS = dict(KINDS, filter=9)      # the kinds of a plan with the whole-word filter (plan(seed, words=True))
+COUNT_KINDS = dict(WORD_KINDS, scan_ext=10, count=9, count_sel=5, cnt_fetch=4)      # ... and of one with the counts as well (plan(seed, counts=True))
 READERS = ("records", "packed", "checksum", "text", "scan_finish")          # what reads a finished scan, besides the passes
 
 
@@ -804,6 +953,8 @@ def _propose(rng, m, kinds=KINDS):
         op.pop("slot")
         op["tab"] = str(rng.choice(sorted(TABLES)))
         op["knob"] = int(rng.choice(TABLES[op["tab"]]["knobs"]))
+        if kinds is COUNT_KINDS:
+            op["cknob"] = int(rng.integers(0, len(CKNOBS)))
     elif kind == "set_flen":
         op.pop("slot")
     elif kind == "set_reps":
@@ -841,6 +992,14 @@ def _propose(rng, m, kinds=KINDS):
     elif kind == "filter":
         op["f"] = int(rng.integers(0, len(FILTERS)))
         op["heap"] = str(rng.choice(["none", "slot"])) if sc and sc["ext"] and rng.random() < 0.3 else "own"
+    elif kind == "count":
+        op.update(_count_op(slot, dst=str(rng.choice(["own", "caller", "misaligned"], p=[.5, .45, .05])), acc=bool(rng.random() < 0.4),
+                            heap=str(rng.choice(["none", "slot"])) if sc and sc["ext"] and rng.random() < 0.3 else "own",
+                            ns=str(rng.choice(["ok", "minus", "plus", "zero"], p=[.85, .05, .05, .05]))))
+    elif kind == "count_sel":
+        mine = ("own" if s.sel["own"] else "caller") if s.sel else "own"
+        op.update(_count_sel_op(slot, dst=str(rng.choice(["own", "caller"])), acc=bool(rng.random() < 0.4),
+                                sel=mine if rng.random() < 0.75 else str(rng.choice(["own", "junk", "misaligned"]))))
     elif kind == "set_stream":
         op["slot"] = 1
         op["share"] = not m.slots[1].shared
@@ -855,6 +1014,14 @@ def _pass_op(kind, slot, own=True):
     if kind == "select":
         op["entry"] = 0
     return op
+
+
+def _count_op(slot, dst="own", acc=False, heap="own", ns="ok"):
+    return dict(op="count", slot=slot, dst=dst, acc=acc, heap=heap, ns=ns)
+
+
+def _count_sel_op(slot, dst="own", acc=False, sel="own"):
+    return dict(op="count_sel", slot=slot, dst=dst, acc=acc, sel=sel)
 
 
 PRODUCER_OF = {v: k for k, v in FETCH_OF.items()}
@@ -926,14 +1093,132 @@ def _filter_step(rng, slot):
     return step
 
 
-def plan(seed, n_ops=PLAN_OPS, words=False):
+def _scan_step(rng, slot, other=False):
+    """A scan of the current table the session means to succeed (`other`: of another input than the slot's last)."""
+    def step(m):
+        if m.tab is None:
+            return None
+        n_in = len(TABLES[m.tab]["inputs"])
+        inp = int(rng.integers(0, n_in))
+        sc = m.slots[slot].scan
+        if other and sc is not None and sc["inp"] == inp:
+            inp = (inp + 1) % n_in
+        n = m.x.input_size(m.tab, inp)
+        return dict(op="scan_bytes", slot=slot, inp=inp, no=n if rng.random() < 0.6 else (n * 5) // 8)
+    return step
+
+
+def _ext_step(rng, slot, start=False):
+    """A scan of the current table into a caller's heap: one that fits, or (two times in five) one half the size.
+    `start`: a scan_start into the slot's own heap instead, which fits."""
+    def step(m):
+        if m.tab is None:
+            return None
+        inp = int(rng.integers(0, len(TABLES[m.tab]["inputs"])))
+        no = m.x.input_size(m.tab, inp)
+        cnt = m.x.count(m.tab, inp, no)
+        if start:
+            return dict(op="scan_start", slot=slot, inp=inp, no=no, cap=cnt + cnt // 4 + 65536)
+        return dict(op="scan_ext", slot=slot, inp=inp, no=no, cap=cnt // 2 if cnt >= 64 and rng.random() < 0.4 else cnt + cnt // 4 + 65536)
+    return step
+
+
+def _between_count_and_fetch(rng, slot):
+    """What happens between a count into the slot-owned buffer and the fetch of it: the counts outlive all of it."""
+    what = str(rng.choice(["scan", "upload", "grow", "filter", "pass", "caller", "refused"]))
+    if what == "scan":
+        return [_scan_step(rng, slot, other=True)]
+    if what == "upload":
+        tab = str(rng.choice(sorted(TABLES)))
+        return [dict(op="load_table", tab=tab, knob=int(rng.choice(TABLES[tab]["knobs"])), cknob=int(rng.integers(0, len(CKNOBS))))]
+    if what == "grow":
+        which = str(rng.choice(["records", "both"]))
+        return [lambda m: dict(op="reserve_grow", slot=slot, which=which, k=m.slots[slot].grow + 1)]
+    if what == "filter":
+        return _prepare(rng, "filter", slot) + [_filter_step(rng, slot)]
+    if what == "pass":
+        kind = str(rng.choice(PASSES))
+        return _prepare(rng, kind, slot) + [_pass_op(kind, slot)]
+    if what == "caller":
+        return [_count_op(slot, dst="caller", acc=bool(rng.random() < 0.5))]
+    return [_count_op(slot, ns=str(rng.choice(["minus", "plus", "zero"])))]
+
+
+def _count_agenda(rng, m, chosen, st, agenda):
+    """The histories the count family aims at (the rules of plan(seed, counts=True)); returns the new agenda."""
+    if st != OK:
+        return agenda
+    kind, slot = chosen["op"], chosen.get("slot", 0)
+    sc = m.slots[slot].scan
+    dst = lambda: str(rng.choice(["own", "caller"]))            # noqa: E731
+    fetch = dict(op="cnt_fetch", slot=slot)
+    if kind in ("scan_bytes", "scan_finish") and rng.random() < 0.5:
+        # a fresh scan is counted, then read by something else
+        reader = str(rng.choice(["checksum", "text", "records"]))
+        read = (lambda m: dict(op="records", slot=slot, first=0, n=m._count(m.slots[slot].scan)) if m.slots[slot].scan else None) \
+            if reader == "records" else dict(op=reader, slot=slot, base=int(rng.choice(TEXT_BASES)))
+        odd = []
+        if rng.random() < 0.3:                                  # a refused call first: a misaligned d_counts, a wrong n_states
+            what = str(rng.choice(["misaligned", "minus", "plus", "zero"]))
+            odd = [_count_op(slot, dst="misaligned") if what == "misaligned" else _count_op(slot, dst=dst(), acc=bool(rng.random() < 0.5), ns=what)]
+        agenda = odd + [_count_op(slot, dst=dst(), acc=bool(rng.random() < 0.3)), read] + agenda
+    elif kind in ("checksum", "text", "records") and sc is not None and not sc["ext"] and rng.random() < 0.3:
+        agenda = [_ext_step(rng, slot)] + agenda                # the next scan goes to a caller's heap
+    elif kind in ("checksum", "text", "records") and sc is not None and rng.random() < 0.2:
+        # the next scan is counted while it is pending (PFAC_E_STATE), and by the other slot's rules once it has finished
+        agenda = [_ext_step(rng, slot, start=True), _count_op(slot, dst=dst(), acc=bool(rng.random() < 0.5))] + agenda
+    elif kind == "scan_start" and rng.random() < 0.5:
+        agenda = [_count_op(slot, dst=dst())] + agenda          # a scan that is not finished: PFAC_E_STATE
+    elif kind == "reserve_grow" and sc is None and rng.random() < 0.6:
+        agenda = [_count_op(slot, dst=dst())] + agenda          # a reserve that dropped the scan: PFAC_E_STATE
+    elif kind == "scan_ext":
+        # a caller's heap: the right pointer, now and then a wrong one first; an overflowed one is PFAC_E_OVERFLOW
+        wrong = [_count_op(slot, dst=dst(), heap=str(rng.choice(["none", "slot"])))] if not sc["over"] and rng.random() < 0.4 else []
+        agenda = wrong + [_count_op(slot, dst=dst(), acc=bool(rng.random() < 0.3))] + agenda
+    elif kind == "filter" and rng.random() < 0.6:
+        agenda = [_count_op(slot, dst=dst(), acc=bool(rng.random() < 0.4))] + agenda
+    elif kind in ("select", "select_docs") and rng.random() < 0.12:
+        # a selection made with an earlier table: PFAC_E_STATE
+        tab = str(rng.choice(sorted(TABLES)))
+        agenda = [dict(op="load_table", tab=tab, knob=int(rng.choice(TABLES[tab]["knobs"])), cknob=int(rng.integers(0, len(CKNOBS)))),
+                  _count_sel_op(slot, dst=dst(), sel="own" if chosen["own"] else "caller")] + agenda
+    elif kind in ("select", "select_docs") and rng.random() < 0.7:
+        # NULL for a selection in the caller's d_out, a buffer that holds none, a misaligned one: refused, then the count
+        null = [_count_sel_op(slot, dst=dst(), sel="own")] if not chosen["own"] and rng.random() < 0.4 else []
+        bad = [_count_sel_op(slot, dst=dst(), acc=bool(rng.random() < 0.5), sel=str(rng.choice(["junk", "misaligned"])))] if rng.random() < 0.3 else []
+        agenda = null + bad + [_count_sel_op(slot, dst=dst(), acc=bool(rng.random() < 0.4), sel="own" if chosen["own"] else "caller")] + agenda
+    elif kind == "load_table" and rng.random() < 0.5:
+        # an accumulate onto the slot's counts of the table before is PFAC_E_STATE; a plain count replaces them
+        slot = int(rng.integers(0, N_SLOTS))
+        agenda = [_scan_step(rng, slot), _count_op(slot, acc=True), _count_op(slot), dict(op="cnt_fetch", slot=slot)] + agenda
+    elif kind in ("count", "count_sel") and chosen["dst"] == "own" and not chosen["acc"] and rng.random() < 0.3:
+        # two or three accumulating counts over different scans of one table, then the fetch
+        more = []
+        for _ in range(int(rng.integers(2, 4))):
+            more += [_scan_step(rng, slot, other=True), _count_op(slot, acc=True)]
+        if rng.random() < 0.5:
+            more += _prepare(rng, "select", slot)[1:] + [_pass_op("select", slot), _count_sel_op(slot, acc=True)]
+        agenda = more + [fetch] + agenda
+    elif kind in ("count", "count_sel") and chosen["dst"] == "own" and rng.random() < 0.7:
+        agenda = agenda + _between_count_and_fetch(rng, slot) + [fetch]
+    if kind == "count_sel" and rng.random() < 0.25:
+        # a new scan or a filter makes the selection stale: the same count again is PFAC_E_STATE
+        agenda = [_scan_step(rng, slot) if rng.random() < 0.5 else _filter_step(rng, slot), dict(chosen, acc=bool(rng.random() < 0.5))] + agenda
+    return agenda
+
+
+def plan(seed, n_ops=PLAN_OPS, words=False, counts=False):
     """The plan of `seed`: a list of operations (dicts).  Deterministic; the model decides what each one is worth.
     `words`: the second family of plans, in which the whole-word filter is one of the operations (the first family is
-    what it was before the filter existed, seed for seed)."""
-    rng = np.random.default_rng([seed, 0x53455353494F4E] + ([0x574F5244] if words else []))
-    kinds = WORD_KINDS if words else KINDS
+    what it was before the filter existed, seed for seed).  `counts`: the third family, the second one's operations and
+    the per-pattern counts (count, count_sel, cnt_fetch; tables installed under an entry of CKNOBS)."""
+    rng = np.random.default_rng([seed, 0x53455353494F4E] + ([0x434F554E54] if counts else [0x574F5244] if words else []))
+    kinds = COUNT_KINDS if counts else WORD_KINDS if words else KINDS
+    words = words or counts                                     # (the count family filters like the word family)
     m = Model()
     ops, agenda = [], []
+    if counts:                                                  # (a fetch before any count: PFAC_E_STATE)
+        agenda = [dict(op="cnt_fetch", slot=int(rng.integers(0, N_SLOTS)))] if rng.random() < 0.3 else []
     while len(ops) < n_ops:
         want_err = rng.random() < (1 / 16 if words else 1 / 8)   # (words: the filter between a selection and its replace adds errors of its own)
         chosen = None
@@ -964,6 +1249,8 @@ def plan(seed, n_ops=PLAN_OPS, words=False):
                 agenda = _prepare(rng, "filter", cand["slot"], docs=FILTERS[cand["f"]]["doc"] == "slot") + [cand]
         if chosen is None:
             continue
+        if counts and chosen["op"] == "load_table" and "cknob" not in chosen:
+            chosen = dict(chosen, cknob=int(rng.integers(0, len(CKNOBS))))
         st = m.apply(chosen).status
         ops.append(chosen)
         if words:
@@ -1013,12 +1300,14 @@ def plan(seed, n_ops=PLAN_OPS, words=False):
         if st == OK and chosen["op"] == "scan_start" and rng.random() < 0.7:    # the other slot works while this scan is pending
             agenda = [dict(op="scan_bytes", slot=1 - chosen["slot"], inp=chosen["inp"], no=chosen["no"]),
                       dict(op="scan_finish", slot=chosen["slot"])] + agenda
+        if counts:
+            agenda = _count_agenda(rng, m, chosen, st, agenda)
     return ops
 
 
-def shrink(seed, k, n_ops=PLAN_OPS, words=False):
+def shrink(seed, k, n_ops=PLAN_OPS, words=False, counts=False):
     """The plan of `seed` with operation k onwards removed: cut a failing history down by hand."""
-    return plan(seed, n_ops, words)[:k]
+    return plan(seed, n_ops, words, counts)[:k]
 
 
 # ---------------------------------------------------------------------------
@@ -1027,6 +1316,53 @@ def shrink(seed, k, n_ops=PLAN_OPS, words=False):
 class _SlotBufs:
     def __init__(self):
         self.inp = self.rec = self.sel = self.first = None      # caller-owned device buffers the slot's state refers to
+        self.last_sel = None                                    # the d_out of the last selection that went to the caller
+        self.cnt = None                                         # the caller's count buffer (_CountBuf) and the model's serial of it
+        self.cnt_serial = 0
+
+
+class Odd:
+    """A pointer four bytes into `buf`, for a stand-in device whose buffers have no addresses."""
+
+    def __init__(self, buf):
+        self.buf = buf
+
+
+class _CountBuf:
+    """The caller's d_counts: exactly n x 8 bytes between guard bands, every byte CNT_FILL (heapguard.GuardedBuffer; on
+    a stand-in device one of its buffers, the bands behind the payload)."""
+
+    def __init__(self, g, n):
+        self.n = int(n)
+        if hasattr(g, "alloc"):
+            self.guard, self.buf = None, g.alloc(self.n * 8 + 64)
+            self.buf.a[:] = CNT_FILL
+            self.ptr, self.odd = self.buf, Odd(self.buf)
+        else:
+            from heapguard import GuardedBuffer
+            self.guard = GuardedBuffer(self.n * 8, fill=CNT_FILL, device=f"cuda:{g.device}")
+            self.ptr, self.odd = self.guard.ptr, self.guard.ptr + 4
+
+    def read(self):
+        raw = self.guard.host() if self.guard is not None else self.buf.a[:self.n * 8]
+        return raw.view(np.uint64).copy()
+
+    def check(self, what):
+        if self.guard is not None:
+            self.guard.check(what=what)
+        else:
+            assert (self.buf.a[self.n * 8:] == CNT_FILL).all(), f"bytes behind {what} changed"
+
+
+def _raw_count(g, slot, d_records, d_counts, n_states, flags):
+    """pfac_records_count_states itself, for an n_states the wrapper would not pass."""
+    if hasattr(g, "raw_count_states"):
+        return g.raw_count_states(slot, d_records, d_counts, n_states, flags)
+    import ctypes as C
+    from phfpfac_amd.matcher import _ptr
+    n = C.c_uint64(0)
+    g._check(g._L.pfac_records_count_states(g._ctx, slot, _ptr(d_records), _ptr(d_counts), int(n_states), int(flags), C.byref(n)))
+    return n.value
 
 
 def _alloc(g, n_bytes):
@@ -1079,7 +1415,8 @@ class Executor:
         self.g, self.m = g, model
         self.x = model.x
         self.bufs = [_SlotBufs() for _ in range(N_SLOTS)]
-        self.stats = dict(ops=0, errors=0, compared=0, filters=0, widths=set(), staging=set(), variants=set(), statuses=set())
+        self.stats = dict(ops=0, errors=0, compared=0, filters=0, counts=0, widths=set(), staging=set(), variants=set(), statuses=set(),
+                          regimes=set())                        # (regimes: (entry of CKNOBS, "direct" / "cache") of every count that ran)
         self.ids_direct = getattr(g, "states_are_ids", False)
 
     def ids(self, tab, states):
@@ -1119,10 +1456,11 @@ class Executor:
 
     # -- tables -------------------------------------------------------------
     def do_load_table(self, op, exp, before):
-        saved = {k: os.environ.get(k) for k in KNOB_NAMES}
-        for k in KNOB_NAMES:
+        saved = {k: os.environ.get(k) for k in KNOB_NAMES + list(CKNOB_NAMES)}
+        for k in saved:
             os.environ.pop(k, None)
         os.environ.update(KNOBS[op["knob"]])                    # knobs are read when a table is installed
+        os.environ.update(CKNOBS[op.get("cknob", 0)])
         try:
             self.g.load_table(self.x.table(op["tab"]))
         finally:
@@ -1253,7 +1591,7 @@ class Executor:
         d_out = _alloc(g, cap * 8 + 16)
         n, ex = g.select_leftmost_longest(op["entry"], d_out=d_out, out_cap=cap, slot=slot, d_records=self.bufs[slot].rec)
         g.sync(slot)
-        self.bufs[slot].sel = d_out
+        self.bufs[slot].sel = self.bufs[slot].last_sel = d_out
         return (int(n), int(ex)) + self.recs(exp.tab, _download(g, d_out, REC, int(n)))
 
     def do_select_docs(self, op, exp, before):
@@ -1267,6 +1605,7 @@ class Executor:
         n = int(g.select_leftmost_longest_documents(nd, d_out=d_out, out_cap=cap, d_doc_first=d_first, slot=slot, d_records=self.bufs[slot].rec))
         g.sync(slot)
         self.bufs[slot].sel, self.bufs[slot].first = d_out, d_first
+        self.bufs[slot].last_sel = d_out
         return (n, _download(g, d_first, np.uint64, nd + 1)) + self.recs(exp.tab, _download(g, d_out, REC, n))
 
     def _sel_n(self, slot):
@@ -1316,6 +1655,97 @@ class Executor:
     def do_rpd_fetch(self, op, exp, before):
         rpd = self.m.slots[op["slot"]].rpd
         return self.g.replacement_doc_offsets_to_host(int(rpd["off"]().size - 1) if rpd else 1, op["slot"])
+
+    # -- counts per pattern ---------------------------------------------------
+    def n_entries(self, tab):
+        """Entries of a count buffer of table `tab`: its final states (its pattern ids, on a device that works in ids)."""
+        if tab is None:
+            return 1
+        return self.x.n_ids(tab) if self.ids_direct else int(self.x.table(tab).num_final)
+
+    def by_id(self, tab, counts, parts):
+        """Device counts per state, summed into their pattern ids; where no two states share an id they are first
+        compared state for state, so that two states swapping counts cannot cancel."""
+        counts = np.asarray(counts, dtype=np.uint64)
+        assert counts.size == self.n_entries(tab), f"{counts.size} counts, want {self.n_entries(tab)}"
+        self.stats["compared"] += int(counts.size)
+        if self.ids_direct:
+            return counts
+        if self.x.injective(tab):
+            _same(counts, self.x.sum_counts(tab, parts, by_state=True), "counts per state")
+        out = np.zeros(self.x.n_ids(tab), dtype=np.uint64)
+        np.add.at(out, np.asarray(self.x.table(tab).idmap, dtype=np.int64), counts)
+        return out
+
+    def _counted(self, op, call):
+        """One count call: into the slot's caller's buffer (allocated afresh when the model says so) or the slot-owned
+        one.  The guard bands hold after every call; after a refused one the payload is byte for byte what it was."""
+        slot = op["slot"]
+        s, b = self.m.slots[slot], self.bufs[slot]
+        if op["dst"] == "own":
+            was = b.cnt.read() if b.cnt is not None else None
+            try:
+                n = int(call(None))
+            finally:                                            # (the caller's buffer of an earlier call: not this call's to touch)
+                if was is not None:
+                    self.g.sync(slot)
+                    b.cnt.check("the caller's d_counts after a count into the slot-owned buffer")
+                    assert np.array_equal(b.cnt.read(), was), "a count into the slot-owned buffer changed the caller's d_counts"
+            self.stats["counts"] += 1
+            return n
+        if b.cnt is None or b.cnt_serial != s.cbuf["serial"]:
+            b.cnt, b.cnt_serial = _CountBuf(self.g, self.n_entries(self.m.tab)), s.cbuf["serial"]
+        was = b.cnt.read()
+        try:
+            n = int(call(b.cnt.odd if op["dst"] == "misaligned" else b.cnt.ptr))
+        except PfacError:
+            self.g.sync(slot)
+            b.cnt.check("the caller's d_counts after a refused count")
+            assert np.array_equal(b.cnt.read(), was), "a refused count changed the caller's d_counts"
+            raise
+        self.g.sync(slot)
+        b.cnt.check("the caller's d_counts")
+        got = b.cnt.read()
+        if s.cbuf["base"]:
+            got = got - np.uint64(CNT_ENTRY)                    # (an accumulate onto the fresh buffer: its constant is still there)
+        self.stats["counts"] += 1
+        return n, self.by_id(s.cbuf["tab"], got, s.cbuf["parts"])
+
+    def do_count(self, op, exp, before):
+        g, slot = self.g, op["slot"]
+        b = self.bufs[slot]
+        heap = {"own": b.rec, "none": None, "slot": g.records_ptr(slot) or None}[op["heap"]]
+        if op["ns"] == "ok" or self.m.tab is None:
+            out = self._counted(op, lambda d: g.count_states(slot, d_records=heap, d_counts=d, accumulate=op["acc"]))
+        else:
+            nf = self.n_entries(self.m.tab)
+            ns = {"minus": nf - 1, "plus": nf + 1, "zero": 0}[op["ns"]]
+            out = self._counted(op, lambda d: _raw_count(g, slot, heap, d, ns, int(op["acc"])))
+        bins = int(CKNOBS[self.m.cknob].get("PFAC_COUNT_BINS", 0))
+        direct = int(self.x.table(self.m.tab).num_final) <= (min(bins, COUNT_DIRECT_MAX) if bins else COUNT_DIRECT_MAX)
+        self.stats["regimes"].add((self.m.cknob, "direct" if direct else "cache"))
+        assert g.last_count(slot) == (out if op["dst"] == "own" else out[0]), "n_counted is not the scan's match count"
+        return out
+
+    def do_count_sel(self, op, exp, before):
+        g, slot = self.g, op["slot"]
+        b, n_sel = self.bufs[slot], self._sel_n(slot)[0]
+        if op["sel"] in ("junk", "misaligned"):
+            junk = _alloc(g, max(n_sel, 1) * 8 + 16)
+            if hasattr(junk, "fill_"):
+                junk.fill_(0xFF)                                # states past any n_states
+            else:
+                junk.a[:] = 0xFF
+                junk.junk = True
+            d_sel = junk if op["sel"] == "junk" else Odd(junk) if hasattr(g, "alloc") else int(junk.data_ptr()) + 4
+        else:
+            d_sel = None if op["sel"] == "own" else b.sel if b.sel is not None else b.last_sel      # (after a failed select: the one before)
+        return self._counted(op, lambda d: g.count_selection_states(slot, d_sel=d_sel, d_counts=d, accumulate=op["acc"]))
+
+    def do_cnt_fetch(self, op, exp, before):
+        cnt = self.m.slots[op["slot"]].cnt
+        got = self.g.state_counts_to_host(op["slot"])
+        return self.by_id(cnt["tab"], got, cnt["parts"]) if cnt else got
 
     # -- plumbing -----------------------------------------------------------
     def do_set_stream(self, op, exp, before):

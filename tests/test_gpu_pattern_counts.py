@@ -22,6 +22,7 @@ from orc import Oracle, match_checksum
 from phfpfac_amd import GpuMatcher, PfacError, PfacTable, _ffi
 from phfpfac_amd.matcher import tiled_bytes
 from test_gpu_whole_words import VARIANTS
+from test_pattern_counts_ref import CHAIN_FORMS, CHAIN_N, CUT_LISTS, _chain_whole, chain_cuts, chain_parts, chain_reference
 
 pytestmark = pytest.mark.gpu
 
@@ -300,6 +301,55 @@ def test_accumulated_ranges_equal_one_scan(resolve):
         np.testing.assert_array_equal(g.state_counts_to_host(), before)
         g.count_states()
         np.testing.assert_array_equal(g.state_counts_to_host(), countref.state_counts(table, ids[second]))
+
+
+@pytest.mark.parametrize("name", CUT_LISTS)
+@pytest.mark.parametrize("form", range(len(CHAIN_FORMS)), ids=[f[0] for f in CHAIN_FORMS])
+def test_chained_and_chunked_counts_equal_one_scan(form, name, resolve, monkeypatch):
+    """The header's promise: counts accumulated over chained ranges "are the counts of one scan of the whole" -- for
+    2-, 4- and 8-byte records, seeded random cuts into 2, 5 and 17 ranges and the fixed list of shapes where chaining goes
+    wrong (test_pattern_counts_ref.chain_cuts), and for four accumulations, each into the slot-owned buffer and into a
+    guarded caller's buffer: the scan's counts, the counts after the whole-word filter (prev_byte / next_byte from the
+    neighbours), and the selection's counts without and with the filter (entry chained from the previous exit).  Every
+    step's n_counted is the reference's count for that range; the sums are the histograms of ONE oracle scan of the
+    whole through wordref.filter_words and llref.greedy (the CPU twin in test_pattern_counts_ref.py shows the parts'
+    references sum to them for these very cuts)."""
+    pat, env, width = CHAIN_FORMS[form]
+    assert (pat, env, width) in VARIANTS and CHAIN_N == N
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    path, para = resolve(pat), resolve("paragraph402")
+    table = PfacTable.from_file(path, 256)
+    buf, pos, _, lens, M = _chain_whole(path, para)
+    ref = chain_reference(path, para, name, form)
+    parts = chain_parts(buf, chain_cuts(name, form, buf, pos, lens, M), M)
+    assert M == table.max_pat_len and len(parts) == len(ref["ranges"])
+    with GpuMatcher(0, 1) as g:
+        g.load_table(table)
+        g.set_final_lengths(table.final_lengths())
+        for what in ("plain", "kept", "sel", "fsel"):
+            guard = guarded_counts(table, fill=0x3C)
+            entry = 0
+            for k, ((a, b, part, prev, nxt), r) in enumerate(zip(parts, ref["ranges"])):
+                tag = f"{pat} {name} {what}: range {k} [{a}, {b})"
+                assert scan(g, part, b - a) == r["plain"].size, tag
+                if k == 0:
+                    assert g.scan_format()[0] == width
+                if what in ("kept", "fsel"):
+                    assert g.filter_whole_words(prev_byte=prev, next_byte=nxt) == r["kept"].size, tag
+                if what in ("sel", "fsel"):
+                    assert entry == r["entry" if what == "sel" else "fentry"], tag
+                    n_sel, entry = g.select_leftmost_longest(entry)
+                    assert n_sel == r[what].size, tag
+                count = g.count_selection_states if what in ("sel", "fsel") else g.count_states
+                assert count(accumulate=k > 0) == r[what].size, tag
+                assert count(d_counts=guard.ptr, accumulate=k > 0) == r[what].size, tag
+            g.sync()
+            guard.check(what=f"the caller's d_counts ({pat} {name} {what})")
+            want = countref.state_counts(table, ref["whole"][what])
+            np.testing.assert_array_equal(g.state_counts_to_host(), want, err_msg=f"{pat} {name} {what}: the slot's counts")
+            np.testing.assert_array_equal(counts_of(guard), want, err_msg=f"{pat} {name} {what}: the caller's counts")
+            assert int(want.sum()) == ref["whole"][what].size > 0
 
 
 # ---------------------------------------------------------------------------

@@ -2,7 +2,8 @@
 kernel knobs, many sizes, two slots, passes in any order, results fetched late, documented errors in between -- every
 result compared bit for bit with what include/pfac.h promises for that history.  The random plans are the suite's seeds;
 the named sessions are histories random plans reach rarely; half of the plans and the sessions at the end of this file
-have the whole-word filter among their calls.  Run with -m gpu on an MI355X.  Expectations come from the
+have the whole-word filter among their calls, a third of the plans and the last group of sessions the per-pattern counts.
+Run with -m gpu on an MI355X.  Expectations come from the
 CPU oracle, llref, replref, docref, docreplref and the pattern files, never from the device.  No session aims at the
 scan's wait protocol: they provoke the errors the header documents, nothing else."""
 import gc
@@ -26,8 +27,10 @@ def k(tab, **knobs):
     return i
 
 
-def load(tab, rkey="r0", **knobs):
-    return [dict(op="load_table", tab=tab, knob=k(tab, **knobs)), dict(op="set_flen"), dict(op="set_reps", rkey=rkey)]
+def load(tab, rkey="r0", cknob=None, **knobs):
+    """Upload, lengths, replacements; `cknob`: the entry of S.CKNOBS (the count knobs) the table is installed under."""
+    up = dict(op="load_table", tab=tab, knob=k(tab, **knobs), **({} if cknob is None else {"cknob": cknob}))
+    return [up, dict(op="set_flen"), dict(op="set_reps", rkey=rkey)]
 
 
 def scan(tab, inp, slot=0, no=None):
@@ -63,6 +66,18 @@ def fetch(kind, slot=0, **kw):
     return dict(op=kind, slot=slot, **kw)
 
 
+def cnt(slot=0, dst="own", acc=False, heap="own", ns="ok"):
+    return dict(op="count", slot=slot, dst=dst, acc=acc, heap=heap, ns=ns)
+
+
+def cnt_sel(slot=0, dst="own", acc=False, sel="own"):
+    return dict(op="count_sel", slot=slot, dst=dst, acc=acc, sel=sel)
+
+
+def cnt_fetch(slot=0):
+    return dict(op="cnt_fetch", slot=slot)
+
+
 def run(ops, want=None):
     """The operations on one fresh context; `want`: the statuses the model must give, as a check of the session itself."""
     m = S.Model()
@@ -74,15 +89,18 @@ def run(ops, want=None):
         return S.run(g, ops, m, seed="named")
 
 
-@pytest.mark.parametrize("seed,words", [(s, False) for s in S.SEEDS] + [(s, True) for s in S.WORD_SEEDS],
-                         ids=[str(s) for s in S.SEEDS] + [f"words-{s}" for s in S.WORD_SEEDS])
-def test_session(seed, words):
-    """One random plan on one context; `words`: a plan of the family that filters whole words."""
-    ops = S.plan(seed, words=words)
+@pytest.mark.parametrize("seed,family", [(s, "") for s in S.SEEDS] + [(s, "words") for s in S.WORD_SEEDS] + [(s, "counts") for s in S.COUNT_SEEDS],
+                         ids=[str(s) for s in S.SEEDS] + [f"words-{s}" for s in S.WORD_SEEDS] + [f"counts-{s}" for s in S.COUNT_SEEDS])
+def test_session(seed, family):
+    """One random plan on one context; `family`: "words" = a plan that filters whole words, "counts" = one that also
+    counts matches per pattern."""
+    ops = S.plan(seed, words=family == "words", counts=family == "counts")
+    tag = f" ({family})" if family else ""
     with GpuMatcher(0, S.N_SLOTS) as g:
-        st = S.run(g, ops, S.Model(), seed=f"{seed} (words)" if words else seed)
-    print(f"session {seed}{' (words)' if words else ''}: {st['ops']} operations ({st['errors']} documented errors), {st['compared']} records and bytes compared, "
-          f"record widths {sorted(st['widths'])}, staging {sorted(st['staging'])}, {sorted(st['variants'])}")
+        st = S.run(g, ops, S.Model(), seed=f"{seed}{tag}" if family else seed)
+    print(f"session {seed}{tag}: {st['ops']} operations ({st['errors']} documented errors), {st['compared']} records and bytes compared, "
+          f"record widths {sorted(st['widths'])}, staging {sorted(st['staging'])}, {sorted(st['variants'])}, {st['counts']} counts under "
+          f"{sorted(st['regimes'])}")
 
 
 def test_large_dense_then_tiny_sparse_then_every_pass():
@@ -437,3 +455,123 @@ def test_class_and_escaped_tables_through_the_filter(t, inp, knobs, a, b):
     if S.expectations().width(t, k(t, **knobs)) != 8:
         ops.append(fetch("packed"))
     run(ops, want=[S.OK] * len(ops))
+
+
+# ---------------------------------------------------------------------------
+# the per-pattern counts as calls among many on a long-lived context
+
+BINS16 = S.CKNOBS.index({"PFAC_COUNT_BINS": "16"})
+A, E, O = S.E_ARG, S.E_STATE, S.E_OVERFLOW
+
+
+@pytest.mark.parametrize("cknob", [0, BINS16], ids=["default", "bins16"])
+def test_counts_in_buffers_sized_by_a_large_scan(cknob):
+    """2 000 003 bytes, then 4097 on the same slot: the tile index, the scratch and the staging are the large scan's, longer
+    than the small one; the 150 final states behind a table or behind 16 cache slots."""
+    t = "mid4"
+    ops = load(t, cknob=cknob) + [scan(t, 0), cnt(), cnt(dst="caller"), cnt_fetch(), scan(t, 1), cnt(), cnt(dst="caller"), cnt_fetch(),
+                                  flt(1), cnt(acc=True), cnt(dst="caller", acc=True), pss("select"), cnt_sel(acc=True), cnt_sel(dst="caller"),
+                                  cnt_fetch(), records(t, 1, f=fkey(t, (1, "")))]
+    st = run(ops, want=[S.OK] * len(ops))
+    assert st["regimes"] == {(cknob, "cache" if cknob else "direct")}
+
+
+def test_counts_across_record_widths_2_8_4():
+    """A count after each width; the slot's counts fetched before the next upload and once more after it, when they are
+    still the old table's num_final entries."""
+    up = lambda tab, **knobs: dict(op="load_table", tab=tab, knob=k(tab, **knobs), cknob=BINS16)      # noqa: E731
+    ops = [up("abc2"), scan("abc2", 0), cnt(), cnt_fetch(), cnt(dst="caller"),
+           up("wide8", PFAC_WIDE="1"), cnt_fetch(), cnt(acc=True), scan("wide8", 1), cnt(acc=True), cnt(), cnt(dst="caller"), cnt_fetch(),
+           up("mid4"), cnt_fetch(), scan("mid4", 2), cnt(dst="caller", acc=True), cnt_fetch(), cnt(), cnt_fetch(), records("mid4", 2)]
+    st = run(ops, want=[0] * 5 + [0, 0, E, 0, E, 0, 0, 0] + [0] * 8)
+    assert st["widths"] == {2, 4, 8} and st["regimes"] == {(BINS16, "direct"), (BINS16, "cache")}
+
+
+def test_slot_counts_across_reserve_upload_filter_and_every_pass():
+    """The five passes run between a count and its fetch, slot-owned outputs each, on the same slot; then every pass's
+    result is what it was, also after another count; then a filter, a reserve that drops the scan and an upload."""
+    t, inp = "l2", 0
+    no = X.input_size(t, inp)
+    rp = fetch("rp_fetch", first=0, n=int(X.docsel(t, inp, no, "d0", (), "r0")[4].size))
+    late = [fetch("seg_fetch"), fetch("docsel_fetch"), fetch("sel_fetch"), rp, fetch("rpd_fetch")]
+    ops = load(t, PFAC_FORCE_L2="1") + [scan(t, inp), doc(t, inp, "d0"), cnt(), pss("segment"), pss("select"), pss("replace"), pss("select_docs"),
+                                        pss("replace_docs"), cnt_fetch()] + late + [cnt_sel(acc=True), cnt(dst="caller"), cnt_fetch()] + late
+    ops += [flt(1), cnt_fetch(), cnt(acc=True), dict(op="reserve_grow", slot=0, which="records", k=1), cnt_fetch(), cnt(), cnt_sel(), cnt_fetch(),
+            dict(op="load_table", tab="abc2", knob=k("abc2")), cnt_fetch(), cnt(acc=True), cnt_fetch()] + late[:3]
+    run(ops, want=[0] * 3 + [0] * 9 + [0] * 5 + [0] * 3 + [0] * 5 + [0, 0, 0, 0, 0, E, E, 0, 0, 0, E, 0] + [0] * 3)
+
+
+def test_accumulate_over_scan_filtered_scan_and_selection():
+    """The slot-owned and the caller's buffer side by side, a refused call of each kind in between: a wrong n_states, a
+    misaligned d_counts, a stale selection, a foreign heap.  Both buffers are what they were after each."""
+    t, inp = "mid4", 2
+    no = X.input_size(t, inp)
+    c = X.count(t, inp, no)
+    both = lambda **kw: [cnt(acc=True, **kw), cnt(dst="caller", acc=True, **kw)]      # noqa: E731
+    ops = load(t) + [scan(t, inp), cnt(), cnt(dst="caller"), cnt(ns="plus", acc=True), cnt(dst="caller", ns="minus", acc=True), cnt(dst="caller", ns="zero"),
+                     cnt_fetch(), flt(1)] + both() + [cnt(dst="misaligned", acc=True), pss("select"), cnt_sel(acc=True), cnt_sel(dst="caller", acc=True), flt(3),
+                     cnt_sel(acc=True), cnt_sel(dst="caller", acc=True), cnt_fetch(), dict(op="scan_ext", slot=0, inp=inp, no=no, cap=c + c // 4 + 65536)]
+    ops += both(heap="none") + both(heap="slot") + [cnt_fetch()] + both() + [cnt_fetch(), records(t, inp)]
+    run(ops, want=[0] * 3 + [0, 0, 0, A, A, A, 0, 0, 0, 0, A, 0, 0, 0, 0, E, E, 0, 0, A, A, A, A, 0, 0, 0, 0, 0])
+
+
+@pytest.mark.parametrize("share", [True, False], ids=["shared-stream", "own-streams"])
+def test_two_slots_count_while_the_other_scans(share):
+    """Slot 0 has a scan pending while slot 1 counts and fetches, then the reverse; the counts never leak between slots."""
+    t = "l2"
+    c = X.count(t, 0, 300_007)
+    start = lambda slot: dict(op="scan_start", slot=slot, inp=0, no=300_007, cap=c + c // 4 + 65536)      # noqa: E731
+    fin = lambda slot: dict(op="scan_finish", slot=slot)      # noqa: E731
+    ops = [dict(op="set_stream", slot=1, share=True)] if share else []
+    ops += load(t, PFAC_FORCE_L2="1") + [scan(t, 1, slot=1), start(0), cnt(slot=1), cnt_fetch(slot=1), cnt(slot=0), cnt_fetch(slot=0), cnt(slot=1, dst="caller"),
+                                         fin(0), cnt(slot=0), cnt(slot=0, dst="caller"), start(1), cnt(slot=1, acc=True), cnt(slot=0, acc=True), cnt_fetch(slot=0),
+                                         cnt_fetch(slot=1), fin(1), cnt(slot=1, acc=True), cnt(slot=1, dst="caller", acc=True), cnt_fetch(slot=1), cnt_fetch(slot=0),
+                                         records(t, 0, slot=0), records(t, 0, slot=1)]
+    run(ops, want=[0] * (4 if share else 3) + [0, 0, 0, 0, E, E, 0, 0, 0, 0, 0, E, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0])
+
+
+def test_counts_of_a_scan_into_the_callers_heap():
+    """The right pointer counts; NULL and the slot's own heap are not the scan's (PFAC_E_ARG); an overflowed rescan is
+    PFAC_E_OVERFLOW whatever the arguments; the counts made before survive."""
+    t, inp = "mid4", 2
+    no = X.input_size(t, inp)
+    c = X.count(t, inp, no)
+    ext = lambda cap: dict(op="scan_ext", slot=0, inp=inp, no=no, cap=cap)      # noqa: E731
+    ops = load(t) + [scan(t, 1), cnt(), ext(c + c // 4 + 65536), cnt(acc=True), cnt(dst="caller"), cnt(heap="none"), cnt(dst="caller", heap="slot", acc=True),
+                     cnt_fetch(), flt(1), cnt(dst="caller", acc=True), ext(c // 2), cnt(), cnt(dst="caller", acc=True), cnt(heap="none", ns="plus"), cnt_fetch(),
+                     scan(t, inp), cnt(acc=True), cnt_fetch()]
+    run(ops, want=[0] * 3 + [0, 0, 0, 0, 0, A, A, 0, 0, 0, 0, O, O, O, 0, 0, 0, 0])
+
+
+def test_selection_counts_as_calls_in_a_session():
+    """The selection in the caller's d_out; a failed select into a too-small d_out leaves no selection to count (the
+    earlier one's buffer included); a per-document selection is still counted after new offsets, which end only the
+    per-document replace's right to it."""
+    t, inp = "l2", 1
+    small = dict(op="select", slot=0, own=False, small=True, entry=0)
+    assert X.sel(t, inp, X.input_size(t, inp), 0)[0].size > 1
+    ops = load(t, PFAC_FORCE_L2="1") + [scan(t, inp), cnt_sel(), pss("select", own=False), cnt_sel(sel="caller"), cnt_sel(sel="own"), cnt_sel(sel="junk", acc=True),
+                                        cnt_sel(sel="misaligned"), cnt_sel(sel="caller", dst="caller"), cnt_fetch(), small, cnt_sel(sel="caller"), cnt_sel(sel="own"),
+                                        cnt_fetch(), doc(t, inp, "d0"), pss("select_docs"), cnt_sel(acc=True), doc(t, inp, "d1"), cnt_sel(acc=True),
+                                        cnt_sel(dst="caller", acc=True), pss("replace_docs"), cnt_fetch(), fetch("docsel_fetch")]
+    run(ops, want=[0] * 3 + [0, E, 0, 0, E, A, A, 0, 0, O, E, E, 0, 0, 0, 0, 0, 0, 0, E, 0, 0])
+
+
+@pytest.mark.parametrize("t,inp,knobs", [("cclass", 0, {}), ("negcc", 0, dict(PFAC_FORCE_L2="1", PFAC_DENSE="1")), ("nlesc", 0, dict(PFAC_DENSE="1"))],
+                         ids=["cclass", "negcc", "nlesc"])
+def test_class_and_escaped_tables_counted_by_id(t, inp, knobs):
+    """Final states that stand for several patterns, a record or two per byte, newline and NUL patterns: the scan's, the
+    filtered scan's and both selections' counts, compared by pattern id."""
+    ops = load(t, cknob=1, **knobs) + [scan(t, inp), cnt(), cnt(dst="caller"), cnt_fetch(), pss("select"), cnt_sel(acc=True), cnt_sel(dst="caller", acc=True),
+                                       flt(1), cnt(acc=True), cnt_fetch(), doc(t, inp, "d0"), pss("select_docs", own=False), cnt_sel(sel="caller"),
+                                       cnt_sel(sel="caller", dst="caller"), cnt_fetch()]
+    st = run(ops, want=[S.OK] * len(ops))
+    assert st["regimes"] == {(1, "cache")}
+
+
+def test_same_table_uploaded_twice_is_a_new_generation():
+    """An accumulate onto the slot's counts of the upload before is PFAC_E_STATE, onto the caller's buffer it is allowed."""
+    t = "dups"
+    ops = load(t) + [scan(t, 0), cnt(), cnt(dst="caller")] + load(t) + [cnt_fetch(), cnt(acc=True), scan(t, 1), cnt(acc=True), cnt(dst="caller", acc=True),
+                                                                        cnt_fetch(), cnt_sel(acc=True), cnt(), cnt(acc=True), cnt_fetch()]
+    run(ops, want=[0] * 3 + [0, 0, 0] + [0] * 3 + [0, E, 0, E, 0, 0, E, 0, 0, 0])

@@ -4,11 +4,15 @@ fetch) order; the executor and the model run every plan against CpuDevice, a sta
 contract of include/pfac.h in the most obvious way; and each of CpuDevice's switchable defects makes a plan fail at or
 after the first operation the defect touches -- the harness has teeth without a kernel being mutated.  The plans come in
 two families: those of S.SEEDS, pinned by a digest to what they were before the whole-word filter existed, and those of
-S.WORD_SEEDS, in which the filter is an operation like any other."""
+S.WORD_SEEDS, in which the filter is an operation like any other, pinned likewise since the counts joined; and those
+of S.COUNT_SEEDS, which add the per-pattern counts (count, count_sel, cnt_fetch) under the count knobs of S.CKNOBS."""
 import collections
+import copy
 import hashlib
 import json
 import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -53,6 +57,7 @@ class _CpuSlot:
         self.prev_first = 0
         self.heap = CpuBuf(16)     # stands for the slot's own record heap where a pointer is compared
         self.last_n = 0
+        self.cnt = None            # the slot-owned counts: dict(gen, a)
 
 
 DEFECTS = ("stale_selection_survives_upload", "late_segment_returns_selection", "smaller_scan_returns_tail",
@@ -61,6 +66,13 @@ DEFECTS = ("stale_selection_survives_upload", "late_segment_returns_selection", 
 WORD_DEFECTS = ("count_stays_the_unfiltered_one", "selection_survives_filter", "refused_filter_filters_anyway",
                 "second_filter_replaces_first", "filter_ignores_neighbour_bytes", "filter_ignores_document_offsets",
                 "slot1_filter_changes_slot0", "text_follows_a_later_filter")
+
+
+# ... and those of the per-pattern counts, which only the plans of S.COUNT_SEEDS can meet
+COUNT_DEFECTS = ("accumulate_zeroes_first", "plain_count_does_not_zero", "counts_ignore_the_filter", "n_counted_stays_the_unfiltered_count",
+                 "refused_count_zeroes_its_destination", "caller_count_replaces_the_slots_counts", "counts_lost_at_upload",
+                 "counts_lost_at_reserve", "accumulate_across_upload_allowed", "stale_selection_still_counted",
+                 "docsel_counted_as_whole_stream", "slots_share_one_count_buffer", "count_disturbs_the_selection")
 
 
 class CpuDevice:
@@ -112,6 +124,9 @@ class CpuDevice:
         self.width = record_width(int(table.num_final), knobs)
         self.gen += 1
         self.flen, self.reps = False, None
+        for s in self.slots:
+            if s.cnt is not None and s.cnt["a"].any() and self._defect("counts_lost_at_upload"):
+                s.cnt = None
 
     def info(self):
         return {"variant": "cpu", "staging_buffers": 0, "staging_records": 0}
@@ -137,6 +152,8 @@ class CpuDevice:
         s = self.slots[slot]
         if (input_bytes > s.in_cap and s.in_cap) or (record_capacity > s.rec_cap and s.rec_cap):
             s.scan = None                                       # a buffer is replaced: no finished scan
+            if s.cnt is not None and self._defect("counts_lost_at_reserve"):
+                s.cnt = None
         if input_bytes > s.in_cap:
             s.in_cap = (input_bytes + 4095) // 4096 * 4096 + 1280
         s.rec_cap = max(s.rec_cap, record_capacity)
@@ -280,6 +297,109 @@ class CpuDevice:
             raise _err(S.E_ARG, "beyond the text")
         return self.slots[slot].text[first:first + n_bytes]
 
+    # -- counts per pattern ---------------------------------------------------
+    def _cnt_slot(self, slot):
+        if slot == 1 and self._defect("slots_share_one_count_buffer"):
+            return self.slots[0]
+        return self.slots[slot]
+
+    def _count(self, slot, ids, n, d_counts, n_states, flags):
+        """The arguments both count calls share, then the histogram of `ids` into the destination."""
+        own, acc = d_counts is None, bool(flags & 1)
+        cs = self._cnt_slot(slot)
+        n_ids = self.x.n_ids(self.tab)
+        if flags > 1 or n_states != n_ids or isinstance(d_counts, S.Odd):
+            raise _err(S.E_ARG, "flags, n_states or a misaligned d_counts")
+        if own and acc and cs.cnt is not None and cs.cnt["gen"] != self.gen and not self._defect("accumulate_across_upload_allowed"):
+            raise _err(S.E_STATE, "the slot's counts belong to an earlier table")
+        hist = np.bincount(ids, minlength=n_ids).astype(np.uint64)
+        if own:
+            old = cs.cnt["a"] if cs.cnt is not None and cs.cnt["a"].size == n_ids else np.zeros(n_ids, np.uint64)
+        else:
+            old = d_counts.a[:n_ids * 8].view(np.uint64).copy()
+        if acc and old.any() and self._defect("accumulate_zeroes_first"):
+            acc = False
+        if not acc and old.any() and hist.any() and self._defect("plain_count_does_not_zero"):
+            acc = True
+        new = old + hist if acc else hist
+        if own:
+            cs.cnt = dict(gen=self.gen, a=new)
+        else:
+            d_counts.put(new)
+            if self._defect("caller_count_replaces_the_slots_counts"):
+                cs.cnt = dict(gen=self.gen, a=hist)
+        sel = self.slots[slot].sel
+        if sel is not None and sel["own"] and sel["rec"].size and self._defect("count_disturbs_the_selection"):
+            sel["rec"] = sel["rec"].copy()
+            sel["rec"]["state"][0] += 1
+        return int(n)
+
+    def _refused(self, slot, d_counts, fn):
+        try:
+            return fn()
+        except PfacError:
+            buf = d_counts.buf if isinstance(d_counts, S.Odd) else d_counts
+            if "refused_count_zeroes_its_destination" in self.defects:
+                cs = self.slots[slot]
+                if buf is None and cs.cnt is not None and cs.cnt["a"].any() and self._defect("refused_count_zeroes_its_destination"):
+                    cs.cnt["a"] = np.zeros_like(cs.cnt["a"])
+                if buf is not None and self._defect("refused_count_zeroes_its_destination"):
+                    buf.a[:buf.a.size - 64] = 0
+            raise
+
+    def raw_count_states(self, slot, d_records, d_counts, n_states, flags):
+        def call():
+            s = self.slots[slot]
+            sc = self._finished(slot, 0)
+            if self.tab is None or sc["gen"] != self.gen:
+                raise _err(S.E_STATE, "a scan made with an earlier table")
+            if sc["over"]:
+                raise _err(S.E_OVERFLOW, "the scan overflowed")
+            if (d_records if d_records is not None else s.heap) is not sc["heap"]:
+                raise _err(S.E_ARG, "not the heap of the slot's last scan")
+            ids, n = sc["ids"], sc["ids"].size
+            if ids.size != sc["full"][1].size and self._defect("counts_ignore_the_filter"):
+                ids = sc["full"][1]
+            if n != sc["full"][1].size and self._defect("n_counted_stays_the_unfiltered_count"):
+                n = sc["full"][1].size
+            return self._count(slot, ids, n, d_counts, n_states, flags)
+        return self._refused(slot, d_counts, call)
+
+    def count_states(self, slot=0, d_records=None, d_counts=None, accumulate=False):
+        if self.tab is None:
+            raise _err(S.E_STATE, "no table")
+        return self.raw_count_states(slot, d_records, d_counts, self.x.n_ids(self.tab), int(accumulate))
+
+    def count_selection_states(self, slot=0, d_sel=None, d_counts=None, accumulate=False):
+        def call():
+            s = self.slots[slot]
+            sc, sel = s.scan, s.sel
+            if sc is None or sc["pending"] or sel is None:
+                raise _err(S.E_STATE, "no selection since the slot's last scan")
+            if sel["seq"] != sc["seq"] and not (sel["gen"] == self.gen and self._defect("stale_selection_still_counted")):
+                raise _err(S.E_STATE, "no selection since the slot's last scan")
+            if self.tab is None or sc["gen"] != self.gen or sel["gen"] != self.gen:
+                raise _err(S.E_STATE, "earlier table")
+            if d_sel is None and not sel["own"]:
+                raise _err(S.E_STATE, "the selection went to the caller's buffer")
+            if isinstance(d_sel, S.Odd):
+                raise _err(S.E_ARG, "misaligned d_sel")
+            ids = sel["rec"]["state"].astype(np.int64)
+            if d_sel is not None and ids.size and (getattr(d_sel, "junk", False) or d_sel is not sel["buf"]):
+                raise _err(S.E_ARG, "not a selection of this scan and table")
+            if sel["kind"] == "docs" and "docsel_counted_as_whole_stream" in self.defects:
+                idx, _ = greedy(sc["pos"], sc["lens"], 0, sc["no"])
+                if not np.array_equal(sc["ids"][idx], ids) and self._defect("docsel_counted_as_whole_stream"):
+                    ids = sc["ids"][idx]
+            return self._count(slot, ids, ids.size, d_counts, self.x.n_ids(self.tab), int(accumulate))
+        return self._refused(slot, d_counts, call)
+
+    def state_counts_to_host(self, slot=0):
+        cs = self._cnt_slot(slot)
+        if cs.cnt is None:
+            raise _err(S.E_STATE, "the slot holds no counts")
+        return cs.cnt["a"].copy()
+
     # -- documents ----------------------------------------------------------
     def set_doc_offsets(self, offsets, slot=0):
         s = self.slots[slot]
@@ -376,7 +496,7 @@ class CpuDevice:
             d_out.put(rec)
             if d_first is not None:
                 d_first.put(first)
-        return dict(rec=rec, first=first, own=d_out is None)
+        return dict(rec=rec, first=first, own=d_out is None, buf=d_out)
 
     def segment_records(self, n_docs, d_doc_offsets=None, d_out=None, out_cap=0, d_doc_first=None, slot=0, d_records=None):
         s = self.slots[slot]
@@ -513,6 +633,11 @@ def word_plans():
     return {seed: S.plan(seed, words=True) for seed in S.WORD_SEEDS}
 
 
+@pytest.fixture(scope="module")
+def count_plans():
+    return {seed: S.plan(seed, counts=True) for seed in S.COUNT_SEEDS}
+
+
 # SHA-256 of json.dumps([plan(seed) for seed in SEEDS], sort_keys=True) at the commit before the filter joined the
 # harness (with the pool's pattern lines in a fixed order, see _gen_lines): the first family has not moved.
 OLD_PLANS_SHA256 = "e756864a7526abf17871316573c9079f43bc1106d0403266a50f5130050b937a"
@@ -522,6 +647,18 @@ def test_the_plans_without_the_filter_are_what_they_were(plans):
     assert [seed for seed in plans] == S.SEEDS and len(S.SEEDS) == 24
     assert hashlib.sha256(json.dumps([plans[seed] for seed in S.SEEDS], sort_keys=True).encode()).hexdigest() == OLD_PLANS_SHA256
     assert not any(op["op"] == "filter" for ops in plans.values() for op in ops)
+
+
+# ... and of json.dumps([plan(seed, words=True) for seed in WORD_SEEDS], sort_keys=True) at the commit before the counts
+# joined the harness: the second family has not moved either.
+WORD_PLANS_SHA256 = "5cbdcad3040302c5db5d67f19c7157018a74c11ca9fbfca3e56f190d3e672657"
+COUNT_OPS = ("count", "count_sel", "cnt_fetch")
+
+
+def test_the_plans_with_the_filter_are_what_they_were(word_plans):
+    assert [seed for seed in word_plans] == S.WORD_SEEDS and len(S.WORD_SEEDS) == 24
+    assert hashlib.sha256(json.dumps([word_plans[seed] for seed in S.WORD_SEEDS], sort_keys=True).encode()).hexdigest() == WORD_PLANS_SHA256
+    assert not any(op["op"] in COUNT_OPS or "cknob" in op for ops in word_plans.values() for op in ops)
 
 
 def test_plans_are_deterministic_and_well_formed(plans, word_plans):
@@ -718,10 +855,12 @@ def first_touch(seed, ops, defect):
     return touched, None
 
 
-@pytest.mark.parametrize("defect", DEFECTS + WORD_DEFECTS)
-def test_every_defect_is_caught(defect, plans, word_plans):
+@pytest.mark.parametrize("defect", DEFECTS + WORD_DEFECTS + COUNT_DEFECTS)
+def test_every_defect_is_caught(defect, plans, word_plans, count_plans):
     caught = []
     family = {f"{seed} (words)": ops for seed, ops in word_plans.items()} if defect in WORD_DEFECTS else plans
+    if defect in COUNT_DEFECTS:
+        family = {f"{seed} (counts)": ops for seed, ops in count_plans.items()}
     for seed, ops in family.items():
         touched, failed = first_touch(seed, ops, defect)
         assert failed is None or (touched is not None and failed >= touched), f"seed {seed}: failed at {failed} before the defect acted ({touched})"
@@ -745,5 +884,199 @@ def test_shrink_keeps_a_failure(plans):
             with pytest.raises(AssertionError):
                 S.run(CpuDevice([defect]), S.shrink(seed, failed + 1), S.Model(), seed=seed)
             S.run(CpuDevice([defect]), S.shrink(seed, failed), S.Model(), seed=seed)
+            return
+    raise AssertionError("no plan to shrink")
+
+
+# ---------------------------------------------------------------------------
+# the third family: the per-pattern counts
+
+def test_the_pool_tables_with_an_injective_idmap():
+    """Counts of these tables are compared state for state as well as by pattern id: all the literal tables (the
+    unreachable states of `dups` report the losing lines' ids), not the two class tables."""
+    x = S.expectations()
+    assert {t for t in S.TABLES if x.injective(t)} == set(S.TABLES) - {"cclass", "negcc"}
+    for t in S.TABLES:
+        assert x.n_ids(t) > int(np.asarray(x.table(t).idmap).max())
+        if x.injective(t):
+            part = ("scan", t, 0, x.input_size(t, 0), ())
+            assert int(x.part_states(part).sum()) == int(x.part_counts(part).sum()) == x.count(*part[1:])
+
+
+def test_count_plans_are_deterministic_and_well_formed(count_plans, word_plans):
+    for seed in S.COUNT_SEEDS[:3]:
+        assert S.plan(seed, counts=True) == count_plans[seed] != word_plans[seed]
+        assert S.shrink(seed, 23, counts=True) == count_plans[seed][:23]
+    assert count_plans[0] != count_plans[1]
+    for seed, ops in count_plans.items():
+        assert len(ops) == S.PLAN_OPS
+        m = S.Model()
+        for k, op in enumerate(ops):
+            assert hasattr(S.Executor, "do_" + op["op"]), f"seed {seed} op {k}: the executor cannot perform {S.fmt(op)}"
+            assert ("cknob" in op) == (op["op"] == "load_table")
+            st = m.apply(op).status
+            assert st in (S.OK, S.E_ARG, S.E_STATE, S.E_OVERFLOW), f"seed {seed} op {k}: the contract does not decide {S.fmt(op)}"
+
+
+def test_count_plans_are_the_same_in_another_process(count_plans):
+    """The plans replay between processes (another hash seed: no set or dict order leaks into them)."""
+    seeds = S.COUNT_SEEDS[:3]
+    code = ("import hashlib, json, session as S; print(hashlib.sha256(json.dumps([S.plan(s, counts=True) for s in %r], sort_keys=True).encode()).hexdigest())" % seeds)
+    here = os.path.dirname(os.path.abspath(__file__))
+    env = dict(os.environ, PYTHONHASHSEED="12345", PYTHONPATH=os.pathsep.join([here, os.path.dirname(here)]))
+    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, check=True, timeout=300).stdout.split()[-1]
+    assert out == hashlib.sha256(json.dumps([count_plans[s] for s in seeds], sort_keys=True).encode()).hexdigest()
+
+
+def _walk_models(plans):
+    """(seed, k, op, status, the model before the operation, the model after it) over the plans."""
+    for seed, ops in plans.items():
+        m = S.Model()
+        for k, op in enumerate(ops):
+            was = copy.deepcopy(m)
+            yield seed, k, op, m.apply(op).status, was, m
+
+
+def test_count_plans_reach_everything(count_plans):
+    """Conditions, not measurements: the histories the count family exists for all occur in the suite's 24 plans."""
+    x = S.expectations()
+    kinds, ok, sel_ok, late, errs, overlays = set(), set(), set(), set(), set(), set()
+    most_parts, mixed, errors, total = 0, False, 0, 0
+    since = {}                                                  # (seed, slot) -> what happened since the slot's last OK own count
+    dropped = {}                                                # (seed, slot) -> its scan was dropped by a reserve_grow
+    for seed, k, op, st, was, m in _walk_models(count_plans):
+        kind, slot = op["op"], op.get("slot", 0)
+        kinds.add(kind)
+        total += 1
+        errors += st != S.OK
+        ws, s = was.slots[slot], m.slots[slot]
+        sc = ws.scan
+        ev = since.get((seed, slot))
+        if kind == "load_table":
+            for key in since:
+                if key[0] == seed:
+                    since[key].add("upload")
+        elif ev is not None and st == S.OK:
+            if kind in ("scan_bytes", "scan_ext", "scan_start"):
+                ev.add("scan")
+            elif kind == "reserve_grow" and sc is not None and s.scan is None:
+                ev.add("grow")
+            elif kind == "filter":
+                ev.add("filter")
+            elif kind in S.PASSES:
+                ev.add("pass")
+            elif kind in COUNT_OPS[:2] and op["dst"] == "caller":
+                ev.add("caller")
+        elif ev is not None and kind in COUNT_OPS[:2]:
+            ev.add("refused")
+        if kind == "reserve_grow":
+            dropped[(seed, slot)] = sc is not None and s.scan is None
+        elif kind.startswith("scan") and st == S.OK:
+            dropped[(seed, slot)] = False
+        if kind == "count" and st == S.OK:
+            ok |= {("dst", op["dst"], op["acc"]), ("slot", slot), ("ext", sc["ext"]), ("filtered", bool(sc["filt"])),
+                   ("empty", was._count(sc) == 0), ("width", x.width(sc["tab"], sc["knob"])), ("shared", slot == 1 and ws.shared)}
+            bins = int(S.CKNOBS[was.cknob].get("PFAC_COUNT_BINS", 0))
+            overlays.add((was.cknob, bool(bins) and int(x.table(sc["tab"]).num_final) > bins))
+        if kind == "count_sel" and st == S.OK:
+            sel_ok |= {("kind", ws.sel["kind"]), ("sel", op["sel"]), ("dst", op["dst"], op["acc"])}
+        if kind in COUNT_OPS[:2] and st == S.OK and op["dst"] == "own":
+            since[(seed, slot)] = set()
+            parts = s.cnt["parts"]
+            most_parts = max(most_parts, len(parts))
+            mixed |= len({p[0] == "scan" for p in parts}) == 2
+        if kind == "cnt_fetch":
+            if st == S.OK:
+                late |= ev
+            else:
+                errs.add(("cnt_fetch", "E_STATE"))
+        if kind == "count" and st != S.OK:
+            if sc is None:
+                errs.add(("count", "E_STATE after reserve" if dropped.get((seed, slot)) else "E_STATE no scan"))
+            elif sc["pending"]:
+                errs.add(("count", "E_STATE pending"))
+            elif sc["gen"] != was.gen:
+                errs.add(("count", "E_STATE earlier table"))
+            elif st == S.E_OVERFLOW:
+                errs.add(("count", "E_OVERFLOW"))
+            elif st == S.E_STATE:
+                errs.add(("count", "E_STATE accumulate onto an earlier generation"))
+            else:
+                assert st == S.E_ARG
+                errs.add(("count", "E_ARG " + ("n_states " + op["ns"] if op["ns"] != "ok" else "d_counts" if op["dst"] == "misaligned" else "heap")))
+        if kind == "count_sel" and st != S.OK:
+            if st == S.E_ARG:
+                errs.add(("count_sel", "E_ARG " + op["sel"]))
+            elif ws.sel is None or sc is None:
+                errs.add(("count_sel", "E_STATE no selection"))
+            elif ws.sel["seq"] != sc["seq"]:
+                errs.add(("count_sel", "E_STATE stale"))
+            elif sc["gen"] != was.gen:
+                errs.add(("count_sel", "E_STATE earlier table"))
+            elif op["sel"] == "own" and not ws.sel["own"]:
+                errs.add(("count_sel", "E_STATE NULL for a caller's selection"))
+            else:
+                errs.add(("count_sel", "E_STATE accumulate onto an earlier generation"))
+    assert kinds == set(S.COUNT_KINDS), set(S.COUNT_KINDS) - kinds
+    want = {("dst", d, a) for d in ("own", "caller") for a in (False, True)} | {("slot", 0), ("slot", 1), ("ext", True), ("ext", False),
+            ("filtered", True), ("filtered", False), ("empty", True), ("width", 2), ("width", 4), ("width", 8), ("shared", True)}
+    assert ok >= want, sorted(want - ok, key=str)
+    want = {(c, "PFAC_COUNT_BINS" in d) for c, d in enumerate(S.CKNOBS)}     # every overlay; where it sets the bins, the cache regime
+    assert overlays >= want, sorted(want - overlays)
+    want = {("kind", "whole"), ("kind", "docs"), ("sel", "own"), ("sel", "caller")} | {("dst", d, a) for d in ("own", "caller") for a in (False, True)}
+    assert sel_ok >= want, sorted(want - sel_ok, key=str)
+    want = {"scan", "upload", "grow", "filter", "pass", "caller", "refused"}
+    assert late >= want, sorted(want - late)
+    assert most_parts >= 3 and mixed, (most_parts, mixed)
+    want = {("count", e) for e in ("E_STATE no scan", "E_STATE pending", "E_STATE earlier table", "E_STATE after reserve", "E_OVERFLOW",
+                                   "E_ARG n_states minus", "E_ARG n_states plus", "E_ARG n_states zero", "E_ARG heap", "E_ARG d_counts",
+                                   "E_STATE accumulate onto an earlier generation")}
+    want |= {("count_sel", e) for e in ("E_STATE no selection", "E_STATE stale", "E_STATE earlier table", "E_STATE NULL for a caller's selection",
+                                       "E_ARG junk", "E_ARG misaligned")} | {("cnt_fetch", "E_STATE")}
+    assert errs >= want, sorted(want - errs)
+    assert 0.08 < errors / total < 0.25, f"{errors} of {total} operations are illegal"
+
+
+def test_count_plans_count_something(count_plans):
+    """By the reference alone: the count vectors the plans compare are not trivial."""
+    x = S.expectations()
+    rich = set()
+    filtered = selected = summed = False
+    for seed, k, op, st, was, m in _walk_models(count_plans):
+        if st != S.OK or op["op"] not in COUNT_OPS:
+            continue
+        s = m.slots[op["slot"]]
+        if op["op"] == "cnt_fetch" or op["dst"] == "caller":
+            held = s.cnt if op["op"] == "cnt_fetch" else s.cbuf
+            parts = held["parts"]
+            vec = x.sum_counts(held["tab"], parts)
+            if int((vec > 0).sum()) >= 2:
+                rich.add(seed)
+            summed |= len(parts) > 1 and not np.array_equal(vec, x.part_counts(parts[-1]))
+        if op["op"] == "cnt_fetch":
+            continue
+        part = (s.cnt if op["dst"] == "own" else s.cbuf)["parts"][-1]
+        if part[0] == "scan" and part[4]:
+            filtered |= not np.array_equal(x.part_counts(part), x.state_counts(*part[1:4]))
+        if part[0] != "scan":
+            selected |= not np.array_equal(x.part_counts(part), x.state_counts(part[1], part[2], part[3], part[5]))
+    assert 2 * len(rich) >= len(count_plans), sorted(rich)
+    assert filtered and selected and summed, (filtered, selected, summed)
+
+
+@pytest.mark.parametrize("seed", S.COUNT_SEEDS)
+def test_count_plan_passes_on_the_cpu_device(seed, count_plans):
+    stats = S.run(CpuDevice(), count_plans[seed], S.Model(), seed=f"{seed} (counts)")
+    assert stats["ops"] == S.PLAN_OPS and stats["errors"] > 0 and stats["counts"] > 0
+
+
+def test_shrink_keeps_a_count_failure(count_plans):
+    defect = "plain_count_does_not_zero"
+    for seed, ops in count_plans.items():
+        touched, failed = first_touch(seed, ops, defect)
+        if failed is not None:
+            with pytest.raises(AssertionError):
+                S.run(CpuDevice([defect]), S.shrink(seed, failed + 1, counts=True), S.Model(), seed=seed)
+            S.run(CpuDevice([defect]), S.shrink(seed, failed, counts=True), S.Model(), seed=seed)
             return
     raise AssertionError("no plan to shrink")
