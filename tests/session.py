@@ -124,6 +124,7 @@ CKNOB_NAMES = ("PFAC_COUNT_BINS", "PFAC_COUNT_GRID", "PFAC_COUNT_THREADS")
 COUNT_DIRECT_MAX = 8192                 # final states a workgroup's LDS table holds (include/pfac.h); fewer under PFAC_COUNT_BINS
 CNT_FILL = 0x11                         # a fresh caller's count buffer: every entry CNT_ENTRY, so that an accumulate that
 CNT_ENTRY = CNT_FILL * 0x0101010101010101   # zeroes, or a plain count that does not, shows at the first use
+OUT_FILL = 0xC7                         # every byte of a fresh caller's pass output and of the guard bands around it
 MAX_FILTERS = 3                         # distinct filters on one scan: more would only thin out the cache
 WORD_TAB = {"cclass": b"abcxyz", "negcc": b"abcy", "nlesc": b"abxq\n"}     # (the other tables: the first half of their symbols)
 
@@ -1315,7 +1316,8 @@ def shrink(seed, k, n_ops=PLAN_OPS, words=False, counts=False):
 
 class _SlotBufs:
     def __init__(self):
-        self.inp = self.rec = self.sel = self.first = None      # caller-owned device buffers the slot's state refers to
+        self.inp = self.rec = None                              # caller-owned device buffers the slot's state refers to
+        self.sel = self.first = None                            # ... and the guarded outputs (_OutBuf) of its last selection
         self.last_sel = None                                    # the d_out of the last selection that went to the caller
         self.cnt = None                                         # the caller's count buffer (_CountBuf) and the model's serial of it
         self.cnt_serial = 0
@@ -1354,6 +1356,37 @@ class _CountBuf:
             assert (self.buf.a[self.n * 8:] == CNT_FILL).all(), f"bytes behind {what} changed"
 
 
+class _OutBuf:
+    """A pass's caller-owned output (d_out, d_doc_first, d_out_offsets): exactly n_bytes -- what the ABI asks for, not a
+    byte of slack -- between guard bands, every byte OUT_FILL (heapguard.GuardedBuffer; on a stand-in device one of its
+    buffers, the band behind the payload).  `ptr` is what the call is given."""
+
+    def __init__(self, g, n_bytes):
+        self.n = int(n_bytes)
+        if hasattr(g, "alloc"):
+            self.guard, self.buf = None, g.alloc(self.n + 64)
+            self.buf.a[:] = OUT_FILL
+            self.ptr = self.buf
+        else:
+            from heapguard import GuardedBuffer
+            self.guard = GuardedBuffer(self.n, fill=OUT_FILL, device=f"cuda:{g.device}")
+            self.ptr = self.guard.ptr
+
+    def read(self, dtype, count):
+        nb = int(count) * np.dtype(dtype).itemsize
+        assert nb <= self.n, f"the call reports {count} entries, the buffer was sized for {self.n // np.dtype(dtype).itemsize}"
+        raw = self.guard.host(nb) if self.guard is not None else self.buf.a[:nb]
+        return raw.view(dtype).copy()
+
+    def check(self, what, untouched=False):
+        """The guard bands hold; with `untouched` the payload is still the fill too (a refused call wrote nothing)."""
+        if self.guard is not None:
+            self.guard.check(payload_untouched=untouched, what=what)
+        else:
+            assert (self.buf.a[self.n:] == OUT_FILL).all(), f"bytes behind {what} changed"
+            assert not untouched or (self.buf.a[:self.n] == OUT_FILL).all(), f"payload of {what} changed"
+
+
 def _raw_count(g, slot, d_records, d_counts, n_states, flags):
     """pfac_records_count_states itself, for an n_states the wrapper would not pass."""
     if hasattr(g, "raw_count_states"):
@@ -1381,12 +1414,6 @@ def _upload(g, arr):
         buf[:arr.nbytes].copy_(torch.from_numpy(np.ascontiguousarray(arr).view(np.uint8).copy()))
     torch.cuda.synchronize(g.device)
     return buf
-
-
-def _download(g, buf, dtype, count):
-    if hasattr(g, "download"):
-        return g.download(buf, dtype, count)
-    return buf.cpu().numpy()[:count * np.dtype(dtype).itemsize].view(dtype).copy()
 
 
 def _same(got, want, what="value"):
@@ -1569,10 +1596,10 @@ class Executor:
         if op["own"]:
             return int(g.segment_records(nd, slot=slot, d_records=self.bufs[slot].rec))
         cap = self._cap(op, exp)
-        d_out, d_first = _alloc(g, cap * 8 + 16), _alloc(g, (nd + 1) * 8)
-        n = int(g.segment_records(nd, d_out=d_out, out_cap=cap, d_doc_first=d_first, slot=slot, d_records=self.bufs[slot].rec))
-        g.sync(slot)
-        return (n, _download(g, d_first, np.uint64, nd + 1)) + self.recs(exp.tab, _download(g, d_out, REC, n))
+        d_out, d_first = _OutBuf(g, cap * 8), _OutBuf(g, (nd + 1) * 8)
+        n = int(self._guarded(slot, {"d_out": d_out, "d_doc_first": d_first}, "segment_records", lambda: g.segment_records(
+            nd, d_out=d_out.ptr, out_cap=cap, d_doc_first=d_first.ptr, slot=slot, d_records=self.bufs[slot].rec)))
+        return (n, d_first.read(np.uint64, nd + 1)) + self.recs(exp.tab, d_out.read(REC, n))
 
     def do_seg_fetch(self, op, exp, before):
         seg = self.m.slots[op["slot"]].seg
@@ -1581,32 +1608,63 @@ class Executor:
         return (first,) + self.recs(exp.tab, rec)
 
     # -- selection ----------------------------------------------------------
+    def _guarded(self, slot, outs, what, call):
+        """One pass call into the caller's outputs `outs` ({name: _OutBuf}, each exactly as long as the ABI asks for): the
+        guard bands hold after it, and after a refused call every payload is byte for byte what it was."""
+        try:
+            got = call()
+        except PfacError:
+            self.g.sync(slot)
+            for name, b in outs.items():
+                b.check(f"the caller's {name} after a refused {what}", untouched=True)
+            raise
+        self.g.sync(slot)
+        for name, b in outs.items():
+            b.check(f"the caller's {name} of {what}")
+        return got
+
+    def _check_kept(self, slot, when):
+        """The outputs of the slot's last selection that later operations still refer to: their guard bands hold."""
+        b = self.bufs[slot]
+        for name, buf in (("d_out", b.sel), ("d_doc_first", b.first), ("d_out", b.last_sel)):
+            if buf is not None:
+                buf.check(f"the caller's {name} of the last selection, {when}")
+
+    def _drop_selection(self, slot):
+        self._check_kept(slot, "when it is replaced")
+        self.bufs[slot].sel = self.bufs[slot].first = None
+
+    def finish(self):
+        for slot in range(N_SLOTS):
+            self._check_kept(slot, "at the end of the session")
+
     def do_select(self, op, exp, before):
         g, slot = self.g, op["slot"]
-        self.bufs[slot].sel = self.bufs[slot].first = None
+        self._drop_selection(slot)
         if op["own"]:
             n, ex = g.select_leftmost_longest(op["entry"], slot=slot, d_records=self.bufs[slot].rec)
             return int(n), int(ex)
         cap = self._cap(op, exp)
-        d_out = _alloc(g, cap * 8 + 16)
-        n, ex = g.select_leftmost_longest(op["entry"], d_out=d_out, out_cap=cap, slot=slot, d_records=self.bufs[slot].rec)
-        g.sync(slot)
+        d_out = _OutBuf(g, cap * 8)
+        n, ex = self._guarded(slot, {"d_out": d_out}, "select_leftmost_longest", lambda: g.select_leftmost_longest(
+            op["entry"], d_out=d_out.ptr, out_cap=cap, slot=slot, d_records=self.bufs[slot].rec))
         self.bufs[slot].sel = self.bufs[slot].last_sel = d_out
-        return (int(n), int(ex)) + self.recs(exp.tab, _download(g, d_out, REC, int(n)))
+        return (int(n), int(ex)) + self.recs(exp.tab, d_out.read(REC, int(n)))
 
     def do_select_docs(self, op, exp, before):
         g, slot = self.g, op["slot"]
         nd = self._n_docs(slot)
-        self.bufs[slot].sel = self.bufs[slot].first = None
+        self._drop_selection(slot)
         if op["own"]:
             return int(g.select_leftmost_longest_documents(nd, slot=slot, d_records=self.bufs[slot].rec))
         cap = self._cap(op, exp)
-        d_out, d_first = _alloc(g, cap * 8 + 16), _alloc(g, (nd + 1) * 8)
-        n = int(g.select_leftmost_longest_documents(nd, d_out=d_out, out_cap=cap, d_doc_first=d_first, slot=slot, d_records=self.bufs[slot].rec))
-        g.sync(slot)
+        d_out, d_first = _OutBuf(g, cap * 8), _OutBuf(g, (nd + 1) * 8)
+        n = int(self._guarded(slot, {"d_out": d_out, "d_doc_first": d_first}, "select_leftmost_longest_documents",
+                              lambda: g.select_leftmost_longest_documents(nd, d_out=d_out.ptr, out_cap=cap, d_doc_first=d_first.ptr, slot=slot,
+                                                                          d_records=self.bufs[slot].rec)))
         self.bufs[slot].sel, self.bufs[slot].first = d_out, d_first
         self.bufs[slot].last_sel = d_out
-        return (n, _download(g, d_first, np.uint64, nd + 1)) + self.recs(exp.tab, _download(g, d_out, REC, n))
+        return (n, d_first.read(np.uint64, nd + 1)) + self.recs(exp.tab, d_out.read(REC, n))
 
     def _sel_n(self, slot):
         sel = self.m.slots[slot].sel
@@ -1628,22 +1686,26 @@ class Executor:
     def do_replace(self, op, exp, before, docs=False):
         g, slot = self.g, op["slot"]
         b, sel = self.bufs[slot], before["sel"]
-        kw = dict(d_input=b.inp, slot=slot, d_sel=b.sel)
+        kw = dict(d_input=b.inp, slot=slot, d_sel=b.sel.ptr if b.sel is not None else None)
         if docs:
-            kw["d_doc_first"] = b.first
+            kw["d_doc_first"] = b.first.ptr if b.first is not None else None
         call = g.replace_selection_documents if docs else g.replace_selection
         if op["own"]:
             return int(call(**kw))
         cap = self._cap(op, exp)
-        d_out = _alloc(g, cap + 64)
+        outs = {"d_out": _OutBuf(g, cap)}
         nd = int(self.x.offsets(*sel["key"][:4]).size - 1) if docs and sel is not None and sel["kind"] == "docs" else 1
         if docs:
-            kw["d_out_offsets"] = _alloc(g, (nd + 1) * 8)
-        n = int(call(d_out=d_out, out_cap=cap, **kw))
-        g.sync(slot)
+            outs["d_out_offsets"] = _OutBuf(g, (nd + 1) * 8)
+            kw["d_out_offsets"] = outs["d_out_offsets"].ptr
+        try:
+            n = int(self._guarded(slot, outs, "replace_selection_documents" if docs else "replace_selection",
+                                  lambda: call(d_out=outs["d_out"].ptr, out_cap=cap, **kw)))
+        finally:
+            self._check_kept(slot, "after a replace that read it")
         self.stats["compared"] += n
-        out = (n, _download(g, d_out, np.uint8, n))
-        return out + (_download(g, kw["d_out_offsets"], np.uint64, nd + 1),) if docs else out
+        out = (n, outs["d_out"].read(np.uint8, n))
+        return out + (outs["d_out_offsets"].read(np.uint64, nd + 1),) if docs else out
 
     def do_replace_docs(self, op, exp, before):
         return self.do_replace(op, exp, before, docs=True)
@@ -1739,7 +1801,8 @@ class Executor:
                 junk.junk = True
             d_sel = junk if op["sel"] == "junk" else Odd(junk) if hasattr(g, "alloc") else int(junk.data_ptr()) + 4
         else:
-            d_sel = None if op["sel"] == "own" else b.sel if b.sel is not None else b.last_sel      # (after a failed select: the one before)
+            kept = b.sel if b.sel is not None else b.last_sel  # (after a failed select: the one before)
+            d_sel = None if op["sel"] == "own" or kept is None else kept.ptr
         return self._counted(op, lambda d: g.count_selection_states(slot, d_sel=d_sel, d_counts=d, accumulate=op["acc"]))
 
     def do_cnt_fetch(self, op, exp, before):
@@ -1773,4 +1836,8 @@ def run(g, ops, model=None, seed=None):
             e2 = AssertionError(f"session seed {seed}, operation {k} {fmt(op)}: {e}\n  the operations up to it (cut the plan with shrink({seed}, k)):\n{hist}")
             e2.op_index = k
             raise e2 from e
+    try:
+        ex.finish()                                             # the outputs the slots still refer to: their guard bands
+    except AssertionError as e:
+        raise AssertionError(f"session seed {seed}, behind the last operation: {e}") from e
     return ex.stats
