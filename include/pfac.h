@@ -390,6 +390,38 @@ int pfac_table_set_final_lengths(pfac_ctx *ctx, const int32_t *len, size_t n);
 /* Document boundaries for a slot: n_docs + 1 offsets, copied into a slot-owned device buffer on the slot's stream
  * (the host array may be reused when the call returns). */
 int pfac_slot_doc_offsets(pfac_ctx *ctx, int slot, const uint64_t *host_offsets, uint64_t n_docs);
+/* Document boundaries from a delimiter byte, made ON THE DEVICE from bytes that are already there (a log or a JSONL
+ * stream cut at '\n'): no host pass over the input, no upload of 8 bytes per line.  A document ends AFTER every delimiter
+ * byte:
+ *   E        = { i + 1 : 0 <= i < n_bytes, in[i] == delimiter }, ascending
+ *   offsets  = 0, then E, then n_bytes once more if n_bytes > 0 and in[n_bytes - 1] != delimiter
+ *   *n_docs  = number of offsets - 1;  n_bytes == 0: the single offset 0, *n_docs == 0
+ *   *tail_start = the start of the unterminated last document, or n_bytes if there is none: a chunked reader carries
+ *              in[tail_start : n_bytes] over to the next chunk.
+ * A run of delimiters yields documents that hold only their delimiter.  A document keeps its trailing delimiter, so a
+ * pattern that ends in '\n' (escaped pattern files) still matches inside its line.  The offsets satisfy the rules of
+ * pfac_records_segment by construction (off[0] == 0, non-decreasing, off[n_docs] == n_bytes).
+ *   d_input    NULL = the slot's input buffer (PFAC_E_ARG if n_bytes exceeds it); else a device pointer, 16-B aligned
+ *   n_bytes    <= 2^32
+ *   delimiter  0..255, else PFAC_E_ARG
+ * No byte at or past n_bytes influences the result, whatever the buffer holds there: whole 16-byte chunks inside
+ * [0, n_bytes) are loaded as such, the last partial one byte by byte.
+ * Effect: exactly that of a successful pfac_slot_doc_offsets with the same offsets -- they live in the slot-owned buffer,
+ * every document pass takes them with d_doc_offsets = NULL and *n_docs, and a per-document selection made before is
+ * refused by pfac_replace_documents(d_doc_offsets = NULL).  The call needs no finished scan and reads no scan state; it
+ * runs on the slot's stream, behind the slot's H2D copies, before or after the scan of the same bytes.  It returns once
+ * *n_docs and *tail_start are known (one 16-byte copy back, which also sizes the buffer); the offsets are then written
+ * asynchronously on the slot's stream.  PFAC_E_ARG also for a misaligned d_input, n_bytes > 2^32, and a result of 2^32
+ * documents (every one of 2^32 bytes a delimiter).  Every error leaves the slot's offsets as they were.
+ * Kernels: delimiters per 4 KiB tile (one wave per tile at a time, four dwordx4 loads per lane, an exact SWAR byte
+ * compare), sums per group of 64 tiles, the group prefix, then the same loads again and one store of i + 1 per delimiter
+ * at 1 + its rank; a tile without a delimiter is not read a second time. */
+int pfac_slot_doc_offsets_split(pfac_ctx *ctx, int slot, const void *d_input, uint64_t n_bytes, int delimiter,
+                                uint64_t *n_docs, uint64_t *tail_start);
+/* D2H of offsets [first, first + n) of the slot's document offsets, whichever call set them.  Asynchronous on the slot's
+ * stream; pfac_slot_sync completes it.  PFAC_E_STATE if the slot holds none, PFAC_E_ARG when first + n exceeds
+ * n_docs + 1. */
+int pfac_slot_doc_offsets_d2h(pfac_ctx *ctx, int slot, uint64_t *host_offsets, uint64_t first, uint64_t n);
 /* The slot's last finished scan, cut into documents [off[d], off[d+1]):
  *   d_records      the scan's record heap, NULL = the slot's
  *   d_doc_offsets  device uint64[n_docs + 1], NULL = the slot's (pfac_slot_doc_offsets, same n_docs).  Required:
@@ -420,6 +452,30 @@ int pfac_records_segment(pfac_ctx *ctx, int slot, const void *d_records, const u
  * returns PFAC_E_STATE, as it does when the pass wrote into the caller's buffers.  The two selections share one
  * slot-owned buffer and count as one pass here; so do the two replaces. */
 int pfac_segment_d2h(pfac_ctx *ctx, int slot, pfac_record *host_records, uint64_t *host_doc_first);
+
+/* Which documents matched?  (grep -F -f patterns over lines; PFAC_DOCS_INVERT: grep -v.)  Document d is reported iff
+ *   (doc_first[d + 1] > doc_first[d]) != invert;
+ * the ids are written ascending, *n_matching of them.  doc_first[d + 1] - doc_first[d] is document d's match count, so
+ * grep -c needs no call of its own: it is the difference of two fetched entries.
+ *   d_doc_first  NULL = the slot-owned doc_first of the slot's last pfac_records_segment (PFAC_E_STATE if there is none
+ *                or it went to the caller's buffer, PFAC_E_ARG if n_docs differs from that call's); else any device
+ *                array of n_docs + 1 entries, 8-B aligned -- the caller's d_doc_first of the segment pass or of
+ *                pfac_records_leftmost_longest_documents: a document has a pick iff it has a kept record, so either
+ *                gives the same ids
+ *   d_ids_out    NULL = a slot-owned buffer grown to fit (fetched with pfac_documents_matching_d2h; the lifetime rule of
+ *                pfac_segment_d2h); else 8-B aligned, out_cap entries.  No entry at or past *n_matching is written.
+ *   n_docs       < 2^32; 0 gives 0 ids
+ * It reads nothing but doc_first.  Returns once *n_matching is known; the writes are asynchronous on the slot's stream.
+ * PFAC_E_OVERFLOW (with *n_matching exact, nothing written) when out_cap is too small for a caller's d_ids_out;
+ * PFAC_E_ARG for flags outside 0..1 or misaligned buffers.
+ * Kernels: an ordered stream compaction -- one wave per 64 blocks of 64 documents, ballot and popcount per block, the
+ * group prefix, then the write at group prefix + blocks before + ballot rank. */
+#define PFAC_DOCS_INVERT 1u   /* the documents WITHOUT a kept record (grep -v) */
+int pfac_documents_matching(pfac_ctx *ctx, int slot, const uint64_t *d_doc_first, uint64_t n_docs, uint32_t flags,
+                            uint64_t *d_ids_out, uint64_t out_cap, uint64_t *n_matching);
+/* D2H of the slot-owned ids of the last pfac_documents_matching (*n_matching entries).  Asynchronous on the slot's
+ * stream; pfac_slot_sync completes it. */
+int pfac_documents_matching_d2h(pfac_ctx *ctx, int slot, uint64_t *host_ids);
 
 /* Whole-word filter: drops, IN PLACE, the records of the slot's last finished scan that split a word, so that every
  * consumer of the scan (the fetches, the text emitter, the checksum, the segment pass, both selections and both

@@ -31,6 +31,7 @@ PFAC_E_INTERNAL = -9
 PFAC_WORD_LEFT = 1      # pfac_records_filter_words: the match must not begin inside a word
 PFAC_WORD_RIGHT = 2     # ... must not end inside one
 PFAC_COUNT_ACCUMULATE = 1   # pfac_records_count_states / pfac_selection_count_states: add onto the counts already there
+PFAC_DOCS_INVERT = 1        # pfac_documents_matching: the documents WITHOUT a kept record
 
 _STATUS_NAMES = {
     0: "PFAC_OK", -1: "PFAC_E_ARG", -2: "PFAC_E_IO", -3: "PFAC_E_PATTERN", -4: "PFAC_E_NOMEM",
@@ -94,6 +95,7 @@ HIP_SYMBOLS = (
     "pfac_records_leftmost_longest_documents", "pfac_leftmost_longest_documents_d2h", "pfac_replace_documents",
     "pfac_replace_documents_d2h", "pfac_records_filter_words",
     "pfac_records_count_states", "pfac_selection_count_states", "pfac_state_counts_d2h",
+    "pfac_slot_doc_offsets_split", "pfac_slot_doc_offsets_d2h", "pfac_documents_matching", "pfac_documents_matching_d2h",
 )
 
 _host = None
@@ -224,5 +226,9 @@ def hip_lib() -> C.CDLL:
         L.pfac_records_count_states.argtypes = [vp, i, vp, vp, u64, C.c_uint32, C.POINTER(u64)]
         L.pfac_selection_count_states.argtypes = [vp, i, vp, vp, u64, C.c_uint32, C.POINTER(u64)]
         L.pfac_state_counts_d2h.argtypes = [vp, i, vp]
+        L.pfac_slot_doc_offsets_split.argtypes = [vp, i, vp, u64, i, C.POINTER(u64), C.POINTER(u64)]
+        L.pfac_slot_doc_offsets_d2h.argtypes = [vp, i, vp, u64, u64]
+        L.pfac_documents_matching.argtypes = [vp, i, vp, u64, C.c_uint32, vp, u64, C.POINTER(u64)]
+        L.pfac_documents_matching_d2h.argtypes = [vp, i, vp]
         _hip = L
     return _hip

@@ -3407,6 +3407,152 @@ __global__ void pfac_fill_tiled_kernel(unsigned char *dst, unsigned long long n,
 }
 
 // ---------------------------------------------------------------------------
+// Document offsets from a delimiter (pfac_slot_doc_offsets_split): a document ends after every delimiter byte.  The
+// shape of the other passes, over INPUT bytes: delimiters per 4 KiB tile (one wave per tile at a time, four dwordx4 loads
+// per lane, the exact SWAR compare of root_mask<1>), sums per group of 64 tiles, pfac_scan_groups_kernel, then the same
+// loads again and one 8-byte store per delimiter at its rank.  A tile word = delimiters in the tile | (1 + tile-local
+// offset of its last delimiter, 0 if none) << 32: the maximum of those ends over the input is tail_start.
+
+// The lane's 16 bytes at offset b of in[0, n): one dwordx4 load where the chunk lies inside the input; the chunk that
+// holds byte n - 1 is read byte by byte, its bytes at or past n replaced by a value that is not the delimiter (pad_x4),
+// and a chunk at or past n is all padding -- no byte at or past n is read, whatever the buffer holds there.
+__device__ __forceinline__ u32x4 split_chunk(const unsigned char *in, unsigned long long b, unsigned long long n, unsigned pad_x4) {
+    u32x4 w = {pad_x4, pad_x4, pad_x4, pad_x4};
+    if (b + 16 <= n) {
+        w = *reinterpret_cast<const u32x4 *>(in + b);
+    } else if (b < n) {
+#pragma unroll
+        for (int j = 0; j < 16; j++)
+            if (b + j < n) w[j >> 2] = (w[j >> 2] & ~(0xFFu << (8 * (j & 3)))) | ((unsigned)in[b + j] << (8 * (j & 3)));
+    }
+    return w;
+}
+__device__ __forceinline__ unsigned long long wave_max64(unsigned long long x) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) { const unsigned long long y = __shfl_xor(x, d, WAVE); x = y > x ? y : x; }
+    return x;
+}
+
+__global__ void __launch_bounds__(256)
+pfac_split_count_kernel(const unsigned char *in, unsigned long long n, unsigned long long n_tiles, unsigned delim_x4,
+                        unsigned long long *tile) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    const unsigned long long n_waves = (unsigned long long)gridDim.x * (blockDim.x >> 6);
+    for (unsigned long long t = (unsigned long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); t < n_tiles; t += n_waves) {
+        const unsigned long long base = t * WTILE + (unsigned)lane * 16u;
+        u32x4 w[SUBS];
+#pragma unroll
+        for (int s = 0; s < SUBS; s++) w[s] = split_chunk(in, base + (unsigned)s * SUB, n, ~delim_x4);
+        unsigned cnt = 0, last = 0;
+#pragma unroll
+        for (int s = 0; s < SUBS; s++) {
+            const unsigned m = root_mask<1>(w[s], nullptr, delim_x4);
+            cnt += (unsigned)__popc(m);
+            if (m) last = (unsigned)s * SUB + (unsigned)lane * 16u + (32u - (unsigned)__clz(m));
+        }
+        const unsigned long long sum = wave_sum64(cnt), end = wave_max64(last);
+        if (lane == 0) tile[t] = sum | (end << 32);
+    }
+}
+// per group of 64 tiles: its delimiters, and the end (1 + offset in the input) of its last one (0 if none)
+__global__ void pfac_split_group_kernel(const unsigned long long *tile, unsigned long long n_tiles, unsigned long long *gsum,
+                                        unsigned long long *glast, unsigned n_groups) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    const unsigned g = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (g >= n_groups) return;
+    const unsigned long long t = (unsigned long long)g * XGROUP + lane;
+    const unsigned long long e = t < n_tiles ? tile[t] : 0ull;
+    const unsigned long long sum = wave_sum64(e & 0xFFFFFFFFull);
+    const unsigned long long end = wave_max64((e >> 32) ? t * WTILE + (e >> 32) : 0ull);
+    if (lane == 0) { gsum[g] = sum; glast[g] = end; }
+}
+// behind the group prefix: res[0] = delimiters in the input, res[1] = the end of the last one = tail_start
+__global__ void pfac_split_ends_kernel(const unsigned long long *gsum, const unsigned long long *glast, unsigned n_groups,
+                                       unsigned long long *res) {                         // ONE block of 1024 threads
+    __shared__ unsigned long long part[1024];
+    unsigned long long m = 0;
+    for (unsigned i = threadIdx.x; i < n_groups; i += 1024) { const unsigned long long v = glast[i]; m = v > m ? v : m; }
+    part[threadIdx.x] = m;
+    __syncthreads();
+    for (unsigned d = 512; d >= 1; d >>= 1) {
+        if (threadIdx.x < d) { const unsigned long long v = part[threadIdx.x + d]; if (v > part[threadIdx.x]) part[threadIdx.x] = v; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) { res[0] = gsum[n_groups]; res[1] = part[0]; }
+}
+// off[1 + rank] = i + 1 for every delimiter in[i]; one lane writes off[0] = 0 and, for an unterminated last document, the
+// closing off[close_at] = n (close_at 0: none).  A rank at or past `total` (the count pass's sum: the offsets buffer was
+// sized from it) is never stored, so an input rewritten between the two passes costs wrong offsets, not a stray write.
+__global__ void __launch_bounds__(256)
+pfac_split_write_kernel(const unsigned char *in, unsigned long long n, unsigned long long n_tiles, unsigned delim_x4,
+                        const unsigned long long *tile, const unsigned long long *gpre, unsigned long long total,
+                        unsigned long long close_at, unsigned long long *off) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    const unsigned long long wave0 = (unsigned long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const unsigned long long n_waves = (unsigned long long)gridDim.x * (blockDim.x >> 6);
+    if (wave0 == 0 && lane == 0) {
+        off[0] = 0;
+        if (close_at) off[close_at] = n;
+    }
+    for (unsigned long long t = wave0; t < n_tiles; t += n_waves) {
+        const unsigned long long g = t / XGROUP, tl = g * XGROUP + lane;
+        const int j = (int)(t % XGROUP);
+        const unsigned c = tl < n_tiles ? (unsigned)tile[tl] : 0u;
+        if (__shfl(c, j, WAVE) == 0) continue;                          // (wave-uniform: a tile without a delimiter is not read again)
+        unsigned long long rank = gpre[g] + wave_sum64(lane < j ? c : 0u);
+        const unsigned long long base = t * WTILE + (unsigned)lane * 16u;
+        u32x4 w[SUBS];
+#pragma unroll
+        for (int s = 0; s < SUBS; s++) w[s] = split_chunk(in, base + (unsigned)s * SUB, n, ~delim_x4);
+#pragma unroll
+        for (int s = 0; s < SUBS; s++) {
+            unsigned m = root_mask<1>(w[s], nullptr, delim_x4);
+            const unsigned k = (unsigned)__popc(m), incl = wave_incl_scan(k);
+            unsigned long long r = rank + (incl - k);
+            rank += bcast_last(incl);
+            const unsigned long long at = base + (unsigned)s * SUB + 1u;
+            while (m) {
+                const unsigned b = (unsigned)__ffs(m) - 1u;
+                m &= m - 1u;
+                if (r < total) off[1 + r] = at + b;
+                r++;
+            }
+        }
+    }
+}
+
+// The documents that hold (or lack) a match (pfac_documents_matching): an ordered stream compaction over the flags
+// (doc_first[d + 1] > doc_first[d]) != invert.  One wave per group of 64 blocks of 64 documents, a ballot and a popcount
+// per block; the count form leaves the group's sum, the write form starts at the group's prefix and stores document d at
+// prefix + flags before it.  Like the split's write, no index at or past `total` is stored.
+constexpr int DM_BLOCKS = 64;
+template <bool WRITE>
+__global__ void __launch_bounds__(256)
+pfac_docs_matching_kernel(const unsigned long long *doc_first, unsigned long long n_docs, unsigned invert, unsigned long long *gsum,
+                          unsigned n_groups, unsigned long long total, unsigned long long *ids) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    const unsigned g = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (g >= n_groups) return;
+    const unsigned long long d0 = (unsigned long long)g * (DM_BLOCKS * WAVE);
+    const unsigned long long below = (1ull << lane) - 1ull;
+    unsigned long long run = WRITE ? gsum[g] : 0ull;
+#pragma unroll 4
+    for (int b = 0; b < DM_BLOCKS; b++) {
+        const unsigned long long d = d0 + (unsigned long long)b * WAVE + lane;
+        const bool have = d < n_docs;
+        const unsigned long long lo = have ? doc_first[d] : 0ull, hi = have ? doc_first[d + 1] : 0ull;
+        const bool flag = have && ((hi > lo) != (invert != 0u));
+        const unsigned long long mask = __ballot(flag);
+        if (WRITE && flag) {
+            const unsigned long long r = run + (unsigned long long)__popcll(mask & below);
+            if (r < total) ids[r] = d;
+        }
+        run += (unsigned long long)__popcll(mask);
+    }
+    if (!WRITE && lane == 0) gsum[g] = run;
+}
+
+// ---------------------------------------------------------------------------
 // runtime
 
 thread_local std::string g_err;
@@ -3533,6 +3679,12 @@ struct Slot {
     DevBuf<unsigned long long> cnt;       // slot-owned state counts (d_counts NULL): cnt_states of them, ...
     uint64_t cnt_states = 0, cnt_table = 0;       // ... counted with this table (pfac_ctx::table_gen)
     bool cnt_done = false;
+    // pfac_slot_doc_offsets_split
+    DevBuf<unsigned long long> sp_tile;   // per input tile: delimiters | end of the last one << 32
+    // pfac_documents_matching
+    DevBuf<unsigned long long> dm_out;    // slot-owned ids (d_ids_out NULL): dm_n of them
+    uint64_t dm_n = 0;
+    bool dm_done = false, dm_own = false;
 };
 
 }  // namespace
@@ -4760,6 +4912,82 @@ int pfac_slot_doc_offsets(pfac_ctx *ctx, int slot, const uint64_t *host_offsets,
     return PFAC_OK;
 }
 
+int pfac_slot_doc_offsets_split(pfac_ctx *ctx, int slot, const void *d_input, uint64_t n_bytes, int delimiter,
+                                uint64_t *n_docs, uint64_t *tail_start) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    if (!n_docs || !tail_start) return fail(ctx, PFAC_E_ARG, "null argument");
+    *n_docs = *tail_start = 0;
+    Slot &s = ctx->slots[slot];
+    const std::string fn = "pfac_slot_doc_offsets_split";
+    if (delimiter < 0 || delimiter > 255) return fail(ctx, PFAC_E_ARG, fn + ": the delimiter must be a byte value, 0..255");
+    if (n_bytes > (1ull << 32)) return fail(ctx, PFAC_E_ARG, fn + ": n_bytes must be at most 2^32");
+    const unsigned char *in = d_input ? static_cast<const unsigned char *>(d_input) : s.input.p;
+    if ((uintptr_t)in & 15) return fail(ctx, PFAC_E_ARG, fn + ": d_input must be 16-byte aligned");
+    if (!d_input && n_bytes > s.input.cap) return fail(ctx, PFAC_E_ARG, fn + ": n_bytes exceeds the slot's input buffer");
+    USE_DEVICE(ctx);
+    const uint64_t n_tiles = (n_bytes + WTILE - 1) / WTILE;
+    const unsigned n_groups = (unsigned)((n_tiles + XGROUP - 1) / XGROUP);
+    uint64_t total = 0, tail = 0;                            // delimiters, and the end of the last one
+    const unsigned x4 = (unsigned)delimiter * 0x01010101u;
+    const unsigned tblocks = (unsigned)std::min<uint64_t>((n_tiles + 3) / 4, 2048);
+    if (n_groups) {
+        rc = ensure_gsum(ctx, s, 2 * n_groups + 2);          // group prefixes, the total, the groups' last ends, the two results
+        if (rc) return rc;
+        rc = s.sp_tile.ensure(ctx, s.stream, n_tiles, quarter_more(n_tiles));
+        if (rc) return rc;
+        unsigned long long *glast = s.gsum.p + n_groups + 1, *res = glast + n_groups;
+        hipLaunchKernelGGL(pfac_split_count_kernel, dim3(tblocks), dim3(256), 0, s.stream, in, (unsigned long long)n_bytes,
+                           (unsigned long long)n_tiles, x4, s.sp_tile.p);
+        hipLaunchKernelGGL(pfac_split_group_kernel, dim3((n_groups + 3) / 4), dim3(256), 0, s.stream, s.sp_tile.p,
+                           (unsigned long long)n_tiles, s.gsum.p, glast, n_groups);
+        hipLaunchKernelGGL(pfac_scan_groups_kernel, dim3(1), dim3(1024), 0, s.stream, s.gsum.p, n_groups);
+        hipLaunchKernelGGL(pfac_split_ends_kernel, dim3(1), dim3(1024), 0, s.stream, s.gsum.p, glast, n_groups, res);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(s.h_ctl + H_PASS, res, 16, hipMemcpyDeviceToHost, s.stream));
+        HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+        total = host_u64(s, H_PASS);
+        tail = host_u64(s, H_PASS1);
+    }
+    const uint64_t docs = total + (tail != n_bytes ? 1 : 0);
+    if (docs >= (1ull << 32)) return fail(ctx, PFAC_E_ARG, fn + ": 2^32 documents (every byte is a delimiter); n_docs must be below 2^32");
+    // the new offsets go into a buffer of their own where the old one is too small: a failure up to here, the allocation
+    // included, leaves the slot's offsets as they were
+    if (docs + 1 > s.doc_off.cap) {
+        DevBuf<unsigned long long> grown;
+        rc = ensure_docs(ctx, s, grown, docs);
+        if (rc) return rc;
+        HIP_TRY(ctx, hipStreamSynchronize(s.stream));        // (nothing queued still reads the old one)
+        s.doc_off = std::move(grown);
+    }
+    if (n_groups) {
+        hipLaunchKernelGGL(pfac_split_write_kernel, dim3(tblocks), dim3(256), 0, s.stream, in, (unsigned long long)n_bytes,
+                           (unsigned long long)n_tiles, x4, s.sp_tile.p, s.gsum.p, (unsigned long long)total,
+                           (unsigned long long)(tail != n_bytes ? total + 1 : 0), s.doc_off.p);
+        HIP_TRY(ctx, hipGetLastError());
+    } else {
+        HIP_TRY(ctx, hipMemsetAsync(s.doc_off.p, 0, 8, s.stream));   // no bytes: the single offset 0
+    }
+    s.doc_n = docs;
+    s.doc_set = true;
+    s.doc_gen++;
+    *n_docs = docs;
+    *tail_start = tail;
+    return PFAC_OK;
+}
+
+int pfac_slot_doc_offsets_d2h(pfac_ctx *ctx, int slot, uint64_t *host_offsets, uint64_t first, uint64_t n) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    Slot &s = ctx->slots[slot];
+    if (!s.doc_set) return fail(ctx, PFAC_E_STATE, "pfac_slot_doc_offsets_d2h: no document offsets for the slot");
+    if (first > s.doc_n + 1 || n > s.doc_n + 1 - first) return fail(ctx, PFAC_E_ARG, "pfac_slot_doc_offsets_d2h: [first, first + n) exceeds the n_docs + 1 offsets");
+    if (!host_offsets && n) return fail(ctx, PFAC_E_ARG, "null host buffer");
+    USE_DEVICE(ctx);
+    if (n) HIP_TRY(ctx, hipMemcpyAsync(host_offsets, s.doc_off.p + first, n * 8, hipMemcpyDeviceToHost, s.stream));
+    return PFAC_OK;
+}
+
 int pfac_records_segment(pfac_ctx *ctx, int slot, const void *d_records, const uint64_t *d_doc_offsets, uint64_t n_docs,
                          pfac_record *d_out, uint64_t out_cap, uint64_t *d_doc_first, uint64_t *n_kept) {
     int rc = check_slot(ctx, slot);
@@ -4837,6 +5065,69 @@ int pfac_segment_d2h(pfac_ctx *ctx, int slot, pfac_record *host_records, uint64_
         HIP_TRY(ctx, hipMemcpyAsync(host_records, s.seg_out.p, s.seg_kept * sizeof(pfac_record), hipMemcpyDeviceToHost, s.stream));
     if (host_doc_first)
         HIP_TRY(ctx, hipMemcpyAsync(host_doc_first, s.seg_first.p, (s.seg_docs + 1) * 8, hipMemcpyDeviceToHost, s.stream));
+    return PFAC_OK;
+}
+
+int pfac_documents_matching(pfac_ctx *ctx, int slot, const uint64_t *d_doc_first, uint64_t n_docs, uint32_t flags,
+                            uint64_t *d_ids_out, uint64_t out_cap, uint64_t *n_matching) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    if (!n_matching) return fail(ctx, PFAC_E_ARG, "null argument");
+    *n_matching = 0;
+    Slot &s = ctx->slots[slot];
+    s.dm_done = false;
+    const std::string fn = "pfac_documents_matching";
+    const unsigned long long *first = reinterpret_cast<const unsigned long long *>(d_doc_first);
+    if (!first) {
+        if (!s.seg_done || !s.seg_own_first)
+            return fail(ctx, PFAC_E_STATE, fn + ": the slot holds no doc_first of a pfac_records_segment (none yet, or it went to the caller's buffer)");
+        if (n_docs != s.seg_docs) return fail(ctx, PFAC_E_ARG, fn + ": n_docs differs from the slot's last pfac_records_segment");
+        first = s.seg_first.p;
+    }
+    if (flags > PFAC_DOCS_INVERT) return fail(ctx, PFAC_E_ARG, fn + ": flags must be 0 or PFAC_DOCS_INVERT");
+    if (n_docs >= (1ull << 32)) return fail(ctx, PFAC_E_ARG, fn + ": n_docs must be below 2^32");
+    if (((uintptr_t)first | (uintptr_t)d_ids_out) & 7) return fail(ctx, PFAC_E_ARG, fn + ": device buffers must be 8-byte aligned");
+    USE_DEVICE(ctx);
+    const unsigned n_groups = (unsigned)((n_docs + DM_BLOCKS * WAVE - 1) / (DM_BLOCKS * WAVE));
+    uint64_t total = 0;
+    if (n_groups) {
+        rc = ensure_gsum(ctx, s, n_groups);
+        if (rc) return rc;
+        hipLaunchKernelGGL(pfac_docs_matching_kernel<false>, dim3((n_groups + 3) / 4), dim3(256), 0, s.stream, first,
+                           (unsigned long long)n_docs, (unsigned)flags, s.gsum.p, n_groups, 0ull, (unsigned long long *)nullptr);
+        hipLaunchKernelGGL(pfac_scan_groups_kernel, dim3(1), dim3(1024), 0, s.stream, s.gsum.p, n_groups);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(s.h_ctl + H_PASS, s.gsum.p + n_groups, 8, hipMemcpyDeviceToHost, s.stream));
+        HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+        total = host_u64(s, H_PASS);
+    }
+    *n_matching = total;
+    const bool own = d_ids_out == nullptr;
+    if (!own && total > out_cap)
+        return fail(ctx, PFAC_E_OVERFLOW, fn + ": " + std::to_string(total) + " documents, out_cap is " + std::to_string(out_cap));
+    rc = own ? s.dm_out.ensure(ctx, s.stream, total, total + total / 8 + 4096) : PFAC_OK;
+    if (rc) return rc;
+    if (total) {
+        hipLaunchKernelGGL(pfac_docs_matching_kernel<true>, dim3((n_groups + 3) / 4), dim3(256), 0, s.stream, first,
+                           (unsigned long long)n_docs, (unsigned)flags, s.gsum.p, n_groups, (unsigned long long)total,
+                           own ? s.dm_out.p : reinterpret_cast<unsigned long long *>(d_ids_out));
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    s.dm_n = total;
+    s.dm_own = own;
+    s.dm_done = true;
+    return PFAC_OK;
+}
+
+int pfac_documents_matching_d2h(pfac_ctx *ctx, int slot, uint64_t *host_ids) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    Slot &s = ctx->slots[slot];
+    if (!s.dm_done) return fail(ctx, PFAC_E_STATE, "pfac_documents_matching_d2h without a finished pfac_documents_matching");
+    if (!s.dm_own) return fail(ctx, PFAC_E_STATE, "pfac_documents_matching_d2h: the last pfac_documents_matching wrote into the caller's buffer");
+    if (!host_ids && s.dm_n) return fail(ctx, PFAC_E_ARG, "null host buffer");
+    USE_DEVICE(ctx);
+    if (s.dm_n) HIP_TRY(ctx, hipMemcpyAsync(host_ids, s.dm_out.p, s.dm_n * 8, hipMemcpyDeviceToHost, s.stream));
     return PFAC_OK;
 }
 

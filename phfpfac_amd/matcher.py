@@ -13,7 +13,8 @@ from typing import Optional, Tuple
 
 import numpy as np
 
-from ._ffi import PFAC_COUNT_ACCUMULATE, PFAC_E_OVERFLOW, PFAC_WORD_LEFT, PFAC_WORD_RIGHT, CRecord, PfacError, hip_lib
+from ._ffi import (PFAC_COUNT_ACCUMULATE, PFAC_DOCS_INVERT, PFAC_E_OVERFLOW, PFAC_WORD_LEFT, PFAC_WORD_RIGHT, CRecord, PfacError,
+                   hip_lib)
 from .table import RECORD_DTYPE, PfacTable, redaction_table, replacement_table
 
 
@@ -40,6 +41,15 @@ _EDGES = {"both": PFAC_WORD_LEFT | PFAC_WORD_RIGHT, "left": PFAC_WORD_LEFT, "rig
 def _word_bytes(whole_words):
     """The ``word_bytes`` of ``filter_whole_words`` for a ``whole_words`` keyword: True = the default set."""
     return None if whole_words is True else whole_words
+
+
+def _delimiter_byte(delimiter) -> int:
+    """The delimiter of the ``*_lines`` calls and ``split_documents``: one byte (``b"\\n"``) or its value."""
+    if isinstance(delimiter, (bytes, bytearray)):
+        if len(delimiter) != 1:
+            raise ValueError("the delimiter is a single byte")
+        return delimiter[0]
+    return int(delimiter)
 
 
 def _ptr(x) -> int:
@@ -476,6 +486,104 @@ class GpuMatcher:
         _, n_docs = self._scan_docs(docs, slot, whole_words)
         kept = self.segment_records(n_docs, slot=slot)
         return self.segment_to_host(kept, n_docs, slot)
+
+    # -- lines: documents cut at a delimiter, on the device ------------------
+    def split_documents(self, n_bytes: int, delimiter=b"\n", d_input=None, slot: int = 0) -> Tuple[int, int]:
+        """Document offsets from a delimiter byte, made on the GPU from bytes that are already there
+        (``pfac_slot_doc_offsets_split``): a document ends after every delimiter, an unterminated rest is the last
+        document.  ``d_input`` None = the slot's input buffer.  The offsets become the slot's, as after
+        ``set_doc_offsets``.  Returns (n_docs, tail_start): ``tail_start`` is where the unterminated last document
+        starts (``n_bytes`` if there is none) -- what a chunked reader carries over."""
+        n, tail = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._L.pfac_slot_doc_offsets_split(self._ctx, slot, _ptr(d_input), int(n_bytes),
+                                                        _delimiter_byte(delimiter), C.byref(n), C.byref(tail)))
+        return n.value, tail.value
+
+    def doc_offsets_to_host(self, n_docs: int, slot: int = 0, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """Offsets [first, first + n) of the slot's document offsets (default: all ``n_docs + 1``), whichever call set
+        them."""
+        n = int(n_docs) + 1 - int(first) if n is None else int(n)
+        out = np.empty(max(n, 0), dtype=np.uint64)
+        self._check(self._L.pfac_slot_doc_offsets_d2h(self._ctx, slot, out.ctypes.data if out.size else None, int(first), n))
+        self.sync(slot)
+        return out
+
+    def matching_documents(self, n_docs: int, invert: bool = False, d_doc_first=None, d_out=None, out_cap: int = 0,
+                           slot: int = 0) -> int:
+        """The documents that hold a match (``invert``: that hold none), ascending, on the GPU
+        (``pfac_documents_matching``).  ``d_doc_first`` None = the slot-owned doc_first of the slot's last
+        ``segment_records``, else a device array of ``n_docs + 1`` entries (of the segment pass or of
+        ``select_leftmost_longest_documents``); ``d_out`` None = a slot-owned buffer (``matching_documents_to_host``).
+        Returns the number of documents.  A too small ``out_cap`` raises PfacError(PFAC_E_OVERFLOW) whose
+        ``n_matching`` attribute holds the exact count."""
+        n = C.c_uint64(0)
+        rc = self._L.pfac_documents_matching(self._ctx, slot, _ptr(d_doc_first), int(n_docs),
+                                             PFAC_DOCS_INVERT if invert else 0, _ptr(d_out), int(out_cap), C.byref(n))
+        if rc:
+            e = PfacError(rc, (self._L.pfac_last_error(self._ctx) or b"").decode())
+            e.n_matching = n.value
+            raise e
+        return n.value
+
+    def matching_documents_to_host(self, n: int, slot: int = 0) -> np.ndarray:
+        """The ids (uint64[n]) of the slot's last ``matching_documents`` into its slot-owned buffer."""
+        out = np.empty(int(n), dtype=np.uint64)
+        self._check(self._L.pfac_documents_matching_d2h(self._ctx, slot, out.ctypes.data if n else None))
+        self.sync(slot)
+        return out
+
+    def _scan_lines(self, data, delimiter, slot: int, whole_words=False) -> Tuple[np.ndarray, int]:
+        """``_scan_docs`` for one buffer whose documents end at ``delimiter``: upload, scan, offsets made on the device
+        (only they come back, for the caller), then the whole-word filter if asked for.  Returns (offsets
+        uint64[n_docs + 1], n_docs)."""
+        buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data.view(np.uint8).ravel()
+        n = int(buf.size)
+        self._ensure_final_lengths()
+        self.reserve(slot, max(n, 1), max(n // 8, 4096))
+        if n:
+            self.h2d(buf, slot)
+        self.scan_resident(n, n, slot=slot)
+        n_docs, _ = self.split_documents(n, delimiter, slot=slot)
+        if whole_words is not False and n_docs:
+            self.filter_whole_words(slot, _word_bytes(whole_words), n_docs=n_docs)
+        return self.doc_offsets_to_host(n_docs, slot), n_docs
+
+    def scan_lines(self, data, delimiter=b"\n", slot: int = 0, whole_words=False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """``scan_documents`` of one buffer cut into lines at ``delimiter`` on the device (a line keeps its
+        delimiter).  Returns (doc_first, records, offsets uint64[n_docs + 1])."""
+        offsets, n_docs = self._scan_lines(data, delimiter, slot, whole_words)
+        kept = self.segment_records(n_docs, slot=slot)
+        first, rec = self.segment_to_host(kept, n_docs, slot)
+        return first, rec, offsets
+
+    def select_lines(self, data, delimiter=b"\n", slot: int = 0, whole_words=False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """``select_documents`` of one buffer cut into lines at ``delimiter`` on the device.  Returns (doc_first,
+        records with positions relative to the line, offsets)."""
+        offsets, n_docs = self._scan_lines(data, delimiter, slot, whole_words)
+        n = self.select_leftmost_longest_documents(n_docs, slot=slot)
+        first, rec = self.doc_selection_to_host(n, n_docs, slot)
+        if n:
+            doc = np.repeat(np.arange(n_docs, dtype=np.int64), np.diff(first.astype(np.int64)))
+            rec["pos"] -= offsets[doc].astype(np.uint32)
+        return first, rec, offsets
+
+    def replace_lines(self, data, delimiter=b"\n", slot: int = 0, whole_words=False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """``replace_documents`` of one buffer cut into lines at ``delimiter`` on the device.  Returns (out_offsets,
+        out, offsets)."""
+        offsets, n_docs = self._scan_lines(data, delimiter, slot, whole_words)
+        self.select_leftmost_longest_documents(n_docs, slot=slot)
+        n = self.replace_selection_documents(slot=slot)
+        out_off = self.replacement_doc_offsets_to_host(n_docs, slot)
+        return out_off, self.replacement_to_host(n, slot), offsets
+
+    def matching_lines(self, data, delimiter=b"\n", invert: bool = False, slot: int = 0, whole_words=False) -> Tuple[np.ndarray, np.ndarray]:
+        """Which lines of ``data`` hold a match (``invert``: hold none) -- ``grep -F -f patterns``, ``-v``: scan, split,
+        document cut and compaction on the device; only the ids and the offsets come back.  Returns (ids uint64,
+        offsets uint64[n_docs + 1]): line k is ``data[offsets[ids[k]]:offsets[ids[k] + 1]]``."""
+        offsets, n_docs = self._scan_lines(data, delimiter, slot, whole_words)
+        self.segment_records(n_docs, slot=slot)
+        n = self.matching_documents(n_docs, invert=invert, slot=slot)
+        return self.matching_documents_to_host(n, slot), offsets
 
     # -- leftmost-longest non-overlapping matches ---------------------------
     def select_leftmost_longest(self, entry: int = 0, d_out=None, out_cap: int = 0, slot: int = 0,
