@@ -476,6 +476,68 @@ int pfac_documents_matching(pfac_ctx *ctx, int slot, const uint64_t *d_doc_first
 /* D2H of the slot-owned ids of the last pfac_documents_matching (*n_matching entries).  Asynchronous on the slot's
  * stream; pfac_slot_sync completes it. */
 int pfac_documents_matching_d2h(pfac_ctx *ctx, int slot, uint64_t *host_ids);
+/* pfac_documents_matching with context lines (grep -B before, -A after; -C n is both).  Document d is reported iff some
+ * document e with d - after <= e <= d + before has a kept record, both window ends clamped to [0, n_docs - 1]:
+ *   doc_first[min(d + before, n_docs - 1) + 1] > doc_first[d - min(d, after)]
+ * -- doc_first is a prefix array, so the question about a window costs the same two loads as the one about a document.
+ * Any before / after up to 2^64 - 1 is legal and clamps (d + before does not wrap).  The ids are ascending and each
+ * appears once: overlapping contexts merge, as in grep; grep's "--" separator lines are not produced.  With
+ * before == after == 0 the result is that of pfac_documents_matching(flags = 0).
+ *   flags   must be 0.  PFAC_DOCS_INVERT gives PFAC_E_ARG: context around the documents WITHOUT a record asks whether a
+ *           window holds a document with no record, which needs the number of matching documents in the window; a
+ *           prefix of record counts does not give it (one document with many records and many with one look alike).
+ * d_doc_first, d_ids_out, out_cap, *n_matching, PFAC_E_OVERFLOW (exact count, nothing written), the alignment and
+ * n_docs < 2^32 are exactly those of pfac_documents_matching.  The two calls are ONE pass: they share the slot-owned id
+ * buffer and pfac_documents_matching_d2h, and the next call of either discards the result, even when that call fails.
+ * Kernels: the compaction of pfac_documents_matching, instantiated with the window flag. */
+int pfac_documents_matching_context(pfac_ctx *ctx, int slot, const uint64_t *d_doc_first, uint64_t n_docs, uint64_t before,
+                                    uint64_t after, uint32_t flags, uint64_t *d_ids_out, uint64_t out_cap, uint64_t *n_matching);
+
+/* The selected documents' bytes, back to back in one device buffer (what grep prints; with the two calls above the line
+ * path ends on the device like every other consumer).  With off = the document offsets and len(k) = off[ids[k] + 1] -
+ * off[ids[k]]:
+ *   out_off[k]     = sum of len(j) over j < k;  out_off[n_ids] = *out_bytes
+ *   out[out_off[k] : out_off[k + 1]] = in[off[ids[k]] : off[ids[k] + 1]]
+ *   d_input        NULL = the slot's input buffer (PFAC_E_ARG if n_bytes exceeds it); else a device pointer, 16-B aligned
+ *   n_bytes        <= 2^32: the bytes readable.  No byte at or past n_bytes is read: whole 16-byte chunks inside
+ *                  [0, n_bytes) are loaded as such, also where they reach outside a selected document, the last partial
+ *                  one byte by byte (the rule of pfac_slot_doc_offsets_split)
+ *   d_doc_offsets  NULL = the slot's offsets, whichever call set them (PFAC_E_STATE if there are none or n_docs is not
+ *                  theirs, as in pfac_records_filter_words); else device uint64[n_docs + 1], 8-B aligned; n_docs < 2^32
+ *   d_ids          NULL = the slot-owned ids of the slot's last pfac_documents_matching or _context (PFAC_E_STATE if there
+ *                  are none or they went to the caller's buffer, PFAC_E_ARG if n_ids differs from that call's count);
+ *                  else device uint64[n_ids], 8-B aligned, n_ids < 2^32.  The ids may come in ANY order and may repeat:
+ *                  a caller may gather a permutation, or a document twice
+ *   d_out          NULL = a slot-owned buffer grown to fit (fetched with pfac_documents_gather_d2h); else 16-B aligned,
+ *                  out_cap bytes.  No byte at or past *out_bytes is written (only the last partial 16 B is stored in
+ *                  pieces), so a buffer of exactly *out_bytes bytes is enough
+ *   d_out_offsets  NULL = a slot-owned buffer (pfac_documents_gather_offsets_d2h); else 8-B aligned, n_ids + 1 entries
+ * Checked on the device, in the first pass, before anything is written: every ids[k] < n_docs, and off[ids[k]] <=
+ * off[ids[k] + 1] <= n_bytes -- for the SELECTED documents only (offsets that break the rule at a document nobody
+ * selected do not matter).  A violation gives PFAC_E_ARG.
+ * Returns once *out_bytes is known (one 16-byte copy back: the total and the error word); the offsets and the bytes are
+ * then written asynchronously on the slot's stream (pfac_slot_sync completes them).  PFAC_E_OVERFLOW (with *out_bytes
+ * exact) when out_cap is too small for a caller's d_out; PFAC_E_ARG also for misaligned buffers, n_bytes > 2^32, n_docs or
+ * n_ids >= 2^32.  EVERY error leaves every caller's buffer of the call untouched, d_out_offsets included: the offsets
+ * are written behind the host's check of the total.  n_ids == 0: *out_bytes = 0, out_off[0] = 0 is written, nothing else.
+ * The call needs no finished scan and reads no scan state, like the split; it only reads the input, the offsets and the
+ * ids.  The slot-owned result follows the lifetime rule of pfac_segment_d2h: the next pfac_documents_gather discards it
+ * even when that call fails; the fetches then return PFAC_E_STATE, as they do when the output went to the caller's
+ * buffers.
+ * Kernels: lengths per block of 64 ids and per group of 1024 (two 8-byte gathers of the offsets per id, the checks in
+ * the same pass), the group prefix, out_off per id, then an output-driven write in the shape of the replace's: every
+ * wave owns windows of 1 KiB, finds the id that holds the window's first byte by a galloping search over the block
+ * offsets (never a walk from id 0; 1-byte and empty documents are skipped by the block), each lane assembles its 16
+ * bytes in registers from the unaligned source runs that cover it and stores one dwordx4. */
+int pfac_documents_gather(pfac_ctx *ctx, int slot, const void *d_input, uint64_t n_bytes, const uint64_t *d_doc_offsets,
+                          uint64_t n_docs, const uint64_t *d_ids, uint64_t n_ids, void *d_out, uint64_t out_cap,
+                          uint64_t *d_out_offsets, uint64_t *out_bytes);
+/* D2H of bytes [first, first + n) of the slot-owned output of the last pfac_documents_gather.  Asynchronous on the slot's
+ * stream; pfac_slot_sync completes it.  first + n > *out_bytes gives PFAC_E_ARG; n == 0 does nothing. */
+int pfac_documents_gather_d2h(pfac_ctx *ctx, int slot, void *host, uint64_t first, uint64_t n);
+/* D2H of the slot-owned output offsets of the last pfac_documents_gather (n_ids + 1 entries).  Asynchronous on the slot's
+ * stream; pfac_slot_sync completes it. */
+int pfac_documents_gather_offsets_d2h(pfac_ctx *ctx, int slot, uint64_t *host_out_offsets);
 
 /* Whole-word filter: drops, IN PLACE, the records of the slot's last finished scan that split a word, so that every
  * consumer of the scan (the fetches, the text emitter, the checksum, the segment pass, both selections and both

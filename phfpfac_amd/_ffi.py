@@ -96,6 +96,7 @@ HIP_SYMBOLS = (
     "pfac_replace_documents_d2h", "pfac_records_filter_words",
     "pfac_records_count_states", "pfac_selection_count_states", "pfac_state_counts_d2h",
     "pfac_slot_doc_offsets_split", "pfac_slot_doc_offsets_d2h", "pfac_documents_matching", "pfac_documents_matching_d2h",
+    "pfac_documents_matching_context", "pfac_documents_gather", "pfac_documents_gather_d2h", "pfac_documents_gather_offsets_d2h",
 )
 
 _host = None
@@ -230,5 +231,9 @@ def hip_lib() -> C.CDLL:
         L.pfac_slot_doc_offsets_d2h.argtypes = [vp, i, vp, u64, u64]
         L.pfac_documents_matching.argtypes = [vp, i, vp, u64, C.c_uint32, vp, u64, C.POINTER(u64)]
         L.pfac_documents_matching_d2h.argtypes = [vp, i, vp]
+        L.pfac_documents_matching_context.argtypes = [vp, i, vp, u64, u64, u64, C.c_uint32, vp, u64, C.POINTER(u64)]
+        L.pfac_documents_gather.argtypes = [vp, i, vp, u64, vp, u64, vp, u64, vp, u64, vp, C.POINTER(u64)]
+        L.pfac_documents_gather_d2h.argtypes = [vp, i, vp, u64, u64]
+        L.pfac_documents_gather_offsets_d2h.argtypes = [vp, i, vp]
         _hip = L
     return _hip

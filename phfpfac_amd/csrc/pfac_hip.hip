@@ -3525,11 +3525,14 @@ pfac_split_write_kernel(const unsigned char *in, unsigned long long n, unsigned 
 // (doc_first[d + 1] > doc_first[d]) != invert.  One wave per group of 64 blocks of 64 documents, a ballot and a popcount
 // per block; the count form leaves the group's sum, the write form starts at the group's prefix and stores document d at
 // prefix + flags before it.  Like the split's write, no index at or past `total` is stored.
+// The context form (pfac_documents_matching_context, grep -A / -B / -C) is the same compaction over another flag: doc_first
+// is a prefix array, so "some document of [d - after, d + before] has a record" is doc_first[hi + 1] > doc_first[lo] with
+// both ends clamped -- still two loads per document.  `before` and `after` arrive clamped to n_docs (d + before cannot wrap).
 constexpr int DM_BLOCKS = 64;
-template <bool WRITE>
-__global__ void __launch_bounds__(256)
-pfac_docs_matching_kernel(const unsigned long long *doc_first, unsigned long long n_docs, unsigned invert, unsigned long long *gsum,
-                          unsigned n_groups, unsigned long long total, unsigned long long *ids) {
+template <bool WRITE, bool CONTEXT>
+__device__ __forceinline__ void docs_matching_body(const unsigned long long *doc_first, unsigned long long n_docs, unsigned invert,
+                                                   unsigned long long before, unsigned long long after, unsigned long long *gsum,
+                                                   unsigned n_groups, unsigned long long total, unsigned long long *ids) {
     const int lane = threadIdx.x & (WAVE - 1);
     const unsigned g = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (g >= n_groups) return;
@@ -3540,8 +3543,15 @@ pfac_docs_matching_kernel(const unsigned long long *doc_first, unsigned long lon
     for (int b = 0; b < DM_BLOCKS; b++) {
         const unsigned long long d = d0 + (unsigned long long)b * WAVE + lane;
         const bool have = d < n_docs;
-        const unsigned long long lo = have ? doc_first[d] : 0ull, hi = have ? doc_first[d + 1] : 0ull;
-        const bool flag = have && ((hi > lo) != (invert != 0u));
+        bool flag;
+        if (CONTEXT) {
+            const unsigned long long first = d - (after < d ? after : d), last = d + before < n_docs ? d + before : n_docs - 1;
+            const unsigned long long lo = have ? doc_first[first] : 0ull, hi = have ? doc_first[last + 1] : 0ull;
+            flag = have && hi > lo;
+        } else {
+            const unsigned long long lo = have ? doc_first[d] : 0ull, hi = have ? doc_first[d + 1] : 0ull;
+            flag = have && ((hi > lo) != (invert != 0u));
+        }
         const unsigned long long mask = __ballot(flag);
         if (WRITE && flag) {
             const unsigned long long r = run + (unsigned long long)__popcll(mask & below);
@@ -3550,6 +3560,156 @@ pfac_docs_matching_kernel(const unsigned long long *doc_first, unsigned long lon
         run += (unsigned long long)__popcll(mask);
     }
     if (!WRITE && lane == 0) gsum[g] = run;
+}
+template <bool WRITE>
+__global__ void __launch_bounds__(256)
+pfac_docs_matching_kernel(const unsigned long long *doc_first, unsigned long long n_docs, unsigned invert, unsigned long long *gsum,
+                          unsigned n_groups, unsigned long long total, unsigned long long *ids) {
+    docs_matching_body<WRITE, false>(doc_first, n_docs, invert, 0ull, 0ull, gsum, n_groups, total, ids);
+}
+template <bool WRITE>
+__global__ void __launch_bounds__(256)
+pfac_docs_context_kernel(const unsigned long long *doc_first, unsigned long long n_docs, unsigned long long before,
+                         unsigned long long after, unsigned long long *gsum, unsigned n_groups, unsigned long long total,
+                         unsigned long long *ids) {
+    docs_matching_body<WRITE, true>(doc_first, n_docs, 0u, before, after, gsum, n_groups, total, ids);
+}
+
+// ---------------------------------------------------------------------------
+// The selected documents' bytes, back to back (pfac_documents_gather): segment k is in[off[ids[k]], off[ids[k] + 1]), at
+// output offset out_off[k] = the sum of the lengths before it.  The replace's shape with the picks taken out:
+//   pfac_ga_count_kernel     one workgroup per 1024 ids: two 8-byte gathers of the offsets per id, the checks (id <
+//                            n_docs, off[id] <= off[id + 1] <= n_bytes) into an error word, per block of 64 ids X[b] = the
+//                            lengths before it in its group, and the group's sum
+//   pfac_scan_groups_kernel  the group prefixes and the total = out_bytes, which the host checks before anything is written
+//   pfac_ga_offsets_kernel   one wave per block: out_off[k] for every id, out_off[n_ids] = out_bytes
+//   pfac_ga_write_kernel     output-driven, the loop of pfac_rp_write_kernel: every wave owns `wins` windows of 1 KiB, one
+//                            16-B chunk per lane.  rp_find (gallop, then narrow, 64 probes a round) gives the block that
+//                            holds the window's first byte -- never a walk from id 0, and blocks of empty documents are
+//                            skipped; the block's 65 output offsets and 64 source offsets go to LDS; each lane finds its
+//                            segments there by bisection, merges their unaligned source runs in registers (rp_merge) and
+//                            stores one dwordx4.  Only the last partial 16 B of the output is stored in pieces.
+// A block's prefix is O_{64b} = X[b] + gpre[b / RP_GROUP] (rp_block_out), as in the replace.
+
+__global__ void __launch_bounds__(RP_GROUP / 4 * WAVE)
+pfac_ga_count_kernel(const unsigned long long *ids, unsigned long long n, const unsigned long long *off, unsigned long long n_docs,
+                     unsigned long long n_bytes, unsigned long long *X, unsigned long long *gsum, unsigned long long *res) {
+    __shared__ unsigned long long bsum[RP_GROUP];
+    const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x >> 6;
+    const unsigned long long nb = (n + RP_BLOCK - 1) / RP_BLOCK;
+    bool bad = false;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const unsigned lb = (unsigned)w * 4 + (unsigned)i;
+        const unsigned long long k = ((unsigned long long)blockIdx.x * RP_GROUP + lb) * RP_BLOCK + (unsigned)lane;
+        unsigned long long len = 0;
+        if (k < n) {
+            const unsigned long long id = ids[k];
+            if (id < n_docs) {
+                const unsigned long long lo = off[id], hi = off[id + 1];
+                if (lo <= hi && hi <= n_bytes) len = hi - lo;
+                else bad = true;
+            } else {
+                bad = true;
+            }
+        }
+        const unsigned long long s = wave_sum64(len);
+        if (lane == 0) bsum[lb] = s;
+    }
+    if (__ballot(bad) && lane == 0) atomicOr(&res[0], 1ull);
+    __syncthreads();
+    if (threadIdx.x < RP_GROUP) {
+        const unsigned long long b = (unsigned long long)blockIdx.x * RP_GROUP + threadIdx.x;
+        unsigned long long pre = 0;
+        for (unsigned j = 0; j < threadIdx.x; j++) pre += bsum[j];
+        if (b < nb) X[b] = pre;
+        if (threadIdx.x == RP_GROUP - 1) gsum[blockIdx.x] = pre + bsum[RP_GROUP - 1];
+    }
+}
+
+// (behind the host's check of the count pass: every id is below n_docs and its offsets ascend)
+__global__ void __launch_bounds__(4 * WAVE)
+pfac_ga_offsets_kernel(const unsigned long long *ids, unsigned long long n, const unsigned long long *off,
+                       const unsigned long long *X, const unsigned long long *gpre, unsigned long long *out_off) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    const unsigned long long b = (unsigned long long)blockIdx.x * 4 + (threadIdx.x >> 6), k = b * RP_BLOCK + (unsigned)lane;
+    if (b * RP_BLOCK >= n) return;
+    unsigned long long len = 0;
+    if (k < n) {
+        const unsigned long long id = ids[k];
+        len = off[id + 1] - off[id];
+    }
+    const unsigned long long incl = rp_block_out(X, gpre, b) + wave_incl_scan64(len);
+    if (k < n) out_off[k] = incl - len;
+    if (k + 1 == n) out_off[n] = incl;
+}
+
+__global__ void __launch_bounds__(RP_WAVES * WAVE)
+pfac_ga_write_kernel(const unsigned char *in, unsigned long long n_bytes, const unsigned long long *ids, unsigned long long n,
+                     const unsigned long long *off, const unsigned long long *out_off, const unsigned long long *X,
+                     const unsigned long long *gpre, unsigned long long out_bytes, unsigned wins, unsigned char *out) {
+    __shared__ unsigned long long s_o[RP_WAVES][RP_BLOCK + 1];      // segment k's output offset (k = cnt: the block's end)
+    __shared__ unsigned long long s_src[RP_WAVES][RP_BLOCK];        // where it starts in the input
+    const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x >> 6;
+    const unsigned long long A = ((unsigned long long)blockIdx.x * RP_WAVES + (unsigned)w) * wins * RP_WIN;
+    if (A >= out_bytes) return;
+    const unsigned long long nb = (n + RP_BLOCK - 1) / RP_BLOCK;    // (n > 0: there are output bytes)
+    unsigned long long *so = s_o[w], *ssrc = s_src[w];
+    unsigned long long b = rp_find(X, gpre, nb, 0, A);
+    unsigned long long Ob = 0, hi = 0;
+    unsigned cnt = 0;
+    auto load_block = [&]() {
+        const unsigned long long k = b * RP_BLOCK + (unsigned)lane;
+        cnt = (unsigned)min((unsigned long long)RP_BLOCK, n - b * RP_BLOCK);
+        if (k <= n) so[lane] = out_off[k];                          // (lane <= cnt; out_off has n + 1 entries)
+        if (k < n) ssrc[lane] = off[ids[k]];
+        if (lane == 0 && cnt == (unsigned)RP_BLOCK) so[RP_BLOCK] = out_off[k + RP_BLOCK];
+        wave_lds_sync();
+        Ob = so[0];
+        hi = so[cnt];
+    };
+    load_block();
+    for (unsigned wi = 0; wi < wins; wi++) {
+        const unsigned long long W = A + (unsigned long long)wi * RP_WIN;
+        if (W >= out_bytes) break;
+        const unsigned long long o = W + 16ull * (unsigned)lane;
+        uint4 acc = make_uint4(0u, 0u, 0u, 0u);
+        for (;;) {
+            const unsigned long long e = min(o + 16, hi);
+            unsigned long long pos = max(o, Ob);
+            while (pos < e) {
+                unsigned l = 0, h = cnt;                            // the last segment k < cnt with so[k] <= pos: so[k + 1] > pos
+                while (h - l > 1) {
+                    const unsigned m = (l + h) >> 1;
+                    if (so[m] <= pos) l = m;
+                    else h = m;
+                }
+                const unsigned long long pe = min(so[l + 1], e);
+                rp_merge(acc, in, (long long)(ssrc[l] + o - so[l]), n_bytes, (unsigned)(pos - o), (unsigned)(pe - o));
+                pos = pe;
+            }
+            if (hi >= W + RP_WIN || hi >= out_bytes) break;
+            b = rp_find(X, gpre, nb, b + 1, hi);
+            wave_lds_sync();                                        // (every lane is done with the old block)
+            load_block();
+        }
+        if (o + 16 <= out_bytes) {
+            *reinterpret_cast<uint4 *>(out + o) = acc;
+        } else if (o < out_bytes) {                                 // the last partial 16 B of the whole output
+            const unsigned m = (unsigned)(out_bytes - o);
+            const unsigned v[4] = {acc.x, acc.y, acc.z, acc.w};
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                if ((unsigned)(4 * i + 4) <= m) {
+                    *reinterpret_cast<unsigned *>(out + o + 4 * i) = v[i];
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; j++)
+                        if ((unsigned)(4 * i + j) < m) out[o + 4 * i + j] = (unsigned char)(v[i] >> (8 * j));
+                }
+            }
+        }
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -3685,6 +3845,12 @@ struct Slot {
     DevBuf<unsigned long long> dm_out;    // slot-owned ids (d_ids_out NULL): dm_n of them
     uint64_t dm_n = 0;
     bool dm_done = false, dm_own = false;
+    // pfac_documents_gather
+    DevBuf<unsigned long long> ga_x;      // X per block of 64 ids
+    DevBuf<unsigned char> ga_out;         // slot-owned bytes (d_out NULL): ga_bytes of them
+    DevBuf<unsigned long long> ga_off;    // slot-owned output offsets (d_out_offsets NULL): ga_ids + 1 of them
+    uint64_t ga_bytes = 0, ga_ids = 0;
+    bool ga_done = false, ga_own_out = false, ga_own_off = false;
 };
 
 }  // namespace
@@ -5068,15 +5234,16 @@ int pfac_segment_d2h(pfac_ctx *ctx, int slot, pfac_record *host_records, uint64_
     return PFAC_OK;
 }
 
-int pfac_documents_matching(pfac_ctx *ctx, int slot, const uint64_t *d_doc_first, uint64_t n_docs, uint32_t flags,
-                            uint64_t *d_ids_out, uint64_t out_cap, uint64_t *n_matching) {
+// Both matching calls: the plain one (context false: flags 0 or PFAC_DOCS_INVERT) and the one with context lines
+// (flags 0; before / after as the caller gave them).  One pass: one slot-owned id buffer, one fetch, one lifetime.
+static int dm_run(pfac_ctx *ctx, int slot, const std::string &fn, const uint64_t *d_doc_first, uint64_t n_docs, bool context,
+                  uint64_t before, uint64_t after, uint32_t flags, uint64_t *d_ids_out, uint64_t out_cap, uint64_t *n_matching) {
     int rc = check_slot(ctx, slot);
     if (rc) return rc;
     if (!n_matching) return fail(ctx, PFAC_E_ARG, "null argument");
     *n_matching = 0;
     Slot &s = ctx->slots[slot];
     s.dm_done = false;
-    const std::string fn = "pfac_documents_matching";
     const unsigned long long *first = reinterpret_cast<const unsigned long long *>(d_doc_first);
     if (!first) {
         if (!s.seg_done || !s.seg_own_first)
@@ -5084,17 +5251,24 @@ int pfac_documents_matching(pfac_ctx *ctx, int slot, const uint64_t *d_doc_first
         if (n_docs != s.seg_docs) return fail(ctx, PFAC_E_ARG, fn + ": n_docs differs from the slot's last pfac_records_segment");
         first = s.seg_first.p;
     }
+    if (context && flags) return fail(ctx, PFAC_E_ARG, fn + ": flags must be 0 (context around non-matching documents is not defined by doc_first)");
     if (flags > PFAC_DOCS_INVERT) return fail(ctx, PFAC_E_ARG, fn + ": flags must be 0 or PFAC_DOCS_INVERT");
     if (n_docs >= (1ull << 32)) return fail(ctx, PFAC_E_ARG, fn + ": n_docs must be below 2^32");
     if (((uintptr_t)first | (uintptr_t)d_ids_out) & 7) return fail(ctx, PFAC_E_ARG, fn + ": device buffers must be 8-byte aligned");
     USE_DEVICE(ctx);
     const unsigned n_groups = (unsigned)((n_docs + DM_BLOCKS * WAVE - 1) / (DM_BLOCKS * WAVE));
+    const unsigned long long bef = std::min(before, n_docs), aft = std::min(after, n_docs);   // (a window wider than the input is the input)
+    const dim3 grid((n_groups + 3) / 4), block(256);
     uint64_t total = 0;
     if (n_groups) {
         rc = ensure_gsum(ctx, s, n_groups);
         if (rc) return rc;
-        hipLaunchKernelGGL(pfac_docs_matching_kernel<false>, dim3((n_groups + 3) / 4), dim3(256), 0, s.stream, first,
-                           (unsigned long long)n_docs, (unsigned)flags, s.gsum.p, n_groups, 0ull, (unsigned long long *)nullptr);
+        if (context)
+            hipLaunchKernelGGL(pfac_docs_context_kernel<false>, grid, block, 0, s.stream, first, (unsigned long long)n_docs, bef, aft,
+                               s.gsum.p, n_groups, 0ull, (unsigned long long *)nullptr);
+        else
+            hipLaunchKernelGGL(pfac_docs_matching_kernel<false>, grid, block, 0, s.stream, first,
+                               (unsigned long long)n_docs, (unsigned)flags, s.gsum.p, n_groups, 0ull, (unsigned long long *)nullptr);
         hipLaunchKernelGGL(pfac_scan_groups_kernel, dim3(1), dim3(1024), 0, s.stream, s.gsum.p, n_groups);
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipMemcpyAsync(s.h_ctl + H_PASS, s.gsum.p + n_groups, 8, hipMemcpyDeviceToHost, s.stream));
@@ -5108,15 +5282,30 @@ int pfac_documents_matching(pfac_ctx *ctx, int slot, const uint64_t *d_doc_first
     rc = own ? s.dm_out.ensure(ctx, s.stream, total, total + total / 8 + 4096) : PFAC_OK;
     if (rc) return rc;
     if (total) {
-        hipLaunchKernelGGL(pfac_docs_matching_kernel<true>, dim3((n_groups + 3) / 4), dim3(256), 0, s.stream, first,
-                           (unsigned long long)n_docs, (unsigned)flags, s.gsum.p, n_groups, (unsigned long long)total,
-                           own ? s.dm_out.p : reinterpret_cast<unsigned long long *>(d_ids_out));
+        unsigned long long *ids = own ? s.dm_out.p : reinterpret_cast<unsigned long long *>(d_ids_out);
+        if (context)
+            hipLaunchKernelGGL(pfac_docs_context_kernel<true>, grid, block, 0, s.stream, first, (unsigned long long)n_docs, bef, aft,
+                               s.gsum.p, n_groups, (unsigned long long)total, ids);
+        else
+            hipLaunchKernelGGL(pfac_docs_matching_kernel<true>, grid, block, 0, s.stream, first,
+                               (unsigned long long)n_docs, (unsigned)flags, s.gsum.p, n_groups, (unsigned long long)total, ids);
         HIP_TRY(ctx, hipGetLastError());
     }
     s.dm_n = total;
     s.dm_own = own;
     s.dm_done = true;
     return PFAC_OK;
+}
+
+int pfac_documents_matching(pfac_ctx *ctx, int slot, const uint64_t *d_doc_first, uint64_t n_docs, uint32_t flags,
+                            uint64_t *d_ids_out, uint64_t out_cap, uint64_t *n_matching) {
+    return dm_run(ctx, slot, "pfac_documents_matching", d_doc_first, n_docs, false, 0, 0, flags, d_ids_out, out_cap, n_matching);
+}
+
+int pfac_documents_matching_context(pfac_ctx *ctx, int slot, const uint64_t *d_doc_first, uint64_t n_docs, uint64_t before,
+                                    uint64_t after, uint32_t flags, uint64_t *d_ids_out, uint64_t out_cap, uint64_t *n_matching) {
+    return dm_run(ctx, slot, "pfac_documents_matching_context", d_doc_first, n_docs, true, before, after, flags, d_ids_out,
+                  out_cap, n_matching);
 }
 
 int pfac_documents_matching_d2h(pfac_ctx *ctx, int slot, uint64_t *host_ids) {
@@ -5128,6 +5317,121 @@ int pfac_documents_matching_d2h(pfac_ctx *ctx, int slot, uint64_t *host_ids) {
     if (!host_ids && s.dm_n) return fail(ctx, PFAC_E_ARG, "null host buffer");
     USE_DEVICE(ctx);
     if (s.dm_n) HIP_TRY(ctx, hipMemcpyAsync(host_ids, s.dm_out.p, s.dm_n * 8, hipMemcpyDeviceToHost, s.stream));
+    return PFAC_OK;
+}
+
+int pfac_documents_gather(pfac_ctx *ctx, int slot, const void *d_input, uint64_t n_bytes, const uint64_t *d_doc_offsets,
+                          uint64_t n_docs, const uint64_t *d_ids, uint64_t n_ids, void *d_out, uint64_t out_cap,
+                          uint64_t *d_out_offsets, uint64_t *out_bytes) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    if (!out_bytes) return fail(ctx, PFAC_E_ARG, "null argument");
+    *out_bytes = 0;
+    Slot &s = ctx->slots[slot];
+    s.ga_done = false;
+    const std::string fn = "pfac_documents_gather";
+    if (n_bytes > (1ull << 32)) return fail(ctx, PFAC_E_ARG, fn + ": n_bytes must be at most 2^32");
+    const unsigned char *in = d_input ? static_cast<const unsigned char *>(d_input) : s.input.p;
+    if (!d_input && n_bytes > s.input.cap) return fail(ctx, PFAC_E_ARG, fn + ": n_bytes exceeds the slot's input buffer");
+    const unsigned long long *off = reinterpret_cast<const unsigned long long *>(d_doc_offsets);
+    if (!off) {
+        if (!s.doc_set || n_docs != s.doc_n)
+            return fail(ctx, PFAC_E_STATE, fn + ": the slot has no document offsets for this n_docs (pfac_slot_doc_offsets)");
+        off = s.doc_off.p;
+    }
+    const unsigned long long *ids = reinterpret_cast<const unsigned long long *>(d_ids);
+    if (!ids) {
+        if (!s.dm_done || !s.dm_own)
+            return fail(ctx, PFAC_E_STATE, fn + ": the slot holds no ids of a pfac_documents_matching (none yet, or they went to the caller's buffer)");
+        if (n_ids != s.dm_n) return fail(ctx, PFAC_E_ARG, fn + ": n_ids differs from the slot's last pfac_documents_matching");
+        ids = s.dm_out.p;
+    }
+    if (n_docs >= (1ull << 32) || n_ids >= (1ull << 32)) return fail(ctx, PFAC_E_ARG, fn + ": n_docs and n_ids must be below 2^32");
+    if (((uintptr_t)in | (uintptr_t)d_out) & 15) return fail(ctx, PFAC_E_ARG, fn + ": d_input and d_out must be 16-byte aligned");
+    if (((uintptr_t)off | (uintptr_t)ids | (uintptr_t)d_out_offsets) & 7)
+        return fail(ctx, PFAC_E_ARG, fn + ": d_doc_offsets, d_ids and d_out_offsets must be 8-byte aligned");
+    USE_DEVICE(ctx);
+    const bool own_out = d_out == nullptr, own_off = d_out_offsets == nullptr;
+    const uint64_t nb = (n_ids + RP_BLOCK - 1) / RP_BLOCK;
+    const unsigned n_groups = (unsigned)((nb + RP_GROUP - 1) / RP_GROUP);
+    uint64_t total = 0;
+    if (n_ids) {
+        rc = s.ga_x.ensure(ctx, s.stream, nb, quarter_more(nb));
+        if (rc) return rc;
+        rc = ensure_gsum(ctx, s, n_groups + 1);             // group prefixes, the total, the error word
+        if (rc) return rc;
+        unsigned long long *res = s.gsum.p + n_groups + 1;
+        HIP_TRY(ctx, hipMemsetAsync(res, 0, 8, s.stream));
+        hipLaunchKernelGGL(pfac_ga_count_kernel, dim3(n_groups), dim3(RP_GROUP / 4 * WAVE), 0, s.stream, ids,
+                           (unsigned long long)n_ids, off, (unsigned long long)n_docs, (unsigned long long)n_bytes, s.ga_x.p,
+                           s.gsum.p, res);
+        hipLaunchKernelGGL(pfac_scan_groups_kernel, dim3(1), dim3(1024), 0, s.stream, s.gsum.p, n_groups);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(s.h_ctl + H_PASS, s.gsum.p + n_groups, 16, hipMemcpyDeviceToHost, s.stream));
+        HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+        if (host_u64(s, H_PASS1))
+            return fail(ctx, PFAC_E_ARG, fn + ": every id must be below n_docs, and off[id] <= off[id + 1] <= n_bytes for every selected document");
+        total = host_u64(s, H_PASS);
+    }
+    *out_bytes = total;
+    if (!own_out && total > out_cap)
+        return fail(ctx, PFAC_E_OVERFLOW, fn + ": " + std::to_string(total) + " output bytes, out_cap is " + std::to_string(out_cap));
+    rc = own_off ? ensure_docs(ctx, s, s.ga_off, n_ids) : PFAC_OK;      // (everything allocated before the first write)
+    if (rc) return rc;
+    rc = own_out ? s.ga_out.ensure(ctx, s.stream, total, align_up(total + total / 8, 4096)) : PFAC_OK;
+    if (rc) return rc;
+    unsigned long long *oo = own_off ? s.ga_off.p : reinterpret_cast<unsigned long long *>(d_out_offsets);
+    if (n_ids) {
+        hipLaunchKernelGGL(pfac_ga_offsets_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(4 * WAVE), 0, s.stream, ids,
+                           (unsigned long long)n_ids, off, (const unsigned long long *)s.ga_x.p,
+                           (const unsigned long long *)s.gsum.p, oo);
+        HIP_TRY(ctx, hipGetLastError());
+    } else {
+        HIP_TRY(ctx, hipMemsetAsync(oo, 0, 8, s.stream));    // no ids: the single offset 0
+    }
+    if (total) {
+        // one window of 1 KiB per wave while the output is small (every window's search runs in parallel), four above
+        uint64_t wins = total >= (64ull << 20) ? 4 : 1;
+        const uint64_t max_blocks = 1ull << 20;
+        const uint64_t per_block = (uint64_t)RP_WAVES * RP_WIN;
+        if ((total + per_block * wins - 1) / (per_block * wins) > max_blocks) wins = (total + per_block * max_blocks - 1) / (per_block * max_blocks);
+        const uint64_t blocks = (total + per_block * wins - 1) / (per_block * wins);
+        hipLaunchKernelGGL(pfac_ga_write_kernel, dim3((unsigned)blocks), dim3(RP_WAVES * WAVE), 0, s.stream, in,
+                           (unsigned long long)n_bytes, ids, (unsigned long long)n_ids, off, (const unsigned long long *)oo,
+                           (const unsigned long long *)s.ga_x.p, (const unsigned long long *)s.gsum.p, (unsigned long long)total,
+                           (unsigned)wins, own_out ? s.ga_out.p : static_cast<unsigned char *>(d_out));
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    s.ga_bytes = total;
+    s.ga_ids = n_ids;
+    s.ga_own_out = own_out;
+    s.ga_own_off = own_off;
+    s.ga_done = true;
+    return PFAC_OK;
+}
+
+int pfac_documents_gather_d2h(pfac_ctx *ctx, int slot, void *host, uint64_t first, uint64_t n) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    Slot &s = ctx->slots[slot];
+    if (!s.ga_done) return fail(ctx, PFAC_E_STATE, "pfac_documents_gather_d2h without a finished pfac_documents_gather");
+    if (!s.ga_own_out) return fail(ctx, PFAC_E_STATE, "pfac_documents_gather_d2h: the last gather wrote into the caller's buffer");
+    if (first > s.ga_bytes || n > s.ga_bytes - first) return fail(ctx, PFAC_E_ARG, "pfac_documents_gather_d2h: [first, first + n) exceeds the output");
+    if (!host && n) return fail(ctx, PFAC_E_ARG, "null host buffer");
+    USE_DEVICE(ctx);
+    if (n) HIP_TRY(ctx, hipMemcpyAsync(host, s.ga_out.p + first, n, hipMemcpyDeviceToHost, s.stream));
+    return PFAC_OK;
+}
+
+int pfac_documents_gather_offsets_d2h(pfac_ctx *ctx, int slot, uint64_t *host_out_offsets) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    Slot &s = ctx->slots[slot];
+    if (!s.ga_done) return fail(ctx, PFAC_E_STATE, "pfac_documents_gather_offsets_d2h without a finished pfac_documents_gather");
+    if (!s.ga_own_off) return fail(ctx, PFAC_E_STATE, "pfac_documents_gather_offsets_d2h: the last gather wrote its offsets into the caller's buffer");
+    if (!host_out_offsets) return fail(ctx, PFAC_E_ARG, "null host buffer");
+    USE_DEVICE(ctx);
+    HIP_TRY(ctx, hipMemcpyAsync(host_out_offsets, s.ga_off.p, (s.ga_ids + 1) * 8, hipMemcpyDeviceToHost, s.stream));
     return PFAC_OK;
 }
 

@@ -509,16 +509,26 @@ class GpuMatcher:
         return out
 
     def matching_documents(self, n_docs: int, invert: bool = False, d_doc_first=None, d_out=None, out_cap: int = 0,
-                           slot: int = 0) -> int:
+                           slot: int = 0, before: int = 0, after: int = 0) -> int:
         """The documents that hold a match (``invert``: that hold none), ascending, on the GPU
         (``pfac_documents_matching``).  ``d_doc_first`` None = the slot-owned doc_first of the slot's last
         ``segment_records``, else a device array of ``n_docs + 1`` entries (of the segment pass or of
         ``select_leftmost_longest_documents``); ``d_out`` None = a slot-owned buffer (``matching_documents_to_host``).
-        Returns the number of documents.  A too small ``out_cap`` raises PfacError(PFAC_E_OVERFLOW) whose
-        ``n_matching`` attribute holds the exact count."""
+        ``before`` / ``after`` (grep's ``-B`` / ``-A``; any value up to 2^64 - 1 clamps) add the documents around a
+        matching one (``pfac_documents_matching_context``), each id once; they do not combine with ``invert``
+        (ValueError).  Returns the number of documents.  A too small ``out_cap`` raises PfacError(PFAC_E_OVERFLOW)
+        whose ``n_matching`` attribute holds the exact count."""
         n = C.c_uint64(0)
-        rc = self._L.pfac_documents_matching(self._ctx, slot, _ptr(d_doc_first), int(n_docs),
-                                             PFAC_DOCS_INVERT if invert else 0, _ptr(d_out), int(out_cap), C.byref(n))
+        if before or after:
+            if invert:
+                raise ValueError("context lines (before / after) do not combine with invert")
+            if before < 0 or after < 0:
+                raise ValueError("before and after must not be negative")
+            rc = self._L.pfac_documents_matching_context(self._ctx, slot, _ptr(d_doc_first), int(n_docs), int(before),
+                                                         int(after), 0, _ptr(d_out), int(out_cap), C.byref(n))
+        else:
+            rc = self._L.pfac_documents_matching(self._ctx, slot, _ptr(d_doc_first), int(n_docs),
+                                                 PFAC_DOCS_INVERT if invert else 0, _ptr(d_out), int(out_cap), C.byref(n))
         if rc:
             e = PfacError(rc, (self._L.pfac_last_error(self._ctx) or b"").decode())
             e.n_matching = n.value
@@ -532,10 +542,42 @@ class GpuMatcher:
         self.sync(slot)
         return out
 
-    def _scan_lines(self, data, delimiter, slot: int, whole_words=False) -> Tuple[np.ndarray, int]:
+    def gather_documents(self, n_docs: int, n_ids: int, n_bytes: int, d_input=None, d_doc_offsets=None, d_ids=None,
+                         d_out=None, out_cap: int = 0, d_out_offsets=None, slot: int = 0) -> int:
+        """The bytes of documents ``ids[0 .. n_ids)`` of ``d_input[0 .. n_bytes)``, back to back, on the GPU
+        (``pfac_documents_gather``), with the output offset of each.  ``d_input`` None = the slot's input buffer,
+        ``d_doc_offsets`` None = the slot's offsets (``set_doc_offsets`` / ``split_documents``), ``d_ids`` None = the
+        slot-owned ids of the slot's last ``matching_documents`` (else any ids, in any order, repeats allowed);
+        ``d_out`` / ``d_out_offsets`` None = slot-owned buffers (``gathered_to_host`` /
+        ``gathered_offsets_to_host``).  Returns the output's length.  A too small ``out_cap`` raises
+        PfacError(PFAC_E_OVERFLOW) whose ``out_bytes`` attribute holds the exact length."""
+        n = C.c_uint64(0)
+        rc = self._L.pfac_documents_gather(self._ctx, slot, _ptr(d_input), int(n_bytes), _ptr(d_doc_offsets), int(n_docs),
+                                           _ptr(d_ids), int(n_ids), _ptr(d_out), int(out_cap), _ptr(d_out_offsets), C.byref(n))
+        if rc:
+            e = PfacError(rc, (self._L.pfac_last_error(self._ctx) or b"").decode())
+            e.out_bytes = n.value
+            raise e
+        return n.value
+
+    def gathered_to_host(self, n: int, slot: int = 0, first: int = 0) -> np.ndarray:
+        """Bytes [first, first + n) of the slot's last ``gather_documents`` into its slot-owned buffer."""
+        out = np.empty(int(n), dtype=np.uint8)
+        self._check(self._L.pfac_documents_gather_d2h(self._ctx, slot, out.ctypes.data if n else None, int(first), int(n)))
+        self.sync(slot)
+        return out
+
+    def gathered_offsets_to_host(self, n_ids: int, slot: int = 0) -> np.ndarray:
+        """The output offsets (uint64[n_ids + 1]) of the slot's last ``gather_documents`` into its slot-owned buffer."""
+        out = np.empty(int(n_ids) + 1, dtype=np.uint64)
+        self._check(self._L.pfac_documents_gather_offsets_d2h(self._ctx, slot, out.ctypes.data))
+        self.sync(slot)
+        return out
+
+    def _scan_lines(self, data, delimiter, slot: int, whole_words=False, fetch_offsets: bool = True) -> Tuple[Optional[np.ndarray], int]:
         """``_scan_docs`` for one buffer whose documents end at ``delimiter``: upload, scan, offsets made on the device
-        (only they come back, for the caller), then the whole-word filter if asked for.  Returns (offsets
-        uint64[n_docs + 1], n_docs)."""
+        (only they come back, for the caller -- not even they with ``fetch_offsets`` False), then the whole-word filter
+        if asked for.  Returns (offsets uint64[n_docs + 1] or None, n_docs)."""
         buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data.view(np.uint8).ravel()
         n = int(buf.size)
         self._ensure_final_lengths()
@@ -546,7 +588,7 @@ class GpuMatcher:
         n_docs, _ = self.split_documents(n, delimiter, slot=slot)
         if whole_words is not False and n_docs:
             self.filter_whole_words(slot, _word_bytes(whole_words), n_docs=n_docs)
-        return self.doc_offsets_to_host(n_docs, slot), n_docs
+        return (self.doc_offsets_to_host(n_docs, slot) if fetch_offsets else None), n_docs
 
     def scan_lines(self, data, delimiter=b"\n", slot: int = 0, whole_words=False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """``scan_documents`` of one buffer cut into lines at ``delimiter`` on the device (a line keeps its
@@ -584,6 +626,23 @@ class GpuMatcher:
         self.segment_records(n_docs, slot=slot)
         n = self.matching_documents(n_docs, invert=invert, slot=slot)
         return self.matching_documents_to_host(n, slot), offsets
+
+    def grep_lines(self, data, delimiter=b"\n", invert: bool = False, before: int = 0, after: int = 0, slot: int = 0,
+                   whole_words=False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The lines of ``data`` that hold a match, as bytes -- what ``grep -F -f patterns`` prints (``invert``: ``-v``;
+        ``before`` / ``after``: ``-B`` / ``-A``, without the ``--`` separators): scan, split, document cut, compaction
+        and gather on the device, from the slot's own input, offsets and ids.  Only the selected lines' bytes, their
+        offsets and their ids come back.  Returns (out uint8[out_bytes], out_offsets uint64[n + 1], ids uint64[n]):
+        selected line k is ``out[out_offsets[k]:out_offsets[k + 1]]``, line ``ids[k]`` of the input."""
+        buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data.view(np.uint8).ravel()
+        if invert and (before or after):
+            raise ValueError("context lines (before / after) do not combine with invert")
+        _, n_docs = self._scan_lines(buf, delimiter, slot, whole_words, fetch_offsets=False)
+        self.segment_records(n_docs, slot=slot)
+        n = self.matching_documents(n_docs, invert=invert, slot=slot, before=before, after=after)
+        out_bytes = self.gather_documents(n_docs, n, int(buf.size), slot=slot)
+        return (self.gathered_to_host(out_bytes, slot), self.gathered_offsets_to_host(n, slot),
+                self.matching_documents_to_host(n, slot))
 
     # -- leftmost-longest non-overlapping matches ---------------------------
     def select_leftmost_longest(self, entry: int = 0, d_out=None, out_cap: int = 0, slot: int = 0,
