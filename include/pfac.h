@@ -244,7 +244,13 @@ void *pfac_slot_stream(pfac_ctx *ctx, int slot);         /* the slot's hipStream
 int pfac_slot_set_stream(pfac_ctx *ctx, int slot, void *stream_handle);
 
 /* Async H2D of input bytes into the slot's input buffer at dst_offset
- * (cudaMemcpy H2D, master_kernel.cu:359, made asynchronous on the slot's stream). */
+ * (cudaMemcpy H2D, master_kernel.cu:359, made asynchronous).  Ordered like a copy on the slot's stream: it starts
+ * behind EVERYTHING the slot's stream has queued when the call is made, and what the slot queues afterwards starts behind
+ * it.  That covers every reader of the slot's input, not the last scan alone: pfac_replace_leftmost_longest,
+ * pfac_replace_documents, pfac_slot_doc_offsets_split and pfac_documents_gather return as soon as their size is known
+ * and read the input once more from a kernel queued behind that, so the next chunk may be uploaded into the same slot
+ * before their output has been fetched.  (The copies of all slots run on one copy stream of the context, in call order.)
+ * Bytes written by other means -- a kernel of the caller's on another stream -- are the caller's to order. */
 int pfac_slot_h2d(pfac_ctx *ctx, int slot, const void *host, uint64_t n_bytes, uint64_t dst_offset);
 /* Block until the slot's last pfac_slot_h2d has left the host buffer (which may then be refilled while the scan that
  * follows it on the stream is still running): what lets a reader pool run ahead of the copies. */

@@ -3796,6 +3796,7 @@ struct Slot {
     DevBuf<unsigned long long> sum;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipEvent_t ev_h2d = nullptr;          // behind the slot's last pfac_slot_h2d: the host buffer may be reused once it has fired
+    hipEvent_t ev_rd = nullptr;           // recorded on the slot's stream at a pfac_slot_h2d: behind every queued reader of the input
     bool h2d_issued = false;
     uint64_t last_cap = 0, last_tiles = 0, last_total = 0, last_used = 0;
     bool scanned = false, pending = false, last_dense = false;
@@ -4406,6 +4407,7 @@ int pfac_ctx_create(int device, int n_streams, pfac_ctx **out) {
         HIP_TRY(ctx, hipEventCreate(&s.ev0));
         HIP_TRY(ctx, hipEventCreate(&s.ev1));
         HIP_TRY(ctx, hipEventCreateWithFlags(&s.ev_h2d, hipEventDisableTiming));
+        HIP_TRY(ctx, hipEventCreateWithFlags(&s.ev_rd, hipEventDisableTiming));
     }
     *out = ctx;
     return PFAC_OK;
@@ -4420,6 +4422,7 @@ void pfac_ctx_destroy(pfac_ctx *ctx) {
         if (s.ev0) (void)hipEventDestroy(s.ev0);
         if (s.ev1) (void)hipEventDestroy(s.ev1);
         if (s.ev_h2d) (void)hipEventDestroy(s.ev_h2d);
+        if (s.ev_rd) (void)hipEventDestroy(s.ev_rd);
         if (s.own_stream) (void)hipStreamDestroy(s.own_stream);
     }
     if (ctx->copy_stream) { (void)hipStreamSynchronize(ctx->copy_stream); (void)hipStreamDestroy(ctx->copy_stream); }
@@ -4512,9 +4515,13 @@ int pfac_slot_h2d(pfac_ctx *ctx, int slot, const void *host, uint64_t n_bytes, u
     Slot &s = ctx->slots[slot];
     if (!host || dst_offset + n_bytes > s.input.cap) return fail(ctx, PFAC_E_ARG, "pfac_slot_h2d: range exceeds the reserved input buffer");
     USE_DEVICE(ctx);
-    // on the context's copy stream, behind whatever the slot's stream still does with the buffer (its last scan reads it);
-    // the slot's stream then waits for the copy: same ordering as a copy on the slot's stream, without the gaps
+    // on the context's copy stream, behind whatever the slot's stream still does with the buffer: its last scan reads it,
+    // and so do kernels queued behind the scan by calls that have already returned (the write kernels of the replace passes,
+    // of the split and of the gather). ev_rd, recorded here, is behind all of them; ev1 covers a scan whose stream was
+    // swapped since. The slot's stream then waits for the copy: same ordering as a copy on the slot's stream, without the gaps
     if (s.scanned) HIP_TRY(ctx, hipStreamWaitEvent(ctx->copy_stream, s.ev1, 0));
+    HIP_TRY(ctx, hipEventRecord(s.ev_rd, s.stream));
+    HIP_TRY(ctx, hipStreamWaitEvent(ctx->copy_stream, s.ev_rd, 0));
     HIP_TRY(ctx, hipMemcpyAsync(s.input.p + dst_offset, host, n_bytes, hipMemcpyHostToDevice, ctx->copy_stream));
     HIP_TRY(ctx, hipEventRecord(s.ev_h2d, ctx->copy_stream));
     HIP_TRY(ctx, hipStreamWaitEvent(s.stream, s.ev_h2d, 0));

@@ -38,6 +38,10 @@ class GuardedBuffer:
         self.tensor = torch.full((self.front + self.n_bytes + self.back,), self.fill, dtype=torch.uint8, device=device)
         self.ptr = int(self.tensor.data_ptr()) + self.front
         assert self.ptr % 16 == 0, "the allocator returned a tensor that is not 16-byte aligned"
+        if self.tensor.is_cuda:
+            # the fill runs on torch's stream, what is tested writes on a slot's non-blocking stream: without this the
+            # fill may land on top of a kernel launched right behind the constructor
+            torch.cuda.synchronize(self.tensor.device)
 
     def payload(self):
         """The payload as a tensor view (uint8[n_bytes])."""

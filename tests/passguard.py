@@ -16,7 +16,10 @@ Three parts:
                               replref, docref / docreplref -- never the device.  Sizes come from here alone (the packed
                               form's `used` is the one number the ABI itself takes from pfac_scan_format).
   Device                      one context per record width, and one method per pass that builds the guarded buffers of
-                              a case and drives exact_call (imports torch lazily; nothing here needs a GPU to import)."""
+                              a case and drives exact_call (imports torch lazily; nothing here needs a GPU to import).
+                              A GuardedBuffer is filled on torch's stream and the pass writes on the slot's non-blocking
+                              one: the buffer's constructor synchronises the device behind its fill, as `upload` does
+                              behind its copy, so no fill can land on top of a pass launched right behind it."""
 import atexit
 import os
 import tempfile

@@ -16,7 +16,10 @@ Three parts, none of which needs a GPU to import:
                        plan(seed, counts=True) a third with the per-pattern counts as well (pfac_records_count_states,
                        pfac_selection_count_states, pfac_state_counts_d2h: slot-owned counts that belong to a table
                        generation, are shared by two producers, can be added to and outlive everything else); the first
-                       two are pinned to what they were before.
+                       three are pinned to what they were before.  plan(seed, lines=True) is a fourth with the line
+                       path as well: the delimiter split, the matching documents with and without context lines and
+                       the gather of their bytes (split, doc_fetch, matching, context, ids_fetch, gather, ga_fetch,
+                       gaoff_fetch), whose values come from splitref and gatherref.
 
 The device under test hands out final STATES; they are mapped to pattern ids with the idmap of the table the scan ran
 with (a stand-in that already works in ids says so with ``states_are_ids``)."""
@@ -32,11 +35,13 @@ import wordref
 from classfuzz import ClassMatcher as _ClassMatcher
 from docref import oracle_per_doc, random_offsets
 from docreplref import per_doc
+from gatherref import context_ids, gather_ref
 from llref import greedy
 from orc import Oracle, match_checksum
 from passfuzz import GROUP, KNOB_NAMES, KNOBS, record_width
 from phfpfac_amd import PfacError, PfacTable
 from replref import rep_table, splice
+from splitref import matching_ids, split_offsets
 
 OK, E_ARG, E_STATE, E_OVERFLOW = 0, -1, -7, -8
 STATUS_NAMES = {OK: "OK", E_ARG: "PFAC_E_ARG", E_STATE: "PFAC_E_STATE", E_OVERFLOW: "PFAC_E_OVERFLOW", None: "UNDEFINED"}
@@ -45,7 +50,10 @@ N_SLOTS = 2
 SEEDS = list(range(24))                 # the suite's plans
 WORD_SEEDS = list(range(24))            # ... and the seeds of its plans with the whole-word filter: plan(seed, words=True)
 COUNT_SEEDS = list(range(24))           # ... and of its plans with the per-pattern counts as well: plan(seed, counts=True)
+LINE_SEEDS = list(range(24))            # ... and of its plans with the line path as well: plan(seed, lines=True)
 PLAN_OPS = 60
+LINE_PLAN_OPS = 160                     # (a line plan is longer: its histories need a scan, offsets, a segment and ids first)
+U64_MAX = 2**64 - 1
 IN_STEP, REC_STEP = 8 << 20, 4 << 20    # reserve_grow number k asks for k * IN_STEP bytes / k * REC_STEP records: above
                                         # anything a plan's scans reserve (inputs <= 2 000 003 bytes, heaps below 4 Mi records)
 REC = np.dtype([("pos", np.uint32), ("state", np.uint32)])
@@ -316,7 +324,28 @@ class Expectations:
         return self._memo(("replace", t, i, no, entry, rkey, f), make)
 
     # -- documents ----------------------------------------------------------
+    def delims(self, t, i):
+        """The delimiters a session splits input `i` of table `t` at: (its most frequent byte, its rarest byte that
+        occurs, a byte that does not occur) -- for the empty input, three newlines."""
+        def make():
+            h = np.bincount(self.input(t, i), minlength=256)
+            if not h.any():
+                return (10, 10, 10)
+            present = np.flatnonzero(h)
+            assert (h == 0).any(), "every byte occurs: no delimiter without a document end"
+            return int(np.argmax(h)), int(present[np.argmin(h[present])]), int(np.flatnonzero(h == 0)[0])
+        return self._memo(("delims", t, i), make)
+
+    def split(self, t, i, nb, delim):
+        """(offsets, n_docs, tail_start) of the first `nb` bytes of the input cut at `delim` (splitref.split_offsets)."""
+        return self._memo(("split", t, i, nb, delim), lambda: split_offsets(self.input(t, i)[:nb], delim))
+
     def offsets(self, t, i, no, dkey):
+        """The document offsets `dkey` of the first `no` bytes of input `i`: one of DOC_KEYS (seeded cuts), or
+        "split:<byte>" -- what the device-side split at that delimiter leaves in the slot."""
+        if dkey.startswith("split:"):
+            return self.split(t, i, no, int(dkey[6:]))[0]
+
         def make():
             rng = np.random.default_rng([sorted(TABLES).index(t), i, no, DOC_KEYS.index(dkey), 0x444F])
             off = random_offsets(rng, no, int(rng.integers(1, 60)), empties=int(rng.integers(0, 4)))
@@ -355,6 +384,49 @@ class Expectations:
             return first, pos.astype(np.int64) + off[doc].astype(np.int64), ids.astype(np.int64), out_off, out
         return self._memo(("docsel", t, i, no, dkey, f, rkey), make)
 
+
+    # -- lines: matching documents and their bytes ---------------------------
+    def doc_first(self, src, key):
+        """The doc_first a matching call reads: of the segment ("seg") or of the per-document selection ("docsel") `key`."""
+        return (self.seg if src == "seg" else self.docsel)(*key)[0]
+
+    def doc_ids(self, spec):
+        """The ids of a matching call.  spec = (src, key, "m", invert) or (src, key, "c", before, after):
+        splitref.matching_ids / gatherref.context_ids over doc_first(src, key)."""
+        def make():
+            first = self.doc_first(spec[0], spec[1])
+            return matching_ids(first, spec[3]) if spec[2] == "m" else context_ids(first, spec[3], spec[4])
+        return self._memo(("ids",) + spec, make)
+
+    def id_list(self, spec, form, n_docs):
+        """The ids a gather is given.  form "own": those of matching call `spec`; else a caller's list made from them
+        (from 0 .. min(n_docs, 40) - 1 without a matching call): "same", a permutation ("perm"), reversed ("rev"), every
+        id twice ("twice"), none ("empty"), or with one entry replaced by n_docs ("bad_id"); "all": every document."""
+        if form == "all":
+            return np.arange(n_docs, dtype=np.uint64)
+        base = self.doc_ids(spec) if spec is not None else np.arange(min(n_docs, 40), dtype=np.uint64)
+        if form in ("own", "same"):
+            return base
+        if form == "perm":
+            return base[np.random.default_rng([base.size, 0x504D]).permutation(base.size)]
+        if form == "rev":
+            return base[::-1].copy()
+        if form == "twice":
+            return np.repeat(base, 2)
+        if form == "empty":
+            return base[:0]
+        assert form == "bad_id"
+        bad = np.append(base, np.uint64(0))[:max(base.size, 1)].copy()
+        bad[bad.size // 2] = n_docs
+        return bad
+
+    def gather(self, t, i, nb, doc, spec, form):
+        """(out, out_off) of gatherref.gather_ref over the first `nb` bytes of input `i` of table `t`, the offsets `doc`
+        (an argument tuple of `offsets`) and id_list(spec, form)."""
+        def make():
+            off = self.offsets(*doc)
+            return gather_ref(self.input(t, i)[:nb], off, self.id_list(spec, form, int(off.size) - 1))
+        return self._memo(("gather", t, i, nb, doc, spec, form), make)
 
     # -- counts per pattern ---------------------------------------------------
     # A contribution to a count buffer ("part"): ("scan", t, i, no, f), ("sel", t, i, no, entry, f) or
@@ -456,6 +528,11 @@ class _Slot:
         self.shared = False
         self.cnt = None           # the slot-owned counts: dict(tab, gen, parts) -- their value is the sum of the parts' histograms
         self.cbuf = None          # the caller's count buffer of this slot: dict(tab, serial, base, parts); base: CNT_ENTRY is still in every entry
+        # the line path (all tuples: a copy of the model shares them)
+        self.up = None            # (tab, inp, n) of the bytes last uploaded into the slot's input buffer; None: unknown
+        self.segc = None          # the key of the last segment whose doc_first went to the caller's buffer (still the caller's)
+        self.dm = None            # (spec, own) of the slot's last matching / context call: Expectations.doc_ids(spec)
+        self.ga = None            # (args of Expectations.gather, own_out, own_off) of the slot's last gather
 
 
 PASSES = ("segment", "select", "select_docs", "replace", "replace_docs")
@@ -463,6 +540,13 @@ FETCH_OF = {"segment": "seg_fetch", "select": "sel_fetch", "select_docs": "docse
 
 
 class Model:
+    """What include/pfac.h promises for a history of calls (never what pfac_hip.hip does): `apply(op)` moves the state and
+    returns the Exp of the operation, `predict(op)` the same on a copy.  The state holds keys into the Expectations only.
+    For the line path it also tracks the BYTES of each slot's input buffer -- those of the last upload and their length
+    (`_Slot.up`).  A plan never asks a split or a gather of the slot's input for n_bytes beyond the last upload, or after
+    a reserve_grow that replaced the input buffer: the header promises nothing about those bytes, and the model answers
+    UNDEFINED (status None), which no plan may contain."""
+
     def __init__(self, exps=None):
         self.x = exps or expectations()
         self.tab = None
@@ -538,7 +622,13 @@ class Model:
             return (pos[first:], ids[first:]) if n is None else (pos[first:first + n], ids[first:first + n])
         return fn
 
+    def _uploaded(self, op, s):
+        """A scan of a host buffer reserves the slot's input and uploads the WHOLE buffer before it asks for a table."""
+        tab = self.tab or "abc2"
+        s.up = (tab, op["inp"], self.x.input_size(tab, op["inp"]))
+
     def _scan_bytes(self, op, s):
+        self._uploaded(op, s)
         s.has_in = s.has_rec = True                             # (scan_bytes reserves both before it scans)
         if self.tab is None:
             return Exp(E_STATE)
@@ -546,6 +636,7 @@ class Model:
         return Exp(OK, self._rec_fn(s.scan), tab=self.tab)
 
     def _scan_start(self, op, s):
+        self._uploaded(op, s)
         s.has_in = s.has_rec = True
         if self.tab is None:
             return Exp(E_STATE)
@@ -670,6 +761,8 @@ class Model:
         if d["doc"] != "none":
             if s.doc is None or d["doc"] == "wrong_n":
                 arg.add(E_STATE)                                # (offsets that are not this n_docs' are not looked at)
+            elif self.x.offsets(*s.doc).size == 1:
+                pass                                            # (a split of nothing left no document: n_docs 0 is "no documents")
             elif not offsets_ok(self.x.offsets(*s.doc), sc["no"]):
                 arg.add(E_ARG)
             elif s.doc[:3] != (sc["tab"], sc["inp"], sc["no"]):
@@ -700,6 +793,7 @@ class Model:
         s.seg = dict(key=key, own=op["own"], tab=s.scan["tab"])
         if op["own"]:
             return Exp(OK, lambda: n)
+        s.segc = key
         return Exp(OK, lambda: (n,) + self.x.seg(*key), tab=s.scan["tab"])
 
     def _seg_fetch(self, op, s):
@@ -894,6 +988,172 @@ class Model:
         tab, parts = s.cnt["tab"], list(s.cnt["parts"])
         return Exp(OK, lambda: self.x.sum_counts(tab, parts), tab=tab)
 
+    # -- lines: split, matching documents, gather -------------------------------
+    # The model of the line path knows the BYTES of the slot's input buffer: those of the last upload (`up`: every scan
+    # of a host buffer uploads the whole buffer), and their length.  A plan never asks a split or a gather of the slot's
+    # input for n_bytes beyond that upload, or after a reserve_grow that replaced the input buffer: the header promises
+    # nothing about those bytes, and the model answers UNDEFINED.  Among several broken rules the header promises no
+    # order: an illegal operation breaks exactly one (two faults with different statuses are UNDEFINED).
+    @staticmethod
+    def _one(faults):
+        return Exp(None) if len(faults) > 1 else Exp(next(iter(faults)))
+
+    def _op_split(self, op, s):
+        """pfac_slot_doc_offsets_split.  src: "slot" = d_input NULL, "caller" = a caller's copy of input (tab, inp), "odd" =
+        four bytes into it; nb: n_bytes, or "over" = more than the slot's input buffer holds; delim: 0..255, or 256 / -1.
+        Needs no table and no scan; on success the slot's offsets are the split's, as after set_doc.  Every error leaves
+        the slot's offsets as they were."""
+        faults = set()
+        if not 0 <= op["delim"] <= 255:
+            faults.add(E_ARG)
+        if op["src"] == "odd":
+            faults.add(E_ARG)
+        if op["nb"] == "over":
+            if op["src"] != "slot" or not s.has_in:
+                return Exp(None)
+            faults.add(E_ARG)
+        elif op["src"] == "slot":
+            if not s.has_in or s.up is None or s.up[:2] != (op["tab"], op["inp"]) or op["nb"] > s.up[2]:
+                return Exp(None)
+        elif op["nb"] > self.x.input_size(op["tab"], op["inp"]):
+            return Exp(None)
+        if faults:
+            return self._one(faults)
+        key = (op["tab"], op["inp"], op["nb"], op["delim"])
+        s.doc = key[:3] + (f"split:{op['delim']}",)
+        s.doc_gen += 1
+        return Exp(OK, lambda: self.x.split(*key)[1:])
+
+    def _doc_fetch(self, op, s):
+        if s.doc is None:
+            return Exp(E_STATE)
+        doc = s.doc
+        if op["first"] + op["n"] > self.x.offsets(*doc).size:
+            return Exp(E_ARG)
+        return Exp(OK, lambda: self.x.offsets(*doc)[op["first"]:op["first"] + op["n"]])
+
+    def _first_of(self, op, s):
+        """(src, key) of the doc_first a matching call is given, "none" where the slot holds none for NULL, or None where
+        there is no such caller's buffer to pass."""
+        if op["first"] == "own":
+            return ("seg", s.seg["key"]) if s.seg is not None and s.seg["own"] else "none"
+        if op["first"] == "seg":
+            return ("seg", s.segc) if s.segc is not None else None
+        sel = s.sel
+        return ("docsel", sel["key"]) if sel is not None and sel["kind"] == "docs" and not sel["own"] else None
+
+    def _op_matching(self, op, s, context=False):
+        """pfac_documents_matching / _context.  first: "own" = d_doc_first NULL, "seg" / "docsel" = the caller's doc_first
+        of an earlier segment / per-document selection; nd: n_docs of that doc_first ("ok") or one more; flags; out:
+        "own" = d_ids_out NULL, "caller" = exactly *n_matching entries, "small" = one fewer, "odd" = misaligned.  The
+        slot-owned ids are dropped at the start of either call, whatever it returns; nothing else drops them."""
+        s.dm = None
+        src = self._first_of(op, s)
+        if src is None:
+            return Exp(None)
+        faults = set()
+        if src == "none":
+            faults.add(E_STATE)
+        if op["nd"] != "ok":
+            if op["first"] != "own" or src == "none":
+                return Exp(None)                                # (a caller's doc_first of another length: nothing can tell)
+            faults.add(E_ARG)
+        if op["flags"] > 1 or (context and op["flags"]):
+            faults.add(E_ARG)
+        if op["out"] == "odd":
+            faults.add(E_ARG)
+        if faults:
+            return Exp(None) if op["out"] == "small" else self._one(faults)
+        spec = src + (("c", op["before"], op["after"]) if context else ("m", bool(op["flags"])))
+        n = int(self.x.doc_ids(spec).size)
+        if op["out"] == "small":
+            return Exp(E_OVERFLOW if n > 0 else None, count=n)
+        s.dm = (spec, op["out"] == "own")
+        if op["out"] == "own":
+            return Exp(OK, lambda: n)
+        return Exp(OK, lambda: (n, self.x.doc_ids(spec)))
+
+    def _op_context(self, op, s):
+        return self._op_matching(op, s, context=True)
+
+    def _ids_fetch(self, op, s):
+        if s.dm is None or not s.dm[1]:
+            return Exp(E_STATE)
+        spec = s.dm[0]
+        return Exp(OK, lambda: self.x.doc_ids(spec))
+
+    def _op_gather(self, op, s):
+        """pfac_documents_gather.  src / nb as in split (tab, inp: the caller's input); off: "slot" = d_doc_offsets NULL,
+        "caller" = a caller's copy of the slot's offsets; nd: n_docs of the offsets or one more; ids: "own" = d_ids NULL,
+        else a caller's list (Expectations.id_list); ni: n_ids of the list or one more; out / oo: d_out ("own", "caller" at
+        exactly *out_bytes, "small", "odd") and d_out_offsets ("own", "caller").  The slot-owned outputs are dropped at the
+        start of every gather."""
+        s.ga = None
+        x = self.x
+        faults = set()
+        if op["src"] == "slot":
+            if not s.has_in or s.up is None or op["nb"] > s.up[2]:
+                return Exp(None)
+            t, i = s.up[:2]
+        else:
+            t, i = op["tab"], op["inp"]
+            if op["nb"] > x.input_size(t, i):
+                return Exp(None)
+            if op["src"] == "odd":
+                faults.add(E_ARG)
+        doc = s.doc
+        if doc is None:
+            if op["off"] != "slot" or op["nd"] != "ok":
+                return Exp(None)
+            faults.add(E_STATE)
+        elif op["nd"] != "ok":
+            if op["off"] != "slot":
+                return Exp(None)
+            faults.add(E_STATE)
+        spec = s.dm[0] if s.dm is not None else None
+        if op["ids"] == "own":
+            if s.dm is None or not s.dm[1]:
+                faults.add(E_STATE)
+                if op["ni"] != "ok":
+                    return Exp(None)
+            elif op["ni"] != "ok":
+                faults.add(E_ARG)
+        elif op["ni"] != "ok":
+            return Exp(None)                                    # (a caller's list of another length: nothing can tell)
+        if op["out"] == "odd":
+            faults.add(E_ARG)
+        known = doc is not None and not (op["ids"] == "own" and (s.dm is None or not s.dm[1]))
+        if known:                                               # what the device checks: the ids, and the SELECTED documents
+            off = x.offsets(*doc).astype(np.int64)
+            ids = x.id_list(spec, op["ids"], int(off.size) - 1).astype(np.int64)
+            good = ids < off.size - 1
+            a, b = off[ids[good]], off[ids[good] + 1]
+            if not good.all() or (a > b).any() or (b > op["nb"]).any():
+                faults.add(E_ARG)
+        if faults:
+            return Exp(None) if op["out"] == "small" else self._one(faults)
+        args = (t, i, op["nb"], doc, spec, op["ids"])
+        n = int(x.gather(*args)[0].size)
+        if op["out"] == "small":
+            return Exp(E_OVERFLOW if n > 0 else None, count=n)
+        own_out, own_off = op["out"] == "own", op["oo"] == "own"
+        s.ga = (args, own_out, own_off)
+        return Exp(OK, lambda: (n,) + (() if own_out else (x.gather(*args)[0],)) + (() if own_off else (x.gather(*args)[1],)))
+
+    def _ga_fetch(self, op, s):
+        if s.ga is None or not s.ga[1]:
+            return Exp(E_STATE)
+        args = s.ga[0]
+        if op["first"] + op["n"] > self.x.gather(*args)[0].size:
+            return Exp(E_ARG)
+        return Exp(OK, lambda: self.x.gather(*args)[0][op["first"]:op["first"] + op["n"]])
+
+    def _gaoff_fetch(self, op, s):
+        if s.ga is None or not s.ga[2]:
+            return Exp(E_STATE)
+        args = s.ga[0]
+        return Exp(OK, lambda: self.x.gather(*args)[1])
+
     # -- plumbing -----------------------------------------------------------
     def _set_stream(self, op, s):
         s.shared = op["share"]
@@ -909,6 +1169,8 @@ class Model:
         grow_in, grow_rec = op["which"] in ("input", "both"), op["which"] in ("records", "both")
         if (grow_in and s.has_in) or (grow_rec and s.has_rec):
             s.scan = None
+        if grow_in:
+            s.up = None                                         # (a new input buffer: the header promises nothing about its bytes)
         s.has_in, s.has_rec = s.has_in or grow_in, s.has_rec or grow_rec
         return Exp()
 
@@ -937,6 +1199,9 @@ KINDS = {"load_table": 4, "set_flen": 1, "set_reps": 2, "scan_bytes": 9, "scan_s
          "reserve_grow": 3}
 WORD_KINDS = dict(KINDS, filter=9)      # the kinds of a plan with the whole-word filter (plan(seed, words=True))
 COUNT_KINDS = dict(WORD_KINDS, scan_ext=10, count=9, count_sel=5, cnt_fetch=4)      # ... and of one with the counts as well (plan(seed, counts=True))
+# ... and of one with the line path as well (plan(seed, lines=True))
+LINE_KINDS = dict(COUNT_KINDS, sync=2, split=14, doc_fetch=8, matching=10, context=10, ids_fetch=5, gather=14, ga_fetch=7, gaoff_fetch=5)
+LINE_OPS = ("split", "doc_fetch", "matching", "context", "ids_fetch", "gather", "ga_fetch", "gaoff_fetch")
 READERS = ("records", "packed", "checksum", "text", "scan_finish")          # what reads a finished scan, besides the passes
 
 
@@ -954,7 +1219,7 @@ def _propose(rng, m, kinds=KINDS):
         op.pop("slot")
         op["tab"] = str(rng.choice(sorted(TABLES)))
         op["knob"] = int(rng.choice(TABLES[op["tab"]]["knobs"]))
-        if kinds is COUNT_KINDS:
+        if "count" in kinds:
             op["cknob"] = int(rng.integers(0, len(CKNOBS)))
     elif kind == "set_flen":
         op.pop("slot")
@@ -1001,6 +1266,18 @@ def _propose(rng, m, kinds=KINDS):
         mine = ("own" if s.sel["own"] else "caller") if s.sel else "own"
         op.update(_count_sel_op(slot, dst=str(rng.choice(["own", "caller"])), acc=bool(rng.random() < 0.4),
                                 sel=mine if rng.random() < 0.75 else str(rng.choice(["own", "junk", "misaligned"]))))
+    elif kind == "split":
+        op.update(_draw_split(rng, m, slot))
+    elif kind == "doc_fetch":
+        total = int(x.offsets(*s.doc).size) if s.doc else 2
+        op["first"], op["n"] = _window(rng, total)
+    elif kind in ("matching", "context"):
+        op.update(_draw_matching(rng, m, slot, kind == "context"))
+    elif kind == "gather":
+        op.update(_draw_gather(rng, m, slot))
+    elif kind == "ga_fetch":
+        total = int(x.gather(*s.ga[0])[0].size) if s.ga else 3
+        op["first"], op["n"] = _window(rng, total)
     elif kind == "set_stream":
         op["slot"] = 1
         op["share"] = not m.slots[1].shared
@@ -1008,6 +1285,298 @@ def _propose(rng, m, kinds=KINDS):
         op["which"] = str(rng.choice(["input", "records", "both"]))
         op["k"] = s.grow + 1
     return op
+
+
+def _draw_split(rng, m, slot):
+    """The arguments of a split on `slot`: mostly the slot's own input up to the scan's n_owned, at one of the input's
+    three delimiters; now and then fewer bytes, none, a caller's copy, or one of the documented errors."""
+    s = m.slots[slot]
+    tab, inp = s.up[:2] if s.up else (m.tab or "abc2", 0)
+    size = m.x.input_size(tab, inp)
+    no = s.scan["no"] if s.scan and s.up and (s.scan["tab"], s.scan["inp"]) == (tab, inp) else size
+    r = rng.random()
+    nb = no if r < 0.65 else size if r < 0.75 else (no * 3) // 4 if r < 0.88 else 0
+    op = dict(src="slot" if rng.random() < 0.7 else "caller", tab=tab, inp=inp, nb=nb,
+              delim=int(rng.choice(m.x.delims(tab, inp), p=[.5, .3, .2])))
+    r = rng.random()
+    if r < 0.04:
+        op["delim"] = int(rng.choice([256, -1]))
+    elif r < 0.08:
+        op.update(src="slot", nb="over")
+    elif r < 0.12:
+        op["src"] = "odd"
+    return op
+
+
+CONTEXTS = ((0, 0), (1, 0), (0, 1), (2, 3), (0, U64_MAX), (U64_MAX, U64_MAX), (1 << 33, 0), (5, 1 << 33))    # (2^33: more than any n_docs)
+
+
+def _draw_matching(rng, m, slot, context):
+    s = m.slots[slot]
+    have = ["own"] * 3 + (["seg"] if s.segc else []) + (["docsel"] if s.sel and s.sel["kind"] == "docs" and not s.sel["own"] else [])
+    op = dict(first=str(rng.choice(have)), nd="ok", flags=0 if context else int(rng.random() < 0.35),
+              out=str(rng.choice(["own", "caller", "small", "odd"], p=[.55, .3, .1, .05])))
+    if context:
+        op["before"], op["after"] = CONTEXTS[int(rng.integers(0, len(CONTEXTS)))]
+    r = rng.random()
+    if r < 0.04:
+        op["flags"] = 1 if context else 2
+    elif r < 0.08:
+        op["nd"] = "plus"
+    return op
+
+
+ID_FORMS = ("own", "same", "perm", "rev", "twice", "empty", "bad_id", "all")
+
+
+def _draw_gather(rng, m, slot):
+    s = m.slots[slot]
+    tab, inp = s.up[:2] if s.up else (m.tab or "abc2", 0)
+    if s.doc is not None and rng.random() < 0.85:                # mostly the input the offsets were made for
+        tab, inp = s.doc[:2]
+    size = m.x.input_size(tab, inp)
+    nb = min(s.doc[2], size) if s.doc is not None and rng.random() < 0.85 else size
+    mine = s.up is not None and s.up[:2] == (tab, inp)
+    op = dict(src="slot" if mine and rng.random() < 0.7 else "caller", tab=tab, inp=inp, nb=nb, off=str(rng.choice(["slot", "caller"], p=[.7, .3])), nd="ok",
+              ids=str(rng.choice(ID_FORMS, p=[.4, .1, .1, .1, .1, .07, .08, .05])), ni="ok",
+              out=str(rng.choice(["own", "caller", "small", "odd"], p=[.55, .3, .1, .05])), oo=str(rng.choice(["own", "caller"], p=[.6, .4])))
+    r = rng.random()
+    if r < 0.04:
+        op["nd"] = "plus"
+    elif r < 0.08:
+        op["ni"] = "plus"
+    elif r < 0.12:
+        op["src"] = "odd"
+    elif r < 0.16 and nb > 0:
+        op["nb"] = nb - 1                                       # the last document then passes n_bytes: PFAC_E_ARG if it is selected
+    return op
+
+
+def _matching_op(slot, first="own", out="own", flags=0, context=None):
+    op = dict(op="context" if context else "matching", slot=slot, first=first, nd="ok", flags=flags, out=out)
+    if context:
+        op["before"], op["after"] = context
+    return op
+
+
+def _gather_op(slot, m, **kw):
+    """A gather of the slot's own input, offsets and ids into slot-owned outputs, up to the end of the offsets."""
+    s = m.slots[slot]
+    if s.up is None or s.doc is None:
+        return None
+    op = dict(op="gather", slot=slot, src="slot", tab=s.up[0], inp=s.up[1], nb=min(s.doc[2], s.up[2]), off="slot", nd="ok", ids="own", ni="ok",
+              out="own", oo="own")
+    op.update(kw)
+    return op
+
+
+def _split_step(rng, slot, part=1.0):
+    """A split of the slot's own input up to the scan's n_owned (`part`: up to that part of it), at a delimiter drawn now."""
+    which = int(rng.choice(3, p=[.5, .3, .2]))
+
+    def step(m):
+        s = m.slots[slot]
+        if s.up is None or s.scan is None or (s.scan["tab"], s.scan["inp"]) != s.up[:2]:
+            return None
+        return dict(op="split", slot=slot, src="slot", tab=s.up[0], inp=s.up[1], nb=int(s.scan["no"] * part), delim=m.x.delims(*s.up[:2])[which])
+    return step
+
+
+def _line_prepare(rng, slot, upto):
+    """What a session does so that `upto` ("segment", "matching" or "gather") has something to work on: a scan of a host
+    buffer, offsets for it (a split, or set_doc), the segment into the slot's buffers, a matching call."""
+    use_split = rng.random() < 0.7
+
+    def offsets(m):
+        s = m.slots[slot]
+        sc = s.scan
+        if sc is None or sc["ext"] and use_split:
+            return None
+        if s.doc is not None and s.doc[:3] == (sc["tab"], sc["inp"], sc["no"]) and not s.doc[3].startswith("bad"):
+            return None
+        if use_split and s.up is not None and s.up[:2] == (sc["tab"], sc["inp"]):
+            return _split_step(rng, slot)(m)
+        return dict(op="set_doc", slot=slot, tab=sc["tab"], inp=sc["inp"], no=sc["no"], dkey=str(rng.choice(DOC_KEYS[:2])))
+
+    def segment(m):
+        s = m.slots[slot]
+        if s.seg is None or not s.seg["own"] or s.doc is None or s.seg["key"][:4] != s.doc:
+            return _pass_op("segment", slot)
+
+    def ids(m):
+        if m.slots[slot].dm is None or not m.slots[slot].dm[1]:
+            return _matching_op(slot, flags=int(rng.random() < 0.3))
+
+    steps = _prepare(rng, "select", slot) + [offsets]
+    if upto in ("matching", "gather"):
+        steps.append(segment)
+    if upto == "gather":
+        steps.append(ids)
+    return steps
+
+
+# what may come between a producer of the line path and the late fetch of its result (the reach test wants every pair)
+BETWEEN = ("split", "set_doc", "segment", "matching", "context", "gather", "scan", "upload", "grow", "filter")
+LATE = {"split": ("doc_fetch",), "set_doc": ("doc_fetch",), "matching": ("ids_fetch",), "context": ("ids_fetch",), "gather": ("ga_fetch", "gaoff_fetch")}
+
+
+def _between_steps(rng, slot, what):
+    """One intervening call `what` on `slot`, meant to succeed."""
+    if what == "split":
+        return [_split_step(rng, slot)]
+    if what == "set_doc":
+        return [lambda m: dict(op="set_doc", slot=slot, tab=m.slots[slot].scan["tab"], inp=m.slots[slot].scan["inp"], no=m.slots[slot].scan["no"],
+                               dkey=str(DOC_KEYS[int(rng.integers(0, 2))])) if m.slots[slot].scan else None]
+    if what == "segment":
+        return _line_prepare(rng, slot, "segment") + [_pass_op("segment", slot, own=bool(rng.random() < 0.7))]
+    if what in ("matching", "context"):
+        ctx = CONTEXTS[int(rng.integers(0, len(CONTEXTS)))] if what == "context" else None
+        return _line_prepare(rng, slot, "matching") + [_matching_op(slot, out=str(rng.choice(["own", "caller"])), context=ctx)]
+    if what == "gather":
+        return _line_prepare(rng, slot, "gather") + [lambda m: _gather_op(slot, m)]
+    if what == "scan":
+        return [_scan_step(rng, slot, other=True)]
+    if what == "upload":
+        tab = str(rng.choice(sorted(TABLES)))
+        return [dict(op="load_table", tab=tab, knob=int(rng.choice(TABLES[tab]["knobs"])), cknob=int(rng.integers(0, len(CKNOBS))))]
+    if what == "grow":
+        which = str(rng.choice(["records", "input", "both"]))
+        return [lambda m: dict(op="reserve_grow", slot=slot, which=which, k=m.slots[slot].grow + 1)]
+    assert what == "filter"
+    return _prepare(rng, "filter", slot) + [_filter_step(rng, slot)]
+
+
+def _late_fetch(rng, slot, kind, beyond=False):
+    """The fetch of a slot-owned result: all of it from a place drawn now (`beyond`: one entry more than there is)."""
+    at = rng.random()
+
+    def step(m):
+        s = m.slots[slot]
+        if kind in ("doc_fetch", "ga_fetch"):
+            total = (int(m.x.offsets(*s.doc).size) if s.doc else 0) if kind == "doc_fetch" else (int(m.x.gather(*s.ga[0])[0].size) if s.ga else 0)
+            first = int(at * total) if at < 0.7 else 0
+            return dict(op=kind, slot=slot, first=first, n=total - first + beyond)
+        return dict(op=kind, slot=slot)
+    return step
+
+
+class _Quiet:
+    """An agenda step whose operation the line agenda does not follow up: what comes between a producer and its late
+    fetch must not make the producer's pass run again."""
+
+    def __init__(self, step):
+        self.step = step
+
+
+# the refused variants of a call that has just succeeded (one broken rule each), tried right behind it
+REFUSED = {"split": (dict(delim=256), dict(delim=-1), dict(src="slot", nb="over"), dict(src="odd")),
+           "matching": (dict(out="small"), dict(flags=2), dict(nd="plus"), dict(out="odd")),
+           "context": (dict(out="small"), dict(flags=1), dict(nd="plus"), dict(out="odd")),
+           "gather": (dict(out="small"), dict(nd="plus"), dict(ni="plus"), dict(src="odd"), dict(out="odd"), dict(ids="bad_id"), dict(nb=-1))}
+
+
+def _next(turn, key):
+    """The next value of the plan's counter `key` (it starts at five times the seed: every plan elsewhere in a cycle of 2,
+    3, 4, 7, 8, 9 or 32)."""
+    turn[key] = turn.get(key, turn["seed"] * 5 + len(key)) + 1
+    return turn[key] - 1
+
+
+def _refused(chosen, turn):
+    err = dict(REFUSED[chosen["op"]][_next(turn, "refused " + chosen["op"]) % len(REFUSED[chosen["op"]])])
+    if err.get("nb") == -1:
+        err["nb"] = max(chosen["nb"] - 1, 0)
+    if "nd" in err and chosen["op"] == "gather":
+        err["off"] = "slot"                                     # (only the slot's offsets have an n_docs of their own)
+    if "ni" in err:
+        err["ids"] = "own"                                      # (... and only the slot's ids a count)
+    return dict(chosen, **err)
+
+
+def _line_agenda(rng, m, chosen, st, agenda, turn):
+    """The histories the line family aims at (the rules of plan(seed, lines=True)); returns the new agenda.  `turn`
+    holds counters that walk BETWEEN, the 32 combinations of NULL and caller's arguments of the gather, and
+    REFUSED, so that every (producer, intervening call, late fetch) order, every combination and every refusal comes up
+    in the suite's plans and not only the likely ones."""
+    kind, slot = chosen["op"], chosen.get("slot", 0)
+    s = m.slots[slot]
+    if st != OK:
+        return agenda
+    fetches = [f for f in LATE.get(kind, ()) if kind in ("split", "set_doc") or chosen["oo" if f == "gaoff_fetch" else "out"] == "own"]
+    follow = []
+    if kind in ("matching", "context"):
+        # the ids are there to be gathered: every combination of NULL and caller's arguments in turn
+        for c in (_next(turn, "combination"), _next(turn, "combination")):
+            form = "own" if chosen["out"] == "own" and c & 4 else str(rng.choice(("same", "perm", "rev", "twice", "empty", "all")))
+            follow.append(lambda m, c=c, form=form: _gather_op(slot, m, src="slot" if c & 1 else "caller", off="slot" if c & 2 else "caller", ids=form,
+                                                               out="own" if c & 8 else "caller", oo="own" if c & 16 else "caller"))
+    if kind == "split" and chosen["nb"] != "over" and s.scan is not None and chosen["nb"] != s.scan["no"]:
+        # offsets that do not end at the scan's n_owned: the document passes and the filter answer PFAC_E_ARG
+        what = ("segment", "select_docs", "filter")[_next(turn, "other bytes") % 3]
+        follow = [lambda m: None if m.flen else dict(op="set_flen"),
+                  dict(op="filter", slot=slot, f=int(rng.integers(5, 10)), heap="own") if what == "filter" else _pass_op(what, slot)]
+    if fetches and len(agenda) < 40 and rng.random() < 0.95:
+        # a producer, one or two other calls, then the late fetch
+        between = [b for b in BETWEEN if b not in {"split": ("split", "set_doc"), "set_doc": ("split", "set_doc"), "matching": ("matching", "context"),
+                                                    "context": ("matching", "context"), "gather": ("gather",)}[kind]]
+        steps = _between_steps(rng, slot, between[_next(turn, "between " + kind) % len(between)])
+        if rng.random() < 0.25:
+            steps += _between_steps(rng, slot, str(rng.choice([b for b in between if b not in ("grow", "upload")])))
+        if kind == "gather" and fetches == list(LATE[kind]) and rng.random() < 0.35:
+            # a larger gather first: the slot-owned outputs regrow while nothing has fetched the first
+            steps = [lambda m: _gather_op(slot, m, ids="twice", src="caller"), _late_fetch(rng, slot, "ga_fetch")] + steps
+        steps = [_Quiet(step) for step in steps]
+        late = [_late_fetch(rng, slot, f) for f in fetches]
+        if fetches[0] != "ids_fetch" and rng.random() < 0.25:
+            late = [_late_fetch(rng, slot, fetches[0], beyond=True)] + late
+        again = [_refused(chosen, turn)] if kind in REFUSED and rng.random() < 0.4 else []    # (refused once nothing needs the result any more)
+        if kind == "gather" and chosen["src"] == "slot" and rng.random() < 0.3:
+            # the slot's input is what was uploaded last, whatever the slot has scanned since: a scan of a caller's buffer, the gather again
+            again = [_Quiet(_ext_step(rng, slot)), _Quiet(dict(chosen)), _Quiet(_late_fetch(rng, slot, fetches[0]))] + again
+        return (follow + steps + late if kind == "split" else steps + late + follow) + again + agenda
+    if kind in REFUSED and rng.random() < 0.5:
+        agenda = [_refused(chosen, turn)] + agenda
+    if kind == "segment" and chosen["own"] and rng.random() < 0.4:
+        # segment, filter, segment, matching: the ids are those of the filtered scan's doc_first -- not of the unfiltered
+        # one, and not of a per-document selection made before the filter
+        before = [_pass_op("select_docs", slot, own=bool(rng.random() < 0.5))] if rng.random() < 0.5 else []
+        agenda = before + [_filter_step(rng, slot), _pass_op("segment", slot), _matching_op(slot, flags=int(rng.random() < 0.3)),
+                           dict(op="ids_fetch", slot=slot)] + agenda
+    elif kind == "segment" and chosen["own"] and rng.random() < 0.25:
+        # the doc_first of a per-document selection in the caller's buffer gives the same ids
+        ctx = CONTEXTS[int(rng.integers(0, len(CONTEXTS)))] if rng.random() < 0.4 else None
+        agenda = [_pass_op("select_docs", slot, own=False), _matching_op(slot, first="docsel", out=str(rng.choice(["own", "caller"])), context=ctx)] + agenda
+    elif kind == "segment" and chosen["own"] and rng.random() < 0.25:
+        agenda = [_pass_op("segment", slot, own=False)] + agenda  # the same again into the caller's buffers
+    elif kind == "segment" and chosen["own"]:
+        ctx = CONTEXTS[int(rng.integers(0, len(CONTEXTS)))] if rng.random() < 0.65 else None
+        agenda = [_matching_op(slot, out=str(rng.choice(["own", "caller"], p=[.85, .15])), flags=int(ctx is None and rng.random() < 0.3), context=ctx)] + agenda
+    elif kind == "segment" and not chosen["own"]:
+        # the segment went to the caller's buffers: NULL is refused, the caller's doc_first is not
+        ctx = CONTEXTS[int(rng.integers(0, len(CONTEXTS)))] if _next(turn, "caller's segment") % 2 else None
+        agenda = [_matching_op(slot, context=ctx), _matching_op(slot, first="seg", out=str(rng.choice(["own", "caller"])), context=ctx)] + agenda
+    elif kind == "select_docs" and not chosen["own"] and rng.random() < 0.7:
+        agenda = [_matching_op(slot, first="docsel", context=CONTEXTS[int(rng.integers(0, len(CONTEXTS)))] if rng.random() < 0.5 else None)] + agenda
+    elif follow:
+        agenda = follow + agenda
+    elif kind == "scan_bytes" and rng.random() < 0.08:
+        # the split needs no finished scan: it runs while the next one is pending
+        agenda = [_ext_step(rng, slot, start=True), _split_step(rng, slot), dict(op="scan_finish", slot=slot)] + agenda
+    elif kind in ("scan_bytes", "scan_finish") and s.scan is not None and rng.random() < 0.25:
+        agenda = [_split_step(rng, slot, part=float(rng.choice([0.75, 0.0])))] + agenda      # a split of fewer bytes than the scan owns, or of none
+    elif kind in ("scan_bytes", "scan_finish") and s.scan is not None and rng.random() < 0.3:
+        agenda = _line_prepare(rng, slot, "matching") + agenda
+    elif kind in ("scan_bytes", "scan_finish") and s.scan is not None and rng.random() < 0.5:
+        agenda = _line_prepare(rng, slot, "gather") + [lambda m: _gather_op(slot, m)] + agenda
+    elif kind == "set_doc" and chosen["dkey"].startswith("bad") and rng.random() < 0.7:
+        # offsets that break the rules: refused once a document that breaks them is selected
+        agenda = [lambda m: _gather_op(slot, m, ids="all", nb=m.slots[slot].up[2] if m.slots[slot].up else 0)] + agenda
+    elif kind == "scan_start" and rng.random() < 0.5:
+        agenda = [_split_step(rng, slot)] + agenda              # a split while the scan is pending
+    if kind == "select_docs" and rng.random() < 0.3:
+        # a split makes the per-document selection stale for replace_docs with NULL offsets
+        agenda = [_split_step(rng, slot), _pass_op("replace_docs", slot)] + agenda
+    return agenda
 
 
 def _pass_op(kind, slot, own=True):
@@ -1208,23 +1777,34 @@ def _count_agenda(rng, m, chosen, st, agenda):
     return agenda
 
 
-def plan(seed, n_ops=PLAN_OPS, words=False, counts=False):
+def plan(seed, n_ops=None, words=False, counts=False, lines=False):
     """The plan of `seed`: a list of operations (dicts).  Deterministic; the model decides what each one is worth.
     `words`: the second family of plans, in which the whole-word filter is one of the operations (the first family is
     what it was before the filter existed, seed for seed).  `counts`: the third family, the second one's operations and
-    the per-pattern counts (count, count_sel, cnt_fetch; tables installed under an entry of CKNOBS)."""
-    rng = np.random.default_rng([seed, 0x53455353494F4E] + ([0x434F554E54] if counts else [0x574F5244] if words else []))
-    kinds = COUNT_KINDS if counts else WORD_KINDS if words else KINDS
+    the per-pattern counts (count, count_sel, cnt_fetch; tables installed under an entry of CKNOBS).  `lines`: the
+    fourth family, the third one's operations and the line path (LINE_OPS), LINE_PLAN_OPS operations long."""
+    n_ops = n_ops or (LINE_PLAN_OPS if lines else PLAN_OPS)
+    rng = np.random.default_rng([seed, 0x53455353494F4E] + ([0x4C494E4553] if lines else [0x434F554E54] if counts else [0x574F5244] if words else []))
+    kinds = LINE_KINDS if lines else COUNT_KINDS if counts else WORD_KINDS if words else KINDS
+    counts = counts or lines                                    # (the line family counts like the count family)
     words = words or counts                                     # (the count family filters like the word family)
+    turn = {"seed": seed}                                       # (the line family's walks start elsewhere in every plan)
     m = Model()
     ops, agenda = [], []
     if counts:                                                  # (a fetch before any count: PFAC_E_STATE)
         agenda = [dict(op="cnt_fetch", slot=int(rng.integers(0, N_SLOTS)))] if rng.random() < 0.3 else []
+    if lines and rng.random() < 0.5:                            # (a fetch before anything was made: PFAC_E_STATE)
+        early = str(rng.choice(["doc_fetch", "ids_fetch", "gaoff_fetch"]))
+        agenda.append(dict(op=early, slot=int(rng.integers(0, N_SLOTS)), **({"first": 0, "n": 1} if early == "doc_fetch" else {})))
+    if lines and rng.random() < 0.5:                            # (half of the line plans begin with slot 1 on slot 0's stream)
+        agenda.append(dict(op="set_stream", slot=1, share=True))
     while len(ops) < n_ops:
         want_err = rng.random() < (1 / 16 if words else 1 / 8)   # (words: the filter between a selection and its replace adds errors of its own)
-        chosen = None
+        chosen, quiet = None, False
         while agenda and chosen is None and not want_err:      # what the session set out to do comes first
             cand = agenda.pop(0)
+            quiet = isinstance(cand, _Quiet)
+            cand = cand.step if quiet else cand
             cand = cand(m) if callable(cand) else cand
             if cand is not None and m.predict(cand).status is not None:
                 chosen = cand
@@ -1248,6 +1828,12 @@ def plan(seed, n_ops=PLAN_OPS, words=False, counts=False):
                     agenda = _prepare(rng, prod, cand["slot"]) + [_pass_op(prod, cand["slot"]), cand]
             elif st != OK and not agenda and cand["op"] == "filter" and cand["heap"] == "own":
                 agenda = _prepare(rng, "filter", cand["slot"], docs=FILTERS[cand["f"]]["doc"] == "slot") + [cand]
+            elif st != OK and not agenda and cand["op"] in ("matching", "context", "gather", "ids_fetch", "ga_fetch", "gaoff_fetch"):
+                # the line path with nothing to work on: a scan, offsets, a segment and ids first
+                upto = "matching" if cand["op"] in ("matching", "context") else "gather"
+                made = {"ids_fetch": [_matching_op(cand["slot"])], "ga_fetch": [lambda m, c=cand: _gather_op(c["slot"], m)],
+                        "gaoff_fetch": [lambda m, c=cand: _gather_op(c["slot"], m)]}.get(cand["op"], [])
+                agenda = _line_prepare(rng, cand["slot"], upto) + made + ([] if cand["op"] == "ga_fetch" else [cand])
         if chosen is None:
             continue
         if counts and chosen["op"] == "load_table" and "cknob" not in chosen:
@@ -1301,14 +1887,16 @@ def plan(seed, n_ops=PLAN_OPS, words=False, counts=False):
         if st == OK and chosen["op"] == "scan_start" and rng.random() < 0.7:    # the other slot works while this scan is pending
             agenda = [dict(op="scan_bytes", slot=1 - chosen["slot"], inp=chosen["inp"], no=chosen["no"]),
                       dict(op="scan_finish", slot=chosen["slot"])] + agenda
-        if counts:
+        if counts and (not lines or rng.random() < 0.25):           # (the line family has an agenda of its own to get through)
             agenda = _count_agenda(rng, m, chosen, st, agenda)
+        if lines and not quiet:
+            agenda = _line_agenda(rng, m, chosen, st, agenda, turn)
     return ops
 
 
-def shrink(seed, k, n_ops=PLAN_OPS, words=False, counts=False):
+def shrink(seed, k, n_ops=None, words=False, counts=False, lines=False):
     """The plan of `seed` with operation k onwards removed: cut a failing history down by hand."""
-    return plan(seed, n_ops, words, counts)[:k]
+    return plan(seed, n_ops, words, counts, lines)[:k]
 
 
 # ---------------------------------------------------------------------------
@@ -1321,6 +1909,7 @@ class _SlotBufs:
         self.last_sel = None                                    # the d_out of the last selection that went to the caller
         self.cnt = None                                         # the caller's count buffer (_CountBuf) and the model's serial of it
         self.cnt_serial = 0
+        self.seg_first = None                                   # the d_doc_first (_OutBuf) of the last segment into the caller's buffers
 
 
 class Odd:
@@ -1398,6 +1987,32 @@ def _raw_count(g, slot, d_records, d_counts, n_states, flags):
     return n.value
 
 
+def _raw_matching(g, slot, context, d_first, n_docs, before, after, flags, d_out, out_cap):
+    """pfac_documents_matching / _context themselves, for the flags the wrapper would not pass."""
+    if hasattr(g, "raw_matching"):
+        return g.raw_matching(slot, context, d_first, n_docs, before, after, flags, d_out, out_cap)
+    import ctypes as C
+    from phfpfac_amd.matcher import _ptr
+    n = C.c_uint64(0)
+    if context:
+        rc = g._L.pfac_documents_matching_context(g._ctx, slot, _ptr(d_first), int(n_docs), int(before), int(after), int(flags), _ptr(d_out),
+                                                  int(out_cap), C.byref(n))
+    else:
+        rc = g._L.pfac_documents_matching(g._ctx, slot, _ptr(d_first), int(n_docs), int(flags), _ptr(d_out), int(out_cap), C.byref(n))
+    if rc:
+        e = PfacError(rc, (g._L.pfac_last_error(g._ctx) or b"").decode())
+        e.n_matching = n.value
+        raise e
+    return n.value
+
+
+def _odd(g, buf):
+    """Four bytes into a caller's buffer: a misaligned pointer."""
+    if hasattr(g, "alloc"):
+        return Odd(buf)
+    return (buf if isinstance(buf, int) else int(buf.data_ptr())) + 4
+
+
 def _alloc(g, n_bytes):
     if hasattr(g, "alloc"):
         return g.alloc(n_bytes)
@@ -1443,7 +2058,9 @@ class Executor:
         self.x = model.x
         self.bufs = [_SlotBufs() for _ in range(N_SLOTS)]
         self.stats = dict(ops=0, errors=0, compared=0, filters=0, counts=0, widths=set(), staging=set(), variants=set(), statuses=set(),
-                          regimes=set())                        # (regimes: (entry of CKNOBS, "direct" / "cache") of every count that ran)
+                          regimes=set(),                        # (regimes: (entry of CKNOBS, "direct" / "cache") of every count that ran)
+                          splits=0, matchings=0, gathers=0, ids=0)   # (the line path: calls that succeeded, document ids compared)
+        self.inputs = {}                                        # (tab, inp) -> a caller's device copy of that input
         self.ids_direct = getattr(g, "states_are_ids", False)
 
     def ids(self, tab, states):
@@ -1473,7 +2090,7 @@ class Executor:
         except PfacError as e:
             assert e.status == exp.status, f"raised {e} (status {e.status}), want {STATUS_NAMES[exp.status]}"
             if exp.count is not None:
-                n = [getattr(e, a) for a in ("n_kept", "n_selected", "out_bytes") if hasattr(e, a)]
+                n = [getattr(e, a) for a in ("n_kept", "n_selected", "out_bytes", "n_matching") if hasattr(e, a)]
                 assert n == [exp.count], f"the overflow error carries {n}, want [{exp.count}]"
             self.stats["errors"] += 1
             return exp.status
@@ -1599,6 +2216,7 @@ class Executor:
         d_out, d_first = _OutBuf(g, cap * 8), _OutBuf(g, (nd + 1) * 8)
         n = int(self._guarded(slot, {"d_out": d_out, "d_doc_first": d_first}, "segment_records", lambda: g.segment_records(
             nd, d_out=d_out.ptr, out_cap=cap, d_doc_first=d_first.ptr, slot=slot, d_records=self.bufs[slot].rec)))
+        self.bufs[slot].seg_first = d_first
         return (n, d_first.read(np.uint64, nd + 1)) + self.recs(exp.tab, d_out.read(REC, n))
 
     def do_seg_fetch(self, op, exp, before):
@@ -1809,6 +2427,109 @@ class Executor:
         cnt = self.m.slots[op["slot"]].cnt
         got = self.g.state_counts_to_host(op["slot"])
         return self.by_id(cnt["tab"], got, cnt["parts"]) if cnt else got
+
+    # -- lines: split, matching documents, gather -------------------------------
+    def _caller_input(self, tab, inp):
+        if (tab, inp) not in self.inputs:
+            self.inputs[(tab, inp)] = _upload(self.g, self.x.input(tab, inp))
+        return self.inputs[(tab, inp)]
+
+    def _d_input(self, op):
+        if op["src"] == "slot":
+            return None
+        buf = self._caller_input(op["tab"], op["inp"])
+        return _odd(self.g, buf) if op["src"] == "odd" else buf
+
+    def do_split(self, op, exp, before):
+        nb = (1 << 31) if op["nb"] == "over" else op["nb"]       # (2 GiB: above every input buffer of a session, below the 2^32 limit)
+        n_docs, tail = self.g.split_documents(nb, op["delim"], d_input=self._d_input(op), slot=op["slot"])
+        self.stats["splits"] += 1
+        return int(n_docs), int(tail)
+
+    def do_doc_fetch(self, op, exp, before):
+        doc = self.m.slots[op["slot"]].doc
+        nd = int(self.x.offsets(*doc).size) - 1 if doc else 0
+        self.stats["ids"] += op["n"]
+        return self.g.doc_offsets_to_host(nd, op["slot"], first=op["first"], n=op["n"])
+
+    def do_matching(self, op, exp, before, context=False):
+        g, slot = self.g, op["slot"]
+        b, s = self.bufs[slot], self.m.slots[slot]
+        # n_docs and the pointer of the doc_first the call is given (the model has judged them already)
+        if op["first"] == "own":
+            nd, d_first = (int(self.x.offsets(*s.seg["key"][:4]).size) - 1 if s.seg else 1), None
+        elif op["first"] == "seg":
+            nd, d_first = int(self.x.offsets(*s.segc[:4]).size) - 1, b.seg_first.ptr
+        else:
+            nd, d_first = int(self.x.offsets(*s.sel["key"][:4]).size) - 1, b.first.ptr
+        nd += op["nd"] != "ok"
+        n = int(exp.value() if op["out"] == "own" else exp.value()[0]) if exp.status == OK else (exp.count or 0)
+        cap = n - 1 if op["out"] == "small" else n
+        out = None if op["out"] == "own" else _OutBuf(g, (cap + (op["out"] == "odd")) * 8)
+        d_out = None if out is None else _odd(g, out.ptr) if op["out"] == "odd" else out.ptr
+        bef, aft = (op["before"], op["after"]) if context else (0, 0)
+        if op["flags"] > 1 or (context and (op["flags"] or not (bef or aft))):     # (what the wrapper would not pass, or not to this call)
+            call = lambda: _raw_matching(g, slot, context, d_first, nd, bef, aft, op["flags"], d_out, cap)      # noqa: E731
+        else:
+            call = lambda: g.matching_documents(nd, invert=bool(op["flags"]), d_doc_first=d_first, d_out=d_out, out_cap=cap, slot=slot,   # noqa: E731
+                                                before=bef, after=aft)
+        got = int(call() if out is None else self._guarded(slot, {"d_ids_out": out}, "matching_documents", call))
+        self.stats["matchings"] += 1
+        if out is None:
+            return got
+        self.stats["ids"] += got
+        return got, out.read(np.uint64, got)
+
+    def do_context(self, op, exp, before):
+        return self.do_matching(op, exp, before, context=True)
+
+    def do_ids_fetch(self, op, exp, before):
+        dm = self.m.slots[op["slot"]].dm
+        n = int(self.x.doc_ids(dm[0]).size) if dm else 0
+        self.stats["ids"] += n
+        return self.g.matching_documents_to_host(n, op["slot"])
+
+    def do_gather(self, op, exp, before):
+        g, slot, x = self.g, op["slot"], self.x
+        s = self.m.slots[slot]
+        doc, dm = s.doc, s.dm
+        off = x.offsets(*doc) if doc else np.zeros(2, np.uint64)
+        nd = int(off.size) - 1
+        own_ids = op["ids"] == "own"
+        ids = x.id_list(dm[0] if dm else None, op["ids"], nd) if not own_ids or dm else np.zeros(0, np.uint64)
+        d_off = None if op["off"] == "slot" else _upload(g, off)
+        d_ids = None if own_ids else _upload(g, ids)
+        n = int(exp.value()[0]) if exp.status == OK else (exp.count or 0)
+        cap = n - 1 if op["out"] == "small" else n
+        outs = {}
+        if op["out"] != "own":
+            outs["d_out"] = _OutBuf(g, cap + 16 * (op["out"] == "odd"))
+        if op["oo"] != "own":
+            outs["d_out_offsets"] = _OutBuf(g, (int(ids.size) + (op["ni"] != "ok") + 1) * 8)
+        d_out = None if op["out"] == "own" else _odd(g, outs["d_out"].ptr) if op["out"] == "odd" else outs["d_out"].ptr
+        d_oo = outs["d_out_offsets"].ptr if "d_out_offsets" in outs else None
+        got = int(self._guarded(slot, outs, "gather_documents", lambda: g.gather_documents(
+            nd + (op["nd"] != "ok"), int(ids.size) + (op["ni"] != "ok"), op["nb"], d_input=self._d_input(op), d_doc_offsets=d_off, d_ids=d_ids,
+            d_out=d_out, out_cap=cap, d_out_offsets=d_oo, slot=slot)))
+        self.stats["gathers"] += 1
+        res = (got,)
+        if "d_out" in outs:
+            self.stats["compared"] += got
+            res += (outs["d_out"].read(np.uint8, got),)
+        if d_oo is not None:
+            self.stats["ids"] += int(ids.size) + 1
+            res += (outs["d_out_offsets"].read(np.uint64, int(ids.size) + 1),)
+        return res
+
+    def do_ga_fetch(self, op, exp, before):
+        self.stats["compared"] += op["n"]
+        return self.g.gathered_to_host(op["n"], op["slot"], first=op["first"])
+
+    def do_gaoff_fetch(self, op, exp, before):
+        ga = self.m.slots[op["slot"]].ga
+        n_ids = int(self.x.gather(*ga[0])[1].size) - 1 if ga else 0
+        self.stats["ids"] += n_ids + 1
+        return self.g.gathered_offsets_to_host(n_ids, op["slot"])
 
     # -- plumbing -----------------------------------------------------------
     def do_set_stream(self, op, exp, before):

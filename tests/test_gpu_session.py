@@ -2,9 +2,10 @@
 kernel knobs, many sizes, two slots, passes in any order, results fetched late, documented errors in between -- every
 result compared bit for bit with what include/pfac.h promises for that history.  The random plans are the suite's seeds;
 the named sessions are histories random plans reach rarely; half of the plans and the sessions at the end of this file
-have the whole-word filter among their calls, a third of the plans and the last group of sessions the per-pattern counts.
+have the whole-word filter among their calls, a third of the plans and a group of sessions the per-pattern counts, and a
+fourth family of plans and the last group of sessions the line path (split, matching documents, context lines, gather).
 Run with -m gpu on an MI355X.  Expectations come from the
-CPU oracle, llref, replref, docref, docreplref and the pattern files, never from the device.  No session aims at the
+CPU oracle, llref, replref, docref, docreplref, splitref, gatherref and the pattern files, never from the device.  No session aims at the
 scan's wait protocol: they provoke the errors the header documents, nothing else."""
 import gc
 import weakref
@@ -14,11 +15,12 @@ import pytest
 
 import session as S
 from phfpfac_amd import GpuMatcher
-from phfpfac_amd.matcher import splitmix64_bytes
+from phfpfac_amd.matcher import splitmix64_bytes, tiled_bytes
 
 pytestmark = pytest.mark.gpu
 
 X = S.expectations()
+TILE_BYTES = S.TILE
 
 
 def k(tab, **knobs):
@@ -89,18 +91,22 @@ def run(ops, want=None):
         return S.run(g, ops, m, seed="named")
 
 
-@pytest.mark.parametrize("seed,family", [(s, "") for s in S.SEEDS] + [(s, "words") for s in S.WORD_SEEDS] + [(s, "counts") for s in S.COUNT_SEEDS],
-                         ids=[str(s) for s in S.SEEDS] + [f"words-{s}" for s in S.WORD_SEEDS] + [f"counts-{s}" for s in S.COUNT_SEEDS])
+@pytest.mark.parametrize("seed,family", [(s, "") for s in S.SEEDS] + [(s, "words") for s in S.WORD_SEEDS] + [(s, "counts") for s in S.COUNT_SEEDS]
+                         + [(s, "lines") for s in S.LINE_SEEDS],
+                         ids=[str(s) for s in S.SEEDS] + [f"words-{s}" for s in S.WORD_SEEDS] + [f"counts-{s}" for s in S.COUNT_SEEDS]
+                         + [f"lines-{s}" for s in S.LINE_SEEDS])
 def test_session(seed, family):
     """One random plan on one context; `family`: "words" = a plan that filters whole words, "counts" = one that also
-    counts matches per pattern."""
-    ops = S.plan(seed, words=family == "words", counts=family == "counts")
+    counts matches per pattern, "lines" = one that also splits at a delimiter, lists the matching documents and gathers
+    their bytes."""
+    ops = S.plan(seed, words=family == "words", counts=family == "counts", lines=family == "lines")
     tag = f" ({family})" if family else ""
     with GpuMatcher(0, S.N_SLOTS) as g:
         st = S.run(g, ops, S.Model(), seed=f"{seed}{tag}" if family else seed)
     print(f"session {seed}{tag}: {st['ops']} operations ({st['errors']} documented errors), {st['compared']} records and bytes compared, "
           f"record widths {sorted(st['widths'])}, staging {sorted(st['staging'])}, {sorted(st['variants'])}, {st['counts']} counts under "
-          f"{sorted(st['regimes'])}")
+          f"{sorted(st['regimes'])}, {st['splits']} splits, {st['matchings']} matching calls, {st['gathers']} gathers, {st['ids']} document ids "
+          f"and offsets compared")
 
 
 def test_large_dense_then_tiny_sparse_then_every_pass():
@@ -251,7 +257,8 @@ def test_scan_finish_keeps_the_copy_queued_after_scan_async():
 
 def test_fill_then_partial_h2d_into_the_same_buffer():
     """fill_random of a 1 GiB slot input, then 4 KiB of known bytes into its last tile: the fills return once the slot's
-    stream is idle, so the copy -- which is ordered after the slot's last SCAN only -- cannot be overtaken by the fill.
+    stream is idle, so the copy -- which is ordered behind what the slot's stream has queued when pfac_slot_h2d is called,
+    and a fill on another stream would not be -- cannot be overtaken by the fill.
     The tile is read back through a scan with no match and a replace without picks, which copies its input."""
     t, n = "abc2", 1 << 30
     rng = np.random.default_rng(5)
@@ -279,6 +286,110 @@ def test_fill_then_partial_h2d_into_the_same_buffer():
         assert n_before == int((want == ord("a")).sum())
         if n_before == 0:
             np.testing.assert_array_equal(g.replacement_to_host(m), want)
+
+
+# The input's readers and the next upload.  Three passes return to the host as soon as a count is known and read the slot's
+# input AGAIN from a kernel queued behind that: the write kernels of the replace, of the split and of the gather.  The next
+# chunk's pfac_slot_h2d into the same slot must wait for them (include/pfac.h), not for the slot's last scan only.  1 GiB of
+# input makes the write kernel long enough for a 4 KiB copy to overtake it where the order is missing; every expectation is
+# analytic or a window of splitmix64, so no host array is larger than a few KiB.  A wrong byte, never a fault.
+UP_N, UP_TAIL = 1 << 30, 4096
+
+
+def _random_window(first, n, seed):
+    """Bytes [first, first + n) of what fill_random(.., seed) writes (first a multiple of 8)."""
+    assert first % 8 == 0
+    return splitmix64_bytes(n, seed + first // 8)
+
+
+def _upload_over_the_tail(g, original_tail):
+    """The next chunk's upload, at once: 4 KiB into the end of the slot's input, every byte different from what is there."""
+    assert original_tail.size == UP_TAIL
+    g.h2d(original_tail ^ np.uint8(0xFF), 0, dst_offset=UP_N - UP_TAIL)
+
+
+def test_upload_waits_for_the_replace_that_reads_the_input():
+    """Tiled bytes outside the table's alphabet: no match, so the replace's output is its input.  The upload of other
+    bytes over the input's last 4 KiB right behind the replace must not show in the output's last 8 KiB."""
+    t = "abc2"
+    period = bytes(range(0x20, 0x20 + 61))                      # (61 bytes, none of them a, b or c: a period that is no divisor of the tile)
+    assert not set(period) & set(b"abc")
+    want = tiled_bytes(2 * UP_TAIL, period, phase=(UP_N - 2 * UP_TAIL) % len(period))
+    with GpuMatcher(0, 1) as g:
+        g.load_table(X.table(t))
+        g.set_final_lengths(X.table(t).final_lengths())
+        g.set_replacements(X.reps(t, "r0"))
+        g.reserve(0, UP_N, 1 << 20)
+        g.fill_tiled(g.input_ptr(0), UP_N, period)
+        g.scan_async(UP_N, UP_N, slot=0)
+        assert g.scan_finish(0) == (0, False)
+        assert g.select_leftmost_longest(0) == (0, 0)
+        assert g.replace_selection() == UP_N
+        _upload_over_the_tail(g, want[UP_TAIL:])
+        got = g.replacement_to_host(2 * UP_TAIL, first=UP_N - 2 * UP_TAIL)
+        g.sync(0)
+    bad = np.flatnonzero(got != want)
+    print(f"replace, then the upload: {bad.size} of {got.size} bytes of the output's tail are not the original's")
+    assert bad.size == 0, f"{bad.size} bytes of the output come from the NEXT upload, the first at {UP_N - 2 * UP_TAIL + int(bad[0])}"
+
+
+@pytest.mark.parametrize("order", ["ascending", "reversed"])
+def test_upload_waits_for_the_gather_that_reads_the_input(order):
+    """1024 documents of 1 MiB cut by the caller's offsets, ids 0..1023 or 1023..0, over fill_random's bytes: ascending
+    the output is the input; reversed its first MiB is the input's last document, which the upload goes into, and its
+    last is document 0."""
+    import torch
+    seed, n_docs = 0x51DE, 1024
+    size = UP_N // n_docs
+    to_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint64).view(np.int64).copy()).to("cuda:0")      # noqa: E731
+    d_off = to_dev(np.arange(n_docs + 1, dtype=np.uint64) * np.uint64(size))
+    ids = np.arange(n_docs, dtype=np.uint64)
+    d_ids = to_dev(ids if order == "ascending" else ids[::-1])
+    torch.cuda.synchronize()
+    in_tail = _random_window(UP_N - 2 * UP_TAIL, 2 * UP_TAIL, seed)
+    doc0_tail = _random_window(size - 2 * UP_TAIL, 2 * UP_TAIL, seed)
+    with GpuMatcher(0, 1) as g:
+        g.reserve(0, UP_N, 4096)
+        g.fill_random(g.input_ptr(0), UP_N, seed)
+        assert g.gather_documents(n_docs, n_docs, UP_N, d_doc_offsets=d_off.data_ptr(), d_ids=d_ids.data_ptr()) == UP_N
+        _upload_over_the_tail(g, in_tail[UP_TAIL:])
+        # where the input's last 8 KiB and document 0's last 8 KiB are in the output
+        at_in, at_doc0 = (UP_N - 2 * UP_TAIL, size - 2 * UP_TAIL) if order == "ascending" else (size - 2 * UP_TAIL, UP_N - 2 * UP_TAIL)
+        got_in = g.gathered_to_host(2 * UP_TAIL, first=at_in)
+        got_doc0 = g.gathered_to_host(2 * UP_TAIL, first=at_doc0)
+        got_off = g.gathered_offsets_to_host(n_docs)
+        g.sync(0)
+    bad = np.flatnonzero(got_in != in_tail)
+    print(f"gather ({order}), then the upload: {bad.size} of {got_in.size} bytes of the input's tail in the output are not the original's")
+    np.testing.assert_array_equal(got_off, np.arange(n_docs + 1, dtype=np.uint64) * np.uint64(size))
+    np.testing.assert_array_equal(got_doc0, doc0_tail)
+    assert bad.size == 0, f"{bad.size} bytes of the output come from the NEXT upload, the first at {at_in + int(bad[0])}"
+
+
+def test_upload_waits_for_the_split_that_reads_the_input():
+    """One delimiter per period of 509 bytes: document k starts at 509 k and the rest behind the last delimiter is an
+    unterminated tail.  The split's second read of the input places the offsets; the upload right behind the call holds no
+    delimiter, so offsets of the last two tiles that are wrong or missing show that it came first."""
+    P, delim = 509, 0x0A
+    period = bytes([0x41 + k % 26 for k in range(P - 1)]) + bytes([delim])
+    full = UP_N // P
+    assert UP_N % P and (UP_N - 2 * TILE_BYTES) // P < full - 8
+    k = 2 * TILE_BYTES // P + 4                                # the offsets fetched: every delimiter of the last two tiles, and more
+    want = np.concatenate([np.arange(full + 1 - (k - 1), full + 1, dtype=np.uint64) * np.uint64(P), np.array([UP_N], dtype=np.uint64)])
+    tail = tiled_bytes(UP_TAIL, period, phase=(UP_N - UP_TAIL) % P)
+    with GpuMatcher(0, 1) as g:
+        g.reserve(0, UP_N, 4096)
+        g.fill_tiled(g.input_ptr(0), UP_N, period)
+        n_docs, tail_start = g.split_documents(UP_N, bytes([delim]))
+        up = tail ^ np.uint8(0xFF)
+        assert not (up == delim).any()
+        g.h2d(up, 0, dst_offset=UP_N - UP_TAIL)
+        got = g.doc_offsets_to_host(n_docs, first=max(n_docs + 1 - k, 0), n=k)
+        g.sync(0)
+    assert (n_docs, tail_start) == (full + 1, full * P)
+    bad = np.flatnonzero(got != want)
+    print(f"split, then the upload: {bad.size} of the last {k} offsets are not the original's")
+    assert bad.size == 0, f"offset {n_docs + 1 - k + int(bad[0])} is {int(got[bad[0]])}, not {int(want[bad[0]])}"
 
 
 def test_stream_change_between_a_selection_and_its_replace():
@@ -575,3 +686,132 @@ def test_same_table_uploaded_twice_is_a_new_generation():
     ops = load(t) + [scan(t, 0), cnt(), cnt(dst="caller")] + load(t) + [cnt_fetch(), cnt(acc=True), scan(t, 1), cnt(acc=True), cnt(dst="caller", acc=True),
                                                                         cnt_fetch(), cnt_sel(acc=True), cnt(), cnt(acc=True), cnt_fetch()]
     run(ops, want=[0] * 3 + [0, 0, 0] + [0] * 3 + [0, E, 0, E, 0, 0, E, 0, 0, 0])
+
+
+# ---------------------------------------------------------------------------
+# the line path as calls on a long-lived context: split, matching documents, context lines, gather
+
+def spl(tab, inp, slot=0, nb=None, which=0, src="slot", delim=None):
+    """A split of input `inp`; which: 0 = at its most frequent byte, 1 = at its rarest, 2 = at a byte that does not occur."""
+    return dict(op="split", slot=slot, src=src, tab=tab, inp=inp, nb=X.input_size(tab, inp) if nb is None else nb,
+                delim=X.delims(tab, inp)[which] if delim is None else delim)
+
+
+def mat(slot=0, first="own", out="own", flags=0, ctx=None, nd="ok"):
+    return dict(S._matching_op(slot, first=first, out=out, flags=flags, context=ctx), nd=nd)
+
+
+def gat(tab, inp, slot=0, nb=None, **kw):
+    op = dict(op="gather", slot=slot, src="slot", tab=tab, inp=inp, nb=X.input_size(tab, inp) if nb is None else nb, off="slot", nd="ok", ids="own",
+              ni="ok", out="own", oo="own")
+    op.update(kw)
+    return op
+
+
+def whole(ops):
+    """The operations with every doc_fetch / ga_fetch that has no window yet asking for all there is at that point."""
+    m, out = S.Model(), []
+    for op in ops:
+        s = m.slots[op.get("slot", 0)]
+        if op["op"] == "doc_fetch" and "n" not in op:
+            op = dict(op, first=0, n=int(X.offsets(*s.doc).size))
+        if op["op"] == "ga_fetch" and "n" not in op:
+            op = dict(op, first=0, n=int(X.gather(*s.ga[0])[0].size))
+        m.apply(op)
+        out.append(op)
+    return out
+
+
+def test_large_lines_then_tiny_lines():
+    """Split and gather of the largest pool input at its most frequent byte, then of a 17-byte input, then matching,
+    context and gather: the per-tile arrays, group sums, offsets, ids and outputs are sized by the large call, and nothing
+    of it may show in the small one."""
+    big, t = "mid4", "abc2"
+    ops = load(big) + [scan(big, 0), spl(big, 0), fetch("doc_fetch"), pss("segment"), mat(), gat(big, 0), fetch("ga_fetch"), fetch("gaoff_fetch")]
+    ops += load(t) + [scan(t, 3), spl(t, 3), fetch("doc_fetch"), gat(t, 3, ids="all"), fetch("ga_fetch"), fetch("gaoff_fetch"), pss("segment"), mat(),
+                      fetch("ids_fetch"), mat(ctx=(1, 1)), fetch("ids_fetch"), gat(t, 3), fetch("ga_fetch"), fetch("gaoff_fetch"),
+                      mat(flags=1, out="caller"), gat(t, 3, ids="rev", out="caller", oo="caller"), spl(t, 3, which=2), fetch("doc_fetch")]
+    ops = whole(ops)
+    st = run(ops, want=[S.OK] * len(ops))
+    print(f"large lines, then tiny ones: {st['compared']} bytes and {st['ids']} document ids and offsets compared")
+    assert st["splits"] == 3 and st["gathers"] == 4 and st["compared"] > 2_000_000
+
+
+def test_slot_buffers_regrow_behind_a_queued_gather():
+    """A gather with everything slot-owned returns before its bytes are written; the very next call makes the slot's
+    offsets buffer (set_doc with more documents, then a split into many), or its ids (a matching call over many more
+    documents), outgrow their allocation.  The gather's output, fetched afterwards, is that of the old offsets and ids."""
+    t = "abc2"
+    first = [scan(t, 0), spl(t, 0, which=2), pss("segment"), mat(flags=1), gat(t, 0)]             # one document without a delimiter, reported by invert
+    late = [fetch("ga_fetch"), fetch("gaoff_fetch")]
+    ops = load(t) + first + [doc(t, 0, "d1")] + late
+    ops += [spl(t, 0, which=2), gat(t, 0, ids="all"), spl(t, 0)] + late + [fetch("doc_fetch")]
+    ops += [doc(t, 0, "d0"), pss("segment"), mat(), gat(t, 0), spl(t, 0), pss("segment"), mat(ctx=(1, 1))] + late + [fetch("ids_fetch"), gat(t, 0)] + late
+    ops = whole(ops)
+    st = run(ops, want=[S.OK] * len(ops))
+    assert st["gathers"] == 4
+
+
+def test_stream_change_between_matching_and_its_gather():
+    """The ids of a matching call are written asynchronously on the slot's stream; set_stream moves the slot to another
+    stream, where the gather reads them through NULL.  The line-path twin of the selection and its replace above."""
+    t = "mid4"
+    ops = load(t) + [scan(t, 0, slot=1), spl(t, 0, slot=1), pss("segment", slot=1)]
+    for rnd in range(6):
+        ops += [mat(slot=1, flags=rnd % 2) if rnd % 3 else mat(slot=1, ctx=(rnd, 1)), dict(op="set_stream", slot=1, share=rnd % 2 == 0),
+                gat(t, 0, slot=1), fetch("ga_fetch", slot=1), fetch("gaoff_fetch", slot=1)]
+    ops = whole(ops)
+    run(ops, want=[S.OK] * len(ops))
+
+
+def test_matching_and_context_are_one_pass():
+    """The two calls share one id buffer and one fetch: each replaces the other's ids, a refused call of either discards
+    them, ids that went to the caller cannot be fetched, and an overflow carries the exact count."""
+    t = "abc2"
+    E, A, V = S.E_STATE, S.E_ARG, S.E_OVERFLOW
+    ops = load(t) + [scan(t, 2), doc(t, 2, "d0"), pss("segment"),
+                     mat(), fetch("ids_fetch"), mat(ctx=(1, 0)), fetch("ids_fetch"), mat(flags=1), fetch("ids_fetch"),
+                     mat(flags=2), fetch("ids_fetch"), mat(ctx=(0, 1)), mat(ctx=(0, 1), flags=1), fetch("ids_fetch"),
+                     mat(), mat(ctx=(2, 3), out="small"), fetch("ids_fetch"), mat(ctx=(S.U64_MAX, 0)), mat(nd="plus"), fetch("ids_fetch"),
+                     mat(out="caller"), fetch("ids_fetch"), mat(ctx=(0, 0), out="caller"), fetch("ids_fetch"), mat(ctx=(0, 0)), fetch("ids_fetch"),
+                     mat(out="odd"), gat(t, 2), mat(flags=1), gat(t, 2), fetch("ga_fetch"), fetch("gaoff_fetch")]
+    ops = whole(ops)
+    run(ops, want=[0] * 3 + [0, 0, 0] + [0, 0, 0, 0, 0, 0] + [A, E, 0, A, E] + [0, V, E, 0, A, E] + [0, E, 0, E, 0, 0] + [A, E, 0, 0, 0, 0])
+
+
+def test_a_chunked_reader_carries_the_tail_over():
+    """tail_start is what a chunked reader carries over: three chunks of one pool input cut at arbitrary places, each
+    uploaded behind the unterminated rest of the one before, split, and its complete lines gathered.  The offsets and the
+    gathered bytes of the chunks, put together, are those of one split of the whole input (splitref, gatherref)."""
+    import torch
+    from gatherref import gather_ref
+    from splitref import split_offsets
+    t = "abc2"
+    data = X.input(t, 0)
+    delim = X.delims(t, 0)[1]
+    want_off, want_docs, want_tail = split_offsets(data, delim)
+    assert want_docs > 64 * 64 and want_tail != data.size, "the input must end in an unterminated line"
+    cuts = [0, 100_003, 100_003 + 131_072 + 5, data.size]
+    offsets, pieces, carry, base = [np.zeros(1, np.uint64)], [], data[:0], 0
+    with GpuMatcher(0, 1) as g:
+        g.reserve(0, data.size, 4096)
+        for a, b in zip(cuts[:-1], cuts[1:]):
+            buf = np.concatenate([carry, data[a:b]])
+            g.h2d(buf, 0)
+            n_docs, tail = g.split_documents(buf.size, delim)
+            last = b == data.size
+            n_lines = n_docs if last or tail == buf.size else n_docs - 1      # the unterminated rest waits for the next chunk
+            off = g.doc_offsets_to_host(n_docs)
+            ids = torch.arange(max(n_lines, 1), dtype=torch.int64, device="cuda:0")
+            torch.cuda.synchronize()
+            n = g.gather_documents(n_docs, n_lines, buf.size, d_ids=ids.data_ptr())
+            pieces.append(g.gathered_to_host(n))
+            assert n == int(off[n_lines])
+            offsets.append(off[1:n_lines + 1] + np.uint64(base))
+            carry = buf[int(off[n_lines]):].copy()
+            assert last or carry.size == buf.size - tail
+            base += int(off[n_lines])
+            g.sync(0)
+    np.testing.assert_array_equal(np.concatenate(offsets), want_off)
+    want, _ = gather_ref(data, want_off, np.arange(want_docs, dtype=np.uint64))
+    np.testing.assert_array_equal(np.concatenate(pieces), want)

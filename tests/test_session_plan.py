@@ -5,7 +5,10 @@ contract of include/pfac.h in the most obvious way; and each of CpuDevice's swit
 after the first operation the defect touches -- the harness has teeth without a kernel being mutated.  The plans come in
 two families: those of S.SEEDS, pinned by a digest to what they were before the whole-word filter existed, and those of
 S.WORD_SEEDS, in which the filter is an operation like any other, pinned likewise since the counts joined; and those
-of S.COUNT_SEEDS, which add the per-pattern counts (count, count_sel, cnt_fetch) under the count knobs of S.CKNOBS."""
+of S.COUNT_SEEDS, which add the per-pattern counts (count, count_sel, cnt_fetch) under the count knobs of S.CKNOBS,
+pinned likewise since the line path joined; and those of S.LINE_SEEDS, which add the delimiter split, the matching
+documents with and without context lines and the gather of their bytes (S.LINE_OPS), and have their own reach test,
+their own defects (LINE_DEFECTS) and a digest of their own."""
 import collections
 import copy
 import hashlib
@@ -58,6 +61,9 @@ class _CpuSlot:
         self.heap = CpuBuf(16)     # stands for the slot's own record heap where a pointer is compared
         self.last_n = 0
         self.cnt = None            # the slot-owned counts: dict(gen, a)
+        self.dm = None             # the ids of the last matching call: dict(ids, own)
+        self.dm_before = None      # ... and of the one before it
+        self.ga = None             # the last gather: dict(out, off, own_out, own_off)
 
 
 DEFECTS = ("stale_selection_survives_upload", "late_segment_returns_selection", "smaller_scan_returns_tail",
@@ -73,6 +79,14 @@ COUNT_DEFECTS = ("accumulate_zeroes_first", "plain_count_does_not_zero", "counts
                  "refused_count_zeroes_its_destination", "caller_count_replaces_the_slots_counts", "counts_lost_at_upload",
                  "counts_lost_at_reserve", "accumulate_across_upload_allowed", "stale_selection_still_counted",
                  "docsel_counted_as_whole_stream", "slots_share_one_count_buffer", "count_disturbs_the_selection")
+
+
+# ... and those of the line path, which only the plans of S.LINE_SEEDS can meet
+LINE_DEFECTS = ("failed_split_clears_the_offsets", "split_keeps_the_offsets_generation", "failed_matching_keeps_the_ids",
+                "context_and_matching_keep_separate_ids", "matching_null_first_is_the_selections", "matching_follows_a_segment_to_the_caller",
+                "gather_uses_the_count_before_last", "gather_writes_offsets_on_an_error", "gather_lost_at_upload", "gather_lost_at_reserve",
+                "ids_lost_at_a_new_scan", "slot1_gather_reads_slot0s_offsets", "unterminated_tail_offset_dropped",
+                "gather_reads_the_input_of_the_last_scan")
 
 
 class CpuDevice:
@@ -127,6 +141,8 @@ class CpuDevice:
         for s in self.slots:
             if s.cnt is not None and s.cnt["a"].any() and self._defect("counts_lost_at_upload"):
                 s.cnt = None
+            if s.ga is not None and (s.ga["own_out"] or s.ga["own_off"]) and self._defect("gather_lost_at_upload"):
+                s.ga = None
 
     def info(self):
         return {"variant": "cpu", "staging_buffers": 0, "staging_records": 0}
@@ -154,6 +170,8 @@ class CpuDevice:
             s.scan = None                                       # a buffer is replaced: no finished scan
             if s.cnt is not None and self._defect("counts_lost_at_reserve"):
                 s.cnt = None
+            if s.ga is not None and (s.ga["own_out"] or s.ga["own_off"]) and self._defect("gather_lost_at_reserve"):
+                s.ga = None
         if input_bytes > s.in_cap:
             s.in_cap = (input_bytes + 4095) // 4096 * 4096 + 1280
         s.rec_cap = max(s.rec_cap, record_capacity)
@@ -187,6 +205,8 @@ class CpuDevice:
         pos, ids, lens = self.x.scan(self.tab, inp, n_owned)
         cap = capacity if d_records is not None else s.rec_cap
         prev = s.scan
+        if s.dm is not None and s.dm["own"] and self._defect("ids_lost_at_a_new_scan"):
+            s.dm = None
         s.seq += 1
         s.scan = dict(tab=self.tab, width=self.width, gen=self.gen, data=self.x.input(self.tab, inp), no=n_owned, pos=pos, ids=ids, lens=lens,
                       over=pos.size > cap, pending=True, seq=s.seq, prev=(prev["pos"], prev["ids"]) if prev else None,
@@ -425,6 +445,168 @@ class CpuDevice:
         keep = sc["pos"] + sc["lens"] <= off[doc + 1]
         return off, doc[keep], sc["pos"][keep], sc["ids"][keep], sc["lens"][keep]
 
+    # -- lines: split, matching documents, gather -------------------------------
+    def _input(self, slot, d_input, n_bytes, what):
+        """The bytes a call reads: the slot's input (d_input None) or a caller's buffer."""
+        s = self.slots[slot]
+        if isinstance(d_input, S.Odd):
+            raise _err(S.E_ARG, what + ": misaligned d_input")
+        if d_input is not None:
+            return d_input.src
+        if n_bytes > s.in_cap:
+            raise _err(S.E_ARG, what + ": n_bytes exceeds the slot's input buffer")
+        return s.data if s.data is not None else np.zeros(0, np.uint8)
+
+    def split_documents(self, n_bytes, delimiter=b"\n", d_input=None, slot=0):
+        s = self.slots[slot]
+        try:
+            delim = delimiter[0] if isinstance(delimiter, (bytes, bytearray)) else int(delimiter)
+            if not 0 <= delim <= 255:
+                raise _err(S.E_ARG, "the delimiter is one byte")
+            data = self._input(slot, d_input, n_bytes, "split")[:n_bytes]
+        except PfacError:
+            if s.doc is not None and self._defect("failed_split_clears_the_offsets"):
+                s.doc = None
+            raise
+        ends = [i + 1 for i, b in enumerate(data.tobytes()) if b == delim]
+        off = [0] + ends + ([n_bytes] if n_bytes and (not ends or ends[-1] != n_bytes) else [])
+        tail = n_bytes if not n_bytes or (ends and ends[-1] == n_bytes) else (ends[-1] if ends else 0)
+        if len(off) >= 3 and tail != n_bytes and self._defect("unterminated_tail_offset_dropped"):
+            off = off[:-1]
+        s.doc = np.array(off, dtype=np.uint64)
+        if not (s.sel is not None and s.sel["kind"] == "docs" and self._defect("split_keeps_the_offsets_generation")):
+            s.doc_gen += 1
+        return len(off) - 1, tail
+
+    def doc_offsets_to_host(self, n_docs, slot=0, first=0, n=None):
+        s = self.slots[slot]
+        if s.doc is None:
+            raise _err(S.E_STATE, "the slot holds no document offsets")
+        n = int(n_docs) + 1 - first if n is None else n
+        if first + n > s.doc.size:
+            raise _err(S.E_ARG, "beyond the offsets")
+        return s.doc[first:first + n].copy()
+
+    def raw_matching(self, slot, context, d_first, n_docs, before, after, flags, d_out, out_cap):
+        s = self.slots[slot]
+        old, s.dm = s.dm, None
+        try:
+            return self._matching(s, old, context, d_first, n_docs, before, after, flags, d_out, out_cap)
+        except PfacError:
+            if old is not None and old["own"] and self._defect("failed_matching_keeps_the_ids"):
+                s.dm = old
+            raise
+
+    def _matching(self, s, old, context, d_first, n_docs, before, after, flags, d_out, out_cap):
+        if d_first is None:
+            seg = s.seg
+            if seg is not None and not seg["own"] and self._defect("matching_follows_a_segment_to_the_caller"):
+                first = seg["first"]
+            elif seg is None or not seg["own"]:
+                raise _err(S.E_STATE, "the slot holds no doc_first of a segment")
+            else:
+                first = seg["first"]
+                sel = s.sel
+                if (sel is not None and sel["kind"] == "docs" and sel["first"].size == first.size
+                        and not np.array_equal(np.diff(sel["first"].astype(np.int64)) > 0, np.diff(first.astype(np.int64)) > 0)
+                        and self._defect("matching_null_first_is_the_selections")):
+                    first = sel["first"]
+            if n_docs != first.size - 1:
+                raise _err(S.E_ARG, "n_docs differs from the segment's")
+        else:
+            first = d_first.a[:(n_docs + 1) * 8].view(np.uint64)
+        if flags > 1 or (context and flags) or isinstance(d_out, S.Odd):
+            raise _err(S.E_ARG, "flags or a misaligned d_ids_out")
+        has = [int(first[d + 1]) > int(first[d]) for d in range(n_docs)]
+        if context:                                             # (matching documents before d, so that a window costs two lookups)
+            seen = [0]
+            for h in has:
+                seen.append(seen[-1] + h)
+            ids = [d for d in range(n_docs) if seen[min(d + min(before, n_docs), n_docs - 1) + 1] > seen[max(d - min(after, n_docs), 0)]]
+        else:
+            ids = [d for d in range(n_docs) if has[d] != bool(flags)]
+        ids = np.array(ids, dtype=np.uint64)
+        if d_out is not None and ids.size > out_cap:
+            raise _err(S.E_OVERFLOW, "out_cap too small", n_matching=int(ids.size))
+        if d_out is not None:
+            d_out.put(ids)
+        s.dm_before = old
+        s.dm = dict(ids=ids, own=d_out is None, context=context)
+        if (d_out is None and old is not None and old["own"] and old["context"] != context and not np.array_equal(old["ids"], ids)
+                and self._defect("context_and_matching_keep_separate_ids")):
+            s.dm = dict(old, kept=True)                           # (the fetch and the gather go on reading the other call's buffer)
+        return int(ids.size)
+
+    def matching_documents(self, n_docs, invert=False, d_doc_first=None, d_out=None, out_cap=0, slot=0, before=0, after=0):
+        return self.raw_matching(slot, bool(before or after), d_doc_first, n_docs, before, after, int(invert), d_out, out_cap)
+
+    def matching_documents_to_host(self, n, slot=0):
+        s = self.slots[slot]
+        if s.dm is None or not s.dm["own"]:
+            raise _err(S.E_STATE, "no slot-owned ids")
+        return s.dm["ids"].copy()
+
+    def gather_documents(self, n_docs, n_ids, n_bytes, d_input=None, d_doc_offsets=None, d_ids=None, d_out=None, out_cap=0, d_out_offsets=None,
+                         slot=0):
+        s = self.slots[slot]
+        s.ga = None
+        data = self._input(slot, d_input, n_bytes, "gather")
+        sc = s.scan
+        if d_input is None and sc is not None and sc["data"] is not data and sc["data"].size >= n_bytes and self._defect("gather_reads_the_input_of_the_last_scan"):
+            data = sc["data"]
+        if d_doc_offsets is None:
+            ds = self.slots[0] if slot == 1 and self.slots[0].doc is not None and self._defect("slot1_gather_reads_slot0s_offsets") else s
+            if ds.doc is None or n_docs != ds.doc.size - 1:
+                raise _err(S.E_STATE, "the slot has no document offsets for this n_docs")
+            off = ds.doc
+        else:
+            off = d_doc_offsets.src
+        if d_ids is None:
+            if s.dm is None or not s.dm["own"]:
+                raise _err(S.E_STATE, "the slot holds no ids")
+            count = s.dm["ids"].size
+            if s.dm_before is not None and s.dm_before["ids"].size != count and self._defect("gather_uses_the_count_before_last"):
+                count = s.dm_before["ids"].size
+            if n_ids != count:
+                raise _err(S.E_ARG, "n_ids differs from the last matching call's count")
+            ids = s.dm["ids"]
+        else:
+            ids = d_ids.src
+        if isinstance(d_out, S.Odd):
+            raise _err(S.E_ARG, "misaligned d_out")
+        pieces, out_off = [], [0]
+        for k in ids.tolist():
+            if k >= n_docs or not int(off[k]) <= int(off[k + 1]) <= n_bytes:
+                if d_out_offsets is not None and self._defect("gather_writes_offsets_on_an_error"):
+                    d_out_offsets.put(np.array(out_off, dtype=np.uint64))
+                raise _err(S.E_ARG, "an id beyond n_docs, or a selected document whose offsets break the rules")
+            pieces.append(data[int(off[k]):int(off[k + 1])])
+            out_off.append(out_off[-1] + pieces[-1].size)
+        out = np.concatenate(pieces) if pieces else np.zeros(0, np.uint8)
+        out_off = np.array(out_off, dtype=np.uint64)
+        if d_out is not None and out.size > out_cap:
+            raise _err(S.E_OVERFLOW, "out_cap too small", out_bytes=int(out.size))
+        if d_out is not None:
+            d_out.put(out)
+        if d_out_offsets is not None:
+            d_out_offsets.put(out_off)
+        s.ga = dict(out=out, off=out_off, own_out=d_out is None, own_off=d_out_offsets is None)
+        return int(out.size)
+
+    def gathered_to_host(self, n, slot=0, first=0):
+        s = self.slots[slot]
+        if s.ga is None or not s.ga["own_out"]:
+            raise _err(S.E_STATE, "no slot-owned gather output")
+        if first + n > s.ga["out"].size:
+            raise _err(S.E_ARG, "beyond the output")
+        return s.ga["out"][first:first + n].copy()
+
+    def gathered_offsets_to_host(self, n_ids, slot=0):
+        s = self.slots[slot]
+        if s.ga is None or not s.ga["own_off"]:
+            raise _err(S.E_STATE, "no slot-owned output offsets")
+        return s.ga["off"].copy()
+
     # -- the whole-word filter ------------------------------------------------
     def filter_whole_words(self, slot=0, word_bytes=None, edges="both", prev_byte=-1, next_byte=-1, n_docs=0, d_doc_offsets=None,
                            d_input=None, d_records=None):
@@ -649,6 +831,11 @@ def test_the_plans_without_the_filter_are_what_they_were(plans):
     assert not any(op["op"] == "filter" for ops in plans.values() for op in ops)
 
 
+@pytest.fixture(scope="module")
+def line_plans():
+    return {seed: S.plan(seed, lines=True) for seed in S.LINE_SEEDS}
+
+
 # ... and of json.dumps([plan(seed, words=True) for seed in WORD_SEEDS], sort_keys=True) at the commit before the counts
 # joined the harness: the second family has not moved either.
 WORD_PLANS_SHA256 = "5cbdcad3040302c5db5d67f19c7157018a74c11ca9fbfca3e56f190d3e672657"
@@ -659,6 +846,17 @@ def test_the_plans_with_the_filter_are_what_they_were(word_plans):
     assert [seed for seed in word_plans] == S.WORD_SEEDS and len(S.WORD_SEEDS) == 24
     assert hashlib.sha256(json.dumps([word_plans[seed] for seed in S.WORD_SEEDS], sort_keys=True).encode()).hexdigest() == WORD_PLANS_SHA256
     assert not any(op["op"] in COUNT_OPS or "cknob" in op for ops in word_plans.values() for op in ops)
+
+
+# ... and of json.dumps([plan(seed, counts=True) for seed in COUNT_SEEDS], sort_keys=True) at the commit before the line path
+# joined the harness: the third family has not moved either.
+COUNT_PLANS_SHA256 = "70c235477764f42868f257baa0e6032d0772d3b0cc86025bd3d64149ad34018a"
+
+
+def test_the_plans_with_the_counts_are_what_they_were(count_plans):
+    assert [seed for seed in count_plans] == S.COUNT_SEEDS and len(S.COUNT_SEEDS) == 24
+    assert hashlib.sha256(json.dumps([count_plans[seed] for seed in S.COUNT_SEEDS], sort_keys=True).encode()).hexdigest() == COUNT_PLANS_SHA256
+    assert not any(op["op"] in S.LINE_OPS for ops in count_plans.values() for op in ops)
 
 
 def test_plans_are_deterministic_and_well_formed(plans, word_plans):
@@ -1078,5 +1276,236 @@ def test_shrink_keeps_a_count_failure(count_plans):
             with pytest.raises(AssertionError):
                 S.run(CpuDevice([defect]), S.shrink(seed, failed + 1, counts=True), S.Model(), seed=seed)
             S.run(CpuDevice([defect]), S.shrink(seed, failed, counts=True), S.Model(), seed=seed)
+            return
+    raise AssertionError("no plan to shrink")
+
+
+# ---------------------------------------------------------------------------
+# the fourth family: the line path (split, matching documents, context lines, gather)
+
+# SHA-256 of json.dumps([plan(seed, lines=True) for seed in LINE_SEEDS], sort_keys=True): the line plans are pinned too, so
+# that a later family, or a change to the planner, cannot move them unnoticed.
+LINE_PLANS_SHA256 = "6ed0d24f240ed2d015f4c4cd11eadae22bbe72f6e6aa636af66fee9a15bb946a"
+
+
+def test_the_plans_with_the_line_path_are_pinned(line_plans):
+    assert [seed for seed in line_plans] == S.LINE_SEEDS and len(S.LINE_SEEDS) == 24
+    assert hashlib.sha256(json.dumps([line_plans[seed] for seed in S.LINE_SEEDS], sort_keys=True).encode()).hexdigest() == LINE_PLANS_SHA256
+
+
+def test_line_plans_are_deterministic_and_well_formed(line_plans, count_plans):
+    for seed in S.LINE_SEEDS[:3]:
+        assert S.plan(seed, lines=True) == line_plans[seed] != count_plans[seed]
+        assert S.shrink(seed, 23, lines=True) == line_plans[seed][:23]
+    assert line_plans[0] != line_plans[1]
+    for seed, ops in line_plans.items():
+        assert len(ops) == S.LINE_PLAN_OPS
+        m = S.Model()
+        for k, op in enumerate(ops):
+            assert hasattr(S.Executor, "do_" + op["op"]), f"seed {seed} op {k}: the executor cannot perform {S.fmt(op)}"
+            st = m.apply(op).status
+            assert st in (S.OK, S.E_ARG, S.E_STATE, S.E_OVERFLOW), f"seed {seed} op {k}: the contract does not decide {S.fmt(op)}"
+
+
+def test_line_plans_are_the_same_in_another_process(line_plans):
+    seeds = S.LINE_SEEDS[:3]
+    code = ("import hashlib, json, session as S; print(hashlib.sha256(json.dumps([S.plan(s, lines=True) for s in %r], sort_keys=True).encode()).hexdigest())" % seeds)
+    here = os.path.dirname(os.path.abspath(__file__))
+    env = dict(os.environ, PYTHONHASHSEED="54321", PYTHONPATH=os.pathsep.join([here, os.path.dirname(here)]))
+    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, check=True, timeout=300).stdout.split()[-1]
+    assert out == hashlib.sha256(json.dumps([line_plans[s] for s in seeds], sort_keys=True).encode()).hexdigest()
+
+
+LINE_STATUSES = {"split": {S.OK, S.E_ARG}, "doc_fetch": {S.OK, S.E_STATE, S.E_ARG}, "matching": {S.OK, S.E_ARG, S.E_STATE, S.E_OVERFLOW},
+                 "context": {S.OK, S.E_ARG, S.E_STATE, S.E_OVERFLOW}, "ids_fetch": {S.OK, S.E_STATE},
+                 "gather": {S.OK, S.E_ARG, S.E_STATE, S.E_OVERFLOW}, "ga_fetch": {S.OK, S.E_ARG, S.E_STATE}, "gaoff_fetch": {S.OK, S.E_STATE}}
+
+
+def _between_kind(op, st, was, m):
+    """The name in S.BETWEEN of an operation that succeeded, or None."""
+    kind, slot = op["op"], op.get("slot", 0)
+    if st != S.OK:
+        return None
+    if kind in ("scan_bytes", "scan_ext", "scan_start"):
+        return "scan"
+    if kind == "load_table":
+        return "upload"
+    if kind == "reserve_grow":
+        return "grow"
+    return kind if kind in S.BETWEEN else None
+
+
+def test_line_plans_reach_everything(line_plans):
+    """Conditions, not measurements: over S.LINE_SEEDS every new operation meets every documented status, every argument
+    form, both slots and the shared stream; every (producer, intervening call, late fetch) order occurs; and the splits
+    produce every line shape."""
+    x = S.expectations()
+    kinds, seen, forms, where, orders, shapes, errs = set(), collections.defaultdict(set), set(), set(), set(), set(), set()
+    errors = total = 0
+    since = {}                                                  # (seed, slot, fetch) -> (producer, what has happened on the slot since)
+    for seed, k, op, st, was, m in _walk_models(line_plans):
+        kind, slot = op["op"], op.get("slot", 0)
+        kinds.add(kind)
+        total += 1
+        errors += st != S.OK
+        ws, s = was.slots[slot], m.slots[slot]
+        b = _between_kind(op, st, was, m)
+        for key, (prod, mid) in since.items():
+            if key[0] == seed and b is not None and (kind == "load_table" or key[1] == slot):
+                mid.add(b)
+        if kind in S.LINE_OPS:
+            seen[kind].add(st)
+            where |= {(kind, "slot", slot), (kind, "shared", slot == 1 and ws.shared)}
+        if kind in S.LATE and st == S.OK:
+            own = kind in ("split", "set_doc") or op["out"] == "own"
+            for f in S.LATE[kind]:
+                if own and (f != "gaoff_fetch" or op["oo"] == "own"):
+                    since[(seed, slot, f)] = (kind, set())
+                else:
+                    since.pop((seed, slot, f), None)
+        elif kind in S.LATE or kind in ("matching", "context", "gather"):
+            for f in S.LATE.get(kind, ()):                       # (a refused call of the same pass discards the result)
+                if kind not in ("split", "set_doc"):
+                    since.pop((seed, slot, f), None)
+        if kind in ("doc_fetch", "ids_fetch", "ga_fetch", "gaoff_fetch") and st == S.OK and (seed, slot, kind) in since:
+            prod, mid = since[(seed, slot, kind)]
+            orders |= {(prod, b2, kind) for b2 in mid}
+        # -- the split
+        if kind == "split":
+            sc = ws.scan
+            if st == S.OK:
+                off, nd, tail = x.split(op["tab"], op["inp"], op["nb"], op["delim"])
+                d = x.delims(op["tab"], op["inp"])
+                forms |= {("split", "src", op["src"]), ("split", "delim", "frequent" if op["delim"] == d[0] else "rare" if op["delim"] == d[1] else "absent")}
+                if sc is not None:
+                    forms.add(("split", "nb", "n_owned" if op["nb"] == sc["no"] else "zero" if op["nb"] == 0 else "smaller" if op["nb"] < sc["no"] else "larger"))
+                    forms.add(("split", "pending", sc["pending"]))
+                forms.add(("split", "table", was.tab is not None))
+                lens = np.diff(off.astype(np.int64))
+                if (lens == 1).sum() >= 2 and nd >= 3:
+                    shapes.add("runs of delimiters")
+                if op["nb"] and tail != op["nb"]:
+                    shapes.add("unterminated tail")
+                if op["nb"] and tail == op["nb"]:
+                    shapes.add("terminated last line")
+                if op["nb"] and nd == 1 and tail == 0:
+                    shapes.add("no delimiter")
+                if nd > 64 * 64:
+                    shapes.add("more than 64 x 64 documents")
+                if op["nb"] > 64 * S.TILE:
+                    shapes.add("more than 64 tiles")
+            else:
+                errs.add(("split", "delim %d" % op["delim"] if not 0 <= op["delim"] <= 255 else "over" if op["nb"] == "over" else op["src"]))
+                assert (s.doc, s.doc_gen) == (ws.doc, ws.doc_gen)
+        # -- what the split's offsets do to the document passes
+        if kind in ("segment", "select_docs", "filter") and ws.doc is not None and ws.doc[3].startswith("split:") and ws.scan is not None:
+            if st == S.OK and ws.doc[2] == ws.scan["no"] and (kind != "filter" or S.FILTERS[op["f"]]["doc"] == "slot"):
+                forms.add(("after a split", kind, "NULL offsets"))
+            if st == S.E_ARG and ws.doc[2] != ws.scan["no"] and (kind != "filter" or S.FILTERS[op["f"]]["doc"] == "slot"):
+                errs.add(("after a split of other bytes", kind))
+        if kind == "replace_docs" and st == S.E_STATE and ws.sel is not None and ws.sel["kind"] == "docs" and ws.doc is not None \
+                and ws.doc[3].startswith("split:") and ws.sel["doc_gen"] != ws.doc_gen and ws.scan is not None and ws.sel["seq"] == ws.scan["seq"]:
+            errs.add(("replace_docs", "stale after a split"))
+        if kind == "doc_fetch":
+            if st == S.OK:
+                forms.add(("doc_fetch", "after", "split" if ws.doc[3].startswith("split:") else "set_doc"))
+                forms.add(("doc_fetch", "window", "all" if op["first"] == 0 and op["n"] == x.offsets(*ws.doc).size else "part"))
+        # -- matching and context
+        if kind in ("matching", "context"):
+            if st == S.OK:
+                forms |= {(kind, "first", op["first"]), (kind, "out", op["out"]), (kind, "flags", op["flags"])}
+                if kind == "context":
+                    nd = int(x.doc_first(*s.dm[0][:2]).size) - 1
+                    for v in (op["before"], op["after"]):
+                        forms.add(("context", "window", "0" if v == 0 else "1" if v == 1 else "2^64-1" if v == S.U64_MAX else "> n_docs" if v > nd else "some"))
+            elif st == S.E_OVERFLOW:
+                errs.add((kind, "small"))
+            elif st == S.E_STATE:
+                errs.add((kind, "no slot-owned doc_first" + (" (it went to the caller)" if ws.seg is not None else "")))
+            else:
+                errs.add((kind, "flags %d" % op["flags"] if op["flags"] > (0 if kind == "context" else 1) else "n_docs" if op["nd"] != "ok" else "misaligned"))
+            assert st == S.OK or s.dm is None
+        elif kind not in ("ids_fetch",) and st is not None:
+            assert s.dm == ws.dm, f"seed {seed} op {k}: {kind} dropped the ids"
+        # -- the gather
+        if kind == "gather":
+            if st == S.OK:
+                forms.add(("gather", "args", op["src"] == "slot", op["off"] == "slot", op["ids"] == "own", op["out"] == "own", op["oo"] == "own"))
+                forms.add(("gather", "ids", op["ids"]))
+            elif st == S.E_OVERFLOW:
+                errs.add(("gather", "small"))
+            elif st == S.E_STATE:
+                errs.add(("gather", "n_docs" if op["nd"] != "ok" else "no offsets" if ws.doc is None else
+                          "the ids went to the caller" if ws.dm is not None else "no ids"))
+            else:
+                off = x.offsets(*ws.doc).astype(np.int64) if ws.doc is not None else None
+                errs.add(("gather", "n_ids" if op["ni"] != "ok" else "misaligned input" if op["src"] == "odd" else "misaligned output" if op["out"] == "odd" else
+                          "bad id" if op["ids"] == "bad_id" else "a selected document passes n_bytes" if off is not None and op["nb"] < off[-1] else
+                          "selected offsets"))
+    missing = {"kinds": sorted(set(S.LINE_KINDS) - kinds),
+               "statuses": sorted((k2, S.STATUS_NAMES[v]) for k2 in LINE_STATUSES for v in LINE_STATUSES[k2] - seen[k2])}
+    assert all(seen[k2] <= LINE_STATUSES[k2] for k2 in seen), "a status the header does not document"
+    want = {(k, "slot", sl) for k in S.LINE_OPS for sl in (0, 1)} | {(k, "shared", True) for k in S.LINE_OPS}
+    missing["slots and streams"] = sorted(want - where, key=str)
+    want = {("split", "src", v) for v in ("slot", "caller")} | {("split", "delim", v) for v in ("frequent", "rare", "absent")}
+    want |= {("split", "nb", v) for v in ("n_owned", "smaller", "zero")} | {("split", "pending", True), ("split", "table", False)}
+    want |= {("after a split", k2, "NULL offsets") for k2 in ("segment", "select_docs", "filter")}
+    want |= {("doc_fetch", "after", "split"), ("doc_fetch", "after", "set_doc"), ("doc_fetch", "window", "all"), ("doc_fetch", "window", "part")}
+    want |= {(k2, "first", v) for k2 in ("matching", "context") for v in ("own", "seg", "docsel")}
+    want |= {(k2, "out", v) for k2 in ("matching", "context") for v in ("own", "caller")} | {("matching", "flags", 0), ("matching", "flags", 1)}
+    want |= {("context", "window", v) for v in ("0", "1", "> n_docs", "2^64-1")}
+    want |= {("gather", "args") + tuple(bool(c >> j & 1) for j in range(5)) for c in range(32)}
+    want |= {("gather", "ids", v) for v in S.ID_FORMS if v != "bad_id"}
+    missing["argument forms"] = sorted(want - forms, key=str)
+    want = {("split", v) for v in ("delim 256", "delim -1", "over", "odd")}
+    want |= {("after a split of other bytes", k2) for k2 in ("segment", "select_docs", "filter")} | {("replace_docs", "stale after a split")}
+    want |= {(k2, v) for k2 in ("matching", "context") for v in ("small", "no slot-owned doc_first", "no slot-owned doc_first (it went to the caller)",
+                                                                  "n_docs", "misaligned")}
+    want |= {("matching", "flags 2"), ("context", "flags 1")}
+    want |= {("gather", v) for v in ("small", "n_docs", "no offsets", "the ids went to the caller", "no ids", "n_ids", "misaligned input",
+                                     "misaligned output", "bad id", "a selected document passes n_bytes", "selected offsets")}
+    missing["errors"] = sorted(want - errs)
+    want = {(p, b2, f) for p, fs in S.LATE.items() for f in fs for b2 in S.BETWEEN
+            if b2 not in {"doc_fetch": ("split", "set_doc"), "ids_fetch": ("matching", "context"), "ga_fetch": ("gather",), "gaoff_fetch": ("gather",)}[f]}
+    missing["orders"] = sorted(want - orders)
+    want = {"runs of delimiters", "unterminated tail", "terminated last line", "no delimiter", "more than 64 x 64 documents", "more than 64 tiles"}
+    missing["line shapes"] = sorted(want - shapes)
+    missing = {k2: v for k2, v in missing.items() if v}
+    assert not missing, "the line plans never reach:\n" + "\n".join(f"  {k2}: {v}" for k2, v in missing.items())
+    assert 0.08 < errors / total < 0.25, f"{errors} of {total} operations are illegal"
+
+
+@pytest.mark.parametrize("seed", S.LINE_SEEDS)
+def test_line_plan_passes_on_the_cpu_device(seed, line_plans):
+    stats = S.run(CpuDevice(), line_plans[seed], S.Model(), seed=f"{seed} (lines)")
+    assert stats["ops"] == S.LINE_PLAN_OPS and stats["errors"] > 0 and stats["splits"] + stats["matchings"] + stats["gathers"] > 0
+
+
+@pytest.mark.parametrize("defect", LINE_DEFECTS)
+def test_every_line_defect_is_caught(defect, line_plans):
+    caught = []
+    for seed, ops in line_plans.items():
+        seed = f"{seed} (lines)"
+        touched, failed = first_touch(seed, ops, defect)
+        assert failed is None or (touched is not None and failed >= touched), f"seed {seed}: failed at {failed} before the defect acted ({touched})"
+        if failed is not None:
+            with pytest.raises(AssertionError) as e:
+                S.run(CpuDevice([defect]), ops, S.Model(), seed=seed)
+            assert f"session seed {seed}, operation {failed} " in str(e.value) and e.value.op_index == failed
+            caught.append((seed, touched, failed))
+            if len(caught) == 2:
+                break
+    assert caught, f"no line plan notices {defect}"
+    print(f"{defect}: caught by plans (seed, first touched, failed at) {caught}")
+
+
+def test_shrink_keeps_a_line_failure(line_plans):
+    defect = "failed_matching_keeps_the_ids"
+    for seed, ops in line_plans.items():
+        touched, failed = first_touch(seed, ops, defect)
+        if failed is not None:
+            with pytest.raises(AssertionError):
+                S.run(CpuDevice([defect]), S.shrink(seed, failed + 1, lines=True), S.Model(), seed=seed)
+            S.run(CpuDevice([defect]), S.shrink(seed, failed, lines=True), S.Model(), seed=seed)
             return
     raise AssertionError("no plan to shrink")

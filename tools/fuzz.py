@@ -4,10 +4,12 @@ The cases and checks are tests/passfuzz.py's (the suite runs a fixed list of its
 usage: fuzz.py [seconds] [seed]
        fuzz.py session [seconds] [seed]     random SESSIONS instead: one context per plan driven through about 60 calls
                                             in random order (tests/session.py: the model, plans and executor of the suite);
-                                            the plans rotate through the three families: plain, with the whole-word filter
+                                            the plans rotate through the four families: plain, with the whole-word filter
                                             among the calls (plan(seed, words=True): filtered scans read by every pass and
                                             reader, results fetched across a filter), and with the per-pattern counts as well
-                                            (plan(seed, counts=True): counts accumulated and fetched late, count knobs)
+                                            (plan(seed, counts=True): counts accumulated and fetched late, count knobs),
+                                            and with the line path as well (plan(seed, lines=True): the delimiter split,
+                                            matching documents with context lines, and the gather of their bytes)
        fuzz.py class [seconds] [seed]       character-class and escaped-file cases instead (tests/classfuzz.py), against the
                                             brute-force matcher oracle/charclass_oracle.py and the escape-aware CPU oracle
        fuzz.py guard [seconds] [seed]       the capacity contract instead (tests/heapguard.py): the scan of random cases into
@@ -32,14 +34,14 @@ if len(sys.argv) > 1 and sys.argv[1] == "session":
     import session as S
     seconds = float(sys.argv[2]) if len(sys.argv) > 2 else 60.0
     seed = int(sys.argv[3]) if len(sys.argv) > 3 else 1
-    t0 = t_last = time.time(); plans = 0; tot = {"ops": 0, "errors": 0, "compared": 0, "filters": 0, "counts": 0}; widths = set(); staging = set()
+    t0 = t_last = time.time(); plans = 0; tot = {"ops": 0, "errors": 0, "compared": 0, "filters": 0, "counts": 0, "splits": 0, "matchings": 0, "gathers": 0, "ids": 0}; widths = set(); staging = set()
     regimes = set()
     while time.time() - t0 < seconds:
-        plan_seed = (seed << 20) + len(S.SEEDS) + plans // 3   # (beyond the suite's seeds; the three families in turn)
-        family = ("", "words", "counts")[plans % 3]
+        plan_seed = (seed << 20) + len(S.SEEDS) + plans // 4   # (beyond the suite's seeds; the four families in turn)
+        family = ("", "words", "counts", "lines")[plans % 4]
         with GpuMatcher(0, S.N_SLOTS) as g:
             try:
-                st = S.run(g, S.plan(plan_seed, words=family == "words", counts=family == "counts"), S.Model(),
+                st = S.run(g, S.plan(plan_seed, words=family == "words", counts=family == "counts", lines=family == "lines"), S.Model(),
                            seed=f"{plan_seed} ({family})" if family else plan_seed)
             except AssertionError as e:
                 raise SystemExit(f"MISMATCH in plan {plans}: {e}")
@@ -48,7 +50,8 @@ if len(sys.argv) > 1 and sys.argv[1] == "session":
         if time.time() - t_last > 30:
             t_last = time.time(); print(f"  ... {plans} plans, {tot['ops']} operations, {tot['compared']} records and bytes compared, {t_last - t0:.0f} s", flush=True)
     print(f"session fuzz ok: {plans} plans in {time.time() - t0:.0f} s (seed {seed}), {tot['ops']} operations of which {tot['errors']} "
-          f"documented errors, {tot['filters']} whole-word filters and {tot['counts']} counts, {tot['compared']} records and bytes compared")
+          f"documented errors, {tot['filters']} whole-word filters, {tot['counts']} counts, {tot['splits']} splits, {tot['matchings']} matching calls and {tot['gathers']} "
+          f"gathers, {tot['compared']} records and bytes and {tot['ids']} document ids and offsets compared")
     print(f"record widths {sorted(widths)}, staging layouts (buffers, records) {sorted(staging)}, count regimes (overlay, regime) {sorted(regimes)}")
     raise SystemExit(0)
 if len(sys.argv) > 1 and sys.argv[1] == "class":
