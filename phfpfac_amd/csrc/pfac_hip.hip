@@ -3759,8 +3759,43 @@ struct DevBuf {
     }
 };
 
+// An output of a pass that goes to the caller's device buffer or to this slot-owned one, and what ties the buffer to
+// its result: n elements, `done` (the pass has finished since it last invalidated), `own` (it wrote here, not into the
+// caller's buffer).  The rule it owns: a pass invalidates its outputs before its first check -- a refused call discards
+// the slot's earlier result -- and commits them together, behind its last launch.  Only a done, own result is fetched
+// (fetch) or stands in for a NULL argument of the pass that follows (consume).
+constexpr uint64_t ANY_N = ~0ull;         // consume: the caller names no count
+template <typename T>
+struct PassOut {
+    DevBuf<T> buf;
+    uint64_t n = 0;
+    bool done = false, own = false;
+    void invalidate() { done = false; }
+    void commit(uint64_t n_, bool own_) { n = n_; own = own_; done = true; }
+    // where `need` elements go: the caller's buffer, or the slot's grown (with the slot's stream) to the capacity the pass names
+    template <typename U>
+    int bind(pfac_ctx *ctx, hipStream_t stream, U *caller, uint64_t need, uint64_t new_cap, T **dst) {
+        int rc = caller ? PFAC_OK : buf.ensure(ctx, stream, need, new_cap);
+        *dst = caller ? reinterpret_cast<T *>(caller) : buf.p;
+        return rc;
+    }
+    // the NULL default of the next pass's argument: the caller's pointer, or this result where it is the slot's
+    template <typename U>
+    int consume(pfac_ctx *ctx, const std::string &fn, const char *noun, const U *caller, uint64_t expect, const T **src) const {
+        *src = reinterpret_cast<const T *>(caller);
+        if (caller) return PFAC_OK;
+        if (!done || !own)
+            return fail(ctx, PFAC_E_STATE, fn + ": the slot holds no " + noun + " (none yet, or it went to the caller's buffer; pass that)");
+        if (expect != ANY_N && expect != n) return fail(ctx, PFAC_E_ARG, fn + ": the count given differs from the slot's " + noun);
+        *src = buf.p;
+        return PFAC_OK;
+    }
+};
+
 // capacity of a per-tile array asked for n entries: a quarter more, 4096 at least
 uint64_t quarter_more(uint64_t n) { return n < 4096 ? 4096 : n + n / 4; }
+// ... of a slot-owned array of n_docs + 1 entries (offsets, doc_first)
+uint64_t docs_cap(uint64_t n_docs) { return n_docs + 1 < 4096 ? 4096 : n_docs + 1 + n_docs / 4; }
 
 // 64-bit words in Slot::h_ctl (as indices of its 32-bit words)
 enum : int {
@@ -3780,8 +3815,8 @@ struct Slot {
     DevBuf<unsigned long long> tile_index;        // per tile of the last scan: first record | count << 40
     DevBuf<unsigned> d2log;               // dense mode, second form: the record logs of the grid's compute waves
     DevBuf<unsigned long long> gsum;      // scratch of the expand / text paths: record (byte) prefix per group of 64 tiles (+ the total)
-    DevBuf<unsigned char> text;           // pfac_emit_text_device: the formatted lines of the slot's last scan
-    uint64_t text_bytes = 0;
+    DevBuf<unsigned char> text;           // pfac_emit_text_device: the formatted lines of the slot's last scan (no PassOut:
+    uint64_t text_bytes = 0;              // it has no "never made" state -- before the first text its length is 0)
     DevBuf<pfac_record> wide;             // scratch of pfac_records_d2h: packed records expanded on the device
     int last_rec_bytes = 4;               // record form of the slot's last scan (2, 4 or 8 bytes)
     const void *last_records = nullptr;   // ... and where it wrote
@@ -3804,54 +3839,39 @@ struct Slot {
     uint64_t last_table = 0;              // ... and the table it ran with (pfac_ctx::table_gen)
     DevBuf<unsigned long long> dbg;       // PFAC_TRACE_BUILD + PFAC_TRACE
     // pfac_slot_doc_offsets / pfac_records_segment
-    DevBuf<unsigned long long> doc_off;   // the slot's document offsets (doc_n + 1 of them)
-    uint64_t doc_n = 0;
-    bool doc_set = false;
+    PassOut<unsigned long long> doc;      // the slot's document offsets (n_docs + 1 of them; always the slot's own)
     DevBuf<unsigned> seg_tcnt;            // kept records per tile of the last segment pass
-    DevBuf<pfac_record> seg_out;          // slot-owned outputs of the last segment pass (d_out / d_doc_first NULL)
-    DevBuf<unsigned long long> seg_first;
-    uint64_t seg_kept = 0, seg_docs = 0;
-    bool seg_done = false, seg_own_out = false, seg_own_first = false;
+    PassOut<pfac_record> seg_out;         // the last segment pass: the kept records, ...
+    PassOut<unsigned long long> seg_first;        // ... and doc_first (n_docs + 1 entries)
     // pfac_records_leftmost_longest
     DevBuf<unsigned char> ll_tmp;         // group functions, group entries, picks per tile, per-tile selection bitmaps
-    DevBuf<pfac_record> ll_out;           // slot-owned selection (d_out NULL)
-    uint64_t ll_n = 0;
-    bool ll_done = false, ll_own_out = false;
+    PassOut<pfac_record> ll_out;          // the selection
     uint64_t ll_seq = 0;                  // the scan it selected from (scan_seq), ...
     uint32_t ll_entry = 0, ll_exit = 0;   // ... and its entry and exit offsets
     // pfac_replace_leftmost_longest
     uint64_t last_avail = 0;              // n_avail of the slot's last scan (the input bytes it may read)
     uint64_t scan_seq = 0;                // record sets of this slot: scans issued + whole-word filters run over them
     DevBuf<unsigned char> rp_tmp;         // X per block of 64 picks
-    DevBuf<unsigned char> rp_out;         // slot-owned output (d_out NULL)
-    uint64_t rp_bytes = 0;
-    bool rp_done = false, rp_own_out = false;
+    PassOut<unsigned char> rp_out;        // the output bytes
     // pfac_records_leftmost_longest_documents / pfac_replace_documents
     uint64_t doc_gen = 0;                 // pfac_slot_doc_offsets calls: a selection remembers the offsets it cut with
     bool ll_docs = false;                 // the slot's last selection was per document, ...
-    uint64_t lld_docs = 0, lld_gen = 0;   // ... over this many documents, with the slot's offsets of this generation
-    bool lld_own_off = false, lld_own_first = false;   // (or the caller's offsets / doc_first)
-    DevBuf<unsigned long long> lld_first; // slot-owned doc_first (d_doc_first NULL)
+    uint64_t lld_gen = 0;                 // ... with the slot's offsets of this generation
+    bool lld_own_off = false;             // (or the caller's offsets)
+    PassOut<unsigned long long> lld_first;        // its doc_first (n_docs + 1 entries)
     DevBuf<unsigned long long> rpd_tmp;   // D_k per pick (and the total behind them)
-    DevBuf<unsigned long long> rpd_off;   // slot-owned output offsets (d_out_offsets NULL)
-    uint64_t rpd_docs = 0;
-    bool rpd_done = false, rpd_own_off = false;
+    PassOut<unsigned long long> rpd_off;  // the output offsets (n_docs + 1 entries)
     // pfac_records_count_states / pfac_selection_count_states
-    DevBuf<unsigned long long> cnt;       // slot-owned state counts (d_counts NULL): cnt_states of them, ...
-    uint64_t cnt_states = 0, cnt_table = 0;       // ... counted with this table (pfac_ctx::table_gen)
-    bool cnt_done = false;
+    PassOut<unsigned long long> cnt;      // the state counts; committed by slot-owned counts only, never invalidated: they
+    uint64_t cnt_table = 0;               // accumulate across calls.  Counted with this table (pfac_ctx::table_gen)
     // pfac_slot_doc_offsets_split
     DevBuf<unsigned long long> sp_tile;   // per input tile: delimiters | end of the last one << 32
     // pfac_documents_matching
-    DevBuf<unsigned long long> dm_out;    // slot-owned ids (d_ids_out NULL): dm_n of them
-    uint64_t dm_n = 0;
-    bool dm_done = false, dm_own = false;
+    PassOut<unsigned long long> dm_out;   // the ids
     // pfac_documents_gather
     DevBuf<unsigned long long> ga_x;      // X per block of 64 ids
-    DevBuf<unsigned char> ga_out;         // slot-owned bytes (d_out NULL): ga_bytes of them
-    DevBuf<unsigned long long> ga_off;    // slot-owned output offsets (d_out_offsets NULL): ga_ids + 1 of them
-    uint64_t ga_bytes = 0, ga_ids = 0;
-    bool ga_done = false, ga_own_out = false, ga_own_off = false;
+    PassOut<unsigned char> ga_out;        // the bytes, ...
+    PassOut<unsigned long long> ga_off;   // ... and the output offsets (n_ids + 1 entries)
 };
 
 }  // namespace
@@ -3952,6 +3972,26 @@ int check_slot(pfac_ctx *ctx, int slot) {
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// [first, first + n) within a result of `total` elements (subtracting: first + n may wrap)
+bool in_window(uint64_t first, uint64_t n, uint64_t total) { return first <= total && n <= total - first; }
+
+// One fetch of a slot-owned result: elements [first, first + n) of `o` to `host`, asynchronous on the slot's stream
+// (whole-result fetches pass 0, o.n).  Checked in this order: `pass` has finished, else PFAC_E_STATE; `optional` and no
+// host pointer: the half of a pair fetch that the caller does not want; the result is the slot's, else PFAC_E_STATE;
+// the window lies in it and there is a host pointer where elements are asked for, else PFAC_E_ARG.
+template <typename T>
+int fetch(pfac_ctx *ctx, Slot &s, const PassOut<T> &o, const std::string &fn, const char *pass, void *host, uint64_t first,
+          uint64_t n, bool optional = false) {
+    if (!o.done) return fail(ctx, PFAC_E_STATE, fn + " without a finished " + pass);
+    if (optional && !host) return PFAC_OK;
+    if (!o.own) return fail(ctx, PFAC_E_STATE, fn + ": the last " + pass + " wrote into the caller's buffer");
+    if (!in_window(first, n, o.n)) return fail(ctx, PFAC_E_ARG, fn + ": [first, first + n) exceeds the result of the last " + pass);
+    if (!host && n) return fail(ctx, PFAC_E_ARG, fn + ": null host buffer");
+    USE_DEVICE(ctx);
+    if (n) HIP_TRY(ctx, hipMemcpyAsync(host, o.buf.p + first, n * sizeof(T), hipMemcpyDeviceToHost, s.stream));
+    return PFAC_OK;
+}
+
 constexpr size_t CTL_REGION = (CTL_WORDS * 4 + 255) / 256 * 256;
 
 int ensure_ctl(pfac_ctx *ctx, Slot &s) {
@@ -3972,7 +4012,7 @@ int ensure_gsum(pfac_ctx *ctx, Slot &s, unsigned n_groups) {
 
 // a slot-owned array of n_docs + 1 entries (offsets, doc_first)
 int ensure_docs(pfac_ctx *ctx, Slot &s, DevBuf<unsigned long long> &b, uint64_t n_docs) {
-    return b.ensure(ctx, s.stream, n_docs + 1, n_docs + 1 < 4096 ? 4096 : n_docs + 1 + n_docs / 4);
+    return b.ensure(ctx, s.stream, n_docs + 1, docs_cap(n_docs));
 }
 
 // f(std::integral_constant<int, BYTES>()) for a record width of 2, 4 or 8 bytes: how a pass picks the kernel of the
@@ -3983,6 +4023,15 @@ auto by_width(int rec_bytes, F f) {
 }
 
 uint64_t host_u64(const Slot &s, int word) { return ((uint64_t)s.h_ctl[word + 1] << 32) | s.h_ctl[word]; }
+
+// The result words of a pass, from behind its group prefixes into h_ctl (read them with host_u64): the launch-error
+// check of the kernels that made them, the copy, and the ONE synchronise a pass spends on learning its total.
+int pass_words(pfac_ctx *ctx, Slot &s, const unsigned long long *dev, int n_words, int first_word = H_PASS) {
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(s.h_ctl + first_word, dev, (size_t)n_words * 8, hipMemcpyDeviceToHost, s.stream));
+    HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+    return PFAC_OK;
+}
 
 // What a pass needs of the slot's last scan, tested in this order (the first failure is the one reported).
 enum : unsigned {
@@ -4010,9 +4059,9 @@ int resolve_docs(pfac_ctx *ctx, const Slot &s, const std::string &fn, const uint
                  uintptr_t others, const unsigned long long **off) {
     *off = reinterpret_cast<const unsigned long long *>(d_doc_offsets);
     if (!*off) {
-        if (!s.doc_set) return fail(ctx, PFAC_E_STATE, fn + ": no document offsets for the slot (pfac_slot_doc_offsets)");
-        if (n_docs != s.doc_n) return fail(ctx, PFAC_E_ARG, fn + ": n_docs differs from the slot's document offsets");
-        *off = s.doc_off.p;
+        if (!s.doc.done) return fail(ctx, PFAC_E_STATE, fn + ": no document offsets for the slot (pfac_slot_doc_offsets)");
+        if (n_docs + 1 != s.doc.n) return fail(ctx, PFAC_E_ARG, fn + ": n_docs differs from the slot's document offsets");
+        *off = s.doc.buf.p;
     }
     if (n_docs >= (1ull << 32)) return fail(ctx, PFAC_E_ARG, fn + ": n_docs must be below 2^32");
     if (n_docs == 0 && s.last_owned != 0) return fail(ctx, PFAC_E_ARG, fn + ": no documents, but the scan owns bytes");
@@ -4729,7 +4778,7 @@ static int expand_records(pfac_ctx *ctx, Slot &s, const void *src, uint64_t firs
     // records that do not exist, or that the last scan could not write, are never delivered as if they did: the copy
     // kernel skips them and the caller would read whatever its buffer held before
     if (s.pending) return fail(ctx, PFAC_E_STATE, "records requested before pfac_scan_finish");
-    if (first + n > s.last_total) return fail(ctx, PFAC_E_ARG, "records [first, first + n) exceed the scan's match count");
+    if (!in_window(first, n, s.last_total)) return fail(ctx, PFAC_E_ARG, "records [first, first + n) exceed the scan's match count");
     int rc = last_scan_usable(ctx, s, "", SCAN_FITS);
     if (rc) return rc;
     if (n == 0 || s.last_tiles == 0) return PFAC_OK;
@@ -4873,7 +4922,7 @@ int pfac_text_d2h(pfac_ctx *ctx, int slot, void *host, uint64_t first, uint64_t 
     int rc = check_slot(ctx, slot);
     if (rc) return rc;
     Slot &s = ctx->slots[slot];
-    if (first + n > s.text_bytes) return fail(ctx, PFAC_E_ARG, "pfac_text_d2h: range exceeds the text of the slot's last pfac_emit_text_device");
+    if (!in_window(first, n, s.text_bytes)) return fail(ctx, PFAC_E_ARG, "pfac_text_d2h: range exceeds the text of the slot's last pfac_emit_text_device");
     if (n == 0) return PFAC_OK;
     if (!host) return fail(ctx, PFAC_E_ARG, "null buffer");
     USE_DEVICE(ctx);
@@ -4933,7 +4982,7 @@ int count_run(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *heap, b
         return fail(ctx, PFAC_E_ARG, fn + ": n_states must be num_final of the uploaded table (" + std::to_string(ctx->num_final) + ")");
     if ((uintptr_t)d_counts & 7) return fail(ctx, PFAC_E_ARG, fn + ": d_counts must be 8-byte aligned");
     const bool own = d_counts == nullptr, acc = (flags & PFAC_COUNT_ACCUMULATE) != 0;
-    if (own && acc && s.cnt_done && s.cnt_table != ctx->table_gen)
+    if (own && acc && s.cnt.done && s.cnt_table != ctx->table_gen)
         return fail(ctx, PFAC_E_STATE, fn + ": the slot's counts belong to an earlier table; they cannot be added to");
     const uint64_t expect = is_sel ? n_sel : s.last_total;
     const uint64_t n_items = is_sel ? (n_sel + WAVE - 1) / WAVE : s.last_tiles;
@@ -4947,18 +4996,14 @@ int count_run(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *heap, b
         HIP_TRY(ctx, hipMemsetAsync(res, 0, 16, s.stream));
         const unsigned blocks = (unsigned)std::min<uint64_t>((n_sel + 255) / 256, 1024);
         hipLaunchKernelGGL(pfac_sel_check_kernel, dim3(blocks), dim3(256), 0, s.stream, sel, (unsigned long long)n_sel, ns, res + 1);
-        HIP_TRY(ctx, hipGetLastError());
-        HIP_TRY(ctx, hipMemcpyAsync(s.h_ctl + H_PASS1, res + 1, 8, hipMemcpyDeviceToHost, s.stream));
-        HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+        rc = pass_words(ctx, s, res + 1, 1, H_PASS1);
+        if (rc) return rc;
         if (host_u64(s, H_PASS1)) return fail(ctx, PFAC_E_ARG, fn + ": d_sel is not the selection of this scan and table");
     }
-    unsigned long long *dst = reinterpret_cast<unsigned long long *>(d_counts);
-    const bool zero = !acc || (own && !s.cnt_done);
-    if (own) {                                              // (it grows only where the counts start from zero)
-        rc = s.cnt.ensure(ctx, s.stream, std::max<uint64_t>(n_states, 1), std::max<uint64_t>(n_states, 1));
-        if (rc) { s.cnt_done = false; return rc; }
-        dst = s.cnt.p;
-    }
+    unsigned long long *dst;
+    const bool zero = !acc || (own && !s.cnt.done);
+    rc = s.cnt.bind(ctx, s.stream, d_counts, std::max<uint64_t>(n_states, 1), std::max<uint64_t>(n_states, 1), &dst);
+    if (rc) { s.cnt.invalidate(); return rc; }             // (it grows only where the counts start from zero)
     HIP_TRY(ctx, hipMemsetAsync(res, 0, 8, s.stream));
     if (zero && n_states) HIP_TRY(ctx, hipMemsetAsync(dst, 0, n_states * 8, s.stream));
     if (n_items && n_states) {
@@ -4984,15 +5029,13 @@ int count_run(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *heap, b
         hipLaunchKernelGGL(k, dim3(grid), dim3(threads), lds, s.stream, is_sel ? (const void *)sel : heap,
                            is_sel ? (const unsigned long long *)nullptr : s.tile_index.p, (unsigned long long)n_items,
                            (unsigned long long)(is_sel ? n_sel : s.last_cap), ns, bins, dst, res);
-        HIP_TRY(ctx, hipGetLastError());
     }
-    HIP_TRY(ctx, hipMemcpyAsync(s.h_ctl + H_PASS, res, 8, hipMemcpyDeviceToHost, s.stream));
-    HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+    rc = pass_words(ctx, s, res, 1);
+    if (rc) return rc;
     const uint64_t total = host_u64(s, H_PASS);
     if (own) {
-        s.cnt_states = n_states;
+        s.cnt.commit(n_states, true);
         s.cnt_table = ctx->table_gen;
-        s.cnt_done = true;
     }
     *n_counted = total;
     if (total != expect)
@@ -5029,25 +5072,22 @@ int pfac_selection_count_states(pfac_ctx *ctx, int slot, const pfac_record *d_se
     Slot &s = ctx->slots[slot];
     const std::string fn = "pfac_selection_count_states";
     // the rules of pfac_replace_leftmost_longest's d_sel
-    if (!s.scanned || s.pending || !s.ll_done || s.ll_seq != s.scan_seq)
+    if (!s.scanned || s.pending || !s.ll_out.done || s.ll_seq != s.scan_seq)
         return fail(ctx, PFAC_E_STATE, fn + " needs a leftmost-longest selection since the slot's last scan");
     if (!ctx->have_table || s.last_table != ctx->table_gen)
         return fail(ctx, PFAC_E_STATE, fn + ": the selection was made with an earlier table");
-    if (!d_sel && !s.ll_own_out)
-        return fail(ctx, PFAC_E_STATE, fn + ": the selection went to the caller's buffer; pass it as d_sel");
+    const pfac_record *sel;
+    rc = s.ll_out.consume(ctx, fn, "selection (d_sel)", d_sel, ANY_N, &sel);
+    if (rc) return rc;
     if ((uintptr_t)d_sel & 7) return fail(ctx, PFAC_E_ARG, fn + ": d_sel must be 8-byte aligned");
-    return count_run(ctx, s, fn, nullptr, true, d_sel ? d_sel : s.ll_out.p, s.ll_n, d_sel != nullptr, d_counts, n_states, flags, n_counted);
+    return count_run(ctx, s, fn, nullptr, true, sel, s.ll_out.n, d_sel != nullptr, d_counts, n_states, flags, n_counted);
 }
 
 int pfac_state_counts_d2h(pfac_ctx *ctx, int slot, uint64_t *host_counts) {
     int rc = check_slot(ctx, slot);
     if (rc) return rc;
     Slot &s = ctx->slots[slot];
-    if (!s.cnt_done) return fail(ctx, PFAC_E_STATE, "pfac_state_counts_d2h without slot-owned counts (pfac_records_count_states with d_counts NULL)");
-    if (!host_counts && s.cnt_states) return fail(ctx, PFAC_E_ARG, "null host buffer");
-    USE_DEVICE(ctx);
-    if (s.cnt_states) HIP_TRY(ctx, hipMemcpyAsync(host_counts, s.cnt.p, s.cnt_states * 8, hipMemcpyDeviceToHost, s.stream));
-    return PFAC_OK;
+    return fetch(ctx, s, s.cnt, "pfac_state_counts_d2h", "slot-owned count (pfac_records_count_states with d_counts NULL)", host_counts, 0, s.cnt.n);
 }
 
 int pfac_table_set_final_lengths(pfac_ctx *ctx, const int32_t *len, size_t n) {
@@ -5074,13 +5114,12 @@ int pfac_slot_doc_offsets(pfac_ctx *ctx, int slot, const uint64_t *host_offsets,
     if (!host_offsets || n_docs >= (1ull << 32)) return fail(ctx, PFAC_E_ARG, "pfac_slot_doc_offsets: need n_docs + 1 offsets, n_docs < 2^32");
     Slot &s = ctx->slots[slot];
     USE_DEVICE(ctx);
-    s.doc_set = false;
-    rc = ensure_docs(ctx, s, s.doc_off, n_docs);
+    s.doc.invalidate();
+    rc = ensure_docs(ctx, s, s.doc.buf, n_docs);
     if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(s.doc_off.p, host_offsets, (n_docs + 1) * 8, hipMemcpyHostToDevice, s.stream));
+    HIP_TRY(ctx, hipMemcpyAsync(s.doc.buf.p, host_offsets, (n_docs + 1) * 8, hipMemcpyHostToDevice, s.stream));
     HIP_TRY(ctx, hipStreamSynchronize(s.stream));        // (the caller's array may go once this returns)
-    s.doc_n = n_docs;
-    s.doc_set = true;
+    s.doc.commit(n_docs + 1, true);
     s.doc_gen++;
     return PFAC_OK;
 }
@@ -5116,9 +5155,8 @@ int pfac_slot_doc_offsets_split(pfac_ctx *ctx, int slot, const void *d_input, ui
                            (unsigned long long)n_tiles, s.gsum.p, glast, n_groups);
         hipLaunchKernelGGL(pfac_scan_groups_kernel, dim3(1), dim3(1024), 0, s.stream, s.gsum.p, n_groups);
         hipLaunchKernelGGL(pfac_split_ends_kernel, dim3(1), dim3(1024), 0, s.stream, s.gsum.p, glast, n_groups, res);
-        HIP_TRY(ctx, hipGetLastError());
-        HIP_TRY(ctx, hipMemcpyAsync(s.h_ctl + H_PASS, res, 16, hipMemcpyDeviceToHost, s.stream));
-        HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+        rc = pass_words(ctx, s, res, 2);
+        if (rc) return rc;
         total = host_u64(s, H_PASS);
         tail = host_u64(s, H_PASS1);
     }
@@ -5126,23 +5164,22 @@ int pfac_slot_doc_offsets_split(pfac_ctx *ctx, int slot, const void *d_input, ui
     if (docs >= (1ull << 32)) return fail(ctx, PFAC_E_ARG, fn + ": 2^32 documents (every byte is a delimiter); n_docs must be below 2^32");
     // the new offsets go into a buffer of their own where the old one is too small: a failure up to here, the allocation
     // included, leaves the slot's offsets as they were
-    if (docs + 1 > s.doc_off.cap) {
+    if (docs + 1 > s.doc.buf.cap) {
         DevBuf<unsigned long long> grown;
         rc = ensure_docs(ctx, s, grown, docs);
         if (rc) return rc;
         HIP_TRY(ctx, hipStreamSynchronize(s.stream));        // (nothing queued still reads the old one)
-        s.doc_off = std::move(grown);
+        s.doc.buf = std::move(grown);
     }
     if (n_groups) {
         hipLaunchKernelGGL(pfac_split_write_kernel, dim3(tblocks), dim3(256), 0, s.stream, in, (unsigned long long)n_bytes,
                            (unsigned long long)n_tiles, x4, s.sp_tile.p, s.gsum.p, (unsigned long long)total,
-                           (unsigned long long)(tail != n_bytes ? total + 1 : 0), s.doc_off.p);
+                           (unsigned long long)(tail != n_bytes ? total + 1 : 0), s.doc.buf.p);
         HIP_TRY(ctx, hipGetLastError());
     } else {
-        HIP_TRY(ctx, hipMemsetAsync(s.doc_off.p, 0, 8, s.stream));   // no bytes: the single offset 0
+        HIP_TRY(ctx, hipMemsetAsync(s.doc.buf.p, 0, 8, s.stream));   // no bytes: the single offset 0
     }
-    s.doc_n = docs;
-    s.doc_set = true;
+    s.doc.commit(docs + 1, true);
     s.doc_gen++;
     *n_docs = docs;
     *tail_start = tail;
@@ -5153,12 +5190,7 @@ int pfac_slot_doc_offsets_d2h(pfac_ctx *ctx, int slot, uint64_t *host_offsets, u
     int rc = check_slot(ctx, slot);
     if (rc) return rc;
     Slot &s = ctx->slots[slot];
-    if (!s.doc_set) return fail(ctx, PFAC_E_STATE, "pfac_slot_doc_offsets_d2h: no document offsets for the slot");
-    if (first > s.doc_n + 1 || n > s.doc_n + 1 - first) return fail(ctx, PFAC_E_ARG, "pfac_slot_doc_offsets_d2h: [first, first + n) exceeds the n_docs + 1 offsets");
-    if (!host_offsets && n) return fail(ctx, PFAC_E_ARG, "null host buffer");
-    USE_DEVICE(ctx);
-    if (n) HIP_TRY(ctx, hipMemcpyAsync(host_offsets, s.doc_off.p + first, n * 8, hipMemcpyDeviceToHost, s.stream));
-    return PFAC_OK;
+    return fetch(ctx, s, s.doc, "pfac_slot_doc_offsets_d2h", "pfac_slot_doc_offsets or pfac_slot_doc_offsets_split", host_offsets, first, n);
 }
 
 int pfac_records_segment(pfac_ctx *ctx, int slot, const void *d_records, const uint64_t *d_doc_offsets, uint64_t n_docs,
@@ -5168,7 +5200,8 @@ int pfac_records_segment(pfac_ctx *ctx, int slot, const void *d_records, const u
     if (!n_kept) return fail(ctx, PFAC_E_ARG, "null argument");
     *n_kept = 0;
     Slot &s = ctx->slots[slot];
-    s.seg_done = false;
+    s.seg_out.invalidate();
+    s.seg_first.invalidate();
     const std::string fn = "pfac_records_segment";
     rc = last_scan_usable(ctx, s, fn, SCAN_FINISHED | SCAN_LENGTHS | SCAN_TABLE | SCAN_FITS);
     if (rc) return rc;
@@ -5194,21 +5227,18 @@ int pfac_records_segment(pfac_ctx *ctx, int slot, const void *d_records, const u
                        (unsigned long long)s.last_cap, off, (unsigned long long)n_docs, (unsigned long long)s.last_owned,
                        ctx->flen.p, (unsigned)ctx->num_final, s.seg_tcnt.p, s.gsum.p, n_groups, s.gsum.p + n_groups + 1);
     if (n_groups) hipLaunchKernelGGL(pfac_scan_groups_kernel, dim3(1), dim3(1024), 0, s.stream, s.gsum.p, n_groups);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(s.h_ctl + H_PASS, s.gsum.p + n_groups, 16, hipMemcpyDeviceToHost, s.stream));
-    HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+    rc = pass_words(ctx, s, s.gsum.p + n_groups, 2);
+    if (rc) return rc;
     const uint64_t total = host_u64(s, H_PASS);
     if (host_u64(s, H_PASS1)) return bad_doc_offsets(ctx, s, fn);
     *n_kept = total;
-    const bool own_out = d_out == nullptr, own_first = d_doc_first == nullptr;
-    if (!own_out && total > out_cap)
+    if (d_out && total > out_cap)
         return fail(ctx, PFAC_E_OVERFLOW, fn + ": " + std::to_string(total) + " records kept, out_cap is " + std::to_string(out_cap));
-    rc = own_out ? s.seg_out.ensure(ctx, s.stream, total, total + total / 8 + 4096) : PFAC_OK;
+    pfac_record *out;
+    unsigned long long *first;
+    rc = s.seg_out.bind(ctx, s.stream, d_out, total, total + total / 8 + 4096, &out);
+    if (!rc) rc = s.seg_first.bind(ctx, s.stream, d_doc_first, n_docs + 1, docs_cap(n_docs), &first);
     if (rc) return rc;
-    rc = own_first ? ensure_docs(ctx, s, s.seg_first, n_docs) : PFAC_OK;
-    if (rc) return rc;
-    pfac_record *out = own_out ? s.seg_out.p : d_out;
-    unsigned long long *first = own_first ? s.seg_first.p : reinterpret_cast<unsigned long long *>(d_doc_first);
     if (n_groups) {
         auto wk = by_width(rb, [](auto w) { return pfac_seg_write_kernel<w()>; });
         hipLaunchKernelGGL(wk, dim3((unsigned)gblocks), dim3(256), 0, s.stream, src, s.tile_index.p, (unsigned long long)n_tiles,
@@ -5218,11 +5248,8 @@ int pfac_records_segment(pfac_ctx *ctx, int slot, const void *d_records, const u
     } else {
         HIP_TRY(ctx, hipMemsetAsync(first, 0, (n_docs + 1) * 8, s.stream));   // nothing scanned: every document is empty
     }
-    s.seg_kept = total;
-    s.seg_docs = n_docs;
-    s.seg_own_out = own_out;
-    s.seg_own_first = own_first;
-    s.seg_done = true;
+    s.seg_out.commit(total, !d_out);
+    s.seg_first.commit(n_docs + 1, !d_doc_first);
     return PFAC_OK;
 }
 
@@ -5230,15 +5257,31 @@ int pfac_segment_d2h(pfac_ctx *ctx, int slot, pfac_record *host_records, uint64_
     int rc = check_slot(ctx, slot);
     if (rc) return rc;
     Slot &s = ctx->slots[slot];
-    if (!s.seg_done) return fail(ctx, PFAC_E_STATE, "pfac_segment_d2h without a finished pfac_records_segment");
-    if ((host_records && !s.seg_own_out) || (host_doc_first && !s.seg_own_first))
-        return fail(ctx, PFAC_E_STATE, "pfac_segment_d2h: the last pfac_records_segment wrote into the caller's buffers");
-    USE_DEVICE(ctx);
-    if (host_records && s.seg_kept)
-        HIP_TRY(ctx, hipMemcpyAsync(host_records, s.seg_out.p, s.seg_kept * sizeof(pfac_record), hipMemcpyDeviceToHost, s.stream));
-    if (host_doc_first)
-        HIP_TRY(ctx, hipMemcpyAsync(host_doc_first, s.seg_first.p, (s.seg_docs + 1) * 8, hipMemcpyDeviceToHost, s.stream));
-    return PFAC_OK;
+    rc = fetch(ctx, s, s.seg_out, "pfac_segment_d2h", "pfac_records_segment", host_records, 0, s.seg_out.n, true);
+    return rc ? rc : fetch(ctx, s, s.seg_first, "pfac_segment_d2h", "pfac_records_segment", host_doc_first, 0, s.seg_first.n, true);
+}
+
+// The offsets' rules alone, on the slot's stream (pfac_seg_count_kernel without tiles): *bad becomes non-zero where
+// the offsets do not start at 0, decrease, or do not end at the scan's n_owned.
+static void launch_offsets_check(pfac_ctx *ctx, Slot &s, const unsigned long long *off, uint64_t n_docs, unsigned long long *bad) {
+    const unsigned vblocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_docs + 255) / 256, 4096));
+    hipLaunchKernelGGL(pfac_seg_count_kernel<4>, dim3(vblocks), dim3(256), 0, s.stream, (const void *)nullptr,
+                       (const unsigned long long *)nullptr, 0ull, 0ull, off, (unsigned long long)n_docs,
+                       (unsigned long long)s.last_owned, ctx->flen.p, (unsigned)ctx->num_final, (unsigned *)nullptr,
+                       (unsigned long long *)nullptr, 0u, bad);
+}
+
+// Grid of the output-windowed write kernels (replace, gather) for `total` output bytes: one window of 1 KiB per wave
+// while the output is small (every window's search runs in parallel), four above, more where the grid would pass 2^20.
+struct WriteGrid {
+    unsigned blocks, wins;
+};
+static WriteGrid write_grid(uint64_t total) {
+    uint64_t wins = total >= (64ull << 20) ? 4 : 1;
+    const uint64_t max_blocks = 1ull << 20;
+    const uint64_t per_block = (uint64_t)RP_WAVES * RP_WIN;
+    if ((total + per_block * wins - 1) / (per_block * wins) > max_blocks) wins = (total + per_block * max_blocks - 1) / (per_block * max_blocks);
+    return {(unsigned)((total + per_block * wins - 1) / (per_block * wins)), (unsigned)wins};
 }
 
 // Both matching calls: the plain one (context false: flags 0 or PFAC_DOCS_INVERT) and the one with context lines
@@ -5250,14 +5293,10 @@ static int dm_run(pfac_ctx *ctx, int slot, const std::string &fn, const uint64_t
     if (!n_matching) return fail(ctx, PFAC_E_ARG, "null argument");
     *n_matching = 0;
     Slot &s = ctx->slots[slot];
-    s.dm_done = false;
-    const unsigned long long *first = reinterpret_cast<const unsigned long long *>(d_doc_first);
-    if (!first) {
-        if (!s.seg_done || !s.seg_own_first)
-            return fail(ctx, PFAC_E_STATE, fn + ": the slot holds no doc_first of a pfac_records_segment (none yet, or it went to the caller's buffer)");
-        if (n_docs != s.seg_docs) return fail(ctx, PFAC_E_ARG, fn + ": n_docs differs from the slot's last pfac_records_segment");
-        first = s.seg_first.p;
-    }
+    s.dm_out.invalidate();
+    const unsigned long long *first;
+    rc = s.seg_first.consume(ctx, fn, "doc_first of a pfac_records_segment (n_docs + 1 entries)", d_doc_first, n_docs + 1, &first);
+    if (rc) return rc;
     if (context && flags) return fail(ctx, PFAC_E_ARG, fn + ": flags must be 0 (context around non-matching documents is not defined by doc_first)");
     if (flags > PFAC_DOCS_INVERT) return fail(ctx, PFAC_E_ARG, fn + ": flags must be 0 or PFAC_DOCS_INVERT");
     if (n_docs >= (1ull << 32)) return fail(ctx, PFAC_E_ARG, fn + ": n_docs must be below 2^32");
@@ -5277,19 +5316,17 @@ static int dm_run(pfac_ctx *ctx, int slot, const std::string &fn, const uint64_t
             hipLaunchKernelGGL(pfac_docs_matching_kernel<false>, grid, block, 0, s.stream, first,
                                (unsigned long long)n_docs, (unsigned)flags, s.gsum.p, n_groups, 0ull, (unsigned long long *)nullptr);
         hipLaunchKernelGGL(pfac_scan_groups_kernel, dim3(1), dim3(1024), 0, s.stream, s.gsum.p, n_groups);
-        HIP_TRY(ctx, hipGetLastError());
-        HIP_TRY(ctx, hipMemcpyAsync(s.h_ctl + H_PASS, s.gsum.p + n_groups, 8, hipMemcpyDeviceToHost, s.stream));
-        HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+        rc = pass_words(ctx, s, s.gsum.p + n_groups, 1);
+        if (rc) return rc;
         total = host_u64(s, H_PASS);
     }
     *n_matching = total;
-    const bool own = d_ids_out == nullptr;
-    if (!own && total > out_cap)
+    if (d_ids_out && total > out_cap)
         return fail(ctx, PFAC_E_OVERFLOW, fn + ": " + std::to_string(total) + " documents, out_cap is " + std::to_string(out_cap));
-    rc = own ? s.dm_out.ensure(ctx, s.stream, total, total + total / 8 + 4096) : PFAC_OK;
+    unsigned long long *ids;
+    rc = s.dm_out.bind(ctx, s.stream, d_ids_out, total, total + total / 8 + 4096, &ids);
     if (rc) return rc;
     if (total) {
-        unsigned long long *ids = own ? s.dm_out.p : reinterpret_cast<unsigned long long *>(d_ids_out);
         if (context)
             hipLaunchKernelGGL(pfac_docs_context_kernel<true>, grid, block, 0, s.stream, first, (unsigned long long)n_docs, bef, aft,
                                s.gsum.p, n_groups, (unsigned long long)total, ids);
@@ -5298,9 +5335,7 @@ static int dm_run(pfac_ctx *ctx, int slot, const std::string &fn, const uint64_t
                                (unsigned long long)n_docs, (unsigned)flags, s.gsum.p, n_groups, (unsigned long long)total, ids);
         HIP_TRY(ctx, hipGetLastError());
     }
-    s.dm_n = total;
-    s.dm_own = own;
-    s.dm_done = true;
+    s.dm_out.commit(total, !d_ids_out);
     return PFAC_OK;
 }
 
@@ -5319,12 +5354,7 @@ int pfac_documents_matching_d2h(pfac_ctx *ctx, int slot, uint64_t *host_ids) {
     int rc = check_slot(ctx, slot);
     if (rc) return rc;
     Slot &s = ctx->slots[slot];
-    if (!s.dm_done) return fail(ctx, PFAC_E_STATE, "pfac_documents_matching_d2h without a finished pfac_documents_matching");
-    if (!s.dm_own) return fail(ctx, PFAC_E_STATE, "pfac_documents_matching_d2h: the last pfac_documents_matching wrote into the caller's buffer");
-    if (!host_ids && s.dm_n) return fail(ctx, PFAC_E_ARG, "null host buffer");
-    USE_DEVICE(ctx);
-    if (s.dm_n) HIP_TRY(ctx, hipMemcpyAsync(host_ids, s.dm_out.p, s.dm_n * 8, hipMemcpyDeviceToHost, s.stream));
-    return PFAC_OK;
+    return fetch(ctx, s, s.dm_out, "pfac_documents_matching_d2h", "pfac_documents_matching", host_ids, 0, s.dm_out.n);
 }
 
 int pfac_documents_gather(pfac_ctx *ctx, int slot, const void *d_input, uint64_t n_bytes, const uint64_t *d_doc_offsets,
@@ -5335,30 +5365,26 @@ int pfac_documents_gather(pfac_ctx *ctx, int slot, const void *d_input, uint64_t
     if (!out_bytes) return fail(ctx, PFAC_E_ARG, "null argument");
     *out_bytes = 0;
     Slot &s = ctx->slots[slot];
-    s.ga_done = false;
+    s.ga_out.invalidate();
+    s.ga_off.invalidate();
     const std::string fn = "pfac_documents_gather";
     if (n_bytes > (1ull << 32)) return fail(ctx, PFAC_E_ARG, fn + ": n_bytes must be at most 2^32");
     const unsigned char *in = d_input ? static_cast<const unsigned char *>(d_input) : s.input.p;
     if (!d_input && n_bytes > s.input.cap) return fail(ctx, PFAC_E_ARG, fn + ": n_bytes exceeds the slot's input buffer");
     const unsigned long long *off = reinterpret_cast<const unsigned long long *>(d_doc_offsets);
     if (!off) {
-        if (!s.doc_set || n_docs != s.doc_n)
+        if (!s.doc.done || n_docs + 1 != s.doc.n)
             return fail(ctx, PFAC_E_STATE, fn + ": the slot has no document offsets for this n_docs (pfac_slot_doc_offsets)");
-        off = s.doc_off.p;
+        off = s.doc.buf.p;
     }
-    const unsigned long long *ids = reinterpret_cast<const unsigned long long *>(d_ids);
-    if (!ids) {
-        if (!s.dm_done || !s.dm_own)
-            return fail(ctx, PFAC_E_STATE, fn + ": the slot holds no ids of a pfac_documents_matching (none yet, or they went to the caller's buffer)");
-        if (n_ids != s.dm_n) return fail(ctx, PFAC_E_ARG, fn + ": n_ids differs from the slot's last pfac_documents_matching");
-        ids = s.dm_out.p;
-    }
+    const unsigned long long *ids;
+    rc = s.dm_out.consume(ctx, fn, "ids of a pfac_documents_matching (n_ids of them)", d_ids, n_ids, &ids);
+    if (rc) return rc;
     if (n_docs >= (1ull << 32) || n_ids >= (1ull << 32)) return fail(ctx, PFAC_E_ARG, fn + ": n_docs and n_ids must be below 2^32");
     if (((uintptr_t)in | (uintptr_t)d_out) & 15) return fail(ctx, PFAC_E_ARG, fn + ": d_input and d_out must be 16-byte aligned");
     if (((uintptr_t)off | (uintptr_t)ids | (uintptr_t)d_out_offsets) & 7)
         return fail(ctx, PFAC_E_ARG, fn + ": d_doc_offsets, d_ids and d_out_offsets must be 8-byte aligned");
     USE_DEVICE(ctx);
-    const bool own_out = d_out == nullptr, own_off = d_out_offsets == nullptr;
     const uint64_t nb = (n_ids + RP_BLOCK - 1) / RP_BLOCK;
     const unsigned n_groups = (unsigned)((nb + RP_GROUP - 1) / RP_GROUP);
     uint64_t total = 0;
@@ -5373,21 +5399,20 @@ int pfac_documents_gather(pfac_ctx *ctx, int slot, const void *d_input, uint64_t
                            (unsigned long long)n_ids, off, (unsigned long long)n_docs, (unsigned long long)n_bytes, s.ga_x.p,
                            s.gsum.p, res);
         hipLaunchKernelGGL(pfac_scan_groups_kernel, dim3(1), dim3(1024), 0, s.stream, s.gsum.p, n_groups);
-        HIP_TRY(ctx, hipGetLastError());
-        HIP_TRY(ctx, hipMemcpyAsync(s.h_ctl + H_PASS, s.gsum.p + n_groups, 16, hipMemcpyDeviceToHost, s.stream));
-        HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+        rc = pass_words(ctx, s, s.gsum.p + n_groups, 2);
+        if (rc) return rc;
         if (host_u64(s, H_PASS1))
             return fail(ctx, PFAC_E_ARG, fn + ": every id must be below n_docs, and off[id] <= off[id + 1] <= n_bytes for every selected document");
         total = host_u64(s, H_PASS);
     }
     *out_bytes = total;
-    if (!own_out && total > out_cap)
+    if (d_out && total > out_cap)
         return fail(ctx, PFAC_E_OVERFLOW, fn + ": " + std::to_string(total) + " output bytes, out_cap is " + std::to_string(out_cap));
-    rc = own_off ? ensure_docs(ctx, s, s.ga_off, n_ids) : PFAC_OK;      // (everything allocated before the first write)
+    unsigned long long *oo;
+    unsigned char *out;
+    rc = s.ga_off.bind(ctx, s.stream, d_out_offsets, n_ids + 1, docs_cap(n_ids), &oo);      // (everything allocated before the first write)
+    if (!rc) rc = s.ga_out.bind(ctx, s.stream, d_out, total, align_up(total + total / 8, 4096), &out);
     if (rc) return rc;
-    rc = own_out ? s.ga_out.ensure(ctx, s.stream, total, align_up(total + total / 8, 4096)) : PFAC_OK;
-    if (rc) return rc;
-    unsigned long long *oo = own_off ? s.ga_off.p : reinterpret_cast<unsigned long long *>(d_out_offsets);
     if (n_ids) {
         hipLaunchKernelGGL(pfac_ga_offsets_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(4 * WAVE), 0, s.stream, ids,
                            (unsigned long long)n_ids, off, (const unsigned long long *)s.ga_x.p,
@@ -5397,23 +5422,15 @@ int pfac_documents_gather(pfac_ctx *ctx, int slot, const void *d_input, uint64_t
         HIP_TRY(ctx, hipMemsetAsync(oo, 0, 8, s.stream));    // no ids: the single offset 0
     }
     if (total) {
-        // one window of 1 KiB per wave while the output is small (every window's search runs in parallel), four above
-        uint64_t wins = total >= (64ull << 20) ? 4 : 1;
-        const uint64_t max_blocks = 1ull << 20;
-        const uint64_t per_block = (uint64_t)RP_WAVES * RP_WIN;
-        if ((total + per_block * wins - 1) / (per_block * wins) > max_blocks) wins = (total + per_block * max_blocks - 1) / (per_block * max_blocks);
-        const uint64_t blocks = (total + per_block * wins - 1) / (per_block * wins);
-        hipLaunchKernelGGL(pfac_ga_write_kernel, dim3((unsigned)blocks), dim3(RP_WAVES * WAVE), 0, s.stream, in,
+        const WriteGrid g = write_grid(total);
+        hipLaunchKernelGGL(pfac_ga_write_kernel, dim3(g.blocks), dim3(RP_WAVES * WAVE), 0, s.stream, in,
                            (unsigned long long)n_bytes, ids, (unsigned long long)n_ids, off, (const unsigned long long *)oo,
                            (const unsigned long long *)s.ga_x.p, (const unsigned long long *)s.gsum.p, (unsigned long long)total,
-                           (unsigned)wins, own_out ? s.ga_out.p : static_cast<unsigned char *>(d_out));
+                           g.wins, out);
         HIP_TRY(ctx, hipGetLastError());
     }
-    s.ga_bytes = total;
-    s.ga_ids = n_ids;
-    s.ga_own_out = own_out;
-    s.ga_own_off = own_off;
-    s.ga_done = true;
+    s.ga_out.commit(total, !d_out);
+    s.ga_off.commit(n_ids + 1, !d_out_offsets);
     return PFAC_OK;
 }
 
@@ -5421,25 +5438,14 @@ int pfac_documents_gather_d2h(pfac_ctx *ctx, int slot, void *host, uint64_t firs
     int rc = check_slot(ctx, slot);
     if (rc) return rc;
     Slot &s = ctx->slots[slot];
-    if (!s.ga_done) return fail(ctx, PFAC_E_STATE, "pfac_documents_gather_d2h without a finished pfac_documents_gather");
-    if (!s.ga_own_out) return fail(ctx, PFAC_E_STATE, "pfac_documents_gather_d2h: the last gather wrote into the caller's buffer");
-    if (first > s.ga_bytes || n > s.ga_bytes - first) return fail(ctx, PFAC_E_ARG, "pfac_documents_gather_d2h: [first, first + n) exceeds the output");
-    if (!host && n) return fail(ctx, PFAC_E_ARG, "null host buffer");
-    USE_DEVICE(ctx);
-    if (n) HIP_TRY(ctx, hipMemcpyAsync(host, s.ga_out.p + first, n, hipMemcpyDeviceToHost, s.stream));
-    return PFAC_OK;
+    return fetch(ctx, s, s.ga_out, "pfac_documents_gather_d2h", "pfac_documents_gather", host, first, n);
 }
 
 int pfac_documents_gather_offsets_d2h(pfac_ctx *ctx, int slot, uint64_t *host_out_offsets) {
     int rc = check_slot(ctx, slot);
     if (rc) return rc;
     Slot &s = ctx->slots[slot];
-    if (!s.ga_done) return fail(ctx, PFAC_E_STATE, "pfac_documents_gather_offsets_d2h without a finished pfac_documents_gather");
-    if (!s.ga_own_off) return fail(ctx, PFAC_E_STATE, "pfac_documents_gather_offsets_d2h: the last gather wrote its offsets into the caller's buffer");
-    if (!host_out_offsets) return fail(ctx, PFAC_E_ARG, "null host buffer");
-    USE_DEVICE(ctx);
-    HIP_TRY(ctx, hipMemcpyAsync(host_out_offsets, s.ga_off.p, (s.ga_ids + 1) * 8, hipMemcpyDeviceToHost, s.stream));
-    return PFAC_OK;
+    return fetch(ctx, s, s.ga_off, "pfac_documents_gather_offsets_d2h", "pfac_documents_gather", host_out_offsets, 0, s.ga_off.n);
 }
 
 int pfac_records_filter_words(pfac_ctx *ctx, int slot, const void *d_input, void *d_records, const uint64_t word_set[4],
@@ -5463,7 +5469,7 @@ int pfac_records_filter_words(pfac_ctx *ctx, int slot, const void *d_input, void
     if (!d_input && s.last_avail > s.input.cap) return fail(ctx, PFAC_E_ARG, fn + ": the scan read more than the slot's input buffer holds");
     if (!in && s.last_total) return fail(ctx, PFAC_E_ARG, fn + ": no input buffer");
     const unsigned long long *off = nullptr;
-    if (n_docs && !d_doc_offsets && (!s.doc_set || n_docs != s.doc_n))
+    if (n_docs && !d_doc_offsets && (!s.doc.done || n_docs + 1 != s.doc.n))
         return fail(ctx, PFAC_E_STATE, fn + ": the slot has no document offsets for this n_docs (pfac_slot_doc_offsets)");
     rc = n_docs ? resolve_docs(ctx, s, fn, d_doc_offsets, n_docs, 0, &off) : PFAC_OK;
     if (rc) return rc;
@@ -5477,13 +5483,7 @@ int pfac_records_filter_words(pfac_ctx *ctx, int slot, const void *d_input, void
     if (rc) return rc;
     unsigned long long *res = s.gsum.p;
     HIP_TRY(ctx, hipMemsetAsync(res, 0, 16, s.stream));
-    if (n_docs) {                                           // the offsets' rules (pfac_seg_count_kernel without tiles), in front of the filter
-        const unsigned vblocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_docs + 255) / 256, 4096));
-        hipLaunchKernelGGL(pfac_seg_count_kernel<4>, dim3(vblocks), dim3(256), 0, s.stream, (const void *)nullptr,
-                           (const unsigned long long *)nullptr, 0ull, 0ull, off, (unsigned long long)n_docs,
-                           (unsigned long long)s.last_owned, ctx->flen.p, (unsigned)ctx->num_final, (unsigned *)nullptr,
-                           (unsigned long long *)nullptr, 0u, res + 1);
-    }
+    if (n_docs) launch_offsets_check(ctx, s, off, n_docs, res + 1);     // in front of the filter
     if (n_groups) {
         const bool dk = n_docs != 0;
         auto fk = by_width(s.last_rec_bytes, [dk](auto w) { return dk ? pfac_filter_words_kernel<w(), true> : pfac_filter_words_kernel<w(), false>; });
@@ -5492,9 +5492,8 @@ int pfac_records_filter_words(pfac_ctx *ctx, int slot, const void *d_input, void
                            ws, (unsigned)edges, prev_byte, next_byte, off, (unsigned long long)n_docs,
                            (const unsigned long long *)(res + 1), res);
     }
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(s.h_ctl + H_PASS, res, 16, hipMemcpyDeviceToHost, s.stream));
-    HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+    rc = pass_words(ctx, s, res, 2);
+    if (rc) return rc;
     if (host_u64(s, H_PASS1)) return bad_doc_offsets(ctx, s, fn);
     // the kept records ARE the scan's records from here on: its match count (a repeated pfac_scan_finish reads it from
     // the result words), and a new record set for whatever selected from the old one
@@ -5519,7 +5518,8 @@ struct LlDocs {
 // the tile passes in their document form, and the document write.
 static int ll_select(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *d_records, uint32_t entry, pfac_record *d_out,
                      uint64_t out_cap, uint64_t *n_selected, uint32_t *exit_offset, const LlDocs *docs) {
-    s.ll_done = false;
+    s.ll_out.invalidate();
+    s.lld_first.invalidate();
     int rc = last_scan_usable(ctx, s, fn, SCAN_FINISHED | SCAN_LENGTHS | SCAN_TABLE);
     if (rc) return rc;
     // (PFAC_E_STATE, as pfac.h documents for the selections; the other passes report PFAC_E_OVERFLOW)
@@ -5537,43 +5537,32 @@ static int ll_select(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *
     if (rc) return rc;
     USE_DEVICE(ctx);
     const uint64_t n_tiles = s.last_tiles;
-    const bool own_out = d_out == nullptr, own_first = docs && !docs->first;
-    unsigned long long *first = docs ? reinterpret_cast<unsigned long long *>(docs->first) : nullptr;
+    unsigned long long *first = nullptr;
     auto done = [&](uint64_t total, uint32_t ex) {
         s.ll_seq = s.scan_seq;
         s.ll_entry = entry;
-        s.ll_n = total;
         s.ll_exit = ex;
-        s.ll_own_out = own_out;
         s.ll_docs = docs != nullptr;
         if (docs) {
-            s.lld_docs = n_docs;
             s.lld_gen = s.doc_gen;
             s.lld_own_off = docs->off == nullptr;
-            s.lld_own_first = own_first;
+            s.lld_first.commit(n_docs + 1, !docs->first);
         }
-        s.ll_done = true;
+        s.ll_out.commit(total, !d_out);
         return PFAC_OK;
     };
     if (n_tiles == 0) {                                     // nothing scanned: nothing picked, the cursor stays
         if (!docs) return done(0, entry);
-        // every document is empty: check the offsets (pfac_seg_count_kernel without tiles), then doc_first = 0
+        // every document is empty: check the offsets (no tiles: n_owned is 0), then doc_first = 0
         rc = ensure_gsum(ctx, s, 1);
         if (rc) return rc;
         HIP_TRY(ctx, hipMemsetAsync(s.gsum.p, 0, 8, s.stream));
-        const unsigned vblocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_docs + 255) / 256, 4096));
-        hipLaunchKernelGGL(pfac_seg_count_kernel<4>, dim3(vblocks), dim3(256), 0, s.stream, (const void *)nullptr,
-                           (const unsigned long long *)nullptr, 0ull, 0ull, off, (unsigned long long)n_docs, 0ull,
-                           ctx->flen.p, (unsigned)ctx->num_final, (unsigned *)nullptr, (unsigned long long *)nullptr, 0u, s.gsum.p);
-        HIP_TRY(ctx, hipGetLastError());
-        HIP_TRY(ctx, hipMemcpyAsync(s.h_ctl + H_PASS1, s.gsum.p, 8, hipMemcpyDeviceToHost, s.stream));
-        HIP_TRY(ctx, hipStreamSynchronize(s.stream));
-        if (host_u64(s, H_PASS1)) return bad_doc_offsets(ctx, s, fn);      // (no tiles: n_owned is 0)
-        if (own_first) {
-            rc = ensure_docs(ctx, s, s.lld_first, n_docs);
-            if (rc) return rc;
-            first = s.lld_first.p;
-        }
+        launch_offsets_check(ctx, s, off, n_docs, s.gsum.p);
+        rc = pass_words(ctx, s, s.gsum.p, 1, H_PASS1);
+        if (rc) return rc;
+        if (host_u64(s, H_PASS1)) return bad_doc_offsets(ctx, s, fn);
+        rc = s.lld_first.bind(ctx, s.stream, docs->first, n_docs + 1, docs_cap(n_docs), &first);
+        if (rc) return rc;
         HIP_TRY(ctx, hipMemsetAsync(first, 0, (n_docs + 1) * 8, s.stream));
         return done(0, entry);
     }
@@ -5612,9 +5601,8 @@ static int ll_select(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *
                        (unsigned)ctx->num_final, M, (unsigned short *)nullptr, (const unsigned short *)gat, bits, tcnt, s.gsum.p,
                        off, nd, (unsigned long long *)nullptr);
     hipLaunchKernelGGL(pfac_scan_groups_kernel, dim3(1), dim3(1024), 0, s.stream, s.gsum.p, n_groups);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(s.h_ctl + H_PASS, s.gsum.p + n_groups, docs ? 24 : 16, hipMemcpyDeviceToHost, s.stream));
-    HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+    rc = pass_words(ctx, s, s.gsum.p + n_groups, docs ? 3 : 2);
+    if (rc) return rc;
     const uint64_t total = host_u64(s, H_PASS);
     if (docs) {
         if (host_u64(s, H_PASS2)) return bad_doc_offsets(ctx, s, fn);
@@ -5622,17 +5610,14 @@ static int ll_select(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *
     }
     *n_selected = total;
     *exit_offset = s.h_ctl[H_PASS1];
-    if (!own_out && total > out_cap)
+    if (d_out && total > out_cap)
         return fail(ctx, PFAC_E_OVERFLOW, fn + ": " + std::to_string(total) + " records selected, out_cap is " + std::to_string(out_cap));
-    rc = own_out ? s.ll_out.ensure(ctx, s.stream, total, total + total / 8 + 4096) : PFAC_OK;
+    pfac_record *out;
+    rc = s.ll_out.bind(ctx, s.stream, d_out, total, total + total / 8 + 4096, &out);
     if (rc) return rc;
-    pfac_record *out = own_out ? s.ll_out.p : d_out;
     if (docs) {
-        if (own_first) {
-            rc = ensure_docs(ctx, s, s.lld_first, n_docs);
-            if (rc) return rc;
-            first = s.lld_first.p;
-        }
+        rc = s.lld_first.bind(ctx, s.stream, docs->first, n_docs + 1, docs_cap(n_docs), &first);
+        if (rc) return rc;
         auto wk = by_width(rb, [](auto w) { return pfac_ll_doc_write_kernel<w()>; });
         hipLaunchKernelGGL(wk, dim3((n_groups + 3) / 4), dim3(256), 0, s.stream, src, s.tile_index.p, nt, cap, off, nd, ctx->flen.p,
                            (unsigned)ctx->num_final, bits, tcnt, s.gsum.p, n_groups, out, first);
@@ -5674,28 +5659,17 @@ int pfac_leftmost_longest_d2h(pfac_ctx *ctx, int slot, pfac_record *host) {
     int rc = check_slot(ctx, slot);
     if (rc) return rc;
     Slot &s = ctx->slots[slot];
-    if (!s.ll_done) return fail(ctx, PFAC_E_STATE, "pfac_leftmost_longest_d2h without a finished pfac_records_leftmost_longest");
-    if (!s.ll_own_out) return fail(ctx, PFAC_E_STATE, "pfac_leftmost_longest_d2h: the last selection wrote into the caller's buffer");
-    if (!host && s.ll_n) return fail(ctx, PFAC_E_ARG, "null host buffer");
-    USE_DEVICE(ctx);
-    if (s.ll_n) HIP_TRY(ctx, hipMemcpyAsync(host, s.ll_out.p, s.ll_n * sizeof(pfac_record), hipMemcpyDeviceToHost, s.stream));
-    return PFAC_OK;
+    return fetch(ctx, s, s.ll_out, "pfac_leftmost_longest_d2h", "pfac_records_leftmost_longest", host, 0, s.ll_out.n);
 }
 
 int pfac_leftmost_longest_documents_d2h(pfac_ctx *ctx, int slot, pfac_record *host_records, uint64_t *host_doc_first) {
     int rc = check_slot(ctx, slot);
     if (rc) return rc;
     Slot &s = ctx->slots[slot];
-    if (!s.ll_done || !s.ll_docs)
-        return fail(ctx, PFAC_E_STATE, "pfac_leftmost_longest_documents_d2h without a finished pfac_records_leftmost_longest_documents");
-    if ((host_records && !s.ll_own_out) || (host_doc_first && !s.lld_own_first))
-        return fail(ctx, PFAC_E_STATE, "pfac_leftmost_longest_documents_d2h: the last selection wrote into the caller's buffers");
-    USE_DEVICE(ctx);
-    if (host_records && s.ll_n)
-        HIP_TRY(ctx, hipMemcpyAsync(host_records, s.ll_out.p, s.ll_n * sizeof(pfac_record), hipMemcpyDeviceToHost, s.stream));
-    if (host_doc_first)
-        HIP_TRY(ctx, hipMemcpyAsync(host_doc_first, s.lld_first.p, (s.lld_docs + 1) * 8, hipMemcpyDeviceToHost, s.stream));
-    return PFAC_OK;
+    const char *fn = "pfac_leftmost_longest_documents_d2h", *pass = "pfac_records_leftmost_longest_documents";
+    if (!s.ll_docs) return fail(ctx, PFAC_E_STATE, std::string(fn) + " without a finished " + pass);   // (the last selection was a plain one)
+    rc = fetch(ctx, s, s.ll_out, fn, pass, host_records, 0, s.ll_out.n, true);
+    return rc ? rc : fetch(ctx, s, s.lld_first, fn, pass, host_doc_first, 0, s.lld_first.n, true);
 }
 
 int pfac_table_set_replacements(pfac_ctx *ctx, const uint32_t *offsets, uint64_t n_states, const void *bytes, uint64_t n_bytes) {
@@ -5734,20 +5708,20 @@ struct RpDocs {
 
 static int rp_run(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *d_input, const pfac_record *d_sel, void *d_out,
                   uint64_t out_cap, uint64_t *out_bytes, const RpDocs *docs) {
-    s.rp_done = false;
-    s.rpd_done = false;
-    if (!s.scanned || !s.ll_done || s.ll_seq != s.scan_seq || (docs && !s.ll_docs))
+    s.rp_out.invalidate();
+    s.rpd_off.invalidate();
+    if (!s.scanned || !s.ll_out.done || s.ll_seq != s.scan_seq || (docs && !s.ll_docs))
         return fail(ctx, PFAC_E_STATE, fn + (docs ? " needs a pfac_records_leftmost_longest_documents since the slot's last scan"
                                                   : " needs a pfac_records_leftmost_longest since the slot's last scan"));
     if (!ctx->have_table || s.last_table != ctx->table_gen)
         return fail(ctx, PFAC_E_STATE, fn + ": the selection was made with an earlier table");
     if (!ctx->rep.p) return fail(ctx, PFAC_E_STATE, fn + ": no replacements for the uploaded table (pfac_table_set_replacements)");
     if (!ctx->flen.p) return fail(ctx, PFAC_E_STATE, fn + ": no final-state lengths for the uploaded table");
-    if (!d_sel && !s.ll_own_out)
-        return fail(ctx, PFAC_E_STATE, fn + ": the selection went to the caller's buffer; pass it as d_sel");
-    const pfac_record *sel = d_sel ? d_sel : s.ll_out.p;
+    const pfac_record *sel;
+    int rc = s.ll_out.consume(ctx, fn, "selection (d_sel)", d_sel, ANY_N, &sel);
+    if (rc) return rc;
     const unsigned char *in = d_input ? static_cast<const unsigned char *>(d_input) : s.input.p;
-    const uint64_t n = s.ll_n, n_owned = s.last_owned, n_avail = s.last_avail, entry = s.ll_entry, ex = s.ll_exit;
+    const uint64_t n = s.ll_out.n, n_owned = s.last_owned, n_avail = s.last_avail, entry = s.ll_entry, ex = s.ll_exit;
     if (((uintptr_t)d_out & 15) || ((uintptr_t)in & 15) || ((uintptr_t)d_sel & 7))
         return fail(ctx, PFAC_E_ARG, fn + ": misaligned buffer (d_input and d_out 16 B, d_sel 8 B)");
     if (n_owned > entry && !in) return fail(ctx, PFAC_E_ARG, fn + ": no input buffer");
@@ -5756,17 +5730,14 @@ static int rp_run(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *d_i
     unsigned long long *dout_off = nullptr;
     if (docs) {
         doff = reinterpret_cast<const unsigned long long *>(docs->off);
-        dfirst = reinterpret_cast<const unsigned long long *>(docs->first);
         dout_off = reinterpret_cast<unsigned long long *>(docs->out_off);
         if (!doff) {
             if (!s.lld_own_off) return fail(ctx, PFAC_E_STATE, fn + ": the selection cut the caller's document offsets; pass them as d_doc_offsets");
-            if (s.lld_gen != s.doc_gen || !s.doc_set) return fail(ctx, PFAC_E_STATE, fn + ": the slot's document offsets changed since the selection");
-            doff = s.doc_off.p;
+            if (s.lld_gen != s.doc_gen || !s.doc.done) return fail(ctx, PFAC_E_STATE, fn + ": the slot's document offsets changed since the selection");
+            doff = s.doc.buf.p;
         }
-        if (!dfirst) {
-            if (!s.lld_own_first) return fail(ctx, PFAC_E_STATE, fn + ": the selection's doc_first went to the caller's buffer; pass it as d_doc_first");
-            dfirst = s.lld_first.p;
-        }
+        rc = s.lld_first.consume(ctx, fn, "doc_first of the selection (d_doc_first)", docs->first, ANY_N, &dfirst);
+        if (rc) return rc;
         if (((uintptr_t)doff & 7) || ((uintptr_t)dfirst & 7) || ((uintptr_t)dout_off & 7))
             return fail(ctx, PFAC_E_ARG, fn + ": device buffers must be 8-byte aligned");
     }
@@ -5776,7 +5747,6 @@ static int rp_run(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *d_i
     const uint64_t n_groups = (nb + RP_GROUP - 1) / RP_GROUP;
     if (n_groups >= (1ull << 32)) return fail(ctx, PFAC_E_ARG, fn + ": too many picks");
     unsigned long long *X = nullptr;
-    int rc;
     if (n) {
         const size_t need = nb * 8;
         rc = s.rp_tmp.ensure(ctx, s.stream, need, need + need / 4 + 4096);
@@ -5790,9 +5760,8 @@ static int rp_run(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *d_i
                            (unsigned long long)n, (unsigned long long)entry, (unsigned long long)n_owned, ctx->flen.p,
                            ctx->rep_off.p, (unsigned)ctx->num_final, X, s.gsum.p, res);
         hipLaunchKernelGGL(pfac_scan_groups_kernel, dim3(1), dim3(1024), 0, s.stream, s.gsum.p, (unsigned)n_groups);
-        HIP_TRY(ctx, hipGetLastError());
-        HIP_TRY(ctx, hipMemcpyAsync(s.h_ctl + H_PASS, s.gsum.p + n_groups, 24, hipMemcpyDeviceToHost, s.stream));
-        HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+        rc = pass_words(ctx, s, s.gsum.p + n_groups, 3);
+        if (rc) return rc;
         delta = (int64_t)host_u64(s, H_PASS);
         const uint64_t err = host_u64(s, H_PASS1), c_last = host_u64(s, H_PASS2);
         if (err || (c_last > n_owned ? c_last - n_owned : 0) != ex)
@@ -5802,33 +5771,27 @@ static int rp_run(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *d_i
     if (total < 0) return fail(ctx, PFAC_E_INTERNAL, fn + ": negative output length");
     const uint64_t ob = (uint64_t)total;
     *out_bytes = ob;
-    const bool own_out = d_out == nullptr;
-    if (!own_out && ob > out_cap)
+    if (d_out && ob > out_cap)
         return fail(ctx, PFAC_E_OVERFLOW, fn + ": " + std::to_string(ob) + " output bytes, out_cap is " + std::to_string(out_cap));
-    const uint64_t n_docs = s.lld_docs;
+    const uint64_t n_docs = docs ? s.lld_first.n - 1 : 0;
+    unsigned long long *oo = nullptr;
     if (docs) {                                             // (everything allocated before the first write)
-        rc = dout_off ? PFAC_OK : ensure_docs(ctx, s, s.rpd_off, n_docs);
+        rc = s.rpd_off.bind(ctx, s.stream, dout_off, n_docs + 1, docs_cap(n_docs), &oo);
         if (!rc && n) rc = s.rpd_tmp.ensure(ctx, s.stream, n + 1, n + 1 + n / 8 + 4096);
         if (rc) return rc;
     }
-    rc = own_out ? s.rp_out.ensure(ctx, s.stream, ob, align_up(ob + ob / 8, 4096)) : PFAC_OK;
+    unsigned char *out;
+    rc = s.rp_out.bind(ctx, s.stream, d_out, ob, align_up(ob + ob / 8, 4096), &out);
     if (rc) return rc;
-    unsigned char *out = own_out ? s.rp_out.p : static_cast<unsigned char *>(d_out);
     if (ob) {
-        // one window of 1 KiB per wave while the output is small (every window's search runs in parallel), four above
-        uint64_t wins = ob >= (64ull << 20) ? 4 : 1;
-        const uint64_t max_blocks = 1ull << 20;
-        const uint64_t per_block = (uint64_t)RP_WAVES * RP_WIN;
-        if ((ob + per_block * wins - 1) / (per_block * wins) > max_blocks) wins = (ob + per_block * max_blocks - 1) / (per_block * max_blocks);
-        const uint64_t blocks = (ob + per_block * wins - 1) / (per_block * wins);
-        hipLaunchKernelGGL(pfac_rp_write_kernel, dim3((unsigned)blocks), dim3(RP_WAVES * WAVE), 0, s.stream, in,
+        const WriteGrid g = write_grid(ob);
+        hipLaunchKernelGGL(pfac_rp_write_kernel, dim3(g.blocks), dim3(RP_WAVES * WAVE), 0, s.stream, in,
                            (unsigned long long)n_avail, sel, (unsigned long long)n, (unsigned long long)entry, ctx->flen.p,
                            ctx->rep_off.p, ctx->rep.p, (unsigned long long)ctx->rep.cap, X, s.gsum.p,
-                           (unsigned long long)ob, (unsigned)wins, out);
+                           (unsigned long long)ob, g.wins, out);
         HIP_TRY(ctx, hipGetLastError());
     }
     if (docs) {
-        unsigned long long *oo = dout_off ? dout_off : s.rpd_off.p;
         if (n)
             hipLaunchKernelGGL(pfac_rp_doc_delta_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(4 * WAVE), 0, s.stream, sel,
                                (unsigned long long)n, ctx->flen.p, ctx->rep_off.p, X, s.gsum.p, s.rpd_tmp.p);
@@ -5836,13 +5799,9 @@ static int rp_run(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *d_i
         hipLaunchKernelGGL(pfac_rp_doc_offsets_kernel, dim3(oblocks), dim3(256), 0, s.stream, doff, dfirst,
                            (unsigned long long)n_docs, (const unsigned long long *)s.rpd_tmp.p, (unsigned long long)n, oo);
         HIP_TRY(ctx, hipGetLastError());
-        s.rpd_docs = n_docs;
-        s.rpd_own_off = dout_off == nullptr;
-        s.rpd_done = true;
+        s.rpd_off.commit(n_docs + 1, !dout_off);
     }
-    s.rp_bytes = ob;
-    s.rp_own_out = own_out;
-    s.rp_done = true;
+    s.rp_out.commit(ob, !d_out);
     return PFAC_OK;
 }
 
@@ -5869,25 +5828,14 @@ int pfac_replace_documents_d2h(pfac_ctx *ctx, int slot, uint64_t *host_out_offse
     int rc = check_slot(ctx, slot);
     if (rc) return rc;
     Slot &s = ctx->slots[slot];
-    if (!s.rpd_done) return fail(ctx, PFAC_E_STATE, "pfac_replace_documents_d2h without a finished pfac_replace_documents");
-    if (!s.rpd_own_off) return fail(ctx, PFAC_E_STATE, "pfac_replace_documents_d2h: the last replacement wrote its offsets into the caller's buffer");
-    if (!host_out_offsets) return fail(ctx, PFAC_E_ARG, "null host buffer");
-    USE_DEVICE(ctx);
-    HIP_TRY(ctx, hipMemcpyAsync(host_out_offsets, s.rpd_off.p, (s.rpd_docs + 1) * 8, hipMemcpyDeviceToHost, s.stream));
-    return PFAC_OK;
+    return fetch(ctx, s, s.rpd_off, "pfac_replace_documents_d2h", "pfac_replace_documents", host_out_offsets, 0, s.rpd_off.n);
 }
 
 int pfac_replace_d2h(pfac_ctx *ctx, int slot, void *host, uint64_t first, uint64_t n) {
     int rc = check_slot(ctx, slot);
     if (rc) return rc;
     Slot &s = ctx->slots[slot];
-    if (!s.rp_done) return fail(ctx, PFAC_E_STATE, "pfac_replace_d2h without a finished pfac_replace_leftmost_longest");
-    if (!s.rp_own_out) return fail(ctx, PFAC_E_STATE, "pfac_replace_d2h: the last replacement wrote into the caller's buffer");
-    if (first > s.rp_bytes || n > s.rp_bytes - first) return fail(ctx, PFAC_E_ARG, "pfac_replace_d2h: [first, first + n) exceeds the output");
-    if (!host && n) return fail(ctx, PFAC_E_ARG, "null host buffer");
-    USE_DEVICE(ctx);
-    if (n) HIP_TRY(ctx, hipMemcpyAsync(host, s.rp_out.p + first, n, hipMemcpyDeviceToHost, s.stream));
-    return PFAC_OK;
+    return fetch(ctx, s, s.rp_out, "pfac_replace_d2h", "pfac_replace_leftmost_longest / pfac_replace_documents", host, first, n);
 }
 
 int pfac_fill_tiled(pfac_ctx *ctx, int slot, void *d_dst, uint64_t n, const void *host_pattern, uint32_t period, uint64_t phase) {

@@ -88,6 +88,24 @@ class GpuMatcher:
             raise PfacError(rc, (self._L.pfac_last_error(self._ctx) or b"").decode())
         return rc
 
+    def _counted(self, rc: int, n, attr: str) -> int:
+        """The count ``n`` a pass returned through its pointer; a failed pass raises PfacError with that count (exact
+        after an overflow) as its attribute ``attr``."""
+        if rc:
+            e = PfacError(rc, (self._L.pfac_last_error(self._ctx) or b"").decode())
+            setattr(e, attr, n.value)
+            raise e
+        return n.value
+
+    def _to_host(self, slot: int, fetch, *shapes):
+        """One fetch of a slot-owned result into new host arrays, one per ``(n, dtype)`` of ``shapes``: ``fetch`` gets
+        their data pointers (None for an empty array), is checked, and the slot is synchronised.  Returns the array, or
+        the tuple of them."""
+        out = tuple(np.empty(int(n), dtype=dt) for n, dt in shapes)
+        self._check(fetch(*(a.ctypes.data if a.size else None for a in out)))
+        self.sync(slot)
+        return out[0] if len(out) == 1 else out
+
     def close(self):
         if getattr(self, "_ctx", None):
             self._L.pfac_ctx_destroy(self._ctx)
@@ -367,10 +385,8 @@ class GpuMatcher:
     def state_counts_to_host(self, slot: int = 0) -> np.ndarray:
         """The slot-owned counts of ``count_states`` / ``count_selection_states``: uint64[num_final] of the table they
         were counted with."""
-        out = np.empty(self._cnt_n.get(slot, 0), dtype=np.uint64)   # (no counts yet: the call says PFAC_E_STATE)
-        self._check(self._L.pfac_state_counts_d2h(self._ctx, slot, out.ctypes.data if out.size else None))
-        self.sync(slot)
-        return out
+        return self._to_host(slot, lambda p: self._L.pfac_state_counts_d2h(self._ctx, slot, p),
+                             (self._cnt_n.get(slot, 0), np.uint64))     # (no counts yet: the call says PFAC_E_STATE)
 
     def count_patterns(self, data, n_owned: Optional[int] = None, slot: int = 0, whole_words=False, prev_byte: int = -1,
                        next_byte: int = -1, accumulate: bool = False) -> np.ndarray:
@@ -436,18 +452,12 @@ class GpuMatcher:
         n = C.c_uint64(0)
         rc = self._L.pfac_records_segment(self._ctx, slot, _ptr(d_records), _ptr(d_doc_offsets), int(n_docs), _ptr(d_out),
                                           int(out_cap), _ptr(d_doc_first), C.byref(n))
-        if rc:
-            e = PfacError(rc, (self._L.pfac_last_error(self._ctx) or b"").decode())
-            e.n_kept = n.value
-            raise e
-        return n.value
+        return self._counted(rc, n, "n_kept")
 
     def segment_to_host(self, n_kept: int, n_docs: int, slot: int = 0) -> Tuple[np.ndarray, np.ndarray]:
         """(doc_first uint64[n_docs + 1], records) of the slot's last ``segment_records`` into slot-owned buffers."""
-        rec = np.empty(int(n_kept), dtype=RECORD_DTYPE)
-        first = np.empty(int(n_docs) + 1, dtype=np.uint64)
-        self._check(self._L.pfac_segment_d2h(self._ctx, slot, rec.ctypes.data if n_kept else None, first.ctypes.data))
-        self.sync(slot)
+        rec, first = self._to_host(slot, lambda r, f: self._L.pfac_segment_d2h(self._ctx, slot, r, f),
+                                   (n_kept, RECORD_DTYPE), (int(n_docs) + 1, np.uint64))
         return first, rec
 
     def _ensure_final_lengths(self) -> None:
@@ -503,10 +513,8 @@ class GpuMatcher:
         """Offsets [first, first + n) of the slot's document offsets (default: all ``n_docs + 1``), whichever call set
         them."""
         n = int(n_docs) + 1 - int(first) if n is None else int(n)
-        out = np.empty(max(n, 0), dtype=np.uint64)
-        self._check(self._L.pfac_slot_doc_offsets_d2h(self._ctx, slot, out.ctypes.data if out.size else None, int(first), n))
-        self.sync(slot)
-        return out
+        return self._to_host(slot, lambda p: self._L.pfac_slot_doc_offsets_d2h(self._ctx, slot, p, int(first), n),
+                             (max(n, 0), np.uint64))
 
     def matching_documents(self, n_docs: int, invert: bool = False, d_doc_first=None, d_out=None, out_cap: int = 0,
                            slot: int = 0, before: int = 0, after: int = 0) -> int:
@@ -529,18 +537,11 @@ class GpuMatcher:
         else:
             rc = self._L.pfac_documents_matching(self._ctx, slot, _ptr(d_doc_first), int(n_docs),
                                                  PFAC_DOCS_INVERT if invert else 0, _ptr(d_out), int(out_cap), C.byref(n))
-        if rc:
-            e = PfacError(rc, (self._L.pfac_last_error(self._ctx) or b"").decode())
-            e.n_matching = n.value
-            raise e
-        return n.value
+        return self._counted(rc, n, "n_matching")
 
     def matching_documents_to_host(self, n: int, slot: int = 0) -> np.ndarray:
         """The ids (uint64[n]) of the slot's last ``matching_documents`` into its slot-owned buffer."""
-        out = np.empty(int(n), dtype=np.uint64)
-        self._check(self._L.pfac_documents_matching_d2h(self._ctx, slot, out.ctypes.data if n else None))
-        self.sync(slot)
-        return out
+        return self._to_host(slot, lambda p: self._L.pfac_documents_matching_d2h(self._ctx, slot, p), (n, np.uint64))
 
     def gather_documents(self, n_docs: int, n_ids: int, n_bytes: int, d_input=None, d_doc_offsets=None, d_ids=None,
                          d_out=None, out_cap: int = 0, d_out_offsets=None, slot: int = 0) -> int:
@@ -554,25 +555,17 @@ class GpuMatcher:
         n = C.c_uint64(0)
         rc = self._L.pfac_documents_gather(self._ctx, slot, _ptr(d_input), int(n_bytes), _ptr(d_doc_offsets), int(n_docs),
                                            _ptr(d_ids), int(n_ids), _ptr(d_out), int(out_cap), _ptr(d_out_offsets), C.byref(n))
-        if rc:
-            e = PfacError(rc, (self._L.pfac_last_error(self._ctx) or b"").decode())
-            e.out_bytes = n.value
-            raise e
-        return n.value
+        return self._counted(rc, n, "out_bytes")
 
     def gathered_to_host(self, n: int, slot: int = 0, first: int = 0) -> np.ndarray:
         """Bytes [first, first + n) of the slot's last ``gather_documents`` into its slot-owned buffer."""
-        out = np.empty(int(n), dtype=np.uint8)
-        self._check(self._L.pfac_documents_gather_d2h(self._ctx, slot, out.ctypes.data if n else None, int(first), int(n)))
-        self.sync(slot)
-        return out
+        return self._to_host(slot, lambda p: self._L.pfac_documents_gather_d2h(self._ctx, slot, p, int(first), int(n)),
+                             (n, np.uint8))
 
     def gathered_offsets_to_host(self, n_ids: int, slot: int = 0) -> np.ndarray:
         """The output offsets (uint64[n_ids + 1]) of the slot's last ``gather_documents`` into its slot-owned buffer."""
-        out = np.empty(int(n_ids) + 1, dtype=np.uint64)
-        self._check(self._L.pfac_documents_gather_offsets_d2h(self._ctx, slot, out.ctypes.data))
-        self.sync(slot)
-        return out
+        return self._to_host(slot, lambda p: self._L.pfac_documents_gather_offsets_d2h(self._ctx, slot, p),
+                             (int(n_ids) + 1, np.uint64))
 
     def _scan_lines(self, data, delimiter, slot: int, whole_words=False, fetch_offsets: bool = True) -> Tuple[Optional[np.ndarray], int]:
         """``_scan_docs`` for one buffer whose documents end at ``delimiter``: upload, scan, offsets made on the device
@@ -656,18 +649,11 @@ class GpuMatcher:
         ex = C.c_uint32(0)
         rc = self._L.pfac_records_leftmost_longest(self._ctx, slot, _ptr(d_records), int(entry), _ptr(d_out), int(out_cap),
                                                    C.byref(n), C.byref(ex))
-        if rc:
-            e = PfacError(rc, (self._L.pfac_last_error(self._ctx) or b"").decode())
-            e.n_selected = n.value
-            raise e
-        return n.value, ex.value
+        return self._counted(rc, n, "n_selected"), ex.value
 
     def selection_to_host(self, n_selected: int, slot: int = 0) -> np.ndarray:
         """The records of the slot's last ``select_leftmost_longest`` into its slot-owned buffer, ascending pos."""
-        rec = np.empty(int(n_selected), dtype=RECORD_DTYPE)
-        self._check(self._L.pfac_leftmost_longest_d2h(self._ctx, slot, rec.ctypes.data if n_selected else None))
-        self.sync(slot)
-        return rec
+        return self._to_host(slot, lambda p: self._L.pfac_leftmost_longest_d2h(self._ctx, slot, p), (n_selected, RECORD_DTYPE))
 
     def scan_leftmost_longest(self, data, n_owned: Optional[int] = None, entry: int = 0, slot: int = 0, whole_words=False,
                               prev_byte: int = -1, next_byte: int = -1) -> Tuple[np.ndarray, int]:
@@ -701,20 +687,13 @@ class GpuMatcher:
         rc = self._L.pfac_records_leftmost_longest_documents(self._ctx, slot, _ptr(d_records), _ptr(d_doc_offsets),
                                                              int(n_docs), _ptr(d_out), int(out_cap), _ptr(d_doc_first),
                                                              C.byref(n))
-        if rc:
-            e = PfacError(rc, (self._L.pfac_last_error(self._ctx) or b"").decode())
-            e.n_selected = n.value
-            raise e
-        return n.value
+        return self._counted(rc, n, "n_selected")
 
     def doc_selection_to_host(self, n_selected: int, n_docs: int, slot: int = 0) -> Tuple[np.ndarray, np.ndarray]:
         """(doc_first uint64[n_docs + 1], records) of the slot's last ``select_leftmost_longest_documents`` into
         slot-owned buffers; positions relative to the scan."""
-        rec = np.empty(int(n_selected), dtype=RECORD_DTYPE)
-        first = np.empty(int(n_docs) + 1, dtype=np.uint64)
-        self._check(self._L.pfac_leftmost_longest_documents_d2h(self._ctx, slot, rec.ctypes.data if n_selected else None,
-                                                                first.ctypes.data))
-        self.sync(slot)
+        rec, first = self._to_host(slot, lambda r, f: self._L.pfac_leftmost_longest_documents_d2h(self._ctx, slot, r, f),
+                                   (n_selected, RECORD_DTYPE), (int(n_docs) + 1, np.uint64))
         return first, rec
 
     def select_documents(self, docs, slot: int = 0, whole_words=False) -> Tuple[np.ndarray, np.ndarray]:
@@ -759,18 +738,11 @@ class GpuMatcher:
         n = C.c_uint64(0)
         rc = self._L.pfac_replace_leftmost_longest(self._ctx, slot, _ptr(d_input), _ptr(d_sel), _ptr(d_out), int(out_cap),
                                                    C.byref(n))
-        if rc:
-            e = PfacError(rc, (self._L.pfac_last_error(self._ctx) or b"").decode())
-            e.out_bytes = n.value
-            raise e
-        return n.value
+        return self._counted(rc, n, "out_bytes")
 
     def replacement_to_host(self, n: int, slot: int = 0, first: int = 0) -> np.ndarray:
         """Bytes [first, first + n) of the slot's last ``replace_selection`` into its slot-owned buffer."""
-        out = np.empty(int(n), dtype=np.uint8)
-        self._check(self._L.pfac_replace_d2h(self._ctx, slot, out.ctypes.data if n else None, int(first), int(n)))
-        self.sync(slot)
-        return out
+        return self._to_host(slot, lambda p: self._L.pfac_replace_d2h(self._ctx, slot, p, int(first), int(n)), (n, np.uint8))
 
     def replace(self, data, n_owned: Optional[int] = None, entry: int = 0, slot: int = 0, whole_words=False,
                 prev_byte: int = -1, next_byte: int = -1) -> Tuple[np.ndarray, int]:
@@ -802,18 +774,12 @@ class GpuMatcher:
         n = C.c_uint64(0)
         rc = self._L.pfac_replace_documents(self._ctx, slot, _ptr(d_input), _ptr(d_sel), _ptr(d_doc_offsets),
                                             _ptr(d_doc_first), _ptr(d_out), int(out_cap), _ptr(d_out_offsets), C.byref(n))
-        if rc:
-            e = PfacError(rc, (self._L.pfac_last_error(self._ctx) or b"").decode())
-            e.out_bytes = n.value
-            raise e
-        return n.value
+        return self._counted(rc, n, "out_bytes")
 
     def replacement_doc_offsets_to_host(self, n_docs: int, slot: int = 0) -> np.ndarray:
         """The output offsets (uint64[n_docs + 1]) of the slot's last ``replace_selection_documents``."""
-        out = np.empty(int(n_docs) + 1, dtype=np.uint64)
-        self._check(self._L.pfac_replace_documents_d2h(self._ctx, slot, out.ctypes.data))
-        self.sync(slot)
-        return out
+        return self._to_host(slot, lambda p: self._L.pfac_replace_documents_d2h(self._ctx, slot, p),
+                             (int(n_docs) + 1, np.uint64))
 
     def replace_documents(self, docs, slot: int = 0, whole_words=False) -> Tuple[np.ndarray, np.ndarray]:
         """Find-and-replace in a batch of independent documents (``docs`` as ``scan_documents`` takes it) in one scan,
