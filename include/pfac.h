@@ -280,8 +280,13 @@ int pfac_scan_async(pfac_ctx *ctx, int slot, const void *d_input, uint64_t n_own
 int pfac_scan_finish(pfac_ctx *ctx, int slot, uint64_t *n_matches);
 /* After pfac_scan_finish: a record capacity that the same scan fits (the finished scan's heap use + margin). */
 int pfac_scan_capacity_hint(pfac_ctx *ctx, int slot, uint64_t *capacity);
-/* Kernel time of the slot's last scan (hipEvent pair around the launch, the
- * analogue of "2. MASTER: The elapsed time is %f ms", master_kernel.cu:400-421). */
+/* Kernel time of the slot's last scan (the analogue of "2. MASTER: The elapsed
+ * time is %f ms", master_kernel.cu:400-421): first workgroup in -> last
+ * workgroup out, taken by the kernel itself from the device's constant-rate
+ * clock.  The dispatch carries no events for it and pays nothing for it; the
+ * figure leaves out the dispatch's ramp and the fence at its end, which an
+ * event pair around the launch includes.  0 for an empty scan.  Waits for the
+ * scan if it is still running. */
 int pfac_scan_elapsed_ms(pfac_ctx *ctx, int slot, float *ms);
 /* D2H of records [first, first+n) of the sorted sequence as pfac_record (the compact replacement of the dense
  * cudaMemcpy D2H, master_kernel.cu:428).  Asynchronous; pfac_slot_sync() completes it.  n == 0 does nothing.

@@ -51,6 +51,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <chrono>
 #include <mutex>
 #include <type_traits>
 #include <string>
@@ -150,6 +151,11 @@ constexpr unsigned CTL_WORDS = 64u * (TICKET_WAYS + 1);   // control header in 3
 constexpr unsigned SPIN_MAX = 1u << 22;    // bounded spins (default; PFAC_SPIN_MAX): ~0.5 s of LDS polls, seconds of global polls
 // words of the control header (first ticket line) the kernel reports through: device memory, ordinary device atomics
 constexpr unsigned CTL_ERR = 32, CTL_OVF = 33, CTL_DONE = 34, CTL_OVF2 = 35, CTL_TOTAL = 36 /* u64: matches */;
+constexpr unsigned CTL_T0 = 38;            // u64: ~(earliest entry time of the first T0_GROUPS workgroups), folded with a max (the header starts at zero)
+constexpr unsigned T0_GROUPS = 8;          // (one workgroup per XCD: the dispatcher deals the first eight round-robin)
+// words of the host-visible result block (ScanArgs::res, Slot::h_ctl) behind the counts
+constexpr unsigned RES_DONE = 7;           // stored LAST by the last workgroup to leave, system-scope release: the scan's completion
+constexpr unsigned RES_T0 = 16, RES_T1 = 18;       // u64 each: first workgroup in / last workgroup out, s_memrealtime ticks
 constexpr unsigned CTL_CURSOR = 64u * TICKET_WAYS;     // u64: first free record of the heap (on a line of its own)
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
@@ -209,9 +215,11 @@ struct ScanArgs {
     unsigned ticket_ways;          // counters in use: min(TICKET_WAYS, grid)
     uint4 *zero_next;              // the slot's OTHER control header: this launch zeroes it for the next one ...
     unsigned zero_vec;             // ... this many 16-byte units (no memset between back-to-back scans)
-    unsigned *res;                 // host-mapped pinned words the host reads after the stream sync, no D2H copy, written with
-                                   // plain stores by the last workgroup to leave: [0..1] matches (u64), [2] error flags,
-                                   // [3] tiles denser than sparse_cap, [4..5] heap cursor = records of capacity used (u64)
+    unsigned *res;                 // host-mapped pinned words, no D2H copy, written with plain stores by the last workgroup
+                                   // to leave: [0..1] matches (u64), [2] error flags, [3] tiles denser than sparse_cap,
+                                   // [4..5] heap cursor = records of capacity used (u64), [6] tiles denser than small_cap,
+                                   // [RES_T0], [RES_T1] the kernel's own start and end time -- and then [RES_DONE] = 1 with a
+                                   // system-scope release: the host waits for THAT word, the dispatch carries no signal
     unsigned long long *dbg;       // PFAC_TRACE_BUILD only: per-round timestamps (10 ns units), else null
 };
 
@@ -1866,6 +1874,11 @@ __global__ __launch_bounds__(WAVE * MAX_WAVES_PER_BLOCK) void pfac_scan_kernel(S
 #ifdef PFAC_TRACE_BUILD                        // column 15 of a traced workgroup's rows 0 / 1 / 2: entry, tables staged, last wave out
     if (a.dbg && blockIdx.x < 8 && threadIdx.x == 0) a.dbg[((size_t)blockIdx.x * 64 + 0) * 32 + 15] = __builtin_amdgcn_s_memrealtime();
 #endif
+    // the kernel's start time, by its own clock: the earliest entry among the first workgroups (no return value: the lane
+    // does not wait for the atomic)
+    if (blockIdx.x < T0_GROUPS && threadIdx.x == 0)
+        (void)__hip_atomic_fetch_max(reinterpret_cast<unsigned long long *>(a.ctl + CTL_T0), ~__builtin_amdgcn_s_memrealtime(),
+                                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     scan_body<TLDS, W8, ROOT, FUSED, NW, NB>(a, smem, err);
     // ---- leaving: the last wave of the workgroup counts the workgroup out; the last workgroup of the grid copies
     // the error flags and the dense-tile count from the control header (device memory) to the host-visible result
@@ -1892,6 +1905,13 @@ __global__ __launch_bounds__(WAVE * MAX_WAVES_PER_BLOCK) void pfac_scan_kernel(S
                 a.res[3] = __hip_atomic_load(&a.ctl[CTL_OVF], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 a.res[4] = (unsigned)cur; a.res[5] = (unsigned)(cur >> 32);
                 a.res[6] = __hip_atomic_load(&a.ctl[CTL_OVF2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                // first workgroup in -> last workgroup out, then the completion word: ONE wave, once per launch, releases
+                // the result words above to the host (not the per-workgroup write-back that the comment above is about)
+                const unsigned long long t0 = ~__hip_atomic_load(reinterpret_cast<unsigned long long *>(a.ctl + CTL_T0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                const unsigned long long t1 = __builtin_amdgcn_s_memrealtime();
+                a.res[RES_T0] = (unsigned)t0; a.res[RES_T0 + 1] = (unsigned)(t0 >> 32);
+                a.res[RES_T1] = (unsigned)t1; a.res[RES_T1 + 1] = (unsigned)(t1 >> 32);
+                __hip_atomic_store(&a.res[RES_DONE], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
             }
         }
     }
@@ -3801,10 +3821,13 @@ uint64_t docs_cap(uint64_t n_docs) { return n_docs + 1 < 4096 ? 4096 : n_docs + 
 enum : int {
     H_MATCHES = 0,                        // written by the scan kernel: matches, ...
     H_USED = 4,                           // ... heap records used
+    H_DONE = RES_DONE,                    // (one 32-bit word) the scan's completion: cleared by pfac_scan_async, set by the kernel
     H_CHECKSUM = 8,                       // pfac_records_checksum
     H_PASS = 10,                          // what a pass copies back from behind its group prefixes: the total, ...
     H_PASS1 = 12,                         // ... the word behind it (segment: bad offsets; selection: exit offset; replace: error), ...
     H_PASS2 = 14,                         // ... and the one behind that (document selection: bad offsets; replace: c_{n-1})
+    H_T0 = RES_T0, H_T1 = RES_T1,         // written by the scan kernel: its start and end by its own clock (ticks)
+    H_CTL_BYTES = 128,
 };
 
 struct Slot {
@@ -3825,11 +3848,12 @@ struct Slot {
     bool clean[2] = {false, false};       // header known to be zero
     int flip = 0;                         // header of the next scan
     unsigned *h_ctl = nullptr;            // pinned, device-visible: [0..1] matches, [2] err, [3] dense tiles, [4..5] heap
-                                          // records used (written by the kernel), [8..9] checksum, [10..15] a pass's
-                                          // results (the H_ constants above name the 64-bit ones)
+                                          // records used, [7] done, [16..19] start and end time (written by the kernel),
+                                          // [8..9] checksum, [10..15] a pass's results (the H_ constants above name them)
     unsigned *d_res = nullptr;            // device-side address of h_ctl
     DevBuf<unsigned long long> sum;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;      // PFAC_EVENT_TIMING only (else null): start / stop events on the scan's dispatch
+    double spin_ms = 0;                   // how long wait_scan polls for the pending scan before it asks the stream
     hipEvent_t ev_h2d = nullptr;          // behind the slot's last pfac_slot_h2d: the host buffer may be reused once it has fired
     hipEvent_t ev_rd = nullptr;           // recorded on the slot's stream at a pfac_slot_h2d: behind every queued reader of the input
     bool h2d_issued = false;
@@ -3930,6 +3954,12 @@ struct pfac_ctx {
     unsigned child0 = 0, child1 = 0;
     // tuning / test knobs, read from the environment ONCE, when a table is installed
     unsigned spin_max = SPIN_MAX, fault = 0, ticket_ways_knob = 0;
+    bool event_timing = false;            // PFAC_EVENT_TIMING=1 (read when the context is created): the scan's dispatch carries a
+                                          // start and a stop event, completion and pfac_scan_elapsed_ms come from them -- the
+                                          // earlier form, kept to compare the two clocks and the two boundaries on one build
+    double tick_ms = 1e-5;                // one tick of the kernel's clock (s_memrealtime) in ms: 1 / hipDeviceAttributeWallClockRate
+    double clk_diff_ms = 0;               // PFAC_EVENT_TIMING: event time - the kernel's own, summed over the timed scans, ...
+    uint64_t clk_n = 0;                   // ... and how many (printed when the context goes, under PFAC_VERBOSE)
     unsigned count_bins = 0, count_grid = 0, count_threads = 0;   // PFAC_COUNT_BINS / _GRID / _THREADS (0: the defaults)
     std::string trace_file;
     std::string err;
@@ -4084,6 +4114,32 @@ const char *knob(const char *name) {
 int env_int(const char *name, int dflt) {
     const char *v = knob(name);
     return v && *v ? atoi(v) : dflt;
+}
+
+// Waits for the slot's last scan -- for IT, not for the stream: another slot may share the stream (launch pipelining), and
+// its scan, enqueued behind this one, keeps the GPU busy while the host reads this result.  The kernel's last workgroup
+// stores H_DONE behind the other result words; the host polls that word.  Nothing is queued on the stream meanwhile (no
+// query, no event): a signalled packet between two scans is what the dispatch no longer pays for.  The poll is bounded
+// by Slot::spin_ms, a generous multiple of the scan's time; past it the stream itself is waited for, and a stream that
+// has gone idle with the word still unset is an error, as is one that failed.
+int wait_scan(pfac_ctx *ctx, Slot &s) {
+    if (ctx->event_timing) { HIP_TRY(ctx, hipEventSynchronize(s.ev1)); return PFAC_OK; }
+    const volatile unsigned *done = s.h_ctl + H_DONE;
+    auto is_done = [&] { return __atomic_load_n(done, __ATOMIC_ACQUIRE) != 0; };
+    if (is_done()) return PFAC_OK;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (;;) {
+        for (int i = 0; i < 64; i++) {
+            if (is_done()) return PFAC_OK;
+#if defined(__x86_64__) || defined(__i386__)
+            __builtin_ia32_pause();
+#endif
+        }
+        if (std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() > s.spin_ms) break;
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+    if (!is_done()) return fail(ctx, PFAC_E_INTERNAL, "the scan's stream is idle, but the scan has not reported its completion");
+    return PFAC_OK;
 }
 
 static int max_lds(const pfac_ctx *ctx) {
@@ -4383,7 +4439,7 @@ int install_table(pfac_ctx *ctx, const int *d_blob, const int32_t *hdr, size_t n
     const size_t off_id = off_T + (size_t)ht_size * 8;
     const size_t total = align_up(off_id + (size_t)num_final * 4, 16) + 16;
     for (auto &sl : ctx->slots)                             // a scan still in flight reads the tables freed below
-        if (sl.pending) HIP_TRY(ctx, hipEventSynchronize(sl.ev1));
+        if (sl.pending) { int rc = wait_scan(ctx, sl); if (rc) return rc; }
     ctx->tab.reset();
     ctx->flen.reset();                                      // the lengths belong to the old table
     ctx->rep_off.reset();                                   // ... and so do the replacements
@@ -4443,18 +4499,24 @@ int pfac_ctx_create(int device, int n_streams, pfac_ctx **out) {
     hipDeviceProp_t prop;
     HIP_TRY(ctx, hipGetDeviceProperties(&prop, device));
     ctx->n_cu = prop.multiProcessorCount;
+    int khz = 0;
+    if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device) != hipSuccess) (void)hipGetLastError();
+    ctx->tick_ms = 1.0 / (khz > 0 ? khz : 100000);          // (100 MHz where the runtime does not say)
+    ctx->event_timing = env_int("PFAC_EVENT_TIMING", 0) != 0;
     ctx->slots.resize(n_streams);
     HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
     for (auto &s : ctx->slots) {
         HIP_TRY(ctx, hipStreamCreateWithFlags(&s.own_stream, hipStreamNonBlocking));
         s.stream = s.own_stream;
-        HIP_TRY(ctx, hipHostMalloc((void **)&s.h_ctl, 64, hipHostMallocMapped));
-        memset(s.h_ctl, 0, 64);
+        HIP_TRY(ctx, hipHostMalloc((void **)&s.h_ctl, H_CTL_BYTES, hipHostMallocMapped));
+        memset(s.h_ctl, 0, H_CTL_BYTES);
         HIP_TRY(ctx, hipHostGetDevicePointer((void **)&s.d_res, s.h_ctl, 0));
         int rc = s.sum.ensure(ctx, nullptr, 2, 2);
         if (rc) return rc;
-        HIP_TRY(ctx, hipEventCreate(&s.ev0));
-        HIP_TRY(ctx, hipEventCreate(&s.ev1));
+        if (ctx->event_timing) {
+            HIP_TRY(ctx, hipEventCreate(&s.ev0));
+            HIP_TRY(ctx, hipEventCreate(&s.ev1));
+        }
         HIP_TRY(ctx, hipEventCreateWithFlags(&s.ev_h2d, hipEventDisableTiming));
         HIP_TRY(ctx, hipEventCreateWithFlags(&s.ev_rd, hipEventDisableTiming));
     }
@@ -4465,6 +4527,9 @@ int pfac_ctx_create(int device, int n_streams, pfac_ctx **out) {
 void pfac_ctx_destroy(pfac_ctx *ctx) {
     if (!ctx) return;
     DeviceGuard device_guard_(ctx->device);
+    if (ctx->clk_n && knob("PFAC_VERBOSE"))
+        fprintf(stderr, "pfac: event time - kernel's own clock: mean %.2f us over %llu timed scans\n",
+                ctx->clk_diff_ms * 1e3 / (double)ctx->clk_n, (unsigned long long)ctx->clk_n);
     for (auto &s : ctx->slots) {
         if (s.own_stream) (void)hipStreamSynchronize(s.own_stream);
         if (s.h_ctl) (void)hipHostFree(s.h_ctl);
@@ -4533,7 +4598,7 @@ int pfac_slot_reserve(pfac_ctx *ctx, int slot, uint64_t input_bytes, uint64_t re
     // scan -- the slot is back to "no finished scan", so nothing reads it as if it held the last one.
     if ((input_bytes > s.input.cap && s.input.p) || (record_capacity > s.records.cap && s.records.p)) {
         HIP_TRY(ctx, hipStreamSynchronize(s.stream));
-        if (s.pending) HIP_TRY(ctx, hipEventSynchronize(s.ev1));       // (the stream may have been swapped under the scan)
+        if (s.pending) { rc = wait_scan(ctx, s); if (rc) return rc; }
         if (s.h2d_issued) HIP_TRY(ctx, hipEventSynchronize(s.ev_h2d));
         s.scanned = s.pending = false;
     }
@@ -4553,7 +4618,11 @@ int pfac_slot_set_stream(pfac_ctx *ctx, int slot, void *stream_handle) {
     hipStream_t ns = stream_handle ? reinterpret_cast<hipStream_t>(stream_handle) : s.own_stream;
     // what the slot still has queued on the old stream finishes first: a scan in flight zeroes the next scan's control
     // words, and the writes of a pass (a selection, say) are asynchronous -- the next pass, on the new stream, reads them
-    if (ns != s.stream) { USE_DEVICE(ctx); HIP_TRY(ctx, hipStreamSynchronize(s.stream)); }
+    if (ns != s.stream) {
+        USE_DEVICE(ctx);
+        HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+        if (s.pending) { rc = wait_scan(ctx, s); if (rc) return rc; }   // (the scan itself: it is not left behind on the old stream)
+    }
     s.stream = ns;
     return PFAC_OK;
 }
@@ -4566,9 +4635,9 @@ int pfac_slot_h2d(pfac_ctx *ctx, int slot, const void *host, uint64_t n_bytes, u
     USE_DEVICE(ctx);
     // on the context's copy stream, behind whatever the slot's stream still does with the buffer: its last scan reads it,
     // and so do kernels queued behind the scan by calls that have already returned (the write kernels of the replace passes,
-    // of the split and of the gather). ev_rd, recorded here, is behind all of them; ev1 covers a scan whose stream was
-    // swapped since. The slot's stream then waits for the copy: same ordering as a copy on the slot's stream, without the gaps
-    if (s.scanned) HIP_TRY(ctx, hipStreamWaitEvent(ctx->copy_stream, s.ev1, 0));
+    // of the split and of the gather). ev_rd, recorded here, is behind all of them: a stream swap leaves no scan behind on
+    // the old stream (pfac_slot_set_stream waits for it). The slot's stream then waits for the copy: same ordering as a
+    // copy on the slot's stream, without the gaps
     HIP_TRY(ctx, hipEventRecord(s.ev_rd, s.stream));
     HIP_TRY(ctx, hipStreamWaitEvent(ctx->copy_stream, s.ev_rd, 0));
     HIP_TRY(ctx, hipMemcpyAsync(s.input.p + dst_offset, host, n_bytes, hipMemcpyHostToDevice, ctx->copy_stream));
@@ -4616,7 +4685,11 @@ int pfac_scan_async(pfac_ctx *ctx, int slot, const void *d_input, uint64_t n_own
     s.last_cap = capacity;
     s.scanned = true;
     s.pending = true;
-    for (int i = 0; i < 7; i++) s.h_ctl[i] = 0;        // result words (the kernel writes them through the host mapping)
+    for (int i = 0; i < 8; i++) s.h_ctl[i] = 0;        // result words and H_DONE (the kernel writes them through the host mapping)
+    s.h_ctl[H_T0] = s.h_ctl[H_T0 + 1] = s.h_ctl[H_T1] = s.h_ctl[H_T1 + 1] = 0;
+    // wait_scan polls for 2 ms + what the owned bytes take at 50 GB/s (a hundred times the headline scan, six times the
+    // dictionary's) before it asks the stream instead
+    s.spin_ms = 2.0 + (double)n_owned / 50e6;
     // staging mode of this launch (see pfac_scan_finish for the adaptation)
     const bool dense = ctx->run_dense();
     const StageLayout &L = ctx->layout(dense);
@@ -4638,7 +4711,6 @@ int pfac_scan_async(pfac_ctx *ctx, int slot, const void *d_input, uint64_t n_own
     const uint64_t n_batches = (n_tiles + wpb - 2) / (wpb - 1);
     unsigned *const cur = s.d_ctlbuf[s.flip], *const nxt = s.d_ctlbuf[1 - s.flip];
     if (n_tiles > 0 && !s.clean[s.flip]) HIP_TRY(ctx, hipMemsetAsync(cur, 0, CTL_REGION, s.stream));
-    if (n_tiles == 0) HIP_TRY(ctx, hipEventRecord(s.ev0, s.stream));
     if (n_tiles > 0) {
         ScanArgs a;
         a.in = in; a.n_owned = n_owned; a.n_avail = n_avail;
@@ -4701,15 +4773,19 @@ int pfac_scan_async(pfac_ctx *ctx, int slot, const void *d_input, uint64_t n_own
         if (chunk > (1u << 22)) chunk = 1u << 22;
         a.chunk = (chunk >= 1024 && !dense) ? (unsigned)chunk : 0u;      // (dense mode: every tile takes its own space)
         void *kargs[] = {&a};
-        // the slot's two events ride on the dispatch itself (start / stop of THIS kernel): no barrier packets of their own
-        // in front of and behind every scan
+        // A plain dispatch: no completion signal, no timestamps (a dispatch that carries them makes the command processor
+        // retire the kernel, fence, write both and signal before it looks at the next packet).  Completion is the H_DONE
+        // word and the time is the kernel's own.  PFAC_EVENT_TIMING: both events ride on the dispatch itself (null otherwise).
         HIP_TRY(ctx, hipExtLaunchKernel(dense ? ctx->kernel_d : (ctx->lag2 ? ctx->kernel3 : ctx->kernel), dim3((unsigned)grid),
                                         dim3(WAVE * wpb), kargs, (size_t)L.lds_bytes, s.stream, s.ev0, s.ev1, 0));
         s.clean[s.flip] = false;               // used by this scan
         s.clean[1 - s.flip] = true;            // zeroed by this scan
         s.flip = 1 - s.flip;
     }
-    if (n_tiles == 0) HIP_TRY(ctx, hipEventRecord(s.ev1, s.stream));
+    if (n_tiles == 0) {                                // nothing launched: complete, in no time
+        if (ctx->event_timing) HIP_TRY(ctx, hipEventRecord(s.ev1, s.stream));
+        __atomic_store_n(s.h_ctl + H_DONE, 1u, __ATOMIC_RELEASE);
+    }
     return PFAC_OK;
 }
 
@@ -4719,9 +4795,10 @@ int pfac_scan_finish(pfac_ctx *ctx, int slot, uint64_t *n_matches) {
     Slot &s = ctx->slots[slot];
     if (!s.scanned) return fail(ctx, PFAC_E_STATE, "pfac_scan_finish without a scan");
     USE_DEVICE(ctx);
-    // wait for THIS scan's end event, not for the stream: another slot may share the stream (launch pipelining), and
-    // its scan -- enqueued after this one -- should keep the GPU busy while the host reads this result
-    HIP_TRY(ctx, hipEventSynchronize(s.ev1));
+    rc = wait_scan(ctx, s);
+    if (rc) return rc;
+    // (an empty scan launched nothing that ran behind the slot's uploads: a caller releases their host buffers now)
+    if (s.last_tiles == 0 && s.h2d_issued) HIP_TRY(ctx, hipEventSynchronize(s.ev_h2d));
     s.pending = false;
     const uint64_t total = host_u64(s, H_MATCHES);
     s.last_total = total;
@@ -4767,8 +4844,16 @@ int pfac_scan_elapsed_ms(pfac_ctx *ctx, int slot, float *ms) {
     if (!ms) return fail(ctx, PFAC_E_ARG, "null argument");
     Slot &s = ctx->slots[slot];
     if (!s.scanned) return fail(ctx, PFAC_E_STATE, "no scan to time");
-    HIP_TRY(ctx, hipEventSynchronize(s.ev1));
-    HIP_TRY(ctx, hipEventElapsedTime(ms, s.ev0, s.ev1));
+    USE_DEVICE(ctx);
+    rc = wait_scan(ctx, s);
+    if (rc) return rc;
+    if (s.last_tiles == 0) *ms = 0.0f;
+    else if (ctx->event_timing) {
+        HIP_TRY(ctx, hipEventElapsedTime(ms, s.ev0, s.ev1));
+        ctx->clk_diff_ms += *ms - (double)(host_u64(s, H_T1) - host_u64(s, H_T0)) * ctx->tick_ms;   // the two clocks, same launch
+        ctx->clk_n++;
+    }
+    else *ms = (float)((double)(host_u64(s, H_T1) - host_u64(s, H_T0)) * ctx->tick_ms);
     return PFAC_OK;
 }
 

@@ -1,8 +1,12 @@
 """GPU diagnostic: the boundary between back-to-back scans, issued the way bench.py issues its steps (two slots on ONE
 stream, step k+1 enqueued while step k runs, every count read back).
 usage: rocprofv3 --kernel-trace --output-format csv -d DIR -- python3 tools/dispatch_gap.py run [launches] [pattern fixture]
-       python3 tools/dispatch_gap.py parse DIR       start(k+1) - end(k) and kernel time of the full-size scan launches"""
-import glob, os, sys
+       python3 tools/dispatch_gap.py parse DIR       start(k+1) - end(k) and kernel time of the full-size scan launches
+       python3 tools/dispatch_gap.py both [launches] the boundary WITHOUT a tracer (under one, every dispatch carries a signal and
+                                                     timestamps, whatever the library asks for): wall clock per launch minus
+                                                     elapsed_ms, of the plain dispatch with the kernel's own clock and, in a
+                                                     second process, of the dispatch with events (PFAC_EVENT_TIMING=1)"""
+import glob, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -56,7 +60,11 @@ def parse(d):
 
 
 if __name__ == "__main__":
-    if sys.argv[1] == "run":
+    if sys.argv[1] == "both":
+        for knob in ({}, {"PFAC_EVENT_TIMING": "1"}):
+            subprocess.run([sys.executable, os.path.join(ROOT, "tools", "launch_wall.py"), sys.argv[2] if len(sys.argv) > 2 else "800", "2"],
+                           env=dict(os.environ, PFAC_ENABLE_KNOBS="1", **knob), check=True)
+    elif sys.argv[1] == "run":
         run(int(sys.argv[2]) if len(sys.argv) > 2 else 200, sys.argv[3] if len(sys.argv) > 3 else "experimentpattern")
     else:
         parse(sys.argv[2])
