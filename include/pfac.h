@@ -117,6 +117,29 @@ int pfac_table_build_mem_charclass(const void *patterns, size_t n_bytes, int wid
                                    char *err, size_t err_len);
 void pfac_outputs_free(pfac_outputs *o);
 
+/* Case-insensitive tables (grep -i, the `nocase` of Snort-style rules).  pfac_fold_ascii is THE fold, the one the scan
+ * kernel applies under PFAC_FOLD_ASCII (pfac_table_set_case_fold): every byte 0x41..0x5A ('A'..'Z') gets 0x20 or-ed in,
+ * every other byte is copied unchanged -- bytes >= 0x80 never change, so UTF-8 passes through whole and there is no
+ * Latin-1 folding.  dst == src folds in place; neither pointer needs any alignment; n == 0 does nothing.
+ * The _nocase builders fold the PATTERNS after they are read and before they are sorted: for the escaped reader after
+ * escape decoding ("\x41" folds, the 'x' of an escape is never touched); in a class the listed set is folded (upper-case
+ * members become their lower-case letters) and "[^...]" complements the folded set, so "[^A]" rejects 'a' -- and hence 'A'
+ * once the input is folded.  Sorting, "the last line wins" among duplicates ("Foo" and "foo" are duplicates) and the
+ * partition cuts act on the folded bytes.  The result is, blob for blob, the table the plain builder makes from a
+ * pattern file folded beforehand; pfac_table and the blob do not record it, and nothing about the table says "fold":
+ * the caller sets the scan's mode with pfac_table_set_case_fold after the upload.
+ *   _mem_nocase            part / n_parts as pfac_table_build_mem_part; 0, 1 = the whole file
+ *   _file_nocase           escapes != 0: the reader of pfac_table_build_file_escaped, else that of pfac_table_build_file */
+int pfac_fold_ascii(void *dst, const void *src, size_t n);
+int pfac_table_build_mem_nocase(const void *patterns, size_t n_bytes, int width, int part, int n_parts, pfac_table **out,
+                                char *err, size_t err_len);
+int pfac_table_build_file_nocase(const char *pattern_file, int width, int escapes, pfac_table **out, char *err,
+                                 size_t err_len);
+int pfac_table_build_mem_charclass_nocase(const void *patterns, size_t n_bytes, int width, pfac_table **out,
+                                          pfac_outputs **outputs, char *err, size_t err_len);
+int pfac_table_build_file_charclass_nocase(const char *pattern_file, int width, pfac_table **out, pfac_outputs **outputs,
+                                           char *err, size_t err_len);
+
 /* The device lookup evaluated on the host (property tests; never used on the scan path). */
 int32_t pfac_table_lookup(const pfac_table *t, int32_t state, int32_t ch);
 /* len[s] for s in [0, num_final): bytes of the pattern(s) ending in final state s (= its depth in the trie / DFA);
@@ -214,6 +237,26 @@ const char *pfac_last_error(const pfac_ctx *ctx);                    /* ctx may 
  * PFAC_E_STATE for such a scan. */
 int pfac_table_upload(pfac_ctx *ctx, const int32_t *blob, size_t n_words);
 int pfac_table_upload_device(pfac_ctx *ctx, const void *d_blob, size_t n_words, void *stream_handle);
+
+/* Case-insensitive scans: the scan folds the INPUT on its way into the kernel's on-chip copy, with the fold of
+ * pfac_fold_ascii -- bytes 0x41..0x5A get 0x20 or-ed in, no other byte changes (none >= 0x80: UTF-8 is safe).  The caller's
+ * input buffer is never written.  Records, counts, the leftmost-longest selections and the emitted text are those of an
+ * EXACT scan of the folded input with the same table; with a table from a _nocase builder (folded patterns) that is
+ * grep -i.  With a table that holds upper-case letters the folded scan simply never takes those edges.
+ * Every pass behind the scan that reads the input reads the ORIGINAL bytes: the whole-word filter judges them, both
+ * replaces and the gather copy them (grep -i prints the line as it was written), the split cuts them.  A custom word set
+ * that separates the cases therefore sees the case the input was written in.
+ *   mode   PFAC_FOLD_NONE or PFAC_FOLD_ASCII; anything else: PFAC_E_ARG, and the setting stays as it was
+ * PFAC_E_STATE before a table upload (as pfac_table_set_final_lengths).  The setting belongs to the uploaded table: it
+ * holds until the next pfac_table_upload / pfac_table_upload_device, which resets it to PFAC_FOLD_NONE.  It applies to
+ * every pfac_scan_async queued after the call, on every slot; a scan queued before keeps the mode it was launched with
+ * (the mode is fixed at launch: every scan kernel has a twin that folds, and the launch picks one), so the call waits
+ * for nothing and costs no device work.  An exact scan runs the kernel it always ran. */
+#define PFAC_FOLD_NONE  0u
+#define PFAC_FOLD_ASCII 1u
+int pfac_table_set_case_fold(pfac_ctx *ctx, uint32_t mode);
+/* The current setting (PFAC_FOLD_NONE after an upload).  PFAC_E_STATE before a table upload. */
+int pfac_table_case_fold(pfac_ctx *ctx, uint32_t *mode);
 
 /* Pinned host memory, replaces cudaHostAlloc(..., cudaHostAllocPortable) (main.cc:147,161). */
 int pfac_host_alloc(void **p, size_t n_bytes);

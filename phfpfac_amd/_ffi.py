@@ -32,6 +32,8 @@ PFAC_WORD_LEFT = 1      # pfac_records_filter_words: the match must not begin in
 PFAC_WORD_RIGHT = 2     # ... must not end inside one
 PFAC_COUNT_ACCUMULATE = 1   # pfac_records_count_states / pfac_selection_count_states: add onto the counts already there
 PFAC_DOCS_INVERT = 1        # pfac_documents_matching: the documents WITHOUT a kept record
+PFAC_FOLD_NONE = 0          # pfac_table_set_case_fold: an exact scan
+PFAC_FOLD_ASCII = 1         # ... the scan folds A-Z of the input to a-z
 
 _STATUS_NAMES = {
     0: "PFAC_OK", -1: "PFAC_E_ARG", -2: "PFAC_E_IO", -3: "PFAC_E_PATTERN", -4: "PFAC_E_NOMEM",
@@ -80,6 +82,8 @@ HOST_SYMBOLS = (
     "pfac_table_blob_words", "pfac_table_to_blob", "pfac_table_from_blob", "pfac_table_from_reference_arrays",
     "pfac_emit_records", "pfac_emit_records_mt", "pfac_emit_packed", "pfac_table_build_file_charclass",
     "pfac_table_build_mem_charclass", "pfac_outputs_free", "pfac_emit_records_multi", "pfac_table_final_lengths",
+    "pfac_fold_ascii", "pfac_table_build_mem_nocase", "pfac_table_build_file_nocase",
+    "pfac_table_build_mem_charclass_nocase", "pfac_table_build_file_charclass_nocase",
 )
 HIP_SYMBOLS = (
     "pfac_device_count", "pfac_ctx_create", "pfac_ctx_destroy", "pfac_last_error", "pfac_table_upload",
@@ -97,6 +101,7 @@ HIP_SYMBOLS = (
     "pfac_records_count_states", "pfac_selection_count_states", "pfac_state_counts_d2h",
     "pfac_slot_doc_offsets_split", "pfac_slot_doc_offsets_d2h", "pfac_documents_matching", "pfac_documents_matching_d2h",
     "pfac_documents_matching_context", "pfac_documents_gather", "pfac_documents_gather_d2h", "pfac_documents_gather_offsets_d2h",
+    "pfac_table_set_case_fold", "pfac_table_case_fold",
 )
 
 _host = None
@@ -144,6 +149,11 @@ def host_lib() -> C.CDLL:
         L.pfac_emit_records_multi.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, OP]
         L.pfac_emit_records_multi.restype = C.c_int64
         L.pfac_table_final_lengths.argtypes = [TP, C.c_void_p, C.c_size_t]
+        L.pfac_fold_ascii.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.pfac_table_build_mem_nocase.argtypes = L.pfac_table_build_mem_part.argtypes
+        L.pfac_table_build_file_nocase.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(TP), C.c_char_p, C.c_size_t]
+        L.pfac_table_build_file_charclass_nocase.argtypes = L.pfac_table_build_file_charclass.argtypes
+        L.pfac_table_build_mem_charclass_nocase.argtypes = L.pfac_table_build_mem_charclass.argtypes
         _host = L
     return _host
 
@@ -235,5 +245,7 @@ def hip_lib() -> C.CDLL:
         L.pfac_documents_gather.argtypes = [vp, i, vp, u64, vp, u64, vp, u64, vp, u64, vp, C.POINTER(u64)]
         L.pfac_documents_gather_d2h.argtypes = [vp, i, vp, u64, u64]
         L.pfac_documents_gather_offsets_d2h.argtypes = [vp, i, vp]
+        L.pfac_table_set_case_fold.argtypes = [vp, C.c_uint32]
+        L.pfac_table_case_fold.argtypes = [vp, C.POINTER(C.c_uint32)]
         _hip = L
     return _hip

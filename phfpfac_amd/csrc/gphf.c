@@ -40,7 +40,9 @@
  * multi-worker dealing and the shared in-order output can be exercised on a single device; PFAC_CHUNK_MB sets the chunk
  * size (default 32); PFAC_INGEST=pread makes a pool of PFAC_READ_THREADS threads (default: cores, at most 16) copy the file into
  * pinned staging buffers instead of mapping it (also the fallback where the driver cannot pin page-cache pages);
- * PFAC_EMIT=host|device; PFAC_EMIT_THREADS the host formatter's / the writer pool's threads; PFAC_TIMELINE=1 prints milestones.
+ * PFAC_EMIT=host|device; PFAC_EMIT_THREADS the host formatter's / the writer pool's threads; PFAC_TIMELINE=1 prints milestones;
+ * PFAC_IGNORE_CASE=1 matches like grep -i: the table is built from folded patterns (A-Z -> a-z) and every worker's scans fold
+ * the input on the device (pfac_table_set_case_fold) -- the ingest stays zero-copy, arguments and output format are unchanged.
  */
 #define _FILE_OFFSET_BITS 64
 #define _GNU_SOURCE
@@ -127,6 +129,7 @@ static double now_ms(void) {
 /* PFAC_TIMELINE=1: milestones on stderr, milliseconds since program start */
 static double g_t_start = 0;
 static int g_timeline = 0;
+static int g_ignore_case = 0;         /* PFAC_IGNORE_CASE=1: nocase table, folded scans */
 static unsigned char *g_map = NULL;     /* zero-copy ingest: the input file, mapped MAP_SHARED (the page cache itself) */
 static uint64_t g_map_len = 0;
 /* ... registered for DMA piece by piece (a piece = a whole number of chunks, ~256 MiB) by ONE registrar thread that runs a
@@ -546,6 +549,7 @@ static void *worker(void *arg) {
         w->table_wait_ms = now_ms() - tw;
     }
     if ((rc = pfac_table_upload(ctx, g_blob, g_blob_words))) { fail(w, ctx, rc, "table upload"); goto out; }
+    if (g_ignore_case && (rc = pfac_table_set_case_fold(ctx, PFAC_FOLD_ASCII))) { fail(w, ctx, rc, "case fold"); goto out; }
     MILESTONE("worker %d: table installed", w->index);
     for (int j = 0; j < w->n_mine && !w->rc; j++) {
         const int k = w->index + j * w->n_workers;
@@ -666,6 +670,7 @@ int main(int argc, char *argv[]) {
     const double t_start = now_ms();
     g_t_start = t_start;
     g_timeline = getenv("PFAC_TIMELINE") != NULL;
+    g_ignore_case = getenv("PFAC_IGNORE_CASE") != NULL && atoi(getenv("PFAC_IGNORE_CASE")) != 0;
     if (getenv("PFAC_GPHF_SKIP")) { g_skip_read = strcmp(getenv("PFAC_GPHF_SKIP"), "read") == 0; g_skip_gpu = strcmp(getenv("PFAC_GPHF_SKIP"), "gpu") == 0; }
     int streamnum = atoi(argv[2]);
     int width = atoi(argv[3]);
@@ -760,7 +765,8 @@ int main(int argc, char *argv[]) {
     pfac_table *tab = NULL;
     int32_t *blob = NULL;
     const double t0 = now_ms();
-    rc = pfac_table_build_file(argv[1], width, &tab, err, sizeof err);     /* main.cc:108,125 */
+    rc = g_ignore_case ? pfac_table_build_file_nocase(argv[1], width, 0, &tab, err, sizeof err)
+                       : pfac_table_build_file(argv[1], width, &tab, err, sizeof err);     /* main.cc:108,125 */
     const double t1 = now_ms();
     size_t words = 0;
     if (!rc) {

@@ -58,6 +58,7 @@
 #include <vector>
 
 #include "pfac.h"
+#include "pfac_fold.h"
 
 namespace {
 
@@ -159,6 +160,13 @@ constexpr unsigned RES_T0 = 16, RES_T1 = 18;       // u64 each: first workgroup 
 constexpr unsigned CTL_CURSOR = 64u * TICKET_WAYS;     // u64: first free record of the heap (on a line of its own)
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+// the case fold of pfac_fold.h over the four dwords of a 16-byte load
+__device__ __forceinline__ u32x4 fold4(u32x4 v) {
+    u32x4 o;
+    o[0] = pfac_fold_dword(v[0]); o[1] = pfac_fold_dword(v[1]); o[2] = pfac_fold_dword(v[2]); o[3] = pfac_fold_dword(v[3]);
+    return o;
+}
 
 struct ScanArgs {
     const unsigned char *in;
@@ -1340,7 +1348,7 @@ __device__ __forceinline__ unsigned eq_mask32(const u32x4 lo16, const u32x4 hi16
 #endif
 constexpr int MAX_WAVES_NW4 = 10;          // four walks per lane, staged in LDS: dense mode's buffers leave room for 9-10 waves per workgroup
 
-template <bool TLDS, bool W8, int ROOT, bool FUSED, int NW, int NB>
+template <bool TLDS, bool W8, int ROOT, bool FUSED, int NW, int NB, bool FOLD>
 __device__ __forceinline__ void scan_body(const ScanArgs &a, unsigned char *smem, const ErrCh &err) {
     unsigned *hdr = reinterpret_cast<unsigned *>(smem + SH_HDR);
     int *s0 = reinterpret_cast<int *>(smem + SH_S0);
@@ -1629,6 +1637,15 @@ __device__ __forceinline__ void scan_body(const ScanArgs &a, unsigned char *smem
         PFAC_STAMP(trace, 4);
         // ---- registers -> LDS (tile + halo), then start the loads of the tile LOAD_DEPTH rounds ahead right away
 #ifndef PFAC_ABL_NOLDSCOPY                     // ablation builds only: the tile never reaches LDS (wrong masks)
+        // (case-insensitive scans fold here, and in the tail patch below: everything that looks at input bytes afterwards
+        // reads this LDS copy, and the caller's buffer is only ever loaded.  FOLD is a template parameter: the exact kernels
+        // hold no trace of it -- a runtime flag around this block came out of its A/B call 1 % slower with the fold OFF on
+        // the headline workload)
+        if (FOLD) {
+#pragma unroll
+            for (int j = 0; j < SUBS; j++) w[j] = fold4(w[j]);
+            hw = fold4(hw);
+        }
 #pragma unroll
         for (int j = 0; j < SUBS; j++) *reinterpret_cast<u32x4 *>(tile + j * SUB + lane * 16) = w[j];
         if (lane * 16 < a.halo) *reinterpret_cast<u32x4 *>(tile + WTILE + lane * 16) = hw;
@@ -1637,7 +1654,10 @@ __device__ __forceinline__ void scan_body(const ScanArgs &a, unsigned char *smem
 #endif
         if (lim & 15u) {                       // ragged end of the input (last tile only): patch the tail bytes
             wave_lds_sync();
-            if (lane < (int)(lim & 15u)) tile[(lim & ~15u) + lane] = a.in[tile_base + (lim & ~15u) + lane];
+            if (lane < (int)(lim & 15u)) {
+                const unsigned char b = a.in[tile_base + (lim & ~15u) + lane];
+                tile[(lim & ~15u) + lane] = FOLD ? pfac_fold_byte(b) : b;
+            }
         }
         wave_lds_sync();
         PFAC_STAMP(trace, 5);
@@ -1864,7 +1884,7 @@ __device__ __forceinline__ void scan_body(const ScanArgs &a, unsigned char *smem
     }
 }
 
-template <bool TLDS, bool W8, int ROOT, bool FUSED, int NW, int NB = 2>
+template <bool TLDS, bool W8, int ROOT, bool FUSED, int NW, int NB = 2, bool FOLD = false>
 __global__ __launch_bounds__(WAVE * MAX_WAVES_PER_BLOCK) void pfac_scan_kernel(ScanArgs a) {
     static_assert(NB == 2 || (NB == 3 && NW <= 3), "three staging buffers: the sparse-mode kernels (dense mode has one)");
     static_assert(!(TLDS && FUSED), "the fused table is for tables gathered through L2");
@@ -1879,7 +1899,7 @@ __global__ __launch_bounds__(WAVE * MAX_WAVES_PER_BLOCK) void pfac_scan_kernel(S
     if (blockIdx.x < T0_GROUPS && threadIdx.x == 0)
         (void)__hip_atomic_fetch_max(reinterpret_cast<unsigned long long *>(a.ctl + CTL_T0), ~__builtin_amdgcn_s_memrealtime(),
                                      __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    scan_body<TLDS, W8, ROOT, FUSED, NW, NB>(a, smem, err);
+    scan_body<TLDS, W8, ROOT, FUSED, NW, NB, FOLD>(a, smem, err);
     // ---- leaving: the last wave of the workgroup counts the workgroup out; the last workgroup of the grid copies
     // the error flags and the dense-tile count from the control header (device memory) to the host-visible result
     // words with plain stores.  Every wave comes through here, whichever way it left the loop.
@@ -3923,9 +3943,9 @@ struct pfac_ctx {
     int width_bit = 0, num_final = 0, max_pat_len = 0, max_row = 0, ht_size = 0, state_num = 0;
     bool have_table = false;
     int variant = 1;
-    const void *kernel = nullptr;
-    const void *kernel_d = nullptr;       // the kernel dense mode launches (four walks per lane on fused L2 tables)
-    const void *kernel3 = nullptr;        // the three-staging-buffer twin of `kernel` (tables in LDS only), else null
+    const void *kernel[2] = {};           // [0] the exact kernel, [1] its twin that folds the input's case (ctx->fold chooses)
+    const void *kernel_d[2] = {};         // the kernel dense mode launches (four walks per lane on fused L2 tables)
+    const void *kernel3[2] = {};          // the three-staging-buffer twin of `kernel` (tables in LDS only), else null
     int shared_bytes = 0, halo = 0, root_mode = 0;
     unsigned root_byte = 0;
     int root_state = -1;
@@ -3947,6 +3967,7 @@ struct pfac_ctx {
     DevBuf<short> flen;                   // pattern length of every final state (pfac_table_set_final_lengths), cleared by an upload
     DevBuf<unsigned> rep_off;             // replacement of every final state (pfac_table_set_replacements): offsets[num_final + 1]
     DevBuf<unsigned char> rep;            // ... and the bytes, zero-padded to its capacity (a multiple of 16); cleared by an upload
+    unsigned fold = PFAC_FOLD_NONE;       // case fold of the scans to come (pfac_table_set_case_fold), reset by an upload
     uint64_t table_gen = 0;               // tables installed so far: a scan's final states index the lengths of ITS table only
     // level-2 filter (ScanArgs::l2f_mode)
     DevBuf<unsigned char> bm2;            // 2-byte-prefix bitmap, 256 rows of 32 bytes
@@ -4152,25 +4173,30 @@ static int max_lds(const pfac_ctx *ctx) {
 int lds_of_one_block_per_cu(int lds_bytes) { return lds_bytes < LDS_TOTAL / 2 + 256 ? LDS_TOTAL / 2 + 256 : lds_bytes; }
 
 // The scan kernel of a table placement (0: tables via L2, 1: tables in LDS, 2: fused L2 tables, 3: fused L2 tables
-// with four walks per lane -- dense mode, two staging buffers only), hash width, root test and NB staging buffers.
-template <int NB, bool TLDS, bool FUSED, int NW>
+// with four walks per lane -- dense mode, two staging buffers only), hash width, root test, NB staging buffers and case
+// fold (every kernel has a twin that folds its tile on the way into LDS).
+template <int NB, bool TLDS, bool FUSED, int NW, bool FOLD>
 const void *scan_kernel_of(bool w8, int root) {
     const void *const k[2][2] = {
-        {(const void *)pfac_scan_kernel<TLDS, false, 0, FUSED, NW, NB>, (const void *)pfac_scan_kernel<TLDS, false, 1, FUSED, NW, NB>},
-        {(const void *)pfac_scan_kernel<TLDS, true, 0, FUSED, NW, NB>, (const void *)pfac_scan_kernel<TLDS, true, 1, FUSED, NW, NB>}};
+        {(const void *)pfac_scan_kernel<TLDS, false, 0, FUSED, NW, NB, FOLD>, (const void *)pfac_scan_kernel<TLDS, false, 1, FUSED, NW, NB, FOLD>},
+        {(const void *)pfac_scan_kernel<TLDS, true, 0, FUSED, NW, NB, FOLD>, (const void *)pfac_scan_kernel<TLDS, true, 1, FUSED, NW, NB, FOLD>}};
     return k[w8 ? 1 : 0][root];
 }
-template <int NB>
-const void *scan_kernel(int placement, bool w8, int root) {
+template <int NB, bool FOLD>
+const void *scan_kernel_fold(int placement, bool w8, int root) {
     // (three walks per lane for the sparse fused kernels -- one round per tile of the 75 840-pattern set on random bytes
     // instead of 1.45 -- measured 3 % slower than two: 112 VGPRs and the longer round cost more than the second round)
     constexpr int FNW = PFAC_SPARSE_FUSED_NW;   // walks per lane of the sparse-mode kernels on fused L2 tables
     switch (placement) {
-    case 0: return scan_kernel_of<NB, false, false, 2>(w8, root);
-    case 1: return scan_kernel_of<NB, true, false, 1>(w8, root);
-    case 2: return scan_kernel_of<NB, false, true, FNW>(w8, root);
-    default: return scan_kernel_of<2, false, true, 4>(w8, root);
+    case 0: return scan_kernel_of<NB, false, false, 2, FOLD>(w8, root);
+    case 1: return scan_kernel_of<NB, true, false, 1, FOLD>(w8, root);
+    case 2: return scan_kernel_of<NB, false, true, FNW, FOLD>(w8, root);
+    default: return scan_kernel_of<2, false, true, 4, FOLD>(w8, root);
     }
+}
+template <int NB>
+const void *scan_kernel(int placement, bool w8, int root, unsigned fold) {
+    return fold ? scan_kernel_fold<NB, true>(placement, w8, root) : scan_kernel_fold<NB, false>(placement, w8, root);
 }
 
 // layout of pfac_ctx::d_d1: rows (d1_rows x 256 int32) | 256-byte row index | the depth-1 states | (packed rows) {r[], child
@@ -4402,20 +4428,24 @@ int configure_kernel(pfac_ctx *ctx, const int32_t *s0_host) {
         HIP_TRY(ctx, hipDeviceSynchronize());
     }
     const int placement = ctx->variant == 0 ? 1 : (fused ? 2 : 0);
-    ctx->kernel = scan_kernel<2>(placement, w8, ctx->root_mode);
-    ctx->kernel_d = ctx->kernel;
-    ctx->kernel3 = scan_kernel<3>(placement, w8, ctx->root_mode);
-    HIP_TRY(ctx, hipFuncSetAttribute(ctx->kernel3, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds(ctx)));
+    for (unsigned f = 0; f < 2; f++) {         // [1]: the twins that fold (pfac_table_set_case_fold chooses per launch)
+        ctx->kernel[f] = scan_kernel<2>(placement, w8, ctx->root_mode, f);
+        ctx->kernel_d[f] = ctx->kernel[f];
+        ctx->kernel3[f] = scan_kernel<3>(placement, w8, ctx->root_mode, f);
+        HIP_TRY(ctx, hipFuncSetAttribute(ctx->kernel3[f], hipFuncAttributeMaxDynamicSharedMemorySize, max_lds(ctx)));
+    }
     // dense mode on fused L2 tables: four walks per lane (needs <= MAX_WAVES_NW4 waves per workgroup)
     if (fused && !knob("PFAC_NO_NW4")) {
-        ctx->kernel_d = scan_kernel<2>(3, w8, ctx->root_mode);
+        for (unsigned f = 0; f < 2; f++) ctx->kernel_d[f] = scan_kernel<2>(3, w8, ctx->root_mode, f);
         if (!ctx->dense2 && D.waves_per_block > MAX_WAVES_NW4) {
             D.waves_per_block = MAX_WAVES_NW4;
             D.lds_bytes = lds_of_one_block_per_cu(ctx->shared_bytes + (MAX_WAVES_NW4 - 1) * D.pw_bytes);
         }
-        HIP_TRY(ctx, hipFuncSetAttribute(ctx->kernel_d, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds(ctx)));
+        for (unsigned f = 0; f < 2; f++)
+            HIP_TRY(ctx, hipFuncSetAttribute(ctx->kernel_d[f], hipFuncAttributeMaxDynamicSharedMemorySize, max_lds(ctx)));
     }
-    HIP_TRY(ctx, hipFuncSetAttribute(ctx->kernel, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds(ctx)));
+    for (unsigned f = 0; f < 2; f++)
+        HIP_TRY(ctx, hipFuncSetAttribute(ctx->kernel[f], hipFuncAttributeMaxDynamicSharedMemorySize, max_lds(ctx)));
     if (knob("PFAC_VERBOSE"))
         fprintf(stderr, "pfac: variant %d fused %d shared LDS %d B; sparse: %d waves x %d B; dense%s: %d waves x %d B; dense rows %d x %d, %d depth-2 states, level-2 filter mode %d\n",
                 ctx->variant, (int)fused, ctx->shared_bytes, ctx->lay[0].waves_per_block, ctx->lay[0].pw_bytes, ctx->dense2 ? " (second form)" : "",
@@ -4442,6 +4472,7 @@ int install_table(pfac_ctx *ctx, const int *d_blob, const int32_t *hdr, size_t n
         if (sl.pending) { int rc = wait_scan(ctx, sl); if (rc) return rc; }
     ctx->tab.reset();
     ctx->flen.reset();                                      // the lengths belong to the old table
+    ctx->fold = PFAC_FOLD_NONE;                             // ... and so does the case fold
     ctx->rep_off.reset();                                   // ... and so do the replacements
     ctx->rep.reset();
     int rc = ctx->tab.ensure(ctx, nullptr, total, total);
@@ -4773,10 +4804,11 @@ int pfac_scan_async(pfac_ctx *ctx, int slot, const void *d_input, uint64_t n_own
         if (chunk > (1u << 22)) chunk = 1u << 22;
         a.chunk = (chunk >= 1024 && !dense) ? (unsigned)chunk : 0u;      // (dense mode: every tile takes its own space)
         void *kargs[] = {&a};
+        const unsigned fold = ctx->fold == PFAC_FOLD_ASCII ? 1u : 0u;       // the mode of THIS launch: its kernel
         // A plain dispatch: no completion signal, no timestamps (a dispatch that carries them makes the command processor
         // retire the kernel, fence, write both and signal before it looks at the next packet).  Completion is the H_DONE
         // word and the time is the kernel's own.  PFAC_EVENT_TIMING: both events ride on the dispatch itself (null otherwise).
-        HIP_TRY(ctx, hipExtLaunchKernel(dense ? ctx->kernel_d : (ctx->lag2 ? ctx->kernel3 : ctx->kernel), dim3((unsigned)grid),
+        HIP_TRY(ctx, hipExtLaunchKernel(dense ? ctx->kernel_d[fold] : (ctx->lag2 ? ctx->kernel3[fold] : ctx->kernel[fold]), dim3((unsigned)grid),
                                         dim3(WAVE * wpb), kargs, (size_t)L.lds_bytes, s.stream, s.ev0, s.ev1, 0));
         s.clean[s.flip] = false;               // used by this scan
         s.clean[1 - s.flip] = true;            // zeroed by this scan
@@ -5190,6 +5222,25 @@ int pfac_table_set_final_lengths(pfac_ctx *ctx, const int32_t *len, size_t n) {
     int rc = ctx->flen.ensure(ctx, nullptr, h.size(), h.size());
     if (rc) return rc;
     HIP_TRY(ctx, hipMemcpy(ctx->flen.p, h.data(), h.size() * sizeof(short), hipMemcpyHostToDevice));
+    return PFAC_OK;
+}
+
+int pfac_table_set_case_fold(pfac_ctx *ctx, uint32_t mode) {
+    if (!ctx) return fail(nullptr, PFAC_E_ARG, "null context");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (!ctx->have_table) return fail(ctx, PFAC_E_STATE, "pfac_table_set_case_fold before a table upload");
+    if (mode != PFAC_FOLD_NONE && mode != PFAC_FOLD_ASCII)
+        return fail(ctx, PFAC_E_ARG, "pfac_table_set_case_fold: mode must be PFAC_FOLD_NONE or PFAC_FOLD_ASCII");
+    ctx->fold = mode;                  // read by the next pfac_scan_async: it chooses the kernel a launch runs, so a scan
+                                       // already queued keeps the one it was launched with
+    return PFAC_OK;
+}
+
+int pfac_table_case_fold(pfac_ctx *ctx, uint32_t *mode) {
+    if (!ctx || !mode) return fail(ctx, PFAC_E_ARG, "pfac_table_case_fold: null argument");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (!ctx->have_table) return fail(ctx, PFAC_E_STATE, "pfac_table_case_fold before a table upload");
+    *mode = ctx->fold;
     return PFAC_OK;
 }
 

@@ -28,6 +28,7 @@
  *            not (tests/test_table.py checks every (state, byte) cell).
  */
 #include "pfac.h"
+#include "pfac_fold.h"
 
 #include <fcntl.h>
 #include <pthread.h>
@@ -242,6 +243,38 @@ int pfac_table_build_mem_part(const void *patterns, size_t n_bytes, int width, i
     return build_mem_part(patterns, n_bytes, width, part, n_parts, out, err, err_len);
 }
 
+/* The fold of pfac_fold.h over a buffer: whole dwords through pfac_fold_dword (memcpy in and out: no alignment is
+ * asked of either pointer), the last n % 4 bytes one by one.  dst == src folds in place. */
+int pfac_fold_ascii(void *dst, const void *src, size_t n) {
+    if ((!dst || !src) && n) return PFAC_E_ARG;
+    unsigned char *d = (unsigned char *)dst;
+    const unsigned char *s = (const unsigned char *)src;
+    size_t i = 0;
+    for (; i + 4 <= n; i += 4) {
+        uint32_t x;
+        memcpy(&x, s + i, 4);
+        x = pfac_fold_dword(x);
+        memcpy(d + i, &x, 4);
+    }
+    for (; i < n; i++) d[i] = pfac_fold_byte(s[i]);
+    return PFAC_OK;
+}
+
+/* Case-insensitive tables: the patterns are folded after they are read and before they are sorted, so the sort, the
+ * "last line wins" rule and the partition cuts all see folded bytes.  A newline is no letter: folding the file image is
+ * folding every pattern of the plain reader. */
+int pfac_table_build_mem_nocase(const void *patterns, size_t n_bytes, int width, int part, int n_parts, pfac_table **out,
+                                char *err, size_t err_len) {
+    if (!patterns || !out) { set_err(err, err_len, "null argument%ld", 0); return PFAC_E_ARG; }
+    *out = NULL;
+    unsigned char *img = (unsigned char *)malloc(n_bytes ? n_bytes : 1);
+    if (!img) { set_err(err, err_len, "out of memory (%ld bytes of pattern file)", (long)n_bytes); return PFAC_E_NOMEM; }
+    pfac_fold_ascii(img, patterns, n_bytes);
+    const int rc = build_mem_part(img, n_bytes, width, part, n_parts, out, err, err_len);
+    free(img);
+    return rc;
+}
+
 /*
  * Escape-aware reader: the reference's read_pattern_ext() / fgetc_ext() (create_table_reorder.c:131-185,
  * ctdef.h:37-99; present but never called there).  Inside a pattern a backslash introduces
@@ -321,7 +354,8 @@ static int getc_escaped(mem_cursor *c) {
     return c0;
 }
 
-static int build_escaped_mem(const unsigned char *img, size_t n_bytes, int width, pfac_table **out, char *err, size_t err_len) {
+/* fold: the DECODED bytes are folded ("\x41" folds, the x of an escape is never touched) */
+static int build_escaped_mem(const unsigned char *img, size_t n_bytes, int width, int fold, pfac_table **out, char *err, size_t err_len) {
     mem_cursor cur = {img, img + n_bytes};
     size_t cap = 1024, n = 0, arena_cap = 1 << 16, arena_len = 0, total = 0;
     pat_t *pats = (pat_t *)malloc(cap * sizeof(pat_t));
@@ -354,6 +388,7 @@ static int build_escaped_mem(const unsigned char *img, size_t n_bytes, int width
             arena = (unsigned char *)realloc(arena, arena_cap);
             if (!arena) break;
         }
+        if (fold) pfac_fold_ascii(str, str, (size_t)len);
         memcpy(arena + arena_len, str, (size_t)len);
         offs[n] = arena_len;
         pats[n].id = (int32_t)(n + 1);
@@ -373,14 +408,10 @@ static int build_escaped_mem(const unsigned char *img, size_t n_bytes, int width
     return rc;
 }
 
-int pfac_table_build_file_escaped(const char *pattern_file, int width, pfac_table **out, char *err, size_t err_len) {
-    if (!pattern_file || !out) return PFAC_E_ARG;
-    *out = NULL;
-    if (!is_pow2(width) || width > PFAC_COL_MAX) {
-        set_err(err, err_len, "PHF width %ld must be a power of two <= 4096", width); return PFAC_E_ARG;
-    }
-    FILE *f = fopen(pattern_file, "rb");
-    if (!f) { if (err && err_len) snprintf(err, err_len, "cannot open pattern file %s", pattern_file); return PFAC_E_IO; }
+/* the whole file in memory (malloc'ed; the caller frees *img) */
+static int read_file(const char *path, unsigned char **img_out, size_t *n_out, char *err, size_t err_len) {
+    FILE *f = fopen(path, "rb");
+    if (!f) { if (err && err_len) snprintf(err, err_len, "cannot open pattern file %s", path); return PFAC_E_IO; }
     size_t cap = 1 << 16, n = 0;
     unsigned char *img = (unsigned char *)malloc(cap);
     while (img) {
@@ -392,8 +423,42 @@ int pfac_table_build_file_escaped(const char *pattern_file, int width, pfac_tabl
     const int io_error = ferror(f);
     fclose(f);
     if (!img) { set_err(err, err_len, "out of memory (%ld bytes of pattern file)", (long)n); return PFAC_E_NOMEM; }
-    if (io_error) { free(img); if (err && err_len) snprintf(err, err_len, "cannot read pattern file %s", pattern_file); return PFAC_E_IO; }
-    const int rc = build_escaped_mem(img, n, width, out, err, err_len);
+    if (io_error) { free(img); if (err && err_len) snprintf(err, err_len, "cannot read pattern file %s", path); return PFAC_E_IO; }
+    *img_out = img;
+    *n_out = n;
+    return PFAC_OK;
+}
+
+static int build_file_escaped(const char *pattern_file, int width, int fold, pfac_table **out, char *err, size_t err_len) {
+    if (!pattern_file || !out) return PFAC_E_ARG;
+    *out = NULL;
+    if (!is_pow2(width) || width > PFAC_COL_MAX) {
+        set_err(err, err_len, "PHF width %ld must be a power of two <= 4096", width); return PFAC_E_ARG;
+    }
+    unsigned char *img = NULL;
+    size_t n = 0;
+    int rc = read_file(pattern_file, &img, &n, err, err_len);
+    if (rc) return rc;
+    rc = build_escaped_mem(img, n, width, fold, out, err, err_len);
+    free(img);
+    return rc;
+}
+
+int pfac_table_build_file_escaped(const char *pattern_file, int width, pfac_table **out, char *err, size_t err_len) {
+    return build_file_escaped(pattern_file, width, 0, out, err, err_len);
+}
+
+int pfac_table_build_file_nocase(const char *pattern_file, int width, int escapes, pfac_table **out, char *err,
+                                 size_t err_len) {
+    if (escapes) return build_file_escaped(pattern_file, width, 1, out, err, err_len);
+    if (!pattern_file || !out) return PFAC_E_ARG;
+    *out = NULL;
+    unsigned char *img = NULL;
+    size_t n = 0;
+    int rc = read_file(pattern_file, &img, &n, err, err_len);
+    if (rc) return rc;
+    pfac_fold_ascii(img, img, n);
+    rc = build_mem_part(img, n, width, 0, 1, out, err, err_len);
     free(img);
     return rc;
 }
@@ -963,8 +1028,14 @@ static uint64_t hash_members(const int32_t *m, int32_t n, int32_t depth) {
     return h;
 }
 
-static int build_charclass_mem(const unsigned char *img, size_t n_bytes, int width, pfac_table **out, pfac_outputs **outs,
-                               char *err, size_t err_len) {
+/* The elements of a nocase pattern: every upper-case member of the POSITIVE set moves to its lower-case letter. */
+static void cset_fold(cset_t *s) {
+    for (int c = 'A'; c <= 'Z'; c++)
+        if (cset_has(s, c)) { cset_put(s, c, 0); cset_put(s, c | 0x20, 1); }
+}
+
+static int build_charclass_mem(const unsigned char *img, size_t n_bytes, int width, int fold, pfac_table **out,
+                               pfac_outputs **outs, char *err, size_t err_len) {
     /* ---- parse: elems[] arena, pattern p = elems[poff[p] .. poff[p] + plen[p]) ---- */
     mem_cursor cur = {img, img + n_bytes};
     size_t ecap = 1024, n_elem = 0, pcap = 256, n_pat = 0;
@@ -1000,8 +1071,13 @@ static int build_charclass_mem(const unsigned char *img, size_t n_bytes, int wid
                     ch = getc_escaped(&cur);
                 }
                 if (bad) { set_err(err, err_len, "pattern %ld: character class not closed before the end of the line", (long)n_pat + 1); rc = PFAC_E_PATTERN; break; }
+                if (fold) {                    /* "[^...]": the listed set is folded, THEN complemented ("[^A]" rejects 'a') */
+                    if (!setting) for (int k = 0; k < 4; k++) s.w[k] = ~s.w[k];
+                    cset_fold(&s);
+                    if (!setting) for (int k = 0; k < 4; k++) s.w[k] = ~s.w[k];
+                }
             } else {
-                cset_put(&s, (unsigned char)ch, 1);
+                cset_put(&s, fold ? pfac_fold_byte((unsigned char)ch) : (unsigned char)ch, 1);
             }
             if (n_elem == ecap) { ecap *= 2; elems = (cset_t *)realloc(elems, ecap * sizeof(cset_t)); if (!elems) break; }
             elems[n_elem++] = s;
@@ -1139,35 +1215,45 @@ static int build_charclass_mem(const unsigned char *img, size_t n_bytes, int wid
     return PFAC_OK;
 }
 
-int pfac_table_build_mem_charclass(const void *patterns, size_t n_bytes, int width, pfac_table **out, pfac_outputs **outputs,
-                                   char *err, size_t err_len) {
+static int build_mem_charclass(const void *patterns, size_t n_bytes, int width, int fold, pfac_table **out,
+                               pfac_outputs **outputs, char *err, size_t err_len) {
     if (!patterns || !out || !outputs) return PFAC_E_ARG;
     *out = NULL; *outputs = NULL;
     if (!is_pow2(width) || width > PFAC_COL_MAX) { set_err(err, err_len, "PHF width %ld must be a power of two <= 4096", width); return PFAC_E_ARG; }
-    return build_charclass_mem((const unsigned char *)patterns, n_bytes, width, out, outputs, err, err_len);
+    return build_charclass_mem((const unsigned char *)patterns, n_bytes, width, fold, out, outputs, err, err_len);
+}
+
+static int build_file_charclass(const char *pattern_file, int width, int fold, pfac_table **out, pfac_outputs **outputs,
+                                char *err, size_t err_len) {
+    if (!pattern_file || !out || !outputs) return PFAC_E_ARG;
+    *out = NULL; *outputs = NULL;
+    unsigned char *img = NULL;
+    size_t n = 0;
+    int rc = read_file(pattern_file, &img, &n, err, err_len);
+    if (rc) return rc;
+    rc = build_mem_charclass(img, n, width, fold, out, outputs, err, err_len);
+    free(img);
+    return rc;
+}
+
+int pfac_table_build_mem_charclass(const void *patterns, size_t n_bytes, int width, pfac_table **out, pfac_outputs **outputs,
+                                   char *err, size_t err_len) {
+    return build_mem_charclass(patterns, n_bytes, width, 0, out, outputs, err, err_len);
 }
 
 int pfac_table_build_file_charclass(const char *pattern_file, int width, pfac_table **out, pfac_outputs **outputs, char *err,
                                     size_t err_len) {
-    if (!pattern_file || !out || !outputs) return PFAC_E_ARG;
-    *out = NULL; *outputs = NULL;
-    FILE *f = fopen(pattern_file, "rb");
-    if (!f) { if (err && err_len) snprintf(err, err_len, "cannot open pattern file %s", pattern_file); return PFAC_E_IO; }
-    size_t cap = 1 << 16, n = 0;
-    unsigned char *img = (unsigned char *)malloc(cap);
-    while (img) {
-        n += fread(img + n, 1, cap - n, f);
-        if (n < cap) break;
-        cap *= 2;
-        img = (unsigned char *)realloc(img, cap);
-    }
-    const int io_error = ferror(f);
-    fclose(f);
-    if (!img) { set_err(err, err_len, "out of memory (%ld bytes of pattern file)", (long)n); return PFAC_E_NOMEM; }
-    if (io_error) { free(img); if (err && err_len) snprintf(err, err_len, "cannot read pattern file %s", pattern_file); return PFAC_E_IO; }
-    const int rc = pfac_table_build_mem_charclass(img, n, width, out, outputs, err, err_len);
-    free(img);
-    return rc;
+    return build_file_charclass(pattern_file, width, 0, out, outputs, err, err_len);
+}
+
+int pfac_table_build_mem_charclass_nocase(const void *patterns, size_t n_bytes, int width, pfac_table **out,
+                                          pfac_outputs **outputs, char *err, size_t err_len) {
+    return build_mem_charclass(patterns, n_bytes, width, 1, out, outputs, err, err_len);
+}
+
+int pfac_table_build_file_charclass_nocase(const char *pattern_file, int width, pfac_table **out, pfac_outputs **outputs,
+                                           char *err, size_t err_len) {
+    return build_file_charclass(pattern_file, width, 1, out, outputs, err, err_len);
 }
 
 /* One line per (record, pattern that ends in the record's final state), patterns in ascending id. */

@@ -58,11 +58,17 @@ def shard_read_range(n_total: int, rank: int, world: int, halo: int) -> Tuple[in
     return lo, hi, min(n_total, hi + halo)
 
 
-def broadcast_table(table: Optional[PfacTable], device: torch.device, src: int = 0) -> Tuple[torch.Tensor, PfacTable]:
+def broadcast_table(table: Optional[PfacTable], device: torch.device, src: int = 0,
+                    ignore_case: bool = False) -> Tuple[torch.Tensor, PfacTable]:
     """Rank ``src`` passes its ``PfacTable``; every rank returns (int32 image on ``device``, host table).
 
     Two collectives: the image length, then the image itself (one flat int32 buffer: root row +
     r + HT + val + idmap, <= ~17 MiB for the largest pattern sets) -- a single broadcast over xGMI.
+
+    ``ignore_case``: the table holds folded patterns (``PfacTable.from_file(..., ignore_case=True)`` on ``src``).  The
+    image does not say so and is broadcast unchanged; EVERY rank passes the same value, the host table it gets back
+    carries it, and ``GpuMatcher.load_table_device(..., host_table=table)`` turns the scan's case fold on after the
+    rank's upload.
     """
     rank = dist.get_rank()
     wire = _wire(device)
@@ -81,7 +87,9 @@ def broadcast_table(table: Optional[PfacTable], device: torch.device, src: int =
         blob = torch.empty(words, dtype=torch.int32, device=wire)
     dist.broadcast(blob, src)
     if rank != src:
-        table = PfacTable.from_blob(blob.cpu().numpy())
+        table = PfacTable.from_blob(blob.cpu().numpy(), ignore_case=ignore_case)
+    elif bool(table.ignore_case) != bool(ignore_case):
+        raise ValueError("broadcast_table: ignore_case must be what the source rank's table was built with")
     return blob.to(device), table
 
 

@@ -13,7 +13,7 @@ from typing import Optional, Tuple
 
 import numpy as np
 
-from ._ffi import (PFAC_COUNT_ACCUMULATE, PFAC_DOCS_INVERT, PFAC_E_OVERFLOW, PFAC_WORD_LEFT, PFAC_WORD_RIGHT, CRecord, PfacError,
+from ._ffi import (PFAC_COUNT_ACCUMULATE, PFAC_DOCS_INVERT, PFAC_E_OVERFLOW, PFAC_FOLD_ASCII, PFAC_FOLD_NONE, PFAC_WORD_LEFT, PFAC_WORD_RIGHT, CRecord, PfacError,
                    hip_lib)
 from .table import RECORD_DTYPE, PfacTable, redaction_table, replacement_table
 
@@ -134,6 +134,8 @@ class GpuMatcher:
             self.table = PfacTable.from_blob(blob)
         self._flen_set = False
         self._check(self._L.pfac_table_upload(self._ctx, blob.ctypes.data, blob.size))
+        if self.table.ignore_case:          # (an upload leaves the fold off)
+            self.set_case_fold(True)
 
     def load_table_device(self, d_blob, n_words: int, stream: int = 0, host_table: Optional[PfacTable] = None) -> None:
         """Install a table image that already sits in this GPU's memory (e.g. after an RCCL broadcast)."""
@@ -141,6 +143,21 @@ class GpuMatcher:
         self._check(self._L.pfac_table_upload_device(self._ctx, _ptr(d_blob), int(n_words), stream))
         if host_table is not None:
             self.table = host_table
+            if host_table.ignore_case:
+                self.set_case_fold(True)
+
+    def set_case_fold(self, on: bool) -> None:
+        """Case-insensitive scans (``pfac_table_set_case_fold``): every scan queued from now on, on every slot, matches
+        as if A-Z of the input were a-z; scans already queued keep their mode.  The input buffer is never written, and
+        the passes behind the scan (whole-word filter, replaces, split, gather) see the bytes as they are.  Meant for a
+        table of folded patterns (``ignore_case=True``); the next table upload turns it off."""
+        self._check(self._L.pfac_table_set_case_fold(self._ctx, PFAC_FOLD_ASCII if on else PFAC_FOLD_NONE))
+
+    @property
+    def case_fold(self) -> bool:
+        mode = C.c_uint32()
+        self._check(self._L.pfac_table_case_fold(self._ctx, C.byref(mode)))
+        return mode.value == PFAC_FOLD_ASCII
 
     def info(self) -> dict:
         v, t, g, l = C.c_int(), C.c_int(), C.c_int(), C.c_int()

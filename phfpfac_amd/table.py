@@ -23,10 +23,14 @@ class PfacTable:
     ``r``, ``HT``, ``val`` (the perfect hash), ``width``, ``ht_size`` (HTSize),
     ``state_num``, ``num_final`` (final_state_num), ``max_pat_len``; ``idmap``
     is ``patternIdMaps`` (final state -> 1-based pattern line number).
+
+    ``ignore_case``: the table was built from folded patterns (``ignore_case=True`` of a constructor) and is meant
+    for folded scans; ``GpuMatcher.load_table`` sets the scan's case fold from it.  The blob does not carry it.
     """
 
-    def __init__(self, ptr):
+    def __init__(self, ptr, ignore_case: bool = False):
         self._ptr = ptr
+        self.ignore_case = bool(ignore_case)
         t = ptr.contents
         for name in ("width", "width_bit", "n_patterns", "num_final", "state_num", "max_pat_len", "max_row",
                      "ht_size", "n_keys"):
@@ -39,32 +43,42 @@ class PfacTable:
 
     # -- construction -----------------------------------------------------
     @classmethod
-    def from_file(cls, pattern_file: str, width: int = 256, escapes: bool = False) -> "PfacTable":
-        """``escapes=True`` reads the file like the reference's ``read_pattern_ext`` (backslash escapes)."""
+    def from_file(cls, pattern_file: str, width: int = 256, escapes: bool = False, ignore_case: bool = False) -> "PfacTable":
+        """``escapes=True`` reads the file like the reference's ``read_pattern_ext`` (backslash escapes).
+        ``ignore_case=True`` folds the patterns (A-Z -> a-z, after escape decoding) before they are sorted."""
         L = host_lib()
         ptr = C.POINTER(CTable)()
         err = C.create_string_buffer(256)
-        fn = L.pfac_table_build_file_escaped if escapes else L.pfac_table_build_file
-        rc = fn(os.fsencode(pattern_file), int(width), C.byref(ptr), err, 256)
+        if ignore_case:
+            rc = L.pfac_table_build_file_nocase(os.fsencode(pattern_file), int(width), int(bool(escapes)), C.byref(ptr), err, 256)
+        else:
+            fn = L.pfac_table_build_file_escaped if escapes else L.pfac_table_build_file
+            rc = fn(os.fsencode(pattern_file), int(width), C.byref(ptr), err, 256)
         if rc:
             raise PfacError(rc, err.value.decode(errors="replace"))
-        return cls(ptr)
+        return cls(ptr, ignore_case)
 
     @classmethod
-    def from_bytes(cls, patterns: bytes, width: int = 256, part: int = 0, n_parts: int = 1) -> "PfacTable":
+    def from_bytes(cls, patterns: bytes, width: int = 256, part: int = 0, n_parts: int = 1,
+                   ignore_case: bool = False) -> "PfacTable":
         L = host_lib()
         ptr = C.POINTER(CTable)()
         err = C.create_string_buffer(256)
         buf = C.create_string_buffer(patterns, len(patterns))
-        rc = L.pfac_table_build_mem_part(buf, len(patterns), int(width), int(part), int(n_parts), C.byref(ptr), err, 256)
+        fn = L.pfac_table_build_mem_nocase if ignore_case else L.pfac_table_build_mem_part
+        rc = fn(buf, len(patterns), int(width), int(part), int(n_parts), C.byref(ptr), err, 256)
         if rc:
             raise PfacError(rc, err.value.decode(errors="replace"))
-        return cls(ptr)
+        return cls(ptr, ignore_case)
 
     @classmethod
-    def from_file_part(cls, pattern_file: str, width: int, part: int, n_parts: int) -> "PfacTable":
+    def from_file_part(cls, pattern_file: str, width: int, part: int, n_parts: int, ignore_case: bool = False) -> "PfacTable":
         """Partition ``part`` of ``n_parts`` of the sorted pattern list -- the reference's pattern partitioning
-        (create_table_reorder.c:217-247): every partition scans the whole input, ``merge_partitions`` merges."""
+        (create_table_reorder.c:217-247): every partition scans the whole input, ``merge_partitions`` merges.
+        ``ignore_case=True``: the cuts are those of the folded, sorted list."""
+        if ignore_case:
+            with open(pattern_file, "rb") as f:
+                return cls.from_bytes(f.read(), width, part, n_parts, ignore_case=True)
         L = host_lib()
         ptr = C.POINTER(CTable)()
         err = C.create_string_buffer(256)
@@ -75,23 +89,26 @@ class PfacTable:
         return cls(ptr)
 
     @classmethod
-    def from_charclass(cls, patterns, width: int = 256) -> "PfacTable":
+    def from_charclass(cls, patterns, width: int = 256, ignore_case: bool = False) -> "PfacTable":
         """Character-class pattern file (path) or image (bytes): single characters and ``[...]`` / ``[^...]`` classes
         with ``l-r`` ranges, escape-aware (charset_table_reorder.c:45-168).  The table's final states can stand for
         several patterns: ``out_first`` / ``out_ids`` list them (``idmap`` holds the first); print with
-        ``emit_records_multi``."""
+        ``emit_records_multi``.  ``ignore_case=True`` folds single characters and the listed set of every class;
+        ``[^...]`` complements the folded set."""
         from ._ffi import COutputs
         L = host_lib()
         ptr, optr = C.POINTER(CTable)(), C.POINTER(COutputs)()
         err = C.create_string_buffer(256)
         if isinstance(patterns, (bytes, bytearray)):
             buf = C.create_string_buffer(bytes(patterns), len(patterns))
-            rc = L.pfac_table_build_mem_charclass(buf, len(patterns), int(width), C.byref(ptr), C.byref(optr), err, 256)
+            fn = L.pfac_table_build_mem_charclass_nocase if ignore_case else L.pfac_table_build_mem_charclass
+            rc = fn(buf, len(patterns), int(width), C.byref(ptr), C.byref(optr), err, 256)
         else:
-            rc = L.pfac_table_build_file_charclass(os.fsencode(patterns), int(width), C.byref(ptr), C.byref(optr), err, 256)
+            fn = L.pfac_table_build_file_charclass_nocase if ignore_case else L.pfac_table_build_file_charclass
+            rc = fn(os.fsencode(patterns), int(width), C.byref(ptr), C.byref(optr), err, 256)
         if rc:
             raise PfacError(rc, err.value.decode(errors="replace"))
-        t = cls(ptr)
+        t = cls(ptr, ignore_case)
         o = optr.contents
         t.out_first = np.ctypeslib.as_array(o.first, (o.n_states + 1,)).copy()
         t.out_ids = np.ctypeslib.as_array(o.ids, (max(int(t.out_first[-1]), 1),))[: int(t.out_first[-1])].copy()
@@ -99,14 +116,15 @@ class PfacTable:
         return t
 
     @classmethod
-    def from_blob(cls, blob: np.ndarray) -> "PfacTable":
+    def from_blob(cls, blob: np.ndarray, ignore_case: bool = False) -> "PfacTable":
+        """``ignore_case``: what the table's builder was told -- the image does not carry it."""
         L = host_lib()
         blob = np.ascontiguousarray(blob, dtype=np.int32)
         ptr = C.POINTER(CTable)()
         rc = L.pfac_table_from_blob(blob.ctypes.data, blob.size, C.byref(ptr))
         if rc:
             raise PfacError(rc, "bad table image")
-        return cls(ptr)
+        return cls(ptr, ignore_case)
 
     @classmethod
     def from_reference_arrays(cls, s0, r, HT, val, idmap, width, state_num, num_final, ht_size, max_pat_len):
@@ -178,6 +196,18 @@ class PfacTable:
             except Exception:
                 pass
             self._ptr = None
+
+
+def fold_ascii(data) -> np.ndarray:
+    """The case fold of an ``ignore_case`` scan, on the host (``pfac_fold_ascii``): a uint8 copy of ``data`` (bytes or a
+    uint8 array) with A-Z turned into a-z and every other byte, all of 0x80..0xFF included, unchanged."""
+    src = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview))
+                               else np.asarray(data, dtype=np.uint8))
+    out = np.empty_like(src)
+    rc = host_lib().pfac_fold_ascii(out.ctypes.data, src.ctypes.data, src.size)
+    if rc:
+        raise PfacError(rc, "pfac_fold_ascii")
+    return out
 
 
 MAX_REPLACEMENT = 65536              # bytes of one replacement (PFAC_MAX_REPLACEMENT)

@@ -14,6 +14,7 @@ build)
   c=$2; tag=$3; d=$(mktemp -d); mkdir -p $d/include abx
   git show $c:phfpfac_amd/csrc/pfac_hip.hip > $d/pfac_hip.hip
   git show $c:include/pfac.h > $d/include/pfac.h
+  git show $c:phfpfac_amd/csrc/pfac_fold.h > $d/pfac_fold.h 2>/dev/null || rm -f $d/pfac_fold.h   # (commits before the case fold have none)
   echo 'extern "C" {' > $d/stubs.cc
   for s in $(python3 -c "import sys; sys.path.insert(0, '.'); from phfpfac_amd import _ffi; print(' '.join(_ffi.HIP_SYMBOLS))"); do
     grep -q "$s" $d/pfac_hip.hip || echo "int $s() { return -7; }" >> $d/stubs.cc
