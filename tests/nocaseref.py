@@ -259,3 +259,47 @@ def passes_case():
     """The input of the passes behind the scan: lines of mixed-case text, words next to the matches."""
     pats = b"england\nEngland were\ncricket\nODI\nover\nruns per over\nteam\nlanD\n"          # (nothing of the text's second sentence)
     return Case("passes-lines", pats, mixed_text(6 * TILE + 77, seed=11))
+
+
+# ---------------------------------------------------------------------------
+# character classes
+
+def fold_class_set(listed):
+    """The listed set of a class (256 booleans) with its upper-case members turned into their lower-case letters."""
+    out = np.array(listed, dtype=bool)
+    up = out[0x41:0x5B].copy()
+    out[0x41:0x5B] = False
+    out[0x61:0x7B] |= up
+    return out
+
+
+def folded_classes(image):
+    """The class image `image` as ClassMatcher's `parsed`: every single character folded, the LISTED set of every class
+    folded, `[^...]` complementing the folded set -- the rule of from_charclass(..., ignore_case=True), written from its
+    documentation.  For images without backslash escapes (the first `]` closes a class)."""
+    assert b"\\" not in image and image.endswith(b"\n")
+    pats = []
+    for line in image[:-1].split(b"\n"):
+        elems, k = [], 0
+        while k < len(line):
+            listed, negated = np.zeros(256, dtype=bool), False
+            if line[k] == 0x5B:
+                end = line.index(b"]", k + 1)
+                body = line[k + 1:end]
+                negated = body[:1] == b"^"
+                body, j = body[1:] if negated else body, 0
+                while j < len(body):
+                    if j + 2 < len(body) and body[j + 1] == 0x2D:
+                        listed[body[j]:body[j + 2] + 1] = True
+                        j += 3
+                    else:
+                        listed[body[j]] = True
+                        j += 1
+                k = end + 1
+            else:
+                listed[line[k]] = True
+                k += 1
+            listed = fold_class_set(listed)
+            elems.append(~listed if negated else listed)
+        pats.append(elems)
+    return pats

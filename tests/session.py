@@ -20,6 +20,11 @@ Three parts, none of which needs a GPU to import:
                        path as well: the delimiter split, the matching documents with and without context lines and
                        the gather of their bytes (split, doc_fetch, matching, context, ids_fetch, gather, ga_fetch,
                        gaoff_fetch), whose values come from splitref and gatherref.
+                       plan(seed, fold=True) is a fifth with the case fold as well (set_fold, get_fold, an upload of
+                       the image alone through load_table_device): the setting belongs to the uploaded table, a scan
+                       keeps the mode it was queued with, and its expectation is the same CPU matcher over
+                       nocaseref.fold(input) while every pass behind it keeps reading the original bytes.  It draws from
+                       POOL: the nine tables of the other families and the four nocase tables of FOLD_TABLES.
 
 The device under test hands out final STATES; they are mapped to pattern ids with the idmap of the table the scan ran
 with (a stand-in that already works in ids says so with ``states_are_ids``)."""
@@ -31,6 +36,7 @@ import tempfile
 import numpy as np
 
 import countref
+import nocaseref
 import wordref
 from classfuzz import ClassMatcher as _ClassMatcher
 from docref import oracle_per_doc, random_offsets
@@ -100,6 +106,48 @@ TABLES = {
     "dups": dict(gen=(105, 3, 9, 4, 3), knobs=[_k(), _k(PFAC_DENSE="1")],
                  inputs=[("m300", 300_007, "plant"), ("t4095", 4095, "plant"), ("empty", 0, "plant")]),
 }
+# The tables of the fold family (plan(seed, fold=True)), next to the nine above, which the pinned plans index and which
+# stay as they are: four small tables with `nocase` -- built with ignore_case=True, so that GpuMatcher.load_table leaves
+# the case fold ON after the upload -- whose inputs are mixed-case text.  wordsi: words and letters of paragraph402 in
+# Title and UPPER case, fifteen lines (two-byte records), one dense and one matchless input of >= 64 tiles, so that the
+# staging mode flips with the fold on; symi: nocaseref.symbol_patterns(); cclassi: a class file through
+# from_charclass(..., ignore_case=True); root1i: the one-edge root of nocaseref.root1_cases().
+WORDSI = (b"A\n" b"I\n" b"E\n" b"T\n" b"O\n" b"N\n" b"The\n" b"AND\n" b"In\n" b"ENGLAND\n" b"Cricket\n" b"WITH\n" b"Over\n" b"Team\n"
+          b"TEAM\n")                                              # (fifteen lines: two-byte records hold sixteen final states)
+CCLASSI = b"[A-C]x\n" b"[^A]b\n" b"[^a-z0-9 ]\n" b"q[0-9][0-9]\n" b"Ax\n" b"B[x-z]\n" b"[a-c]X\n"     # (the last: the first in the other case)
+CCLASSI_UNIT = b"Ax bX cx.AB ab Q12 q07-b Zb!aX By,q1x CX;bb.Cz Q99 "
+ROOT1I = b"Qa\nQb\nQax\nQbY\n"
+ROOT1I_UNIT = b"..Qa..QA.QAB.xa.QABC,QB;QBY QAX-QCZ.xcz..QC" + b"." * 21      # (nocaseref.root1_cases: no lower-case q anywhere)
+NOMATCH_UNIT = b"0123456789 .,;-\n"                              # (no letter: matchless for wordsi, folded or not)
+FOLD_TABLES = {
+    "wordsi": dict(patterns=WORDSI, nocase=True,
+                   knobs=[_k(), _k(PFAC_LAG="1"), _k(PFAC_LAG="2"), _k(PFAC_L2F="3"), _k(PFAC_TICKET_WAYS="1"), _k(PFAC_NWB="4")],
+                   inputs=[("dense", 300_007, "mixed"), ("none", 300_007, "nomatch"), ("g1", GROUP + 1, "mixed"), ("t4097", 4097, "mixed"),
+                           ("s17", 17, "mixed")]),
+    "symi": dict(patterns=nocaseref.symbol_patterns(), nocase=True,
+                 knobs=[_k(PFAC_FORCE_L2="1"), _k(PFAC_FORCE_L2="1", PFAC_DENSE="1"), _k(PFAC_FORCE_L2="1", PFAC_DENSE="1", PFAC_D2_LOGCAP="64"),
+                        _k(PFAC_REC_BYTES="4")],
+                 inputs=[("m70", 70_001, "mixedsym"), ("t4095", 4095, "mixedsym"), ("one", 1, "mixedsym")]),
+    "cclassi": dict(cclass=CCLASSI, nocase=True, knobs=[_k(), _k(PFAC_REC_BYTES="4"), _k(PFAC_FORCE_L2="1"), _k(PFAC_DENSE="1")],
+                    inputs=[("gm1", GROUP - 1, "ccunit"), ("t4097", 4097, "ccunit")]),
+    "root1i": dict(patterns=ROOT1I, nocase=True, knobs=[_k(), _k(PFAC_FORCE_L2="1"), _k(PFAC_L2F="0"), _k(PFAC_L2F="2")],
+                   inputs=[("t3", 3 * TILE + 11, "root1"), ("s17", 17, "root1")]),
+}
+# One more input for each of the nine old tables, which only the fold family scans (TABLES itself stays byte for byte):
+# the table's own input 0 (input 1 where that is the large one) with a seeded half of its lower-case letters in upper
+# case -- for abc2, whose inputs hold a, b and c only, that is the one input the fold changes anything for.
+FOLD_INPUTS = {t: ("upper", TABLES[t]["inputs"][1 if t == "mid4" else 0][1], "upper:%d" % (1 if t == "mid4" else 0)) for t in TABLES}
+POOL = {t: dict(d, inputs=d["inputs"] + [FOLD_INPUTS[t]]) for t, d in TABLES.items()}
+POOL.update(FOLD_TABLES)
+FOLD_SEEDS = list(range(24))            # ... and of its plans with the case fold as well: plan(seed, fold=True)
+FOLD_PLAN_OPS = 120
+
+
+def _tix(t):
+    """The number of table `t` in the seeds of what is drawn for it (the nine old tables keep theirs)."""
+    return sorted(TABLES).index(t) if t in TABLES else len(TABLES) + sorted(FOLD_TABLES).index(t)
+
+
 REP_KEYS = ("r0", "r1", "redact")
 DOC_KEYS = ("d0", "d1", "bad_end", "bad_order")
 TEXT_BASES = (0, 999_999_990)
@@ -135,6 +183,7 @@ CNT_ENTRY = CNT_FILL * 0x0101010101010101   # zeroes, or a plain count that does
 OUT_FILL = 0xC7                         # every byte of a fresh caller's pass output and of the guard bands around it
 MAX_FILTERS = 3                         # distinct filters on one scan: more would only thin out the cache
 WORD_TAB = {"cclass": b"abcxyz", "negcc": b"abcy", "nlesc": b"abxq\n"}     # (the other tables: the first half of their symbols)
+WORD_TAB.update({t: b"abcdefghijklmnopqrstuvwxyz" for t in FOLD_TABLES})       # lower-case letters only: the set separates the cases
 
 
 def _gen_lines(seed, alpha, npat, maxlen, dups):
@@ -165,10 +214,22 @@ class Expectations:
 
     # -- tables -------------------------------------------------------------
     def _table(self, t):
-        d = TABLES[t]
+        d = POOL[t]
+        if "cclass" in d and d.get("nocase"):                   # (the reference: the class image with its listed sets folded, nocaseref.folded_classes)
+            m = _ClassMatcher(d["cclass"], parsed=nocaseref.folded_classes(d["cclass"]))
+            return dict(table=PfacTable.from_charclass(d["cclass"], 256, ignore_case=True), matcher=m, ll=m.lens, symbols=None, lines=None)
         if "cclass" in d:
             m = _ClassMatcher(d["cclass"])
             return dict(table=PfacTable.from_charclass(d["cclass"], 256), matcher=m, ll=m.lens, symbols=None, lines=None)
+        if "patterns" in d:                                     # a nocase table: the file as written goes to the builder, its numpy fold to the CPU oracle
+            assert d["nocase"]
+            path = os.path.join(self.dir, t + ".pat")
+            with open(path, "wb") as f:
+                f.write(d["patterns"])
+            with open(path + ".folded", "wb") as f:
+                f.write(nocaseref.fold_bytes(d["patterns"]))
+            ll = np.array([0] + [len(p) for p in d["patterns"][:-1].split(b"\n")], dtype=np.int64)
+            return dict(table=PfacTable.from_file(path, 256, ignore_case=True), matcher=Oracle(path + ".folded", 1, 1), ll=ll, symbols=None, lines=None)
         if "escaped" in d:                                      # (lengths from the parsed lines; the matcher is the CPU oracle's escape-aware reader)
             path = os.path.join(self.dir, t + ".pat")
             with open(path, "wb") as f:
@@ -203,8 +264,19 @@ class Expectations:
 
     # -- inputs -------------------------------------------------------------
     def _input(self, t, i):
-        name, n, style = TABLES[t]["inputs"][i]
-        rng = np.random.default_rng([sorted(TABLES).index(t), i, 0x494E])
+        name, n, style = POOL[t]["inputs"][i]
+        if style in ("mixed", "mixedsym"):
+            return nocaseref.mixed_text(n, seed=402 + i, symbols=style == "mixedsym")
+        if style in ("nomatch", "ccunit", "root1"):
+            return nocaseref.tiled(n, {"nomatch": NOMATCH_UNIT, "ccunit": CCLASSI_UNIT, "root1": ROOT1I_UNIT}[style])
+        if style.startswith("upper:"):                          # (the fold family's extra input of an old table)
+            buf = self.input(t, int(style[6:])).copy()
+            if t == "abc2":
+                buf = buf[:n].copy()
+            lower = (buf >= 0x61) & (buf <= 0x7A)
+            buf[lower & (np.random.default_rng([_tix(t), 0x5550]).random(buf.size) < 0.5)] &= 0xDF
+            return buf
+        rng = np.random.default_rng([_tix(t), i, 0x494E])
         if style.startswith("abc:"):
             d = float(style[4:])
             u = rng.random(n)
@@ -226,7 +298,7 @@ class Expectations:
         return self._memo(("input", t, i), lambda: self._input(t, i))
 
     def input_size(self, t, i):
-        return TABLES[t]["inputs"][i][1]
+        return POOL[t]["inputs"][i][1]
 
     # -- whole-word filters ---------------------------------------------------
     def word_bytes(self, t, ws):
@@ -251,8 +323,9 @@ class Expectations:
         d = FILTERS[f]
         return (EDGE_BITS[d["edges"]], d["ws"], self.neighbour(t, d["ws"], d["prev"]), self.neighbour(t, d["ws"], d["next"]), dkey or "")
 
-    def _keep(self, t, i, no, one):
-        """The keep mask of ONE applied filter over the unfiltered records of the scan (composition is intersection)."""
+    def _keep(self, t, i, no, one, fold=False):
+        """The keep mask of ONE applied filter over the unfiltered records of the scan (composition is intersection).
+        The filter judges the ORIGINAL bytes, whatever the scan's fold."""
         def make():
             edges, ws, prev, nxt, dkey = one
             chars = self.word_bytes(t, ws)
@@ -261,67 +334,77 @@ class Expectations:
                 bits = np.zeros(4, dtype=np.uint64)
                 for b in chars:
                     bits[b >> 6] |= np.uint64(1 << (b & 63))
-            pos, _, lens = self.scan(t, i, no)
+            pos, _, lens = self.scan(t, i, no, fold=fold)
             off = self.offsets(t, i, no, dkey) if dkey else None
             return wordref.filter_words(self.input(t, i), pos, lens, bits, edges, prev, nxt, off)   # (n_avail: the whole input)
-        return self._memo(("keep", t, i, no, one), make)
+        return self._memo(("keep", t, i, no, fold, one), make)
 
     # -- the scan -----------------------------------------------------------
-    def scan(self, t, i, no, f=()):
+    def scan(self, t, i, no, f=(), fold=False):
         """(pos, ids, lens) of the records that start in [0, no); walks may read the whole input (the halo).  `f`: the
-        scan's filter state (`applied`), whose filters the records have passed."""
+        scan's filter state (`applied`), whose filters the records have passed.  `fold`: a case-insensitive scan -- the
+        header's sentence and nothing else: the same matcher (the same pattern file) over nocaseref.fold(input).  The
+        cache keys a scan by (table, input, n_owned, fold, filter state)."""
         def make():
             info = self.tinfo(t)
-            pos, ids = self._memo(("whole", t, i), lambda: info["matcher"].scan_spec(self.input(t, i), None))
+            data = nocaseref.fold(self.input(t, i)) if fold else self.input(t, i)
+            pos, ids = self._memo(("whole", t, i, fold), lambda: info["matcher"].scan_spec(data, None))
             own = pos < no
             pos, ids = pos[own].astype(np.int64), ids[own].astype(np.int64)
             return pos, ids, info["ll"][ids]
 
         def filtered():
-            pos, ids, lens = self.scan(t, i, no)
+            pos, ids, lens = self.scan(t, i, no, fold=fold)
             keep = np.ones(pos.size, dtype=bool)
             for one in f:
-                keep &= self._keep(t, i, no, one)
+                keep &= self._keep(t, i, no, one, fold)
             return pos[keep], ids[keep], lens[keep]
-        return self._memo(("scan", t, i, no, f), filtered) if f else self._memo(("scan", t, i, no), make)
+        return self._memo(("scan", t, i, no, fold, f), filtered) if f else self._memo(("scan", t, i, no, fold), make)
 
-    def count(self, t, i, no, f=()):
-        return int(self.scan(t, i, no, f)[0].size)
-
-    def text(self, t, i, no, base, f=()):
+    def fold_differs(self, t, i):
+        """Whether the fold changes the records of the whole input `i` of table `t` (the same matcher, folded or not)."""
         def make():
-            pos, ids, _ = self.scan(t, i, no, f)
-            return "".join("At position %4d, match pattern %d\n" % (p + base, k) for p, k in zip(pos.tolist(), ids.tolist())).encode()
-        return self._memo(("text", t, i, no, base, f), make)
+            a, b = self.scan(t, i, self.input_size(t, i)), self.scan(t, i, self.input_size(t, i), fold=True)
+            return a[0].size != b[0].size or not (np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]))
+        return self._memo(("differs", t, i), make)
 
-    def checksum(self, t, i, no, base, f=()):
-        pos, ids, _ = self.scan(t, i, no, f)
+    def count(self, t, i, no, f=(), fold=False):
+        return int(self.scan(t, i, no, f, fold)[0].size)
+
+    def text(self, t, i, no, base, f=(), fold=False):
+        def make():
+            pos, ids, _ = self.scan(t, i, no, f, fold)
+            return "".join("At position %4d, match pattern %d\n" % (p + base, k) for p, k in zip(pos.tolist(), ids.tolist())).encode()
+        return self._memo(("text", t, i, no, fold, base, f), make)
+
+    def checksum(self, t, i, no, base, f=(), fold=False):
+        pos, ids, _ = self.scan(t, i, no, f, fold)
         return match_checksum(pos + base, ids)
 
     # -- selection and replace ------------------------------------------------
-    def sel(self, t, i, no, entry, f=()):
+    def sel(self, t, i, no, entry, f=(), fold=False):
         """(pos, ids, exit) of the leftmost-longest selection from `entry`."""
         def make():
-            pos, ids, lens = self.scan(t, i, no, f)
+            pos, ids, lens = self.scan(t, i, no, f, fold)
             idx, ex = greedy(pos, lens, entry, no)
             return pos[idx], ids[idx], int(ex)
-        return self._memo(("sel", t, i, no, entry, f), make)
+        return self._memo(("sel", t, i, no, fold, entry, f), make)
 
     def reps(self, t, rkey):
         def make():
             ll = self.tinfo(t)["ll"]
             if rkey == "redact":
                 return {k: b"#" * int(ll[k]) for k in range(1, ll.size)}
-            rng = np.random.default_rng([sorted(TABLES).index(t), REP_KEYS.index(rkey), 0x5245])
+            rng = np.random.default_rng([_tix(t), REP_KEYS.index(rkey), 0x5245])
             return {k: rng.integers(0, 256, int(rng.integers(1000, 3000)) if rng.random() < 0.02 else int(rng.integers(0, 33))).astype(np.uint8).tobytes()
                     for k in range(1, ll.size)}
         return self._memo(("reps", t, rkey), make)
 
-    def replace(self, t, i, no, entry, rkey, f=()):
-        def make():
-            spos, sids, _ = self.sel(t, i, no, entry, f)
+    def replace(self, t, i, no, entry, rkey, f=(), fold=False):
+        def make():                                             # (the splice copies the ORIGINAL bytes between the picks)
+            spos, sids, _ = self.sel(t, i, no, entry, f, fold)
             return splice(self.input(t, i), entry, no, spos, self.tinfo(t)["ll"][sids], sids, rep_table(self.reps(t, rkey)))
-        return self._memo(("replace", t, i, no, entry, rkey, f), make)
+        return self._memo(("replace", t, i, no, fold, entry, rkey, f), make)
 
     # -- documents ----------------------------------------------------------
     def delims(self, t, i):
@@ -347,7 +430,7 @@ class Expectations:
             return self.split(t, i, no, int(dkey[6:]))[0]
 
         def make():
-            rng = np.random.default_rng([sorted(TABLES).index(t), i, no, DOC_KEYS.index(dkey), 0x444F])
+            rng = np.random.default_rng([_tix(t), i, no, DOC_KEYS.index(dkey), 0x444F])
             off = random_offsets(rng, no, int(rng.integers(1, 60)), empties=int(rng.integers(0, 4)))
             cuts = [c for k in rng.integers(1, max(no // TILE, 1) + 1, 2) for c in (int(k) * TILE - 1, int(k) * TILE, int(k) * TILE + 1) if c <= no]
             off = np.sort(np.concatenate([off, np.array(cuts, dtype=np.uint64)]))
@@ -362,33 +445,37 @@ class Expectations:
             return off.astype(np.uint64)
         return self._memo(("off", t, i, no, dkey), make)
 
-    def _doc_matcher(self, t, i, no, dkey, f):
-        """What docref / docreplref scan every document with: the CPU oracle, or for a filtered scan the scan's kept
-        records cut at the documents (the filter judged them in the whole buffer, which no scan of a document repeats)."""
-        return _DocCut(self.scan(t, i, no, f), self.offsets(t, i, no, dkey)) if f else self.tinfo(t)["matcher"]
+    def _doc_matcher(self, t, i, no, dkey, f, fold=False):
+        """What docref / docreplref scan every document with: the CPU oracle (under the fold: the oracle over the folded
+        bytes of the document it is handed), or for a filtered scan the scan's kept records cut at the documents (the
+        filter judged them in the whole buffer, which no scan of a document repeats)."""
+        if f:
+            return _DocCut(self.scan(t, i, no, f, fold), self.offsets(t, i, no, dkey))
+        return _Folding(self.tinfo(t)["matcher"]) if fold else self.tinfo(t)["matcher"]
 
-    def seg(self, t, i, no, dkey, f=()):
+    def seg(self, t, i, no, dkey, f=(), fold=False):
         """(doc_first, pos relative to the document, ids) of every document scanned on its own."""
         def make():
-            first, pos, ids = oracle_per_doc(self._doc_matcher(t, i, no, dkey, f), self.input(t, i)[:no], self.offsets(t, i, no, dkey))
+            first, pos, ids = oracle_per_doc(self._doc_matcher(t, i, no, dkey, f, fold), self.input(t, i)[:no], self.offsets(t, i, no, dkey))
             return first, pos.astype(np.int64), ids.astype(np.int64)
-        return self._memo(("seg", t, i, no, dkey, f), make)
+        return self._memo(("seg", t, i, no, fold, dkey, f), make)
 
-    def docsel(self, t, i, no, dkey, f=(), rkey=None):
-        """(doc_first, pos relative to the SCAN, ids, out_off, out) of every document's own selection (and output)."""
+    def docsel(self, t, i, no, dkey, f=(), rkey=None, fold=False):
+        """(doc_first, pos relative to the SCAN, ids, out_off, out) of every document's own selection (and output, spliced
+        from the ORIGINAL bytes)."""
         def make():
             off = self.offsets(t, i, no, dkey)
             tab = None if rkey is None else rep_table(self.reps(t, rkey))
-            first, pos, ids, out_off, out = per_doc(self._doc_matcher(t, i, no, dkey, f), self.input(t, i)[:no], off, self.tinfo(t)["ll"], tab)
+            first, pos, ids, out_off, out = per_doc(self._doc_matcher(t, i, no, dkey, f, fold), self.input(t, i)[:no], off, self.tinfo(t)["ll"], tab)
             doc = np.repeat(np.arange(off.size - 1, dtype=np.int64), np.diff(first.astype(np.int64)))
             return first, pos.astype(np.int64) + off[doc].astype(np.int64), ids.astype(np.int64), out_off, out
-        return self._memo(("docsel", t, i, no, dkey, f, rkey), make)
+        return self._memo(("docsel", t, i, no, fold, dkey, f, rkey), make)
 
 
     # -- lines: matching documents and their bytes ---------------------------
     def doc_first(self, src, key):
         """The doc_first a matching call reads: of the segment ("seg") or of the per-document selection ("docsel") `key`."""
-        return (self.seg if src == "seg" else self.docsel)(*key)[0]
+        return self.seg(*key)[0] if src == "seg" else self.docsel(*key[:5], None, key[5])[0]
 
     def doc_ids(self, spec):
         """The ids of a matching call.  spec = (src, key, "m", invert) or (src, key, "c", before, after):
@@ -429,8 +516,8 @@ class Expectations:
         return self._memo(("gather", t, i, nb, doc, spec, form), make)
 
     # -- counts per pattern ---------------------------------------------------
-    # A contribution to a count buffer ("part"): ("scan", t, i, no, f), ("sel", t, i, no, entry, f) or
-    # ("docsel", t, i, no, dkey, f) -- the keys of scan / sel / docsel above.
+    # A contribution to a count buffer ("part"): ("scan", t, i, no, f, fold), ("sel", t, i, no, entry, f, fold) or
+    # ("docsel", t, i, no, dkey, f, fold) -- the arguments of scan / sel / docsel above.
     def n_ids(self, t):
         return int(self.tinfo(t)["ll"].size)
 
@@ -440,7 +527,7 @@ class Expectations:
         return int(np.unique(idmap).size) == int(self.table(t).num_final)
 
     def part_ids(self, part):
-        return {"scan": lambda: self.scan(*part[1:])[1], "sel": lambda: self.sel(*part[1:])[1], "docsel": lambda: self.docsel(*part[1:])[2]}[part[0]]()
+        return {"scan": lambda: self.scan(*part[1:])[1], "sel": lambda: self.sel(*part[1:])[1], "docsel": lambda: self.docsel(*part[1:6], None, part[6])[2]}[part[0]]()
 
     def part_counts(self, part):
         """uint64[n_ids]: the histogram by pattern id of one contribution (numpy.bincount over the CPU's records)."""
@@ -451,19 +538,29 @@ class Expectations:
         assert self.injective(part[1])
         return self._memo(("cnts",) + part, lambda: countref.state_counts(self.table(part[1]), self.part_ids(part)))
 
-    def state_counts(self, t, i, no, f=()):
-        """Counts by pattern id of Expectations.scan(t, i, no, f)."""
-        return self.part_counts(("scan", t, i, no, f))
+    def state_counts(self, t, i, no, f=(), fold=False):
+        """Counts by pattern id of Expectations.scan(t, i, no, f, fold)."""
+        return self.part_counts(("scan", t, i, no, f, fold))
 
-    def sel_counts(self, t, i, no, entry=0, f=(), dkey=None):
+    def sel_counts(self, t, i, no, entry=0, f=(), dkey=None, fold=False):
         """Counts by pattern id of the picks of sel(t, i, no, entry, f), or with `dkey` of docsel(t, i, no, dkey, f)."""
-        return self.part_counts(("sel", t, i, no, entry, f) if dkey is None else ("docsel", t, i, no, dkey, f))
+        return self.part_counts(("sel", t, i, no, entry, f, fold) if dkey is None else ("docsel", t, i, no, dkey, f, fold))
 
     def sum_counts(self, t, parts, by_state=False):
         out = np.zeros(int(self.table(t).num_final) if by_state else self.n_ids(t), dtype=np.uint64)
         for part in parts:
             out = out + (self.part_states(part) if by_state else self.part_counts(part))
         return out
+
+
+class _Folding:
+    """The CPU matcher over the folded bytes of whatever it is handed (the documents of a folded scan, one at a time)."""
+
+    def __init__(self, matcher):
+        self.matcher = matcher
+
+    def scan_spec(self, buf, *rest):
+        return self.matcher.scan_spec(nocaseref.fold(buf), *rest)
 
 
 class _DocCut:
@@ -555,6 +652,8 @@ class Model:
         self.flen = False
         self.reps = None
         self.cknob = 0            # the entry of CKNOBS the table was installed under
+        self.fold = False         # the case fold of the scans to come: the uploaded table's setting (pfac_table_set_case_fold)
+        self.pool = TABLES        # the tables and inputs a PLAN draws from (POOL for the fold family); the model itself asks nothing of it
         self.serial = 0           # caller's count buffers handed out
         self.slots = [_Slot() for _ in range(N_SLOTS)]
 
@@ -583,10 +682,30 @@ class Model:
 
     # -- tables -------------------------------------------------------------
     def _load_table(self, op, s):
+        """via: "host" = GpuMatcher.load_table, which turns the fold on behind the upload of a table built with
+        ignore_case; "device" = load_table_device of the image without host_table -- pfac_table_upload_device and nothing
+        else, which like every upload leaves the fold off."""
         self.tab, self.knob, self.cknob = op["tab"], op["knob"], op.get("cknob", 0)
         self.gen += 1
         self.flen, self.reps = False, None                      # lengths and replacements go with the old table
+        self.fold = bool(POOL[op["tab"]].get("nocase")) and op.get("via", "host") == "host"      # ... and so does the fold
         return Exp()
+
+    def _set_fold(self, op, s):
+        """pfac_table_set_case_fold(mode): modes 0 and 1 through GpuMatcher.set_case_fold, anything else through the raw
+        entry point."""
+        if self.tab is None:
+            return Exp(E_STATE)
+        if op["mode"] not in (0, 1):
+            return Exp(E_ARG)                                   # ... and the setting stays as it was
+        self.fold = bool(op["mode"])
+        return Exp()
+
+    def _get_fold(self, op, s):
+        if self.tab is None:
+            return Exp(E_STATE)
+        mode = int(self.fold)
+        return Exp(OK, lambda: mode)
 
     def _set_flen(self, op, s):
         if self.tab is None:
@@ -604,12 +723,13 @@ class Model:
     def _new_scan(self, s, op, pending, ext, over=False):
         s.seq += 1
         s.scan = dict(tab=self.tab, knob=self.knob, gen=self.gen, inp=op["inp"], no=op["no"], over=over, pending=pending, ext=ext, seq=s.seq,
-                      filt=())                                  # (filt: the filters applied to it, Expectations.applied, sorted)
+                      filt=(),                                  # (filt: the filters applied to it, Expectations.applied, sorted)
+                      fold=self.fold)                           # (the mode at the moment it was queued: nothing later changes it)
 
     @staticmethod
     def _sk(sc):
-        """The scan as the expectations key it: table, input, n_owned and filter state."""
-        return sc["tab"], sc["inp"], sc["no"], sc["filt"]
+        """The scan as the expectations take it: table, input, n_owned, filter state and fold."""
+        return sc["tab"], sc["inp"], sc["no"], sc["filt"], sc["fold"]
 
     def _count(self, sc):
         return self.x.count(*self._sk(sc))
@@ -654,7 +774,7 @@ class Model:
     def _scan_ext(self, op, s):
         if self.tab is None:
             return Exp(E_STATE)
-        n = self.x.count(self.tab, op["inp"], op["no"])
+        n = self.x.count(self.tab, op["inp"], op["no"], (), self.fold)
         fit = n + n // 4 + 65536                                # the slack the header asks for, and more
         assert op["cap"] >= fit or op["cap"] < n, "a capacity the contract does not decide"
         self._new_scan(s, op, False, True, over=op["cap"] < n)
@@ -694,7 +814,7 @@ class Model:
         if sc["over"]:
             return Exp(E_OVERFLOW)
         key = self._sk(sc)
-        return Exp(OK, lambda: self.x.checksum(*key[:3], op["base"], key[3]))
+        return Exp(OK, lambda: self.x.checksum(*key[:3], op["base"], key[3], key[4]))
 
     def _text(self, op, s):
         s.text = None
@@ -705,7 +825,7 @@ class Model:
             return Exp(E_STATE)
         if sc["over"]:
             return Exp(E_OVERFLOW)
-        s.text = (sc["tab"], sc["inp"], sc["no"], op["base"], sc["filt"])      # (the filter state at emission: a later filter leaves the text alone)
+        s.text = (sc["tab"], sc["inp"], sc["no"], op["base"], sc["filt"], sc["fold"])      # (the filter state at emission: a later filter leaves the text alone)
         key = s.text
         return Exp(OK, lambda: self.x.text(*key))
 
@@ -741,7 +861,7 @@ class Model:
         sc = s.scan
         if s.doc[:3] != (sc["tab"], sc["inp"], sc["no"]):
             return None
-        return (sc["tab"], sc["inp"], sc["no"], s.doc[3], sc["filt"])
+        return (sc["tab"], sc["inp"], sc["no"], s.doc[3], sc["filt"], sc["fold"])
 
     # -- the whole-word filter ------------------------------------------------
     def _filter(self, op, s):
@@ -811,7 +931,7 @@ class Model:
         sc = s.scan
         if op["entry"] > self.x.M(sc["tab"]):
             return Exp(E_ARG)
-        key = (sc["tab"], sc["inp"], sc["no"], op["entry"], sc["filt"])
+        key = (sc["tab"], sc["inp"], sc["no"], op["entry"], sc["filt"], sc["fold"])
         n = int(self.x.sel(*key)[0].size)
         if not op["own"] and op["small"]:
             return Exp(E_OVERFLOW if n > 0 else None, count=n)
@@ -819,6 +939,10 @@ class Model:
         if op["own"]:
             return Exp(OK, lambda: (n, self.x.sel(*key)[2]))
         return Exp(OK, lambda: (n, self.x.sel(*key)[2]) + self.x.sel(*key)[:2], tab=sc["tab"])
+
+    def _ds(self, key, rkey=None):
+        """Expectations.docsel of a per-document selection's key (table, input, n_owned, dkey, filter state, fold)."""
+        return self.x.docsel(*key[:5], rkey, key[5])
 
     def _select_docs(self, op, s):
         s.sel = None
@@ -828,13 +952,13 @@ class Model:
         key = self._doc_value_key(s)
         if key is None:
             return Exp(None)
-        n = int(self.x.docsel(*key)[0][-1])
+        n = int(self._ds(key)[0][-1])
         if not op["own"] and op["small"]:
             return Exp(E_OVERFLOW if n > 0 else None, count=n)
         s.sel = dict(kind="docs", key=key, own=op["own"], tab=s.scan["tab"], seq=s.scan["seq"], entry=0, doc_gen=s.doc_gen)
         if op["own"]:
             return Exp(OK, lambda: n)
-        return Exp(OK, lambda: (n,) + self.x.docsel(*key)[:3], tab=s.scan["tab"])
+        return Exp(OK, lambda: (n,) + self._ds(key)[:3], tab=s.scan["tab"])
 
     def _sel_fetch(self, op, s):
         if s.sel is None or not s.sel["own"]:
@@ -842,13 +966,13 @@ class Model:
         sel = s.sel
         if sel["kind"] == "whole":
             return Exp(OK, lambda: self.x.sel(*sel["key"])[:2], tab=sel["tab"])
-        return Exp(OK, lambda: self.x.docsel(*sel["key"])[1:3], tab=sel["tab"])
+        return Exp(OK, lambda: self._ds(sel["key"])[1:3], tab=sel["tab"])
 
     def _docsel_fetch(self, op, s):
         if s.sel is None or s.sel["kind"] != "docs" or not s.sel["own"]:
             return Exp(E_STATE)
         sel = s.sel
-        return Exp(OK, lambda: self.x.docsel(*sel["key"])[:3], tab=sel["tab"])
+        return Exp(OK, lambda: self._ds(sel["key"])[:3], tab=sel["tab"])
 
     # -- replace ------------------------------------------------------------
     def _rp_state(self, s, docs, reps=True):
@@ -862,9 +986,9 @@ class Model:
 
     def _rp_out(self, sel, rkey):
         if sel["kind"] == "whole":
-            t, i, no, entry, f = sel["key"]
-            return lambda: self.x.replace(t, i, no, entry, rkey, f)
-        return lambda: self.x.docsel(*sel["key"], rkey)[4]
+            t, i, no, entry, f, fold = sel["key"]
+            return lambda: self.x.replace(t, i, no, entry, rkey, f, fold)
+        return lambda: self._ds(sel["key"], rkey)[4]
 
     def _replace(self, op, s, docs=False):
         s.rp = s.rpd = None
@@ -878,7 +1002,7 @@ class Model:
             return Exp(E_OVERFLOW if n > 0 else None, count=n)
         s.rp = dict(out=out, own=op["own"])
         if docs:
-            off = lambda: self.x.docsel(*sel["key"], rkey)[3]                # noqa: E731
+            off = lambda: self._ds(sel["key"], rkey)[3]                      # noqa: E731
             s.rpd = dict(off=off, own=op["own"])
             return Exp(OK, (lambda: n) if op["own"] else (lambda: (n, out(), off())))
         return Exp(OK, (lambda: n) if op["own"] else (lambda: (n, out())))
@@ -1201,6 +1325,9 @@ WORD_KINDS = dict(KINDS, filter=9)      # the kinds of a plan with the whole-wor
 COUNT_KINDS = dict(WORD_KINDS, scan_ext=10, count=9, count_sel=5, cnt_fetch=4)      # ... and of one with the counts as well (plan(seed, counts=True))
 # ... and of one with the line path as well (plan(seed, lines=True))
 LINE_KINDS = dict(COUNT_KINDS, sync=2, split=14, doc_fetch=8, matching=10, context=10, ids_fetch=5, gather=14, ga_fetch=7, gaoff_fetch=5)
+# ... and of one with the case fold as well (plan(seed, fold=True))
+FOLD_KINDS = dict(LINE_KINDS, load_table=6, scan_bytes=12, set_fold=7, get_fold=4)
+FOLD_OPS = ("set_fold", "get_fold")
 LINE_OPS = ("split", "doc_fetch", "matching", "context", "ids_fetch", "gather", "ga_fetch", "gaoff_fetch")
 READERS = ("records", "packed", "checksum", "text", "scan_finish")          # what reads a finished scan, besides the passes
 
@@ -1217,10 +1344,17 @@ def _propose(rng, m, kinds=KINDS):
     op = dict(op=kind, slot=slot)
     if kind == "load_table":
         op.pop("slot")
-        op["tab"] = str(rng.choice(sorted(TABLES)))
-        op["knob"] = int(rng.choice(TABLES[op["tab"]]["knobs"]))
+        op["tab"] = str(rng.choice(sorted(m.pool)))
+        op["knob"] = int(rng.choice(POOL[op["tab"]]["knobs"]))
         if "count" in kinds:
             op["cknob"] = int(rng.integers(0, len(CKNOBS)))
+        if "set_fold" in kinds and rng.random() < 0.3:
+            op["via"] = "device"                                # (the image alone: pfac_table_upload_device, no host_table)
+    elif kind == "set_fold":
+        op.pop("slot")
+        op["mode"] = int(rng.choice([0, 1, 2, 0xFFFFFFFF], p=[.4, .4, .1, .1]))
+    elif kind == "get_fold":
+        op.pop("slot")
     elif kind == "set_flen":
         op.pop("slot")
     elif kind == "set_reps":
@@ -1228,11 +1362,13 @@ def _propose(rng, m, kinds=KINDS):
         op["rkey"] = str(rng.choice(REP_KEYS))
     elif kind in ("scan_bytes", "scan_start", "scan_ext"):
         tab = m.tab or "abc2"
-        op["inp"] = int(rng.integers(0, len(TABLES[tab]["inputs"])))
+        op["inp"] = int(rng.integers(0, len(m.pool[tab]["inputs"])))
+        if m.fold and "set_fold" in kinds:
+            op["inp"] = _fold_input(rng, m, op["inp"])
         n = x.input_size(tab, op["inp"])
         op["no"] = n if rng.random() < 0.6 else (n * 5) // 8
         if kind != "scan_bytes":
-            cnt = x.count(tab, op["inp"], op["no"])
+            cnt = x.count(tab, op["inp"], op["no"], (), m.fold)
             op["cap"] = cnt // 2 if (kind == "scan_ext" and cnt >= 64 and rng.random() < 0.3) else cnt + cnt // 4 + 65536
     elif kind == "records":
         total = m._count(sc) if sc else 5
@@ -1285,6 +1421,13 @@ def _propose(rng, m, kinds=KINDS):
         op["which"] = str(rng.choice(["input", "records", "both"]))
         op["k"] = s.grow + 1
     return op
+
+
+def _fold_input(rng, m, inp):
+    """The fold family, fold on: nine times in ten an input whose records the fold changes, where the table has one
+    (so that the family's folded scans are mostly worth their name)."""
+    good = [i for i in range(len(m.pool[m.tab]["inputs"])) if m.x.fold_differs(m.tab, i)]
+    return int(rng.choice(good)) if good and rng.random() < 0.9 else inp
 
 
 def _draw_split(rng, m, slot):
@@ -1420,7 +1563,7 @@ BETWEEN = ("split", "set_doc", "segment", "matching", "context", "gather", "scan
 LATE = {"split": ("doc_fetch",), "set_doc": ("doc_fetch",), "matching": ("ids_fetch",), "context": ("ids_fetch",), "gather": ("ga_fetch", "gaoff_fetch")}
 
 
-def _between_steps(rng, slot, what):
+def _between_steps(rng, slot, what, pool=TABLES):
     """One intervening call `what` on `slot`, meant to succeed."""
     if what == "split":
         return [_split_step(rng, slot)]
@@ -1437,8 +1580,8 @@ def _between_steps(rng, slot, what):
     if what == "scan":
         return [_scan_step(rng, slot, other=True)]
     if what == "upload":
-        tab = str(rng.choice(sorted(TABLES)))
-        return [dict(op="load_table", tab=tab, knob=int(rng.choice(TABLES[tab]["knobs"])), cknob=int(rng.integers(0, len(CKNOBS))))]
+        tab = str(rng.choice(sorted(pool)))
+        return [dict(op="load_table", tab=tab, knob=int(rng.choice(POOL[tab]["knobs"])), cknob=int(rng.integers(0, len(CKNOBS))))]
     if what == "grow":
         which = str(rng.choice(["records", "input", "both"]))
         return [lambda m: dict(op="reserve_grow", slot=slot, which=which, k=m.slots[slot].grow + 1)]
@@ -1519,9 +1662,9 @@ def _line_agenda(rng, m, chosen, st, agenda, turn):
         # a producer, one or two other calls, then the late fetch
         between = [b for b in BETWEEN if b not in {"split": ("split", "set_doc"), "set_doc": ("split", "set_doc"), "matching": ("matching", "context"),
                                                     "context": ("matching", "context"), "gather": ("gather",)}[kind]]
-        steps = _between_steps(rng, slot, between[_next(turn, "between " + kind) % len(between)])
+        steps = _between_steps(rng, slot, between[_next(turn, "between " + kind) % len(between)], m.pool)
         if rng.random() < 0.25:
-            steps += _between_steps(rng, slot, str(rng.choice([b for b in between if b not in ("grow", "upload")])))
+            steps += _between_steps(rng, slot, str(rng.choice([b for b in between if b not in ("grow", "upload")])), m.pool)
         if kind == "gather" and fetches == list(LATE[kind]) and rng.random() < 0.35:
             # a larger gather first: the slot-owned outputs regrow while nothing has fetched the first
             steps = [lambda m: _gather_op(slot, m, ids="twice", src="caller"), _late_fetch(rng, slot, "ga_fetch")] + steps
@@ -1603,15 +1746,17 @@ def _prepare(rng, kind, slot, docs=False):
     operation, or None when nothing is missing."""
     def table(m):
         if m.tab is None:
-            tab = str(rng.choice(sorted(TABLES)))
-            return dict(op="load_table", tab=tab, knob=int(rng.choice(TABLES[tab]["knobs"])))
+            tab = str(rng.choice(sorted(m.pool)))
+            return dict(op="load_table", tab=tab, knob=int(rng.choice(POOL[tab]["knobs"])))
 
     def scan(m):
         sc = m.slots[slot].scan
         if sc is not None and sc["pending"]:
             return dict(op="scan_finish", slot=slot)
         if sc is None or sc["over"] or sc["gen"] != m.gen:
-            inp = int(rng.integers(0, len(TABLES[m.tab]["inputs"])))
+            inp = int(rng.integers(0, len(m.pool[m.tab]["inputs"])))
+            if m.fold and m.pool is POOL:
+                inp = _fold_input(rng, m, inp)
             n = m.x.input_size(m.tab, inp)
             return dict(op="scan_bytes", slot=slot, inp=inp, no=n if rng.random() < 0.6 else (n * 5) // 8)
 
@@ -1668,9 +1813,11 @@ def _scan_step(rng, slot, other=False):
     def step(m):
         if m.tab is None:
             return None
-        n_in = len(TABLES[m.tab]["inputs"])
+        n_in = len(m.pool[m.tab]["inputs"])
         inp = int(rng.integers(0, n_in))
         sc = m.slots[slot].scan
+        if m.fold and m.pool is POOL:
+            inp = _fold_input(rng, m, inp)
         if other and sc is not None and sc["inp"] == inp:
             inp = (inp + 1) % n_in
         n = m.x.input_size(m.tab, inp)
@@ -1684,23 +1831,25 @@ def _ext_step(rng, slot, start=False):
     def step(m):
         if m.tab is None:
             return None
-        inp = int(rng.integers(0, len(TABLES[m.tab]["inputs"])))
+        inp = int(rng.integers(0, len(m.pool[m.tab]["inputs"])))
+        if m.fold and m.pool is POOL:
+            inp = _fold_input(rng, m, inp)
         no = m.x.input_size(m.tab, inp)
-        cnt = m.x.count(m.tab, inp, no)
+        cnt = m.x.count(m.tab, inp, no, (), m.fold)
         if start:
             return dict(op="scan_start", slot=slot, inp=inp, no=no, cap=cnt + cnt // 4 + 65536)
         return dict(op="scan_ext", slot=slot, inp=inp, no=no, cap=cnt // 2 if cnt >= 64 and rng.random() < 0.4 else cnt + cnt // 4 + 65536)
     return step
 
 
-def _between_count_and_fetch(rng, slot):
+def _between_count_and_fetch(rng, slot, pool=TABLES):
     """What happens between a count into the slot-owned buffer and the fetch of it: the counts outlive all of it."""
     what = str(rng.choice(["scan", "upload", "grow", "filter", "pass", "caller", "refused"]))
     if what == "scan":
         return [_scan_step(rng, slot, other=True)]
     if what == "upload":
-        tab = str(rng.choice(sorted(TABLES)))
-        return [dict(op="load_table", tab=tab, knob=int(rng.choice(TABLES[tab]["knobs"])), cknob=int(rng.integers(0, len(CKNOBS))))]
+        tab = str(rng.choice(sorted(pool)))
+        return [dict(op="load_table", tab=tab, knob=int(rng.choice(POOL[tab]["knobs"])), cknob=int(rng.integers(0, len(CKNOBS))))]
     if what == "grow":
         which = str(rng.choice(["records", "both"]))
         return [lambda m: dict(op="reserve_grow", slot=slot, which=which, k=m.slots[slot].grow + 1)]
@@ -1749,8 +1898,8 @@ def _count_agenda(rng, m, chosen, st, agenda):
         agenda = [_count_op(slot, dst=dst(), acc=bool(rng.random() < 0.4))] + agenda
     elif kind in ("select", "select_docs") and rng.random() < 0.12:
         # a selection made with an earlier table: PFAC_E_STATE
-        tab = str(rng.choice(sorted(TABLES)))
-        agenda = [dict(op="load_table", tab=tab, knob=int(rng.choice(TABLES[tab]["knobs"])), cknob=int(rng.integers(0, len(CKNOBS)))),
+        tab = str(rng.choice(sorted(m.pool)))
+        agenda = [dict(op="load_table", tab=tab, knob=int(rng.choice(POOL[tab]["knobs"])), cknob=int(rng.integers(0, len(CKNOBS)))),
                   _count_sel_op(slot, dst=dst(), sel="own" if chosen["own"] else "caller")] + agenda
     elif kind in ("select", "select_docs") and rng.random() < 0.7:
         # NULL for a selection in the caller's d_out, a buffer that holds none, a misaligned one: refused, then the count
@@ -1770,26 +1919,88 @@ def _count_agenda(rng, m, chosen, st, agenda):
             more += _prepare(rng, "select", slot)[1:] + [_pass_op("select", slot), _count_sel_op(slot, acc=True)]
         agenda = more + [fetch] + agenda
     elif kind in ("count", "count_sel") and chosen["dst"] == "own" and rng.random() < 0.7:
-        agenda = agenda + _between_count_and_fetch(rng, slot) + [fetch]
+        agenda = agenda + _between_count_and_fetch(rng, slot, m.pool) + [fetch]
     if kind == "count_sel" and rng.random() < 0.25:
         # a new scan or a filter makes the selection stale: the same count again is PFAC_E_STATE
         agenda = [_scan_step(rng, slot) if rng.random() < 0.5 else _filter_step(rng, slot), dict(chosen, acc=bool(rng.random() < 0.5))] + agenda
     return agenda
 
 
-def plan(seed, n_ops=None, words=False, counts=False, lines=False):
+def _fold_agenda(rng, m, chosen, st, agenda):
+    """The histories the fold family aims at (the rules of plan(seed, fold=True)); returns the new agenda."""
+    if st != OK:
+        return agenda
+    kind, slot = chosen["op"], chosen.get("slot", 0)
+    sc = m.slots[slot].scan
+    toggle = lambda m: dict(op="set_fold", mode=int(not m.fold))        # noqa: E731
+
+    def scan_unless_pending(slot):
+        step = _scan_step(rng, slot)
+        return lambda m: None if m.slots[slot].scan is not None and m.slots[slot].scan["pending"] else step(m)
+
+    if kind == "load_table":
+        if m.fold and rng.random() < 0.8:
+            # the upload of a nocase table through load_table left the fold on: a scan before anything toggles
+            agenda = [_scan_step(rng, int(rng.integers(0, N_SLOTS)))] + agenda
+        elif not m.fold and rng.random() < 0.8:
+            # a table whose fold is off after its upload (an old table, or an image through load_table_device): on, by hand
+            agenda = [dict(op="get_fold"), dict(op="set_fold", mode=1)] + agenda
+    elif kind == "scan_start" and rng.random() < 0.8:
+        agenda = [toggle] + agenda                              # the toggle comes while this scan is pending: it keeps its mode
+    elif kind == "set_fold" and rng.random() < 0.75:
+        # the new mode applies to the scans queued from now on, on EVERY slot
+        first = int(rng.integers(0, N_SLOTS))
+        agenda = [scan_unless_pending(first), scan_unless_pending(1 - first)] + agenda
+    elif kind in ("scan_bytes", "scan_finish", "scan_ext") and sc is not None and (sc["fold"] or POOL[sc["tab"]].get("nocase")) and not sc["over"] \
+            and not sc["pending"] and m._count(sc) >= 16 and rng.random() < 0.5:
+        # a folded scan with something to drop (or the exact scan of a table whose fold is otherwise on): the filter judges the ORIGINAL bytes (the word set `tab` of a nocase table
+        # is the lower-case letters only), then a selection and its replace, which copies them, or a count
+        flt = dict(op="filter", slot=slot, f=int(rng.choice([1, 2, 3])), heap="own")
+        whole = lambda m: dict(op="rp_fetch", slot=slot, first=0, n=int(m.slots[slot].rp["out"]().size)) if m.slots[slot].rp else None      # noqa: E731
+        picks = lambda m: _count_sel_op(slot, dst=dst, sel="own" if m.slots[slot].sel is None or m.slots[slot].sel["own"] else "caller")   # noqa: E731
+        dst, r = str(rng.choice(["own", "caller"])), rng.random()
+        if r < 0.2:
+            after = [_count_op(slot, dst=dst)]
+        elif r < 0.45:
+            after = _prepare(rng, "replace", slot) + [picks, _pass_op("replace", slot), whole]
+        elif r < 0.65:
+            # the matching lines with one line of context each side, and their bytes as they were written
+            after = _line_prepare(rng, slot, "matching") + [_matching_op(slot, context=(1, 1)), lambda m: _gather_op(slot, m), _late_fetch(rng, slot, "ga_fetch")]
+        else:
+            after = _prepare(rng, "replace_docs", slot) + [picks, _pass_op("replace_docs", slot), whole, dict(op="rpd_fetch", slot=slot)]
+        agenda = _prepare(rng, "filter", slot) + [flt] + after + agenda
+    elif kind in ("scan_bytes", "scan_finish") and sc is not None and sc["fold"] and not sc["pending"] and rng.random() < 0.25:
+        # the same table uploaded again: the fold is off, and the folded scan's records are fetched late
+        again = dict(op="load_table", tab=m.tab, knob=m.knob, cknob=m.cknob, **({"via": "device"} if rng.random() < 0.4 else {}))
+        agenda = [again, dict(op="get_fold"), lambda m: dict(op="records", slot=slot, first=0, n=m._count(m.slots[slot].scan)) if m.slots[slot].scan else None,
+                  dict(op="packed", slot=slot)] + agenda
+    elif kind == "count" and chosen["dst"] == "own" and not chosen["acc"] and rng.random() < 0.5:
+        # counts accumulated over an exact and a folded scan of one table generation
+        # (the first one counts the scan that is there, made in the other mode: the counts are the SCAN's, not the setting's)
+        agenda = [_Quiet(toggle), _count_op(slot, acc=True), _scan_step(rng, slot), _count_op(slot, acc=True), dict(op="cnt_fetch", slot=slot)] + agenda
+    return agenda
+
+
+def plan(seed, n_ops=None, words=False, counts=False, lines=False, fold=False):
     """The plan of `seed`: a list of operations (dicts).  Deterministic; the model decides what each one is worth.
     `words`: the second family of plans, in which the whole-word filter is one of the operations (the first family is
     what it was before the filter existed, seed for seed).  `counts`: the third family, the second one's operations and
     the per-pattern counts (count, count_sel, cnt_fetch; tables installed under an entry of CKNOBS).  `lines`: the
-    fourth family, the third one's operations and the line path (LINE_OPS), LINE_PLAN_OPS operations long."""
-    n_ops = n_ops or (LINE_PLAN_OPS if lines else PLAN_OPS)
-    rng = np.random.default_rng([seed, 0x53455353494F4E] + ([0x4C494E4553] if lines else [0x434F554E54] if counts else [0x574F5244] if words else []))
-    kinds = LINE_KINDS if lines else COUNT_KINDS if counts else WORD_KINDS if words else KINDS
+    fourth family, the third one's operations and the line path (LINE_OPS), LINE_PLAN_OPS operations long.  `fold`:
+    the fifth family, the fourth one's operations and the case fold (set_fold, get_fold, the upload of an image through
+    load_table_device), drawn from POOL -- the nine old tables, each with one more input, and the four nocase tables
+    of FOLD_TABLES -- and FOLD_PLAN_OPS operations long."""
+    n_ops = n_ops or (FOLD_PLAN_OPS if fold else LINE_PLAN_OPS if lines else PLAN_OPS)
+    rng = np.random.default_rng([seed, 0x53455353494F4E] + ([0x464F4C44] if fold else [0x4C494E4553] if lines else [0x434F554E54] if counts else
+                                                             [0x574F5244] if words else []))
+    kinds = FOLD_KINDS if fold else LINE_KINDS if lines else COUNT_KINDS if counts else WORD_KINDS if words else KINDS
+    lines = lines or fold                                       # (the fold family works the line path like the line family)
     counts = counts or lines                                    # (the line family counts like the count family)
     words = words or counts                                     # (the count family filters like the word family)
     turn = {"seed": seed}                                       # (the line family's walks start elsewhere in every plan)
     m = Model()
+    if fold:
+        m.pool = POOL
     ops, agenda = [], []
     if counts:                                                  # (a fetch before any count: PFAC_E_STATE)
         agenda = [dict(op="cnt_fetch", slot=int(rng.integers(0, N_SLOTS)))] if rng.random() < 0.3 else []
@@ -1798,9 +2009,11 @@ def plan(seed, n_ops=None, words=False, counts=False, lines=False):
         agenda.append(dict(op=early, slot=int(rng.integers(0, N_SLOTS)), **({"first": 0, "n": 1} if early == "doc_fetch" else {})))
     if lines and rng.random() < 0.5:                            # (half of the line plans begin with slot 1 on slot 0's stream)
         agenda.append(dict(op="set_stream", slot=1, share=True))
+    if fold and rng.random() < 0.4:                             # (the setting before any upload: PFAC_E_STATE)
+        agenda.append(dict(op="set_fold", mode=1) if rng.random() < 0.5 else dict(op="get_fold"))
     while len(ops) < n_ops:
         want_err = rng.random() < (1 / 16 if words else 1 / 8)   # (words: the filter between a selection and its replace adds errors of its own)
-        chosen, quiet = None, False
+        chosen, quiet, proposed = None, False, False
         while agenda and chosen is None and not want_err:      # what the session set out to do comes first
             cand = agenda.pop(0)
             quiet = isinstance(cand, _Quiet)
@@ -1818,7 +2031,7 @@ def plan(seed, n_ops=None, words=False, counts=False, lines=False):
             if st is None:
                 continue
             if (st != OK) == want_err:
-                chosen = cand
+                chosen, proposed = cand, True
             elif st != OK and not agenda and (cand["op"] in PASSES or cand["op"] in PRODUCER_OF):
                 # a pass (or the fetch of one) with nothing to work on: do what is missing first, then the pass
                 if cand["op"] in PASSES:
@@ -1836,6 +2049,10 @@ def plan(seed, n_ops=None, words=False, counts=False, lines=False):
                 agenda = _line_prepare(rng, cand["slot"], upto) + made + ([] if cand["op"] == "ga_fetch" else [cand])
         if chosen is None:
             continue
+        if fold and chosen["op"] == "load_table" and proposed:
+            # the uploads a fold plan draws walk the pool and each table's knobs, so that the suite's plans fold them all
+            tab = sorted(POOL)[_next(turn, "table") % len(POOL)]
+            chosen = dict(chosen, tab=tab, knob=POOL[tab]["knobs"][_next(turn, "knob of " + tab) % len(POOL[tab]["knobs"])])
         if counts and chosen["op"] == "load_table" and "cknob" not in chosen:
             chosen = dict(chosen, cknob=int(rng.integers(0, len(CKNOBS))))
         st = m.apply(chosen).status
@@ -1873,8 +2090,8 @@ def plan(seed, n_ops=None, words=False, counts=False, lines=False):
         # histories the header has a sentence for: a replace of a selection made before a table upload; records of a
         # scan that overflowed its heap; ...
         if st == OK and chosen["op"] in ("select", "select_docs") and rng.random() < 0.15:
-            tab = str(rng.choice(sorted(TABLES)))
-            agenda = [dict(op="load_table", tab=tab, knob=int(rng.choice(TABLES[tab]["knobs"]))), dict(op="set_flen"),
+            tab = str(rng.choice(sorted(m.pool)))
+            agenda = [dict(op="load_table", tab=tab, knob=int(rng.choice(POOL[tab]["knobs"]))), dict(op="set_flen"),
                       dict(op="set_reps", rkey=str(rng.choice(REP_KEYS))), _pass_op("replace", chosen["slot"])] + agenda
         if st == OK and chosen["op"] == "select_docs" and rng.random() < 0.15:     # ... a per-document replace after new offsets
             sc = m.slots[chosen["slot"]].scan
@@ -1889,14 +2106,16 @@ def plan(seed, n_ops=None, words=False, counts=False, lines=False):
                       dict(op="scan_finish", slot=chosen["slot"])] + agenda
         if counts and (not lines or rng.random() < 0.25):           # (the line family has an agenda of its own to get through)
             agenda = _count_agenda(rng, m, chosen, st, agenda)
-        if lines and not quiet:
+        if lines and not quiet and (not fold or rng.random() < 0.5):
             agenda = _line_agenda(rng, m, chosen, st, agenda, turn)
+        if fold and not (quiet and chosen["op"] == "set_fold"):
+            agenda = _fold_agenda(rng, m, chosen, st, agenda)
     return ops
 
 
-def shrink(seed, k, n_ops=None, words=False, counts=False, lines=False):
+def shrink(seed, k, n_ops=None, words=False, counts=False, lines=False, fold=False):
     """The plan of `seed` with operation k onwards removed: cut a failing history down by hand."""
-    return plan(seed, n_ops, words, counts, lines)[:k]
+    return plan(seed, n_ops, words, counts, lines, fold)[:k]
 
 
 # ---------------------------------------------------------------------------
@@ -2059,7 +2278,8 @@ class Executor:
         self.bufs = [_SlotBufs() for _ in range(N_SLOTS)]
         self.stats = dict(ops=0, errors=0, compared=0, filters=0, counts=0, widths=set(), staging=set(), variants=set(), statuses=set(),
                           regimes=set(),                        # (regimes: (entry of CKNOBS, "direct" / "cache") of every count that ran)
-                          splits=0, matchings=0, gathers=0, ids=0)   # (the line path: calls that succeeded, document ids compared)
+                          splits=0, matchings=0, gathers=0, ids=0,   # (the line path: calls that succeeded, document ids compared)
+                          folded=0, toggles=0, modes=0)         # (the fold: scans queued with it on, set_fold calls that succeeded, modes compared)
         self.inputs = {}                                        # (tab, inp) -> a caller's device copy of that input
         self.ids_direct = getattr(g, "states_are_ids", False)
 
@@ -2070,6 +2290,9 @@ class Executor:
     def recs(self, tab, rec):
         self.stats["compared"] += int(rec.size)
         return rec["pos"].astype(np.int64), self.ids(tab, rec["state"])
+
+    def note_fold(self, slot):
+        self.stats["folded"] += bool(self.m.slots[slot].scan["fold"])
 
     def note_scan(self, slot):
         self.stats["widths"].add(int(self.g.scan_format(slot)[0]))
@@ -2106,12 +2329,32 @@ class Executor:
         os.environ.update(KNOBS[op["knob"]])                    # knobs are read when a table is installed
         os.environ.update(CKNOBS[op.get("cknob", 0)])
         try:
-            self.g.load_table(self.x.table(op["tab"]))
+            table = self.x.table(op["tab"])
+            if op.get("via", "host") == "device":               # the image alone, as after a broadcast: no host_table, so no fold
+                blob = table.blob()
+                self.g.load_table_device(_upload(self.g, blob), int(blob.size))
+                self.g.table = table                            # (the wrapper's lengths and replacements come from the host table)
+            else:
+                self.g.load_table(table)
         finally:
             for k, v in saved.items():
                 os.environ.pop(k, None)
                 if v is not None:
                     os.environ[k] = v
+
+    def do_set_fold(self, op, exp, before):
+        g = self.g
+        if op["mode"] in (0, 1):
+            g.set_case_fold(bool(op["mode"]))
+        elif hasattr(g, "raw_set_case_fold"):
+            g.raw_set_case_fold(op["mode"])
+        else:                                                   # (a mode the wrapper would not pass)
+            g._check(g._L.pfac_table_set_case_fold(g._ctx, op["mode"]))
+        self.stats["toggles"] += 1
+
+    def do_get_fold(self, op, exp, before):
+        self.stats["modes"] += 1
+        return int(self.g.case_fold)
 
     def do_set_flen(self, op, exp, before):
         t = self.m.tab
@@ -2134,6 +2377,7 @@ class Executor:
         self._own_scan(op["slot"])
         rec = self.g.scan_bytes(self._data(op), op["no"], slot=op["slot"])
         self.note_scan(op["slot"])
+        self.note_fold(op["slot"])
         return self.recs(exp.tab, rec)
 
     def do_scan_start(self, op, exp, before):
@@ -2143,6 +2387,7 @@ class Executor:
         if data.size:
             g.h2d(data, slot)
         g.scan_async(op["no"], data.size, slot=slot)
+        self.note_fold(slot)
 
     def do_scan_finish(self, op, exp, before):
         n, over = self.g.scan_finish(op["slot"], allow_overflow=True)
@@ -2156,6 +2401,7 @@ class Executor:
         self.bufs[slot].inp, self.bufs[slot].rec = d_in, d_rec
         n, over = g.scan_finish(slot, allow_overflow=True)
         self.note_scan(slot)
+        self.note_fold(slot)
         return int(n), bool(over)
 
     def do_records(self, op, exp, before):
@@ -2169,7 +2415,7 @@ class Executor:
 
     def do_checksum(self, op, exp, before):
         sc = before["scan"]
-        n = self.x.count(sc["tab"], sc["inp"], sc["no"], sc["filt"]) if sc else 1
+        n = self.x.count(sc["tab"], sc["inp"], sc["no"], sc["filt"], sc["fold"]) if sc else 1
         return int(self.g.checksum(n, op["base"], op["slot"], d_records=self.bufs[op["slot"]].rec))
 
     def do_text(self, op, exp, before):
@@ -2290,7 +2536,7 @@ class Executor:
             return 0, 1
         if sel["kind"] == "whole":
             return int(self.x.sel(*sel["key"])[0].size), 1
-        return int(self.x.docsel(*sel["key"])[0][-1]), int(self.x.offsets(*sel["key"][:4]).size - 1)
+        return int(self.m._ds(sel["key"])[0][-1]), int(self.x.offsets(*sel["key"][:4]).size - 1)
 
     def do_sel_fetch(self, op, exp, before):
         return self.recs(exp.tab, self.g.selection_to_host(self._sel_n(op["slot"])[0], op["slot"]))

@@ -3,7 +3,8 @@ kernel knobs, many sizes, two slots, passes in any order, results fetched late, 
 result compared bit for bit with what include/pfac.h promises for that history.  The random plans are the suite's seeds;
 the named sessions are histories random plans reach rarely; half of the plans and the sessions at the end of this file
 have the whole-word filter among their calls, a third of the plans and a group of sessions the per-pattern counts, and a
-fourth family of plans and the last group of sessions the line path (split, matching documents, context lines, gather).
+fourth family of plans and a group of sessions the line path (split, matching documents, context lines, gather), and a
+fifth family and the last group of sessions the case fold (pfac_table_set_case_fold) as a setting with a life of its own.
 Run with -m gpu on an MI355X.  Expectations come from the
 CPU oracle, llref, replref, docref, docreplref, splitref, gatherref and the pattern files, never from the device.  No session aims at the
 scan's wait protocol: they provoke the errors the header documents, nothing else."""
@@ -14,6 +15,7 @@ import numpy as np
 import pytest
 
 import session as S
+from passfuzz import knob_label
 from phfpfac_amd import GpuMatcher
 from phfpfac_amd.matcher import splitmix64_bytes, tiled_bytes
 
@@ -25,7 +27,7 @@ TILE_BYTES = S.TILE
 
 def k(tab, **knobs):
     i = S.KNOBS.index(knobs)
-    assert i in S.TABLES[tab]["knobs"]
+    assert i in S.POOL[tab]["knobs"]
     return i
 
 
@@ -92,21 +94,21 @@ def run(ops, want=None):
 
 
 @pytest.mark.parametrize("seed,family", [(s, "") for s in S.SEEDS] + [(s, "words") for s in S.WORD_SEEDS] + [(s, "counts") for s in S.COUNT_SEEDS]
-                         + [(s, "lines") for s in S.LINE_SEEDS],
+                         + [(s, "lines") for s in S.LINE_SEEDS] + [(s, "fold") for s in S.FOLD_SEEDS],
                          ids=[str(s) for s in S.SEEDS] + [f"words-{s}" for s in S.WORD_SEEDS] + [f"counts-{s}" for s in S.COUNT_SEEDS]
-                         + [f"lines-{s}" for s in S.LINE_SEEDS])
+                         + [f"lines-{s}" for s in S.LINE_SEEDS] + [f"fold-{s}" for s in S.FOLD_SEEDS])
 def test_session(seed, family):
     """One random plan on one context; `family`: "words" = a plan that filters whole words, "counts" = one that also
     counts matches per pattern, "lines" = one that also splits at a delimiter, lists the matching documents and gathers
-    their bytes."""
-    ops = S.plan(seed, words=family == "words", counts=family == "counts", lines=family == "lines")
+    their bytes, "fold" = one that also toggles the case fold, over the larger pool with the nocase tables."""
+    ops = S.plan(seed, words=family == "words", counts=family == "counts", lines=family == "lines", fold=family == "fold")
     tag = f" ({family})" if family else ""
     with GpuMatcher(0, S.N_SLOTS) as g:
         st = S.run(g, ops, S.Model(), seed=f"{seed}{tag}" if family else seed)
     print(f"session {seed}{tag}: {st['ops']} operations ({st['errors']} documented errors), {st['compared']} records and bytes compared, "
           f"record widths {sorted(st['widths'])}, staging {sorted(st['staging'])}, {sorted(st['variants'])}, {st['counts']} counts under "
           f"{sorted(st['regimes'])}, {st['splits']} splits, {st['matchings']} matching calls, {st['gathers']} gathers, {st['ids']} document ids "
-          f"and offsets compared")
+          f"and offsets compared, {st['folded']} folded scans, {st['toggles']} toggles and {st['modes']} modes compared")
 
 
 def test_large_dense_then_tiny_sparse_then_every_pass():
@@ -815,3 +817,199 @@ def test_a_chunked_reader_carries_the_tail_over():
     np.testing.assert_array_equal(np.concatenate(offsets), want_off)
     want, _ = gather_ref(data, want_off, np.arange(want_docs, dtype=np.uint64))
     np.testing.assert_array_equal(np.concatenate(pieces), want)
+
+
+# ---------------------------------------------------------------------------
+# the case fold as a setting on a long-lived context: it belongs to the uploaded table, is fixed for a scan when the scan
+# is queued, and no pass behind a folded scan sees a folded byte
+
+def fold(mode):
+    return dict(op="set_fold", mode=mode)
+
+
+GET = dict(op="get_fold")
+
+
+def filled(ops):
+    """The operations with every records / rp_fetch / ga_fetch that has no window yet asking for all there is at that point."""
+    m, out = S.Model(), []
+    for op in ops:
+        s = m.slots[op.get("slot", 0)]
+        if "n" not in op and op["op"] == "records":
+            op = dict(op, first=0, n=m._count(s.scan))
+        if "n" not in op and op["op"] == "rp_fetch":
+            op = dict(op, first=0, n=int(s.rp["out"]().size))
+        if "n" not in op and op["op"] == "ga_fetch":
+            op = dict(op, first=0, n=int(X.gather(*s.ga[0])[0].size))
+        m.apply(op)
+        out.append(op)
+    return out
+
+
+def ok(ops):
+    return run(ops, want=[S.OK] * len(ops))
+
+
+def test_staging_layout_flips_both_ways_folded():
+    """test_staging_layout_flips_both_ways_with_exact_records with the fold on throughout: wordsi with no knob pinned, its
+    dense input (a record every other byte once folded) and its matchless one in turn -- the twin of whichever kernel
+    the staging mode picks is the one that runs.  Then the old-table case: negcc's record-heavy input under the fold, with
+    no knob pinned and in dense mode."""
+    t = "wordsi"
+    seen, folded = [], 0
+    with GpuMatcher(0, S.N_SLOTS) as g:
+        ex = S.Executor(g, S.Model())
+        for op in load(t):
+            ex.step(op)
+        seen.append(g.info()["staging_buffers"])
+        for rnd, inp in enumerate((0, 1, 0, 0, 1, 1, 0, 1)):
+            ex.step(GET)
+            ex.step(scan(t, inp, slot=rnd % 2))
+            assert ex.m.slots[rnd % 2].scan["fold"]
+            seen.append(g.info()["staging_buffers"])
+            ex.step(dict(op="records", slot=rnd % 2, first=0, n=X.count(t, inp, 300_007, (), True)))
+            ex.step(fetch("checksum", slot=rnd % 2, base=0))
+        folded = ex.stats["folded"]
+        for knobs in ({}, dict(PFAC_DENSE="1")):
+            for op in filled(load("negcc", **knobs) + [fold(1), scan("negcc", 1), dict(op="records", slot=0), fetch("packed"), fetch("text", base=0)]):
+                ex.step(op)
+    to_dense = sum(a != 1 and b == 1 for a, b in zip(seen, seen[1:]))
+    from_dense = sum(a == 1 and b != 1 for a, b in zip(seen, seen[1:]))
+    assert to_dense >= 1 and from_dense >= 1 and folded == 8, (seen, folded)
+    assert X.count("negcc", 1, 70_001, (), True) > 70_001 and X.fold_differs("negcc", 1)
+
+
+def test_record_width_2_then_8_then_4_on_one_heap_fold_on():
+    """test_record_width_2_then_8_then_4_on_one_heap with every scan folded: wordsi (two-byte records, the fold on from
+    its upload), wide8 and mid4 (eight and four bytes, the fold set by hand after each upload)."""
+    E = S.E_STATE
+    ops = load("wordsi") + [GET, scan("wordsi", 0), dict(op="records", slot=0), pss("select")]
+    ops += load("wide8", PFAC_WIDE="1") + [GET, fold(1), dict(op="records", slot=0, first=5, n=1000), fetch("packed"), fetch("checksum", base=0),
+                                            fetch("text", base=0), pss("select"), pss("replace"), fetch("sel_fetch"),
+                                            scan("wide8", 3), dict(op="records", slot=0), fetch("packed"), fetch("checksum", base=0), pss("select")]
+    ops += load("mid4") + [fold(1), dict(op="records", slot=0), pss("segment"), scan("mid4", 1), dict(op="records", slot=0), fetch("packed"), pss("select"),
+                           fetch("sel_fetch"), pss("replace"), dict(op="rp_fetch", slot=0)]
+    st = run(filled(ops), want=[0] * 3 + [0, 0, 0, 0] + [0] * 3 + [0, 0, 0, 0, E, E, E, E, E, 0, 0, E, 0, 0] + [0] * 3 + [0, 0, E, 0, 0, 0, 0, 0, 0, 0])
+    assert st["widths"] == {2, 4, 8} and st["folded"] == 3
+    assert X.fold_differs("wide8", 3) and X.fold_differs("mid4", 1)
+
+
+@pytest.mark.parametrize("share", [True, False], ids=["shared-stream", "own-streams"])
+def test_toggle_between_two_slots_queued_scans(share):
+    """Fold on, scan_start on slot 0; fold off, scan_start on slot 1; fold on again; then both finishes: each scan keeps the
+    mode it was queued with, and the filter (which judges the bytes as written), the selection, the replace and the count
+    behind each are those of ITS scan."""
+    t, inp = "wordsi", 2
+    no = X.input_size(t, inp)
+    cf, ce = X.count(t, inp, no, (), True), X.count(t, inp, no)
+    assert cf > ce > 0
+    start = lambda slot, c: dict(op="scan_start", slot=slot, inp=inp, no=no, cap=c + c // 4 + 65536)      # noqa: E731
+    ops = [dict(op="set_stream", slot=1, share=True)] if share else []
+    ops += load(t, rkey="redact") + [GET, start(0, cf), fold(0), start(1, ce), fold(1), GET, dict(op="scan_finish", slot=0), dict(op="scan_finish", slot=1)]
+    for slot in (0, 1):
+        ops += [dict(op="records", slot=slot), flt(1, slot=slot), dict(op="records", slot=slot), pss("select", slot=slot), fetch("sel_fetch", slot=slot),
+                pss("replace", slot=slot), dict(op="rp_fetch", slot=slot), cnt(slot=slot), cnt_fetch(slot=slot), cnt(slot=slot, dst="caller")]
+    ops = filled(ops)
+    probe = S.Model()
+    for op in ops:
+        probe.apply(op)
+    assert probe.slots[0].scan["fold"] and not probe.slots[1].scan["fold"] and probe.fold
+    f1 = fkey(t, (1, ""))
+    assert 0 < X.count(t, inp, no, f1) < ce and X.count(t, inp, no, f1) < X.count(t, inp, no, f1, True) < cf
+    st = ok(ops)
+    assert st["folded"] == 1 and st["toggles"] == 2
+
+
+def test_an_upload_resets_the_fold_and_the_folded_records_survive():
+    """A folded scan, then the same table's image uploaded again by pfac_table_upload_device alone: the fold reads off,
+    the next scan is exact; the first scan's records are still the folded ones (records, packed), while its text and a
+    selection from it need the table it was scanned with: PFAC_E_STATE."""
+    t, E = "wordsi", S.E_STATE
+    again = dict(op="load_table", tab=t, knob=k(t), via="device")
+    ops = load(t) + [GET, scan(t, 0, slot=0), again, GET, dict(op="set_flen"), scan(t, 0, slot=1), dict(op="records", slot=1), dict(op="records", slot=0),
+                     fetch("packed", slot=0), fetch("text", slot=0, base=0), pss("select", slot=0), fetch("checksum", slot=1, base=0)]
+    st = run(filled(ops), want=[0] * 3 + [0, 0, 0, 0, 0, 0, 0, 0, 0, E, E, 0])
+    assert st["folded"] == 1 and X.count(t, 0, 300_007, (), True) > X.count(t, 0, 300_007)
+
+
+def test_a_word_set_that_separates_the_cases_sees_the_input_as_written():
+    """wordsi, a folded scan, the filter with the lower-case letters as the word set: an upper-case neighbour is no word
+    byte, so the kept set is the one wordref gives on the ORIGINAL bytes and not the one on folded bytes; the selection's
+    replace and the per-document one copy the original bytes around their picks."""
+    import wordref
+    t, inp = "wordsi", 2
+    no = X.input_size(t, inp)
+    f1 = fkey(t, (1, ""))
+    pos, ids, lens = X.scan(t, inp, no, (), True)
+    bits = np.zeros(4, dtype=np.uint64)
+    for b in S.WORD_TAB[t]:
+        bits[b >> 6] |= np.uint64(1 << (b & 63))
+    on_folded = wordref.filter_words(S.nocaseref.fold(X.input(t, inp)), pos, lens, bits, wordref.BOTH, -1, -1, None)
+    kept = X.scan(t, inp, no, f1, True)[0]
+    assert 0 < int(on_folded.sum()) < kept.size < pos.size, "the word set does not separate the cases on this input"
+    out = X.replace(t, inp, no, 0, "redact", f1, True)
+    spos, sids, _ = X.sel(t, inp, no, 0, f1, True)
+    outside = np.ones(no, dtype=bool)
+    for p, n in zip(spos.tolist(), X.tinfo(t)["ll"][sids].tolist()):
+        outside[p:p + n] = False
+    assert out.size == no and np.array_equal(out[outside], X.input(t, inp)[:no][outside]) and (out[~outside] == ord("#")).all()
+    assert (X.input(t, inp)[:no][outside] != S.nocaseref.fold(X.input(t, inp)[:no])[outside]).any()
+    ops = load(t, rkey="redact") + [scan(t, inp), flt(1), dict(op="records", slot=0), pss("select"), fetch("sel_fetch"), pss("replace"),
+                                    dict(op="rp_fetch", slot=0), doc(t, inp, "d0"), pss("select_docs"), fetch("docsel_fetch"), pss("replace_docs"),
+                                    dict(op="rp_fetch", slot=0), fetch("rpd_fetch"), pss("replace_docs", own=False), pss("replace", own=False)]
+    ok(filled(ops))
+
+
+def test_folded_scan_of_the_callers_guarded_buffers():
+    """A folded scan reads the caller's input between guard bands, odd-aligned by 16 bytes into its tensor, and writes the
+    caller's heap at exactly the capacity the hint names: the records are the folded ones, and neither the guard bands
+    nor one byte of the input have changed afterwards (the fold happens on the way into the kernel's on-chip copy)."""
+    import torch
+    from heapguard import GuardedBuffer
+    t, inp = "wordsi", 2
+    data = X.input(t, inp)
+    no = data.size
+    pos, ids, _ = X.scan(t, inp, no, (), True)
+    with GpuMatcher(0, 1) as g:
+        g.load_table(X.table(t))
+        assert g.case_fold
+        d_in = GuardedBuffer(no, front=4096 + 16, fill=0xA5)
+        d_in.payload().copy_(torch.from_numpy(data))
+        torch.cuda.synchronize()
+        roomy = GuardedBuffer(4 << 20)                          # (a roomy heap first, for the hint)
+        g.scan_async(no, no, d_input=d_in.ptr, d_records=roomy.ptr, capacity=(4 << 20) // 8, slot=0)
+        n, over = g.scan_finish(0, allow_overflow=True)
+        cap = int(g.capacity_hint(0))
+        heap = GuardedBuffer(cap * g.scan_format(0)[0], fill=0x3C)
+        g.scan_async(no, no, d_input=d_in.ptr, d_records=heap.ptr, capacity=cap, slot=0)
+        n, over = g.scan_finish(0, allow_overflow=True)
+        assert (n, over) == (pos.size, False)
+        rec = g.records_to_host(n, 0, d_records=heap.ptr)
+        g.sync(0)
+        heap.check(what="the caller's heap of a folded scan")
+        d_in.check(what="the caller's input of a folded scan")
+        np.testing.assert_array_equal(d_in.host(), data)
+    np.testing.assert_array_equal(rec["pos"].astype(np.int64), pos)
+    np.testing.assert_array_equal(np.asarray(X.table(t).idmap)[rec["state"]], ids)
+
+
+@pytest.mark.parametrize("t,knob", [(t, kn) for t in ("cclassi", "root1i") for kn in S.FOLD_TABLES[t]["knobs"]],
+                         ids=[f"{t}-{knob_label(S.KNOBS[kn])}" for t in ("cclassi", "root1i") for kn in S.FOLD_TABLES[t]["knobs"]])
+def test_class_and_one_edge_root_tables_through_the_fold(t, knob):
+    """from_charclass(..., ignore_case=True) and the root with ONE edge, folded on a GPU under each of their knobs: the
+    scan, its counts by pattern id, the matching lines with one line of context each side, and their bytes -- in the case
+    they were written in."""
+    inp = 0
+    no = X.input_size(t, inp)
+    assert X.fold_differs(t, inp)
+    ops = [dict(op="load_table", tab=t, knob=knob, cknob=0), dict(op="set_flen"), GET, scan(t, inp), dict(op="records", slot=0), cnt(), cnt_fetch(),
+           cnt(dst="caller"), spl(t, inp, which=0), pss("segment"), mat(), fetch("ids_fetch"), mat(ctx=(1, 1)), fetch("ids_fetch"), gat(t, inp),
+           dict(op="ga_fetch", slot=0), fetch("gaoff_fetch")]
+    ops = filled(ops)
+    probe = S.Model()
+    for op in ops:
+        probe.apply(op)
+    out = X.gather(*probe.slots[0].ga[0])[0]
+    assert out.size and (out != S.nocaseref.fold(out)).any(), "the gathered lines hold no upper-case letter"
+    st = ok(ops)
+    assert st["folded"] == 1 and st["gathers"] == 1

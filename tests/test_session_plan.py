@@ -8,7 +8,10 @@ S.WORD_SEEDS, in which the filter is an operation like any other, pinned likewis
 of S.COUNT_SEEDS, which add the per-pattern counts (count, count_sel, cnt_fetch) under the count knobs of S.CKNOBS,
 pinned likewise since the line path joined; and those of S.LINE_SEEDS, which add the delimiter split, the matching
 documents with and without context lines and the gather of their bytes (S.LINE_OPS), and have their own reach test,
-their own defects (LINE_DEFECTS) and a digest of their own."""
+their own defects (LINE_DEFECTS) and a digest of their own; and those of S.FOLD_SEEDS, which add the case fold as a
+setting with a life of its own (set_fold, get_fold, uploads that set or reset it) over the larger pool S.POOL, with
+their own reach test, the cap that three quarters of their folded scans differ from the exact ones, FOLD_DEFECTS and a
+digest."""
 import collections
 import copy
 import hashlib
@@ -20,6 +23,7 @@ import sys
 import numpy as np
 import pytest
 
+import nocaseref
 import session as S
 from llref import greedy
 from orc import match_checksum
@@ -89,6 +93,13 @@ LINE_DEFECTS = ("failed_split_clears_the_offsets", "split_keeps_the_offsets_gene
                 "gather_reads_the_input_of_the_last_scan")
 
 
+# ... and those of the case fold, which only the plans of S.FOLD_SEEDS can meet
+FOLD_DEFECTS = ("fold_survives_upload", "fold_survives_device_upload", "fold_is_per_slot", "toggle_reaches_pending_scan", "ext_scan_ignores_fold",
+                "bad_mode_clears_fold", "filter_judges_folded_bytes", "replace_copies_folded_bytes", "doc_replace_copies_folded_bytes",
+                "gather_copies_folded_bytes", "counts_follow_current_mode", "dense_staging_ignores_fold")
+DENSE_PER_TILE = 1024                     # the stand-in's staging mode: dense after a scan of >= 64 tiles with more records per tile
+
+
 class CpuDevice:
     """GpuMatcher's surface on the CPU: every result recomputed from the oracle's records, outputs kept in dicts.  Works
     in pattern ids (``states_are_ids``).  `defects`: names from DEFECTS to switch on."""
@@ -105,6 +116,10 @@ class CpuDevice:
         self.reps = None
         self.slots = [_CpuSlot() for _ in range(S.N_SLOTS)]
         self.hit = False
+        self.table = None
+        self.fold = False                   # pfac_table_set_case_fold: the uploaded table's setting, read when a scan is queued
+        self.fold_slot1 = False             # (defect fold_is_per_slot: what slot 1 goes by)
+        self.dense = self.dense_pinned = False
 
     def _defect(self, name):
         if name in self.defects:
@@ -133,7 +148,25 @@ class CpuDevice:
 
     # -- tables -------------------------------------------------------------
     def load_table(self, table):
-        self.tab = next(t for t in S.TABLES if self.x.table(t) is table)
+        self._install(next(t for t in S.POOL if self.x.table(t) is table), "fold_survives_upload")
+        if table.ignore_case:               # (GpuMatcher.load_table: the upload leaves the fold off, the wrapper turns it on)
+            self.set_case_fold(True)
+
+    def load_table_device(self, d_blob, n_words, stream=0, host_table=None):
+        blob = np.asarray(d_blob.src).ravel()
+        tab = next(t for t in S.POOL if ("table", t) in self.x._c and self.x.table(t).blob().size == blob.size and np.array_equal(self.x.table(t).blob(), blob))
+        self._install(tab, "fold_survives_device_upload")
+        if host_table is not None and host_table.ignore_case:
+            self.set_case_fold(True)
+
+    def _install(self, tab, fold_defect):
+        table = self.x.table(tab)
+        self.tab = tab
+        if not (self.fold and self._defect(fold_defect)):
+            self.fold = False               # every upload resets the fold
+        self.fold_slot1 = self.fold
+        self.dense_pinned = "PFAC_DENSE" in os.environ
+        self.dense = os.environ.get("PFAC_DENSE") == "1"
         knobs = {k: os.environ[k] for d in KNOBS for k in d if k in os.environ}
         self.width = record_width(int(table.num_final), knobs)
         self.gen += 1
@@ -145,7 +178,28 @@ class CpuDevice:
                 s.ga = None
 
     def info(self):
-        return {"variant": "cpu", "staging_buffers": 0, "staging_records": 0}
+        return {"variant": "cpu", "staging_buffers": 1 if self.dense else 2, "staging_records": 0}
+
+    def raw_set_case_fold(self, mode):
+        if self.tab is None:
+            raise _err(S.E_STATE, "pfac_table_set_case_fold before a table upload")
+        if mode not in (0, 1):
+            if self.fold and self._defect("bad_mode_clears_fold"):
+                self.fold = self.fold_slot1 = False
+            raise _err(S.E_ARG, "mode must be PFAC_FOLD_NONE or PFAC_FOLD_ASCII")
+        if self.fold_slot1 != bool(mode) and self._defect("fold_is_per_slot"):
+            self.fold = bool(mode)          # (slot 1 keeps the mode it had)
+            return
+        self.fold = self.fold_slot1 = bool(mode)
+
+    def set_case_fold(self, on):
+        self.raw_set_case_fold(int(bool(on)))
+
+    @property
+    def case_fold(self):
+        if self.tab is None:
+            raise _err(S.E_STATE, "pfac_table_case_fold before a table upload")
+        return self.fold
 
     def set_final_lengths(self, lengths):
         if self.tab is None:
@@ -199,10 +253,16 @@ class CpuDevice:
         data = d_input.src if d_input is not None else s.data
         n_avail = n_owned if n_avail is None else n_avail
         if n_avail == 0:
-            inp = next(i for i, d in enumerate(S.TABLES[self.tab]["inputs"]) if d[1] == 0)
+            inp = next(i for i, d in enumerate(S.POOL[self.tab]["inputs"]) if d[1] == 0)
         else:
-            inp = next(i for i in range(len(S.TABLES[self.tab]["inputs"])) if self.x.input(self.tab, i) is data)
-        pos, ids, lens = self.x.scan(self.tab, inp, n_owned)
+            inp = next(i for i in range(len(S.POOL[self.tab]["inputs"])) if self.x.input(self.tab, i) is data)
+        fold = self.fold_slot1 if slot == 1 else self.fold       # the mode of THIS launch (fold_slot1 differs under a defect only)
+        changes = lambda: not all(np.array_equal(a, b) for a, b in zip(self.x.scan(self.tab, inp, n_owned), self.x.scan(self.tab, inp, n_owned, (), True)))   # noqa: E731
+        if fold and d_records is not None and changes() and self._defect("ext_scan_ignores_fold"):
+            fold = False
+        if fold and self.dense and changes() and self._defect("dense_staging_ignores_fold"):
+            fold = False
+        pos, ids, lens = self.x.scan(self.tab, inp, n_owned, (), fold)
         cap = capacity if d_records is not None else s.rec_cap
         prev = s.scan
         if s.dm is not None and s.dm["own"] and self._defect("ids_lost_at_a_new_scan"):
@@ -210,12 +270,20 @@ class CpuDevice:
         s.seq += 1
         s.scan = dict(tab=self.tab, width=self.width, gen=self.gen, data=self.x.input(self.tab, inp), no=n_owned, pos=pos, ids=ids, lens=lens,
                       over=pos.size > cap, pending=True, seq=s.seq, prev=(prev["pos"], prev["ids"]) if prev else None,
-                      heap=d_records if d_records is not None else s.heap, full=(pos, ids, lens))
+                      heap=d_records if d_records is not None else s.heap, full=(pos, ids, lens), fold=fold, inp=inp, cap=cap,
+                      tiles=(n_avail + 4095) // 4096)
 
     def scan_finish(self, slot=0, allow_overflow=False):
         s = self.slots[slot]
         if s.scan is None:
             raise _err(S.E_STATE, "no scan")
+        sc = s.scan
+        if sc["pending"] and sc["fold"] != self.fold and "toggle_reaches_pending_scan" in self.defects:
+            pos, ids, lens = self.x.scan(sc["tab"], sc["inp"], sc["no"], (), self.fold)      # (the mode read at the finish, not at the launch)
+            if (pos.size != sc["pos"].size or not np.array_equal(pos, sc["pos"])) and self._defect("toggle_reaches_pending_scan"):
+                sc.update(pos=pos, ids=ids, lens=lens, full=(pos, ids, lens), over=pos.size > sc["cap"], fold=self.fold)
+        if sc["pending"] and not self.dense_pinned and sc["tiles"] >= 64 and sc["width"] != 8:
+            self.dense = sc["pos"].size > DENSE_PER_TILE * sc["tiles"] // 4       # (the next scans of the context run in this mode)
         s.scan["pending"] = False
         if s.scan["over"] and not allow_overflow:
             raise _err(S.E_OVERFLOW, "overflow")
@@ -378,6 +446,10 @@ class CpuDevice:
             if (d_records if d_records is not None else s.heap) is not sc["heap"]:
                 raise _err(S.E_ARG, "not the heap of the slot's last scan")
             ids, n = sc["ids"], sc["ids"].size
+            if sc["fold"] != self.fold and ids.size == sc["full"][1].size and "counts_follow_current_mode" in self.defects:
+                other = self.x.scan(sc["tab"], sc["inp"], sc["no"], (), self.fold)[1]
+                if not np.array_equal(np.bincount(other, minlength=1), np.bincount(ids, minlength=1)) and self._defect("counts_follow_current_mode"):
+                    ids, n = other, other.size
             if ids.size != sc["full"][1].size and self._defect("counts_ignore_the_filter"):
                 ids = sc["full"][1]
             if n != sc["full"][1].size and self._defect("n_counted_stays_the_unfiltered_count"):
@@ -583,6 +655,9 @@ class CpuDevice:
             pieces.append(data[int(off[k]):int(off[k + 1])])
             out_off.append(out_off[-1] + pieces[-1].size)
         out = np.concatenate(pieces) if pieces else np.zeros(0, np.uint8)
+        if d_input is None and sc is not None and sc["fold"] and sc["data"] is data and "gather_copies_folded_bytes" in self.defects:
+            if not np.array_equal(nocaseref.fold(out), out) and self._defect("gather_copies_folded_bytes"):
+                out = nocaseref.fold(out)                        # (as if the folded scan had folded the slot's input in place)
         out_off = np.array(out_off, dtype=np.uint64)
         if d_out is not None and out.size > out_cap:
             raise _err(S.E_OVERFLOW, "out_cap too small", out_bytes=int(out.size))
@@ -614,6 +689,12 @@ class CpuDevice:
         sc = self._pass_scan(slot, S.E_OVERFLOW)
         if (d_records if d_records is not None else s.heap) is not sc["heap"]:
             raise _err(S.E_ARG, "not the heap of the slot's last scan")
+        sc.pop("judged", None)
+        if sc["fold"] and "filter_judges_folded_bytes" in self.defects:
+            isw = np.zeros(256, dtype=bool)
+            isw[list(b"0123456789ABCDEFGHIJKLMNOPQRSTUVWXYZ_abcdefghijklmnopqrstuvwxyz" if word_bytes is None else word_bytes)] = True
+            if not np.array_equal(isw[nocaseref.fold(sc["data"])], isw[sc["data"]]) and self._defect("filter_judges_folded_bytes"):
+                sc["judged"] = nocaseref.fold(sc["data"])
         off = None
         if n_docs:
             if s.doc is None or n_docs != s.doc.size - 1:
@@ -645,7 +726,7 @@ class CpuDevice:
         """bool[n_avail + 1]: a word runs on across i (W of the byte before i and of the byte at i), no document starts there."""
         isw = np.zeros(256, dtype=bool)
         isw[list(b"0123456789ABCDEFGHIJKLMNOPQRSTUVWXYZ_abcdefghijklmnopqrstuvwxyz" if word_bytes is None else word_bytes)] = True
-        w = isw[sc["data"]]
+        w = isw[sc.get("judged", sc["data"])]
         cut = np.concatenate(([prev_byte >= 0 and isw[prev_byte]], w)) & np.concatenate((w, [next_byte >= 0 and isw[next_byte]]))
         if off is not None:
             cut[off] = False
@@ -762,12 +843,15 @@ class CpuDevice:
             raise _err(S.E_STATE, "the offsets changed since the selection")
         table = rep_table(self.reps if not stale else {k: b"?" for k in range(1, 4096)})
         pos, ids, lens = sel["rec"]["pos"].astype(np.int64), sel["rec"]["state"].astype(np.int64), sel["lens"]
+        src = sc["data"]
+        if sc["fold"] and not np.array_equal(nocaseref.fold(src[:sc["no"]]), src[:sc["no"]]) and self._defect("doc_replace_copies_folded_bytes" if docs else "replace_copies_folded_bytes"):
+            src = nocaseref.fold(src)
         if sel["kind"] == "whole":
-            out = splice(sc["data"], sel["entry"], sc["no"], pos, lens, ids, table)
+            out = splice(src, sel["entry"], sc["no"], pos, lens, ids, table)
             out_off = None
         else:
             off, first = sel["off"], sel["first"].astype(np.int64)
-            parts = [splice(sc["data"][int(off[d]):int(off[d + 1])], 0, int(off[d + 1] - off[d]), pos[first[d]:first[d + 1]] - off[d],
+            parts = [splice(src[int(off[d]):int(off[d + 1])], 0, int(off[d + 1] - off[d]), pos[first[d]:first[d + 1]] - off[d],
                             lens[first[d]:first[d + 1]], ids[first[d]:first[d + 1]], table) for d in range(off.size - 1)]
             out = np.concatenate(parts) if parts else np.empty(0, np.uint8)
             out_off = np.concatenate([[0], np.cumsum([p.size for p in parts])]).astype(np.uint64)
@@ -1509,3 +1593,249 @@ def test_shrink_keeps_a_line_failure(line_plans):
             S.run(CpuDevice([defect]), S.shrink(seed, failed, lines=True), S.Model(), seed=seed)
             return
     raise AssertionError("no plan to shrink")
+
+
+# ---------------------------------------------------------------------------
+# the fifth family: the case fold (pfac_table_set_case_fold as a piece of context state with a life of its own)
+
+@pytest.fixture(scope="module")
+def fold_plans():
+    return {seed: S.plan(seed, fold=True) for seed in S.FOLD_SEEDS}
+
+
+# SHA-256 of json.dumps([plan(seed, fold=True) for seed in FOLD_SEEDS], sort_keys=True): pinned like the four before it.
+FOLD_PLANS_SHA256 = "f014f6014658aca7e43593b13a03e94e3b839eb6e46f7302d91fc5d6b0162f0b"
+
+
+def test_the_plans_with_the_fold_are_pinned(fold_plans):
+    assert [seed for seed in fold_plans] == S.FOLD_SEEDS and len(S.FOLD_SEEDS) == 24
+    assert hashlib.sha256(json.dumps([fold_plans[seed] for seed in S.FOLD_SEEDS], sort_keys=True).encode()).hexdigest() == FOLD_PLANS_SHA256
+
+
+def test_fold_plans_are_deterministic_and_well_formed(fold_plans, line_plans):
+    for seed in S.FOLD_SEEDS[:3]:
+        assert S.plan(seed, fold=True) == fold_plans[seed] != line_plans[seed]
+        assert S.shrink(seed, 23, fold=True) == fold_plans[seed][:23]
+    assert fold_plans[0] != fold_plans[1]
+    for seed, ops in fold_plans.items():
+        assert len(ops) == S.FOLD_PLAN_OPS
+        m = S.Model()
+        for k, op in enumerate(ops):
+            assert hasattr(S.Executor, "do_" + op["op"]), f"seed {seed} op {k}: the executor cannot perform {S.fmt(op)}"
+            st = m.apply(op).status
+            assert st in (S.OK, S.E_ARG, S.E_STATE, S.E_OVERFLOW), f"seed {seed} op {k}: the contract does not decide {S.fmt(op)}"
+
+
+def test_fold_plans_are_the_same_in_another_process(fold_plans):
+    seeds = S.FOLD_SEEDS[:3]
+    code = ("import hashlib, json, session as S; print(hashlib.sha256(json.dumps([S.plan(s, fold=True) for s in %r], sort_keys=True).encode()).hexdigest())" % seeds)
+    here = os.path.dirname(os.path.abspath(__file__))
+    env = dict(os.environ, PYTHONHASHSEED="2468", PYTHONPATH=os.pathsep.join([here, os.path.dirname(here)]))
+    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, check=True, timeout=300).stdout.split()[-1]
+    assert out == hashlib.sha256(json.dumps([fold_plans[s] for s in seeds], sort_keys=True).encode()).hexdigest()
+
+
+def _rows(scan):
+    return set(zip(scan[0].tolist(), scan[1].tolist()))
+
+
+def test_the_old_pool_is_what_it_was_and_the_new_tables_say_nocase():
+    assert list(S.POOL)[:9] == list(S.TABLES) and set(S.POOL) - set(S.TABLES) == set(S.FOLD_TABLES) == {"wordsi", "symi", "cclassi", "root1i"}
+    x = S.expectations()
+    for t in S.TABLES:
+        assert S.POOL[t]["inputs"][:-1] == S.TABLES[t]["inputs"] and S.POOL[t]["knobs"] == S.TABLES[t]["knobs"]
+        assert not x.table(t).ignore_case
+    for t in S.FOLD_TABLES:
+        assert x.table(t).ignore_case and S.POOL[t]["nocase"]
+        assert set(S.WORD_TAB[t]) == set(range(0x61, 0x7B))
+    assert x.width("wordsi", S.FOLD_TABLES["wordsi"]["knobs"][0]) == 2 and x.width("symi", S.FOLD_TABLES["symi"]["knobs"][0]) == 4
+    sizes = {t: [d[1] for d in S.FOLD_TABLES[t]["inputs"]] for t in S.FOLD_TABLES}
+    assert sizes["wordsi"] == [300_007, 300_007, S.GROUP + 1, 4097, 17] and sizes["symi"] == [70_001, 4095, 1]
+    assert sizes["root1i"] == [3 * S.TILE + 11, 17] and x.count("wordsi", 1, 300_007, (), True) == 0 and 300_007 >= 64 * S.TILE
+
+
+def test_the_fold_adds_records_on_every_input_of_the_new_tables():
+    """By the references alone: folded = the table's CPU matcher over nocaseref.fold(input), exact = the same matcher over
+    the input as written.  For the three literal tables an exact match is a run of bytes the fold leaves alone, so the
+    folded records CONTAIN the exact ones; they contain them strictly on every input with a letter in it (not on the
+    matchless input of wordsi, and not on the one byte of symi, an E, where both are empty).  cclassi is no superset and
+    cannot be: its one-byte negated class [^a-z0-9 ] reports every upper-case letter of the exact scan and none of them
+    once the input is folded -- there the fold both adds records ([A-C]x over Ax, Bx, aX ...) and takes some away."""
+    x = S.expectations()
+    for t in S.FOLD_TABLES:
+        for i, (name, n, style) in enumerate(S.FOLD_TABLES[t]["inputs"]):
+            exact, folded = _rows(x.scan(t, i, n)), _rows(x.scan(t, i, n, (), True))
+            print(t, name, len(exact), len(folded))
+            if t == "cclassi":
+                assert folded - exact and exact - folded, (t, name)
+                lost = {p for p, k in exact - folded}
+                assert all(0x41 <= int(x.input(t, i)[p]) <= 0x5A or 0x41 <= int(x.input(t, i)[p + 1]) <= 0x5A for p in lost)
+            elif style == "nomatch" or n == 1:
+                assert folded == exact == set(), (t, name)
+            else:
+                assert folded > exact, (t, name)
+
+
+def test_every_old_table_has_an_input_the_fold_changes():
+    """... except dense2, whose three symbols are 0xDE, 0xEB and 0xAC: no line of it holds a letter, so no input exists
+    for which the fold changes its records (a letter of the input is outside the alphabet folded or not)."""
+    x = S.expectations()
+    for t in S.TABLES:
+        differs = [i for i in range(len(S.POOL[t]["inputs"])) if x.fold_differs(t, i)]
+        if t == "dense2":
+            letters = set(range(0x41, 0x5B)) | set(range(0x61, 0x7B))
+            assert not letters & set(b"".join(x.tinfo(t)["lines"])) and not differs
+        else:
+            assert differs, t
+    assert not any(x.fold_differs("abc2", i) for i in range(4)) and x.fold_differs("abc2", 4)
+
+
+def test_the_folded_class_reference_against_the_oracle():
+    """nocaseref.folded_classes on the class file of cclassi: element for element the sets oracle/charclass_oracle.py
+    parses from the same file with its letters written in lower case by hand ([^A] -> [^a]: the LISTED set is folded, the
+    negation complements it), and the lengths ClassMatcher takes from them."""
+    cco = S._ClassMatcher.__init__.__globals__["cco"]
+    by_hand = b"[a-c]x\n" b"[^a]b\n" b"[^a-z0-9 ]\n" b"q[0-9][0-9]\n" b"ax\n" b"b[x-z]\n" b"[a-c]x\n"
+    got, want = nocaseref.folded_classes(S.CCLASSI), cco.parse(by_hand)
+    assert [len(p) for p in got] == [len(p) for p in want]
+    for a, b in zip(got, want):
+        for sa, sb in zip(a, b):
+            np.testing.assert_array_equal(sa, sb)
+    assert not any(s[0x41:0x5B].any() for p in got[:1] + got[3:] for s in p)       # (no listed upper-case letter is left)
+    np.testing.assert_array_equal(np.flatnonzero(~got[1][0]), [ord("a")])          # [^A]: everything but a
+    assert got[2][0][0x41:0x5B].all()                                              # [^a-z0-9 ]: A-Z pass -- but a folded input has none
+    np.testing.assert_array_equal(nocaseref.fold_class_set(cco.parse(b"[Z-a]\n")[0][0]).nonzero()[0], [0x5B, 0x5C, 0x5D, 0x5E, 0x5F, 0x60, 0x61, 0x7A])
+    x = S.expectations()
+    assert x.tinfo("cclassi")["matcher"].parsed is not None and x.tinfo("cclassi")["ll"].tolist() == [0, 2, 2, 1, 3, 2, 2, 2]
+
+
+@pytest.mark.parametrize("seed", S.FOLD_SEEDS)
+def test_fold_plan_passes_on_the_cpu_device(seed, fold_plans):
+    stats = S.run(CpuDevice(), fold_plans[seed], S.Model(), seed=f"{seed} (fold)")
+    assert stats["ops"] == S.FOLD_PLAN_OPS and stats["errors"] > 0 and stats["folded"] > 0 and stats["toggles"] + stats["modes"] > 0
+
+
+@pytest.mark.parametrize("defect", FOLD_DEFECTS)
+def test_every_fold_defect_is_caught(defect, fold_plans):
+    caught = []
+    for seed, ops in fold_plans.items():
+        seed = f"{seed} (fold)"
+        touched, failed = first_touch(seed, ops, defect)
+        assert failed is None or (touched is not None and failed >= touched), f"seed {seed}: failed at {failed} before the defect acted ({touched})"
+        if failed is not None:
+            with pytest.raises(AssertionError) as e:
+                S.run(CpuDevice([defect]), ops, S.Model(), seed=seed)
+            assert f"session seed {seed}, operation {failed} " in str(e.value) and e.value.op_index == failed
+            caught.append((seed, touched, failed, S.fmt(ops[failed])))
+            if len(caught) == 2:
+                break
+    assert caught, f"no fold plan notices {defect}"
+    print(f"{defect}: caught by plans (seed, first touched, failed at, the failing operation) {caught}")
+
+
+def test_shrink_keeps_a_fold_failure(fold_plans):
+    defect = "toggle_reaches_pending_scan"
+    for seed, ops in fold_plans.items():
+        touched, failed = first_touch(seed, ops, defect)
+        if failed is not None:
+            with pytest.raises(AssertionError):
+                S.run(CpuDevice([defect]), S.shrink(seed, failed + 1, fold=True), S.Model(), seed=seed)
+            S.run(CpuDevice([defect]), S.shrink(seed, failed, fold=True), S.Model(), seed=seed)
+            return
+    raise AssertionError("no plan to shrink")
+
+
+def _est_dense(dense, knob, width, n_avail, count):
+    """The stand-in's staging rule (CpuDevice.scan_finish), for the reach test: the mode after a scan's finish."""
+    tiles = (n_avail + 4095) // 4096
+    if "PFAC_DENSE" in KNOBS[knob] or tiles < 64 or width == 8:
+        return dense
+    return count > DENSE_PER_TILE * tiles // 4
+
+
+BEHIND = ("filter",) + S.PASSES + ("count", "count_sel", "split", "matching", "context", "gather")
+
+
+def test_fold_plans_reach_everything(fold_plans):
+    """Conditions, not measurements, over S.FOLD_SEEDS."""
+    x = S.expectations()
+    kinds, where, tables, widths, placed, behind, fold_statuses = set(), set(), set(), set(), set(), set(), set()
+    toggle_while_pending = off_after_upload = late_records = flipped = False
+    errors = total = 0
+    seed_now = None
+    for seed, k, op, st, was, m in _walk_models(fold_plans):
+        if seed != seed_now:
+            seed_now, dense, last_mode, on_at_upload, pending_mode = seed, False, None, False, {}
+        kind, slot = op["op"], op.get("slot", 0)
+        kinds.add(kind)
+        total += 1
+        errors += st != S.OK
+        ws = was.slots[slot]
+        if kind == "load_table":
+            on_at_upload = was.fold
+            dense = KNOBS[op["knob"]].get("PFAC_DENSE") == "1"
+        if kind == "set_fold":
+            fold_statuses.add(st)
+            on_at_upload = False
+            if st == S.OK and op["mode"] != int(was.fold) and any(s.scan is not None and s.scan["pending"] for s in was.slots):
+                toggle_while_pending = True
+        if kind == "get_fold" and st == S.OK:
+            fold_statuses.add("read")
+            off_after_upload |= on_at_upload and not was.fold
+        if kind in ("scan_bytes", "scan_ext", "scan_start") and st == S.OK:
+            sc = m.slots[slot].scan
+            width = x.width(sc["tab"], sc["knob"])
+            where |= {(sc["fold"], "slot", slot), (sc["fold"], "shared", slot == 1 and ws.shared)}
+            if sc["fold"]:
+                tables.add(sc["tab"])
+                widths.add(width)
+                knobs = KNOBS[sc["knob"]]
+                placed.add("through L2" if "PFAC_FORCE_L2" in knobs else "in LDS")
+                if dense:
+                    placed.add("dense staging")
+                flipped |= last_mode is not None and last_mode != dense
+            last_mode = dense
+            if kind == "scan_start":
+                pending_mode[slot] = True
+            else:
+                dense = _est_dense(dense, sc["knob"], width, x.input_size(sc["tab"], sc["inp"]), m._count(sc))
+        if kind == "scan_finish" and st == S.OK and pending_mode.pop(slot, False):
+            sc = m.slots[slot].scan
+            dense = _est_dense(dense, sc["knob"], x.width(sc["tab"], sc["knob"]), x.input_size(sc["tab"], sc["inp"]), m._count(sc))
+        sc = ws.scan
+        if kind in BEHIND and st == S.OK and sc is not None and not sc["pending"] and sc["gen"] == was.gen:
+            if sc["fold"]:
+                behind.add((kind, "folded"))
+            elif S.POOL[sc["tab"]].get("nocase"):
+                behind.add((kind, "exact scan of a nocase table"))
+        if kind == "records" and st == S.OK and op["n"] and sc["fold"] and sc["gen"] != was.gen:
+            late_records = True
+    missing = {"kinds": sorted(set(S.FOLD_KINDS) - kinds)}
+    want = {(f, "slot", sl) for f in (False, True) for sl in (0, 1)} | {(f, "shared", True) for f in (False, True)}
+    missing["modes on slots and the shared stream"] = sorted(want - where, key=str)
+    missing["set_fold / get_fold statuses"] = sorted({S.OK, S.E_STATE, S.E_ARG, "read"} - fold_statuses, key=str)
+    missing["tables folded"] = sorted(set(S.POOL) - tables)
+    missing["widths folded"] = sorted({2, 4, 8} - widths)
+    missing["placements folded"] = sorted({"in LDS", "through L2", "dense staging"} - placed)
+    missing["behind"] = sorted({(b, w) for b in BEHIND for w in ("folded", "exact scan of a nocase table")} - behind)
+    missing["histories"] = [name for name, seen in (("a toggle while a scan is pending", toggle_while_pending),
+                                                   ("get_fold reads off after an upload that followed an on", off_after_upload),
+                                                   ("a folded scan in another staging mode than the scan before it", flipped),
+                                                   ("records of a folded scan fetched after a later upload", late_records)) if not seen]
+    missing = {k2: v for k2, v in missing.items() if v}
+    assert not missing, "the fold plans never reach:\n" + "\n".join(f"  {k2}: {v}" for k2, v in missing.items())
+    assert 0.06 < errors / total < 0.25, f"{errors} of {total} operations are illegal"
+
+
+def test_three_quarters_of_the_folded_scans_differ_from_the_exact_ones(fold_plans):
+    """By the reference alone: the family does not hide behind inputs the fold changes nothing for."""
+    x = S.expectations()
+    folded = differ = 0
+    for seed, k, op, st, was, m in _walk_models(fold_plans):
+        if op["op"] in ("scan_bytes", "scan_ext", "scan_start") and st == S.OK and m.slots[op["slot"]].scan["fold"]:
+            sc = m.slots[op["slot"]].scan
+            a, b = x.scan(sc["tab"], sc["inp"], sc["no"]), x.scan(sc["tab"], sc["inp"], sc["no"], (), True)
+            folded += 1
+            differ += not (np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]))
+    print(f"{differ} of {folded} folded scans differ from the exact scan of the same input")
+    assert folded >= 4 * len(fold_plans) and 4 * differ >= 3 * folded, (differ, folded)       # (four folded scans a plan at the least)
