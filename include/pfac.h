@@ -234,7 +234,12 @@ const char *pfac_last_error(const pfac_ctx *ctx);                    /* ctx may 
  * pfac_records_d2h, pfac_records_expand and the packed fetches deliver them, their `state` indexing the idmap of the
  * table they were scanned with.  Everything that needs that table on the device is gone with it: the text emitter and
  * the checksum (idmap), the segment pass, both selections and both replaces (final lengths, replacements) return
- * PFAC_E_STATE for such a scan. */
+ * PFAC_E_STATE for such a scan.
+ * An upload installs its table whole or not at all.  An image whose HEADER is refused (magic, version, sizes: PFAC_E_ARG)
+ * leaves the installed table, what is attached to it and every earlier scan exactly as they were.  Any refusal past the
+ * header -- an image whose states or displacements point outside its tables, a failed device allocation -- leaves the
+ * context with NO table: pfac_scan_async, pfac_scan_info and the pfac_table_set_* calls return PFAC_E_STATE until an
+ * upload succeeds, and every earlier scan counts as one made with an earlier table, as above. */
 int pfac_table_upload(pfac_ctx *ctx, const int32_t *blob, size_t n_words);
 int pfac_table_upload_device(pfac_ctx *ctx, const void *d_blob, size_t n_words, void *stream_handle);
 

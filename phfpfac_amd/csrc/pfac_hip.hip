@@ -3918,12 +3918,52 @@ struct Slot {
     PassOut<unsigned long long> ga_off;   // ... and the output offsets (n_ids + 1 entries)
 };
 
-}  // namespace
-
 struct StageLayout {                      // per-wave LDS of one staging mode
     int nbuf = 2, pw_bytes = 0, waves_per_block = 0, lds_bytes = 0;
     unsigned stage_cap = 0;               // records per buffer (0: final states do not fit the packed word)
 };
+
+// Tuning and test knobs: the environment as ONE install reads it (read_knobs), once, before anything is built.
+struct Knobs {
+    bool force_l2 = false, no_d1 = false, no_fuse = false, no_d1pack = false, no_secf = false, no_nw4 = false, no_dense2 = false, verbose = false;
+    int l2f = -1;                         // PFAC_L2F 0: filter off; 2: lookup form even where the SWAR / flag-only form applies; 3: flags only
+    int nwb = 0, lag = 0;                 // PFAC_NWB: fewer waves per workgroup; PFAC_LAG 1 / 2: pin the emission lag (tests, A/B runs)
+    int rec_bytes = 0, d2_logcap = 0;     // PFAC_REC_BYTES / _WIDE: a WIDER record form; PFAC_D2_LOGCAP: tiles with more records take the fallback pass
+    int dense = -1;                       // PFAC_DENSE=0/1 pins the staging mode
+    unsigned ticket_ways = 0, count_bins = 0, count_grid = 0, count_threads = 0;   // PFAC_TICKET_WAYS, PFAC_COUNT_BINS / _GRID / _THREADS (0: the defaults)
+    unsigned spin_max = SPIN_MAX, fault = 0;                      // (they go into ScanArgs as they are)
+    std::string trace_file;
+};
+
+// Everything ONE installed table fixes about the scans that run with it.  install_table builds it aside and moves it
+// into the context whole, or not at all: no scan ever launches from a plan that an install has left half made.  What a
+// kernel argument already says (the header's num_final, wbit, r_words = max_row, ht_size; the table views s0, r, T; the
+// level-2 filter, the dense rows' numbers, the shared LDS carve, the root) is kept in `base` only.
+struct TablePlan {
+    DevBuf<unsigned char> tab;            // the repacked tables: base.s0, base.r, base.T and ...
+    const int *d_idmap = nullptr;         // ... final state -> pattern id
+    DevBuf<int> d1;                       // dense depth-1 rows + (after them) the 256-byte row index
+    DevBuf<unsigned char> bm2;            // level-2 filter: 2-byte-prefix bitmap, 256 rows of 32 bytes, + the second-byte flags
+    DevBuf<int4> T4_alloc;                // fused slots (variant 1, width >= 256), from slot min(0, min r) = -base.rn_bias
+    int max_pat_len = 0, state_num = 0;   // header facts that no kernel argument carries
+    ScanArgs base{};                      // every argument that does not change between uploads; a launch adds the rest
+    int variant = 1;                      // 0: tables in LDS, 1: via L2
+    bool fused = false;                   // ... as fused slots, one gather per step
+    int root_mode = 0;                    // 1: the root has ONE edge, exact SWAR root test; 0: LDS flag tables
+    StageLayout lay[2];                   // sparse staging: [0] two buffers (emission lags one round), [1] three (two rounds)
+    StageLayout lay_d;                    // dense staging: one big buffer per wave (stage_cap 0: dense mode unavailable)
+    bool lag2_ok = false;                 // the three-buffer layout is usable
+    bool dense2 = false;                  // dense mode runs in its second form (dense2_tile): fused tables, packed dense rows, 4-byte records
+    int grid_blocks = 0;
+    const void *kernel[2] = {};           // [0] the exact kernel, [1] its twin that folds the input's case (pfac_ctx::fold chooses)
+    const void *kernel_d[2] = {};         // the kernel dense mode launches (four walks per lane on fused L2 tables)
+    const void *kernel3[2] = {};          // the three-staging-buffer twin of `kernel`
+    Knobs knobs;
+    const void *kernel_of(bool dense, bool lag2, unsigned fold) const { return dense ? kernel_d[fold] : (lag2 ? kernel3[fold] : kernel[fold]); }
+    int max_lds() const { return std::max(lay_d.lds_bytes, std::max(lay[0].lds_bytes, lay[1].lds_bytes)); }
+};
+
+}  // namespace
 
 struct pfac_ctx {
     int device = 0;
@@ -3933,56 +3973,26 @@ struct pfac_ctx {
                                           // back on one DMA queue run at the link's rate (55 GB/s), copies that alternate with
                                           // kernels on the slots' own streams leave gaps (45 GB/s measured); the slot's stream
                                           // waits for its copy through an event
-    // table
-    DevBuf<unsigned char> tab;            // the repacked tables: the four views below
-    int *d_s0 = nullptr, *d_r = nullptr, *d_idmap = nullptr;
-    int2 *d_T = nullptr;
-    int4 *d_T4 = nullptr;                 // fused slots (variant 1, width >= 256), else null: slot 0 of ...
-    DevBuf<int4> T4_alloc;                // ... this allocation, which starts at slot min(0, min r) = -rn_bias
-    int rn_bias = 0;
-    int width_bit = 0, num_final = 0, max_pat_len = 0, max_row = 0, ht_size = 0, state_num = 0;
+    // table: what the installed one fixes, ...
+    TablePlan plan;
     bool have_table = false;
-    int variant = 1;
-    const void *kernel[2] = {};           // [0] the exact kernel, [1] its twin that folds the input's case (ctx->fold chooses)
-    const void *kernel_d[2] = {};         // the kernel dense mode launches (four walks per lane on fused L2 tables)
-    const void *kernel3[2] = {};          // the three-staging-buffer twin of `kernel` (tables in LDS only), else null
-    int shared_bytes = 0, halo = 0, root_mode = 0;
-    unsigned root_byte = 0;
-    int root_state = -1;
-    StageLayout lay[2];                   // sparse staging: [0] two buffers (emission lags one round), [1] three (two rounds)
-    bool lag2_ok = false, lag2 = false, lag_forced = false;   // three-buffer layout usable / in use / pinned (PFAC_LAG)
-    const StageLayout &sparse() const { return lay[lag2 ? 1 : 0]; }
-    StageLayout lay_d;                    // dense staging: one big buffer per wave (stage_cap 0: dense mode unavailable)
-    bool dense = false;                   // current staging mode (adapts to the match density seen by the last scan)
-    bool run_dense() const { return dense && lay_d.stage_cap; }       // ... of the next launch
-    const StageLayout &layout(bool dense_mode) const { return dense_mode ? lay_d : sparse(); }
-    bool dense2 = false;                  // dense mode runs in its second form (dense2_tile): fused tables, packed dense rows, 4-byte records
-    unsigned d2log_cap = 0;               // ... words of record log per compute wave (test knob PFAC_D2_LOGCAP: a smaller one)
-    int dense_forced = -1;                // PFAC_DENSE=0/1 pins the mode
-    DevBuf<int> d1;                       // dense depth-1 rows + (after them) the 256-byte row index
-    int d1_rows = 0, d1_stride = 0, d1_ncols = 0, d1_lds_bytes = 0;
-    int d1_n2 = 0;                        // > 0: dense rows are packed (fused tables), r[] of the depth-2 states follows them
-    int grid_blocks = 0;
-    int rec_bytes = 4;                    // record form: 2 (<= 16 final states), 4 (<= 2^20), 8 bytes (pfac_record)
-    DevBuf<short> flen;                   // pattern length of every final state (pfac_table_set_final_lengths), cleared by an upload
+    uint64_t table_gen = 0;               // installs begun so far: a scan's final states index the lengths of ITS table only
+    // ... what the caller attaches to it (an upload drops all four), ...
+    DevBuf<short> flen;                   // pattern length of every final state (pfac_table_set_final_lengths)
     DevBuf<unsigned> rep_off;             // replacement of every final state (pfac_table_set_replacements): offsets[num_final + 1]
-    DevBuf<unsigned char> rep;            // ... and the bytes, zero-padded to its capacity (a multiple of 16); cleared by an upload
-    unsigned fold = PFAC_FOLD_NONE;       // case fold of the scans to come (pfac_table_set_case_fold), reset by an upload
-    uint64_t table_gen = 0;               // tables installed so far: a scan's final states index the lengths of ITS table only
-    // level-2 filter (ScanArgs::l2f_mode)
-    DevBuf<unsigned char> bm2;            // 2-byte-prefix bitmap, 256 rows of 32 bytes
-    int l2f_mode = 0, n_child = 0, bm2_rows = 0, sh_bm2 = 0, sec_filter = 0, sh_t0 = 0;
-    unsigned child0 = 0, child1 = 0;
-    // tuning / test knobs, read from the environment ONCE, when a table is installed
-    unsigned spin_max = SPIN_MAX, fault = 0, ticket_ways_knob = 0;
+    DevBuf<unsigned char> rep;            // ... and the bytes, zero-padded to its capacity (a multiple of 16)
+    unsigned fold = PFAC_FOLD_NONE;       // case fold of the scans to come (pfac_table_set_case_fold)
+    // ... and what adapts to the match density seen by the last scan (pfac_scan_finish)
+    bool dense = false;                   // staging mode
+    bool lag2 = false;                    // three-buffer layout in use
+    bool run_dense() const { return dense && plan.lay_d.stage_cap; }       // ... of the next launch
+    const StageLayout &layout(bool dense_mode) const { return dense_mode ? plan.lay_d : plan.lay[lag2 ? 1 : 0]; }
     bool event_timing = false;            // PFAC_EVENT_TIMING=1 (read when the context is created): the scan's dispatch carries a
                                           // start and a stop event, completion and pfac_scan_elapsed_ms come from them -- the
                                           // earlier form, kept to compare the two clocks and the two boundaries on one build
     double tick_ms = 1e-5;                // one tick of the kernel's clock (s_memrealtime) in ms: 1 / hipDeviceAttributeWallClockRate
     double clk_diff_ms = 0;               // PFAC_EVENT_TIMING: event time - the kernel's own, summed over the timed scans, ...
     uint64_t clk_n = 0;                   // ... and how many (printed when the context goes, under PFAC_VERBOSE)
-    unsigned count_bins = 0, count_grid = 0, count_threads = 0;   // PFAC_COUNT_BINS / _GRID / _THREADS (0: the defaults)
-    std::string trace_file;
     std::string err;
     std::mutex mu;
 };
@@ -4163,15 +4173,6 @@ int wait_scan(pfac_ctx *ctx, Slot &s) {
     return PFAC_OK;
 }
 
-static int max_lds(const pfac_ctx *ctx) {
-    int v = ctx->lay_d.lds_bytes;
-    for (const StageLayout &L : ctx->lay) v = L.lds_bytes > v ? L.lds_bytes : v;
-    return v;
-}
-
-// one workgroup per CU: ask for more than half of the LDS so two never share a CU while another idles
-int lds_of_one_block_per_cu(int lds_bytes) { return lds_bytes < LDS_TOTAL / 2 + 256 ? LDS_TOTAL / 2 + 256 : lds_bytes; }
-
 // The scan kernel of a table placement (0: tables via L2, 1: tables in LDS, 2: fused L2 tables, 3: fused L2 tables
 // with four walks per lane -- dense mode, two staging buffers only), hash width, root test, NB staging buffers and case
 // fold (every kernel has a twin that folds its tile on the way into LDS).
@@ -4199,261 +4200,307 @@ const void *scan_kernel(int placement, bool w8, int root, unsigned fold) {
     return fold ? scan_kernel_fold<NB, true>(placement, w8, root) : scan_kernel_fold<NB, false>(placement, w8, root);
 }
 
-// layout of pfac_ctx::d_d1: rows (d1_rows x 256 int32) | 256-byte row index | the depth-1 states | (packed rows) {r[], child
+// layout of TablePlan::d1: rows (d1_rows x 256 int32) | 256-byte row index | the depth-1 states | (packed rows) {r[], child
 // mask} of the depth-2 states (8-byte aligned) | counter | column map | column bytes
 size_t d1_off_r2(int d1_rows) { return align_up((size_t)d1_rows * 1024 + 256 + (size_t)d1_rows * 4, 8); }
 size_t d1_off_col(int d1_rows) { return d1_off_r2(d1_rows) + (size_t)D1_N2_MAX * 8 + 16; }
 
-int configure_kernel(pfac_ctx *ctx, const int32_t *s0_host) {
-    // table bytes if staged in LDS: r (16-B rounded) + T
-    const size_t tbytes = align_up((size_t)ctx->max_row * 4, 16) + (size_t)ctx->ht_size * 8;
-    ctx->variant = tbytes <= (size_t)LDS_TABLE_MAX ? 0 : 1;
-    if (knob("PFAC_FORCE_L2")) ctx->variant = 1;             // tuning knob: tables via L2 even if they fit LDS
-    int halo = ctx->max_pat_len > 1 ? ctx->max_pat_len - 1 : 0;
-    ctx->halo = (halo + 15) & ~15;
-    // dense rows for the depth-1 states (children of the root), when there are few enough of them
-    int fan = 0, rb = 0;
-    int d1state[256];
-    unsigned char d1idx[256];
+// ---- install, step 1: every knob, read once per table install
+Knobs read_knobs() {
+    Knobs k;
+    auto is_set = [](const char *name) { return knob(name) != nullptr; };
+    k.force_l2 = is_set("PFAC_FORCE_L2");                  // tuning knob: tables via L2 even if they fit LDS
+    k.no_d1 = is_set("PFAC_NO_D1"); k.no_d1pack = is_set("PFAC_NO_D1PACK"); k.no_fuse = is_set("PFAC_NO_FUSE");
+    k.no_secf = is_set("PFAC_NO_SECF"); k.no_nw4 = is_set("PFAC_NO_NW4"); k.no_dense2 = is_set("PFAC_NO_DENSE2");
+    k.verbose = is_set("PFAC_VERBOSE");
+    k.l2f = env_int("PFAC_L2F", -1);
+    k.nwb = env_int("PFAC_NWB", 0);
+    k.lag = env_int("PFAC_LAG", 0);
+    k.rec_bytes = env_int("PFAC_REC_BYTES", is_set("PFAC_WIDE") ? 8 : 0);
+    k.d2_logcap = env_int("PFAC_D2_LOGCAP", 0);
+    k.dense = is_set("PFAC_DENSE") ? atoi(knob("PFAC_DENSE")) : -1;
+    k.spin_max = std::max(64u, (unsigned)env_int("PFAC_SPIN_MAX", (int)SPIN_MAX));
+    k.fault = (unsigned)env_int("PFAC_FAULT", 0);
+    k.ticket_ways = (unsigned)env_int("PFAC_TICKET_WAYS", 0);
+    k.trace_file = is_set("PFAC_TRACE") ? knob("PFAC_TRACE") : "";
+    // the state histogram: a smaller LDS table (the cache regime and its collisions at small automata), a fixed grid
+    const int cbins = env_int("PFAC_COUNT_BINS", 0), cgrid = env_int("PFAC_COUNT_GRID", 0), cthreads = env_int("PFAC_COUNT_THREADS", 0);
+    k.count_bins = cbins >= 1 && (unsigned)cbins <= COUNT_BINS_MAX ? (unsigned)cbins : 0u;
+    k.count_grid = cgrid >= 1 ? (unsigned)std::min(cgrid, 65536) : 0u;
+    k.count_threads = cthreads == 256 || cthreads == 512 || cthreads == 1024 ? (unsigned)cthreads : 0u;
+    return k;
+}
+
+// The root's edges, as the repacked tables have them.
+struct RootFan {
+    int32_t s0[256];
+    int fan = 0, last = 0;                // edges, and the byte of the last one (fan == 1: of the only one)
+    int state[256];                       // the depth-1 states, by edge ...
+    unsigned char idx[256];               // ... and root byte -> edge (its dense row)
+};
+
+// ---- the tables themselves: the image repacked into P.tab (on `stream`), its header facts and views, the root's edges.
+// d_blob: device-resident blob image; hdr: its first 16 words on the host, already checked
+int plan_tables(pfac_ctx *ctx, TablePlan &P, const int *d_blob, const int32_t *hdr, hipStream_t stream, RootFan &root) {
+    const int width = hdr[2], wbit = hdr[3], num_final = hdr[5], state_num = hdr[6], max_row = hdr[8], ht_size = hdr[9];
+    const size_t off_r = 256 * 4, off_T = align_up(off_r + (size_t)max_row * 4, 16), off_id = off_T + (size_t)ht_size * 8;
+    const size_t total = align_up(off_id + (size_t)num_final * 4, 16) + 16;
+    if (int rc = P.tab.ensure(ctx, nullptr, total, total)) return rc;
+    unsigned char *base = P.tab.p;
+    int *d_s0 = reinterpret_cast<int *>(base), *d_r = reinterpret_cast<int *>(base + off_r);
+    int2 *d_T = reinterpret_cast<int2 *>(base + off_T);
+    int *d_idmap = reinterpret_cast<int *>(base + off_id), *d_bad = reinterpret_cast<int *>(base + total - 16);
+    HIP_TRY(ctx, hipMemsetAsync(d_bad, 0, 4, stream));
+    hipLaunchKernelGGL(pfac_repack_kernel, dim3(256), dim3(256), 0, stream, d_blob, d_s0, d_r, d_T, d_idmap, max_row, ht_size,
+                       num_final, state_num, width, d_bad);
+    HIP_TRY(ctx, hipGetLastError());
+    int bad = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    if (bad) return fail(ctx, PFAC_E_ARG, "table image: a displacement or a state points outside the tables");
+    ScanArgs &B = P.base;
+    B.s0 = d_s0; B.r = d_r; B.T = d_T; P.d_idmap = d_idmap;
+    B.r_words = max_row; B.t_entries = B.ht_size = ht_size; B.wbit = wbit; B.num_final = num_final; P.state_num = state_num; P.max_pat_len = hdr[7];
+    HIP_TRY(ctx, hipMemcpy(root.s0, d_s0, sizeof root.s0, hipMemcpyDeviceToHost));
     for (int i = 0; i < 256; i++) {
-        d1idx[i] = 0;
-        if (s0_host[i] >= 0) { d1state[fan] = s0_host[i]; d1idx[i] = (unsigned char)(fan < 255 ? fan : 255); fan++; rb = i; }
+        root.idx[i] = 0;
+        if (root.s0[i] >= 0) { root.state[root.fan] = root.s0[i]; root.idx[i] = (unsigned char)(root.fan < 255 ? root.fan : 255); root.fan++; root.last = i; }
     }
-    // (rows are built in device memory in full, 256 columns; LDS takes the columns that have an edge in some row)
-    ctx->d1_rows = (fan >= 1 && fan <= 255 && !knob("PFAC_NO_D1")) ? fan : 0;
-    ctx->d1_stride = 0; ctx->d1_lds_bytes = 0;
-    // tables via L2 and PHF width >= 256: fused slots, one gather per step
-    const bool fused = ctx->variant == 1 && ctx->width_bit >= 8 && !knob("PFAC_NO_FUSE");
-    ctx->d1_n2 = 0;
-    ctx->d1.reset();
-    if (ctx->d1_rows) {
-        const size_t off_r2 = d1_off_r2(ctx->d1_rows);
-        const size_t off_col = d1_off_col(ctx->d1_rows);
-        int rc = ctx->d1.ensure(ctx, nullptr, (off_col + 512) / 4, (off_col + 512) / 4);
-        if (rc) return rc;
-        unsigned char *b = reinterpret_cast<unsigned char *>(ctx->d1.p);
-        int *d_state = reinterpret_cast<int *>(b + (size_t)ctx->d1_rows * 1024 + 256);
-        HIP_TRY(ctx, hipMemcpy(b + (size_t)ctx->d1_rows * 1024, d1idx, 256, hipMemcpyHostToDevice));
-        HIP_TRY(ctx, hipMemcpy(d_state, d1state, (size_t)ctx->d1_rows * 4, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(pfac_build_d1_kernel, dim3(ctx->d1_rows), dim3(256), 0, 0, d_state, ctx->d_r, ctx->d_T,
-                           ctx->width_bit, ctx->ht_size, ctx->d1.p);
-        HIP_TRY(ctx, hipGetLastError());
-        HIP_TRY(ctx, hipDeviceSynchronize());
-        // which bytes are the second byte of some pattern: the LDS rows keep those columns only (host copy of the
-        // rows: at most 255 KiB); too many rows x columns for LDS: no dense level
-        std::vector<int> rows((size_t)ctx->d1_rows * 256);
-        HIP_TRY(ctx, hipMemcpy(rows.data(), ctx->d1.p, rows.size() * 4, hipMemcpyDeviceToHost));
-        unsigned char colmap[256], colbyte[256];
-        int ncols = 0;
-        for (int c = 0; c < 256; c++) {
-            bool used = false;
-            for (int f = 0; f < ctx->d1_rows && !used; f++) used = rows[(size_t)f * 256 + c] >= 0;
-            if (used) colbyte[ncols++] = (unsigned char)c;
-        }
-        const int stride = ncols < 256 ? ncols + 1 : 256;      // one more column, "no edge", unless every byte has its own
-        for (int c = 0; c < 256; c++) colmap[c] = (unsigned char)(ncols & 255);
-        for (int k = 0; k < ncols; k++) colmap[colbyte[k]] = (unsigned char)k;
-        if ((size_t)ctx->d1_rows * stride * 4 > (size_t)D1_LDS_MAX) {
-            ctx->d1.reset();
-            ctx->d1_rows = 0;
-        } else {
-            ctx->d1_stride = stride;
-            ctx->d1_ncols = ncols;
-            ctx->d1_lds_bytes = (int)align_up((size_t)(ctx->d1_rows + 1) * ctx->d1_stride * 4, 16);   // (+ one row without edges)
-            HIP_TRY(ctx, hipMemcpy(b + off_col, colmap, 256, hipMemcpyHostToDevice));
-            HIP_TRY(ctx, hipMemcpy(b + off_col + 256, colbyte, 256, hipMemcpyHostToDevice));
-        }
-        if (ctx->d1_rows && fused && ctx->state_num <= (1 << D1_STATE_BITS) && !knob("PFAC_NO_D1PACK")) {
-            // how many depth-2 states are there?
-            int n2 = 0;
-            for (int v : rows) n2 += v >= 0;
-            if (n2 >= 1 && n2 <= D1_N2_MAX) {
-                int2 *r2 = reinterpret_cast<int2 *>(b + off_r2);
-                int *counter = reinterpret_cast<int *>(r2 + D1_N2_MAX);
-                HIP_TRY(ctx, hipMemset(counter, 0, 4));
-                hipLaunchKernelGGL(pfac_pack_d1_kernel, dim3((unsigned)ctx->d1_rows), dim3(256), 0, 0, ctx->d1.p,
-                                   ctx->d1_rows * 256, ctx->d_r, ctx->d_T, ctx->width_bit, ctx->ht_size, ctx->max_row, r2, counter);
-                HIP_TRY(ctx, hipGetLastError());
-                HIP_TRY(ctx, hipDeviceSynchronize());
-                ctx->d1_n2 = n2;
-            }
-        }
-    }
-    ctx->shared_bytes = SH_D1 + ctx->d1_lds_bytes + (ctx->variant == 0 ? (int)align_up(tbytes, 16) : (int)align_up((size_t)(ctx->d1_n2 ? ctx->d1_n2 + 1 : 0) * 8, 16));
-    if (fused && ctx->d1_rows == 0) ctx->shared_bytes += 1024;   // r[] of the depth-1 states by root byte
-    ctx->sh_t0 = 0;
-    if (ctx->d1_n2 > 0) { ctx->sh_t0 = ctx->shared_bytes; ctx->shared_bytes += 1024; }   // dense mode, second form: its root table
-    // ---- level-2 filter: the 2-byte-prefix bitmap is built on the device from the uploaded tables; a single-edge
-    // root with at most two grandchildren gets the bit-parallel form (their bytes), everything else the lookup form
-    int rc = ctx->bm2.ensure(ctx, nullptr, 256 * 32 + 256, 256 * 32 + 256);   // bitmap + the second-byte flags
-    if (rc) return rc;
-    hipLaunchKernelGGL(pfac_build_bm2_kernel, dim3(256), dim3(256), 0, 0, ctx->d_s0, ctx->d_r, ctx->d_T, ctx->width_bit,
-                       ctx->ht_size, reinterpret_cast<unsigned long long *>(ctx->bm2.p));
+    return PFAC_OK;
+}
+
+// ---- install, step 2: dense rows for the depth-1 states (children of the root), when there are few enough of them.
+// Rows are built in device memory in full, 256 columns; LDS takes the columns that have an edge in some row.  On fused
+// tables with few enough depth-2 states the rows are packed: an entry carries the index of its state's {r[], child mask}.
+int plan_dense_rows(pfac_ctx *ctx, TablePlan &P, const RootFan &root) {
+    ScanArgs &B = P.base;
+    const int n_rows = (root.fan >= 1 && root.fan <= 255 && !P.knobs.no_d1) ? root.fan : 0;
+    if (!n_rows) return PFAC_OK;
+    const size_t off_r2 = d1_off_r2(n_rows), off_col = d1_off_col(n_rows);
+    if (int rc = P.d1.ensure(ctx, nullptr, (off_col + 512) / 4, (off_col + 512) / 4)) return rc;
+    unsigned char *b = reinterpret_cast<unsigned char *>(P.d1.p);
+    int *d_state = reinterpret_cast<int *>(b + (size_t)n_rows * 1024 + 256);
+    HIP_TRY(ctx, hipMemcpy(b + (size_t)n_rows * 1024, root.idx, 256, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(d_state, root.state, (size_t)n_rows * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(pfac_build_d1_kernel, dim3(n_rows), dim3(256), 0, 0, d_state, B.r, B.T, B.wbit, B.ht_size, P.d1.p);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipDeviceSynchronize());
-    ctx->l2f_mode = 2;
-    ctx->bm2_rows = 256;
-    ctx->n_child = 0;
-    ctx->child0 = ctx->child1 = 0;
+    // which bytes are the second byte of some pattern: the LDS rows keep those columns only (host copy of the
+    // rows: at most 255 KiB); too many rows x columns for LDS: no dense level
+    std::vector<int> rows((size_t)n_rows * 256);
+    HIP_TRY(ctx, hipMemcpy(rows.data(), P.d1.p, rows.size() * 4, hipMemcpyDeviceToHost));
+    unsigned char colmap[256], colbyte[256];
+    int ncols = 0;
+    for (int c = 0; c < 256; c++) {
+        bool used = false;
+        for (int f = 0; f < n_rows && !used; f++) used = rows[(size_t)f * 256 + c] >= 0;
+        if (used) colbyte[ncols++] = (unsigned char)c;
+    }
+    const int stride = ncols < 256 ? ncols + 1 : 256;      // one more column, "no edge", unless every byte has its own
+    for (int c = 0; c < 256; c++) colmap[c] = (unsigned char)(ncols & 255);
+    for (int k = 0; k < ncols; k++) colmap[colbyte[k]] = (unsigned char)k;
+    if ((size_t)n_rows * stride * 4 > (size_t)D1_LDS_MAX) { P.d1.reset(); return PFAC_OK; }
+    HIP_TRY(ctx, hipMemcpy(b + off_col, colmap, 256, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(b + off_col + 256, colbyte, 256, hipMemcpyHostToDevice));
+    B.d1 = P.d1.p; B.d1idx = b + (size_t)n_rows * 1024; B.d1_colmap = b + off_col; B.d1_colbyte = b + off_col + 256;
+    B.d1_rows = n_rows; B.d1_stride = stride; B.d1_ncols = ncols;
+    B.d1_lds_bytes = (int)align_up((size_t)(n_rows + 1) * stride * 4, 16);   // (+ one row without edges)
+    if (!P.fused || P.state_num > (1 << D1_STATE_BITS) || P.knobs.no_d1pack) return PFAC_OK;
+    int n2 = 0;                                             // how many depth-2 states are there?
+    for (int v : rows) n2 += v >= 0;
+    if (n2 < 1 || n2 > D1_N2_MAX) return PFAC_OK;
+    int2 *r2 = reinterpret_cast<int2 *>(b + off_r2);
+    int *counter = reinterpret_cast<int *>(r2 + D1_N2_MAX);
+    HIP_TRY(ctx, hipMemset(counter, 0, 4));
+    hipLaunchKernelGGL(pfac_pack_d1_kernel, dim3((unsigned)n_rows), dim3(256), 0, 0, P.d1.p, n_rows * 256, B.r, B.T, B.wbit,
+                       B.ht_size, B.r_words, r2, counter);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    B.d1r2 = r2; B.d1_n2 = n2;
+    return PFAC_OK;
+}
+
+// ---- install, step 3: the level-2 filter.  The 2-byte-prefix bitmap is built on the device from the uploaded tables; a
+// single-edge root with at most two grandchildren gets the bit-parallel form (their bytes), everything else the lookup form
+int plan_l2_filter(pfac_ctx *ctx, TablePlan &P, const RootFan &root) {
+    ScanArgs &B = P.base;
+    if (int rc = P.bm2.ensure(ctx, nullptr, 256 * 32 + 256, 256 * 32 + 256)) return rc;   // bitmap + the second-byte flags
+    hipLaunchKernelGGL(pfac_build_bm2_kernel, dim3(256), dim3(256), 0, 0, B.s0, B.r, B.T, B.wbit, B.ht_size,
+                       reinterpret_cast<unsigned long long *>(P.bm2.p));
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    B.bm2 = P.bm2.p; B.sec2 = P.bm2.p + 256 * 32;
+    B.l2f_mode = 2; B.bm2_rows = 256;
     std::vector<unsigned char> bm2_host(256 * 32 + 256);
-    HIP_TRY(ctx, hipMemcpy(bm2_host.data(), ctx->bm2.p, 256 * 32, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(bm2_host.data(), P.bm2.p, 256 * 32, hipMemcpyDeviceToHost));
     for (int c = 0; c < 256; c++) {                         // column OR: can byte c be a pattern's second byte?
         unsigned char any = 0;
         for (int b0 = 0; b0 < 256; b0++) any |= (unsigned char)(bm2_host[(size_t)b0 * 32 + (c >> 3)] >> (c & 7) & 1);
         bm2_host[256 * 32 + c] = any;
     }
-    HIP_TRY(ctx, hipMemcpy(ctx->bm2.p + 256 * 32, bm2_host.data() + 256 * 32, 256, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(P.bm2.p + 256 * 32, bm2_host.data() + 256 * 32, 256, hipMemcpyHostToDevice));
     bool any_fin1 = false;                                  // a 1-byte pattern: its survivors are kept whatever follows
-    for (int i = 0; i < 256; i++) any_fin1 = any_fin1 || (s0_host[i] >= 0 && s0_host[i] < ctx->num_final);
-    ctx->sec_filter = (fan != 1 && !any_fin1 && !knob("PFAC_NO_SECF")) ? 1 : 0;
-    if (fan == 1) {
-        const unsigned char *row = bm2_host.data() + (size_t)rb * 32;
+    for (int i = 0; i < 256; i++) any_fin1 = any_fin1 || (root.s0[i] >= 0 && root.s0[i] < B.num_final);
+    B.sec_filter = (root.fan != 1 && !any_fin1 && !P.knobs.no_secf) ? 1 : 0;
+    if (root.fan == 1) {
+        const unsigned char *row = bm2_host.data() + (size_t)root.last * 32;
         int nch = 0, ch[2] = {0, 0};
         for (int c = 0; c < 256; c++)
             if (row[c >> 3] >> (c & 7) & 1) { if (nch < 2) ch[nch] = c; nch++; }
-        ctx->bm2_rows = 1;
+        B.bm2_rows = 1;
         if (nch <= 2) {
-            ctx->l2f_mode = 1;
-            ctx->n_child = nch;
-            ctx->child0 = (unsigned)ch[0] * 0x01010101u;
-            ctx->child1 = (unsigned)ch[nch > 1 ? 1 : 0] * 0x01010101u;
+            B.l2f_mode = 1; B.n_child = nch;
+            B.child0 = (unsigned)ch[0] * 0x01010101u;
+            B.child1 = (unsigned)ch[nch > 1 ? 1 : 0] * 0x01010101u;
         }
     }
     // multi-edge root without 1-byte patterns: when most (first byte, second byte) combinations of the flagged bytes
     // ARE 2-byte prefixes, the bitmap lookup would drop few of the survivors the second-byte flags let through -- they
     // all go to the walk instead (mode 3), whose dense depth-1 row is the same lookup done 64 lanes wide
-    if (fan != 1 && ctx->sec_filter) {
+    if (root.fan != 1 && B.sec_filter) {
         long pairs = 0, nsec = 0;
         for (int i = 0; i < 256 * 32; i++) pairs += __builtin_popcount(bm2_host[(size_t)i]);
         for (int c = 0; c < 256; c++) nsec += bm2_host[256 * 32 + c];
-        if (nsec > 0 && pairs * 100 >= (long)fan * nsec * PFAC_PAIR_DENSITY_PCT) ctx->l2f_mode = 3;
+        if (nsec > 0 && pairs * 100 >= (long)root.fan * nsec * PFAC_PAIR_DENSITY_PCT) B.l2f_mode = 3;
     }
-    const int l2f_env = env_int("PFAC_L2F", -1);          // 0: filter off; 2: lookup form even where the SWAR / flag-only form applies; 3: flags only
-    if (l2f_env == 0) ctx->l2f_mode = 0;
-    else if (l2f_env == 2) ctx->l2f_mode = 2;
-    else if (l2f_env == 3 && fan != 1 && ctx->sec_filter) ctx->l2f_mode = 3;
-    ctx->sh_bm2 = ctx->shared_bytes;
-    if (ctx->l2f_mode == 2) ctx->shared_bytes += ctx->bm2_rows * 32;
-    // knobs (tuning and tests), read once per table install
-    ctx->spin_max = (unsigned)env_int("PFAC_SPIN_MAX", (int)SPIN_MAX);
-    if (ctx->spin_max < 64) ctx->spin_max = 64;
-    ctx->fault = (unsigned)env_int("PFAC_FAULT", 0);
-    ctx->ticket_ways_knob = (unsigned)env_int("PFAC_TICKET_WAYS", 0);
-    ctx->trace_file = knob("PFAC_TRACE") ? knob("PFAC_TRACE") : "";
-    // the state histogram: a smaller LDS table (the cache regime and its collisions at small automata), a fixed grid
-    const int cbins = env_int("PFAC_COUNT_BINS", 0), cgrid = env_int("PFAC_COUNT_GRID", 0);
-    ctx->count_bins = cbins >= 1 && (unsigned)cbins <= COUNT_BINS_MAX ? (unsigned)cbins : 0u;
-    ctx->count_grid = cgrid >= 1 ? (unsigned)std::min(cgrid, 65536) : 0u;
-    const int cthreads = env_int("PFAC_COUNT_THREADS", 0);
-    ctx->count_threads = cthreads == 256 || cthreads == 512 || cthreads == 1024 ? (unsigned)cthreads : 0u;
-    // The two-buffer layout fixes the number of waves; LDS that no further wave fits into goes to the staging buffers
-    // (up to 1024 records per 4 KiB tile before it has to be walked a second time).  The three-buffer layout (emission
-    // at the top of the round, see NBUF_MAX) is used when it keeps that many waves with room for >= CAPW3_MIN records.
-    const int nwb_knob = env_int("PFAC_NWB", 0);
-    for (int nb = 2; nb <= NBUF_MAX; nb++) {
-        StageLayout &L = ctx->lay[nb - 2];
-        L.nbuf = nb;
-        L.pw_bytes = (int)align_up((size_t)PW_FIXED_1BUF + (size_t)nb * CAPW * 4 + ctx->halo, 16);
-        int nwb = (LDS_TOTAL - ctx->shared_bytes) / L.pw_bytes + 1;     // compute waves + the coordinator (no LDS region)
-        if (nb == 3) {                                                  // as many waves as with two buffers, smaller buffers if need be
-            nwb = ctx->lay[0].waves_per_block;
-            L.pw_bytes = (int)align_up((size_t)PW_FIXED_1BUF + ctx->halo, 16);
-        }
-        if (nwb > MAX_WAVES_PER_BLOCK) nwb = MAX_WAVES_PER_BLOCK;
-        if (nwb_knob > 0 && nwb_knob < nwb) nwb = nwb_knob;
-        if (nwb < 2) return fail(ctx, PFAC_E_INTERNAL, "LDS budget cannot hold one compute wave");
-        L.waves_per_block = nwb;
-        const int base_cap = nb == 3 ? 0 : CAPW;
-        const int spare = (LDS_TOTAL - ctx->shared_bytes) / (nwb - 1) - L.pw_bytes;         // bytes per compute wave
-        const int extra = spare > 0 ? (spare / (nb * 4)) & ~15 : 0;                         // records per staging buffer
-        unsigned cap = (unsigned)(base_cap + ((nwb_knob && nb == 2) ? 0 : extra));
-        if (cap > 1024u) cap = 1024u;
-        L.pw_bytes += (int)(cap - base_cap) * nb * 4;
-        L.stage_cap = cap;
-        L.lds_bytes = lds_of_one_block_per_cu(ctx->shared_bytes + (nwb - 1) * L.pw_bytes);
-    }
-    const int lag_knob = env_int("PFAC_LAG", 0);          // 1 / 2: pin the emission lag (tests, A/B runs)
-    ctx->lag2_ok = ctx->lay[1].stage_cap >= (unsigned)CAPW3_MIN && lag_knob != 1;
-    ctx->lag2 = ctx->lag2_ok;
-    ctx->lag_forced = lag_knob == 1 || lag_knob == 2;
-    ctx->grid_blocks = ctx->n_cu;
-    // root fan-out 1 -> exact SWAR root test (ROOT = 1), else LDS flag tables (ROOT = 0)
-    ctx->root_mode = fan == 1 ? 1 : 0;
-    ctx->root_byte = (unsigned)rb * 0x01010101u;
-    ctx->root_state = s0_host[rb];
-    // records are as wide as the automaton needs: 12 position bits + the final state
-    ctx->rec_bytes = ctx->num_final <= 16 ? 2 : (ctx->num_final <= (1 << PACK_STATE_BITS) ? 4 : 8);
-    const int rb_knob = env_int("PFAC_REC_BYTES", knob("PFAC_WIDE") ? 8 : 0);     // test knob: a WIDER form than needed
-    if ((rb_knob == 4 || rb_knob == 8) && rb_knob > ctx->rec_bytes) ctx->rec_bytes = rb_knob;
-    if (ctx->rec_bytes == 8) {                              // nothing is staged: every tile is written as it is walked
-        ctx->lay[0].stage_cap = ctx->lay[1].stage_cap = 0u;
-        ctx->lag2_ok = ctx->lag2 = false;
-    }
-    // dense-mode layout
-    ctx->dense2 = fused && !knob("PFAC_NO_NW4") && !knob("PFAC_NO_DENSE2") && ctx->d1_rows > 0 && ctx->d1_n2 > 0 &&
-                  ctx->num_final <= 65535 && ctx->rec_bytes == 4;
-    ctx->d2log_cap = D2_LOG_CAP;
-    const int d2cap_knob = env_int("PFAC_D2_LOGCAP", 0);     // test knob: tiles with more records than this take the fallback pass
-    if (d2cap_knob >= 16 && (unsigned)d2cap_knob < D2_LOG_CAP) ctx->d2log_cap = (unsigned)d2cap_knob;
-    StageLayout &D = ctx->lay_d;
-    D.nbuf = 1;
-    D.pw_bytes = (int)align_up((size_t)(ctx->dense2 ? PW_FIXED_DENSE2 : PW_FIXED_DENSE) + ctx->halo, 16);
-    int nwd = (LDS_TOTAL - ctx->shared_bytes) / D.pw_bytes + 1;
-    if (nwd > MAX_WAVES_PER_BLOCK) nwd = MAX_WAVES_PER_BLOCK;
-    D.waves_per_block = nwd;
-    D.lds_bytes = lds_of_one_block_per_cu(ctx->shared_bytes + (nwd - 1) * D.pw_bytes);
-    D.stage_cap = (nwd >= 4 && ctx->lay[0].stage_cap) ? (unsigned)CAPW_DENSE : 0u;   // 0: dense mode unavailable
-    ctx->dense_forced = knob("PFAC_DENSE") ? atoi(knob("PFAC_DENSE")) : -1;
-    ctx->dense = ctx->dense_forced == 1 && D.stage_cap;
-    const bool w8 = ctx->width_bit == 8;
-    ctx->T4_alloc.reset();
-    ctx->d_T4 = nullptr;
-    ctx->rn_bias = 0;
-    if (fused) {
-        std::vector<int> r_host((size_t)ctx->max_row);
-        HIP_TRY(ctx, hipMemcpy(r_host.data(), ctx->d_r, r_host.size() * 4, hipMemcpyDeviceToHost));
-        long long lo = 0, hi = ctx->ht_size;
-        for (int v : r_host) {
-            lo = v < lo ? v : lo;
-            hi = (long long)v + (1 << ctx->width_bit) > hi ? (long long)v + (1 << ctx->width_bit) : hi;
-        }
-        if (hi - lo >= (1ll << 28)) return fail(ctx, PFAC_E_ARG, "table image: more than 2^28 hash slots");
-        rc = ctx->T4_alloc.ensure(ctx, nullptr, (uint64_t)(hi - lo), (uint64_t)(hi - lo));
-        if (rc) return rc;
-        ctx->d_T4 = ctx->T4_alloc.p - lo;
-        ctx->rn_bias = (int)-lo;
-        hipLaunchKernelGGL(pfac_fuse_kernel, dim3(256), dim3(256), 0, 0, ctx->d_T, ctx->d_r, ctx->width_bit, ctx->ht_size,
-                           ctx->max_row, ctx->d_T4, (int)lo, (int)hi);
-        HIP_TRY(ctx, hipGetLastError());
-        HIP_TRY(ctx, hipDeviceSynchronize());
-    }
-    const int placement = ctx->variant == 0 ? 1 : (fused ? 2 : 0);
-    for (unsigned f = 0; f < 2; f++) {         // [1]: the twins that fold (pfac_table_set_case_fold chooses per launch)
-        ctx->kernel[f] = scan_kernel<2>(placement, w8, ctx->root_mode, f);
-        ctx->kernel_d[f] = ctx->kernel[f];
-        ctx->kernel3[f] = scan_kernel<3>(placement, w8, ctx->root_mode, f);
-        HIP_TRY(ctx, hipFuncSetAttribute(ctx->kernel3[f], hipFuncAttributeMaxDynamicSharedMemorySize, max_lds(ctx)));
-    }
-    // dense mode on fused L2 tables: four walks per lane (needs <= MAX_WAVES_NW4 waves per workgroup)
-    if (fused && !knob("PFAC_NO_NW4")) {
-        for (unsigned f = 0; f < 2; f++) ctx->kernel_d[f] = scan_kernel<2>(3, w8, ctx->root_mode, f);
-        if (!ctx->dense2 && D.waves_per_block > MAX_WAVES_NW4) {
-            D.waves_per_block = MAX_WAVES_NW4;
-            D.lds_bytes = lds_of_one_block_per_cu(ctx->shared_bytes + (MAX_WAVES_NW4 - 1) * D.pw_bytes);
-        }
-        for (unsigned f = 0; f < 2; f++)
-            HIP_TRY(ctx, hipFuncSetAttribute(ctx->kernel_d[f], hipFuncAttributeMaxDynamicSharedMemorySize, max_lds(ctx)));
-    }
-    for (unsigned f = 0; f < 2; f++)
-        HIP_TRY(ctx, hipFuncSetAttribute(ctx->kernel[f], hipFuncAttributeMaxDynamicSharedMemorySize, max_lds(ctx)));
-    if (knob("PFAC_VERBOSE"))
-        fprintf(stderr, "pfac: variant %d fused %d shared LDS %d B; sparse: %d waves x %d B; dense%s: %d waves x %d B; dense rows %d x %d, %d depth-2 states, level-2 filter mode %d\n",
-                ctx->variant, (int)fused, ctx->shared_bytes, ctx->lay[0].waves_per_block, ctx->lay[0].pw_bytes, ctx->dense2 ? " (second form)" : "",
-                D.waves_per_block, D.pw_bytes, ctx->d1_rows, ctx->d1_stride, ctx->d1_n2, ctx->l2f_mode);
+    if (P.knobs.l2f == 0) B.l2f_mode = 0;
+    else if (P.knobs.l2f == 2) B.l2f_mode = 2;
+    else if (P.knobs.l2f == 3 && root.fan != 1 && B.sec_filter) B.l2f_mode = 3;
     return PFAC_OK;
 }
 
-// d_blob: device-resident blob image; hdr: its first 16 words on the host
+// table bytes if staged in LDS: r (16-B rounded) + T
+size_t lds_table_bytes(const ScanArgs &B) { return align_up((size_t)B.r_words * 4, 16) + (size_t)B.ht_size * 8; }
+// one workgroup per CU: ask for more than half of the LDS so two never share a CU while another idles
+int lds_of_one_block_per_cu(int lds_bytes) { return lds_bytes < LDS_TOTAL / 2 + 256 ? LDS_TOTAL / 2 + 256 : lds_bytes; }
+
+// ---- install, step 4: the LDS carve -- plain arithmetic on what the steps before have put into the plan: no HIP call,
+// no environment.  First the region every wave of a workgroup shares (its offsets go to the kernel: shared_bytes, sh_t0,
+// sh_bm2), then one region per compute wave in each of the three staging modes.  False: not even one compute wave fits.
+bool plan_lds(TablePlan &P) {
+    ScanArgs &B = P.base;
+    const Knobs &K = P.knobs;
+    B.shared_bytes = SH_D1 + B.d1_lds_bytes + (P.variant == 0 ? (int)align_up(lds_table_bytes(B), 16) : (int)align_up((size_t)(B.d1_n2 ? B.d1_n2 + 1 : 0) * 8, 16));
+    if (P.fused && B.d1_rows == 0) B.shared_bytes += 1024;   // r[] of the depth-1 states by root byte
+    if (B.d1_n2 > 0) { B.sh_t0 = B.shared_bytes; B.shared_bytes += 1024; }   // dense mode, second form: its root table
+    B.sh_bm2 = B.shared_bytes;
+    if (B.l2f_mode == 2) B.shared_bytes += B.bm2_rows * 32;
+    // The two-buffer layout fixes the number of waves; LDS that no further wave fits into goes to the staging buffers
+    // (up to 1024 records per 4 KiB tile before it has to be walked a second time).  The three-buffer layout (emission
+    // at the top of the round, see NBUF_MAX) is used when it keeps that many waves with room for >= CAPW3_MIN records.
+    for (int nb = 2; nb <= NBUF_MAX; nb++) {
+        StageLayout &L = P.lay[nb - 2];
+        L.nbuf = nb;
+        L.pw_bytes = (int)align_up((size_t)PW_FIXED_1BUF + (size_t)nb * CAPW * 4 + B.halo, 16);
+        int nwb = (LDS_TOTAL - B.shared_bytes) / L.pw_bytes + 1;        // compute waves + the coordinator (no LDS region)
+        if (nb == 3) {                                                  // as many waves as with two buffers, smaller buffers if need be
+            nwb = P.lay[0].waves_per_block;
+            L.pw_bytes = (int)align_up((size_t)PW_FIXED_1BUF + B.halo, 16);
+        }
+        if (nwb > MAX_WAVES_PER_BLOCK) nwb = MAX_WAVES_PER_BLOCK;
+        if (K.nwb > 0 && K.nwb < nwb) nwb = K.nwb;
+        if (nwb < 2) return false;
+        L.waves_per_block = nwb;
+        const int base_cap = nb == 3 ? 0 : CAPW;
+        const int spare = (LDS_TOTAL - B.shared_bytes) / (nwb - 1) - L.pw_bytes;            // bytes per compute wave
+        const int extra = spare > 0 ? (spare / (nb * 4)) & ~15 : 0;                         // records per staging buffer
+        unsigned cap = (unsigned)(base_cap + ((K.nwb && nb == 2) ? 0 : extra));
+        if (cap > 1024u) cap = 1024u;
+        L.pw_bytes += (int)(cap - base_cap) * nb * 4;
+        L.stage_cap = cap;
+        L.lds_bytes = lds_of_one_block_per_cu(B.shared_bytes + (nwb - 1) * L.pw_bytes);
+    }
+    P.lag2_ok = P.lay[1].stage_cap >= (unsigned)CAPW3_MIN && K.lag != 1;
+    if (B.rec_bytes == 8) {                                 // nothing is staged: every tile is written as it is walked
+        P.lay[0].stage_cap = P.lay[1].stage_cap = 0u;
+        P.lag2_ok = false;
+    }
+    // dense-mode layout; on fused L2 tables it runs four walks per lane, which needs <= MAX_WAVES_NW4 waves per workgroup
+    StageLayout &D = P.lay_d;
+    D.nbuf = 1;
+    D.pw_bytes = (int)align_up((size_t)(P.dense2 ? PW_FIXED_DENSE2 : PW_FIXED_DENSE) + B.halo, 16);
+    int nwd = (LDS_TOTAL - B.shared_bytes) / D.pw_bytes + 1;
+    if (nwd > MAX_WAVES_PER_BLOCK) nwd = MAX_WAVES_PER_BLOCK;
+    D.stage_cap = (nwd >= 4 && P.lay[0].stage_cap) ? (unsigned)CAPW_DENSE : 0u;   // 0: dense mode unavailable
+    if (P.fused && !K.no_nw4 && !P.dense2 && nwd > MAX_WAVES_NW4) nwd = MAX_WAVES_NW4;
+    D.waves_per_block = nwd;
+    D.lds_bytes = lds_of_one_block_per_cu(B.shared_bytes + (nwd - 1) * D.pw_bytes);
+    return true;
+}
+
+// ---- install, step 5: tables via L2 and PHF width >= 256: fused slots, one gather per step
+int plan_fused_tables(pfac_ctx *ctx, TablePlan &P) {
+    if (!P.fused) return PFAC_OK;
+    ScanArgs &B = P.base;
+    std::vector<int> r_host((size_t)B.r_words);
+    HIP_TRY(ctx, hipMemcpy(r_host.data(), B.r, r_host.size() * 4, hipMemcpyDeviceToHost));
+    long long lo = 0, hi = B.ht_size;
+    for (int v : r_host) { lo = std::min<long long>(lo, v); hi = std::max(hi, (long long)v + (1 << B.wbit)); }
+    if (hi - lo >= (1ll << 28)) return fail(ctx, PFAC_E_ARG, "table image: more than 2^28 hash slots");
+    if (int rc = P.T4_alloc.ensure(ctx, nullptr, (uint64_t)(hi - lo), (uint64_t)(hi - lo))) return rc;
+    B.T4 = P.T4_alloc.p;
+    B.rn_bias = (int)-lo;
+    hipLaunchKernelGGL(pfac_fuse_kernel, dim3(256), dim3(256), 0, 0, B.T, B.r, B.wbit, B.ht_size, B.r_words, P.T4_alloc.p - lo,
+                       (int)lo, (int)hi);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    return PFAC_OK;
+}
+
+// ---- install, step 6: the kernels of this placement, hash width and root test, each allowed the largest LDS carve
+int plan_kernels(pfac_ctx *ctx, TablePlan &P) {
+    const bool w8 = P.base.wbit == 8;
+    const int placement = P.variant == 0 ? 1 : (P.fused ? 2 : 0);
+    const bool nw4 = P.fused && !P.knobs.no_nw4;           // dense mode on fused L2 tables: four walks per lane
+    for (unsigned f = 0; f < 2; f++) {         // [1]: the twins that fold (pfac_table_set_case_fold chooses per launch)
+        P.kernel[f] = scan_kernel<2>(placement, w8, P.root_mode, f);
+        P.kernel_d[f] = nw4 ? scan_kernel<2>(3, w8, P.root_mode, f) : P.kernel[f];
+        P.kernel3[f] = scan_kernel<3>(placement, w8, P.root_mode, f);
+        for (const void *k : {P.kernel3[f], P.kernel_d[f], P.kernel[f]})
+            HIP_TRY(ctx, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, P.max_lds()));
+    }
+    return PFAC_OK;
+}
+
+// The plan of one table image, every step in turn; any refusal leaves P to its caller, who drops it.
+int build_plan(pfac_ctx *ctx, TablePlan &P, const int *d_blob, const int32_t *hdr, hipStream_t stream) {
+    P.knobs = read_knobs();
+    RootFan root;
+    int rc = plan_tables(ctx, P, d_blob, hdr, stream, root);
+    if (rc) return rc;
+    ScanArgs &B = P.base;
+    P.variant = lds_table_bytes(B) <= (size_t)LDS_TABLE_MAX && !P.knobs.force_l2 ? 0 : 1;
+    P.fused = P.variant == 1 && B.wbit >= 8 && !P.knobs.no_fuse;
+    B.halo = ((P.max_pat_len > 1 ? P.max_pat_len - 1 : 0) + 15) & ~15;
+    // root fan-out 1 -> exact SWAR root test (ROOT = 1), else LDS flag tables (ROOT = 0)
+    P.root_mode = root.fan == 1 ? 1 : 0;
+    B.root_byte = (unsigned)root.last * 0x01010101u;
+    B.root_state = root.s0[root.last];
+    // records are as wide as the automaton needs: 12 position bits + the final state
+    B.rec_bytes = B.num_final <= 16 ? 2 : (B.num_final <= (1 << PACK_STATE_BITS) ? 4 : 8);
+    if ((P.knobs.rec_bytes == 4 || P.knobs.rec_bytes == 8) && (unsigned)P.knobs.rec_bytes > B.rec_bytes) B.rec_bytes = (unsigned)P.knobs.rec_bytes;
+    B.spin_max = P.knobs.spin_max; B.fault = P.knobs.fault;
+    P.grid_blocks = ctx->n_cu;
+    if ((rc = plan_dense_rows(ctx, P, root))) return rc;
+    if ((rc = plan_l2_filter(ctx, P, root))) return rc;
+    P.dense2 = P.fused && !P.knobs.no_nw4 && !P.knobs.no_dense2 && B.d1_rows > 0 && B.d1_n2 > 0 && B.num_final <= 65535 && B.rec_bytes == 4;
+    B.d2log_cap = P.knobs.d2_logcap >= 16 && (unsigned)P.knobs.d2_logcap < D2_LOG_CAP ? (unsigned)P.knobs.d2_logcap : D2_LOG_CAP;
+    if (!plan_lds(P)) return fail(ctx, PFAC_E_INTERNAL, "LDS budget cannot hold one compute wave");
+    B.sparse_cap = P.lay[0].stage_cap;     // tiles with more matches than these count towards the mode adaptation
+    B.small_cap = P.lay[P.lag2_ok ? 1 : 0].stage_cap;
+    if ((rc = plan_fused_tables(ctx, P))) return rc;
+    if ((rc = plan_kernels(ctx, P))) return rc;
+    if (P.knobs.verbose)
+        fprintf(stderr, "pfac: variant %d fused %d shared LDS %d B; sparse: %d waves x %d B; dense%s: %d waves x %d B; dense rows %d x %d, %d depth-2 states, level-2 filter mode %d\n",
+                P.variant, (int)P.fused, B.shared_bytes, P.lay[0].waves_per_block, P.lay[0].pw_bytes, P.dense2 ? " (second form)" : "",
+                P.lay_d.waves_per_block, P.lay_d.pw_bytes, B.d1_rows, B.d1_stride, B.d1_n2, B.l2f_mode);
+    return PFAC_OK;
+}
+
+// An upload.  A refused header leaves the installed table as it was.  Past the header checks the install is all or
+// nothing: the old plan and what the caller attached to it are dropped first (so the old tables are gone before the new
+// ones are allocated) and every earlier scan becomes one "made with an earlier table"; the new plan is built aside and
+// moved into the context only when every step has succeeded.  After a refusal the context has NO table.
 int install_table(pfac_ctx *ctx, const int *d_blob, const int32_t *hdr, size_t n_words, hipStream_t stream) {
     if (hdr[0] != PFAC_BLOB_MAGIC || hdr[1] != PFAC_BLOB_VERSION) return fail(ctx, PFAC_E_ARG, "not a PFAC table image");
     const int width = hdr[2], wbit = hdr[3], num_final = hdr[5], state_num = hdr[6], max_pat_len = hdr[7];
@@ -4464,43 +4511,19 @@ int install_table(pfac_ctx *ctx, const int *d_blob, const int32_t *hdr, size_t n
         return fail(ctx, PFAC_E_ARG, "inconsistent PFAC table image header");
     if ((int64_t)max_row < ((int64_t)state_num * 256 >> wbit) + 1)
         return fail(ctx, PFAC_E_ARG, "table image: r[] shorter than state_num*256/width+1");
-    const size_t off_r = 256 * 4;
-    const size_t off_T = align_up(off_r + (size_t)max_row * 4, 16);
-    const size_t off_id = off_T + (size_t)ht_size * 8;
-    const size_t total = align_up(off_id + (size_t)num_final * 4, 16) + 16;
     for (auto &sl : ctx->slots)                             // a scan still in flight reads the tables freed below
         if (sl.pending) { int rc = wait_scan(ctx, sl); if (rc) return rc; }
-    ctx->tab.reset();
-    ctx->flen.reset();                                      // the lengths belong to the old table
-    ctx->fold = PFAC_FOLD_NONE;                             // ... and so does the case fold
-    ctx->rep_off.reset();                                   // ... and so do the replacements
-    ctx->rep.reset();
-    int rc = ctx->tab.ensure(ctx, nullptr, total, total);
-    if (rc) return rc;
-    unsigned char *base = ctx->tab.p;
-    ctx->d_s0 = reinterpret_cast<int *>(base);
-    ctx->d_r = reinterpret_cast<int *>(base + off_r);
-    ctx->d_T = reinterpret_cast<int2 *>(base + off_T);
-    ctx->d_idmap = reinterpret_cast<int *>(base + off_id);
-    int *d_bad = reinterpret_cast<int *>(base + total - 16);
-    HIP_TRY(ctx, hipMemsetAsync(d_bad, 0, 4, stream));
-    hipLaunchKernelGGL(pfac_repack_kernel, dim3(256), dim3(256), 0, stream, d_blob, ctx->d_s0, ctx->d_r, ctx->d_T,
-                       ctx->d_idmap, max_row, ht_size, num_final, state_num, width, d_bad);
-    HIP_TRY(ctx, hipGetLastError());
-    int bad = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(ctx, hipStreamSynchronize(stream));
-    if (bad) {
-        ctx->have_table = false;
-        return fail(ctx, PFAC_E_ARG, "table image: a displacement or a state points outside the tables");
-    }
-    ctx->table_gen++;
-    ctx->width_bit = wbit; ctx->num_final = num_final; ctx->max_pat_len = max_pat_len;
-    ctx->max_row = max_row; ctx->ht_size = ht_size; ctx->state_num = state_num;
+    ctx->plan = TablePlan();
+    ctx->flen.reset(); ctx->fold = PFAC_FOLD_NONE;          // the lengths belong to the old table, and so does the case fold
+    ctx->rep_off.reset(); ctx->rep.reset();                 // ... and so do the replacements
+    ctx->have_table = false; ctx->table_gen++;
+    TablePlan P;
+    if (int rc = build_plan(ctx, P, d_blob, hdr, stream)) return rc;
+    ctx->plan = std::move(P);
+    ctx->dense = ctx->plan.knobs.dense == 1 && ctx->plan.lay_d.stage_cap;
+    ctx->lag2 = ctx->plan.lag2_ok;
     ctx->have_table = true;
-    int32_t s0_host[256];
-    HIP_TRY(ctx, hipMemcpy(s0_host, ctx->d_s0, sizeof s0_host, hipMemcpyDeviceToHost));
-    return configure_kernel(ctx, s0_host);
+    return PFAC_OK;
 }
 
 }  // namespace
@@ -4722,6 +4745,7 @@ int pfac_scan_async(pfac_ctx *ctx, int slot, const void *d_input, uint64_t n_own
     // dictionary's) before it asks the stream instead
     s.spin_ms = 2.0 + (double)n_owned / 50e6;
     // staging mode of this launch (see pfac_scan_finish for the adaptation)
+    const TablePlan &P = ctx->plan;
     const bool dense = ctx->run_dense();
     const StageLayout &L = ctx->layout(dense);
     const int wpb = L.waves_per_block;
@@ -4731,7 +4755,7 @@ int pfac_scan_async(pfac_ctx *ctx, int slot, const void *d_input, uint64_t n_own
     s.last_avail = n_avail;
     s.scan_seq++;
     s.last_table = ctx->table_gen;
-    s.last_rec_bytes = ctx->rec_bytes;
+    s.last_rec_bytes = (int)P.base.rec_bytes;
     s.last_records = d_records;
     // The control header (ticket counters, flags, heap cursor) must start at zero.  The slot has two: every scan
     // zeroes, in its own prologue, the other one for the scan after it, so back-to-back scans need no memset.
@@ -4743,60 +4767,32 @@ int pfac_scan_async(pfac_ctx *ctx, int slot, const void *d_input, uint64_t n_own
     unsigned *const cur = s.d_ctlbuf[s.flip], *const nxt = s.d_ctlbuf[1 - s.flip];
     if (n_tiles > 0 && !s.clean[s.flip]) HIP_TRY(ctx, hipMemsetAsync(cur, 0, CTL_REGION, s.stream));
     if (n_tiles > 0) {
-        ScanArgs a;
+        ScanArgs a = P.base;                   // what the table fixes; below, what this launch adds
         a.in = in; a.n_owned = n_owned; a.n_avail = n_avail;
         a.out = d_records; a.out_cap = capacity;
         a.tile_index = s.tile_index.p;
-        a.rec_bytes = (unsigned)ctx->rec_bytes;
-        a.l2f_mode = ctx->l2f_mode; a.child0 = ctx->child0; a.child1 = ctx->child1; a.n_child = ctx->n_child;
-        a.bm2 = ctx->bm2.p; a.bm2_rows = ctx->bm2_rows; a.sh_bm2 = ctx->sh_bm2; a.sh_t0 = ctx->sh_t0;
-        a.sec2 = ctx->bm2.p + 256 * 32; a.sec_filter = ctx->sec_filter;
-        a.spin_max = ctx->spin_max; a.fault = ctx->fault;
-        a.s0 = ctx->d_s0; a.r = ctx->d_r; a.T = ctx->d_T; a.T4 = ctx->T4_alloc.p; a.rn_bias = ctx->rn_bias;
-        a.r_words = ctx->max_row; a.t_entries = ctx->ht_size;
-        a.ht_size = ctx->ht_size; a.wbit = ctx->width_bit; a.num_final = ctx->num_final;
-        a.halo = ctx->halo;
-        a.shared_bytes = ctx->shared_bytes; a.pw_bytes = L.pw_bytes;
-        a.d1 = ctx->d1.p; a.d1_rows = ctx->d1_rows; a.d1_stride = ctx->d1_stride; a.d1_ncols = ctx->d1_ncols; a.d1_lds_bytes = ctx->d1_lds_bytes;
-        a.d1_colmap = ctx->d1.p ? reinterpret_cast<const unsigned char *>(ctx->d1.p) + d1_off_col(ctx->d1_rows) : nullptr;
-        a.d1_colbyte = a.d1_colmap ? a.d1_colmap + 256 : nullptr;
-        a.d1_n2 = ctx->d1_n2;
-        a.d1r2 = ctx->d1_n2 ? reinterpret_cast<const int2 *>(reinterpret_cast<const unsigned char *>(ctx->d1.p) + d1_off_r2(ctx->d1_rows))
-                            : nullptr;
-        a.d1idx = ctx->d1.p ? reinterpret_cast<const unsigned char *>(ctx->d1.p) + (size_t)ctx->d1_rows * 1024 : nullptr;
-        a.root_byte = ctx->root_byte;
-        a.root_state = ctx->root_state;
-        a.stage_cap = L.stage_cap;
-        a.nbuf = (unsigned)L.nbuf;
-        a.dense2 = dense && ctx->dense2 ? 1 : 0;
-        a.d2log = nullptr; a.d2log_cap = ctx->d2log_cap;
+        a.pw_bytes = L.pw_bytes; a.stage_cap = L.stage_cap; a.nbuf = (unsigned)L.nbuf;
+        a.dense2 = dense && P.dense2 ? 1 : 0;
         if (a.dense2) {
             a.stage_cap = 0;                   // (its LDS carve has no staging buffer: a tile it gives up on is counted, then written directly)
-            const size_t words = (size_t)ctx->grid_blocks * (size_t)(wpb - 1) * ctx->d2log_cap;
+            const size_t words = (size_t)P.grid_blocks * (size_t)(wpb - 1) * a.d2log_cap;
             rc = s.d2log.ensure(ctx, s.stream, words, words);
             if (rc) return rc;
             a.d2log = s.d2log.p;
         }
-        a.sparse_cap = ctx->lay[0].stage_cap;
-        a.small_cap = ctx->lag2_ok ? ctx->lay[1].stage_cap : ctx->lay[0].stage_cap;
-        a.n_tiles = (unsigned)n_tiles;
-        a.ctl = cur;
-        a.zero_next = reinterpret_cast<uint4 *>(nxt);
-        a.zero_vec = (unsigned)(CTL_REGION / 16);
-        a.res = s.d_res;
-        a.dbg = nullptr;
+        a.n_tiles = (unsigned)n_tiles; a.ctl = cur; a.res = s.d_res;
+        a.zero_next = reinterpret_cast<uint4 *>(nxt); a.zero_vec = (unsigned)(CTL_REGION / 16);
 #ifdef PFAC_TRACE_BUILD
-        if (!ctx->trace_file.empty()) {
+        if (!P.knobs.trace_file.empty()) {
             rc = s.dbg.ensure(ctx, s.stream, 8 * 64 * 32, 8 * 64 * 32);
             if (rc) return rc;
             HIP_TRY(ctx, hipMemsetAsync(s.dbg.p, 0, 8 * 64 * 32 * 8, s.stream));
             a.dbg = s.dbg.p;
         }
 #endif
-        const uint64_t want = n_batches;
-        uint64_t grid = (uint64_t)ctx->grid_blocks < want ? (uint64_t)ctx->grid_blocks : want;
+        const uint64_t grid = std::min<uint64_t>((uint64_t)P.grid_blocks, n_batches);
         a.ticket_ways = grid < TICKET_WAYS ? (unsigned)grid : TICKET_WAYS;
-        if (ctx->ticket_ways_knob >= 1 && ctx->ticket_ways_knob < a.ticket_ways) a.ticket_ways = ctx->ticket_ways_knob;
+        if (P.knobs.ticket_ways >= 1 && P.knobs.ticket_ways < a.ticket_ways) a.ticket_ways = P.knobs.ticket_ways;
         // heap chunk: 1/32 of an even share of the record array per workgroup -- the current and the spare chunk of
         // every workgroup can stay unfilled at the end, i.e. at most 1/16 of the capacity; record arrays too small for
         // chunks of 1024 records get exact allocations (one atomic per batch)
@@ -4808,8 +4804,8 @@ int pfac_scan_async(pfac_ctx *ctx, int slot, const void *d_input, uint64_t n_own
         // A plain dispatch: no completion signal, no timestamps (a dispatch that carries them makes the command processor
         // retire the kernel, fence, write both and signal before it looks at the next packet).  Completion is the H_DONE
         // word and the time is the kernel's own.  PFAC_EVENT_TIMING: both events ride on the dispatch itself (null otherwise).
-        HIP_TRY(ctx, hipExtLaunchKernel(dense ? ctx->kernel_d[fold] : (ctx->lag2 ? ctx->kernel3[fold] : ctx->kernel[fold]), dim3((unsigned)grid),
-                                        dim3(WAVE * wpb), kargs, (size_t)L.lds_bytes, s.stream, s.ev0, s.ev1, 0));
+        HIP_TRY(ctx, hipExtLaunchKernel(P.kernel_of(dense, ctx->lag2, fold), dim3((unsigned)grid), dim3(WAVE * wpb), kargs,
+                                        (size_t)L.lds_bytes, s.stream, s.ev0, s.ev1, 0));
         s.clean[s.flip] = false;               // used by this scan
         s.clean[1 - s.flip] = true;            // zeroed by this scan
         s.flip = 1 - s.flip;
@@ -4837,10 +4833,10 @@ int pfac_scan_finish(pfac_ctx *ctx, int slot, uint64_t *n_matches) {
     s.last_used = host_u64(s, H_USED);
     if (n_matches) *n_matches = total;
 #ifdef PFAC_TRACE_BUILD
-    if (s.dbg.p && !ctx->trace_file.empty()) {
+    if (s.dbg.p && !ctx->plan.knobs.trace_file.empty()) {
         std::vector<unsigned long long> h(8 * 64 * 32);
         if (hipMemcpy(h.data(), s.dbg.p, h.size() * 8, hipMemcpyDeviceToHost) == hipSuccess) {
-            if (FILE *f = fopen(ctx->trace_file.c_str(), "wb")) { fwrite(h.data(), 8, h.size(), f); fclose(f); }
+            if (FILE *f = fopen(ctx->plan.knobs.trace_file.c_str(), "wb")) { fwrite(h.data(), 8, h.size(), f); fclose(f); }
         }
     }
 #endif
@@ -4854,12 +4850,12 @@ int pfac_scan_finish(pfac_ctx *ctx, int slot, uint64_t *n_matches) {
     // when fewer than 1/16 do.  PFAC_DENSE=0/1 pins the mode.  Likewise between the three- and the two-buffer layout,
     // on the tiles above the (smaller) three-buffer capacity: 1/16 of the tiles walked twice cost what the earlier
     // emission gains.  PFAC_LAG=1/2 pins that.
-    if (ctx->dense_forced < 0 && ctx->lay_d.stage_cap && s.last_tiles >= 64) {
+    if (ctx->plan.knobs.dense < 0 && ctx->plan.lay_d.stage_cap && s.last_tiles >= 64) {
         const uint64_t ovf = s.h_ctl[3];
         if (!ctx->dense && ovf * 4 > s.last_tiles) ctx->dense = true;
         else if (ctx->dense && ovf * 16 < s.last_tiles) ctx->dense = false;
     }
-    if (ctx->lag2_ok && !ctx->lag_forced && s.last_tiles >= 64) {
+    if (ctx->plan.lag2_ok && ctx->plan.knobs.lag != 1 && ctx->plan.knobs.lag != 2 && s.last_tiles >= 64) {
         const uint64_t ovf2 = s.h_ctl[6];
         if (ctx->lag2 && ovf2 * 16 > s.last_tiles) ctx->lag2 = false;
         else if (!ctx->lag2 && ovf2 * 64 < s.last_tiles) ctx->lag2 = true;
@@ -5018,7 +5014,7 @@ int pfac_emit_text_device(pfac_ctx *ctx, int slot, const void *d_records, uint64
     const unsigned gblocks = (n_groups + 3) / 4;           // four waves (groups of 64 tiles) per 256-thread block
     auto sk = by_width(s.last_rec_bytes, [](auto w) { return pfac_text_size_kernel<w()>; });
     hipLaunchKernelGGL(sk, dim3(gblocks), dim3(256), 0, s.stream, src, s.tile_index.p, (unsigned long long)s.last_tiles,
-                       (unsigned long long)s.last_cap, (unsigned long long)base, ctx->d_idmap, s.gsum.p, n_groups);
+                       (unsigned long long)s.last_cap, (unsigned long long)base, ctx->plan.d_idmap, s.gsum.p, n_groups);
     hipLaunchKernelGGL(pfac_scan_groups_kernel, dim3(1), dim3(1024), 0, s.stream, s.gsum.p, n_groups);
     HIP_TRY(ctx, hipGetLastError());
     unsigned long long total = 0;
@@ -5028,7 +5024,7 @@ int pfac_emit_text_device(pfac_ctx *ctx, int slot, const void *d_records, uint64
     if (rc) return rc;
     auto fk = by_width(s.last_rec_bytes, [](auto w) { return pfac_text_format_kernel<w()>; });
     hipLaunchKernelGGL(fk, dim3(gblocks), dim3(256), 0, s.stream, src, s.tile_index.p, (unsigned long long)s.last_tiles,
-                       (unsigned long long)s.last_cap, (unsigned long long)base, ctx->d_idmap, s.gsum.p, n_groups, s.text.p);
+                       (unsigned long long)s.last_cap, (unsigned long long)base, ctx->plan.d_idmap, s.gsum.p, n_groups, s.text.p);
     HIP_TRY(ctx, hipGetLastError());
     s.text_bytes = total;
     *n_bytes = total;
@@ -5073,7 +5069,7 @@ int pfac_records_checksum(pfac_ctx *ctx, int slot, const void *d_records, uint64
     if (n && s.last_tiles) {
         auto ck = by_width(s.last_rec_bytes, [](auto w) { return pfac_checksum_kernel<w()>; });
         hipLaunchKernelGGL(ck, dim3(1024), dim3(256), 0, s.stream, src, s.tile_index.p, (unsigned long long)s.last_tiles,
-                           (unsigned long long)s.last_cap, (unsigned long long)base, ctx->d_idmap, s.sum.p);
+                           (unsigned long long)s.last_cap, (unsigned long long)base, ctx->plan.d_idmap, s.sum.p);
         HIP_TRY(ctx, hipGetLastError());
     }
     HIP_TRY(ctx, hipMemcpyAsync(s.h_ctl + H_CHECKSUM, s.sum.p, 8, hipMemcpyDeviceToHost, s.stream));
@@ -5095,8 +5091,8 @@ using CountKernel = void (*)(const void *, const unsigned long long *, unsigned 
 int count_run(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *heap, bool is_sel, const pfac_record *sel, uint64_t n_sel,
               bool check_sel, uint64_t *d_counts, uint64_t n_states, uint32_t flags, uint64_t *n_counted) {
     if (flags > PFAC_COUNT_ACCUMULATE) return fail(ctx, PFAC_E_ARG, fn + ": flags must be 0 or PFAC_COUNT_ACCUMULATE");
-    if (n_states != (uint64_t)ctx->num_final)
-        return fail(ctx, PFAC_E_ARG, fn + ": n_states must be num_final of the uploaded table (" + std::to_string(ctx->num_final) + ")");
+    if (n_states != (uint64_t)ctx->plan.base.num_final)
+        return fail(ctx, PFAC_E_ARG, fn + ": n_states must be num_final of the uploaded table (" + std::to_string(ctx->plan.base.num_final) + ")");
     if ((uintptr_t)d_counts & 7) return fail(ctx, PFAC_E_ARG, fn + ": d_counts must be 8-byte aligned");
     const bool own = d_counts == nullptr, acc = (flags & PFAC_COUNT_ACCUMULATE) != 0;
     if (own && acc && s.cnt.done && s.cnt_table != ctx->table_gen)
@@ -5125,8 +5121,8 @@ int count_run(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *heap, b
     if (zero && n_states) HIP_TRY(ctx, hipMemsetAsync(dst, 0, n_states * 8, s.stream));
     if (n_items && n_states) {
         // a direct table while the states fit it, else the cache
-        const bool direct = ns <= (ctx->count_bins ? std::min(ctx->count_bins, COUNT_DIRECT_MAX) : COUNT_DIRECT_MAX);
-        const unsigned bins = ctx->count_bins ? ctx->count_bins : COUNT_CACHE_SLOTS;
+        const bool direct = ns <= (ctx->plan.knobs.count_bins ? std::min(ctx->plan.knobs.count_bins, COUNT_DIRECT_MAX) : COUNT_DIRECT_MAX);
+        const unsigned bins = ctx->plan.knobs.count_bins ? ctx->plan.knobs.count_bins : COUNT_CACHE_SLOTS;
         const size_t lds = direct ? (size_t)ns * 4 : (size_t)bins * 8;
         // The grid.  Direct table: workgroups of four waves, as many per CU as their LDS lets be resident, eight at
         // most (the loads of 32 waves hide the heap's latency).  Cache: ONE workgroup of sixteen waves per CU with
@@ -5135,10 +5131,10 @@ int count_run(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *heap, b
         // section 12).  Never fewer than two workgroups (the bound of a workgroup's 32-bit partials, see the
         // kernel), never more than there is work for.
         const unsigned per_cu = direct ? (unsigned)std::min<size_t>(8, LDS_TOTAL / std::max<size_t>(lds, 1)) : 1u;
-        const unsigned threads = ctx->count_threads ? ctx->count_threads : (unsigned)(direct ? COUNT_THREADS : COUNT_THREADS_MAX);
+        const unsigned threads = ctx->plan.knobs.count_threads ? ctx->plan.knobs.count_threads : (unsigned)(direct ? COUNT_THREADS : COUNT_THREADS_MAX);
         const uint64_t wanted = (n_items + threads / WAVE - 1) / (threads / WAVE);
         unsigned grid = (unsigned)std::min<uint64_t>(wanted, (uint64_t)per_cu * (unsigned)std::max(ctx->n_cu, 1));
-        if (ctx->count_grid) grid = ctx->count_grid;
+        if (ctx->plan.knobs.count_grid) grid = ctx->plan.knobs.count_grid;
         if (grid < 2) grid = 2;
         CountKernel k = direct ? pfac_count_kernel<0, true> : pfac_count_kernel<0, false>;
         if (!is_sel) k = by_width(s.last_rec_bytes, [direct](auto w) -> CountKernel { return direct ? pfac_count_kernel<w(), true> : pfac_count_kernel<w(), false>; });
@@ -5211,7 +5207,7 @@ int pfac_table_set_final_lengths(pfac_ctx *ctx, const int32_t *len, size_t n) {
     if (!ctx) return fail(nullptr, PFAC_E_ARG, "null context");
     std::lock_guard<std::mutex> lk(ctx->mu);
     if (!ctx->have_table) return fail(ctx, PFAC_E_STATE, "pfac_table_set_final_lengths before a table upload");
-    if (n != (size_t)ctx->num_final || (!len && n)) return fail(ctx, PFAC_E_ARG, "pfac_table_set_final_lengths: need num_final lengths");
+    if (n != (size_t)ctx->plan.base.num_final || (!len && n)) return fail(ctx, PFAC_E_ARG, "pfac_table_set_final_lengths: need num_final lengths");
     std::vector<short> h(n ? n : 1, (short)-1);
     for (size_t i = 0; i < n; i++) {
         if (len[i] != -1 && (len[i] < 1 || len[i] > 1024))
@@ -5361,7 +5357,7 @@ int pfac_records_segment(pfac_ctx *ctx, int slot, const void *d_records, const u
     auto ck = by_width(rb, [](auto w) { return pfac_seg_count_kernel<w()>; });
     hipLaunchKernelGGL(ck, dim3(cblocks), dim3(256), 0, s.stream, src, s.tile_index.p, (unsigned long long)n_tiles,
                        (unsigned long long)s.last_cap, off, (unsigned long long)n_docs, (unsigned long long)s.last_owned,
-                       ctx->flen.p, (unsigned)ctx->num_final, s.seg_tcnt.p, s.gsum.p, n_groups, s.gsum.p + n_groups + 1);
+                       ctx->flen.p, (unsigned)ctx->plan.base.num_final, s.seg_tcnt.p, s.gsum.p, n_groups, s.gsum.p + n_groups + 1);
     if (n_groups) hipLaunchKernelGGL(pfac_scan_groups_kernel, dim3(1), dim3(1024), 0, s.stream, s.gsum.p, n_groups);
     rc = pass_words(ctx, s, s.gsum.p + n_groups, 2);
     if (rc) return rc;
@@ -5378,7 +5374,7 @@ int pfac_records_segment(pfac_ctx *ctx, int slot, const void *d_records, const u
     if (n_groups) {
         auto wk = by_width(rb, [](auto w) { return pfac_seg_write_kernel<w()>; });
         hipLaunchKernelGGL(wk, dim3((unsigned)gblocks), dim3(256), 0, s.stream, src, s.tile_index.p, (unsigned long long)n_tiles,
-                           (unsigned long long)s.last_cap, off, (unsigned long long)n_docs, ctx->flen.p, (unsigned)ctx->num_final, s.seg_tcnt.p, s.gsum.p,
+                           (unsigned long long)s.last_cap, off, (unsigned long long)n_docs, ctx->flen.p, (unsigned)ctx->plan.base.num_final, s.seg_tcnt.p, s.gsum.p,
                            n_groups, out, first);
         HIP_TRY(ctx, hipGetLastError());
     } else {
@@ -5403,7 +5399,7 @@ static void launch_offsets_check(pfac_ctx *ctx, Slot &s, const unsigned long lon
     const unsigned vblocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_docs + 255) / 256, 4096));
     hipLaunchKernelGGL(pfac_seg_count_kernel<4>, dim3(vblocks), dim3(256), 0, s.stream, (const void *)nullptr,
                        (const unsigned long long *)nullptr, 0ull, 0ull, off, (unsigned long long)n_docs,
-                       (unsigned long long)s.last_owned, ctx->flen.p, (unsigned)ctx->num_final, (unsigned *)nullptr,
+                       (unsigned long long)s.last_owned, ctx->flen.p, (unsigned)ctx->plan.base.num_final, (unsigned *)nullptr,
                        (unsigned long long *)nullptr, 0u, bad);
 }
 
@@ -5624,7 +5620,7 @@ int pfac_records_filter_words(pfac_ctx *ctx, int slot, const void *d_input, void
         const bool dk = n_docs != 0;
         auto fk = by_width(s.last_rec_bytes, [dk](auto w) { return dk ? pfac_filter_words_kernel<w(), true> : pfac_filter_words_kernel<w(), false>; });
         hipLaunchKernelGGL(fk, dim3((n_groups + 3) / 4), dim3(256), 0, s.stream, heap, s.tile_index.p, (unsigned long long)n_tiles,
-                           (unsigned long long)s.last_cap, in, (unsigned long long)s.last_avail, ctx->flen.p, (unsigned)ctx->num_final,
+                           (unsigned long long)s.last_cap, in, (unsigned long long)s.last_avail, ctx->flen.p, (unsigned)ctx->plan.base.num_final,
                            ws, (unsigned)edges, prev_byte, next_byte, off, (unsigned long long)n_docs,
                            (const unsigned long long *)(res + 1), res);
     }
@@ -5660,7 +5656,7 @@ static int ll_select(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *
     if (rc) return rc;
     // (PFAC_E_STATE, as pfac.h documents for the selections; the other passes report PFAC_E_OVERFLOW)
     if (s.last_used > s.last_cap) return fail(ctx, PFAC_E_STATE, fn + ": the slot's last scan overflowed its record heap");
-    const unsigned M = (unsigned)ctx->max_pat_len;
+    const unsigned M = (unsigned)ctx->plan.max_pat_len;
     if (entry > M) return fail(ctx, PFAC_E_ARG, fn + ": entry " + std::to_string(entry) + " exceeds max_pat_len " + std::to_string(M));
     const int rb = s.last_rec_bytes;
     const void *src = d_records ? d_records : s.records.p;
@@ -5727,14 +5723,14 @@ static int ll_select(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *
     HIP_TRY(ctx, hipFuncSetAttribute((const void *)mk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const unsigned long long nt = n_tiles, cap = s.last_cap, own = s.last_owned, nd = n_docs;
     hipLaunchKernelGGL(fk, dim3(n_groups), dim3(LL_WAVES * WAVE), lds, s.stream, src, s.tile_index.p, nt, cap, own, ctx->flen.p,
-                       (unsigned)ctx->num_final, M, gfun, (const unsigned short *)nullptr, bits, tcnt, s.gsum.p, off, nd, bad);
+                       (unsigned)ctx->plan.base.num_final, M, gfun, (const unsigned short *)nullptr, bits, tcnt, s.gsum.p, off, nd, bad);
     hipLaunchKernelGGL(pfac_ll_compose_kernel, dim3(nb), dim3(1024), LL_CHUNK_BYTES, s.stream, gfun, M1, n_groups, (unsigned)XGROUP, hfun);
     hipLaunchKernelGGL(pfac_ll_walk_kernel, dim3(1), dim3(256), LL_CHUNK_BYTES, s.stream, hfun, M1, nb, nb, (const unsigned short *)nullptr,
                        (unsigned)entry, hat, s.gsum.p + n_groups + 1);
     hipLaunchKernelGGL(pfac_ll_walk_kernel, dim3(nb), dim3(256), LL_CHUNK_BYTES, s.stream, gfun, M1, n_groups, (unsigned)XGROUP,
                        (const unsigned short *)hat, 0u, gat, (unsigned long long *)nullptr);
     hipLaunchKernelGGL(mk, dim3(n_groups), dim3(LL_WAVES * WAVE), lds, s.stream, src, s.tile_index.p, nt, cap, own, ctx->flen.p,
-                       (unsigned)ctx->num_final, M, (unsigned short *)nullptr, (const unsigned short *)gat, bits, tcnt, s.gsum.p,
+                       (unsigned)ctx->plan.base.num_final, M, (unsigned short *)nullptr, (const unsigned short *)gat, bits, tcnt, s.gsum.p,
                        off, nd, (unsigned long long *)nullptr);
     hipLaunchKernelGGL(pfac_scan_groups_kernel, dim3(1), dim3(1024), 0, s.stream, s.gsum.p, n_groups);
     rc = pass_words(ctx, s, s.gsum.p + n_groups, docs ? 3 : 2);
@@ -5756,7 +5752,7 @@ static int ll_select(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *
         if (rc) return rc;
         auto wk = by_width(rb, [](auto w) { return pfac_ll_doc_write_kernel<w()>; });
         hipLaunchKernelGGL(wk, dim3((n_groups + 3) / 4), dim3(256), 0, s.stream, src, s.tile_index.p, nt, cap, off, nd, ctx->flen.p,
-                           (unsigned)ctx->num_final, bits, tcnt, s.gsum.p, n_groups, out, first);
+                           (unsigned)ctx->plan.base.num_final, bits, tcnt, s.gsum.p, n_groups, out, first);
         HIP_TRY(ctx, hipGetLastError());
     } else if (total) {
         auto wk = by_width(rb, [](auto w) { return pfac_ll_write_kernel<w()>; });
@@ -5812,8 +5808,8 @@ int pfac_table_set_replacements(pfac_ctx *ctx, const uint32_t *offsets, uint64_t
     if (!ctx) return fail(nullptr, PFAC_E_ARG, "null context");
     std::lock_guard<std::mutex> lk(ctx->mu);
     if (!ctx->have_table) return fail(ctx, PFAC_E_STATE, "pfac_table_set_replacements before a table upload");
-    if (n_states != (uint64_t)ctx->num_final || !offsets || (!bytes && n_bytes))
-        return fail(ctx, PFAC_E_ARG, "pfac_table_set_replacements: need num_final + 1 offsets (num_final " + std::to_string(ctx->num_final) + ")");
+    if (n_states != (uint64_t)ctx->plan.base.num_final || !offsets || (!bytes && n_bytes))
+        return fail(ctx, PFAC_E_ARG, "pfac_table_set_replacements: need num_final + 1 offsets (num_final " + std::to_string(ctx->plan.base.num_final) + ")");
     if (n_bytes >= (1ull << 32)) return fail(ctx, PFAC_E_ARG, "pfac_table_set_replacements: n_bytes must be below 2^32");
     for (uint64_t i = 0; i < n_states; i++) {
         if (offsets[i + 1] < offsets[i] || offsets[i + 1] > n_bytes)
@@ -5894,7 +5890,7 @@ static int rp_run(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *d_i
         HIP_TRY(ctx, hipMemsetAsync(res, 0, 16, s.stream));
         hipLaunchKernelGGL(pfac_rp_count_kernel, dim3((unsigned)n_groups), dim3(RP_GROUP / 4 * WAVE), 0, s.stream, sel,
                            (unsigned long long)n, (unsigned long long)entry, (unsigned long long)n_owned, ctx->flen.p,
-                           ctx->rep_off.p, (unsigned)ctx->num_final, X, s.gsum.p, res);
+                           ctx->rep_off.p, (unsigned)ctx->plan.base.num_final, X, s.gsum.p, res);
         hipLaunchKernelGGL(pfac_scan_groups_kernel, dim3(1), dim3(1024), 0, s.stream, s.gsum.p, (unsigned)n_groups);
         rc = pass_words(ctx, s, s.gsum.p + n_groups, 3);
         if (rc) return rc;
@@ -6012,9 +6008,9 @@ int pfac_fill_random(pfac_ctx *ctx, int slot, void *d_dst, uint64_t n, uint64_t 
 int pfac_scan_info(pfac_ctx *ctx, int *variant, int *tile_bytes, int *grid_blocks, int *lds_bytes) {
     if (!ctx) return fail(nullptr, PFAC_E_ARG, "null context");
     if (!ctx->have_table) return fail(ctx, PFAC_E_STATE, "no table uploaded");
-    if (variant) *variant = ctx->variant;
+    if (variant) *variant = ctx->plan.variant;
     if (tile_bytes) *tile_bytes = WTILE;
-    if (grid_blocks) *grid_blocks = ctx->grid_blocks;
+    if (grid_blocks) *grid_blocks = ctx->plan.grid_blocks;
     if (lds_bytes) *lds_bytes = ctx->layout(ctx->run_dense()).lds_bytes;
     return PFAC_OK;
 }
@@ -6026,7 +6022,7 @@ int pfac_scan_staging(pfac_ctx *ctx, int *buffers, uint32_t *records_per_buffer)
     const StageLayout &L = ctx->layout(dense);
     if (buffers) *buffers = L.nbuf;
     // (dense mode's second form has no staging buffer: what bounds a tile there is the wave's record log)
-    if (records_per_buffer) *records_per_buffer = dense && ctx->dense2 ? ctx->d2log_cap : L.stage_cap;
+    if (records_per_buffer) *records_per_buffer = dense && ctx->plan.dense2 ? ctx->plan.base.d2log_cap : L.stage_cap;
     return PFAC_OK;
 }
 

@@ -1,5 +1,5 @@
 """Seeded pattern sets whose automata sit exactly at the bit-width limits of the scan's packed words (include/pfac.h,
-phfpfac_amd/csrc/pfac_hip.hip configure_kernel, pfac_table.c's size check), and the inputs that drive them.
+phfpfac_amd/csrc/pfac_hip.hip build_plan, pfac_table.c's size check), and the inputs that drive them.
 
 What the generators rely on (pfac_table.c build_from_patterns):
 - the final states are 0..F-1 in sorted pattern order (F = lines, duplicates included), so the greatest pattern owns

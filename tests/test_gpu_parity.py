@@ -11,6 +11,7 @@ import pytest
 
 from orc import Oracle, match_checksum
 from phfpfac_amd import GpuMatcher, PfacError, PfacTable, emit_records
+from phfpfac_amd._ffi import PFAC_E_ARG, PFAC_E_STATE
 from phfpfac_amd.matcher import splitmix64_bytes, tiled_bytes, trace_table_compat
 
 pytestmark = pytest.mark.gpu
@@ -946,12 +947,18 @@ def test_staging_layout_follows_the_match_density(tmp_path):
         assert seen == [3, 2, 2, 3, 3, 1, 2, 3], seen
 
 
-def test_malformed_table_image_is_refused_at_upload(resolve):
-    """The fused walk indexes its slot array unchecked (the array is padded to every index a well-formed image can
-    produce), so an image whose next states, root states or row displacements point outside the tables must not get
-    onto the device: the upload checks them all (pfac_repack_kernel) and fails with PFAC_E_ARG."""
+@pytest.fixture(scope="module")
+def xaa_case(resolve):
+    """The xaa table, its image, the first 50 001 bytes of the 1 MB input and the oracle's matches in them: the upload tests
+    below share them."""
     table = PfacTable.from_file(resolve("xaa"), 256)
-    blob = np.array(table.blob(), dtype=np.int32)
+    data = open(resolve("1M"), "rb").read()[:50001]
+    pos, ids = oracle_pairs(resolve("xaa"), data)
+    return table, np.array(table.blob(), dtype=np.int32), data, pos, ids
+
+
+def device_refused_images(blob):
+    """Images with a sound header that pfac_repack_kernel refuses on the device."""
     max_row, ht = int(blob[8]), int(blob[9])
     base_r, base_ht = 16 + 256, 16 + 256 + max_row
     owned = np.flatnonzero(blob[base_ht:base_ht + ht] >= 0)
@@ -960,15 +967,105 @@ def test_malformed_table_image_is_refused_at_upload(resolve):
     b = blob.copy(); b[16 + ord("a")] = 1 << 30; bad_images.append(b)                                       # a root edge to nowhere
     b = blob.copy(); b[base_r + 1] = ht + 7; bad_images.append(b)                                           # a row displaced past the table
     b = blob.copy(); b[base_r + 2] = -(1 << 20); bad_images.append(b)                                       # ... or far before it
+    return bad_images
+
+
+def raises_state(call):
+    with pytest.raises(PfacError) as e:
+        call()
+    assert e.value.status == PFAC_E_STATE, e.value
+
+
+def test_malformed_table_image_is_refused_at_upload(xaa_case):
+    """The fused walk indexes its slot array unchecked (the array is padded to every index a well-formed image can
+    produce), so an image whose next states, root states or row displacements point outside the tables must not get
+    onto the device: the upload checks them all (pfac_repack_kernel) and fails with PFAC_E_ARG."""
+    table, blob, data, pos, ids = xaa_case
     with GpuMatcher(0, 1) as g:
-        for b in bad_images:
+        for b in device_refused_images(blob):
             with pytest.raises(PfacError, match="outside the tables"):
                 g.load_table(b)
         g.load_table(blob)                                                                                   # the image itself is fine
-        data = open(resolve("1M"), "rb").read()[:50001]
         rec = g.scan_bytes(data)
-    pos, ids = oracle_pairs(resolve("xaa"), data)
     assert_same(table, rec, pos, ids)
+
+
+def test_device_refused_image_leaves_no_table(xaa_case):
+    """An install is all or nothing: an image refused past its header (here by pfac_repack_kernel, after the old tables
+    have been freed) leaves the context WITHOUT a table -- scans, info and the setters say PFAC_E_STATE -- and the scan made
+    before it is one "made with an earlier table": its records are still fetched, the passes that need the table on the
+    device say PFAC_E_STATE.  The next good upload starts clean: the case fold is off, the scan equals the oracle."""
+    table, blob, data, pos, ids = xaa_case
+    with GpuMatcher(0, 1) as g:
+        g.load_table(blob)
+        assert_same(table, g.scan_bytes(data), pos, ids)
+        g.set_case_fold(True)                                      # attached to the good table: gone with it
+        for b in device_refused_images(blob):
+            with pytest.raises(PfacError, match="outside the tables"):
+                g.load_table(b)
+            raises_state(lambda: g.scan_async(len(data)))
+            raises_state(g.info)
+            raises_state(lambda: g.set_case_fold(True))
+            raises_state(lambda: g.set_final_lengths(table.final_lengths()))
+            assert_same(table, g.records_to_host(pos.size), pos, ids)
+            raises_state(lambda: g.checksum(pos.size))
+            raises_state(g.emit_text_device)
+            raises_state(g.count_states)
+        g.load_table(blob)
+        assert g.case_fold is False
+        assert_same(table, g.scan_bytes(data), pos, ids)
+
+
+def test_header_refused_image_leaves_the_table_installed(xaa_case):
+    """An image refused by its header -- a wrong magic word, a wrong version, one word fewer than the header implies --
+    changes nothing: info() is what it was, the scan made before it still counts its states, a new scan equals the oracle."""
+    table, blob, data, pos, ids = xaa_case
+    need = 16 + 256 + int(blob[8]) + 2 * int(blob[9]) + int(blob[5])          # header, s0, r, the two halves of T, idmap
+    assert need <= blob.size
+    magic, version = blob.copy(), blob.copy()
+    magic[0] ^= 0x5A5A
+    version[1] += 1
+    with GpuMatcher(0, 1) as g:
+        g.load_table(table)
+        info = g.info()
+        assert_same(table, g.scan_bytes(data), pos, ids)
+        for image, n_words in ((magic, magic.size), (version, version.size), (blob, need - 1)):
+            assert g._L.pfac_table_upload(g._ctx, image.ctypes.data, n_words) == PFAC_E_ARG
+            assert g.info() == info
+            assert g.count_states() == pos.size
+            np.testing.assert_array_equal(g.state_counts_to_host(), np.bincount(g.records_to_host(pos.size)["state"].astype(np.int64), minlength=table.num_final))
+        assert_same(table, g.scan_bytes(data), pos, ids)
+
+
+def test_reupload_leaves_nothing_of_the_previous_plan(xaa_case, resolve, monkeypatch):
+    """Upload A (xaa with PFAC_FORCE_L2: tables via L2, 4-byte records), B (experimentpattern: tables in LDS, 2-byte
+    records), A again on ONE context: after each upload info() and the records of the scan are those of a fresh context
+    that has only ever had that table -- nothing of the plan before shows in the kernel arguments of the plan after."""
+    table_a, _, data, pos, ids = xaa_case
+    table_b = PfacTable.from_file(resolve("experimentpattern"), 256)
+
+    def upload_and_scan(g, table, force_l2):
+        if force_l2:
+            monkeypatch.setenv("PFAC_FORCE_L2", "1")               # (knobs are read at every install)
+        else:
+            monkeypatch.delenv("PFAC_FORCE_L2", raising=False)
+        g.load_table(table)
+        info = g.info()
+        rec = g.scan_bytes(data)
+        return info, g.scan_format()[0], rec
+
+    fresh = []
+    for table, force_l2 in ((table_a, True), (table_b, False)):
+        with GpuMatcher(0, 1) as g:
+            fresh.append(upload_and_scan(g, table, force_l2))
+    assert (fresh[0][0]["variant"], fresh[0][1]) == ("tables_via_l2", 4)
+    assert (fresh[1][0]["variant"], fresh[1][1]) == ("tables_in_lds", 2)
+    assert_same(table_a, fresh[0][2], pos, ids)
+    with GpuMatcher(0, 1) as g:
+        for table, force_l2, want in ((table_a, True, fresh[0]), (table_b, False, fresh[1]), (table_a, True, fresh[0])):
+            info, rec_bytes, rec = upload_and_scan(g, table, force_l2)
+            assert (info, rec_bytes) == want[:2]
+            np.testing.assert_array_equal(rec, want[2])
 
 
 @pytest.mark.parametrize("force_l2", [False, True])
