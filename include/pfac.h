@@ -598,6 +598,57 @@ int pfac_documents_gather_d2h(pfac_ctx *ctx, int slot, void *host, uint64_t firs
  * stream; pfac_slot_sync completes it. */
 int pfac_documents_gather_offsets_d2h(pfac_ctx *ctx, int slot, uint64_t *host_out_offsets);
 
+/* Pattern groups: which of the caller's pattern CLASSES occur in each document (content rules whose strings must all
+ * occur, grep -e groups joined by AND / NOT, label sets per line).  masks[s] is a 64-bit set: bit g is set iff the
+ * pattern(s) that end in final state s belong to group g, 0 <= g < 64.  A state with mask 0 belongs to no group; the
+ * scan still matches it and every other pass still sees it.  n_states must be num_final of the uploaded table, else
+ * PFAC_E_ARG and the earlier masks stay; PFAC_E_STATE before a table upload.  The masks live on the device with the
+ * table, like the final lengths: the next pfac_table_upload / _upload_device clears them (a failed upload past the header
+ * leaves none), a second call replaces them.  The call waits for no scan; a group pass already queued keeps the masks
+ * it was launched with (the old buffer is freed behind it, as pfac_table_set_replacements frees its own).  More than 64
+ * groups: set other masks and run the pass again. */
+int pfac_table_set_state_groups(pfac_ctx *ctx, const uint64_t *masks, uint64_t n_states);
+/* A group mask per document, straight from the record heap of the slot's last finished scan:
+ *   mask[d] = OR of masks[state] over the records (pos, state) with off[d] <= pos and pos + len[state] <= off[d + 1]
+ * -- the keep rule of pfac_records_segment: a record that runs across a document's end counts for no document.  A
+ * document without such a record, an empty one included, gets 0.  After pfac_records_filter_words only the kept records
+ * count; the records of a folded scan count as they are.  The heap is read through the tile index; no input byte is read.
+ *   d_records      the scan's record heap, NULL = the slot's; anything else that is not that heap gives PFAC_E_ARG
+ *   d_doc_offsets  device uint64[n_docs + 1] under the rules of pfac_records_segment (checked on the device, in the same
+ *                  pass); NULL = the slot's offsets, whichever call set them, with the same n_docs, else PFAC_E_STATE
+ *   d_masks_out    NULL = a slot-owned buffer grown to fit (fetched with pfac_group_masks_d2h; the lifetime rule of
+ *                  pfac_segment_d2h); else a device pointer, 8-B aligned: exactly n_docs x 8 bytes are written
+ *   *any_mask      the OR of all mask[d]: the groups that occurred at all
+ * Returns once *any_mask and the offsets' flag are known (one 16-byte copy back); the masks are then complete on the
+ * slot's stream (pfac_slot_sync).  Judged in this order -- PFAC_E_STATE: no finished scan, a scan made with an earlier
+ * table, no final lengths or no state groups for the current table, no offsets for the slot; PFAC_E_OVERFLOW: the scan
+ * overflowed its heap; PFAC_E_ARG: misaligned buffers, n_docs >= 2^32, a d_records that is not this scan's heap, offsets
+ * that break the rules.  Every error leaves a caller's buffer as it was (the masks are made in the slot's buffer and
+ * copied behind the host's check of the offsets' flag); the slot-owned result is discarded even when the call fails.
+ * n_docs == 0 (then n_owned == 0) writes nothing and sets *any_mask = 0.
+ * One kernel behind a memset of the masks: one wave per 64 tiles walks the records as the segment pass's count does,
+ * ORs the masks of a document's records in registers (a segmented OR scan over the 64 lanes, the open run carried across
+ * chunks and tiles) and writes each document once -- a plain 8-byte store where the document lies inside the wave's
+ * tiles, an atomic OR for the at most two that straddle their ends.  No atomic per record. */
+int pfac_documents_group_masks(pfac_ctx *ctx, int slot, const void *d_records, const uint64_t *d_doc_offsets, uint64_t n_docs,
+                               uint64_t *d_masks_out, uint64_t *any_mask);
+/* D2H of masks [first, first + n) of the slot-owned result of the last pfac_documents_group_masks.  Asynchronous on the
+ * slot's stream; pfac_slot_sync completes it.  first + n > n_docs gives PFAC_E_ARG; n == 0 does nothing. */
+int pfac_group_masks_d2h(pfac_ctx *ctx, int slot, uint64_t *host_masks, uint64_t first, uint64_t n);
+/* The documents whose group mask m = mask[d] satisfies a predicate.  Document d is reported iff
+ *   ((m & all_of) == all_of && (any_of == 0 || (m & any_of) != 0) && (m & none_of) == 0) != invert
+ * (flags: 0 or PFAC_DOCS_INVERT); all_of = none_of = 0, any_of = ~0 is "some grouped pattern matched".
+ *   d_masks  NULL = the slot-owned masks of the slot's last pfac_documents_group_masks (PFAC_E_STATE if there are none or
+ *            they went to the caller's buffer, PFAC_E_ARG if n_docs differs from that call's); else any device
+ *            uint64[n_docs], 8-B aligned
+ * d_ids_out, out_cap, *n_matching, PFAC_E_OVERFLOW (exact count, nothing written), the alignment and n_docs < 2^32 are
+ * exactly those of pfac_documents_matching, and the call is ONE pass with it and _context: the same slot-owned id
+ * buffer, pfac_documents_matching_d2h, and pfac_documents_gather(d_ids = NULL) consumes its ids unchanged.
+ * Kernels: the compaction of pfac_documents_matching, instantiated with the predicate (one load per document). */
+int pfac_documents_matching_groups(pfac_ctx *ctx, int slot, const uint64_t *d_masks, uint64_t n_docs, uint64_t all_of,
+                                   uint64_t any_of, uint64_t none_of, uint32_t flags, uint64_t *d_ids_out, uint64_t out_cap,
+                                   uint64_t *n_matching);
+
 /* Whole-word filter: drops, IN PLACE, the records of the slot's last finished scan that split a word, so that every
  * consumer of the scan (the fetches, the text emitter, the checksum, the segment pass, both selections and both
  * replaces) sees whole-word matches only -- a selection then chooses among whole-word candidates, which no filter

@@ -102,6 +102,7 @@ HIP_SYMBOLS = (
     "pfac_slot_doc_offsets_split", "pfac_slot_doc_offsets_d2h", "pfac_documents_matching", "pfac_documents_matching_d2h",
     "pfac_documents_matching_context", "pfac_documents_gather", "pfac_documents_gather_d2h", "pfac_documents_gather_offsets_d2h",
     "pfac_table_set_case_fold", "pfac_table_case_fold",
+    "pfac_table_set_state_groups", "pfac_documents_group_masks", "pfac_group_masks_d2h", "pfac_documents_matching_groups",
 )
 
 _host = None
@@ -247,5 +248,9 @@ def hip_lib() -> C.CDLL:
         L.pfac_documents_gather_offsets_d2h.argtypes = [vp, i, vp]
         L.pfac_table_set_case_fold.argtypes = [vp, C.c_uint32]
         L.pfac_table_case_fold.argtypes = [vp, C.POINTER(C.c_uint32)]
+        L.pfac_table_set_state_groups.argtypes = [vp, vp, u64]
+        L.pfac_documents_group_masks.argtypes = [vp, i, vp, vp, u64, vp, C.POINTER(u64)]
+        L.pfac_group_masks_d2h.argtypes = [vp, i, vp, u64, u64]
+        L.pfac_documents_matching_groups.argtypes = [vp, i, vp, u64, u64, u64, u64, C.c_uint32, vp, u64, C.POINTER(u64)]
         _hip = L
     return _hip

@@ -2481,6 +2481,109 @@ __global__ void pfac_seg_write_kernel(const void *rec, const unsigned long long 
 }
 
 // ---------------------------------------------------------------------------
+// Pattern groups (pfac_documents_group_masks): mask[d] = the OR of gmask[state] over the records the segment pass would
+// keep for document d -- the walk of pfac_seg_count_kernel (record, length, document, keep rule; the offsets' rules in
+// the same pass) with 8 bytes per DOCUMENT behind it instead of a count per tile, and no global atomic per record.
+// One wave per group of 64 tiles.  A tile's records come in position order, so the documents of the contributing lanes
+// (kept, mask != 0) ascend: every lane takes the document of the nearest contributing lane at or below it (the first
+// one's in front of it) with mask 0 where it contributes nothing, and a segmented inclusive OR scan keyed on the
+// document (six shuffle steps) leaves each run's OR in its last lane.  The chunk's last run stays open in two
+// wave-uniform registers (cd, cm) across chunks and tiles; a run is flushed ONCE, when the document changes or the
+// wave's tiles end.
+// Who writes mask[d]: the wave's tiles cover the bytes [B0, B1) and every record of them starts there.  A document with
+// B0 <= off[d] and off[d + 1] <= B1 gets all its records from this wave, which flushes it once: a plain 8-byte store
+// over the zero that the host's memset left.  The others -- at most the one that runs in from below B0 and the one that
+// runs out past B1 -- may be flushed by several waves and are OR-ed with an agent-scope atomic whose result nobody
+// reads; no wave ever stores plainly to them, so store and atomic never meet on one word.  The interior documents are
+// [a, e - 1) with a = the first d with off[d] >= B0 and e = the first index with off[e] > B1 (the last wave has no
+// B1): two binary searches per wave.  Documents without a contributing record are never written -- the memset is their 0.
+// With offsets that break the rules the documents stay clamped to [0, n_docs) (tile_docs), the result is garbage in
+// bounds, and the host discards it behind the flag.
+template <int BYTES>
+__global__ void __launch_bounds__(256)
+pfac_group_masks_kernel(const void *rec, const unsigned long long *tix, unsigned long long n_tiles, unsigned long long cap,
+                        const unsigned long long *off, unsigned long long n_docs, unsigned long long n_owned,
+                        const short *flen, const unsigned long long *gmask, unsigned num_final, unsigned long long *out,
+                        unsigned n_groups, unsigned long long *res) {        // res[0]: the OR of all masks, res[1]: bad offsets
+    const unsigned long long gtid = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const unsigned long long gstride = (unsigned long long)gridDim.x * blockDim.x;
+    for (unsigned long long d = gtid; d < n_docs; d += gstride)
+        if (off[d] > off[d + 1]) res[1] = 1ull;
+    if (gtid == 0 && (off[0] != 0ull || off[n_docs] != n_owned)) res[1] = 1ull;
+    const int lane = threadIdx.x & (WAVE - 1);
+    const unsigned g = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (g >= n_groups) return;
+    const bool fsmall = num_final <= (unsigned)WAVE;
+    const int freg = fsmall && (unsigned)lane < num_final ? (int)flen[lane] : 0;
+    const unsigned long long greg = fsmall && (unsigned)lane < num_final ? gmask[lane] : 0ull;
+    const unsigned long long t = (unsigned long long)g * XGROUP + lane;
+    const unsigned long long e = t < n_tiles ? tix[t] : 0ull;
+    const unsigned c = (unsigned)(e >> TIX_CNT_SHIFT);
+    const unsigned long long lo = e & TIX_BASE_MASK;
+    if (__ballot(c != 0u) == 0ull) return;                      // a range without records writes nothing
+    unsigned long long ds = 0, de = 0, dlo = 0, dhi = 0;
+    if (c) tile_docs(off, n_docs, t, n_tiles, ds, de, dlo, dhi);
+    // the documents this wave alone writes: [ia, ie)
+    const bool last = ((unsigned long long)g + 1) * XGROUP >= n_tiles;
+    const unsigned long long ia = doc_lower_bound(off, n_docs + 1, (unsigned long long)g * XGROUP * WTILE);
+    const unsigned long long ib = last ? n_docs + 1 : doc_lower_bound(off, n_docs + 1, ((unsigned long long)g + 1) * XGROUP * WTILE + 1ull);
+    const unsigned long long ie = ib ? ib - 1 : 0ull;
+    auto flush = [&](unsigned d, unsigned long long m) {
+        if (m == 0ull) return;
+        if (d >= ia && d < ie) out[d] = m;
+        else (void)__hip_atomic_fetch_or(out + d, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    };
+    bool cvalid = false;                                        // the open run (wave-uniform)
+    unsigned cd = 0;
+    unsigned long long cm = 0, any = 0;
+    for (int j = 0; j < XGROUP; j++) {
+        const unsigned tc = __shfl(c, j, WAVE);
+        if (tc == 0) continue;
+        const unsigned long long tlo = __shfl(lo, j, WAVE);
+        const DocWin w = doc_window(off, __shfl(dlo, j, WAVE), __shfl(dhi, j, WAVE), lane);
+        for (unsigned c0 = 0; c0 < tc; c0 += WAVE) {
+            const unsigned i = c0 + (unsigned)lane;
+            const bool have = i < tc && tlo + i < cap;
+            unsigned pos = 0, st = 0;
+            if (have) heap_record<BYTES>(rec, tlo + i, (unsigned long long)g * XGROUP + j, pos, st);
+            const int len = final_len(flen, freg, fsmall, have, st);
+            const unsigned long long gm = fsmall ? __shfl(greg, (int)st, WAVE) : (have ? gmask[st] : 0ull);
+            unsigned long long d, base, end;
+            doc_lookup(w, off, have, pos, d, base, end);
+            const bool keep = have && len > 0 && (unsigned long long)pos + (unsigned)len <= end;
+            unsigned long long m = keep ? gm : 0ull;
+            const unsigned long long b = __ballot(m != 0ull);
+            if (b == 0ull) continue;
+            any |= m;
+            const unsigned long long below = b & ((2ull << lane) - 1ull);        // contributing lanes up to this one
+            unsigned dk = (unsigned)__shfl((unsigned)d, below ? 63 - __clzll(below) : __ffsll((long long)b) - 1, WAVE);
+#pragma unroll
+            for (int s = 1; s < WAVE; s <<= 1) {
+                const unsigned du = (unsigned)__shfl_up(dk, s, WAVE);
+                const unsigned long long mu = __shfl_up(m, s, WAVE);
+                if (lane >= s && du == dk) m |= mu;
+            }
+            if (cvalid) {
+                if (__ballot(dk == cd) != 0ull) {
+                    if (dk == cd) m |= cm;                      // the open run goes on (it starts at lane 0)
+                } else if (lane == 0) {
+                    flush(cd, cm);
+                }
+            }
+            const unsigned dn = (unsigned)__shfl_down(dk, 1, WAVE);
+            if (lane != WAVE - 1 && dn != dk) flush(dk, m);
+            cd = (unsigned)__shfl(dk, WAVE - 1, WAVE);
+            cm = __shfl(m, WAVE - 1, WAVE);
+            cvalid = true;
+        }
+    }
+    if (cvalid && lane == 0) flush(cd, cm);
+#pragma unroll
+    for (int s = 1; s < WAVE; s <<= 1) any |= __shfl_xor(any, s, WAVE);
+    if (lane == 0 && any) (void)__hip_atomic_fetch_or(res, any, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// ---------------------------------------------------------------------------
 // Whole-word filter (pfac_records_filter_words): drops, IN PLACE, the records that split a word.  With W the 256-bit
 // set of word bytes, cut(i) = W(in[i-1]) && W(in[i]) (in[-1] = prev, in[n_avail] = next, -1 = no byte; never at a
 // document offset); a record (pos, state) of length L goes when its tested edge(s) cut: cut(pos), cut(pos + L).
@@ -3568,11 +3671,15 @@ pfac_split_write_kernel(const unsigned char *in, unsigned long long n, unsigned 
 // The context form (pfac_documents_matching_context, grep -A / -B / -C) is the same compaction over another flag: doc_first
 // is a prefix array, so "some document of [d - after, d + before] has a record" is doc_first[hi + 1] > doc_first[lo] with
 // both ends clamped -- still two loads per document.  `before` and `after` arrive clamped to n_docs (d + before cannot wrap).
+// The groups form (pfac_documents_matching_groups) is the third flag: the array holds a group mask per document (one
+// load per document) and the three words are the predicate's sets, all_of / any_of / none_of.
 constexpr int DM_BLOCKS = 64;
-template <bool WRITE, bool CONTEXT>
+enum : int { DM_PLAIN = 0, DM_CONTEXT = 1, DM_GROUPS = 2 };
+template <bool WRITE, int PRED>
 __device__ __forceinline__ void docs_matching_body(const unsigned long long *doc_first, unsigned long long n_docs, unsigned invert,
-                                                   unsigned long long before, unsigned long long after, unsigned long long *gsum,
-                                                   unsigned n_groups, unsigned long long total, unsigned long long *ids) {
+                                                   unsigned long long before, unsigned long long after, unsigned long long none_of,
+                                                   unsigned long long *gsum, unsigned n_groups, unsigned long long total,
+                                                   unsigned long long *ids) {
     const int lane = threadIdx.x & (WAVE - 1);
     const unsigned g = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (g >= n_groups) return;
@@ -3584,7 +3691,11 @@ __device__ __forceinline__ void docs_matching_body(const unsigned long long *doc
         const unsigned long long d = d0 + (unsigned long long)b * WAVE + lane;
         const bool have = d < n_docs;
         bool flag;
-        if (CONTEXT) {
+        if (PRED == DM_GROUPS) {                                // before = all_of, after = any_of
+            const unsigned long long m = have ? doc_first[d] : 0ull;
+            const bool ok = (m & before) == before && (after == 0ull || (m & after) != 0ull) && (m & none_of) == 0ull;
+            flag = have && (ok != (invert != 0u));
+        } else if (PRED == DM_CONTEXT) {
             const unsigned long long first = d - (after < d ? after : d), last = d + before < n_docs ? d + before : n_docs - 1;
             const unsigned long long lo = have ? doc_first[first] : 0ull, hi = have ? doc_first[last + 1] : 0ull;
             flag = have && hi > lo;
@@ -3605,14 +3716,21 @@ template <bool WRITE>
 __global__ void __launch_bounds__(256)
 pfac_docs_matching_kernel(const unsigned long long *doc_first, unsigned long long n_docs, unsigned invert, unsigned long long *gsum,
                           unsigned n_groups, unsigned long long total, unsigned long long *ids) {
-    docs_matching_body<WRITE, false>(doc_first, n_docs, invert, 0ull, 0ull, gsum, n_groups, total, ids);
+    docs_matching_body<WRITE, DM_PLAIN>(doc_first, n_docs, invert, 0ull, 0ull, 0ull, gsum, n_groups, total, ids);
 }
 template <bool WRITE>
 __global__ void __launch_bounds__(256)
 pfac_docs_context_kernel(const unsigned long long *doc_first, unsigned long long n_docs, unsigned long long before,
                          unsigned long long after, unsigned long long *gsum, unsigned n_groups, unsigned long long total,
                          unsigned long long *ids) {
-    docs_matching_body<WRITE, true>(doc_first, n_docs, 0u, before, after, gsum, n_groups, total, ids);
+    docs_matching_body<WRITE, DM_CONTEXT>(doc_first, n_docs, 0u, before, after, 0ull, gsum, n_groups, total, ids);
+}
+template <bool WRITE>
+__global__ void __launch_bounds__(256)
+pfac_docs_groups_kernel(const unsigned long long *masks, unsigned long long n_docs, unsigned invert, unsigned long long all_of,
+                        unsigned long long any_of, unsigned long long none_of, unsigned long long *gsum, unsigned n_groups,
+                        unsigned long long total, unsigned long long *ids) {
+    docs_matching_body<WRITE, DM_GROUPS>(masks, n_docs, invert, all_of, any_of, none_of, gsum, n_groups, total, ids);
 }
 
 // ---------------------------------------------------------------------------
@@ -3912,6 +4030,8 @@ struct Slot {
     DevBuf<unsigned long long> sp_tile;   // per input tile: delimiters | end of the last one << 32
     // pfac_documents_matching
     PassOut<unsigned long long> dm_out;   // the ids
+    // pfac_documents_group_masks
+    PassOut<unsigned long long> gm_out;   // the masks (n_docs of them); scratch of a call that writes to the caller's buffer
     // pfac_documents_gather
     DevBuf<unsigned long long> ga_x;      // X per block of 64 ids
     PassOut<unsigned char> ga_out;        // the bytes, ...
@@ -3977,10 +4097,11 @@ struct pfac_ctx {
     TablePlan plan;
     bool have_table = false;
     uint64_t table_gen = 0;               // installs begun so far: a scan's final states index the lengths of ITS table only
-    // ... what the caller attaches to it (an upload drops all four), ...
+    // ... what the caller attaches to it (an upload drops all five), ...
     DevBuf<short> flen;                   // pattern length of every final state (pfac_table_set_final_lengths)
     DevBuf<unsigned> rep_off;             // replacement of every final state (pfac_table_set_replacements): offsets[num_final + 1]
     DevBuf<unsigned char> rep;            // ... and the bytes, zero-padded to its capacity (a multiple of 16)
+    DevBuf<unsigned long long> gmask;     // group set of every final state (pfac_table_set_state_groups)
     unsigned fold = PFAC_FOLD_NONE;       // case fold of the scans to come (pfac_table_set_case_fold)
     // ... and what adapts to the match density seen by the last scan (pfac_scan_finish)
     bool dense = false;                   // staging mode
@@ -4516,6 +4637,7 @@ int install_table(pfac_ctx *ctx, const int *d_blob, const int32_t *hdr, size_t n
     ctx->plan = TablePlan();
     ctx->flen.reset(); ctx->fold = PFAC_FOLD_NONE;          // the lengths belong to the old table, and so does the case fold
     ctx->rep_off.reset(); ctx->rep.reset();                 // ... and so do the replacements
+    ctx->gmask.reset();                                     // ... and the state groups
     ctx->have_table = false; ctx->table_gen++;
     TablePlan P;
     if (int rc = build_plan(ctx, P, d_blob, hdr, stream)) return rc;
@@ -5393,6 +5515,80 @@ int pfac_segment_d2h(pfac_ctx *ctx, int slot, pfac_record *host_records, uint64_
     return rc ? rc : fetch(ctx, s, s.seg_first, "pfac_segment_d2h", "pfac_records_segment", host_doc_first, 0, s.seg_first.n, true);
 }
 
+int pfac_table_set_state_groups(pfac_ctx *ctx, const uint64_t *masks, uint64_t n_states) {
+    if (!ctx) return fail(nullptr, PFAC_E_ARG, "null context");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (!ctx->have_table) return fail(ctx, PFAC_E_STATE, "pfac_table_set_state_groups before a table upload");
+    if (n_states != (uint64_t)ctx->plan.base.num_final || (!masks && n_states))
+        return fail(ctx, PFAC_E_ARG, "pfac_table_set_state_groups: need num_final masks (num_final " + std::to_string(ctx->plan.base.num_final) + ")");
+    USE_DEVICE(ctx);
+    // as the replacements: a buffer of its own for every call, and freeing the old one waits for the device -- a group
+    // pass that still reads the old masks has finished before they go
+    ctx->gmask.reset();
+    const uint64_t n = std::max<uint64_t>(n_states, 1);
+    int rc = ctx->gmask.ensure(ctx, nullptr, n, n);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemset(ctx->gmask.p, 0, n * 8));
+    if (n_states) HIP_TRY(ctx, hipMemcpy(ctx->gmask.p, masks, n_states * 8, hipMemcpyHostToDevice));
+    return PFAC_OK;
+}
+
+int pfac_documents_group_masks(pfac_ctx *ctx, int slot, const void *d_records, const uint64_t *d_doc_offsets, uint64_t n_docs,
+                               uint64_t *d_masks_out, uint64_t *any_mask) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    if (!any_mask) return fail(ctx, PFAC_E_ARG, "null argument");
+    *any_mask = 0;
+    Slot &s = ctx->slots[slot];
+    s.gm_out.invalidate();
+    const std::string fn = "pfac_documents_group_masks";
+    rc = last_scan_usable(ctx, s, fn, SCAN_FINISHED | SCAN_LENGTHS | SCAN_TABLE);
+    if (rc) return rc;
+    if (!ctx->gmask.p) return fail(ctx, PFAC_E_STATE, fn + ": no state groups for the uploaded table (pfac_table_set_state_groups)");
+    if (!d_doc_offsets && (!s.doc.done || n_docs + 1 != s.doc.n))
+        return fail(ctx, PFAC_E_STATE, fn + ": the slot has no document offsets for this n_docs (pfac_slot_doc_offsets, pfac_slot_doc_offsets_split)");
+    rc = last_scan_usable(ctx, s, fn, SCAN_FITS);
+    if (rc) return rc;
+    const unsigned long long *off;
+    rc = resolve_docs(ctx, s, fn, d_doc_offsets, n_docs, (uintptr_t)d_masks_out, &off);
+    if (rc) return rc;
+    const void *src = d_records ? d_records : (const void *)s.records.p;
+    if (s.last_tiles && src != s.last_records) return fail(ctx, PFAC_E_ARG, fn + ": d_records is not the record heap of the slot's last scan");
+    USE_DEVICE(ctx);
+    const uint64_t n_tiles = n_docs ? s.last_tiles : 0;     // (no documents: the scan owns no bytes, only the offsets are judged)
+    const unsigned n_groups = (unsigned)((n_tiles + XGROUP - 1) / XGROUP);
+    rc = ensure_gsum(ctx, s, 1);                            // the OR of all masks, the offsets' error flag
+    if (rc) return rc;
+    // The masks are made in the slot's buffer and reach a caller's only behind the host's check of the offsets' flag:
+    // a refused call leaves the caller's buffer as it was.
+    unsigned long long *masks;
+    rc = s.gm_out.bind(ctx, s.stream, (uint64_t *)nullptr, std::max<uint64_t>(n_docs, 1), docs_cap(n_docs), &masks);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemsetAsync(s.gsum.p, 0, 16, s.stream));
+    if (n_docs) HIP_TRY(ctx, hipMemsetAsync(masks, 0, n_docs * 8, s.stream));     // the 0 of every document without a grouped record
+    const uint64_t gblocks = (n_groups + 3) / 4, vblocks = (n_docs + 255) / 256;
+    const unsigned blocks = (unsigned)std::max<uint64_t>(1, std::max<uint64_t>(gblocks, std::min<uint64_t>(vblocks, 4096)));
+    auto mk = by_width(s.last_rec_bytes, [](auto w) { return pfac_group_masks_kernel<w()>; });
+    hipLaunchKernelGGL(mk, dim3(blocks), dim3(256), 0, s.stream, src, s.tile_index.p, (unsigned long long)n_tiles,
+                       (unsigned long long)s.last_cap, off, (unsigned long long)n_docs, (unsigned long long)s.last_owned,
+                       ctx->flen.p, ctx->gmask.p, (unsigned)ctx->plan.base.num_final, masks, n_groups, s.gsum.p);
+    rc = pass_words(ctx, s, s.gsum.p, 2);
+    if (rc) return rc;
+    if (host_u64(s, H_PASS1)) return bad_doc_offsets(ctx, s, fn);
+    if (d_masks_out && n_docs)
+        HIP_TRY(ctx, hipMemcpyAsync(d_masks_out, masks, n_docs * 8, hipMemcpyDeviceToDevice, s.stream));
+    *any_mask = host_u64(s, H_PASS);
+    s.gm_out.commit(n_docs, !d_masks_out);
+    return PFAC_OK;
+}
+
+int pfac_group_masks_d2h(pfac_ctx *ctx, int slot, uint64_t *host_masks, uint64_t first, uint64_t n) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    Slot &s = ctx->slots[slot];
+    return fetch(ctx, s, s.gm_out, "pfac_group_masks_d2h", "pfac_documents_group_masks", host_masks, first, n);
+}
+
 // The offsets' rules alone, on the slot's stream (pfac_seg_count_kernel without tiles): *bad becomes non-zero where
 // the offsets do not start at 0, decrease, or do not end at the scan's n_owned.
 static void launch_offsets_check(pfac_ctx *ctx, Slot &s, const unsigned long long *off, uint64_t n_docs, unsigned long long *bad) {
@@ -5416,18 +5612,23 @@ static WriteGrid write_grid(uint64_t total) {
     return {(unsigned)((total + per_block * wins - 1) / (per_block * wins)), (unsigned)wins};
 }
 
-// Both matching calls: the plain one (context false: flags 0 or PFAC_DOCS_INVERT) and the one with context lines
-// (flags 0; before / after as the caller gave them).  One pass: one slot-owned id buffer, one fetch, one lifetime.
-static int dm_run(pfac_ctx *ctx, int slot, const std::string &fn, const uint64_t *d_doc_first, uint64_t n_docs, bool context,
-                  uint64_t before, uint64_t after, uint32_t flags, uint64_t *d_ids_out, uint64_t out_cap, uint64_t *n_matching) {
+// The three matching calls: the plain one (DM_PLAIN: flags 0 or PFAC_DOCS_INVERT), the one with context lines
+// (DM_CONTEXT: flags 0; before / after as the caller gave them) and the one over group masks (DM_GROUPS: d_doc_first
+// is the masks, before / after / none_of are all_of / any_of / none_of).  One pass: one slot-owned id buffer, one
+// fetch, one lifetime.
+static int dm_run(pfac_ctx *ctx, int slot, const std::string &fn, const uint64_t *d_doc_first, uint64_t n_docs, int pred,
+                  uint64_t before, uint64_t after, uint64_t none_of, uint32_t flags, uint64_t *d_ids_out, uint64_t out_cap,
+                  uint64_t *n_matching) {
     int rc = check_slot(ctx, slot);
     if (rc) return rc;
     if (!n_matching) return fail(ctx, PFAC_E_ARG, "null argument");
     *n_matching = 0;
     Slot &s = ctx->slots[slot];
     s.dm_out.invalidate();
+    const bool context = pred == DM_CONTEXT, groups = pred == DM_GROUPS;
     const unsigned long long *first;
-    rc = s.seg_first.consume(ctx, fn, "doc_first of a pfac_records_segment (n_docs + 1 entries)", d_doc_first, n_docs + 1, &first);
+    rc = groups ? s.gm_out.consume(ctx, fn, "group masks of a pfac_documents_group_masks (n_docs entries)", d_doc_first, n_docs, &first)
+                : s.seg_first.consume(ctx, fn, "doc_first of a pfac_records_segment (n_docs + 1 entries)", d_doc_first, n_docs + 1, &first);
     if (rc) return rc;
     if (context && flags) return fail(ctx, PFAC_E_ARG, fn + ": flags must be 0 (context around non-matching documents is not defined by doc_first)");
     if (flags > PFAC_DOCS_INVERT) return fail(ctx, PFAC_E_ARG, fn + ": flags must be 0 or PFAC_DOCS_INVERT");
@@ -5435,13 +5636,17 @@ static int dm_run(pfac_ctx *ctx, int slot, const std::string &fn, const uint64_t
     if (((uintptr_t)first | (uintptr_t)d_ids_out) & 7) return fail(ctx, PFAC_E_ARG, fn + ": device buffers must be 8-byte aligned");
     USE_DEVICE(ctx);
     const unsigned n_groups = (unsigned)((n_docs + DM_BLOCKS * WAVE - 1) / (DM_BLOCKS * WAVE));
-    const unsigned long long bef = std::min(before, n_docs), aft = std::min(after, n_docs);   // (a window wider than the input is the input)
+    // (a window wider than the input is the input; the groups form passes its sets as they are)
+    const unsigned long long bef = groups ? before : std::min(before, n_docs), aft = groups ? after : std::min(after, n_docs);
     const dim3 grid((n_groups + 3) / 4), block(256);
     uint64_t total = 0;
     if (n_groups) {
         rc = ensure_gsum(ctx, s, n_groups);
         if (rc) return rc;
-        if (context)
+        if (groups)
+            hipLaunchKernelGGL(pfac_docs_groups_kernel<false>, grid, block, 0, s.stream, first, (unsigned long long)n_docs, (unsigned)flags,
+                               bef, aft, (unsigned long long)none_of, s.gsum.p, n_groups, 0ull, (unsigned long long *)nullptr);
+        else if (context)
             hipLaunchKernelGGL(pfac_docs_context_kernel<false>, grid, block, 0, s.stream, first, (unsigned long long)n_docs, bef, aft,
                                s.gsum.p, n_groups, 0ull, (unsigned long long *)nullptr);
         else
@@ -5459,7 +5664,10 @@ static int dm_run(pfac_ctx *ctx, int slot, const std::string &fn, const uint64_t
     rc = s.dm_out.bind(ctx, s.stream, d_ids_out, total, total + total / 8 + 4096, &ids);
     if (rc) return rc;
     if (total) {
-        if (context)
+        if (groups)
+            hipLaunchKernelGGL(pfac_docs_groups_kernel<true>, grid, block, 0, s.stream, first, (unsigned long long)n_docs, (unsigned)flags,
+                               bef, aft, (unsigned long long)none_of, s.gsum.p, n_groups, (unsigned long long)total, ids);
+        else if (context)
             hipLaunchKernelGGL(pfac_docs_context_kernel<true>, grid, block, 0, s.stream, first, (unsigned long long)n_docs, bef, aft,
                                s.gsum.p, n_groups, (unsigned long long)total, ids);
         else
@@ -5473,12 +5681,19 @@ static int dm_run(pfac_ctx *ctx, int slot, const std::string &fn, const uint64_t
 
 int pfac_documents_matching(pfac_ctx *ctx, int slot, const uint64_t *d_doc_first, uint64_t n_docs, uint32_t flags,
                             uint64_t *d_ids_out, uint64_t out_cap, uint64_t *n_matching) {
-    return dm_run(ctx, slot, "pfac_documents_matching", d_doc_first, n_docs, false, 0, 0, flags, d_ids_out, out_cap, n_matching);
+    return dm_run(ctx, slot, "pfac_documents_matching", d_doc_first, n_docs, DM_PLAIN, 0, 0, 0, flags, d_ids_out, out_cap, n_matching);
 }
 
 int pfac_documents_matching_context(pfac_ctx *ctx, int slot, const uint64_t *d_doc_first, uint64_t n_docs, uint64_t before,
                                     uint64_t after, uint32_t flags, uint64_t *d_ids_out, uint64_t out_cap, uint64_t *n_matching) {
-    return dm_run(ctx, slot, "pfac_documents_matching_context", d_doc_first, n_docs, true, before, after, flags, d_ids_out,
+    return dm_run(ctx, slot, "pfac_documents_matching_context", d_doc_first, n_docs, DM_CONTEXT, before, after, 0, flags, d_ids_out,
+                  out_cap, n_matching);
+}
+
+int pfac_documents_matching_groups(pfac_ctx *ctx, int slot, const uint64_t *d_masks, uint64_t n_docs, uint64_t all_of,
+                                   uint64_t any_of, uint64_t none_of, uint32_t flags, uint64_t *d_ids_out, uint64_t out_cap,
+                                   uint64_t *n_matching) {
+    return dm_run(ctx, slot, "pfac_documents_matching_groups", d_masks, n_docs, DM_GROUPS, all_of, any_of, none_of, flags, d_ids_out,
                   out_cap, n_matching);
 }
 

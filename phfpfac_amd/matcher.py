@@ -654,6 +654,78 @@ class GpuMatcher:
         return (self.gathered_to_host(out_bytes, slot), self.gathered_offsets_to_host(n, slot),
                 self.matching_documents_to_host(n, slot))
 
+    # -- pattern groups: a group bitmask per document ------------------------
+    def set_pattern_groups(self, groups) -> None:
+        """The groups of every pattern of the uploaded table (``PfacTable.state_group_masks``: one entry per 1-based
+        pattern id -- a group index 0..63, an iterable of them, None, or a uint64 array of ready masks), kept on the
+        device until the next table upload (``pfac_table_set_state_groups``)."""
+        if self.table is None:
+            raise PfacError(-7, "no host table to map pattern ids to states (load_table first)")
+        masks = self.table.state_group_masks(groups)
+        self._check(self._L.pfac_table_set_state_groups(self._ctx, masks.ctypes.data if masks.size else None, masks.size))
+
+    def document_group_masks(self, n_docs: int, d_doc_offsets=None, d_out=None, slot: int = 0, d_records=None) -> int:
+        """Which pattern groups occur in each document of the slot's last finished scan, on the GPU
+        (``pfac_documents_group_masks``): ``mask[d]`` ORs the groups of the records the document cut would keep, straight
+        from the record heap -- no segment pass.  ``d_doc_offsets`` None = the slot's (``set_doc_offsets`` /
+        ``split_documents``); ``d_out`` None = a slot-owned buffer (``group_masks_to_host``), else a device buffer of
+        ``n_docs`` uint64.  Returns the OR of all masks: the groups that occurred at all."""
+        m = C.c_uint64(0)
+        self._check(self._L.pfac_documents_group_masks(self._ctx, slot, _ptr(d_records), _ptr(d_doc_offsets), int(n_docs),
+                                                       _ptr(d_out), C.byref(m)))
+        return m.value
+
+    def group_masks_to_host(self, n_docs: int, slot: int = 0, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """Masks [first, first + n) of the slot's last ``document_group_masks`` into its slot-owned buffer (default:
+        all ``n_docs``)."""
+        n = int(n_docs) - int(first) if n is None else int(n)
+        return self._to_host(slot, lambda p: self._L.pfac_group_masks_d2h(self._ctx, slot, p, int(first), n),
+                             (max(n, 0), np.uint64))
+
+    def matching_documents_where(self, n_docs: int, all_of: int = 0, any_of: int = 0, none_of: int = 0, invert: bool = False,
+                                 d_masks=None, d_out=None, out_cap: int = 0, slot: int = 0) -> int:
+        """The documents whose group mask holds every group of ``all_of``, some group of ``any_of`` (0: no such demand)
+        and none of ``none_of`` (``invert``: the others), ascending, on the GPU (``pfac_documents_matching_groups``).
+        ``d_masks`` None = the slot-owned masks of the slot's last ``document_group_masks``, else a device array of
+        ``n_docs`` uint64.  The ids go where ``matching_documents`` puts them (``d_out`` None = the slot-owned buffer,
+        ``matching_documents_to_host``; ``gather_documents`` consumes them).  Returns the number of documents; a too
+        small ``out_cap`` raises PfacError(PFAC_E_OVERFLOW) whose ``n_matching`` attribute holds the exact count."""
+        n = C.c_uint64(0)
+        full = 2**64 - 1
+        rc = self._L.pfac_documents_matching_groups(self._ctx, slot, _ptr(d_masks), int(n_docs), int(all_of) & full,
+                                                    int(any_of) & full, int(none_of) & full,
+                                                    PFAC_DOCS_INVERT if invert else 0, _ptr(d_out), int(out_cap), C.byref(n))
+        return self._counted(rc, n, "n_matching")
+
+    def tag_documents(self, docs, whole_words=False, slot: int = 0) -> np.ndarray:
+        """The group mask of every document of a batch (``docs`` as ``scan_documents`` takes it) in one scan: uint64
+        [n_docs], bit g set iff a pattern of group g (``set_pattern_groups``) matches inside the document.  Only the
+        masks come back."""
+        _, n_docs = self._scan_docs(docs, slot, whole_words)
+        self.document_group_masks(n_docs, slot=slot)
+        return self.group_masks_to_host(n_docs, slot)
+
+    def tag_lines(self, data, delimiter=b"\n", whole_words=False, slot: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+        """``tag_documents`` of one buffer cut into lines at ``delimiter`` on the device.  Returns (offsets uint64
+        [n_docs + 1], masks uint64[n_docs])."""
+        offsets, n_docs = self._scan_lines(data, delimiter, slot, whole_words)
+        self.document_group_masks(n_docs, slot=slot)
+        return offsets, self.group_masks_to_host(n_docs, slot)
+
+    def grep_lines_where(self, data, all_of: int = 0, any_of: int = 0, none_of: int = 0, invert: bool = False,
+                         delimiter=b"\n", whole_words=False, slot: int = 0) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The lines of ``data`` whose pattern groups satisfy the predicate of ``matching_documents_where``, as bytes --
+        several ``grep -e`` groups joined by AND and NOT: scan, split, the mask pass, the predicate and the gather on
+        the device, with no document cut in between.  Returns what ``grep_lines`` returns: (out uint8[out_bytes],
+        out_offsets uint64[n + 1], ids uint64[n])."""
+        buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data.view(np.uint8).ravel()
+        _, n_docs = self._scan_lines(buf, delimiter, slot, whole_words, fetch_offsets=False)
+        self.document_group_masks(n_docs, slot=slot)
+        n = self.matching_documents_where(n_docs, all_of, any_of, none_of, invert=invert, slot=slot)
+        out_bytes = self.gather_documents(n_docs, n, int(buf.size), slot=slot)
+        return (self.gathered_to_host(out_bytes, slot), self.gathered_offsets_to_host(n, slot),
+                self.matching_documents_to_host(n, slot))
+
     # -- leftmost-longest non-overlapping matches ---------------------------
     def select_leftmost_longest(self, entry: int = 0, d_out=None, out_cap: int = 0, slot: int = 0,
                                 d_records=None) -> Tuple[int, int]:

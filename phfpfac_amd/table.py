@@ -188,6 +188,35 @@ class PfacTable:
         np.add.at(out, ids, counts)
         return out
 
+    def state_group_masks(self, groups) -> np.ndarray:
+        """Pattern groups -> uint64[num_final] for ``pfac_table_set_state_groups``: bit g of ``masks[s]`` is set iff a
+        pattern that ends in final state s belongs to group g (0..63).  ``groups`` is indexed by the 1-based pattern
+        id (entry 0 is unused), one entry per id the table can report, as ``counts_by_pattern`` returns them: a group
+        index, an iterable of indices, or None for a pattern in no group; a uint64 array holds ready masks.  A literal
+        table takes ``masks[s]`` from ``idmap[s]``: of duplicate lines the winning line's groups.  A character-class
+        table ORs the groups of every pattern that ends in state s (``out_ids[out_first[s]:out_first[s + 1]]``)."""
+        first = getattr(self, "out_first", None)
+        ids = np.asarray(self.idmap if first is None else self.out_ids, dtype=np.int64)
+        need = max(int(self.n_patterns), int(ids.max()) if ids.size else 0) + 1
+        if isinstance(groups, np.ndarray) and groups.dtype == np.uint64:
+            by_id = groups.ravel()
+        else:
+            entries = list(groups)
+            by_id = np.zeros(len(entries), dtype=np.uint64)
+            for i, e in enumerate(entries[1:], 1):
+                for g in (() if e is None else (e,) if isinstance(e, (int, np.integer)) else e):
+                    if not 0 <= int(g) < 64:
+                        raise ValueError(f"group {int(g)} of pattern id {i} is outside 0..63")
+                    by_id[i] |= np.uint64(1) << np.uint64(int(g))
+        if by_id.size != need:
+            raise ValueError(f"need one entry per pattern id and the unused entry 0 ({need}), got {by_id.size}")
+        per = by_id[ids]
+        if first is None:
+            return np.ascontiguousarray(per[: self.num_final], dtype=np.uint64)
+        out = np.zeros(int(self.num_final), dtype=np.uint64)
+        np.bitwise_or.at(out, np.repeat(np.arange(int(self.num_final)), np.diff(np.asarray(first, dtype=np.int64))), per)
+        return out
+
     def __del__(self):
         ptr = getattr(self, "_ptr", None)
         if ptr is not None:
