@@ -694,6 +694,60 @@ int pfac_records_filter_words(pfac_ctx *ctx, int slot, const void *d_input, void
                               uint32_t edges, int prev_byte, int next_byte, const uint64_t *d_doc_offsets, uint64_t n_docs,
                               uint64_t *n_kept);
 
+/* Spans: WHERE in its document (line) a pattern may match -- ^pat, pat$, grep -x, the offset / depth qualifiers of a
+ * content rule.  One span per final state of the uploaded table; PFAC_SPAN_ANY is "not bounded".  n_states must be
+ * num_final, and every `reserved` 0, else PFAC_E_ARG and the earlier spans stay; PFAC_E_STATE before a table upload.
+ * The spans live on the device with the table, like the state groups: the next pfac_table_upload / _upload_device clears
+ * them, a second call replaces them.  The call waits for no scan; a filter already queued keeps the spans it was launched
+ * with (the old buffer is freed behind it). */
+#define PFAC_SPAN_ANY 0xFFFFFFFFu
+typedef struct pfac_state_span {   /* 16 bytes: one dwordx4 gather per record */
+    uint32_t min_start;            /* rel >= min_start                                  (Snort offset) */
+    uint32_t max_start;            /* rel <= max_start   (0: ^;  offset + depth - L)                   */
+    uint32_t max_tail;             /* tail <= max_tail   (0: $);  PFAC_SPAN_ANY: not judged            */
+    uint32_t reserved;             /* must be 0, else PFAC_E_ARG                                       */
+} pfac_state_span;
+int pfac_table_set_state_spans(pfac_ctx *ctx, const pfac_state_span *spans, uint64_t n_states);
+/* Span filter: the positional sibling of pfac_records_filter_words.  Drops, IN PLACE, the records of the slot's last
+ * finished scan whose state's span does not admit them, so that every consumer of the scan sees the admissible matches
+ * only, and a selection chooses among them.  The scan kernel is not involved.
+ * The rule.  A record (pos, s), L = the final length of s.  With documents (n_docs > 0; d_doc_offsets under the rules of
+ * pfac_records_segment), d is the last document with off[d] <= pos; n_docs == 0 means ONE document [0, n_avail).  Then
+ *   rel  = pos - off[d],  E = off[d + 1]
+ *   C    = E - 1 if delimiter >= 0 and E > off[d] and in[E - 1] == delimiter, else C = E
+ *          (a line keeps its delimiter, so `$` sits in front of it)
+ *   tail = C - (pos + L)  if pos + L <= C
+ *        = 0              if C < pos + L <= E   (the match covers the delimiter: `foo\n` from an escaped file)
+ *        = infinite       if pos + L > E        (a record that runs across its document's end fails every max_tail other
+ *                                                than PFAC_SPAN_ANY; its start rule is judged as usual)
+ *   the record is KEPT iff  min_start <= rel <= max_start && (max_tail == PFAC_SPAN_ANY || tail <= max_tail).
+ * flags & PFAC_SPANS_LINE judges every state as {0, 0, 0} -- grep -x -- and needs no spans set.
+ * Input reads: in[E - 1] alone, only for a record whose max_tail is judged, only when delimiter >= 0.  E <= n_owned <=
+ * n_avail, so no byte at or past n_avail is read.  With delimiter == -1 d_input is ignored and the input is never read.
+ * Under a folded scan the bytes are read as they are (the scan never writes its input), as in the whole-word filter.
+ * Effect, as pfac_records_filter_words: every tile's kept words are compacted to the front of the tile's own run of the
+ * heap, order preserved; tile_index[t] keeps its FIRST and gets the new COUNT; *n_kept becomes the scan's match count
+ * for everything that follows.  used, record_bytes and n_tiles of pfac_scan_format do not change, and no byte outside
+ * the words the scan itself wrote is written.  A selection made before the call is stale (pfac_replace_* return
+ * PFAC_E_STATE).  Filtering again with the same arguments changes nothing.  The filter composes with the whole-word
+ * filter in either order: the result is the intersection.
+ *   d_input        NULL = the slot's input buffer; else the buffer the scan read (16-B aligned); ignored without delimiter
+ *   d_records      NULL = the slot's heap; else the heap the scan wrote (any other pointer: PFAC_E_ARG)
+ *   delimiter      -1 = none (C = E), else the byte 0..255 that ends a line
+ *   n_docs         0 = one document [0, n_avail).  Else d_doc_offsets (NULL = the slot's, with the same n_docs) are
+ *                  checked on the device in front of the filter, whose kernel reads the check's flag and leaves at once.
+ * Returns once *n_kept is known.  Judged in this order -- PFAC_E_STATE: no finished scan, a scan made with an earlier
+ * table, no final lengths, no spans for the current table (unless PFAC_SPANS_LINE is set), an n_docs that is not that
+ * of the slot's offsets; PFAC_E_OVERFLOW: the scan overflowed its heap; PFAC_E_ARG: delimiter outside -1..255, flags
+ * outside 0..1, a misaligned d_input, a d_records that is not this scan's heap, offsets that break the rules.  Every
+ * error leaves heap, index and count as they were.
+ * Kernel: the walk of the whole-word filter (one wave per tile at a time, 64 tiles per wave); per chunk of 64 records the
+ * record, its length, its span (one 16-byte gather; registers and shuffles for tables of at most 64 final states;
+ * nothing under PFAC_SPANS_LINE), its document, a ballot, and the kept words stored at FIRST + kept + rank. */
+#define PFAC_SPANS_LINE 1u         /* every state judged as {0, 0, 0}: grep -x; needs no spans set */
+int pfac_records_filter_spans(pfac_ctx *ctx, int slot, const void *d_input, void *d_records, int delimiter,
+                              uint32_t flags, const uint64_t *d_doc_offsets, uint64_t n_docs, uint64_t *n_kept);
+
 /* Leftmost-longest, non-overlapping selection over the slot's last finished scan.  From a cursor c = entry
  * (0 <= entry <= max_pat_len of the uploaded table): take the smallest position p >= c that has a record, select its
  * record of the greatest pattern length (the last one at p), set c = p + len, repeat while records remain at or after c.

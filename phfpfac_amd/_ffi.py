@@ -34,6 +34,8 @@ PFAC_COUNT_ACCUMULATE = 1   # pfac_records_count_states / pfac_selection_count_s
 PFAC_DOCS_INVERT = 1        # pfac_documents_matching: the documents WITHOUT a kept record
 PFAC_FOLD_NONE = 0          # pfac_table_set_case_fold: an exact scan
 PFAC_FOLD_ASCII = 1         # ... the scan folds A-Z of the input to a-z
+PFAC_SPAN_ANY = 0xFFFFFFFF  # pfac_state_span: a bound that is not judged
+PFAC_SPANS_LINE = 1         # pfac_records_filter_spans: every state judged as {0, 0, 0} (grep -x)
 
 _STATUS_NAMES = {
     0: "PFAC_OK", -1: "PFAC_E_ARG", -2: "PFAC_E_IO", -3: "PFAC_E_PATTERN", -4: "PFAC_E_NOMEM",
@@ -76,6 +78,9 @@ class CThreadData(C.Structure):
                 ("HT", C.c_void_p), ("val", C.c_void_p)]
 
 
+# struct pfac_state_span as a numpy dtype (16 bytes: what pfac_table_set_state_spans takes)
+SPAN_DTYPE = [("min_start", "<u4"), ("max_start", "<u4"), ("max_tail", "<u4"), ("reserved", "<u4")]
+
 HOST_SYMBOLS = (
     "pfac_table_build_file", "pfac_table_build_file_escaped", "pfac_table_build_mem", "pfac_table_build_file_part",
     "pfac_table_build_mem_part", "pfac_merge_partitions", "pfac_table_free", "pfac_table_lookup",
@@ -103,6 +108,7 @@ HIP_SYMBOLS = (
     "pfac_documents_matching_context", "pfac_documents_gather", "pfac_documents_gather_d2h", "pfac_documents_gather_offsets_d2h",
     "pfac_table_set_case_fold", "pfac_table_case_fold",
     "pfac_table_set_state_groups", "pfac_documents_group_masks", "pfac_group_masks_d2h", "pfac_documents_matching_groups",
+    "pfac_table_set_state_spans", "pfac_records_filter_spans",
 )
 
 _host = None
@@ -252,5 +258,7 @@ def hip_lib() -> C.CDLL:
         L.pfac_documents_group_masks.argtypes = [vp, i, vp, vp, u64, vp, C.POINTER(u64)]
         L.pfac_group_masks_d2h.argtypes = [vp, i, vp, u64, u64]
         L.pfac_documents_matching_groups.argtypes = [vp, i, vp, u64, u64, u64, u64, C.c_uint32, vp, u64, C.POINTER(u64)]
+        L.pfac_table_set_state_spans.argtypes = [vp, vp, u64]
+        L.pfac_records_filter_spans.argtypes = [vp, i, vp, vp, i, C.c_uint32, vp, u64, C.POINTER(u64)]
         _hip = L
     return _hip

@@ -2686,6 +2686,95 @@ __global__ void pfac_filter_words_kernel(void *rec, unsigned long long *tix, uns
 }
 
 // ---------------------------------------------------------------------------
+// Span filter (pfac_records_filter_spans): the positional sibling of the whole-word filter -- drops, IN PLACE, the
+// records that start or end where their state's span (pfac_state_span) does not admit them.  With d the record's
+// document [base, E) (DOCS; else [0, n_avail)), rel = pos - base, C = E - 1 if the document ends in the delimiter, else
+// E, and tail = C - (pos + L), 0 where the match covers the delimiter, infinite where it runs across E:
+//   kept iff min_start <= rel <= max_start && (max_tail == PFAC_SPAN_ANY || tail <= max_tail).
+// LINE judges every state as {0, 0, 0} and loads no span.  The input is read for in[E - 1] alone, by the records whose
+// tail is judged and end inside their document, and only with a delimiter (E <= n_avail: the read stays in the buffer).
+// The grid and the walk are the whole-word filter's: one wave per tile at a time, 64 tiles per wave; per chunk of 64
+// records the record, its length, its span -- ONE 16-byte gather, or three shuffles from lane `state` when the table
+// has at most 64 final states -- its document (doc_window / doc_lookup), a ballot, heap_put at FIRST + kept + rank.
+// In place is safe for the same reason: the stores of chunk k depend on the ballot over ALL lanes' loads of chunk k, so
+// those loads have completed; they land in [FIRST, FIRST + 64 (k + 1)), at or below the chunk's own slots, and chunk
+// k + 1 loads from FIRST + 64 (k + 1) on.  Stores are record-wide (2 bytes for a 16-bit word: the dword may be shared
+// with the neighbouring tile's run, which another wave owns).  One atomicAdd per wave carries the kept total.
+template <int BYTES, bool DOCS, bool LINE>
+__global__ void pfac_filter_spans_kernel(void *rec, unsigned long long *tix, unsigned long long n_tiles, unsigned long long cap,
+                                         const unsigned char *in, unsigned long long n_avail, const short *flen,
+                                         const uint4 *spans, unsigned num_final, int delimiter,
+                                         const unsigned long long *off, unsigned long long n_docs,
+                                         const unsigned long long *bad, unsigned long long *total) {
+    if (DOCS && *bad) return;                                   // offsets that break the rules: nothing is touched
+    const int lane = threadIdx.x & (WAVE - 1);
+    const unsigned g = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const unsigned n_groups = (unsigned)((n_tiles + XGROUP - 1) / XGROUP);
+    if (g >= n_groups) return;
+    const bool fsmall = num_final <= (unsigned)WAVE;
+    const int freg = fsmall && (unsigned)lane < num_final ? (int)flen[lane] : 0;
+    uint4 sreg = make_uint4(0u, LINE ? 0u : PFAC_SPAN_ANY, LINE ? 0u : PFAC_SPAN_ANY, 0u);
+    if (!LINE && fsmall && (unsigned)lane < num_final) sreg = spans[lane];
+    const unsigned long long t = (unsigned long long)g * XGROUP + lane;
+    const unsigned long long e = t < n_tiles ? tix[t] : 0ull;
+    const unsigned c = (unsigned)(e >> TIX_CNT_SHIFT);
+    const unsigned long long lo = e & TIX_BASE_MASK;
+    unsigned long long ds = 0, de = 0, dlo = 0, dhi = 0;
+    if (DOCS && c) tile_docs(off, n_docs, t, n_tiles, ds, de, dlo, dhi);
+    unsigned mine = c;                                          // records tile t keeps
+    for (int j = 0; j < XGROUP; j++) {
+        const unsigned tc = __shfl(c, j, WAVE);
+        if (tc == 0) continue;
+        const unsigned long long tlo = __shfl(lo, j, WAVE);
+        DocWin w;
+        if (DOCS) w = doc_window(off, __shfl(dlo, j, WAVE), __shfl(dhi, j, WAVE), lane);
+        unsigned kept = 0;
+        for (unsigned c0 = 0; c0 < tc; c0 += WAVE) {
+            const unsigned i = c0 + (unsigned)lane;
+            const bool have = i < tc && tlo + i < cap;
+            unsigned pos = 0, st = 0;
+            if (have) heap_record<BYTES>(rec, tlo + i, (unsigned long long)g * XGROUP + j, pos, st);
+            const int len = final_len(flen, freg, fsmall, have, st);
+            unsigned smin = 0, smax = 0, stail = 0;             // (LINE: {0, 0, 0})
+            if (!LINE) {
+                if (fsmall) {
+                    smin = __shfl(sreg.x, (int)st, WAVE);
+                    smax = __shfl(sreg.y, (int)st, WAVE);
+                    stail = __shfl(sreg.z, (int)st, WAVE);
+                } else if (have) {
+                    const uint4 sp = spans[st];
+                    smin = sp.x; smax = sp.y; stail = sp.z;
+                }
+            }
+            unsigned long long dbase = 0, dend = n_avail;       // no documents: the one document [0, n_avail)
+            if (DOCS) {
+                unsigned long long d;
+                doc_lookup(w, off, have, pos, d, dbase, dend);
+            }
+            const unsigned long long rel = (unsigned long long)pos - dbase;
+            bool keep = have && rel >= smin && rel <= smax;
+            if (keep && stail != PFAC_SPAN_ANY) {
+                const unsigned long long pe = (unsigned long long)pos + (unsigned)(len > 0 ? len : 0);
+                if (pe > dend) keep = false;                    // runs across its document's end: the tail is infinite
+                else {
+                    unsigned long long cend = dend;             // a line keeps its delimiter: `$` sits in front of it
+                    if (delimiter >= 0 && dend > dbase && (int)in[dend - 1] == delimiter) cend = dend - 1;
+                    keep = pe >= cend || cend - pe <= stail;    // (pe > cend: the match covers the delimiter, tail 0)
+                }
+            }
+            const unsigned long long b = __ballot(keep);
+            const unsigned to = kept + (unsigned)__popcll(b & ((1ull << lane) - 1ull));
+            if (keep && to != i) heap_put<BYTES>(rec, tlo + to, pos, st);
+            kept += (unsigned)__popcll(b);
+        }
+        if (lane == j) mine = kept;
+    }
+    if (t < n_tiles && mine != c) tix[t] = lo | (unsigned long long)mine << TIX_CNT_SHIFT;
+    const unsigned long long sum = wave_sum64(mine);
+    if (lane == 0 && sum) atomicAdd(total, sum);
+}
+
+// ---------------------------------------------------------------------------
 // Leftmost-longest non-overlapping selection (pfac_records_leftmost_longest).  The greedy -- from cursor c take the
 // first position p >= c that has a record, its longest record, c = p + len -- is sequential, but with
 // M = max_pat_len the cursor that reaches tile t lies in [4096t, 4096t + M]: every earlier pick started before the
@@ -4097,11 +4186,12 @@ struct pfac_ctx {
     TablePlan plan;
     bool have_table = false;
     uint64_t table_gen = 0;               // installs begun so far: a scan's final states index the lengths of ITS table only
-    // ... what the caller attaches to it (an upload drops all five), ...
+    // ... what the caller attaches to it (an upload drops all six), ...
     DevBuf<short> flen;                   // pattern length of every final state (pfac_table_set_final_lengths)
     DevBuf<unsigned> rep_off;             // replacement of every final state (pfac_table_set_replacements): offsets[num_final + 1]
     DevBuf<unsigned char> rep;            // ... and the bytes, zero-padded to its capacity (a multiple of 16)
     DevBuf<unsigned long long> gmask;     // group set of every final state (pfac_table_set_state_groups)
+    DevBuf<uint4> spans;                  // span of every final state (pfac_table_set_state_spans): pfac_state_span as one dwordx4
     unsigned fold = PFAC_FOLD_NONE;       // case fold of the scans to come (pfac_table_set_case_fold)
     // ... and what adapts to the match density seen by the last scan (pfac_scan_finish)
     bool dense = false;                   // staging mode
@@ -4638,6 +4728,7 @@ int install_table(pfac_ctx *ctx, const int *d_blob, const int32_t *hdr, size_t n
     ctx->flen.reset(); ctx->fold = PFAC_FOLD_NONE;          // the lengths belong to the old table, and so does the case fold
     ctx->rep_off.reset(); ctx->rep.reset();                 // ... and so do the replacements
     ctx->gmask.reset();                                     // ... and the state groups
+    ctx->spans.reset();                                     // ... and the state spans
     ctx->have_table = false; ctx->table_gen++;
     TablePlan P;
     if (int rc = build_plan(ctx, P, d_blob, hdr, stream)) return rc;
@@ -5844,6 +5935,91 @@ int pfac_records_filter_words(pfac_ctx *ctx, int slot, const void *d_input, void
     if (host_u64(s, H_PASS1)) return bad_doc_offsets(ctx, s, fn);
     // the kept records ARE the scan's records from here on: its match count (a repeated pfac_scan_finish reads it from
     // the result words), and a new record set for whatever selected from the old one
+    const uint64_t total = host_u64(s, H_PASS);
+    s.last_total = total;
+    s.h_ctl[H_MATCHES] = (unsigned)total;
+    s.h_ctl[H_MATCHES + 1] = (unsigned)(total >> 32);
+    s.scan_seq++;
+    *n_kept = total;
+    return PFAC_OK;
+}
+
+int pfac_table_set_state_spans(pfac_ctx *ctx, const pfac_state_span *spans, uint64_t n_states) {
+    static_assert(sizeof(pfac_state_span) == sizeof(uint4), "a span is one dwordx4");
+    if (!ctx) return fail(nullptr, PFAC_E_ARG, "null context");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (!ctx->have_table) return fail(ctx, PFAC_E_STATE, "pfac_table_set_state_spans before a table upload");
+    if (n_states != (uint64_t)ctx->plan.base.num_final || (!spans && n_states))
+        return fail(ctx, PFAC_E_ARG, "pfac_table_set_state_spans: need num_final spans (num_final " + std::to_string(ctx->plan.base.num_final) + ")");
+    for (uint64_t i = 0; i < n_states; i++)
+        if (spans[i].reserved)
+            return fail(ctx, PFAC_E_ARG, "pfac_table_set_state_spans: reserved must be 0 (final state " + std::to_string(i) + ")");
+    USE_DEVICE(ctx);
+    // as the state groups: a buffer of its own for every call, built aside; freeing the old one waits for the device --
+    // a filter that still reads the old spans has finished before they go
+    DevBuf<uint4> fresh;
+    const uint64_t n = std::max<uint64_t>(n_states, 1);
+    int rc = fresh.ensure(ctx, nullptr, n, n);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemset(fresh.p, 0xFF, n * sizeof(uint4)));
+    if (n_states) HIP_TRY(ctx, hipMemcpy(fresh.p, spans, n_states * sizeof(uint4), hipMemcpyHostToDevice));
+    ctx->spans = std::move(fresh);
+    return PFAC_OK;
+}
+
+int pfac_records_filter_spans(pfac_ctx *ctx, int slot, const void *d_input, void *d_records, int delimiter, uint32_t flags,
+                              const uint64_t *d_doc_offsets, uint64_t n_docs, uint64_t *n_kept) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    if (!n_kept) return fail(ctx, PFAC_E_ARG, "null argument");
+    *n_kept = 0;
+    Slot &s = ctx->slots[slot];
+    const std::string fn = "pfac_records_filter_spans";
+    rc = last_scan_usable(ctx, s, fn, SCAN_FINISHED | SCAN_LENGTHS | SCAN_TABLE);
+    if (rc) return rc;
+    const bool line = (flags & PFAC_SPANS_LINE) != 0;
+    if (!line && !ctx->spans.p) return fail(ctx, PFAC_E_STATE, fn + ": no state spans for the uploaded table (pfac_table_set_state_spans)");
+    if (n_docs && !d_doc_offsets && (!s.doc.done || n_docs + 1 != s.doc.n))
+        return fail(ctx, PFAC_E_STATE, fn + ": the slot has no document offsets for this n_docs (pfac_slot_doc_offsets, pfac_slot_doc_offsets_split)");
+    rc = last_scan_usable(ctx, s, fn, SCAN_FITS);
+    if (rc) return rc;
+    if (delimiter < -1 || delimiter > 255) return fail(ctx, PFAC_E_ARG, fn + ": delimiter must be -1 (none) or 0..255");
+    if (flags > PFAC_SPANS_LINE) return fail(ctx, PFAC_E_ARG, fn + ": flags must be 0 or PFAC_SPANS_LINE");
+    void *heap = d_records ? d_records : (void *)s.records.p;
+    if (heap != s.last_records) return fail(ctx, PFAC_E_ARG, fn + ": d_records is not the record heap of the slot's last scan");
+    const unsigned char *in = nullptr;                       // no delimiter: the input is never read
+    if (delimiter >= 0) {
+        in = d_input ? static_cast<const unsigned char *>(d_input) : s.input.p;
+        if ((uintptr_t)in & 15) return fail(ctx, PFAC_E_ARG, fn + ": d_input must be 16-byte aligned");
+        if (!d_input && s.last_avail > s.input.cap) return fail(ctx, PFAC_E_ARG, fn + ": the scan read more than the slot's input buffer holds");
+        if (!in && s.last_total) return fail(ctx, PFAC_E_ARG, fn + ": no input buffer");
+    }
+    const unsigned long long *off = nullptr;
+    rc = n_docs ? resolve_docs(ctx, s, fn, d_doc_offsets, n_docs, 0, &off) : PFAC_OK;
+    if (rc) return rc;
+    USE_DEVICE(ctx);
+    const uint64_t n_tiles = s.last_tiles;
+    const unsigned n_groups = (unsigned)((n_tiles + XGROUP - 1) / XGROUP);
+    rc = ensure_gsum(ctx, s, 1);                            // the kept total and the offsets' error flag
+    if (rc) return rc;
+    unsigned long long *res = s.gsum.p;
+    HIP_TRY(ctx, hipMemsetAsync(res, 0, 16, s.stream));
+    if (n_docs) launch_offsets_check(ctx, s, off, n_docs, res + 1);     // in front of the filter
+    if (n_groups) {
+        const bool dk = n_docs != 0;
+        auto fk = by_width(s.last_rec_bytes, [dk, line](auto w) {
+            return dk ? (line ? pfac_filter_spans_kernel<w(), true, true> : pfac_filter_spans_kernel<w(), true, false>)
+                      : (line ? pfac_filter_spans_kernel<w(), false, true> : pfac_filter_spans_kernel<w(), false, false>);
+        });
+        hipLaunchKernelGGL(fk, dim3((n_groups + 3) / 4), dim3(256), 0, s.stream, heap, s.tile_index.p, (unsigned long long)n_tiles,
+                           (unsigned long long)s.last_cap, in, (unsigned long long)s.last_avail, ctx->flen.p,
+                           (const uint4 *)(line ? nullptr : ctx->spans.p), (unsigned)ctx->plan.base.num_final, delimiter, off,
+                           (unsigned long long)n_docs, (const unsigned long long *)(res + 1), res);
+    }
+    rc = pass_words(ctx, s, res, 2);
+    if (rc) return rc;
+    if (host_u64(s, H_PASS1)) return bad_doc_offsets(ctx, s, fn);
+    // as after the whole-word filter: the kept records ARE the scan's records from here on
     const uint64_t total = host_u64(s, H_PASS);
     s.last_total = total;
     s.h_ctl[H_MATCHES] = (unsigned)total;

@@ -13,7 +13,7 @@ from typing import Optional, Tuple
 
 import numpy as np
 
-from ._ffi import (PFAC_COUNT_ACCUMULATE, PFAC_DOCS_INVERT, PFAC_E_OVERFLOW, PFAC_FOLD_ASCII, PFAC_FOLD_NONE, PFAC_WORD_LEFT, PFAC_WORD_RIGHT, CRecord, PfacError,
+from ._ffi import (PFAC_COUNT_ACCUMULATE, PFAC_DOCS_INVERT, PFAC_E_OVERFLOW, PFAC_FOLD_ASCII, PFAC_FOLD_NONE, PFAC_SPANS_LINE, PFAC_WORD_LEFT, PFAC_WORD_RIGHT, CRecord, PfacError,
                    hip_lib)
 from .table import RECORD_DTYPE, PfacTable, redaction_table, replacement_table
 
@@ -367,6 +367,33 @@ class GpuMatcher:
         self._last_n[slot] = n.value
         return n.value
 
+    # -- anchored matches: where in a line a pattern may match ----------------
+    def set_pattern_spans(self, rules) -> None:
+        """The span of every pattern of the uploaded table (``PfacTable.state_spans``: one entry per 1-based pattern id
+        -- None, ``"^"``, ``"$"``, ``"^$"`` or ``(min_start, max_start, max_tail)``; ``strip_anchors`` makes them from
+        grep's pattern lines), kept on the device until the next table upload (``pfac_table_set_state_spans``)."""
+        if self.table is None:
+            raise PfacError(-7, "no host table to map pattern ids to states (load_table first)")
+        spans = self.table.state_spans(rules)
+        self._check(self._L.pfac_table_set_state_spans(self._ctx, spans.ctypes.data if spans.size else None, spans.size))
+
+    def filter_spans(self, slot: int = 0, delimiter=None, line_match: bool = False, n_docs: int = 0, d_doc_offsets=None,
+                     d_input=None, d_records=None) -> int:
+        """Drops, in place on the GPU, the records of the slot's last finished scan that their pattern's span does not
+        admit (``pfac_records_filter_spans``): a match must start ``min_start .. max_start`` bytes into its document and
+        end at most ``max_tail`` bytes in front of the document's end -- in front of its ``delimiter`` (a byte or its
+        value; None = none) where the document ends in one.  ``line_match``: every pattern must cover its whole line
+        (``grep -x``), whatever spans are set.  ``n_docs`` 0: the scanned buffer is the one document; else
+        ``d_doc_offsets`` (None = the slot's) cut it.  Everything that reads the scan afterwards sees the kept records
+        only.  Returns their number, which ``last_count`` reports from then on."""
+        n = C.c_uint64(0)
+        self._check(self._L.pfac_records_filter_spans(self._ctx, slot, _ptr(d_input), _ptr(d_records),
+                                                      -1 if delimiter is None else _delimiter_byte(delimiter),
+                                                      PFAC_SPANS_LINE if line_match else 0, _ptr(d_doc_offsets), int(n_docs),
+                                                      C.byref(n)))
+        self._last_n[slot] = n.value
+        return n.value
+
     # -- counts per pattern --------------------------------------------------
     def _n_states(self) -> int:
         if self.table is None:
@@ -488,10 +515,11 @@ class GpuMatcher:
             self.table._final_lengths = lens          # once per table
         self.set_final_lengths(lens)
 
-    def _scan_docs(self, docs, slot: int, whole_words=False) -> Tuple[np.ndarray, int]:
+    def _scan_docs(self, docs, slot: int, whole_words=False, spans: bool = False, line_match: bool = False) -> Tuple[np.ndarray, int]:
         """Upload and scan a batch of documents (``docs`` as ``scan_documents`` takes it) and set its offsets on the
-        slot; with ``whole_words`` the whole-word filter follows, document ends being boundaries.  Returns (offsets
-        uint64[n_docs + 1], n_docs)."""
+        slot; with ``whole_words`` the whole-word filter follows, document ends being boundaries; with ``spans`` (the
+        rules of ``set_pattern_spans``) or ``line_match`` (every pattern covers its whole document) the span filter
+        follows that, without a delimiter.  Returns (offsets uint64[n_docs + 1], n_docs)."""
         buf, offsets = _docs_buffer(docs)
         n = int(buf.size)
         self._ensure_final_lengths()
@@ -502,15 +530,19 @@ class GpuMatcher:
         self.set_doc_offsets(offsets, slot)
         if whole_words is not False and offsets.size > 1:
             self.filter_whole_words(slot, _word_bytes(whole_words), n_docs=int(offsets.size) - 1)
+        if (spans or line_match) and offsets.size > 1:
+            self.filter_spans(slot, None, line_match, n_docs=int(offsets.size) - 1)
         return offsets, int(offsets.size) - 1
 
-    def scan_documents(self, docs, slot: int = 0, whole_words=False) -> Tuple[np.ndarray, np.ndarray]:
+    def scan_documents(self, docs, slot: int = 0, whole_words=False, spans: bool = False, line_match: bool = False) -> Tuple[np.ndarray, np.ndarray]:
         """Match a batch of independent documents in one scan.  ``docs`` is a sequence of bytes-like objects, or a
         ``(buffer, offsets)`` pair whose offsets (an integer array or list, n_docs + 1 of them, from 0 to len(buffer))
         cut ``buffer`` into documents.  Returns (doc_first uint64[n_docs + 1], records): the records of document d are
         ``records[doc_first[d]:doc_first[d + 1]]``, positions relative to the document, in (offset, pattern length)
-        order -- what scanning each document on its own yields (and, with ``whole_words``, filtering it on its own)."""
-        _, n_docs = self._scan_docs(docs, slot, whole_words)
+        order -- what scanning each document on its own yields (and, with ``whole_words``, filtering it on its own).
+        ``spans``: only the matches that the patterns' spans (``set_pattern_spans``) admit in their document;
+        ``line_match``: only those that cover their whole document (``filter_spans``, behind the whole-word filter)."""
+        _, n_docs = self._scan_docs(docs, slot, whole_words, spans, line_match)
         kept = self.segment_records(n_docs, slot=slot)
         return self.segment_to_host(kept, n_docs, slot)
 
@@ -584,10 +616,12 @@ class GpuMatcher:
         return self._to_host(slot, lambda p: self._L.pfac_documents_gather_offsets_d2h(self._ctx, slot, p),
                              (int(n_ids) + 1, np.uint64))
 
-    def _scan_lines(self, data, delimiter, slot: int, whole_words=False, fetch_offsets: bool = True) -> Tuple[Optional[np.ndarray], int]:
+    def _scan_lines(self, data, delimiter, slot: int, whole_words=False, fetch_offsets: bool = True, spans: bool = False,
+                    line_match: bool = False) -> Tuple[Optional[np.ndarray], int]:
         """``_scan_docs`` for one buffer whose documents end at ``delimiter``: upload, scan, offsets made on the device
         (only they come back, for the caller -- not even they with ``fetch_offsets`` False), then the whole-word filter
-        if asked for.  Returns (offsets uint64[n_docs + 1] or None, n_docs)."""
+        and the span filter (with the lines' ``delimiter``: ``$`` sits in front of it) if asked for.  Returns (offsets
+        uint64[n_docs + 1] or None, n_docs)."""
         buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data.view(np.uint8).ravel()
         n = int(buf.size)
         self._ensure_final_lengths()
@@ -598,20 +632,22 @@ class GpuMatcher:
         n_docs, _ = self.split_documents(n, delimiter, slot=slot)
         if whole_words is not False and n_docs:
             self.filter_whole_words(slot, _word_bytes(whole_words), n_docs=n_docs)
+        if (spans or line_match) and n_docs:
+            self.filter_spans(slot, delimiter, line_match, n_docs=n_docs)
         return (self.doc_offsets_to_host(n_docs, slot) if fetch_offsets else None), n_docs
 
-    def scan_lines(self, data, delimiter=b"\n", slot: int = 0, whole_words=False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    def scan_lines(self, data, delimiter=b"\n", slot: int = 0, whole_words=False, spans: bool = False, line_match: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """``scan_documents`` of one buffer cut into lines at ``delimiter`` on the device (a line keeps its
         delimiter).  Returns (doc_first, records, offsets uint64[n_docs + 1])."""
-        offsets, n_docs = self._scan_lines(data, delimiter, slot, whole_words)
+        offsets, n_docs = self._scan_lines(data, delimiter, slot, whole_words, spans=spans, line_match=line_match)
         kept = self.segment_records(n_docs, slot=slot)
         first, rec = self.segment_to_host(kept, n_docs, slot)
         return first, rec, offsets
 
-    def select_lines(self, data, delimiter=b"\n", slot: int = 0, whole_words=False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    def select_lines(self, data, delimiter=b"\n", slot: int = 0, whole_words=False, spans: bool = False, line_match: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """``select_documents`` of one buffer cut into lines at ``delimiter`` on the device.  Returns (doc_first,
         records with positions relative to the line, offsets)."""
-        offsets, n_docs = self._scan_lines(data, delimiter, slot, whole_words)
+        offsets, n_docs = self._scan_lines(data, delimiter, slot, whole_words, spans=spans, line_match=line_match)
         n = self.select_leftmost_longest_documents(n_docs, slot=slot)
         first, rec = self.doc_selection_to_host(n, n_docs, slot)
         if n:
@@ -619,35 +655,38 @@ class GpuMatcher:
             rec["pos"] -= offsets[doc].astype(np.uint32)
         return first, rec, offsets
 
-    def replace_lines(self, data, delimiter=b"\n", slot: int = 0, whole_words=False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    def replace_lines(self, data, delimiter=b"\n", slot: int = 0, whole_words=False, spans: bool = False, line_match: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """``replace_documents`` of one buffer cut into lines at ``delimiter`` on the device.  Returns (out_offsets,
         out, offsets)."""
-        offsets, n_docs = self._scan_lines(data, delimiter, slot, whole_words)
+        offsets, n_docs = self._scan_lines(data, delimiter, slot, whole_words, spans=spans, line_match=line_match)
         self.select_leftmost_longest_documents(n_docs, slot=slot)
         n = self.replace_selection_documents(slot=slot)
         out_off = self.replacement_doc_offsets_to_host(n_docs, slot)
         return out_off, self.replacement_to_host(n, slot), offsets
 
-    def matching_lines(self, data, delimiter=b"\n", invert: bool = False, slot: int = 0, whole_words=False) -> Tuple[np.ndarray, np.ndarray]:
+    def matching_lines(self, data, delimiter=b"\n", invert: bool = False, slot: int = 0, whole_words=False, spans: bool = False,
+                       line_match: bool = False) -> Tuple[np.ndarray, np.ndarray]:
         """Which lines of ``data`` hold a match (``invert``: hold none) -- ``grep -F -f patterns``, ``-v``: scan, split,
         document cut and compaction on the device; only the ids and the offsets come back.  Returns (ids uint64,
         offsets uint64[n_docs + 1]): line k is ``data[offsets[ids[k]]:offsets[ids[k] + 1]]``."""
-        offsets, n_docs = self._scan_lines(data, delimiter, slot, whole_words)
+        offsets, n_docs = self._scan_lines(data, delimiter, slot, whole_words, spans=spans, line_match=line_match)
         self.segment_records(n_docs, slot=slot)
         n = self.matching_documents(n_docs, invert=invert, slot=slot)
         return self.matching_documents_to_host(n, slot), offsets
 
     def grep_lines(self, data, delimiter=b"\n", invert: bool = False, before: int = 0, after: int = 0, slot: int = 0,
-                   whole_words=False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+                   whole_words=False, spans: bool = False, line_match: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """The lines of ``data`` that hold a match, as bytes -- what ``grep -F -f patterns`` prints (``invert``: ``-v``;
         ``before`` / ``after``: ``-B`` / ``-A``, without the ``--`` separators): scan, split, document cut, compaction
         and gather on the device, from the slot's own input, offsets and ids.  Only the selected lines' bytes, their
         offsets and their ids come back.  Returns (out uint8[out_bytes], out_offsets uint64[n + 1], ids uint64[n]):
-        selected line k is ``out[out_offsets[k]:out_offsets[k + 1]]``, line ``ids[k]`` of the input."""
+        selected line k is ``out[out_offsets[k]:out_offsets[k + 1]]``, line ``ids[k]`` of the input.  ``spans``: the
+        patterns match only where their spans admit them (``set_pattern_spans``: ``^pat``, ``pat$``, offset / depth;
+        ``$`` sits in front of the line's delimiter); ``line_match``: ``grep -x``, a pattern must be the whole line."""
         buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data.view(np.uint8).ravel()
         if invert and (before or after):
             raise ValueError("context lines (before / after) do not combine with invert")
-        _, n_docs = self._scan_lines(buf, delimiter, slot, whole_words, fetch_offsets=False)
+        _, n_docs = self._scan_lines(buf, delimiter, slot, whole_words, fetch_offsets=False, spans=spans, line_match=line_match)
         self.segment_records(n_docs, slot=slot)
         n = self.matching_documents(n_docs, invert=invert, slot=slot, before=before, after=after)
         out_bytes = self.gather_documents(n_docs, n, int(buf.size), slot=slot)
@@ -697,29 +736,30 @@ class GpuMatcher:
                                                     PFAC_DOCS_INVERT if invert else 0, _ptr(d_out), int(out_cap), C.byref(n))
         return self._counted(rc, n, "n_matching")
 
-    def tag_documents(self, docs, whole_words=False, slot: int = 0) -> np.ndarray:
+    def tag_documents(self, docs, whole_words=False, slot: int = 0, spans: bool = False, line_match: bool = False) -> np.ndarray:
         """The group mask of every document of a batch (``docs`` as ``scan_documents`` takes it) in one scan: uint64
         [n_docs], bit g set iff a pattern of group g (``set_pattern_groups``) matches inside the document.  Only the
         masks come back."""
-        _, n_docs = self._scan_docs(docs, slot, whole_words)
+        _, n_docs = self._scan_docs(docs, slot, whole_words, spans, line_match)
         self.document_group_masks(n_docs, slot=slot)
         return self.group_masks_to_host(n_docs, slot)
 
-    def tag_lines(self, data, delimiter=b"\n", whole_words=False, slot: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+    def tag_lines(self, data, delimiter=b"\n", whole_words=False, slot: int = 0, spans: bool = False, line_match: bool = False) -> Tuple[np.ndarray, np.ndarray]:
         """``tag_documents`` of one buffer cut into lines at ``delimiter`` on the device.  Returns (offsets uint64
         [n_docs + 1], masks uint64[n_docs])."""
-        offsets, n_docs = self._scan_lines(data, delimiter, slot, whole_words)
+        offsets, n_docs = self._scan_lines(data, delimiter, slot, whole_words, spans=spans, line_match=line_match)
         self.document_group_masks(n_docs, slot=slot)
         return offsets, self.group_masks_to_host(n_docs, slot)
 
     def grep_lines_where(self, data, all_of: int = 0, any_of: int = 0, none_of: int = 0, invert: bool = False,
-                         delimiter=b"\n", whole_words=False, slot: int = 0) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+                         delimiter=b"\n", whole_words=False, slot: int = 0, spans: bool = False,
+                         line_match: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """The lines of ``data`` whose pattern groups satisfy the predicate of ``matching_documents_where``, as bytes --
         several ``grep -e`` groups joined by AND and NOT: scan, split, the mask pass, the predicate and the gather on
         the device, with no document cut in between.  Returns what ``grep_lines`` returns: (out uint8[out_bytes],
         out_offsets uint64[n + 1], ids uint64[n])."""
         buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data.view(np.uint8).ravel()
-        _, n_docs = self._scan_lines(buf, delimiter, slot, whole_words, fetch_offsets=False)
+        _, n_docs = self._scan_lines(buf, delimiter, slot, whole_words, fetch_offsets=False, spans=spans, line_match=line_match)
         self.document_group_masks(n_docs, slot=slot)
         n = self.matching_documents_where(n_docs, all_of, any_of, none_of, invert=invert, slot=slot)
         out_bytes = self.gather_documents(n_docs, n, int(buf.size), slot=slot)
@@ -785,12 +825,12 @@ class GpuMatcher:
                                    (n_selected, RECORD_DTYPE), (int(n_docs) + 1, np.uint64))
         return first, rec
 
-    def select_documents(self, docs, slot: int = 0, whole_words=False) -> Tuple[np.ndarray, np.ndarray]:
+    def select_documents(self, docs, slot: int = 0, whole_words=False, spans: bool = False, line_match: bool = False) -> Tuple[np.ndarray, np.ndarray]:
         """Leftmost-longest selection of a batch of independent documents (``docs`` as ``scan_documents`` takes it) in
         one scan.  Returns (doc_first uint64[n_docs + 1], records): the picks of document d are
         ``records[doc_first[d]:doc_first[d + 1]]``, positions relative to the document -- what
         ``scan_leftmost_longest`` of each document on its own returns."""
-        offsets, n_docs = self._scan_docs(docs, slot, whole_words)
+        offsets, n_docs = self._scan_docs(docs, slot, whole_words, spans, line_match)
         n = self.select_leftmost_longest_documents(n_docs, slot=slot)
         first, rec = self.doc_selection_to_host(n, n_docs, slot)
         if n:
@@ -870,11 +910,11 @@ class GpuMatcher:
         return self._to_host(slot, lambda p: self._L.pfac_replace_documents_d2h(self._ctx, slot, p),
                              (int(n_docs) + 1, np.uint64))
 
-    def replace_documents(self, docs, slot: int = 0, whole_words=False) -> Tuple[np.ndarray, np.ndarray]:
+    def replace_documents(self, docs, slot: int = 0, whole_words=False, spans: bool = False, line_match: bool = False) -> Tuple[np.ndarray, np.ndarray]:
         """Find-and-replace in a batch of independent documents (``docs`` as ``scan_documents`` takes it) in one scan,
         every document on its own.  Returns (out_offsets uint64[n_docs + 1], out uint8[out_bytes]): document d's
         output is ``out[out_offsets[d]:out_offsets[d + 1]]`` -- what ``replace`` of each document alone returns."""
-        _, n_docs = self._scan_docs(docs, slot, whole_words)
+        _, n_docs = self._scan_docs(docs, slot, whole_words, spans, line_match)
         self.select_leftmost_longest_documents(n_docs, slot=slot)
         n = self.replace_selection_documents(slot=slot)
         out_off = self.replacement_doc_offsets_to_host(n_docs, slot)

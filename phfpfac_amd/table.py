@@ -11,9 +11,11 @@ import os
 
 import numpy as np
 
-from ._ffi import CTable, PfacError, host_lib
+from ._ffi import PFAC_SPAN_ANY, CTable, PfacError, host_lib
+from ._ffi import SPAN_DTYPE as _SPAN_FIELDS
 
 RECORD_DTYPE = np.dtype([("pos", np.uint32), ("state", np.uint32)])
+SPAN_DTYPE = np.dtype(_SPAN_FIELDS)         # struct pfac_state_span
 
 
 class PfacTable:
@@ -217,6 +219,41 @@ class PfacTable:
         np.bitwise_or.at(out, np.repeat(np.arange(int(self.num_final)), np.diff(np.asarray(first, dtype=np.int64))), per)
         return out
 
+    def state_spans(self, rules) -> np.ndarray:
+        """Anchors and offsets of the patterns -> ``SPAN_DTYPE[num_final]`` for ``pfac_table_set_state_spans``.
+        ``rules`` is indexed by the 1-based pattern id (entry 0 is unused), one entry per id the table can report, as in
+        ``state_group_masks``.  An entry is None (anywhere), ``"^"`` (at its line's start), ``"$"`` (at its end, in
+        front of the delimiter), ``"^$"`` (the whole line), or ``(min_start, max_start, max_tail)`` with None for a
+        bound that is not judged -- Snort's ``offset`` o and ``depth`` d of a pattern of length L are ``(o, o + d - L,
+        None)``; a negative ``max_start`` (a depth shorter than the pattern) admits no start.  A literal table takes the
+        rule of ``idmap[s]``: of duplicate lines the winning line's.  On a character-class table the ids that share a
+        final state must carry the same rule: ValueError names them."""
+        first = getattr(self, "out_first", None)
+        ids = np.asarray(self.idmap if first is None else self.out_ids, dtype=np.int64)
+        need = max(int(self.n_patterns), int(ids.max()) if ids.size else 0) + 1
+        entries = list(rules)
+        if len(entries) != need:
+            raise ValueError(f"need one entry per pattern id and the unused entry 0 ({need}), got {len(entries)}")
+        by_id = np.zeros(need, dtype=SPAN_DTYPE)
+        by_id["max_start"] = by_id["max_tail"] = PFAC_SPAN_ANY
+        for i, e in enumerate(entries[1:], 1):
+            by_id[i] = _span_of(e, i)
+        per = by_id[ids]
+        if first is None:
+            return np.ascontiguousarray(per[: self.num_final])
+        first = np.asarray(first, dtype=np.int64)
+        out = np.zeros(int(self.num_final), dtype=SPAN_DTYPE)
+        out["max_start"] = out["max_tail"] = PFAC_SPAN_ANY          # (a state no pattern ends in)
+        for s in range(int(self.num_final)):
+            mine = per[first[s]:first[s + 1]]
+            if mine.size:
+                odd = np.flatnonzero(mine != mine[0])
+                if odd.size:
+                    a, b = int(ids[first[s]]), int(ids[first[s] + odd[0]])
+                    raise ValueError(f"pattern ids {a} and {b} end in one final state ({s}) but carry different span rules")
+                out[s] = mine[0]
+        return out
+
     def __del__(self):
         ptr = getattr(self, "_ptr", None)
         if ptr is not None:
@@ -225,6 +262,46 @@ class PfacTable:
             except Exception:
                 pass
             self._ptr = None
+
+
+_ANCHORS = {"^": (0, 0, None), "$": (0, None, 0), "^$": (0, 0, 0)}
+
+
+def _span_of(rule, pattern_id: int) -> tuple:
+    """One entry of ``PfacTable.state_spans`` -> (min_start, max_start, max_tail, 0) in the struct's terms."""
+    if rule is None:
+        return (0, PFAC_SPAN_ANY, PFAC_SPAN_ANY, 0)
+    if isinstance(rule, str):
+        if rule not in _ANCHORS:
+            raise ValueError(f"the rule of pattern id {pattern_id} must be one of {sorted(_ANCHORS)}, a tuple or None")
+        rule = _ANCHORS[rule]
+    lo, hi, tail = rule
+    lo = 0 if lo is None else int(lo)
+    hi = PFAC_SPAN_ANY if hi is None else int(hi)
+    tail = PFAC_SPAN_ANY if tail is None else int(tail)
+    if hi < 0:                              # no admissible start: min_start > max_start
+        lo, hi = 1, 0
+    if not (0 <= lo <= PFAC_SPAN_ANY and hi <= PFAC_SPAN_ANY and 0 <= tail <= PFAC_SPAN_ANY):
+        raise ValueError(f"the rule of pattern id {pattern_id} is outside 0..2^32 - 1")
+    return (lo, hi, tail, 0)
+
+
+def strip_anchors(lines) -> tuple:
+    """Pattern lines with grep's anchors -> (lines, rules): a leading ``^`` and a trailing ``$`` are taken off every
+    line (bytes) and become the line's rule for ``PfacTable.state_spans`` (``rules[0]`` is the unused entry 0, line k
+    has pattern id k + 1).  Escapes are not handled: a caller whose patterns hold a literal ``^`` or ``$`` there passes
+    the rules itself.  Two lines that differ only in their anchors become duplicate lines: one final state, and the
+    winning line's rule.  A line that is empty after stripping raises ValueError."""
+    out, rules = [], [None]
+    for k, line in enumerate(lines):
+        line = bytes(line)
+        head, tail = line.startswith(b"^"), line.endswith(b"$") and len(line) > (1 if line.startswith(b"^") else 0)
+        body = line[1 if head else 0:len(line) - (1 if tail else 0)]
+        if not body:
+            raise ValueError(f"pattern line {k + 1} is empty once its anchors are stripped")
+        out.append(body)
+        rules.append(("^" if head else "") + ("$" if tail else "") or None)
+    return out, rules
 
 
 def fold_ascii(data) -> np.ndarray:
