@@ -509,7 +509,8 @@ int pfac_records_segment(pfac_ctx *ctx, int slot, const void *d_records, const u
  * pfac_slot_reserve, pfac_slot_doc_offsets and pfac_table_set_replacements (a replace output holds the bytes of the
  * replacements set when it ran).  The next call of the same pass discards it even when that call fails; the fetch then
  * returns PFAC_E_STATE, as it does when the pass wrote into the caller's buffers.  The two selections share one
- * slot-owned buffer and count as one pass here; so do the two replaces. */
+ * slot-owned buffer and count as one pass here; so do the two replaces.  The extraction
+ * (pfac_extract_leftmost_longest) is a pass of its own: neither it nor a replace discards the other's result. */
 int pfac_segment_d2h(pfac_ctx *ctx, int slot, pfac_record *host_records, uint64_t *host_doc_first);
 
 /* Which documents matched?  (grep -F -f patterns over lines; PFAC_DOCS_INVERT: grep -v.)  Document d is reported iff
@@ -854,6 +855,56 @@ int pfac_replace_documents(pfac_ctx *ctx, int slot, const void *d_input, const p
 /* D2H of the slot-owned output offsets of the last pfac_replace_documents (n_docs + 1 entries).  Asynchronous on the
  * slot's stream; pfac_slot_sync completes it. */
 int pfac_replace_documents_d2h(pfac_ctx *ctx, int slot, uint64_t *host_out_offsets);
+
+/* Replacement templates: replacements that quote the matched text (sed's `&`, grep --color, <mark>...</mark>,
+ * [ORG:...]).  offsets, bytes and n_bytes follow the contract, the limits and the errors of pfac_table_set_replacements;
+ * splits holds one entry per final state:
+ *   splits[s] == PFAC_TEMPLATE_PLAIN   a pick of state s is replaced by R_s, as pfac_table_set_replacements has it
+ *   splits[s] <= R_s                   the pick (p, s) of length L is rewritten to
+ *                                        R_s[:split] + input[p : p + L] + R_s[split:]
+ *                                      with the input's bytes as the caller wrote them -- under a case fold
+ *                                      (pfac_table_set_case_fold) the matcher saw folded bytes, the output carries the
+ *                                      unfolded ones.  One quote of the whole match per template.
+ *   any other value                    PFAC_E_ARG
+ * splits == NULL: every state is plain, which is pfac_table_set_replacements; that call itself clears the splits.
+ * Everything is checked before anything changes: a refused call leaves the earlier replacements and splits in force.
+ * The splits are one more device attachment of the installed table: a table upload drops them with the replacements.
+ * The old buffers are freed behind the device's queued work (a write kernel that still reads them has finished), as
+ * the spans and the groups are.
+ * With templates pfac_replace_leftmost_longest and pfac_replace_documents keep their signatures and contracts:
+ *   *out_bytes = n_owned + exit - entry + sum_k (R_k - L_k * [state s_k is plain]),
+ * out_off[d] of the documents call follows the same per-pick delta, chained ranges still concatenate (a pick that
+ * starts below n_owned and ends in the halo is emitted whole by the range that owns its start), and input reads stay
+ * inside [0, n_avail).  While no state quotes, the replaces run the kernels they ran before this call existed. */
+#define PFAC_TEMPLATE_PLAIN 0xFFFFFFFFu
+int pfac_table_set_replacement_templates(pfac_ctx *ctx, const uint32_t *offsets, const uint32_t *splits,
+                                         uint64_t n_states, const void *bytes, uint64_t n_bytes);
+
+/* Match extraction (grep -o): the rewritten picks of the slot's last leftmost-longest selection alone, back to back,
+ *   E_0 + E_1 + ... + E_{n-1},   E_k = R_k[:split] + input[p_k : p_k + L_k] + R_k[split:]   (a plain state: R_k alone)
+ * with no gaps between them and no tail behind them.  With the template (b"", b"\n") on every state this is what
+ * grep -o prints.
+ *   d_input, d_sel   as pfac_replace_leftmost_longest; the selection may be the whole-stream one or the per-document one
+ *                    (document d's matches are out[pick_off[doc_first[d]] : pick_off[doc_first[d + 1]]])
+ *   d_out            NULL = a slot-owned buffer OF THE EXTRACTION's own (fetched with pfac_extract_d2h): a later replace
+ *                    does not invalidate it, nor does an extraction invalidate the replace's; else a device pointer,
+ *                    16-B aligned, of out_cap bytes.  No byte at or past *out_bytes is written.
+ *   d_pick_offsets   pick_off[k] = the output offset of E_k, pick_off[n] = *out_bytes: n + 1 entries (n = the
+ *                    selection's count), 8-B aligned; NULL = a slot-owned buffer (pfac_extract_offsets_d2h)
+ * *out_bytes = sum_k |E_k|; no picks: zero bytes and pick_off[0] = 0.  Preconditions, argument checks, PFAC_E_OVERFLOW
+ * (with *out_bytes exact, nothing written -- the pick offsets neither) and PFAC_E_STATE are those of
+ * pfac_replace_leftmost_longest, in its order.  Chained ranges concatenate; the caller rebases the offsets by the
+ * bytes of the ranges before.
+ * Kernels: the replace's three with every gap taken as empty and no tail segment -- the count pass sums |E_k|, the
+ * write is the same output-driven one, and the per-pick prefix kernel of pfac_replace_documents writes the offsets. */
+int pfac_extract_leftmost_longest(pfac_ctx *ctx, int slot, const void *d_input, const pfac_record *d_sel,
+                                  void *d_out, uint64_t out_cap, uint64_t *d_pick_offsets, uint64_t *out_bytes);
+/* D2H of bytes [first, first + n) of the slot-owned output of the last pfac_extract_leftmost_longest.  Asynchronous on
+ * the slot's stream; pfac_slot_sync completes it. */
+int pfac_extract_d2h(pfac_ctx *ctx, int slot, void *host, uint64_t first, uint64_t n);
+/* D2H of the slot-owned pick offsets of the last pfac_extract_leftmost_longest (n + 1 entries).  Asynchronous on the
+ * slot's stream; pfac_slot_sync completes it. */
+int pfac_extract_offsets_d2h(pfac_ctx *ctx, int slot, uint64_t *host_pick_offsets);
 
 /* Synthetic input generators, written straight into device memory (the
  * reference built big inputs by tiling a small text, creatbiginput.sh:2-5).

@@ -6,7 +6,7 @@ the scan runs in a hand-written gfx950 HIP kernel (``csrc/pfac_hip.hip``) behind
 ``torch.distributed`` plumbing that shards the input byte stream across GPUs.
 """
 from ._ffi import PFAC_COUNT_ACCUMULATE, PfacError  # noqa: F401
-from .table import RECORD_DTYPE, SPAN_DTYPE, PfacTable, emit_packed, emit_records, emit_records_multi, fold_ascii, merge_partitions, replacement_table, strip_anchors  # noqa: F401
+from .table import RECORD_DTYPE, SPAN_DTYPE, PfacTable, emit_packed, emit_records, emit_records_multi, fold_ascii, merge_partitions, replacement_table, strip_anchors, template_table  # noqa: F401
 from .matcher import GpuMatcher, device_count, word_set  # noqa: F401
 
-__all__ = ["PfacError", "PfacTable", "GpuMatcher", "RECORD_DTYPE", "emit_records", "emit_packed", "emit_records_multi", "merge_partitions", "replacement_table", "fold_ascii", "device_count", "word_set", "PFAC_COUNT_ACCUMULATE", "SPAN_DTYPE", "strip_anchors"]
+__all__ = ["PfacError", "PfacTable", "GpuMatcher", "RECORD_DTYPE", "emit_records", "emit_packed", "emit_records_multi", "merge_partitions", "replacement_table", "fold_ascii", "device_count", "word_set", "PFAC_COUNT_ACCUMULATE", "SPAN_DTYPE", "strip_anchors", "template_table"]

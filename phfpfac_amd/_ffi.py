@@ -109,6 +109,7 @@ HIP_SYMBOLS = (
     "pfac_table_set_case_fold", "pfac_table_case_fold",
     "pfac_table_set_state_groups", "pfac_documents_group_masks", "pfac_group_masks_d2h", "pfac_documents_matching_groups",
     "pfac_table_set_state_spans", "pfac_records_filter_spans",
+    "pfac_table_set_replacement_templates", "pfac_extract_leftmost_longest", "pfac_extract_d2h", "pfac_extract_offsets_d2h",
 )
 
 _host = None
@@ -240,6 +241,10 @@ def hip_lib() -> C.CDLL:
         L.pfac_leftmost_longest_documents_d2h.argtypes = [vp, i, vp, vp]
         L.pfac_replace_documents.argtypes = [vp, i, vp, vp, vp, vp, vp, u64, vp, C.POINTER(u64)]
         L.pfac_replace_documents_d2h.argtypes = [vp, i, vp]
+        L.pfac_table_set_replacement_templates.argtypes = [vp, vp, vp, u64, vp, u64]
+        L.pfac_extract_leftmost_longest.argtypes = [vp, i, vp, vp, vp, u64, vp, C.POINTER(u64)]
+        L.pfac_extract_d2h.argtypes = [vp, i, vp, u64, u64]
+        L.pfac_extract_offsets_d2h.argtypes = [vp, i, vp]
         L.pfac_records_filter_words.argtypes = [vp, i, vp, vp, vp, C.c_uint32, i, i, vp, u64, C.POINTER(u64)]
         L.pfac_records_count_states.argtypes = [vp, i, vp, vp, u64, C.c_uint32, C.POINTER(u64)]
         L.pfac_selection_count_states.argtypes = [vp, i, vp, vp, u64, C.c_uint32, C.POINTER(u64)]

@@ -3191,6 +3191,9 @@ __global__ void pfac_ll_doc_write_kernel(const void *rec, const unsigned long lo
 //                            merges the pieces of its chunk in registers and stores it with one dwordx4.
 // Blocks whose segments are all empty (deletions with no gap between them) are never loaded: after a block the next
 // one is found by galloping from it, so a window costs its bytes times a log factor, whatever collapses into it.
+// With replacement templates (pfac_table_set_replacement_templates) a quoting state's segment is its gap, R[:split],
+// the matched input bytes [p_k, p_k + L_k), then R[split:], and D_k sums R_j - L_j [j plain].  The match extraction
+// (pfac_extract_leftmost_longest) is the same write with every gap empty and no segment n.
 
 constexpr int RP_BLOCK = 64;                        // picks per block (one wave)
 constexpr int RP_GROUP = 16;                        // blocks per workgroup of the count kernel (1024 picks)
@@ -3207,10 +3210,16 @@ __device__ __forceinline__ unsigned long long wave_incl_scan64(unsigned long lon
     return x;
 }
 
+// The three kernels are templates on <TEMPLATES, GAPS>.  TEMPLATES: some state quotes its match (split[s] !=
+// PFAC_TEMPLATE_PLAIN: the pick becomes R[:split] + input[p, p + L) + R[split:], so its delta is R, not R - L).  GAPS
+// false is the extraction (pfac_extract_leftmost_longest): the same segments without their gaps and without the tail,
+// so a pick's "delta" is its whole length E_k and O_k is the sum of the lengths before it.  <false, true> is the plain
+// replace: none of the code below that names split or tests GAPS is in it.
+template <bool TEMPLATES, bool GAPS>
 __global__ void __launch_bounds__(RP_GROUP / 4 * WAVE)
 pfac_rp_count_kernel(const pfac_record *sel, unsigned long long n, unsigned long long entry, unsigned long long n_owned,
                      const short *flen, const unsigned *roff, unsigned num_final, unsigned long long *X,
-                     unsigned long long *gsum, unsigned long long *res) {
+                     unsigned long long *gsum, unsigned long long *res, const unsigned *split) {
     __shared__ unsigned long long bsum[RP_GROUP];
     __shared__ unsigned long long cst[RP_GROUP];
     const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x >> 6;
@@ -3230,7 +3239,14 @@ pfac_rp_count_kernel(const pfac_record *sel, unsigned long long n, unsigned long
                 const int L = flen[r.state];
                 const unsigned R = roff[r.state + 1] - roff[r.state];
                 end = p + (unsigned long long)(L > 0 ? L : 0);
-                d = (unsigned long long)((long long)R - (long long)L);   // (two's complement: sums wrap correctly)
+                if constexpr (!TEMPLATES && GAPS) {
+                    d = (unsigned long long)((long long)R - (long long)L);   // (two's complement: sums wrap correctly)
+                } else {
+                    bool quote = false;
+                    if constexpr (TEMPLATES) quote = split[r.state] != PFAC_TEMPLATE_PLAIN;
+                    const long long M = quote && L > 0 ? (long long)L : 0ll;     // the quoted bytes
+                    d = (unsigned long long)(GAPS ? (long long)R - (long long)L + M : (long long)R + M);
+                }
                 bad |= L < 1;
             } else {
                 bad = true;
@@ -3261,7 +3277,7 @@ pfac_rp_count_kernel(const pfac_record *sel, unsigned long long n, unsigned long
         const unsigned long long b = (unsigned long long)blockIdx.x * RP_GROUP + threadIdx.x;
         unsigned long long pre = 0;
         for (unsigned j = 0; j < threadIdx.x; j++) pre += bsum[j];
-        if (b < nb) X[b] = cst[threadIdx.x] - entry + pre;
+        if (b < nb) X[b] = GAPS ? cst[threadIdx.x] - entry + pre : pre;
         if (threadIdx.x == RP_GROUP - 1) gsum[blockIdx.x] = pre + bsum[RP_GROUP - 1];
     }
 }
@@ -3332,21 +3348,25 @@ __device__ __forceinline__ void rp_merge(uint4 &acc, const unsigned char *buf, l
     acc.w = (acc.w & ~m3) | (v3 & m3);
 }
 
+template <bool TEMPLATES, bool GAPS>
 __global__ void __launch_bounds__(RP_WAVES * WAVE)
 pfac_rp_write_kernel(const unsigned char *in, unsigned long long n_avail, const pfac_record *sel, unsigned long long n,
                      unsigned long long entry, const short *flen, const unsigned *roff, const unsigned char *rep,
                      unsigned long long rep_size, const unsigned long long *X, const unsigned long long *gpre,
-                     unsigned long long out_bytes, unsigned wins, unsigned char *out) {
+                     unsigned long long out_bytes, unsigned wins, unsigned char *out, const unsigned *split) {
     __shared__ unsigned long long s_o[RP_WAVES][RP_BLOCK + 1];      // segment k's output offset (k = cnt: the tail entry)
-    __shared__ unsigned long long s_src[RP_WAVES][RP_BLOCK + 1];    // c_{k-1}: where its gap starts in the input
-    __shared__ unsigned long long s_glen[RP_WAVES][RP_BLOCK + 1];   // its gap's length
+    __shared__ unsigned long long s_src[RP_WAVES][RP_BLOCK + 1];    // c_{k-1}: where its gap starts in the input (no GAPS: p_k)
+    __shared__ unsigned long long s_glen[GAPS ? RP_WAVES : 1][RP_BLOCK + 1];   // its gap's length
     __shared__ unsigned s_roff[RP_WAVES][RP_BLOCK];                 // its replacement's offset in rep
+    __shared__ unsigned s_split[TEMPLATES ? RP_WAVES : 1][RP_BLOCK];   // TEMPLATES: the replacement bytes before the match (plain: R), ...
+    __shared__ unsigned s_mlen[TEMPLATES ? RP_WAVES : 1][RP_BLOCK];    // ... and the quoted bytes (plain: 0)
     const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x >> 6;
     const unsigned long long A = ((unsigned long long)blockIdx.x * RP_WAVES + (unsigned)w) * wins * RP_WIN;
     if (A >= out_bytes) return;
     const unsigned long long nb = n ? (n + RP_BLOCK - 1) / RP_BLOCK : 1;
-    unsigned long long *so = s_o[w], *ssrc = s_src[w], *sgl = s_glen[w];
+    unsigned long long *so = s_o[w], *ssrc = s_src[w], *sgl = s_glen[GAPS ? w : 0];
     unsigned *sro = s_roff[w];
+    unsigned *ssp = s_split[TEMPLATES ? w : 0], *sml = s_mlen[TEMPLATES ? w : 0];
     unsigned long long b = rp_find(X, gpre, nb, 0, A);
     unsigned long long Ob = 0, hi = 0;
     unsigned cnt = 0;
@@ -3354,13 +3374,18 @@ pfac_rp_write_kernel(const unsigned char *in, unsigned long long n_avail, const 
         const unsigned long long k = b * RP_BLOCK + (unsigned)lane;
         const bool v = k < n;
         unsigned long long p = 0, end = 0;
-        unsigned ro = 0, R = 0;
+        unsigned ro = 0, R = 0, sp = 0, M = 0;
         if (v) {
             const pfac_record r = sel[k];
             p = r.pos;
             end = p + (unsigned long long)flen[r.state];
             ro = roff[r.state];
             R = roff[r.state + 1] - ro;
+            if constexpr (TEMPLATES) {
+                sp = split[r.state];
+                M = sp != PFAC_TEMPLATE_PLAIN ? (unsigned)(end - p) : 0u;
+                sp = min(sp, R);                                // (plain: all of R stands before the empty match)
+            }
         }
         unsigned long long prev = __shfl_up(end, 1u, WAVE);
         if (lane == 0) {
@@ -3370,16 +3395,17 @@ pfac_rp_write_kernel(const unsigned char *in, unsigned long long n_avail, const 
                 prev = (unsigned long long)r.pos + (unsigned long long)flen[r.state];
             }
         }
-        const unsigned long long G = v ? p - prev : 0ull;
-        const unsigned long long seg = v ? G + R : 0ull;
+        const unsigned long long G = GAPS && v ? p - prev : 0ull;
+        const unsigned long long seg = v ? G + R + M : 0ull;
         const unsigned long long incl = wave_incl_scan64(seg);
         Ob = rp_block_out(X, gpre, b);
         cnt = (unsigned)min((unsigned long long)RP_BLOCK, n - min(n, b * RP_BLOCK));
         if (v) {
             so[lane] = Ob + incl - seg;
-            ssrc[lane] = prev;
-            sgl[lane] = G;
+            ssrc[lane] = GAPS ? prev : p;                       // (either way the match starts at ssrc + G)
+            if constexpr (GAPS) sgl[lane] = G;
             sro[lane] = ro;
+            if constexpr (TEMPLATES) { ssp[lane] = sp; sml[lane] = M; }
         }
         const unsigned long long oT = Ob + (cnt ? __shfl(incl, (int)cnt - 1, WAVE) : 0ull);
         const unsigned long long cT = cnt ? __shfl(end, (int)cnt - 1, WAVE) : __shfl(prev, 0, WAVE);
@@ -3387,9 +3413,9 @@ pfac_rp_write_kernel(const unsigned char *in, unsigned long long n_avail, const 
         if (lane == 0) {
             so[cnt] = oT;
             ssrc[cnt] = cT;
-            sgl[cnt] = last ? out_bytes - oT : 0ull;
+            if constexpr (GAPS) sgl[cnt] = last ? out_bytes - oT : 0ull;
         }
-        hi = last ? out_bytes : oT;
+        hi = last ? out_bytes : oT;                             // (no GAPS: no tail, the last block ends at out_bytes = oT)
         wave_lds_sync();
     };
     load_block();
@@ -3408,14 +3434,26 @@ pfac_rp_write_kernel(const unsigned char *in, unsigned long long n_avail, const 
                     if (so[m] <= pos) l = m;
                     else h = m;
                 }
-                const unsigned long long gs = so[l], ge = gs + sgl[l];
+                const unsigned long long gs = so[l], ge = GAPS ? gs + sgl[l] : gs;
                 unsigned long long pe;
-                if (pos < ge) {                                 // the input gap
+                if (GAPS && pos < ge) {                         // the input gap
                     pe = min(ge, e);
                     rp_merge(acc, in, (long long)(ssrc[l] + o - gs), n_avail, (unsigned)(pos - o), (unsigned)(pe - o));
-                } else {                                        // the replacement (l < cnt here)
+                } else if constexpr (!TEMPLATES) {              // the replacement (l < cnt here)
                     pe = min(so[l + 1], e);
                     rp_merge(acc, rep, (long long)sro[l] + (long long)(o - ge), rep_size, (unsigned)(pos - o), (unsigned)(pe - o));
+                } else {                                        // R[:split], the match as the caller wrote it, R[split:]
+                    const unsigned long long m0 = ge + ssp[l], m1 = m0 + sml[l];
+                    if (pos < m0) {
+                        pe = min(m0, e);
+                        rp_merge(acc, rep, (long long)sro[l] + (long long)(o - ge), rep_size, (unsigned)(pos - o), (unsigned)(pe - o));
+                    } else if (pos < m1) {
+                        pe = min(m1, e);
+                        rp_merge(acc, in, (long long)(ssrc[l] + (ge - gs)) + (long long)(o - m0), n_avail, (unsigned)(pos - o), (unsigned)(pe - o));
+                    } else {
+                        pe = min(so[l + 1], e);
+                        rp_merge(acc, rep, (long long)sro[l] + (long long)ssp[l] + (long long)(o - m1), rep_size, (unsigned)(pos - o), (unsigned)(pe - o));
+                    }
                 }
                 pos = pe;
             }
@@ -3448,21 +3486,36 @@ pfac_rp_write_kernel(const unsigned char *in, unsigned long long n_avail, const 
 //   pfac_rp_doc_delta_kernel    one wave per block of 64 picks: D_k for every pick, D[n] = the total.  The block's base
 //                               comes from the count kernel: O_{64b} = c_{64b-1} + D_{64b} (entry 0).
 //   pfac_rp_doc_offsets_kernel  one thread per document.
+// Without GAPS (the extraction) D_k under the same definition is the output offset of pick k: the block's base is
+// O_{64b} itself, no cursor subtracted, and D is the caller's pick offsets.
+template <bool TEMPLATES, bool GAPS>
 __global__ void __launch_bounds__(4 * WAVE)
 pfac_rp_doc_delta_kernel(const pfac_record *sel, unsigned long long n, const short *flen, const unsigned *roff,
-                         const unsigned long long *X, const unsigned long long *gpre, unsigned long long *D) {
+                         const unsigned long long *X, const unsigned long long *gpre, unsigned long long *D,
+                         const unsigned *split) {
     const int lane = threadIdx.x & (WAVE - 1);
     const unsigned long long b = (unsigned long long)blockIdx.x * 4 + (threadIdx.x >> 6), k = b * RP_BLOCK + (unsigned)lane;
     if (b * RP_BLOCK >= n) return;
     unsigned long long dk = 0;
     if (k < n) {
         const pfac_record r = sel[k];
-        dk = (unsigned long long)((long long)(roff[r.state + 1] - roff[r.state]) - (long long)flen[r.state]);
+        if constexpr (!TEMPLATES && GAPS) {
+            dk = (unsigned long long)((long long)(roff[r.state + 1] - roff[r.state]) - (long long)flen[r.state]);
+        } else {
+            bool quote = false;
+            if constexpr (TEMPLATES) quote = split[r.state] != PFAC_TEMPLATE_PLAIN;
+            const long long R = (long long)(roff[r.state + 1] - roff[r.state]), L = (long long)flen[r.state];
+            dk = (unsigned long long)(R + (quote ? L : 0ll) - (GAPS ? L : 0ll));
+        }
     }
     unsigned long long base = 0;                                // D_{64b}
     if (b > 0) {
-        const pfac_record r = sel[b * RP_BLOCK - 1];
-        base = X[b] + gpre[b / RP_GROUP] - ((unsigned long long)r.pos + (unsigned long long)flen[r.state]);
+        if constexpr (GAPS) {
+            const pfac_record r = sel[b * RP_BLOCK - 1];
+            base = X[b] + gpre[b / RP_GROUP] - ((unsigned long long)r.pos + (unsigned long long)flen[r.state]);
+        } else {
+            base = X[b] + gpre[b / RP_GROUP];
+        }
     }
     const unsigned long long incl = base + wave_incl_scan64(dk);
     if (k < n) D[k] = incl - dk;
@@ -4104,6 +4157,9 @@ struct Slot {
     uint64_t scan_seq = 0;                // record sets of this slot: scans issued + whole-word filters run over them
     DevBuf<unsigned char> rp_tmp;         // X per block of 64 picks
     PassOut<unsigned char> rp_out;        // the output bytes
+    // pfac_extract_leftmost_longest (X and the group prefixes are the replace's scratch: both are used up on the stream)
+    PassOut<unsigned char> ex_out;        // the rewritten picks, back to back, ...
+    PassOut<unsigned long long> ex_off;   // ... and their output offsets (n + 1 entries)
     // pfac_records_leftmost_longest_documents / pfac_replace_documents
     uint64_t doc_gen = 0;                 // pfac_slot_doc_offsets calls: a selection remembers the offsets it cut with
     bool ll_docs = false;                 // the slot's last selection was per document, ...
@@ -4186,10 +4242,12 @@ struct pfac_ctx {
     TablePlan plan;
     bool have_table = false;
     uint64_t table_gen = 0;               // installs begun so far: a scan's final states index the lengths of ITS table only
-    // ... what the caller attaches to it (an upload drops all six), ...
+    // ... what the caller attaches to it (an upload drops all seven), ...
     DevBuf<short> flen;                   // pattern length of every final state (pfac_table_set_final_lengths)
     DevBuf<unsigned> rep_off;             // replacement of every final state (pfac_table_set_replacements): offsets[num_final + 1]
     DevBuf<unsigned char> rep;            // ... and the bytes, zero-padded to its capacity (a multiple of 16)
+    DevBuf<unsigned> rep_split;           // where a state's replacement quotes the match (pfac_table_set_replacement_templates);
+                                          // null while every state is plain: the replaces then run their plain kernels
     DevBuf<unsigned long long> gmask;     // group set of every final state (pfac_table_set_state_groups)
     DevBuf<uint4> spans;                  // span of every final state (pfac_table_set_state_spans): pfac_state_span as one dwordx4
     unsigned fold = PFAC_FOLD_NONE;       // case fold of the scans to come (pfac_table_set_case_fold)
@@ -4726,7 +4784,7 @@ int install_table(pfac_ctx *ctx, const int *d_blob, const int32_t *hdr, size_t n
         if (sl.pending) { int rc = wait_scan(ctx, sl); if (rc) return rc; }
     ctx->plan = TablePlan();
     ctx->flen.reset(); ctx->fold = PFAC_FOLD_NONE;          // the lengths belong to the old table, and so does the case fold
-    ctx->rep_off.reset(); ctx->rep.reset();                 // ... and so do the replacements
+    ctx->rep_off.reset(); ctx->rep.reset(); ctx->rep_split.reset();       // ... and so do the replacements and their splits
     ctx->gmask.reset();                                     // ... and the state groups
     ctx->spans.reset();                                     // ... and the state spans
     ctx->have_table = false; ctx->table_gen++;
@@ -6195,31 +6253,56 @@ int pfac_leftmost_longest_documents_d2h(pfac_ctx *ctx, int slot, pfac_record *ho
     return rc ? rc : fetch(ctx, s, s.lld_first, fn, pass, host_doc_first, 0, s.lld_first.n, true);
 }
 
-int pfac_table_set_replacements(pfac_ctx *ctx, const uint32_t *offsets, uint64_t n_states, const void *bytes, uint64_t n_bytes) {
+// Both setters of the replacements: everything is checked first, the new buffers are made aside and take the place of the
+// old ones together, so a refused call leaves the earlier replacements and splits in force.  The old buffers are freed
+// behind that (hipFree waits for the device: a write kernel that still reads them has finished before they go), as the
+// spans and the groups are.
+static int set_replacements(pfac_ctx *ctx, const std::string &fn, const uint32_t *offsets, const uint32_t *splits,
+                            uint64_t n_states, const void *bytes, uint64_t n_bytes) {
     if (!ctx) return fail(nullptr, PFAC_E_ARG, "null context");
     std::lock_guard<std::mutex> lk(ctx->mu);
-    if (!ctx->have_table) return fail(ctx, PFAC_E_STATE, "pfac_table_set_replacements before a table upload");
+    if (!ctx->have_table) return fail(ctx, PFAC_E_STATE, fn + " before a table upload");
     if (n_states != (uint64_t)ctx->plan.base.num_final || !offsets || (!bytes && n_bytes))
-        return fail(ctx, PFAC_E_ARG, "pfac_table_set_replacements: need num_final + 1 offsets (num_final " + std::to_string(ctx->plan.base.num_final) + ")");
-    if (n_bytes >= (1ull << 32)) return fail(ctx, PFAC_E_ARG, "pfac_table_set_replacements: n_bytes must be below 2^32");
+        return fail(ctx, PFAC_E_ARG, fn + ": need num_final + 1 offsets (num_final " + std::to_string(ctx->plan.base.num_final) + ")");
+    if (n_bytes >= (1ull << 32)) return fail(ctx, PFAC_E_ARG, fn + ": n_bytes must be below 2^32");
+    bool quoting = false;
     for (uint64_t i = 0; i < n_states; i++) {
         if (offsets[i + 1] < offsets[i] || offsets[i + 1] > n_bytes)
-            return fail(ctx, PFAC_E_ARG, "pfac_table_set_replacements: offsets must ascend within n_bytes (final state " + std::to_string(i) + ")");
+            return fail(ctx, PFAC_E_ARG, fn + ": offsets must ascend within n_bytes (final state " + std::to_string(i) + ")");
         if (offsets[i + 1] - offsets[i] > PFAC_MAX_REPLACEMENT)
-            return fail(ctx, PFAC_E_ARG, "pfac_table_set_replacements: the replacement of final state " + std::to_string(i) + " exceeds " +
+            return fail(ctx, PFAC_E_ARG, fn + ": the replacement of final state " + std::to_string(i) + " exceeds " +
                                              std::to_string(PFAC_MAX_REPLACEMENT) + " bytes");
+        if (splits && splits[i] != PFAC_TEMPLATE_PLAIN) {
+            if (splits[i] > offsets[i + 1] - offsets[i])
+                return fail(ctx, PFAC_E_ARG, fn + ": the split of final state " + std::to_string(i) + " lies past its replacement");
+            quoting = true;
+        }
     }
     USE_DEVICE(ctx);
-    ctx->rep_off.reset();
-    ctx->rep.reset();
+    DevBuf<unsigned> off, split;
+    DevBuf<unsigned char> rep;
     const uint64_t size = align_up(n_bytes, 16) + 16;
-    int rc = ctx->rep_off.ensure(ctx, nullptr, n_states + 1, n_states + 1);
-    if (!rc) rc = ctx->rep.ensure(ctx, nullptr, size, size);
+    int rc = off.ensure(ctx, nullptr, n_states + 1, n_states + 1);
+    if (!rc) rc = rep.ensure(ctx, nullptr, size, size);
+    if (!rc && quoting) rc = split.ensure(ctx, nullptr, n_states, n_states);
     if (rc) return rc;
-    HIP_TRY(ctx, hipMemset(ctx->rep.p, 0, size));
-    HIP_TRY(ctx, hipMemcpy(ctx->rep_off.p, offsets, (n_states + 1) * 4, hipMemcpyHostToDevice));
-    if (n_bytes) HIP_TRY(ctx, hipMemcpy(ctx->rep.p, bytes, n_bytes, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemset(rep.p, 0, size));
+    HIP_TRY(ctx, hipMemcpy(off.p, offsets, (n_states + 1) * 4, hipMemcpyHostToDevice));
+    if (n_bytes) HIP_TRY(ctx, hipMemcpy(rep.p, bytes, n_bytes, hipMemcpyHostToDevice));
+    if (quoting) HIP_TRY(ctx, hipMemcpy(split.p, splits, n_states * 4, hipMemcpyHostToDevice));
+    ctx->rep_off = std::move(off);                          // (a swap: the old buffers go with the three locals)
+    ctx->rep = std::move(rep);
+    ctx->rep_split = std::move(split);
     return PFAC_OK;
+}
+
+int pfac_table_set_replacements(pfac_ctx *ctx, const uint32_t *offsets, uint64_t n_states, const void *bytes, uint64_t n_bytes) {
+    return set_replacements(ctx, "pfac_table_set_replacements", offsets, nullptr, n_states, bytes, n_bytes);
+}
+
+int pfac_table_set_replacement_templates(pfac_ctx *ctx, const uint32_t *offsets, const uint32_t *splits, uint64_t n_states,
+                                         const void *bytes, uint64_t n_bytes) {
+    return set_replacements(ctx, "pfac_table_set_replacement_templates", offsets, splits, n_states, bytes, n_bytes);
 }
 
 // The documents of pfac_replace_documents as the caller passed them (NULL: the slot's offsets / doc_first of the
@@ -6228,11 +6311,23 @@ struct RpDocs {
     const uint64_t *off, *first;
     uint64_t *out_off;
 };
+// pfac_extract_leftmost_longest: the caller's pick offsets (NULL: the slot-owned ones).  rp_run with it writes the picks
+// alone, into the extraction's own outputs; the replace's stay as they are, and the reverse.
+struct RpExtract {
+    uint64_t *pick_off;
+};
+
+// f(kernel<TEMPLATES, GAPS>) for the instantiation a call runs: TEMPLATES while some state quotes its match, GAPS
+// unless the call is the extraction
+#define RP_KERNEL(name, tpl, gaps)                                                                          \
+    ((tpl) ? ((gaps) ? name<true, true> : name<true, false>) : ((gaps) ? name<false, true> : name<false, false>))
 
 static int rp_run(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *d_input, const pfac_record *d_sel, void *d_out,
-                  uint64_t out_cap, uint64_t *out_bytes, const RpDocs *docs) {
-    s.rp_out.invalidate();
-    s.rpd_off.invalidate();
+                  uint64_t out_cap, uint64_t *out_bytes, const RpDocs *docs, const RpExtract *ext = nullptr) {
+    PassOut<unsigned char> &bytes_out = ext ? s.ex_out : s.rp_out;
+    bytes_out.invalidate();
+    if (ext) s.ex_off.invalidate();
+    else s.rpd_off.invalidate();
     if (!s.scanned || !s.ll_out.done || s.ll_seq != s.scan_seq || (docs && !s.ll_docs))
         return fail(ctx, PFAC_E_STATE, fn + (docs ? " needs a pfac_records_leftmost_longest_documents since the slot's last scan"
                                                   : " needs a pfac_records_leftmost_longest since the slot's last scan"));
@@ -6245,8 +6340,9 @@ static int rp_run(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *d_i
     if (rc) return rc;
     const unsigned char *in = d_input ? static_cast<const unsigned char *>(d_input) : s.input.p;
     const uint64_t n = s.ll_out.n, n_owned = s.last_owned, n_avail = s.last_avail, entry = s.ll_entry, ex = s.ll_exit;
-    if (((uintptr_t)d_out & 15) || ((uintptr_t)in & 15) || ((uintptr_t)d_sel & 7))
-        return fail(ctx, PFAC_E_ARG, fn + ": misaligned buffer (d_input and d_out 16 B, d_sel 8 B)");
+    if (((uintptr_t)d_out & 15) || ((uintptr_t)in & 15) || ((uintptr_t)d_sel & 7) || (ext && ((uintptr_t)ext->pick_off & 7)))
+        return fail(ctx, PFAC_E_ARG, fn + (ext ? ": misaligned buffer (d_input and d_out 16 B, d_sel and d_pick_offsets 8 B)"
+                                               : ": misaligned buffer (d_input and d_out 16 B, d_sel 8 B)"));
     if (n_owned > entry && !in) return fail(ctx, PFAC_E_ARG, fn + ": no input buffer");
     if (!d_input && n_avail > s.input.cap) return fail(ctx, PFAC_E_ARG, fn + ": the scan read more than the slot's input buffer holds");
     const unsigned long long *doff = nullptr, *dfirst = nullptr;
@@ -6265,6 +6361,7 @@ static int rp_run(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *d_i
             return fail(ctx, PFAC_E_ARG, fn + ": device buffers must be 8-byte aligned");
     }
     USE_DEVICE(ctx);
+    const bool tpl = ctx->rep_split.p != nullptr, gaps = !ext;
     int64_t delta = 0;
     const uint64_t nb = n ? (n + RP_BLOCK - 1) / RP_BLOCK : 1;
     const uint64_t n_groups = (nb + RP_GROUP - 1) / RP_GROUP;
@@ -6279,9 +6376,10 @@ static int rp_run(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *d_i
         if (rc) return rc;
         unsigned long long *res = s.gsum.p + n_groups + 1;
         HIP_TRY(ctx, hipMemsetAsync(res, 0, 16, s.stream));
-        hipLaunchKernelGGL(pfac_rp_count_kernel, dim3((unsigned)n_groups), dim3(RP_GROUP / 4 * WAVE), 0, s.stream, sel,
-                           (unsigned long long)n, (unsigned long long)entry, (unsigned long long)n_owned, ctx->flen.p,
-                           ctx->rep_off.p, (unsigned)ctx->plan.base.num_final, X, s.gsum.p, res);
+        hipLaunchKernelGGL(RP_KERNEL(pfac_rp_count_kernel, tpl, gaps), dim3((unsigned)n_groups), dim3(RP_GROUP / 4 * WAVE), 0,
+                           s.stream, sel, (unsigned long long)n, (unsigned long long)entry, (unsigned long long)n_owned,
+                           ctx->flen.p, ctx->rep_off.p, (unsigned)ctx->plan.base.num_final, X, s.gsum.p, res,
+                           (const unsigned *)ctx->rep_split.p);
         hipLaunchKernelGGL(pfac_scan_groups_kernel, dim3(1), dim3(1024), 0, s.stream, s.gsum.p, (unsigned)n_groups);
         rc = pass_words(ctx, s, s.gsum.p + n_groups, 3);
         if (rc) return rc;
@@ -6290,7 +6388,7 @@ static int rp_run(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *d_i
         if (err || (c_last > n_owned ? c_last - n_owned : 0) != ex)
             return fail(ctx, PFAC_E_ARG, fn + ": the selection is not one of this scan and table");
     }
-    const int64_t total = (int64_t)(n_owned + ex) - (int64_t)entry + delta;
+    const int64_t total = ext ? delta : (int64_t)(n_owned + ex) - (int64_t)entry + delta;    // (the picks alone: the sum of their lengths)
     if (total < 0) return fail(ctx, PFAC_E_INTERNAL, fn + ": negative output length");
     const uint64_t ob = (uint64_t)total;
     *out_bytes = ob;
@@ -6303,28 +6401,44 @@ static int rp_run(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *d_i
         if (!rc && n) rc = s.rpd_tmp.ensure(ctx, s.stream, n + 1, n + 1 + n / 8 + 4096);
         if (rc) return rc;
     }
+    unsigned long long *po = nullptr;
+    if (ext) {
+        rc = s.ex_off.bind(ctx, s.stream, ext->pick_off, n + 1, docs_cap(n), &po);
+        if (rc) return rc;
+    }
     unsigned char *out;
-    rc = s.rp_out.bind(ctx, s.stream, d_out, ob, align_up(ob + ob / 8, 4096), &out);
+    rc = bytes_out.bind(ctx, s.stream, d_out, ob, align_up(ob + ob / 8, 4096), &out);
     if (rc) return rc;
     if (ob) {
         const WriteGrid g = write_grid(ob);
-        hipLaunchKernelGGL(pfac_rp_write_kernel, dim3(g.blocks), dim3(RP_WAVES * WAVE), 0, s.stream, in,
+        hipLaunchKernelGGL(RP_KERNEL(pfac_rp_write_kernel, tpl, gaps), dim3(g.blocks), dim3(RP_WAVES * WAVE), 0, s.stream, in,
                            (unsigned long long)n_avail, sel, (unsigned long long)n, (unsigned long long)entry, ctx->flen.p,
                            ctx->rep_off.p, ctx->rep.p, (unsigned long long)ctx->rep.cap, X, s.gsum.p,
-                           (unsigned long long)ob, g.wins, out);
+                           (unsigned long long)ob, g.wins, out, (const unsigned *)ctx->rep_split.p);
         HIP_TRY(ctx, hipGetLastError());
+    }
+    if (ext) {                                              // the pick offsets: D_k of the delta kernel as they come
+        if (n)
+            hipLaunchKernelGGL(RP_KERNEL(pfac_rp_doc_delta_kernel, tpl, false), dim3((unsigned)((nb + 3) / 4)), dim3(4 * WAVE), 0,
+                               s.stream, sel, (unsigned long long)n, ctx->flen.p, ctx->rep_off.p, X, s.gsum.p, po,
+                               (const unsigned *)ctx->rep_split.p);
+        else
+            HIP_TRY(ctx, hipMemsetAsync(po, 0, 8, s.stream));
+        HIP_TRY(ctx, hipGetLastError());
+        s.ex_off.commit(n + 1, !ext->pick_off);
     }
     if (docs) {
         if (n)
-            hipLaunchKernelGGL(pfac_rp_doc_delta_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(4 * WAVE), 0, s.stream, sel,
-                               (unsigned long long)n, ctx->flen.p, ctx->rep_off.p, X, s.gsum.p, s.rpd_tmp.p);
+            hipLaunchKernelGGL(RP_KERNEL(pfac_rp_doc_delta_kernel, tpl, true), dim3((unsigned)((nb + 3) / 4)), dim3(4 * WAVE), 0,
+                               s.stream, sel, (unsigned long long)n, ctx->flen.p, ctx->rep_off.p, X, s.gsum.p, s.rpd_tmp.p,
+                               (const unsigned *)ctx->rep_split.p);
         const unsigned oblocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_docs + 1 + 255) / 256, 65536));
         hipLaunchKernelGGL(pfac_rp_doc_offsets_kernel, dim3(oblocks), dim3(256), 0, s.stream, doff, dfirst,
                            (unsigned long long)n_docs, (const unsigned long long *)s.rpd_tmp.p, (unsigned long long)n, oo);
         HIP_TRY(ctx, hipGetLastError());
         s.rpd_off.commit(n_docs + 1, !dout_off);
     }
-    s.rp_out.commit(ob, !d_out);
+    bytes_out.commit(ob, !d_out);
     return PFAC_OK;
 }
 
@@ -6359,6 +6473,30 @@ int pfac_replace_d2h(pfac_ctx *ctx, int slot, void *host, uint64_t first, uint64
     if (rc) return rc;
     Slot &s = ctx->slots[slot];
     return fetch(ctx, s, s.rp_out, "pfac_replace_d2h", "pfac_replace_leftmost_longest / pfac_replace_documents", host, first, n);
+}
+
+int pfac_extract_leftmost_longest(pfac_ctx *ctx, int slot, const void *d_input, const pfac_record *d_sel, void *d_out,
+                                  uint64_t out_cap, uint64_t *d_pick_offsets, uint64_t *out_bytes) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    if (!out_bytes) return fail(ctx, PFAC_E_ARG, "null argument");
+    *out_bytes = 0;
+    const RpExtract ext{d_pick_offsets};
+    return rp_run(ctx, ctx->slots[slot], "pfac_extract_leftmost_longest", d_input, d_sel, d_out, out_cap, out_bytes, nullptr, &ext);
+}
+
+int pfac_extract_d2h(pfac_ctx *ctx, int slot, void *host, uint64_t first, uint64_t n) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    Slot &s = ctx->slots[slot];
+    return fetch(ctx, s, s.ex_out, "pfac_extract_d2h", "pfac_extract_leftmost_longest", host, first, n);
+}
+
+int pfac_extract_offsets_d2h(pfac_ctx *ctx, int slot, uint64_t *host_pick_offsets) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    Slot &s = ctx->slots[slot];
+    return fetch(ctx, s, s.ex_off, "pfac_extract_offsets_d2h", "pfac_extract_leftmost_longest", host_pick_offsets, 0, s.ex_off.n);
 }
 
 int pfac_fill_tiled(pfac_ctx *ctx, int slot, void *d_dst, uint64_t n, const void *host_pattern, uint32_t period, uint64_t phase) {

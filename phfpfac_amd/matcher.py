@@ -15,7 +15,7 @@ import numpy as np
 
 from ._ffi import (PFAC_COUNT_ACCUMULATE, PFAC_DOCS_INVERT, PFAC_E_OVERFLOW, PFAC_FOLD_ASCII, PFAC_FOLD_NONE, PFAC_SPANS_LINE, PFAC_WORD_LEFT, PFAC_WORD_RIGHT, CRecord, PfacError,
                    hip_lib)
-from .table import RECORD_DTYPE, PfacTable, redaction_table, replacement_table
+from .table import RECORD_DTYPE, TEMPLATE_PLAIN, PfacTable, redaction_table, replacement_table, template_table, _state_lengths
 
 
 def device_count() -> int:
@@ -858,6 +858,35 @@ class GpuMatcher:
             raise PfacError(-7, "no host table to take the final-state lengths from (load_table first)")
         self._set_replacement_table(*redaction_table(self.table, fill))
 
+    def _set_template_table(self, offsets, splits, data: bytes) -> None:
+        off = np.ascontiguousarray(offsets, dtype=np.uint32)
+        spl = np.ascontiguousarray(splits, dtype=np.uint32)
+        buf = np.frombuffer(data, dtype=np.uint8) if data else np.zeros(1, dtype=np.uint8)
+        self._check(self._L.pfac_table_set_replacement_templates(self._ctx, off.ctypes.data, spl.ctypes.data if spl.size else None,
+                                                                 off.size - 1, buf.ctypes.data, len(data)))
+
+    def set_replacement_templates(self, templates) -> None:
+        """The replacement template of every pattern of the uploaded table (``template_table``: a dict {id: template}
+        or one entry per line; a template is bytes, or (prefix, suffix) around the matched text as the input has it),
+        kept on the device until the next table upload.  ``replace``, ``replace_lines``, ``replace_documents`` and the
+        ``replace_selection*`` calls then write them; ``extract*`` writes the rewritten picks alone."""
+        if self.table is None:
+            raise PfacError(-7, "no host table to map pattern ids to states (load_table first)")
+        self._set_template_table(*template_table(self.table, templates))
+
+    def set_highlight(self, prefix: bytes, suffix: bytes) -> None:
+        """Templates that wrap every match: ``prefix`` + the matched text + ``suffix`` (``<b>&</b>``, grep --color;
+        with (b"", b"\n") ``extract_lines`` is grep -o)."""
+        if self.table is None:
+            raise PfacError(-7, "no host table to take the final-state lengths from (load_table first)")
+        prefix, suffix = bytes(prefix), bytes(suffix)
+        live = _state_lengths(self.table) >= 1
+        r = prefix + suffix
+        offsets = np.zeros(int(self.table.num_final) + 1, dtype=np.uint32)
+        offsets[1:] = np.cumsum(np.where(live, len(r), 0), dtype=np.uint64)
+        splits = np.where(live, len(prefix), TEMPLATE_PLAIN).astype(np.uint32)
+        self._set_template_table(offsets, splits, r * int(live.sum()))
+
     def replace_selection(self, d_input=None, d_out=None, out_cap: int = 0, slot: int = 0, d_sel=None) -> int:
         """Rewrites the slot's last scan on the GPU: every pick of its last ``select_leftmost_longest`` replaced by its
         state's replacement, the bytes between copied, from the selection's entry to n_owned.  Returns the output's
@@ -892,6 +921,57 @@ class GpuMatcher:
         _, ex = self.select_leftmost_longest(entry, slot=slot)
         n = self.replace_selection(slot=slot)
         return self.replacement_to_host(n, slot), ex
+
+    # -- match extraction: the rewritten picks alone ------------------------
+    def extract_selection(self, d_input=None, d_out=None, out_cap: int = 0, d_pick_offsets=None, slot: int = 0, d_sel=None) -> int:
+        """The picks of the slot's last selection (whole-stream or per document) as their replacements or templates
+        write them, back to back, on the GPU (``pfac_extract_leftmost_longest``).  Returns the output's length.
+        ``d_out`` / ``d_pick_offsets`` None = slot-owned buffers of the extraction's own (``extracted_to_host`` /
+        ``extract_offsets_to_host``); ``d_sel`` None = the slot-owned selection.  A too small ``out_cap`` raises
+        PfacError(PFAC_E_OVERFLOW) whose ``out_bytes`` attribute holds the exact length."""
+        n = C.c_uint64(0)
+        rc = self._L.pfac_extract_leftmost_longest(self._ctx, slot, _ptr(d_input), _ptr(d_sel), _ptr(d_out), int(out_cap),
+                                                   _ptr(d_pick_offsets), C.byref(n))
+        return self._counted(rc, n, "out_bytes")
+
+    def extracted_to_host(self, n: int, slot: int = 0, first: int = 0) -> np.ndarray:
+        """Bytes [first, first + n) of the slot's last ``extract_selection`` into its slot-owned buffer."""
+        return self._to_host(slot, lambda p: self._L.pfac_extract_d2h(self._ctx, slot, p, int(first), int(n)), (n, np.uint8))
+
+    def extract_offsets_to_host(self, n_picks: int, slot: int = 0) -> np.ndarray:
+        """The pick offsets (uint64[n_picks + 1]) of the slot's last ``extract_selection``."""
+        return self._to_host(slot, lambda p: self._L.pfac_extract_offsets_d2h(self._ctx, slot, p),
+                             (int(n_picks) + 1, np.uint64))
+
+    def extract(self, data, n_owned: Optional[int] = None, entry: int = 0, slot: int = 0, whole_words=False,
+                prev_byte: int = -1, next_byte: int = -1) -> Tuple[np.ndarray, np.ndarray, int]:
+        """H2D + scan + selection + extraction of one host buffer, with the keywords of ``replace``.  Returns (bytes,
+        pick_offsets uint64[n_picks + 1], exit): pick k is ``bytes[pick_offsets[k]:pick_offsets[k + 1]]``."""
+        buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data.view(np.uint8).ravel()
+        n_avail = int(buf.size)
+        n_owned = n_avail if n_owned is None else int(n_owned)
+        self._ensure_final_lengths()
+        self.reserve(slot, max(n_avail, 1), max(n_avail // 8, 4096))
+        if n_avail:
+            self.h2d(buf, slot)
+        self.scan_resident(n_owned, n_avail, slot=slot)
+        if whole_words is not False:
+            self.filter_whole_words(slot, _word_bytes(whole_words), prev_byte=prev_byte, next_byte=next_byte)
+        n_sel, ex = self.select_leftmost_longest(entry, slot=slot)
+        n = self.extract_selection(slot=slot)
+        return self.extracted_to_host(n, slot), self.extract_offsets_to_host(n_sel, slot), ex
+
+    def extract_lines(self, data, delimiter=b"\n", whole_words=False, spans: bool = False, line_match: bool = False,
+                      slot: int = 0) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The matches of one buffer cut into lines at ``delimiter`` on the device, every line selected on its own
+        (``select_lines``' path), then extracted.  Returns (bytes, pick_offsets uint64[n_picks + 1], doc_first uint64
+        [n_docs + 1]): line d's matches are ``bytes[pick_offsets[doc_first[d]]:pick_offsets[doc_first[d + 1]]]``.  With
+        ``set_highlight(b"", b"\n")`` the bytes are what grep -o prints."""
+        _, n_docs = self._scan_lines(data, delimiter, slot, whole_words, fetch_offsets=False, spans=spans, line_match=line_match)
+        n_sel = self.select_leftmost_longest_documents(n_docs, slot=slot)
+        first, _ = self.doc_selection_to_host(0, n_docs, slot)
+        n = self.extract_selection(slot=slot)
+        return self.extracted_to_host(n, slot), self.extract_offsets_to_host(n_sel, slot), first
 
     def replace_selection_documents(self, d_input=None, d_out=None, out_cap: int = 0, d_out_offsets=None, slot: int = 0,
                                     d_sel=None, d_doc_offsets=None, d_doc_first=None) -> int:

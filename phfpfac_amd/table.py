@@ -360,6 +360,66 @@ def replacement_table(table: "PfacTable", replacements) -> tuple:
     return offsets, b"".join(parts)
 
 
+TEMPLATE_PLAIN = 0xFFFFFFFF          # PFAC_TEMPLATE_PLAIN: the state's replacement does not quote the match
+
+
+def _template_of(t, pattern_id: int) -> tuple:
+    """One template -> (replacement bytes, split): bytes = plain, (prefix, suffix) = the match quoted between them."""
+    if isinstance(t, (bytes, bytearray, memoryview, np.ndarray)):
+        r, split = bytes(t), TEMPLATE_PLAIN
+    else:
+        try:
+            prefix, suffix = t
+        except (TypeError, ValueError):
+            raise ValueError(f"the template of pattern id {pattern_id} must be bytes or a (prefix, suffix) pair") from None
+        prefix, suffix = bytes(prefix), bytes(suffix)
+        r, split = prefix + suffix, len(prefix)
+    if len(r) > MAX_REPLACEMENT:
+        raise ValueError(f"the template of pattern id {pattern_id} is longer than {MAX_REPLACEMENT} bytes")
+    return r, split
+
+
+def template_table(table: "PfacTable", templates) -> tuple:
+    """-> (offsets uint32[num_final + 1], splits uint32[num_final], bytes): the replacement template of every final
+    state, for ``pfac_table_set_replacement_templates``.  ``templates`` is a dict {pattern id: template} or a sequence
+    with one entry per line of the pattern file, resolved through ``idmap`` exactly as ``replacement_table`` does.  A
+    template is bytes (a plain replacement) or a pair (prefix, suffix): the pick becomes prefix + the matched bytes as
+    they stand in the input + suffix.  Unreachable states get an empty plain one; every reachable state must be
+    covered.  On a character-class table the ids that share a final state must carry the same template: ValueError
+    names them, as ``state_spans`` does."""
+    lens = _state_lengths(table)
+    ids = np.asarray(table.idmap, dtype=np.int64)
+    first = getattr(table, "out_first", None)
+    if isinstance(templates, dict):
+        get = templates.get
+    else:
+        seq = list(templates)
+        get = lambda i: seq[i - 1] if 1 <= i <= len(seq) else None   # noqa: E731
+    n_states = int(table.num_final)
+    offsets = np.zeros(n_states + 1, dtype=np.uint32)
+    splits = np.full(n_states, TEMPLATE_PLAIN, dtype=np.uint32)
+    parts, missing, at = [], [], 0
+    for s in range(n_states):
+        if lens[s] >= 1:
+            i = int(ids[s])
+            t = get(i)
+            if t is None:
+                missing.append(i)
+            else:
+                r, splits[s] = _template_of(t, i)
+                if first is not None:
+                    for j in table.out_ids[int(first[s]):int(first[s + 1])]:
+                        other = get(int(j))
+                        if other is None or _template_of(other, int(j)) != (r, int(splits[s])):
+                            raise ValueError(f"pattern ids {i} and {int(j)} end in one final state ({s}) but carry different templates")
+                parts.append(r)
+                at += len(r)
+        offsets[s + 1] = at
+    if missing:
+        raise ValueError(f"no template for pattern id {min(missing)}")
+    return offsets, splits, b"".join(parts)
+
+
 def redaction_table(table: "PfacTable", fill: bytes = b"*") -> tuple:
     """``replacement_table`` of a redaction: every reachable state gets ``fill`` repeated to its pattern length."""
     lens = _state_lengths(table)
