@@ -2372,18 +2372,31 @@ __device__ __forceinline__ int final_len(const short *flen, int freg, bool fsmal
     if (fsmall) return __shfl(freg, (int)st, WAVE);
     return have ? (int)flen[st] : 0;
 }
+// The offsets' rules (off[0] == 0, no decrease, off[n_docs] == n_owned), one thread per document, grid-stride: a flag,
+// and the host writes nothing behind it.  Called by the first kernel of every document-aware pass, and by
+// pfac_offsets_check_kernel where no such kernel runs.  The thread's index in the grid and the grid's size come from the
+// kernel (GRID_THREAD, GRID_THREADS, #undef'd behind the last of the three): the workgroup's size folds to a load of
+// the kernel's arguments only in a kernel's own body; read in here the three kernels compile to other code than the
+// parent's (DESIGN.md section 19 has the figures).
+#define GRID_THREAD ((unsigned long long)blockIdx.x * blockDim.x + threadIdx.x)
+#define GRID_THREADS ((unsigned long long)gridDim.x * blockDim.x)
+__device__ __forceinline__ void offsets_rule(unsigned long long gtid, unsigned long long gstride, const unsigned long long *off,
+                                             unsigned long long n_docs, unsigned long long n_owned, unsigned long long *bad) {
+    for (unsigned long long d = gtid; d < n_docs; d += gstride)
+        if (off[d] > off[d + 1]) *bad = 1ull;
+    if (gtid == 0 && (off[0] != 0ull || off[n_docs] != n_owned)) *bad = 1ull;
+}
+__global__ void pfac_offsets_check_kernel(const unsigned long long *off, unsigned long long n_docs, unsigned long long n_owned,
+                                          unsigned long long *bad) {
+    offsets_rule(GRID_THREAD, GRID_THREADS, off, n_docs, n_owned, bad);
+}
 
 template <int BYTES>
 __global__ void pfac_seg_count_kernel(const void *rec, const unsigned long long *tix, unsigned long long n_tiles, unsigned long long cap,
                                       const unsigned long long *off, unsigned long long n_docs, unsigned long long n_owned,
                                       const short *flen, unsigned num_final, unsigned *tcnt, unsigned long long *gsum,
                                       unsigned n_groups, unsigned long long *bad) {
-    // the offsets' rules, one thread per document: a flag, and the host writes nothing behind it
-    const unsigned long long gtid = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const unsigned long long gstride = (unsigned long long)gridDim.x * blockDim.x;
-    for (unsigned long long d = gtid; d < n_docs; d += gstride)
-        if (off[d] > off[d + 1]) *bad = 1ull;
-    if (gtid == 0 && (off[0] != 0ull || off[n_docs] != n_owned)) *bad = 1ull;
+    offsets_rule(GRID_THREAD, GRID_THREADS, off, n_docs, n_owned, bad);
     const int lane = threadIdx.x & (WAVE - 1);
     const unsigned g = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (g >= n_groups) return;
@@ -2505,11 +2518,7 @@ pfac_group_masks_kernel(const void *rec, const unsigned long long *tix, unsigned
                         const unsigned long long *off, unsigned long long n_docs, unsigned long long n_owned,
                         const short *flen, const unsigned long long *gmask, unsigned num_final, unsigned long long *out,
                         unsigned n_groups, unsigned long long *res) {        // res[0]: the OR of all masks, res[1]: bad offsets
-    const unsigned long long gtid = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const unsigned long long gstride = (unsigned long long)gridDim.x * blockDim.x;
-    for (unsigned long long d = gtid; d < n_docs; d += gstride)
-        if (off[d] > off[d + 1]) res[1] = 1ull;
-    if (gtid == 0 && (off[0] != 0ull || off[n_docs] != n_owned)) res[1] = 1ull;
+    offsets_rule(GRID_THREAD, GRID_THREADS, off, n_docs, n_owned, res + 1);
     const int lane = threadIdx.x & (WAVE - 1);
     const unsigned g = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (g >= n_groups) return;
@@ -2869,13 +2878,7 @@ pfac_ll_tiles_kernel(const void *rec, const unsigned long long *tix, unsigned lo
     unsigned long long wsel = 0;                                // selected records of this wave's tiles
     unsigned long long tdlo = 0, tdhi = 0;                      // DOCS: documents of tile 64g + lane
     if constexpr (DOCS) {
-        if constexpr (!MARK) {                                  // the offsets' rules, one thread per document
-            const unsigned long long gtid = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-            const unsigned long long gstride = (unsigned long long)gridDim.x * blockDim.x;
-            for (unsigned long long d = gtid; d < n_docs; d += gstride)
-                if (off[d] > off[d + 1]) *bad = 1ull;
-            if (gtid == 0 && (off[0] != 0ull || off[n_docs] != n_owned)) *bad = 1ull;
-        }
+        if constexpr (!MARK) offsets_rule(GRID_THREAD, GRID_THREADS, off, n_docs, n_owned, bad);
         const unsigned long long tl = (unsigned long long)g * XGROUP + (unsigned)lane;
         unsigned long long ds, de;
         if (tl < n_tiles) tile_docs(off, n_docs, tl, n_tiles, ds, de, tdlo, tdhi);
@@ -3022,6 +3025,8 @@ pfac_ll_tiles_kernel(const void *rec, const unsigned long long *tix, unsigned lo
         }
     }
 }
+#undef GRID_THREAD
+#undef GRID_THREADS
 
 // out[b] = fun[f1 - 1] o ... o fun[f0] for [f0, f1) = block b's `per` functions (blockDim >= M + 1: one entry each)
 __global__ void pfac_ll_compose_kernel(const unsigned short *fun, unsigned M1, unsigned n, unsigned per, unsigned short *out) {
@@ -3210,6 +3215,30 @@ __device__ __forceinline__ unsigned long long wave_incl_scan64(unsigned long lon
     return x;
 }
 
+// The end of a count kernel (replace, gather), behind the waves' sums of their blocks in bsum[]: X[b] = first(lb) + the
+// sums of the group's blocks in front of block b (lb: its index in the group), and the group's sum.
+template <typename First>
+__device__ __forceinline__ void rp_count_out(const unsigned long long *bsum, unsigned long long nb, unsigned long long *X,
+                                             unsigned long long *gsum, First first) {
+    __syncthreads();
+    if (threadIdx.x < RP_GROUP) {
+        const unsigned long long b = (unsigned long long)blockIdx.x * RP_GROUP + threadIdx.x;
+        unsigned long long pre = 0;
+        for (unsigned j = 0; j < threadIdx.x; j++) pre += bsum[j];
+        if (b < nb) X[b] = first(threadIdx.x) + pre;
+        if (threadIdx.x == RP_GROUP - 1) gsum[blockIdx.x] = pre + bsum[RP_GROUP - 1];
+    }
+}
+
+// One wave per block of 64 items of size x (pick k's delta, id k's length): out[k] = base + the sizes in front of k in
+// the block, and behind the last item out[n] = the total.
+__device__ __forceinline__ void rp_block_offsets(unsigned long long base, unsigned long long x, unsigned long long k,
+                                                 unsigned long long n, unsigned long long *out) {
+    const unsigned long long incl = base + wave_incl_scan64(x);
+    if (k < n) out[k] = incl - x;
+    if (k + 1 == n) out[n] = incl;
+}
+
 // The three kernels are templates on <TEMPLATES, GAPS>.  TEMPLATES: some state quotes its match (split[s] !=
 // PFAC_TEMPLATE_PLAIN: the pick becomes R[:split] + input[p, p + L) + R[split:], so its delta is R, not R - L).  GAPS
 // false is the extraction (pfac_extract_leftmost_longest): the same segments without their gaps and without the tail,
@@ -3272,14 +3301,7 @@ pfac_rp_count_kernel(const pfac_record *sel, unsigned long long n, unsigned long
         if (lane == 0) { bsum[lb] = s; cst[lb] = prev; }
     }
     if (__ballot(bad) && lane == 0) atomicOr(&res[0], 1ull);
-    __syncthreads();
-    if (threadIdx.x < RP_GROUP) {
-        const unsigned long long b = (unsigned long long)blockIdx.x * RP_GROUP + threadIdx.x;
-        unsigned long long pre = 0;
-        for (unsigned j = 0; j < threadIdx.x; j++) pre += bsum[j];
-        if (b < nb) X[b] = GAPS ? cst[threadIdx.x] - entry + pre : pre;
-        if (threadIdx.x == RP_GROUP - 1) gsum[blockIdx.x] = pre + bsum[RP_GROUP - 1];
-    }
+    rp_count_out(bsum, nb, X, gsum, [&](unsigned lb) { return GAPS ? cst[lb] - entry : 0ull; });
 }
 
 // O_{64b}: the output offset of block b's first segment (b < nb)
@@ -3348,6 +3370,69 @@ __device__ __forceinline__ void rp_merge(uint4 &acc, const unsigned char *buf, l
     acc.w = (acc.w & ~m3) | (v3 & m3);
 }
 
+// the last segment k in [0, h) with so[k] <= pos (so[0] <= pos)
+__device__ __forceinline__ unsigned rp_segment(const unsigned long long *so, unsigned h, unsigned long long pos) {
+    unsigned l = 0;
+    while (h - l > 1) {
+        const unsigned m = (l + h) >> 1;
+        if (so[m] <= pos) l = m;
+        else h = m;
+    }
+    return l;
+}
+
+// The output-driven loop of the write kernels (replace, gather): each wave owns `wins` windows of RP_WIN bytes, one
+// 16-byte chunk at o per lane (lane `lane` of wave w of the workgroup).  b is the block of 64 segments at hand, cnt
+// how many it has and [Ob, hi) the output bytes it covers: the caller's load_block(b, Ob, hi, cnt) puts block b's
+// segments into the wave's LDS and sets the other three, and piece(cnt, acc, o, pos, e) merges into acc the run that
+// starts at pos of the piece that holds it and returns its end (at most e).  rp_find gives the window's first block,
+// and after a block the next one that is not empty.  A chunk is stored with one dwordx4; only the last partial 16 B of
+// the whole output goes in pieces.  The block's state lives HERE, not in the kernels: handed in by reference it stays
+// in memory until the loop is inlined into its kernel, behind the loop passes, and the kernels compile to other code
+// than the parent's (DESIGN.md section 19 has the figures).
+template <typename Load, typename Piece>
+__device__ __forceinline__ void rp_write_windows(int lane, int w, const unsigned long long *X, const unsigned long long *gpre, unsigned long long nb,
+                                                 unsigned long long out_bytes, unsigned wins, unsigned char *out,
+                                                 Load load_block, Piece piece) {
+    const unsigned long long A = ((unsigned long long)blockIdx.x * RP_WAVES + (unsigned)w) * wins * RP_WIN;
+    if (A >= out_bytes) return;
+    unsigned long long b = rp_find(X, gpre, nb, 0, A);
+    unsigned long long Ob = 0, hi = 0;
+    unsigned cnt = 0;
+    load_block(b, Ob, hi, cnt);
+    for (unsigned wi = 0; wi < wins; wi++) {
+        const unsigned long long W = A + (unsigned long long)wi * RP_WIN;
+        if (W >= out_bytes) break;
+        const unsigned long long o = W + 16ull * (unsigned)lane;
+        uint4 acc = make_uint4(0u, 0u, 0u, 0u);
+        for (;;) {
+            const unsigned long long e = min(o + 16, hi);
+            unsigned long long pos = max(o, Ob);
+            while (pos < e) pos = piece(cnt, acc, o, pos, e);
+            if (hi >= W + RP_WIN || hi >= out_bytes) break;
+            b = rp_find(X, gpre, nb, b + 1, hi);
+            wave_lds_sync();                                    // (every lane is done with the old block)
+            load_block(b, Ob, hi, cnt);
+        }
+        if (o + 16 <= out_bytes) {
+            *reinterpret_cast<uint4 *>(out + o) = acc;
+        } else if (o < out_bytes) {                             // the last partial 16 B of the whole output
+            const unsigned m = (unsigned)(out_bytes - o);
+            const unsigned v[4] = {acc.x, acc.y, acc.z, acc.w};
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                if ((unsigned)(4 * i + 4) <= m) {
+                    *reinterpret_cast<unsigned *>(out + o + 4 * i) = v[i];
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; j++)
+                        if ((unsigned)(4 * i + j) < m) out[o + 4 * i + j] = (unsigned char)(v[i] >> (8 * j));
+                }
+            }
+        }
+    }
+}
+
 template <bool TEMPLATES, bool GAPS>
 __global__ void __launch_bounds__(RP_WAVES * WAVE)
 pfac_rp_write_kernel(const unsigned char *in, unsigned long long n_avail, const pfac_record *sel, unsigned long long n,
@@ -3361,16 +3446,11 @@ pfac_rp_write_kernel(const unsigned char *in, unsigned long long n_avail, const 
     __shared__ unsigned s_split[TEMPLATES ? RP_WAVES : 1][RP_BLOCK];   // TEMPLATES: the replacement bytes before the match (plain: R), ...
     __shared__ unsigned s_mlen[TEMPLATES ? RP_WAVES : 1][RP_BLOCK];    // ... and the quoted bytes (plain: 0)
     const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x >> 6;
-    const unsigned long long A = ((unsigned long long)blockIdx.x * RP_WAVES + (unsigned)w) * wins * RP_WIN;
-    if (A >= out_bytes) return;
     const unsigned long long nb = n ? (n + RP_BLOCK - 1) / RP_BLOCK : 1;
     unsigned long long *so = s_o[w], *ssrc = s_src[w], *sgl = s_glen[GAPS ? w : 0];
     unsigned *sro = s_roff[w];
     unsigned *ssp = s_split[TEMPLATES ? w : 0], *sml = s_mlen[TEMPLATES ? w : 0];
-    unsigned long long b = rp_find(X, gpre, nb, 0, A);
-    unsigned long long Ob = 0, hi = 0;
-    unsigned cnt = 0;
-    auto load_block = [&]() {
+    auto load_block = [&](unsigned long long b, unsigned long long &Ob, unsigned long long &hi, unsigned &cnt) {
         const unsigned long long k = b * RP_BLOCK + (unsigned)lane;
         const bool v = k < n;
         unsigned long long p = 0, end = 0;
@@ -3418,67 +3498,32 @@ pfac_rp_write_kernel(const unsigned char *in, unsigned long long n_avail, const 
         hi = last ? out_bytes : oT;                             // (no GAPS: no tail, the last block ends at out_bytes = oT)
         wave_lds_sync();
     };
-    load_block();
-    for (unsigned wi = 0; wi < wins; wi++) {
-        const unsigned long long W = A + (unsigned long long)wi * RP_WIN;
-        if (W >= out_bytes) break;
-        const unsigned long long o = W + 16ull * (unsigned)lane;
-        uint4 acc = make_uint4(0u, 0u, 0u, 0u);
-        for (;;) {
-            const unsigned long long e = min(o + 16, hi);
-            unsigned long long pos = max(o, Ob);
-            while (pos < e) {
-                unsigned l = 0, h = cnt + 1;                    // the last segment k with so[k] <= pos
-                while (h - l > 1) {
-                    const unsigned m = (l + h) >> 1;
-                    if (so[m] <= pos) l = m;
-                    else h = m;
-                }
-                const unsigned long long gs = so[l], ge = GAPS ? gs + sgl[l] : gs;
-                unsigned long long pe;
-                if (GAPS && pos < ge) {                         // the input gap
-                    pe = min(ge, e);
-                    rp_merge(acc, in, (long long)(ssrc[l] + o - gs), n_avail, (unsigned)(pos - o), (unsigned)(pe - o));
-                } else if constexpr (!TEMPLATES) {              // the replacement (l < cnt here)
-                    pe = min(so[l + 1], e);
-                    rp_merge(acc, rep, (long long)sro[l] + (long long)(o - ge), rep_size, (unsigned)(pos - o), (unsigned)(pe - o));
-                } else {                                        // R[:split], the match as the caller wrote it, R[split:]
-                    const unsigned long long m0 = ge + ssp[l], m1 = m0 + sml[l];
-                    if (pos < m0) {
-                        pe = min(m0, e);
-                        rp_merge(acc, rep, (long long)sro[l] + (long long)(o - ge), rep_size, (unsigned)(pos - o), (unsigned)(pe - o));
-                    } else if (pos < m1) {
-                        pe = min(m1, e);
-                        rp_merge(acc, in, (long long)(ssrc[l] + (ge - gs)) + (long long)(o - m0), n_avail, (unsigned)(pos - o), (unsigned)(pe - o));
-                    } else {
-                        pe = min(so[l + 1], e);
-                        rp_merge(acc, rep, (long long)sro[l] + (long long)ssp[l] + (long long)(o - m1), rep_size, (unsigned)(pos - o), (unsigned)(pe - o));
-                    }
-                }
-                pos = pe;
-            }
-            if (hi >= W + RP_WIN || hi >= out_bytes) break;
-            b = rp_find(X, gpre, nb, b + 1, hi);
-            wave_lds_sync();                                    // (every lane is done with the old block)
-            load_block();
-        }
-        if (o + 16 <= out_bytes) {
-            *reinterpret_cast<uint4 *>(out + o) = acc;
-        } else if (o < out_bytes) {                             // the last partial 16 B of the whole output
-            const unsigned m = (unsigned)(out_bytes - o);
-            const unsigned v[4] = {acc.x, acc.y, acc.z, acc.w};
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                if ((unsigned)(4 * i + 4) <= m) {
-                    *reinterpret_cast<unsigned *>(out + o + 4 * i) = v[i];
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 4; j++)
-                        if ((unsigned)(4 * i + j) < m) out[o + 4 * i + j] = (unsigned char)(v[i] >> (8 * j));
-                }
+    rp_write_windows(lane, w, X, gpre, nb, out_bytes, wins, out, load_block,
+                     [&](unsigned cnt, uint4 &acc, unsigned long long o, unsigned long long pos, unsigned long long e) {
+        const unsigned l = rp_segment(so, cnt + 1, pos);
+        const unsigned long long gs = so[l], ge = GAPS ? gs + sgl[l] : gs;
+        unsigned long long pe;
+        if (GAPS && pos < ge) {                                 // the input gap
+            pe = min(ge, e);
+            rp_merge(acc, in, (long long)(ssrc[l] + o - gs), n_avail, (unsigned)(pos - o), (unsigned)(pe - o));
+        } else if constexpr (!TEMPLATES) {                      // the replacement (l < cnt here)
+            pe = min(so[l + 1], e);
+            rp_merge(acc, rep, (long long)sro[l] + (long long)(o - ge), rep_size, (unsigned)(pos - o), (unsigned)(pe - o));
+        } else {                                                // R[:split], the match as the caller wrote it, R[split:]
+            const unsigned long long m0 = ge + ssp[l], m1 = m0 + sml[l];
+            if (pos < m0) {
+                pe = min(m0, e);
+                rp_merge(acc, rep, (long long)sro[l] + (long long)(o - ge), rep_size, (unsigned)(pos - o), (unsigned)(pe - o));
+            } else if (pos < m1) {
+                pe = min(m1, e);
+                rp_merge(acc, in, (long long)(ssrc[l] + (ge - gs)) + (long long)(o - m0), n_avail, (unsigned)(pos - o), (unsigned)(pe - o));
+            } else {
+                pe = min(so[l + 1], e);
+                rp_merge(acc, rep, (long long)sro[l] + (long long)ssp[l] + (long long)(o - m1), rep_size, (unsigned)(pos - o), (unsigned)(pe - o));
             }
         }
-    }
+        return pe;
+    });
 }
 
 // Per-document output offsets (pfac_replace_documents), for a selection made from entry 0: out_off[d] = off[d] +
@@ -3517,9 +3562,7 @@ pfac_rp_doc_delta_kernel(const pfac_record *sel, unsigned long long n, const sho
             base = X[b] + gpre[b / RP_GROUP];
         }
     }
-    const unsigned long long incl = base + wave_incl_scan64(dk);
-    if (k < n) D[k] = incl - dk;
-    if (k + 1 == n) D[n] = incl;
+    rp_block_offsets(base, dk, k, n, D);
 }
 
 __global__ void pfac_rp_doc_offsets_kernel(const unsigned long long *off, const unsigned long long *doc_first,
@@ -3883,12 +3926,9 @@ pfac_docs_groups_kernel(const unsigned long long *masks, unsigned long long n_do
 //                            lengths before it in its group, and the group's sum
 //   pfac_scan_groups_kernel  the group prefixes and the total = out_bytes, which the host checks before anything is written
 //   pfac_ga_offsets_kernel   one wave per block: out_off[k] for every id, out_off[n_ids] = out_bytes
-//   pfac_ga_write_kernel     output-driven, the loop of pfac_rp_write_kernel: every wave owns `wins` windows of 1 KiB, one
-//                            16-B chunk per lane.  rp_find (gallop, then narrow, 64 probes a round) gives the block that
-//                            holds the window's first byte -- never a walk from id 0, and blocks of empty documents are
-//                            skipped; the block's 65 output offsets and 64 source offsets go to LDS; each lane finds its
-//                            segments there by bisection, merges their unaligned source runs in registers (rp_merge) and
-//                            stores one dwordx4.  Only the last partial 16 B of the output is stored in pieces.
+//   pfac_ga_write_kernel     output-driven, the replace's loop (rp_write_windows) -- never a walk from id 0, and blocks
+//                            of empty documents are skipped -- over its own block: 65 output offsets and 64 source
+//                            offsets in LDS, and a segment that is one piece, an unaligned source run (rp_merge).
 // A block's prefix is O_{64b} = X[b] + gpre[b / RP_GROUP] (rp_block_out), as in the replace.
 
 __global__ void __launch_bounds__(RP_GROUP / 4 * WAVE)
@@ -3917,14 +3957,7 @@ pfac_ga_count_kernel(const unsigned long long *ids, unsigned long long n, const 
         if (lane == 0) bsum[lb] = s;
     }
     if (__ballot(bad) && lane == 0) atomicOr(&res[0], 1ull);
-    __syncthreads();
-    if (threadIdx.x < RP_GROUP) {
-        const unsigned long long b = (unsigned long long)blockIdx.x * RP_GROUP + threadIdx.x;
-        unsigned long long pre = 0;
-        for (unsigned j = 0; j < threadIdx.x; j++) pre += bsum[j];
-        if (b < nb) X[b] = pre;
-        if (threadIdx.x == RP_GROUP - 1) gsum[blockIdx.x] = pre + bsum[RP_GROUP - 1];
-    }
+    rp_count_out(bsum, nb, X, gsum, [](unsigned) { return 0ull; });
 }
 
 // (behind the host's check of the count pass: every id is below n_docs and its offsets ascend)
@@ -3939,9 +3972,7 @@ pfac_ga_offsets_kernel(const unsigned long long *ids, unsigned long long n, cons
         const unsigned long long id = ids[k];
         len = off[id + 1] - off[id];
     }
-    const unsigned long long incl = rp_block_out(X, gpre, b) + wave_incl_scan64(len);
-    if (k < n) out_off[k] = incl - len;
-    if (k + 1 == n) out_off[n] = incl;
+    rp_block_offsets(rp_block_out(X, gpre, b), len, k, n, out_off);
 }
 
 __global__ void __launch_bounds__(RP_WAVES * WAVE)
@@ -3951,14 +3982,9 @@ pfac_ga_write_kernel(const unsigned char *in, unsigned long long n_bytes, const 
     __shared__ unsigned long long s_o[RP_WAVES][RP_BLOCK + 1];      // segment k's output offset (k = cnt: the block's end)
     __shared__ unsigned long long s_src[RP_WAVES][RP_BLOCK];        // where it starts in the input
     const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x >> 6;
-    const unsigned long long A = ((unsigned long long)blockIdx.x * RP_WAVES + (unsigned)w) * wins * RP_WIN;
-    if (A >= out_bytes) return;
     const unsigned long long nb = (n + RP_BLOCK - 1) / RP_BLOCK;    // (n > 0: there are output bytes)
     unsigned long long *so = s_o[w], *ssrc = s_src[w];
-    unsigned long long b = rp_find(X, gpre, nb, 0, A);
-    unsigned long long Ob = 0, hi = 0;
-    unsigned cnt = 0;
-    auto load_block = [&]() {
+    auto load_block = [&](unsigned long long b, unsigned long long &Ob, unsigned long long &hi, unsigned &cnt) {
         const unsigned long long k = b * RP_BLOCK + (unsigned)lane;
         cnt = (unsigned)min((unsigned long long)RP_BLOCK, n - b * RP_BLOCK);
         if (k <= n) so[lane] = out_off[k];                          // (lane <= cnt; out_off has n + 1 entries)
@@ -3968,48 +3994,13 @@ pfac_ga_write_kernel(const unsigned char *in, unsigned long long n_bytes, const 
         Ob = so[0];
         hi = so[cnt];
     };
-    load_block();
-    for (unsigned wi = 0; wi < wins; wi++) {
-        const unsigned long long W = A + (unsigned long long)wi * RP_WIN;
-        if (W >= out_bytes) break;
-        const unsigned long long o = W + 16ull * (unsigned)lane;
-        uint4 acc = make_uint4(0u, 0u, 0u, 0u);
-        for (;;) {
-            const unsigned long long e = min(o + 16, hi);
-            unsigned long long pos = max(o, Ob);
-            while (pos < e) {
-                unsigned l = 0, h = cnt;                            // the last segment k < cnt with so[k] <= pos: so[k + 1] > pos
-                while (h - l > 1) {
-                    const unsigned m = (l + h) >> 1;
-                    if (so[m] <= pos) l = m;
-                    else h = m;
-                }
-                const unsigned long long pe = min(so[l + 1], e);
-                rp_merge(acc, in, (long long)(ssrc[l] + o - so[l]), n_bytes, (unsigned)(pos - o), (unsigned)(pe - o));
-                pos = pe;
-            }
-            if (hi >= W + RP_WIN || hi >= out_bytes) break;
-            b = rp_find(X, gpre, nb, b + 1, hi);
-            wave_lds_sync();                                        // (every lane is done with the old block)
-            load_block();
-        }
-        if (o + 16 <= out_bytes) {
-            *reinterpret_cast<uint4 *>(out + o) = acc;
-        } else if (o < out_bytes) {                                 // the last partial 16 B of the whole output
-            const unsigned m = (unsigned)(out_bytes - o);
-            const unsigned v[4] = {acc.x, acc.y, acc.z, acc.w};
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                if ((unsigned)(4 * i + 4) <= m) {
-                    *reinterpret_cast<unsigned *>(out + o + 4 * i) = v[i];
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 4; j++)
-                        if ((unsigned)(4 * i + j) < m) out[o + 4 * i + j] = (unsigned char)(v[i] >> (8 * j));
-                }
-            }
-        }
-    }
+    rp_write_windows(lane, w, X, gpre, nb, out_bytes, wins, out, load_block,
+                     [&](unsigned cnt, uint4 &acc, unsigned long long o, unsigned long long pos, unsigned long long e) {
+        const unsigned l = rp_segment(so, cnt, pos);                // (k < cnt: so[k + 1] > pos)
+        const unsigned long long pe = min(so[l + 1], e);
+        rp_merge(acc, in, (long long)(ssrc[l] + o - so[l]), n_bytes, (unsigned)(pos - o), (unsigned)(pe - o));
+        return pe;
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -5738,14 +5729,12 @@ int pfac_group_masks_d2h(pfac_ctx *ctx, int slot, uint64_t *host_masks, uint64_t
     return fetch(ctx, s, s.gm_out, "pfac_group_masks_d2h", "pfac_documents_group_masks", host_masks, first, n);
 }
 
-// The offsets' rules alone, on the slot's stream (pfac_seg_count_kernel without tiles): *bad becomes non-zero where
-// the offsets do not start at 0, decrease, or do not end at the scan's n_owned.
-static void launch_offsets_check(pfac_ctx *ctx, Slot &s, const unsigned long long *off, uint64_t n_docs, unsigned long long *bad) {
+// The offsets' rules alone, on the slot's stream (offsets_rule, for a pass whose first kernel does not carry it): *bad
+// becomes non-zero where the offsets do not start at 0, decrease, or do not end at the scan's n_owned.
+static void launch_offsets_check(Slot &s, const unsigned long long *off, uint64_t n_docs, unsigned long long *bad) {
     const unsigned vblocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_docs + 255) / 256, 4096));
-    hipLaunchKernelGGL(pfac_seg_count_kernel<4>, dim3(vblocks), dim3(256), 0, s.stream, (const void *)nullptr,
-                       (const unsigned long long *)nullptr, 0ull, 0ull, off, (unsigned long long)n_docs,
-                       (unsigned long long)s.last_owned, ctx->flen.p, (unsigned)ctx->plan.base.num_final, (unsigned *)nullptr,
-                       (unsigned long long *)nullptr, 0u, bad);
+    hipLaunchKernelGGL(pfac_offsets_check_kernel, dim3(vblocks), dim3(256), 0, s.stream, off, (unsigned long long)n_docs,
+                       (unsigned long long)s.last_owned, bad);
 }
 
 // Grid of the output-windowed write kernels (replace, gather) for `total` output bytes: one window of 1 KiB per wave
@@ -5979,7 +5968,7 @@ int pfac_records_filter_words(pfac_ctx *ctx, int slot, const void *d_input, void
     if (rc) return rc;
     unsigned long long *res = s.gsum.p;
     HIP_TRY(ctx, hipMemsetAsync(res, 0, 16, s.stream));
-    if (n_docs) launch_offsets_check(ctx, s, off, n_docs, res + 1);     // in front of the filter
+    if (n_docs) launch_offsets_check(s, off, n_docs, res + 1);          // in front of the filter
     if (n_groups) {
         const bool dk = n_docs != 0;
         auto fk = by_width(s.last_rec_bytes, [dk](auto w) { return dk ? pfac_filter_words_kernel<w(), true> : pfac_filter_words_kernel<w(), false>; });
@@ -6062,7 +6051,7 @@ int pfac_records_filter_spans(pfac_ctx *ctx, int slot, const void *d_input, void
     if (rc) return rc;
     unsigned long long *res = s.gsum.p;
     HIP_TRY(ctx, hipMemsetAsync(res, 0, 16, s.stream));
-    if (n_docs) launch_offsets_check(ctx, s, off, n_docs, res + 1);     // in front of the filter
+    if (n_docs) launch_offsets_check(s, off, n_docs, res + 1);          // in front of the filter
     if (n_groups) {
         const bool dk = n_docs != 0;
         auto fk = by_width(s.last_rec_bytes, [dk, line](auto w) {
@@ -6138,7 +6127,7 @@ static int ll_select(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *
         rc = ensure_gsum(ctx, s, 1);
         if (rc) return rc;
         HIP_TRY(ctx, hipMemsetAsync(s.gsum.p, 0, 8, s.stream));
-        launch_offsets_check(ctx, s, off, n_docs, s.gsum.p);
+        launch_offsets_check(s, off, n_docs, s.gsum.p);
         rc = pass_words(ctx, s, s.gsum.p, 1, H_PASS1);
         if (rc) return rc;
         if (host_u64(s, H_PASS1)) return bad_doc_offsets(ctx, s, fn);

@@ -95,7 +95,8 @@ def length_cases():
         _case("one_5000_between_short", np.concatenate([short[:20], [5000], short[20:]]), np.arange(41), 6, "long_doc"),
         _case("one_doc_whole_input", [big], [0], 7, "whole_input"),
         _case("many_empty_then_one", np.concatenate([np.zeros(3000, np.int64), [37]]), np.arange(3001), 8, "empty_blocks"),
-    ]
+        # the whole output one byte short of, exactly, and one byte past a lane's 16-byte chunk and a wave's 1 KiB window
+    ] + [_case(f"out_{n}", [n - 9, 0, 9], [0, 1, 2], 40 + n) for n in (15, 16, 17, 1023, 1024, 1025)]
 
 
 def ladder_cases():

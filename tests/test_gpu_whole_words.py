@@ -374,6 +374,21 @@ def test_bad_offsets_leave_the_scan_unfiltered(resolve):
         g.set_doc_offsets(np.array([0, 20_000], dtype=np.uint64))
         assert status_of(lambda: g.filter_whole_words(n_docs=2)) == _ffi.PFAC_E_STATE     # not the slot's n_docs
         assert g.filter_whole_words(n_docs=1) == int(wordref.filter_words(buf, pos, lens).sum())
+        # The offsets' check with no tiles behind it: a scan of zero bytes owns none, so every offset must be 0.  n_docs on
+        # both sides of one workgroup of the check and above its grid of 4096 x 256 threads (the stride loop runs twice);
+        # the broken rule first in thread 0's offsets, then in the last thread's (a decreasing pair needs two documents).
+        assert scan(g, np.zeros(0, dtype=np.uint8)) == 0
+        for n_docs in (1, 256, 257, 4096 * 256 + 300):
+            for k in (0, n_docs - 1) if n_docs > 1 else (0,):
+                off = np.zeros(n_docs + 1, dtype=np.uint64)
+                off[k] = 1                                      # k = 0: off[0] != 0; else off[k] > off[k + 1]
+                g.set_doc_offsets(off)
+                assert status_of(lambda: g.filter_whole_words(n_docs=n_docs)) == _ffi.PFAC_E_ARG
+                assert status_of(lambda: g.select_leftmost_longest_documents(n_docs)) == _ffi.PFAC_E_ARG
+                assert g.scan_finish()[0] == 0
+            g.set_doc_offsets(np.zeros(n_docs + 1, dtype=np.uint64))
+            assert g.filter_whole_words(n_docs=n_docs) == 0
+            assert g.select_leftmost_longest_documents(n_docs) == 0
 
 
 # ---------------------------------------------------------------------------
