@@ -20,7 +20,13 @@ usage: fuzz.py [seconds] [seed]
                                             edges, word sets, neighbour bytes and document cuts -- the filtered records,
                                             the selection and the replacement or the document cut behind the filter,
                                             against tests/wordref.py over the CPU oracle's records.  One child process
-                                            per case under a time limit, as `guard`"""
+                                            per case under a time limit, as `guard`
+       fuzz.py late [seconds] [seed]        the passes behind those instead (tests/latefuzz.py): the span filter, the group
+                                            masks with their predicate and the gather, the per-document selection, replacement
+                                            templates and match extraction per document and over the whole stream, the plain
+                                            replace on the same selection -- exact and case-folded tables, lines cut on the
+                                            device or explicit offsets, every step against the host references over the CPU
+                                            oracle's records.  One child process per case under a time limit, as `guard`"""
 import os, sys, tempfile, time
 os.environ.setdefault("PFAC_ENABLE_KNOBS", "1")     # tuning / test knobs of libpfac_hip.so are opt-in
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -168,6 +174,43 @@ if len(sys.argv) > 1 and sys.argv[1] == "words":
             t_last = time.time(); print(f"  ... {cases} cases, {recs} records compared, {t_last - t0:.0f} s", flush=True)
     print(f"words fuzz ok: {cases} cases in {time.time() - t0:.0f} s (seed {seed}), {recs} records compared (scan, filter, "
           f"selection + replace or documents)")
+    print("cases per knob set: " + ", ".join(f"{k} {v}" for k, v in sorted(per_knob.items())))
+    raise SystemExit(0)
+if len(sys.argv) > 1 and sys.argv[1] == "late-case":          # one case on the GPU (the child of `late` below)
+    import latefuzz as LF
+    case_seed = int(sys.argv[2])
+    c = LF.LateCase(case_seed, LF.KNOBS[int(np.random.default_rng([case_seed, 0x4B4E4F42]).integers(0, len(LF.KNOBS)))])
+    for k in set(KNOB_NAMES) | set(LF.KNOB_NAMES): os.environ.pop(k, None)
+    os.environ.update(c.knobs)
+    try:
+        n_rec, n_bytes = LF.run_late_case(lambda: GpuMatcher(0, 1), c, tempfile.mkdtemp())
+    except AssertionError as e:
+        raise SystemExit(f"MISMATCH: {e}")
+    print(f"{n_rec} {n_bytes} {knob_label(c.knobs)}")
+    raise SystemExit(0)
+if len(sys.argv) > 1 and sys.argv[1] == "late":
+    import subprocess
+    import latefuzz as LF
+    seconds = float(sys.argv[2]) if len(sys.argv) > 2 else 60.0
+    seed = int(sys.argv[3]) if len(sys.argv) > 3 else 1
+    STEP_LIMIT = 120                                           # seconds one case may take
+    t0 = t_last = time.time(); cases = 0; recs = 0; nbytes = 0; per_knob = {}
+    while time.time() - t0 < seconds:
+        case_seed = (seed << 32) + len(LF.SEEDS) + cases       # (beyond the suite's seeds)
+        try:                                                   # (this process never opens the GPU: every case is a fresh child)
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "late-case", str(case_seed)], capture_output=True,
+                               text=True, timeout=STEP_LIMIT)
+        except subprocess.TimeoutExpired:
+            raise SystemExit(f"TIME LIMIT: case {cases} (fuzz.py late-case {case_seed}) ran over {STEP_LIMIT} s; stopping")
+        if r.returncode:
+            raise SystemExit(f"FAILED case {cases} (fuzz.py late-case {case_seed}), exit status {r.returncode}; stopping\n"
+                             + r.stdout[-2000:] + r.stderr[-4000:])
+        n, b, label = r.stdout.strip().split("\n")[-1].split(" ", 2)
+        recs += int(n); nbytes += int(b); per_knob[label] = per_knob.get(label, 0) + 1; cases += 1
+        if time.time() - t_last > 30:
+            t_last = time.time(); print(f"  ... {cases} cases, {recs} records and {nbytes} bytes compared, {t_last - t0:.0f} s", flush=True)
+    print(f"late fuzz ok: {cases} cases in {time.time() - t0:.0f} s (seed {seed}), {recs} records and {nbytes} bytes compared (scan, "
+          f"span filter, group masks + gather, selections, templated replace + extraction, plain replace)")
     print("cases per knob set: " + ", ".join(f"{k} {v}" for k, v in sorted(per_knob.items())))
     raise SystemExit(0)
 seconds = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
