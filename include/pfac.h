@@ -599,6 +599,56 @@ int pfac_documents_gather_d2h(pfac_ctx *ctx, int slot, void *host, uint64_t firs
  * stream; pfac_slot_sync completes it. */
 int pfac_documents_gather_offsets_d2h(pfac_ctx *ctx, int slot, uint64_t *host_out_offsets);
 
+/* The gather with labels: the finished text of grep -n, -b, -A / -B / -C and the final newline.  Segment k of the output
+ * is, in this order (id = ids[k], off = the document offsets):
+ *   1. group_sep[0 : group_sep_len], if group_sep_len > 0 and either k > 0 && ids[k] != ids[k - 1] + 1 (a repeat or a
+ *      descending step is "not adjacent"), or k == 0 with PFAC_LINE_SEP_FIRST
+ *   2. with PFAC_LINE_NUMBER: the decimal of id + number_base, no padding, then the label separator
+ *   3. with PFAC_LINE_OFFSET: the decimal of off[id] + offset_base, then the label separator
+ *   4. the body, in[off[id] : off[id + 1]]
+ *   5. with PFAC_LINE_TERMINATE: the byte `terminator`, if the document is empty or its last byte is not `terminator`
+ * out_off[k] is the offset of segment k's first byte, its group separator included; out_off[n_ids] = *out_bytes.
+ * The label separator is sep_match; under PFAC_LINE_CONTEXT_SEP it is sep_context where doc_first[id + 1] ==
+ * doc_first[id] (a context line: a document without a kept record).  d_doc_first is read only under that flag: NULL =
+ * the slot-owned doc_first of the slot's last pfac_records_segment, with the rules and errors of
+ * pfac_documents_matching (PFAC_E_STATE if the slot holds none, PFAC_E_ARG if n_docs is not that call's).
+ * A chunked reader continues the numbering with number_base and offset_base (the lines and bytes of the chunks before
+ * this one) and PFAC_LINE_SEP_FIRST (the chunk before printed a line that the first one here does not follow).
+ * fmt == NULL, or a fmt with flags == 0 and group_sep_len == 0, gives output and offsets byte for byte those of
+ * pfac_documents_gather.  Every other argument follows pfac_documents_gather: its checks on the device before anything
+ * is written, PFAC_E_OVERFLOW with *out_bytes exact and every caller's buffer untouched, n_ids == 0 writing the single
+ * offset 0 (a separator stands in front of a segment, never on its own).  PFAC_E_ARG also for flags outside the five,
+ * group_sep_len > 8, and number_base + n_docs > 10^18 or offset_base + n_bytes > 10^18 (every printed value has at most
+ * 18 digits).  Input reads stay below n_bytes: the terminator test reads in[off[id + 1] - 1] and nothing else, whole
+ * 16-byte loads follow the gather's rule.  No byte at or past *out_bytes is written.
+ * The call is ONE pass with pfac_documents_gather: they share the slot-owned output and offsets,
+ * pfac_documents_gather_d2h and pfac_documents_gather_offsets_d2h fetch either call's result, and the next call of
+ * either discards it, even when that call fails.
+ * Kernels: siblings of the gather's.  The count pass adds the label lengths (digit counts), the id in front (a lane
+ * shuffle) and, under PFAC_LINE_TERMINATE, one input byte; the write keeps each segment's id, source offset and piece
+ * lengths (one 32-bit word) in LDS and makes the digits a lane owns in registers -- one divide by a power of ten, then
+ * peeled by 10 -- so the output is written once, in whole 16-byte stores, with no scratch copy of the labels. */
+#define PFAC_LINE_NUMBER      1u   /* decimal of ids[k] + number_base, then the label separator          */
+#define PFAC_LINE_OFFSET      2u   /* decimal of off[ids[k]] + offset_base, then the label separator     */
+#define PFAC_LINE_TERMINATE   4u   /* append `terminator` to a document that is empty or does not end in it */
+#define PFAC_LINE_CONTEXT_SEP 8u   /* label separator = sep_context for a document without a kept record */
+#define PFAC_LINE_SEP_FIRST  16u   /* the group separator also in front of ids[0]                        */
+#define PFAC_LINE_MAX_GROUP_SEP 8u
+typedef struct pfac_line_format {
+    uint32_t flags;
+    uint8_t  sep_match;        /* ':' */
+    uint8_t  sep_context;      /* '-' */
+    uint8_t  terminator;       /* '\n' */
+    uint8_t  group_sep_len;    /* 0..8; 0 = no group separators */
+    uint8_t  group_sep[8];     /* "--\n" */
+    uint64_t number_base;      /* grep -n: 1 */
+    uint64_t offset_base;      /* bytes of the chunks before this one */
+} pfac_line_format;
+int pfac_documents_gather_format(pfac_ctx *ctx, int slot, const void *d_input, uint64_t n_bytes, const uint64_t *d_doc_offsets,
+                                 uint64_t n_docs, const uint64_t *d_ids, uint64_t n_ids, const uint64_t *d_doc_first,
+                                 const pfac_line_format *fmt, void *d_out, uint64_t out_cap, uint64_t *d_out_offsets,
+                                 uint64_t *out_bytes);
+
 /* Pattern groups: which of the caller's pattern CLASSES occur in each document (content rules whose strings must all
  * occur, grep -e groups joined by AND / NOT, label sets per line).  masks[s] is a 64-bit set: bit g is set iff the
  * pattern(s) that end in final state s belong to group g, 0 <= g < 64.  A state with mask 0 belongs to no group; the

@@ -36,6 +36,12 @@ PFAC_FOLD_NONE = 0          # pfac_table_set_case_fold: an exact scan
 PFAC_FOLD_ASCII = 1         # ... the scan folds A-Z of the input to a-z
 PFAC_SPAN_ANY = 0xFFFFFFFF  # pfac_state_span: a bound that is not judged
 PFAC_SPANS_LINE = 1         # pfac_records_filter_spans: every state judged as {0, 0, 0} (grep -x)
+PFAC_LINE_NUMBER = 1        # pfac_documents_gather_format: the decimal of ids[k] + number_base, then the label separator
+PFAC_LINE_OFFSET = 2        # ... the decimal of off[ids[k]] + offset_base, then the label separator
+PFAC_LINE_TERMINATE = 4     # ... the terminator behind a document that is empty or does not end in it
+PFAC_LINE_CONTEXT_SEP = 8   # ... sep_context as label separator for a document without a kept record
+PFAC_LINE_SEP_FIRST = 16    # ... the group separator also in front of ids[0]
+PFAC_LINE_MAX_GROUP_SEP = 8
 
 _STATUS_NAMES = {
     0: "PFAC_OK", -1: "PFAC_E_ARG", -2: "PFAC_E_IO", -3: "PFAC_E_PATTERN", -4: "PFAC_E_NOMEM",
@@ -78,6 +84,13 @@ class CThreadData(C.Structure):
                 ("HT", C.c_void_p), ("val", C.c_void_p)]
 
 
+class CLineFormat(C.Structure):
+    """struct pfac_line_format (pfac_documents_gather_format)."""
+    _fields_ = [("flags", C.c_uint32), ("sep_match", C.c_uint8), ("sep_context", C.c_uint8), ("terminator", C.c_uint8),
+                ("group_sep_len", C.c_uint8), ("group_sep", C.c_uint8 * 8), ("number_base", C.c_uint64),
+                ("offset_base", C.c_uint64)]
+
+
 # struct pfac_state_span as a numpy dtype (16 bytes: what pfac_table_set_state_spans takes)
 SPAN_DTYPE = [("min_start", "<u4"), ("max_start", "<u4"), ("max_tail", "<u4"), ("reserved", "<u4")]
 
@@ -110,6 +123,7 @@ HIP_SYMBOLS = (
     "pfac_table_set_state_groups", "pfac_documents_group_masks", "pfac_group_masks_d2h", "pfac_documents_matching_groups",
     "pfac_table_set_state_spans", "pfac_records_filter_spans",
     "pfac_table_set_replacement_templates", "pfac_extract_leftmost_longest", "pfac_extract_d2h", "pfac_extract_offsets_d2h",
+    "pfac_documents_gather_format",
 )
 
 _host = None
@@ -255,6 +269,8 @@ def hip_lib() -> C.CDLL:
         L.pfac_documents_matching_d2h.argtypes = [vp, i, vp]
         L.pfac_documents_matching_context.argtypes = [vp, i, vp, u64, u64, u64, C.c_uint32, vp, u64, C.POINTER(u64)]
         L.pfac_documents_gather.argtypes = [vp, i, vp, u64, vp, u64, vp, u64, vp, u64, vp, C.POINTER(u64)]
+        L.pfac_documents_gather_format.argtypes = [vp, i, vp, u64, vp, u64, vp, u64, vp, C.POINTER(CLineFormat), vp, u64, vp,
+                                                   C.POINTER(u64)]
         L.pfac_documents_gather_d2h.argtypes = [vp, i, vp, u64, u64]
         L.pfac_documents_gather_offsets_d2h.argtypes = [vp, i, vp]
         L.pfac_table_set_case_fold.argtypes = [vp, C.c_uint32]

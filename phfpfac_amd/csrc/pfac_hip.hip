@@ -4004,6 +4004,264 @@ pfac_ga_write_kernel(const unsigned char *in, unsigned long long n_bytes, const 
 }
 
 // ---------------------------------------------------------------------------
+// The gather with labels (pfac_documents_gather_format: grep -n, -b, the "--" lines of -A / -B / -C, the final
+// newline).  Segment k is up to five pieces: the group separator (ids[k] does not follow ids[k - 1]), the decimal of
+// the line number and its label separator, the decimal of the byte offset and its label separator, the body, and the
+// terminator where the body lacks it.  The gather's shape, as siblings of its kernels (the plain gather's are not
+// touched: they keep their code):
+//   pfac_gf_count_kernel     the gather's count with gf_segment_len for the length: besides the two offset gathers the
+//                            id in front (a lane shuffle; a load for lane 0) and, under TERMINATE, the body's last byte
+//   pfac_scan_groups_kernel
+//   pfac_gf_offsets_kernel   out_off[k] from the same lengths
+//   pfac_gf_write_kernel     rp_write_windows over a block whose LDS also holds each segment's id, its source offset
+//                            and, in one 32-bit word, its piece lengths.  The digits a lane owns are made in registers:
+//                            one divide by a power of ten, then peeled by 10.  No scratch copy of the labels, no second
+//                            pass over the output.
+
+struct GfFormat {
+    unsigned flags;                         // PFAC_LINE_*
+    unsigned sep_len;                       // group_sep_len
+    unsigned chars;                         // sep_match | sep_context << 8 | terminator << 16
+    unsigned long long sep;                 // group_sep, byte i at bits [8 i, 8 i + 8)
+    unsigned long long number_base, offset_base;
+};
+
+// piece lengths of a segment in one word: the group separator (0..8), the number with its label separator (0..19), the
+// offset with its (0..19), the terminator (0..1), and whether the label separator is sep_context
+constexpr unsigned GF_NUM_SHIFT = 4, GF_OFF_SHIFT = 9, GF_TERM_SHIFT = 14, GF_CTX_SHIFT = 15;
+
+// the pieces in front of the body of the segment of document id at source offset lo, `follows`: id == the id in front + 1
+__device__ __forceinline__ unsigned gf_head_pieces(const GfFormat &f, unsigned long long id, unsigned long long lo, bool first,
+                                                   bool follows) {
+    unsigned w = 0;
+    if (first ? (f.flags & PFAC_LINE_SEP_FIRST) != 0 : !follows) w = f.sep_len;
+    if (f.flags & PFAC_LINE_NUMBER) w |= (ndigits64(id + f.number_base) + 1u) << GF_NUM_SHIFT;
+    if (f.flags & PFAC_LINE_OFFSET) w |= (ndigits64(lo + f.offset_base) + 1u) << GF_OFF_SHIFT;
+    return w;
+}
+__device__ __forceinline__ unsigned gf_head_len(unsigned w) {
+    return (w & 15u) + ((w >> GF_NUM_SHIFT) & 31u) + ((w >> GF_OFF_SHIFT) & 31u);
+}
+
+// Length of segment k (valid id, lo <= hi <= n_bytes): lane `lane` of a wave whose lanes hold consecutive k
+__device__ __forceinline__ unsigned long long gf_segment_len(const GfFormat &f, const unsigned char *in, const unsigned long long *ids,
+                                                             unsigned long long k, unsigned long long id, bool ok,
+                                                             unsigned long long lo, unsigned long long hi, int lane) {
+    unsigned long long prev = __shfl_up(id, 1u, WAVE);
+    if (lane == 0 && k > 0 && ok) prev = ids[k - 1];
+    if (!ok) return 0ull;
+    unsigned long long len = gf_head_len(gf_head_pieces(f, id, lo, k == 0, id == prev + 1)) + (hi - lo);
+    if (f.flags & PFAC_LINE_TERMINATE) len += (hi == lo || in[hi - 1] != (unsigned char)(f.chars >> 16)) ? 1u : 0u;
+    return len;
+}
+
+__global__ void __launch_bounds__(RP_GROUP / 4 * WAVE)
+pfac_gf_count_kernel(const unsigned char *in, const unsigned long long *ids, unsigned long long n, const unsigned long long *off,
+                     unsigned long long n_docs, unsigned long long n_bytes, GfFormat f, unsigned long long *X,
+                     unsigned long long *gsum, unsigned long long *res) {
+    __shared__ unsigned long long bsum[RP_GROUP];
+    const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x >> 6;
+    const unsigned long long nb = (n + RP_BLOCK - 1) / RP_BLOCK;
+    bool bad = false;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const unsigned lb = (unsigned)w * 4 + (unsigned)i;
+        const unsigned long long k = ((unsigned long long)blockIdx.x * RP_GROUP + lb) * RP_BLOCK + (unsigned)lane;
+        unsigned long long id = 0, lo = 0, hi = 0;
+        bool ok = false;
+        if (k < n) {
+            id = ids[k];
+            if (id < n_docs) {
+                lo = off[id];
+                hi = off[id + 1];
+                ok = lo <= hi && hi <= n_bytes;
+            }
+            bad |= !ok;
+        }
+        const unsigned long long s = wave_sum64(gf_segment_len(f, in, ids, k, id, ok, lo, hi, lane));
+        if (lane == 0) bsum[lb] = s;
+    }
+    if (__ballot(bad) && lane == 0) atomicOr(&res[0], 1ull);
+    rp_count_out(bsum, nb, X, gsum, [](unsigned) { return 0ull; });
+}
+
+// (behind the host's check of the count pass: every id is below n_docs and its offsets ascend)
+__global__ void __launch_bounds__(4 * WAVE)
+pfac_gf_offsets_kernel(const unsigned char *in, const unsigned long long *ids, unsigned long long n, const unsigned long long *off,
+                       GfFormat f, const unsigned long long *X, const unsigned long long *gpre, unsigned long long *out_off) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    const unsigned long long b = (unsigned long long)blockIdx.x * 4 + (threadIdx.x >> 6), k = b * RP_BLOCK + (unsigned)lane;
+    if (b * RP_BLOCK >= n) return;
+    unsigned long long id = 0, lo = 0, hi = 0;
+    if (k < n) {
+        id = ids[k];
+        lo = off[id];
+        hi = off[id + 1];
+    }
+    rp_block_offsets(rp_block_out(X, gpre, b), gf_segment_len(f, in, ids, k, id, k < n, lo, hi, lane), k, n, out_off);
+}
+
+// acc bytes [j0, j1) := bytes [j0, j1) of the 16 bytes (hi : lo), lo's lowest byte being byte 0
+__device__ __forceinline__ void gf_put(uint4 &acc, unsigned long long lo, unsigned long long hi, unsigned j0, unsigned j1) {
+    auto low = [](int m) -> unsigned { return m <= 0 ? 0u : m >= 4 ? 0xffffffffu : (1u << (8 * m)) - 1u; };
+    const unsigned m0 = low((int)j1) & ~low((int)j0), m1 = low((int)j1 - 4) & ~low((int)j0 - 4);
+    const unsigned m2 = low((int)j1 - 8) & ~low((int)j0 - 8), m3 = low((int)j1 - 12) & ~low((int)j0 - 12);
+    acc.x = (acc.x & ~m0) | ((unsigned)lo & m0);
+    acc.y = (acc.y & ~m1) | ((unsigned)(lo >> 32) & m1);
+    acc.z = (acc.z & ~m2) | ((unsigned)hi & m2);
+    acc.w = (acc.w & ~m3) | ((unsigned)(hi >> 32) & m3);
+}
+// byte c at byte j (0..15) of (hi : lo)
+__device__ __forceinline__ void gf_byte(unsigned long long &lo, unsigned long long &hi, unsigned j, unsigned c) {
+    if (j < 8u) lo |= (unsigned long long)c << (8u * j);
+    else hi |= (unsigned long long)c << (8u * (j - 8u));
+}
+
+__device__ __forceinline__ unsigned long long gf_pow10(unsigned e) {         // e <= 17
+    unsigned long long p = e & 1u ? 10ull : 1ull;
+    if (e & 2u) p *= 100ull;
+    if (e & 4u) p *= 10000ull;
+    if (e & 8u) p *= 100000000ull;
+    if (e & 16u) p *= 10000000000000000ull;
+    return p;
+}
+
+// 16 bytes in registers that grow at the front: push(c) makes c byte 0 and moves the others up by one
+struct GfBytes {
+    unsigned w0 = 0, w1 = 0, w2 = 0, w3 = 0;
+    __device__ __forceinline__ void push(unsigned c) {
+        w3 = __builtin_amdgcn_alignbit(w3, w2, 24);
+        w2 = __builtin_amdgcn_alignbit(w2, w1, 24);
+        w1 = __builtin_amdgcn_alignbit(w1, w0, 24);
+        w0 = w0 << 8 | c;
+    }
+    // acc bytes [j0, j1) := bytes [0, j1 - j0)
+    __device__ __forceinline__ void put(uint4 &acc, unsigned j0, unsigned j1) const {
+        const unsigned q = j0 >> 2, r = 8u * (j0 & 3u);
+        const unsigned y0 = q == 0 ? w0 : 0u, y1 = q == 0 ? w1 : q == 1 ? w0 : 0u;
+        const unsigned y2 = q == 0 ? w2 : q == 1 ? w1 : q == 2 ? w0 : 0u, y3 = q == 0 ? w3 : q == 1 ? w2 : q == 2 ? w1 : w0;
+        const unsigned long long lo = (unsigned long long)y1 << 32 | y0, hi = (unsigned long long)y3 << 32 | y2;
+        gf_put(acc, lo << r, r ? hi << r | lo >> (64u - r) : hi, j0, j1);
+    }
+};
+
+// The bytes [pos, pe) of a label -- the nd digits of v, then the label separator c -- that starts at output offset ps,
+// into the chunk at o (pos >= o, pe <= o + 16, pe <= ps + nd + 1): digits [pos - ps, min(pe - ps, nd)) of v, the most
+// significant being digit 0, by one divide (only where the chunk ends inside the digits) and a peel from the least
+// significant of them, in 32 bits as soon as the value fits.
+__device__ __forceinline__ void gf_label(uint4 &acc, unsigned long long o, unsigned long long ps, unsigned nd, unsigned long long v,
+                                         unsigned c, unsigned long long pos, unsigned long long pe) {
+    GfBytes w;
+    const unsigned d0 = (unsigned)(pos - ps);
+    unsigned d1 = (unsigned)(pe - ps);
+    if (d1 > nd) {
+        w.push(c);
+        d1 = nd;
+    }
+    if (d1 > d0) {
+        unsigned cnt = d1 - d0;
+        if (v >> 32) {
+            if (d1 < nd) v /= gf_pow10(nd - d1);
+            while (cnt && (v >> 32)) {
+                const unsigned long long q = v / 10ull;
+                w.push((unsigned)'0' + (unsigned)(v - q * 10ull));
+                v = q;
+                cnt--;
+            }
+        } else if (d1 < nd) {
+            v = (unsigned)v / (unsigned)gf_pow10(nd - d1);
+        }
+        unsigned v32 = (unsigned)v;
+        while (cnt) {
+            const unsigned q = v32 / 10u;
+            w.push((unsigned)'0' + (v32 - q * 10u));
+            v32 = q;
+            cnt--;
+        }
+    }
+    w.put(acc, (unsigned)(pos - o), (unsigned)(pe - o));
+}
+
+__global__ void __launch_bounds__(RP_WAVES * WAVE)
+pfac_gf_write_kernel(const unsigned char *in, unsigned long long n_bytes, const unsigned long long *ids, unsigned long long n,
+                     const unsigned long long *off, const unsigned long long *doc_first, GfFormat f,
+                     const unsigned long long *out_off, const unsigned long long *X, const unsigned long long *gpre,
+                     unsigned long long out_bytes, unsigned wins, unsigned char *out) {
+    __shared__ unsigned long long s_o[RP_WAVES][RP_BLOCK + 1];      // segment k's output offset (k = cnt: the block's end)
+    __shared__ unsigned long long s_src[RP_WAVES][RP_BLOCK];        // where its body starts in the input
+    __shared__ unsigned s_id[RP_WAVES][RP_BLOCK];                   // its document (below 2^32)
+    __shared__ unsigned s_pc[RP_WAVES][RP_BLOCK];                   // its piece lengths
+    const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x >> 6;
+    const unsigned long long nb = (n + RP_BLOCK - 1) / RP_BLOCK;    // (n > 0: there are output bytes)
+    unsigned long long *so = s_o[w], *ssrc = s_src[w];
+    unsigned *sid = s_id[w], *spc = s_pc[w];
+    auto load_block = [&](unsigned long long b, unsigned long long &Ob, unsigned long long &hi, unsigned &cnt) {
+        const unsigned long long k = b * RP_BLOCK + (unsigned)lane;
+        cnt = (unsigned)min((unsigned long long)RP_BLOCK, n - b * RP_BLOCK);
+        unsigned long long id = 0;
+        if (k < n) id = ids[k];
+        unsigned long long prev = __shfl_up(id, 1u, WAVE);
+        if (lane == 0 && k > 0) prev = ids[k - 1];
+        if (k <= n) so[lane] = out_off[k];                          // (lane <= cnt; out_off has n + 1 entries)
+        if (k < n) {
+            const unsigned long long lo = off[id], len = out_off[k + 1] - out_off[k];
+            unsigned pc = gf_head_pieces(f, id, lo, k == 0, id == prev + 1);
+            // (the terminator is what the count pass added to the head and the body)
+            pc |= (unsigned)(len - gf_head_len(pc) - (off[id + 1] - lo)) << GF_TERM_SHIFT;
+            if ((f.flags & PFAC_LINE_CONTEXT_SEP) && doc_first[id + 1] == doc_first[id]) pc |= 1u << GF_CTX_SHIFT;
+            ssrc[lane] = lo;
+            sid[lane] = (unsigned)id;
+            spc[lane] = pc;
+        }
+        if (lane == 0 && cnt == (unsigned)RP_BLOCK) so[RP_BLOCK] = out_off[k + RP_BLOCK];
+        wave_lds_sync();
+        Ob = so[0];
+        hi = so[cnt];
+    };
+    rp_write_windows(lane, w, X, gpre, nb, out_bytes, wins, out, load_block,
+                     [&](unsigned cnt, uint4 &acc, unsigned long long o, unsigned long long pos, unsigned long long e) {
+        // everything of the segment that holds pos inside [pos, e), in one call: the bisection runs once per segment
+        // and chunk, as in the plain gather, however many pieces the segment has
+        const unsigned l = rp_segment(so, cnt, pos);                // (k < cnt: so[k + 1] > pos)
+        const unsigned pc = spc[l];
+        const unsigned long long end = so[l + 1], pe = min(end, e);
+        unsigned long long ps = so[l], pn = ps + (pc & 15u);        // the piece at hand is [ps, pn); [a, b) of it lies in [pos, pe)
+        unsigned long long a = max(ps, pos), b = min(pn, pe);
+        if (a < b) {                                                // the group separator
+            const long long sh = (long long)(ps - o);               // -8 < sh < 16
+            const unsigned long long lo = sh < 0 ? f.sep >> (unsigned)(-8 * sh) : sh < 8 ? f.sep << (unsigned)(8 * sh) : 0ull;
+            const unsigned long long hi = sh <= 0 ? 0ull : sh < 8 ? f.sep >> (unsigned)(64 - 8 * sh) : f.sep << (unsigned)(8 * (sh - 8));
+            gf_put(acc, lo, hi, (unsigned)(a - o), (unsigned)(b - o));
+        }
+        const unsigned c = pc >> GF_CTX_SHIFT & 1u ? f.chars >> 8 & 255u : f.chars & 255u;
+        ps = pn;
+        pn = ps + ((pc >> GF_NUM_SHIFT) & 31u);
+        a = max(ps, pos);
+        b = min(pn, pe);
+        if (a < b)                                                  // the line number
+            gf_label(acc, o, ps, (unsigned)(pn - ps) - 1u, (unsigned long long)sid[l] + f.number_base, c, a, b);
+        ps = pn;
+        pn = ps + ((pc >> GF_OFF_SHIFT) & 31u);
+        a = max(ps, pos);
+        b = min(pn, pe);
+        if (a < b)                                                  // the byte offset
+            gf_label(acc, o, ps, (unsigned)(pn - ps) - 1u, ssrc[l] + f.offset_base, c, a, b);
+        ps = pn;
+        pn = end - ((pc >> GF_TERM_SHIFT) & 1u);
+        a = max(ps, pos);
+        b = min(pn, pe);
+        if (a < b)                                                  // the body
+            rp_merge(acc, in, (long long)(ssrc[l] + o - ps), n_bytes, (unsigned)(a - o), (unsigned)(b - o));
+        if (pn < end && pe == end) {                                // the terminator: the segment's last byte (end - 1 >= pos)
+            unsigned long long lo = 0, hi = 0;
+            gf_byte(lo, hi, (unsigned)(pn - o), f.chars >> 16 & 255u);
+            gf_put(acc, lo, hi, (unsigned)(pn - o), (unsigned)(pn - o) + 1u);
+        }
+        return pe;
+    });
+}
+
+// ---------------------------------------------------------------------------
 // runtime
 
 thread_local std::string g_err;
@@ -5842,9 +6100,11 @@ int pfac_documents_matching_d2h(pfac_ctx *ctx, int slot, uint64_t *host_ids) {
     return fetch(ctx, s, s.dm_out, "pfac_documents_matching_d2h", "pfac_documents_matching", host_ids, 0, s.dm_out.n);
 }
 
-int pfac_documents_gather(pfac_ctx *ctx, int slot, const void *d_input, uint64_t n_bytes, const uint64_t *d_doc_offsets,
-                          uint64_t n_docs, const uint64_t *d_ids, uint64_t n_ids, void *d_out, uint64_t out_cap,
-                          uint64_t *d_out_offsets, uint64_t *out_bytes) {
+// The two gathers: the plain one (fmt NULL, or a format that asks for nothing: the plain kernels) and the one with
+// labels.  One pass: one slot-owned output, one slot-owned offset array, one lifetime.
+static int ga_run(pfac_ctx *ctx, int slot, const std::string &fn, const void *d_input, uint64_t n_bytes, const uint64_t *d_doc_offsets,
+                  uint64_t n_docs, const uint64_t *d_ids, uint64_t n_ids, const uint64_t *d_doc_first, const pfac_line_format *fmt,
+                  void *d_out, uint64_t out_cap, uint64_t *d_out_offsets, uint64_t *out_bytes) {
     int rc = check_slot(ctx, slot);
     if (rc) return rc;
     if (!out_bytes) return fail(ctx, PFAC_E_ARG, "null argument");
@@ -5852,7 +6112,6 @@ int pfac_documents_gather(pfac_ctx *ctx, int slot, const void *d_input, uint64_t
     Slot &s = ctx->slots[slot];
     s.ga_out.invalidate();
     s.ga_off.invalidate();
-    const std::string fn = "pfac_documents_gather";
     if (n_bytes > (1ull << 32)) return fail(ctx, PFAC_E_ARG, fn + ": n_bytes must be at most 2^32");
     const unsigned char *in = d_input ? static_cast<const unsigned char *>(d_input) : s.input.p;
     if (!d_input && n_bytes > s.input.cap) return fail(ctx, PFAC_E_ARG, fn + ": n_bytes exceeds the slot's input buffer");
@@ -5869,6 +6128,28 @@ int pfac_documents_gather(pfac_ctx *ctx, int slot, const void *d_input, uint64_t
     if (((uintptr_t)in | (uintptr_t)d_out) & 15) return fail(ctx, PFAC_E_ARG, fn + ": d_input and d_out must be 16-byte aligned");
     if (((uintptr_t)off | (uintptr_t)ids | (uintptr_t)d_out_offsets) & 7)
         return fail(ctx, PFAC_E_ARG, fn + ": d_doc_offsets, d_ids and d_out_offsets must be 8-byte aligned");
+    const bool labels = fmt && (fmt->flags || fmt->group_sep_len);
+    GfFormat gf = {};
+    const unsigned long long *first = nullptr;
+    if (labels) {
+        const uint32_t known = PFAC_LINE_NUMBER | PFAC_LINE_OFFSET | PFAC_LINE_TERMINATE | PFAC_LINE_CONTEXT_SEP | PFAC_LINE_SEP_FIRST;
+        const uint64_t bound = 1000000000000000000ull;          // of ndigits64
+        if (fmt->flags & ~known) return fail(ctx, PFAC_E_ARG, fn + ": unknown flags in the format");
+        if (fmt->group_sep_len > PFAC_LINE_MAX_GROUP_SEP) return fail(ctx, PFAC_E_ARG, fn + ": group_sep_len must be at most 8");
+        if (fmt->number_base > bound || fmt->number_base + n_docs > bound || fmt->offset_base > bound || fmt->offset_base + n_bytes > bound)
+            return fail(ctx, PFAC_E_ARG, fn + ": number_base + n_docs and offset_base + n_bytes must be at most 10^18");
+        if (fmt->flags & PFAC_LINE_CONTEXT_SEP) {
+            rc = s.seg_first.consume(ctx, fn, "doc_first of a pfac_records_segment (n_docs + 1 entries)", d_doc_first, n_docs + 1, &first);
+            if (rc) return rc;
+            if ((uintptr_t)first & 7) return fail(ctx, PFAC_E_ARG, fn + ": d_doc_first must be 8-byte aligned");
+        }
+        gf.flags = fmt->flags;
+        gf.sep_len = fmt->group_sep_len;
+        gf.chars = (unsigned)fmt->sep_match | (unsigned)fmt->sep_context << 8 | (unsigned)fmt->terminator << 16;
+        for (unsigned i = 0; i < gf.sep_len; i++) gf.sep |= (unsigned long long)fmt->group_sep[i] << (8 * i);
+        gf.number_base = fmt->number_base;
+        gf.offset_base = fmt->offset_base;
+    }
     USE_DEVICE(ctx);
     const uint64_t nb = (n_ids + RP_BLOCK - 1) / RP_BLOCK;
     const unsigned n_groups = (unsigned)((nb + RP_GROUP - 1) / RP_GROUP);
@@ -5880,9 +6161,14 @@ int pfac_documents_gather(pfac_ctx *ctx, int slot, const void *d_input, uint64_t
         if (rc) return rc;
         unsigned long long *res = s.gsum.p + n_groups + 1;
         HIP_TRY(ctx, hipMemsetAsync(res, 0, 8, s.stream));
-        hipLaunchKernelGGL(pfac_ga_count_kernel, dim3(n_groups), dim3(RP_GROUP / 4 * WAVE), 0, s.stream, ids,
-                           (unsigned long long)n_ids, off, (unsigned long long)n_docs, (unsigned long long)n_bytes, s.ga_x.p,
-                           s.gsum.p, res);
+        if (labels)
+            hipLaunchKernelGGL(pfac_gf_count_kernel, dim3(n_groups), dim3(RP_GROUP / 4 * WAVE), 0, s.stream, in, ids,
+                               (unsigned long long)n_ids, off, (unsigned long long)n_docs, (unsigned long long)n_bytes, gf,
+                               s.ga_x.p, s.gsum.p, res);
+        else
+            hipLaunchKernelGGL(pfac_ga_count_kernel, dim3(n_groups), dim3(RP_GROUP / 4 * WAVE), 0, s.stream, ids,
+                               (unsigned long long)n_ids, off, (unsigned long long)n_docs, (unsigned long long)n_bytes, s.ga_x.p,
+                               s.gsum.p, res);
         hipLaunchKernelGGL(pfac_scan_groups_kernel, dim3(1), dim3(1024), 0, s.stream, s.gsum.p, n_groups);
         rc = pass_words(ctx, s, s.gsum.p + n_groups, 2);
         if (rc) return rc;
@@ -5899,24 +6185,50 @@ int pfac_documents_gather(pfac_ctx *ctx, int slot, const void *d_input, uint64_t
     if (!rc) rc = s.ga_out.bind(ctx, s.stream, d_out, total, align_up(total + total / 8, 4096), &out);
     if (rc) return rc;
     if (n_ids) {
-        hipLaunchKernelGGL(pfac_ga_offsets_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(4 * WAVE), 0, s.stream, ids,
-                           (unsigned long long)n_ids, off, (const unsigned long long *)s.ga_x.p,
-                           (const unsigned long long *)s.gsum.p, oo);
+        if (labels)
+            hipLaunchKernelGGL(pfac_gf_offsets_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(4 * WAVE), 0, s.stream, in, ids,
+                               (unsigned long long)n_ids, off, gf, (const unsigned long long *)s.ga_x.p,
+                               (const unsigned long long *)s.gsum.p, oo);
+        else
+            hipLaunchKernelGGL(pfac_ga_offsets_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(4 * WAVE), 0, s.stream, ids,
+                               (unsigned long long)n_ids, off, (const unsigned long long *)s.ga_x.p,
+                               (const unsigned long long *)s.gsum.p, oo);
         HIP_TRY(ctx, hipGetLastError());
     } else {
         HIP_TRY(ctx, hipMemsetAsync(oo, 0, 8, s.stream));    // no ids: the single offset 0
     }
     if (total) {
         const WriteGrid g = write_grid(total);
-        hipLaunchKernelGGL(pfac_ga_write_kernel, dim3(g.blocks), dim3(RP_WAVES * WAVE), 0, s.stream, in,
-                           (unsigned long long)n_bytes, ids, (unsigned long long)n_ids, off, (const unsigned long long *)oo,
-                           (const unsigned long long *)s.ga_x.p, (const unsigned long long *)s.gsum.p, (unsigned long long)total,
-                           g.wins, out);
+        if (labels)
+            hipLaunchKernelGGL(pfac_gf_write_kernel, dim3(g.blocks), dim3(RP_WAVES * WAVE), 0, s.stream, in,
+                               (unsigned long long)n_bytes, ids, (unsigned long long)n_ids, off, first, gf,
+                               (const unsigned long long *)oo, (const unsigned long long *)s.ga_x.p,
+                               (const unsigned long long *)s.gsum.p, (unsigned long long)total, g.wins, out);
+        else
+            hipLaunchKernelGGL(pfac_ga_write_kernel, dim3(g.blocks), dim3(RP_WAVES * WAVE), 0, s.stream, in,
+                               (unsigned long long)n_bytes, ids, (unsigned long long)n_ids, off, (const unsigned long long *)oo,
+                               (const unsigned long long *)s.ga_x.p, (const unsigned long long *)s.gsum.p, (unsigned long long)total,
+                               g.wins, out);
         HIP_TRY(ctx, hipGetLastError());
     }
     s.ga_out.commit(total, !d_out);
     s.ga_off.commit(n_ids + 1, !d_out_offsets);
     return PFAC_OK;
+}
+
+int pfac_documents_gather(pfac_ctx *ctx, int slot, const void *d_input, uint64_t n_bytes, const uint64_t *d_doc_offsets,
+                          uint64_t n_docs, const uint64_t *d_ids, uint64_t n_ids, void *d_out, uint64_t out_cap,
+                          uint64_t *d_out_offsets, uint64_t *out_bytes) {
+    return ga_run(ctx, slot, "pfac_documents_gather", d_input, n_bytes, d_doc_offsets, n_docs, d_ids, n_ids, nullptr, nullptr, d_out,
+                  out_cap, d_out_offsets, out_bytes);
+}
+
+int pfac_documents_gather_format(pfac_ctx *ctx, int slot, const void *d_input, uint64_t n_bytes, const uint64_t *d_doc_offsets,
+                                 uint64_t n_docs, const uint64_t *d_ids, uint64_t n_ids, const uint64_t *d_doc_first,
+                                 const pfac_line_format *fmt, void *d_out, uint64_t out_cap, uint64_t *d_out_offsets,
+                                 uint64_t *out_bytes) {
+    return ga_run(ctx, slot, "pfac_documents_gather_format", d_input, n_bytes, d_doc_offsets, n_docs, d_ids, n_ids, d_doc_first, fmt,
+                  d_out, out_cap, d_out_offsets, out_bytes);
 }
 
 int pfac_documents_gather_d2h(pfac_ctx *ctx, int slot, void *host, uint64_t first, uint64_t n) {

@@ -15,6 +15,8 @@ import numpy as np
 
 from ._ffi import (PFAC_COUNT_ACCUMULATE, PFAC_DOCS_INVERT, PFAC_E_OVERFLOW, PFAC_FOLD_ASCII, PFAC_FOLD_NONE, PFAC_SPANS_LINE, PFAC_WORD_LEFT, PFAC_WORD_RIGHT, CRecord, PfacError,
                    hip_lib)
+from ._ffi import (PFAC_LINE_CONTEXT_SEP, PFAC_LINE_MAX_GROUP_SEP, PFAC_LINE_NUMBER, PFAC_LINE_OFFSET, PFAC_LINE_SEP_FIRST,
+                   PFAC_LINE_TERMINATE, CLineFormat)
 from .table import RECORD_DTYPE, TEMPLATE_PLAIN, PfacTable, redaction_table, replacement_table, template_table, _state_lengths
 
 
@@ -616,6 +618,38 @@ class GpuMatcher:
         return self._to_host(slot, lambda p: self._L.pfac_documents_gather_offsets_d2h(self._ctx, slot, p),
                              (int(n_ids) + 1, np.uint64))
 
+    def gather_documents_formatted(self, n_docs: int, n_ids: int, n_bytes: int, number: bool = False, byte_offset: bool = False,
+                                   terminate=None, context_sep: bool = False, group_sep: bytes = b"", sep_first: bool = False,
+                                   number_base: int = 1, offset_base: int = 0, sep_match=b":", sep_context=b"-",
+                                   d_input=None, d_doc_offsets=None, d_ids=None, d_doc_first=None, d_out=None, out_cap: int = 0,
+                                   d_out_offsets=None, slot: int = 0) -> int:
+        """``gather_documents`` with grep's labels, made on the GPU (``pfac_documents_gather_format``): in front of
+        every document ``group_sep`` where its id does not follow the id before it (``sep_first``: also in front of the
+        first), with ``number`` the decimal of ``id + number_base`` and a label separator, with ``byte_offset`` the
+        decimal of its offset ``+ offset_base`` and a label separator; behind it, with ``terminate`` (one byte or its
+        value), that byte where the document is empty or does not end in it.  The label separator is ``sep_match``,
+        and with ``context_sep`` it is ``sep_context`` for a document without a kept record (``d_doc_first`` None =
+        the slot's last ``segment_records``).  The buffer keywords, the result and the fetches are those of
+        ``gather_documents``; the two share one slot-owned result."""
+        group_sep = bytes(group_sep)
+        if len(group_sep) > PFAC_LINE_MAX_GROUP_SEP:
+            raise ValueError(f"group_sep holds at most {PFAC_LINE_MAX_GROUP_SEP} bytes")
+        fmt = CLineFormat()
+        fmt.flags = ((PFAC_LINE_NUMBER if number else 0) | (PFAC_LINE_OFFSET if byte_offset else 0) |
+                     (PFAC_LINE_TERMINATE if terminate is not None else 0) | (PFAC_LINE_CONTEXT_SEP if context_sep else 0) |
+                     (PFAC_LINE_SEP_FIRST if sep_first else 0))
+        fmt.sep_match, fmt.sep_context = _delimiter_byte(sep_match), _delimiter_byte(sep_context)
+        fmt.terminator = _delimiter_byte(terminate) if terminate is not None else 0
+        fmt.group_sep_len = len(group_sep)
+        for i, b in enumerate(group_sep):
+            fmt.group_sep[i] = b
+        fmt.number_base, fmt.offset_base = int(number_base), int(offset_base)
+        n = C.c_uint64(0)
+        rc = self._L.pfac_documents_gather_format(self._ctx, slot, _ptr(d_input), int(n_bytes), _ptr(d_doc_offsets), int(n_docs),
+                                                  _ptr(d_ids), int(n_ids), _ptr(d_doc_first), C.byref(fmt), _ptr(d_out),
+                                                  int(out_cap), _ptr(d_out_offsets), C.byref(n))
+        return self._counted(rc, n, "out_bytes")
+
     def _scan_lines(self, data, delimiter, slot: int, whole_words=False, fetch_offsets: bool = True, spans: bool = False,
                     line_match: bool = False) -> Tuple[Optional[np.ndarray], int]:
         """``_scan_docs`` for one buffer whose documents end at ``delimiter``: upload, scan, offsets made on the device
@@ -690,6 +724,31 @@ class GpuMatcher:
         self.segment_records(n_docs, slot=slot)
         n = self.matching_documents(n_docs, invert=invert, slot=slot, before=before, after=after)
         out_bytes = self.gather_documents(n_docs, n, int(buf.size), slot=slot)
+        return (self.gathered_to_host(out_bytes, slot), self.gathered_offsets_to_host(n, slot),
+                self.matching_documents_to_host(n, slot))
+
+    def grep_text(self, data, delimiter=b"\n", number: bool = False, byte_offset: bool = False, invert: bool = False,
+                  before: int = 0, after: int = 0, whole_words=False, spans: bool = False, line_match: bool = False,
+                  number_base: int = 1, offset_base: int = 0, sep_first: bool = False, slot: int = 0) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """``grep_lines`` with grep's output formatting made on the device: byte for byte what ``grep -F -f patterns``
+        prints with ``-n`` (``number``), ``-b`` (``byte_offset``), ``-v``, ``-B`` / ``-A`` (a ``-`` behind the label
+        of a context line, ``--`` and the delimiter between groups of lines that are not adjacent) and a delimiter
+        behind an unterminated last line.  A chunked reader passes the lines and bytes in front of ``data`` as
+        ``number_base`` - 1 and ``offset_base``, and ``sep_first`` where the chunk before printed a line that the first
+        one here does not follow.  Returns (text uint8[], out_offsets uint64[n + 1], ids uint64[n]): printed line k,
+        its ``--`` line included, is ``text[out_offsets[k]:out_offsets[k + 1]]``."""
+        buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data.view(np.uint8).ravel()
+        if invert and (before or after):
+            raise ValueError("context lines (before / after) do not combine with invert")
+        context = bool(before or after)
+        delim = _delimiter_byte(delimiter)
+        _, n_docs = self._scan_lines(buf, delimiter, slot, whole_words, fetch_offsets=False, spans=spans, line_match=line_match)
+        self.segment_records(n_docs, slot=slot)
+        n = self.matching_documents(n_docs, invert=invert, slot=slot, before=before, after=after)
+        out_bytes = self.gather_documents_formatted(n_docs, n, int(buf.size), number=number, byte_offset=byte_offset,
+                                                    terminate=delim, context_sep=context,
+                                                    group_sep=b"--" + bytes([delim]) if context else b"", sep_first=sep_first,
+                                                    number_base=number_base, offset_base=offset_base, slot=slot)
         return (self.gathered_to_host(out_bytes, slot), self.gathered_offsets_to_host(n, slot),
                 self.matching_documents_to_host(n, slot))
 
