@@ -700,6 +700,92 @@ int pfac_documents_matching_groups(pfac_ctx *ctx, int slot, const uint64_t *d_ma
                                    uint64_t any_of, uint64_t none_of, uint32_t flags, uint64_t *d_ids_out, uint64_t out_cap,
                                    uint64_t *n_matching);
 
+/* Document scores: HOW MUCH of the pattern set a document holds (a blocklist's hit count, hits per 1000 bytes, a rule
+ * engine's weighted sum against a threshold, grep -c per document).  weights[s] is the weight of final state s, any
+ * int32, 0 included.  n_states must be num_final of the uploaded table, else PFAC_E_ARG and the earlier weights stay;
+ * PFAC_E_STATE before a table upload.  The weights live on the device with the table, like the state groups: the next
+ * pfac_table_upload / _upload_device clears them, a second call replaces them.  The call waits for no scan; a score
+ * pass already queued keeps the weights it was launched with (the old buffer is freed behind it). */
+typedef struct {
+    int64_t  score;            /* sum of the weights, two's-complement wrap */
+    uint64_t count;            /* records summed */
+} pfac_doc_score;              /* 16 bytes */
+int pfac_table_set_state_weights(pfac_ctx *ctx, const int32_t *weights, uint64_t n_states);
+/* A score per document, straight from the record heap of the slot's last finished scan: over the records (pos, state)
+ * with off[d] <= pos and pos + len[state] <= off[d + 1] -- the keep rule of pfac_records_segment --
+ *   count[d] = how many there are,   score[d] = the sum of weights[state], in int64 with two's-complement wrap.
+ * A record of weight 0 counts.  A document without such a record, an empty one included, gets {0, 0}.  After
+ * pfac_records_filter_words / _filter_spans only the kept records count; the records of a folded scan count as they
+ * are.  The heap is read through the tile index; no input byte is read.
+ *   d_records      the scan's record heap, NULL = the slot's; anything else that is not that heap gives PFAC_E_ARG
+ *   d_doc_offsets  device uint64[n_docs + 1] under the rules of pfac_records_segment (checked on the device, in the same
+ *                  pass); NULL = the slot's offsets, whichever call set them, with the same n_docs, else PFAC_E_STATE
+ *   d_scores_out   NULL = a slot-owned buffer grown to fit (fetched with pfac_document_scores_d2h; the lifetime rule of
+ *                  pfac_segment_d2h); else a device pointer, 16-B aligned: exactly n_docs x 16 bytes are written
+ *   *total         the sums of score[d] and count[d] over all documents
+ * Returns once *total and the offsets' flag are known (one 24-byte copy back); the scores are then complete on the
+ * slot's stream (pfac_slot_sync).  Judged in this order -- PFAC_E_STATE: no finished scan, a scan made with an earlier
+ * table, no final lengths or no state weights for the current table, no offsets for the slot; PFAC_E_OVERFLOW: the scan
+ * overflowed its heap; PFAC_E_ARG: misaligned buffers, n_docs >= 2^32, a d_records that is not this scan's heap, offsets
+ * that break the rules.  Every error leaves a caller's buffer as it was (the scores are made in the slot's buffer and
+ * copied behind the host's check of the offsets' flag); the slot-owned result is discarded even when the call fails.
+ * n_docs == 0 (then n_owned == 0) writes nothing and sets *total = {0, 0}.
+ * Kernels: the kernel of pfac_documents_group_masks, instantiated with the sum of the pair (weight, 1) in place of the
+ * OR, behind a memset of the scores: a segmented add over the 64 lanes, the open run carried across chunks and tiles,
+ * each document written once -- one 16-byte store where the document lies inside the wave's 64 tiles, two 64-bit atomic
+ * adds for the at most two that straddle their ends.  No atomic per record. */
+int pfac_documents_scores(pfac_ctx *ctx, int slot, const void *d_records, const uint64_t *d_doc_offsets, uint64_t n_docs,
+                          pfac_doc_score *d_scores_out, pfac_doc_score *total);
+/* The same two numbers over a record array that is already cut per document: document d owns
+ * d_sel[d_doc_first[d] .. d_doc_first[d + 1]), and every one of those records counts (positions are not read).
+ *   d_sel, d_doc_first  both NULL = the slot-owned picks and doc_first of the slot's last
+ *                  pfac_records_leftmost_longest_documents, under the rules of pfac_selection_count_states' d_sel
+ *                  (PFAC_E_STATE: no such selection since the slot's last scan, a selection made with an earlier table,
+ *                  or one that went to the caller's buffers).  Both non-NULL = any device arrays, 8-B aligned: the output
+ *                  of pfac_records_segment, or a selection written to the caller's buffers; d_doc_first has n_docs + 1
+ *                  entries and d_sel holds d_doc_first[n_docs] records (that one entry is read back first, to size
+ *                  the launch).  One NULL and one not gives PFAC_E_ARG.
+ * Checked on the device, in the same pass and before anything reaches a caller's buffer, else PFAC_E_ARG:
+ * d_doc_first[0] == 0, d_doc_first does not decrease, every state is below num_final.  PFAC_E_STATE (no table, no state
+ * weights) comes before PFAC_E_ARG (misaligned buffers, n_docs >= 2^32).  d_scores_out, *total, the slot-owned result,
+ * its fetch and its lifetime are those of pfac_documents_scores: the two are ONE pass.
+ * Kernels: pick-driven, one lane per record, a wave per 256 records; a record's document by a search in d_doc_first
+ * between the documents of its chunk's first and last record; the segmented add and the store / atomic rule of the
+ * heap kernel (a document is stored plainly where all its records lie in the wave's range). */
+int pfac_selection_document_scores(pfac_ctx *ctx, int slot, const pfac_record *d_sel, const uint64_t *d_doc_first,
+                                   uint64_t n_docs, pfac_doc_score *d_scores_out, pfac_doc_score *total);
+/* D2H of scores [first, first + n) of the slot-owned result of the last pfac_documents_scores /
+ * pfac_selection_document_scores.  Asynchronous on the slot's stream; pfac_slot_sync completes it.  first + n > n_docs
+ * gives PFAC_E_ARG; n == 0 does nothing. */
+int pfac_document_scores_d2h(pfac_ctx *ctx, int slot, pfac_doc_score *host, uint64_t first, uint64_t n);
+/* The documents whose score satisfies a rule.  Document d is reported iff
+ *   (min_count <= count[d] <= max_count && min_score <= score[d] <= max_score && density(d)) != invert
+ * (flags: 0 or PFAC_DOCS_INVERT), where density(d) is true when density_den == 0 and else
+ *   score[d] * density_den >= density_num * (off[d + 1] - off[d])
+ * compared exactly (two 128-bit products): "at least density_num / density_den per byte", e.g. 3 / 1000.
+ *   d_scores       NULL = the slot-owned scores of the slot's last score pass (PFAC_E_STATE if there are none or they
+ *                  went to the caller's buffer, PFAC_E_ARG if n_docs differs from that call's); else any device
+ *                  pfac_doc_score[n_docs], 16-B aligned
+ *   d_doc_offsets  read only when density_den != 0 (n_docs + 1 entries, 8-B aligned; they are not checked: a length
+ *                  is off[d + 1] - off[d] as it comes); NULL = the slot's offsets, PFAC_E_STATE if it has none,
+ *                  PFAC_E_ARG if n_docs differs from theirs
+ *   rule           NULL gives PFAC_E_ARG
+ * d_ids_out, out_cap, *n_matching, PFAC_E_OVERFLOW (exact count, nothing written), the alignment and n_docs < 2^32 are
+ * exactly those of pfac_documents_matching, and the call is ONE pass with it, _context and _groups: the same slot-owned
+ * id buffer, pfac_documents_matching_d2h, and pfac_documents_gather(d_ids = NULL) / _gather_format consume its ids
+ * unchanged.
+ * Kernels: the compaction of pfac_documents_matching, instantiated with the rule (one 16-byte load per document; with a
+ * density two 8-byte loads of the offsets more). */
+typedef struct {
+    int64_t  min_score, max_score;      /* inclusive; INT64_MIN / INT64_MAX = not judged */
+    uint64_t min_count, max_count;      /* inclusive; 0 / UINT64_MAX = not judged */
+    int64_t  density_num;               /* judged only when density_den != 0 */
+    uint64_t density_den;
+} pfac_score_rule;
+int pfac_documents_matching_scores(pfac_ctx *ctx, int slot, const pfac_doc_score *d_scores, const uint64_t *d_doc_offsets,
+                                   uint64_t n_docs, const pfac_score_rule *rule, uint32_t flags, uint64_t *d_ids_out,
+                                   uint64_t out_cap, uint64_t *n_matching);
+
 /* Whole-word filter: drops, IN PLACE, the records of the slot's last finished scan that split a word, so that every
  * consumer of the scan (the fetches, the text emitter, the checksum, the segment pass, both selections and both
  * replaces) sees whole-word matches only -- a selection then chooses among whole-word candidates, which no filter

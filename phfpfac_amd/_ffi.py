@@ -94,6 +94,21 @@ class CLineFormat(C.Structure):
 # struct pfac_state_span as a numpy dtype (16 bytes: what pfac_table_set_state_spans takes)
 SPAN_DTYPE = [("min_start", "<u4"), ("max_start", "<u4"), ("max_tail", "<u4"), ("reserved", "<u4")]
 
+# struct pfac_doc_score as a numpy dtype (16 bytes: what the score passes write)
+SCORE_DTYPE = [("score", "<i8"), ("count", "<u8")]
+
+
+class CDocScore(C.Structure):
+    """struct pfac_doc_score (the totals of pfac_documents_scores)."""
+    _fields_ = [("score", C.c_int64), ("count", C.c_uint64)]
+
+
+class CScoreRule(C.Structure):
+    """struct pfac_score_rule (pfac_documents_matching_scores)."""
+    _fields_ = [("min_score", C.c_int64), ("max_score", C.c_int64), ("min_count", C.c_uint64), ("max_count", C.c_uint64),
+                ("density_num", C.c_int64), ("density_den", C.c_uint64)]
+
+
 HOST_SYMBOLS = (
     "pfac_table_build_file", "pfac_table_build_file_escaped", "pfac_table_build_mem", "pfac_table_build_file_part",
     "pfac_table_build_mem_part", "pfac_merge_partitions", "pfac_table_free", "pfac_table_lookup",
@@ -124,6 +139,8 @@ HIP_SYMBOLS = (
     "pfac_table_set_state_spans", "pfac_records_filter_spans",
     "pfac_table_set_replacement_templates", "pfac_extract_leftmost_longest", "pfac_extract_d2h", "pfac_extract_offsets_d2h",
     "pfac_documents_gather_format",
+    "pfac_table_set_state_weights", "pfac_documents_scores", "pfac_selection_document_scores", "pfac_document_scores_d2h",
+    "pfac_documents_matching_scores",
 )
 
 _host = None
@@ -279,6 +296,11 @@ def hip_lib() -> C.CDLL:
         L.pfac_documents_group_masks.argtypes = [vp, i, vp, vp, u64, vp, C.POINTER(u64)]
         L.pfac_group_masks_d2h.argtypes = [vp, i, vp, u64, u64]
         L.pfac_documents_matching_groups.argtypes = [vp, i, vp, u64, u64, u64, u64, C.c_uint32, vp, u64, C.POINTER(u64)]
+        L.pfac_table_set_state_weights.argtypes = [vp, vp, u64]
+        L.pfac_documents_scores.argtypes = [vp, i, vp, vp, u64, vp, C.POINTER(CDocScore)]
+        L.pfac_selection_document_scores.argtypes = [vp, i, vp, vp, u64, vp, C.POINTER(CDocScore)]
+        L.pfac_document_scores_d2h.argtypes = [vp, i, vp, u64, u64]
+        L.pfac_documents_matching_scores.argtypes = [vp, i, vp, vp, u64, C.POINTER(CScoreRule), C.c_uint32, vp, u64, C.POINTER(u64)]
         L.pfac_table_set_state_spans.argtypes = [vp, vp, u64]
         L.pfac_records_filter_spans.argtypes = [vp, i, vp, vp, i, C.c_uint32, vp, u64, C.POINTER(u64)]
         _hip = L

@@ -2494,37 +2494,144 @@ __global__ void pfac_seg_write_kernel(const void *rec, const unsigned long long 
 }
 
 // ---------------------------------------------------------------------------
-// Pattern groups (pfac_documents_group_masks): mask[d] = the OR of gmask[state] over the records the segment pass would
-// keep for document d -- the walk of pfac_seg_count_kernel (record, length, document, keep rule; the offsets' rules in
-// the same pass) with 8 bytes per DOCUMENT behind it instead of a count per tile, and no global atomic per record.
+// Per-document reductions straight from the heap: pattern groups (pfac_documents_group_masks, mask[d] = the OR of
+// gmask[state]) and scores (pfac_documents_scores, {score, count}[d] = the sum of {weight[state], 1}), both over the
+// records the segment pass would keep for document d -- the walk of pfac_seg_count_kernel (record, length, document, keep
+// rule; the offsets' rules in the same pass) with one value per DOCUMENT behind it instead of a count per tile, and no
+// global atomic per record.  ONE kernel, pfac_doc_reduce_kernel, templated on the reduction (GroupOr, ScoreAdd below):
+// the value types (a lane's inside a chunk, a run's across chunks), what a kept record brings, which lanes contribute,
+// the combines, the store and the atomic.
 // One wave per group of 64 tiles.  A tile's records come in position order, so the documents of the contributing lanes
-// (kept, mask != 0) ascend: every lane takes the document of the nearest contributing lane at or below it (the first
-// one's in front of it) with mask 0 where it contributes nothing, and a segmented inclusive OR scan keyed on the
-// document (six shuffle steps) leaves each run's OR in its last lane.  The chunk's last run stays open in two
+// ascend: every lane takes the document of the nearest contributing lane at or below it (the first one's in front of
+// it) with the neutral value where it contributes nothing, and a segmented inclusive scan keyed on the document (six
+// shuffle steps, doc_reduce_chunk) leaves each run's value in its last lane.  The chunk's last run stays open in two
 // wave-uniform registers (cd, cm) across chunks and tiles; a run is flushed ONCE, when the document changes or the
 // wave's tiles end.
-// Who writes mask[d]: the wave's tiles cover the bytes [B0, B1) and every record of them starts there.  A document with
-// B0 <= off[d] and off[d + 1] <= B1 gets all its records from this wave, which flushes it once: a plain 8-byte store
-// over the zero that the host's memset left.  The others -- at most the one that runs in from below B0 and the one that
-// runs out past B1 -- may be flushed by several waves and are OR-ed with an agent-scope atomic whose result nobody
-// reads; no wave ever stores plainly to them, so store and atomic never meet on one word.  The interior documents are
-// [a, e - 1) with a = the first d with off[d] >= B0 and e = the first index with off[e] > B1 (the last wave has no
+// Exactly once, which a sum needs and an OR did not: the open run (cd, cm) enters a chunk only through the lanes whose
+// key equals cd.  Keys ascend and cd is at most the first key, so those lanes are a prefix of the chunk, and cm goes
+// into every one of them -- they hold INCLUSIVE prefixes of the run, of which only the last lane's is ever used: it is
+// flushed where the next lane's key differs, or it leaves through lane 63 as the new (cd, cm).  Where no key equals cd
+// the run is closed and lane 0 flushes it as it stands.  Either way cm is consumed by one flush or one carry, never both.
+// Who contributes: GroupOr the lanes whose kept record has a mask (a mask of 0 changes nothing, the document keeps the
+// memset's 0); ScoreAdd every lane that KEEPS its record -- a weight of 0 still counts, and weights that cancel still
+// leave a count to write.
+// Who writes out[d]: the wave's tiles cover the bytes [B0, B1) and every record of them starts there.  A document with
+// B0 <= off[d] and off[d + 1] <= B1 gets all its records from this wave, which flushes it once: a plain store of the
+// whole value (8 or 16 bytes) over the zero that the host's memset left.  The others -- at most the one that runs in from
+// below B0 and the one that runs out past B1 -- may be flushed by several waves and are combined with agent-scope atomics
+// whose result nobody reads (one OR; two 64-bit adds, of which nobody needs the pair to be seen together before the
+// kernel ends); no wave ever stores plainly to them, so store and atomic never meet on one word.  The interior documents
+// are [a, e - 1) with a = the first d with off[d] >= B0 and e = the first index with off[e] > B1 (the last wave has no
 // B1): two binary searches per wave.  Documents without a contributing record are never written -- the memset is their 0.
 // With offsets that break the rules the documents stay clamped to [0, n_docs) (tile_docs), the result is garbage in
 // bounds, and the host discards it behind the flag.
-template <int BYTES>
+struct GroupOr {
+    using Tab = unsigned long long;                             // per final state: its group set
+    using Lane = unsigned long long;                            // what a lane carries through a chunk's scan, ...
+    using Val = unsigned long long;                             // ... and what a run is worth once it meets the open run
+    using Out = unsigned long long;
+    static constexpr int RES_WORDS = 1;                         // res[0]: the OR of all masks; res[RES_WORDS]: bad offsets
+    static __device__ __forceinline__ Lane lane_none() { return 0ull; }
+    static __device__ __forceinline__ Lane of(Tab t) { return t; }
+    static __device__ __forceinline__ bool contributes(bool, Lane v) { return v != 0ull; }
+    static __device__ __forceinline__ void lane_add(Lane &a, Lane b) { a |= b; }
+    static __device__ __forceinline__ Lane lane_shfl_up(Lane v, int s) { return __shfl_up(v, s, WAVE); }
+    static __device__ __forceinline__ Val widen(Lane v) { return v; }
+    static __device__ __forceinline__ Val none() { return 0ull; }
+    static __device__ __forceinline__ bool empty(Val v) { return v == 0ull; }
+    static __device__ __forceinline__ void add(Val &a, Val b) { a |= b; }
+    static __device__ __forceinline__ Val shfl(Val v, int l) { return __shfl(v, l, WAVE); }
+    static __device__ __forceinline__ void store(Out *out, unsigned d, Val v) { out[d] = v; }
+    static __device__ __forceinline__ void atomic(Out *out, unsigned d, Val v) {
+        (void)__hip_atomic_fetch_or(out + d, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    static __device__ __forceinline__ void total(unsigned long long *res, Val any, int lane) {
+#pragma unroll
+        for (int s = 1; s < WAVE; s <<= 1) any |= __shfl_xor(any, s, WAVE);
+        if (lane == 0 && any) (void)__hip_atomic_fetch_or(res, any, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+};
+struct ScoreAdd {
+    using Tab = int;                                            // per final state: its weight
+    // Inside a chunk a run holds at most 64 records: its count fits 8 bits and its score, below 2^37 in size, the 56
+    // above them, so a lane carries score * 256 + count in ONE word and the scan shuffles what the mask pass shuffles.
+    using Lane = unsigned long long;
+    struct Val { unsigned long long s, c; };                    // the score (two's complement: it wraps) and the count
+    using Out = pfac_doc_score;
+    static constexpr int RES_WORDS = 2;                         // res[0], res[1]: the totals; res[RES_WORDS]: the pass's flag
+    static __device__ __forceinline__ Lane lane_none() { return 0ull; }
+    static __device__ __forceinline__ Lane of(Tab t) { return ((unsigned long long)(long long)t << 8) + 1ull; }
+    static __device__ __forceinline__ bool contributes(bool keep, Lane) { return keep; }
+    static __device__ __forceinline__ void lane_add(Lane &a, Lane b) { a += b; }
+    static __device__ __forceinline__ Lane lane_shfl_up(Lane v, int s) { return __shfl_up(v, s, WAVE); }
+    static __device__ __forceinline__ Val widen(Lane v) {
+        const unsigned long long c = v & 255ull;
+        return Val{(unsigned long long)((long long)(v - c) >> 8), c};
+    }
+    static __device__ __forceinline__ Val none() { return Val{0ull, 0ull}; }
+    static __device__ __forceinline__ bool empty(Val) { return false; }      // (a run holds a kept record: count >= 1)
+    static __device__ __forceinline__ void add(Val &a, Val b) { a.s += b.s; a.c += b.c; }
+    static __device__ __forceinline__ Val shfl(Val v, int l) { return Val{__shfl(v.s, l, WAVE), __shfl(v.c, l, WAVE)}; }
+    static __device__ __forceinline__ void store(Out *out, unsigned d, Val v) {       // one dwordx4
+        reinterpret_cast<ulonglong2 *>(out)[d] = make_ulonglong2(v.s, v.c);
+    }
+    static __device__ __forceinline__ void atomic(Out *out, unsigned d, Val v) {
+        unsigned long long *w = reinterpret_cast<unsigned long long *>(out + d);
+        (void)__hip_atomic_fetch_add(w, v.s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        (void)__hip_atomic_fetch_add(w + 1, v.c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    static __device__ __forceinline__ void total(unsigned long long *res, Val any, int lane) {
+        const unsigned long long s = wave_sum64(any.s), c = wave_sum64(any.c);
+        if (lane == 0 && c) {
+            (void)__hip_atomic_fetch_add(res, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            (void)__hip_atomic_fetch_add(res + 1, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+};
+
+// One chunk of 64 lanes of a per-document reduction: lane values lm (R::lane_none() where the lane does not
+// contribute), the contributing lanes b (not empty) and their documents d, ascending; (cvalid, cd, cm) is the open run,
+// flush(d, value) closes one.  Every lane of the wave takes part.
+template <class R, class Flush>
+__device__ __forceinline__ void doc_reduce_chunk(int lane, unsigned long long b, unsigned long long d, typename R::Lane lm, bool &cvalid,
+                                                 unsigned &cd, typename R::Val &cm, Flush flush) {
+    const unsigned long long below = b & ((2ull << lane) - 1ull);        // contributing lanes up to this one
+    unsigned dk = (unsigned)__shfl((unsigned)d, below ? 63 - __clzll(below) : __ffsll((long long)b) - 1, WAVE);
+#pragma unroll
+    for (int s = 1; s < WAVE; s <<= 1) {
+        const unsigned du = (unsigned)__shfl_up(dk, s, WAVE);
+        const typename R::Lane mu = R::lane_shfl_up(lm, s);
+        if (lane >= s && du == dk) R::lane_add(lm, mu);
+    }
+    typename R::Val m = R::widen(lm);
+    if (cvalid) {
+        if (__ballot(dk == cd) != 0ull) {
+            if (dk == cd) R::add(m, cm);                        // the open run goes on (it starts at lane 0)
+        } else if (lane == 0) {
+            flush(cd, cm);
+        }
+    }
+    const unsigned dn = (unsigned)__shfl_down(dk, 1, WAVE);
+    if (lane != WAVE - 1 && dn != dk) flush(dk, m);
+    cd = (unsigned)__shfl(dk, WAVE - 1, WAVE);
+    cm = R::shfl(m, WAVE - 1);
+    cvalid = true;
+}
+
+template <int BYTES, class R>
 __global__ void __launch_bounds__(256)
-pfac_group_masks_kernel(const void *rec, const unsigned long long *tix, unsigned long long n_tiles, unsigned long long cap,
-                        const unsigned long long *off, unsigned long long n_docs, unsigned long long n_owned,
-                        const short *flen, const unsigned long long *gmask, unsigned num_final, unsigned long long *out,
-                        unsigned n_groups, unsigned long long *res) {        // res[0]: the OR of all masks, res[1]: bad offsets
-    offsets_rule(GRID_THREAD, GRID_THREADS, off, n_docs, n_owned, res + 1);
+pfac_doc_reduce_kernel(const void *rec, const unsigned long long *tix, unsigned long long n_tiles, unsigned long long cap,
+                       const unsigned long long *off, unsigned long long n_docs, unsigned long long n_owned,
+                       const short *flen, const typename R::Tab *tab, unsigned num_final, typename R::Out *out,
+                       unsigned n_groups, unsigned long long *res) {         // res: R::RES_WORDS totals, then bad offsets
+    using Val = typename R::Val;
+    offsets_rule(GRID_THREAD, GRID_THREADS, off, n_docs, n_owned, res + R::RES_WORDS);
     const int lane = threadIdx.x & (WAVE - 1);
     const unsigned g = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (g >= n_groups) return;
     const bool fsmall = num_final <= (unsigned)WAVE;
     const int freg = fsmall && (unsigned)lane < num_final ? (int)flen[lane] : 0;
-    const unsigned long long greg = fsmall && (unsigned)lane < num_final ? gmask[lane] : 0ull;
+    const typename R::Tab greg = fsmall && (unsigned)lane < num_final ? tab[lane] : typename R::Tab(0);
     const unsigned long long t = (unsigned long long)g * XGROUP + lane;
     const unsigned long long e = t < n_tiles ? tix[t] : 0ull;
     const unsigned c = (unsigned)(e >> TIX_CNT_SHIFT);
@@ -2537,14 +2644,14 @@ pfac_group_masks_kernel(const void *rec, const unsigned long long *tix, unsigned
     const unsigned long long ia = doc_lower_bound(off, n_docs + 1, (unsigned long long)g * XGROUP * WTILE);
     const unsigned long long ib = last ? n_docs + 1 : doc_lower_bound(off, n_docs + 1, ((unsigned long long)g + 1) * XGROUP * WTILE + 1ull);
     const unsigned long long ie = ib ? ib - 1 : 0ull;
-    auto flush = [&](unsigned d, unsigned long long m) {
-        if (m == 0ull) return;
-        if (d >= ia && d < ie) out[d] = m;
-        else (void)__hip_atomic_fetch_or(out + d, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    auto flush = [&](unsigned d, Val m) {
+        if (R::empty(m)) return;
+        if (d >= ia && d < ie) R::store(out, d, m);
+        else R::atomic(out, d, m);
     };
     bool cvalid = false;                                        // the open run (wave-uniform)
     unsigned cd = 0;
-    unsigned long long cm = 0, any = 0;
+    Val cm = R::none(), any = R::none();
     for (int j = 0; j < XGROUP; j++) {
         const unsigned tc = __shfl(c, j, WAVE);
         if (tc == 0) continue;
@@ -2556,40 +2663,73 @@ pfac_group_masks_kernel(const void *rec, const unsigned long long *tix, unsigned
             unsigned pos = 0, st = 0;
             if (have) heap_record<BYTES>(rec, tlo + i, (unsigned long long)g * XGROUP + j, pos, st);
             const int len = final_len(flen, freg, fsmall, have, st);
-            const unsigned long long gm = fsmall ? __shfl(greg, (int)st, WAVE) : (have ? gmask[st] : 0ull);
+            const typename R::Tab gm = fsmall ? __shfl(greg, (int)st, WAVE) : (have ? tab[st] : typename R::Tab(0));
             unsigned long long d, base, end;
             doc_lookup(w, off, have, pos, d, base, end);
             const bool keep = have && len > 0 && (unsigned long long)pos + (unsigned)len <= end;
-            unsigned long long m = keep ? gm : 0ull;
-            const unsigned long long b = __ballot(m != 0ull);
+            const typename R::Lane m = keep ? R::of(gm) : R::lane_none();
+            const unsigned long long b = __ballot(R::contributes(keep, m));
             if (b == 0ull) continue;
-            any |= m;
-            const unsigned long long below = b & ((2ull << lane) - 1ull);        // contributing lanes up to this one
-            unsigned dk = (unsigned)__shfl((unsigned)d, below ? 63 - __clzll(below) : __ffsll((long long)b) - 1, WAVE);
-#pragma unroll
-            for (int s = 1; s < WAVE; s <<= 1) {
-                const unsigned du = (unsigned)__shfl_up(dk, s, WAVE);
-                const unsigned long long mu = __shfl_up(m, s, WAVE);
-                if (lane >= s && du == dk) m |= mu;
-            }
-            if (cvalid) {
-                if (__ballot(dk == cd) != 0ull) {
-                    if (dk == cd) m |= cm;                      // the open run goes on (it starts at lane 0)
-                } else if (lane == 0) {
-                    flush(cd, cm);
-                }
-            }
-            const unsigned dn = (unsigned)__shfl_down(dk, 1, WAVE);
-            if (lane != WAVE - 1 && dn != dk) flush(dk, m);
-            cd = (unsigned)__shfl(dk, WAVE - 1, WAVE);
-            cm = __shfl(m, WAVE - 1, WAVE);
-            cvalid = true;
+            R::add(any, R::widen(m));
+            doc_reduce_chunk<R>(lane, b, d, m, cvalid, cd, cm, flush);
         }
     }
     if (cvalid && lane == 0) flush(cd, cm);
-#pragma unroll
-    for (int s = 1; s < WAVE; s <<= 1) any |= __shfl_xor(any, s, WAVE);
-    if (lane == 0 && any) (void)__hip_atomic_fetch_or(res, any, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    R::total(res, any, lane);
+}
+
+// Scores of a record array that is already cut per document (pfac_selection_document_scores): document d owns
+// sel[first[d] .. first[d + 1]), n = first[n_docs] records in all.  Pick-driven: a wave owns SS_RANGE consecutive picks,
+// a lane takes one record; its document is the last d with first[d] <= i, searched between the documents of the
+// chunk's first and last pick (two wave-uniform searches; none per lane where those two agree).  Every pick
+// contributes; the same segmented add (doc_reduce_chunk<ScoreAdd>) and the same rule for the store: the documents whose
+// picks lie inside the wave's range, [ia, ie) by the two searches of the heap kernel, are stored plainly, the two that
+// may straddle its ends are added atomically.  Checked in the same pass, into res[2]: first[0] == 0, no decrease,
+// first[n_docs] == n, every state below num_final (a state past the table reads no weight).  Behind a failed check the
+// result is garbage in bounds -- documents stay in [0, n_docs) -- and the host discards it.
+constexpr unsigned SS_RANGE = 4 * WAVE;
+__global__ void __launch_bounds__(256)
+pfac_sel_scores_kernel(const pfac_record *sel, unsigned long long n, const unsigned long long *first, unsigned long long n_docs,
+                       const int *wtab, unsigned num_final, pfac_doc_score *out, unsigned long long *res) {
+    using R = ScoreAdd;
+    bool bad = false;
+    for (unsigned long long d = GRID_THREAD; d < n_docs; d += GRID_THREADS) bad = bad || first[d] > first[d + 1];
+    if (GRID_THREAD == 0) bad = bad || first[0] != 0ull || first[n_docs] != n;
+    const int lane = threadIdx.x & (WAVE - 1);
+    const unsigned long long p0 = ((unsigned long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * SS_RANGE;
+    if (p0 < n && n_docs) {                                     // (wave-uniform)
+        const unsigned long long p1 = min(p0 + SS_RANGE, n);
+        const bool fsmall = num_final <= (unsigned)WAVE;
+        const int wreg = fsmall && (unsigned)lane < num_final ? wtab[lane] : 0;
+        const unsigned long long ia = doc_lower_bound(first, n_docs + 1, p0);
+        const unsigned long long ib = p1 >= n ? n_docs + 1 : doc_lower_bound(first, n_docs + 1, p1 + 1ull);
+        const unsigned long long ie = ib ? ib - 1 : 0ull;
+        auto flush = [&](unsigned d, R::Val m) {
+            if (d >= ia && d < ie) R::store(out, d, m);
+            else R::atomic(out, d, m);
+        };
+        bool cvalid = false;
+        unsigned cd = 0;
+        R::Val cm = R::none(), any = R::none();
+        unsigned long long dlo = 0;
+        for (unsigned long long c0 = p0; c0 < p1; c0 += WAVE) {
+            const unsigned long long i = c0 + (unsigned)lane;
+            const bool have = i < p1;
+            dlo = doc_of(first, dlo, n_docs - 1, c0);
+            const unsigned long long dhi = doc_of(first, dlo, n_docs - 1, min(c0 + (WAVE - 1), p1 - 1));
+            const unsigned st = have ? sel[i].state : 0u;
+            const bool known = st < num_final;
+            bad = bad || !known;
+            const int wt = fsmall ? __shfl(wreg, known ? (int)st : 0, WAVE) : (have && known ? wtab[st] : 0);
+            const unsigned long long d = have ? doc_of(first, dlo, dhi, i) : dlo;
+            const R::Lane m = have ? R::of(known ? wt : 0) : R::lane_none();
+            R::add(any, R::widen(m));
+            doc_reduce_chunk<R>(lane, __ballot(have), d, m, cvalid, cd, cm, flush);
+        }
+        if (cvalid && lane == 0) flush(cd, cm);
+        R::total(res, any, lane);
+    }
+    if (bad) res[R::RES_WORDS] = 1ull;
 }
 
 // ---------------------------------------------------------------------------
@@ -3858,13 +3998,18 @@ pfac_split_write_kernel(const unsigned char *in, unsigned long long n, unsigned 
 // both ends clamped -- still two loads per document.  `before` and `after` arrive clamped to n_docs (d + before cannot wrap).
 // The groups form (pfac_documents_matching_groups) is the third flag: the array holds a group mask per document (one
 // load per document) and the three words are the predicate's sets, all_of / any_of / none_of.
+// The scores forms (pfac_documents_matching_scores) are the fourth and fifth: the array holds a pfac_doc_score per
+// document (one 16-byte load) judged against the windows of a pfac_score_rule; DM_DENSITY also loads the document's two
+// offsets and compares score * den with num * length as two 128-bit products -- |score|, |num| <= 2^63 and den,
+// length < 2^64, so each product lies inside (-2^127, 2^127) and the compare is exact.
 constexpr int DM_BLOCKS = 64;
-enum : int { DM_PLAIN = 0, DM_CONTEXT = 1, DM_GROUPS = 2 };
+enum : int { DM_PLAIN = 0, DM_CONTEXT = 1, DM_GROUPS = 2, DM_SCORES = 3, DM_DENSITY = 4 };
 template <bool WRITE, int PRED>
 __device__ __forceinline__ void docs_matching_body(const unsigned long long *doc_first, unsigned long long n_docs, unsigned invert,
                                                    unsigned long long before, unsigned long long after, unsigned long long none_of,
                                                    unsigned long long *gsum, unsigned n_groups, unsigned long long total,
-                                                   unsigned long long *ids) {
+                                                   unsigned long long *ids, const pfac_score_rule *rule = nullptr,
+                                                   const unsigned long long *off = nullptr) {
     const int lane = threadIdx.x & (WAVE - 1);
     const unsigned g = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (g >= n_groups) return;
@@ -3876,7 +4021,16 @@ __device__ __forceinline__ void docs_matching_body(const unsigned long long *doc
         const unsigned long long d = d0 + (unsigned long long)b * WAVE + lane;
         const bool have = d < n_docs;
         bool flag;
-        if (PRED == DM_GROUPS) {                                // before = all_of, after = any_of
+        if (PRED == DM_SCORES || PRED == DM_DENSITY) {          // doc_first is the scores
+            const ulonglong2 v = have ? reinterpret_cast<const ulonglong2 *>(doc_first)[d] : make_ulonglong2(0ull, 0ull);
+            const long long sc = (long long)v.x;
+            bool ok = v.y >= rule->min_count && v.y <= rule->max_count && sc >= rule->min_score && sc <= rule->max_score;
+            if (PRED == DM_DENSITY) {
+                const unsigned long long lo = have ? off[d] : 0ull, hi = have ? off[d + 1] : 0ull;
+                ok = ok && (__int128)sc * (__int128)rule->density_den >= (__int128)rule->density_num * (__int128)(hi - lo);
+            }
+            flag = have && (ok != (invert != 0u));
+        } else if (PRED == DM_GROUPS) {                                // before = all_of, after = any_of
             const unsigned long long m = have ? doc_first[d] : 0ull;
             const bool ok = (m & before) == before && (after == 0ull || (m & after) != 0ull) && (m & none_of) == 0ull;
             flag = have && (ok != (invert != 0u));
@@ -3916,6 +4070,14 @@ pfac_docs_groups_kernel(const unsigned long long *masks, unsigned long long n_do
                         unsigned long long any_of, unsigned long long none_of, unsigned long long *gsum, unsigned n_groups,
                         unsigned long long total, unsigned long long *ids) {
     docs_matching_body<WRITE, DM_GROUPS>(masks, n_docs, invert, all_of, any_of, none_of, gsum, n_groups, total, ids);
+}
+template <bool WRITE, bool DENSITY>
+__global__ void __launch_bounds__(256)
+pfac_docs_scores_kernel(const pfac_doc_score *scores, unsigned long long n_docs, unsigned invert, pfac_score_rule rule,
+                        const unsigned long long *off, unsigned long long *gsum, unsigned n_groups, unsigned long long total,
+                        unsigned long long *ids) {
+    docs_matching_body<WRITE, DENSITY ? DM_DENSITY : DM_SCORES>(reinterpret_cast<const unsigned long long *>(scores), n_docs, invert,
+                                                                0ull, 0ull, 0ull, gsum, n_groups, total, ids, &rule, off);
 }
 
 // ---------------------------------------------------------------------------
@@ -4426,6 +4588,8 @@ struct Slot {
     PassOut<unsigned long long> dm_out;   // the ids
     // pfac_documents_group_masks
     PassOut<unsigned long long> gm_out;   // the masks (n_docs of them); scratch of a call that writes to the caller's buffer
+    // pfac_documents_scores / pfac_selection_document_scores
+    PassOut<pfac_doc_score> sc_out;       // the scores (n_docs of them); scratch of a call that writes to the caller's buffer
     // pfac_documents_gather
     DevBuf<unsigned long long> ga_x;      // X per block of 64 ids
     PassOut<unsigned char> ga_out;        // the bytes, ...
@@ -4491,13 +4655,14 @@ struct pfac_ctx {
     TablePlan plan;
     bool have_table = false;
     uint64_t table_gen = 0;               // installs begun so far: a scan's final states index the lengths of ITS table only
-    // ... what the caller attaches to it (an upload drops all seven), ...
+    // ... what the caller attaches to it (an upload drops all eight), ...
     DevBuf<short> flen;                   // pattern length of every final state (pfac_table_set_final_lengths)
     DevBuf<unsigned> rep_off;             // replacement of every final state (pfac_table_set_replacements): offsets[num_final + 1]
     DevBuf<unsigned char> rep;            // ... and the bytes, zero-padded to its capacity (a multiple of 16)
     DevBuf<unsigned> rep_split;           // where a state's replacement quotes the match (pfac_table_set_replacement_templates);
                                           // null while every state is plain: the replaces then run their plain kernels
     DevBuf<unsigned long long> gmask;     // group set of every final state (pfac_table_set_state_groups)
+    DevBuf<int> sweight;                  // weight of every final state (pfac_table_set_state_weights)
     DevBuf<uint4> spans;                  // span of every final state (pfac_table_set_state_spans): pfac_state_span as one dwordx4
     unsigned fold = PFAC_FOLD_NONE;       // case fold of the scans to come (pfac_table_set_case_fold)
     // ... and what adapts to the match density seen by the last scan (pfac_scan_finish)
@@ -5035,6 +5200,7 @@ int install_table(pfac_ctx *ctx, const int *d_blob, const int32_t *hdr, size_t n
     ctx->flen.reset(); ctx->fold = PFAC_FOLD_NONE;          // the lengths belong to the old table, and so does the case fold
     ctx->rep_off.reset(); ctx->rep.reset(); ctx->rep_split.reset();       // ... and so do the replacements and their splits
     ctx->gmask.reset();                                     // ... and the state groups
+    ctx->sweight.reset();                                   // ... and the state weights
     ctx->spans.reset();                                     // ... and the state spans
     ctx->have_table = false; ctx->table_gen++;
     TablePlan P;
@@ -5931,6 +6097,80 @@ int pfac_table_set_state_groups(pfac_ctx *ctx, const uint64_t *masks, uint64_t n
     return PFAC_OK;
 }
 
+int pfac_table_set_state_weights(pfac_ctx *ctx, const int32_t *weights, uint64_t n_states) {
+    if (!ctx) return fail(nullptr, PFAC_E_ARG, "null context");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (!ctx->have_table) return fail(ctx, PFAC_E_STATE, "pfac_table_set_state_weights before a table upload");
+    if (n_states != (uint64_t)ctx->plan.base.num_final || (!weights && n_states))
+        return fail(ctx, PFAC_E_ARG, "pfac_table_set_state_weights: need num_final weights (num_final " + std::to_string(ctx->plan.base.num_final) + ")");
+    USE_DEVICE(ctx);
+    // as the state groups: a buffer of its own for every call, and freeing the old one waits for the device
+    ctx->sweight.reset();
+    const uint64_t n = std::max<uint64_t>(n_states, 1);
+    int rc = ctx->sweight.ensure(ctx, nullptr, n, n);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemset(ctx->sweight.p, 0, n * 4));
+    if (n_states) HIP_TRY(ctx, hipMemcpy(ctx->sweight.p, weights, n_states * 4, hipMemcpyHostToDevice));
+    return PFAC_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// The per-document reductions over the heap (pfac_documents_group_masks: R = GroupOr, `tab` the state groups;
+// pfac_documents_scores: R = ScoreAdd, `tab` the state weights; `what` names the table for the error): the checks in
+// the header's order, the memset, pfac_doc_reduce_kernel into the slot's buffer `o`, the copy back of the totals and
+// the offsets' flag (h_ctl from H_PASS on), and behind the host's check of the flag the copy to the caller's buffer.
+template <class R>
+int doc_reduce_run(pfac_ctx *ctx, Slot &s, const std::string &fn, const typename R::Tab *tab, const char *what,
+                   PassOut<typename R::Out> &o, const void *d_records, const uint64_t *d_doc_offsets, uint64_t n_docs,
+                   typename R::Out *d_out) {
+    constexpr size_t SZ = sizeof(typename R::Out);
+    o.invalidate();
+    int rc = last_scan_usable(ctx, s, fn, SCAN_FINISHED | SCAN_LENGTHS | SCAN_TABLE);
+    if (rc) return rc;
+    if (!tab) return fail(ctx, PFAC_E_STATE, fn + ": no state " + what + " for the uploaded table (pfac_table_set_state_" + what + ")");
+    if (!d_doc_offsets && (!s.doc.done || n_docs + 1 != s.doc.n))
+        return fail(ctx, PFAC_E_STATE, fn + ": the slot has no document offsets for this n_docs (pfac_slot_doc_offsets, pfac_slot_doc_offsets_split)");
+    rc = last_scan_usable(ctx, s, fn, SCAN_FITS);
+    if (rc) return rc;
+    const unsigned long long *off;
+    rc = resolve_docs(ctx, s, fn, d_doc_offsets, n_docs, (uintptr_t)d_out, &off);
+    if (rc) return rc;
+    if ((uintptr_t)d_out & (SZ - 1)) return fail(ctx, PFAC_E_ARG, fn + ": the output buffer must be aligned to its elements");
+    const void *src = d_records ? d_records : (const void *)s.records.p;
+    if (s.last_tiles && src != s.last_records) return fail(ctx, PFAC_E_ARG, fn + ": d_records is not the record heap of the slot's last scan");
+    USE_DEVICE(ctx);
+    const uint64_t n_tiles = n_docs ? s.last_tiles : 0;     // (no documents: the scan owns no bytes, only the offsets are judged)
+    const unsigned n_groups = (unsigned)((n_tiles + XGROUP - 1) / XGROUP);
+    rc = ensure_gsum(ctx, s, R::RES_WORDS);                 // the totals, the offsets' error flag
+    if (rc) return rc;
+    // The result is made in the slot's buffer and reaches a caller's only behind the host's check of the offsets' flag:
+    // a refused call leaves the caller's buffer as it was.
+    typename R::Out *out;
+    rc = o.bind(ctx, s.stream, (typename R::Out *)nullptr, std::max<uint64_t>(n_docs, 1), docs_cap(n_docs), &out);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemsetAsync(s.gsum.p, 0, (R::RES_WORDS + 1) * 8, s.stream));
+    if (n_docs) HIP_TRY(ctx, hipMemsetAsync(out, 0, n_docs * SZ, s.stream));      // the 0 of every document without a contributing record
+    const uint64_t gblocks = (n_groups + 3) / 4, vblocks = (n_docs + 255) / 256;
+    const unsigned blocks = (unsigned)std::max<uint64_t>(1, std::max<uint64_t>(gblocks, std::min<uint64_t>(vblocks, 4096)));
+    auto mk = by_width(s.last_rec_bytes, [](auto w) { return pfac_doc_reduce_kernel<w(), R>; });
+    hipLaunchKernelGGL(mk, dim3(blocks), dim3(256), 0, s.stream, src, s.tile_index.p, (unsigned long long)n_tiles,
+                       (unsigned long long)s.last_cap, off, (unsigned long long)n_docs, (unsigned long long)s.last_owned,
+                       ctx->flen.p, tab, (unsigned)ctx->plan.base.num_final, out, n_groups, s.gsum.p);
+    rc = pass_words(ctx, s, s.gsum.p, R::RES_WORDS + 1);
+    if (rc) return rc;
+    if (host_u64(s, H_PASS + 2 * R::RES_WORDS)) return bad_doc_offsets(ctx, s, fn);
+    if (d_out && n_docs) HIP_TRY(ctx, hipMemcpyAsync(d_out, out, n_docs * SZ, hipMemcpyDeviceToDevice, s.stream));
+    o.commit(n_docs, !d_out);
+    return PFAC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
 int pfac_documents_group_masks(pfac_ctx *ctx, int slot, const void *d_records, const uint64_t *d_doc_offsets, uint64_t n_docs,
                                uint64_t *d_masks_out, uint64_t *any_mask) {
     int rc = check_slot(ctx, slot);
@@ -5938,46 +6178,90 @@ int pfac_documents_group_masks(pfac_ctx *ctx, int slot, const void *d_records, c
     if (!any_mask) return fail(ctx, PFAC_E_ARG, "null argument");
     *any_mask = 0;
     Slot &s = ctx->slots[slot];
-    s.gm_out.invalidate();
-    const std::string fn = "pfac_documents_group_masks";
-    rc = last_scan_usable(ctx, s, fn, SCAN_FINISHED | SCAN_LENGTHS | SCAN_TABLE);
+    rc = doc_reduce_run<GroupOr>(ctx, s, "pfac_documents_group_masks", ctx->gmask.p, "groups", s.gm_out, d_records, d_doc_offsets,
+                                 n_docs, reinterpret_cast<unsigned long long *>(d_masks_out));
+    if (rc == PFAC_OK) *any_mask = host_u64(s, H_PASS);
+    return rc;
+}
+
+int pfac_documents_scores(pfac_ctx *ctx, int slot, const void *d_records, const uint64_t *d_doc_offsets, uint64_t n_docs,
+                          pfac_doc_score *d_scores_out, pfac_doc_score *total) {
+    int rc = check_slot(ctx, slot);
     if (rc) return rc;
-    if (!ctx->gmask.p) return fail(ctx, PFAC_E_STATE, fn + ": no state groups for the uploaded table (pfac_table_set_state_groups)");
-    if (!d_doc_offsets && (!s.doc.done || n_docs + 1 != s.doc.n))
-        return fail(ctx, PFAC_E_STATE, fn + ": the slot has no document offsets for this n_docs (pfac_slot_doc_offsets, pfac_slot_doc_offsets_split)");
-    rc = last_scan_usable(ctx, s, fn, SCAN_FITS);
+    if (!total) return fail(ctx, PFAC_E_ARG, "null argument");
+    *total = pfac_doc_score{0, 0};
+    Slot &s = ctx->slots[slot];
+    rc = doc_reduce_run<ScoreAdd>(ctx, s, "pfac_documents_scores", ctx->sweight.p, "weights", s.sc_out, d_records, d_doc_offsets,
+                                  n_docs, d_scores_out);
+    if (rc == PFAC_OK) *total = pfac_doc_score{(int64_t)host_u64(s, H_PASS), host_u64(s, H_PASS1)};
+    return rc;
+}
+
+int pfac_selection_document_scores(pfac_ctx *ctx, int slot, const pfac_record *d_sel, const uint64_t *d_doc_first,
+                                   uint64_t n_docs, pfac_doc_score *d_scores_out, pfac_doc_score *total) {
+    int rc = check_slot(ctx, slot);
     if (rc) return rc;
-    const unsigned long long *off;
-    rc = resolve_docs(ctx, s, fn, d_doc_offsets, n_docs, (uintptr_t)d_masks_out, &off);
-    if (rc) return rc;
-    const void *src = d_records ? d_records : (const void *)s.records.p;
-    if (s.last_tiles && src != s.last_records) return fail(ctx, PFAC_E_ARG, fn + ": d_records is not the record heap of the slot's last scan");
+    if (!total) return fail(ctx, PFAC_E_ARG, "null argument");
+    *total = pfac_doc_score{0, 0};
+    Slot &s = ctx->slots[slot];
+    s.sc_out.invalidate();
+    const std::string fn = "pfac_selection_document_scores";
+    if (!ctx->have_table) return fail(ctx, PFAC_E_STATE, fn + " before a table upload");
+    if (!ctx->sweight.p) return fail(ctx, PFAC_E_STATE, fn + ": no state weights for the uploaded table (pfac_table_set_state_weights)");
+    const pfac_record *sel = d_sel;
+    const unsigned long long *first = reinterpret_cast<const unsigned long long *>(d_doc_first);
+    uint64_t n = 0;
+    const bool own = !d_sel && !d_doc_first;
+    if (own) {                                              // the rules of pfac_selection_count_states' d_sel
+        if (!s.scanned || s.pending || !s.ll_out.done || s.ll_seq != s.scan_seq || !s.ll_docs)
+            return fail(ctx, PFAC_E_STATE, fn + " needs a pfac_records_leftmost_longest_documents since the slot's last scan");
+        if (s.last_table != ctx->table_gen) return fail(ctx, PFAC_E_STATE, fn + ": the selection was made with an earlier table");
+        rc = s.ll_out.consume(ctx, fn, "selection (d_sel)", d_sel, ANY_N, &sel);
+        if (rc) return rc;
+        rc = s.lld_first.consume(ctx, fn, "doc_first of the selection (d_doc_first)", d_doc_first, n_docs + 1, &first);
+        if (rc) return rc;
+        n = s.ll_out.n;
+    } else if (!d_sel || !d_doc_first) {
+        return fail(ctx, PFAC_E_ARG, fn + ": d_sel and d_doc_first are the slot's (both NULL) or the caller's (neither)");
+    }
+    if (n_docs >= (1ull << 32)) return fail(ctx, PFAC_E_ARG, fn + ": n_docs must be below 2^32");
+    if ((((uintptr_t)sel | (uintptr_t)first) & 7) || ((uintptr_t)d_scores_out & 15))
+        return fail(ctx, PFAC_E_ARG, fn + ": misaligned buffer (d_sel and d_doc_first 8 B, d_scores_out 16 B)");
     USE_DEVICE(ctx);
-    const uint64_t n_tiles = n_docs ? s.last_tiles : 0;     // (no documents: the scan owns no bytes, only the offsets are judged)
-    const unsigned n_groups = (unsigned)((n_tiles + XGROUP - 1) / XGROUP);
-    rc = ensure_gsum(ctx, s, 1);                            // the OR of all masks, the offsets' error flag
+    if (!own) {                                             // how many records the caller's arrays hold: doc_first[n_docs]
+        HIP_TRY(ctx, hipMemcpyAsync(s.h_ctl + H_PASS, first + n_docs, 8, hipMemcpyDeviceToHost, s.stream));
+        HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+        n = host_u64(s, H_PASS);
+    }
+    const uint64_t n_waves = (n + SS_RANGE - 1) / SS_RANGE;
+    if (n_waves >= (1ull << 33)) return fail(ctx, PFAC_E_ARG, fn + ": too many records");
+    rc = ensure_gsum(ctx, s, ScoreAdd::RES_WORDS);
     if (rc) return rc;
-    // The masks are made in the slot's buffer and reach a caller's only behind the host's check of the offsets' flag:
-    // a refused call leaves the caller's buffer as it was.
-    unsigned long long *masks;
-    rc = s.gm_out.bind(ctx, s.stream, (uint64_t *)nullptr, std::max<uint64_t>(n_docs, 1), docs_cap(n_docs), &masks);
+    pfac_doc_score *out;
+    rc = s.sc_out.bind(ctx, s.stream, (pfac_doc_score *)nullptr, std::max<uint64_t>(n_docs, 1), docs_cap(n_docs), &out);
     if (rc) return rc;
-    HIP_TRY(ctx, hipMemsetAsync(s.gsum.p, 0, 16, s.stream));
-    if (n_docs) HIP_TRY(ctx, hipMemsetAsync(masks, 0, n_docs * 8, s.stream));     // the 0 of every document without a grouped record
-    const uint64_t gblocks = (n_groups + 3) / 4, vblocks = (n_docs + 255) / 256;
-    const unsigned blocks = (unsigned)std::max<uint64_t>(1, std::max<uint64_t>(gblocks, std::min<uint64_t>(vblocks, 4096)));
-    auto mk = by_width(s.last_rec_bytes, [](auto w) { return pfac_group_masks_kernel<w()>; });
-    hipLaunchKernelGGL(mk, dim3(blocks), dim3(256), 0, s.stream, src, s.tile_index.p, (unsigned long long)n_tiles,
-                       (unsigned long long)s.last_cap, off, (unsigned long long)n_docs, (unsigned long long)s.last_owned,
-                       ctx->flen.p, ctx->gmask.p, (unsigned)ctx->plan.base.num_final, masks, n_groups, s.gsum.p);
-    rc = pass_words(ctx, s, s.gsum.p, 2);
+    HIP_TRY(ctx, hipMemsetAsync(s.gsum.p, 0, (ScoreAdd::RES_WORDS + 1) * 8, s.stream));
+    if (n_docs) HIP_TRY(ctx, hipMemsetAsync(out, 0, n_docs * sizeof(pfac_doc_score), s.stream));
+    const uint64_t vblocks = (n_docs + 255) / 256;
+    const unsigned blocks = (unsigned)std::max<uint64_t>(1, std::max<uint64_t>((n_waves + 3) / 4, std::min<uint64_t>(vblocks, 4096)));
+    hipLaunchKernelGGL(pfac_sel_scores_kernel, dim3(blocks), dim3(256), 0, s.stream, sel, (unsigned long long)n, first,
+                       (unsigned long long)n_docs, ctx->sweight.p, (unsigned)ctx->plan.base.num_final, out, s.gsum.p);
+    rc = pass_words(ctx, s, s.gsum.p, ScoreAdd::RES_WORDS + 1);
     if (rc) return rc;
-    if (host_u64(s, H_PASS1)) return bad_doc_offsets(ctx, s, fn);
-    if (d_masks_out && n_docs)
-        HIP_TRY(ctx, hipMemcpyAsync(d_masks_out, masks, n_docs * 8, hipMemcpyDeviceToDevice, s.stream));
-    *any_mask = host_u64(s, H_PASS);
-    s.gm_out.commit(n_docs, !d_masks_out);
+    if (host_u64(s, H_PASS2))
+        return fail(ctx, PFAC_E_ARG, fn + ": d_doc_first must start at 0 and not decrease, and every state of d_sel must be below num_final");
+    if (d_scores_out && n_docs)
+        HIP_TRY(ctx, hipMemcpyAsync(d_scores_out, out, n_docs * sizeof(pfac_doc_score), hipMemcpyDeviceToDevice, s.stream));
+    *total = pfac_doc_score{(int64_t)host_u64(s, H_PASS), host_u64(s, H_PASS1)};
+    s.sc_out.commit(n_docs, !d_scores_out);
     return PFAC_OK;
+}
+
+int pfac_document_scores_d2h(pfac_ctx *ctx, int slot, pfac_doc_score *host, uint64_t first, uint64_t n) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    Slot &s = ctx->slots[slot];
+    return fetch(ctx, s, s.sc_out, "pfac_document_scores_d2h", "score pass (pfac_documents_scores, pfac_selection_document_scores)", host, first, n);
 }
 
 int pfac_group_masks_d2h(pfac_ctx *ctx, int slot, uint64_t *host_masks, uint64_t first, uint64_t n) {
@@ -6010,21 +6294,38 @@ static WriteGrid write_grid(uint64_t total) {
 
 // The three matching calls: the plain one (DM_PLAIN: flags 0 or PFAC_DOCS_INVERT), the one with context lines
 // (DM_CONTEXT: flags 0; before / after as the caller gave them) and the one over group masks (DM_GROUPS: d_doc_first
-// is the masks, before / after / none_of are all_of / any_of / none_of).  One pass: one slot-owned id buffer, one
-// fetch, one lifetime.
-static int dm_run(pfac_ctx *ctx, int slot, const std::string &fn, const uint64_t *d_doc_first, uint64_t n_docs, int pred,
+// is the masks, before / after / none_of are all_of / any_of / none_of) and the one over scores (DM_SCORES: d_doc_first
+// is the scores, `rule` the windows; with a density `d_doc_offsets` or the slot's offsets are read too: DM_DENSITY).
+// One pass: one slot-owned id buffer, one fetch, one lifetime.
+static int dm_run(pfac_ctx *ctx, int slot, const std::string &fn, const void *d_doc_first, uint64_t n_docs, int pred,
                   uint64_t before, uint64_t after, uint64_t none_of, uint32_t flags, uint64_t *d_ids_out, uint64_t out_cap,
-                  uint64_t *n_matching) {
+                  uint64_t *n_matching, const pfac_score_rule *rule = nullptr, const uint64_t *d_doc_offsets = nullptr) {
     int rc = check_slot(ctx, slot);
     if (rc) return rc;
     if (!n_matching) return fail(ctx, PFAC_E_ARG, "null argument");
     *n_matching = 0;
     Slot &s = ctx->slots[slot];
     s.dm_out.invalidate();
-    const bool context = pred == DM_CONTEXT, groups = pred == DM_GROUPS;
-    const unsigned long long *first;
-    rc = groups ? s.gm_out.consume(ctx, fn, "group masks of a pfac_documents_group_masks (n_docs entries)", d_doc_first, n_docs, &first)
-                : s.seg_first.consume(ctx, fn, "doc_first of a pfac_records_segment (n_docs + 1 entries)", d_doc_first, n_docs + 1, &first);
+    const bool context = pred == DM_CONTEXT, groups = pred == DM_GROUPS, scores = pred == DM_SCORES;
+    const unsigned long long *first, *off = nullptr;
+    if (scores) {
+        const pfac_doc_score *sc;
+        rc = s.sc_out.consume(ctx, fn, "scores of a score pass (n_docs entries)", static_cast<const pfac_doc_score *>(d_doc_first), n_docs, &sc);
+        first = reinterpret_cast<const unsigned long long *>(sc);
+        if (rc == PFAC_OK && !rule) rc = fail(ctx, PFAC_E_ARG, fn + ": null rule");
+        if (rc == PFAC_OK && rule->density_den) {
+            off = reinterpret_cast<const unsigned long long *>(d_doc_offsets);
+            if (!off && !s.doc.done) rc = fail(ctx, PFAC_E_STATE, fn + ": no document offsets for the slot (pfac_slot_doc_offsets)");
+            else if (!off && n_docs + 1 != s.doc.n) rc = fail(ctx, PFAC_E_ARG, fn + ": n_docs differs from the slot's document offsets");
+            else if (!off) off = s.doc.buf.p;
+        }
+        if (rc == PFAC_OK && ((((uintptr_t)first) & 15) || ((uintptr_t)off & 7)))
+            rc = fail(ctx, PFAC_E_ARG, fn + ": misaligned buffer (d_scores 16 B, d_doc_offsets 8 B)");
+    } else {
+        const uint64_t *df = static_cast<const uint64_t *>(d_doc_first);
+        rc = groups ? s.gm_out.consume(ctx, fn, "group masks of a pfac_documents_group_masks (n_docs entries)", df, n_docs, &first)
+                    : s.seg_first.consume(ctx, fn, "doc_first of a pfac_records_segment (n_docs + 1 entries)", df, n_docs + 1, &first);
+    }
     if (rc) return rc;
     if (context && flags) return fail(ctx, PFAC_E_ARG, fn + ": flags must be 0 (context around non-matching documents is not defined by doc_first)");
     if (flags > PFAC_DOCS_INVERT) return fail(ctx, PFAC_E_ARG, fn + ": flags must be 0 or PFAC_DOCS_INVERT");
@@ -6035,11 +6336,18 @@ static int dm_run(pfac_ctx *ctx, int slot, const std::string &fn, const uint64_t
     // (a window wider than the input is the input; the groups form passes its sets as they are)
     const unsigned long long bef = groups ? before : std::min(before, n_docs), aft = groups ? after : std::min(after, n_docs);
     const dim3 grid((n_groups + 3) / 4), block(256);
+    const pfac_doc_score *sc = reinterpret_cast<const pfac_doc_score *>(first);
     uint64_t total = 0;
     if (n_groups) {
         rc = ensure_gsum(ctx, s, n_groups);
         if (rc) return rc;
-        if (groups)
+        if (scores && off)
+            hipLaunchKernelGGL((pfac_docs_scores_kernel<false, true>), grid, block, 0, s.stream, sc, (unsigned long long)n_docs, (unsigned)flags,
+                               *rule, off, s.gsum.p, n_groups, 0ull, (unsigned long long *)nullptr);
+        else if (scores)
+            hipLaunchKernelGGL((pfac_docs_scores_kernel<false, false>), grid, block, 0, s.stream, sc, (unsigned long long)n_docs, (unsigned)flags,
+                               *rule, off, s.gsum.p, n_groups, 0ull, (unsigned long long *)nullptr);
+        else if (groups)
             hipLaunchKernelGGL(pfac_docs_groups_kernel<false>, grid, block, 0, s.stream, first, (unsigned long long)n_docs, (unsigned)flags,
                                bef, aft, (unsigned long long)none_of, s.gsum.p, n_groups, 0ull, (unsigned long long *)nullptr);
         else if (context)
@@ -6060,7 +6368,13 @@ static int dm_run(pfac_ctx *ctx, int slot, const std::string &fn, const uint64_t
     rc = s.dm_out.bind(ctx, s.stream, d_ids_out, total, total + total / 8 + 4096, &ids);
     if (rc) return rc;
     if (total) {
-        if (groups)
+        if (scores && off)
+            hipLaunchKernelGGL((pfac_docs_scores_kernel<true, true>), grid, block, 0, s.stream, sc, (unsigned long long)n_docs, (unsigned)flags,
+                               *rule, off, s.gsum.p, n_groups, (unsigned long long)total, ids);
+        else if (scores)
+            hipLaunchKernelGGL((pfac_docs_scores_kernel<true, false>), grid, block, 0, s.stream, sc, (unsigned long long)n_docs, (unsigned)flags,
+                               *rule, off, s.gsum.p, n_groups, (unsigned long long)total, ids);
+        else if (groups)
             hipLaunchKernelGGL(pfac_docs_groups_kernel<true>, grid, block, 0, s.stream, first, (unsigned long long)n_docs, (unsigned)flags,
                                bef, aft, (unsigned long long)none_of, s.gsum.p, n_groups, (unsigned long long)total, ids);
         else if (context)
@@ -6091,6 +6405,13 @@ int pfac_documents_matching_groups(pfac_ctx *ctx, int slot, const uint64_t *d_ma
                                    uint64_t *n_matching) {
     return dm_run(ctx, slot, "pfac_documents_matching_groups", d_masks, n_docs, DM_GROUPS, all_of, any_of, none_of, flags, d_ids_out,
                   out_cap, n_matching);
+}
+
+int pfac_documents_matching_scores(pfac_ctx *ctx, int slot, const pfac_doc_score *d_scores, const uint64_t *d_doc_offsets,
+                                   uint64_t n_docs, const pfac_score_rule *rule, uint32_t flags, uint64_t *d_ids_out,
+                                   uint64_t out_cap, uint64_t *n_matching) {
+    return dm_run(ctx, slot, "pfac_documents_matching_scores", d_scores, n_docs, DM_SCORES, 0, 0, 0, flags, d_ids_out, out_cap,
+                  n_matching, rule, d_doc_offsets);
 }
 
 int pfac_documents_matching_d2h(pfac_ctx *ctx, int slot, uint64_t *host_ids) {

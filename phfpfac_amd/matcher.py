@@ -16,8 +16,8 @@ import numpy as np
 from ._ffi import (PFAC_COUNT_ACCUMULATE, PFAC_DOCS_INVERT, PFAC_E_OVERFLOW, PFAC_FOLD_ASCII, PFAC_FOLD_NONE, PFAC_SPANS_LINE, PFAC_WORD_LEFT, PFAC_WORD_RIGHT, CRecord, PfacError,
                    hip_lib)
 from ._ffi import (PFAC_LINE_CONTEXT_SEP, PFAC_LINE_MAX_GROUP_SEP, PFAC_LINE_NUMBER, PFAC_LINE_OFFSET, PFAC_LINE_SEP_FIRST,
-                   PFAC_LINE_TERMINATE, CLineFormat)
-from .table import RECORD_DTYPE, TEMPLATE_PLAIN, PfacTable, redaction_table, replacement_table, template_table, _state_lengths
+                   PFAC_LINE_TERMINATE, CDocScore, CLineFormat, CScoreRule)
+from .table import RECORD_DTYPE, SCORE_DTYPE, TEMPLATE_PLAIN, PfacTable, redaction_table, replacement_table, template_table, _state_lengths
 
 
 def device_count() -> int:
@@ -821,6 +821,105 @@ class GpuMatcher:
         _, n_docs = self._scan_lines(buf, delimiter, slot, whole_words, fetch_offsets=False, spans=spans, line_match=line_match)
         self.document_group_masks(n_docs, slot=slot)
         n = self.matching_documents_where(n_docs, all_of, any_of, none_of, invert=invert, slot=slot)
+        out_bytes = self.gather_documents(n_docs, n, int(buf.size), slot=slot)
+        return (self.gathered_to_host(out_bytes, slot), self.gathered_offsets_to_host(n, slot),
+                self.matching_documents_to_host(n, slot))
+
+    # -- document scores: a weighted match sum and a count per document -----
+    def set_pattern_weights(self, weights) -> None:
+        """The weight of every pattern of the uploaded table (``PfacTable.state_weights``: one integer per 1-based
+        pattern id, entry 0 unused), kept on the device until the next table upload
+        (``pfac_table_set_state_weights``)."""
+        if self.table is None:
+            raise PfacError(-7, "no host table to map pattern ids to states (load_table first)")
+        w = self.table.state_weights(weights)
+        self._check(self._L.pfac_table_set_state_weights(self._ctx, w.ctypes.data if w.size else None, w.size))
+
+    def document_scores(self, n_docs: int, d_doc_offsets=None, d_out=None, slot: int = 0, d_records=None) -> Tuple[int, int]:
+        """How much of the pattern set each document of the slot's last finished scan holds, on the GPU
+        (``pfac_documents_scores``): ``count[d]`` = the records the document cut would keep, ``score[d]`` = the sum of
+        their patterns' weights (``set_pattern_weights``; int64, wrapping), straight from the record heap -- no segment
+        pass.  ``d_doc_offsets`` None = the slot's; ``d_out`` None = a slot-owned buffer
+        (``document_scores_to_host``), else a device buffer of ``n_docs`` x 16 bytes.  Returns the totals over all
+        documents, (score, count)."""
+        t = CDocScore(0, 0)
+        self._check(self._L.pfac_documents_scores(self._ctx, slot, _ptr(d_records), _ptr(d_doc_offsets), int(n_docs),
+                                                  _ptr(d_out), C.byref(t)))
+        return t.score, t.count
+
+    def selection_document_scores(self, n_docs: int, d_sel=None, d_doc_first=None, d_out=None, slot: int = 0) -> Tuple[int, int]:
+        """``document_scores`` over records that are already cut per document (``pfac_selection_document_scores``):
+        ``d_sel`` and ``d_doc_first`` both None = the picks of the slot's last
+        ``select_leftmost_longest_documents`` -- non-overlapping matches, so "ass" inside "assassin" is not counted
+        three times; else the device arrays of a selection or of ``segment_records``.  Returns the totals."""
+        t = CDocScore(0, 0)
+        self._check(self._L.pfac_selection_document_scores(self._ctx, slot, _ptr(d_sel), _ptr(d_doc_first), int(n_docs),
+                                                           _ptr(d_out), C.byref(t)))
+        return t.score, t.count
+
+    def document_scores_to_host(self, n_docs: int, slot: int = 0, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """Scores [first, first + n) of the slot's last score pass into its slot-owned buffer (default: all
+        ``n_docs``): a structured array of ``SCORE_DTYPE`` (``score`` int64, ``count`` uint64)."""
+        n = int(n_docs) - int(first) if n is None else int(n)
+        return self._to_host(slot, lambda p: self._L.pfac_document_scores_d2h(self._ctx, slot, p, int(first), n),
+                             (max(n, 0), SCORE_DTYPE))
+
+    def matching_documents_scored(self, n_docs: int, min_score=None, max_score=None, min_count=None, max_count=None,
+                                  density=None, invert: bool = False, d_scores=None, d_doc_offsets=None, d_out=None,
+                                  out_cap: int = 0, slot: int = 0) -> int:
+        """The documents whose score lies in [``min_score``, ``max_score``] and whose count lies in [``min_count``,
+        ``max_count``] (None: that end is open) and, with ``density`` = (num, den), whose score is at least num / den
+        per byte -- ``score * den >= num * length``, compared exactly (``invert``: the others), ascending, on the GPU
+        (``pfac_documents_matching_scores``).  ``d_scores`` None = the slot-owned scores of the slot's last score
+        pass; ``d_doc_offsets`` (read for a density only) None = the slot's offsets.  The ids go where
+        ``matching_documents`` puts them.  Returns the number of documents; a too small ``out_cap`` raises
+        PfacError(PFAC_E_OVERFLOW) whose ``n_matching`` attribute holds the exact count."""
+        num, den = (0, 0) if density is None else (int(density[0]), int(density[1]))
+        if density is not None and den <= 0:
+            raise ValueError("the density's denominator must be positive")
+        rule = CScoreRule(-(2 ** 63) if min_score is None else int(min_score), 2 ** 63 - 1 if max_score is None else int(max_score),
+                          0 if min_count is None else int(min_count), 2 ** 64 - 1 if max_count is None else int(max_count), num, den)
+        n = C.c_uint64(0)
+        rc = self._L.pfac_documents_matching_scores(self._ctx, slot, _ptr(d_scores), _ptr(d_doc_offsets), int(n_docs),
+                                                    C.byref(rule), PFAC_DOCS_INVERT if invert else 0, _ptr(d_out),
+                                                    int(out_cap), C.byref(n))
+        return self._counted(rc, n, "n_matching")
+
+    def _score_pass(self, n_docs: int, slot: int, non_overlapping: bool) -> None:
+        if non_overlapping:
+            self.select_leftmost_longest_documents(n_docs, slot=slot)
+            self.selection_document_scores(n_docs, slot=slot)
+        else:
+            self.document_scores(n_docs, slot=slot)
+
+    def score_documents(self, docs, whole_words=False, slot: int = 0, spans: bool = False, line_match: bool = False,
+                        non_overlapping: bool = False) -> np.ndarray:
+        """The score and match count of every document of a batch (``docs`` as ``scan_documents`` takes it) in one
+        scan: ``SCORE_DTYPE[n_docs]``.  ``non_overlapping``: over the leftmost-longest picks of each document instead
+        of every match.  Only the scores come back."""
+        _, n_docs = self._scan_docs(docs, slot, whole_words, spans, line_match)
+        self._score_pass(n_docs, slot, non_overlapping)
+        return self.document_scores_to_host(n_docs, slot)
+
+    def score_lines(self, data, delimiter=b"\n", whole_words=False, slot: int = 0, spans: bool = False, line_match: bool = False,
+                    non_overlapping: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+        """``score_documents`` of one buffer cut into lines at ``delimiter`` on the device -- ``grep -c`` per line, or
+        a weighted sum.  Returns (offsets uint64[n_docs + 1], scores ``SCORE_DTYPE[n_docs]``)."""
+        offsets, n_docs = self._scan_lines(data, delimiter, slot, whole_words, spans=spans, line_match=line_match)
+        self._score_pass(n_docs, slot, non_overlapping)
+        return offsets, self.document_scores_to_host(n_docs, slot)
+
+    def grep_lines_scored(self, data, min_score=None, max_score=None, min_count=None, max_count=None, density=None,
+                          invert: bool = False, delimiter=b"\n", whole_words=False, slot: int = 0, spans: bool = False,
+                          line_match: bool = False, non_overlapping: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The lines of ``data`` whose score satisfies the rule of ``matching_documents_scored``, as bytes -- "the
+        lines with at least three hits", "the lines whose weights sum to 5 or more": scan, split, the score pass, the
+        rule and the gather on the device, with no document cut in between.  Returns what ``grep_lines`` returns: (out
+        uint8[out_bytes], out_offsets uint64[n + 1], ids uint64[n])."""
+        buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data.view(np.uint8).ravel()
+        _, n_docs = self._scan_lines(buf, delimiter, slot, whole_words, fetch_offsets=False, spans=spans, line_match=line_match)
+        self._score_pass(n_docs, slot, non_overlapping)
+        n = self.matching_documents_scored(n_docs, min_score, max_score, min_count, max_count, density, invert=invert, slot=slot)
         out_bytes = self.gather_documents(n_docs, n, int(buf.size), slot=slot)
         return (self.gathered_to_host(out_bytes, slot), self.gathered_offsets_to_host(n, slot),
                 self.matching_documents_to_host(n, slot))

@@ -12,10 +12,12 @@ import os
 import numpy as np
 
 from ._ffi import PFAC_SPAN_ANY, CTable, PfacError, host_lib
+from ._ffi import SCORE_DTYPE as _SCORE_FIELDS
 from ._ffi import SPAN_DTYPE as _SPAN_FIELDS
 
 RECORD_DTYPE = np.dtype([("pos", np.uint32), ("state", np.uint32)])
 SPAN_DTYPE = np.dtype(_SPAN_FIELDS)         # struct pfac_state_span
+SCORE_DTYPE = np.dtype(_SCORE_FIELDS)       # struct pfac_doc_score
 
 
 class PfacTable:
@@ -218,6 +220,35 @@ class PfacTable:
         out = np.zeros(int(self.num_final), dtype=np.uint64)
         np.bitwise_or.at(out, np.repeat(np.arange(int(self.num_final)), np.diff(np.asarray(first, dtype=np.int64))), per)
         return out
+
+    def state_weights(self, weights) -> np.ndarray:
+        """Pattern weights -> int32[num_final] for ``pfac_table_set_state_weights``.  ``weights`` is indexed by the
+        1-based pattern id (entry 0 is unused), one integer per id the table can report, as in
+        ``state_group_masks``.  A literal table takes ``weights[idmap[s]]``: of duplicate lines the winning line's
+        weight.  A character-class table SUMS the weights of every pattern that ends in state s
+        (``out_ids[out_first[s]:out_first[s + 1]]``), because every one of them matched there.  ValueError if a
+        weight or a sum leaves int32."""
+        first = getattr(self, "out_first", None)
+        ids = np.asarray(self.idmap if first is None else self.out_ids, dtype=np.int64)
+        need = max(int(self.n_patterns), int(ids.max()) if ids.size else 0) + 1
+        given = list(weights)
+        if len(given) != need:
+            raise ValueError(f"need one entry per pattern id and the unused entry 0 ({need}), got {len(given)}")
+        entries = [0] + [int(w) for w in given[1:]]
+        lo, hi = -(2 ** 31), 2 ** 31 - 1
+        for i, w in enumerate(entries):
+            if not lo <= w <= hi:
+                raise ValueError(f"weight {w} of pattern id {i} is outside int32")
+        per = np.array(entries, dtype=np.int64)[ids]
+        if first is None:
+            out = per[: self.num_final]
+        else:
+            out = np.zeros(int(self.num_final), dtype=np.int64)
+            np.add.at(out, np.repeat(np.arange(int(self.num_final)), np.diff(np.asarray(first, dtype=np.int64))), per)
+            over = np.flatnonzero((out < lo) | (out > hi))
+            if over.size:
+                raise ValueError(f"the weights of the patterns that end in final state {int(over[0])} sum to {int(out[over[0]])}, outside int32")
+        return np.ascontiguousarray(out, dtype=np.int32)
 
     def state_spans(self, rules) -> np.ndarray:
         """Anchors and offsets of the patterns -> ``SPAN_DTYPE[num_final]`` for ``pfac_table_set_state_spans``.
