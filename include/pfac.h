@@ -785,6 +785,52 @@ typedef struct {
 int pfac_documents_matching_scores(pfac_ctx *ctx, int slot, const pfac_doc_score *d_scores, const uint64_t *d_doc_offsets,
                                    uint64_t n_docs, const pfac_score_rule *rule, uint32_t flags, uint64_t *d_ids_out,
                                    uint64_t out_cap, uint64_t *n_matching);
+/* The k best documents by score or by count, in order: "the 100 most suspicious lines", "the 20 best hits".
+ *   candidates     rule == NULL: every document.  Else the documents pfac_documents_matching_scores reports for (rule,
+ *                  rule_flags), density and PFAC_DOCS_INVERT included; d_doc_offsets is read only for a density, under
+ *                  that call's rules.  "Matched documents only" is min_count = 1
+ *   rank order     by key, ties to the smaller id.  The key is score[d], compared as signed 64-bit, largest first;
+ *                  PFAC_TOP_BY_COUNT: count[d], compared as unsigned 64-bit; PFAC_TOP_LOWEST: smallest first
+ *   *n_top         min(k, the number of candidates); any k up to 2^64 - 1 clamps.  k == 0 or n_docs == 0 gives 0 and
+ *                  writes nothing
+ *   reported       the first *n_top candidates in rank order: where k cuts through a class of equal keys, its members
+ *                  with the smallest ids.  PFAC_TOP_RANKED: ids[j] is the document of rank j; else the same documents,
+ *                  ids ascending (document order, as grep prints).  top_scores[j] = scores[ids[j]], the whole pair
+ *   d_scores, n_docs < 2^32, the alignments and the PFAC_E_STATE / PFAC_E_ARG ladder are exactly those of
+ *                  pfac_documents_matching_scores (NULL = the slot-owned scores of the slot's last score pass)
+ *   d_ids_out      as in pfac_documents_matching: the call is ONE pass with it, _context, _groups and _scores -- the same
+ *                  slot-owned id buffer, pfac_documents_matching_d2h, and pfac_documents_gather(d_ids = NULL) /
+ *                  _gather_format consume the ids unchanged, in rank order too (the gather takes any order)
+ *   d_top_scores_out  NULL = a slot-owned buffer of its own (pfac_documents_top_scores_d2h; the lifetime rule of
+ *                  pfac_segment_d2h: the next pfac_documents_top_scores discards it, a matching call does not); else a
+ *                  device pointer, 16-B aligned, out_cap entries like d_ids_out
+ * PFAC_E_OVERFLOW with *n_top exact when out_cap < *n_top and either output is the caller's; PFAC_E_ARG also for flags
+ * outside the three and rule_flags outside PFAC_DOCS_INVERT.  Every error leaves every caller's buffer untouched; a
+ * failed call discards the slot-owned ids and pairs.  No entry at or past *n_top is written in either output: buffers
+ * of exactly *n_top x 8 and *n_top x 16 bytes are enough.  Returns once *n_top is known (one 8-byte copy back); the
+ * writes complete on the slot's stream.  The same call on the same scores gives the same bytes.
+ * A rank by DENSITY (score per byte) is out of scope: a ratio has no radix key.  A density only filters.
+ * Kernels: (1) an MSB-first radix select of the key of rank *n_top over an order-preserving 64-bit word (sign bit
+ * flipped for scores, all bits inverted for "largest first"): eight passes of 8 bits, each a grid-stride read of the
+ * pairs into LDS histograms (lanes that agree on the digit are found by ballots and add once) flushed with 64-bit
+ * atomics; the digit that holds the rank is chosen on the device, by every wave of the next pass from the small
+ * histogram; the first pass counts the candidates.  (2) The compaction of pfac_documents_matching with two counts per
+ * block and group -- keys in front of the threshold key T, keys equal to T -- which takes every candidate in front of T
+ * and the first `need` of those equal to it, ascending, and writes the pairs in the same pass.  (3) PFAC_TOP_RANKED: a
+ * stable LSD radix sort of the *n_top (key word, id) entries, ranks inside a wave from ballots; stability is the tie
+ * rule, since step 2 delivers ascending ids.  Up to PFAC_TOP_SORT_BLOCK entries it is one workgroup working in LDS,
+ * above that blocks of PFAC_TOP_SORT_BLOCK with a histogram, a prefix and a scatter per pass between two scratch
+ * buffers.  The last pass writes the ids and gathers the pairs. */
+#define PFAC_TOP_BY_COUNT  1u   /* key = count[d] (uint64); default key = score[d] (int64, signed order) */
+#define PFAC_TOP_LOWEST    2u   /* the k smallest keys instead of the k largest */
+#define PFAC_TOP_RANKED    4u   /* ids in rank order; default: the same ids, ascending (document order, as grep prints) */
+#define PFAC_TOP_SORT_BLOCK 1024u   /* entries per workgroup of the ranked sort, and the most that one workgroup sorts alone */
+int pfac_documents_top_scores(pfac_ctx *ctx, int slot, const pfac_doc_score *d_scores, const uint64_t *d_doc_offsets,
+                              uint64_t n_docs, const pfac_score_rule *rule, uint32_t rule_flags, uint64_t k, uint32_t flags,
+                              uint64_t *d_ids_out, uint64_t out_cap, pfac_doc_score *d_top_scores_out, uint64_t *n_top);
+/* D2H of pairs [first, first + n) of the slot-owned result of the last pfac_documents_top_scores.  Asynchronous on the
+ * slot's stream; pfac_slot_sync completes it.  first + n > *n_top gives PFAC_E_ARG; n == 0 does nothing. */
+int pfac_documents_top_scores_d2h(pfac_ctx *ctx, int slot, pfac_doc_score *host, uint64_t first, uint64_t n);
 
 /* Whole-word filter: drops, IN PLACE, the records of the slot's last finished scan that split a word, so that every
  * consumer of the scan (the fetches, the text emitter, the checksum, the segment pass, both selections and both

@@ -42,6 +42,10 @@ PFAC_LINE_TERMINATE = 4     # ... the terminator behind a document that is empty
 PFAC_LINE_CONTEXT_SEP = 8   # ... sep_context as label separator for a document without a kept record
 PFAC_LINE_SEP_FIRST = 16    # ... the group separator also in front of ids[0]
 PFAC_LINE_MAX_GROUP_SEP = 8
+PFAC_TOP_BY_COUNT = 1       # pfac_documents_top_scores: key = count[d] (default: score[d], signed)
+PFAC_TOP_LOWEST = 2         # ... the k smallest keys instead of the k largest
+PFAC_TOP_RANKED = 4         # ... ids in rank order (default: the same ids, ascending)
+PFAC_TOP_SORT_BLOCK = 1024  # ... entries per workgroup of the ranked sort
 
 _STATUS_NAMES = {
     0: "PFAC_OK", -1: "PFAC_E_ARG", -2: "PFAC_E_IO", -3: "PFAC_E_PATTERN", -4: "PFAC_E_NOMEM",
@@ -141,6 +145,7 @@ HIP_SYMBOLS = (
     "pfac_documents_gather_format",
     "pfac_table_set_state_weights", "pfac_documents_scores", "pfac_selection_document_scores", "pfac_document_scores_d2h",
     "pfac_documents_matching_scores",
+    "pfac_documents_top_scores", "pfac_documents_top_scores_d2h",
 )
 
 _host = None
@@ -301,6 +306,9 @@ def hip_lib() -> C.CDLL:
         L.pfac_selection_document_scores.argtypes = [vp, i, vp, vp, u64, vp, C.POINTER(CDocScore)]
         L.pfac_document_scores_d2h.argtypes = [vp, i, vp, u64, u64]
         L.pfac_documents_matching_scores.argtypes = [vp, i, vp, vp, u64, C.POINTER(CScoreRule), C.c_uint32, vp, u64, C.POINTER(u64)]
+        L.pfac_documents_top_scores.argtypes = [vp, i, vp, vp, u64, C.POINTER(CScoreRule), C.c_uint32, u64, C.c_uint32, vp, u64, vp,
+                                                C.POINTER(u64)]
+        L.pfac_documents_top_scores_d2h.argtypes = [vp, i, vp, u64, u64]
         L.pfac_table_set_state_spans.argtypes = [vp, vp, u64]
         L.pfac_records_filter_spans.argtypes = [vp, i, vp, vp, i, C.c_uint32, vp, u64, C.POINTER(u64)]
         _hip = L

@@ -4081,6 +4081,340 @@ pfac_docs_scores_kernel(const pfac_doc_score *scores, unsigned long long n_docs,
 }
 
 // ---------------------------------------------------------------------------
+// The k best documents by score or by count (pfac_documents_top_scores).  A document's key is mapped to a 64-bit word
+// whose UNSIGNED ASCENDING order is the rank order (top_key): the count as it is, the score with its sign bit flipped,
+// and all bits inverted for "largest first".  Three steps, none of which goes back to the host for a digit:
+//   pfac_top_hist_kernel     TOP_PASSES times, most significant digit first: a grid-stride read of the pairs (and of the
+//                            two offsets under a density); the candidates whose higher digits equal the prefix found so
+//                            far are counted by their next digit -- the lanes of a wave that agree on the digit are
+//                            found with ballots and ONE of them adds their number to the workgroup's 32-bit LDS
+//                            partial; the non-zero partials go to the 64-bit histogram with no-return atomics.
+//                            (TOP_COPIES histograms per pass, dealt to the workgroups round-robin).
+//                            The digit that holds the rank is chosen by the first wave of EVERY WORKGROUP of the next
+//                            pass from the small histograms (top_pick: 4 bins per lane, a scan over the lanes):
+//                            prefix |= digit, krem -= the candidates in front of it; the first thread of the grid
+//                            records that state (words of their own per pass: nobody reads what another writes in the
+//                            same launch).  The first histograms' sum is n_cand, the word the host copies back:
+//                            n_top = min(k, n_cand).  pfac_top_final_kernel, one wave, does the same behind the last
+//                            pass: prefix = T, the key of rank n_top, and krem = need, the candidates with key T that
+//                            are still to be taken
+//   pfac_top_compact_kernel  the matching pass's compaction with TWO counts per block and group: candidates with key < T
+//                            and with key == T.
+//                            Document d is reported iff its key < T, or its key == T and fewer than `need` candidates
+//                            with key T have a smaller id; it lands at (keys < T in front of it) + min(keys == T in
+//                            front of it, need) -- ascending ids.  Unranked: the id and the pair are stored there.
+//                            Ranked: the entry (key word, id) goes to the sort's first buffer
+//   the sort                 (PFAC_TOP_RANKED) a stable LSD radix sort of the entries by the key word, TOP_PASSES
+//                            passes.  Ascending ids in, a stable sort: ties end with the smaller id first.  An entry's
+//                            rank among its wave's equal digits comes from the ballots (ts_rank) -- no atomic on the
+//                            output.  n_top <= TS_BLOCK: pfac_top_sort_one_kernel, one workgroup, all passes through
+//                            LDS.  Above: per pass pfac_top_sort_hist_kernel (digit counts per block of TS_BLOCK
+//                            entries, digit-major, so ONE exclusive scan, pfac_scan_groups_kernel, gives every (digit,
+//                            block) its base) and pfac_top_sort_scatter_kernel, ping-pong between two buffers.  The
+//                            last pass writes the ids and gathers each winner's pair from the scores.
+// Nothing is stored at or past n_top in either output.
+constexpr int TOP_BITS = 8;
+constexpr int TOP_BINS = 1 << TOP_BITS;
+constexpr int TOP_PASSES = 64 / TOP_BITS;
+constexpr int TOP_PER_LANE = TOP_BINS / WAVE;
+constexpr int TOP_COPIES = 8;                                       // histograms per pass: workgroup b adds to copy b % 8 (an address takes
+                                                                    // its atomics one at a time: 2048 workgroups on one would be the pass)
+constexpr int TOP_STATE = TOP_PASSES * TOP_COPIES * TOP_BINS;       // behind the histograms: (prefix, krem) in front of pass p at
+constexpr int TOP_NCAND = TOP_STATE + 2 * (TOP_PASSES + 1);         // TOP_STATE + 2 p (1 <= p <= TOP_PASSES), then the candidates
+constexpr int TOP_WORK_WORDS = TOP_NCAND + 1;
+constexpr int TS_ITEMS = 4;                                         // entries per thread of a sort block, ...
+constexpr int TS_WAVES = 4;
+constexpr int TS_BLOCK = TS_WAVES * WAVE * TS_ITEMS;                // ... which holds 1024: wave w owns [256 w, 256 w + 256)
+static_assert(TS_BLOCK == PFAC_TOP_SORT_BLOCK, "the header names the sort's block size");
+static_assert(TS_WAVES * WAVE == TOP_BINS, "one thread per digit in the histogram flush and the sort's bases");
+
+__device__ __forceinline__ unsigned long long top_key(const ulonglong2 v, unsigned flags) {
+    const unsigned long long w = (flags & PFAC_TOP_BY_COUNT) ? v.y : v.x ^ (1ull << 63);
+    return (flags & PFAC_TOP_LOWEST) ? w : ~w;
+}
+// the rule of docs_matching_body's scores forms, for a document that exists (d < n_docs)
+template <bool DENSITY>
+__device__ __forceinline__ bool top_candidate(const ulonglong2 v, const pfac_score_rule &rule, unsigned invert,
+                                              const unsigned long long *off, unsigned long long d) {
+    const long long sc = (long long)v.x;
+    bool ok = v.y >= rule.min_count && v.y <= rule.max_count && sc >= rule.min_score && sc <= rule.max_score;
+    if (DENSITY) {
+        const unsigned long long lo = off[d], hi = off[d + 1];
+        ok = ok && (__int128)sc * (__int128)rule.density_den >= (__int128)rule.density_num * (__int128)(hi - lo);
+    }
+    return ok != (invert != 0u);
+}
+// match-any over the digit's bits: the `valid` lanes of the wave whose digit equals this lane's (called by the whole
+// wave; the value of a lane without `valid` means nothing)
+__device__ __forceinline__ unsigned long long wave_match_digit(unsigned digit, bool valid) {
+    unsigned long long m = __ballot(valid);
+#pragma unroll
+    for (int b = 0; b < TOP_BITS; b++) {
+        const bool bit = (digit >> b) & 1u;
+        const unsigned long long s = __ballot(bit);
+        m &= bit ? s : ~s;
+    }
+    return m;
+}
+// The state behind pass `pass` from the state in front of it and that pass's histogram (called by a whole wave; every
+// lane gets the same values): the digit that holds rank krem.  In front of pass 0 the state is (0, k), and k clamps to
+// the candidates, the histogram's sum (n_cand means that for pass 0 only).  krem == 0 (no candidate, or k == 0) picks
+// nothing and stays 0.
+__device__ __forceinline__ void top_pick(const unsigned long long *work, int pass, unsigned long long k, unsigned long long &prefix,
+                                         unsigned long long &krem, unsigned long long &n_cand) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    const unsigned long long *h = work + pass * (TOP_COPIES * TOP_BINS) + lane * TOP_PER_LANE;
+    unsigned long long c[TOP_PER_LANE], sum = 0;
+#pragma unroll
+    for (int j = 0; j < TOP_PER_LANE; j++) {
+        c[j] = 0ull;
+#pragma unroll
+        for (int i = 0; i < TOP_COPIES; i++) c[j] += h[i * TOP_BINS + j];
+        sum += c[j];
+    }
+    unsigned long long incl = sum;
+#pragma unroll
+    for (int d = 1; d < WAVE; d <<= 1) {
+        const unsigned long long y = __shfl_up(incl, d, WAVE);
+        if (lane >= d) incl += y;
+    }
+    n_cand = __shfl(incl, WAVE - 1, WAVE);
+    if (pass == 0) { prefix = 0ull; krem = k < n_cand ? k : n_cand; }
+    else { prefix = work[TOP_STATE + 2 * pass]; krem = work[TOP_STATE + 2 * pass + 1]; }
+    unsigned long long run = incl - sum;                            // candidates in front of this lane's digits
+    const bool mine = krem > run && krem <= incl;                   // one lane (1 <= krem <= the sum), or none
+    unsigned digit = (unsigned)lane * TOP_PER_LANE;
+#pragma unroll
+    for (int j = 0; j < TOP_PER_LANE - 1; j++) {
+        if (krem > run + c[j]) { run += c[j]; digit++; }
+        else break;
+    }
+    const unsigned long long who = __ballot(mine);
+    if (who) {
+        const int src = __ffsll((long long)who) - 1;
+        prefix |= (unsigned long long)__shfl(digit, src, WAVE) << (64 - TOP_BITS * (pass + 1));
+        krem = __shfl(krem - run, src, WAVE);
+    }
+}
+
+template <bool DENSITY>
+__global__ void __launch_bounds__(TOP_BINS)
+pfac_top_hist_kernel(const pfac_doc_score *scores, unsigned long long n_docs, unsigned invert, pfac_score_rule rule,
+                     const unsigned long long *off, unsigned flags, int pass, unsigned long long k, unsigned long long *work) {
+    __shared__ unsigned part[TOP_BINS];
+    __shared__ unsigned long long picked;
+    part[threadIdx.x] = 0u;
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int shift = 64 - TOP_BITS * (pass + 1);
+    if (pass > 0 && threadIdx.x < WAVE) {                           // the first wave picks for the workgroup
+        unsigned long long p, krem, n_cand;
+        top_pick(work, pass - 1, k, p, krem, n_cand);
+        if (threadIdx.x == 0) {
+            picked = p;
+            if (blockIdx.x == 0) {
+                work[TOP_STATE + 2 * pass] = p;
+                work[TOP_STATE + 2 * pass + 1] = krem;
+                if (pass == 1) work[TOP_NCAND] = n_cand;
+            }
+        }
+    }
+    __syncthreads();
+    const unsigned long long prefix = pass > 0 ? picked : 0ull;
+    const unsigned long long stride = (unsigned long long)gridDim.x * TOP_BINS;
+    for (unsigned long long d0 = (unsigned long long)blockIdx.x * TOP_BINS + (threadIdx.x & ~(WAVE - 1)); d0 < n_docs; d0 += stride) {
+        const unsigned long long d = d0 + lane;                          // (d0 is wave-uniform: the ballots see all 64 lanes)
+        const bool have = d < n_docs;
+        const ulonglong2 v = have ? reinterpret_cast<const ulonglong2 *>(scores)[d] : make_ulonglong2(0ull, 0ull);
+        const unsigned long long w = top_key(v, flags);
+        bool cand = have && top_candidate<DENSITY>(v, rule, invert, off, d);
+        if (pass > 0) cand = cand && ((w ^ prefix) >> (shift + TOP_BITS)) == 0ull;
+        const unsigned digit = (unsigned)(w >> shift) & (TOP_BINS - 1u);
+        const unsigned long long m = wave_match_digit(digit, cand);
+        if (cand && lane == __ffsll((long long)m) - 1)
+            __hip_atomic_fetch_add(part + digit, (unsigned)__popcll(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    __syncthreads();
+    const unsigned c = part[threadIdx.x];
+    if (c)
+        __hip_atomic_fetch_add(work + (pass * TOP_COPIES + blockIdx.x % TOP_COPIES) * TOP_BINS + threadIdx.x, (unsigned long long)c,
+                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// behind the last pass, ONE wave: T and need into the words "in front of pass TOP_PASSES"
+__global__ void __launch_bounds__(WAVE)
+pfac_top_final_kernel(unsigned long long *work, unsigned long long k) {
+    unsigned long long T, need, n_cand;
+    top_pick(work, TOP_PASSES - 1, k, T, need, n_cand);
+    if (threadIdx.x == 0) {
+        work[TOP_STATE + 2 * TOP_PASSES] = T;
+        work[TOP_STATE + 2 * TOP_PASSES + 1] = need;
+        if (TOP_PASSES == 1) work[TOP_NCAND] = n_cand;
+    }
+}
+
+template <bool WRITE, bool DENSITY>
+__global__ void __launch_bounds__(256)
+pfac_top_compact_kernel(const pfac_doc_score *scores, unsigned long long n_docs, unsigned invert, pfac_score_rule rule,
+                        const unsigned long long *off, unsigned flags, const unsigned long long *work, unsigned long long *bsum,
+                        unsigned long long *esum, unsigned n_groups, unsigned long long total, unsigned long long *ids,
+                        pfac_doc_score *top, ulonglong2 *ent) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    const unsigned g = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (g >= n_groups) return;
+    const unsigned long long T = work[TOP_STATE + 2 * TOP_PASSES], need = work[TOP_STATE + 2 * TOP_PASSES + 1];
+    const unsigned long long d0 = (unsigned long long)g * (DM_BLOCKS * WAVE);
+    const unsigned long long below = (1ull << lane) - 1ull;
+    unsigned long long run_b = WRITE ? bsum[g] : 0ull, run_e = WRITE ? esum[g] : 0ull;
+#pragma unroll 4
+    for (int b = 0; b < DM_BLOCKS; b++) {
+        const unsigned long long d = d0 + (unsigned long long)b * WAVE + lane;
+        const bool have = d < n_docs;
+        const ulonglong2 v = have ? reinterpret_cast<const ulonglong2 *>(scores)[d] : make_ulonglong2(0ull, 0ull);
+        const unsigned long long w = top_key(v, flags);
+        const bool cand = have && top_candidate<DENSITY>(v, rule, invert, off, d);
+        const bool before = cand && w < T, equal = cand && w == T;
+        const unsigned long long mb = __ballot(before), me = __ballot(equal);
+        if (WRITE) {
+            const unsigned long long eq_front = run_e + (unsigned long long)__popcll(me & below);
+            const unsigned long long r = run_b + (unsigned long long)__popcll(mb & below) + (eq_front < need ? eq_front : need);
+            if ((before || (equal && eq_front < need)) && r < total) {
+                if (ent) ent[r] = make_ulonglong2(w, d);
+                else { ids[r] = d; reinterpret_cast<ulonglong2 *>(top)[r] = v; }
+            }
+        }
+        run_b += (unsigned long long)__popcll(mb);
+        run_e += (unsigned long long)__popcll(me);
+    }
+    if (!WRITE && lane == 0) { bsum[g] = run_b; esum[g] = run_e; }
+}
+
+// The sort.  A block's entry c of thread t is number 256 wave + 64 c + lane of the block: a wave walks its 256 in order.
+__device__ __forceinline__ unsigned long long ts_index(int c) {
+    return (unsigned long long)blockIdx.x * TS_BLOCK + (unsigned)((threadIdx.x >> 6) * (WAVE * TS_ITEMS) + c * WAVE + (threadIdx.x & (WAVE - 1)));
+}
+// the digit counts of each wave's 256 entries into cnt[wave][digit] (zeroed here; barriers in front and behind)
+__device__ __forceinline__ void ts_count(const ulonglong2 (&e)[TS_ITEMS], unsigned long long n, int shift, unsigned *cnt) {
+    const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x >> 6;
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < TS_WAVES; j++) cnt[j * TOP_BINS + threadIdx.x] = 0u;
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < TS_ITEMS; c++) {
+        const bool have = ts_index(c) < n;
+        const unsigned digit = (unsigned)(e[c].x >> shift) & (TOP_BINS - 1u);
+        const unsigned long long m = wave_match_digit(digit, have);
+        if (have && lane == __ffsll((long long)m) - 1)
+            __hip_atomic_fetch_add(cnt + wave * TOP_BINS + digit, (unsigned)__popcll(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    __syncthreads();
+}
+// Where entry c goes (n: it does not exist): the wave's base of its digit, which then moves on by the wave's entries
+// with that digit -- the lanes in front of this one with the same digit come first.  Called by the whole wave, c ascending.
+__device__ __forceinline__ unsigned long long ts_rank(const ulonglong2 e, bool have, unsigned long long n, int shift,
+                                                      volatile unsigned long long *mine) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    const unsigned digit = (unsigned)(e.x >> shift) & (TOP_BINS - 1u);
+    const unsigned long long m = wave_match_digit(digit, have);
+    const unsigned long long r = have ? mine[digit] + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull)) : n;
+    wave_lds_sync();                                                // every lane has its base before a leader moves it on
+    if (have && lane == __ffsll((long long)m) - 1) mine[digit] += (unsigned long long)__popcll(m);
+    wave_lds_sync();
+    return r;
+}
+// the last pass's store: ids[r] = the id of rank r, top[r] = its pair (an id is one: nothing is read past the scores)
+__device__ __forceinline__ void ts_store_last(unsigned long long r, unsigned long long id, unsigned long long *ids, pfac_doc_score *top,
+                                              const pfac_doc_score *scores, unsigned long long n_docs) {
+    if (id >= n_docs) return;
+    ids[r] = id;
+    reinterpret_cast<ulonglong2 *>(top)[r] = reinterpret_cast<const ulonglong2 *>(scores)[id];
+}
+
+// bh[digit * n_blocks + block] = the block's entries with that digit
+__global__ void __launch_bounds__(TS_WAVES * WAVE)
+pfac_top_sort_hist_kernel(const ulonglong2 *src, unsigned long long n, int shift, unsigned n_blocks, unsigned long long *bh) {
+    __shared__ unsigned cnt[TS_WAVES * TOP_BINS];
+    ulonglong2 e[TS_ITEMS];
+#pragma unroll
+    for (int c = 0; c < TS_ITEMS; c++) e[c] = ts_index(c) < n ? src[ts_index(c)] : make_ulonglong2(0ull, 0ull);
+    ts_count(e, n, shift, cnt);
+    unsigned sum = 0;
+#pragma unroll
+    for (int j = 0; j < TS_WAVES; j++) sum += cnt[j * TOP_BINS + threadIdx.x];
+    bh[(unsigned long long)threadIdx.x * n_blocks + blockIdx.x] = sum;
+}
+
+// bh holds the exclusive prefixes.  dst != NULL: the entries move to dst; else (the last pass) the ids and the pairs.
+__global__ void __launch_bounds__(TS_WAVES * WAVE)
+pfac_top_sort_scatter_kernel(const ulonglong2 *src, unsigned long long n, int shift, unsigned n_blocks, const unsigned long long *bh,
+                             ulonglong2 *dst, unsigned long long *ids, pfac_doc_score *top, const pfac_doc_score *scores,
+                             unsigned long long n_docs) {
+    __shared__ unsigned cnt[TS_WAVES * TOP_BINS];
+    __shared__ unsigned long long base[TS_WAVES * TOP_BINS];
+    ulonglong2 e[TS_ITEMS];
+#pragma unroll
+    for (int c = 0; c < TS_ITEMS; c++) e[c] = ts_index(c) < n ? src[ts_index(c)] : make_ulonglong2(0ull, 0ull);
+    ts_count(e, n, shift, cnt);
+    unsigned long long acc = bh[(unsigned long long)threadIdx.x * n_blocks + blockIdx.x];
+#pragma unroll
+    for (int j = 0; j < TS_WAVES; j++) { base[j * TOP_BINS + threadIdx.x] = acc; acc += cnt[j * TOP_BINS + threadIdx.x]; }
+    __syncthreads();
+    volatile unsigned long long *mine = base + (threadIdx.x >> 6) * TOP_BINS;     // this wave's bases: only its own lanes touch them
+#pragma unroll
+    for (int c = 0; c < TS_ITEMS; c++) {
+        const unsigned long long r = ts_rank(e[c], ts_index(c) < n, n, shift, mine);
+        if (r < n) {
+            if (dst) dst[r] = e[c];
+            else ts_store_last(r, e[c].y, ids, top, scores, n_docs);
+        }
+    }
+}
+
+// n <= TS_BLOCK entries, ONE workgroup: every pass through LDS, the entries in registers in between.
+__global__ void __launch_bounds__(TS_WAVES * WAVE)
+pfac_top_sort_one_kernel(const ulonglong2 *src, unsigned long long n, unsigned long long *ids, pfac_doc_score *top,
+                         const pfac_doc_score *scores, unsigned long long n_docs) {
+    __shared__ unsigned cnt[TS_WAVES * TOP_BINS];
+    __shared__ unsigned long long base[TS_WAVES * TOP_BINS];
+    __shared__ ulonglong2 buf[TS_BLOCK];
+    __shared__ unsigned wsum[TS_WAVES];
+    const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x >> 6;
+    ulonglong2 e[TS_ITEMS];
+#pragma unroll
+    for (int c = 0; c < TS_ITEMS; c++) e[c] = ts_index(c) < n ? src[ts_index(c)] : make_ulonglong2(0ull, 0ull);
+    volatile unsigned long long *mine = base + wave * TOP_BINS;
+    for (int pass = 0; pass < TOP_PASSES; pass++) {
+        const int shift = pass * TOP_BITS;
+        ts_count(e, n, shift, cnt);
+        unsigned sum = 0;                                           // thread t: the entries with digit t, ...
+#pragma unroll
+        for (int j = 0; j < TS_WAVES; j++) sum += cnt[j * TOP_BINS + threadIdx.x];
+        const unsigned incl = wave_incl_scan(sum);                  // ... and those with a smaller one: across the wave, then the waves
+        if (lane == WAVE - 1) wsum[wave] = incl;
+        __syncthreads();
+        unsigned long long acc = incl - sum;
+#pragma unroll
+        for (int j = 0; j < TS_WAVES; j++) acc += j < wave ? wsum[j] : 0u;
+#pragma unroll
+        for (int j = 0; j < TS_WAVES; j++) { base[j * TOP_BINS + threadIdx.x] = acc; acc += cnt[j * TOP_BINS + threadIdx.x]; }
+        __syncthreads();
+        const bool last = pass == TOP_PASSES - 1;
+#pragma unroll
+        for (int c = 0; c < TS_ITEMS; c++) {
+            const unsigned long long r = ts_rank(e[c], ts_index(c) < n, n, shift, mine);
+            if (r < n) {
+                if (last) ts_store_last(r, e[c].y, ids, top, scores, n_docs);
+                else buf[r] = e[c];
+            }
+        }
+        if (last) break;
+        __syncthreads();
+#pragma unroll
+        for (int c = 0; c < TS_ITEMS; c++) e[c] = ts_index(c) < n ? buf[ts_index(c)] : make_ulonglong2(0ull, 0ull);
+    }
+}
+
+// ---------------------------------------------------------------------------
 // The selected documents' bytes, back to back (pfac_documents_gather): segment k is in[off[ids[k]], off[ids[k] + 1]), at
 // output offset out_off[k] = the sum of the lengths before it.  The replace's shape with the picks taken out:
 //   pfac_ga_count_kernel     one workgroup per 1024 ids: two 8-byte gathers of the offsets per id, the checks (id <
@@ -4590,6 +4924,11 @@ struct Slot {
     PassOut<unsigned long long> gm_out;   // the masks (n_docs of them); scratch of a call that writes to the caller's buffer
     // pfac_documents_scores / pfac_selection_document_scores
     PassOut<pfac_doc_score> sc_out;       // the scores (n_docs of them); scratch of a call that writes to the caller's buffer
+    // pfac_documents_top_scores (its ids are dm_out)
+    DevBuf<unsigned long long> tp_work;   // the select's histograms and its state words
+    DevBuf<ulonglong2> tp_ent;            // PFAC_TOP_RANKED: the sort's two buffers of (key word, id), n_top entries each, ...
+    DevBuf<unsigned long long> tp_bh;     // ... and its digit counts per block (and the total behind them)
+    PassOut<pfac_doc_score> tp_out;       // the winners' pairs
     // pfac_documents_gather
     DevBuf<unsigned long long> ga_x;      // X per block of 64 ids
     PassOut<unsigned char> ga_out;        // the bytes, ...
@@ -6419,6 +6758,135 @@ int pfac_documents_matching_d2h(pfac_ctx *ctx, int slot, uint64_t *host_ids) {
     if (rc) return rc;
     Slot &s = ctx->slots[slot];
     return fetch(ctx, s, s.dm_out, "pfac_documents_matching_d2h", "pfac_documents_matching", host_ids, 0, s.dm_out.n);
+}
+
+// The k best documents: the select (its passes and picks queued back to back, then the ONE copy back: n_top), the
+// compaction, and under PFAC_TOP_RANKED the sort.  The ids are dm_out's -- one pass with the matching calls.
+int pfac_documents_top_scores(pfac_ctx *ctx, int slot, const pfac_doc_score *d_scores, const uint64_t *d_doc_offsets,
+                              uint64_t n_docs, const pfac_score_rule *rule, uint32_t rule_flags, uint64_t k, uint32_t flags,
+                              uint64_t *d_ids_out, uint64_t out_cap, pfac_doc_score *d_top_scores_out, uint64_t *n_top) {
+    const std::string fn = "pfac_documents_top_scores";
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    if (!n_top) return fail(ctx, PFAC_E_ARG, "null argument");
+    *n_top = 0;
+    Slot &s = ctx->slots[slot];
+    s.dm_out.invalidate();
+    s.tp_out.invalidate();
+    const pfac_doc_score *sc;
+    const unsigned long long *off = nullptr;
+    rc = s.sc_out.consume(ctx, fn, "scores of a score pass (n_docs entries)", d_scores, n_docs, &sc);
+    if (rc == PFAC_OK && rule && rule->density_den) {
+        off = reinterpret_cast<const unsigned long long *>(d_doc_offsets);
+        if (!off && !s.doc.done) rc = fail(ctx, PFAC_E_STATE, fn + ": no document offsets for the slot (pfac_slot_doc_offsets)");
+        else if (!off && n_docs + 1 != s.doc.n) rc = fail(ctx, PFAC_E_ARG, fn + ": n_docs differs from the slot's document offsets");
+        else if (!off) off = s.doc.buf.p;
+    }
+    if (rc == PFAC_OK && (((uintptr_t)sc & 15) || ((uintptr_t)off & 7)))
+        rc = fail(ctx, PFAC_E_ARG, fn + ": misaligned buffer (d_scores 16 B, d_doc_offsets 8 B)");
+    if (rc) return rc;
+    if (rule_flags > PFAC_DOCS_INVERT) return fail(ctx, PFAC_E_ARG, fn + ": rule_flags must be 0 or PFAC_DOCS_INVERT");
+    if (flags & ~(PFAC_TOP_BY_COUNT | PFAC_TOP_LOWEST | PFAC_TOP_RANKED))
+        return fail(ctx, PFAC_E_ARG, fn + ": flags outside PFAC_TOP_BY_COUNT | PFAC_TOP_LOWEST | PFAC_TOP_RANKED");
+    if (n_docs >= (1ull << 32)) return fail(ctx, PFAC_E_ARG, fn + ": n_docs must be below 2^32");
+    if (((uintptr_t)d_ids_out & 7) || ((uintptr_t)d_top_scores_out & 15))
+        return fail(ctx, PFAC_E_ARG, fn + ": misaligned buffer (d_ids_out 8 B, d_top_scores_out 16 B)");
+    USE_DEVICE(ctx);
+    // no rule: every document is a candidate
+    const pfac_score_rule r = rule ? *rule : pfac_score_rule{INT64_MIN, INT64_MAX, 0, UINT64_MAX, 0, 0};
+    const unsigned invert = rule ? (unsigned)rule_flags : 0u;
+    uint64_t total = 0;
+    if (n_docs && k) {
+        rc = s.tp_work.ensure(ctx, s.stream, TOP_WORK_WORDS, TOP_WORK_WORDS);
+        if (rc) return rc;
+        unsigned long long *work = s.tp_work.p;
+        HIP_TRY(ctx, hipMemsetAsync(work, 0, TOP_WORK_WORDS * sizeof(unsigned long long), s.stream));
+        const dim3 hgrid((unsigned)std::min<uint64_t>((n_docs + TOP_BINS - 1) / TOP_BINS, 2048)), hblock(TOP_BINS);
+        for (int pass = 0; pass < TOP_PASSES; pass++) {
+            if (off)
+                hipLaunchKernelGGL(pfac_top_hist_kernel<true>, hgrid, hblock, 0, s.stream, sc, (unsigned long long)n_docs, invert, r, off,
+                                   (unsigned)flags, pass, (unsigned long long)k, work);
+            else
+                hipLaunchKernelGGL(pfac_top_hist_kernel<false>, hgrid, hblock, 0, s.stream, sc, (unsigned long long)n_docs, invert, r, off,
+                                   (unsigned)flags, pass, (unsigned long long)k, work);
+        }
+        hipLaunchKernelGGL(pfac_top_final_kernel, dim3(1), dim3(WAVE), 0, s.stream, work, (unsigned long long)k);
+        rc = pass_words(ctx, s, work + TOP_NCAND, 1);           // (written by the second pass: the first histograms' sum)
+        if (rc) return rc;
+        total = std::min<uint64_t>(k, host_u64(s, H_PASS));
+    }
+    *n_top = total;
+    if ((d_ids_out || d_top_scores_out) && total > out_cap)
+        return fail(ctx, PFAC_E_OVERFLOW, fn + ": " + std::to_string(total) + " documents, out_cap is " + std::to_string(out_cap));
+    unsigned long long *ids;
+    pfac_doc_score *top;
+    rc = s.dm_out.bind(ctx, s.stream, d_ids_out, total, total + total / 8 + 4096, &ids);
+    if (rc) return rc;
+    rc = s.tp_out.bind(ctx, s.stream, d_top_scores_out, total, total + total / 8 + 4096, &top);
+    if (rc) return rc;
+    if (total) {
+        const bool ranked = (flags & PFAC_TOP_RANKED) != 0;
+        const unsigned n_groups = (unsigned)((n_docs + DM_BLOCKS * WAVE - 1) / (DM_BLOCKS * WAVE));
+        const unsigned n_blocks = (unsigned)((total + TS_BLOCK - 1) / TS_BLOCK);
+        rc = ensure_gsum(ctx, s, 2 * n_groups + 1);          // the group prefixes of the keys in front of T and their total, the same of the keys equal to T
+        if (rc) return rc;
+        if (ranked) {
+            rc = s.tp_ent.ensure(ctx, s.stream, 2 * total, 2 * (total + total / 8 + 4096));
+            if (rc) return rc;
+        }
+        if (ranked && total > TS_BLOCK) {
+            rc = s.tp_bh.ensure(ctx, s.stream, (uint64_t)TOP_BINS * n_blocks + 1, (uint64_t)TOP_BINS * quarter_more(n_blocks) + 1);
+            if (rc) return rc;
+        }
+        const unsigned long long *st = s.tp_work.p;
+        const bool one = total <= TS_BLOCK;                      // the sort in one workgroup
+        unsigned long long *bsum = s.gsum.p, *esum = s.gsum.p + n_groups + 1;
+        ulonglong2 *ent = ranked ? s.tp_ent.p : nullptr;
+        const dim3 grid((n_groups + 3) / 4), block(256);
+        if (off) {
+            hipLaunchKernelGGL((pfac_top_compact_kernel<false, true>), grid, block, 0, s.stream, sc, (unsigned long long)n_docs, invert, r, off,
+                               (unsigned)flags, st, bsum, esum, n_groups, 0ull, (unsigned long long *)nullptr, (pfac_doc_score *)nullptr, (ulonglong2 *)nullptr);
+        } else {
+            hipLaunchKernelGGL((pfac_top_compact_kernel<false, false>), grid, block, 0, s.stream, sc, (unsigned long long)n_docs, invert, r, off,
+                               (unsigned)flags, st, bsum, esum, n_groups, 0ull, (unsigned long long *)nullptr, (pfac_doc_score *)nullptr, (ulonglong2 *)nullptr);
+        }
+        hipLaunchKernelGGL(pfac_scan_groups_kernel, dim3(1), dim3(1024), 0, s.stream, bsum, n_groups);
+        hipLaunchKernelGGL(pfac_scan_groups_kernel, dim3(1), dim3(1024), 0, s.stream, esum, n_groups);
+        if (off) {
+            hipLaunchKernelGGL((pfac_top_compact_kernel<true, true>), grid, block, 0, s.stream, sc, (unsigned long long)n_docs, invert, r, off,
+                               (unsigned)flags, st, bsum, esum, n_groups, (unsigned long long)total, ids, top, ent);
+        } else {
+            hipLaunchKernelGGL((pfac_top_compact_kernel<true, false>), grid, block, 0, s.stream, sc, (unsigned long long)n_docs, invert, r, off,
+                               (unsigned)flags, st, bsum, esum, n_groups, (unsigned long long)total, ids, top, ent);
+        }
+        if (ranked && one) {
+            hipLaunchKernelGGL(pfac_top_sort_one_kernel, dim3(1), dim3(TS_WAVES * WAVE), 0, s.stream, (const ulonglong2 *)ent,
+                               (unsigned long long)total, ids, top, sc, (unsigned long long)n_docs);
+        } else if (ranked) {
+            ulonglong2 *a = ent, *b = ent + total;
+            for (int pass = 0; pass < TOP_PASSES; pass++) {
+                const bool last = pass == TOP_PASSES - 1;
+                hipLaunchKernelGGL(pfac_top_sort_hist_kernel, dim3(n_blocks), dim3(TS_WAVES * WAVE), 0, s.stream, (const ulonglong2 *)a,
+                                   (unsigned long long)total, pass * TOP_BITS, n_blocks, s.tp_bh.p);
+                hipLaunchKernelGGL(pfac_scan_groups_kernel, dim3(1), dim3(1024), 0, s.stream, s.tp_bh.p, (unsigned)TOP_BINS * n_blocks);
+                hipLaunchKernelGGL(pfac_top_sort_scatter_kernel, dim3(n_blocks), dim3(TS_WAVES * WAVE), 0, s.stream, (const ulonglong2 *)a,
+                                   (unsigned long long)total, pass * TOP_BITS, n_blocks, (const unsigned long long *)s.tp_bh.p,
+                                   last ? (ulonglong2 *)nullptr : b, ids, top, sc, (unsigned long long)n_docs);
+                std::swap(a, b);
+            }
+        }
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    s.dm_out.commit(total, !d_ids_out);
+    s.tp_out.commit(total, !d_top_scores_out);
+    return PFAC_OK;
+}
+
+int pfac_documents_top_scores_d2h(pfac_ctx *ctx, int slot, pfac_doc_score *host, uint64_t first, uint64_t n) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    Slot &s = ctx->slots[slot];
+    return fetch(ctx, s, s.tp_out, "pfac_documents_top_scores_d2h", "pfac_documents_top_scores", host, first, n);
 }
 
 // The two gathers: the plain one (fmt NULL, or a format that asks for nothing: the plain kernels) and the one with

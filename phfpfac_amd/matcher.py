@@ -17,6 +17,7 @@ from ._ffi import (PFAC_COUNT_ACCUMULATE, PFAC_DOCS_INVERT, PFAC_E_OVERFLOW, PFA
                    hip_lib)
 from ._ffi import (PFAC_LINE_CONTEXT_SEP, PFAC_LINE_MAX_GROUP_SEP, PFAC_LINE_NUMBER, PFAC_LINE_OFFSET, PFAC_LINE_SEP_FIRST,
                    PFAC_LINE_TERMINATE, CDocScore, CLineFormat, CScoreRule)
+from ._ffi import PFAC_TOP_BY_COUNT, PFAC_TOP_LOWEST, PFAC_TOP_RANKED
 from .table import RECORD_DTYPE, SCORE_DTYPE, TEMPLATE_PLAIN, PfacTable, redaction_table, replacement_table, template_table, _state_lengths
 
 
@@ -923,6 +924,71 @@ class GpuMatcher:
         out_bytes = self.gather_documents(n_docs, n, int(buf.size), slot=slot)
         return (self.gathered_to_host(out_bytes, slot), self.gathered_offsets_to_host(n, slot),
                 self.matching_documents_to_host(n, slot))
+
+    # -- rank: the k best documents by score or count -----------------------
+    def top_documents(self, n_docs: int, k: int, by: str = "score", lowest: bool = False, ranked: bool = True, min_score=None,
+                      max_score=None, min_count=None, max_count=None, density=None, invert: bool = False, d_scores=None,
+                      d_doc_offsets=None, d_out=None, out_cap: int = 0, d_top_scores=None, slot: int = 0) -> int:
+        """The ``k`` best documents, on the GPU (``pfac_documents_top_scores``): by ``"score"`` (signed) or by
+        ``"count"``, the largest first (``lowest``: the smallest), ties to the smaller id.  With ``ranked`` the ids come
+        in rank order, else the same ids ascending.  The windows, ``density`` and ``invert`` are the rule of
+        ``matching_documents_scored`` and choose the candidates; with none of them every document is one
+        (``min_count=1``: matched documents only).  ``d_scores`` None = the slot-owned scores of the slot's last score
+        pass.  The ids go where ``matching_documents`` puts them (``matching_documents_to_host``,
+        ``gather_documents(d_ids=None)``), the winners' pairs to ``d_top_scores`` or a slot-owned buffer
+        (``top_scores_to_host``); both caller's buffers hold ``out_cap`` entries.  Returns min(k, candidates); a too
+        small ``out_cap`` raises PfacError(PFAC_E_OVERFLOW) whose ``n_top`` attribute holds the exact count."""
+        if by not in ("score", "count"):
+            raise ValueError('by is "score" or "count"')
+        if k < 0:
+            raise ValueError("k must not be negative")
+        flags = (PFAC_TOP_BY_COUNT if by == "count" else 0) | (PFAC_TOP_LOWEST if lowest else 0) | (PFAC_TOP_RANKED if ranked else 0)
+        ruled = not (min_score is None and max_score is None and min_count is None and max_count is None and density is None
+                     and not invert)
+        num, den = (0, 0) if density is None else (int(density[0]), int(density[1]))
+        if density is not None and den <= 0:
+            raise ValueError("the density's denominator must be positive")
+        rule = CScoreRule(-(2 ** 63) if min_score is None else int(min_score), 2 ** 63 - 1 if max_score is None else int(max_score),
+                          0 if min_count is None else int(min_count), 2 ** 64 - 1 if max_count is None else int(max_count), num, den)
+        n = C.c_uint64(0)
+        rc = self._L.pfac_documents_top_scores(self._ctx, slot, _ptr(d_scores), _ptr(d_doc_offsets), int(n_docs),
+                                               C.byref(rule) if ruled else None, PFAC_DOCS_INVERT if invert else 0,
+                                               min(int(k), 2 ** 64 - 1), flags, _ptr(d_out), int(out_cap), _ptr(d_top_scores),
+                                               C.byref(n))
+        return self._counted(rc, n, "n_top")
+
+    def top_scores_to_host(self, n: int, slot: int = 0, first: int = 0) -> np.ndarray:
+        """Pairs [first, first + n) of the slot's last ``top_documents`` into its slot-owned buffer, in the order of
+        its ids: ``SCORE_DTYPE[n]``."""
+        return self._to_host(slot, lambda p: self._L.pfac_documents_top_scores_d2h(self._ctx, slot, p, int(first), int(n)),
+                             (n, SCORE_DTYPE))
+
+    def top_scored_documents(self, docs, k: int, by: str = "score", lowest: bool = False, ranked: bool = True, min_score=None,
+                             max_score=None, min_count=None, max_count=None, density=None, invert: bool = False,
+                             whole_words=False, slot: int = 0, spans: bool = False, line_match: bool = False,
+                             non_overlapping: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+        """The ``k`` best documents of a batch (``docs`` as ``scan_documents`` takes it): scan, the score pass and
+        ``top_documents`` on the device.  Returns (ids uint64[n], scores ``SCORE_DTYPE[n]``), n = min(k, candidates)."""
+        _, n_docs = self._scan_docs(docs, slot, whole_words, spans, line_match)
+        self._score_pass(n_docs, slot, non_overlapping)
+        n = self.top_documents(n_docs, k, by, lowest, ranked, min_score, max_score, min_count, max_count, density, invert, slot=slot)
+        return self.matching_documents_to_host(n, slot), self.top_scores_to_host(n, slot)
+
+    def top_lines(self, data, k: int, by: str = "score", lowest: bool = False, ranked: bool = True, min_score=None, max_score=None,
+                  min_count=None, max_count=None, density=None, invert: bool = False, delimiter=b"\n", whole_words=False,
+                  slot: int = 0, spans: bool = False, line_match: bool = False,
+                  non_overlapping: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """The ``k`` best lines of ``data``, as bytes -- "the 100 most suspicious lines of this log": scan, split, the
+        score pass, ``top_documents`` and the gather on the device; neither the scores of all lines nor the ids travel.
+        Returns (out uint8[out_bytes], out_offsets uint64[n + 1], ids uint64[n], scores ``SCORE_DTYPE[n]``): the
+        lines back to back in the order of the ids (rank order with ``ranked``)."""
+        buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data.view(np.uint8).ravel()
+        _, n_docs = self._scan_lines(buf, delimiter, slot, whole_words, fetch_offsets=False, spans=spans, line_match=line_match)
+        self._score_pass(n_docs, slot, non_overlapping)
+        n = self.top_documents(n_docs, k, by, lowest, ranked, min_score, max_score, min_count, max_count, density, invert, slot=slot)
+        out_bytes = self.gather_documents(n_docs, n, int(buf.size), slot=slot)
+        return (self.gathered_to_host(out_bytes, slot), self.gathered_offsets_to_host(n, slot),
+                self.matching_documents_to_host(n, slot), self.top_scores_to_host(n, slot))
 
     # -- leftmost-longest non-overlapping matches ---------------------------
     def select_leftmost_longest(self, entry: int = 0, d_out=None, out_cap: int = 0, slot: int = 0,
