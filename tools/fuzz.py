@@ -26,6 +26,13 @@ usage: fuzz.py [seconds] [seed]
                                             templates and match extraction per document and over the whole stream, the plain
                                             replace on the same selection -- exact and case-folded tables, lines cut on the
                                             device or explicit offsets, every step against the host references over the CPU
+                                            oracle's records.  One child process per case under a time limit, as `guard`
+       fuzz.py rank [seconds] [seed]        the passes behind those instead (tests/rankfuzz.py): document scores behind a drawn
+                                            filter (none, whole words, spans), the score rule and the gather, three top draws
+                                            and the formatted gather of a ranked one, the context path (segment, matching
+                                            documents with context, the formatted gather under context_sep), the selection's
+                                            scores and their rank, every fourth case again into the caller's buffers -- document
+                                            counts from 1 to about 40 000, every step against the host references over the CPU
                                             oracle's records.  One child process per case under a time limit, as `guard`"""
 import os, sys, tempfile, time
 os.environ.setdefault("PFAC_ENABLE_KNOBS", "1")     # tuning / test knobs of libpfac_hip.so are opt-in
@@ -211,6 +218,43 @@ if len(sys.argv) > 1 and sys.argv[1] == "late":
             t_last = time.time(); print(f"  ... {cases} cases, {recs} records and {nbytes} bytes compared, {t_last - t0:.0f} s", flush=True)
     print(f"late fuzz ok: {cases} cases in {time.time() - t0:.0f} s (seed {seed}), {recs} records and {nbytes} bytes compared (scan, "
           f"span filter, group masks + gather, selections, templated replace + extraction, plain replace)")
+    print("cases per knob set: " + ", ".join(f"{k} {v}" for k, v in sorted(per_knob.items())))
+    raise SystemExit(0)
+if len(sys.argv) > 1 and sys.argv[1] == "rank-case":          # one case on the GPU (the child of `rank` below)
+    import rankfuzz as RF
+    case_seed = int(sys.argv[2])
+    c = RF.RankCase(case_seed, RF.KNOBS[int(np.random.default_rng([case_seed, 0x4B4E4F42]).integers(0, len(RF.KNOBS)))])
+    for k in set(KNOB_NAMES) | set(RF.KNOB_NAMES): os.environ.pop(k, None)
+    os.environ.update(c.knobs)
+    try:
+        n_rec, n_doc, n_bytes = RF.run_rank_case(lambda: GpuMatcher(0, 1), c, tempfile.mkdtemp())
+    except AssertionError as e:
+        raise SystemExit(f"MISMATCH: {e}")
+    print(f"{n_rec} {n_doc} {n_bytes} {knob_label(c.knobs)}")
+    raise SystemExit(0)
+if len(sys.argv) > 1 and sys.argv[1] == "rank":
+    import subprocess
+    import rankfuzz as RF
+    seconds = float(sys.argv[2]) if len(sys.argv) > 2 else 60.0
+    seed = int(sys.argv[3]) if len(sys.argv) > 3 else 1
+    STEP_LIMIT = 120                                           # seconds one case may take
+    t0 = t_last = time.time(); cases = 0; recs = 0; ndocs = 0; nbytes = 0; per_knob = {}
+    while time.time() - t0 < seconds:
+        case_seed = (seed << 32) + len(RF.SEEDS) + cases       # (beyond the suite's seeds)
+        try:                                                   # (this process never opens the GPU: every case is a fresh child)
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "rank-case", str(case_seed)], capture_output=True,
+                               text=True, timeout=STEP_LIMIT)
+        except subprocess.TimeoutExpired:
+            raise SystemExit(f"TIME LIMIT: case {cases} (fuzz.py rank-case {case_seed}) ran over {STEP_LIMIT} s; stopping")
+        if r.returncode:
+            raise SystemExit(f"FAILED case {cases} (fuzz.py rank-case {case_seed}), exit status {r.returncode}; stopping\n"
+                             + r.stdout[-2000:] + r.stderr[-4000:])
+        n, d, b, label = r.stdout.strip().split("\n")[-1].split(" ", 3)
+        recs += int(n); ndocs += int(d); nbytes += int(b); per_knob[label] = per_knob.get(label, 0) + 1; cases += 1
+        if time.time() - t_last > 30:
+            t_last = time.time(); print(f"  ... {cases} cases, {recs} records, {ndocs} document entries and {nbytes} bytes compared, {t_last - t0:.0f} s", flush=True)
+    print(f"rank fuzz ok: {cases} cases in {time.time() - t0:.0f} s (seed {seed}), {recs} records, {ndocs} document entries and {nbytes} "
+          f"bytes compared (scan, filter, scores x2 + rule + gather, three ranks + formatted gather, context path, selection scores)")
     print("cases per knob set: " + ", ".join(f"{k} {v}" for k, v in sorted(per_knob.items())))
     raise SystemExit(0)
 seconds = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
