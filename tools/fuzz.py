@@ -10,6 +10,12 @@ usage: fuzz.py [seconds] [seed]
                                             (plan(seed, counts=True): counts accumulated and fetched late, count knobs),
                                             and with the line path as well (plan(seed, lines=True): the delimiter split,
                                             matching documents with context lines, and the gather of their bytes)
+       fuzz.py verdict [seconds] [seed]     random VERDICT sessions instead (tests/verdictsession.py): one context per plan driven
+                                            through about 160 calls of the pattern groups, the document scores, the rank and both
+                                            gathers in random order, results fetched late behind scans, uploads, filters, reserves,
+                                            new offsets and stream changes -- plan(seed) for seeds past the suite's.  One child
+                                            process per plan under a time limit; the first child that fails, ends by a signal or
+                                            runs over stops the tool
        fuzz.py class [seconds] [seed]       character-class and escaped-file cases instead (tests/classfuzz.py), against the
                                             brute-force matcher oracle/charclass_oracle.py and the escape-aware CPU oracle
        fuzz.py guard [seconds] [seed]       the capacity contract instead (tests/heapguard.py): the scan of random cases into
@@ -66,6 +72,44 @@ if len(sys.argv) > 1 and sys.argv[1] == "session":
           f"documented errors, {tot['filters']} whole-word filters, {tot['counts']} counts, {tot['splits']} splits, {tot['matchings']} matching calls and {tot['gathers']} "
           f"gathers, {tot['compared']} records and bytes and {tot['ids']} document ids and offsets compared")
     print(f"record widths {sorted(widths)}, staging layouts (buffers, records) {sorted(staging)}, count regimes (overlay, regime) {sorted(regimes)}")
+    raise SystemExit(0)
+if len(sys.argv) > 1 and sys.argv[1] == "verdict-plan":        # one plan on the GPU (the child of `verdict` below)
+    import verdictsession as V
+    plan_seed = int(sys.argv[2])
+    with GpuMatcher(0, V.N_SLOTS) as g:
+        try:
+            st = V.run(g, V.plan(plan_seed), V.Model(), seed=plan_seed)
+        except AssertionError as e:
+            raise SystemExit(f"MISMATCH: {e}")
+    print(f"{st['ops']} {st['verdict']} {st['errors']} {st['docs']} {st['bytes']} " + ",".join(f"{r}:{n}" for r, n in st["rules"].items()))
+    raise SystemExit(0)
+if len(sys.argv) > 1 and sys.argv[1] == "verdict":
+    import subprocess
+    import verdictsession as V
+    seconds = float(sys.argv[2]) if len(sys.argv) > 2 else 60.0
+    seed = int(sys.argv[3]) if len(sys.argv) > 3 else 1
+    STEP_LIMIT = 300                                           # seconds one plan may take (the references of a 130-tile input, 160 calls)
+    t0 = t_last = time.time(); plans = 0; tot = [0, 0, 0, 0, 0]; rules = {r: 0 for r in V.RULES}
+    while time.time() - t0 < seconds:
+        plan_seed = (seed << 20) + len(V.SEEDS) + plans        # (beyond the suite's seeds)
+        try:                                                   # (this process never opens the GPU: every plan is a fresh child)
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "verdict-plan", str(plan_seed)], capture_output=True,
+                               text=True, timeout=STEP_LIMIT)
+        except subprocess.TimeoutExpired:
+            raise SystemExit(f"TIME LIMIT: plan {plans} (fuzz.py verdict-plan {plan_seed}) ran over {STEP_LIMIT} s; stopping")
+        if r.returncode:
+            how = f"signal {-r.returncode}" if r.returncode < 0 else f"exit status {r.returncode}"
+            raise SystemExit(f"FAILED plan {plans} (fuzz.py verdict-plan {plan_seed}), {how}; stopping\n" + r.stdout[-2000:] + r.stderr[-4000:])
+        *nums, seen = r.stdout.strip().split("\n")[-1].split(" ")
+        tot = [a + int(b) for a, b in zip(tot, nums)]
+        for item in seen.split(","):
+            rules[item.split(":")[0]] += int(item.split(":")[1])
+        plans += 1
+        if time.time() - t_last > 30:
+            t_last = time.time(); print(f"  ... {plans} plans, {tot[0]} operations, {t_last - t0:.0f} s", flush=True)
+    print(f"verdict fuzz ok: {plans} plans in {time.time() - t0:.0f} s (seed {seed}), {tot[0]} operations of which {tot[1]} verdict operations and "
+          f"{tot[2]} documented errors, {tot[3]} document entries and {tot[4]} bytes compared")
+    print("operations in which a rule decided the outcome: " + ", ".join(f"{r} {n}" for r, n in rules.items()))
     raise SystemExit(0)
 if len(sys.argv) > 1 and sys.argv[1] == "class":
     import classfuzz as F
