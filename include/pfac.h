@@ -831,6 +831,65 @@ int pfac_documents_top_scores(pfac_ctx *ctx, int slot, const pfac_doc_score *d_s
 /* D2H of pairs [first, first + n) of the slot-owned result of the last pfac_documents_top_scores.  Asynchronous on the
  * slot's stream; pfac_slot_sync completes it.  first + n > *n_top gives PFAC_E_ARG; n == 0 does nothing. */
 int pfac_documents_top_scores_d2h(pfac_ctx *ctx, int slot, pfac_doc_score *host, uint64_t first, uint64_t n);
+/* Term counts per document: WHICH final states each document holds and how often -- the document-term matrix (the
+ * bag-of-words vector of every line under a dictionary) as the three arrays of a CSR matrix, which
+ * torch.sparse_csr_tensor takes as they are.  The input is a record array that is already cut per document: document d
+ * owns d_sel[d_doc_first[d] .. d_doc_first[d + 1]); positions are not read.
+ *   d_sel, d_doc_first  both non-NULL = any device arrays, 8-B aligned: the caller's output of pfac_records_segment or of
+ *                  the per-document selection; d_doc_first has n_docs + 1 entries and d_sel holds d_doc_first[n_docs]
+ *                  records (that one entry is read back first, to size the launch).  Both NULL, flags 0 = the
+ *                  slot-owned records and doc_first of the slot's last pfac_records_segment (PFAC_E_STATE: none, it
+ *                  went to the caller's buffers, or it was cut with an earlier table).  Both NULL,
+ *                  PFAC_TERMS_SELECTION = the slot-owned picks and doc_first of the slot's last
+ *                  pfac_records_leftmost_longest_documents, under the rules of pfac_selection_count_states' d_sel
+ *                  (PFAC_E_STATE: no such selection since the slot's last scan, one made with an earlier table, or one
+ *                  that went to the caller's buffers).  Both NULL with an n_docs that is not that call's gives
+ *                  PFAC_E_ARG; so does one NULL and one not.
+ *   n_docs < 2^32, and the record count N = d_doc_first[n_docs] < 2^32 (every count fits 32 bits), else PFAC_E_ARG
+ *   result         let U be the distinct (d, state) pairs over all records, in (d, state) order: *n_terms = |U|,
+ *                  states[j] and counts[j] are the state and the multiplicity of the j-th pair, row_ptr[d] = the pairs
+ *                  whose document is < d (row_ptr[0] = 0, row_ptr[n_docs] = *n_terms).  Within a document the states
+ *                  strictly ascend; an empty or unmatched document has row_ptr[d + 1] == row_ptr[d].  A state is a
+ *                  final state, as in pfac_records_count_states: the host turns states into pattern ids
+ *   d_row_ptr_out  NULL = a slot-owned buffer grown to fit; else a device pointer, 8-B aligned, n_docs + 1 entries
+ *   d_states_out, d_counts_out  each NULL = a slot-owned buffer grown to fit; else device pointers, 4-B aligned,
+ *                  out_cap entries each
+ * Checked on the device, before anything reaches a caller's buffer, else PFAC_E_ARG: d_doc_first[0] == 0, d_doc_first
+ * does not decrease, every state is below num_final of the uploaded table.  PFAC_E_STATE (no table; a slot-owned input
+ * that is missing, stale or from an earlier table) comes before PFAC_E_ARG (misaligned buffers, n_docs >= 2^32,
+ * N >= 2^32, flags outside 0..1).  PFAC_E_OVERFLOW with *n_terms exact when out_cap < *n_terms and either of the two
+ * entry arrays is the caller's.  Every error leaves every caller's buffer of the call untouched, d_row_ptr_out
+ * included.  Nothing at or past *n_terms is written in the entry arrays and nothing at or past n_docs + 1 in row_ptr:
+ * buffers of exactly (n_docs + 1) x 8, *n_terms x 4 and *n_terms x 4 bytes are enough.  n_docs == 0 writes the single
+ * row_ptr[0] = 0; N == 0 writes n_docs + 1 zeros and no entries.
+ * A pass of its own, with the lifetime rule of pfac_segment_d2h: it discards no other pass's result and is discarded by
+ * none; a failed call discards its own slot-owned result.  Returns once *n_terms is known (one small copy back: the
+ * total and the error word); the writes complete on the slot's stream.  The same call on the same input gives the same
+ * bytes.  It reads neither the input bytes nor the record heap.
+ * Kernels: (1) one lane per record, a wave per 256 records: the record's document by a search in d_doc_first bounded by
+ * its chunk's first and last record, the three checks, and the 8-byte key doc << sbits | state with sbits =
+ * bit_width(num_final - 1) -- packed, so that (2) a stable LSD radix sort of the keys runs ceil((sbits +
+ * bit_width(n_docs - 1)) / 8) passes of 8 bits and no more; ranks inside a wave from ballots; a workgroup takes as
+ * many consecutive chunks of PFAC_TERMS_SORT_BLOCK keys per histogram row as keep a pass within PFAC_TERMS_SORT_ROWS
+ * workgroups, and the prefix of a pass is one workgroup per digit over that digit's row; up to PFAC_TERMS_SORT_BLOCK
+ * keys are sorted by one workgroup in LDS.  The key is document-major: document d's records still lie in
+ * [doc_first[d], doc_first[d + 1]).
+ * (3) Entry i is a head iff i == 0 or key[i] != key[i - 1]: heads per block of 64 and per group of 4096, the group
+ * prefix, and every block's 64-bit head ballot kept.  (4) Behind the host's overflow check every head of rank j stores
+ * states[j] and its index; counts[j] is the difference of two neighbouring head indices, and row_ptr[d] is three loads
+ * and a popcount at entry doc_first[d] -- no loop runs as long as a run of equal records or of empty documents. */
+#define PFAC_TERMS_SELECTION 1u   /* d_sel == d_doc_first == NULL means the slot's per-document selection, not its segment result */
+#define PFAC_TERMS_SORT_BLOCK 1024u   /* keys per chunk of the sort, and the most that one workgroup sorts alone */
+#define PFAC_TERMS_SORT_ROWS  4096u   /* the most workgroups (histogram rows per digit) of one sort pass */
+int pfac_documents_term_counts(pfac_ctx *ctx, int slot, const pfac_record *d_sel, const uint64_t *d_doc_first,
+                               uint64_t n_docs, uint32_t flags,
+                               uint64_t *d_row_ptr_out, uint32_t *d_states_out, uint32_t *d_counts_out, uint64_t out_cap,
+                               uint64_t *n_terms);
+/* D2H of the slot-owned result of the last pfac_documents_term_counts: n_docs + 1 row_ptr entries, *n_terms states and
+ * *n_terms counts.  Any of the three may be NULL (it must be where that output was the caller's: PFAC_E_STATE else).
+ * Asynchronous on the slot's stream; pfac_slot_sync completes it. */
+int pfac_documents_term_counts_d2h(pfac_ctx *ctx, int slot, uint64_t *host_row_ptr, uint32_t *host_states,
+                                   uint32_t *host_counts);
 
 /* Whole-word filter: drops, IN PLACE, the records of the slot's last finished scan that split a word, so that every
  * consumer of the scan (the fetches, the text emitter, the checksum, the segment pass, both selections and both

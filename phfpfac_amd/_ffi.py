@@ -46,6 +46,9 @@ PFAC_TOP_BY_COUNT = 1       # pfac_documents_top_scores: key = count[d] (default
 PFAC_TOP_LOWEST = 2         # ... the k smallest keys instead of the k largest
 PFAC_TOP_RANKED = 4         # ... ids in rank order (default: the same ids, ascending)
 PFAC_TOP_SORT_BLOCK = 1024  # ... entries per workgroup of the ranked sort
+PFAC_TERMS_SELECTION = 1    # pfac_documents_term_counts: NULL inputs mean the slot's per-document selection
+PFAC_TERMS_SORT_BLOCK = 1024    # ... keys per chunk of its sort, and the most that one workgroup sorts alone
+PFAC_TERMS_SORT_ROWS = 4096     # ... the most workgroups of one sort pass
 
 _STATUS_NAMES = {
     0: "PFAC_OK", -1: "PFAC_E_ARG", -2: "PFAC_E_IO", -3: "PFAC_E_PATTERN", -4: "PFAC_E_NOMEM",
@@ -146,6 +149,7 @@ HIP_SYMBOLS = (
     "pfac_table_set_state_weights", "pfac_documents_scores", "pfac_selection_document_scores", "pfac_document_scores_d2h",
     "pfac_documents_matching_scores",
     "pfac_documents_top_scores", "pfac_documents_top_scores_d2h",
+    "pfac_documents_term_counts", "pfac_documents_term_counts_d2h",
 )
 
 _host = None
@@ -309,6 +313,8 @@ def hip_lib() -> C.CDLL:
         L.pfac_documents_top_scores.argtypes = [vp, i, vp, vp, u64, C.POINTER(CScoreRule), C.c_uint32, u64, C.c_uint32, vp, u64, vp,
                                                 C.POINTER(u64)]
         L.pfac_documents_top_scores_d2h.argtypes = [vp, i, vp, u64, u64]
+        L.pfac_documents_term_counts.argtypes = [vp, i, vp, vp, u64, C.c_uint32, vp, vp, vp, u64, C.POINTER(u64)]
+        L.pfac_documents_term_counts_d2h.argtypes = [vp, i, vp, vp, vp]
         L.pfac_table_set_state_spans.argtypes = [vp, vp, u64]
         L.pfac_records_filter_spans.argtypes = [vp, i, vp, vp, i, C.c_uint32, vp, u64, C.POINTER(u64)]
         _hip = L

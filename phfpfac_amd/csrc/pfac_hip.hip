@@ -4415,6 +4415,288 @@ pfac_top_sort_one_kernel(const ulonglong2 *src, unsigned long long n, unsigned l
 }
 
 // ---------------------------------------------------------------------------
+// Term counts per document (pfac_documents_term_counts): the distinct (document, state) pairs of a record array that is
+// already cut per document, with their multiplicities, as the three arrays of a CSR matrix.
+//   pfac_tc_key_kernel       one lane per record, a wave per SS_RANGE records as in pfac_sel_scores_kernel: the record's
+//                            document by the same bounded searches, key = doc << sbits | state (8 bytes, no payload),
+//                            and the three checks (first[0] == 0, no decrease, every state below num_final) into one
+//                            word.  Behind a failed check the keys are garbage in bounds and the host discards them.
+//   the sort                 a stable LSD radix sort of the keys over the passes the host names (ceil of the key's bits
+//                            / 8): siblings of the ranked sort's kernels over 8-byte entries, with the ballot ranks of
+//                            ts_rank (wave_match_digit is shared, ts_count and ts_rank are not touched).  Per pass:
+//                            pfac_tc_sort_hist_kernel (a workgroup takes `chunks` consecutive chunks of TC_BLOCK keys
+//                            per histogram row: PFAC_TERMS_SORT_ROWS workgroups at most), pfac_tc_sort_rows_kernel (the
+//                            prefix, one workgroup per digit over its row) and pfac_tc_sort_scatter_kernel.
+//                            n <= TC_BLOCK: pfac_tc_sort_one_kernel, one workgroup, LDS.
+//   pfac_tc_heads_kernel     entry i is a head iff i == 0 or key[i] != key[i - 1].  The compaction's shape: a wave per
+//                            group of DM_BLOCKS blocks of 64 entries; kept per block: its 64-bit head ballot and the
+//                            heads in front of it in its group; per group the sum, for pfac_scan_groups_kernel.
+//   pfac_tc_write_kernel     behind the host's overflow check: the head of rank j stores states[j] = key & mask and its
+//                            index into scratch, hidx[j] (hidx[n_terms] = n)
+//   pfac_tc_counts_kernel    counts[j] = hidx[j + 1] - hidx[j]: no loop over a run of equal records
+//   pfac_tc_rowptr_kernel    one lane per document: the sort keeps document d's records in [first[d], first[d + 1]), so
+//                            row_ptr[d] = the heads in front of entry first[d] = group prefix + block prefix + a
+//                            popcount of the block's ballot below that bit: no loop over a run of empty documents
+constexpr int TC_BLOCK = TS_BLOCK;                                  // entries per chunk: wave w owns [256 w, 256 w + 256) of it
+static_assert(TC_BLOCK == PFAC_TERMS_SORT_BLOCK, "the header names the sort's chunk size");
+#define GRID_THREAD ((unsigned long long)blockIdx.x * blockDim.x + threadIdx.x)        // (as the document kernels define them)
+#define GRID_THREADS ((unsigned long long)gridDim.x * blockDim.x)
+
+__global__ void __launch_bounds__(256)
+pfac_tc_key_kernel(const pfac_record *sel, unsigned long long n, const unsigned long long *first, unsigned long long n_docs,
+                   unsigned num_final, unsigned sbits, unsigned long long *keys, unsigned long long *bad_out) {
+    bool bad = false;
+    for (unsigned long long d = GRID_THREAD; d < n_docs; d += GRID_THREADS) bad = bad || first[d] > first[d + 1];
+    if (GRID_THREAD == 0) bad = bad || first[0] != 0ull || first[n_docs] != n;
+    const int lane = threadIdx.x & (WAVE - 1);
+    const unsigned long long p0 = ((unsigned long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * SS_RANGE;
+    if (p0 < n && n_docs) {                                     // (wave-uniform)
+        const unsigned long long p1 = min(p0 + SS_RANGE, n);
+        unsigned long long dlo = 0;
+        for (unsigned long long c0 = p0; c0 < p1; c0 += WAVE) {
+            const unsigned long long i = c0 + (unsigned)lane;
+            const bool have = i < p1;
+            dlo = doc_of(first, dlo, n_docs - 1, c0);
+            const unsigned long long dhi = doc_of(first, dlo, n_docs - 1, min(c0 + (WAVE - 1), p1 - 1));
+            const unsigned st = have ? sel[i].state : 0u;
+            const bool known = st < num_final;
+            bad = bad || !known;
+            if (have) keys[i] = doc_of(first, dlo, dhi, i) << sbits | (known ? st : 0u);
+        }
+    }
+    if (bad) bad_out[0] = 1ull;
+}
+
+// entry c of this thread in chunk `chunk`
+__device__ __forceinline__ unsigned long long tc_index(unsigned long long chunk, int c) {
+    return chunk * TC_BLOCK + (unsigned)((threadIdx.x >> 6) * (WAVE * TS_ITEMS) + c * WAVE + (threadIdx.x & (WAVE - 1)));
+}
+__device__ __forceinline__ void tc_load(unsigned long long (&e)[TS_ITEMS], const unsigned long long *src, unsigned long long chunk,
+                                        unsigned long long n) {
+#pragma unroll
+    for (int c = 0; c < TS_ITEMS; c++) e[c] = tc_index(chunk, c) < n ? src[tc_index(chunk, c)] : 0ull;
+}
+__device__ __forceinline__ void tc_zero(unsigned *cnt) {            // (barriers in front and behind)
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < TS_WAVES; j++) cnt[j * TOP_BINS + threadIdx.x] = 0u;
+    __syncthreads();
+}
+// ADDS the digit counts of each wave's 256 entries of the chunk to cnt[wave][digit] (no barrier: a wave's row is its own)
+__device__ __forceinline__ void tc_count(const unsigned long long (&e)[TS_ITEMS], unsigned long long chunk, unsigned long long n,
+                                         int shift, unsigned *cnt) {
+    const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int c = 0; c < TS_ITEMS; c++) {
+        const bool have = tc_index(chunk, c) < n;
+        const unsigned digit = (unsigned)(e[c] >> shift) & (TOP_BINS - 1u);
+        const unsigned long long m = wave_match_digit(digit, have);
+        if (have && lane == __ffsll((long long)m) - 1)
+            __hip_atomic_fetch_add(cnt + wave * TOP_BINS + digit, (unsigned)__popcll(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+}
+// ts_rank over a key alone, with 32-bit bases (n < 2^32); the value of a lane without `have` means nothing
+__device__ __forceinline__ unsigned tc_rank(unsigned long long e, bool have, int shift, volatile unsigned *mine) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    const unsigned digit = (unsigned)(e >> shift) & (TOP_BINS - 1u);
+    const unsigned long long m = wave_match_digit(digit, have);
+    const unsigned r = have ? mine[digit] + (unsigned)__popcll(m & ((1ull << lane) - 1ull)) : 0u;
+    wave_lds_sync();                                                // every lane has its base before a leader moves it on
+    if (have && lane == __ffsll((long long)m) - 1) mine[digit] += (unsigned)__popcll(m);
+    wave_lds_sync();
+    return r;
+}
+
+// bh[digit * n_blocks + block] = the entries with that digit in the block's `chunks` chunks
+__global__ void __launch_bounds__(TS_WAVES * WAVE)
+pfac_tc_sort_hist_kernel(const unsigned long long *src, unsigned long long n, int shift, unsigned chunks, unsigned n_blocks,
+                         unsigned *bh) {
+    __shared__ unsigned cnt[TS_WAVES * TOP_BINS];
+    tc_zero(cnt);
+    for (unsigned ch = 0; ch < chunks; ch++) {
+        const unsigned long long chunk = (unsigned long long)blockIdx.x * chunks + ch;
+        if (chunk * TC_BLOCK >= n) break;
+        unsigned long long e[TS_ITEMS];
+        tc_load(e, src, chunk, n);
+        tc_count(e, chunk, n, shift, cnt);
+    }
+    __syncthreads();
+    unsigned sum = 0;
+#pragma unroll
+    for (int j = 0; j < TS_WAVES; j++) sum += cnt[j * TOP_BINS + threadIdx.x];
+    bh[(unsigned long long)threadIdx.x * n_blocks + blockIdx.x] = sum;
+}
+
+// The prefix of a pass, ONE WORKGROUP PER DIGIT: the digit's row of n_blocks counts becomes its exclusive prefix, in place,
+// 256 counts per trip with the sum so far carried; tot[digit] = the row's sum.  (The ranked sort hands all 256 x n_blocks
+// counts to the one workgroup of pfac_scan_groups_kernel: fine for its n_top, the whole pass here -- DESIGN.md, section 23.)
+__global__ void __launch_bounds__(TS_WAVES * WAVE)
+pfac_tc_sort_rows_kernel(unsigned *bh, unsigned n_blocks, unsigned *tot) {
+    __shared__ unsigned wsum[TS_WAVES];
+    const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x >> 6;
+    unsigned *row = bh + (unsigned long long)blockIdx.x * n_blocks;
+    unsigned carry = 0;
+    for (unsigned b0 = 0; b0 < n_blocks; b0 += TS_WAVES * WAVE) {
+        const unsigned b = b0 + threadIdx.x;
+        const unsigned v = b < n_blocks ? row[b] : 0u;
+        const unsigned incl = wave_incl_scan(v);
+        __syncthreads();                                            // (the trip before has read wsum)
+        if (lane == WAVE - 1) wsum[wave] = incl;
+        __syncthreads();
+        unsigned pre = carry + incl - v;
+#pragma unroll
+        for (int j = 0; j < TS_WAVES; j++) {
+            pre += j < wave ? wsum[j] : 0u;
+            carry += wsum[j];
+        }
+        if (b < n_blocks) row[b] = pre;
+    }
+    if (threadIdx.x == 0) tot[blockIdx.x] = carry;
+}
+
+// bh holds the rows' exclusive prefixes, tot the rows' sums: digit t's first entry of this workgroup goes to the digits
+// in front of t (a scan of tot, here) + the workgroups in front of this one with t.  Thread t keeps digit t's base in a
+// register across the chunks, which go in order.
+__global__ void __launch_bounds__(TS_WAVES * WAVE)
+pfac_tc_sort_scatter_kernel(const unsigned long long *src, unsigned long long n, int shift, unsigned chunks, unsigned n_blocks,
+                            const unsigned *bh, const unsigned *tot, unsigned long long *dst) {
+    __shared__ unsigned cnt[TS_WAVES * TOP_BINS];
+    __shared__ unsigned base[TS_WAVES * TOP_BINS];
+    __shared__ unsigned wsum[TS_WAVES];
+    const unsigned mytot = tot[threadIdx.x];
+    const unsigned incl = wave_incl_scan(mytot);
+    if ((threadIdx.x & (WAVE - 1)) == WAVE - 1) wsum[threadIdx.x >> 6] = incl;
+    __syncthreads();
+    unsigned run = incl - mytot + bh[(unsigned long long)threadIdx.x * n_blocks + blockIdx.x];
+#pragma unroll
+    for (int j = 0; j < TS_WAVES; j++) run += j < (int)(threadIdx.x >> 6) ? wsum[j] : 0u;
+    volatile unsigned *mine = base + (threadIdx.x >> 6) * TOP_BINS;         // this wave's bases: only its own lanes touch them
+    for (unsigned ch = 0; ch < chunks; ch++) {
+        const unsigned long long chunk = (unsigned long long)blockIdx.x * chunks + ch;
+        if (chunk * TC_BLOCK >= n) break;
+        unsigned long long e[TS_ITEMS];
+        tc_load(e, src, chunk, n);
+        tc_zero(cnt);                                               // (its first barrier: every wave has left the chunk before)
+        tc_count(e, chunk, n, shift, cnt);
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < TS_WAVES; j++) { base[j * TOP_BINS + threadIdx.x] = run; run += cnt[j * TOP_BINS + threadIdx.x]; }
+        __syncthreads();
+#pragma unroll
+        for (int c = 0; c < TS_ITEMS; c++) {
+            const bool have = tc_index(chunk, c) < n;
+            const unsigned r = tc_rank(e[c], have, shift, mine);
+            if (have && r < n) dst[r] = e[c];
+        }
+    }
+}
+
+// n <= TC_BLOCK keys, ONE workgroup, in place: every key is in a register before the first store.
+__global__ void __launch_bounds__(TS_WAVES * WAVE)
+pfac_tc_sort_one_kernel(unsigned long long *keys, unsigned long long n, int passes) {
+    __shared__ unsigned cnt[TS_WAVES * TOP_BINS];
+    __shared__ unsigned base[TS_WAVES * TOP_BINS];
+    __shared__ unsigned long long buf[TC_BLOCK];
+    __shared__ unsigned wsum[TS_WAVES];
+    const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x >> 6;
+    unsigned long long e[TS_ITEMS];
+    tc_load(e, keys, 0ull, n);
+    volatile unsigned *mine = base + wave * TOP_BINS;
+    for (int pass = 0; pass < passes; pass++) {
+        const int shift = pass * TOP_BITS;
+        tc_zero(cnt);
+        tc_count(e, 0ull, n, shift, cnt);
+        __syncthreads();
+        unsigned sum = 0;                                           // thread t: the entries with digit t, ...
+#pragma unroll
+        for (int j = 0; j < TS_WAVES; j++) sum += cnt[j * TOP_BINS + threadIdx.x];
+        const unsigned incl = wave_incl_scan(sum);                  // ... and those with a smaller one
+        if (lane == WAVE - 1) wsum[wave] = incl;
+        __syncthreads();
+        unsigned acc = incl - sum;
+#pragma unroll
+        for (int j = 0; j < TS_WAVES; j++) acc += j < wave ? wsum[j] : 0u;
+#pragma unroll
+        for (int j = 0; j < TS_WAVES; j++) { base[j * TOP_BINS + threadIdx.x] = acc; acc += cnt[j * TOP_BINS + threadIdx.x]; }
+        __syncthreads();
+        const bool last = pass == passes - 1;
+#pragma unroll
+        for (int c = 0; c < TS_ITEMS; c++) {
+            const bool have = tc_index(0ull, c) < n;
+            const unsigned r = tc_rank(e[c], have, shift, mine);
+            if (have && r < n) {
+                if (last) keys[r] = e[c];
+                else buf[r] = e[c];
+            }
+        }
+        if (last) break;
+        __syncthreads();
+#pragma unroll
+        for (int c = 0; c < TS_ITEMS; c++) e[c] = tc_index(0ull, c) < n ? buf[tc_index(0ull, c)] : 0ull;
+    }
+}
+
+__global__ void __launch_bounds__(256)
+pfac_tc_heads_kernel(const unsigned long long *keys, unsigned long long n, unsigned long long *bal, unsigned *X,
+                     unsigned long long *gsum, unsigned n_groups) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    const unsigned g = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (g >= n_groups) return;
+    const unsigned long long i0 = (unsigned long long)g * (DM_BLOCKS * WAVE);
+    unsigned run = 0;
+    for (int b = 0; b < DM_BLOCKS; b++) {
+        const unsigned long long ib = i0 + (unsigned long long)b * WAVE, i = ib + lane;
+        if (ib >= n) break;                                         // (wave-uniform)
+        const bool have = i < n;
+        const unsigned long long k = have ? keys[i] : 0ull;
+        unsigned long long prev = __shfl_up(k, 1, WAVE);
+        if (lane == 0 && i > 0) prev = keys[i - 1];
+        const unsigned long long m = __ballot(have && (i == 0 || k != prev));
+        if (lane == 0) { bal[ib >> 6] = m; X[ib >> 6] = run; }
+        run += (unsigned)__popcll(m);
+    }
+    if (lane == 0) gsum[g] = run;
+}
+
+__global__ void __launch_bounds__(256)
+pfac_tc_write_kernel(const unsigned long long *keys, unsigned long long n, const unsigned long long *bal, const unsigned *X,
+                     const unsigned long long *gpre, unsigned n_groups, unsigned long long mask, unsigned long long n_terms,
+                     unsigned *states, unsigned *hidx) {
+    if (GRID_THREAD == 0) hidx[n_terms] = (unsigned)n;
+    const int lane = threadIdx.x & (WAVE - 1);
+    const unsigned g = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (g >= n_groups) return;
+    const unsigned long long i0 = (unsigned long long)g * (DM_BLOCKS * WAVE), pre = gpre[g];
+    for (int b = 0; b < DM_BLOCKS; b++) {
+        const unsigned long long ib = i0 + (unsigned long long)b * WAVE, i = ib + lane;
+        if (ib >= n) break;
+        const unsigned long long m = bal[ib >> 6];
+        const unsigned long long j = pre + X[ib >> 6] + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
+        if (((m >> lane) & 1ull) && i < n && j < n_terms) {
+            states[j] = (unsigned)(keys[i] & mask);
+            hidx[j] = (unsigned)i;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256)
+pfac_tc_counts_kernel(const unsigned *hidx, unsigned long long n_terms, unsigned *counts) {
+    for (unsigned long long j = GRID_THREAD; j < n_terms; j += GRID_THREADS) counts[j] = hidx[j + 1] - hidx[j];
+}
+
+__global__ void __launch_bounds__(256)
+pfac_tc_rowptr_kernel(const unsigned long long *first, unsigned long long n_docs, unsigned long long n, const unsigned long long *bal,
+                      const unsigned *X, const unsigned long long *gpre, unsigned long long n_terms, unsigned long long *row) {
+    for (unsigned long long d = GRID_THREAD; d <= n_docs; d += GRID_THREADS) {
+        const unsigned long long i = first[d];
+        row[d] = i >= n ? n_terms
+                        : gpre[i / (DM_BLOCKS * WAVE)] + X[i >> 6] + (unsigned long long)__popcll(bal[i >> 6] & ((1ull << (i & 63)) - 1ull));
+    }
+}
+#undef GRID_THREAD
+#undef GRID_THREADS
+
+// ---------------------------------------------------------------------------
 // The selected documents' bytes, back to back (pfac_documents_gather): segment k is in[off[ids[k]], off[ids[k] + 1]), at
 // output offset out_off[k] = the sum of the lengths before it.  The replace's shape with the picks taken out:
 //   pfac_ga_count_kernel     one workgroup per 1024 ids: two 8-byte gathers of the offsets per id, the checks (id <
@@ -4929,6 +5211,15 @@ struct Slot {
     DevBuf<ulonglong2> tp_ent;            // PFAC_TOP_RANKED: the sort's two buffers of (key word, id), n_top entries each, ...
     DevBuf<unsigned long long> tp_bh;     // ... and its digit counts per block (and the total behind them)
     PassOut<pfac_doc_score> tp_out;       // the winners' pairs
+    // pfac_documents_term_counts
+    uint64_t seg_table = 0;               // the table the slot's last segment pass ran with (pfac_ctx::table_gen)
+    DevBuf<unsigned long long> tc_keys;   // the sort's two buffers of keys, n entries each, ...
+    DevBuf<unsigned> tc_bh;               // ... its digit counts per workgroup (and the 256 digit sums behind them), ...
+    DevBuf<unsigned long long> tc_bal;    // ... the head ballot of every block of 64 sorted keys, ...
+    DevBuf<unsigned> tc_x;                // ... the heads in front of the block in its group, ...
+    DevBuf<unsigned> tc_hidx;             // ... and the index of every head (n_terms + 1 entries)
+    PassOut<unsigned long long> tc_row;   // row_ptr (n_docs + 1 entries), ...
+    PassOut<unsigned> tc_st, tc_cnt;      // ... the states and the counts (n_terms entries each)
     // pfac_documents_gather
     DevBuf<unsigned long long> ga_x;      // X per block of 64 ids
     PassOut<unsigned char> ga_out;        // the bytes, ...
@@ -4948,6 +5239,7 @@ struct Knobs {
     int rec_bytes = 0, d2_logcap = 0;     // PFAC_REC_BYTES / _WIDE: a WIDER record form; PFAC_D2_LOGCAP: tiles with more records take the fallback pass
     int dense = -1;                       // PFAC_DENSE=0/1 pins the staging mode
     unsigned ticket_ways = 0, count_bins = 0, count_grid = 0, count_threads = 0;   // PFAC_TICKET_WAYS, PFAC_COUNT_BINS / _GRID / _THREADS (0: the defaults)
+    unsigned terms_rows = 0;              // PFAC_TERMS_ROWS: workgroups of a sort pass of pfac_documents_term_counts (0: PFAC_TERMS_SORT_ROWS)
     unsigned spin_max = SPIN_MAX, fault = 0;                      // (they go into ScanArgs as they are)
     std::string trace_file;
 };
@@ -5250,6 +5542,9 @@ Knobs read_knobs() {
     k.count_bins = cbins >= 1 && (unsigned)cbins <= COUNT_BINS_MAX ? (unsigned)cbins : 0u;
     k.count_grid = cgrid >= 1 ? (unsigned)std::min(cgrid, 65536) : 0u;
     k.count_threads = cthreads == 256 || cthreads == 512 || cthreads == 1024 ? (unsigned)cthreads : 0u;
+    // the term counts' sort: another limit on the workgroups (histogram rows) of a pass
+    const int trows = env_int("PFAC_TERMS_ROWS", 0);
+    k.terms_rows = trows >= 1 ? (unsigned)std::min(trows, 1 << 20) : 0u;
     return k;
 }
 
@@ -6407,6 +6702,7 @@ int pfac_records_segment(pfac_ctx *ctx, int slot, const void *d_records, const u
     }
     s.seg_out.commit(total, !d_out);
     s.seg_first.commit(n_docs + 1, !d_doc_first);
+    s.seg_table = s.last_table;
     return PFAC_OK;
 }
 
@@ -6887,6 +7183,155 @@ int pfac_documents_top_scores_d2h(pfac_ctx *ctx, int slot, pfac_doc_score *host,
     if (rc) return rc;
     Slot &s = ctx->slots[slot];
     return fetch(ctx, s, s.tp_out, "pfac_documents_top_scores_d2h", "pfac_documents_top_scores", host, first, n);
+}
+
+// Term counts: the key kernel (with the checks), the sort, the heads and their group prefix queued back to back, then the
+// ONE copy back (the total and the error word); behind the host's checks the write, the counts and row_ptr.
+int pfac_documents_term_counts(pfac_ctx *ctx, int slot, const pfac_record *d_sel, const uint64_t *d_doc_first, uint64_t n_docs,
+                               uint32_t flags, uint64_t *d_row_ptr_out, uint32_t *d_states_out, uint32_t *d_counts_out,
+                               uint64_t out_cap, uint64_t *n_terms) {
+    const std::string fn = "pfac_documents_term_counts";
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    if (!n_terms) return fail(ctx, PFAC_E_ARG, "null argument");
+    *n_terms = 0;
+    Slot &s = ctx->slots[slot];
+    s.tc_row.invalidate();
+    s.tc_st.invalidate();
+    s.tc_cnt.invalidate();
+    if (!ctx->have_table) return fail(ctx, PFAC_E_STATE, fn + " before a table upload");
+    const pfac_record *sel = d_sel;
+    const unsigned long long *first = reinterpret_cast<const unsigned long long *>(d_doc_first);
+    uint64_t n = 0;
+    const bool own = !d_sel && !d_doc_first;
+    if (own && flags == PFAC_TERMS_SELECTION) {             // the rules of pfac_selection_count_states' d_sel
+        if (!s.scanned || s.pending || !s.ll_out.done || s.ll_seq != s.scan_seq || !s.ll_docs)
+            return fail(ctx, PFAC_E_STATE, fn + " needs a pfac_records_leftmost_longest_documents since the slot's last scan");
+        if (s.last_table != ctx->table_gen) return fail(ctx, PFAC_E_STATE, fn + ": the selection was made with an earlier table");
+        if (!s.ll_out.own || !s.lld_first.done || !s.lld_first.own)
+            return fail(ctx, PFAC_E_STATE, fn + ": the slot holds no selection (it went to the caller's buffers; pass those)");
+    } else if (own && flags == 0) {
+        if (!s.seg_out.done || !s.seg_out.own || !s.seg_first.done || !s.seg_first.own)
+            return fail(ctx, PFAC_E_STATE, fn + ": the slot holds no pfac_records_segment result (none yet, or it went to the caller's buffers; pass those)");
+        if (s.seg_table != ctx->table_gen) return fail(ctx, PFAC_E_STATE, fn + ": the segment pass ran with an earlier table");
+    }
+    if (flags > PFAC_TERMS_SELECTION) return fail(ctx, PFAC_E_ARG, fn + ": flags must be 0 or PFAC_TERMS_SELECTION");
+    if (own) {
+        const bool picks = flags == PFAC_TERMS_SELECTION;
+        rc = (picks ? s.ll_out : s.seg_out).consume(ctx, fn, "records (d_sel)", d_sel, ANY_N, &sel);
+        if (rc) return rc;
+        rc = (picks ? s.lld_first : s.seg_first).consume(ctx, fn, "doc_first (d_doc_first)", d_doc_first, n_docs + 1, &first);
+        if (rc) return rc;
+        n = picks ? s.ll_out.n : s.seg_out.n;
+    } else if (!d_sel || !d_doc_first) {
+        return fail(ctx, PFAC_E_ARG, fn + ": d_sel and d_doc_first are the slot's (both NULL) or the caller's (neither)");
+    }
+    if (n_docs >= (1ull << 32)) return fail(ctx, PFAC_E_ARG, fn + ": n_docs must be below 2^32");
+    if ((((uintptr_t)sel | (uintptr_t)first | (uintptr_t)d_row_ptr_out) & 7) || (((uintptr_t)d_states_out | (uintptr_t)d_counts_out) & 3))
+        return fail(ctx, PFAC_E_ARG, fn + ": misaligned buffer (d_sel, d_doc_first and d_row_ptr_out 8 B, d_states_out and d_counts_out 4 B)");
+    USE_DEVICE(ctx);
+    if (!own) {                                             // how many records the caller's arrays hold: doc_first[n_docs]
+        HIP_TRY(ctx, hipMemcpyAsync(s.h_ctl + H_PASS, first + n_docs, 8, hipMemcpyDeviceToHost, s.stream));
+        HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+        n = host_u64(s, H_PASS);
+    }
+    if (n >= (1ull << 32)) return fail(ctx, PFAC_E_ARG, fn + ": the record count, d_doc_first[n_docs], must be below 2^32");
+    const char *rules = ": d_doc_first must start at 0 and not decrease, and every state of d_sel must be below num_final";
+    if (n_docs == 0 && n) return fail(ctx, PFAC_E_ARG, fn + rules);
+    const unsigned num_final = (unsigned)ctx->plan.base.num_final;
+    auto bit_width = [](uint64_t v) { unsigned b = 0; while (v) { b++; v >>= 1; } return b; };
+    const unsigned sbits = bit_width(num_final ? num_final - 1 : 0), dbits = bit_width(n_docs ? n_docs - 1 : 0);
+    const int passes = (int)((sbits + dbits + TOP_BITS - 1) / TOP_BITS);
+    const unsigned n_groups = (unsigned)((n + DM_BLOCKS * WAVE - 1) / (DM_BLOCKS * WAVE));
+    const uint64_t n_heads_blocks = (n + WAVE - 1) / WAVE;
+    // the sort's shape: a block takes `chunks` chunks of TC_BLOCK keys, so that a pass has PFAC_TERMS_SORT_ROWS blocks at most
+    const uint64_t n_chunks = (n + TC_BLOCK - 1) / TC_BLOCK;
+    const uint64_t rows = ctx->plan.knobs.terms_rows ? ctx->plan.knobs.terms_rows : PFAC_TERMS_SORT_ROWS;
+    const unsigned chunks = (unsigned)std::max<uint64_t>(1, (n_chunks + rows - 1) / rows);
+    const unsigned n_blocks = (unsigned)((n_chunks + chunks - 1) / chunks);
+    const bool one = n <= (uint64_t)TC_BLOCK;
+    rc = ensure_gsum(ctx, s, n_groups + 1);                 // the group prefixes, the total, the error word
+    if (rc) return rc;
+    unsigned long long *res = s.gsum.p + n_groups;
+    HIP_TRY(ctx, hipMemsetAsync(res, 0, 16, s.stream));
+    const unsigned long long *sorted = nullptr;
+    if (n) {
+        rc = s.tc_keys.ensure(ctx, s.stream, 2 * n, 2 * (n + n / 8 + 4096));
+        if (!rc) rc = s.tc_bal.ensure(ctx, s.stream, n_heads_blocks, quarter_more(n_heads_blocks));
+        if (!rc) rc = s.tc_x.ensure(ctx, s.stream, n_heads_blocks, quarter_more(n_heads_blocks));
+        if (!rc && !one && passes)
+            rc = s.tc_bh.ensure(ctx, s.stream, (uint64_t)TOP_BINS * (n_blocks + 1), (uint64_t)TOP_BINS * (quarter_more(n_blocks) + 1));
+        if (rc) return rc;
+    }
+    if (n_docs) {
+        const uint64_t n_waves = (n + SS_RANGE - 1) / SS_RANGE, vblocks = (n_docs + 255) / 256;
+        const unsigned blocks = (unsigned)std::max<uint64_t>(1, std::max<uint64_t>((n_waves + 3) / 4, std::min<uint64_t>(vblocks, 4096)));
+        hipLaunchKernelGGL(pfac_tc_key_kernel, dim3(blocks), dim3(256), 0, s.stream, sel, (unsigned long long)n, first,
+                           (unsigned long long)n_docs, num_final, sbits, s.tc_keys.p, res + 1);
+    }
+    if (n) {
+        unsigned long long *a = s.tc_keys.p, *b = s.tc_keys.p + n;
+        if (one && passes) {
+            hipLaunchKernelGGL(pfac_tc_sort_one_kernel, dim3(1), dim3(TS_WAVES * WAVE), 0, s.stream, a, (unsigned long long)n, passes);
+        } else {
+            unsigned *tot = s.tc_bh.p + (uint64_t)TOP_BINS * n_blocks;
+            for (int pass = 0; pass < passes; pass++) {
+                hipLaunchKernelGGL(pfac_tc_sort_hist_kernel, dim3(n_blocks), dim3(TS_WAVES * WAVE), 0, s.stream, (const unsigned long long *)a,
+                                   (unsigned long long)n, pass * TOP_BITS, chunks, n_blocks, s.tc_bh.p);
+                hipLaunchKernelGGL(pfac_tc_sort_rows_kernel, dim3(TOP_BINS), dim3(TS_WAVES * WAVE), 0, s.stream, s.tc_bh.p, n_blocks, tot);
+                hipLaunchKernelGGL(pfac_tc_sort_scatter_kernel, dim3(n_blocks), dim3(TS_WAVES * WAVE), 0, s.stream, (const unsigned long long *)a,
+                                   (unsigned long long)n, pass * TOP_BITS, chunks, n_blocks, (const unsigned *)s.tc_bh.p, (const unsigned *)tot, b);
+                std::swap(a, b);
+            }
+        }
+        sorted = a;
+        hipLaunchKernelGGL(pfac_tc_heads_kernel, dim3((n_groups + 3) / 4), dim3(256), 0, s.stream, sorted, (unsigned long long)n,
+                           s.tc_bal.p, s.tc_x.p, s.gsum.p, n_groups);
+        hipLaunchKernelGGL(pfac_scan_groups_kernel, dim3(1), dim3(1024), 0, s.stream, s.gsum.p, n_groups);
+    }
+    rc = pass_words(ctx, s, res, 2);
+    if (rc) return rc;
+    if (host_u64(s, H_PASS1)) return fail(ctx, PFAC_E_ARG, fn + rules);
+    const uint64_t total = host_u64(s, H_PASS);
+    *n_terms = total;
+    if ((d_states_out || d_counts_out) && total > out_cap)
+        return fail(ctx, PFAC_E_OVERFLOW, fn + ": " + std::to_string(total) + " terms, out_cap is " + std::to_string(out_cap));
+    unsigned long long *row;
+    unsigned *st, *cn;
+    rc = s.tc_row.bind(ctx, s.stream, d_row_ptr_out, n_docs + 1, docs_cap(n_docs), &row);
+    if (!rc) rc = s.tc_st.bind(ctx, s.stream, d_states_out, total, total + total / 8 + 4096, &st);
+    if (!rc) rc = s.tc_cnt.bind(ctx, s.stream, d_counts_out, total, total + total / 8 + 4096, &cn);
+    if (!rc) rc = s.tc_hidx.ensure(ctx, s.stream, total + 1, total + total / 8 + 4096);
+    if (rc) return rc;
+    if (total) {
+        hipLaunchKernelGGL(pfac_tc_write_kernel, dim3((n_groups + 3) / 4), dim3(256), 0, s.stream, sorted, (unsigned long long)n,
+                           (const unsigned long long *)s.tc_bal.p, (const unsigned *)s.tc_x.p, (const unsigned long long *)s.gsum.p, n_groups,
+                           (1ull << sbits) - 1ull, (unsigned long long)total, st, s.tc_hidx.p);
+        const unsigned cblocks = (unsigned)std::min<uint64_t>((total + 255) / 256, 1u << 20);
+        hipLaunchKernelGGL(pfac_tc_counts_kernel, dim3(cblocks), dim3(256), 0, s.stream, (const unsigned *)s.tc_hidx.p,
+                           (unsigned long long)total, cn);
+        const unsigned rblocks = (unsigned)std::min<uint64_t>((n_docs + 1 + 255) / 256, 1u << 20);
+        hipLaunchKernelGGL(pfac_tc_rowptr_kernel, dim3(rblocks), dim3(256), 0, s.stream, first, (unsigned long long)n_docs,
+                           (unsigned long long)n, (const unsigned long long *)s.tc_bal.p, (const unsigned *)s.tc_x.p,
+                           (const unsigned long long *)s.gsum.p, (unsigned long long)total, row);
+        HIP_TRY(ctx, hipGetLastError());
+    } else {
+        HIP_TRY(ctx, hipMemsetAsync(row, 0, (n_docs + 1) * 8, s.stream));     // no record: every document is empty
+    }
+    s.tc_row.commit(n_docs + 1, !d_row_ptr_out);
+    s.tc_st.commit(total, !d_states_out);
+    s.tc_cnt.commit(total, !d_counts_out);
+    return PFAC_OK;
+}
+
+int pfac_documents_term_counts_d2h(pfac_ctx *ctx, int slot, uint64_t *host_row_ptr, uint32_t *host_states, uint32_t *host_counts) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    Slot &s = ctx->slots[slot];
+    const char *me = "pfac_documents_term_counts_d2h", *pass = "pfac_documents_term_counts";
+    rc = fetch(ctx, s, s.tc_row, me, pass, host_row_ptr, 0, s.tc_row.n, true);
+    if (!rc) rc = fetch(ctx, s, s.tc_st, me, pass, host_states, 0, s.tc_st.n, true);
+    return rc ? rc : fetch(ctx, s, s.tc_cnt, me, pass, host_counts, 0, s.tc_cnt.n, true);
 }
 
 // The two gathers: the plain one (fmt NULL, or a format that asks for nothing: the plain kernels) and the one with

@@ -18,6 +18,7 @@ from ._ffi import (PFAC_COUNT_ACCUMULATE, PFAC_DOCS_INVERT, PFAC_E_OVERFLOW, PFA
 from ._ffi import (PFAC_LINE_CONTEXT_SEP, PFAC_LINE_MAX_GROUP_SEP, PFAC_LINE_NUMBER, PFAC_LINE_OFFSET, PFAC_LINE_SEP_FIRST,
                    PFAC_LINE_TERMINATE, CDocScore, CLineFormat, CScoreRule)
 from ._ffi import PFAC_TOP_BY_COUNT, PFAC_TOP_LOWEST, PFAC_TOP_RANKED
+from ._ffi import PFAC_TERMS_SELECTION
 from .table import RECORD_DTYPE, SCORE_DTYPE, TEMPLATE_PLAIN, PfacTable, redaction_table, replacement_table, template_table, _state_lengths
 
 
@@ -989,6 +990,63 @@ class GpuMatcher:
         out_bytes = self.gather_documents(n_docs, n, int(buf.size), slot=slot)
         return (self.gathered_to_host(out_bytes, slot), self.gathered_offsets_to_host(n, slot),
                 self.matching_documents_to_host(n, slot), self.top_scores_to_host(n, slot))
+
+    # -- term counts: the document-term matrix in CSR form --------------------
+    def document_term_counts(self, n_docs: int, d_sel=None, d_doc_first=None, selection: bool = False, d_row_ptr=None,
+                             d_states=None, d_counts=None, out_cap: int = 0, slot: int = 0) -> int:
+        """Which final states each document holds and how often, on the GPU (``pfac_documents_term_counts``): the
+        distinct (document, state) pairs of a record array that is already cut per document, as a CSR matrix --
+        ``row_ptr`` uint64[n_docs + 1], ``states`` and ``counts`` uint32[n_terms], the states of a document
+        ascending.  ``d_sel`` and ``d_doc_first`` both None = the slot-owned result of the slot's last
+        ``segment_records`` (``selection``: of its last ``select_leftmost_longest_documents``); else the device arrays
+        of either.  ``d_row_ptr`` / ``d_states`` / ``d_counts`` None = slot-owned buffers (``term_counts_to_host``);
+        else device buffers, the two entry arrays of ``out_cap`` entries.  Returns the number of pairs; a too small
+        ``out_cap`` raises PfacError(PFAC_E_OVERFLOW) whose ``n_terms`` attribute holds the exact count."""
+        n = C.c_uint64(0)
+        rc = self._L.pfac_documents_term_counts(self._ctx, slot, _ptr(d_sel), _ptr(d_doc_first), int(n_docs),
+                                                PFAC_TERMS_SELECTION if selection else 0, _ptr(d_row_ptr), _ptr(d_states),
+                                                _ptr(d_counts), int(out_cap), C.byref(n))
+        return self._counted(rc, n, "n_terms")
+
+    def term_counts_to_host(self, n_docs: int, n_terms: int, slot: int = 0) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(row_ptr uint64[n_docs + 1], states uint32[n_terms], counts uint32[n_terms]) of the slot's last
+        ``document_term_counts`` into slot-owned buffers."""
+        return self._to_host(slot, lambda r, s, c: self._L.pfac_documents_term_counts_d2h(self._ctx, slot, r, s, c),
+                             (int(n_docs) + 1, np.uint64), (n_terms, np.uint32), (n_terms, np.uint32))
+
+    def _term_pass(self, n_docs: int, slot: int, non_overlapping: bool) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        if non_overlapping:
+            self.select_leftmost_longest_documents(n_docs, slot=slot)
+        else:
+            self.segment_records(n_docs, slot=slot)
+        n_terms = self.document_term_counts(n_docs, selection=non_overlapping, slot=slot)
+        return self.term_counts_to_host(n_docs, n_terms, slot)
+
+    def term_counts_documents(self, docs, whole_words=False, spans: bool = False, line_match: bool = False,
+                              non_overlapping: bool = False, slot: int = 0) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The document-term matrix of a batch (``docs`` as ``scan_documents`` takes it) in one scan: the scan, the
+        document cut (``non_overlapping``: the leftmost-longest picks of each document instead of every match) and
+        ``document_term_counts`` on the device; only the three CSR arrays come back -- (row_ptr, states, counts).
+        ``PfacTable.states_to_patterns`` turns the states into pattern ids."""
+        _, n_docs = self._scan_docs(docs, slot, whole_words, spans, line_match)
+        return self._term_pass(n_docs, slot, non_overlapping)
+
+    def term_counts_lines(self, data, delimiter=b"\n", whole_words=False, spans: bool = False, line_match: bool = False,
+                          non_overlapping: bool = False, slot: int = 0) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """``term_counts_documents`` of one buffer cut into lines at ``delimiter`` on the device: row d is line d."""
+        _, n_docs = self._scan_lines(data, delimiter, slot, whole_words, fetch_offsets=False, spans=spans, line_match=line_match)
+        return self._term_pass(n_docs, slot, non_overlapping)
+
+    def term_matrix(self, n_docs: int, n_terms: int, d_row_ptr, d_states, d_counts):
+        """The caller's device tensors of a ``document_term_counts`` (``d_row_ptr`` int64 or uint64 storage of n_docs + 1
+        entries, ``d_states`` and ``d_counts`` 32-bit storage of at least ``n_terms``) as a ``torch.sparse_csr_tensor``
+        of shape (n_docs, num_final) on their device.  The column indices are widened in torch; nothing is copied to
+        the host.  The pass writes on the slot's stream: synchronise it (``sync``) before torch reads the matrix."""
+        import torch
+        row = d_row_ptr.view(torch.int64)[: int(n_docs) + 1]
+        col = d_states.view(torch.int32)[: int(n_terms)].to(torch.int64)
+        val = d_counts.view(torch.int32)[: int(n_terms)]
+        return torch.sparse_csr_tensor(row, col, val, size=(int(n_docs), self._n_states()))
 
     # -- leftmost-longest non-overlapping matches ---------------------------
     def select_leftmost_longest(self, entry: int = 0, d_out=None, out_cap: int = 0, slot: int = 0,

@@ -174,6 +174,20 @@ class PfacTable:
     def pattern_ids(self, records: np.ndarray) -> np.ndarray:
         return self.idmap[records["state"]]
 
+    def states_to_patterns(self, states) -> np.ndarray:
+        """The 1-based pattern id of every final state of ``states`` (the column indices of
+        ``GpuMatcher.term_counts_to_host``): ``idmap[state]``.  Only for a table with one id per final state: a
+        character-class table whose states stand for several patterns raises ValueError -- read its ``outputs``
+        (``out_first`` / ``out_ids``) instead."""
+        first = getattr(self, "out_first", None)
+        if first is not None and np.any(np.diff(np.asarray(first, dtype=np.int64)) != 1):
+            raise ValueError("a final state of this character-class table stands for several patterns: take them from "
+                             "its outputs (out_ids[out_first[s]:out_first[s + 1]])")
+        st = np.asarray(states, dtype=np.int64)
+        if st.size and (int(st.min()) < 0 or int(st.max()) >= self.num_final):
+            raise ValueError(f"a state outside [0, num_final = {self.num_final})")
+        return np.asarray(self.idmap, dtype=np.int64)[st]
+
     def counts_by_pattern(self, state_counts) -> np.ndarray:
         """Counts per final state (``GpuMatcher.state_counts_to_host``) -> uint64 counts indexed by the 1-based pattern
         id (entry 0 is unused), long enough for every id the table can report.  A literal table puts ``counts[s]`` at
