@@ -1147,6 +1147,67 @@ int pfac_extract_d2h(pfac_ctx *ctx, int slot, void *host, uint64_t first, uint64
  * slot's stream; pfac_slot_sync completes it. */
 int pfac_extract_offsets_d2h(pfac_ctx *ctx, int slot, uint64_t *host_pick_offsets);
 
+/* Tokenization: the token ids of the leftmost-longest picks, in order -- greedy longest-match (forward maximum
+ * matching, the MaxMatch step of WordPiece, a dictionary tokenizer) with a per-byte fallback.  Two attachments of the
+ * installed table: tok[s], an int32 per final state, and btok[b], an int32 per byte value; PFAC_TOKEN_DROP is allowed
+ * in both.  state_ids holds n_states == num_final entries (else PFAC_E_ARG), byte_ids 256 (NULL = every byte DROP);
+ * every value must be >= 0 or PFAC_TOKEN_DROP (else PFAC_E_ARG).  A pattern id's token goes to its state as a
+ * replacement does.  Everything is checked before anything changes.  A device attachment like the replacements: a
+ * table upload drops it, and the old buffers are freed behind the device's queued work. */
+#define PFAC_TOKEN_DROP (-1)
+int pfac_table_set_token_ids(pfac_ctx *ctx, const int32_t *state_ids, uint64_t n_states, const int32_t *byte_ids);
+/* THE RULE.  Over the slot's last finished scan (n_owned, n_avail, its input) and its last leftmost-longest selection
+ * (picks (p_k, s_k), k < n, ascending, made from `entry`, ending in `exit`; L_k = the final length of s_k), with C the
+ * union of [p_k, p_k + L_k): every position i of [entry, n_owned), ascending,
+ *   - if i == p_k for some k: emits tok[s_k], unless that is PFAC_TOKEN_DROP;
+ *   - else if i is not in C: emits btok[input[i]], unless that is PFAC_TOKEN_DROP;
+ *   - else emits nothing.
+ * input[i] is the byte as the caller wrote it: under a case fold (pfac_table_set_case_fold) the matcher saw folded
+ * bytes, btok sees the unfolded ones.  Every position emits at most one token.  *n_tokens is their number, ids[j] the j-th token and, with
+ * PFAC_TOKENS_POSITIONS, pos[j] its position i as uint32, relative to the scan (like pfac_record.pos).  No position at
+ * or past n_owned emits; a pick that starts below n_owned and ends in the halo emits its one token, and the next
+ * range's entry skips its bytes: chained ranges (entry = the previous range's exit) concatenate to the tokens of one
+ * scan of the whole range (positions: plus each range's base).
+ *   d_input  NULL = the slot's input buffer; else the buffer the scan read (16-B aligned)
+ *   d_sel    NULL = the slot-owned selection; else the caller's d_out of the selection (8-B aligned).  Checked on the
+ *            device in the count pass: states below num_final, picks ascending and not overlapping, none before entry
+ *            or at or past n_owned, the last end agreeing with exit.
+ *   d_ids    NULL = a slot-owned buffer of this pass's own (fetched with pfac_tokens_d2h): no replace, extraction or
+ *            other pass invalidates it, and it invalidates none; else 16-B aligned, holding out_cap entries
+ *   d_pos    without PFAC_TOKENS_POSITIONS it must be NULL; with it NULL = slot-owned, else 16-B aligned, out_cap entries
+ * No word at or past *n_tokens is written (the output is not rounded up to 16 bytes).  Input reads stay inside
+ * [0, n_avail).  Returns once *n_tokens is known (one copy back per call); the writes are asynchronous on the slot's
+ * stream.  PFAC_E_STATE (checked first, in the order of pfac_replace_leftmost_longest): no selection since the slot's
+ * last scan, a selection of an earlier table, no token ids or no final lengths for the current table, a
+ * pfac_slot_reserve that replaced a buffer.  PFAC_E_ARG: unknown flags, d_pos without the flag, misaligned buffers, a
+ * d_sel that is not a selection of this scan and table.  PFAC_E_OVERFLOW (with *n_tokens exact, nothing written to any
+ * buffer of the call) when out_cap is too small for a caller's d_ids or d_pos.
+ * Kernels (position-driven over the scan's 4 KiB tiles; the replace's pick-driven passes do not fit, because with DROP
+ * in btok the tokens of a gap depend on its bytes and a gap has no length bound): one thread per tile finds the tile's
+ * first pick; a count pass builds every tile's 4096-bit "emits" bitmap in LDS (coverage and kept pick starts from the
+ * tile's picks, btok from LDS for the bytes) and keeps it with a 16-bit token prefix per 64-bit word and the sums per
+ * 64 tiles; the group prefix; then a write pass that ranks every token by popcounts of the saved bitmap, stages the
+ * tile's tokens in LDS in rank order and stores whole 16-B chunks, the ragged ends in pieces. */
+#define PFAC_TOKENS_POSITIONS 1u
+int pfac_tokenize_leftmost_longest(pfac_ctx *ctx, int slot, const void *d_input, const pfac_record *d_sel, uint32_t flags,
+                                   int32_t *d_ids, uint64_t out_cap, uint32_t *d_pos, uint64_t *n_tokens);
+/* Tokenization per document: pfac_tokenize_leftmost_longest over the slot's last selection, which must be a
+ * pfac_records_leftmost_longest_documents since the slot's last scan (else PFAC_E_STATE), with the same ids, plus
+ * tok_off[n_docs + 1]: tok_off[d] = the tokens at positions < off[d], tok_off[n_docs] = *n_tokens.  No pick crosses a
+ * document end, so ids[tok_off[d] : tok_off[d + 1]] is what tokenizing document d alone gives; ids and tok_off are the
+ * pair that torch.nn.functional.embedding_bag(input, weight, offsets) takes (offsets = tok_off[:-1]).
+ *   d_doc_offsets, d_doc_first   as pfac_replace_documents, with its NULL rules and PFAC_E_STATE cases
+ *   d_tok_offsets                NULL = a slot-owned buffer (pfac_tokens_offsets_d2h); else 8-B aligned, n_docs + 1
+ * One more kernel: a thread per document, tok_off[d] = group prefix + tile prefix + word prefix + a popcount. */
+int pfac_tokenize_documents(pfac_ctx *ctx, int slot, const void *d_input, const pfac_record *d_sel, const uint64_t *d_doc_offsets,
+                            const uint64_t *d_doc_first, uint32_t flags, int32_t *d_ids, uint64_t out_cap, uint32_t *d_pos,
+                            uint64_t *d_tok_offsets, uint64_t *n_tokens);
+/* D2H of tokens [first, first + n) of the slot-owned result of the last tokenize pass (host_pos may be NULL; else the
+ * pass must have written slot-owned positions).  Asynchronous on the slot's stream; pfac_slot_sync completes it. */
+int pfac_tokens_d2h(pfac_ctx *ctx, int slot, int32_t *host_ids, uint32_t *host_pos, uint64_t first, uint64_t n);
+/* D2H of the slot-owned token offsets of the last pfac_tokenize_documents (n_docs + 1 entries). */
+int pfac_tokens_offsets_d2h(pfac_ctx *ctx, int slot, uint64_t *host_tok_off);
+
 /* Synthetic input generators, written straight into device memory (the
  * reference built big inputs by tiling a small text, creatbiginput.sh:2-5).
  *   tiled : byte i = pattern[(phase + i) % period]

@@ -49,6 +49,8 @@ PFAC_TOP_SORT_BLOCK = 1024  # ... entries per workgroup of the ranked sort
 PFAC_TERMS_SELECTION = 1    # pfac_documents_term_counts: NULL inputs mean the slot's per-document selection
 PFAC_TERMS_SORT_BLOCK = 1024    # ... keys per chunk of its sort, and the most that one workgroup sorts alone
 PFAC_TERMS_SORT_ROWS = 4096     # ... the most workgroups of one sort pass
+PFAC_TOKEN_DROP = -1        # pfac_table_set_token_ids: the state or byte emits no token
+PFAC_TOKENS_POSITIONS = 1   # pfac_tokenize_*: also the tokens' positions
 
 _STATUS_NAMES = {
     0: "PFAC_OK", -1: "PFAC_E_ARG", -2: "PFAC_E_IO", -3: "PFAC_E_PATTERN", -4: "PFAC_E_NOMEM",
@@ -150,6 +152,8 @@ HIP_SYMBOLS = (
     "pfac_documents_matching_scores",
     "pfac_documents_top_scores", "pfac_documents_top_scores_d2h",
     "pfac_documents_term_counts", "pfac_documents_term_counts_d2h",
+    "pfac_table_set_token_ids", "pfac_tokenize_leftmost_longest", "pfac_tokenize_documents", "pfac_tokens_d2h",
+    "pfac_tokens_offsets_d2h",
 )
 
 _host = None
@@ -315,6 +319,11 @@ def hip_lib() -> C.CDLL:
         L.pfac_documents_top_scores_d2h.argtypes = [vp, i, vp, u64, u64]
         L.pfac_documents_term_counts.argtypes = [vp, i, vp, vp, u64, C.c_uint32, vp, vp, vp, u64, C.POINTER(u64)]
         L.pfac_documents_term_counts_d2h.argtypes = [vp, i, vp, vp, vp]
+        L.pfac_table_set_token_ids.argtypes = [vp, vp, u64, vp]
+        L.pfac_tokenize_leftmost_longest.argtypes = [vp, i, vp, vp, C.c_uint32, vp, u64, vp, C.POINTER(u64)]
+        L.pfac_tokenize_documents.argtypes = [vp, i, vp, vp, vp, vp, C.c_uint32, vp, u64, vp, vp, C.POINTER(u64)]
+        L.pfac_tokens_d2h.argtypes = [vp, i, vp, vp, u64, u64]
+        L.pfac_tokens_offsets_d2h.argtypes = [vp, i, vp]
         L.pfac_table_set_state_spans.argtypes = [vp, vp, u64]
         L.pfac_records_filter_spans.argtypes = [vp, i, vp, vp, i, C.c_uint32, vp, u64, C.POINTER(u64)]
         _hip = L

@@ -5040,6 +5040,262 @@ pfac_gf_write_kernel(const unsigned char *in, unsigned long long n_bytes, const 
 }
 
 // ---------------------------------------------------------------------------
+// Token ids of the leftmost-longest picks (pfac_tokenize_leftmost_longest, pfac_tokenize_documents).  Position i of
+// [entry, n_owned) emits tok[s_k] at a pick's start, btok[input[i]] outside every pick, nothing inside one; DROP emits
+// nothing.  The number of tokens in a gap depends on the gap's bytes and a gap has no length bound, so the pass is
+// position-driven, over the scan's 4 KiB tiles, not pick-driven like the replace:
+//   pfac_tk_first_kernel     one thread per tile: first[t] = the first pick at or behind the tile's start (a lower bound
+//                            over sel[].pos), first[n_tiles] = n.  Patterns are shorter than HALO_MAX, so the one pick
+//                            that can reach into tile t from the front is pick first[t] - 1.
+//   pfac_tk_count_kernel     a workgroup per group of 64 tiles, a wave per tile at a time.  The lanes that own the tile's
+//                            picks set the coverage bits (and the start bit where tok[s] != DROP) in LDS, the byte lanes
+//                            look their 16 bytes up in btok (LDS); emits = (byte & ~covered | start) & [entry, n_owned).
+//                            Kept per tile: the 64 bitmap words, the 16-bit count of the tokens in front of each word,
+//                            and the tokens in front of the tile in its group; per group the sum.  Every pick is checked
+//                            by the one tile that owns its start (state, length, inside the tile and below n_owned, not
+//                            before the end of the pick in front of it), and first[] must not decrease: with first[0]
+//                            == 0 and first[n_tiles] == n that covers every pick exactly once.
+//   pfac_scan_groups_kernel  the group prefixes and the total, which the host checks before anything is written
+//   pfac_tk_write_kernel     one wave per tile.  The tile's tokens are ids[base .. base + cnt), base = group prefix +
+//                            tile prefix.  A token's rank is its word's prefix + a popcount of the saved bitmap below its
+//                            bit; the values are staged in LDS in rank order, shifted by base & 3 so that LDS chunk c is
+//                            the aligned 16 bytes of the output, and stored as whole dwordx4 where all four entries are
+//                            the tile's, in pieces at the two ragged ends.  Byte tokens are staged first, then the pick
+//                            tokens over them (a kept pick start is the one emitting position whose byte is not its
+//                            value).  A lane whose 16 positions emit nothing loads no input.
+//   pfac_tk_doc_kernel       one thread per document: tok_off[d] = group prefix + tile prefix + word prefix + a popcount
+//                            of the word below off[d]; off[d] == n_owned gives the total.
+constexpr int TK_GROUP = 64;                        // tiles per workgroup of the count kernel (one group of the prefix)
+constexpr int TK_WAVES = 4;                         // its waves: 16 tiles each
+constexpr int TK_WORDS = WTILE / 64;                // bitmap words of a tile
+constexpr int TK_STAGE = WTILE + 4;                 // staged entries of the write: a full tile shifted by up to 3
+static_assert(TK_WORDS == WAVE, "a lane per bitmap word");
+
+__device__ __forceinline__ unsigned long long tk_below(unsigned bit) { return (1ull << bit) - 1ull; }   // bit < 64
+
+__global__ void pfac_tk_first_kernel(const pfac_record *sel, unsigned long long n, unsigned long long n_tiles,
+                                     unsigned long long *first) {
+    const unsigned long long t = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t > n_tiles) return;
+    unsigned long long lo = 0, hi = n;
+    if (t == n_tiles) lo = n;
+    const unsigned long long start = t * WTILE;
+    while (lo < hi) {
+        const unsigned long long m = lo + (hi - lo) / 2;
+        if ((unsigned long long)sel[m].pos < start) lo = m + 1;
+        else hi = m;
+    }
+    first[t] = lo;
+}
+
+// 16 input bytes at the 16-aligned position g; bytes at or past n_avail read as 0
+__device__ __forceinline__ uint4 tk_load16(const unsigned char *in, unsigned long long g, unsigned long long n_avail) {
+    if (g + 16 <= n_avail) return *reinterpret_cast<const uint4 *>(in + g);
+    unsigned v[4] = {0u, 0u, 0u, 0u};
+    for (int i = 0; i < 16; i++)
+        if (g + (unsigned)i < n_avail) v[i >> 2] |= (unsigned)in[g + (unsigned)i] << (8 * (i & 3));
+    return make_uint4(v[0], v[1], v[2], v[3]);
+}
+
+// the 16 positions from g on that lie in [entry, n_owned), as a mask
+__device__ __forceinline__ unsigned tk_domain16(unsigned long long g, unsigned long long entry, unsigned long long n_owned) {
+    const unsigned lo = entry > g ? (entry - g < 16 ? (unsigned)(entry - g) : 16u) : 0u;
+    const unsigned hi = n_owned > g ? (n_owned - g < 16 ? (unsigned)(n_owned - g) : 16u) : 0u;
+    return hi > lo ? ((1u << hi) - 1u) & ~((1u << lo) - 1u) : 0u;
+}
+
+__global__ void __launch_bounds__(TK_WAVES * WAVE)
+pfac_tk_count_kernel(const unsigned char *in, unsigned long long n_avail, const pfac_record *sel, unsigned long long n,
+                     unsigned long long entry, unsigned long long n_owned, unsigned long long n_tiles, const short *flen,
+                     const int *tok, const int *btok, unsigned num_final, const unsigned long long *first,
+                     unsigned long long *bm, unsigned short *wpre, unsigned *tpre, unsigned long long *gsum,
+                     unsigned long long *res) {
+    __shared__ int s_btok[256];
+    __shared__ unsigned long long s_cov[TK_WAVES][TK_WORDS], s_start[TK_WAVES][TK_WORDS], s_emit[TK_WAVES][TK_WORDS];
+    __shared__ unsigned s_cnt[TK_GROUP];
+    const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x >> 6;
+    s_btok[threadIdx.x] = btok[threadIdx.x];
+    __syncthreads();
+    bool bad = false;
+    for (int i = 0; i < TK_GROUP / TK_WAVES; i++) {
+        const unsigned lt = (unsigned)i * TK_WAVES + (unsigned)w;
+        const unsigned long long t = (unsigned long long)blockIdx.x * TK_GROUP + lt;
+        if (t >= n_tiles) {                                         // (wave-uniform)
+            if (lane == 0) s_cnt[lt] = 0u;
+            continue;
+        }
+        const unsigned long long tile_lo = t * WTILE, tile_hi = tile_lo + WTILE;
+        const unsigned long long own_hi = tile_hi < n_owned ? tile_hi : n_owned;
+        s_cov[w][lane] = 0ull;
+        s_start[w][lane] = 0ull;
+        wave_lds_sync();
+        const unsigned long long f0 = first[t], f1 = first[t + 1];
+        bad |= f0 > f1 || f1 > n;
+        const unsigned long long k1 = f1 < n ? f1 : n;
+        for (unsigned long long k = (f0 ? f0 - 1 : 0ull) + (unsigned)lane; k < k1; k += WAVE) {
+            const pfac_record r = sel[k];
+            const bool own = k >= f0;                               // else the pick in front of the tile's first
+            const unsigned long long p = r.pos;
+            int L = 0;
+            bool drop = true;
+            if (r.state < num_final) {
+                L = flen[r.state];
+                drop = tok[r.state] < 0;
+            }
+            if (own) {
+                unsigned long long prev = entry;
+                if (k > 0) {
+                    const pfac_record q = sel[k - 1];
+                    const int Lq = q.state < num_final ? (int)flen[q.state] : 0;
+                    prev = (unsigned long long)q.pos + (unsigned long long)(Lq > 0 ? Lq : 0);
+                }
+                bad |= r.state >= num_final || L < 1 || p < tile_lo || p >= own_hi || p < prev;
+                if (k + 1 == n) res[2] = p + (unsigned long long)(L > 0 ? L : 0);   // c_{n-1}
+            }
+            const unsigned long long a = p > tile_lo ? p : tile_lo;
+            const unsigned long long e = p + (unsigned long long)(L > 0 ? L : 0);
+            const unsigned long long b = e < tile_hi ? e : tile_hi;
+            if (a < b) {                                            // at most 17 words: patterns are shorter than HALO_MAX
+                const unsigned la = (unsigned)(a - tile_lo), lb = (unsigned)(b - tile_lo) - 1u;
+                for (unsigned x = la >> 6; x <= lb >> 6; x++) {
+                    unsigned long long m = ~0ull;
+                    if (x == la >> 6) m &= ~tk_below(la & 63u);
+                    if (x == lb >> 6 && (lb & 63u) != 63u) m &= tk_below((lb & 63u) + 1u);
+                    atomicOr(&s_cov[w][x], m);
+                }
+                if (own && !drop && p >= tile_lo && p < tile_hi)
+                    atomicOr(&s_start[w][(unsigned)(p - tile_lo) >> 6], 1ull << ((unsigned)(p - tile_lo) & 63u));
+            }
+        }
+        wave_lds_sync();
+#pragma unroll
+        for (int j = 0; j < SUBS; j++) {
+            const unsigned lp = (unsigned)j * SUB + (unsigned)lane * 16u, sh = lp & 63u;
+            const unsigned long long g = tile_lo + lp;
+            const unsigned dom = tk_domain16(g, entry, n_owned);
+            const unsigned cov = (unsigned)(s_cov[w][lp >> 6] >> sh) & 0xffffu;
+            const unsigned st = (unsigned)(s_start[w][lp >> 6] >> sh) & 0xffffu;
+            unsigned byte_bits = 0u;
+            if (dom & ~cov) {
+                const uint4 v = tk_load16(in, g, n_avail);
+                const unsigned q[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (int c = 0; c < 16; c++) byte_bits |= (unsigned)(s_btok[(q[c >> 2] >> (8 * (c & 3))) & 255u] >= 0) << c;
+            }
+            unsigned long long e = (unsigned long long)(((byte_bits & ~cov) | st) & dom) << sh;
+            e |= __shfl_xor(e, 1, WAVE);
+            e |= __shfl_xor(e, 2, WAVE);
+            if ((lane & 3) == 0) s_emit[w][lp >> 6] = e;
+        }
+        wave_lds_sync();
+        const unsigned long long word = s_emit[w][lane];
+        const unsigned c = (unsigned)__popcll(word), incl = wave_incl_scan(c);
+        bm[t * TK_WORDS + (unsigned)lane] = word;
+        wpre[t * TK_WORDS + (unsigned)lane] = (unsigned short)(incl - c);
+        if (lane == WAVE - 1) s_cnt[lt] = incl;
+    }
+    if (__ballot(bad) && lane == 0) atomicOr(&res[1], 1ull);
+    __syncthreads();
+    if (w == 0) {
+        const unsigned long long t = (unsigned long long)blockIdx.x * TK_GROUP + (unsigned)lane;
+        const unsigned c = s_cnt[lane], incl = wave_incl_scan(c);
+        if (t < n_tiles) tpre[t] = incl - c;
+        if (lane == WAVE - 1) gsum[blockIdx.x] = incl;
+    }
+}
+
+template <bool POS>
+__global__ void __launch_bounds__(WAVE)
+pfac_tk_write_kernel(const unsigned char *in, unsigned long long n_avail, const pfac_record *sel, unsigned num_final,
+                     const int *tok, const int *btok, const unsigned long long *first, const unsigned long long *bm,
+                     const unsigned short *wpre, const unsigned *tpre, const unsigned long long *gpre, int *ids,
+                     unsigned *pos) {
+    __shared__ int s_btok[256];
+    __shared__ unsigned long long s_bm[TK_WORDS];
+    __shared__ unsigned short s_pre[TK_WORDS];
+    __shared__ __attribute__((aligned(16))) int s_ids[TK_STAGE];
+    __shared__ __attribute__((aligned(16))) unsigned s_pos[POS ? TK_STAGE : 4];
+    const int lane = threadIdx.x;
+    const unsigned long long t = blockIdx.x;
+    const unsigned long long word = bm[t * TK_WORDS + (unsigned)lane];
+    const unsigned wp = wpre[t * TK_WORDS + (unsigned)lane];
+    const unsigned cnt = bcast_last(wp + (unsigned)__popcll(word));
+    if (cnt == 0) return;                                           // (wave-uniform)
+    const unsigned long long base = gpre[t / TK_GROUP] + tpre[t];
+    const unsigned a = (unsigned)(base & 3ull);
+    const unsigned long long tile_lo = t * WTILE;
+    s_bm[lane] = word;
+    s_pre[lane] = (unsigned short)wp;
+#pragma unroll
+    for (int i = 0; i < 4; i++) s_btok[i * WAVE + lane] = btok[i * WAVE + lane];
+    wave_lds_sync();
+#pragma unroll
+    for (int j = 0; j < SUBS; j++) {                                // the byte tokens, in rank order
+        const unsigned lp = (unsigned)j * SUB + (unsigned)lane * 16u, sh = lp & 63u;
+        const unsigned long long wv = s_bm[lp >> 6];
+        unsigned e = (unsigned)(wv >> sh) & 0xffffu;
+        if (!e) continue;
+        unsigned rank = a + s_pre[lp >> 6] + (unsigned)__popcll(wv & tk_below(sh));
+        const uint4 v = tk_load16(in, tile_lo + lp, n_avail);
+        const unsigned q[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int c = 0; c < 16; c++) {
+            if (e >> c & 1u) {
+                s_ids[rank] = s_btok[(q[c >> 2] >> (8 * (c & 3))) & 255u];
+                if constexpr (POS) s_pos[rank] = (unsigned)(tile_lo + lp + (unsigned)c);
+                rank++;
+            }
+        }
+    }
+    wave_lds_sync();
+    const unsigned long long f1 = first[t + 1];
+    for (unsigned long long k = first[t] + (unsigned)lane; k < f1; k += WAVE) {     // the kept picks, over their bytes
+        const pfac_record r = sel[k];
+        const unsigned lp = (r.pos - (unsigned)tile_lo) & (WTILE - 1u);
+        const unsigned long long wv = s_bm[lp >> 6];
+        const int v = r.state < num_final ? tok[r.state] : -1;
+        if (v >= 0 && (wv >> (lp & 63u) & 1ull)) {
+            const unsigned rank = a + s_pre[lp >> 6] + (unsigned)__popcll(wv & tk_below(lp & 63u));
+            s_ids[rank] = v;
+            if constexpr (POS) s_pos[rank] = (unsigned)tile_lo + lp;
+        }
+    }
+    wave_lds_sync();
+    const unsigned long long g0 = base - a;                         // a multiple of 4: ids + g0 is 16-B aligned
+    for (unsigned c = (unsigned)lane; c * 4u < a + cnt; c += WAVE) {
+        const unsigned s0 = c * 4u;
+        if (s0 >= a && s0 + 4u <= a + cnt) {
+            *reinterpret_cast<uint4 *>(ids + g0 + s0) = *reinterpret_cast<const uint4 *>(&s_ids[s0]);
+            if constexpr (POS) *reinterpret_cast<uint4 *>(pos + g0 + s0) = *reinterpret_cast<const uint4 *>(&s_pos[s0]);
+        } else {
+            for (unsigned x = s0; x < s0 + 4u; x++) {
+                if (x >= a && x < a + cnt) {
+                    ids[g0 + x] = s_ids[x];
+                    if constexpr (POS) pos[g0 + x] = s_pos[x];
+                }
+            }
+        }
+    }
+}
+
+__global__ void pfac_tk_doc_kernel(const unsigned long long *off, unsigned long long n_docs, unsigned long long n_owned,
+                                   unsigned long long n_tiles, unsigned n_groups, const unsigned long long *bm,
+                                   const unsigned short *wpre, const unsigned *tpre, const unsigned long long *gpre,
+                                   unsigned long long *tok_off) {
+    const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
+    for (unsigned long long d = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; d <= n_docs; d += stride) {
+        const unsigned long long o = off[d], t = o >> 12;
+        unsigned long long v = gpre[n_groups];                      // the total: off[d] == n_owned (or no tile at all)
+        if (o < n_owned && t < n_tiles) {
+            const unsigned x = (unsigned)(o & (WTILE - 1u)) >> 6;
+            v = gpre[t / TK_GROUP] + tpre[t] + wpre[t * TK_WORDS + x] +
+                (unsigned long long)__popcll(bm[t * TK_WORDS + x] & tk_below((unsigned)o & 63u));
+        }
+        tok_off[d] = v;
+    }
+}
+
+// ---------------------------------------------------------------------------
 // runtime
 
 thread_local std::string g_err;
@@ -5224,6 +5480,14 @@ struct Slot {
     DevBuf<unsigned long long> ga_x;      // X per block of 64 ids
     PassOut<unsigned char> ga_out;        // the bytes, ...
     PassOut<unsigned long long> ga_off;   // ... and the output offsets (n_ids + 1 entries)
+    // pfac_tokenize_leftmost_longest / pfac_tokenize_documents
+    DevBuf<unsigned long long> tk_first;  // per tile: its first pick (n_tiles + 1 entries), ...
+    DevBuf<unsigned long long> tk_bm;     // ... its 64 words of emitting positions, ...
+    DevBuf<unsigned short> tk_wpre;       // ... the tokens in front of each word, ...
+    DevBuf<unsigned> tk_tpre;             // ... and the tokens in front of the tile in its group of 64
+    PassOut<int> tk_ids;                  // the token ids, ...
+    PassOut<unsigned> tk_pos;             // ... their positions (PFAC_TOKENS_POSITIONS), ...
+    PassOut<unsigned long long> tk_off;   // ... and the documents' token offsets (n_docs + 1 entries)
 };
 
 struct StageLayout {                      // per-wave LDS of one staging mode
@@ -5286,7 +5550,7 @@ struct pfac_ctx {
     TablePlan plan;
     bool have_table = false;
     uint64_t table_gen = 0;               // installs begun so far: a scan's final states index the lengths of ITS table only
-    // ... what the caller attaches to it (an upload drops all eight), ...
+    // ... what the caller attaches to it (an upload drops all ten), ...
     DevBuf<short> flen;                   // pattern length of every final state (pfac_table_set_final_lengths)
     DevBuf<unsigned> rep_off;             // replacement of every final state (pfac_table_set_replacements): offsets[num_final + 1]
     DevBuf<unsigned char> rep;            // ... and the bytes, zero-padded to its capacity (a multiple of 16)
@@ -5295,6 +5559,8 @@ struct pfac_ctx {
     DevBuf<unsigned long long> gmask;     // group set of every final state (pfac_table_set_state_groups)
     DevBuf<int> sweight;                  // weight of every final state (pfac_table_set_state_weights)
     DevBuf<uint4> spans;                  // span of every final state (pfac_table_set_state_spans): pfac_state_span as one dwordx4
+    DevBuf<int> tok;                      // token id of every final state (pfac_table_set_token_ids), PFAC_TOKEN_DROP = none, ...
+    DevBuf<int> btok;                     // ... and of every byte value (256 entries; all DROP when the caller gave none)
     unsigned fold = PFAC_FOLD_NONE;       // case fold of the scans to come (pfac_table_set_case_fold)
     // ... and what adapts to the match density seen by the last scan (pfac_scan_finish)
     bool dense = false;                   // staging mode
@@ -5836,6 +6102,7 @@ int install_table(pfac_ctx *ctx, const int *d_blob, const int32_t *hdr, size_t n
     ctx->gmask.reset();                                     // ... and the state groups
     ctx->sweight.reset();                                   // ... and the state weights
     ctx->spans.reset();                                     // ... and the state spans
+    ctx->tok.reset(); ctx->btok.reset();                    // ... and the token ids
     ctx->have_table = false; ctx->table_gen++;
     TablePlan P;
     if (int rc = build_plan(ctx, P, d_blob, hdr, stream)) return rc;
@@ -8032,6 +8299,189 @@ int pfac_extract_offsets_d2h(pfac_ctx *ctx, int slot, uint64_t *host_pick_offset
     if (rc) return rc;
     Slot &s = ctx->slots[slot];
     return fetch(ctx, s, s.ex_off, "pfac_extract_offsets_d2h", "pfac_extract_leftmost_longest", host_pick_offsets, 0, s.ex_off.n);
+}
+
+// The token ids: checked whole, made aside, swapped in together; the old buffers are freed behind that (hipFree waits
+// for the device), as the replacements are.
+int pfac_table_set_token_ids(pfac_ctx *ctx, const int32_t *state_ids, uint64_t n_states, const int32_t *byte_ids) {
+    if (!ctx) return fail(nullptr, PFAC_E_ARG, "null context");
+    const std::string fn = "pfac_table_set_token_ids";
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (!ctx->have_table) return fail(ctx, PFAC_E_STATE, fn + " before a table upload");
+    if (n_states != (uint64_t)ctx->plan.base.num_final || (!state_ids && n_states))
+        return fail(ctx, PFAC_E_ARG, fn + ": need num_final state ids (num_final " + std::to_string(ctx->plan.base.num_final) + ")");
+    for (uint64_t i = 0; i < n_states; i++)
+        if (state_ids[i] < PFAC_TOKEN_DROP)
+            return fail(ctx, PFAC_E_ARG, fn + ": the id of final state " + std::to_string(i) + " is neither >= 0 nor PFAC_TOKEN_DROP");
+    int32_t bytes[256];
+    for (int b = 0; b < 256; b++) {
+        bytes[b] = byte_ids ? byte_ids[b] : PFAC_TOKEN_DROP;
+        if (bytes[b] < PFAC_TOKEN_DROP)
+            return fail(ctx, PFAC_E_ARG, fn + ": the id of byte " + std::to_string(b) + " is neither >= 0 nor PFAC_TOKEN_DROP");
+    }
+    USE_DEVICE(ctx);
+    DevBuf<int> tok, btok;
+    const uint64_t n = std::max<uint64_t>(n_states, 1);
+    int rc = tok.ensure(ctx, nullptr, n, n);
+    if (!rc) rc = btok.ensure(ctx, nullptr, 256, 256);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemset(tok.p, 0xff, n * 4));
+    if (n_states) HIP_TRY(ctx, hipMemcpy(tok.p, state_ids, n_states * 4, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(btok.p, bytes, sizeof bytes, hipMemcpyHostToDevice));
+    ctx->tok = std::move(tok);                              // (a swap: the old buffers go with the two locals)
+    ctx->btok = std::move(btok);
+    return PFAC_OK;
+}
+
+// The documents of pfac_tokenize_documents as the caller passed them (NULL: the slot's offsets / doc_first of the
+// selection, the slot-owned token offsets); tk_run without them is pfac_tokenize_leftmost_longest.
+struct TkDocs {
+    const uint64_t *off, *first;
+    uint64_t *tok_off;
+};
+
+static int tk_run(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *d_input, const pfac_record *d_sel, uint32_t flags,
+                  int32_t *d_ids, uint64_t out_cap, uint32_t *d_pos, uint64_t *n_tokens, const TkDocs *docs) {
+    s.tk_ids.invalidate();
+    s.tk_pos.invalidate();
+    s.tk_off.invalidate();
+    if (!s.scanned || !s.ll_out.done || s.ll_seq != s.scan_seq || (docs && !s.ll_docs))
+        return fail(ctx, PFAC_E_STATE, fn + (docs ? " needs a pfac_records_leftmost_longest_documents since the slot's last scan"
+                                                  : " needs a pfac_records_leftmost_longest since the slot's last scan"));
+    if (!ctx->have_table || s.last_table != ctx->table_gen)
+        return fail(ctx, PFAC_E_STATE, fn + ": the selection was made with an earlier table");
+    if (!ctx->tok.p) return fail(ctx, PFAC_E_STATE, fn + ": no token ids for the uploaded table (pfac_table_set_token_ids)");
+    if (!ctx->flen.p) return fail(ctx, PFAC_E_STATE, fn + ": no final-state lengths for the uploaded table");
+    const pfac_record *sel;
+    int rc = s.ll_out.consume(ctx, fn, "selection (d_sel)", d_sel, ANY_N, &sel);
+    if (rc) return rc;
+    const bool want_pos = flags & PFAC_TOKENS_POSITIONS;
+    if (flags & ~PFAC_TOKENS_POSITIONS) return fail(ctx, PFAC_E_ARG, fn + ": unknown flags");
+    if (d_pos && !want_pos) return fail(ctx, PFAC_E_ARG, fn + ": d_pos without PFAC_TOKENS_POSITIONS");
+    const unsigned char *in = d_input ? static_cast<const unsigned char *>(d_input) : s.input.p;
+    const uint64_t n = s.ll_out.n, n_owned = s.last_owned, n_avail = s.last_avail, entry = s.ll_entry, ex = s.ll_exit;
+    if (((uintptr_t)d_ids & 15) || ((uintptr_t)d_pos & 15) || ((uintptr_t)in & 15) || ((uintptr_t)d_sel & 7))
+        return fail(ctx, PFAC_E_ARG, fn + ": misaligned buffer (d_input, d_ids and d_pos 16 B, d_sel 8 B)");
+    if (n_owned > entry && !in) return fail(ctx, PFAC_E_ARG, fn + ": no input buffer");
+    if (!d_input && n_avail > s.input.cap) return fail(ctx, PFAC_E_ARG, fn + ": the scan read more than the slot's input buffer holds");
+    const unsigned long long *doff = nullptr, *dfirst = nullptr;
+    unsigned long long *dtok_off = nullptr;
+    if (docs) {
+        doff = reinterpret_cast<const unsigned long long *>(docs->off);
+        dtok_off = reinterpret_cast<unsigned long long *>(docs->tok_off);
+        if (!doff) {
+            if (!s.lld_own_off) return fail(ctx, PFAC_E_STATE, fn + ": the selection cut the caller's document offsets; pass them as d_doc_offsets");
+            if (s.lld_gen != s.doc_gen || !s.doc.done) return fail(ctx, PFAC_E_STATE, fn + ": the slot's document offsets changed since the selection");
+            doff = s.doc.buf.p;
+        }
+        rc = s.lld_first.consume(ctx, fn, "doc_first of the selection (d_doc_first)", docs->first, ANY_N, &dfirst);
+        if (rc) return rc;
+        if (((uintptr_t)doff & 7) || ((uintptr_t)dfirst & 7) || ((uintptr_t)dtok_off & 7))
+            return fail(ctx, PFAC_E_ARG, fn + ": device buffers must be 8-byte aligned");
+    }
+    USE_DEVICE(ctx);
+    const uint64_t n_tiles = (n_owned + WTILE - 1) / WTILE, n_groups = (n_tiles + TK_GROUP - 1) / TK_GROUP;
+    uint64_t nt = 0;
+    if (n_tiles) {
+        rc = s.tk_first.ensure(ctx, s.stream, n_tiles + 1, quarter_more(n_tiles + 1));
+        if (!rc) rc = s.tk_bm.ensure(ctx, s.stream, n_tiles * TK_WORDS, quarter_more(n_tiles) * TK_WORDS);
+        if (!rc) rc = s.tk_wpre.ensure(ctx, s.stream, n_tiles * TK_WORDS, quarter_more(n_tiles) * TK_WORDS);
+        if (!rc) rc = s.tk_tpre.ensure(ctx, s.stream, n_tiles, quarter_more(n_tiles));
+        if (!rc) rc = ensure_gsum(ctx, s, (unsigned)n_groups + 2);      // group prefixes, the total, error flag, c_{n-1}
+        if (rc) return rc;
+        unsigned long long *res = s.gsum.p + n_groups;
+        HIP_TRY(ctx, hipMemsetAsync(res, 0, 24, s.stream));
+        hipLaunchKernelGGL(pfac_tk_first_kernel, dim3((unsigned)((n_tiles + 1 + 255) / 256)), dim3(256), 0, s.stream, sel,
+                           (unsigned long long)n, (unsigned long long)n_tiles, s.tk_first.p);
+        hipLaunchKernelGGL(pfac_tk_count_kernel, dim3((unsigned)n_groups), dim3(TK_WAVES * WAVE), 0, s.stream, in,
+                           (unsigned long long)n_avail, sel, (unsigned long long)n, (unsigned long long)entry,
+                           (unsigned long long)n_owned, (unsigned long long)n_tiles, ctx->flen.p, ctx->tok.p, ctx->btok.p,
+                           (unsigned)ctx->plan.base.num_final, s.tk_first.p, s.tk_bm.p, s.tk_wpre.p, s.tk_tpre.p, s.gsum.p, res);
+        hipLaunchKernelGGL(pfac_scan_groups_kernel, dim3(1), dim3(1024), 0, s.stream, s.gsum.p, (unsigned)n_groups);
+        rc = pass_words(ctx, s, res, 3);
+        if (rc) return rc;
+        nt = host_u64(s, H_PASS);
+        const uint64_t err = host_u64(s, H_PASS1), c_last = host_u64(s, H_PASS2);
+        if (err || (n && (c_last > n_owned ? c_last - n_owned : 0) != ex))
+            return fail(ctx, PFAC_E_ARG, fn + ": the selection is not one of this scan and table");
+    } else if (n) {
+        return fail(ctx, PFAC_E_ARG, fn + ": the selection is not one of this scan and table");
+    }
+    *n_tokens = nt;
+    if ((d_ids || d_pos) && nt > out_cap)
+        return fail(ctx, PFAC_E_OVERFLOW, fn + ": " + std::to_string(nt) + " tokens, out_cap is " + std::to_string(out_cap));
+    const uint64_t n_docs = docs ? s.lld_first.n - 1 : 0;
+    const uint64_t cap = align_up(nt + nt / 8, 1024);
+    int *ids = nullptr;
+    unsigned *pos = nullptr;
+    unsigned long long *toff = nullptr;
+    rc = s.tk_ids.bind(ctx, s.stream, d_ids, nt, cap, &ids);       // (everything allocated before the first write)
+    if (!rc && want_pos) rc = s.tk_pos.bind(ctx, s.stream, d_pos, nt, cap, &pos);
+    if (!rc && docs) rc = s.tk_off.bind(ctx, s.stream, dtok_off, n_docs + 1, docs_cap(n_docs), &toff);
+    if (rc) return rc;
+    if (nt) {
+        if (want_pos)
+            hipLaunchKernelGGL(pfac_tk_write_kernel<true>, dim3((unsigned)n_tiles), dim3(WAVE), 0, s.stream, in,
+                               (unsigned long long)n_avail, sel, (unsigned)ctx->plan.base.num_final, ctx->tok.p, ctx->btok.p,
+                               s.tk_first.p, s.tk_bm.p, s.tk_wpre.p, s.tk_tpre.p, s.gsum.p, ids, pos);
+        else
+            hipLaunchKernelGGL(pfac_tk_write_kernel<false>, dim3((unsigned)n_tiles), dim3(WAVE), 0, s.stream, in,
+                               (unsigned long long)n_avail, sel, (unsigned)ctx->plan.base.num_final, ctx->tok.p, ctx->btok.p,
+                               s.tk_first.p, s.tk_bm.p, s.tk_wpre.p, s.tk_tpre.p, s.gsum.p, ids, pos);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    if (docs) {
+        if (n_tiles) {
+            const unsigned oblocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_docs + 1 + 255) / 256, 65536));
+            hipLaunchKernelGGL(pfac_tk_doc_kernel, dim3(oblocks), dim3(256), 0, s.stream, doff, (unsigned long long)n_docs,
+                               (unsigned long long)n_owned, (unsigned long long)n_tiles, (unsigned)n_groups, s.tk_bm.p,
+                               s.tk_wpre.p, s.tk_tpre.p, s.gsum.p, toff);
+            HIP_TRY(ctx, hipGetLastError());
+        } else {
+            HIP_TRY(ctx, hipMemsetAsync(toff, 0, (n_docs + 1) * 8, s.stream));
+        }
+        s.tk_off.commit(n_docs + 1, !dtok_off);
+    }
+    if (want_pos) s.tk_pos.commit(nt, !d_pos);
+    s.tk_ids.commit(nt, !d_ids);
+    return PFAC_OK;
+}
+
+int pfac_tokenize_leftmost_longest(pfac_ctx *ctx, int slot, const void *d_input, const pfac_record *d_sel, uint32_t flags,
+                                   int32_t *d_ids, uint64_t out_cap, uint32_t *d_pos, uint64_t *n_tokens) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    if (!n_tokens) return fail(ctx, PFAC_E_ARG, "null argument");
+    *n_tokens = 0;
+    return tk_run(ctx, ctx->slots[slot], "pfac_tokenize_leftmost_longest", d_input, d_sel, flags, d_ids, out_cap, d_pos, n_tokens, nullptr);
+}
+
+int pfac_tokenize_documents(pfac_ctx *ctx, int slot, const void *d_input, const pfac_record *d_sel, const uint64_t *d_doc_offsets,
+                            const uint64_t *d_doc_first, uint32_t flags, int32_t *d_ids, uint64_t out_cap, uint32_t *d_pos,
+                            uint64_t *d_tok_offsets, uint64_t *n_tokens) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    if (!n_tokens) return fail(ctx, PFAC_E_ARG, "null argument");
+    *n_tokens = 0;
+    const TkDocs docs{d_doc_offsets, d_doc_first, d_tok_offsets};
+    return tk_run(ctx, ctx->slots[slot], "pfac_tokenize_documents", d_input, d_sel, flags, d_ids, out_cap, d_pos, n_tokens, &docs);
+}
+
+int pfac_tokens_d2h(pfac_ctx *ctx, int slot, int32_t *host_ids, uint32_t *host_pos, uint64_t first, uint64_t n) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    Slot &s = ctx->slots[slot];
+    const char *fn = "pfac_tokens_d2h", *pass = "pfac_tokenize_leftmost_longest / pfac_tokenize_documents";
+    rc = fetch(ctx, s, s.tk_ids, fn, pass, host_ids, first, n);
+    if (rc || !host_pos) return rc;
+    return fetch(ctx, s, s.tk_pos, fn, "tokenize pass with PFAC_TOKENS_POSITIONS", host_pos, first, n);
+}
+
+int pfac_tokens_offsets_d2h(pfac_ctx *ctx, int slot, uint64_t *host_tok_off) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    Slot &s = ctx->slots[slot];
+    return fetch(ctx, s, s.tk_off, "pfac_tokens_offsets_d2h", "pfac_tokenize_documents", host_tok_off, 0, s.tk_off.n);
 }
 
 int pfac_fill_tiled(pfac_ctx *ctx, int slot, void *d_dst, uint64_t n, const void *host_pattern, uint32_t period, uint64_t phase) {

@@ -19,7 +19,8 @@ from ._ffi import (PFAC_LINE_CONTEXT_SEP, PFAC_LINE_MAX_GROUP_SEP, PFAC_LINE_NUM
                    PFAC_LINE_TERMINATE, CDocScore, CLineFormat, CScoreRule)
 from ._ffi import PFAC_TOP_BY_COUNT, PFAC_TOP_LOWEST, PFAC_TOP_RANKED
 from ._ffi import PFAC_TERMS_SELECTION
-from .table import RECORD_DTYPE, SCORE_DTYPE, TEMPLATE_PLAIN, PfacTable, redaction_table, replacement_table, template_table, _state_lengths
+from ._ffi import PFAC_TOKENS_POSITIONS
+from .table import RECORD_DTYPE, SCORE_DTYPE, TEMPLATE_PLAIN, TOKEN_DROP, PfacTable, redaction_table, replacement_table, template_table, token_table, _state_lengths
 
 
 def device_count() -> int:
@@ -1281,6 +1282,118 @@ class GpuMatcher:
         n = self.replace_selection_documents(slot=slot)
         out_off = self.replacement_doc_offsets_to_host(n_docs, slot)
         return out_off, self.replacement_to_host(n, slot)
+
+    # -- tokenization: the token ids of the leftmost-longest picks -----------
+    def set_token_ids(self, ids, byte_ids=None, byte_base: Optional[int] = None, drop_bytes: bytes = b"") -> None:
+        """The token id of every pattern of the uploaded table (``token_table``: a dict {pattern id: token id} or one
+        entry per line; patterns not named emit nothing) and of every byte outside a pick: ``byte_ids`` an explicit
+        array of 256 entries, or ``byte_base=B`` for ``B + b``; neither = every byte is dropped.  ``drop_bytes``
+        overrides the entries of those bytes to TOKEN_DROP (whitespace, say).  Kept on the device until the next table
+        upload."""
+        if self.table is None:
+            raise PfacError(-7, "no host table to map pattern ids to states (load_table first)")
+        if byte_ids is not None and byte_base is not None:
+            raise ValueError("byte_ids and byte_base exclude each other")
+        tok = np.ascontiguousarray(token_table(self.table, ids), dtype=np.int32)
+        btok = None
+        if byte_ids is not None:
+            btok = np.array(byte_ids, dtype=np.int32)
+            if btok.shape != (256,):
+                raise ValueError("byte_ids holds 256 entries")
+        elif byte_base is not None:
+            btok = (int(byte_base) + np.arange(256, dtype=np.int64)).astype(np.int32)
+        if btok is not None and len(drop_bytes):
+            btok[np.frombuffer(bytes(drop_bytes), dtype=np.uint8)] = TOKEN_DROP
+        self._check(self._L.pfac_table_set_token_ids(self._ctx, tok.ctypes.data if tok.size else None, tok.size,
+                                                     btok.ctypes.data if btok is not None else None))
+
+    def tokenize_selection(self, d_input=None, d_ids=None, out_cap: int = 0, d_pos=None, positions: bool = False,
+                           slot: int = 0, d_sel=None) -> int:
+        """The token ids of the slot's last ``select_leftmost_longest`` on the GPU (``pfac_tokenize_leftmost_longest``):
+        a pick's token at its start, a byte's token outside every pick, from the selection's entry to n_owned.  Returns
+        the number of tokens.  ``d_ids`` / ``d_pos`` None = slot-owned buffers (``tokens_to_host``); positions are
+        written with ``positions`` (implied by ``d_pos``).  A too small ``out_cap`` raises PfacError(PFAC_E_OVERFLOW)
+        whose ``n_tokens`` attribute holds the exact count."""
+        n = C.c_uint64(0)
+        flags = PFAC_TOKENS_POSITIONS if (positions or d_pos is not None) else 0
+        rc = self._L.pfac_tokenize_leftmost_longest(self._ctx, slot, _ptr(d_input), _ptr(d_sel), flags, _ptr(d_ids),
+                                                    int(out_cap), _ptr(d_pos), C.byref(n))
+        return self._counted(rc, n, "n_tokens")
+
+    def tokenize_selection_documents(self, d_input=None, d_ids=None, out_cap: int = 0, d_pos=None, positions: bool = False,
+                                     d_tok_offsets=None, slot: int = 0, d_sel=None, d_doc_offsets=None, d_doc_first=None) -> int:
+        """``tokenize_selection`` over the slot's last ``select_leftmost_longest_documents``, plus the documents' token
+        offsets (``d_tok_offsets`` None = a slot-owned buffer, ``token_offsets_to_host``): document d's tokens are
+        ``ids[tok_off[d]:tok_off[d + 1]]``.  ``d_doc_offsets`` / ``d_doc_first``: the buffers the selection was given
+        (None = the slot's).  Returns the number of tokens; overflow as ``tokenize_selection``."""
+        n = C.c_uint64(0)
+        flags = PFAC_TOKENS_POSITIONS if (positions or d_pos is not None) else 0
+        rc = self._L.pfac_tokenize_documents(self._ctx, slot, _ptr(d_input), _ptr(d_sel), _ptr(d_doc_offsets), _ptr(d_doc_first),
+                                             flags, _ptr(d_ids), int(out_cap), _ptr(d_pos), _ptr(d_tok_offsets), C.byref(n))
+        return self._counted(rc, n, "n_tokens")
+
+    def tokens_to_host(self, n: int, positions: bool = False, slot: int = 0, first: int = 0):
+        """Tokens [first, first + n) of the slot's last tokenize pass into its slot-owned buffers: ids int32[n], or
+        (ids, pos uint32[n]) with ``positions``."""
+        if positions:
+            return self._to_host(slot, lambda a, b: self._L.pfac_tokens_d2h(self._ctx, slot, a, b, int(first), int(n)),
+                                 (n, np.int32), (n, np.uint32))
+        return self._to_host(slot, lambda a: self._L.pfac_tokens_d2h(self._ctx, slot, a, None, int(first), int(n)), (n, np.int32))
+
+    def token_offsets_to_host(self, n_docs: int, slot: int = 0) -> np.ndarray:
+        """The token offsets (uint64[n_docs + 1]) of the slot's last ``tokenize_selection_documents``."""
+        return self._to_host(slot, lambda p: self._L.pfac_tokens_offsets_d2h(self._ctx, slot, p), (int(n_docs) + 1, np.uint64))
+
+    def tokenize(self, data, n_owned: Optional[int] = None, entry: int = 0, whole_words=False, prev_byte: int = -1,
+                 next_byte: int = -1, positions: bool = False, slot: int = 0):
+        """H2D + scan + selection + tokenization of one host buffer (``n_owned`` < len(data) leaves the rest as halo).
+        Returns (ids, exit), or (ids, pos, exit) with ``positions``: ``exit`` is the ``entry`` of the range that
+        follows.  ``whole_words`` (True, or the word bytes): only whole-word matches become vocabulary tokens;
+        ``prev_byte`` / ``next_byte`` as in ``scan_leftmost_longest``."""
+        buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data.view(np.uint8).ravel()
+        n_avail = int(buf.size)
+        n_owned = n_avail if n_owned is None else int(n_owned)
+        self._ensure_final_lengths()
+        self.reserve(slot, max(n_avail, 1), max(n_avail // 8, 4096))
+        if n_avail:
+            self.h2d(buf, slot)
+        self.scan_resident(n_owned, n_avail, slot=slot)
+        if whole_words is not False:
+            self.filter_whole_words(slot, _word_bytes(whole_words), prev_byte=prev_byte, next_byte=next_byte)
+        _, ex = self.select_leftmost_longest(entry, slot=slot)
+        n = self.tokenize_selection(positions=positions, slot=slot)
+        out = self.tokens_to_host(n, positions, slot)
+        return (out[0], out[1], ex) if positions else (out, ex)
+
+    def _tokenize_docs(self, offsets, n_docs: int, positions: bool, slot: int):
+        self.select_leftmost_longest_documents(n_docs, slot=slot)
+        n = self.tokenize_selection_documents(positions=positions, slot=slot)
+        tok_off = self.token_offsets_to_host(n_docs, slot)
+        if not positions:
+            return self.tokens_to_host(n, False, slot), tok_off
+        ids, pos = self.tokens_to_host(n, True, slot)
+        if n:
+            if offsets is None:
+                offsets = self.doc_offsets_to_host(n_docs, slot)
+            doc = np.repeat(np.arange(n_docs, dtype=np.int64), np.diff(tok_off.astype(np.int64)))
+            pos -= offsets[doc].astype(np.uint32)
+        return ids, pos, tok_off
+
+    def tokenize_documents(self, docs, whole_words=False, spans: bool = False, line_match: bool = False,
+                           positions: bool = False, slot: int = 0):
+        """Tokenization of a batch of independent documents (``docs`` as ``scan_documents`` takes it) in one scan.
+        Returns (ids, tok_off uint64[n_docs + 1]) -- document d's tokens are ``ids[tok_off[d]:tok_off[d + 1]]``, what
+        ``tokenize`` of each document alone returns -- or (ids, pos, tok_off) with ``positions``, the positions relative
+        to the document."""
+        offsets, n_docs = self._scan_docs(docs, slot, whole_words, spans, line_match)
+        return self._tokenize_docs(offsets, n_docs, positions, slot)
+
+    def tokenize_lines(self, data, delimiter=b"\n", whole_words=False, spans: bool = False, line_match: bool = False,
+                       positions: bool = False, slot: int = 0):
+        """``tokenize_documents`` of one buffer cut into lines at ``delimiter`` on the device.  With ``whole_words`` only
+        dictionary words on word boundaries become vocabulary tokens (the pre-tokenized MaxMatch)."""
+        _, n_docs = self._scan_lines(data, delimiter, slot, whole_words, fetch_offsets=False, spans=spans, line_match=line_match)
+        return self._tokenize_docs(None, n_docs, positions, slot)
 
     # -- synthetic inputs (device resident) --------------------------------
     def fill_tiled(self, d_dst, n: int, pattern: bytes, phase: int = 0, slot: int = 0) -> None:

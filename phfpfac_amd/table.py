@@ -405,6 +405,34 @@ def replacement_table(table: "PfacTable", replacements) -> tuple:
     return offsets, b"".join(parts)
 
 
+TOKEN_DROP = -1                      # PFAC_TOKEN_DROP: the state (or byte) emits no token
+
+
+def token_table(table: "PfacTable", ids) -> np.ndarray:
+    """-> int32[num_final]: the token id of every final state, for ``pfac_table_set_token_ids``.  ``ids`` is a dict
+    {pattern id: token id} or a sequence with one entry per line of the pattern file, in file order (``ids[id - 1]``;
+    None = none given).  A state gets the token of ``idmap[s]`` exactly as ``replacement_table`` maps a replacement:
+    the winning line of duplicates, the first (lowest) id of a character-class state.  Patterns that are not named, and
+    unreachable states, are TOKEN_DROP.  A token id is >= 0 or TOKEN_DROP (else ValueError) and fits int32."""
+    lens = _state_lengths(table)
+    idmap = np.asarray(table.idmap, dtype=np.int64)
+    if isinstance(ids, dict):
+        get = ids.get
+    else:
+        seq = list(ids)
+        get = lambda i: seq[i - 1] if 1 <= i <= len(seq) else None   # noqa: E731
+    out = np.full(int(table.num_final), TOKEN_DROP, dtype=np.int32)
+    for s in range(int(table.num_final)):
+        if lens[s] >= 1:
+            t = get(int(idmap[s]))
+            if t is not None:
+                t = int(t)
+                if t < TOKEN_DROP or t >= 2**31:
+                    raise ValueError(f"the token id of pattern id {int(idmap[s])} is neither in [0, 2^31) nor TOKEN_DROP")
+                out[s] = t
+    return out
+
+
 TEMPLATE_PLAIN = 0xFFFFFFFF          # PFAC_TEMPLATE_PLAIN: the state's replacement does not quote the match
 
 
