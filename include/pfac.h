@@ -891,6 +891,81 @@ int pfac_documents_term_counts(pfac_ctx *ctx, int slot, const pfac_record *d_sel
 int pfac_documents_term_counts_d2h(pfac_ctx *ctx, int slot, uint64_t *host_row_ptr, uint32_t *host_states,
                                    uint32_t *host_counts);
 
+/* Proximity rules: WHERE the pattern groups of a document occur relative to each other -- a card number within 60 bytes
+ * of "expires", the within: of two contents of one rule, NEAR/n, "BEGIN before END on the same line".  The group masks
+ * say that both halves occur in a document; this pass says that they occur together, and in which order.  The classes
+ * are the state groups (pfac_table_set_state_groups); the input is a record array that is already cut per document,
+ * exactly as pfac_documents_term_counts takes it -- but here the positions are read.
+ *   d_sel, d_doc_first  both non-NULL = the caller's device arrays, 8-B aligned (d_doc_first[n_docs] is read back first,
+ *                  to size the launch); both NULL, flags 0 = the slot-owned result of the slot's last
+ *                  pfac_records_segment; both NULL, PFAC_NEAR_SELECTION = the slot-owned per-document selection --
+ *                  under the staleness rules of pfac_documents_term_counts (PFAC_E_STATE), and both NULL with an n_docs
+ *                  that is not that call's, or one NULL and one not, gives PFAC_E_ARG.  n_docs < 2^32 and
+ *                  N = d_doc_first[n_docs] < 2^32.  Within a document the positions must not decrease: both producers
+ *                  guarantee it, and it holds for document-relative positions (the segment pass) and stream-relative
+ *                  ones (the selection) alike, because only differences inside one document are used
+ *   rules          HOST array of n_rules <= PFAC_NEAR_MAX_RULES rules, copied at the call (the caller may free it when
+ *                  the call returns).  With A_r(i) = groups[state_i] & a_groups != 0 and B_r likewise,
+ *   rule r fires in document d iff there are two DISTINCT records i < j in [doc_first[d], doc_first[d + 1]) with
+ *                  pos[j] - pos[i] <= max_dist and
+ *                    ordered (PFAC_NEAR_ORDERED):  A_r(i) && B_r(j)
+ *                    unordered:                    (A_r(i) && B_r(j)) || (B_r(i) && A_r(j))
+ *   result         mask[d] has bit r set iff rule r fired in d; a document without records gets 0; *any_mask is the OR
+ *                  of all masks.  n_rules == 0 gives all-zero masks
+ *   d_masks_out    NULL = a slot-owned buffer grown to fit (pfac_near_masks_d2h, pfac_slot_near_masks); else a device
+ *                  pointer, 8-B aligned: exactly n_docs x 8 bytes are written
+ * Two decisions.  "Precedes" (i < j) is the order of the record array, which is (position, pattern length): at equal
+ * starts the shorter pattern is the earlier record, so an ordered rule whose A and B start at one byte fires iff the A
+ * is the shorter; unordered rules do not depend on it, and over the selection no two records share a start.  And a
+ * record never pairs with itself: A and B may overlap, and a rule with a_groups == b_groups means "two occurrences
+ * within max_dist".  max_dist is the start-to-start distance in bytes, inclusive; 0 is legal (two records at one
+ * start); PFAC_NEAR_ANY_DIST makes an ordered rule "an A somewhere before a B in this document".  A rule whose a_groups
+ * or b_groups is 0 never fires.  Not in the rule, on purpose: a minimum distance, and distances measured from the END
+ * of A -- with a maximum only the nearest earlier partner is always the best one, which is what keeps the pass at
+ * O(N x n_rules).
+ * Judged in this order -- PFAC_E_STATE: no table, no state groups for the current table, a slot-owned input that is
+ * missing, stale or from an earlier table; PFAC_E_ARG: misaligned buffers, one input NULL and the other not, call flags
+ * outside 0..1, an n_docs that is not the slot-owned input's, n_docs or N >= 2^32, n_rules > 64, rules == NULL with
+ * n_rules > 0, a rule with flags outside 0..1 or reserved != 0; and, checked on the device: d_doc_first[0] != 0, a
+ * d_doc_first that decreases, a state at or above num_final, a position that decreases inside a document.  Every error
+ * leaves a caller's d_masks_out untouched (the masks are made in the slot's buffer and copied behind the host's check,
+ * as pfac_documents_group_masks does).  n_docs == 0 writes nothing and sets *any_mask = 0.
+ * A pass of its own, with the lifetime rule of pfac_segment_d2h: it discards no other pass's result and is discarded by
+ * none; a failed call discards its own slot-owned result.  Returns once *any_mask and the error word are known (one
+ * 16-byte copy back); the masks are then complete on the slot's stream.  The same call on the same input gives the same
+ * bytes.
+ * Kernels, over blocks of 4096 records: (1) one wave per block writes, per rule and side, the index and position of
+ * the block's last A / last B -- walking its chunks of 64 from the end, and only for the rules still without one;
+ * (2) one workgroup per (rule, side) turns those into every block's carry-in, an exclusive "last non-empty"; (3) the
+ * pass, one wave per block and one read of the records: per chunk of 64 a lane loads its record, gathers its groups and
+ * finds its document by a search in d_doc_first bounded by the chunk's ends; per rule two ballots, the lane's last
+ * earlier partner from the ballot's bits below the lane (its position by one lane permute) or, with none in the chunk,
+ * from the rule's carry, which lane r keeps for rule r; the fired bits of a lane are one word, ORed per document by the
+ * segmented scan of the group-mask kernel: a plain 8-byte store for a document inside the block, an atomic OR for the
+ * at most two that straddle its ends, behind a memset.  No atomic per record, no scratch proportional to N x n_rules
+ * (the table holds N / 4096 x n_rules x 2 entries), no walk over "the records inside the window". */
+#define PFAC_NEAR_MAX_RULES 64u
+#define PFAC_NEAR_ORDERED   1u            /* rule flag: the A record precedes the B record in record order */
+#define PFAC_NEAR_ANY_DIST  0xFFFFFFFFu   /* max_dist: anywhere in the same document */
+typedef struct pfac_near_rule {           /* 32 bytes */
+    uint64_t a_groups;         /* a record is an A of this rule iff groups[state] & a_groups */
+    uint64_t b_groups;         /* ... a B iff groups[state] & b_groups; A and B may overlap */
+    uint32_t max_dist;         /* start-to-start distance in bytes, inclusive */
+    uint32_t flags;            /* 0 or PFAC_NEAR_ORDERED */
+    uint64_t reserved;         /* must be 0 */
+} pfac_near_rule;
+#define PFAC_NEAR_SELECTION 1u   /* call flag: d_sel == d_doc_first == NULL means the slot's per-document selection, as PFAC_TERMS_SELECTION */
+int pfac_documents_near(pfac_ctx *ctx, int slot, const pfac_record *d_sel, const uint64_t *d_doc_first, uint64_t n_docs,
+                        uint32_t flags, const pfac_near_rule *rules, uint32_t n_rules, uint64_t *d_masks_out,
+                        uint64_t *any_mask);
+/* D2H of masks [first, first + n) of the slot-owned result of the last pfac_documents_near.  Asynchronous on the slot's
+ * stream; pfac_slot_sync completes it.  first + n > n_docs gives PFAC_E_ARG; n == 0 does nothing. */
+int pfac_near_masks_d2h(pfac_ctx *ctx, int slot, uint64_t *host_masks, uint64_t first, uint64_t n);
+/* Device pointer of those slot-owned masks (uint64[n_docs]; what pfac_documents_matching_groups takes as d_masks), NULL
+ * if there are none: no finished call, or its masks went to the caller's buffer.  Valid until the slot's next
+ * pfac_documents_near. */
+void *pfac_slot_near_masks(pfac_ctx *ctx, int slot);
+
 /* Whole-word filter: drops, IN PLACE, the records of the slot's last finished scan that split a word, so that every
  * consumer of the scan (the fetches, the text emitter, the checksum, the segment pass, both selections and both
  * replaces) sees whole-word matches only -- a selection then chooses among whole-word candidates, which no filter

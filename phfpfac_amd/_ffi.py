@@ -49,6 +49,10 @@ PFAC_TOP_SORT_BLOCK = 1024  # ... entries per workgroup of the ranked sort
 PFAC_TERMS_SELECTION = 1    # pfac_documents_term_counts: NULL inputs mean the slot's per-document selection
 PFAC_TERMS_SORT_BLOCK = 1024    # ... keys per chunk of its sort, and the most that one workgroup sorts alone
 PFAC_TERMS_SORT_ROWS = 4096     # ... the most workgroups of one sort pass
+PFAC_NEAR_MAX_RULES = 64    # pfac_documents_near: rules per call
+PFAC_NEAR_ORDERED = 1       # ... rule flag: the A record precedes the B record in record order
+PFAC_NEAR_ANY_DIST = 0xFFFFFFFF     # ... max_dist: anywhere in the same document
+PFAC_NEAR_SELECTION = 1     # ... call flag: NULL inputs mean the slot's per-document selection
 PFAC_TOKEN_DROP = -1        # pfac_table_set_token_ids: the state or byte emits no token
 PFAC_TOKENS_POSITIONS = 1   # pfac_tokenize_*: also the tokens' positions
 
@@ -107,6 +111,10 @@ SPAN_DTYPE = [("min_start", "<u4"), ("max_start", "<u4"), ("max_tail", "<u4"), (
 SCORE_DTYPE = [("score", "<i8"), ("count", "<u8")]
 
 
+# struct pfac_near_rule as a numpy dtype (32 bytes: what pfac_documents_near takes)
+NEAR_RULE_DTYPE = [("a_groups", "<u8"), ("b_groups", "<u8"), ("max_dist", "<u4"), ("flags", "<u4"), ("reserved", "<u8")]
+
+
 class CDocScore(C.Structure):
     """struct pfac_doc_score (the totals of pfac_documents_scores)."""
     _fields_ = [("score", C.c_int64), ("count", C.c_uint64)]
@@ -152,6 +160,7 @@ HIP_SYMBOLS = (
     "pfac_documents_matching_scores",
     "pfac_documents_top_scores", "pfac_documents_top_scores_d2h",
     "pfac_documents_term_counts", "pfac_documents_term_counts_d2h",
+    "pfac_documents_near", "pfac_near_masks_d2h", "pfac_slot_near_masks",
     "pfac_table_set_token_ids", "pfac_tokenize_leftmost_longest", "pfac_tokenize_documents", "pfac_tokens_d2h",
     "pfac_tokens_offsets_d2h",
 )
@@ -319,6 +328,10 @@ def hip_lib() -> C.CDLL:
         L.pfac_documents_top_scores_d2h.argtypes = [vp, i, vp, u64, u64]
         L.pfac_documents_term_counts.argtypes = [vp, i, vp, vp, u64, C.c_uint32, vp, vp, vp, u64, C.POINTER(u64)]
         L.pfac_documents_term_counts_d2h.argtypes = [vp, i, vp, vp, vp]
+        L.pfac_documents_near.argtypes = [vp, i, vp, vp, u64, C.c_uint32, vp, C.c_uint32, vp, C.POINTER(u64)]
+        L.pfac_near_masks_d2h.argtypes = [vp, i, vp, u64, u64]
+        L.pfac_slot_near_masks.argtypes = [vp, i]
+        L.pfac_slot_near_masks.restype = vp
         L.pfac_table_set_token_ids.argtypes = [vp, vp, u64, vp]
         L.pfac_tokenize_leftmost_longest.argtypes = [vp, i, vp, vp, C.c_uint32, vp, u64, vp, C.POINTER(u64)]
         L.pfac_tokenize_documents.argtypes = [vp, i, vp, vp, vp, vp, C.c_uint32, vp, u64, vp, vp, C.POINTER(u64)]

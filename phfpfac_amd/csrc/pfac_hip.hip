@@ -5296,6 +5296,227 @@ __global__ void pfac_tk_doc_kernel(const unsigned long long *off, unsigned long 
 }
 
 // ---------------------------------------------------------------------------
+// Proximity rules (pfac_documents_near): bit r of mask[d] is set iff document d holds two distinct records i < j, at
+// most max_dist bytes apart by their starts, that are an (A_r, B_r) pair -- in either order unless the rule is ordered.
+// With a maximum distance only, the nearest earlier A (or B) is the best partner a record can have, so the pass needs
+// per record and rule "the last A / the last B in front of me" and nothing else: O(N x n_rules) whatever max_dist is.
+// The records of a document are contiguous and ordered, so that partner comes from ballots, not from a scan over values.
+// NR_BLOCK records per wave, 64 per chunk; three kernels:
+//   pfac_near_last_kernel    one wave per block: per (rule, side) the index and position of the block's last A / last B
+//                            (NR_NONE: none), into tab[(2 r + side) * n_blocks + block].  The chunks are walked from the
+//                            block's end and only for the rules still open, so a rule whose classes are common costs one
+//                            chunk.  Lane r keeps rule r's two answers.
+//   pfac_near_carry_kernel   one workgroup per (rule, side): its row becomes, in place, the exclusive "last entry that is
+//                            not NR_NONE" over the blocks -- each block's carry-in -- 256 blocks per trip.
+//   pfac_near_kernel         the pass: one read of the records.  Per chunk a lane loads its record, gathers
+//                            groups[state] and finds its document by the bounded searches of pfac_sel_scores_kernel.
+//                            Per rule two ballots; a lane's last earlier A in the chunk is the top bit of the ballot
+//                            below the lane, its position one lane permute; with no earlier A in the chunk the partner
+//                            is the rule's carry (index, position).  A wave cannot keep 64 x 2 carries in scalar
+//                            registers: LANE r holds rule r's, read with a readlane at the loop's (uniform) rule index
+//                            and moved on from the ballot's top bit.  The lane fires iff the partner's index is at or
+//                            above doc_first[d] and the distance is within max_dist.  The fired bits of a lane are one
+//                            word; the per-document OR is doc_reduce_chunk<GroupOr>, with the store rule of
+//                            pfac_sel_scores_kernel: a document inside the wave's block is stored plainly over the
+//                            memset's 0, the at most two that straddle its ends are ORed atomically.
+// Checked in the pass, into res[1]: first[0] == 0, no decrease, first[n_docs] == n, every state below num_final, no
+// position that decreases inside a document.  Behind a failed check the masks are garbage in bounds and the host
+// discards them.  A state past the table reads no group (in all three kernels).
+constexpr unsigned NR_BLOCK = 64 * WAVE;
+#define GRID_THREAD ((unsigned long long)blockIdx.x * blockDim.x + threadIdx.x)        // (as the document kernels define them)
+#define GRID_THREADS ((unsigned long long)gridDim.x * blockDim.x)
+constexpr unsigned long long NR_NONE = ~0ull;                       // (index | position << 32; an index stays below 2^32 - 1)
+static_assert(sizeof(pfac_near_rule) == 32, "a rule is two dwordx4");
+
+__device__ __forceinline__ unsigned long long nr_or64(unsigned long long v) {
+#pragma unroll
+    for (int s = 1; s < WAVE; s <<= 1) v |= __shfl_xor(v, s, WAVE);
+    return (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32 |
+           (unsigned)__builtin_amdgcn_readfirstlane((int)v);     // (uniform, and known to be)
+}
+
+__global__ void __launch_bounds__(256)
+pfac_near_last_kernel(const pfac_record *sel, unsigned long long n, const unsigned long long *gmask, unsigned num_final,
+                      const pfac_near_rule *__restrict__ rules, unsigned n_rules, unsigned n_blocks, unsigned long long *tab) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    const unsigned blk = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (blk >= n_blocks) return;                                // (wave-uniform)
+    const unsigned long long p0 = (unsigned long long)blk * NR_BLOCK, p1 = min(p0 + NR_BLOCK, n);
+    unsigned long long open[2];                                 // the rules without an answer yet, per side (uniform)
+    open[0] = open[1] = n_rules >= 64u ? ~0ull : (1ull << n_rules) - 1ull;
+    unsigned long long last[2] = {NR_NONE, NR_NONE};            // lane r: rule r's last A, last B
+    const unsigned n_chunks = (unsigned)((p1 - p0 + WAVE - 1) / WAVE);
+    for (unsigned c = n_chunks; c-- > 0 && (open[0] | open[1]) != 0ull;) {
+        const unsigned long long c0 = p0 + (unsigned long long)c * WAVE, i = c0 + (unsigned)lane;
+        const bool have = i < p1;
+        pfac_record rec;
+        rec.pos = 0u;
+        rec.state = 0u;
+        if (have) rec = sel[i];
+        const unsigned long long g = have && rec.state < num_final ? gmask[rec.state] : 0ull;
+        const unsigned long long any = nr_or64(g);
+#pragma unroll
+        for (int side = 0; side < 2; side++) {
+            for (unsigned long long todo = open[side]; todo != 0ull; todo &= todo - 1ull) {
+                const int r = __ffsll((long long)todo) - 1;
+                const unsigned long long want = side ? rules[r].b_groups : rules[r].a_groups;
+                if (want == 0ull) { open[side] &= ~(1ull << r); continue; }       // it never matches: NR_NONE stands
+                if ((any & want) == 0ull) continue;
+                const unsigned long long bal = __ballot((g & want) != 0ull);
+                const int top = 63 - __clzll((long long)bal);
+                const unsigned tpos = (unsigned)__builtin_amdgcn_readlane((int)rec.pos, top);
+                if (lane == r) last[side] = (c0 + (unsigned)top) | (unsigned long long)tpos << 32;
+                open[side] &= ~(1ull << r);
+            }
+        }
+    }
+    if ((unsigned)lane < n_rules) {
+        tab[(unsigned long long)(2 * lane) * n_blocks + blk] = last[0];
+        tab[(unsigned long long)(2 * lane + 1) * n_blocks + blk] = last[1];
+    }
+}
+
+__global__ void __launch_bounds__(256)
+pfac_near_carry_kernel(unsigned long long *tab, unsigned n_blocks) {
+    __shared__ unsigned long long wlast[4];
+    const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x >> 6;
+    unsigned long long *row = tab + (unsigned long long)blockIdx.x * n_blocks;
+    unsigned long long carry = NR_NONE;
+    for (unsigned b0 = 0; b0 < n_blocks; b0 += 256) {
+        const unsigned b = b0 + threadIdx.x;
+        const unsigned long long v = b < n_blocks ? row[b] : NR_NONE;
+        unsigned long long inc = v;                             // the last entry at or below this lane, inside the wave
+#pragma unroll
+        for (int s = 1; s < WAVE; s <<= 1) {
+            const unsigned long long u = __shfl_up(inc, s, WAVE);
+            if (lane >= s && inc == NR_NONE) inc = u;
+        }
+        __syncthreads();                                        // (the trip before has read wlast)
+        if (lane == WAVE - 1) wlast[wave] = inc;
+        __syncthreads();
+        unsigned long long pre = carry;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const unsigned long long w = wlast[j];
+            if (w != NR_NONE) {
+                if (j < wave) pre = w;
+                carry = w;
+            }
+        }
+        unsigned long long ex = __shfl_up(inc, 1, WAVE);
+        if (lane == 0 || ex == NR_NONE) ex = pre;
+        if (b < n_blocks) row[b] = ex;
+    }
+}
+
+// the partner of a lane among the other side's records: the last one below the lane in this chunk (ballot `other`), else
+// the rule's carry (ci, cp); fires iff there is one inside the lane's document and within max_dist
+__device__ __forceinline__ bool nr_fires(bool mine, unsigned long long other, unsigned long long below, unsigned c0, unsigned pos,
+                                         unsigned dstart, unsigned ci, unsigned cp, unsigned max_dist) {
+    const unsigned long long m = other & below;
+    const int src = m ? 63 - __clzll((long long)m) : 0;
+    const unsigned ppos = (unsigned)__shfl((int)pos, src, WAVE);
+    const unsigned idx = m ? c0 + (unsigned)src : ci, at = m ? ppos : cp;
+    const bool any = m != 0ull || ci != 0xFFFFFFFFu;
+    return mine && any && idx >= dstart && pos - at <= max_dist;
+}
+
+__global__ void __launch_bounds__(256)
+pfac_near_kernel(const pfac_record *sel, unsigned long long n, const unsigned long long *first, unsigned long long n_docs,
+                 const unsigned long long *gmask, unsigned num_final, const pfac_near_rule *__restrict__ rules, unsigned n_rules,
+                 unsigned n_blocks, const unsigned long long *tab, unsigned long long *out, unsigned long long *res) {
+    using R = GroupOr;
+    bool bad = false;
+    for (unsigned long long d = GRID_THREAD; d < n_docs; d += GRID_THREADS) bad = bad || first[d] > first[d + 1];
+    if (GRID_THREAD == 0) bad = bad || first[0] != 0ull || first[n_docs] != n;
+    const int lane = threadIdx.x & (WAVE - 1);
+    const unsigned blk = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (blk < n_blocks && n_docs) {                             // (wave-uniform)
+        const unsigned long long p0 = (unsigned long long)blk * NR_BLOCK, p1 = min(p0 + NR_BLOCK, n);
+        const unsigned long long ia = doc_lower_bound(first, n_docs + 1, p0);
+        const unsigned long long ib = p1 >= n ? n_docs + 1 : doc_lower_bound(first, n_docs + 1, p1 + 1ull);
+        const unsigned long long ie = ib ? ib - 1 : 0ull;
+        auto flush = [&](unsigned d, R::Val m) {
+            if (R::empty(m)) return;
+            if (d >= ia && d < ie) R::store(out, d, m);
+            else R::atomic(out, d, m);
+        };
+        // lane r: the carries of rule r (the last A and the last B in front of the chunk)
+        unsigned long long ca = NR_NONE, cb = NR_NONE;
+        if ((unsigned)lane < n_rules) {
+            ca = tab[(unsigned long long)(2 * lane) * n_blocks + blk];
+            cb = tab[(unsigned long long)(2 * lane + 1) * n_blocks + blk];
+        }
+        unsigned cai = (unsigned)ca, cap = (unsigned)(ca >> 32), cbi = (unsigned)cb, cbp = (unsigned)(cb >> 32);
+        const unsigned long long below = (1ull << lane) - 1ull;
+        bool cvalid = false;
+        unsigned cd = 0;
+        R::Val cm = R::none(), any = R::none();
+        unsigned long long dlo = doc_of(first, 0ull, n_docs - 1, p0);
+        const unsigned long long dtop = doc_of(first, dlo, n_docs - 1, p1 - 1);
+        unsigned lastpos = p0 ? sel[p0 - 1].pos : 0u;            // the position in front of the chunk (uniform)
+        for (unsigned long long c0 = p0; c0 < p1; c0 += WAVE) {
+            const unsigned long long i = c0 + (unsigned)lane;
+            const bool have = i < p1;
+            pfac_record rec;
+            rec.pos = 0u;
+            rec.state = 0u;
+            if (have) rec = sel[i];
+            const bool known = rec.state < num_final;
+            bad = bad || !known;
+            const unsigned long long g = have && known ? gmask[rec.state] : 0ull;
+            dlo = doc_of(first, dlo, dtop, c0);
+            const unsigned long long dhi = doc_of(first, dlo, dtop, min(c0 + (WAVE - 1), p1 - 1));
+            const unsigned long long d = have ? doc_of(first, dlo, dhi, i) : dlo;
+            const unsigned dstart = (unsigned)first[d];
+            const unsigned pos = rec.pos;
+            unsigned prev = (unsigned)__shfl_up((int)pos, 1, WAVE);
+            if (lane == 0) prev = lastpos;
+            bad = bad || (have && (unsigned)i > dstart && pos < prev);
+            lastpos = (unsigned)__builtin_amdgcn_readlane((int)pos, WAVE - 1);
+            unsigned long long fired = 0ull;
+            for (unsigned r = 0; r < n_rules; r++) {
+                const unsigned long long ag = rules[r].a_groups, bg = rules[r].b_groups;
+                const unsigned max_dist = rules[r].max_dist;
+                const bool both = !(rules[r].flags & PFAC_NEAR_ORDERED);
+                const bool isa = (g & ag) != 0ull, isb = (g & bg) != 0ull;
+                const unsigned long long ba = __ballot(isa), bb = __ballot(isb);
+                if ((ba | bb) == 0ull) continue;                // (uniform) neither class in this chunk: the carries stand
+                const unsigned rai = (unsigned)__builtin_amdgcn_readlane((int)cai, (int)r);
+                const unsigned rap = (unsigned)__builtin_amdgcn_readlane((int)cap, (int)r);
+                bool fire = false;
+                if (bb != 0ull) fire = nr_fires(isb, ba, below, (unsigned)c0, pos, dstart, rai, rap, max_dist);
+                if (both && ba != 0ull) {
+                    const unsigned rbi = (unsigned)__builtin_amdgcn_readlane((int)cbi, (int)r);
+                    const unsigned rbp = (unsigned)__builtin_amdgcn_readlane((int)cbp, (int)r);
+                    fire = nr_fires(isa, bb, below, (unsigned)c0, pos, dstart, rbi, rbp, max_dist) || fire;
+                }
+                if (fire) fired |= 1ull << r;
+                if (ba != 0ull) {
+                    const int top = 63 - __clzll((long long)ba);
+                    const unsigned tpos = (unsigned)__builtin_amdgcn_readlane((int)pos, top);
+                    if ((unsigned)lane == r) { cai = (unsigned)c0 + (unsigned)top; cap = tpos; }
+                }
+                if (bb != 0ull) {
+                    const int top = 63 - __clzll((long long)bb);
+                    const unsigned tpos = (unsigned)__builtin_amdgcn_readlane((int)pos, top);
+                    if ((unsigned)lane == r) { cbi = (unsigned)c0 + (unsigned)top; cbp = tpos; }
+                }
+            }
+            const unsigned long long b = __ballot(fired != 0ull);
+            if (b == 0ull) continue;
+            R::add(any, fired);
+            doc_reduce_chunk<R>(lane, b, d, fired, cvalid, cd, cm, flush);
+        }
+        if (cvalid && lane == 0) flush(cd, cm);
+        R::total(res, any, lane);
+    }
+    if (bad) res[1] = 1ull;
+}
+#undef GRID_THREAD
+#undef GRID_THREADS
+
+// ---------------------------------------------------------------------------
 // runtime
 
 thread_local std::string g_err;
@@ -5476,6 +5697,11 @@ struct Slot {
     DevBuf<unsigned> tc_hidx;             // ... and the index of every head (n_terms + 1 entries)
     PassOut<unsigned long long> tc_row;   // row_ptr (n_docs + 1 entries), ...
     PassOut<unsigned> tc_st, tc_cnt;      // ... the states and the counts (n_terms entries each)
+    // pfac_documents_near
+    pfac_near_rule nr_host[PFAC_NEAR_MAX_RULES];  // the call's rules, copied from the caller's array (the upload reads these), ...
+    DevBuf<pfac_near_rule> nr_rules;      // ... on the device, ...
+    DevBuf<unsigned long long> nr_tab;    // ... per (rule, side) and block of 4096 records: the last A / B, then the block's carry-in
+    PassOut<unsigned long long> nr_out;   // the masks (n_docs of them); scratch of a call that writes to the caller's buffer
     // pfac_documents_gather
     DevBuf<unsigned long long> ga_x;      // X per block of 64 ids
     PassOut<unsigned char> ga_out;        // the bytes, ...
@@ -7599,6 +7825,117 @@ int pfac_documents_term_counts_d2h(pfac_ctx *ctx, int slot, uint64_t *host_row_p
     rc = fetch(ctx, s, s.tc_row, me, pass, host_row_ptr, 0, s.tc_row.n, true);
     if (!rc) rc = fetch(ctx, s, s.tc_st, me, pass, host_states, 0, s.tc_st.n, true);
     return rc ? rc : fetch(ctx, s, s.tc_cnt, me, pass, host_counts, 0, s.tc_cnt.n, true);
+}
+
+// Proximity rules: the rules' upload, the blocks' last A / last B, their carry-in, the memset and the pass queued back to
+// back, then the ONE copy back (the OR of all masks and the error word); behind the host's check the copy to a caller's
+// buffer.
+int pfac_documents_near(pfac_ctx *ctx, int slot, const pfac_record *d_sel, const uint64_t *d_doc_first, uint64_t n_docs,
+                        uint32_t flags, const pfac_near_rule *rules, uint32_t n_rules, uint64_t *d_masks_out, uint64_t *any_mask) {
+    const std::string fn = "pfac_documents_near";
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    if (!any_mask) return fail(ctx, PFAC_E_ARG, "null argument");
+    *any_mask = 0;
+    Slot &s = ctx->slots[slot];
+    s.nr_out.invalidate();
+    if (!ctx->have_table) return fail(ctx, PFAC_E_STATE, fn + " before a table upload");
+    if (!ctx->gmask.p) return fail(ctx, PFAC_E_STATE, fn + ": no state groups for the uploaded table (pfac_table_set_state_groups)");
+    const pfac_record *sel = d_sel;
+    const unsigned long long *first = reinterpret_cast<const unsigned long long *>(d_doc_first);
+    uint64_t n = 0;
+    const bool own = !d_sel && !d_doc_first;
+    if (own && flags == PFAC_NEAR_SELECTION) {              // the rules of pfac_documents_term_counts' slot-owned inputs
+        if (!s.scanned || s.pending || !s.ll_out.done || s.ll_seq != s.scan_seq || !s.ll_docs)
+            return fail(ctx, PFAC_E_STATE, fn + " needs a pfac_records_leftmost_longest_documents since the slot's last scan");
+        if (s.last_table != ctx->table_gen) return fail(ctx, PFAC_E_STATE, fn + ": the selection was made with an earlier table");
+        if (!s.ll_out.own || !s.lld_first.done || !s.lld_first.own)
+            return fail(ctx, PFAC_E_STATE, fn + ": the slot holds no selection (it went to the caller's buffers; pass those)");
+    } else if (own && flags == 0) {
+        if (!s.seg_out.done || !s.seg_out.own || !s.seg_first.done || !s.seg_first.own)
+            return fail(ctx, PFAC_E_STATE, fn + ": the slot holds no pfac_records_segment result (none yet, or it went to the caller's buffers; pass those)");
+        if (s.seg_table != ctx->table_gen) return fail(ctx, PFAC_E_STATE, fn + ": the segment pass ran with an earlier table");
+    }
+    if ((((uintptr_t)d_sel | (uintptr_t)d_doc_first | (uintptr_t)d_masks_out) & 7))
+        return fail(ctx, PFAC_E_ARG, fn + ": misaligned buffer (d_sel, d_doc_first and d_masks_out 8 B)");
+    if (!own && (!d_sel || !d_doc_first))
+        return fail(ctx, PFAC_E_ARG, fn + ": d_sel and d_doc_first are the slot's (both NULL) or the caller's (neither)");
+    if (flags > PFAC_NEAR_SELECTION) return fail(ctx, PFAC_E_ARG, fn + ": flags must be 0 or PFAC_NEAR_SELECTION");
+    if (own) {
+        const bool picks = flags == PFAC_NEAR_SELECTION;
+        rc = (picks ? s.ll_out : s.seg_out).consume(ctx, fn, "records (d_sel)", d_sel, ANY_N, &sel);
+        if (rc) return rc;
+        rc = (picks ? s.lld_first : s.seg_first).consume(ctx, fn, "doc_first (d_doc_first)", d_doc_first, n_docs + 1, &first);
+        if (rc) return rc;
+        n = picks ? s.ll_out.n : s.seg_out.n;
+    }
+    if (n_docs >= (1ull << 32)) return fail(ctx, PFAC_E_ARG, fn + ": n_docs must be below 2^32");
+    if (n_rules > PFAC_NEAR_MAX_RULES) return fail(ctx, PFAC_E_ARG, fn + ": at most 64 rules per call (run it again for more)");
+    if (!rules && n_rules) return fail(ctx, PFAC_E_ARG, fn + ": null rules");
+    for (uint32_t r = 0; r < n_rules; r++)
+        if (rules[r].flags > PFAC_NEAR_ORDERED || rules[r].reserved)
+            return fail(ctx, PFAC_E_ARG, fn + ": rule " + std::to_string(r) + ": flags must be 0 or PFAC_NEAR_ORDERED and reserved 0");
+    USE_DEVICE(ctx);
+    if (!own) {                                             // how many records the caller's arrays hold: doc_first[n_docs]
+        HIP_TRY(ctx, hipMemcpyAsync(s.h_ctl + H_PASS, first + n_docs, 8, hipMemcpyDeviceToHost, s.stream));
+        HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+        n = host_u64(s, H_PASS);
+    }
+    if (n >= (1ull << 32)) return fail(ctx, PFAC_E_ARG, fn + ": the record count, d_doc_first[n_docs], must be below 2^32");
+    const char *broken = ": d_doc_first must start at 0 and not decrease, every state of d_sel must be below num_final, and no position may decrease inside a document";
+    if (n_docs == 0 && n) return fail(ctx, PFAC_E_ARG, fn + broken);
+    const unsigned n_blocks = (unsigned)((n + NR_BLOCK - 1) / NR_BLOCK);
+    rc = ensure_gsum(ctx, s, 1);                            // the OR of all masks, the error word
+    if (rc) return rc;
+    unsigned long long *res = s.gsum.p;
+    // The masks are made in the slot's buffer and reach a caller's only behind the host's check of the error word: a
+    // refused call leaves the caller's buffer as it was.
+    unsigned long long *out;
+    rc = s.nr_out.bind(ctx, s.stream, (unsigned long long *)nullptr, std::max<uint64_t>(n_docs, 1), docs_cap(n_docs), &out);
+    if (!rc && n_rules) rc = s.nr_rules.ensure(ctx, s.stream, n_rules, PFAC_NEAR_MAX_RULES);
+    const uint64_t tab_n = (uint64_t)n_blocks * n_rules * 2;
+    if (!rc && tab_n) rc = s.nr_tab.ensure(ctx, s.stream, tab_n, quarter_more(tab_n));
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemsetAsync(res, 0, 16, s.stream));
+    if (n_docs) {
+        const unsigned num_final = (unsigned)ctx->plan.base.num_final;
+        HIP_TRY(ctx, hipMemsetAsync(out, 0, n_docs * 8, s.stream));      // the 0 of every document in which no rule fired
+        if (n_rules) {
+            memcpy(s.nr_host, rules, (size_t)n_rules * sizeof(pfac_near_rule));
+            HIP_TRY(ctx, hipMemcpyAsync(s.nr_rules.p, s.nr_host, (size_t)n_rules * sizeof(pfac_near_rule), hipMemcpyHostToDevice, s.stream));
+        }
+        if (tab_n) {
+            hipLaunchKernelGGL(pfac_near_last_kernel, dim3((n_blocks + 3) / 4), dim3(256), 0, s.stream, sel, (unsigned long long)n,
+                               (const unsigned long long *)ctx->gmask.p, num_final, (const pfac_near_rule *)s.nr_rules.p, (unsigned)n_rules,
+                               n_blocks, s.nr_tab.p);
+            hipLaunchKernelGGL(pfac_near_carry_kernel, dim3(2 * n_rules), dim3(256), 0, s.stream, s.nr_tab.p, n_blocks);
+        }
+        const uint64_t vblocks = (n_docs + 255) / 256;
+        const unsigned blocks = (unsigned)std::max<uint64_t>(1, std::max<uint64_t>((n_blocks + 3) / 4, std::min<uint64_t>(vblocks, 4096)));
+        hipLaunchKernelGGL(pfac_near_kernel, dim3(blocks), dim3(256), 0, s.stream, sel, (unsigned long long)n, first,
+                           (unsigned long long)n_docs, (const unsigned long long *)ctx->gmask.p, num_final,
+                           (const pfac_near_rule *)s.nr_rules.p, (unsigned)n_rules, n_blocks, (const unsigned long long *)s.nr_tab.p, out, res);
+    }
+    rc = pass_words(ctx, s, res, 2);
+    if (rc) return rc;
+    if (host_u64(s, H_PASS1)) return fail(ctx, PFAC_E_ARG, fn + broken);
+    if (d_masks_out && n_docs) HIP_TRY(ctx, hipMemcpyAsync(d_masks_out, out, n_docs * 8, hipMemcpyDeviceToDevice, s.stream));
+    *any_mask = host_u64(s, H_PASS);
+    s.nr_out.commit(n_docs, !d_masks_out);
+    return PFAC_OK;
+}
+
+int pfac_near_masks_d2h(pfac_ctx *ctx, int slot, uint64_t *host_masks, uint64_t first, uint64_t n) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    Slot &s = ctx->slots[slot];
+    return fetch(ctx, s, s.nr_out, "pfac_near_masks_d2h", "pfac_documents_near", host_masks, first, n);
+}
+
+void *pfac_slot_near_masks(pfac_ctx *ctx, int slot) {
+    if (check_slot(ctx, slot)) return nullptr;
+    const Slot &s = ctx->slots[slot];
+    return s.nr_out.done && s.nr_out.own ? (void *)s.nr_out.buf.p : nullptr;
 }
 
 // The two gathers: the plain one (fmt NULL, or a format that asks for nothing: the plain kernels) and the one with

@@ -20,7 +20,8 @@ from ._ffi import (PFAC_LINE_CONTEXT_SEP, PFAC_LINE_MAX_GROUP_SEP, PFAC_LINE_NUM
 from ._ffi import PFAC_TOP_BY_COUNT, PFAC_TOP_LOWEST, PFAC_TOP_RANKED
 from ._ffi import PFAC_TERMS_SELECTION
 from ._ffi import PFAC_TOKENS_POSITIONS
-from .table import RECORD_DTYPE, SCORE_DTYPE, TEMPLATE_PLAIN, TOKEN_DROP, PfacTable, redaction_table, replacement_table, template_table, token_table, _state_lengths
+from ._ffi import PFAC_NEAR_SELECTION
+from .table import NEAR_RULE_DTYPE, RECORD_DTYPE,SCORE_DTYPE, TEMPLATE_PLAIN, TOKEN_DROP, PfacTable, redaction_table, replacement_table, template_table, token_table, _state_lengths
 
 
 def device_count() -> int:
@@ -66,6 +67,18 @@ def _ptr(x) -> int:
     if hasattr(x, "data_ptr"):
         return int(x.data_ptr())
     raise TypeError(f"cannot take a device pointer from {type(x)!r}")
+
+
+def _near_rules(rules) -> np.ndarray:
+    """The ``rules`` of the proximity calls as one contiguous ``NEAR_RULE_DTYPE`` array: an array of them as it is, or
+    the ``near_rule`` records of a list."""
+    if isinstance(rules, np.ndarray):
+        return np.ascontiguousarray(rules, dtype=NEAR_RULE_DTYPE).ravel()
+    given = list(rules)
+    out = np.zeros(len(given), dtype=NEAR_RULE_DTYPE)
+    for k, r in enumerate(given):
+        out[k] = np.asarray(r, dtype=NEAR_RULE_DTYPE).reshape(())[()]
+    return out
 
 
 class GpuMatcher:
@@ -1048,6 +1061,78 @@ class GpuMatcher:
         col = d_states.view(torch.int32)[: int(n_terms)].to(torch.int64)
         val = d_counts.view(torch.int32)[: int(n_terms)]
         return torch.sparse_csr_tensor(row, col, val, size=(int(n_docs), self._n_states()))
+
+    # -- proximity rules: which pairs of pattern groups lie near each other ----
+    def document_near_masks(self, n_docs: int, rules, d_sel=None, d_doc_first=None, selection: bool = False, d_out=None,
+                            slot: int = 0) -> int:
+        """Which proximity rules fire in each document, on the GPU (``pfac_documents_near``): ``rules`` is up to 64
+        ``near_rule`` records (a list of them, or a ``NEAR_RULE_DTYPE`` array) over the pattern groups
+        (``set_pattern_groups``); bit r of ``mask[d]`` is set iff document d holds two distinct records of rule r's two
+        groups whose starts are at most its ``within`` bytes apart.  The input is a record array cut per document, as
+        ``document_term_counts`` takes it: ``d_sel`` and ``d_doc_first`` both None = the slot-owned result of the slot's
+        last ``segment_records`` (``selection``: of its last ``select_leftmost_longest_documents``).  ``d_out`` None = a
+        slot-owned buffer (``near_masks_to_host``), else a device buffer of ``n_docs`` uint64.  Returns the OR of all
+        masks: the rules that fired at all."""
+        arr = _near_rules(rules)
+        m = C.c_uint64(0)
+        self._check(self._L.pfac_documents_near(self._ctx, slot, _ptr(d_sel), _ptr(d_doc_first), int(n_docs),
+                                                PFAC_NEAR_SELECTION if selection else 0, arr.ctypes.data if arr.size else None,
+                                                int(arr.size), _ptr(d_out), C.byref(m)))
+        return m.value
+
+    def near_masks_to_host(self, n_docs: int, slot: int = 0, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """Masks [first, first + n) of the slot's last ``document_near_masks`` into its slot-owned buffer (default: all
+        ``n_docs``)."""
+        n = int(n_docs) - int(first) if n is None else int(n)
+        return self._to_host(slot, lambda p: self._L.pfac_near_masks_d2h(self._ctx, slot, p, int(first), n),
+                             (max(n, 0), np.uint64))
+
+    def near_masks_ptr(self, slot: int = 0) -> int:
+        """Device pointer of the slot-owned masks of the slot's last ``document_near_masks`` (0: none) -- what
+        ``matching_documents_where`` takes as ``d_masks``."""
+        return int(self._L.pfac_slot_near_masks(self._ctx, slot) or 0)
+
+    def _near_pass(self, n_docs: int, rules, slot: int, non_overlapping: bool) -> int:
+        if non_overlapping:
+            self.select_leftmost_longest_documents(n_docs, slot=slot)
+        else:
+            self.segment_records(n_docs, slot=slot)
+        return self.document_near_masks(n_docs, rules, selection=non_overlapping, slot=slot)
+
+    def near_documents(self, docs, rules, non_overlapping: bool = False, whole_words=False, spans: bool = False,
+                       line_match: bool = False, slot: int = 0) -> np.ndarray:
+        """The proximity rules of every document of a batch (``docs`` as ``scan_documents`` takes it) in one scan: the
+        scan, the document cut (``non_overlapping``: the leftmost-longest picks of each document instead of every
+        match) and ``document_near_masks`` on the device; only the masks come back: uint64[n_docs]."""
+        _, n_docs = self._scan_docs(docs, slot, whole_words, spans, line_match)
+        self._near_pass(n_docs, rules, slot, non_overlapping)
+        return self.near_masks_to_host(n_docs, slot)
+
+    def near_lines(self, data, rules, delimiter=b"\n", non_overlapping: bool = False, whole_words=False, spans: bool = False,
+                   line_match: bool = False, slot: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+        """``near_documents`` of one buffer cut into lines at ``delimiter`` on the device.  Returns (offsets uint64
+        [n_docs + 1], masks uint64[n_docs])."""
+        offsets, n_docs = self._scan_lines(data, delimiter, slot, whole_words, spans=spans, line_match=line_match)
+        self._near_pass(n_docs, rules, slot, non_overlapping)
+        return offsets, self.near_masks_to_host(n_docs, slot)
+
+    def grep_lines_near(self, data, rules, all_of: int = 0, any_of: int = 0, none_of: int = 0, invert: bool = False,
+                        delimiter=b"\n", non_overlapping: bool = False, whole_words=False, slot: int = 0, spans: bool = False,
+                        line_match: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The lines of ``data`` on which the proximity rules satisfy the predicate of ``matching_documents_where``
+        (bit r = rule r; all three 0: some rule fired), as bytes: scan, split, cut, the rule pass, the predicate and
+        the gather on the device -- nothing but those lines crosses the link.  Returns what ``grep_lines_where``
+        returns: (out uint8[out_bytes], out_offsets uint64[n + 1], ids uint64[n])."""
+        buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data.view(np.uint8).ravel()
+        _, n_docs = self._scan_lines(buf, delimiter, slot, whole_words, fetch_offsets=False, spans=spans, line_match=line_match)
+        self._near_pass(n_docs, rules, slot, non_overlapping)
+        if not (all_of or any_of or none_of):
+            any_of = 2**64 - 1
+        n = self.matching_documents_where(n_docs, all_of, any_of, none_of, invert=invert,
+                                          d_masks=self.near_masks_ptr(slot), slot=slot)
+        out_bytes = self.gather_documents(n_docs, n, int(buf.size), slot=slot)
+        return (self.gathered_to_host(out_bytes, slot), self.gathered_offsets_to_host(n, slot),
+                self.matching_documents_to_host(n, slot))
 
     # -- leftmost-longest non-overlapping matches ---------------------------
     def select_leftmost_longest(self, entry: int = 0, d_out=None, out_cap: int = 0, slot: int = 0,

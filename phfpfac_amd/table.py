@@ -11,13 +11,42 @@ import os
 
 import numpy as np
 
-from ._ffi import PFAC_SPAN_ANY, CTable, PfacError, host_lib
+from ._ffi import PFAC_NEAR_ANY_DIST, PFAC_NEAR_ORDERED, PFAC_SPAN_ANY, CTable, PfacError, host_lib
+from ._ffi import NEAR_RULE_DTYPE as _NEAR_RULE_FIELDS
 from ._ffi import SCORE_DTYPE as _SCORE_FIELDS
 from ._ffi import SPAN_DTYPE as _SPAN_FIELDS
 
 RECORD_DTYPE = np.dtype([("pos", np.uint32), ("state", np.uint32)])
 SPAN_DTYPE = np.dtype(_SPAN_FIELDS)         # struct pfac_state_span
 SCORE_DTYPE = np.dtype(_SCORE_FIELDS)       # struct pfac_doc_score
+NEAR_RULE_DTYPE = np.dtype(_NEAR_RULE_FIELDS)       # struct pfac_near_rule
+
+
+def _group_mask(groups) -> int:
+    """A group index 0..63, an iterable of indices, or a ready mask (numpy.uint64) -> the 64-bit mask."""
+    if isinstance(groups, np.uint64):
+        return int(groups)
+    mask = 0
+    for g in ((groups,) if isinstance(groups, (int, np.integer)) else groups):
+        if not 0 <= int(g) < 64:
+            raise ValueError(f"group {int(g)} is outside 0..63")
+        mask |= 1 << int(g)
+    return mask
+
+
+def near_rule(a, b, within=None, ordered: bool = False) -> np.ndarray:
+    """One proximity rule of ``GpuMatcher.document_near_masks`` (``struct pfac_near_rule``, a ``NEAR_RULE_DTYPE``
+    scalar array of shape ()): a record of the groups ``a`` and a record of the groups ``b`` whose starts are at most
+    ``within`` bytes apart (None: anywhere in the same document), ``ordered``: the ``a`` record first.  ``a`` / ``b``
+    are a group index, an iterable of indices, or a ready mask (``numpy.uint64``).  Stack several with ``numpy.stack``
+    or pass a list of them."""
+    dist = PFAC_NEAR_ANY_DIST if within is None else int(within)
+    if not 0 <= dist <= PFAC_NEAR_ANY_DIST:
+        raise ValueError("within is a distance in bytes, 0..2^32 - 1")
+    out = np.zeros((), dtype=NEAR_RULE_DTYPE)
+    out["a_groups"], out["b_groups"] = _group_mask(a), _group_mask(b)
+    out["max_dist"], out["flags"] = dist, PFAC_NEAR_ORDERED if ordered else 0
+    return out
 
 
 class PfacTable:
