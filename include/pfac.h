@@ -891,6 +891,73 @@ int pfac_documents_term_counts(pfac_ctx *ctx, int slot, const pfac_record *d_sel
 int pfac_documents_term_counts_d2h(pfac_ctx *ctx, int slot, uint64_t *host_row_ptr, uint32_t *host_states,
                                    uint32_t *host_counts);
 
+/* Rule sets: WHICH of many rules fired in each document -- the several content: strings of a Snort rule that must all
+ * occur, YARA's "all of them", "2 of ($a, $b, $c)" and "$a and not $b", the words of a label rule -- for thousands of
+ * rules over tens of thousands of patterns at once, where the group masks allow 64 classes and one predicate per call.
+ * It is the join of the document-term matrix (pfac_documents_term_counts) with a rule table.
+ *
+ * The table (pfac_table_set_rules).  Rule r has a set P_r of positive final states, a set N_r of negated ones, disjoint
+ * from P_r, and need_r with 1 <= need_r <= |P_r|.  With S_d the states of row d of the matrix,
+ *   rule r fires in document d iff |P_r & S_d| >= need_r and N_r & S_d is empty.
+ * need = |P| is AND, need = 1 is OR, anything between "k of them".  A rule without a positive term cannot be stated, so
+ * only documents with a record can fire.
+ *   rule_ptr, terms, need  HOST arrays, rule-major, copied at the call: terms[rule_ptr[r] .. rule_ptr[r + 1]) are rule r's
+ *                  final states, bit 31 (PFAC_RULE_NOT) marks a negated one; need[r].  n_rules < 2^31 and fewer than
+ *                  2^32 terms in all.  n_rules == 0 is legal (the pointers may be NULL) and clears the rules only
+ * PFAC_E_STATE before a table upload.  PFAC_E_ARG, with the earlier rules kept: rule_ptr[0] != 0 or a decrease, a state at
+ * or past num_final, a state twice in one rule (under either sign), need == 0 or need above the rule's positive terms.
+ * The host inverts the table to state-major (state_ptr uint32[num_final + 1]; entries rule << 1 | negated, the rules
+ * ascending inside a state; need[]) and uploads it under the lifetime rules of pfac_table_set_state_groups: the arrays
+ * live with the table, an upload clears them, a second call replaces them, and freeing the old buffers waits for the
+ * device, so a pass that still reads them has finished.
+ *
+ * The pass (pfac_documents_rules).
+ *   d_row_ptr, d_states  both non-NULL = any device arrays, 8-B and 4-B aligned: the first two arrays of a document-term
+ *                  matrix as pfac_documents_term_counts writes them (the counts are not read); d_row_ptr has n_docs + 1
+ *                  entries and d_row_ptr[n_docs] is read back first, to size the launch.  Both NULL = the slot-owned
+ *                  row_ptr and states of the slot's last pfac_documents_term_counts (PFAC_E_STATE: none, either went to
+ *                  the caller's buffer, or it was made with an earlier table; an n_docs that is not that call's gives
+ *                  PFAC_E_ARG).  One NULL and one not gives PFAC_E_ARG
+ *   flags          0
+ *   result         a CSR of fired rules: row_ptr uint64[n_docs + 1] and rules uint32[*n_fired], a document's rule ids
+ *                  strictly ascending
+ *   d_row_ptr_out  NULL = a slot-owned buffer grown to fit; else a device pointer, 8-B aligned, n_docs + 1 entries
+ *   d_rules_out    NULL = a slot-owned buffer grown to fit; else a device pointer, 4-B aligned, out_cap entries
+ * Checked on the device, before anything reaches a caller's buffer, else PFAC_E_ARG: d_row_ptr[0] == 0, d_row_ptr does
+ * not decrease, every state is below num_final, the states strictly ascend inside a row.  Judged in this order --
+ * PFAC_E_STATE: no table, no rules for it, a slot-owned input that is missing or from an earlier table; PFAC_E_ARG: one
+ * input NULL and the other not, flags other than 0, misaligned buffers, n_docs >= 2^32, 2^32 or more pairs, the device's
+ * checks, and an expansion E >= 2^32, where E = the sum over all pairs of the rules that name the pair's state.
+ * PFAC_E_OVERFLOW with *n_fired exact when out_cap < *n_fired and d_rules_out is the caller's.  Every error leaves every
+ * caller's buffer untouched; exactly (n_docs + 1) x 8 and *n_fired x 4 bytes are written.  n_docs == 0 writes the single
+ * row_ptr[0] = 0.
+ * A pass of its own, with the lifetime rule of pfac_segment_d2h: it discards no other pass's result and is discarded by
+ * none; a failed call discards its own slot-owned result.  Returns once *n_fired is known (two small copies back: E with
+ * the error word, then the total); the writes complete on the slot's stream.  The same call on the same input gives the
+ * same bytes.  It reads neither the input bytes, nor the record heap, nor the cut records.
+ * Kernels: (1) one lane per pair, a wave per 4096 pairs: the pair's document by a search in d_row_ptr bounded by its
+ * block's first and last pair, c = state_ptr[s + 1] - state_ptr[s], the four checks into one word; kept per pair its
+ * document and the entries in front of it in its group, per group the sum, then the group prefix: E is the total, and
+ * E == 0 writes zeros without a further launch.  (2) Output-driven, one lane per key e < E: its group and its pair by two
+ * searches in the prefixes, then its entry: key = doc << (rbits + 1) | rule << 1 | negated, rbits = bit_width(n_rules -
+ * 1) -- no loop is as long as a state's rule count.  (3) The stable LSD sort of pfac_documents_term_counts (the same
+ * kernels, PFAC_TERMS_SORT_ROWS and its knob) over ceil((bit_width(n_docs - 1) + rbits + 1) / 8) digits.  (4) A (document,
+ * rule) run is now contiguous, its positive entries in front of its negated ones, every entry another term: entry t is
+ * a tail iff t == E - 1 or key[t + 1] >> 1 != key[t] >> 1, and the run fires iff key[t] & 1 == 0, t >= need - 1 and
+ * key[t - (need - 1)] >> 1 == key[t] >> 1 -- one more load per tail, no head ranks, no run lengths; a ballot per 64
+ * entries is kept, the sums per 4096 go through the group prefix.  (5) Behind the host's overflow check the fired tail of
+ * rank j stores rules[j]; row_ptr[d] is a lower bound of d << (rbits + 1) in the sorted keys, two loads and a popcount. */
+#define PFAC_RULE_NOT 0x80000000u   /* bit 31 of a term: the rule must NOT find this state in the document */
+int pfac_table_set_rules(pfac_ctx *ctx, const uint64_t *rule_ptr, const uint32_t *terms, const uint32_t *need,
+                         uint64_t n_rules);
+int pfac_documents_rules(pfac_ctx *ctx, int slot, const uint64_t *d_row_ptr, const uint32_t *d_states, uint64_t n_docs,
+                         uint32_t flags, uint64_t *d_row_ptr_out, uint32_t *d_rules_out, uint64_t out_cap,
+                         uint64_t *n_fired);
+/* D2H of the slot-owned result of the last pfac_documents_rules: n_docs + 1 row_ptr entries and *n_fired rule ids.
+ * Either may be NULL (it must be where that output was the caller's: PFAC_E_STATE else).  Asynchronous on the slot's
+ * stream; pfac_slot_sync completes it. */
+int pfac_documents_rules_d2h(pfac_ctx *ctx, int slot, uint64_t *host_row_ptr, uint32_t *host_rules);
+
 /* Proximity rules: WHERE the pattern groups of a document occur relative to each other -- a card number within 60 bytes
  * of "expires", the within: of two contents of one rule, NEAR/n, "BEGIN before END on the same line".  The group masks
  * say that both halves occur in a document; this pass says that they occur together, and in which order.  The classes

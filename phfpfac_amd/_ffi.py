@@ -49,6 +49,7 @@ PFAC_TOP_SORT_BLOCK = 1024  # ... entries per workgroup of the ranked sort
 PFAC_TERMS_SELECTION = 1    # pfac_documents_term_counts: NULL inputs mean the slot's per-document selection
 PFAC_TERMS_SORT_BLOCK = 1024    # ... keys per chunk of its sort, and the most that one workgroup sorts alone
 PFAC_TERMS_SORT_ROWS = 4096     # ... the most workgroups of one sort pass
+PFAC_RULE_NOT = 0x80000000  # pfac_table_set_rules: bit 31 of a term marks a negated state
 PFAC_NEAR_MAX_RULES = 64    # pfac_documents_near: rules per call
 PFAC_NEAR_ORDERED = 1       # ... rule flag: the A record precedes the B record in record order
 PFAC_NEAR_ANY_DIST = 0xFFFFFFFF     # ... max_dist: anywhere in the same document
@@ -160,6 +161,7 @@ HIP_SYMBOLS = (
     "pfac_documents_matching_scores",
     "pfac_documents_top_scores", "pfac_documents_top_scores_d2h",
     "pfac_documents_term_counts", "pfac_documents_term_counts_d2h",
+    "pfac_table_set_rules", "pfac_documents_rules", "pfac_documents_rules_d2h",
     "pfac_documents_near", "pfac_near_masks_d2h", "pfac_slot_near_masks",
     "pfac_table_set_token_ids", "pfac_tokenize_leftmost_longest", "pfac_tokenize_documents", "pfac_tokens_d2h",
     "pfac_tokens_offsets_d2h",
@@ -328,6 +330,9 @@ def hip_lib() -> C.CDLL:
         L.pfac_documents_top_scores_d2h.argtypes = [vp, i, vp, u64, u64]
         L.pfac_documents_term_counts.argtypes = [vp, i, vp, vp, u64, C.c_uint32, vp, vp, vp, u64, C.POINTER(u64)]
         L.pfac_documents_term_counts_d2h.argtypes = [vp, i, vp, vp, vp]
+        L.pfac_table_set_rules.argtypes = [vp, vp, vp, vp, u64]
+        L.pfac_documents_rules.argtypes = [vp, i, vp, vp, u64, C.c_uint32, vp, vp, u64, C.POINTER(u64)]
+        L.pfac_documents_rules_d2h.argtypes = [vp, i, vp, vp]
         L.pfac_documents_near.argtypes = [vp, i, vp, vp, u64, C.c_uint32, vp, C.c_uint32, vp, C.POINTER(u64)]
         L.pfac_near_masks_d2h.argtypes = [vp, i, vp, u64, u64]
         L.pfac_slot_near_masks.argtypes = [vp, i]

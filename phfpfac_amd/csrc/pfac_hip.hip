@@ -4693,6 +4693,139 @@ pfac_tc_rowptr_kernel(const unsigned long long *first, unsigned long long n_docs
                         : gpre[i / (DM_BLOCKS * WAVE)] + X[i >> 6] + (unsigned long long)__popcll(bal[i >> 6] & ((1ull << (i & 63)) - 1ull));
     }
 }
+
+// ---------------------------------------------------------------------------
+// Rule sets (pfac_documents_rules): the join of a document-term matrix (row_ptr, states) with the state-major rule table
+// of pfac_table_set_rules (sptr[num_final + 1], ent[] = rule << 1 | negated, need[n_rules]).  A pair is one (document,
+// state) of the matrix; pair i expands into c_i = sptr[s + 1] - sptr[s] keys, E keys in all.
+//   pfac_ru_count_kernel     a wave per group of DM_BLOCKS blocks of 64 pairs: the pair's document by the bounded searches
+//                            of pfac_tc_key_kernel, c_i, and the four checks (row_ptr[0] == 0, no decrease, every state
+//                            below num_final, the states strictly ascending inside a row) into one word.  Kept per pair:
+//                            its document and the keys in front of it in its group (32 bits: they mean something only
+//                            while E < 2^32, which the host checks); per group the 64-bit sum, for pfac_scan_groups_kernel.
+//   pfac_ru_expand_kernel    output-driven, one lane per key e < E: its group by a search in the group prefixes, its pair
+//                            by a search in the group's 4096 pair prefixes, its entry at sptr[s] + (e - the pair's first
+//                            key): key[e] = doc << (rbits + 1) | rule << 1 | negated.  No loop is as long as a state's
+//                            rule count.
+//   the sort                 tc_sort: the term counts' kernels over ceil((dbits + rbits + 1) / 8) digits
+//   pfac_ru_fired_kernel     a (document, rule) run is contiguous now, positive entries first, every entry another term.
+//                            Entry t is a tail iff t == E - 1 or key[t + 1] >> 1 != key[t] >> 1; the run fires iff the tail
+//                            is positive (no negated term present) and key[t - (need - 1)] is of the same run (need
+//                            positive terms present).  The compaction's shape, as pfac_tc_heads_kernel.
+//   pfac_ru_write_kernel     behind the host's overflow check: the fired tail of rank j stores rules[j]
+//   pfac_ru_rowptr_kernel    one lane per document: the lower bound of d << (rbits + 1) in the sorted keys is the
+//                            document's first entry; the fired tails in front of it are two loads and a popcount
+__global__ void __launch_bounds__(256)
+pfac_ru_count_kernel(const unsigned long long *row, unsigned long long n_docs, const unsigned *states, unsigned long long n,
+                     const unsigned *sptr, unsigned num_final, unsigned *cpre, unsigned *pdoc, unsigned long long *gsum,
+                     unsigned n_groups, unsigned long long *bad_out) {
+    bool bad = false;
+    for (unsigned long long d = GRID_THREAD; d < n_docs; d += GRID_THREADS) bad = bad || row[d] > row[d + 1];
+    if (GRID_THREAD == 0) bad = bad || row[0] != 0ull || row[n_docs] != n;
+    const int lane = threadIdx.x & (WAVE - 1);
+    const unsigned g = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (g < n_groups && n_docs) {                               // (wave-uniform)
+        const unsigned long long p0 = (unsigned long long)g * (DM_BLOCKS * WAVE), p1 = min(p0 + DM_BLOCKS * WAVE, n);
+        unsigned long long dlo = 0, run = 0;
+        for (unsigned long long c0 = p0; c0 < p1; c0 += WAVE) {
+            const unsigned long long i = c0 + (unsigned)lane;
+            const bool have = i < p1;
+            dlo = doc_of(row, dlo, n_docs - 1, c0);
+            const unsigned long long dhi = doc_of(row, dlo, n_docs - 1, min(c0 + (WAVE - 1), p1 - 1));
+            const unsigned long long d = have ? doc_of(row, dlo, dhi, i) : dlo;
+            const unsigned st = have ? states[i] : 0u;
+            const bool known = st < num_final;
+            unsigned prev = (unsigned)__shfl_up((int)st, 1, WAVE);
+            if (lane == 0 && c0 > 0) prev = states[c0 - 1];
+            bad = bad || (have && (!known || (i > row[d] && prev >= st)));
+            const unsigned c = have && known ? sptr[st + 1] - sptr[st] : 0u;
+            const unsigned incl = wave_incl_scan(c);
+            if (have) { cpre[i] = (unsigned)run + incl - c; pdoc[i] = (unsigned)d; }
+            run += wave_sum64(c);
+        }
+        if (lane == 0) gsum[g] = run;
+    }
+    if (bad) bad_out[0] = 1ull;
+}
+
+__global__ void __launch_bounds__(256)
+pfac_ru_expand_kernel(const unsigned *states, unsigned long long n, const unsigned *cpre, const unsigned *pdoc,
+                      const unsigned long long *gpre, unsigned n_groups, const unsigned *sptr, const unsigned *ent,
+                      unsigned rbits, unsigned long long n_keys, unsigned long long *keys) {
+    for (unsigned long long e = GRID_THREAD; e < n_keys; e += GRID_THREADS) {
+        unsigned glo = 0, ghi = n_groups - 1;                   // the last group with gpre[g] <= e
+        while (glo < ghi) {
+            const unsigned mid = (glo + ghi + 1) >> 1;
+            if (gpre[mid] <= e) glo = mid;
+            else ghi = mid - 1;
+        }
+        const unsigned x = (unsigned)(e - gpre[glo]);
+        unsigned long long lo = (unsigned long long)glo * (DM_BLOCKS * WAVE), hi = min(lo + DM_BLOCKS * WAVE, n) - 1;
+        while (lo < hi) {                                       // the last pair of the group with cpre[i] <= x
+            const unsigned long long mid = (lo + hi + 1) >> 1;
+            if (cpre[mid] <= x) lo = mid;
+            else hi = mid - 1;
+        }
+        const unsigned entry = ent[sptr[states[lo]] + (x - cpre[lo])];
+        keys[e] = (unsigned long long)pdoc[lo] << (rbits + 1u) | entry;
+    }
+}
+
+__global__ void __launch_bounds__(256)
+pfac_ru_fired_kernel(const unsigned long long *keys, unsigned long long n, const unsigned *need, unsigned rmask,
+                     unsigned long long *bal, unsigned *X, unsigned long long *gsum, unsigned n_groups) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    const unsigned g = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (g >= n_groups) return;
+    const unsigned long long i0 = (unsigned long long)g * (DM_BLOCKS * WAVE);
+    unsigned run = 0;
+    for (int b = 0; b < DM_BLOCKS; b++) {
+        const unsigned long long ib = i0 + (unsigned long long)b * WAVE, i = ib + lane;
+        if (ib >= n) break;                                         // (wave-uniform)
+        const bool have = i < n;
+        const unsigned long long k = have ? keys[i] : 0ull;
+        unsigned long long next = __shfl_down(k, 1, WAVE);
+        if (lane == WAVE - 1 && i + 1 < n) next = keys[i + 1];
+        bool fires = have && !(k & 1ull) && (i + 1 == n || (next >> 1) != (k >> 1));
+        if (fires) {
+            const unsigned back = need[(unsigned)(k >> 1) & rmask] - 1u;
+            fires = i >= back && (keys[i - back] >> 1) == (k >> 1);
+        }
+        const unsigned long long m = __ballot(fires);
+        if (lane == 0) { bal[ib >> 6] = m; X[ib >> 6] = run; }
+        run += (unsigned)__popcll(m);
+    }
+    if (lane == 0) gsum[g] = run;
+}
+
+__global__ void __launch_bounds__(256)
+pfac_ru_write_kernel(const unsigned long long *keys, unsigned long long n, const unsigned long long *bal, const unsigned *X,
+                     const unsigned long long *gpre, unsigned n_groups, unsigned rmask, unsigned long long n_fired,
+                     unsigned *rules) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    const unsigned g = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (g >= n_groups) return;
+    const unsigned long long i0 = (unsigned long long)g * (DM_BLOCKS * WAVE), pre = gpre[g];
+    for (int b = 0; b < DM_BLOCKS; b++) {
+        const unsigned long long ib = i0 + (unsigned long long)b * WAVE, i = ib + lane;
+        if (ib >= n) break;
+        const unsigned long long m = bal[ib >> 6];
+        const unsigned long long j = pre + X[ib >> 6] + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
+        if (((m >> lane) & 1ull) && i < n && j < n_fired) rules[j] = (unsigned)(keys[i] >> 1) & rmask;
+    }
+}
+
+__global__ void __launch_bounds__(256)
+pfac_ru_rowptr_kernel(const unsigned long long *keys, unsigned long long n, unsigned long long n_docs, unsigned rbits,
+                      const unsigned long long *bal, const unsigned *X, const unsigned long long *gpre,
+                      unsigned long long n_fired, unsigned long long *row) {
+    for (unsigned long long d = GRID_THREAD; d <= n_docs; d += GRID_THREADS) {
+        unsigned long long i = n;
+        if (d < n_docs) i = doc_lower_bound(keys, n, d << (rbits + 1u));
+        row[d] = i >= n ? n_fired
+                        : gpre[i / (DM_BLOCKS * WAVE)] + X[i >> 6] + (unsigned long long)__popcll(bal[i >> 6] & ((1ull << (i & 63)) - 1ull));
+    }
+}
 #undef GRID_THREAD
 #undef GRID_THREADS
 
@@ -5697,6 +5830,14 @@ struct Slot {
     DevBuf<unsigned> tc_hidx;             // ... and the index of every head (n_terms + 1 entries)
     PassOut<unsigned long long> tc_row;   // row_ptr (n_docs + 1 entries), ...
     PassOut<unsigned> tc_st, tc_cnt;      // ... the states and the counts (n_terms entries each)
+    // pfac_documents_rules (the sort's buffers, the ballots and the block prefixes are the term counts': both are used up
+    // on the stream)
+    uint64_t tc_table = 0;                // the table the slot's last term counts ran with (pfac_ctx::table_gen)
+    DevBuf<unsigned> ru_cpre;             // per pair: the keys in front of it in its group of 4096 pairs, ...
+    DevBuf<unsigned> ru_doc;              // ... and its document
+    DevBuf<unsigned long long> ru_gsum;   // the keys per group of pairs, their prefix, the total E and the error word
+    PassOut<unsigned long long> ru_row;   // row_ptr (n_docs + 1 entries), ...
+    PassOut<unsigned> ru_out;             // ... and the fired rules (n_fired entries)
     // pfac_documents_near
     pfac_near_rule nr_host[PFAC_NEAR_MAX_RULES];  // the call's rules, copied from the caller's array (the upload reads these), ...
     DevBuf<pfac_near_rule> nr_rules;      // ... on the device, ...
@@ -5776,7 +5917,7 @@ struct pfac_ctx {
     TablePlan plan;
     bool have_table = false;
     uint64_t table_gen = 0;               // installs begun so far: a scan's final states index the lengths of ITS table only
-    // ... what the caller attaches to it (an upload drops all ten), ...
+    // ... what the caller attaches to it (an upload drops all of it), ...
     DevBuf<short> flen;                   // pattern length of every final state (pfac_table_set_final_lengths)
     DevBuf<unsigned> rep_off;             // replacement of every final state (pfac_table_set_replacements): offsets[num_final + 1]
     DevBuf<unsigned char> rep;            // ... and the bytes, zero-padded to its capacity (a multiple of 16)
@@ -5787,6 +5928,10 @@ struct pfac_ctx {
     DevBuf<uint4> spans;                  // span of every final state (pfac_table_set_state_spans): pfac_state_span as one dwordx4
     DevBuf<int> tok;                      // token id of every final state (pfac_table_set_token_ids), PFAC_TOKEN_DROP = none, ...
     DevBuf<int> btok;                     // ... and of every byte value (256 entries; all DROP when the caller gave none)
+    DevBuf<unsigned> ru_sptr;             // the rule table, state-major (pfac_table_set_rules): state_ptr[num_final + 1], ...
+    DevBuf<unsigned> ru_ent;              // ... the entries rule << 1 | negated, the rules ascending inside a state, ...
+    DevBuf<unsigned> ru_need;             // ... and need[n_rules]
+    uint64_t ru_n = 0, ru_terms = 0;      // its rules (0: none) and its entries
     unsigned fold = PFAC_FOLD_NONE;       // case fold of the scans to come (pfac_table_set_case_fold)
     // ... and what adapts to the match density seen by the last scan (pfac_scan_finish)
     bool dense = false;                   // staging mode
@@ -5898,6 +6043,46 @@ int pass_words(pfac_ctx *ctx, Slot &s, const unsigned long long *dev, int n_word
     HIP_TRY(ctx, hipMemcpyAsync(s.h_ctl + first_word, dev, (size_t)n_words * 8, hipMemcpyDeviceToHost, s.stream));
     HIP_TRY(ctx, hipStreamSynchronize(s.stream));
     return PFAC_OK;
+}
+
+// The sort of pfac_documents_term_counts and pfac_documents_rules: n 8-byte keys in the first half of s.tc_keys (2 n
+// entries), a stable LSD radix sort over `passes` digits of TOP_BITS bits.  A workgroup takes `chunks` chunks of TC_BLOCK
+// keys, so that a pass has PFAC_TERMS_SORT_ROWS workgroups at most (the PFAC_TERMS_ROWS knob); n <= TC_BLOCK keys are
+// sorted by one workgroup.  tc_sort_reserve grows the digit counts (before the first launch that writes the keys: growing
+// waits for the stream); tc_sort queues the passes and returns the half that holds the sorted keys.
+struct TcSortShape {
+    unsigned chunks, n_blocks;
+    bool one;
+};
+TcSortShape tc_sort_shape(const pfac_ctx *ctx, uint64_t n) {
+    const uint64_t n_chunks = (n + TC_BLOCK - 1) / TC_BLOCK;
+    const uint64_t rows = ctx->plan.knobs.terms_rows ? ctx->plan.knobs.terms_rows : PFAC_TERMS_SORT_ROWS;
+    const unsigned chunks = (unsigned)std::max<uint64_t>(1, (n_chunks + rows - 1) / rows);
+    return TcSortShape{chunks, (unsigned)((n_chunks + chunks - 1) / chunks), n <= (uint64_t)TC_BLOCK};
+}
+int tc_sort_reserve(pfac_ctx *ctx, Slot &s, uint64_t n, int passes) {
+    const TcSortShape sh = tc_sort_shape(ctx, n);
+    if (sh.one || !passes) return PFAC_OK;
+    return s.tc_bh.ensure(ctx, s.stream, (uint64_t)TOP_BINS * (sh.n_blocks + 1), (uint64_t)TOP_BINS * (quarter_more(sh.n_blocks) + 1));
+}
+const unsigned long long *tc_sort(pfac_ctx *ctx, Slot &s, uint64_t n, int passes) {
+    const TcSortShape sh = tc_sort_shape(ctx, n);
+    const unsigned chunks = sh.chunks, n_blocks = sh.n_blocks;
+    unsigned long long *a = s.tc_keys.p, *b = s.tc_keys.p + n;
+    if (sh.one && passes) {
+        hipLaunchKernelGGL(pfac_tc_sort_one_kernel, dim3(1), dim3(TS_WAVES * WAVE), 0, s.stream, a, (unsigned long long)n, passes);
+    } else {
+        unsigned *tot = s.tc_bh.p + (uint64_t)TOP_BINS * n_blocks;
+        for (int pass = 0; pass < passes; pass++) {
+            hipLaunchKernelGGL(pfac_tc_sort_hist_kernel, dim3(n_blocks), dim3(TS_WAVES * WAVE), 0, s.stream, (const unsigned long long *)a,
+                               (unsigned long long)n, pass * TOP_BITS, chunks, n_blocks, s.tc_bh.p);
+            hipLaunchKernelGGL(pfac_tc_sort_rows_kernel, dim3(TOP_BINS), dim3(TS_WAVES * WAVE), 0, s.stream, s.tc_bh.p, n_blocks, tot);
+            hipLaunchKernelGGL(pfac_tc_sort_scatter_kernel, dim3(n_blocks), dim3(TS_WAVES * WAVE), 0, s.stream, (const unsigned long long *)a,
+                               (unsigned long long)n, pass * TOP_BITS, chunks, n_blocks, (const unsigned *)s.tc_bh.p, (const unsigned *)tot, b);
+            std::swap(a, b);
+        }
+    }
+    return a;
 }
 
 // What a pass needs of the slot's last scan, tested in this order (the first failure is the one reported).
@@ -6329,6 +6514,7 @@ int install_table(pfac_ctx *ctx, const int *d_blob, const int32_t *hdr, size_t n
     ctx->sweight.reset();                                   // ... and the state weights
     ctx->spans.reset();                                     // ... and the state spans
     ctx->tok.reset(); ctx->btok.reset();                    // ... and the token ids
+    ctx->ru_sptr.reset(); ctx->ru_ent.reset(); ctx->ru_need.reset(); ctx->ru_n = ctx->ru_terms = 0;     // ... and the rules
     ctx->have_table = false; ctx->table_gen++;
     TablePlan P;
     if (int rc = build_plan(ctx, P, d_blob, hdr, stream)) return rc;
@@ -7737,12 +7923,6 @@ int pfac_documents_term_counts(pfac_ctx *ctx, int slot, const pfac_record *d_sel
     const int passes = (int)((sbits + dbits + TOP_BITS - 1) / TOP_BITS);
     const unsigned n_groups = (unsigned)((n + DM_BLOCKS * WAVE - 1) / (DM_BLOCKS * WAVE));
     const uint64_t n_heads_blocks = (n + WAVE - 1) / WAVE;
-    // the sort's shape: a block takes `chunks` chunks of TC_BLOCK keys, so that a pass has PFAC_TERMS_SORT_ROWS blocks at most
-    const uint64_t n_chunks = (n + TC_BLOCK - 1) / TC_BLOCK;
-    const uint64_t rows = ctx->plan.knobs.terms_rows ? ctx->plan.knobs.terms_rows : PFAC_TERMS_SORT_ROWS;
-    const unsigned chunks = (unsigned)std::max<uint64_t>(1, (n_chunks + rows - 1) / rows);
-    const unsigned n_blocks = (unsigned)((n_chunks + chunks - 1) / chunks);
-    const bool one = n <= (uint64_t)TC_BLOCK;
     rc = ensure_gsum(ctx, s, n_groups + 1);                 // the group prefixes, the total, the error word
     if (rc) return rc;
     unsigned long long *res = s.gsum.p + n_groups;
@@ -7752,8 +7932,7 @@ int pfac_documents_term_counts(pfac_ctx *ctx, int slot, const pfac_record *d_sel
         rc = s.tc_keys.ensure(ctx, s.stream, 2 * n, 2 * (n + n / 8 + 4096));
         if (!rc) rc = s.tc_bal.ensure(ctx, s.stream, n_heads_blocks, quarter_more(n_heads_blocks));
         if (!rc) rc = s.tc_x.ensure(ctx, s.stream, n_heads_blocks, quarter_more(n_heads_blocks));
-        if (!rc && !one && passes)
-            rc = s.tc_bh.ensure(ctx, s.stream, (uint64_t)TOP_BINS * (n_blocks + 1), (uint64_t)TOP_BINS * (quarter_more(n_blocks) + 1));
+        if (!rc) rc = tc_sort_reserve(ctx, s, n, passes);
         if (rc) return rc;
     }
     if (n_docs) {
@@ -7763,21 +7942,7 @@ int pfac_documents_term_counts(pfac_ctx *ctx, int slot, const pfac_record *d_sel
                            (unsigned long long)n_docs, num_final, sbits, s.tc_keys.p, res + 1);
     }
     if (n) {
-        unsigned long long *a = s.tc_keys.p, *b = s.tc_keys.p + n;
-        if (one && passes) {
-            hipLaunchKernelGGL(pfac_tc_sort_one_kernel, dim3(1), dim3(TS_WAVES * WAVE), 0, s.stream, a, (unsigned long long)n, passes);
-        } else {
-            unsigned *tot = s.tc_bh.p + (uint64_t)TOP_BINS * n_blocks;
-            for (int pass = 0; pass < passes; pass++) {
-                hipLaunchKernelGGL(pfac_tc_sort_hist_kernel, dim3(n_blocks), dim3(TS_WAVES * WAVE), 0, s.stream, (const unsigned long long *)a,
-                                   (unsigned long long)n, pass * TOP_BITS, chunks, n_blocks, s.tc_bh.p);
-                hipLaunchKernelGGL(pfac_tc_sort_rows_kernel, dim3(TOP_BINS), dim3(TS_WAVES * WAVE), 0, s.stream, s.tc_bh.p, n_blocks, tot);
-                hipLaunchKernelGGL(pfac_tc_sort_scatter_kernel, dim3(n_blocks), dim3(TS_WAVES * WAVE), 0, s.stream, (const unsigned long long *)a,
-                                   (unsigned long long)n, pass * TOP_BITS, chunks, n_blocks, (const unsigned *)s.tc_bh.p, (const unsigned *)tot, b);
-                std::swap(a, b);
-            }
-        }
-        sorted = a;
+        sorted = tc_sort(ctx, s, n, passes);
         hipLaunchKernelGGL(pfac_tc_heads_kernel, dim3((n_groups + 3) / 4), dim3(256), 0, s.stream, sorted, (unsigned long long)n,
                            s.tc_bal.p, s.tc_x.p, s.gsum.p, n_groups);
         hipLaunchKernelGGL(pfac_scan_groups_kernel, dim3(1), dim3(1024), 0, s.stream, s.gsum.p, n_groups);
@@ -7811,6 +7976,7 @@ int pfac_documents_term_counts(pfac_ctx *ctx, int slot, const pfac_record *d_sel
     } else {
         HIP_TRY(ctx, hipMemsetAsync(row, 0, (n_docs + 1) * 8, s.stream));     // no record: every document is empty
     }
+    s.tc_table = ctx->table_gen;
     s.tc_row.commit(n_docs + 1, !d_row_ptr_out);
     s.tc_st.commit(total, !d_states_out);
     s.tc_cnt.commit(total, !d_counts_out);
@@ -7825,6 +7991,196 @@ int pfac_documents_term_counts_d2h(pfac_ctx *ctx, int slot, uint64_t *host_row_p
     rc = fetch(ctx, s, s.tc_row, me, pass, host_row_ptr, 0, s.tc_row.n, true);
     if (!rc) rc = fetch(ctx, s, s.tc_st, me, pass, host_states, 0, s.tc_st.n, true);
     return rc ? rc : fetch(ctx, s, s.tc_cnt, me, pass, host_counts, 0, s.tc_cnt.n, true);
+}
+
+// The rule table: validated whole on the host (a refused call keeps the earlier rules), inverted to state-major by a
+// counting sort -- the rules ascend inside a state because they are visited in order -- and uploaded as the state groups
+// are: buffers of their own for every call, and freeing the old ones waits for the device.
+int pfac_table_set_rules(pfac_ctx *ctx, const uint64_t *rule_ptr, const uint32_t *terms, const uint32_t *need, uint64_t n_rules) {
+    const std::string fn = "pfac_table_set_rules";
+    if (!ctx) return fail(nullptr, PFAC_E_ARG, "null context");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (!ctx->have_table) return fail(ctx, PFAC_E_STATE, fn + " before a table upload");
+    const uint64_t num_final = (uint64_t)ctx->plan.base.num_final;
+    std::vector<unsigned> sptr(num_final + 1, 0u), ent;
+    if (n_rules) {
+        if (!rule_ptr || !need) return fail(ctx, PFAC_E_ARG, fn + ": null rule_ptr or need");
+        if (n_rules >= (1ull << 31)) return fail(ctx, PFAC_E_ARG, fn + ": n_rules must be below 2^31");
+        if (rule_ptr[0] != 0) return fail(ctx, PFAC_E_ARG, fn + ": rule_ptr[0] must be 0");
+        for (uint64_t r = 0; r < n_rules; r++)
+            if (rule_ptr[r + 1] < rule_ptr[r]) return fail(ctx, PFAC_E_ARG, fn + ": rule_ptr decreases at rule " + std::to_string(r));
+        const uint64_t n_terms = rule_ptr[n_rules];
+        if (n_terms >= (1ull << 32)) return fail(ctx, PFAC_E_ARG, fn + ": the rules must hold fewer than 2^32 terms");
+        if (n_terms && !terms) return fail(ctx, PFAC_E_ARG, fn + ": null terms");
+        std::vector<unsigned> seen(num_final, 0u);              // the last rule (+ 1) that named the state
+        for (uint64_t r = 0; r < n_rules; r++) {
+            uint64_t positive = 0;
+            for (uint64_t t = rule_ptr[r]; t < rule_ptr[r + 1]; t++) {
+                const uint32_t st = terms[t] & ~PFAC_RULE_NOT;
+                if (st >= num_final)
+                    return fail(ctx, PFAC_E_ARG, fn + ": rule " + std::to_string(r) + " names state " + std::to_string(st) + ", num_final is " + std::to_string(num_final));
+                if (seen[st] == (unsigned)r + 1u)
+                    return fail(ctx, PFAC_E_ARG, fn + ": rule " + std::to_string(r) + " names state " + std::to_string(st) + " twice");
+                seen[st] = (unsigned)r + 1u;
+                positive += !(terms[t] & PFAC_RULE_NOT);
+                sptr[st + 1]++;
+            }
+            if (need[r] == 0 || need[r] > positive)
+                return fail(ctx, PFAC_E_ARG, fn + ": need of rule " + std::to_string(r) + " is " + std::to_string(need[r]) + ", it has " + std::to_string(positive) + " positive terms");
+        }
+        for (uint64_t st = 0; st < num_final; st++) sptr[st + 1] += sptr[st];
+        ent.resize(n_terms);
+        std::vector<unsigned> at(sptr.begin(), sptr.end() - 1);
+        for (uint64_t r = 0; r < n_rules; r++)
+            for (uint64_t t = rule_ptr[r]; t < rule_ptr[r + 1]; t++)
+                ent[at[terms[t] & ~PFAC_RULE_NOT]++] = (unsigned)r << 1 | (terms[t] >> 31);
+    }
+    USE_DEVICE(ctx);
+    ctx->ru_sptr.reset(); ctx->ru_ent.reset(); ctx->ru_need.reset();
+    ctx->ru_n = ctx->ru_terms = 0;
+    if (!n_rules) return PFAC_OK;
+    const uint64_t n_ent = std::max<uint64_t>(ent.size(), 1);
+    int rc = ctx->ru_sptr.ensure(ctx, nullptr, num_final + 1, num_final + 1);
+    if (!rc) rc = ctx->ru_ent.ensure(ctx, nullptr, n_ent, n_ent);
+    if (!rc) rc = ctx->ru_need.ensure(ctx, nullptr, n_rules, n_rules);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpy(ctx->ru_sptr.p, sptr.data(), (num_final + 1) * 4, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemset(ctx->ru_ent.p, 0, n_ent * 4));
+    if (!ent.empty()) HIP_TRY(ctx, hipMemcpy(ctx->ru_ent.p, ent.data(), ent.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(ctx->ru_need.p, need, n_rules * 4, hipMemcpyHostToDevice));
+    ctx->ru_n = n_rules;
+    ctx->ru_terms = ent.size();
+    return PFAC_OK;
+}
+
+// Rule sets: the count kernel (with the checks) and its group prefix, then the FIRST copy back (E and the error word:
+// E sizes the expand); the expand, the sort, the fired tails and their group prefix, then the second (the total); behind
+// the host's overflow check the write and row_ptr.
+int pfac_documents_rules(pfac_ctx *ctx, int slot, const uint64_t *d_row_ptr, const uint32_t *d_states, uint64_t n_docs, uint32_t flags,
+                         uint64_t *d_row_ptr_out, uint32_t *d_rules_out, uint64_t out_cap, uint64_t *n_fired) {
+    const std::string fn = "pfac_documents_rules";
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    if (!n_fired) return fail(ctx, PFAC_E_ARG, "null argument");
+    *n_fired = 0;
+    Slot &s = ctx->slots[slot];
+    s.ru_row.invalidate();
+    s.ru_out.invalidate();
+    if (!ctx->have_table) return fail(ctx, PFAC_E_STATE, fn + " before a table upload");
+    if (!ctx->ru_n) return fail(ctx, PFAC_E_STATE, fn + ": no rules for the uploaded table (pfac_table_set_rules)");
+    const unsigned long long *row_in = reinterpret_cast<const unsigned long long *>(d_row_ptr);
+    const unsigned *st_in = d_states;
+    const bool own = !d_row_ptr && !d_states;
+    uint64_t n = 0;
+    if (own) {
+        if (!s.tc_row.done || !s.tc_row.own || !s.tc_st.done || !s.tc_st.own)
+            return fail(ctx, PFAC_E_STATE, fn + ": the slot holds no pfac_documents_term_counts result (none yet, or it went to the caller's buffers; pass those)");
+        if (s.tc_table != ctx->table_gen) return fail(ctx, PFAC_E_STATE, fn + ": the term counts were made with an earlier table");
+    } else if (!d_row_ptr || !d_states) {
+        return fail(ctx, PFAC_E_ARG, fn + ": d_row_ptr and d_states are the slot's (both NULL) or the caller's (neither)");
+    }
+    if (flags) return fail(ctx, PFAC_E_ARG, fn + ": flags must be 0");
+    if (own) {
+        rc = s.tc_row.consume(ctx, fn, "row_ptr (d_row_ptr)", d_row_ptr, n_docs + 1, &row_in);
+        if (!rc) rc = s.tc_st.consume(ctx, fn, "states (d_states)", d_states, ANY_N, &st_in);
+        if (rc) return rc;
+        n = s.tc_st.n;
+    }
+    if (n_docs >= (1ull << 32)) return fail(ctx, PFAC_E_ARG, fn + ": n_docs must be below 2^32");
+    if ((((uintptr_t)row_in | (uintptr_t)d_row_ptr_out) & 7) || (((uintptr_t)st_in | (uintptr_t)d_rules_out) & 3))
+        return fail(ctx, PFAC_E_ARG, fn + ": misaligned buffer (d_row_ptr and d_row_ptr_out 8 B, d_states and d_rules_out 4 B)");
+    USE_DEVICE(ctx);
+    if (!own) {                                             // how many pairs the caller's arrays hold: row_ptr[n_docs]
+        HIP_TRY(ctx, hipMemcpyAsync(s.h_ctl + H_PASS, row_in + n_docs, 8, hipMemcpyDeviceToHost, s.stream));
+        HIP_TRY(ctx, hipStreamSynchronize(s.stream));
+        n = host_u64(s, H_PASS);
+    }
+    if (n >= (1ull << 32)) return fail(ctx, PFAC_E_ARG, fn + ": the pair count, d_row_ptr[n_docs], must be below 2^32");
+    const char *broken = ": d_row_ptr must start at 0 and not decrease, and the states of a row must strictly ascend below num_final";
+    if (n_docs == 0 && n) return fail(ctx, PFAC_E_ARG, fn + broken);
+    const unsigned num_final = (unsigned)ctx->plan.base.num_final;
+    auto bit_width = [](uint64_t v) { unsigned b = 0; while (v) { b++; v >>= 1; } return b; };
+    const unsigned rbits = bit_width(ctx->ru_n - 1), dbits = bit_width(n_docs ? n_docs - 1 : 0);
+    const unsigned rmask = (unsigned)((1ull << rbits) - 1ull);
+    const int passes = (int)((dbits + rbits + 1 + TOP_BITS - 1) / TOP_BITS);
+    // 1. the keys of every pair
+    const unsigned p_groups = (unsigned)((n + DM_BLOCKS * WAVE - 1) / (DM_BLOCKS * WAVE));
+    rc = s.ru_gsum.ensure(ctx, s.stream, (uint64_t)p_groups + 2, quarter_more(p_groups) + 2);
+    if (!rc && n) rc = s.ru_cpre.ensure(ctx, s.stream, n, n + n / 8 + 4096);
+    if (!rc && n) rc = s.ru_doc.ensure(ctx, s.stream, n, n + n / 8 + 4096);
+    if (rc) return rc;
+    unsigned long long *pres = s.ru_gsum.p + p_groups;
+    HIP_TRY(ctx, hipMemsetAsync(pres, 0, 16, s.stream));
+    if (n_docs) {
+        const uint64_t vblocks = (n_docs + 255) / 256;
+        const unsigned blocks = (unsigned)std::max<uint64_t>(1, std::max<uint64_t>(((uint64_t)p_groups + 3) / 4, std::min<uint64_t>(vblocks, 4096)));
+        hipLaunchKernelGGL(pfac_ru_count_kernel, dim3(blocks), dim3(256), 0, s.stream, row_in, (unsigned long long)n_docs, st_in,
+                           (unsigned long long)n, (const unsigned *)ctx->ru_sptr.p, num_final, s.ru_cpre.p, s.ru_doc.p, s.ru_gsum.p,
+                           p_groups, pres + 1);
+        if (p_groups) hipLaunchKernelGGL(pfac_scan_groups_kernel, dim3(1), dim3(1024), 0, s.stream, s.ru_gsum.p, p_groups);
+    }
+    rc = pass_words(ctx, s, pres, 2);
+    if (rc) return rc;
+    if (host_u64(s, H_PASS1)) return fail(ctx, PFAC_E_ARG, fn + broken);
+    const uint64_t E = host_u64(s, H_PASS);
+    if (E >= (1ull << 32)) return fail(ctx, PFAC_E_ARG, fn + ": the pairs expand into " + std::to_string(E) + " (document, rule) entries, the limit is 2^32 - 1");
+    // 2. - 4. expand, sort, the fired tails
+    const unsigned n_groups = (unsigned)((E + DM_BLOCKS * WAVE - 1) / (DM_BLOCKS * WAVE));
+    const uint64_t n_blocks64 = (E + WAVE - 1) / WAVE;
+    const unsigned long long *sorted = nullptr;
+    uint64_t total = 0;
+    if (E) {
+        rc = ensure_gsum(ctx, s, n_groups);
+        if (!rc) rc = s.tc_keys.ensure(ctx, s.stream, 2 * E, 2 * (E + E / 8 + 4096));
+        if (!rc) rc = s.tc_bal.ensure(ctx, s.stream, n_blocks64, quarter_more(n_blocks64));
+        if (!rc) rc = s.tc_x.ensure(ctx, s.stream, n_blocks64, quarter_more(n_blocks64));
+        if (!rc) rc = tc_sort_reserve(ctx, s, E, passes);
+        if (rc) return rc;
+        const unsigned eblocks = (unsigned)std::min<uint64_t>((E + 255) / 256, 1u << 20);
+        hipLaunchKernelGGL(pfac_ru_expand_kernel, dim3(eblocks), dim3(256), 0, s.stream, st_in, (unsigned long long)n,
+                           (const unsigned *)s.ru_cpre.p, (const unsigned *)s.ru_doc.p, (const unsigned long long *)s.ru_gsum.p, p_groups,
+                           (const unsigned *)ctx->ru_sptr.p, (const unsigned *)ctx->ru_ent.p, rbits, (unsigned long long)E, s.tc_keys.p);
+        sorted = tc_sort(ctx, s, E, passes);
+        hipLaunchKernelGGL(pfac_ru_fired_kernel, dim3((n_groups + 3) / 4), dim3(256), 0, s.stream, sorted, (unsigned long long)E,
+                           (const unsigned *)ctx->ru_need.p, rmask, s.tc_bal.p, s.tc_x.p, s.gsum.p, n_groups);
+        hipLaunchKernelGGL(pfac_scan_groups_kernel, dim3(1), dim3(1024), 0, s.stream, s.gsum.p, n_groups);
+        rc = pass_words(ctx, s, s.gsum.p + n_groups, 1);
+        if (rc) return rc;
+        total = host_u64(s, H_PASS);
+    }
+    *n_fired = total;
+    if (d_rules_out && total > out_cap)
+        return fail(ctx, PFAC_E_OVERFLOW, fn + ": " + std::to_string(total) + " fired rules, out_cap is " + std::to_string(out_cap));
+    // 5. the write and row_ptr
+    unsigned long long *row;
+    unsigned *out;
+    rc = s.ru_row.bind(ctx, s.stream, d_row_ptr_out, n_docs + 1, docs_cap(n_docs), &row);
+    if (!rc) rc = s.ru_out.bind(ctx, s.stream, d_rules_out, total, total + total / 8 + 4096, &out);
+    if (rc) return rc;
+    if (total) {
+        hipLaunchKernelGGL(pfac_ru_write_kernel, dim3((n_groups + 3) / 4), dim3(256), 0, s.stream, sorted, (unsigned long long)E,
+                           (const unsigned long long *)s.tc_bal.p, (const unsigned *)s.tc_x.p, (const unsigned long long *)s.gsum.p, n_groups,
+                           rmask, (unsigned long long)total, out);
+        const unsigned rblocks = (unsigned)std::min<uint64_t>((n_docs + 1 + 255) / 256, 1u << 20);
+        hipLaunchKernelGGL(pfac_ru_rowptr_kernel, dim3(rblocks), dim3(256), 0, s.stream, sorted, (unsigned long long)E,
+                           (unsigned long long)n_docs, rbits, (const unsigned long long *)s.tc_bal.p, (const unsigned *)s.tc_x.p,
+                           (const unsigned long long *)s.gsum.p, (unsigned long long)total, row);
+        HIP_TRY(ctx, hipGetLastError());
+    } else {
+        HIP_TRY(ctx, hipMemsetAsync(row, 0, (n_docs + 1) * 8, s.stream));     // no rule fired: every row is empty
+    }
+    s.ru_row.commit(n_docs + 1, !d_row_ptr_out);
+    s.ru_out.commit(total, !d_rules_out);
+    return PFAC_OK;
+}
+
+int pfac_documents_rules_d2h(pfac_ctx *ctx, int slot, uint64_t *host_row_ptr, uint32_t *host_rules) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    Slot &s = ctx->slots[slot];
+    const char *me = "pfac_documents_rules_d2h", *pass = "pfac_documents_rules";
+    rc = fetch(ctx, s, s.ru_row, me, pass, host_row_ptr, 0, s.ru_row.n, true);
+    return rc ? rc : fetch(ctx, s, s.ru_out, me, pass, host_rules, 0, s.ru_out.n, true);
 }
 
 // Proximity rules: the rules' upload, the blocks' last A / last B, their carry-in, the memset and the pass queued back to

@@ -21,6 +21,7 @@ from ._ffi import PFAC_TOP_BY_COUNT, PFAC_TOP_LOWEST, PFAC_TOP_RANKED
 from ._ffi import PFAC_TERMS_SELECTION
 from ._ffi import PFAC_TOKENS_POSITIONS
 from ._ffi import PFAC_NEAR_SELECTION
+from ._ffi import PFAC_E_STATE
 from .table import NEAR_RULE_DTYPE, RECORD_DTYPE,SCORE_DTYPE, TEMPLATE_PLAIN, TOKEN_DROP, PfacTable, redaction_table, replacement_table, template_table, token_table, _state_lengths
 
 
@@ -94,6 +95,7 @@ class GpuMatcher:
         self._keep_mark = {}            # per slot: how many of its kept h2d sources were queued before its last scan_async
         self._last_n = {}
         self._flen_set = False          # final-state lengths on the device for the uploaded table (scan_documents)
+        self._n_rules = 0               # rules of the uploaded table (set_rules; an upload drops them)
         self._cnt_n = {}                # per slot: entries of its slot-owned state counts (count_states)
         rc = self._L.pfac_ctx_create(int(device), int(n_streams), C.byref(self._ctx))
         if rc:
@@ -151,6 +153,7 @@ class GpuMatcher:
             blob = np.ascontiguousarray(table, dtype=np.int32)
             self.table = PfacTable.from_blob(blob)
         self._flen_set = False
+        self._n_rules = 0
         self._check(self._L.pfac_table_upload(self._ctx, blob.ctypes.data, blob.size))
         if self.table.ignore_case:          # (an upload leaves the fold off)
             self.set_case_fold(True)
@@ -158,6 +161,7 @@ class GpuMatcher:
     def load_table_device(self, d_blob, n_words: int, stream: int = 0, host_table: Optional[PfacTable] = None) -> None:
         """Install a table image that already sits in this GPU's memory (e.g. after an RCCL broadcast)."""
         self._flen_set = False
+        self._n_rules = 0
         self._check(self._L.pfac_table_upload_device(self._ctx, _ptr(d_blob), int(n_words), stream))
         if host_table is not None:
             self.table = host_table
@@ -1061,6 +1065,82 @@ class GpuMatcher:
         col = d_states.view(torch.int32)[: int(n_terms)].to(torch.int64)
         val = d_counts.view(torch.int32)[: int(n_terms)]
         return torch.sparse_csr_tensor(row, col, val, size=(int(n_docs), self._n_states()))
+
+    # -- rule sets: which of many rules fired in each document ----------------
+    def set_rules(self, rules) -> int:
+        """The rule table of the uploaded table (``pfac_table_set_rules``): ``rules`` is what ``PfacTable.rule_table``
+        takes (a list of rules over pattern ids) or what it returns (``rule_ptr``, ``terms``, ``need``).  Rule r fires
+        in a document iff at least ``need[r]`` of its positive states and none of its negated ones occur there.  A
+        table upload drops the rules; an empty list clears them.  Returns the number of rules."""
+        if isinstance(rules, tuple) and len(rules) == 3 and all(isinstance(a, np.ndarray) for a in rules):
+            ptr, terms, need = rules
+        else:
+            if self.table is None:
+                raise PfacError(PFAC_E_STATE, "set_rules before load_table")
+            ptr, terms, need = self.table.rule_table(rules)
+        ptr = np.ascontiguousarray(ptr, dtype=np.uint64)
+        terms = np.ascontiguousarray(terms, dtype=np.uint32)
+        need = np.ascontiguousarray(need, dtype=np.uint32)
+        if ptr.size != need.size + 1:
+            raise ValueError("rule_ptr has one entry more than need")
+        self._check(self._L.pfac_table_set_rules(self._ctx, ptr.ctypes.data, terms.ctypes.data if terms.size else None,
+                                                 need.ctypes.data if need.size else None, int(need.size)))
+        self._n_rules = int(need.size)
+        return self._n_rules
+
+    def document_rules(self, n_docs: int, d_row_ptr=None, d_states=None, d_row_ptr_out=None, d_rules=None, out_cap: int = 0,
+                       slot: int = 0) -> int:
+        """Which rules of ``set_rules`` fire in each document, on the GPU (``pfac_documents_rules``): the join of a
+        document-term matrix with the rule table, as a CSR -- ``row_ptr`` uint64[n_docs + 1] and ``rules``
+        uint32[n_fired], a document's rule ids strictly ascending.  ``d_row_ptr`` and ``d_states`` both None = the
+        slot-owned result of the slot's last ``document_term_counts``; else the first two device arrays of one.
+        ``d_row_ptr_out`` / ``d_rules`` None = slot-owned buffers (``rules_to_host``); else device buffers, ``d_rules``
+        of ``out_cap`` entries.  Returns the number of fired (document, rule) pairs; a too small ``out_cap`` raises
+        PfacError(PFAC_E_OVERFLOW) whose ``n_fired`` attribute holds the exact count."""
+        n = C.c_uint64(0)
+        rc = self._L.pfac_documents_rules(self._ctx, slot, _ptr(d_row_ptr), _ptr(d_states), int(n_docs), 0, _ptr(d_row_ptr_out),
+                                          _ptr(d_rules), int(out_cap), C.byref(n))
+        return self._counted(rc, n, "n_fired")
+
+    def rules_to_host(self, n_docs: int, n_fired: int, slot: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+        """(row_ptr uint64[n_docs + 1], rules uint32[n_fired]) of the slot's last ``document_rules`` into slot-owned
+        buffers."""
+        return self._to_host(slot, lambda r, f: self._L.pfac_documents_rules_d2h(self._ctx, slot, r, f),
+                             (int(n_docs) + 1, np.uint64), (n_fired, np.uint32))
+
+    def _rules_pass(self, n_docs: int, slot: int, non_overlapping: bool) -> Tuple[np.ndarray, np.ndarray]:
+        if non_overlapping:
+            self.select_leftmost_longest_documents(n_docs, slot=slot)
+        else:
+            self.segment_records(n_docs, slot=slot)
+        self.document_term_counts(n_docs, selection=non_overlapping, slot=slot)
+        return self.rules_to_host(n_docs, self.document_rules(n_docs, slot=slot), slot)
+
+    def rules_documents(self, docs, whole_words=False, spans: bool = False, line_match: bool = False,
+                        non_overlapping: bool = False, slot: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+        """The fired rules of every document of a batch (``docs`` as ``scan_documents`` takes it) in one scan: the scan,
+        the document cut (``non_overlapping``: the leftmost-longest picks of each document instead of every match),
+        the term counts and ``document_rules`` on the device; only the CSR comes back -- (row_ptr, rules)."""
+        _, n_docs = self._scan_docs(docs, slot, whole_words, spans, line_match)
+        return self._rules_pass(n_docs, slot, non_overlapping)
+
+    def rules_lines(self, data, delimiter=b"\n", whole_words=False, spans: bool = False, line_match: bool = False,
+                    non_overlapping: bool = False, slot: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+        """``rules_documents`` of one buffer cut into lines at ``delimiter`` on the device: row d is line d."""
+        _, n_docs = self._scan_lines(data, delimiter, slot, whole_words, fetch_offsets=False, spans=spans, line_match=line_match)
+        return self._rules_pass(n_docs, slot, non_overlapping)
+
+    def rule_matrix(self, n_docs: int, n_fired: int, d_row_ptr, d_rules, n_rules: Optional[int] = None):
+        """The caller's device tensors of a ``document_rules`` (``d_row_ptr`` int64 or uint64 storage of n_docs + 1
+        entries, ``d_rules`` 32-bit storage of at least ``n_fired``) as a ``torch.sparse_csr_tensor`` of shape (n_docs,
+        n_rules) with values 1, on their device (``n_rules`` None: the rules of the last ``set_rules``).  The column
+        indices are widened in torch; nothing is copied to the host.  The pass writes on the slot's stream:
+        synchronise it (``sync``) before torch reads the matrix."""
+        import torch
+        row = d_row_ptr.view(torch.int64)[: int(n_docs) + 1]
+        col = d_rules.view(torch.int32)[: int(n_fired)].to(torch.int64)
+        val = torch.ones(int(n_fired), dtype=torch.int32, device=col.device)
+        return torch.sparse_csr_tensor(row, col, val, size=(int(n_docs), int(self._n_rules if n_rules is None else n_rules)))
 
     # -- proximity rules: which pairs of pattern groups lie near each other ----
     def document_near_masks(self, n_docs: int, rules, d_sel=None, d_doc_first=None, selection: bool = False, d_out=None,

@@ -264,6 +264,95 @@ class PfacTable:
         np.bitwise_or.at(out, np.repeat(np.arange(int(self.num_final)), np.diff(np.asarray(first, dtype=np.int64))), per)
         return out
 
+    def _states_of_patterns(self):
+        """{1-based pattern id: [final states an input can reach that report it]}: the inverse of ``idmap`` (of the
+        outputs of a character-class table).  The state of a line that lost to a duplicate is reached by no input
+        (``final_lengths`` -1) and is left out, so such an id has no entry."""
+        first = getattr(self, "out_first", None)
+        live = self.final_lengths() >= 0
+        out = {}
+        if first is None:
+            for s, i in enumerate(np.asarray(self.idmap, dtype=np.int64).tolist()):
+                if live[s]:
+                    out.setdefault(i, []).append(s)
+        else:
+            first = np.asarray(first, dtype=np.int64)
+            ids = np.asarray(self.out_ids, dtype=np.int64).tolist()
+            for s in range(int(self.num_final)):
+                if live[s]:
+                    for i in ids[first[s]:first[s + 1]]:
+                        out.setdefault(i, []).append(s)
+        return out
+
+    def rule_table(self, rules):
+        """Rules over patterns -> ``(rule_ptr uint64[n_rules + 1], terms uint32[], need uint32[n_rules])`` for
+        ``pfac_table_set_rules`` (``GpuMatcher.set_rules``).  ``rules`` is a list; an item is an iterable of 1-based
+        pattern ids (all of them must occur), a dict ``{"all_of" | "any_of": ids, "none_of": ids, "need": k}``
+        (``all_of``: every id; ``any_of``: one of them; ``need``: at least k of them; ``none_of``: none of these may
+        occur), or a ready ``(positive states, negated states, need)`` triple of final states.  Pattern ids become
+        states through the inverse of ``idmap``; two ids of one rule that end in one state are merged, and a default
+        ``need`` counts distinct states.  ValueError, naming the id, for an id that lost to a duplicate line, a pattern
+        of a character-class table that ends in several states, a negated term on a state that is also positive, and an
+        explicit ``need`` above the distinct positive states."""
+        from ._ffi import PFAC_RULE_NOT
+        by_id, top = None, 0
+        ptr, terms, need = [0], [], []
+
+        def states(ids, r):
+            nonlocal by_id, top
+            if by_id is None:
+                by_id = self._states_of_patterns()
+                top = max(int(self.n_patterns), max(by_id, default=0))
+            out = []
+            for i in ids:
+                st = by_id.get(int(i))
+                if not 1 <= int(i) <= top:
+                    raise ValueError(f"rule {r}: pattern id {int(i)} is outside 1..{top}")
+                if not st:
+                    raise ValueError(f"rule {r}: pattern id {int(i)} lost to a duplicate line: no input reaches its state")
+                if len(st) > 1:
+                    raise ValueError(f"rule {r}: pattern id {int(i)} ends in several final states ({st[0]}, {st[1]}, ...)")
+                out.append((st[0], int(i)))
+            return out
+
+        for r, item in enumerate(rules):
+            k = None
+            if isinstance(item, tuple) and len(item) == 3 and not isinstance(item[0], (int, np.integer)):
+                pos = [(int(s), None) for s in item[0]]
+                neg = [(int(s), None) for s in item[1]]
+                k = int(item[2])
+                for s, _ in pos + neg:
+                    if not 0 <= s < self.num_final:
+                        raise ValueError(f"rule {r}: state {s} is outside [0, num_final = {self.num_final})")
+            elif isinstance(item, dict):
+                unknown = set(item) - {"all_of", "any_of", "none_of", "need"}
+                if unknown or ("all_of" in item) == ("any_of" in item):
+                    raise ValueError(f"rule {r}: a rule names all_of or any_of (one of them), none_of and need")
+                pos = states(item.get("all_of", item.get("any_of")), r)
+                neg = states(item.get("none_of", ()), r)
+                k = int(item["need"]) if "need" in item else (1 if "any_of" in item else None)
+            else:
+                pos, neg = states(item, r), []
+            named = lambda t: f"state {t[0]}" if t[1] is None else f"pattern id {t[1]}"     # noqa: E731
+            p_states = {}
+            for t in pos:
+                p_states.setdefault(t[0], t)
+            n_states = {}
+            for t in neg:
+                if t[0] in p_states:
+                    raise ValueError(f"rule {r}: the negated {named(t)} ends in state {t[0]}, which {named(p_states[t[0]])} makes positive")
+                n_states.setdefault(t[0], t)
+            if not p_states:
+                raise ValueError(f"rule {r}: a rule needs a positive term")
+            if k is None:
+                k = len(p_states)
+            if not 1 <= k <= len(p_states):
+                raise ValueError(f"rule {r}: need {k} is outside 1..{len(p_states)}, its distinct positive states")
+            terms += sorted(p_states) + [s | PFAC_RULE_NOT for s in sorted(n_states)]
+            need.append(k)
+            ptr.append(len(terms))
+        return (np.array(ptr, dtype=np.uint64), np.array(terms, dtype=np.uint32), np.array(need, dtype=np.uint32))
+
     def state_weights(self, weights) -> np.ndarray:
         """Pattern weights -> int32[num_final] for ``pfac_table_set_state_weights``.  ``weights`` is indexed by the
         1-based pattern id (entry 0 is unused), one integer per id the table can report, as in
