@@ -1350,6 +1350,60 @@ int pfac_tokens_d2h(pfac_ctx *ctx, int slot, int32_t *host_ids, uint32_t *host_p
 /* D2H of the slot-owned token offsets of the last pfac_tokenize_documents (n_docs + 1 entries). */
 int pfac_tokens_offsets_d2h(pfac_ctx *ctx, int slot, uint64_t *host_tok_off);
 
+/* WordPiece: `##` continuation pieces and one [UNK] per word, over the passes above.  Whether a piece is word-initial
+ * depends on the input alone, and WordPiece never backtracks (the longest admissible piece, and a word with an
+ * untokenizable remainder is one [UNK]); so it is (1) the scan's records without those whose pattern is not in the
+ * vocabulary half their position asks for, (2) the leftmost-longest selection, (3) every word the picks do not cover
+ * completely collapsed into one [UNK].  ONE automaton over the stripped strings (`##ing` is inserted as `ing`); every
+ * final state has two ids.
+ * The attachment of the installed table: first_ids[s] / cont_ids[s], int32[n_states == num_final] each (kept on the
+ * device as one 8-byte pair per state), the id of s at a word's start / inside a word; byte_ids int32[256] (NULL =
+ * every byte DROP); every value >= 0 or PFAC_TOKEN_DROP.  unk_id >= 0.  word_set: the 256 bits of
+ * pfac_records_filter_words (NULL = [0-9A-Za-z_]).  max_word_bytes in 1..4095 (BERT's default is 100 characters; this
+ * cap counts bytes): a good word therefore touches at most two 4 KiB tiles, and a tile of word bytes alone holds a bad
+ * word by itself.  PFAC_E_ARG for anything else, PFAC_E_STATE before an upload; everything is checked before anything
+ * changes.  A table upload drops the attachment; it does not touch the ids of pfac_table_set_token_ids. */
+int pfac_table_set_wordpiece(pfac_ctx *ctx, const int32_t *first_ids, const int32_t *cont_ids, uint64_t n_states,
+                             const int32_t *byte_ids, int32_t unk_id, const uint64_t word_set[4], uint32_t max_word_bytes);
+/* Role filter: the third sibling of pfac_records_filter_words and pfac_records_filter_spans.  With W the attachment's
+ * word set, role(p) = FIRST if p == 0 or in[p - 1] is not in W, else CONT.  A record (p, s) stays iff in[p] is in W
+ * and the id of role(p) for s is not PFAC_TOKEN_DROP.  As the other filters: heap, tile index and count are rewritten
+ * IN PLACE; every reader and pass sees the kept records afterwards; a selection made before is stale; filters compose;
+ * an error leaves everything untouched.  d_input / d_records as pfac_records_filter_words.  PFAC_E_STATE (first, in
+ * the order of pfac_records_filter_spans): no finished scan, no final lengths, an earlier table, no WordPiece
+ * attachment, an overflowed heap.  The slot remembers that its scan went through this filter and under which
+ * attachment.  No documents form: where document offsets are word boundaries the byte rule already makes a document's
+ * first byte FIRST. */
+int pfac_records_filter_roles(pfac_ctx *ctx, int slot, const void *d_input, void *d_records, uint64_t *n_kept);
+/* THE RULE.  Over the slot's last finished scan and its last leftmost-longest selection (picks (p_k, s_k), made from
+ * entry 0), with C the union of the picks' byte ranges: a WORD is a maximal run of bytes of W inside [0, n_owned)
+ * (position n_owned ends a word); it is GOOD iff it is at most max_word_bytes long and every byte of it lies in C.
+ * Every position i of [0, n_owned), ascending:
+ *   - the first byte of a bad word emits unk_id; nothing else in that word emits;
+ *   - a pick start p_k inside a good word emits the role(p_k) id of s_k, unless that is PFAC_TOKEN_DROP;
+ *   - a byte not in W and outside C emits byte_ids[input[i]] (the byte as the caller wrote it, whatever the case
+ *     fold), unless that is PFAC_TOKEN_DROP;
+ *   - a byte not in W inside C emits nothing.
+ * The rule is stated on bitmaps and stays defined when a pattern holds a byte outside W; it only stops being BERT's.
+ * Parameters, PFAC_TOKENS_POSITIONS, the outputs (the slot-owned ones are the tokenizer's own: ONE result shared with
+ * pfac_tokenize_*, fetched with pfac_tokens_d2h / pfac_tokens_offsets_d2h), PFAC_E_OVERFLOW (exact *n_tokens, nothing
+ * written), the device checks of d_sel and the one copy back per call are those of pfac_tokenize_leftmost_longest and
+ * pfac_tokenize_documents.  PFAC_E_STATE, before PFAC_E_ARG: every state of those calls (with the WordPiece attachment
+ * in the place of the token ids); then a scan that has not been through pfac_records_filter_roles under the current
+ * attachment; then a selection made from entry != 0.  The documents form also needs every document offset on a word
+ * boundary -- off[d] is 0 or n_owned, or one of in[off[d] - 1], in[off[d]] is not in W (lines cut at a delimiter
+ * outside W are) -- checked on the device, one thread per offset; else PFAC_E_ARG, nothing written.
+ * Chained ranges (an entry, a word across n_owned) are out of scope: cut chunks at a byte outside W.
+ * Kernels: the tokenizer's first-pick search, group prefix and document offsets unchanged; an edge pass (a wave per
+ * tile: the bitmaps of word bytes, uncovered word bytes, kept pick starts and byte emitters, kept for the next pass,
+ * and an 8-byte summary of the runs on the tile's two edges); a count pass that reads the two neighbours' summaries
+ * and floods "bad" along the runs of word bits in registers; a write pass like the tokenizer's. */
+int pfac_wordpiece_leftmost_longest(pfac_ctx *ctx, int slot, const void *d_input, const pfac_record *d_sel, uint32_t flags,
+                                    int32_t *d_ids, uint64_t out_cap, uint32_t *d_pos, uint64_t *n_tokens);
+int pfac_wordpiece_documents(pfac_ctx *ctx, int slot, const void *d_input, const pfac_record *d_sel, const uint64_t *d_doc_offsets,
+                             const uint64_t *d_doc_first, uint32_t flags, int32_t *d_ids, uint64_t out_cap, uint32_t *d_pos,
+                             uint64_t *d_tok_offsets, uint64_t *n_tokens);
+
 /* Synthetic input generators, written straight into device memory (the
  * reference built big inputs by tiling a small text, creatbiginput.sh:2-5).
  *   tiled : byte i = pattern[(phase + i) % period]

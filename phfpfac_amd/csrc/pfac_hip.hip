@@ -5429,6 +5429,391 @@ __global__ void pfac_tk_doc_kernel(const unsigned long long *off, unsigned long 
 }
 
 // ---------------------------------------------------------------------------
+// WordPiece (pfac_table_set_wordpiece, pfac_records_filter_roles, pfac_wordpiece_leftmost_longest / _documents).  One
+// automaton over the stripped strings; every final state has a pair of ids, .x for a piece at a word's start (FIRST),
+// .y for one inside a word (CONT).  role(p) depends on the input alone: CONT iff p > 0 and in[p - 1] is a word byte.
+//
+// Role filter (pfac_filter_roles_kernel): the walk of pfac_filter_words_kernel -- a wave per tile at a time, 64 tiles
+// per wave, chunks of 64 records, a ballot, the kept words stored at or below their own slots (in place is safe for the
+// reason given there).  Per record two byte gathers (p - 1, p) and one 8-byte gather of the id pair; kept iff in[p] is a
+// word byte and the id of role(p) is not DROP.
+template <int BYTES>
+__global__ void pfac_filter_roles_kernel(void *rec, unsigned long long *tix, unsigned long long n_tiles, unsigned long long cap,
+                                         const unsigned char *in, unsigned long long n_avail, const int2 *ids,
+                                         unsigned num_final, WordSet ws, unsigned long long *total) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    const unsigned g = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const unsigned n_groups = (unsigned)((n_tiles + XGROUP - 1) / XGROUP);
+    if (g >= n_groups) return;
+    const unsigned long long t = (unsigned long long)g * XGROUP + lane;
+    const unsigned long long e = t < n_tiles ? tix[t] : 0ull;
+    const unsigned c = (unsigned)(e >> TIX_CNT_SHIFT);
+    const unsigned long long lo = e & TIX_BASE_MASK;
+    unsigned mine = c;                                          // records tile t keeps
+    for (int j = 0; j < XGROUP; j++) {
+        const unsigned tc = __shfl(c, j, WAVE);
+        if (tc == 0) continue;
+        const unsigned long long tlo = __shfl(lo, j, WAVE);
+        unsigned kept = 0;
+        for (unsigned c0 = 0; c0 < tc; c0 += WAVE) {
+            const unsigned i = c0 + (unsigned)lane;
+            const bool have = i < tc && tlo + i < cap;
+            unsigned pos = 0, st = 0;
+            if (have) heap_record<BYTES>(rec, tlo + i, (unsigned long long)g * XGROUP + j, pos, st);
+            bool keep = false;
+            if (have && st < num_final && pos < n_avail && word_byte(ws, (int)in[pos])) {
+                const bool cont = pos > 0 && word_byte(ws, (int)in[pos - 1]);
+                const int2 pr = ids[st];
+                keep = (cont ? pr.y : pr.x) >= 0;
+            }
+            const unsigned long long b = __ballot(keep);
+            const unsigned to = kept + (unsigned)__popcll(b & ((1ull << lane) - 1ull));
+            if (keep && to != i) heap_put<BYTES>(rec, tlo + to, pos, st);
+            kept += (unsigned)__popcll(b);
+        }
+        if (lane == j) mine = kept;
+    }
+    if (t < n_tiles && mine != c) tix[t] = lo | (unsigned long long)mine << TIX_CNT_SHIFT;
+    const unsigned long long sum = wave_sum64(mine);
+    if (lane == 0 && sum) atomicAdd(total, sum);
+}
+
+// Token pass.  A word is a maximal run of word bytes inside [0, n_owned); it is good iff it is at most max_word bytes
+// long and every byte of it is covered by a pick.  Positions emit: the first byte of a bad word unk_id; a pick start
+// inside a good word the id of its role (unless DROP); a non-word byte outside every pick btok[byte] (unless DROP).
+//   pfac_tk_first_kernel     the tokenizer's, unchanged
+//   pfac_wp_edge_kernel      one wave per tile.  Four bitmaps of the tile's 4096 positions, KEPT for the count pass
+//                            (2 KiB per tile; it neither loads the input nor walks the picks again): W word bytes
+//                            below n_owned, U = W & ~covered, ST the own pick starts on a word byte whose role id is
+//                            kept, E0 the non-word bytes outside every pick whose btok is kept.  And the tile's edge
+//                            summary, four 16-bit fields: the length of the leading run of W and bit 15 = it holds a
+//                            bit of U; the same for the trailing run.  The d_sel checks of pfac_tk_count_kernel ride
+//                            along (each pick by the tile that owns its start).
+//   pfac_wp_count_kernel     a workgroup per 64 tiles, a wave per tile at a time, a lane per bitmap word; no LDS but the
+//                            tile counts.  max_word <= 4095, so a word touches at most two tiles unless it fills one
+//                            (then it is bad by itself): the verdict of a run on a tile edge needs the NEIGHBOUR's
+//                            summary only -- no scan over tiles.  Seeds of "bad": U; the edge bit of a run the
+//                            neighbour's summary condemns (its part is uncovered, or the two parts are too long
+//                            together); and every position that ends max_word + 1 word bits in a row -- found from the
+//                            run length that reaches each word's bit 0 (a segmented scan over the 64 lanes: + 64 per
+//                            full word) and, for max_word < 64, the AND of max_word + 1 shifted copies of the word by
+//                            doubling.  The seeds flood along W upwards and downwards: a Kogge-Stone fill inside the
+//                            64-bit word, the carries between the lanes by the same fill over the ballots of
+//                            "reaches bit 63 / bit 0" and "all ones".  bad & word start = the [UNK] positions;
+//                            emits = E0 | unk | ST & ~bad.  Kept: bm, wpre, tpre, gsum as the tokenizer keeps them (so
+//                            pfac_scan_groups_kernel and pfac_tk_doc_kernel serve unchanged), and the unk bitmap.
+//   pfac_wp_write_kernel     pfac_tk_write_kernel with two changes: the byte stage writes unk_id at the positions of
+//                            the unk bitmap; the pick stage skips those and takes .x or .y by the W bit in front of
+//                            the pick (one byte gather in front of the tile for its first position).
+//   pfac_wp_docs_kernel      one thread per document offset: 0, n_owned, or a non-word byte on one side of it.
+// No loop's trip count is the length of a word, a gap or a run of documents.
+constexpr int WP_MAPS = 4;                          // W, U, ST, E0
+constexpr unsigned WP_LEN = 0x7fffu, WP_BAD = 0x8000u;          // a summary field: run length (0..4096) | uncovered
+
+// the bits of word x (tile positions 64 x ..) that lie in [lo, hi)
+__device__ __forceinline__ unsigned long long wp_range(unsigned x, unsigned lo, unsigned hi) {
+    const unsigned b = x * 64u;
+    const unsigned a = lo > b ? lo - b : 0u, e = hi > b ? hi - b : 0u;
+    const unsigned long long ma = a >= 64u ? ~0ull : tk_below(a), me = e >= 64u ? ~0ull : tk_below(e);
+    return me & ~ma;
+}
+__device__ __forceinline__ unsigned long long wp_fill_up(unsigned long long g, unsigned long long p) {
+#pragma unroll
+    for (int sh = 1; sh < 64; sh <<= 1) {
+        g |= p & (g << sh);
+        p &= p << sh;
+    }
+    return g;
+}
+__device__ __forceinline__ unsigned long long wp_fill_down(unsigned long long g, unsigned long long p) {
+#pragma unroll
+    for (int sh = 1; sh < 64; sh <<= 1) {
+        g |= p & (g >> sh);
+        p &= p >> sh;
+    }
+    return g;
+}
+
+__global__ void __launch_bounds__(WAVE)
+pfac_wp_edge_kernel(const unsigned char *in, unsigned long long n_avail, const pfac_record *sel, unsigned long long n,
+                    unsigned long long n_owned, const short *flen, const int2 *ids, const int *btok, unsigned num_final,
+                    const unsigned long long *first, WordSet ws, unsigned long long *maps, unsigned long long *sum,
+                    unsigned long long *res) {
+    __shared__ unsigned long long s_w[TK_WORDS], s_e0[TK_WORDS], s_cov[TK_WORDS], s_start[TK_WORDS];
+    const int lane = threadIdx.x;
+    const unsigned long long t = blockIdx.x;
+    const unsigned long long tile_lo = t * WTILE, tile_hi = tile_lo + WTILE;
+    const unsigned long long own_hi = tile_hi < n_owned ? tile_hi : n_owned;
+    WordSet bv;                                                     // the non-word bytes whose btok is kept
+#pragma unroll
+    for (int k = 0; k < 4; k++) bv.w[k] = __ballot(btok[k * WAVE + lane] >= 0) & ~ws.w[k];
+    s_cov[lane] = 0ull;
+    s_start[lane] = 0ull;
+#pragma unroll
+    for (int j = 0; j < SUBS; j++) {
+        const unsigned lp = (unsigned)j * SUB + (unsigned)lane * 16u, sh = lp & 63u;
+        const unsigned long long g = tile_lo + lp;
+        const unsigned dom = tk_domain16(g, 0ull, n_owned);
+        unsigned wb = 0u, nb = 0u;
+        if (dom) {
+            const uint4 v = tk_load16(in, g, n_avail);
+            const unsigned q[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int c = 0; c < 16; c++) {
+                const int byte = (int)((q[c >> 2] >> (8 * (c & 3))) & 255u);
+                wb |= (unsigned)word_byte(ws, byte) << c;
+                nb |= (unsigned)word_byte(bv, byte) << c;
+            }
+        }
+        unsigned long long a = (unsigned long long)(wb & dom) << sh, b = (unsigned long long)(nb & dom) << sh;
+        a |= __shfl_xor(a, 1, WAVE);
+        a |= __shfl_xor(a, 2, WAVE);
+        b |= __shfl_xor(b, 1, WAVE);
+        b |= __shfl_xor(b, 2, WAVE);
+        if ((lane & 3) == 0) {
+            s_w[lp >> 6] = a;
+            s_e0[lp >> 6] = b;
+        }
+    }
+    wave_lds_sync();
+    const bool cont0 = t > 0 && word_byte(ws, (int)in[tile_lo - 1]);       // (tile_lo < n_owned <= n_avail)
+    bool bad = false;
+    const unsigned long long f0 = first[t], f1 = first[t + 1];
+    bad |= f0 > f1 || f1 > n;
+    const unsigned long long k1 = f1 < n ? f1 : n;
+    for (unsigned long long k = (f0 ? f0 - 1 : 0ull) + (unsigned)lane; k < k1; k += WAVE) {
+        const pfac_record r = sel[k];
+        const bool own = k >= f0;                                   // else the pick in front of the tile's first
+        const unsigned long long p = r.pos;
+        const int L = r.state < num_final ? (int)flen[r.state] : 0;
+        if (own) {
+            unsigned long long prev = 0ull;
+            if (k > 0) {
+                const pfac_record q = sel[k - 1];
+                const int Lq = q.state < num_final ? (int)flen[q.state] : 0;
+                prev = (unsigned long long)q.pos + (unsigned long long)(Lq > 0 ? Lq : 0);
+            }
+            bad |= r.state >= num_final || L < 1 || p < tile_lo || p >= own_hi || p < prev;
+            if (k + 1 == n) res[2] = p + (unsigned long long)(L > 0 ? L : 0);       // c_{n-1}
+        }
+        const unsigned long long a = p > tile_lo ? p : tile_lo;
+        const unsigned long long e = p + (unsigned long long)(L > 0 ? L : 0);
+        const unsigned long long b = e < tile_hi ? e : tile_hi;
+        if (a < b) {                                                // at most 17 words: patterns are shorter than HALO_MAX
+            const unsigned la = (unsigned)(a - tile_lo), lb = (unsigned)(b - tile_lo) - 1u;
+            for (unsigned x = la >> 6; x <= lb >> 6; x++) {
+                unsigned long long m = ~0ull;
+                if (x == la >> 6) m &= ~tk_below(la & 63u);
+                if (x == lb >> 6 && (lb & 63u) != 63u) m &= tk_below((lb & 63u) + 1u);
+                atomicOr(&s_cov[x], m);
+            }
+            if (own && r.state < num_final && p >= tile_lo && p < own_hi) {
+                const unsigned lp = (unsigned)(p - tile_lo);
+                const bool cont = lp ? (s_w[(lp - 1u) >> 6] >> ((lp - 1u) & 63u) & 1ull) != 0ull : cont0;
+                const int2 pr = ids[r.state];
+                if ((cont ? pr.y : pr.x) >= 0) atomicOr(&s_start[lp >> 6], 1ull << (lp & 63u));
+            }
+        }
+    }
+    if (__ballot(bad) && lane == 0) atomicOr(&res[1], 1ull);
+    wave_lds_sync();
+    const unsigned long long W = s_w[lane], cov = s_cov[lane], U = W & ~cov;
+    unsigned long long *m = maps + t * (WP_MAPS * TK_WORDS);
+    m[lane] = W;
+    m[TK_WORDS + lane] = U;
+    m[2 * TK_WORDS + lane] = s_start[lane] & W;
+    m[3 * TK_WORDS + lane] = s_e0[lane] & ~cov;
+    const unsigned long long open = __ballot(W != ~0ull);          // the words that end a run
+    unsigned lead = WTILE, trail = WTILE;
+    if (open) {
+        const int x0 = __builtin_ctzll(open), x1 = 63 - __builtin_clzll(open);
+        const unsigned long long w0 = __shfl(W, x0, WAVE), w1 = __shfl(W, x1, WAVE);
+        lead = (unsigned)x0 * 64u + (unsigned)__builtin_ctzll(~w0);
+        trail = (unsigned)(63 - x1) * 64u + (unsigned)__builtin_clzll(~w1);
+    }
+    const bool lbad = __ballot((U & wp_range((unsigned)lane, 0u, lead)) != 0ull) != 0ull;
+    const bool tbad = __ballot((U & wp_range((unsigned)lane, WTILE - trail, WTILE)) != 0ull) != 0ull;
+    if (lane == 0)
+        sum[t] = (unsigned long long)(lead | (lbad ? WP_BAD : 0u)) | (unsigned long long)(trail | (tbad ? WP_BAD : 0u)) << 16;
+}
+
+__global__ void __launch_bounds__(TK_WAVES * WAVE)
+pfac_wp_count_kernel(const unsigned long long *maps, const unsigned long long *sum, unsigned long long n_tiles, unsigned max_word,
+                     unsigned long long *bm, unsigned long long *unk, unsigned short *wpre, unsigned *tpre,
+                     unsigned long long *gsum) {
+    __shared__ unsigned s_cnt[TK_GROUP];
+    const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x >> 6;
+    const unsigned K = max_word + 1u;                               // so many word bits in a row make a word too long
+    for (int i = 0; i < TK_GROUP / TK_WAVES; i++) {
+        const unsigned lt = (unsigned)i * TK_WAVES + (unsigned)w;
+        const unsigned long long t = (unsigned long long)blockIdx.x * TK_GROUP + lt;
+        if (t >= n_tiles) {                                         // (wave-uniform)
+            if (lane == 0) s_cnt[lt] = 0u;
+            continue;
+        }
+        const unsigned long long *m = maps + t * (WP_MAPS * TK_WORDS);
+        const unsigned long long W = m[lane], U = m[TK_WORDS + lane], ST = m[2 * TK_WORDS + lane], E0 = m[3 * TK_WORDS + lane];
+        const unsigned sm = (unsigned)sum[t], prev = t ? (unsigned)sum[t - 1] : 0u, next = t + 1 < n_tiles ? (unsigned)sum[t + 1] : 0u;
+        const unsigned lead = sm & WP_LEN, trail = sm >> 16 & WP_LEN;
+        const unsigned ptrail = prev >> 16 & WP_LEN, nlead = next & WP_LEN;
+        // a run on a tile edge that goes on in the neighbour: what the neighbour's part adds to the verdict
+        const bool seed_lo = lead && ptrail && (lead == WTILE || ptrail == WTILE || lead + ptrail > max_word || (prev >> 16 & WP_BAD));
+        const bool seed_hi = trail && nlead && (trail == WTILE || nlead == WTILE || trail + nlead > max_word || (next & WP_BAD));
+        // word bits in a row up to and including bit 63 of every word; cin = those that reach this word's bit 0
+        const bool full = W == ~0ull;
+        const unsigned lowrun = full ? 64u : (unsigned)__builtin_ctzll(~W);
+        unsigned v = full ? 64u : (unsigned)__builtin_clzll(~W);
+        unsigned f = full ? 0u : 1u;
+#pragma unroll
+        for (int d = 1; d < WAVE; d <<= 1) {
+            const unsigned pv = __shfl_up(v, d, WAVE), pf = __shfl_up(f, d, WAVE);
+            if (lane >= d && !f) {
+                v += pv;
+                f = pf;
+            }
+        }
+        unsigned cin = __shfl_up(v, 1, WAVE);
+        if (lane == 0) cin = 0u;
+        unsigned long long S = U;
+        if (cin + lowrun > max_word) S |= wp_range(0u, max_word > cin ? max_word - cin : 0u, lowrun);
+        if (K <= 64u) {                                             // (uniform) runs of K inside the word
+            unsigned long long acc = ~0ull, pw = W;
+            unsigned am = 0u;
+            for (unsigned bit = 0; bit < 7u; bit++) {
+                if (K >> bit & 1u) {
+                    acc &= pw << am;
+                    am += 1u << bit;
+                }
+                if (bit < 6u) pw &= pw << (1u << bit);
+            }
+            S |= acc;
+        }
+        if (seed_lo && lane == 0) S |= 1ull;
+        if (seed_hi && lane == WAVE - 1) S |= 1ull << 63;
+        S &= W;
+        unsigned long long up = wp_fill_up(S, W), dn = wp_fill_down(S, W);
+        const unsigned long long P = __ballot(full);
+        const unsigned long long cu = wp_fill_up(__ballot(up >> 63 != 0ull) << 1, P << 1);
+        const unsigned long long cd = wp_fill_down(__ballot((dn & 1ull) != 0ull) >> 1, P >> 1);
+        if (cu >> lane & 1ull) up |= W & ~(W + 1ull);               // the carry from below floods the run at bit 0
+        if (cd >> lane & 1ull) dn |= full ? ~0ull : ~(~0ull >> __builtin_clzll(~W));   // ... from above, the run at bit 63
+        const unsigned long long bad = up | dn;
+        unsigned top = (unsigned)(W >> 63);
+        top = __shfl_up(top, 1, WAVE);
+        if (lane == 0) top = ptrail ? 1u : 0u;
+        const unsigned long long ws_ = W & ~(W << 1 | (unsigned long long)top);
+        const unsigned long long uk = ws_ & bad;
+        const unsigned long long word = E0 | uk | (ST & ~bad);
+        const unsigned c = (unsigned)__popcll(word), incl = wave_incl_scan(c);
+        bm[t * TK_WORDS + (unsigned)lane] = word;
+        unk[t * TK_WORDS + (unsigned)lane] = uk;
+        wpre[t * TK_WORDS + (unsigned)lane] = (unsigned short)(incl - c);
+        if (lane == WAVE - 1) s_cnt[lt] = incl;
+    }
+    __syncthreads();
+    if (w == 0) {
+        const unsigned long long t = (unsigned long long)blockIdx.x * TK_GROUP + (unsigned)lane;
+        const unsigned c = s_cnt[lane], incl = wave_incl_scan(c);
+        if (t < n_tiles) tpre[t] = incl - c;
+        if (lane == WAVE - 1) gsum[blockIdx.x] = incl;
+    }
+}
+
+template <bool POS>
+__global__ void __launch_bounds__(WAVE)
+pfac_wp_write_kernel(const unsigned char *in, unsigned long long n_avail, const pfac_record *sel, unsigned num_final,
+                     const int2 *pids, const int *btok, int unk_id, WordSet ws, const unsigned long long *first,
+                     const unsigned long long *maps, const unsigned long long *bm, const unsigned long long *unk,
+                     const unsigned short *wpre, const unsigned *tpre, const unsigned long long *gpre, int *ids, unsigned *pos) {
+    __shared__ int s_btok[256];
+    __shared__ unsigned long long s_bm[TK_WORDS], s_unk[TK_WORDS], s_w[TK_WORDS];
+    __shared__ unsigned short s_pre[TK_WORDS];
+    __shared__ __attribute__((aligned(16))) int s_ids[TK_STAGE];
+    __shared__ __attribute__((aligned(16))) unsigned s_pos[POS ? TK_STAGE : 4];
+    const int lane = threadIdx.x;
+    const unsigned long long t = blockIdx.x;
+    const unsigned long long word = bm[t * TK_WORDS + (unsigned)lane];
+    const unsigned wp = wpre[t * TK_WORDS + (unsigned)lane];
+    const unsigned cnt = bcast_last(wp + (unsigned)__popcll(word));
+    if (cnt == 0) return;                                           // (wave-uniform)
+    const unsigned long long base = gpre[t / TK_GROUP] + tpre[t];
+    const unsigned a = (unsigned)(base & 3ull);
+    const unsigned long long tile_lo = t * WTILE;
+    s_bm[lane] = word;
+    s_unk[lane] = unk[t * TK_WORDS + (unsigned)lane];
+    s_w[lane] = maps[t * (WP_MAPS * TK_WORDS) + (unsigned)lane];
+    s_pre[lane] = (unsigned short)wp;
+#pragma unroll
+    for (int i = 0; i < 4; i++) s_btok[i * WAVE + lane] = btok[i * WAVE + lane];
+    wave_lds_sync();
+#pragma unroll
+    for (int j = 0; j < SUBS; j++) {                                // the byte and [UNK] tokens, in rank order
+        const unsigned lp = (unsigned)j * SUB + (unsigned)lane * 16u, sh = lp & 63u;
+        const unsigned long long wv = s_bm[lp >> 6];
+        unsigned e = (unsigned)(wv >> sh) & 0xffffu;
+        if (!e) continue;
+        const unsigned u = (unsigned)(s_unk[lp >> 6] >> sh) & 0xffffu;
+        unsigned rank = a + s_pre[lp >> 6] + (unsigned)__popcll(wv & tk_below(sh));
+        const uint4 v = tk_load16(in, tile_lo + lp, n_avail);
+        const unsigned q[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int c = 0; c < 16; c++) {
+            if (e >> c & 1u) {
+                s_ids[rank] = (u >> c & 1u) ? unk_id : s_btok[(q[c >> 2] >> (8 * (c & 3))) & 255u];
+                if constexpr (POS) s_pos[rank] = (unsigned)(tile_lo + lp + (unsigned)c);
+                rank++;
+            }
+        }
+    }
+    wave_lds_sync();
+    const bool cont0 = t > 0 && word_byte(ws, (int)in[tile_lo - 1]);
+    const unsigned long long f1 = first[t + 1];
+    for (unsigned long long k = first[t] + (unsigned)lane; k < f1; k += WAVE) {     // the kept picks of good words
+        const pfac_record r = sel[k];
+        const unsigned lp = (r.pos - (unsigned)tile_lo) & (WTILE - 1u);
+        const unsigned long long wv = s_bm[lp >> 6];
+        if (r.state < num_final && (wv >> (lp & 63u) & 1ull) && !(s_unk[lp >> 6] >> (lp & 63u) & 1ull)) {
+            const bool cont = lp ? (s_w[(lp - 1u) >> 6] >> ((lp - 1u) & 63u) & 1ull) != 0ull : cont0;
+            const int2 pr = pids[r.state];
+            const int v = cont ? pr.y : pr.x;
+            if (v >= 0) {
+                const unsigned rank = a + s_pre[lp >> 6] + (unsigned)__popcll(wv & tk_below(lp & 63u));
+                s_ids[rank] = v;
+                if constexpr (POS) s_pos[rank] = (unsigned)tile_lo + lp;
+            }
+        }
+    }
+    wave_lds_sync();
+    const unsigned long long g0 = base - a;                         // a multiple of 4: ids + g0 is 16-B aligned
+    for (unsigned c = (unsigned)lane; c * 4u < a + cnt; c += WAVE) {
+        const unsigned s0 = c * 4u;
+        if (s0 >= a && s0 + 4u <= a + cnt) {
+            *reinterpret_cast<uint4 *>(ids + g0 + s0) = *reinterpret_cast<const uint4 *>(&s_ids[s0]);
+            if constexpr (POS) *reinterpret_cast<uint4 *>(pos + g0 + s0) = *reinterpret_cast<const uint4 *>(&s_pos[s0]);
+        } else {
+            for (unsigned x = s0; x < s0 + 4u; x++) {
+                if (x >= a && x < a + cnt) {
+                    ids[g0 + x] = s_ids[x];
+                    if constexpr (POS) pos[g0 + x] = s_pos[x];
+                }
+            }
+        }
+    }
+}
+
+// every document offset on a word boundary (two byte loads per offset, both below n_owned); else bit 1 of *err
+__global__ void pfac_wp_docs_kernel(const unsigned long long *off, unsigned long long n_docs, unsigned long long n_owned,
+                                    const unsigned char *in, WordSet ws, unsigned long long *err) {
+    const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
+    bool bad = false;
+    for (unsigned long long d = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; d <= n_docs; d += stride) {
+        const unsigned long long o = off[d];
+        if (o > 0 && o < n_owned) bad |= word_byte(ws, (int)in[o - 1]) && word_byte(ws, (int)in[o]);
+    }
+    if (bad) atomicOr(err, 2ull);
+}
+
+// ---------------------------------------------------------------------------
 // Proximity rules (pfac_documents_near): bit r of mask[d] is set iff document d holds two distinct records i < j, at
 // most max_dist bytes apart by their starts, that are an (A_r, B_r) pair -- in either order unless the rule is ordered.
 // With a maximum distance only, the nearest earlier A (or B) is the best partner a record can have, so the pass needs
@@ -5855,6 +6240,13 @@ struct Slot {
     PassOut<int> tk_ids;                  // the token ids, ...
     PassOut<unsigned> tk_pos;             // ... their positions (PFAC_TOKENS_POSITIONS), ...
     PassOut<unsigned long long> tk_off;   // ... and the documents' token offsets (n_docs + 1 entries)
+    // pfac_records_filter_roles / pfac_wordpiece_leftmost_longest / pfac_wordpiece_documents (first, bm, wpre, tpre and
+    // the three outputs are the tokenizer's)
+    bool rf_done = false;                 // the slot's last scan went through the role filter, ...
+    uint64_t rf_gen = 0;                  // ... under this attachment (pfac_ctx::wp_gen)
+    DevBuf<unsigned long long> wp_maps;   // per tile: W, U, ST, E0 (4 x 64 words), ...
+    DevBuf<unsigned long long> wp_sum;    // ... its edge summary, ...
+    DevBuf<unsigned long long> wp_unk;    // ... and its 64 words of [UNK] positions
 };
 
 struct StageLayout {                      // per-wave LDS of one staging mode
@@ -5928,6 +6320,12 @@ struct pfac_ctx {
     DevBuf<uint4> spans;                  // span of every final state (pfac_table_set_state_spans): pfac_state_span as one dwordx4
     DevBuf<int> tok;                      // token id of every final state (pfac_table_set_token_ids), PFAC_TOKEN_DROP = none, ...
     DevBuf<int> btok;                     // ... and of every byte value (256 entries; all DROP when the caller gave none)
+    DevBuf<int2> wp_ids;                  // WordPiece (pfac_table_set_wordpiece): (first id, continuation id) of every final state, ...
+    DevBuf<int> wp_btok;                  // ... the id of every byte value, ...
+    int wp_unk = 0;                       // ... the id of a bad word, ...
+    unsigned wp_max = 0;                  // ... the longest good word in bytes, ...
+    WordSet wp_ws{};                      // ... and the word bytes
+    uint64_t wp_gen = 0;                  // attachments made so far: a role filter remembers the one it ran under
     DevBuf<unsigned> ru_sptr;             // the rule table, state-major (pfac_table_set_rules): state_ptr[num_final + 1], ...
     DevBuf<unsigned> ru_ent;              // ... the entries rule << 1 | negated, the rules ascending inside a state, ...
     DevBuf<unsigned> ru_need;             // ... and need[n_rules]
@@ -6514,6 +6912,7 @@ int install_table(pfac_ctx *ctx, const int *d_blob, const int32_t *hdr, size_t n
     ctx->sweight.reset();                                   // ... and the state weights
     ctx->spans.reset();                                     // ... and the state spans
     ctx->tok.reset(); ctx->btok.reset();                    // ... and the token ids
+    ctx->wp_ids.reset(); ctx->wp_btok.reset();              // ... and the WordPiece ids
     ctx->ru_sptr.reset(); ctx->ru_ent.reset(); ctx->ru_need.reset(); ctx->ru_n = ctx->ru_terms = 0;     // ... and the rules
     ctx->have_table = false; ctx->table_gen++;
     TablePlan P;
@@ -6753,6 +7152,7 @@ int pfac_scan_async(pfac_ctx *ctx, int slot, const void *d_input, uint64_t n_own
     s.last_owned = n_owned;
     s.last_avail = n_avail;
     s.scan_seq++;
+    s.rf_done = false;
     s.last_table = ctx->table_gen;
     s.last_rec_bytes = (int)P.base.rec_bytes;
     s.last_records = d_records;
@@ -9175,6 +9575,232 @@ int pfac_tokens_offsets_d2h(pfac_ctx *ctx, int slot, uint64_t *host_tok_off) {
     if (rc) return rc;
     Slot &s = ctx->slots[slot];
     return fetch(ctx, s, s.tk_off, "pfac_tokens_offsets_d2h", "pfac_tokenize_documents", host_tok_off, 0, s.tk_off.n);
+}
+
+// The WordPiece attachment: checked whole, made aside, swapped in together, as the token ids are; it leaves them alone.
+int pfac_table_set_wordpiece(pfac_ctx *ctx, const int32_t *first_ids, const int32_t *cont_ids, uint64_t n_states,
+                             const int32_t *byte_ids, int32_t unk_id, const uint64_t word_set[4], uint32_t max_word_bytes) {
+    if (!ctx) return fail(nullptr, PFAC_E_ARG, "null context");
+    const std::string fn = "pfac_table_set_wordpiece";
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (!ctx->have_table) return fail(ctx, PFAC_E_STATE, fn + " before a table upload");
+    if (n_states != (uint64_t)ctx->plan.base.num_final || ((!first_ids || !cont_ids) && n_states))
+        return fail(ctx, PFAC_E_ARG, fn + ": need num_final first and continuation ids (num_final " + std::to_string(ctx->plan.base.num_final) + ")");
+    std::vector<int2> pairs(std::max<uint64_t>(n_states, 1), make_int2(PFAC_TOKEN_DROP, PFAC_TOKEN_DROP));
+    for (uint64_t i = 0; i < n_states; i++) {
+        if (first_ids[i] < PFAC_TOKEN_DROP || cont_ids[i] < PFAC_TOKEN_DROP)
+            return fail(ctx, PFAC_E_ARG, fn + ": an id of final state " + std::to_string(i) + " is neither >= 0 nor PFAC_TOKEN_DROP");
+        pairs[i] = make_int2(first_ids[i], cont_ids[i]);
+    }
+    int32_t bytes[256];
+    for (int b = 0; b < 256; b++) {
+        bytes[b] = byte_ids ? byte_ids[b] : PFAC_TOKEN_DROP;
+        if (bytes[b] < PFAC_TOKEN_DROP)
+            return fail(ctx, PFAC_E_ARG, fn + ": the id of byte " + std::to_string(b) + " is neither >= 0 nor PFAC_TOKEN_DROP");
+    }
+    if (unk_id < 0) return fail(ctx, PFAC_E_ARG, fn + ": unk_id must be >= 0");
+    if (max_word_bytes < 1 || max_word_bytes > 4095) return fail(ctx, PFAC_E_ARG, fn + ": max_word_bytes must lie in 1..4095");
+    USE_DEVICE(ctx);
+    DevBuf<int2> ids;
+    DevBuf<int> btok;
+    int rc = ids.ensure(ctx, nullptr, pairs.size(), pairs.size());
+    if (!rc) rc = btok.ensure(ctx, nullptr, 256, 256);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpy(ids.p, pairs.data(), pairs.size() * sizeof(int2), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(btok.p, bytes, sizeof bytes, hipMemcpyHostToDevice));
+    ctx->wp_ids = std::move(ids);                           // (a swap: the old buffers go with the two locals)
+    ctx->wp_btok = std::move(btok);
+    ctx->wp_unk = unk_id;
+    ctx->wp_max = max_word_bytes;
+    for (int k = 0; k < 4; k++)                              // NULL: [0-9A-Za-z_]
+        ctx->wp_ws.w[k] = word_set ? word_set[k] : (k == 0 ? 0x03FF000000000000ull : (k == 1 ? 0x07FFFFFE87FFFFFEull : 0ull));
+    ctx->wp_gen++;
+    return PFAC_OK;
+}
+
+int pfac_records_filter_roles(pfac_ctx *ctx, int slot, const void *d_input, void *d_records, uint64_t *n_kept) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    if (!n_kept) return fail(ctx, PFAC_E_ARG, "null argument");
+    *n_kept = 0;
+    Slot &s = ctx->slots[slot];
+    const std::string fn = "pfac_records_filter_roles";
+    rc = last_scan_usable(ctx, s, fn, SCAN_FINISHED | SCAN_LENGTHS | SCAN_TABLE);
+    if (rc) return rc;
+    if (!ctx->wp_ids.p) return fail(ctx, PFAC_E_STATE, fn + ": no WordPiece ids for the uploaded table (pfac_table_set_wordpiece)");
+    rc = last_scan_usable(ctx, s, fn, SCAN_FITS);
+    if (rc) return rc;
+    void *heap = d_records ? d_records : (void *)s.records.p;
+    if (heap != s.last_records) return fail(ctx, PFAC_E_ARG, fn + ": d_records is not the record heap of the slot's last scan");
+    const unsigned char *in = d_input ? static_cast<const unsigned char *>(d_input) : s.input.p;
+    if ((uintptr_t)in & 15) return fail(ctx, PFAC_E_ARG, fn + ": d_input must be 16-byte aligned");
+    if (!d_input && s.last_avail > s.input.cap) return fail(ctx, PFAC_E_ARG, fn + ": the scan read more than the slot's input buffer holds");
+    if (!in && s.last_total) return fail(ctx, PFAC_E_ARG, fn + ": no input buffer");
+    USE_DEVICE(ctx);
+    const uint64_t n_tiles = s.last_tiles;
+    const unsigned n_groups = (unsigned)((n_tiles + XGROUP - 1) / XGROUP);
+    rc = ensure_gsum(ctx, s, 1);                            // the kept total
+    if (rc) return rc;
+    unsigned long long *res = s.gsum.p;
+    HIP_TRY(ctx, hipMemsetAsync(res, 0, 8, s.stream));
+    if (n_groups) {
+        auto fk = by_width(s.last_rec_bytes, [](auto w) { return pfac_filter_roles_kernel<w()>; });
+        hipLaunchKernelGGL(fk, dim3((n_groups + 3) / 4), dim3(256), 0, s.stream, heap, s.tile_index.p, (unsigned long long)n_tiles,
+                           (unsigned long long)s.last_cap, in, (unsigned long long)s.last_avail, (const int2 *)ctx->wp_ids.p,
+                           (unsigned)ctx->plan.base.num_final, ctx->wp_ws, res);
+    }
+    rc = pass_words(ctx, s, res, 1);
+    if (rc) return rc;
+    // as after the whole-word filter: the kept records ARE the scan's records from here on
+    const uint64_t total = host_u64(s, H_PASS);
+    s.last_total = total;
+    s.h_ctl[H_MATCHES] = (unsigned)total;
+    s.h_ctl[H_MATCHES + 1] = (unsigned)(total >> 32);
+    s.scan_seq++;
+    s.rf_done = true;
+    s.rf_gen = ctx->wp_gen;
+    *n_kept = total;
+    return PFAC_OK;
+}
+
+// tk_run's sibling: the same ladder and outputs, the WordPiece kernels between them
+static int wp_run(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *d_input, const pfac_record *d_sel, uint32_t flags,
+                  int32_t *d_ids, uint64_t out_cap, uint32_t *d_pos, uint64_t *n_tokens, const TkDocs *docs) {
+    s.tk_ids.invalidate();
+    s.tk_pos.invalidate();
+    s.tk_off.invalidate();
+    if (!s.scanned || !s.ll_out.done || s.ll_seq != s.scan_seq || (docs && !s.ll_docs))
+        return fail(ctx, PFAC_E_STATE, fn + (docs ? " needs a pfac_records_leftmost_longest_documents since the slot's last scan"
+                                                  : " needs a pfac_records_leftmost_longest since the slot's last scan"));
+    if (!ctx->have_table || s.last_table != ctx->table_gen)
+        return fail(ctx, PFAC_E_STATE, fn + ": the selection was made with an earlier table");
+    if (!ctx->wp_ids.p) return fail(ctx, PFAC_E_STATE, fn + ": no WordPiece ids for the uploaded table (pfac_table_set_wordpiece)");
+    if (!ctx->flen.p) return fail(ctx, PFAC_E_STATE, fn + ": no final-state lengths for the uploaded table");
+    if (!s.rf_done || s.rf_gen != ctx->wp_gen)
+        return fail(ctx, PFAC_E_STATE, fn + ": the scan has not been through pfac_records_filter_roles under the current WordPiece ids");
+    if (s.ll_entry != 0) return fail(ctx, PFAC_E_STATE, fn + ": the selection was made from an entry other than 0 (chained ranges are out of scope)");
+    const pfac_record *sel;
+    int rc = s.ll_out.consume(ctx, fn, "selection (d_sel)", d_sel, ANY_N, &sel);
+    if (rc) return rc;
+    const bool want_pos = flags & PFAC_TOKENS_POSITIONS;
+    if (flags & ~PFAC_TOKENS_POSITIONS) return fail(ctx, PFAC_E_ARG, fn + ": unknown flags");
+    if (d_pos && !want_pos) return fail(ctx, PFAC_E_ARG, fn + ": d_pos without PFAC_TOKENS_POSITIONS");
+    const unsigned char *in = d_input ? static_cast<const unsigned char *>(d_input) : s.input.p;
+    const uint64_t n = s.ll_out.n, n_owned = s.last_owned, n_avail = s.last_avail, ex = s.ll_exit;
+    if (((uintptr_t)d_ids & 15) || ((uintptr_t)d_pos & 15) || ((uintptr_t)in & 15) || ((uintptr_t)d_sel & 7))
+        return fail(ctx, PFAC_E_ARG, fn + ": misaligned buffer (d_input, d_ids and d_pos 16 B, d_sel 8 B)");
+    if (n_owned && !in) return fail(ctx, PFAC_E_ARG, fn + ": no input buffer");
+    if (!d_input && n_avail > s.input.cap) return fail(ctx, PFAC_E_ARG, fn + ": the scan read more than the slot's input buffer holds");
+    const unsigned long long *doff = nullptr, *dfirst = nullptr;
+    unsigned long long *dtok_off = nullptr;
+    if (docs) {
+        doff = reinterpret_cast<const unsigned long long *>(docs->off);
+        dtok_off = reinterpret_cast<unsigned long long *>(docs->tok_off);
+        if (!doff) {
+            if (!s.lld_own_off) return fail(ctx, PFAC_E_STATE, fn + ": the selection cut the caller's document offsets; pass them as d_doc_offsets");
+            if (s.lld_gen != s.doc_gen || !s.doc.done) return fail(ctx, PFAC_E_STATE, fn + ": the slot's document offsets changed since the selection");
+            doff = s.doc.buf.p;
+        }
+        rc = s.lld_first.consume(ctx, fn, "doc_first of the selection (d_doc_first)", docs->first, ANY_N, &dfirst);
+        if (rc) return rc;
+        if (((uintptr_t)doff & 7) || ((uintptr_t)dfirst & 7) || ((uintptr_t)dtok_off & 7))
+            return fail(ctx, PFAC_E_ARG, fn + ": device buffers must be 8-byte aligned");
+    }
+    USE_DEVICE(ctx);
+    const uint64_t n_docs = docs ? s.lld_first.n - 1 : 0;
+    const uint64_t n_tiles = (n_owned + WTILE - 1) / WTILE, n_groups = (n_tiles + TK_GROUP - 1) / TK_GROUP;
+    const unsigned oblocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_docs + 1 + 255) / 256, 65536));
+    uint64_t nt = 0;
+    if (n_tiles) {
+        rc = s.tk_first.ensure(ctx, s.stream, n_tiles + 1, quarter_more(n_tiles + 1));
+        if (!rc) rc = s.tk_bm.ensure(ctx, s.stream, n_tiles * TK_WORDS, quarter_more(n_tiles) * TK_WORDS);
+        if (!rc) rc = s.tk_wpre.ensure(ctx, s.stream, n_tiles * TK_WORDS, quarter_more(n_tiles) * TK_WORDS);
+        if (!rc) rc = s.tk_tpre.ensure(ctx, s.stream, n_tiles, quarter_more(n_tiles));
+        if (!rc) rc = s.wp_maps.ensure(ctx, s.stream, n_tiles * WP_MAPS * TK_WORDS, quarter_more(n_tiles) * WP_MAPS * TK_WORDS);
+        if (!rc) rc = s.wp_sum.ensure(ctx, s.stream, n_tiles, quarter_more(n_tiles));
+        if (!rc) rc = s.wp_unk.ensure(ctx, s.stream, n_tiles * TK_WORDS, quarter_more(n_tiles) * TK_WORDS);
+        if (!rc) rc = ensure_gsum(ctx, s, (unsigned)n_groups + 2);      // group prefixes, the total, error flags, c_{n-1}
+        if (rc) return rc;
+        unsigned long long *res = s.gsum.p + n_groups;
+        HIP_TRY(ctx, hipMemsetAsync(res, 0, 24, s.stream));
+        hipLaunchKernelGGL(pfac_tk_first_kernel, dim3((unsigned)((n_tiles + 1 + 255) / 256)), dim3(256), 0, s.stream, sel,
+                           (unsigned long long)n, (unsigned long long)n_tiles, s.tk_first.p);
+        hipLaunchKernelGGL(pfac_wp_edge_kernel, dim3((unsigned)n_tiles), dim3(WAVE), 0, s.stream, in, (unsigned long long)n_avail, sel,
+                           (unsigned long long)n, (unsigned long long)n_owned, ctx->flen.p, (const int2 *)ctx->wp_ids.p,
+                           (const int *)ctx->wp_btok.p, (unsigned)ctx->plan.base.num_final, (const unsigned long long *)s.tk_first.p,
+                           ctx->wp_ws, s.wp_maps.p, s.wp_sum.p, res);
+        hipLaunchKernelGGL(pfac_wp_count_kernel, dim3((unsigned)n_groups), dim3(TK_WAVES * WAVE), 0, s.stream,
+                           (const unsigned long long *)s.wp_maps.p, (const unsigned long long *)s.wp_sum.p, (unsigned long long)n_tiles,
+                           ctx->wp_max, s.tk_bm.p, s.wp_unk.p, s.tk_wpre.p, s.tk_tpre.p, s.gsum.p);
+        hipLaunchKernelGGL(pfac_scan_groups_kernel, dim3(1), dim3(1024), 0, s.stream, s.gsum.p, (unsigned)n_groups);
+        if (docs)
+            hipLaunchKernelGGL(pfac_wp_docs_kernel, dim3(oblocks), dim3(256), 0, s.stream, doff, (unsigned long long)n_docs,
+                               (unsigned long long)n_owned, in, ctx->wp_ws, res + 1);
+        rc = pass_words(ctx, s, res, 3);
+        if (rc) return rc;
+        nt = host_u64(s, H_PASS);
+        const uint64_t err = host_u64(s, H_PASS1), c_last = host_u64(s, H_PASS2);
+        if ((err & 1) || (n && (c_last > n_owned ? c_last - n_owned : 0) != ex))
+            return fail(ctx, PFAC_E_ARG, fn + ": the selection is not one of this scan and table");
+        if (err & 2) return fail(ctx, PFAC_E_ARG, fn + ": a document offset lies inside a word");
+    } else if (n) {
+        return fail(ctx, PFAC_E_ARG, fn + ": the selection is not one of this scan and table");
+    }
+    *n_tokens = nt;
+    if ((d_ids || d_pos) && nt > out_cap)
+        return fail(ctx, PFAC_E_OVERFLOW, fn + ": " + std::to_string(nt) + " tokens, out_cap is " + std::to_string(out_cap));
+    const uint64_t cap = align_up(nt + nt / 8, 1024);
+    int *ids = nullptr;
+    unsigned *pos = nullptr;
+    unsigned long long *toff = nullptr;
+    rc = s.tk_ids.bind(ctx, s.stream, d_ids, nt, cap, &ids);       // (everything allocated before the first write)
+    if (!rc && want_pos) rc = s.tk_pos.bind(ctx, s.stream, d_pos, nt, cap, &pos);
+    if (!rc && docs) rc = s.tk_off.bind(ctx, s.stream, dtok_off, n_docs + 1, docs_cap(n_docs), &toff);
+    if (rc) return rc;
+    if (nt) {
+        auto wk = want_pos ? pfac_wp_write_kernel<true> : pfac_wp_write_kernel<false>;
+        hipLaunchKernelGGL(wk, dim3((unsigned)n_tiles), dim3(WAVE), 0, s.stream, in, (unsigned long long)n_avail, sel,
+                           (unsigned)ctx->plan.base.num_final, (const int2 *)ctx->wp_ids.p, (const int *)ctx->wp_btok.p, ctx->wp_unk,
+                           ctx->wp_ws, (const unsigned long long *)s.tk_first.p, (const unsigned long long *)s.wp_maps.p,
+                           (const unsigned long long *)s.tk_bm.p, (const unsigned long long *)s.wp_unk.p,
+                           (const unsigned short *)s.tk_wpre.p, (const unsigned *)s.tk_tpre.p, (const unsigned long long *)s.gsum.p,
+                           ids, pos);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    if (docs) {
+        if (n_tiles) {
+            hipLaunchKernelGGL(pfac_tk_doc_kernel, dim3(oblocks), dim3(256), 0, s.stream, doff, (unsigned long long)n_docs,
+                               (unsigned long long)n_owned, (unsigned long long)n_tiles, (unsigned)n_groups, s.tk_bm.p,
+                               s.tk_wpre.p, s.tk_tpre.p, s.gsum.p, toff);
+            HIP_TRY(ctx, hipGetLastError());
+        } else {
+            HIP_TRY(ctx, hipMemsetAsync(toff, 0, (n_docs + 1) * 8, s.stream));
+        }
+        s.tk_off.commit(n_docs + 1, !dtok_off);
+    }
+    if (want_pos) s.tk_pos.commit(nt, !d_pos);
+    s.tk_ids.commit(nt, !d_ids);
+    return PFAC_OK;
+}
+
+int pfac_wordpiece_leftmost_longest(pfac_ctx *ctx, int slot, const void *d_input, const pfac_record *d_sel, uint32_t flags,
+                                    int32_t *d_ids, uint64_t out_cap, uint32_t *d_pos, uint64_t *n_tokens) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    if (!n_tokens) return fail(ctx, PFAC_E_ARG, "null argument");
+    *n_tokens = 0;
+    return wp_run(ctx, ctx->slots[slot], "pfac_wordpiece_leftmost_longest", d_input, d_sel, flags, d_ids, out_cap, d_pos, n_tokens, nullptr);
+}
+
+int pfac_wordpiece_documents(pfac_ctx *ctx, int slot, const void *d_input, const pfac_record *d_sel, const uint64_t *d_doc_offsets,
+                             const uint64_t *d_doc_first, uint32_t flags, int32_t *d_ids, uint64_t out_cap, uint32_t *d_pos,
+                             uint64_t *d_tok_offsets, uint64_t *n_tokens) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    if (!n_tokens) return fail(ctx, PFAC_E_ARG, "null argument");
+    *n_tokens = 0;
+    const TkDocs docs{d_doc_offsets, d_doc_first, d_tok_offsets};
+    return wp_run(ctx, ctx->slots[slot], "pfac_wordpiece_documents", d_input, d_sel, flags, d_ids, out_cap, d_pos, n_tokens, &docs);
 }
 
 int pfac_fill_tiled(pfac_ctx *ctx, int slot, void *d_dst, uint64_t n, const void *host_pattern, uint32_t period, uint64_t phase) {

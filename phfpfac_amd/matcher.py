@@ -22,7 +22,7 @@ from ._ffi import PFAC_TERMS_SELECTION
 from ._ffi import PFAC_TOKENS_POSITIONS
 from ._ffi import PFAC_NEAR_SELECTION
 from ._ffi import PFAC_E_STATE
-from .table import NEAR_RULE_DTYPE, RECORD_DTYPE,SCORE_DTYPE, TEMPLATE_PLAIN, TOKEN_DROP, PfacTable, redaction_table, replacement_table, template_table, token_table, _state_lengths
+from .table import NEAR_RULE_DTYPE, RECORD_DTYPE,SCORE_DTYPE, TEMPLATE_PLAIN, TOKEN_DROP, WORD_BYTES, PfacTable, redaction_table, replacement_table, template_table, token_table, _state_lengths
 
 
 def device_count() -> int:
@@ -1559,6 +1559,119 @@ class GpuMatcher:
         dictionary words on word boundaries become vocabulary tokens (the pre-tokenized MaxMatch)."""
         _, n_docs = self._scan_lines(data, delimiter, slot, whole_words, fetch_offsets=False, spans=spans, line_match=line_match)
         return self._tokenize_docs(None, n_docs, positions, slot)
+
+    # -- WordPiece: ## continuation pieces and one [UNK] per word -------------
+    def set_wordpiece(self, first_ids, cont_ids, byte_ids=None, unk_id: int = 0, word_bytes=None, max_word_bytes: int = 100) -> None:
+        """The WordPiece ids of the uploaded table (``pfac_table_set_wordpiece``), as ``wordpiece_table`` returns them:
+        ``first_ids`` / ``cont_ids`` int32[num_final], the id of a final state at a word's start / inside a word;
+        ``byte_ids`` 256 entries for the bytes outside words (None = all dropped); ``unk_id`` the id of a word that
+        cannot be tokenized; ``word_bytes`` the bytes that make up words (None = ``[0-9A-Za-z_]``, or a ``word_set``
+        array); ``max_word_bytes`` (1..4095) the longest word that is not ``unk_id`` by its length alone.  Kept on the
+        device until the next table upload; the ids of ``set_token_ids`` stay as they are."""
+        fi = np.ascontiguousarray(first_ids, dtype=np.int32).ravel()
+        ci = np.ascontiguousarray(cont_ids, dtype=np.int32).ravel()
+        if fi.size != ci.size:
+            raise ValueError("first_ids and cont_ids hold one entry per final state each")
+        bt = None
+        if byte_ids is not None:
+            bt = np.ascontiguousarray(byte_ids, dtype=np.int32).ravel()
+            if bt.shape != (256,):
+                raise ValueError("byte_ids holds 256 entries")
+        if word_bytes is None:
+            ws = None
+        elif isinstance(word_bytes, np.ndarray) and word_bytes.dtype == np.uint64:
+            ws = np.ascontiguousarray(word_bytes)
+            if ws.size != 4:
+                raise ValueError("a word set holds four 64-bit words")
+        else:
+            ws = word_set(word_bytes)
+        self._check(self._L.pfac_table_set_wordpiece(self._ctx, fi.ctypes.data if fi.size else None, ci.ctypes.data if ci.size else None,
+                                                     fi.size, bt.ctypes.data if bt is not None else None, int(unk_id),
+                                                     ws.ctypes.data if ws is not None else None, int(max_word_bytes)))
+        self._wp_words = word_set(WORD_BYTES) if ws is None else ws.copy()
+
+    def filter_roles(self, slot: int = 0, d_input=None, d_records=None) -> int:
+        """Drops, in place on the GPU, the records of the slot's last finished scan whose pattern is not in the half of
+        the WordPiece vocabulary that their position asks for (``pfac_records_filter_roles``): a record stays iff it
+        starts on a word byte and its state has an id for its place -- the first id at a word's start, the continuation
+        id behind another word byte.  Everything that reads the scan afterwards sees the kept records only.  Returns
+        their number, which ``last_count`` reports from then on."""
+        n = C.c_uint64(0)
+        self._check(self._L.pfac_records_filter_roles(self._ctx, slot, _ptr(d_input), _ptr(d_records), C.byref(n)))
+        self._last_n[slot] = n.value
+        return n.value
+
+    def wordpiece_selection(self, d_input=None, d_ids=None, out_cap: int = 0, d_pos=None, positions: bool = False,
+                            slot: int = 0, d_sel=None) -> int:
+        """The WordPiece ids of the slot's last ``select_leftmost_longest`` (entry 0) over a scan that went through
+        ``filter_roles`` (``pfac_wordpiece_leftmost_longest``).  Arguments, result and overflow as
+        ``tokenize_selection``; the slot-owned result is fetched with ``tokens_to_host``."""
+        n = C.c_uint64(0)
+        flags = PFAC_TOKENS_POSITIONS if (positions or d_pos is not None) else 0
+        rc = self._L.pfac_wordpiece_leftmost_longest(self._ctx, slot, _ptr(d_input), _ptr(d_sel), flags, _ptr(d_ids),
+                                                     int(out_cap), _ptr(d_pos), C.byref(n))
+        return self._counted(rc, n, "n_tokens")
+
+    def wordpiece_selection_documents(self, d_input=None, d_ids=None, out_cap: int = 0, d_pos=None, positions: bool = False,
+                                      d_tok_offsets=None, slot: int = 0, d_sel=None, d_doc_offsets=None, d_doc_first=None) -> int:
+        """``wordpiece_selection`` over the slot's last ``select_leftmost_longest_documents``, plus the documents' token
+        offsets (``pfac_wordpiece_documents``); arguments as ``tokenize_selection_documents``.  Every document offset
+        must be a word boundary (else PfacError, PFAC_E_ARG)."""
+        n = C.c_uint64(0)
+        flags = PFAC_TOKENS_POSITIONS if (positions or d_pos is not None) else 0
+        rc = self._L.pfac_wordpiece_documents(self._ctx, slot, _ptr(d_input), _ptr(d_sel), _ptr(d_doc_offsets), _ptr(d_doc_first),
+                                              flags, _ptr(d_ids), int(out_cap), _ptr(d_pos), _ptr(d_tok_offsets), C.byref(n))
+        return self._counted(rc, n, "n_tokens")
+
+    def wordpiece(self, data, n_owned: Optional[int] = None, positions: bool = False, slot: int = 0):
+        """H2D + scan + role filter + selection + WordPiece of one host buffer (``n_owned`` < len(data) leaves the rest
+        as halo; cut there at a byte outside words).  Returns (ids, exit), or (ids, pos, exit) with ``positions``, as
+        ``tokenize`` does."""
+        buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data.view(np.uint8).ravel()
+        n_avail = int(buf.size)
+        n_owned = n_avail if n_owned is None else int(n_owned)
+        self._ensure_final_lengths()
+        self.reserve(slot, max(n_avail, 1), max(n_avail // 8, 4096))
+        if n_avail:
+            self.h2d(buf, slot)
+        self.scan_resident(n_owned, n_avail, slot=slot)
+        self.filter_roles(slot)
+        _, ex = self.select_leftmost_longest(0, slot=slot)
+        n = self.wordpiece_selection(positions=positions, slot=slot)
+        out = self.tokens_to_host(n, positions, slot)
+        return (out[0], out[1], ex) if positions else (out, ex)
+
+    def _wordpiece_docs(self, offsets, n_docs: int, positions: bool, slot: int):
+        self.filter_roles(slot)
+        self.select_leftmost_longest_documents(n_docs, slot=slot)
+        n = self.wordpiece_selection_documents(positions=positions, slot=slot)
+        tok_off = self.token_offsets_to_host(n_docs, slot)
+        if not positions:
+            return self.tokens_to_host(n, False, slot), tok_off
+        ids, pos = self.tokens_to_host(n, True, slot)
+        if n:
+            if offsets is None:
+                offsets = self.doc_offsets_to_host(n_docs, slot)
+            doc = np.repeat(np.arange(n_docs, dtype=np.int64), np.diff(tok_off.astype(np.int64)))
+            pos -= offsets[doc].astype(np.uint32)
+        return ids, pos, tok_off
+
+    def wordpiece_documents(self, docs, positions: bool = False, slot: int = 0):
+        """WordPiece of a batch of documents (``docs`` as ``scan_documents`` takes it) in one scan.  No word may run
+        across a document end: two documents that meet between two word bytes raise PfacError (PFAC_E_ARG).  Returns
+        what ``tokenize_documents`` returns."""
+        offsets, n_docs = self._scan_docs(docs, slot)
+        return self._wordpiece_docs(offsets, n_docs, positions, slot)
+
+    def wordpiece_lines(self, data, delimiter=b"\n", positions: bool = False, slot: int = 0):
+        """``wordpiece_documents`` of one buffer cut into lines at ``delimiter`` on the device.  The delimiter must not
+        be a word byte (ValueError): a line then starts and ends on a word boundary by construction."""
+        d = _delimiter_byte(delimiter)
+        ws = getattr(self, "_wp_words", None)
+        if ws is not None and 0 <= d <= 255 and (int(ws[d >> 6]) >> (d & 63)) & 1:
+            raise ValueError("the delimiter is a word byte of the WordPiece attachment")
+        _, n_docs = self._scan_lines(data, delimiter, slot, fetch_offsets=False)
+        return self._wordpiece_docs(None, n_docs, positions, slot)
 
     # -- synthetic inputs (device resident) --------------------------------
     def fill_tiled(self, d_dst, n: int, pattern: bytes, phase: int = 0, slot: int = 0) -> None:

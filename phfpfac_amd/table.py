@@ -551,6 +551,61 @@ def token_table(table: "PfacTable", ids) -> np.ndarray:
     return out
 
 
+WORD_BYTES = b"0123456789ABCDEFGHIJKLMNOPQRSTUVWXYZ_abcdefghijklmnopqrstuvwxyz"    # the default word set of the filters
+
+
+def wordpiece_table(vocab, prefix: bytes = b"##", word_bytes=None, ignore_case: bool = False) -> tuple:
+    """A WordPiece vocabulary as ONE automaton with two ids per final state, for ``pfac_table_set_wordpiece``.
+    ``vocab`` is a sequence of entries (bytes or str; entry k has token id k, as in a BERT ``vocab.txt``) or the path of
+    such a file, one entry per line.  ``word_bytes``: the bytes that make up words (None = ``[0-9A-Za-z_]``).
+    Returns (table, first_ids int32[num_final], cont_ids int32[num_final], byte_ids int32[256], skipped):
+
+    - the patterns are the distinct stripped strings (``##ing`` is inserted as ``ing``) made of word bytes only, folded
+      under ``ignore_case``; a state's first id is the id of the plain entry, its continuation id that of the
+      ``prefix`` entry, TOKEN_DROP where the vocabulary has none;
+    - an entry of one non-word byte gives that byte's id in ``byte_ids`` (TOKEN_DROP elsewhere);
+    - ``skipped`` lists (id, entry) of everything the rule can never produce: ``[CLS]``, a ``##`` piece with a non-word
+      byte, an empty string, an entry that holds a newline, a pattern of 1024 bytes or more, and the later of two
+      entries that are the same piece.
+
+    The states take their ids as ``token_table`` maps them (``idmap[s]``)."""
+    if isinstance(vocab, (str, os.PathLike)):
+        with open(vocab, "rb") as f:
+            lines = f.read().split(b"\n")
+        if lines and lines[-1] == b"":
+            lines.pop()
+        entries = [e[:-1] if e.endswith(b"\r") else e for e in lines]
+    else:
+        entries = [e.encode() if isinstance(e, str) else bytes(e) for e in vocab]
+    prefix = bytes(prefix)
+    words = set(WORD_BYTES if word_bytes is None else bytes(word_bytes))
+    byte_ids = np.full(256, TOKEN_DROP, dtype=np.int32)
+    lines, ids, skipped = [], {}, []           # pattern lines in order; piece -> [first id, continuation id]
+    for k, e in enumerate(entries):
+        cont = len(prefix) > 0 and e.startswith(prefix) and len(e) > len(prefix)
+        piece = e[len(prefix):] if cont else e
+        if ignore_case:
+            piece = bytes(fold_ascii(piece)) if piece else piece
+        if piece and len(piece) < 1024 and b"\n" not in piece and all(b in words for b in piece):
+            pair = ids.get(piece)
+            if pair is None:
+                pair = ids[piece] = [TOKEN_DROP, TOKEN_DROP]
+                lines.append(piece)
+            if pair[cont] == TOKEN_DROP:
+                pair[cont] = k
+                continue
+        elif not cont and len(e) == 1 and e[0] not in words and e != b"\n" and byte_ids[e[0]] == TOKEN_DROP:
+            byte_ids[e[0]] = k
+            continue
+        skipped.append((k, e))
+    if not lines:
+        raise ValueError("the vocabulary holds no piece made of word bytes")
+    table = PfacTable.from_bytes(b"".join(p + b"\n" for p in lines), 256, ignore_case=ignore_case)
+    first = token_table(table, [ids[p][0] for p in lines])
+    cont = token_table(table, [ids[p][1] for p in lines])
+    return table, first, cont, byte_ids, skipped
+
+
 TEMPLATE_PLAIN = 0xFFFFFFFF          # PFAC_TEMPLATE_PLAIN: the state's replacement does not quote the match
 
 
