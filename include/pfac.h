@@ -1404,6 +1404,60 @@ int pfac_wordpiece_documents(pfac_ctx *ctx, int slot, const void *d_input, const
                              const uint64_t *d_doc_first, uint32_t flags, int32_t *d_ids, uint64_t out_cap, uint32_t *d_pos,
                              uint64_t *d_tok_offsets, uint64_t *n_tokens);
 
+/* Unigram (the SentencePiece family: T5, ALBERT, XLNet, mBART): every piece has a score, a word is cut into the
+ * pieces with the highest total, by Viterbi over the lattice of ALL vocabulary matches inside the word -- which is what
+ * the record heap of a scan holds, in (position, length) order.  The first token pass over the heap itself, not over a
+ * selection.  ONE automaton over the stripped strings, as for WordPiece (`▁the` is inserted as `the` and goes to the
+ * FIRST half of its state, a plain `the` to the CONT half).
+ * The attachment of the installed table: pieces[s], one 16-byte entry per final state (n_states == num_final); ids
+ * >= 0 or PFAC_TOKEN_DROP; byte_ids int32[256] (NULL = every byte DROP); byte_score, the score of a byte edge; unk_id
+ * >= 0 (a run of byte edges is one unk_id) or PFAC_TOKEN_DROP (byte fallback: every byte edge emits its byte id);
+ * word_set as for WordPiece, but NULL = every byte except \t \n \v \f \r and space (SentencePiece splits at
+ * whitespace); max_word_bytes in 1..4095.  Scores are integers, the caller's log-probabilities in fixed point; sums
+ * stay in int32: every score, byte_score included, must satisfy |score| * (max_word_bytes + 1) < 2^31.  PFAC_E_ARG for
+ * anything else, PFAC_E_STATE before an upload; everything is checked before anything changes.  A table upload drops
+ * the attachment; old buffers are freed behind queued work; a slot-owned result made under an earlier attachment is
+ * stale (PFAC_E_STATE from the fetches).  It touches neither the token ids nor the WordPiece attachment. */
+typedef struct pfac_unigram_piece { int32_t first_id, cont_id, first_score, cont_score; } pfac_unigram_piece;
+int pfac_table_set_unigram(pfac_ctx *ctx, const pfac_unigram_piece *pieces, uint64_t n_states, const int32_t *byte_ids,
+                           int32_t byte_score, int32_t unk_id, const uint64_t word_set[4], uint32_t max_word_bytes);
+/* THE RULE.  Over the slot's last finished scan: n_owned, n_avail, its input, and its records as they stand (filtered
+ * or not).  W is the word set, L_s the final length of state s.  A WORD is a maximal run of bytes of W inside
+ * [0, n_owned) (position n_owned ends a word).  For a word [a, b), n = b - a, the nodes are 0..n and
+ *   - PIECE EDGES: if n <= max_word_bytes, every record (p, s) with a <= p and p + L_s <= b is an edge
+ *     p - a -> p - a + L_s carrying (first_id, first_score) of s when p == a, (cont_id, cont_score) otherwise; the edge
+ *     exists only if that id is not PFAC_TOKEN_DROP.  A word longer than the cap has no piece edges;
+ *   - BYTE EDGES: j -> j + 1 with byte_score, always;
+ *   - best[0] = 0, best[j] = the maximum over the edges i -> j of best[i] + score; of equal candidates the smaller i
+ *     wins (the longer edge), and of a one-byte piece and the byte edge the piece;
+ *   - the path is the backtrack from n: it is unique.
+ * Every position of [0, n_owned) emits at most one token, ascending:
+ *   - a piece edge of a path emits its id at its first byte;
+ *   - with unk_id >= 0, every maximal run of consecutive byte edges on one word's path emits one unk_id at the run's
+ *     first byte; with unk_id == PFAC_TOKEN_DROP every byte edge emits byte_ids[in[i]], unless that is DROP;
+ *   - a byte outside W emits byte_ids[in[i]], unless that is DROP (never unk_id);
+ *   - in[i] is the byte as the caller wrote it, whatever the case fold.
+ * d_input / d_records as pfac_records_filter_roles (NULL = the slot's buffers).  flags: PFAC_TOKENS_POSITIONS.  The
+ * outputs, their NULL rules and alignments, PFAC_E_OVERFLOW (exact *n_tokens, nothing written) and the one copy back
+ * per call are those of pfac_tokenize_*; the slot-owned result is the tokenizer's own ONE shared result
+ * (pfac_tokens_d2h, pfac_tokens_offsets_d2h).  No word at or past *n_tokens is written; input reads stay below n_avail.
+ * PFAC_E_STATE first, in the filters' order: no finished scan, no final lengths, a scan of an earlier table, no
+ * Unigram attachment for the current table, an overflowed heap, a reserve that replaced a slot buffer the call would
+ * use.  Then PFAC_E_ARG: unknown flags, d_pos without the flag, a d_records that is not the scan's heap, misalignment.
+ * The documents form needs offsets that start at 0, do not decrease and end at n_owned, each on a word boundary
+ * (WordPiece's rule, checked on the device, one thread per offset); else PFAC_E_ARG and nothing written.  tok_off is
+ * as in pfac_tokenize_documents.  Chained ranges are out of scope: cut chunks at a byte outside W.
+ * Kernels: a solve pass (a workgroup per 4 KiB tile; the tile's words and the one that enters from the left, one lane
+ * per word: forward DP in LDS in heap order, backtrack into the bitmaps "edge start" and "byte edge", kept per tile
+ * with the emit bitmap and its prefixes); the tokenizer's group prefix and document offsets; a write pass like the
+ * tokenizer's that finds a piece's state as the record (p, L).  Measured: 24.8 ms for 1 GiB of text with
+ * 448.7 M records, 1.06 times the role filter + selection + WordPiece pass over the same buffer. */
+int pfac_unigram_records(pfac_ctx *ctx, int slot, const void *d_input, const void *d_records, uint32_t flags, int32_t *d_ids,
+                         uint64_t out_cap, uint32_t *d_pos, uint64_t *n_tokens);
+int pfac_unigram_documents(pfac_ctx *ctx, int slot, const void *d_input, const void *d_records, const uint64_t *d_doc_offsets,
+                           uint64_t n_docs, uint32_t flags, int32_t *d_ids, uint64_t out_cap, uint32_t *d_pos,
+                           uint64_t *d_tok_offsets, uint64_t *n_tokens);
+
 /* Synthetic input generators, written straight into device memory (the
  * reference built big inputs by tiling a small text, creatbiginput.sh:2-5).
  *   tiled : byte i = pattern[(phase + i) % period]

@@ -5814,6 +5814,330 @@ __global__ void pfac_wp_docs_kernel(const unsigned long long *off, unsigned long
 }
 
 // ---------------------------------------------------------------------------
+// Unigram (pfac_table_set_unigram, pfac_unigram_records / _documents): the best-scoring cut of every word, by Viterbi
+// over the lattice of ALL records inside the word (THE RULE is in pfac.h).  The first token pass that reads the record
+// heap, not a selection.  Position-driven over the scan's 4 KiB tiles; no dependency between tiles.
+//   pfac_ug_solve_kernel     a workgroup of four waves per tile.  Its region is the tile and EXT bytes on either side
+//                            (EXT = 256 for max_word <= 255, else 4096; EXT > max_word, so the region holds every word
+//                            of at most max_word bytes that touches the tile, whole).  In LDS, by region position: the
+//                            bitmaps W (word bytes below n_owned) and K (bytes whose byte id is kept), 16 bytes per lane
+//                            per load; S (edge starts of the chosen paths) and B (byte edges), which start as W -- a
+//                            word nobody solves (over the cap, or with its start further back than EXT, which is over
+//                            the cap too) is all byte edges.  The word starts of the region that lie in front of the
+//                            tile's end are listed in LDS and dealt to the lanes, one word per lane at a time: the
+//                            word's end from W, then a forward DP over best[] (int32) and the chosen edge (uint16:
+//                            length | UG_BYTE) -- the records of position i pushed in heap order, which is ascending
+//                            length, then the byte edge, each with a strict >, which IS the tie rule -- then the
+//                            backtrack, which clears S inside and B over every piece edge.  The lane finds the first
+//                            record of its word by one binary search in the tile's run and then walks the run (and the
+//                            next tile's) in step with the positions: trip count = the word's bytes + its records.  A
+//                            word that straddles a tile edge is solved by both tiles, from the same bytes and records:
+//                            they agree.  Then one wave derives the tile's emitting positions from the four bitmaps
+//                            (unk fusing needs B of the position in front: the region has it) and keeps W, S, B, the
+//                            emit bitmap, the 16-bit prefix per word and the tile's count.
+//   pfac_ug_group_kernel     one wave per 64 tiles: the counts become the prefixes inside the group, and its sum
+//   pfac_scan_groups_kernel, pfac_wp_docs_kernel, pfac_tk_doc_kernel: unchanged
+//   pfac_ug_write_kernel     one wave per tile, pfac_tk_write_kernel's staging and stores.  Byte and unk tokens first;
+//                            then "first record of position p" (LDS, one lane per record) and a lane per bitmap word
+//                            over its piece starts: a piece runs to the next edge start or the word's end (the next bit
+//                            of S | ~W, in the next tile's maps where it straddles), its state is the record (p, L).
+constexpr int UG_THREADS = 4 * WAVE;
+constexpr int UG_MAPS = 3;                          // W, S, B
+constexpr unsigned UG_BYTE = 0x8000u;               // chosen edge: the byte edge (else a piece of that length)
+constexpr int UG_NEG = -2147483647 - 1;             // best[] of a node nothing has reached yet
+
+// bits [lo, hi) of the 64-bit words of an LDS bitmap cleared (lo < hi)
+__device__ __forceinline__ void ug_clear(unsigned long long *m, unsigned lo, unsigned hi) {
+    for (unsigned x = lo >> 6; x <= (hi - 1u) >> 6; x++) atomicAnd(&m[x], ~wp_range(x, lo, hi));
+}
+
+struct UgRun {                                      // a tile's run of the heap
+    unsigned long long base;
+    unsigned cnt;
+};
+__device__ __forceinline__ UgRun ug_run_of(const unsigned long long *tix, unsigned long long n_tix, unsigned long long cap,
+                                           unsigned long long t) {
+    UgRun r{0ull, 0u};
+    if (t < n_tix) {
+        const unsigned long long e = tix[t];
+        r.base = e & TIX_BASE_MASK;
+        r.cnt = (unsigned)(e >> TIX_CNT_SHIFT);
+        if (r.base >= cap) r.cnt = 0u;                              // (records past the capacity were never written)
+        else if (r.base + r.cnt > cap) r.cnt = (unsigned)(cap - r.base);
+    }
+    return r;
+}
+
+template <int BYTES, int EXT>
+__global__ void __launch_bounds__(UG_THREADS)
+pfac_ug_solve_kernel(const void *rec, const unsigned long long *tix, unsigned long long n_tix, unsigned long long cap,
+                     const unsigned char *in, unsigned long long n_avail, unsigned long long n_owned, const short *flen,
+                     const int4 *pieces, const int *btok, unsigned num_final, int byte_score, int unk_id, unsigned max_word,
+                     WordSet ws, unsigned long long *maps, unsigned long long *bm, unsigned short *wpre, unsigned *tcnt) {
+    constexpr unsigned R = WTILE + 2 * EXT, RW = R / 64;
+    __shared__ int s_best[R];
+    __shared__ unsigned short s_ch[R];
+    __shared__ unsigned short s_list[R / 2 + 64];
+    __shared__ unsigned long long s_W[RW], s_K[RW], s_S[RW], s_B[RW];
+    __shared__ unsigned s_n;
+    const unsigned tid = threadIdx.x;
+    const int lane = (int)(tid & (WAVE - 1));
+    const unsigned long long t = blockIdx.x;
+    const unsigned long long tile_lo = t * WTILE;
+    const unsigned off0 = t ? (unsigned)EXT : 0u;                   // the tile's first position in the region
+    const unsigned long long reg_lo = tile_lo - off0;
+    WordSet kv;                                                     // the bytes whose byte id is kept
+#pragma unroll
+    for (int k = 0; k < 4; k++) kv.w[k] = __ballot(btok[k * WAVE + lane] >= 0);
+    if (tid == 0) s_n = 0u;
+    for (unsigned c = tid; c < R / 16; c += UG_THREADS) {
+        const unsigned long long g = reg_lo + c * 16ull;
+        const unsigned dom = tk_domain16(g, 0ull, n_owned);
+        unsigned wb = 0u, kb = 0u;
+        if (dom) {
+            const uint4 v = tk_load16(in, g, n_avail);
+            const auto four = [&](unsigned q, int at) {
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    const int byte = (int)((q >> (8 * i)) & 255u);
+                    wb |= (unsigned)word_byte(ws, byte) << (at + i);
+                    kb |= (unsigned)word_byte(kv, byte) << (at + i);
+                }
+            };
+            four(v.x, 0);
+            four(v.y, 4);
+            four(v.z, 8);
+            four(v.w, 12);
+        }
+        reinterpret_cast<unsigned short *>(s_W)[c] = (unsigned short)(wb & dom);
+        reinterpret_cast<unsigned short *>(s_K)[c] = (unsigned short)(kb & dom);
+    }
+    for (unsigned r = tid; r < R; r += UG_THREADS) s_best[r] = UG_NEG;
+    __syncthreads();
+    for (unsigned x = tid; x < RW; x += UG_THREADS) {
+        const unsigned long long W = s_W[x];
+        s_S[x] = W;
+        s_B[x] = W;
+        // a start: a word byte with none in front of it; what lies in front of the region is not known (taken as one)
+        const unsigned long long top = x ? s_W[x - 1] >> 63 : (reg_lo ? 1ull : 0ull);
+        unsigned long long st = W & ~(W << 1 | top);
+        if (x * 64u >= off0 + WTILE) st = 0ull;                     // the words that start behind the tile are not its own
+        while (st) {
+            const unsigned b = (unsigned)__builtin_ctzll(st);
+            st &= st - 1ull;
+            s_list[atomicAdd(&s_n, 1u)] = (unsigned short)(x * 64u + b);
+        }
+    }
+    __syncthreads();
+    const unsigned n_words = s_n;
+    for (unsigned k = tid; k < n_words; k += UG_THREADS) {
+        const unsigned a = s_list[k];
+        unsigned b = R;                                             // the word's end: the first 0 of W behind a
+        {
+            unsigned x = a >> 6;
+            unsigned long long inv = ~s_W[x] & ~tk_below(a & 63u);
+            while (!inv && x + 1u < RW && (x + 1u) * 64u <= a + max_word) inv = ~s_W[++x];
+            if (inv) b = x * 64u + (unsigned)__builtin_ctzll(inv);
+        }
+        if (b - a > max_word || b <= off0) continue;                // over the cap: all byte edges, as S and B stand
+        const unsigned long long ga = reg_lo + a;
+        unsigned long long ct = ga >> 12;
+        UgRun run = ug_run_of(tix, n_tix, cap, ct);
+        unsigned j = 0;
+        {                                                           // the first record at or behind a
+            unsigned hi = run.cnt;
+            while (j < hi) {
+                const unsigned m = j + (hi - j) / 2u;
+                unsigned p, s;
+                heap_record<BYTES>(rec, run.base + m, ct, p, s);
+                if ((unsigned long long)p < ga) j = m + 1u;
+                else hi = m;
+            }
+        }
+        unsigned rp = 0u, rs = 0u;
+        bool have = false;
+        s_best[a] = 0;
+        for (unsigned i = a; i < b; i++) {
+            const unsigned long long gi = reg_lo + i;
+            if (gi >> 12 != ct) {                                   // the word goes on in the next tile: its run
+                ct = gi >> 12;
+                run = ug_run_of(tix, n_tix, cap, ct);
+                j = 0u;
+                have = false;
+            }
+            const int bi = s_best[i];
+            for (;;) {
+                if (!have) {
+                    if (j >= run.cnt) break;
+                    heap_record<BYTES>(rec, run.base + j, ct, rp, rs);
+                    have = true;
+                }
+                if ((unsigned long long)rp != gi) break;
+                have = false;
+                j++;
+                if (rs >= num_final) continue;
+                const int L = flen[rs];
+                if (L < 1 || i + (unsigned)L > b) continue;
+                const int4 pc = pieces[rs];
+                const int id = i == a ? pc.x : pc.y, sc = i == a ? pc.z : pc.w;
+                if (id < 0) continue;
+                if (bi + sc > s_best[i + (unsigned)L]) {
+                    s_best[i + (unsigned)L] = bi + sc;
+                    s_ch[i + (unsigned)L] = (unsigned short)L;
+                }
+            }
+            if (bi + byte_score > s_best[i + 1u]) {
+                s_best[i + 1u] = bi + byte_score;
+                s_ch[i + 1u] = (unsigned short)(1u | UG_BYTE);
+            }
+        }
+        for (unsigned e = b; e > a;) {                              // the path, from its end
+            const unsigned c = s_ch[e], L = c & 0x7fffu, p = e - L;
+            if (!(c & UG_BYTE)) {
+                ug_clear(s_B, p, e);
+                if (L > 1u) ug_clear(s_S, p + 1u, e);
+            }
+            e = p;
+        }
+    }
+    __syncthreads();
+    if (tid < WAVE) {
+        const unsigned x = off0 / 64u + (unsigned)lane;
+        const unsigned long long W = s_W[x], K = s_K[x], S = s_S[x], B = s_B[x];
+        const unsigned long long prevb = x ? s_B[x - 1] >> 63 : 0ull;
+        const unsigned long long ub = unk_id >= 0 ? B & ~(B << 1 | prevb) : B & K;
+        const unsigned long long word = (K & ~W) | (S & ~B) | ub;
+        const unsigned c = (unsigned)__popcll(word), incl = wave_incl_scan(c);
+        unsigned long long *m = maps + t * (UG_MAPS * TK_WORDS);
+        m[lane] = W;
+        m[TK_WORDS + lane] = S;
+        m[2 * TK_WORDS + lane] = B;
+        bm[t * TK_WORDS + (unsigned)lane] = word;
+        wpre[t * TK_WORDS + (unsigned)lane] = (unsigned short)(incl - c);
+        if (lane == WAVE - 1) tcnt[t] = incl;
+    }
+}
+
+// the tiles' counts -> the tokens in front of each tile in its group of 64, and the group's sum
+__global__ void __launch_bounds__(WAVE)
+pfac_ug_group_kernel(unsigned *tpre, unsigned long long n_tiles, unsigned long long *gsum) {
+    const unsigned long long t = (unsigned long long)blockIdx.x * TK_GROUP + threadIdx.x;
+    const unsigned c = t < n_tiles ? tpre[t] : 0u, incl = wave_incl_scan(c);
+    if (t < n_tiles) tpre[t] = incl - c;
+    if (threadIdx.x == WAVE - 1) gsum[blockIdx.x] = incl;
+}
+
+template <int BYTES, bool POS>
+__global__ void __launch_bounds__(WAVE)
+pfac_ug_write_kernel(const void *rec, const unsigned long long *tix, unsigned long long n_tix, unsigned long long cap,
+                     const unsigned char *in, unsigned long long n_avail, const short *flen, const int4 *pieces,
+                     const int *btok, unsigned num_final, int unk_id, WordSet ws, const unsigned long long *maps,
+                     unsigned long long n_tiles, const unsigned long long *bm, const unsigned short *wpre,
+                     const unsigned *tpre, const unsigned long long *gpre, int *ids, unsigned *pos) {
+    __shared__ int s_btok[256];
+    __shared__ unsigned long long s_bm[TK_WORDS], s_w[TK_WORDS], s_s[TK_WORDS], s_b[TK_WORDS];
+    __shared__ unsigned short s_pre[TK_WORDS];
+    __shared__ __attribute__((aligned(16))) unsigned s_first[WTILE];
+    __shared__ __attribute__((aligned(16))) int s_ids[TK_STAGE];
+    __shared__ __attribute__((aligned(16))) unsigned s_pos[POS ? TK_STAGE : 4];
+    const int lane = threadIdx.x;
+    const unsigned long long t = blockIdx.x;
+    const unsigned long long word = bm[t * TK_WORDS + (unsigned)lane];
+    const unsigned wp = wpre[t * TK_WORDS + (unsigned)lane];
+    const unsigned cnt = bcast_last(wp + (unsigned)__popcll(word));
+    if (cnt == 0) return;                                           // (wave-uniform)
+    const unsigned long long base = gpre[t / TK_GROUP] + tpre[t];
+    const unsigned a = (unsigned)(base & 3ull);
+    const unsigned long long tile_lo = t * WTILE;
+    const unsigned long long *m = maps + t * (UG_MAPS * TK_WORDS);
+    s_bm[lane] = word;
+    s_w[lane] = m[lane];
+    s_s[lane] = m[TK_WORDS + lane];
+    s_b[lane] = m[2 * TK_WORDS + lane];
+    s_pre[lane] = (unsigned short)wp;
+#pragma unroll
+    for (int i = 0; i < 4; i++) s_btok[i * WAVE + lane] = btok[i * WAVE + lane];
+#pragma unroll
+    for (int i = 0; i < WTILE / (4 * WAVE); i++)
+        *reinterpret_cast<uint4 *>(&s_first[(i * WAVE + lane) * 4]) = make_uint4(~0u, ~0u, ~0u, ~0u);
+    wave_lds_sync();
+#pragma unroll
+    for (int j = 0; j < SUBS; j++) {                                // the byte and unk tokens, in rank order
+        const unsigned lp = (unsigned)j * SUB + (unsigned)lane * 16u, sh = lp & 63u;
+        const unsigned long long wv = s_bm[lp >> 6];
+        unsigned e = (unsigned)(wv >> sh) & 0xffffu;
+        if (!e) continue;
+        const unsigned u = unk_id >= 0 ? (unsigned)(s_b[lp >> 6] >> sh) & 0xffffu : 0u;
+        unsigned rank = a + s_pre[lp >> 6] + (unsigned)__popcll(wv & tk_below(sh));
+        const uint4 v = tk_load16(in, tile_lo + lp, n_avail);
+        const unsigned q[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int c = 0; c < 16; c++) {
+            if (e >> c & 1u) {
+                s_ids[rank] = (u >> c & 1u) ? unk_id : s_btok[(q[c >> 2] >> (8 * (c & 3))) & 255u];
+                if constexpr (POS) s_pos[rank] = (unsigned)(tile_lo + lp + (unsigned)c);
+                rank++;
+            }
+        }
+    }
+    const UgRun run = ug_run_of(tix, n_tix, cap, t);
+    for (unsigned k = (unsigned)lane; k < run.cnt; k += WAVE) {     // the first record of every position
+        unsigned p, s, pp = ~0u, ps;
+        heap_record<BYTES>(rec, run.base + k, t, p, s);
+        if (k) heap_record<BYTES>(rec, run.base + k - 1u, t, pp, ps);
+        if (p != pp && (unsigned long long)p >= tile_lo && (unsigned long long)p < tile_lo + WTILE) s_first[p - (unsigned)tile_lo] = k;
+    }
+    wave_lds_sync();
+    const bool cont0 = t > 0 && word_byte(ws, (int)in[tile_lo - 1]);
+    unsigned long long pw = s_s[lane] & ~s_b[lane] & word;          // this word's piece starts
+    while (pw) {
+        const unsigned q = (unsigned)__builtin_ctzll(pw), lp = (unsigned)lane * 64u + q;
+        pw &= pw - 1ull;
+        unsigned y = (unsigned)lane;                                // the piece's end: the next bit of S | ~W
+        unsigned long long cur = (s_s[y] | ~s_w[y]) & (q == 63u ? 0ull : ~0ull << (q + 1u));
+        while (!cur && y < TK_WORDS + HALO_MAX / 64u) {
+            y++;
+            if (y < (unsigned)TK_WORDS) cur = s_s[y] | ~s_w[y];
+            else if (t + 1 < n_tiles) cur = m[UG_MAPS * TK_WORDS + TK_WORDS + (y - TK_WORDS)] | ~m[UG_MAPS * TK_WORDS + (y - TK_WORDS)];
+            else cur = ~0ull;
+        }
+        const unsigned L = cur ? y * 64u + (unsigned)__builtin_ctzll(cur) - lp : 0u;
+        const bool cont = lp ? (s_w[(lp - 1u) >> 6] >> ((lp - 1u) & 63u) & 1ull) != 0ull : cont0;
+        int v = PFAC_TOKEN_DROP;                                    // (no such record: not an id, so a caller would see it)
+        for (unsigned k = s_first[lp]; k < run.cnt; k++) {          // the record (p, L): at most one per length
+            unsigned p, s;
+            heap_record<BYTES>(rec, run.base + k, t, p, s);
+            if (p != (unsigned)tile_lo + lp) break;
+            if (s < num_final && (unsigned)flen[s] == L) {
+                const int4 pc = pieces[s];
+                v = cont ? pc.y : pc.x;
+                break;
+            }
+        }
+        const unsigned long long wv = s_bm[lane];
+        const unsigned rank = a + s_pre[lane] + (unsigned)__popcll(wv & tk_below(q));
+        s_ids[rank] = v;
+        if constexpr (POS) s_pos[rank] = (unsigned)tile_lo + lp;
+    }
+    wave_lds_sync();
+    const unsigned long long g0 = base - a;                         // a multiple of 4: ids + g0 is 16-B aligned
+    for (unsigned c = (unsigned)lane; c * 4u < a + cnt; c += WAVE) {
+        const unsigned s0 = c * 4u;
+        if (s0 >= a && s0 + 4u <= a + cnt) {
+            *reinterpret_cast<uint4 *>(ids + g0 + s0) = *reinterpret_cast<const uint4 *>(&s_ids[s0]);
+            if constexpr (POS) *reinterpret_cast<uint4 *>(pos + g0 + s0) = *reinterpret_cast<const uint4 *>(&s_pos[s0]);
+        } else {
+            for (unsigned x = s0; x < s0 + 4u; x++) {
+                if (x >= a && x < a + cnt) {
+                    ids[g0 + x] = s_ids[x];
+                    if constexpr (POS) pos[g0 + x] = s_pos[x];
+                }
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Proximity rules (pfac_documents_near): bit r of mask[d] is set iff document d holds two distinct records i < j, at
 // most max_dist bytes apart by their starts, that are an (A_r, B_r) pair -- in either order unless the rule is ordered.
 // With a maximum distance only, the nearest earlier A (or B) is the best partner a record can have, so the pass needs
@@ -6247,6 +6571,9 @@ struct Slot {
     DevBuf<unsigned long long> wp_maps;   // per tile: W, U, ST, E0 (4 x 64 words), ...
     DevBuf<unsigned long long> wp_sum;    // ... its edge summary, ...
     DevBuf<unsigned long long> wp_unk;    // ... and its 64 words of [UNK] positions
+    // pfac_unigram_records / pfac_unigram_documents (bm, wpre, tpre and the three outputs are the tokenizer's)
+    DevBuf<unsigned long long> ug_maps;   // per tile: W, S, B (3 x 64 words)
+    uint64_t ug_gen = 0;                  // the attachment the slot's token result was made under (pfac_ctx::ug_gen; 0: another pass)
 };
 
 struct StageLayout {                      // per-wave LDS of one staging mode
@@ -6326,6 +6653,12 @@ struct pfac_ctx {
     unsigned wp_max = 0;                  // ... the longest good word in bytes, ...
     WordSet wp_ws{};                      // ... and the word bytes
     uint64_t wp_gen = 0;                  // attachments made so far: a role filter remembers the one it ran under
+    DevBuf<int4> ug_pieces;               // Unigram (pfac_table_set_unigram): (first id, cont id, first score, cont score) of every final state, ...
+    DevBuf<int> ug_btok;                  // ... the id of every byte value, ...
+    int ug_unk = 0, ug_bscore = 0;        // ... the id of a run of byte edges (or DROP: byte fallback), the score of a byte edge, ...
+    unsigned ug_max = 0;                  // ... the longest word with piece edges, in bytes, ...
+    WordSet ug_ws{};                      // ... and the word bytes
+    uint64_t ug_gen = 0;                  // attachments made so far
     DevBuf<unsigned> ru_sptr;             // the rule table, state-major (pfac_table_set_rules): state_ptr[num_final + 1], ...
     DevBuf<unsigned> ru_ent;              // ... the entries rule << 1 | negated, the rules ascending inside a state, ...
     DevBuf<unsigned> ru_need;             // ... and need[n_rules]
@@ -6913,6 +7246,7 @@ int install_table(pfac_ctx *ctx, const int *d_blob, const int32_t *hdr, size_t n
     ctx->spans.reset();                                     // ... and the state spans
     ctx->tok.reset(); ctx->btok.reset();                    // ... and the token ids
     ctx->wp_ids.reset(); ctx->wp_btok.reset();              // ... and the WordPiece ids
+    ctx->ug_pieces.reset(); ctx->ug_btok.reset();           // ... and the Unigram pieces
     ctx->ru_sptr.reset(); ctx->ru_ent.reset(); ctx->ru_need.reset(); ctx->ru_n = ctx->ru_terms = 0;     // ... and the rules
     ctx->have_table = false; ctx->table_gen++;
     TablePlan P;
@@ -9438,6 +9772,7 @@ static int tk_run(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *d_i
     s.tk_ids.invalidate();
     s.tk_pos.invalidate();
     s.tk_off.invalidate();
+    s.ug_gen = 0;
     if (!s.scanned || !s.ll_out.done || s.ll_seq != s.scan_seq || (docs && !s.ll_docs))
         return fail(ctx, PFAC_E_STATE, fn + (docs ? " needs a pfac_records_leftmost_longest_documents since the slot's last scan"
                                                   : " needs a pfac_records_leftmost_longest since the slot's last scan"));
@@ -9669,6 +10004,7 @@ static int wp_run(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *d_i
     s.tk_ids.invalidate();
     s.tk_pos.invalidate();
     s.tk_off.invalidate();
+    s.ug_gen = 0;
     if (!s.scanned || !s.ll_out.done || s.ll_seq != s.scan_seq || (docs && !s.ll_docs))
         return fail(ctx, PFAC_E_STATE, fn + (docs ? " needs a pfac_records_leftmost_longest_documents since the slot's last scan"
                                                   : " needs a pfac_records_leftmost_longest since the slot's last scan"));
@@ -9801,6 +10137,207 @@ int pfac_wordpiece_documents(pfac_ctx *ctx, int slot, const void *d_input, const
     *n_tokens = 0;
     const TkDocs docs{d_doc_offsets, d_doc_first, d_tok_offsets};
     return wp_run(ctx, ctx->slots[slot], "pfac_wordpiece_documents", d_input, d_sel, flags, d_ids, out_cap, d_pos, n_tokens, &docs);
+}
+
+// The Unigram attachment: checked whole, made aside, swapped in together, as the WordPiece one is; it leaves that one
+// and the token ids alone.
+int pfac_table_set_unigram(pfac_ctx *ctx, const pfac_unigram_piece *pieces, uint64_t n_states, const int32_t *byte_ids,
+                           int32_t byte_score, int32_t unk_id, const uint64_t word_set[4], uint32_t max_word_bytes) {
+    if (!ctx) return fail(nullptr, PFAC_E_ARG, "null context");
+    const std::string fn = "pfac_table_set_unigram";
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (!ctx->have_table) return fail(ctx, PFAC_E_STATE, fn + " before a table upload");
+    if (n_states != (uint64_t)ctx->plan.base.num_final || (!pieces && n_states))
+        return fail(ctx, PFAC_E_ARG, fn + ": need num_final pieces (num_final " + std::to_string(ctx->plan.base.num_final) + ")");
+    if (max_word_bytes < 1 || max_word_bytes > 4095) return fail(ctx, PFAC_E_ARG, fn + ": max_word_bytes must lie in 1..4095");
+    // sums stay in int32: a path has at most max_word_bytes edges (and one more for slack)
+    const auto fits = [&](int32_t sc) { return (uint64_t)std::llabs((long long)sc) * (max_word_bytes + 1ull) < (1ull << 31); };
+    std::vector<int4> quads(std::max<uint64_t>(n_states, 1), make_int4(PFAC_TOKEN_DROP, PFAC_TOKEN_DROP, 0, 0));
+    for (uint64_t i = 0; i < n_states; i++) {
+        const pfac_unigram_piece &p = pieces[i];
+        if (p.first_id < PFAC_TOKEN_DROP || p.cont_id < PFAC_TOKEN_DROP)
+            return fail(ctx, PFAC_E_ARG, fn + ": an id of final state " + std::to_string(i) + " is neither >= 0 nor PFAC_TOKEN_DROP");
+        if (!fits(p.first_score) || !fits(p.cont_score))
+            return fail(ctx, PFAC_E_ARG, fn + ": a score of final state " + std::to_string(i) + " times max_word_bytes + 1 does not fit int32");
+        quads[i] = make_int4(p.first_id, p.cont_id, p.first_score, p.cont_score);
+    }
+    int32_t bytes[256];
+    for (int b = 0; b < 256; b++) {
+        bytes[b] = byte_ids ? byte_ids[b] : PFAC_TOKEN_DROP;
+        if (bytes[b] < PFAC_TOKEN_DROP)
+            return fail(ctx, PFAC_E_ARG, fn + ": the id of byte " + std::to_string(b) + " is neither >= 0 nor PFAC_TOKEN_DROP");
+    }
+    if (!fits(byte_score)) return fail(ctx, PFAC_E_ARG, fn + ": byte_score times max_word_bytes + 1 does not fit int32");
+    if (unk_id < PFAC_TOKEN_DROP) return fail(ctx, PFAC_E_ARG, fn + ": unk_id must be >= 0 or PFAC_TOKEN_DROP");
+    USE_DEVICE(ctx);
+    DevBuf<int4> dp;
+    DevBuf<int> btok;
+    int rc = dp.ensure(ctx, nullptr, quads.size(), quads.size());
+    if (!rc) rc = btok.ensure(ctx, nullptr, 256, 256);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpy(dp.p, quads.data(), quads.size() * sizeof(int4), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(btok.p, bytes, sizeof bytes, hipMemcpyHostToDevice));
+    ctx->ug_pieces = std::move(dp);                         // (a swap: the old buffers go with the two locals)
+    ctx->ug_btok = std::move(btok);
+    ctx->ug_unk = unk_id;
+    ctx->ug_bscore = byte_score;
+    ctx->ug_max = max_word_bytes;
+    for (int k = 0; k < 4; k++)                              // NULL: everything but \t \n \v \f \r and space
+        ctx->ug_ws.w[k] = word_set ? word_set[k] : (k == 0 ? ~0x0000000100003E00ull : ~0ull);
+    ctx->ug_gen++;
+    for (auto &sl : ctx->slots) {                            // a slot-owned result of the earlier attachment is stale
+        if (!sl.ug_gen) continue;
+        sl.tk_ids.invalidate();
+        sl.tk_pos.invalidate();
+        sl.tk_off.invalidate();
+        sl.ug_gen = 0;
+    }
+    return PFAC_OK;
+}
+
+struct UgDocs {
+    const uint64_t *off;
+    uint64_t n_docs;
+    uint64_t *tok_off;
+};
+
+// wp_run's sibling over the record heap: the filters' ladder, the tokenizer's outputs, the Unigram kernels between them
+static int ug_run(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *d_input, const void *d_records, uint32_t flags,
+                  int32_t *d_ids, uint64_t out_cap, uint32_t *d_pos, uint64_t *n_tokens, const UgDocs *docs) {
+    s.tk_ids.invalidate();
+    s.tk_pos.invalidate();
+    s.tk_off.invalidate();
+    s.ug_gen = 0;
+    int rc = last_scan_usable(ctx, s, fn, SCAN_FINISHED | SCAN_LENGTHS | SCAN_TABLE);
+    if (rc) return rc;
+    if (!ctx->ug_pieces.p) return fail(ctx, PFAC_E_STATE, fn + ": no Unigram pieces for the uploaded table (pfac_table_set_unigram)");
+    if (s.last_used > s.last_cap) return fail(ctx, PFAC_E_STATE, fn + ": the slot's last scan overflowed its record heap: scan again with a larger one");
+    if (!d_records && (const void *)s.records.p != s.last_records)
+        return fail(ctx, PFAC_E_STATE, fn + ": the slot's record heap was replaced since its last scan");
+    if (!d_input && s.last_avail > s.input.cap)
+        return fail(ctx, PFAC_E_STATE, fn + ": the slot's input buffer was replaced since its last scan");
+    const bool want_pos = flags & PFAC_TOKENS_POSITIONS;
+    if (flags & ~PFAC_TOKENS_POSITIONS) return fail(ctx, PFAC_E_ARG, fn + ": unknown flags");
+    if (d_pos && !want_pos) return fail(ctx, PFAC_E_ARG, fn + ": d_pos without PFAC_TOKENS_POSITIONS");
+    const void *heap = d_records ? d_records : (const void *)s.records.p;
+    if (heap != s.last_records) return fail(ctx, PFAC_E_ARG, fn + ": d_records is not the record heap of the slot's last scan");
+    const unsigned char *in = d_input ? static_cast<const unsigned char *>(d_input) : s.input.p;
+    const uint64_t n_owned = s.last_owned, n_avail = s.last_avail;
+    if (((uintptr_t)d_ids & 15) || ((uintptr_t)d_pos & 15) || ((uintptr_t)in & 15))
+        return fail(ctx, PFAC_E_ARG, fn + ": misaligned buffer (d_input, d_ids and d_pos 16 B)");
+    if (n_owned && !in) return fail(ctx, PFAC_E_ARG, fn + ": no input buffer");
+    const unsigned long long *doff = nullptr;
+    unsigned long long *dtok_off = nullptr;
+    uint64_t n_docs = 0;
+    if (docs) {
+        n_docs = docs->n_docs;
+        dtok_off = reinterpret_cast<unsigned long long *>(docs->tok_off);
+        rc = resolve_docs(ctx, s, fn, docs->off, n_docs, (uintptr_t)dtok_off, &doff);
+        if (rc) return rc;
+        if (((uintptr_t)doff & 7) || ((uintptr_t)dtok_off & 7)) return fail(ctx, PFAC_E_ARG, fn + ": device buffers must be 8-byte aligned");
+    }
+    USE_DEVICE(ctx);
+    const uint64_t n_tiles = (n_owned + WTILE - 1) / WTILE, n_groups = (n_tiles + TK_GROUP - 1) / TK_GROUP;
+    const unsigned oblocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_docs + 1 + 255) / 256, 65536));
+    const int rb = s.last_rec_bytes;
+    const bool wide = ctx->ug_max > 255;                     // the region's overhang: 256 bytes, or a whole tile
+    uint64_t nt = 0;
+    if (n_tiles) {
+        rc = s.tk_bm.ensure(ctx, s.stream, n_tiles * TK_WORDS, quarter_more(n_tiles) * TK_WORDS);
+        if (!rc) rc = s.tk_wpre.ensure(ctx, s.stream, n_tiles * TK_WORDS, quarter_more(n_tiles) * TK_WORDS);
+        if (!rc) rc = s.tk_tpre.ensure(ctx, s.stream, n_tiles, quarter_more(n_tiles));
+        if (!rc) rc = s.ug_maps.ensure(ctx, s.stream, n_tiles * UG_MAPS * TK_WORDS, quarter_more(n_tiles) * UG_MAPS * TK_WORDS);
+        if (!rc) rc = ensure_gsum(ctx, s, (unsigned)n_groups + 1);      // group prefixes, the total, error flags
+        if (rc) return rc;
+        unsigned long long *res = s.gsum.p + n_groups;
+        HIP_TRY(ctx, hipMemsetAsync(res, 0, 16, s.stream));
+        auto sk = by_width(rb, [wide](auto w) { return wide ? pfac_ug_solve_kernel<w(), WTILE> : pfac_ug_solve_kernel<w(), 256>; });
+        hipLaunchKernelGGL(sk, dim3((unsigned)n_tiles), dim3(UG_THREADS), 0, s.stream, heap, (const unsigned long long *)s.tile_index.p,
+                           (unsigned long long)s.last_tiles, (unsigned long long)s.last_cap, in, (unsigned long long)n_avail,
+                           (unsigned long long)n_owned, ctx->flen.p, (const int4 *)ctx->ug_pieces.p, (const int *)ctx->ug_btok.p,
+                           (unsigned)ctx->plan.base.num_final, ctx->ug_bscore, ctx->ug_unk, ctx->ug_max, ctx->ug_ws, s.ug_maps.p,
+                           s.tk_bm.p, s.tk_wpre.p, s.tk_tpre.p);
+        hipLaunchKernelGGL(pfac_ug_group_kernel, dim3((unsigned)n_groups), dim3(WAVE), 0, s.stream, s.tk_tpre.p,
+                           (unsigned long long)n_tiles, s.gsum.p);
+        hipLaunchKernelGGL(pfac_scan_groups_kernel, dim3(1), dim3(1024), 0, s.stream, s.gsum.p, (unsigned)n_groups);
+        if (docs) {
+            hipLaunchKernelGGL(pfac_offsets_check_kernel, dim3(oblocks), dim3(256), 0, s.stream, doff, (unsigned long long)n_docs,
+                               (unsigned long long)n_owned, res + 1);
+            hipLaunchKernelGGL(pfac_wp_docs_kernel, dim3(oblocks), dim3(256), 0, s.stream, doff, (unsigned long long)n_docs,
+                               (unsigned long long)n_owned, in, ctx->ug_ws, res + 1);
+        }
+        rc = pass_words(ctx, s, res, 2);
+        if (rc) return rc;
+        nt = host_u64(s, H_PASS);
+        if (host_u64(s, H_PASS1) & 1) return bad_doc_offsets(ctx, s, fn);
+        if (host_u64(s, H_PASS1) & 2) return fail(ctx, PFAC_E_ARG, fn + ": a document offset lies inside a word");
+    } else if (docs) {                                       // nothing owned: the offsets rule alone (every offset is 0)
+        rc = ensure_gsum(ctx, s, 1);
+        if (rc) return rc;
+        unsigned long long *res = s.gsum.p;
+        HIP_TRY(ctx, hipMemsetAsync(res, 0, 16, s.stream));
+        hipLaunchKernelGGL(pfac_offsets_check_kernel, dim3(oblocks), dim3(256), 0, s.stream, doff, (unsigned long long)n_docs,
+                           (unsigned long long)n_owned, res + 1);
+        rc = pass_words(ctx, s, res, 2);
+        if (rc) return rc;
+        if (host_u64(s, H_PASS1) & 1) return bad_doc_offsets(ctx, s, fn);
+    }
+    *n_tokens = nt;
+    if ((d_ids || d_pos) && nt > out_cap)
+        return fail(ctx, PFAC_E_OVERFLOW, fn + ": " + std::to_string(nt) + " tokens, out_cap is " + std::to_string(out_cap));
+    const uint64_t cap = align_up(nt + nt / 8, 1024);
+    int *ids = nullptr;
+    unsigned *pos = nullptr;
+    unsigned long long *toff = nullptr;
+    rc = s.tk_ids.bind(ctx, s.stream, d_ids, nt, cap, &ids);       // (everything allocated before the first write)
+    if (!rc && want_pos) rc = s.tk_pos.bind(ctx, s.stream, d_pos, nt, cap, &pos);
+    if (!rc && docs) rc = s.tk_off.bind(ctx, s.stream, dtok_off, n_docs + 1, docs_cap(n_docs), &toff);
+    if (rc) return rc;
+    if (nt) {
+        auto wk = by_width(rb, [want_pos](auto w) { return want_pos ? pfac_ug_write_kernel<w(), true> : pfac_ug_write_kernel<w(), false>; });
+        hipLaunchKernelGGL(wk, dim3((unsigned)n_tiles), dim3(WAVE), 0, s.stream, heap, (const unsigned long long *)s.tile_index.p,
+                           (unsigned long long)s.last_tiles, (unsigned long long)s.last_cap, in, (unsigned long long)n_avail, ctx->flen.p,
+                           (const int4 *)ctx->ug_pieces.p, (const int *)ctx->ug_btok.p, (unsigned)ctx->plan.base.num_final, ctx->ug_unk,
+                           ctx->ug_ws, (const unsigned long long *)s.ug_maps.p, (unsigned long long)n_tiles,
+                           (const unsigned long long *)s.tk_bm.p, (const unsigned short *)s.tk_wpre.p, (const unsigned *)s.tk_tpre.p,
+                           (const unsigned long long *)s.gsum.p, ids, pos);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    if (docs) {
+        if (n_tiles) {
+            hipLaunchKernelGGL(pfac_tk_doc_kernel, dim3(oblocks), dim3(256), 0, s.stream, doff, (unsigned long long)n_docs,
+                               (unsigned long long)n_owned, (unsigned long long)n_tiles, (unsigned)n_groups, s.tk_bm.p,
+                               s.tk_wpre.p, s.tk_tpre.p, s.gsum.p, toff);
+            HIP_TRY(ctx, hipGetLastError());
+        } else {
+            HIP_TRY(ctx, hipMemsetAsync(toff, 0, (n_docs + 1) * 8, s.stream));
+        }
+        s.tk_off.commit(n_docs + 1, !dtok_off);
+    }
+    if (want_pos) s.tk_pos.commit(nt, !d_pos);
+    s.tk_ids.commit(nt, !d_ids);
+    s.ug_gen = ctx->ug_gen;
+    return PFAC_OK;
+}
+
+int pfac_unigram_records(pfac_ctx *ctx, int slot, const void *d_input, const void *d_records, uint32_t flags, int32_t *d_ids,
+                         uint64_t out_cap, uint32_t *d_pos, uint64_t *n_tokens) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    if (!n_tokens) return fail(ctx, PFAC_E_ARG, "null argument");
+    *n_tokens = 0;
+    return ug_run(ctx, ctx->slots[slot], "pfac_unigram_records", d_input, d_records, flags, d_ids, out_cap, d_pos, n_tokens, nullptr);
+}
+
+int pfac_unigram_documents(pfac_ctx *ctx, int slot, const void *d_input, const void *d_records, const uint64_t *d_doc_offsets,
+                           uint64_t n_docs, uint32_t flags, int32_t *d_ids, uint64_t out_cap, uint32_t *d_pos,
+                           uint64_t *d_tok_offsets, uint64_t *n_tokens) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    if (!n_tokens) return fail(ctx, PFAC_E_ARG, "null argument");
+    *n_tokens = 0;
+    const UgDocs docs{d_doc_offsets, n_docs, d_tok_offsets};
+    return ug_run(ctx, ctx->slots[slot], "pfac_unigram_documents", d_input, d_records, flags, d_ids, out_cap, d_pos, n_tokens, &docs);
 }
 
 int pfac_fill_tiled(pfac_ctx *ctx, int slot, void *d_dst, uint64_t n, const void *host_pattern, uint32_t period, uint64_t phase) {

@@ -606,6 +606,76 @@ def wordpiece_table(vocab, prefix: bytes = b"##", word_bytes=None, ignore_case: 
     return table, first, cont, byte_ids, skipped
 
 
+UNIGRAM_PIECE_DTYPE = np.dtype([("first_id", "<i4"), ("cont_id", "<i4"), ("first_score", "<i4"), ("cont_score", "<i4")])   # pfac_unigram_piece
+UNIGRAM_SPACE = bytes(b for b in range(256) if b not in b"\t\n\v\f\r ")      # the default word set: SentencePiece splits at whitespace
+
+
+def unigram_scale_fits(score: int, max_word_bytes: int) -> bool:
+    """The bound of ``pfac_table_set_unigram``: sums of at most max_word_bytes + 1 such scores stay in int32."""
+    return abs(int(score)) * (int(max_word_bytes) + 1) < 2**31
+
+
+def unigram_table(vocab, prefix="▁", word_bytes=None, max_word_bytes: int = 100, scale=None, ignore_case: bool = False) -> tuple:
+    """A Unigram (SentencePiece-style) vocabulary as ONE automaton with a pair of (id, score) per final state, for
+    ``pfac_table_set_unigram``.  ``vocab`` is a sequence of (piece, score): piece bytes or str, score the piece's
+    log-probability as a float; entry k has token id k.  ``word_bytes``: the bytes that make up words (None = every
+    byte but ``\\t\\n\\v\\f\\r`` and space).  Scores become integers, ``round(score * scale)``; ``scale=None`` picks the
+    largest power of two <= 2^16 under which every score keeps ``|score| * (max_word_bytes + 1) < 2^31``; a given
+    ``scale`` that breaks the bound is a ValueError (the runtime would answer PFAC_E_ARG).
+    Returns (table, pieces UNIGRAM_PIECE_DTYPE[num_final], scale, skipped):
+
+    - the patterns are the distinct stripped strings (``▁the`` is inserted as ``the``) made of word bytes only, folded
+      under ``ignore_case``; ``▁the`` gives its state's first id and score, a plain ``the`` the continuation ones;
+      TOKEN_DROP (score 0) where the vocabulary has none;
+    - ``skipped`` lists (id, entry) of everything the rule can never produce: the bare prefix, a piece with the prefix
+      inside it, a piece with a non-word byte, an empty entry, a pattern of 1024 bytes or more, the later of two
+      entries that are the same piece, and control entries (``<unk>``, ``<s>``, ``<0x0A>``: anything in angle
+      brackets).  Byte-fallback ids are the caller's to pass as ``byte_ids``."""
+    prefix = prefix.encode() if isinstance(prefix, str) else bytes(prefix)
+    words = set(UNIGRAM_SPACE if word_bytes is None else bytes(word_bytes))
+    entries = [((e.encode() if isinstance(e, str) else bytes(e)), float(sc)) for e, sc in vocab]
+    lines, slots, skipped = [], {}, []          # pattern lines in order; piece -> [first entry, continuation entry]
+    for k, (e, _) in enumerate(entries):
+        first = len(prefix) > 0 and e.startswith(prefix)
+        piece = e[len(prefix):] if first else e
+        if ignore_case and piece:
+            piece = bytes(fold_ascii(piece))
+        control = len(e) >= 2 and e.startswith(b"<") and e.endswith(b">")
+        if (piece and not control and len(piece) < 1024 and (not prefix or prefix not in piece) and b"\n" not in piece
+                and all(b in words for b in piece)):
+            pair = slots.get(piece)
+            if pair is None:
+                pair = slots[piece] = [None, None]
+                lines.append(piece)
+            if pair[0 if first else 1] is None:
+                pair[0 if first else 1] = k
+                continue
+        skipped.append((k, e))
+    if not lines:
+        raise ValueError("the vocabulary holds no piece made of word bytes")
+    kept = [k for pair in slots.values() for k in pair if k is not None]
+    top = max(abs(entries[k][1]) for k in kept)
+    if scale is None:
+        scale = 2.0**16
+        while scale > 2.0**-40 and not unigram_scale_fits(round(top * scale), max_word_bytes):
+            scale /= 2.0
+    scale = float(scale)
+    if not unigram_scale_fits(round(top * scale), max_word_bytes):
+        raise ValueError(f"a score of {top} times the scale {scale} breaks |score| * (max_word_bytes + 1) < 2^31")
+    table = PfacTable.from_bytes(b"".join(p + b"\n" for p in lines), 256, ignore_case=ignore_case)
+    line_of = token_table(table, list(range(len(lines))))
+    pieces = np.zeros(int(table.num_final), dtype=UNIGRAM_PIECE_DTYPE)
+    pieces["first_id"] = pieces["cont_id"] = TOKEN_DROP
+    for s, ln in enumerate(line_of):
+        if ln < 0:
+            continue
+        for half, k in zip(("first", "cont"), slots[lines[ln]]):
+            if k is not None:
+                pieces[half + "_id"][s] = k
+                pieces[half + "_score"][s] = int(round(entries[k][1] * scale))
+    return table, pieces, scale, skipped
+
+
 TEMPLATE_PLAIN = 0xFFFFFFFF          # PFAC_TEMPLATE_PLAIN: the state's replacement does not quote the match
 
 
