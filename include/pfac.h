@@ -1458,6 +1458,62 @@ int pfac_unigram_documents(pfac_ctx *ctx, int slot, const void *d_input, const v
                            uint64_t n_docs, uint32_t flags, int32_t *d_ids, uint64_t out_cap, uint32_t *d_pos,
                            uint64_t *d_tok_offsets, uint64_t *n_tokens);
 
+/* Byte-level BPE (GPT-2, RoBERTa, Llama 3, every tiktoken vocabulary): a word starts as its single bytes and the
+ * adjacent pair whose concatenation has the lowest merge rank is merged, until no pair has one.  "Is the concatenation
+ * of these two parts a vocabulary string, and which merge makes it" is a lookup of (start, length) among the records of
+ * the word: the second token pass over the record heap itself, with no pair table and no second automaton.  The
+ * automaton holds the vocabulary strings of at least 2 bytes that a merge makes; single-byte tokens go to byte_ids.
+ * The attachment of the installed table: pieces[s], one 16-byte entry per final state (n_states == num_final): id >= 0
+ * or PFAC_TOKEN_DROP; rank >= 0, the index of the merge that makes this string; split, the byte length of that merge's
+ * left half, or 0 for "any split" (tiktoken's form, where the rank belongs to the string; a split >= L_s can never
+ * apply and is not an error); reserved 0.  byte_ids int32[256] (NULL = every byte DROP); word_set as for Unigram (NULL =
+ * every byte except \t \n \v \f \r and space); lead, a byte value 0..255 that is not in the word set, or -1 for none;
+ * max_word_bytes in 1..255.  PFAC_E_ARG for anything else, PFAC_E_STATE before an upload; everything is checked before
+ * anything changes.  The lifetime is the Unigram attachment's: a table upload drops it; a new one is installed whole
+ * behind queued work; a slot-owned result made under an earlier attachment is stale (PFAC_E_STATE from the fetches).  It
+ * touches none of the other three attachments (token ids, WordPiece, Unigram). */
+typedef struct pfac_bpe_piece { int32_t id, rank; uint32_t split, reserved; } pfac_bpe_piece;
+int pfac_table_set_bpe(pfac_ctx *ctx, const pfac_bpe_piece *pieces, uint64_t n_states, const int32_t *byte_ids,
+                       const uint64_t word_set[4], int32_t lead, uint32_t max_word_bytes);
+/* THE RULE.  Over the slot's last finished scan: n_owned, n_avail, its input, and its records as they stand (filtered
+ * or not).  W is the word set, L_s the final length of state s.
+ * WORDS.  A RUN is a maximal run of bytes of W inside [0, n_owned).  The WORD of a run [a, b) is [a - 1, b) if
+ * lead >= 0, a > 0 and in[a - 1] == lead, else [a, b): of several lead bytes in a row only the last belongs to the word
+ * (what GPT-2's pre-tokenizer does with spaces).
+ * MERGES.  For a word [a, b) with n = b - a <= max_word_bytes:
+ *   - the parts start as the n single bytes;
+ *   - two adjacent parts [l, k), [k, r) are a CANDIDATE iff the heap holds a record (l, s) with L_s == r - l, and
+ *     pieces[s].split is 0 or k - l; the candidate's rank is pieces[s].rank;
+ *   - the candidate with the lowest rank is merged; among equal ranks the smallest l wins;
+ *   - repeat until there is no candidate.
+ * A word longer than the cap has no candidates: its parts stay single bytes.
+ * EMISSION.  Every position of [0, n_owned) emits at most one token, ascending:
+ *   - a part of two or more bytes emits pieces[s].id of its record (l, s) at l, unless that is PFAC_TOKEN_DROP;
+ *   - a part of one byte, and every byte outside all words, emits byte_ids[in[i]], unless that is DROP;
+ *   - in[i] is the byte as the caller wrote it, whatever the case fold.
+ * With split set this is the merge-list rule of the usual BPE implementations as long as no two merges make the same
+ * string: the left part equals the merge's left half iff the concatenation matches and the split point agrees.
+ * d_input / d_records, flags (PFAC_TOKENS_POSITIONS), the outputs, their NULL rules and alignments, PFAC_E_OVERFLOW
+ * (exact *n_tokens, nothing written), the one copy back per call and the ONE slot-owned token result (pfac_tokens_d2h,
+ * pfac_tokens_offsets_d2h) are those of pfac_unigram_records / pfac_unigram_documents.  No word at or past *n_tokens is
+ * written; input reads stay below n_avail.  PFAC_E_STATE first, in the filters' order: no finished scan, no final
+ * lengths, a scan of an earlier table, no BPE attachment for the current table, an overflowed heap, a reserve that
+ * replaced a slot buffer the call would use.  Then PFAC_E_ARG: unknown flags, d_pos without the flag, a d_records that is
+ * not the scan's heap, misalignment.  The documents form needs offsets that start at 0, do not decrease and end at
+ * n_owned; none may lie strictly inside a word, and the position between a lead byte and its run counts as inside
+ * (checked on the device, one thread per offset); else PFAC_E_ARG and nothing written.  Chained ranges are out of scope:
+ * cut chunks at a byte outside W that is not a lead.
+ * Kernels: a solve pass (a workgroup per 4 KiB tile and 256 bytes on either side, one lane per word: a
+ * first-record index per position and a cached rank per boundary in LDS, the lowest rank merged until none is left), the
+ * tokenizer's group prefix and document offsets, a write pass that finds a part's id as the record (p, L).  Measured
+ * (DESIGN.md 29): 81.4 ms for 1 GiB of text with 948.2 M records under 194 merges, 2.34 times the Unigram pass over
+ * the same records. */
+int pfac_bpe_records(pfac_ctx *ctx, int slot, const void *d_input, const void *d_records, uint32_t flags, int32_t *d_ids,
+                     uint64_t out_cap, uint32_t *d_pos, uint64_t *n_tokens);
+int pfac_bpe_documents(pfac_ctx *ctx, int slot, const void *d_input, const void *d_records, const uint64_t *d_doc_offsets,
+                       uint64_t n_docs, uint32_t flags, int32_t *d_ids, uint64_t out_cap, uint32_t *d_pos,
+                       uint64_t *d_tok_offsets, uint64_t *n_tokens);
+
 /* Synthetic input generators, written straight into device memory (the
  * reference built big inputs by tiling a small text, creatbiginput.sh:2-5).
  *   tiled : byte i = pattern[(phase + i) % period]

@@ -11,8 +11,9 @@ from .table import RECORD_DTYPE, SCORE_DTYPE, SPAN_DTYPE, PfacTable, emit_packed
 from ._ffi import PFAC_NEAR_ANY_DIST, PFAC_NEAR_MAX_RULES, PFAC_NEAR_ORDERED, PFAC_NEAR_SELECTION  # noqa: F401
 from .table import NEAR_RULE_DTYPE, near_rule  # noqa: F401
 from .table import UNIGRAM_PIECE_DTYPE, unigram_table  # noqa: F401
+from .table import BPE_PIECE_DTYPE, bpe_byte_alphabet, bpe_table  # noqa: F401
 from ._ffi import PFAC_RULE_NOT  # noqa: F401
 from .matcher import GpuMatcher, device_count, word_set  # noqa: F401
 
 __all__ = ["PfacError", "PfacTable", "GpuMatcher", "RECORD_DTYPE", "emit_records", "emit_packed", "emit_records_multi", "merge_partitions", "replacement_table", "fold_ascii", "device_count", "word_set", "PFAC_COUNT_ACCUMULATE", "SPAN_DTYPE", "SCORE_DTYPE", "strip_anchors", "template_table", "PFAC_TERMS_SELECTION", "token_table", "wordpiece_table", "PFAC_TOKEN_DROP", "PFAC_TOKENS_POSITIONS", "NEAR_RULE_DTYPE", "near_rule", "PFAC_NEAR_MAX_RULES", "PFAC_NEAR_ORDERED", "PFAC_NEAR_ANY_DIST",
-           "PFAC_NEAR_SELECTION", "PFAC_RULE_NOT", "unigram_table", "UNIGRAM_PIECE_DTYPE"]
+           "PFAC_NEAR_SELECTION", "PFAC_RULE_NOT", "unigram_table", "UNIGRAM_PIECE_DTYPE", "bpe_table", "bpe_byte_alphabet", "BPE_PIECE_DTYPE"]

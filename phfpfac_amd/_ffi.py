@@ -167,6 +167,7 @@ HIP_SYMBOLS = (
     "pfac_tokens_offsets_d2h",
     "pfac_table_set_wordpiece", "pfac_records_filter_roles", "pfac_wordpiece_leftmost_longest", "pfac_wordpiece_documents",
     "pfac_table_set_unigram", "pfac_unigram_records", "pfac_unigram_documents",
+    "pfac_table_set_bpe", "pfac_bpe_records", "pfac_bpe_documents",
 )
 
 _host = None
@@ -351,6 +352,9 @@ def hip_lib() -> C.CDLL:
         L.pfac_table_set_unigram.argtypes = [vp, vp, u64, vp, C.c_int32, C.c_int32, vp, C.c_uint32]
         L.pfac_unigram_records.argtypes = [vp, i, vp, vp, C.c_uint32, vp, u64, vp, C.POINTER(u64)]
         L.pfac_unigram_documents.argtypes = [vp, i, vp, vp, vp, u64, C.c_uint32, vp, u64, vp, vp, C.POINTER(u64)]
+        L.pfac_table_set_bpe.argtypes = [vp, vp, u64, vp, vp, C.c_int32, C.c_uint32]
+        L.pfac_bpe_records.argtypes = [vp, i, vp, vp, C.c_uint32, vp, u64, vp, C.POINTER(u64)]
+        L.pfac_bpe_documents.argtypes = [vp, i, vp, vp, vp, u64, C.c_uint32, vp, u64, vp, vp, C.POINTER(u64)]
         L.pfac_table_set_state_spans.argtypes = [vp, vp, u64]
         L.pfac_records_filter_spans.argtypes = [vp, i, vp, vp, i, C.c_uint32, vp, u64, C.POINTER(u64)]
         _hip = L

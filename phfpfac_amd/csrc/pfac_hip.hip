@@ -6138,6 +6138,357 @@ pfac_ug_write_kernel(const void *rec, const unsigned long long *tix, unsigned lo
 }
 
 // ---------------------------------------------------------------------------
+// Byte-level BPE (pfac_table_set_bpe, pfac_bpe_records / _documents): the merges of every word in rank order (THE RULE
+// is in pfac.h).  "Is the concatenation of these two parts a vocabulary string, and which merge makes it" is a lookup of
+// (start, length) among the records of the word: the second token pass over the record heap itself, in the Unigram
+// pass's structure -- a workgroup per 4 KiB tile, a region with overhang, straddling words solved by both tiles.
+//   pfac_bpe_solve_kernel    a workgroup of four waves per tile.  Its region is the tile and 256 bytes on either side
+//                            (the cap is at most 255: the region holds every word under the cap that touches the tile,
+//                            whole).  In LDS, by region position: the bitmaps W (run bytes below n_owned), D (lead
+//                            bytes), K (bytes whose byte id is kept), V (W and the lead bytes that belong to a word), P
+//                            (part starts: all ones until a merge clears a boundary) and E (starts of parts of two or
+//                            more bytes whose id is kept); FIRST, the index of the first record of every position in
+//                            its own tile's run (one lane per record over the runs of the up to three tiles the region
+//                            touches, each clipped to the region by two binary searches); and a cached candidate rank
+//                            per boundary (uint32, all ones = none).  The run starts up to the tile's end are listed and
+//                            dealt to the lanes, one word per lane at a time: the cache is filled for every adjacent
+//                            pair of bytes, then the loop takes the first minimum of the word's boundaries (the leftmost
+//                            of equal ranks), clears that bit of P and looks the two neighbouring boundaries up again.
+//                            A lookup walks the records of position l in ascending length until L_s >= r - l and
+//                            gathers the piece as one int4.  Words are disjoint: only the bitmap words two of them
+//                            share need atomics.  At the end the lane walks its parts and sets E; one wave derives the
+//                            tile's emitting positions and keeps V, P, the emit bitmap, its prefixes and the count.
+//   pfac_ug_group_kernel, pfac_scan_groups_kernel, pfac_offsets_check_kernel, pfac_tk_doc_kernel: unchanged
+//   pfac_bpe_docs_kernel     pfac_wp_docs_kernel with the lead rule: between a lead and its run is inside the word
+//   pfac_bpe_write_kernel    pfac_ug_write_kernel's staging and stores.  Byte tokens first; then a lane per bitmap word
+//                            over its starts of parts of two or more bytes: the part runs to the next bit of P | ~V (in
+//                            the next tile's maps where it straddles), its id is that of the record (p, L).
+constexpr int BPE_THREADS = 4 * WAVE;
+constexpr int BPE_MAPS = 2;                         // V, P
+constexpr int BPE_EXT = 256;                        // the region's overhang: more than the largest cap
+constexpr unsigned BPE_NONE = ~0u;                  // no record / no candidate
+
+// the highest set bit below position k (k > 0) and the lowest at or above k of an LDS bitmap of nw words
+__device__ __forceinline__ unsigned bpe_prev(const volatile unsigned long long *m, unsigned k) {
+    unsigned x = (k - 1u) >> 6;
+    const unsigned q = (k - 1u) & 63u;
+    unsigned long long v = m[x] & (q == 63u ? ~0ull : tk_below(q + 1u));
+    while (!v && x > 0u) v = m[--x];
+    return v ? x * 64u + 63u - (unsigned)__builtin_clzll(v) : 0u;
+}
+__device__ __forceinline__ unsigned bpe_next(const volatile unsigned long long *m, unsigned k, unsigned nw) {
+    unsigned x = k >> 6;
+    unsigned long long v = m[x] & ~tk_below(k & 63u);
+    while (!v && x + 1u < nw) v = m[++x];
+    return v ? x * 64u + (unsigned)__builtin_ctzll(v) : nw * 64u;
+}
+
+template <int BYTES>
+__global__ void __launch_bounds__(BPE_THREADS)
+pfac_bpe_solve_kernel(const void *rec, const unsigned long long *tix, unsigned long long n_tix, unsigned long long cap,
+                      const unsigned char *in, unsigned long long n_avail, unsigned long long n_owned, const short *flen,
+                      const int4 *pieces, const int *btok, unsigned num_final, int lead, unsigned max_word, WordSet ws,
+                      unsigned long long *maps, unsigned long long *bm, unsigned short *wpre, unsigned *tcnt) {
+    constexpr unsigned R = WTILE + 2 * BPE_EXT, RW = R / 64;
+    __shared__ unsigned s_first[R];
+    __shared__ unsigned s_rank[R];
+    __shared__ unsigned short s_list[R / 2 + 64];
+    __shared__ unsigned long long s_W[RW], s_D[RW], s_K[RW], s_V[RW], s_P[RW], s_E[RW];
+    __shared__ unsigned long long s_rbase[3];
+    __shared__ unsigned s_rcnt[3], s_rlo[3], s_rhi[3];
+    __shared__ unsigned s_n;
+    const unsigned tid = threadIdx.x;
+    const int lane = (int)(tid & (WAVE - 1));
+    const unsigned long long t = blockIdx.x;
+    const unsigned long long tile_lo = t * WTILE;
+    const unsigned off0 = t ? (unsigned)BPE_EXT : 0u;               // the tile's first position in the region
+    const unsigned long long reg_lo = tile_lo - off0, T0 = reg_lo >> 12;
+    WordSet kv;                                                     // the bytes whose byte id is kept
+#pragma unroll
+    for (int k = 0; k < 4; k++) kv.w[k] = __ballot(btok[k * WAVE + lane] >= 0);
+    if (tid == 0) s_n = 0u;
+    if (tid < 3u) {                                                 // the runs the region touches, clipped to it
+        const unsigned long long tt = T0 + tid;
+        const UgRun run = ug_run_of(tix, n_tix, cap, tt);
+        const auto lower = [&](unsigned long long g) {              // the first record at or behind g
+            unsigned lo = 0u, hi = run.cnt;
+            while (lo < hi) {
+                const unsigned m = lo + (hi - lo) / 2u;
+                unsigned p, s;
+                heap_record<BYTES>(rec, run.base + m, tt, p, s);
+                if ((unsigned long long)p < g) lo = m + 1u;
+                else hi = m;
+            }
+            return lo;
+        };
+        s_rbase[tid] = run.base;
+        s_rcnt[tid] = run.cnt;
+        s_rlo[tid] = lower(reg_lo);
+        s_rhi[tid] = lower(reg_lo + R);
+    }
+    for (unsigned c = tid; c < R / 16; c += BPE_THREADS) {
+        const unsigned long long g = reg_lo + c * 16ull;
+        const unsigned dom = tk_domain16(g, 0ull, n_owned);
+        unsigned wb = 0u, kb = 0u, db = 0u;
+        if (dom) {
+            const uint4 v = tk_load16(in, g, n_avail);
+            const auto four = [&](unsigned q, int at) {
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    const int byte = (int)((q >> (8 * i)) & 255u);
+                    wb |= (unsigned)word_byte(ws, byte) << (at + i);
+                    kb |= (unsigned)word_byte(kv, byte) << (at + i);
+                    db |= (unsigned)(byte == lead) << (at + i);
+                }
+            };
+            four(v.x, 0);
+            four(v.y, 4);
+            four(v.z, 8);
+            four(v.w, 12);
+        }
+        reinterpret_cast<unsigned short *>(s_W)[c] = (unsigned short)(wb & dom);
+        reinterpret_cast<unsigned short *>(s_K)[c] = (unsigned short)(kb & dom);
+        reinterpret_cast<unsigned short *>(s_D)[c] = (unsigned short)(db & dom);
+    }
+    for (unsigned r = tid; r < R; r += BPE_THREADS) s_first[r] = BPE_NONE;
+    __syncthreads();
+    for (unsigned x = tid; x < RW; x += BPE_THREADS) {
+        const unsigned long long W = s_W[x];
+        // a start: a run byte with none in front of it; what lies in front of the region is not known (taken as one)
+        const unsigned long long top = x ? s_W[x - 1] >> 63 : (reg_lo ? 1ull : 0ull);
+        unsigned long long st = W & ~(W << 1 | top);
+        const unsigned long long nst0 = x + 1u < RW ? s_W[x + 1] & 1ull & ~(W >> 63) : 0ull;
+        s_V[x] = W | (((st >> 1) | (nst0 << 63)) & s_D[x]);         // the lead byte in front of a start belongs to its word
+        s_P[x] = ~0ull;
+        s_E[x] = 0ull;
+        // the words that start behind the tile are not its own; a run that starts right behind it may have its lead inside
+        if (x * 64u > off0 + WTILE) st = 0ull;
+        else if (x * 64u == off0 + WTILE) st &= 1ull;
+        while (st) {
+            const unsigned b = (unsigned)__builtin_ctzll(st);
+            st &= st - 1ull;
+            s_list[atomicAdd(&s_n, 1u)] = (unsigned short)(x * 64u + b);
+        }
+    }
+    for (unsigned ti = 0; ti < 3u; ti++) {                          // the first record of every region position
+        const unsigned long long tt = T0 + ti, base = s_rbase[ti];
+        const unsigned hi = s_rhi[ti];
+        for (unsigned k = s_rlo[ti] + tid; k < hi; k += BPE_THREADS) {
+            unsigned p, s, pp = ~0u, ps;
+            heap_record<BYTES>(rec, base + k, tt, p, s);
+            if (k) heap_record<BYTES>(rec, base + k - 1u, tt, pp, ps);
+            const unsigned long long rp = (unsigned long long)p - reg_lo;
+            if (p != pp && rp < R) s_first[(unsigned)rp] = k;
+        }
+    }
+    __syncthreads();
+    // the state of the record (l, len), or BPE_NONE: the records of a position ascend in length
+    const auto find = [&](unsigned l, unsigned len) -> unsigned {
+        unsigned k = s_first[l];
+        if (k == BPE_NONE) return BPE_NONE;
+        const unsigned long long gl = reg_lo + l, tt = gl >> 12;
+        const unsigned ti = (unsigned)(tt - T0);
+        const unsigned long long base = s_rbase[ti];
+        const unsigned cnt = s_rcnt[ti];
+        for (; k < cnt; k++) {
+            unsigned p, s;
+            heap_record<BYTES>(rec, base + k, tt, p, s);
+            if ((unsigned long long)p != gl) break;
+            if (s >= num_final) continue;
+            const int L = flen[s];
+            if (L < (int)len) continue;
+            return L == (int)len ? s : BPE_NONE;
+        }
+        return BPE_NONE;
+    };
+    // the rank of the candidate [l, k) + [k, r), or BPE_NONE
+    const auto cand = [&](unsigned l, unsigned k, unsigned r) -> unsigned {
+        const unsigned s = find(l, r - l);
+        if (s == BPE_NONE) return BPE_NONE;
+        const int4 pc = pieces[s];
+        return (pc.z == 0 || (unsigned)pc.z == k - l) ? (unsigned)pc.y : BPE_NONE;
+    };
+    const unsigned n_words = s_n;
+    for (unsigned w = tid; w < n_words; w += BPE_THREADS) {
+        const unsigned a0 = s_list[w];
+        unsigned b = R;                                             // the run's end: the first 0 of W behind a0
+        {
+            unsigned x = a0 >> 6;
+            unsigned long long inv = ~s_W[x] & ~tk_below(a0 & 63u);
+            while (!inv && x + 1u < RW && (x + 1u) * 64u <= a0 + max_word) inv = ~s_W[++x];
+            if (inv) b = x * 64u + (unsigned)__builtin_ctzll(inv);
+        }
+        const unsigned a = a0 > 0u && (s_D[(a0 - 1u) >> 6] >> ((a0 - 1u) & 63u) & 1ull) ? a0 - 1u : a0;
+        // over the cap (single bytes, as P stands), in front of the tile, behind it, or one byte: nothing to merge
+        if (b - a > max_word || b <= off0 || a >= off0 + WTILE || b - a < 2u) continue;
+        for (unsigned k = a + 1u; k < b; k++) s_rank[k] = cand(k - 1u, k, k + 1u);
+        for (;;) {
+            unsigned best = BPE_NONE, at = 0u;
+            for (unsigned k = a + 1u; k < b; k++) {
+                const unsigned r = s_rank[k];
+                if (r < best) {
+                    best = r;
+                    at = k;
+                }
+            }
+            if (best == BPE_NONE) break;
+            atomicAnd(&s_P[at >> 6], ~(1ull << (at & 63u)));
+            s_rank[at] = BPE_NONE;
+            const unsigned l = bpe_prev(s_P, at), r = bpe_next(s_P, at + 1u, RW);
+            if (l > a) s_rank[l] = cand(bpe_prev(s_P, l), l, r);
+            if (r < b) s_rank[r] = cand(l, r, bpe_next(s_P, r + 1u, RW));
+        }
+        for (unsigned l = a; l < b;) {                              // the parts of two or more bytes whose id is kept
+            const unsigned r = bpe_next(s_P, l + 1u, RW);
+            if (r - l >= 2u) {
+                const unsigned s = find(l, r - l);
+                if (s != BPE_NONE && pieces[s].x >= 0) atomicOr(&s_E[l >> 6], 1ull << (l & 63u));
+            }
+            l = r;
+        }
+    }
+    __syncthreads();
+    if (tid < WAVE) {
+        const unsigned x = off0 / 64u + (unsigned)lane;
+        const unsigned long long V = s_V[x], P = s_P[x], K = s_K[x], E = s_E[x];
+        const unsigned long long Vn = V >> 1 | s_V[x + 1] << 63, Pn = P >> 1 | s_P[x + 1] << 63;
+        const unsigned long long multi = V & P & Vn & ~Pn;          // a part start with a byte of its part behind it
+        const unsigned long long word = (~(V & ~P) & ~multi & K) | (multi & E);
+        const unsigned c = (unsigned)__popcll(word), incl = wave_incl_scan(c);
+        unsigned long long *m = maps + t * (BPE_MAPS * TK_WORDS);
+        m[lane] = V;
+        m[TK_WORDS + lane] = P;
+        bm[t * TK_WORDS + (unsigned)lane] = word;
+        wpre[t * TK_WORDS + (unsigned)lane] = (unsigned short)(incl - c);
+        if (lane == WAVE - 1) tcnt[t] = incl;
+    }
+}
+
+// every document offset outside every word (three byte loads per offset, all below n_owned): between two run bytes, or
+// between a lead byte and the run behind it, is inside; else bit 1 of *err
+__global__ void pfac_bpe_docs_kernel(const unsigned long long *off, unsigned long long n_docs, unsigned long long n_owned,
+                                     const unsigned char *in, WordSet ws, int lead, unsigned long long *err) {
+    const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
+    bool bad = false;
+    for (unsigned long long d = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; d <= n_docs; d += stride) {
+        const unsigned long long o = off[d];
+        if (o > 0 && o < n_owned) {
+            const int front = (int)in[o - 1];
+            bad |= word_byte(ws, (int)in[o]) && (word_byte(ws, front) || front == lead);
+        }
+    }
+    if (bad) atomicOr(err, 2ull);
+}
+
+template <int BYTES, bool POS>
+__global__ void __launch_bounds__(WAVE)
+pfac_bpe_write_kernel(const void *rec, const unsigned long long *tix, unsigned long long n_tix, unsigned long long cap,
+                      const unsigned char *in, unsigned long long n_avail, const short *flen, const int4 *pieces,
+                      const int *btok, unsigned num_final, const unsigned long long *maps, unsigned long long n_tiles,
+                      const unsigned long long *bm, const unsigned short *wpre, const unsigned *tpre,
+                      const unsigned long long *gpre, int *ids, unsigned *pos) {
+    __shared__ int s_btok[256];
+    __shared__ unsigned long long s_bm[TK_WORDS], s_v[TK_WORDS], s_p[TK_WORDS];
+    __shared__ unsigned short s_pre[TK_WORDS];
+    __shared__ __attribute__((aligned(16))) unsigned s_first[WTILE];
+    __shared__ __attribute__((aligned(16))) int s_ids[TK_STAGE];
+    __shared__ __attribute__((aligned(16))) unsigned s_pos[POS ? TK_STAGE : 4];
+    const int lane = threadIdx.x;
+    const unsigned long long t = blockIdx.x;
+    const unsigned long long word = bm[t * TK_WORDS + (unsigned)lane];
+    const unsigned wp = wpre[t * TK_WORDS + (unsigned)lane];
+    const unsigned cnt = bcast_last(wp + (unsigned)__popcll(word));
+    if (cnt == 0) return;                                           // (wave-uniform)
+    const unsigned long long base = gpre[t / TK_GROUP] + tpre[t];
+    const unsigned a = (unsigned)(base & 3ull);
+    const unsigned long long tile_lo = t * WTILE;
+    const unsigned long long *m = maps + t * (BPE_MAPS * TK_WORDS), *mn = m + BPE_MAPS * TK_WORDS;
+    const bool more = t + 1 < n_tiles;                              // (else mn is not there)
+    s_bm[lane] = word;
+    s_v[lane] = m[lane];
+    s_p[lane] = m[TK_WORDS + lane];
+    s_pre[lane] = (unsigned short)wp;
+#pragma unroll
+    for (int i = 0; i < 4; i++) s_btok[i * WAVE + lane] = btok[i * WAVE + lane];
+#pragma unroll
+    for (int i = 0; i < WTILE / (4 * WAVE); i++)
+        *reinterpret_cast<uint4 *>(&s_first[(i * WAVE + lane) * 4]) = make_uint4(~0u, ~0u, ~0u, ~0u);
+    wave_lds_sync();
+#pragma unroll
+    for (int j = 0; j < SUBS; j++) {                                // the byte tokens, in rank order (a part start's is replaced below)
+        const unsigned lp = (unsigned)j * SUB + (unsigned)lane * 16u, sh = lp & 63u;
+        const unsigned long long wv = s_bm[lp >> 6];
+        const unsigned e = (unsigned)(wv >> sh) & 0xffffu;
+        if (!e) continue;
+        unsigned rank = a + s_pre[lp >> 6] + (unsigned)__popcll(wv & tk_below(sh));
+        const uint4 v = tk_load16(in, tile_lo + lp, n_avail);
+        const unsigned q[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int c = 0; c < 16; c++) {
+            if (e >> c & 1u) {
+                s_ids[rank] = s_btok[(q[c >> 2] >> (8 * (c & 3))) & 255u];
+                if constexpr (POS) s_pos[rank] = (unsigned)(tile_lo + lp + (unsigned)c);
+                rank++;
+            }
+        }
+    }
+    const UgRun run = ug_run_of(tix, n_tix, cap, t);
+    for (unsigned k = (unsigned)lane; k < run.cnt; k += WAVE) {     // the first record of every position
+        unsigned p, s, pp = ~0u, ps;
+        heap_record<BYTES>(rec, run.base + k, t, p, s);
+        if (k) heap_record<BYTES>(rec, run.base + k - 1u, t, pp, ps);
+        if (p != pp && (unsigned long long)p >= tile_lo && (unsigned long long)p < tile_lo + WTILE) s_first[p - (unsigned)tile_lo] = k;
+    }
+    wave_lds_sync();
+    const unsigned long long V = s_v[lane], P = s_p[lane];
+    const unsigned long long nV = lane + 1 < TK_WORDS ? s_v[lane + 1] : (more ? mn[0] : 0ull);
+    const unsigned long long nP = lane + 1 < TK_WORDS ? s_p[lane + 1] : (more ? mn[TK_WORDS] : ~0ull);
+    unsigned long long pw = V & P & (V >> 1 | nV << 63) & ~(P >> 1 | nP << 63) & word;    // this word's starts of parts of >= 2 bytes
+    while (pw) {
+        const unsigned q = (unsigned)__builtin_ctzll(pw), lp = (unsigned)lane * 64u + q;
+        pw &= pw - 1ull;
+        unsigned y = (unsigned)lane;                                // the part's end: the next bit of P | ~V
+        unsigned long long cur = (s_p[y] | ~s_v[y]) & (q == 63u ? 0ull : ~0ull << (q + 1u));
+        while (!cur && y < TK_WORDS + BPE_EXT / 64u) {
+            y++;
+            if (y < (unsigned)TK_WORDS) cur = s_p[y] | ~s_v[y];
+            else if (more) cur = mn[TK_WORDS + (y - TK_WORDS)] | ~mn[y - TK_WORDS];
+            else cur = ~0ull;
+        }
+        const unsigned L = cur ? y * 64u + (unsigned)__builtin_ctzll(cur) - lp : 0u;
+        int v = PFAC_TOKEN_DROP;                                    // (no such record: not an id, so a caller would see it)
+        for (unsigned k = s_first[lp]; k < run.cnt; k++) {          // the record (p, L): at most one per length
+            unsigned p, s;
+            heap_record<BYTES>(rec, run.base + k, t, p, s);
+            if (p != (unsigned)tile_lo + lp) break;
+            if (s < num_final && (unsigned)flen[s] == L) {
+                v = pieces[s].x;
+                break;
+            }
+        }
+        const unsigned rank = a + s_pre[lane] + (unsigned)__popcll(word & tk_below(q));
+        s_ids[rank] = v;
+        if constexpr (POS) s_pos[rank] = (unsigned)tile_lo + lp;
+    }
+    wave_lds_sync();
+    const unsigned long long g0 = base - a;                         // a multiple of 4: ids + g0 is 16-B aligned
+    for (unsigned c = (unsigned)lane; c * 4u < a + cnt; c += WAVE) {
+        const unsigned s0 = c * 4u;
+        if (s0 >= a && s0 + 4u <= a + cnt) {
+            *reinterpret_cast<uint4 *>(ids + g0 + s0) = *reinterpret_cast<const uint4 *>(&s_ids[s0]);
+            if constexpr (POS) *reinterpret_cast<uint4 *>(pos + g0 + s0) = *reinterpret_cast<const uint4 *>(&s_pos[s0]);
+        } else {
+            for (unsigned x = s0; x < s0 + 4u; x++) {
+                if (x >= a && x < a + cnt) {
+                    ids[g0 + x] = s_ids[x];
+                    if constexpr (POS) pos[g0 + x] = s_pos[x];
+                }
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Proximity rules (pfac_documents_near): bit r of mask[d] is set iff document d holds two distinct records i < j, at
 // most max_dist bytes apart by their starts, that are an (A_r, B_r) pair -- in either order unless the rule is ordered.
 // With a maximum distance only, the nearest earlier A (or B) is the best partner a record can have, so the pass needs
@@ -6574,6 +6925,9 @@ struct Slot {
     // pfac_unigram_records / pfac_unigram_documents (bm, wpre, tpre and the three outputs are the tokenizer's)
     DevBuf<unsigned long long> ug_maps;   // per tile: W, S, B (3 x 64 words)
     uint64_t ug_gen = 0;                  // the attachment the slot's token result was made under (pfac_ctx::ug_gen; 0: another pass)
+    // pfac_bpe_records / pfac_bpe_documents (bm, wpre, tpre and the three outputs are the tokenizer's)
+    DevBuf<unsigned long long> bpe_maps;  // per tile: V, P (2 x 64 words)
+    uint64_t bpe_gen = 0;                 // the attachment the slot's token result was made under (pfac_ctx::bpe_gen; 0: another pass)
 };
 
 struct StageLayout {                      // per-wave LDS of one staging mode
@@ -6659,6 +7013,12 @@ struct pfac_ctx {
     unsigned ug_max = 0;                  // ... the longest word with piece edges, in bytes, ...
     WordSet ug_ws{};                      // ... and the word bytes
     uint64_t ug_gen = 0;                  // attachments made so far
+    DevBuf<int4> bpe_pieces;              // BPE (pfac_table_set_bpe): (id, rank, split, 0) of every final state, ...
+    DevBuf<int> bpe_btok;                 // ... the id of every byte value, ...
+    int bpe_lead = -1;                    // ... the byte in front of a run that belongs to its word (or -1), ...
+    unsigned bpe_max = 0;                 // ... the longest word that is merged, in bytes, ...
+    WordSet bpe_ws{};                     // ... and the word bytes
+    uint64_t bpe_gen = 0;                 // attachments made so far
     DevBuf<unsigned> ru_sptr;             // the rule table, state-major (pfac_table_set_rules): state_ptr[num_final + 1], ...
     DevBuf<unsigned> ru_ent;              // ... the entries rule << 1 | negated, the rules ascending inside a state, ...
     DevBuf<unsigned> ru_need;             // ... and need[n_rules]
@@ -7247,6 +7607,7 @@ int install_table(pfac_ctx *ctx, const int *d_blob, const int32_t *hdr, size_t n
     ctx->tok.reset(); ctx->btok.reset();                    // ... and the token ids
     ctx->wp_ids.reset(); ctx->wp_btok.reset();              // ... and the WordPiece ids
     ctx->ug_pieces.reset(); ctx->ug_btok.reset();           // ... and the Unigram pieces
+    ctx->bpe_pieces.reset(); ctx->bpe_btok.reset();         // ... and the BPE pieces
     ctx->ru_sptr.reset(); ctx->ru_ent.reset(); ctx->ru_need.reset(); ctx->ru_n = ctx->ru_terms = 0;     // ... and the rules
     ctx->have_table = false; ctx->table_gen++;
     TablePlan P;
@@ -9773,6 +10134,7 @@ static int tk_run(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *d_i
     s.tk_pos.invalidate();
     s.tk_off.invalidate();
     s.ug_gen = 0;
+    s.bpe_gen = 0;
     if (!s.scanned || !s.ll_out.done || s.ll_seq != s.scan_seq || (docs && !s.ll_docs))
         return fail(ctx, PFAC_E_STATE, fn + (docs ? " needs a pfac_records_leftmost_longest_documents since the slot's last scan"
                                                   : " needs a pfac_records_leftmost_longest since the slot's last scan"));
@@ -10005,6 +10367,7 @@ static int wp_run(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *d_i
     s.tk_pos.invalidate();
     s.tk_off.invalidate();
     s.ug_gen = 0;
+    s.bpe_gen = 0;
     if (!s.scanned || !s.ll_out.done || s.ll_seq != s.scan_seq || (docs && !s.ll_docs))
         return fail(ctx, PFAC_E_STATE, fn + (docs ? " needs a pfac_records_leftmost_longest_documents since the slot's last scan"
                                                   : " needs a pfac_records_leftmost_longest since the slot's last scan"));
@@ -10208,6 +10571,7 @@ static int ug_run(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *d_i
     s.tk_pos.invalidate();
     s.tk_off.invalidate();
     s.ug_gen = 0;
+    s.bpe_gen = 0;
     int rc = last_scan_usable(ctx, s, fn, SCAN_FINISHED | SCAN_LENGTHS | SCAN_TABLE);
     if (rc) return rc;
     if (!ctx->ug_pieces.p) return fail(ctx, PFAC_E_STATE, fn + ": no Unigram pieces for the uploaded table (pfac_table_set_unigram)");
@@ -10338,6 +10702,199 @@ int pfac_unigram_documents(pfac_ctx *ctx, int slot, const void *d_input, const v
     *n_tokens = 0;
     const UgDocs docs{d_doc_offsets, n_docs, d_tok_offsets};
     return ug_run(ctx, ctx->slots[slot], "pfac_unigram_documents", d_input, d_records, flags, d_ids, out_cap, d_pos, n_tokens, &docs);
+}
+
+// The BPE attachment: checked whole, made aside, swapped in together, as the Unigram one is; it leaves the other three
+// attachments alone.
+int pfac_table_set_bpe(pfac_ctx *ctx, const pfac_bpe_piece *pieces, uint64_t n_states, const int32_t *byte_ids,
+                       const uint64_t word_set[4], int32_t lead, uint32_t max_word_bytes) {
+    if (!ctx) return fail(nullptr, PFAC_E_ARG, "null context");
+    const std::string fn = "pfac_table_set_bpe";
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (!ctx->have_table) return fail(ctx, PFAC_E_STATE, fn + " before a table upload");
+    if (n_states != (uint64_t)ctx->plan.base.num_final || (!pieces && n_states))
+        return fail(ctx, PFAC_E_ARG, fn + ": need num_final pieces (num_final " + std::to_string(ctx->plan.base.num_final) + ")");
+    if (max_word_bytes < 1 || max_word_bytes > 255) return fail(ctx, PFAC_E_ARG, fn + ": max_word_bytes must lie in 1..255");
+    std::vector<int4> quads(std::max<uint64_t>(n_states, 1), make_int4(PFAC_TOKEN_DROP, 0, 0, 0));
+    for (uint64_t i = 0; i < n_states; i++) {
+        const pfac_bpe_piece &p = pieces[i];
+        if (p.id < PFAC_TOKEN_DROP)
+            return fail(ctx, PFAC_E_ARG, fn + ": the id of final state " + std::to_string(i) + " is neither >= 0 nor PFAC_TOKEN_DROP");
+        if (p.rank < 0) return fail(ctx, PFAC_E_ARG, fn + ": the rank of final state " + std::to_string(i) + " is negative");
+        if (p.reserved) return fail(ctx, PFAC_E_ARG, fn + ": the reserved field of final state " + std::to_string(i) + " is not 0");
+        quads[i] = make_int4(p.id, p.rank, (int)p.split, 0);
+    }
+    int32_t bytes[256];
+    for (int b = 0; b < 256; b++) {
+        bytes[b] = byte_ids ? byte_ids[b] : PFAC_TOKEN_DROP;
+        if (bytes[b] < PFAC_TOKEN_DROP)
+            return fail(ctx, PFAC_E_ARG, fn + ": the id of byte " + std::to_string(b) + " is neither >= 0 nor PFAC_TOKEN_DROP");
+    }
+    WordSet ws;
+    for (int k = 0; k < 4; k++)                              // NULL: everything but \t \n \v \f \r and space
+        ws.w[k] = word_set ? word_set[k] : (k == 0 ? ~0x0000000100003E00ull : ~0ull);
+    if (lead < -1 || lead > 255) return fail(ctx, PFAC_E_ARG, fn + ": lead must be a byte value or -1");
+    if (lead >= 0 && (ws.w[lead >> 6] >> (lead & 63) & 1ull)) return fail(ctx, PFAC_E_ARG, fn + ": the lead byte is a word byte");
+    USE_DEVICE(ctx);
+    DevBuf<int4> dp;
+    DevBuf<int> btok;
+    int rc = dp.ensure(ctx, nullptr, quads.size(), quads.size());
+    if (!rc) rc = btok.ensure(ctx, nullptr, 256, 256);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpy(dp.p, quads.data(), quads.size() * sizeof(int4), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(btok.p, bytes, sizeof bytes, hipMemcpyHostToDevice));
+    ctx->bpe_pieces = std::move(dp);                        // (a swap: the old buffers go with the two locals)
+    ctx->bpe_btok = std::move(btok);
+    ctx->bpe_lead = lead;
+    ctx->bpe_max = max_word_bytes;
+    ctx->bpe_ws = ws;
+    ctx->bpe_gen++;
+    for (auto &sl : ctx->slots) {                            // a slot-owned result of the earlier attachment is stale
+        if (!sl.bpe_gen) continue;
+        sl.tk_ids.invalidate();
+        sl.tk_pos.invalidate();
+        sl.tk_off.invalidate();
+        sl.bpe_gen = 0;
+    }
+    return PFAC_OK;
+}
+
+// ug_run's sibling: the same ladder, buffers and outputs, the BPE kernels between them
+static int bpe_run(pfac_ctx *ctx, Slot &s, const std::string &fn, const void *d_input, const void *d_records, uint32_t flags,
+                   int32_t *d_ids, uint64_t out_cap, uint32_t *d_pos, uint64_t *n_tokens, const UgDocs *docs) {
+    s.tk_ids.invalidate();
+    s.tk_pos.invalidate();
+    s.tk_off.invalidate();
+    s.ug_gen = 0;
+    s.bpe_gen = 0;
+    int rc = last_scan_usable(ctx, s, fn, SCAN_FINISHED | SCAN_LENGTHS | SCAN_TABLE);
+    if (rc) return rc;
+    if (!ctx->bpe_pieces.p) return fail(ctx, PFAC_E_STATE, fn + ": no BPE pieces for the uploaded table (pfac_table_set_bpe)");
+    if (s.last_used > s.last_cap) return fail(ctx, PFAC_E_STATE, fn + ": the slot's last scan overflowed its record heap: scan again with a larger one");
+    if (!d_records && (const void *)s.records.p != s.last_records)
+        return fail(ctx, PFAC_E_STATE, fn + ": the slot's record heap was replaced since its last scan");
+    if (!d_input && s.last_avail > s.input.cap)
+        return fail(ctx, PFAC_E_STATE, fn + ": the slot's input buffer was replaced since its last scan");
+    const bool want_pos = flags & PFAC_TOKENS_POSITIONS;
+    if (flags & ~PFAC_TOKENS_POSITIONS) return fail(ctx, PFAC_E_ARG, fn + ": unknown flags");
+    if (d_pos && !want_pos) return fail(ctx, PFAC_E_ARG, fn + ": d_pos without PFAC_TOKENS_POSITIONS");
+    const void *heap = d_records ? d_records : (const void *)s.records.p;
+    if (heap != s.last_records) return fail(ctx, PFAC_E_ARG, fn + ": d_records is not the record heap of the slot's last scan");
+    const unsigned char *in = d_input ? static_cast<const unsigned char *>(d_input) : s.input.p;
+    const uint64_t n_owned = s.last_owned, n_avail = s.last_avail;
+    if (((uintptr_t)d_ids & 15) || ((uintptr_t)d_pos & 15) || ((uintptr_t)in & 15))
+        return fail(ctx, PFAC_E_ARG, fn + ": misaligned buffer (d_input, d_ids and d_pos 16 B)");
+    if (n_owned && !in) return fail(ctx, PFAC_E_ARG, fn + ": no input buffer");
+    const unsigned long long *doff = nullptr;
+    unsigned long long *dtok_off = nullptr;
+    uint64_t n_docs = 0;
+    if (docs) {
+        n_docs = docs->n_docs;
+        dtok_off = reinterpret_cast<unsigned long long *>(docs->tok_off);
+        rc = resolve_docs(ctx, s, fn, docs->off, n_docs, (uintptr_t)dtok_off, &doff);
+        if (rc) return rc;
+        if (((uintptr_t)doff & 7) || ((uintptr_t)dtok_off & 7)) return fail(ctx, PFAC_E_ARG, fn + ": device buffers must be 8-byte aligned");
+    }
+    USE_DEVICE(ctx);
+    const uint64_t n_tiles = (n_owned + WTILE - 1) / WTILE, n_groups = (n_tiles + TK_GROUP - 1) / TK_GROUP;
+    const unsigned oblocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_docs + 1 + 255) / 256, 65536));
+    const int rb = s.last_rec_bytes;
+    uint64_t nt = 0;
+    if (n_tiles) {
+        rc = s.tk_bm.ensure(ctx, s.stream, n_tiles * TK_WORDS, quarter_more(n_tiles) * TK_WORDS);
+        if (!rc) rc = s.tk_wpre.ensure(ctx, s.stream, n_tiles * TK_WORDS, quarter_more(n_tiles) * TK_WORDS);
+        if (!rc) rc = s.tk_tpre.ensure(ctx, s.stream, n_tiles, quarter_more(n_tiles));
+        if (!rc) rc = s.bpe_maps.ensure(ctx, s.stream, n_tiles * BPE_MAPS * TK_WORDS, quarter_more(n_tiles) * BPE_MAPS * TK_WORDS);
+        if (!rc) rc = ensure_gsum(ctx, s, (unsigned)n_groups + 1);      // group prefixes, the total, error flags
+        if (rc) return rc;
+        unsigned long long *res = s.gsum.p + n_groups;
+        HIP_TRY(ctx, hipMemsetAsync(res, 0, 16, s.stream));
+        auto sk = by_width(rb, [](auto w) { return pfac_bpe_solve_kernel<w()>; });
+        hipLaunchKernelGGL(sk, dim3((unsigned)n_tiles), dim3(BPE_THREADS), 0, s.stream, heap, (const unsigned long long *)s.tile_index.p,
+                           (unsigned long long)s.last_tiles, (unsigned long long)s.last_cap, in, (unsigned long long)n_avail,
+                           (unsigned long long)n_owned, ctx->flen.p, (const int4 *)ctx->bpe_pieces.p, (const int *)ctx->bpe_btok.p,
+                           (unsigned)ctx->plan.base.num_final, ctx->bpe_lead, ctx->bpe_max, ctx->bpe_ws, s.bpe_maps.p, s.tk_bm.p,
+                           s.tk_wpre.p, s.tk_tpre.p);
+        hipLaunchKernelGGL(pfac_ug_group_kernel, dim3((unsigned)n_groups), dim3(WAVE), 0, s.stream, s.tk_tpre.p,
+                           (unsigned long long)n_tiles, s.gsum.p);
+        hipLaunchKernelGGL(pfac_scan_groups_kernel, dim3(1), dim3(1024), 0, s.stream, s.gsum.p, (unsigned)n_groups);
+        if (docs) {
+            hipLaunchKernelGGL(pfac_offsets_check_kernel, dim3(oblocks), dim3(256), 0, s.stream, doff, (unsigned long long)n_docs,
+                               (unsigned long long)n_owned, res + 1);
+            hipLaunchKernelGGL(pfac_bpe_docs_kernel, dim3(oblocks), dim3(256), 0, s.stream, doff, (unsigned long long)n_docs,
+                               (unsigned long long)n_owned, in, ctx->bpe_ws, ctx->bpe_lead, res + 1);
+        }
+        rc = pass_words(ctx, s, res, 2);
+        if (rc) return rc;
+        nt = host_u64(s, H_PASS);
+        if (host_u64(s, H_PASS1) & 1) return bad_doc_offsets(ctx, s, fn);
+        if (host_u64(s, H_PASS1) & 2) return fail(ctx, PFAC_E_ARG, fn + ": a document offset lies inside a word");
+    } else if (docs) {                                       // nothing owned: the offsets rule alone (every offset is 0)
+        rc = ensure_gsum(ctx, s, 1);
+        if (rc) return rc;
+        unsigned long long *res = s.gsum.p;
+        HIP_TRY(ctx, hipMemsetAsync(res, 0, 16, s.stream));
+        hipLaunchKernelGGL(pfac_offsets_check_kernel, dim3(oblocks), dim3(256), 0, s.stream, doff, (unsigned long long)n_docs,
+                           (unsigned long long)n_owned, res + 1);
+        rc = pass_words(ctx, s, res, 2);
+        if (rc) return rc;
+        if (host_u64(s, H_PASS1) & 1) return bad_doc_offsets(ctx, s, fn);
+    }
+    *n_tokens = nt;
+    if ((d_ids || d_pos) && nt > out_cap)
+        return fail(ctx, PFAC_E_OVERFLOW, fn + ": " + std::to_string(nt) + " tokens, out_cap is " + std::to_string(out_cap));
+    const uint64_t cap = align_up(nt + nt / 8, 1024);
+    int *ids = nullptr;
+    unsigned *pos = nullptr;
+    unsigned long long *toff = nullptr;
+    rc = s.tk_ids.bind(ctx, s.stream, d_ids, nt, cap, &ids);       // (everything allocated before the first write)
+    if (!rc && want_pos) rc = s.tk_pos.bind(ctx, s.stream, d_pos, nt, cap, &pos);
+    if (!rc && docs) rc = s.tk_off.bind(ctx, s.stream, dtok_off, n_docs + 1, docs_cap(n_docs), &toff);
+    if (rc) return rc;
+    if (nt) {
+        auto wk = by_width(rb, [want_pos](auto w) { return want_pos ? pfac_bpe_write_kernel<w(), true> : pfac_bpe_write_kernel<w(), false>; });
+        hipLaunchKernelGGL(wk, dim3((unsigned)n_tiles), dim3(WAVE), 0, s.stream, heap, (const unsigned long long *)s.tile_index.p,
+                           (unsigned long long)s.last_tiles, (unsigned long long)s.last_cap, in, (unsigned long long)n_avail, ctx->flen.p,
+                           (const int4 *)ctx->bpe_pieces.p, (const int *)ctx->bpe_btok.p, (unsigned)ctx->plan.base.num_final,
+                           (const unsigned long long *)s.bpe_maps.p, (unsigned long long)n_tiles, (const unsigned long long *)s.tk_bm.p,
+                           (const unsigned short *)s.tk_wpre.p, (const unsigned *)s.tk_tpre.p, (const unsigned long long *)s.gsum.p, ids, pos);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    if (docs) {
+        if (n_tiles) {
+            hipLaunchKernelGGL(pfac_tk_doc_kernel, dim3(oblocks), dim3(256), 0, s.stream, doff, (unsigned long long)n_docs,
+                               (unsigned long long)n_owned, (unsigned long long)n_tiles, (unsigned)n_groups, s.tk_bm.p,
+                               s.tk_wpre.p, s.tk_tpre.p, s.gsum.p, toff);
+            HIP_TRY(ctx, hipGetLastError());
+        } else {
+            HIP_TRY(ctx, hipMemsetAsync(toff, 0, (n_docs + 1) * 8, s.stream));
+        }
+        s.tk_off.commit(n_docs + 1, !dtok_off);
+    }
+    if (want_pos) s.tk_pos.commit(nt, !d_pos);
+    s.tk_ids.commit(nt, !d_ids);
+    s.bpe_gen = ctx->bpe_gen;
+    return PFAC_OK;
+}
+
+int pfac_bpe_records(pfac_ctx *ctx, int slot, const void *d_input, const void *d_records, uint32_t flags, int32_t *d_ids,
+                     uint64_t out_cap, uint32_t *d_pos, uint64_t *n_tokens) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    if (!n_tokens) return fail(ctx, PFAC_E_ARG, "null argument");
+    *n_tokens = 0;
+    return bpe_run(ctx, ctx->slots[slot], "pfac_bpe_records", d_input, d_records, flags, d_ids, out_cap, d_pos, n_tokens, nullptr);
+}
+
+int pfac_bpe_documents(pfac_ctx *ctx, int slot, const void *d_input, const void *d_records, const uint64_t *d_doc_offsets,
+                       uint64_t n_docs, uint32_t flags, int32_t *d_ids, uint64_t out_cap, uint32_t *d_pos,
+                       uint64_t *d_tok_offsets, uint64_t *n_tokens) {
+    int rc = check_slot(ctx, slot);
+    if (rc) return rc;
+    if (!n_tokens) return fail(ctx, PFAC_E_ARG, "null argument");
+    *n_tokens = 0;
+    const UgDocs docs{d_doc_offsets, n_docs, d_tok_offsets};
+    return bpe_run(ctx, ctx->slots[slot], "pfac_bpe_documents", d_input, d_records, flags, d_ids, out_cap, d_pos, n_tokens, &docs);
 }
 
 int pfac_fill_tiled(pfac_ctx *ctx, int slot, void *d_dst, uint64_t n, const void *host_pattern, uint32_t period, uint64_t phase) {

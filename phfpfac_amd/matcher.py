@@ -23,6 +23,7 @@ from ._ffi import PFAC_TOKENS_POSITIONS
 from ._ffi import PFAC_NEAR_SELECTION
 from ._ffi import PFAC_E_STATE
 from .table import UNIGRAM_PIECE_DTYPE, UNIGRAM_SPACE
+from .table import BPE_PIECE_DTYPE
 from .table import NEAR_RULE_DTYPE, RECORD_DTYPE,SCORE_DTYPE, TEMPLATE_PLAIN, TOKEN_DROP, WORD_BYTES, PfacTable, redaction_table, replacement_table, template_table, token_table, _state_lengths
 
 
@@ -1776,6 +1777,112 @@ class GpuMatcher:
             raise ValueError("the delimiter is a word byte of the Unigram attachment")
         _, n_docs = self._scan_lines(data, delimiter, slot, fetch_offsets=False)
         return self._unigram_docs(None, n_docs, positions, slot)
+
+    # -- byte-level BPE: merges by rank over the record heap, per word --
+    def set_bpe(self, pieces, byte_ids, lead=0x20, word_bytes=None, max_word_bytes: int = 64) -> None:
+        """The BPE pieces of the uploaded table (``pfac_table_set_bpe``), as ``bpe_table`` returns them: ``pieces``
+        BPE_PIECE_DTYPE[num_final] (or int32[num_final, 4]): id, merge rank, split (the byte length of the merge's left
+        half, 0 = any) and 0 of every final state; ``byte_ids`` 256 entries (None = all dropped); ``lead`` the one byte
+        outside words that a word takes from in front of it (a byte value, a one-byte ``bytes``, or None / -1 for
+        none); ``word_bytes`` the bytes that make up words (None = every byte but ``\\t\\n\\v\\f\\r`` and space, or a
+        ``word_set`` array); ``max_word_bytes`` (1..255) the longest word that is merged at all.  Kept on the device
+        until the next table upload; the other token attachments stay as they are."""
+        pc = np.asarray(pieces)
+        if pc.dtype != BPE_PIECE_DTYPE:
+            pc = np.ascontiguousarray(pc, dtype=np.int32)
+            if pc.ndim != 2 or pc.shape[1] != 4:
+                raise ValueError("pieces holds four 32-bit fields per final state")
+        pc = np.ascontiguousarray(pc)
+        n = int(pc.shape[0])
+        bt = None
+        if byte_ids is not None:
+            bt = np.ascontiguousarray(byte_ids, dtype=np.int32).ravel()
+            if bt.shape != (256,):
+                raise ValueError("byte_ids holds 256 entries")
+        if word_bytes is None:
+            ws = None
+        elif isinstance(word_bytes, np.ndarray) and word_bytes.dtype == np.uint64:
+            ws = np.ascontiguousarray(word_bytes)
+            if ws.size != 4:
+                raise ValueError("a word set holds four 64-bit words")
+        else:
+            ws = word_set(word_bytes)
+        if lead is None:
+            lead = -1
+        elif not isinstance(lead, (int, np.integer)):
+            if len(bytes(lead)) != 1:
+                raise ValueError("the lead is one byte")
+            lead = bytes(lead)[0]
+        self._check(self._L.pfac_table_set_bpe(self._ctx, pc.ctypes.data if n else None, n, bt.ctypes.data if bt is not None else None,
+                                               ws.ctypes.data if ws is not None else None, int(lead), int(max_word_bytes)))
+        self._bpe_words = word_set(UNIGRAM_SPACE) if ws is None else ws.copy()
+        self._bpe_lead = int(lead)
+
+    def bpe_records(self, d_input=None, d_ids=None, out_cap: int = 0, d_pos=None, positions: bool = False, slot: int = 0,
+                    d_records=None) -> int:
+        """The BPE ids of the slot's last finished scan, straight from its record heap (``pfac_bpe_records``).
+        Arguments, result and overflow as ``unigram_records``; the slot-owned result is fetched with
+        ``tokens_to_host``."""
+        n = C.c_uint64(0)
+        flags = PFAC_TOKENS_POSITIONS if (positions or d_pos is not None) else 0
+        rc = self._L.pfac_bpe_records(self._ctx, slot, _ptr(d_input), _ptr(d_records), flags, _ptr(d_ids), int(out_cap),
+                                      _ptr(d_pos), C.byref(n))
+        return self._counted(rc, n, "n_tokens")
+
+    def bpe_records_documents(self, n_docs: int, d_input=None, d_ids=None, out_cap: int = 0, d_pos=None, positions: bool = False,
+                              d_tok_offsets=None, slot: int = 0, d_records=None, d_doc_offsets=None) -> int:
+        """``bpe_records`` plus the documents' token offsets (``pfac_bpe_documents``); ``d_doc_offsets`` None = the
+        slot's offsets, which must hold ``n_docs`` documents.  No document offset may lie inside a word, and between a
+        lead byte and its run is inside (else PfacError, PFAC_E_ARG)."""
+        n = C.c_uint64(0)
+        flags = PFAC_TOKENS_POSITIONS if (positions or d_pos is not None) else 0
+        rc = self._L.pfac_bpe_documents(self._ctx, slot, _ptr(d_input), _ptr(d_records), _ptr(d_doc_offsets), int(n_docs), flags,
+                                        _ptr(d_ids), int(out_cap), _ptr(d_pos), _ptr(d_tok_offsets), C.byref(n))
+        return self._counted(rc, n, "n_tokens")
+
+    def bpe(self, data, n_owned: Optional[int] = None, positions: bool = False, slot: int = 0):
+        """H2D + scan + BPE of one host buffer (``n_owned`` < len(data) leaves the rest as halo; cut there at a byte
+        outside words that is not a lead).  Returns ids, or (ids, pos) with ``positions``."""
+        buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data.view(np.uint8).ravel()
+        n_avail = int(buf.size)
+        n_owned = n_avail if n_owned is None else int(n_owned)
+        self._ensure_final_lengths()
+        self.reserve(slot, max(n_avail, 1), max(n_avail // 8, 4096))
+        if n_avail:
+            self.h2d(buf, slot)
+        self.scan_resident(n_owned, n_avail, slot=slot)
+        n = self.bpe_records(positions=positions, slot=slot)
+        return self.tokens_to_host(n, positions, slot)
+
+    def _bpe_docs(self, offsets, n_docs: int, positions: bool, slot: int):
+        n = self.bpe_records_documents(n_docs, positions=positions, slot=slot)
+        tok_off = self.token_offsets_to_host(n_docs, slot)
+        if not positions:
+            return self.tokens_to_host(n, False, slot), tok_off
+        ids, pos = self.tokens_to_host(n, True, slot)
+        if n:
+            if offsets is None:
+                offsets = self.doc_offsets_to_host(n_docs, slot)
+            doc = np.repeat(np.arange(n_docs, dtype=np.int64), np.diff(tok_off.astype(np.int64)))
+            pos -= offsets[doc].astype(np.uint32)
+        return ids, pos, tok_off
+
+    def bpe_documents(self, docs, positions: bool = False, slot: int = 0):
+        """BPE of a batch of documents (``docs`` as ``scan_documents`` takes it) in one scan.  No word may run across a
+        document end, and none may end on a lead byte whose run opens the next: PfacError (PFAC_E_ARG).  Returns what
+        ``tokenize_documents`` returns."""
+        offsets, n_docs = self._scan_docs(docs, slot)
+        return self._bpe_docs(offsets, n_docs, positions, slot)
+
+    def bpe_lines(self, data, delimiter=b"\n", positions: bool = False, slot: int = 0):
+        """``bpe_documents`` of one buffer cut into lines at ``delimiter`` on the device.  The delimiter must be neither
+        a word byte nor the lead (ValueError): a line then starts and ends outside every word by construction."""
+        d = _delimiter_byte(delimiter)
+        ws = getattr(self, "_bpe_words", None)
+        if ws is not None and 0 <= d <= 255 and ((int(ws[d >> 6]) >> (d & 63)) & 1 or d == self._bpe_lead):
+            raise ValueError("the delimiter is a word byte or the lead of the BPE attachment")
+        _, n_docs = self._scan_lines(data, delimiter, slot, fetch_offsets=False)
+        return self._bpe_docs(None, n_docs, positions, slot)
 
     # -- synthetic inputs (device resident) --------------------------------
     def fill_tiled(self, d_dst, n: int, pattern: bytes, phase: int = 0, slot: int = 0) -> None:

@@ -676,6 +676,120 @@ def unigram_table(vocab, prefix="▁", word_bytes=None, max_word_bytes: int = 10
     return table, pieces, scale, skipped
 
 
+BPE_PIECE_DTYPE = np.dtype([("id", "<i4"), ("rank", "<i4"), ("split", "<u4"), ("reserved", "<u4")])   # pfac_bpe_piece
+
+
+def bpe_byte_alphabet() -> dict:
+    """The printable alphabet of byte-level BPE vocabularies (GPT-2's): a byte whose Latin-1 character is printable
+    and not a space stands for itself, every other byte takes the code points 256, 257, ... in ascending order (so the
+    space is ``Ġ`` and the newline ``Ċ``).  Returns byte -> character."""
+    import unicodedata
+    out, spare = {}, 256
+    for b in range(256):
+        if unicodedata.category(chr(b))[0] in "CZ":
+            out[b] = chr(spare)
+            spare += 1
+        else:
+            out[b] = chr(b)
+    return out
+
+
+def bpe_table(vocab, merges, byte_level: bool = True, lead=b" ", word_bytes=None, max_word_bytes: int = 64,
+              any_split: bool = False, ignore_case: bool = False) -> tuple:
+    """A byte-pair-encoding vocabulary as it ships (``vocab.json`` plus ``merges.txt``, or the ``model`` part of a
+    ``tokenizer.json``) as ONE automaton with an (id, rank, split) per final state, for ``pfac_table_set_bpe``.
+    ``vocab`` maps token -> id; ``merges`` is the ordered list of pairs (two-element sequences, or ``"left right"``).
+    ``byte_level``: the tokens are written in the printable byte alphabet (``bpe_byte_alphabet``) and are mapped back
+    to bytes; else a token is its bytes (str: UTF-8).  ``lead``: the one byte outside words that a word takes from in
+    front of it (None: none); ``word_bytes`` as for ``unigram_table``; ``any_split``: every split 0 (the rank belongs
+    to the string, ``tiktoken``'s form); ``max_word_bytes`` is checked against 1..255 and is otherwise the caller's to
+    pass to ``set_bpe``.  Returns (table, pieces BPE_PIECE_DTYPE[num_final], byte_ids int32[256], skipped):
+
+    - the patterns are the distinct merged strings of at least 2 bytes, folded under ``ignore_case``; merge k gives its
+      string rank k and split ``len(left)``; the id is the vocabulary's;
+    - ``byte_ids`` holds the ids of the single-byte tokens, TOKEN_DROP where there is none;
+    - ``skipped`` lists (merge index, (left, right), reason) or (id, token, reason) of what the rule can never produce:
+      a non-word byte other than a lead at offset 0 (``"non-word byte"``), a lead anywhere else (``"lead inside"``),
+      ``"newline"``, 1 024 bytes or more (``"too long"``), a merge whose result is ``"not in vocab"``, the later of two
+      merges that make the same string (``"ambiguous"``), a token outside the byte alphabet (``"not byte-level"``) and
+      a token of two or more bytes that no merge makes (``"no merge"``)."""
+    if not 1 <= int(max_word_bytes) <= 255:
+        raise ValueError("max_word_bytes must lie in 1..255")
+    if lead is None or (isinstance(lead, int) and lead < 0):
+        lead_b = -1
+    else:
+        lead_b = int(lead) if isinstance(lead, int) else bytes(lead)[0]
+    words = set(UNIGRAM_SPACE if word_bytes is None else bytes(word_bytes))
+    if lead_b in words:
+        raise ValueError("the lead byte is a word byte")
+    back = {c: b for b, c in bpe_byte_alphabet().items()} if byte_level else None
+
+    def raw(tok):
+        if isinstance(tok, (bytes, bytearray)):
+            return bytes(tok)
+        if back is None:
+            return tok.encode()
+        try:
+            return bytes(back[c] for c in tok)
+        except KeyError:
+            return None
+
+    def refuses(s):
+        if b"\n" in s:
+            return "newline"
+        if len(s) >= 1024:
+            return "too long"
+        for j, b in enumerate(s):
+            if b not in words:
+                if b != lead_b:
+                    return "non-word byte"
+                if j:
+                    return "lead inside"
+        return None
+    ids, skipped = {}, []
+    byte_ids = np.full(256, TOKEN_DROP, dtype=np.int32)
+    for tok, i in vocab.items():
+        b = raw(tok)
+        if b is None:
+            skipped.append((int(i), tok, "not byte-level"))
+        elif len(b) == 1:
+            byte_ids[b[0]] = int(i)
+        elif b:
+            ids.setdefault(b, (int(i), tok))
+    lines, made = [], {}
+    for k, m in enumerate(merges):
+        l, r = m.split(" ") if isinstance(m, str) else m
+        lb, rb = raw(l), raw(r)
+        if lb is None or rb is None:
+            skipped.append((k, (l, r), "not byte-level"))
+            continue
+        s = lb + rb
+        why = refuses(bytes(fold_ascii(s)) if ignore_case else s)
+        if why is None and s not in ids:
+            why = "not in vocab"
+        key = bytes(fold_ascii(s)) if ignore_case else s
+        if why is None and key in made:
+            why = "ambiguous"
+        if why is not None:
+            skipped.append((k, (l, r), why))
+            continue
+        made[key] = (ids[s][0], k, 0 if any_split else len(lb))
+        lines.append(key)
+    if not lines:
+        raise ValueError("no merge makes a string of word bytes that the vocabulary holds")
+    for s, (i, tok) in ids.items():
+        if (bytes(fold_ascii(s)) if ignore_case else s) not in made:
+            skipped.append((i, tok, "no merge"))
+    table = PfacTable.from_bytes(b"".join(p + b"\n" for p in lines), 256, ignore_case=ignore_case)
+    line_of = token_table(table, list(range(len(lines))))
+    pieces = np.zeros(int(table.num_final), dtype=BPE_PIECE_DTYPE)
+    pieces["id"] = TOKEN_DROP
+    for s, ln in enumerate(line_of):
+        if ln >= 0:
+            pieces["id"][s], pieces["rank"][s], pieces["split"][s] = made[lines[ln]]
+    return table, pieces, byte_ids, skipped
+
+
 TEMPLATE_PLAIN = 0xFFFFFFFF          # PFAC_TEMPLATE_PLAIN: the state's replacement does not quote the match
 
 
